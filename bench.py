@@ -8,6 +8,9 @@ targets, weights) are resident in HBM before the timed region.  `value` = coordi
 summed over all ranks (each rank fits its own volume: weak scaling, no data-path collective; the
 only collective is the final all_gather of metric records over RCCL).
 
+A plain run sets up, warms up, times `--steps` steps and prints the headline line; `--dump-outputs DIR` writes what the timed
+steps computed (losses, final parameters) as .npy files.  Everything below is measured with `--full` only.
+
 Extra objects on the JSON line: `roofline` (the GEMM kernels, HIP-event timed inside the timed region on the stream they
 run on; `traffic` from the tracked rocprofv3 PMC summary, null when that summary was taken from other kernel sources),
 `fp32_mfma` (the same steps on the exact-fp32 f32-input MFMA kernels: the figure that owes nothing to the fp16 split),
@@ -61,6 +64,16 @@ def source_hash():
 def synthetic_volume(side, seed=0):
     """np.random.default_rng(seed).random((side,)*3) as fp32."""
     return np.random.default_rng(seed).random((side, side, side)).astype(np.float32)
+
+
+def dump_outputs(out_dir, losses, net):
+    """What a caller of the timed path receives, as float32 .npy files: `losses.npy` (the per-step losses `SirenFitter.step`
+    returned for the timed steps) and `param.<name>.npy` for every parameter of the network after the last of them (~3.7 MB)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"losses": losses}
+    arrays.update((f"param.{name}", p) for name, p in net.named_parameters())
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().float().cpu().numpy())
 
 
 def cpu_baseline(n_sweep, steps, warmup, B_np, vol, thread_counts):
@@ -476,6 +489,13 @@ def main():
     ap.add_argument("--no-cfg4", action="store_true", help="skip the 11-patient leg (about a minute)")
     ap.add_argument("--fp32-mfma", action="store_true",
                     help="A/B: run the GEMMs on the f32-input MFMA kernels instead of the split-fp16 ones")
+    ap.add_argument("--full", action="store_true",
+                    help="also every secondary figure: roofline (per-class HIP events inside the timed steps), exact-fp32 leg, "
+                         "recon / full fit / real-data and other-config legs, CPU baseline, 11-patient leg at --gpus N > 1 "
+                         "(the --no-* / --cpu-* / --eleven-* options act within it); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float32): the per-step losses the "
+                         "fit call returned and the network's parameters after its last step (rank 0's fit)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -535,8 +555,9 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
-    ops.prof_reset()
-    ops.prof_enable(True)
+    if args.full:
+        ops.prof_reset()
+        ops.prof_enable(True)
     t0 = time.perf_counter()
     losses = fitter.step(x, target, n_steps=args.steps)
     torch.cuda.synchronize()
@@ -544,7 +565,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    ops.prof_enable(False)
+    if args.full:
+        ops.prof_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, net)
 
     # ---- final metric gather (the only collective on the path) --------------------------------------
     record = {"rank": rank, "n": n_lr, "steps": args.steps, "seconds": dt, "final_loss": float(losses[-1])}
@@ -553,7 +577,7 @@ def main():
     total_units = sum(r["n"] * r["steps"] for r in records)
 
     eleven = None
-    if world > 1 and not args.no_eleven:
+    if world > 1 and args.full and not args.no_eleven:
         fitter.release_workspace()
         try:
             eleven = eleven_patients_leg(args.eleven_steps)   # every rank takes part (gangs, all-reduce, gather)
@@ -561,6 +585,22 @@ def main():
             eleven = {"error": f"{type(e).__name__}: {e}"[:400]}
 
     if rank != 0:
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    out = {"metric": "voxels/sec per INR fit (128^3, x4 upscale): train coordinate-steps/s",
+           "value": total_units / dt_max, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True,
+           "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32" if args.fp32_mfma else "f32 as 3 x f16 MFMA products (hi/lo split operands, f32 accumulate)",
+           "data": "synthetic",
+           "config": {"workload": "synthetic 128^3 volume, LR 64x64x128 (N=524288 coords) -> x4 grid 256x256x128; "
+                                  "Siren(256,512,3,1) + 128 Fourier features, Adam 1e-4, full-batch MSE",
+                      "per_gpu_rows": n_lr, "parallelism": f"{world} independent fits (one volume per GPU)"},
+           "kernel_source_hash": source_hash()}
+    if not args.full:
+        print(json.dumps(out))
         if world > 1:
             dist.destroy_process_group()
         return
@@ -648,16 +688,7 @@ def main():
                                   "profiles/r05_kloop_rowown_probe_shared_a.txt); clock-adjusted fractions: roofline.clock_adjusted"}
     ops.prof_reset()
 
-    out = {"metric": "voxels/sec per INR fit (128^3, x4 upscale): train coordinate-steps/s",
-           "value": total_units / dt_max, "unit": "voxels/s", "n_gpus": world, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": dt_max / args.steps * 1e3, "higher_is_better": True,
-           "scaling": "weak", "vs_baseline": None,
-           "dtype": "f32" if args.fp32_mfma else "f32 as 3 x f16 MFMA products (hi/lo split operands, f32 accumulate)",
-           "data": "synthetic",
-           "config": {"workload": "synthetic 128^3 volume, LR 64x64x128 (N=524288 coords) -> x4 grid 256x256x128; "
-                                  "Siren(256,512,3,1) + 128 Fourier features, Adam 1e-4, full-batch MSE",
-                      "per_gpu_rows": n_lr, "parallelism": f"{world} independent fits (one volume per GPU)"},
-           "roofline": roofline, "kernel_source_hash": src_hash}
+    out["roofline"] = roofline
     if eleven is not None:
         out["eleven_patients"] = eleven
 

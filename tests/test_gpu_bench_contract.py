@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_schema():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
                           "--no-extras", "--cpu-sample", "2048", "--cpu-steps", "1", "--cpu-warmup", "0"], capture_output=True,
                          text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -49,7 +49,7 @@ def test_bench_two_ranks_rehearsal_gloo():
     env = dict(os.environ, INR_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-extras", "--no-cpu-baseline", "--eleven-steps", "6"],
+                          "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--no-cpu-baseline", "--eleven-steps", "6"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -80,3 +80,41 @@ def test_bench_gpus_n_starts_its_own_ranks():
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1
     assert d["value"] == pytest.approx(2 * 524288 * 2 / (d["ms_per_step"] * 2e-3), rel=1e-6)
+
+
+def test_plain_run_times_the_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run (no --full): the headline line only, exactly `--steps` timed steps, and --dump-outputs writes what those steps
+    computed -- their losses and the parameters after the last one, float32 -- bit for bit the same in a second run with the
+    same arguments (seeded inputs; the fit sums in a fixed order, no float atomics)."""
+    import numpy as np
+    import torch
+
+    import mri_super_resolution_amd as inr
+    torch.manual_seed(0)
+    init = dict(inr.Siren(256, 512, 3, 1).named_parameters())        # the network bench.py starts from (CPU generator, seed 0)
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+            assert key in line, key
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "voxels/s" and line["higher_is_better"] is True
+        assert line["value"] == pytest.approx(524288 * 3 / (line["ms_per_step"] * 3e-3), rel=1e-6)
+        for moved in ("roofline", "fp32_mfma", "cpu_baseline", "recon", "full_fit", "quality", "rams", "eleven_patients"):
+            assert moved not in line, moved
+        files = {p.name[:-4]: np.load(p) for p in d.glob("*.npy")}
+        assert set(files) == {"losses"} | {f"param.{n}" for n in init}
+        assert sum(a.nbytes for a in files.values()) <= 64 << 20
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in files.values())
+        assert files["losses"].shape == (3,) and (files["losses"] > 0).all()
+        for n, p in init.items():
+            assert files[f"param.{n}"].shape == tuple(p.shape), n
+        assert not np.array_equal(files["param.net.0.linear.weight"], init["net.0.linear.weight"].detach().numpy())   # post-step
+        dumps.append(files)
+    for name, a in dumps[0].items():
+        assert np.array_equal(a.view(np.uint32), dumps[1][name].view(np.uint32)), name

@@ -4,7 +4,7 @@
 ROOT=$(pwd)
 for a in "" 1 2 4 8 3; do
   if [ -z "$a" ]; then unset INR_LIB; tag=full; else export INR_LIB=$ROOT/mri-super-resolution_amd/libinrhip_abl$a.so; tag=abl$a; fi
-  python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  python bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):

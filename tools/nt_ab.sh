@@ -6,7 +6,7 @@ for round in 1 2; do
 for v in "" nth; do
   if [ -z "$v" ]; then unset INR_LIB; tag="product"; else export INR_LIB=$ROOT/mri-super-resolution_amd/libinrhip_$v.so; tag=$v; fi
   [ -n "$v" ] && [ ! -f "$INR_LIB" ] && continue
-  python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 for l in sys.stdin:
     if l.startswith('{'):
