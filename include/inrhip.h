@@ -18,17 +18,19 @@
  *    `stream`).  Consequently (a) whatever the caller enqueues on `stream` after the call is ordered behind all of its work,
  *    (b) calls on DIFFERENT streams are not ordered against each other by the library, and (c) the calls contain no
  *    allocation and no host synchronisation, so a sequence of them can be captured into a HIP graph.  TWO documented
- *    exceptions to "no host sync": when inr_siren_fit / inr_siren_fit_cycle take the persistent cooperative small-network
- *    kernel (hidden 32 / 64, <= 32 input features, one output, few thousand rows) they wait for `stream` once at the end of
- *    the call to read the kernel's completion word, and return INR_E_TIMEOUT if a launch was abandoned (cooperative
- *    launches cannot be captured into a graph in any case); and inr_prof_read() waits for the events it reports on.
+ *    exceptions to "no host sync": when inr_siren_fit / inr_siren_fit_cycle / inr_siren_fit_cycle_batch take the persistent
+ *    cooperative small-network kernel (hidden 32 / 64, <= 32 input features, one output, few thousand rows) they wait for
+ *    `stream` once at the end of the call to read the kernel's completion word(s), and return INR_E_TIMEOUT if a launch
+ *    was abandoned (cooperative launches cannot be captured into a graph in any case); and inr_prof_read() waits for the
+ *    events it reports on.
  *  - threading / concurrency: entry points may be called concurrently from several host threads on different streams with
  *    DISJOINT output and workspace buffers (read-only inputs may be shared); this is what
  *    drivers.run_volumes(concurrent=k) relies on -- k fits of one process, each on a host thread and a stream of its own,
  *    each with its own parameter / moment / workspace buffers.  One call uses one workspace; the same workspace must not be
  *    in use by two calls that may overlap on the device.  The cooperative small-network kernel needs its whole grid
  *    co-resident: two such launches on different streams at the same time can each hold part of the chip and stall until the
- *    grid barrier's poll limit reports INR_E_TIMEOUT -- run those fits one after the other (run_volumes does).
+ *    grid barrier's poll limit reports INR_E_TIMEOUT -- run those fits one after the other (run_volumes does), or together
+ *    in ONE inr_siren_fit_cycle_batch call (one cooperative grid that carries them all).
  *    Process-global state, all of it safe to touch from several threads, none of it carrying tensor data:
  *      (i)   the thread-local message behind inr_last_error();
  *      (ii)  the event profiler behind inr_prof_* (a mutex; off unless enabled);
@@ -236,6 +238,25 @@ int inr_siren_fit_cycle(const inr_siren_desc_t* desc, float* params, float* grad
                         const float* x, const float* targets, const float* weights, int n_acq, int first_acq,
                         int64_t n, int64_t first_step, int n_steps, double lr, double beta1, double beta2, double eps,
                         float* losses, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Several independent fits of ONE shape at once (master.py: one small network per gradient direction, per case, per seed).
+ * Fit i has its own params[i], grads[i], m[i], v[i], targets[i] / weights[i] ([n_acq[i]][n*out_features], weights and any of
+ * its entries nullable), acquisition cycle (n_acq[i], first_acq[i]), losses[i] ([n_steps], array and entries nullable) and
+ * workspaces[i] (each of workspace_bytes >= inr_siren_fit_workspace_bytes(desc, n)); x, n, the step schedule and the Adam
+ * constants are shared.  Pointer arrays are HOST arrays of device pointers.
+ * Contract: the call is equivalent, bit for bit, to calling inr_siren_fit_cycle for i = 0 .. n_fits-1 in order on the same
+ * stream, for every network shape and every inr_debug_set setting.  Where the persistent cooperative kernel serves the shape
+ * and at least two fits' grids are co-resident, the fits share launches: ONE cooperative launch per 64 steps carries up to
+ * 16 of them (fit k owns its own blocks, its own grid barriers and its own reduction), further groups follow on `stream`.
+ * Like that path it waits for `stream` once at the end to read every fit's completion word (INR_E_TIMEOUT names the fits
+ * whose launch was abandoned) and cannot be captured into a HIP graph.  Validation (INR_E_INVALID, before any device work):
+ * n_fits >= 1, no null array or required entry, no params buffer or workspace used twice, 16-byte aligned x / params /
+ * grads / workspaces, 0 <= first_acq[i] < n_acq[i]. */
+int inr_siren_fit_cycle_batch(const inr_siren_desc_t* desc, int n_fits, float* const* params, float* const* grads,
+                              float* const* m, float* const* v, const float* x, const float* const* targets,
+                              const float* const* weights, const int* n_acq, const int* first_acq, int64_t n,
+                              int64_t first_step, int n_steps, double lr, double beta1, double beta2, double eps,
+                              float* const* losses, void* const* workspaces, size_t workspace_bytes, void* stream);
 
 /* (e) one fit split over several GPUs: forward + loss + backward of THIS rank's row shard, no optimizer.
  * The mean of the loss runs over count_total elements (0 = n*out_features, i.e. an unsplit fit), so gradients and
@@ -460,7 +481,8 @@ int inr_debug_set_ptr(int key, void* ptr);   /* key 0: per-wave time-stamp buffe
 #define INR_LF_HP_NARROW   10  /* gemm_hp_nt_kernel: HL32 operands, 64 x 128 tiles (launches too small for the wide tiles) */
 #define INR_LF_HP_FUSED_FWD 11 /* siren_fwd_fused_kernel: every sine layer + the head of a forward in ONE launch, panel in LDS */
 #define INR_LF_HP_ROW      12  /* gemm_hp_row_kernel: HL32 operands, persistent, a block owns 128 rows x all 512 columns, epilogue in line */
-#define INR_LF_COUNT       13
+#define INR_LF_SMALL_BATCH 13  /* siren_small_batch_kernel: several small-network fits in ONE persistent cooperative launch */
+#define INR_LF_COUNT       14
 int inr_launch_count(int family, int64_t* count);
 int inr_launch_counts_reset(void);
 

@@ -13,10 +13,11 @@ from ._build import LIB_PATH
 c_f32p = C.c_void_p      # raw device pointers travel as integers (tensor.data_ptr())
 c_i64p = C.POINTER(C.c_int64)
 c_stream = C.c_void_p
+c_ptr_array = C.POINTER(C.c_void_p)   # host array of device pointers (nullable where the header says so)
 
 
 INR_E_INVALID, INR_E_WORKSPACE, INR_E_ALIGN, INR_E_TIMEOUT = -1, -2, -3, -4     # include/inrhip.h
-INR_LF_COUNT = 13
+INR_LF_COUNT = 14
 
 
 class InrHipError(RuntimeError):
@@ -90,6 +91,10 @@ SIGNATURES = {
     "inr_siren_fit_cycle": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int,
                                       C.c_int, C.c_int64, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double,
                                       C.c_double, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_siren_fit_cycle_batch": (C.c_int, [C.POINTER(SirenDesc), C.c_int, c_ptr_array, c_ptr_array, c_ptr_array, c_ptr_array,
+                                            c_f32p, c_ptr_array, c_ptr_array, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int64,
+                                            C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, c_ptr_array,
+                                            c_ptr_array, C.c_size_t, c_stream]),
     "inr_metric_workspace_bytes": (C.c_size_t, [C.c_int]),
     "inr_psnr": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int64, C.c_double, C.c_void_p, C.c_size_t, c_stream]),
     "inr_ssim2d": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,

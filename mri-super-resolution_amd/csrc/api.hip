@@ -203,6 +203,12 @@ int small_fit_multi(const inr_siren_desc_t* d, const long long* w_off, const lon
                     float* grads, float* m, float* v, const float* x, const float* targets, const float* weights, int n_acq,
                     int first_acq, int64_t n, int64_t first_step, int n_steps, double lr, double b1, double b2, double eps,
                     float* losses, float* ws, hipStream_t st);
+int small_batch_per_launch(const inr_siren_desc_t* d, int64_t n);
+int small_fit_batch(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, int n_fits,
+                    float* const* params, float* const* grads, float* const* m, float* const* v, const float* x,
+                    const float* const* targets, const float* const* weights, const int* n_acq, const int* first_acq, int64_t n,
+                    int64_t first_step, int n_steps, double lr, double b1, double b2, double eps, float* const* losses,
+                    void* const* ws, hipStream_t st);
 int small_fit_step(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, float* params,
                    float* grads, float* m, float* v, const float* x, const float* target, const float* weight, int64_t n,
                    int64_t step, double lr, double b1, double b2, double eps, float* loss_out, float* ws, hipStream_t st);
@@ -1265,6 +1271,64 @@ int inr_siren_fit_cycle(const inr_siren_desc_t* desc, float* params, float* grad
                                           losses ? (losses + it) : loss_sink, st, &h3))
             return rc;
         if (int rc = launch_adam(params, grads, m, v, L.total, first_step + it, lr, beta1, beta2, eps, st)) return rc;
+    }
+    return 0;
+}
+
+// n_fits independent fits of one shape, equivalent bit for bit to inr_siren_fit_cycle(fit 0), (fit 1), ... on `stream`.  Fits
+// the persistent kernel serves, and of which at least two fit one cooperative grid, share launches (small_fit_batch); every
+// other case is that sequence of solo calls.
+int inr_siren_fit_cycle_batch(const inr_siren_desc_t* desc, int n_fits, float* const* params, float* const* grads,
+                              float* const* m, float* const* v, const float* x, const float* const* targets,
+                              const float* const* weights, const int* n_acq, const int* first_acq, int64_t n, int64_t first_step,
+                              int n_steps, double lr, double beta1, double beta2, double eps, float* const* losses,
+                              void* const* workspaces, size_t workspace_bytes, void* stream) {
+    if (int rc = check_desc(desc)) return rc;
+    INR_REQUIRE(n_fits >= 1, INR_E_INVALID, "inr_siren_fit_cycle_batch: n_fits must be >= 1 (got %d)", n_fits);
+    INR_REQUIRE(params && grads && m && v && targets && n_acq && first_acq && workspaces, INR_E_INVALID,
+                "inr_siren_fit_cycle_batch: null array (params, grads, m, v, targets, n_acq, first_acq and workspaces are "
+                "required; weights and losses may be null)");
+    INR_REQUIRE(x != nullptr, INR_E_INVALID, "inr_siren_fit_cycle_batch: x is null");
+    INR_REQUIRE(n >= 1 && n <= MAX_ROWS, INR_E_INVALID, "inr_siren_fit_cycle_batch: bad row count %lld", (long long)n);
+    INR_REQUIRE(first_step >= 1 && n_steps >= 0, INR_E_INVALID, "inr_siren_fit_cycle_batch: first_step >= 1, n_steps >= 0");
+    INR_REQUIRE(aligned16(x), INR_E_INVALID, "inr_siren_fit_cycle_batch: x is not 16-byte aligned");
+    for (int i = 0; i < n_fits; ++i) {
+        INR_REQUIRE(params[i] && grads[i] && m[i] && v[i] && targets[i] && workspaces[i], INR_E_INVALID,
+                    "inr_siren_fit_cycle_batch: fit %d has a null params / grads / m / v / targets / workspace pointer", i);
+        INR_REQUIRE(aligned16(params[i]) && aligned16(grads[i]) && aligned16(workspaces[i]), INR_E_INVALID,
+                    "inr_siren_fit_cycle_batch: fit %d: params / grads / workspace are not 16-byte aligned", i);
+        INR_REQUIRE(n_acq[i] >= 1 && first_acq[i] >= 0 && first_acq[i] < n_acq[i], INR_E_INVALID,
+                    "inr_siren_fit_cycle_batch: fit %d: need n_acq >= 1 and 0 <= first_acq < n_acq (got n_acq %d, first_acq %d)",
+                    i, n_acq[i], first_acq[i]);
+        for (int j = 0; j < i; ++j) {
+            INR_REQUIRE(params[j] != params[i], INR_E_INVALID, "inr_siren_fit_cycle_batch: fits %d and %d share one params buffer",
+                        j, i);
+            INR_REQUIRE(workspaces[j] != workspaces[i], INR_E_INVALID,
+                        "inr_siren_fit_cycle_batch: fits %d and %d share one workspace", j, i);
+        }
+    }
+    const Layout L = make_layout(desc);
+    const FitCarve c = fit_carve(desc, L, n);
+    INR_REQUIRE(workspace_bytes >= c.total, INR_E_WORKSPACE, "inr_siren_fit_cycle_batch: workspace too small (%zu < %zu)",
+                workspace_bytes, c.total);
+    if (small_path_ok(desc, n) && !g_force_generic && g_small_multi && small_batch_per_launch(desc, n) >= 2) {
+        {   // as in inr_siren_fit_cycle: these workspaces' operand images and statistics slots are no longer trustworthy
+            std::lock_guard<std::mutex> lk(g_reuse_mu);
+            for (int i = 0; i < n_fits; ++i)
+                if (ReuseStamp* s = reuse_find(workspaces[i], false)) s->image = s->stats = s->fwd_train = false;
+        }
+        long long w_off[32], b_off[32];
+        for (int l = 0; l <= L.n_sine; ++l) { w_off[l] = L.w_off[l]; b_off[l] = L.b_off[l]; }
+        const int rc = small_fit_batch(desc, w_off, b_off, L.total, n_fits, params, grads, m, v, x, targets, weights, n_acq,
+                                       first_acq, n, first_step, n_steps, lr, beta1, beta2, eps, losses, workspaces,
+                                       (hipStream_t)stream);
+        if (rc != INR_E_FALLBACK) return rc;   // (the device refused the first grid: the solo calls below)
+    }
+    for (int i = 0; i < n_fits; ++i) {
+        if (int rc = inr_siren_fit_cycle(desc, params[i], grads[i], m[i], v[i], x, targets[i], weights ? weights[i] : nullptr,
+                                         n_acq[i], first_acq[i], n, first_step, n_steps, lr, beta1, beta2, eps,
+                                         losses ? losses[i] : nullptr, workspaces[i], workspace_bytes, stream))
+            return rc;
     }
     return 0;
 }

@@ -12,6 +12,7 @@
 // Eligibility (host): hidden in {32, 64}, in_features <= 32, out_features == 1.
 #include "common.h"
 #include <atomic>
+#include <vector>
 
 namespace inr {
 
@@ -408,21 +409,28 @@ constexpr int SM_THREADS = 512;
 constexpr int SM_MAX_STEPS = 64;
 constexpr unsigned SM_SPIN_LIMIT = 1u << 22;
 
-struct SmallMulti {
+// What differs between the problems of one batched launch (siren_small_batch_kernel): each fit's own buffers, its
+// acquisition cycle and the workspace carve (stash, slabs, loss partials, barrier counter and error word).
+struct SmallProb {
     float* params; float* grads; float* m; float* v;
     float* slabs;                 // [nblocks][P]
     float* loss_partial;          // [nblocks]
     float* acts;                  // [S][nblocks*64][H]: acts[l] = input of sine layer l (l = 1..S-1)
     float* dacts;                 // [S][nblocks][8 waves][CTW][64 lanes] float4, accumulator-native
-    const float* x;               // [N][F]
     const float* targets;         // [n_acq][N]
     const float* weights;         // [n_acq][N] or null
     float* losses;                // [n_steps] or null
     unsigned* sync;               // [0] arrivals (zeroed by the host before the launch), [1] error word
+    int n_acq, first_acq;
+};
+
+struct SmallMulti {
+    SmallProb q;                  // the solo kernel's problem (unused by the batched kernel, which has a table of them)
+    const float* x;               // [N][F]
     unsigned spin_limit;          // polls a block waits at a grid barrier before it raises the error word
     long long w_off[SMALL_MAX_LAYERS + 1], b_off[SMALL_MAX_LAYERS + 1];
     long long P;
-    int N, F, S, n_acq, first_acq, n_steps, nblocks, tpp;
+    int N, F, S, n_steps, nblocks, tpp;
     float first_omega, hidden_omega, inv_count;
     float one_minus_b1, b2, one_minus_b2, eps;
     float step_size[SM_MAX_STEPS], bc2_sqrt[SM_MAX_STEPS];
@@ -482,8 +490,10 @@ __device__ __forceinline__ bool small_grid_barrier(unsigned* sync, unsigned targ
     return *flag != 0;
 }
 
+// The kernel body, for one problem: `q` holds its buffers, `blk` is the block index within its own grid of p.nblocks blocks.
+// Both kernels below inline it; the per-problem values stay kernel-argument loads (no per-block copy of a struct).
 template <int H, int ROWS>
-__global__ void __launch_bounds__(SM_THREADS) siren_small_multi_kernel(const SmallMulti p) {
+__device__ __forceinline__ void small_multi_body(const SmallMulti& p, const SmallProb& q, const int blk) {
     constexpr int RT = ROWS / 16;       // 16-row tiles of the block
     constexpr int WPR = 8 / RT;         // waves that share a row tile
     static_assert((H / 16) % WPR == 0, "column tiles must divide over the waves of a row tile");
@@ -510,19 +520,19 @@ __global__ void __launch_bounds__(SM_THREADS) siren_small_multi_kernel(const Sma
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l16 = lane & 15, g = lane >> 4;
     const int rt = wave / WPR, cb = (wave % WPR) * CTW;
-    const int blk = blockIdx.x, nblk = p.nblocks;
+    const int nblk = p.nblocks;
     const int r0 = blk * ROWS;
     const int S = p.S, F = p.F;
     const int KB0 = (F + 15) / 16;                       // k blocks of layer 0 (features zero-padded to 16)
-    float* slab = p.slabs + (long long)blk * p.P;
+    float* slab = q.slabs + (long long)blk * p.P;
     const long long tile_floats = (long long)nblk * ROWS * H;
-    float* tstash = p.acts + (long long)blk * ROWS * H;            // + l * tile_floats: a_l^T [k][64 rows] of this block
-    f32x4* dnat = reinterpret_cast<f32x4*>(p.dacts) + ((long long)blk * 8 + wave) * CTW * 64 + lane;
+    float* tstash = q.acts + (long long)blk * ROWS * H;            // + l * tile_floats: a_l^T [k][64 rows] of this block
+    f32x4* dnat = reinterpret_cast<f32x4*>(q.dacts) + ((long long)blk * 8 + wave) * CTW * 64 + lane;
     const long long dnat_layer = (long long)nblk * 8 * CTW * 64;      // float4 per layer
     unsigned barrier_no = 0;
     // the parameter buffer as seen after other CUs updated it: agent-scope (sc1) buffer loads, 4 or 16 bytes wide
     const __amdgpu_buffer_rsrc_t prsrc =
-        __builtin_amdgcn_make_buffer_rsrc(p.params, 0, (int)(p.P * (long long)sizeof(float)), 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(q.params, 0, (int)(p.P * (long long)sizeof(float)), 0x00020000);
     auto param1 = [&](long long idx) -> float {
         return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(prsrc, (int)(idx * 4), 0, 16));
     };
@@ -578,19 +588,19 @@ __global__ void __launch_bounds__(SM_THREADS) siren_small_multi_kernel(const Sma
     const bool row_ok = r0 + tid / TPR < p.N;
     float xv[XQ], tgt_pre = 0.f, wgt_pre = 1.f;
     auto prefetch_inputs = [&](int step) {
-        const int acq = (p.first_acq + step) % p.n_acq;
+        const int acq = (q.first_acq + step) % q.n_acq;
 #pragma unroll
         for (int i = 0; i < XQ; ++i) {
             const int e = tid + SM_THREADS * i, row = e >> 5, k = e & 31;
             xv[i] = (k < F && r0 + row < p.N) ? p.x[(long long)(r0 + row) * F + k] : 0.f;
         }
-        tgt_pre = row_ok ? p.targets[(long long)acq * p.N + r0 + tid / TPR] : 0.f;
-        wgt_pre = (p.weights && row_ok) ? p.weights[(long long)acq * p.N + r0 + tid / TPR] : 1.f;
+        tgt_pre = row_ok ? q.targets[(long long)acq * p.N + r0 + tid / TPR] : 0.f;
+        wgt_pre = (q.weights && row_ok) ? q.weights[(long long)acq * p.N + r0 + tid / TPR] : 1.f;
     };
     prefetch_inputs(0);
 
     for (int step = 0; step < p.n_steps; ++step) {
-        const bool weighted = p.weights != nullptr;
+        const bool weighted = q.weights != nullptr;
         SM_STAMP(0);
 
         // ---------------------------------------------- forward ----------------------------------------------------
@@ -728,7 +738,7 @@ __global__ void __launch_bounds__(SM_THREADS) siren_small_multi_kernel(const Sma
                 ls += wred[0][w];
                 gs += wred[1][w];
             }
-            store_shared(p.loss_partial + blk, ls);
+            store_shared(q.loss_partial + blk, ls);
             store_shared(slab + p.b_off[S], gs);                         // head bias gradient
         } else if (tid < 4) {
             store_shared(slab + p.b_off[S] + tid, 0.f);                  // 16-byte padding of the 1-float head bias
@@ -875,11 +885,11 @@ __global__ void __launch_bounds__(SM_THREADS) siren_small_multi_kernel(const Sma
         flush_grads();                                                   // layer 0's
         // ------------------------------- gradient reduction + Adam over the whole grid -----------------------------
         SM_STAMP(4);
-        if (!small_grid_barrier<false>(p.sync, ++barrier_no * (unsigned)nblk, &bar_flag, p.spin_limit)) return;
+        if (!small_grid_barrier<false>(q.sync, ++barrier_no * (unsigned)nblk, &bar_flag, p.spin_limit)) return;
         SM_STAMP(5);
         {
             const float step_size = p.step_size[step], bc2_sqrt = p.bc2_sqrt[step];
-            // `tpp` adjacent lanes share a parameter: lane q sums the slabs b = q (mod tpp) -- every load of a batch in
+            // `tpp` adjacent lanes share a parameter: lane ql sums the slabs b = ql (mod tpp) -- every load of a batch in
             // flight together (they come from other CUs: a memory round trip each) -- then the lanes are folded in a fixed
             // order; the order of the whole sum depends on the grid only
             const int tpp = p.tpp;
@@ -887,22 +897,22 @@ __global__ void __launch_bounds__(SM_THREADS) siren_small_multi_kernel(const Sma
             for (long long base = 0; base < p.P; base += gthreads / tpp) {
                 const long long gt = (long long)blk * SM_THREADS + tid;
                 const long long i = base + gt / tpp;
-                const int q = (int)(gt % tpp);
+                const int ql = (int)(gt % tpp);
                 const bool live = i < p.P;
                 float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
                 float m0 = 0.f, v0 = 0.f, w0 = 0.f;
                 if (live) {
-                    if (q == 0) {                      // the optimizer state rides in the same round trip as the slabs
-                        m0 = p.m[i];
-                        v0 = p.v[i];
+                    if (ql == 0) {                      // the optimizer state rides in the same round trip as the slabs
+                        m0 = q.m[i];
+                        v0 = q.v[i];
                         w0 = param1(i);
                     }
                     constexpr int BATCH = 64;
-                    for (int b0 = q; b0 < nblk; b0 += BATCH * tpp) {
+                    for (int b0 = ql; b0 < nblk; b0 += BATCH * tpp) {
                         float t[BATCH];
 #pragma unroll
                         for (int u = 0; u < BATCH; ++u)
-                            t[u] = (b0 + u * tpp < nblk) ? load_shared(p.slabs + (long long)(b0 + u * tpp) * p.P + i) : 0.f;
+                            t[u] = (b0 + u * tpp < nblk) ? load_shared(q.slabs + (long long)(b0 + u * tpp) * p.P + i) : 0.f;
 #pragma unroll
                         for (int u = 0; u < BATCH; u += 4) {
                             a0 += t[u];
@@ -914,29 +924,59 @@ __global__ void __launch_bounds__(SM_THREADS) siren_small_multi_kernel(const Sma
                 }
                 float gi = (a0 + a1) + (a2 + a3);
                 for (int off = 1; off < tpp; off <<= 1) gi += __shfl_xor(gi, off, 64);
-                if (live && q == 0) {
-                    p.grads[i] = gi;
+                if (live && ql == 0) {
+                    q.grads[i] = gi;
                     const float mi = fmaf(gi - m0, p.one_minus_b1, m0);
                     const float vi = fmaf(p.one_minus_b2 * gi, gi, v0 * p.b2);
                     const float denom = __fsqrt_rn(vi) / bc2_sqrt + p.eps;
-                    p.m[i] = mi;
-                    p.v[i] = vi;
-                    store_shared(p.params + i, w0 - step_size * (mi / denom));
+                    q.m[i] = mi;
+                    q.v[i] = vi;
+                    store_shared(q.params + i, w0 - step_size * (mi / denom));
                 }
             }
-            if (blk == 0 && wave == 0 && p.losses) {
+            if (blk == 0 && wave == 0 && q.losses) {
                 float ls = 0.f;
-                for (int b = lane; b < nblk; b += 64) ls += load_shared(p.loss_partial + b);
+                for (int b = lane; b < nblk; b += 64) ls += load_shared(q.loss_partial + b);
 #pragma unroll
                 for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off, 64);
-                if (lane == 0) p.losses[step] = ls * p.inv_count;
+                if (lane == 0) q.losses[step] = ls * p.inv_count;
             }
         }
         if (step + 1 < p.n_steps) prefetch_inputs(step + 1);
         SM_STAMP(6);
-        if (!small_grid_barrier<false>(p.sync, ++barrier_no * (unsigned)nblk, &bar_flag, p.spin_limit)) return;
+        if (!small_grid_barrier<false>(q.sync, ++barrier_no * (unsigned)nblk, &bar_flag, p.spin_limit)) return;
         SM_STAMP(7);
     }
+}
+
+template <int H, int ROWS>
+__global__ void __launch_bounds__(SM_THREADS) siren_small_multi_kernel(const SmallMulti p) {
+    small_multi_body<H, ROWS>(p, p.q, blockIdx.x);
+}
+
+// K independent fits of one shape in one cooperative grid: problem k owns blocks [k nb, (k+1) nb), nb = the solo block count.
+// Each problem's grid barriers count its own nb blocks on its own counter, and its reduction + Adam run over its own slabs with
+// the solo index arithmetic: every fit is bit-identical to its solo launch.
+constexpr int SB_MAX_PROBS = 16;
+struct SmallBatch {
+    SmallMulti p;                 // shared: shape, coordinates, step schedule, rows per block (p.q unused)
+    SmallProb probs[SB_MAX_PROBS];
+};
+
+template <int H, int ROWS>
+__global__ void __launch_bounds__(SM_THREADS) siren_small_batch_kernel(const SmallBatch b) {
+    const int prob = blockIdx.x / b.p.nblocks;        // uniform over the block: scalar kernel-argument loads below
+    small_multi_body<H, ROWS>(b.p, b.probs[prob], blockIdx.x - prob * b.p.nblocks);
+}
+
+// Zeroes the arrival counters (and, on a call's first launch, the error words) of the problems of a batched launch: one
+// launch instead of one memset per problem.
+struct SyncTable {
+    unsigned* sync[SB_MAX_PROBS];
+};
+__global__ void small_batch_sync_reset(const SyncTable t, int count, int words) {
+    const int i = threadIdx.x;
+    if (i < count * words) t.sync[i / words][i % words] = 0u;
 }
 
 tune_int g_small_spin_limit{0};   // inr_debug_set(17, n): poll limit of the grid barrier (0 = SM_SPIN_LIMIT); tests force the abandon path with 1
@@ -1003,25 +1043,31 @@ size_t small_multi_workspace_floats(const inr_siren_desc_t* d, int64_t n, long l
     return 2 * (size_t)S * tile + nb * (size_t)P + nb + 64 + 64;                // acts, dacts, slabs, loss partials, sync words
 }
 
-// n_steps optimizer steps; step `it` fits acquisition (first_acq + it) % n_acq (targets / weights: [n_acq][n] contiguous).
-int small_fit_multi(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, float* params,
-                    float* grads, float* m, float* v, const float* x, const float* targets, const float* weights, int n_acq,
-                    int first_acq, int64_t n, int64_t first_step, int n_steps, double lr, double b1, double b2, double eps,
-                    float* losses, float* ws, hipStream_t st) {
+// One fit's slice of the workspace (inr_siren_fit_workspace_bytes): stash, slabs, loss partials, sync words.
+static SmallProb small_prob(const inr_siren_desc_t* d, int64_t n, long long P, float* params, float* grads, float* m, float* v,
+                            const float* targets, const float* weights, int n_acq, float* ws) {
     const int S = d->hidden_layers + 1, H = d->hidden_features;
-    const int rows = multi_rows(d, n);
-    const int nb = multi_blocks(d, n);
     const size_t tile = (size_t)((n + 63) / 64) * 64 * H;
-    SmallMulti p{};
-    p.params = params; p.grads = grads; p.m = m; p.v = v;
-    p.acts = ws;
-    p.dacts = ws + (size_t)S * tile;
-    p.slabs = p.dacts + (size_t)S * tile;
-    p.loss_partial = p.slabs + (size_t)((n + 31) / 32) * P;
-    p.sync = reinterpret_cast<unsigned*>(p.loss_partial + (((size_t)((n + 31) / 32) + 63) / 64) * 64);
-    p.x = x; p.targets = targets; p.weights = weights;
+    SmallProb q{};
+    q.params = params; q.grads = grads; q.m = m; q.v = v;
+    q.acts = ws;
+    q.dacts = ws + (size_t)S * tile;
+    q.slabs = q.dacts + (size_t)S * tile;
+    q.loss_partial = q.slabs + (size_t)((n + 31) / 32) * P;
+    q.sync = reinterpret_cast<unsigned*>(q.loss_partial + (((size_t)((n + 31) / 32) + 63) / 64) * 64);
+    q.targets = targets; q.weights = weights;
+    q.n_acq = n_acq;
+    return q;
+}
+
+// What the problems of a launch share: shape, coordinates, block split, reduction lanes, Adam constants.
+static void small_shared(SmallMulti& p, const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P,
+                         const float* x, int64_t n, double b1, double b2, double eps) {
+    const int S = d->hidden_layers + 1;
+    const int nb = multi_blocks(d, n);
+    p.x = x;
     for (int l = 0; l <= S; ++l) { p.w_off[l] = w_off[l]; p.b_off[l] = b_off[l]; }
-    p.P = P; p.N = (int)n; p.F = d->in_features; p.S = S; p.n_acq = n_acq; p.nblocks = nb;
+    p.P = P; p.N = (int)n; p.F = d->in_features; p.S = S; p.nblocks = nb;
     p.tpp = 1;
     while (p.tpp < 8 && (long long)nb * SM_THREADS / (2 * p.tpp) >= P) p.tpp *= 2;   // lanes per parameter in the reduction
     p.first_omega = d->first_omega; p.hidden_omega = d->hidden_omega;
@@ -1030,18 +1076,36 @@ int small_fit_multi(const inr_siren_desc_t* d, const long long* w_off, const lon
     p.stamps = g_stamps;
     const int lim = g_small_spin_limit;
     p.spin_limit = lim > 0 ? (unsigned)lim : SM_SPIN_LIMIT;
+}
+
+// The Adam step sizes of steps [first_step + done, first_step + done + k) of one launch.
+static void small_schedule(SmallMulti& p, int64_t first_step, int done, int k, double lr, double b1, double b2) {
+    p.n_steps = k;
+    for (int i = 0; i < k; ++i) {
+        const double t = (double)(first_step + done + i);
+        p.step_size[i] = (float)(lr / (1.0 - pow(b1, t)));
+        p.bc2_sqrt[i] = (float)sqrt(1.0 - pow(b2, t));
+    }
+}
+
+// n_steps optimizer steps; step `it` fits acquisition (first_acq + it) % n_acq (targets / weights: [n_acq][n] contiguous).
+int small_fit_multi(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, float* params,
+                    float* grads, float* m, float* v, const float* x, const float* targets, const float* weights, int n_acq,
+                    int first_acq, int64_t n, int64_t first_step, int n_steps, double lr, double b1, double b2, double eps,
+                    float* losses, float* ws, hipStream_t st) {
+    const int H = d->hidden_features;
+    const int rows = multi_rows(d, n);
+    const int nb = multi_blocks(d, n);
+    SmallMulti p{};
+    p.q = small_prob(d, n, P, params, grads, m, v, targets, weights, n_acq, ws);
+    small_shared(p, d, w_off, b_off, P, x, n, b1, b2, eps);
     for (int done = 0; done < n_steps; done += SM_MAX_STEPS) {
         const int k = n_steps - done < SM_MAX_STEPS ? n_steps - done : SM_MAX_STEPS;
-        p.n_steps = k;
-        p.first_acq = (int)(((long long)first_acq + done) % n_acq);
-        p.losses = losses ? losses + done : nullptr;
-        for (int i = 0; i < k; ++i) {
-            const double t = (double)(first_step + done + i);
-            p.step_size[i] = (float)(lr / (1.0 - pow(b1, t)));
-            p.bc2_sqrt[i] = (float)sqrt(1.0 - pow(b2, t));
-        }
+        p.q.first_acq = (int)(((long long)first_acq + done) % n_acq);
+        p.q.losses = losses ? losses + done : nullptr;
+        small_schedule(p, first_step, done, k, lr, b1, b2);
         ProfScope ps(KC_OTHER, st);
-        INR_HIP(hipMemsetAsync(p.sync, 0, (done == 0 ? 2 : 1) * sizeof(unsigned), st));   // the error word is sticky within a call
+        INR_HIP(hipMemsetAsync(p.q.sync, 0, (done == 0 ? 2 : 1) * sizeof(unsigned), st));   // the error word is sticky within a call
         void* args[] = {(void*)&p};
         const void* fn = (H == 32) ? (const void*)siren_small_multi_kernel<32, 64>
                          : (rows == 32) ? (const void*)siren_small_multi_kernel<64, 32>
@@ -1058,11 +1122,89 @@ int small_fit_multi(const inr_siren_desc_t* d, const long long* w_off, const lon
     // then partly updated.  That must not pass for success, so this path reads the error word back -- the one place where an
     // entry point waits for the stream (cooperative launches cannot be captured into a graph anyway; include/inrhip.h).
     unsigned err = 0;
-    INR_HIP(hipMemcpyAsync(&err, p.sync + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    INR_HIP(hipMemcpyAsync(&err, p.q.sync + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
     INR_HIP(hipStreamSynchronize(st));
     INR_REQUIRE(err == 0, INR_E_TIMEOUT,
                 "small-network persistent kernel: a grid barrier exceeded its poll limit and the launch was abandoned; "
                 "params / m / v / losses of this call are partly updated and must be discarded");
+    return 0;
+}
+
+// Fits of this shape that one batched launch carries: floor(co-resident blocks / solo blocks), at most SB_MAX_PROBS.  0 when the
+// persistent kernel does not serve the shape at all.
+int small_batch_per_launch(const inr_siren_desc_t* d, int64_t n) {
+    if (!small_multi_ok(d, n)) return 0;
+    const int per = multi_capacity(d->hidden_features, multi_rows(d, n)) / multi_blocks(d, n);
+    return per < SB_MAX_PROBS ? per : SB_MAX_PROBS;
+}
+
+// n_fits independent fits of one shape (same n, x, step schedule; own buffers, acquisition cycles and workspaces), packed
+// small_batch_per_launch(d, n) to a cooperative launch, the groups one after the other on `st`.  INR_E_FALLBACK (before any
+// device work) when the device refuses the first launch: the caller then runs the fits one by one.
+int small_fit_batch(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, int n_fits,
+                    float* const* params, float* const* grads, float* const* m, float* const* v, const float* x,
+                    const float* const* targets, const float* const* weights, const int* n_acq, const int* first_acq, int64_t n,
+                    int64_t first_step, int n_steps, double lr, double b1, double b2, double eps, float* const* losses,
+                    void* const* ws, hipStream_t st) {
+    const int H = d->hidden_features;
+    const int rows = multi_rows(d, n);
+    const int nb = multi_blocks(d, n);
+    const int per = small_batch_per_launch(d, n);
+    if (per < 2) return INR_E_FALLBACK;
+    const void* fn = (H == 32) ? (const void*)siren_small_batch_kernel<32, 64>
+                     : (rows == 32) ? (const void*)siren_small_batch_kernel<64, 32>
+                                    : (const void*)siren_small_batch_kernel<64, 64>;
+    std::vector<unsigned*> sync(n_fits);
+    for (int g0 = 0; g0 < n_fits; g0 += per) {
+        const int cnt = n_fits - g0 < per ? n_fits - g0 : per;
+        SmallBatch b{};
+        small_shared(b.p, d, w_off, b_off, P, x, n, b1, b2, eps);
+        b.p.stamps = nullptr;   // (a stamp buffer is sized for one problem's grid: batched launches do not stamp)
+        SyncTable t{};
+        for (int j = 0; j < cnt; ++j) {
+            const int i = g0 + j;
+            b.probs[j] = small_prob(d, n, P, params[i], grads[i], m[i], v[i], targets[i], weights ? weights[i] : nullptr, n_acq[i],
+                                    (float*)ws[i]);
+            t.sync[j] = sync[i] = b.probs[j].sync;
+        }
+        for (int done = 0; done < n_steps; done += SM_MAX_STEPS) {
+            const int k = n_steps - done < SM_MAX_STEPS ? n_steps - done : SM_MAX_STEPS;
+            for (int j = 0; j < cnt; ++j) {
+                const int i = g0 + j;
+                b.probs[j].first_acq = (int)(((long long)first_acq[i] + done) % n_acq[i]);
+                b.probs[j].losses = (losses && losses[i]) ? losses[i] + done : nullptr;
+            }
+            small_schedule(b.p, first_step, done, k, lr, b1, b2);
+            ProfScope ps(KC_OTHER, st);
+            // arrivals back to zero; the error words too on a problem's first launch (sticky within the call)
+            hipLaunchKernelGGL(small_batch_sync_reset, dim3(1), dim3(64), 0, st, t, cnt, done == 0 ? 2 : 1);
+            INR_LAUNCH_CHECK();
+            void* args[] = {(void*)&b};
+            const hipError_t e = hipLaunchCooperativeKernel(fn, dim3(cnt * nb), dim3(SM_THREADS), args, 0, st);
+            if (e == hipErrorCooperativeLaunchTooLarge && g0 == 0 && done == 0) {
+                (void)hipGetLastError();
+                return INR_E_FALLBACK;   // (only the sync words were touched: the solo calls zero them again)
+            }
+            INR_HIP(e);
+            count_launch(LF_SMALL_BATCH);
+        }
+    }
+    // every fit's error word, one wait for the stream (as small_fit_multi does for its one)
+    std::vector<unsigned> err(n_fits, 0u);
+    for (int i = 0; i < n_fits; ++i)
+        INR_HIP(hipMemcpyAsync(&err[i], sync[i] + 1, sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    INR_HIP(hipStreamSynchronize(st));
+    char bad[256] = "";
+    int nbad = 0;
+    for (int i = 0; i < n_fits; ++i) {
+        if (!err[i]) continue;
+        const size_t used = strlen(bad);
+        if (used + 16 < sizeof(bad)) snprintf(bad + used, sizeof(bad) - used, "%s%d", nbad ? ", " : "", i);
+        ++nbad;
+    }
+    INR_REQUIRE(nbad == 0, INR_E_TIMEOUT,
+                "small-network batched persistent kernel: a grid barrier exceeded its poll limit and the launch was abandoned "
+                "for fit(s) %s; params / m / v / losses of those fits are partly updated and must be discarded", bad);
     return 0;
 }
 

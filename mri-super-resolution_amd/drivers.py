@@ -24,7 +24,7 @@ import torch
 
 from . import dist as inr_dist
 from . import matio, metrics, ops
-from .inr import PN, ImageFitting_set, ShardedSirenFitter, Siren, SirenFitter, input_mapping, reconstruct
+from .inr import PN, ImageFitting_set, ShardedSirenFitter, Siren, SirenFitter, fit_cycle_batch, input_mapping, reconstruct
 
 
 def load_mat_volume(path: str, key: Optional[str] = None) -> np.ndarray:
@@ -253,6 +253,59 @@ def fit_with_perturbnet(INR: Siren, B: torch.Tensor, mean_dataset: ImageFitting_
     return [float(v) for v in torch.cat(losses).cpu()] if losses else []
 
 
+def _slice_inputs(acquisitions, weights):
+    """One direction's acquisitions -> (side, [K, N] device targets ``2*img-1``, [K, N] device weights or None)."""
+    imgs = [np.asarray(a, np.float32) for a in acquisitions]
+    side = imgs[0].shape[0]
+    if any(a.shape != (side, side) for a in imgs):
+        raise ValueError("acquisitions must be square 2-D images of one size")
+    # all acquisitions resident as ONE [K, N] tensor: a whole epoch (one weighted Adam step per acquisition) -- and every
+    # epoch before the averaging window -- is a single call (inr_siren_fit_cycle), not 2 K launches per epoch
+    targets = torch.stack([(2.0 * torch.from_numpy(a) - 1.0).reshape(-1) for a in imgs]).cuda()
+    wts = None if weights is None else torch.stack([torch.from_numpy(np.asarray(w, np.float32)).reshape(-1)
+                                                    for w in weights]).cuda()
+    return side, targets, wts
+
+
+def _fit_slices(models, side, inputs, total_steps, seg, scale, lr, divide_by):
+    """The schedule of master.py:130-160 for one or more already drawn models of one side length and one acquisition count:
+    one model steps through ``SirenFitter.step_cycle``, several through ``fit_cycle_batch`` (shared persistent launches).
+    ``seconds`` is the wall time of the whole group."""
+    n_acq = inputs[0][1].shape[0]
+    coords = ImageFitting_set([np.zeros((side, side), np.float32)]).coords[0]          # get_mgrid(side, 2)
+    fitters = [SirenFitter(model, lr=lr) for model in models]
+    predicted = [torch.zeros(side, side, dtype=torch.float64, device="cuda") for _ in models]
+    large = [torch.zeros(side * scale, side * scale, dtype=torch.float64, device="cuda") for _ in models]
+    targets = [t for _, t, _ in inputs]
+    wts = [w for _, _, w in inputs]
+
+    def epochs(n_steps):
+        if len(fitters) == 1:
+            fitters[0].step_cycle(coords, targets[0], n_steps, wts[0])
+        else:
+            fit_cycle_batch(fitters, coords, targets, n_steps, weights=wts)
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    quiet = max(0, total_steps - seg)                                     # epochs before the first snapshot
+    if quiet:
+        epochs(quiet * n_acq)
+    for step in range(quiet, total_steps):
+        epochs(n_acq)
+        if step >= total_steps - seg:                                     # master.py:149-160
+            for k, model in enumerate(models):
+                predicted[k] += reconstruct(model, (side, side), None, clamp_min=None).double()
+                large[k] += reconstruct(model, (side * scale, side * scale), None, clamp_min=None).double()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    # master.py:162-164 divides by args.seg whatever the number of snapshots taken (step >= total - seg gives seg of them
+    # when total_steps >= seg); `divide_by` reproduces that literally
+    n_snap = divide_by if divide_by is not None else min(seg, total_steps)
+    return [{"predicted": (predicted[k] / max(n_snap, 1)).cpu().numpy(), "large": (large[k] / max(n_snap, 1)).cpu().numpy(),
+             "seconds": dt, "optimizer_steps": total_steps * n_acq,
+             "train_voxels_per_s": total_steps * n_acq * side * side / dt, "model": model} for k, model in enumerate(models)]
+
+
 def fit_slice_ensemble(acquisitions: Sequence[np.ndarray], weights: Optional[Sequence[np.ndarray]] = None,
                        total_steps: int = 3000, seg: int = 150, scale: int = 3, hidden_features: int = 64,
                        hidden_layers: int = 6, lr: float = 3e-4, seed: Optional[int] = 0,
@@ -260,41 +313,46 @@ def fit_slice_ensemble(acquisitions: Sequence[np.ndarray], weights: Optional[Seq
     """master.py:130-160 for one gradient direction: raw 2-D coordinates -> Siren(2, H, L, 1); per epoch one weighted
     Adam step per acquisition (targets are ``2*img-1``, nn_mri.py:174-180); the outputs of the last ``seg`` epochs at
     the native and the x``scale`` grid are averaged.  Returns float64 host arrays like the reference."""
-    imgs = [np.asarray(a, np.float32) for a in acquisitions]
-    side = imgs[0].shape[0]
-    if any(a.shape != (side, side) for a in imgs):
-        raise ValueError("acquisitions must be square 2-D images of one size")
+    side, targets, wts = _slice_inputs(acquisitions, weights)
     if seed is not None:
         torch.manual_seed(seed)
     model = Siren(2, hidden_features, hidden_layers, 1).cuda()
-    coords = ImageFitting_set([imgs[0]]).coords[0]                        # get_mgrid(side, 2)
-    # all acquisitions resident as ONE [K, N] tensor: a whole epoch (one weighted Adam step per acquisition) -- and every
-    # epoch before the averaging window -- is a single call (inr_siren_fit_cycle), not 2 K launches per epoch
-    targets = torch.stack([(2.0 * torch.from_numpy(a) - 1.0).reshape(-1) for a in imgs]).cuda()
-    wts = None if weights is None else torch.stack([torch.from_numpy(np.asarray(w, np.float32)).reshape(-1)
-                                                    for w in weights]).cuda()
-    n_acq = len(imgs)
-    fitter = SirenFitter(model, lr=lr)
-    predicted = torch.zeros(side, side, dtype=torch.float64, device="cuda")
-    large = torch.zeros(side * scale, side * scale, dtype=torch.float64, device="cuda")
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    quiet = max(0, total_steps - seg)                                     # epochs before the first snapshot
-    if quiet:
-        fitter.step_cycle(coords, targets, quiet * n_acq, wts)
-    for step in range(quiet, total_steps):
-        fitter.step_cycle(coords, targets, n_acq, wts)
-        if step >= total_steps - seg:                                     # master.py:149-160
-            predicted += reconstruct(model, (side, side), None, clamp_min=None).double()
-            large += reconstruct(model, (side * scale, side * scale), None, clamp_min=None).double()
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    # master.py:162-164 divides by args.seg whatever the number of snapshots taken (step >= total - seg gives seg of them
-    # when total_steps >= seg); `divide_by` reproduces that literally
-    n_snap = divide_by if divide_by is not None else min(seg, total_steps)
-    return {"predicted": (predicted / max(n_snap, 1)).cpu().numpy(), "large": (large / max(n_snap, 1)).cpu().numpy(),
-            "seconds": dt, "optimizer_steps": total_steps * n_acq,
-            "train_voxels_per_s": total_steps * n_acq * side * side / dt, "model": model}
+    return _fit_slices([model], side, [(side, targets, wts)], total_steps, seg, scale, lr, divide_by)[0]
+
+
+def fit_slice_ensembles(jobs: Sequence[tuple], total_steps: int = 3000, seg: int = 150, scale: int = 3,
+                        hidden_features: int = 64, hidden_layers: int = 6, lr: float = 3e-4, seed: Optional[int] = 0,
+                        divide_by: Optional[int] = None) -> List[Dict[str, object]]:
+    """``fit_slice_ensemble`` for several directions (``jobs``: a list of ``(acquisitions, weights)``, all of one side
+    length) with the fits sharing launches: returns what calling ``fit_slice_ensemble`` on each job in order returns.
+
+    The K models are drawn from torch's global generator in job order before any fitting (after ``torch.manual_seed(seed)``
+    per model when ``seed`` is set, as the sequential calls do), so they start from the weights of the sequential run.  The
+    persistent kernel advances all problems of a launch in lockstep, so only jobs with the same number of acquisitions fit
+    together (``fit_cycle_batch`` over the quiet phase and every window epoch, then ``reconstruct`` per model); a job whose
+    acquisition count no other job shares is fitted on its own, sequentially.  ``seconds`` of a job is the wall time of the
+    group it was fitted in."""
+    jobs = list(jobs)
+    if not jobs:
+        return []
+    inputs = [_slice_inputs(acqs, wts) for acqs, wts in jobs]
+    if len({side for side, _, _ in inputs}) > 1:
+        raise ValueError("fit_slice_ensembles: all jobs must have one side length")
+    models = []
+    for _ in jobs:
+        if seed is not None:
+            torch.manual_seed(seed)
+        models.append(Siren(2, hidden_features, hidden_layers, 1).cuda())
+    groups: Dict[int, List[int]] = {}
+    for k, (_, targets, _) in enumerate(inputs):
+        groups.setdefault(int(targets.shape[0]), []).append(k)
+    out: List[Optional[Dict[str, object]]] = [None] * len(jobs)
+    for members in groups.values():
+        res = _fit_slices([models[k] for k in members], inputs[0][0], [inputs[k] for k in members], total_steps, seg, scale,
+                          lr, divide_by)
+        for k, r in zip(members, res):
+            out[k] = r
+    return out
 
 
 RECORD_KEYS = ("job", "n_coords", "steps", "t_fit", "t_recon", "psnr_db", "ssim_mean", "final_loss", "status", "reseeds", "rank",
@@ -499,7 +557,8 @@ def run_volumes(volumes: Sequence[np.ndarray], steps: int = 2500, allow_sharding
                 record(job, res)
     whole = list(plan["whole"][rank])
     # (networks small enough for the persistent cooperative kernel -- grid barriers over co-resident blocks: siren_small.hip -- are
-    #  never run side by side: two such launches could each hold part of the chip and wait for the rest)
+    #  never run side by side: two such launches could each hold part of the chip and wait for the rest.  Small fits share the
+    #  chip safely only inside ONE cooperative launch: inr.fit_cycle_batch / fit_slice_ensembles, inr_siren_fit_cycle_batch)
     cooperative = fit_kwargs.get("hidden_features", 512) in (32, 64) and 2 * fit_kwargs.get("mapping_size", 128) <= 32
     if int(concurrent) > 1 and len(whole) > 1 and torch.cuda.is_available() and not cooperative:
         from concurrent.futures import ThreadPoolExecutor

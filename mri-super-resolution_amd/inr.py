@@ -482,6 +482,56 @@ class SirenFitter:
         self._workspace = None
 
 
+def fit_cycle_batch(fitters, model_input, targets, n_steps, weights=None, first_acqs=None):
+    """``n_steps`` of ``SirenFitter.step_cycle`` for K independent fitters at once: ONE call into
+    ``inr_siren_fit_cycle_batch``, bit for bit the K ``step_cycle`` calls in order.  The fitters share the network shape,
+    ``lr`` / ``betas`` / ``eps``, ``step_count``, the device and ``model_input``; ``targets[k]`` / ``weights[k]`` (entries
+    may be None) are fitter k's [n_acq_k, N] images, ``first_acqs[k]`` its first acquisition (default 0).  For the small
+    master.py networks the fits share persistent launches (several problems per cooperative grid).  Every fitter keeps its
+    own workspace; every ``step_count`` advances.  Returns the [K, n_steps] losses as a device tensor (no sync here)."""
+    fitters = list(fitters)
+    K = len(fitters)
+    if K < 1:
+        raise ValueError("fit_cycle_batch needs at least one fitter")
+    if len(targets) != K or (weights is not None and len(weights) != K) or (first_acqs is not None and len(first_acqs) != K):
+        raise ValueError(f"targets / weights / first_acqs need one entry per fitter ({K})")
+    for f in fitters:
+        if isinstance(f, ShardedSirenFitter):
+            raise TypeError("fit_cycle_batch takes SirenFitter objects (a sharded fit steps through its own collectives)")
+        f._check_views()
+    f0 = fitters[0]
+
+    def shape(d):
+        return tuple(getattr(d, name) for name, _ in d._fields_)
+
+    for k, f in enumerate(fitters[1:], 1):
+        if shape(f.desc) != shape(f0.desc):
+            raise ValueError(f"fitter {k} has another network shape than fitter 0")
+        if (f.lr, f.betas, f.eps) != (f0.lr, f0.betas, f0.eps):
+            raise ValueError(f"fitter {k} has other optimizer settings (lr / betas / eps) than fitter 0")
+        if f.step_count != f0.step_count:
+            raise ValueError(f"fitter {k} is at step {f.step_count}, fitter 0 at {f0.step_count}")
+        if f.flat.device != f0.flat.device:
+            raise ValueError(f"fitter {k} lives on {f.flat.device}, fitter 0 on {f0.flat.device}")
+    x = model_input.detach().reshape(-1, model_input.shape[-1]).contiguous()
+    t = [tg.detach().reshape(tg.shape[0], -1).contiguous() for tg in targets]
+    w = None if weights is None else [None if wt is None else wt.detach().reshape(wt.shape[0], -1).contiguous()
+                                      for wt in weights]
+    losses = torch.empty(K, max(int(n_steps), 1), dtype=torch.float32, device=x.device)
+    need = ops.siren_fit_workspace_bytes(f0.desc, x.shape[0])
+    for f in fitters:
+        if f._workspace is None or f._workspace.numel() < need:
+            f._workspace = None
+            f._workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
+    ops.siren_fit_cycle_batch(f0.desc, [f.flat for f in fitters], [f.grads for f in fitters], [f.m for f in fitters],
+                              [f.v for f in fitters], x, t, w, [0] * K if first_acqs is None else [int(a) for a in first_acqs],
+                              f0.step_count + 1, int(n_steps), f0.lr, f0.betas[0], f0.betas[1], f0.eps,
+                              [losses[k] for k in range(K)], [f._workspace for f in fitters])
+    for f in fitters:
+        f.step_count += int(n_steps)
+    return losses[:, :n_steps]
+
+
 class ShardedSirenFitter(SirenFitter):
     """One fit whose coordinate rows are split over the ranks of a process group (SURVEY.md 8 e): every rank holds
     identical weights and its own row shard; per step the local forward/backward (``inr_siren_loss_grad``, mean taken

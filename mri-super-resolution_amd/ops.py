@@ -433,6 +433,71 @@ def siren_fit_cycle(desc: SirenDesc, params, grads, m, v, x, targets, weights, f
     return workspace
 
 
+def siren_fit_cycle_batch(desc: SirenDesc, params, grads, m, v, x, targets, weights, first_acqs, first_step: int,
+                          n_steps: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, losses=None, workspaces=None):
+    """``inr_siren_fit_cycle_batch``: K independent fits of one shape on one ``x``.  ``params`` / ``grads`` / ``m`` / ``v`` /
+    ``targets`` / ``workspaces`` are lists of K tensors (fit k: ``targets[k]`` is [n_acq_k, n * out_features]);
+    ``weights`` / ``losses`` are None or lists whose entries may be None.  Bit for bit the K ``siren_fit_cycle`` calls in
+    order; small networks share persistent launches.  Returns the list of workspaces."""
+    K = len(params)
+    if K < 1:
+        raise ValueError("need at least one fit")
+    for name, lst in (("grads", grads), ("m", m), ("v", v), ("targets", targets), ("first_acqs", first_acqs)):
+        if len(lst) != K:
+            raise ValueError(f"{name} has {len(lst)} entries, params {K}")
+    for name, lst in (("weights", weights), ("losses", losses), ("workspaces", workspaces)):
+        if lst is not None and len(lst) != K:
+            raise ValueError(f"{name} has {len(lst)} entries, params {K}")
+    total, _ = siren_param_layout(desc)
+    for k in range(K):
+        for name, t in (("params", params[k]), ("grads", grads[k]), ("m", m[k]), ("v", v[k])):
+            _chk(t, f"{name}[{k}]")
+            if t.numel() != total:
+                raise ValueError(f"{name}[{k}] has {t.numel()} floats, layout needs {total}")
+    if len({t.data_ptr() for t in params}) != K:
+        raise ValueError("two fits share one params buffer")
+    _chk(x, "x")
+    if x.dim() != 2 or x.shape[1] != desc.in_features:
+        raise ValueError(f"x {tuple(x.shape)} must be [n,{desc.in_features}]")
+    n = x.shape[0]
+    n_acq = []
+    for k in range(K):
+        _chk(targets[k], f"targets[{k}]")
+        if targets[k].dim() != 2 or targets[k].shape[1] != n * desc.out_features:
+            raise ValueError(f"targets[{k}] must be [n_acq, n*out_features]")
+        n_acq.append(int(targets[k].shape[0]))
+        if weights is not None and weights[k] is not None:
+            _chk(weights[k], f"weights[{k}]")
+            if tuple(weights[k].shape) != tuple(targets[k].shape):
+                raise ValueError(f"weights[{k}] must have the shape of targets[{k}]")
+        if not 0 <= int(first_acqs[k]) < n_acq[k]:
+            raise ValueError(f"first_acqs[{k}] out of range")
+        if losses is not None and losses[k] is not None:
+            _chk(losses[k], f"losses[{k}]")
+            if losses[k].numel() < n_steps:
+                raise ValueError(f"losses[{k}] shorter than n_steps")
+    need = siren_fit_workspace_bytes(desc, n)
+    workspaces = list(workspaces) if workspaces is not None else [None] * K
+    for k in range(K):
+        if workspaces[k] is None:
+            workspaces[k] = _ws(need, x.device)
+        elif workspaces[k].numel() * workspaces[k].element_size() < need:
+            raise ValueError(f"workspaces[{k}] too small")
+    if len({w.data_ptr() for w in workspaces}) != K:
+        raise ValueError("two fits share one workspace")
+    ws_bytes = min(w.numel() * w.element_size() for w in workspaces)
+
+    def ptrs(lst):
+        return (C.c_void_p * K)(*[None if t is None else t.data_ptr() for t in lst])
+
+    check(lib().inr_siren_fit_cycle_batch(
+        C.byref(desc), K, ptrs(params), ptrs(grads), ptrs(m), ptrs(v), x.data_ptr(), ptrs(targets),
+        None if weights is None else ptrs(weights), (C.c_int * K)(*n_acq), (C.c_int * K)(*[int(a) for a in first_acqs]), n,
+        int(first_step), int(n_steps), float(lr), float(beta1), float(beta2), float(eps),
+        None if losses is None else ptrs(losses), ptrs(workspaces), ws_bytes, _stream()), "inr_siren_fit_cycle_batch")
+    return workspaces
+
+
 REUSE_INPUT_IMAGE, REUSE_TARGET_STATS = 1, 2        # INR_REUSE_* of include/inrhip.h
 
 
@@ -504,7 +569,7 @@ def siren_backward_train(desc: SirenDesc, params, grads, gy, workspace):
 
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
-                   "small_step", "hp_narrow", "hp_fused_fwd", "hp_row")   # INR_LF_* of include/inrhip.h, in order
+                   "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order
 
 
 def launch_counts() -> dict:

@@ -11,6 +11,11 @@ arguments -- the module-level ``cases`` list the reference imports was never pub
 hidden_features; ``focus = wide`` widens the ROI to the whole slice, ``weight = True`` asks for acceptance weights, which
 need ``--erd``).  ``--erd 1|2`` (agglomerative-clustering outlier rejection, master.py:79-93) and the DICOM export
 (master.py:228-247) are outside the build's scope: the first is refused, the second is replaced by ``images.mat``.
+
+``--fit_batch K`` (default 1: one direction after the other, as the reference does) fits up to K gradient directions of a
+case together (``drivers.fit_slice_ensembles``: the small networks share persistent launches and start from the weights
+of the sequential run).  Post-processing, CSV rows and ``images.mat`` follow in the usual order and are the same bits;
+the per-fit ``seconds`` of the printed summary is then the wall time of the batch the fit was part of.
 """
 from __future__ import annotations
 
@@ -47,6 +52,8 @@ def build_parser():
     parser.add_argument('--cases', default=None, help='JSON file: list of {pt_id, b, cancer_loc, contralateral_loc, noise, '
                                                       'cancer_slice, acquisitions}')
     parser.add_argument('--experiment', default=None, help='experiments/sr1_exp_N.txt to take steps / depth / hidden / focus from')
+    parser.add_argument('--fit_batch', type=int, default=1, help='fit up to this many gradient directions of a case together '
+                                                                 '(shared launches; same results)')
     return parser
 
 
@@ -96,21 +103,36 @@ def run(args, cases):
                 erd.apply_auto_erd(case, args.erd, r0, r1)
             contrast_fn = lambda im: calculate_contrast(case, 1, im, r0)
             acc = {}
+            prepared = []
             for direction in range(3):
-                print(f'Training for {directions[direction]} direction...')
                 ends = np.cumsum(case.acquisitions)
                 starts = ends - case.acquisitions
                 acqs = range(int(starts[direction]), int(ends[direction]))
                 imgs = [np.asarray(case.dwi[r0:r1, r0:r1, _slice, a], np.float32) for a in acqs]
                 accepts = [np.asarray(case.accept[r0:r1, r0:r1, _slice, a], np.float32) for a in acqs]
+                prepared.append((imgs, accepts))
+            fit_kwargs = dict(total_steps=args.total_steps, seg=args.seg, scale=args.scale,
+                              hidden_features=args.hidden_features, hidden_layers=args.hidden_layers,
+                              lr=args.learning_rate, seed=None, divide_by=args.seg)
+            batch = max(1, int(args.fit_batch))
+            fits = {}
+            for direction in range(3):
+                if batch > 1 and direction % batch == 0:          # fit this direction and the next ones of its batch together
+                    members = list(range(direction, min(direction + batch, 3)))
+                    print(f"Training for {', '.join(directions[d] for d in members)} direction{'s' if len(members) > 1 else ''}...")
+                    res = drivers.fit_slice_ensembles([prepared[d] for d in members], **fit_kwargs)
+                    fits.update(zip(members, res))
+                imgs, accepts = prepared[direction]
                 sum_image = sum(i.astype(np.float64) for i in imgs)
                 sum_accepted = sum(i.astype(np.float64) * a for i, a in zip(imgs, accepts))
                 sum_accepts = sum(a.astype(np.float64) for a in accepts)
                 accepted_mean = sum_accepted / (sum_accepts + contrast.eps)                # master.py:112
                 direction_mean = sum_image / len(imgs)
-                fit = drivers.fit_slice_ensemble(imgs, accepts, total_steps=args.total_steps, seg=args.seg, scale=args.scale,
-                                                 hidden_features=args.hidden_features, hidden_layers=args.hidden_layers,
-                                                 lr=args.learning_rate, seed=None, divide_by=args.seg)
+                if batch > 1:
+                    fit = fits.pop(direction)
+                else:
+                    print(f'Training for {directions[direction]} direction...')
+                    fit = drivers.fit_slice_ensemble(imgs, accepts, **fit_kwargs)
                 orig = direction_mean.copy()                                               # dataset.mean (nn_mri.py:196)
                 erd_img = accepted_mean
                 out_img = fit["predicted"]
