@@ -457,7 +457,9 @@ int  inr_prof_read(int kernel_class, int64_t* launches, double* total_ms);
  * GEMMs of 512 output columns to the row-owning kernel (a block owns 128 rows x all 512 columns, epilogue in line; 0 = default: measured
  * slower, bit-identical) when they have at least key-28 (default 1024) row panels; key 29 = most 128 x 256 tiles (per 256 CUs; default 192) of a launch that
  * still takes the 64 x 128 tiles of gemm_hp_nt_kernel; key 30 = 0 keeps the head step a kernel of its own (1, default: from key-31 = 768
- * row panels on it rides in the epilogue of the last sine layer, gemm_hp_row_kernel<HPE_HEAD>);
+ * row panels on it rides in the epilogue of the last sine layer, gemm_hp_row_kernel<HPE_HEAD>); key 32 = test-only cap on the grid of the
+ * persistent HL32 kernels (pkd, pkc, row-owning, fused head, fused forward; 0 .. 2^20, 0 default = no cap): small launches then walk several
+ * tiles per block; the kernel family chosen and every result bit stay the same;
  * keys 8/9 = time-stamp selection of diagnostic builds.
  * PROCESS-GLOBAL and diagnostic only (see "threading" at the top of this file). */
 int inr_debug_set(int key, int value);     /* INR_E_INVALID for an unknown key or a value outside the key's range */

@@ -111,6 +111,7 @@ extern tune_int g_rams_pregate_min_vox;   // key 26 (rams.hip)
 extern tune_int g_hp_narrow_max_tiles;   // key 29 (gemm_f32.hip)
 extern tune_int g_hp_row_head, g_hp_row_head_min_tiles;   // keys 30, 31 (gemm_f32.hip: the head step fused into the last sine layer)
 extern tune_int g_hp_row, g_hp_row_min_tiles;   // keys 27, 28 (gemm_f32.hip: the row-owning 128 x 512 kernel)
+extern tune_int g_hp_grid_cap;   // key 32 (gemm_f32.hip: test-only cap on the persistent grids)
 extern tune_int g_hp_head_min_rows;   // key 21 (gemm_f32.hip)
 int hp_input_grad_max_rows(int64_t n);
 int hp_input_grad(char* dzprev_hl, const char* dz_hl, const char* WT_hl, const float* mul, int64_t n, int in_f, int out_f,
@@ -1828,6 +1829,7 @@ const DebugKey* debug_table(int* count) {
         {27, &g_hp_row, 0, 0, 1},        {28, &g_hp_row_min_tiles, 1024, 1, 1 << 30},
         {29, &g_hp_narrow_max_tiles, 192, 0, 1 << 30},
         {30, &g_hp_row_head, 1, 0, 1},   {31, &g_hp_row_head_min_tiles, 768, 1, 1 << 30},
+        {32, &g_hp_grid_cap, 0, 0, 1 << 20},
     };
     *count = (int)(sizeof(table) / sizeof(table[0]));
     return table;

@@ -1116,6 +1116,17 @@ static int hp_num_cus() {
     }
     return n;
 }
+// inr_debug_set(32, v): test-only cap on the grid of the persistent kernels (0 = none, the default), so that small launches walk
+// several tiles per block.  Every persistent kernel strides its tiles by gridDim.x and xcd_remap maps [0, tiles) onto itself for any
+// grid, so a cap changes which block computes a tile, never what it computes.  (Not applied in hp_row_plan: the family choice
+// stays that of the chip.)
+tune_int g_hp_grid_cap{0};
+static unsigned hp_persistent_grid(long long tiles) {
+    long long g = tiles < hp_num_cus() ? tiles : hp_num_cus();
+    const int cap = g_hp_grid_cap;
+    if (cap > 0 && g > cap) g = cap;
+    return (unsigned)g;
+}
 bool hp_head_ok(int hidden) { return hidden == 128 || hidden == 256 || hidden == 512 || hidden == 1024; }
 
 // per-step weight preparation (gemm_hp.inc): slots[l] = max|W_l|, slots[8 + l] = 0 (dz maxima), slots[16 + l] = wnorm_l; `part`
@@ -1263,10 +1274,10 @@ int hp_sine_forward(char* act_hl, float* dact, const char* x_hl, const char* W_h
         if (int rc = hp_check_grid(p)) return rc;
         const long long tiles = (long long)p.tiles_m * p.tiles_n;
         const dim3 grid((unsigned)tiles), block(HP_NTH);
-        const dim3 pgrid((unsigned)(tiles < hp_num_cus() ? tiles : hp_num_cus()));
+        const dim3 pgrid(hp_persistent_grid(tiles));
         if (hp_row_ok(plan.wide_rows, out_f, in_f, true)) {   // one block per 128 rows x all 512 columns (gemm_hp_row.inc)
             p.tiles_n = 1;
-            const dim3 rgrid((unsigned)(p.tiles_m < hp_num_cus() ? p.tiles_m : hp_num_cus()));
+            const dim3 rgrid(hp_persistent_grid(p.tiles_m));
             if (z_only) hipLaunchKernelGGL((gemm_hp_row_kernel<HPE_Z>), rgrid, block, 0, stream, p);
             else if (dact) hipLaunchKernelGGL((gemm_hp_row_kernel<HPE_SINE_STASH>), rgrid, block, 0, stream, p);
             else hipLaunchKernelGGL((gemm_hp_row_kernel<HPE_SINE>), rgrid, block, 0, stream, p);
@@ -1338,7 +1349,7 @@ int hp_sine_forward_head(char* dz_hl, const char* x_hl, const char* W_hl, const 
     p.inv_count = (float)(1.0 / (double)(count_total > 0 ? count_total : n));
     p.stamps = hp_stamp_target(KC_GEMM_FWD);
     ProfScope ps(KC_GEMM_FWD, stream);
-    const dim3 rgrid((unsigned)(p.tiles_m < hp_num_cus() ? p.tiles_m : hp_num_cus())), block(HP_NTH);
+    const dim3 rgrid(hp_persistent_grid(p.tiles_m)), block(HP_NTH);
     hipLaunchKernelGGL((gemm_hp_row_kernel<HPE_HEAD>), rgrid, block, 0, stream, p);
     INR_LAUNCH_CHECK();
     count_launch(LF_HP_ROW);
@@ -1371,10 +1382,10 @@ int hp_input_grad(char* dzprev_hl, const char* dz_hl, const char* WT_hl, const f
         if (int rc = hp_check_grid(p)) return rc;
         const long long tiles = (long long)p.tiles_m * p.tiles_n;
         const dim3 grid((unsigned)tiles), block(HP_NTH);
-        const dim3 pgrid((unsigned)(tiles < hp_num_cus() ? tiles : hp_num_cus()));
+        const dim3 pgrid(hp_persistent_grid(tiles));
         if (hp_row_ok(plan.wide_rows, in_f, out_f, false)) {
             p.tiles_n = 1;
-            const dim3 rgrid((unsigned)(p.tiles_m < hp_num_cus() ? p.tiles_m : hp_num_cus()));
+            const dim3 rgrid(hp_persistent_grid(p.tiles_m));
             hipLaunchKernelGGL((gemm_hp_row_kernel<HPE_MUL>), rgrid, block, 0, stream, p);
             count_launch(LF_HP_ROW);
         } else if (g_hp_persistent == 2 && out_f == 512) {   // (K = 256 would spill: the in-line epilogue serves it)
@@ -1487,7 +1498,7 @@ int hp_fused_forward(float* y, const char* x_hl, const unsigned* x_amax, int64_t
     p.head_W = head_W; p.head_b = head_b; p.y = y;
     p.use_clamp = use_clamp; p.clamp_min = clamp_min;
     const long long panels = (n + FW_ROWS - 1) / FW_ROWS;
-    const dim3 grid((unsigned)(panels < hp_num_cus() ? panels : hp_num_cus())), block(FW_NTH);
+    const dim3 grid(hp_persistent_grid(panels)), block(FW_NTH);
     ProfScope ps(KC_GEMM_FWD, stream);
     if (hidden == 512) hipLaunchKernelGGL((siren_fwd_fused_kernel<4>), grid, block, 0, stream, p);
     else hipLaunchKernelGGL((siren_fwd_fused_kernel<2>), grid, block, 0, stream, p);

@@ -13,7 +13,13 @@ silently, one that is too loose loses low bits) under adversarial magnitudes ON 
 1e3, one row 1e6 above the rest, a network built so that the bound is attained, and the weights at the end of a full
 2,500-step fit, where the gradient is a small difference of large terms.  Criterion there: finite, and as close to float64
 as the exact-fp32 (f32-input MFMA) kernels are, up to a small factor.
+
+Last part: blocks of the persistent kernels that walk several panels -- at small sizes under a grid cap (debug key 32: bit for bit
+across caps), and the default fit step at the row counts real fits run (98,176 ... 524,288 rows: fused head, tall head-slab
+reduction, per-layer parameter-gradient launches) against float64 evaluated on the GPU.
 """
+import contextlib
+
 import numpy as np
 import pytest
 import torch
@@ -48,16 +54,19 @@ def make_pair(fin, hidden, layers, seed, dtype=torch.float64):
     return net, ref.to(dtype)
 
 
-def oracle_loss_grads(ref, x, t, w):
-    """float64 loss and gradients in network order (W_0, b_0, ..., W_head, b_head)."""
+def oracle_loss_grads(ref, x, t, w, device="cpu"):
+    """float64 loss and gradients in network order (W_0, b_0, ..., W_head, b_head).  `device="cuda"` evaluates the port with
+    torch's own float64 kernels on the GPU (independent of libinrhip): what the production row counts need."""
+    ref.to(device)
     for p in ref.parameters():
         p.grad = None
-    out = ref(x.double())
-    sq = (out - t.double().reshape(-1, 1)) ** 2
-    loss = (sq if w is None else w.double().reshape(-1, 1) * sq).mean()
+    out = ref(x.to(device).double())
+    sq = (out - t.to(device).double().reshape(-1, 1)) ** 2
+    loss = (sq if w is None else w.to(device).double().reshape(-1, 1) * sq).mean()
     loss.backward()
     mods = [m.linear if isinstance(m, P.PortSine) else m for m in ref.net]
-    return loss.item(), [g for m in mods for g in (m.weight.grad.numpy(), m.bias.grad.numpy())], out.detach().numpy()
+    grads = [host(g) for m in mods for g in (m.weight.grad, m.bias.grad)]
+    return loss.item(), grads, host(out)
 
 
 def fused_loss_grads(net, x, t, w):
@@ -447,12 +456,15 @@ def test_reconstruct_builds_its_input_as_hl32_directly(shape, m, hidden):
     assert O.rel_l2(got, P.port_reconstruct(ref, shape, B.cpu())) < T1
 
 
-@pytest.mark.parametrize("fin,n", [(256, 128 * 40 + 77), (512, 128 * 33), (128, 128 * 9 + 1), (64, 2000)])
+@pytest.mark.parametrize("fin,n", [(256, 128 * 40 + 77), (512, 128 * 33), (128, 128 * 9 + 1), (64, 2000), (256, 128 * 600 + 37)])
 def test_row_owning_kernel_is_bit_identical_to_the_deferred_epilogue_kernel(fin, n):
     """gemm_hp_row_kernel (round 5: one block owns 128 rows x all 512 columns, two 80 KB LDS stages, epilogue in line) against
     gemm_hp_pkd / pkc_kernel on the same launches: every accumulator sees the same sequence of MFMAs and the epilogue is the same
     chunk arithmetic, so a 6-step fit (forward with stash, last layer z-only, input gradients with column sums and maxima), the
-    losses and an inference forward agree BIT FOR BIT -- ragged last panel, first-layer K = 64 ... 512 (the row kernel takes K = 256 / 512 only), one tile per CU or several."""
+    losses and an inference forward agree BIT FOR BIT -- ragged last panel, first-layer K = 64 ... 512 (the row kernel takes K = 256 / 512
+    only).  Up to 41 panels every block of the row kernel owns ONE panel; at 601 panels (76,837 rows) the grid is the chip's 256 CUs and
+    each block walks 2 or 3 of them, so the state carried from one panel into the next (next K-tile 0 in LDS under the epilogue, stage 1
+    reused after it) is on the path.  (test_persistent_grid_cap_keeps_every_bit: the same walk at small sizes under debug key 32.)"""
     from mri_super_resolution_amd._lib import lib
     g = torch.Generator().manual_seed(n)
     x = (torch.rand(n, fin, generator=g) * 2 - 1).cuda()
@@ -573,3 +585,152 @@ def test_fused_head_as_a_row_shard_and_run_to_run_bits():
     assert c1 == c2 == 1 and c0 == 0
     assert np.array_equal(g1, g2) and l1 == l2
     assert abs(l1 - l0) <= 2e-6 * abs(l0) and O.rel_l2(g1, g0) < 2e-6
+
+
+# ------------------------------------------------------------------ blocks that walk several panels (debug key 32) ---------
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+# (name, debug keys, families of ONE inr_siren_loss_grad + ONE inr_siren_forward of Siren(256, 512, 3, 1) at 46 panels; None: the forward
+# alone).  Key 18 = 0 keeps the launches wide (46 panels would take the 64-row tiles, which are not persistent); key 31 = 1 lets 46 panels
+# take the fused head.
+CAP_FAMILIES = [
+    ("pkd+head", {18: 0, 31: 1}, {"hp_pkd": 3 + 3 + 4, "hp_row": 1, "hp_rc": 4}),
+    ("row+head", {18: 0, 27: 1, 28: 1, 31: 1}, {"hp_row": 4 + 3 + 4, "hp_rc": 4}),
+    ("pkc", {18: 0, 10: 1}, {"hp_pkc": 4 + 3 + 4, "hp_rc": 4}),
+    ("fused_fwd", {19: 1}, None),
+]
+
+
+@pytest.mark.parametrize("name,keys,families", CAP_FAMILIES, ids=[c[0] for c in CAP_FAMILIES])
+def test_persistent_grid_cap_keeps_every_bit(name, keys, families):
+    """Debug key 32 caps the grid of the persistent kernels, so that at 46 panels (a ragged last one) a block walks 1, 2 ... 46 of them:
+    the next panel's K-tile 0 lands under the epilogue, stage 1 is reused after it, the head's targets are prefetched for the next panel.
+    Which block computes a panel changes nothing a panel computes (slabs are indexed by panel, maxima are exact), so loss, every gradient
+    and the forward must agree BIT FOR BIT under caps 0 (the chip's grid), 1, 3 and 7; at cap 7 also against float64 (T1 / T2)."""
+    fin, hidden, layers, n = 256, 512, 3, 128 * 45 + 77
+    net, ref = make_pair(fin, hidden, layers, seed=45)
+    net.cuda()
+    g = torch.Generator().manual_seed(n)
+    x = torch.rand(n, fin, generator=g) * 2 - 1
+    t = torch.rand(n, generator=g)
+    w = (torch.rand(n, generator=g) > 0.25).float() * (0.5 + torch.rand(n, generator=g))
+    xd, td, wd = x.cuda(), t.cuda(), w.cuda()
+    desc, flat = inr.flat_parameters(net)
+    runs = {}
+    for cap in (0, 1, 3, 7):
+        with contextlib.ExitStack() as stack:
+            for k, v in {**keys, 32: cap}.items():
+                stack.enter_context(ops.debug_switch(k, v))
+            ops.launch_counts_reset()
+            if families is None:
+                runs[cap] = (None, [], host(ops.siren_forward(desc, flat, xd)))
+                check_families(ops.launch_counts(), {"hp_fused_fwd": 1})
+            else:
+                runs[cap] = fused_loss_grads(net, xd, td, wd)
+                check_families(ops.launch_counts(), families)
+    for cap in (1, 3, 7):
+        assert runs[cap][0] == runs[0][0], (cap, runs[cap][0], runs[0][0])
+        assert np.array_equal(bits(runs[cap][2]), bits(runs[0][2])), cap
+        for k, (a, b) in enumerate(zip(runs[cap][1], runs[0][1])):
+            assert np.array_equal(bits(a), bits(b)), (cap, k)
+    want_loss, want_g, want_y = oracle_loss_grads(ref, x, t, w)
+    loss, got_g, got_y = runs[7]
+    assert O.rel_l2(got_y, want_y) < T1
+    worst = 0.0
+    if families is not None:
+        assert abs(loss - want_loss) <= T2 * want_loss
+        for k, (a, b) in enumerate(zip(got_g, want_g)):
+            assert O.rel_l2(a, b) < T2, (k, O.rel_l2(a, b))
+            worst = max(worst, O.rel_l2(a, b))
+    print(f"\n[cap {name}] bit-identical at caps 1, 3, 7; from float64: forward {O.rel_l2(got_y, want_y):.2e}"
+          + ("" if families is None else f", worst gradient {worst:.2e}"))
+
+
+# ------------------------------------------------------------------ the default fit step at the row counts real fits run ---------
+def pat07_inputs(golden):
+    """Config 2 on pat07 (64 x 64 x 28 = 114,688 rows) as drivers._fit_volume_once builds it: the volume over its maximum, every second
+    in-plane voxel, Fourier features of its grid with the seed-0 matrix."""
+    vol = golden("pat07_volume.npz")["vol"]
+    lr = np.ascontiguousarray((vol / vol.max())[::2, ::2, :])
+    B = torch.from_numpy(P.fourier_matrix(3)).cuda()
+    x = inr.input_mapping(inr.get_mgrid(lr.shape), B)
+    return x, torch.from_numpy(lr.reshape(-1)).cuda(), None
+
+
+def production_inputs(rows, golden):
+    if rows == 114688:
+        return pat07_inputs(golden)
+    g = torch.Generator(device="cuda").manual_seed(rows)
+    if rows == 524288:      # the headline: bench.py's synthetic 128^3 volume, every second in-plane voxel, its Fourier features
+        lr = np.ascontiguousarray(np.random.default_rng(0).random((128, 128, 128)).astype(np.float32)[::2, ::2, :])
+        B = torch.from_numpy(P.fourier_matrix(3)).cuda()
+        return inr.input_mapping(inr.get_mgrid(lr.shape), B), torch.from_numpy(lr.reshape(-1)).cuda(), None
+    x = torch.rand(rows, 256, generator=g, device="cuda") * 2 - 1
+    t = torch.rand(rows, generator=g, device="cuda")
+    if rows == 139264:      # 64 x 64 x 34 with a weight image that has zeros (master.py:143-148)
+        w = (torch.rand(rows, generator=g, device="cuda") > 0.25).float() * (0.5 + torch.rand(rows, generator=g, device="cuda"))
+        return x, t, w
+    return x, t, None
+
+
+@pytest.mark.parametrize("rows", [98176, 98303, 114688, 139264, 524288])
+def test_default_step_at_production_row_counts_vs_float64(rows, golden):
+    """One inr_siren_loss_grad of Siren(256, 512, 3, 1) with NO debug key set, at the row counts real fits run, against the port in float64
+    (on the GPU: torch's own float64 kernels).  767 panels: the last size with the head step kernel; 768 (98,303 rows, ragged): the fused head
+    at its threshold, blocks walk 3 panels; pat07's 896 panels: an uneven walk; 1,088 weighted panels: 2,176 slab rows of the fused head, a
+    tall reduction; 4,096 panels (the headline): per-layer parameter-gradient launches (>= 200,000 rows).  Then key 30 = 0 (the head step
+    kernel) against the default at 2e-6, as in test_fused_head_epilogue_vs_float64_and_vs_the_head_step_kernel."""
+    x, t, w = production_inputs(rows, golden)
+    assert x.shape == (rows, 256)
+    net, ref = make_pair(256, 512, 3, seed=rows)
+    net.cuda()
+    want_loss, want_g, want_y = oracle_loss_grads(ref, x, t, w, device="cuda")
+    del ref
+    ops.launch_counts_reset()
+    loss, got_g, got_y = fused_loss_grads(net, x, t, w)
+    fused = (rows + 127) // 128 >= 768
+    step = expected_families(256, 512, 3, rows, True)
+    if fused:                 # the last sine layer of the loss_grad call is the row kernel with the head in its epilogue
+        step["hp_pkd"] -= 1
+        step["hp_row"] = 1
+    check_families(ops.launch_counts(), step, expected_families(256, 512, 3, rows, False))
+    dist = [O.rel_l2(a, b) for a, b in zip(got_g, want_g)]
+    print(f"\n[{rows} rows] forward {O.rel_l2(got_y, want_y):.2e}, loss {abs(loss - want_loss) / want_loss:.2e}, "
+          f"worst gradient {max(dist):.2e} (tensor {int(np.argmax(dist))}) from float64")
+    assert O.rel_l2(got_y, want_y) < T1
+    assert abs(loss - want_loss) <= T2 * want_loss
+    for k, d in enumerate(dist):
+        assert d < T2, (k, d)
+    with ops.debug_switch(30, 0):
+        ops.launch_counts_reset()
+        loss0, got0, _ = fused_loss_grads(net, x, t, w)
+        assert ops.launch_counts()["hp_row"] == 0
+    assert abs(loss - loss0) <= 2e-6 * abs(loss0)
+    for k, (a, b) in enumerate(zip(got_g, got0)):
+        assert O.rel_l2(a, b) < 2e-6, (k, O.rel_l2(a, b))
+
+
+def test_fused_head_fit_trajectory_at_a_patient_size(golden):
+    """Five SirenFitter steps on pat07 (114,688 rows: the fused head in every step) against the reference loop (port_fit: autograd +
+    torch.optim.Adam) run in float64 on the GPU: per-step losses within 1e-4, the final weights within 1e-4 (tier T3)."""
+    x, t, _ = pat07_inputs(golden)
+    net, ref = make_pair(256, 512, 3, seed=0)
+    net.cuda()
+    fitter = inr.SirenFitter(net, lr=1e-4)
+    ops.launch_counts_reset()
+    losses = host(fitter.step(x, t, 5))
+    c = ops.launch_counts()
+    assert c["hp_row"] == 5 and c["hp_pkd"] > 0 and c["h3"] + c["f32_pipe16"] + c["f32_pipe"] + c["f32_generic"] == 0, c
+    ref.cuda()
+    port_losses, _ = P.port_fit(ref, x.double(), t.double().reshape(-1, 1), 5, lr=1e-4)
+    print(f"\n[pat07 fit] losses {losses}, float64 {np.asarray(port_losses)}")
+    assert np.allclose(losses, port_losses, rtol=1e-4), (losses, port_losses)
+    def weights(m):            # network order: W_0, b_0, ..., W_head, b_head
+        return np.concatenate([host(p).reshape(-1) for l in m.net for p in (getattr(l, "linear", l).weight, getattr(l, "linear", l).bias)])
+
+    got, want = weights(net), weights(ref)
+    assert got.size == want.size == 256 * 512 + 3 * 512 * 512 + 4 * 512 + 512 + 1
+    print(f"[pat07 fit] final weights {O.rel_l2(got, want):.2e} from float64")
+    assert O.rel_l2(got, want) < 1e-4
