@@ -341,6 +341,16 @@ int inr_acquisition_products(float* out, const float* raw_b0, const float* raw_b
 int inr_rescale2d_linear(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
                          void* stream);
 
+/* ---- (f)-3: the through-plane spline baseline (SRDWI.py:132-141 resize_array, used at superresDWI.py:231) -------------------
+ * scipy.interpolate.interp1d(linspace(0, 1, n_in), y, kind='cubic') evaluated at linspace(0, 1, n_out): make_interp_spline(k=3),
+ * not-a-knot end conditions, fp64 throughout.  in [n_lines][n_in] -> out [n_lines][n_out] (the last axis is contiguous:
+ * arr[X, Y, Z] as the reference passes it).  n_out == 1 gives y[0]; n_out < n_in down-samples.  4 <= n_in <= 8192 (scipy refuses
+ * n_in < 4 too: INR_E_INVALID), 1 <= n_lines < 2^31, n_out >= 1; all checked before any device work.
+ * workspace: inr_resize_z_cubic_workspace_bytes(n_lines, n_in) (the per-line spline coefficients). */
+size_t inr_resize_z_cubic_workspace_bytes(int64_t n_lines, int n_in);
+int inr_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
 /* ---- a-13/a-14: RAMS forward + predict_tensor (network.py:91-155, prediction.py:76-83) --------------------------
  * x [B][H][W][channels] fp32 (uint16-range values) -> out [B][scale*H][scale*W] fp32.  clip_round != 0 applies
  * predict_tensor's clip to [0, 2^16] and round-half-to-even.

@@ -111,6 +111,8 @@ SIGNATURES = {
                                            c_stream]),
     "inr_rescale2d_linear": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
     "inr_adc_map": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
+    "inr_resize_z_cubic_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
+    "inr_resize_z_cubic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
     "inr_rams_param_count": (C.c_int64, [C.POINTER(RamsDesc)]),
     "inr_rams_workspace_bytes": (C.c_size_t, [C.POINTER(RamsDesc), C.c_int, C.c_int, C.c_int]),
     "inr_rams_forward": (C.c_int, [C.POINTER(RamsDesc), c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,

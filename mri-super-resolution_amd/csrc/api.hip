@@ -171,6 +171,8 @@ int launch_ssim(double* out, const float* x, const float* y, int nimg, int H, in
                 int use_mask, float mask_thr, double* ws, hipStream_t st);
 int launch_adc(float* out, const float* data, const float* bvals, int64_t npix, int nb, hipStream_t st);
 int launch_rescale_linear(float* out, const float* in, int nimg, int H, int W, int OH, int OW, hipStream_t st);
+size_t resize_z_workspace_doubles(int64_t n_lines, int n_in);
+int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, double* ws, hipStream_t st);
 int launch_auto_erd(float* accept, const double* values, const float* erd_map, int64_t npix, int n, int rule, hipStream_t st);
 int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, const double* signals, int64_t n,
                       hipStream_t st);
@@ -1665,6 +1667,22 @@ int inr_rescale2d_linear(float* out, const float* in, int n_images, int height, 
     INR_REQUIRE((long long)height * width < (1ll << 31) && (long long)out_height * out_width < (1ll << 31), INR_E_INVALID,
                 "inr_rescale2d_linear: image too large");
     return launch_rescale_linear(out, in, n_images, height, width, out_height, out_width, (hipStream_t)stream);
+}
+
+size_t inr_resize_z_cubic_workspace_bytes(int64_t n_lines, int n_in) {
+    return resize_z_workspace_doubles(n_lines > 0 ? n_lines : 1, n_in > 0 ? n_in : 1) * sizeof(double);
+}
+
+int inr_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+    INR_REQUIRE(out && in, INR_E_INVALID, "inr_resize_z_cubic: null pointer");
+    INR_REQUIRE(n_lines >= 1 && n_lines < (1ll << 31) && n_in >= 1 && n_out >= 1, INR_E_INVALID,
+                "inr_resize_z_cubic: bad sizes (n_lines=%lld, n_in=%d, n_out=%d)", (long long)n_lines, n_in, n_out);
+    INR_REQUIRE(n_in >= 4, INR_E_INVALID,
+                "inr_resize_z_cubic: a not-a-knot cubic spline needs at least 4 samples per line (got %d)", n_in);
+    INR_REQUIRE(workspace && workspace_bytes >= inr_resize_z_cubic_workspace_bytes(n_lines, n_in), INR_E_WORKSPACE,
+                "inr_resize_z_cubic: workspace too small");
+    return launch_resize_z_cubic(out, in, n_lines, n_in, n_out, (double*)workspace, (hipStream_t)stream);
 }
 
 int inr_auto_erd(float* accept, const double* values, const float* erd_map, int64_t n_pixels, int n_acquisitions, int rule,

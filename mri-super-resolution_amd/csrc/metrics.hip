@@ -328,6 +328,62 @@ int launch_rescale_linear(float* out, const float* in, int nimg, int H, int W, i
     return 0;
 }
 
+// ---- through-plane spline baseline: SRDWI.py:132-141 resize_array(arr, n_out), i.e. scipy interp1d(linspace(0, 1, n_in), y,
+// kind='cubic') at linspace(0, 1, n_out) -- make_interp_spline(k=3) with not-a-knot ends -- along the contiguous last axis.
+// With c_i = h^2 s''(x_i) the interior conditions read c_{i-1} + 4 c_i + c_{i+1} = 6 (y_{i-1} - 2 y_i + y_{i+1}), i = 1..n-2; the
+// not-a-knot ends (s''' continuous at x_1 and x_{n-2}) give c_0 = 2 c_1 - c_2 and c_{n-1} = 2 c_{n-2} - c_{n-3}, which turn rows 1
+// and n-2 into 6 c_1 = r_1 and 6 c_{n-2} = r_{n-2}.  That tridiagonal system is the same for every line: its Thomas factor (the
+// modified super-diagonal) sits in LDS, and each thread sweeps one line in fp64 with its right-hand side / solution in the
+// workspace, stored [i][line] so that neighbouring threads touch neighbouring doubles.
+__global__ void __launch_bounds__(256) resize_z_cubic_kernel(double* __restrict__ out, const double* __restrict__ in,
+                                                             double* __restrict__ c, int64_t n_lines, int n_in, int n_out) {
+    extern __shared__ double cp[];   // [n_in]: cp[i] = super-diagonal / pivot of row i after elimination
+    const int last = n_in - 2;       // rows 1..last of the reduced system
+    if (threadIdx.x == 0) {
+        cp[1] = 0.0;
+        for (int i = 2; i < last; ++i) cp[i] = 1.0 / (4.0 - cp[i - 1]);
+    }
+    __syncthreads();
+    const int64_t line = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (line >= n_lines) return;
+    const double* y = in + line * n_in;
+    double* ol = out + line * n_out;
+    auto C = [&](int i) -> double& { return c[(int64_t)i * n_lines + line]; };
+    auto D = [&](int i) { return y[i - 1] - 2.0 * y[i] + y[i + 1]; };
+    // forward sweep, C(i) <- eliminated right-hand side: rows 1 and `last` are 6 c_i = 6 D_i; the rows between have the
+    // sub-diagonal 1 and the pivot 4 - cp[i-1]
+    C(1) = D(1);
+    for (int i = 2; i < last; ++i) C(i) = (6.0 * D(i) - C(i - 1)) * cp[i];
+    C(last) = D(last);
+    // back substitution, C(i) <- c_i; then the not-a-knot ends
+    for (int i = last - 1; i >= 1; --i) C(i) -= cp[i] * C(i + 1);
+    C(0) = 2.0 * C(1) - C(2);
+    C(last + 1) = 2.0 * C(last) - C(last - 1);
+    // evaluation at numpy's linspace(0, 1, n_out): o * (1 / (n_out - 1)), the last point exactly 1
+    const double step = n_out > 1 ? 1.0 / (double)(n_out - 1) : 0.0;
+    for (int o = 0; o < n_out; ++o) {
+        const double u = (o == n_out - 1 && n_out > 1 ? 1.0 : o * step) * (double)(n_in - 1);
+        int j = (int)floor(u);
+        j = j < 0 ? 0 : (j > n_in - 2 ? n_in - 2 : j);
+        const double a = u - j, b = 1.0 - a;
+        ol[o] = b * y[j] + a * y[j + 1] + ((b * b * b - b) * C(j) + (a * a * a - a) * C(j + 1)) / 6.0;
+    }
+}
+
+constexpr int RESIZE_Z_MAX_IN = 8192;   // the Thomas factor, n_in doubles, fits the 64 KiB of dynamic LDS
+
+size_t resize_z_workspace_doubles(int64_t n_lines, int n_in) { return (size_t)n_lines * (size_t)n_in; }
+
+int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, double* ws, hipStream_t st) {
+    INR_REQUIRE(n_in >= 4 && n_in <= RESIZE_Z_MAX_IN, INR_E_INVALID, "inr_resize_z_cubic: 4 to %d samples per line (got %d)",
+                RESIZE_Z_MAX_IN, n_in);
+    ProfScope ps(KC_OTHER, st);
+    hipLaunchKernelGGL(resize_z_cubic_kernel, dim3((unsigned)((n_lines + 255) / 256)), dim3(256), (size_t)n_in * sizeof(double), st,
+                       out, in, ws, n_lines, n_in, n_out);
+    INR_LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_adc(float* out, const float* data, const float* bvals, int64_t npix, int nb, hipStream_t st) {
     if (npix == 0) return 0;
     ProfScope ps(KC_OTHER, st);

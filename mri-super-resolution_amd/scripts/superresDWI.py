@@ -12,7 +12,17 @@ flags with the same defaults: ``--number_of_epochs 2500 --pertubation_epochs 10 
     acquisition products, the mean image, the INR fit, the PerturbNet phase (superresDWI.py:44-156);
   * any ``.mat`` holding one volume [X, Y, Z] or [X, Y, Z, b] (e.g. ``anon_data/patNN_mean_b0.mat``, key ``data_mean_b0``):
     the same fit and evaluation without a PerturbNet phase (there are no single acquisitions to perturb towards).
-Plots (superresDWI.py:164-233) are outside the build's scope.
+Two optional products of the same fit (default off, so a plain run writes exactly the files above):
+  * ``--transverse_length T``: through-plane super-resolution (superresDWI.py:217-241; the reference hard-codes T = 100).
+    ``coronal.mat`` holds ``coronal_sr`` [2R, 2R, T] -- the INR on a (2R, 2R, T, 1) grid, b index 0, NOT clamped
+    (superresDWI.py:221) --, ``coronal_spline`` [R, R, T] -- the not-a-knot cubic spline of the HR ROI along z,
+    ``resize_array(mean_img[..., 0], T)`` (SRDWI.py:132-141) on the device -- and ``transverse_length``; ``coronal.npy`` holds
+    ``coronal_sr``.  Needs >= 4 slices (the cubic spline's minimum); ``metrics.json`` gains ``t_coronal_s``.
+  * ``--adc``: ``adc.mat`` with ``adc_sr``, ``adc_spline``, ``adc_hr`` [2R, 2R, Z] and ``b`` (superresDWI.py:189-206): per slice,
+    calculate_ADC of the x2 SR volume, of the x4 spline of the LR ROI and of the x2 spline of the HR ROI, each b-image
+    multiplied back by ``maxes[b, 1]`` (TE index 1; for a plain volume the per-b maxima it was divided by).  Needs >= 2
+    distinct b-values.
+R = roi_end - roi_start.  Plots (superresDWI.py:164-233) are outside the build's scope.
 """
 from __future__ import annotations
 
@@ -49,6 +59,11 @@ def build_parser():
     p.add_argument("--scale", type=float, default=0.5, help="sigma of the Gaussian Fourier features")
     p.add_argument("--learning_rate", type=float, default=1e-4)
     p.add_argument("--seed", type=int, default=None, help="seeds numpy (Fourier matrix) and torch (weights); default: unseeded")
+    p.add_argument("--transverse_length", type=int, default=0,
+                   help="also write coronal.mat / coronal.npy: the INR and a cubic spline on T slices along z (superresDWI.py:"
+                        "217-241, where T = 100 is hard-coded); default 0 = off")
+    p.add_argument("--adc", action="store_true",
+                   help="also write adc.mat: ADC maps of SR, spline and HR (superresDWI.py:189-206); needs >= 2 b-values")
     return p
 
 
@@ -59,6 +74,13 @@ def _patient_id(path):
 
 def load_input(path, key=None):
     """-> (mean_img [X, Y, Z, B] float64, acquisitions or None, bvalues, maxes or None)."""
+    return load_input_and_scale(path, key)[:4]
+
+
+def load_input_and_scale(path, key=None):
+    """``load_input`` plus the per-b factors [B] that turn ``mean_img`` back into signal for the ADC maps: ``maxes[:, 1]``
+    (TE index 1, superresDWI.py:193-195; None when ``hybrid_raw`` has a single TE) or, for a plain volume, the per-b maxima it
+    was divided by."""
     data = matio.loadmat(path)
     if key is None and "hybrid_raw" in data:
         key = "hybrid_raw"
@@ -74,22 +96,24 @@ def load_input(path, key=None):
         norm = [[raw[b][te] / maxes[b, te] for te in range(len(raw[b]))] for b in range(len(raw))]
         acq = drivers.acquisition_products(norm)                       # [X, Y, Z, B, K]
         bvals = np.asarray(data["b"], np.float64).reshape(-1) if "b" in data else np.arange(acq.shape[3], dtype=np.float64)
-        return acq.mean(axis=-1), acq, bvals, maxes
+        return acq.mean(axis=-1), acq, bvals, maxes, (maxes[:, 1] if maxes.shape[1] > 1 else None)
     vol = np.asarray(arr, np.float64)
     if vol.ndim == 3:
         vol = vol[..., None]
-    vol = vol / vol.reshape(-1, vol.shape[-1]).max(axis=0)             # per-b normalisation (superresDWI.py:50-55)
+    per_b_max = vol.reshape(-1, vol.shape[-1]).max(axis=0)
+    vol = vol / per_b_max                                                # per-b normalisation (superresDWI.py:50-55)
     bvals = np.asarray(data["b"], np.float64).reshape(-1) if "b" in data else np.zeros(vol.shape[-1])
-    return vol, None, bvals, None
+    return vol, None, bvals, None, per_b_max
 
 
 def run_patient(path, pt_id, args):
     out_dir = os.path.join(args.output_address, f"pat{pt_id}")
     os.makedirs(out_dir, exist_ok=True)
-    mean_img, acq, bvalues, maxes = load_input(path, args.key)
+    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key)
     r0, r1 = args.roi_start, args.roi_end
     if r1 > min(mean_img.shape[:2]) or r0 < 0 or r1 - r0 < 14:
         raise ValueError(f"ROI {r0}:{r1} does not fit the {mean_img.shape[:2]} slices (SSIM needs >= 7 x 7 LR pixels)")
+    _check_optional_outputs(args, path, mean_img, bvalues, signal_scale)
     if args.seed is not None:
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)
@@ -145,6 +169,12 @@ def run_patient(path, pt_id, args):
         "psnr_spline_db": float(metrics.psnr(hs, sp, 1.0)),
         "ssim_sr_mean": float(ssim_sr[okn].mean()), "ssim_spline_mean": float(ssim_spline[okn].mean()),
     }
+    if args.transverse_length:
+        coronal, summary["t_coronal_s"] = _coronal(INR, B, mean_img, test_shape, args)
+        matio.savemat(os.path.join(out_dir, "coronal.mat"), coronal)
+        np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
+    if args.adc:
+        matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale))
     rec_h, sr_h = recon.cpu().numpy(), SR_recon.cpu().numpy()
     out_vars = {"recon": rec_h, "SR_recon": sr_h, "b": np.asarray(bvalues, np.float64)}
     if maxes is not None:
@@ -155,6 +185,52 @@ def run_patient(path, pt_id, args):
         json.dump(summary, fh, indent=1)
     print(json.dumps(summary))
     return summary
+
+
+def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
+    """Refuses --transverse_length / --adc on an input that cannot give them, before the fit starts."""
+    nz, nb = mean_img.shape[2], mean_img.shape[3]
+    if args.transverse_length < 0:
+        raise ValueError(f"--transverse_length must be >= 0 (got {args.transverse_length})")
+    if args.transverse_length and nz < 4:
+        raise ValueError(f"--transverse_length: the through-plane cubic spline needs at least 4 slices (scipy interp1d "
+                         f"kind='cubic'); {path} has {nz}")
+    if args.adc:
+        if nb < 2:
+            raise ValueError(f"--adc needs at least 2 b-values; {path} has {nb}")
+        if len(bvalues) != nb or np.ptp(bvalues) == 0:
+            raise ValueError(f"--adc needs {nb} distinct b-values (variable 'b'); {path} gives {list(bvalues)}")
+        if signal_scale is None:
+            raise ValueError(f"--adc rescales by maxes[b, 1] (TE index 1, superresDWI.py:193); {path} has a single TE")
+
+
+def _coronal(INR, B, mean_img, test_shape, args):
+    """superresDWI.py:217-241: the INR on a (2R, 2R, T, 1) grid -- the size-1 last axis puts b at -1, b index 0 -- without the
+    clamp (:221), and the cubic spline of the HR ROI's b = 0 image along z (:231; the spline runs per line, so cropping the ROI
+    first changes nothing).  -> (variables of coronal.mat, seconds)."""
+    T = int(args.transverse_length)
+    r0, r1 = args.roi_start, args.roi_end
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    sr = inr.reconstruct(INR, (test_shape[0], test_shape[1], T, 1), B, clamp_min=None)[..., 0]
+    hr0 = torch.from_numpy(np.ascontiguousarray(mean_img[r0:r1, r0:r1, :, 0], dtype=np.float64)).cuda()
+    spline = baselines.resize_z(hr0, T)
+    torch.cuda.synchronize()
+    t = time.perf_counter() - t0
+    return {"coronal_sr": sr.cpu().numpy(), "coronal_spline": spline.cpu().numpy(), "transverse_length": T}, t
+
+
+def _adc_maps(recon, hs, bvalues, signal_scale):
+    """superresDWI.py:189-206 for all slices in one batch: every b-image times maxes[b, 1], then calculate_ADC per pixel, of
+    the x2 SR volume, the x4 spline of the LR ROI and the x2 spline of the HR ROI.  ``hs`` is the HR ROI as [Z, B, R, R]."""
+    scale = torch.as_tensor(np.asarray(signal_scale, np.float32), device=recon.device)
+    to_xyzb = lambda t: t.permute(2, 3, 0, 1).contiguous()                       # [Z, B, 2R, 2R] -> [2R, 2R, Z, B]
+    stacks = {"adc_sr": recon,
+              "adc_spline": to_xyzb(baselines.rescale(hs[:, :, ::2, ::2].contiguous(), 4)),
+              "adc_hr": to_xyzb(baselines.rescale(hs, 2))}
+    out = {k: metrics.calculate_ADC_device(bvalues, (v * scale).contiguous()).cpu().numpy() for k, v in stacks.items()}
+    out["b"] = np.asarray(bvalues, np.float64)
+    return out
 
 
 SUMMARY_KEYS = ("job", "n_coords", "steps", "t_fit_s", "t_recon_s", "train_voxels_per_s", "final_loss", "psnr_db",
