@@ -7,7 +7,7 @@
 #include <mutex>
 #include <vector>
 
-#include "common.h"
+#include "internal.h"
 
 namespace inr {
 
@@ -64,170 +64,10 @@ void prof_end(int kc, hipStream_t s) {
     g_prof.open[kc] = nullptr;
 }
 
-// ---- kernels implemented in gemm_f32.hip / kernels.hip ------------------------------------------------
-int gemm_sine_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n,
-                      int in_f, int out_f, float omega, hipStream_t stream, const H3Args* h3 = nullptr);
-int input_grad_colsum_rows(int64_t n);
-int gemm_input_grad(float* dz_prev, const float* dz, const float* W, const float* mul, int64_t n, int in_f,
-                    int out_f, float* colsum_slab, int* slab_rows, hipStream_t stream, const H3Args* h3 = nullptr);
-size_t h3_planes_bytes(long long weights);
-int h3_tensor_amax(unsigned* out, const float* x, long long n, hipStream_t stream, unsigned floor_bits = 0);
-int h3_weight_split(const float* const* W, const int* out_f, const int* in_f, int layers, _Float16* planes,
-                    unsigned* amax, unsigned* zero_slots, int n_zero, hipStream_t stream);
-int param_grad_splits(int64_t n, int in_f, int out_f);
-// pre-split (HL32) path: gemm_hp.inc
-bool hp_head_ok(int hidden);
-bool hp_row_head_ok(int64_t n, int hidden, int in_f);
-int hp_row_head_rows(int64_t n);
-int hp_sine_forward_head(char* dz_hl, const char* x_hl, const char* W_hl, const float* bias, int64_t n, int in_f, int out_f, float omega,
-                         HpScale sa, HpScale sb, HpScale dz_so, const float* head_w, const float* head_b, const float* target,
-                         const float* weight, int64_t count_total, float* slab_b, float* slab_w, float* part_loss, float* part_g,
-                         unsigned* amax_out, hipStream_t stream);
-int gemm_build_flags();
-size_t hp_prep_part_bytes();
-int hp_weight_prep(const float* const* W, const int* out_f, const int* in_f, int layers, char* planes, unsigned* slots,
-                   unsigned* part, float* head_bound, const float* head_W, const float* head_b, int hidden, const unsigned* tmax,
-                   const unsigned* wtmax, float inv_count, float omega, hipStream_t stream, const float* const* bias = nullptr,
-                   const float* layer_omega = nullptr, float* act_bound = nullptr, const unsigned* x_amax = nullptr);
-int hp_convert(char* out, const float* x, long long rows, int cols, HpScale sc, hipStream_t stream);
-int hp_unconvert(float* out, const char* x, long long rows, int cols, HpScale sc, hipStream_t stream);
-int hp_sine_forward(char* act_hl, float* dact, const char* x_hl, const char* W_hl, const float* bias, int64_t n, int in_f,
-                    int out_f, float omega, HpScale sa, HpScale sb, int reverse_m, hipStream_t stream, bool z_only = false,
-                    HpScale so = HpScale{});
-bool hp_z_stash_ok(int in_f);
-bool hp_grid_fourier_ok(int m, int dim);
-int hp_grid_fourier_hl(char* x_hl, unsigned* x_amax, const int64_t* shape, int dim, int64_t row_begin, int64_t n_rows, const float* B,
-                       int m, hipStream_t stream);
-bool hp_fused_forward_ok(int in_f, int hidden, int n_sine);
-int hp_fused_forward(float* y, const char* x_hl, const unsigned* x_amax, int64_t n, int in_f, int hidden, int n_sine,
-                     const char* const* W_hl, const float* const* bias, const unsigned* const* w_amax, float first_omega,
-                     float hidden_omega, const float* head_W, const float* head_b, int use_clamp, float clamp_min,
-                     hipStream_t stream);
-extern tune_int g_hp_zhead;
-extern tune_int g_hp_head_rows;
-extern tune_int g_rams_epi_fuse;       // key 24 (rams.hip)
-extern tune_int g_reduce_onepass;      // key 25 (kernels.hip)
-extern tune_int g_rams_pregate_min_vox;   // key 26 (rams.hip)
-extern tune_int g_hp_narrow_max_tiles;   // key 29 (gemm_f32.hip)
-extern tune_int g_hp_row_head, g_hp_row_head_min_tiles;   // keys 30, 31 (gemm_f32.hip: the head step fused into the last sine layer)
-extern tune_int g_hp_row, g_hp_row_min_tiles;   // keys 27, 28 (gemm_f32.hip: the row-owning 128 x 512 kernel)
-extern tune_int g_hp_grid_cap;   // key 32 (gemm_f32.hip: test-only cap on the persistent grids)
-extern tune_int g_hp_head_min_rows;   // key 21 (gemm_f32.hip)
-int hp_input_grad_max_rows(int64_t n);
-int hp_input_grad(char* dzprev_hl, const char* dz_hl, const char* WT_hl, const float* mul, int64_t n, int in_f, int out_f,
-                  float* colsum_slab, int* colsum_rows, unsigned* amax_out, HpScale sa, HpScale sb, HpScale so,
-                  hipStream_t stream);
-int64_t hp_head_blocks(int64_t n);
-int hp_param_grad_splits(int64_t n, int in_f, int out_f);
-int hp_param_grad_slabs(float* slabs, int splits, const char* dz_hl, const char* x_hl, int64_t n, int in_f, int out_f,
-                        HpScale sa, HpScale sb, hipStream_t stream);
-int hp_param_grad_multi_max();
-int hp_param_grad_multi(const HpParamGradJob* jobs, int njobs, int64_t n, hipStream_t stream);
-int hp_head_forward(float* y, const char* a_hl, const float* W, const float* bias, int64_t n, int hidden, int use_clamp,
-                    float clamp_min, hipStream_t stream, bool from_z = false, float omega = 0.f, HpScale sa = HpScale{});
-int hp_head_step(char* dz_hl, float* slab_b, float* slab_w, float* part_loss, float* part_g, const char* a_hl,
-                 const float* dact, const float* W, const float* bias, const float* t, const float* wgt, int64_t n, int hidden,
-                 int64_t count_total, unsigned* amax_out, HpScale so, hipStream_t stream, bool from_z = false,
-                 float omega = 0.f, const float* g_ext = nullptr, HpScale sa = HpScale{});
-int hp_head_bound_ext(float* head_bound, const unsigned* gmax, const float* head_W, int hidden, float omega, hipStream_t stream);
-int gemm_param_grad_slabs(float* slabs, int splits, const float* dz, const float* x, int64_t n, int in_f,
-                          int out_f, hipStream_t stream, const H3Args* h3 = nullptr);
-int launch_mgrid(float* out, const int64_t* shape, int dim, int64_t row_begin, int64_t n_rows, hipStream_t st);
-int launch_fourier(float* out, const float* x, const int64_t* shape, int dim, int64_t row_begin, int64_t n_rows,
-                   const float* B, int m, hipStream_t st);
-int launch_head_forward(float* y, const float* a, const float* W, const float* b, int64_t n, int hidden,
-                        int out_f, int use_clamp, float clamp_min, hipStream_t st, float* dy = nullptr);
-int gemm_tanh_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n, int in_f,
-                      int out_f, float scale, hipStream_t stream);
-int mse_blocks(int64_t count);
-int launch_mse(float* gy, float* loss, const float* y, const float* t, const float* w, int64_t count,
-               float* partial, hipStream_t st, int64_t count_total = 0);
-int launch_head_dz(float* dz, const float* gy, const float* W, const float* dact, int64_t n, int hidden,
-                   int out_f, hipStream_t st);
-int64_t colsum_ws_floats(int64_t n, int C, int G);
-int launch_colsum(float* out, const float* X, const float* g, int64_t n, int C, int G, float* slab,
-                  hipStream_t st);
-int64_t reduce_tmp_floats(int64_t nslabs, int64_t len);
-int launch_reduce_slabs(float* out, const float* slab, int nslabs, int64_t len, float* tmp, hipStream_t st);
-bool head_fused_ok(int hidden, int out_f, const void* a, const void* b, const void* c, const void* d);
-int64_t head_fused_blocks(int64_t n);
-int launch_head_bwd_fused(float* dz, float* slab_b, float* slab_w, const float* gy, const float* W, const float* a,
-                          const float* dact, int64_t n, int hidden, hipStream_t st, unsigned* amax_out = nullptr);
-bool head_step_fused_ok(int hidden, int out_f, const void* a, const void* b, const void* c, const void* d);
-int launch_head_step_fused(float* dz, float* slab_b, float* slab_w, float* part_loss, float* part_g, const float* a,
-                           const float* dact, const float* W, const float* bias, const float* t, const float* wgt,
-                           int64_t n, int hidden, int64_t count_total, hipStream_t st, unsigned* amax_out);
-int launch_finish_sum(float* out, const float* partial, int nparts, float scale, hipStream_t st);
-int launch_adam(float* p, const float* g, float* m, float* v, int64_t count, int64_t step, double lr, double b1,
-                double b2, double eps, hipStream_t st);
-int launch_sincos_probe(float* s, float* c, const float* x, int64_t n, hipStream_t st);
-int launch_mul(float* out, const float* a, const float* b, int64_t count, hipStream_t st);
-int launch_acquisition_products(float* out, const float* r0, const float* r1, const float* r2, const float* r3, int64_t nvox,
-                                int n1, int n2, int n3, hipStream_t st);
-int metric_workspace_doubles(int nimg);
-int launch_psnr(double* out, const float* x, const float* y, int nimg, int64_t per_image, double data_range,
-                double* ws, hipStream_t st);
-int launch_ssim(double* out, const float* x, const float* y, int nimg, int H, int W, int win, double data_range,
-                int use_mask, float mask_thr, double* ws, hipStream_t st);
-int launch_adc(float* out, const float* data, const float* bvals, int64_t npix, int nb, hipStream_t st);
-int launch_rescale_linear(float* out, const float* in, int nimg, int H, int W, int OH, int OW, hipStream_t st);
-size_t resize_z_workspace_doubles(int64_t n_lines, int n_in);
-int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, double* ws, hipStream_t st);
-int launch_auto_erd(float* accept, const double* values, const float* erd_map, int64_t npix, int n, int rule, hipStream_t st);
-int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, const double* signals, int64_t n,
-                      hipStream_t st);
-void set_hybrid_variant(int v);
-size_t rams_conv3d_wgrad_ws_floats(long long nvox);
-int rams_conv3d_forward(float* y, const float* x, const float* w, const float* bias, int B, int D1, int D2, int D3, int pad,
-                        int relu, hipStream_t st);
-int rams_conv3d_dgrad_same(float* dx, const float* dy, const float* w, int B, int D1, int D2, int D3, float* ws, hipStream_t st);
-int rams_conv3d_wgrad(float* gw, float* gb, const float* x, const float* dy, int B, int D1, int D2, int D3, int pad, float* ws,
-                      hipStream_t st);
-int rams_conv3d_wgrad_auto(float* gw, float* gb, const float* x, const float* dy, int B, int D1, int D2, int D3, int pad, float* ws,
-                      hipStream_t st);
-int launch_shift_loss_grad(double* loss, float* grad, const float* y_true, const float* y_pred, const float* mask,
-                           const float* upstream, int nimg, int size, int border, double* ws, hipStream_t st);
-int launch_shift_loss(double* out, const float* y_true, const float* y_pred, const float* mask, int nimg, int size,
-                      int border, int mode, double* ws, hipStream_t st);
-long long rams_param_floats(const inr_rams_desc_t* d);
-long long rams_train_param_floats(const inr_rams_desc_t* d);
-int rams_train_param_offsets(const inr_rams_desc_t* d, int64_t* offsets, int max_layers);
-size_t rams_train_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W);
-int rams_train_grads(const inr_rams_desc_t* d, const float* raw, float* raw_grad, const float* x, const float* y_true,
-                     const float* mask, double* loss, float* pred, int B, int H, int W, float* ws, hipStream_t st);
-size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W);
-int rams_forward_impl(const inr_rams_desc_t* d, const float* params, const float* x, float* out, int B, int H, int W,
-                      int clip_round, float* ws, hipStream_t st);
-bool small_path_ok(const inr_siren_desc_t* d, int64_t n);
-size_t small_workspace_floats(const inr_siren_desc_t* d, int64_t n, long long P);
-bool small_multi_ok(const inr_siren_desc_t* d, int64_t n);
-size_t small_multi_workspace_floats(const inr_siren_desc_t* d, int64_t n, long long P);
-int small_fit_multi(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, float* params,
-                    float* grads, float* m, float* v, const float* x, const float* targets, const float* weights, int n_acq,
-                    int first_acq, int64_t n, int64_t first_step, int n_steps, double lr, double b1, double b2, double eps,
-                    float* losses, float* ws, hipStream_t st);
-int small_batch_per_launch(const inr_siren_desc_t* d, int64_t n);
-int small_fit_batch(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, int n_fits,
-                    float* const* params, float* const* grads, float* const* m, float* const* v, const float* x,
-                    const float* const* targets, const float* const* weights, const int* n_acq, const int* first_acq, int64_t n,
-                    int64_t first_step, int n_steps, double lr, double b1, double b2, double eps, float* const* losses,
-                    void* const* ws, hipStream_t st);
-int small_fit_step(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, float* params,
-                   float* grads, float* m, float* v, const float* x, const float* target, const float* weight, int64_t n,
-                   int64_t step, double lr, double b1, double b2, double eps, float* loss_out, float* ws, hipStream_t st);
-extern tune_int g_force_generic;
-extern tune_int g_small_rows, g_small_spin_limit;
-extern tune_int g_rams_h3, g_rams_force_lds, g_rams_lds_waves;
-tune_int g_small_multi{1};  // small networks: 1 = persistent multi-step kernel (default), 0 = two launches per step
-extern tune_int g_mfma16;
-extern tune_int g_h3;
-extern tune_int g_h3_wide;
-static tune_int g_h3_serpentine{1};
-static tune_int g_hp{1};  // pre-split (HL32) GEMM path inside the fused entry points; inr_debug_set(7, 0) falls back to gemm_h3
-extern char* g_h3_scratch;
-extern unsigned long long* g_stamps;
-extern tune_int g_stamp_class, g_stamp_nth;
-extern tune_int g_hp_persistent, g_hp_stagger, g_hp_narrow, g_hp_fused_fwd;
+// ---- switches only this file reads (the others: internal.h) ------------------------------------------------------------------------
+static tune_int g_small_multi{1};  // key 12, small networks: 1 = persistent multi-step kernel (default), 0 = two launches per step
+static tune_int g_h3_serpentine{1};   // key 5
+static tune_int g_hp{1};  // key 7: pre-split (HL32) GEMM path inside the fused entry points; inr_debug_set(7, 0) falls back to gemm_h3
 
 // ---- shared helpers ---------------------------------------------------------------------------------
 static const int64_t MAX_ROWS = (1ll << 31) - 256;
@@ -242,24 +82,25 @@ static int check_desc(const inr_siren_desc_t* d) {
 
 struct Layout {
     int n_sine;                      // 1 + hidden_layers
-    std::vector<int64_t> w_off, b_off;  // per layer, head last
+    std::vector<long long> w_off, b_off;  // per layer, head last (long long: what siren_small.hip and FinalizeSeg take)
     std::vector<int> fan_in, fan_out;
-    int64_t total;
+    long long total;
 };
+static float layer_omega(const inr_siren_desc_t* d, int l) { return l == 0 ? d->first_omega : d->hidden_omega; }
 
 static Layout make_layout(const inr_siren_desc_t* d) {
     Layout L;
     L.n_sine = 1 + d->hidden_layers;
-    int64_t off = 0;
+    long long off = 0;
     for (int l = 0; l <= L.n_sine; ++l) {
         const int fin = (l == 0) ? d->in_features : d->hidden_features;
         const int fout = (l == L.n_sine) ? d->out_features : d->hidden_features;
         L.fan_in.push_back(fin);
         L.fan_out.push_back(fout);
         L.w_off.push_back(off);
-        off += (int64_t)round_up((size_t)fin * fout, 4);
+        off += (long long)round_up((size_t)fin * fout, 4);
         L.b_off.push_back(off);
-        off += (int64_t)round_up((size_t)fout, 4);
+        off += (long long)round_up((size_t)fout, 4);
     }
     L.total = off;
     return L;
@@ -305,111 +146,102 @@ static int input_grad(float* dz_prev, float* gb_prev, const float* dz, const flo
     return launch_colsum(gb_prev, dz_prev, nullptr, n, in_f, 1, ws, st);
 }
 
-// ---- split-fp16 GEMM context of a network (gemm_h3.inc): weight planes + scale slots inside the caller's workspace ----
-// slots: [l] = max|W_l|, [8 + l] = max|dz_l| (both rebuilt every step), [24] = max|x|
-struct H3Ctx {
-    bool on = false;
-    _Float16* planes = nullptr;
-    unsigned* slots = nullptr;
+// ---- split-GEMM context of one network in one workspace ------------------------------------------------------------------------
+// A region of the caller's workspace: the scale slots (common.h: HpSlots), the scratch of the per-step weight statistics, then 8
+// bytes per weight, layer after layer.  The split-fp16 path (gemm_h3.inc) keeps four fp16 planes per layer there (hi, lo, hiT,
+// loT), the pre-split path (gemm_hp.inc) two HL32 images ([out][in], then [in][out]).
+struct SplitCtx {
+    bool on = false;                    // false: the network takes the fp32 kernels, nothing below is set
+    HpSlots slots;
     unsigned* part = nullptr;           // scratch of the per-step weight statistics (gemm_hp.inc)
-    std::vector<long long> plane_off;   // halves, per sine layer
+    char* planes = nullptr;
+    long long w_first[HpSlots::MAX_LAYERS], w_count[HpSlots::MAX_LAYERS];   // weights before sine layer l / of sine layer l
+
+    // gemm_h3.inc: fp16 planes
+    const _Float16* h3_planes(int l) const { return reinterpret_cast<const _Float16*>(planes) + 4 * w_first[l]; }
+    // gemm_hp.inc: HL32 images and the scales of the operands
+    char* w_hl(int l) const { return planes + 8 * w_first[l]; }
+    char* wT_hl(int l) const { return w_hl(l) + 4 * w_count[l]; }
+    HpScale w_scale(int l) const { HpScale s; s.meas = slots.w_max(l); s.mul = 1.f; return s; }
+    HpScale x_scale() const { HpScale s; s.meas = slots.x_max(); s.mul = 1.f; return s; }
+    // input of sine layer l: the network input (measured max|x|) or the output of layer l - 1, whose image is scaled from the
+    // a-priori bound of that layer (written by the per-step weight preparation: gemm_hp.inc, act_bound)
+    HpScale act_scale(int l) const {
+        if (l == 0) return x_scale();
+        HpScale s;
+        s.wn = slots.act_bound(l - 1);
+        s.mul = 1.f;
+        s.kmax = 40;
+        return s;
+    }
 };
 static bool h3_eligible(const Layout& L) {
-    if (!g_h3 || L.n_sine > 8) return false;
+    if (!g_h3 || L.n_sine > HpSlots::MAX_LAYERS) return false;
     for (int l = 0; l < L.n_sine; ++l)
         if (L.fan_in[l] % 32 != 0 || L.fan_out[l] % 32 != 0) return false;
     return true;
 }
-static size_t h3_ctx_bytes(const Layout& L) {
+static bool hp_eligible(const inr_siren_desc_t* d, const Layout& L) {
+    if (!g_hp || !g_h3 || g_force_generic || !h3_eligible(L)) return false;
+    return d->out_features == 1 && hp_head_ok(d->hidden_features);
+}
+static size_t split_ctx_bytes(const Layout& L) {      // (reserved whether or not the network is eligible)
     long long w = 0;
     for (int l = 0; l < L.n_sine; ++l) w += (long long)L.fan_in[l] * L.fan_out[l];
-    return round_up(256 + hp_prep_part_bytes() + h3_planes_bytes(w), 256);
+    return round_up(HpSlots::BYTES + hp_prep_part_bytes() + h3_planes_bytes(w), 256);
 }
-static H3Ctx h3_make_ctx(const Layout& L, char* region) {
-    H3Ctx c;
+// the context inside `region` (split_ctx_bytes(L) bytes) when the network is eligible, else one that is off
+static SplitCtx split_ctx(const Layout& L, char* region) {
+    SplitCtx c;
+    if (!h3_eligible(L)) return c;
     c.on = true;
-    c.slots = reinterpret_cast<unsigned*>(region);
-    c.part = reinterpret_cast<unsigned*>(region + 256);
-    c.planes = reinterpret_cast<_Float16*>(region + 256 + hp_prep_part_bytes());
-    long long off = 0;
+    c.slots.base = reinterpret_cast<unsigned*>(region);
+    c.part = reinterpret_cast<unsigned*>(region + HpSlots::BYTES);
+    c.planes = region + HpSlots::BYTES + hp_prep_part_bytes();
+    long long first = 0;
     for (int l = 0; l < L.n_sine; ++l) {
-        c.plane_off.push_back(off);
-        off += 4ll * L.fan_in[l] * L.fan_out[l];
+        c.w_first[l] = first;
+        c.w_count[l] = (long long)L.fan_in[l] * L.fan_out[l];
+        first += c.w_count[l];
     }
     return c;
 }
 // split every sine layer's weights (once per optimizer step / forward call) and zero the dz slots
-static int h3_refresh_weights(const H3Ctx& c, const Layout& L, const float* params, hipStream_t st) {
-    const float* W[8];
-    int of[8], inf[8];
-    for (int l = 0; l < L.n_sine; ++l) {
-        W[l] = params + L.w_off[l];
-        of[l] = L.fan_out[l];
-        inf[l] = L.fan_in[l];
-    }
-    return h3_weight_split(W, of, inf, L.n_sine, c.planes, c.slots, c.slots, 16, st);
+static int h3_refresh_weights(const SplitCtx& c, const Layout& L, const float* params, hipStream_t st) {
+    const float* W[HpSlots::MAX_LAYERS];
+    for (int l = 0; l < L.n_sine; ++l) W[l] = params + L.w_off[l];
+    return h3_weight_split(W, L.fan_out.data(), L.fan_in.data(), L.n_sine, reinterpret_cast<_Float16*>(c.planes), c.slots.w_max(0),
+                           c.slots.w_max(0), 2 * HpSlots::MAX_LAYERS, st);   // (w_max and dz_max are adjacent: both zeroed)
 }
-static H3Args h3_forward_args(const H3Ctx& c, const Layout& L, int l) {
+static H3Args h3_forward_args(const SplitCtx& c, int l) {
     H3Args a;
-    const long long n = (long long)L.fan_in[l] * L.fan_out[l];
-    a.a_amax = (l == 0) ? c.slots + 24 : nullptr;   // sine outputs are in [-1, 1]; the network input is whatever it is
-    a.b_amax = c.slots + l;
-    a.Bh = c.planes + c.plane_off[l];
-    a.Bl = a.Bh + n;
+    a.a_amax = (l == 0) ? c.slots.x_max() : nullptr;   // sine outputs are in [-1, 1]; the network input is whatever it is
+    a.b_amax = c.slots.w_max(l);
+    a.Bh = c.h3_planes(l);
+    a.Bl = a.Bh + c.w_count[l];
     a.reverse_m = g_h3_serpentine ? (l & 1) : 0;      // layer l+1 starts where layer l stopped writing
     return a;
 }
-static H3Args h3_input_grad_args(const H3Ctx& c, const Layout& L, int l) {
+static H3Args h3_input_grad_args(const SplitCtx& c, int l) {
     H3Args a;
-    const long long n = (long long)L.fan_in[l] * L.fan_out[l];
-    a.a_amax = c.slots + 8 + l;
-    a.b_amax = c.slots + l;
-    a.Bh = c.planes + c.plane_off[l] + 2 * n;
-    a.Bl = a.Bh + n;
-    a.amax_out = c.slots + 8 + l - 1;
+    a.a_amax = c.slots.dz_max(l);
+    a.b_amax = c.slots.w_max(l);
+    a.Bh = c.h3_planes(l) + 2 * c.w_count[l];
+    a.Bl = a.Bh + c.w_count[l];
+    a.amax_out = c.slots.dz_max(l - 1);
     // backward chain: head pass (front to back) -> dW_L (back to front) -> dX_L (front to back) -> dW_{L-1} ... : every
     // kernel starts on the rows the one before it touched last
     a.reverse_m = 0;
     return a;
 }
-static H3Args h3_param_grad_args(const H3Ctx& c, int l) {
+static H3Args h3_param_grad_args(const SplitCtx& c, int l) {
     H3Args a;
-    a.a_amax = c.slots + 8 + l;
-    a.b_amax = (l == 0) ? c.slots + 24 : nullptr;
+    a.a_amax = c.slots.dz_max(l);
+    a.b_amax = (l == 0) ? c.slots.x_max() : nullptr;
     a.reverse_m = g_h3_serpentine ? 1 : 0;
     return a;
 }
 
-
-// ---- pre-split (HL32) context: gemm_hp.inc ------------------------------------------------------------------------------
-// Shares the H3Ctx region: 256 bytes of slots, the statistics scratch, then 8 bytes per weight (HL32 [out][in], then HL32
-// [in][out] per layer).
-// slots: [l] max|W_l| bits, [8 + l] measured max|dz_l| bits, [16 + l] wnorm_l (float bits) -- all three rebuilt every step;
-// [24] max|x| (floor 1), [25] max|target|, [26] max|weight| (per call); [27] bound of the head's dz (float, every step)
-static bool hp_eligible(const inr_siren_desc_t* d, const Layout& L) {
-    if (!g_hp || !g_h3 || g_force_generic || !h3_eligible(L)) return false;
-    return d->out_features == 1 && hp_head_ok(d->hidden_features);
-}
-struct HpNet {
-    const H3Ctx* c;
-    const Layout* L;
-    char* w_hl(int l) const { return reinterpret_cast<char*>(c->planes) + 2 * c->plane_off[l]; }
-    char* wT_hl(int l) const { return w_hl(l) + 4ll * L->fan_in[l] * L->fan_out[l]; }
-    HpScale w_scale(int l) const { HpScale s; s.meas = c->slots + l; s.mul = 1.f; return s; }
-    HpScale x_scale() const { HpScale s; s.meas = c->slots + 24; s.mul = 1.f; return s; }
-    // input of sine layer l: the network input (measured max|x|) or the output of layer l - 1, whose image is scaled from the
-    // a-priori bound of that layer (slots 32 + l - 1, written by the per-step weight preparation: gemm_hp.inc, act_bound)
-    HpScale act_scale(int l) const {
-        if (l == 0) return x_scale();
-        HpScale s;
-        s.wn = reinterpret_cast<const float*>(c->slots + 32 + l - 1);
-        s.mul = 1.f;
-        s.kmax = 40;
-        return s;
-    }
-    float* act_bounds() const { return reinterpret_cast<float*>(c->slots + 32); }
-    float* head_bound() const { return reinterpret_cast<float*>(c->slots + 27); }
-};
 // this step's weights as HL32 images + their scales; with `head` (fit steps) also the a-priori bound of the head's dz
 struct HpHeadBoundArgs {
     const float* W;
@@ -418,27 +250,23 @@ struct HpHeadBoundArgs {
     const unsigned* wtmax;
     float inv_count, omega;
 };
-// x_measured: slot 24 holds max|x| of the rows this step runs on (the fit / forward entry points measure it first); false:
+// x_measured: slots.x_max() holds max|x| of the rows this step runs on (the fit / forward entry points measure it first); false:
 // the input is a coordinate grid or its Fourier features, |x| <= 1 (the dense re-sampling prepares the weights once per call,
 // before any chunk's input exists)
-static int hp_refresh_weights(const HpNet& net, const inr_siren_desc_t* d, const float* params, hipStream_t st, bool x_measured,
-                              const HpHeadBoundArgs* head = nullptr) {
-    const Layout& L = *net.L;
-    const float *W[8], *bias[8];
-    float om[8];
-    int of[8], inf[8];
+static int hp_refresh_weights(const SplitCtx& c, const inr_siren_desc_t* d, const Layout& L, const float* params, hipStream_t st,
+                              bool x_measured, const HpHeadBoundArgs* head = nullptr) {
+    const float *W[HpSlots::MAX_LAYERS], *bias[HpSlots::MAX_LAYERS];
+    float om[HpSlots::MAX_LAYERS];
     for (int l = 0; l < L.n_sine; ++l) {
         W[l] = params + L.w_off[l];
         bias[l] = params + L.b_off[l];
-        om[l] = l == 0 ? d->first_omega : d->hidden_omega;
-        of[l] = L.fan_out[l];
-        inf[l] = L.fan_in[l];
+        om[l] = layer_omega(d, l);
     }
-    return hp_weight_prep(W, of, inf, L.n_sine, reinterpret_cast<char*>(net.c->planes), net.c->slots, net.c->part,
-                          head ? net.head_bound() : nullptr, head ? head->W : nullptr, head ? head->b : nullptr,
+    return hp_weight_prep(W, L.fan_out.data(), L.fan_in.data(), L.n_sine, c.planes, c.slots, c.part,
+                          head ? c.slots.head_bound() : nullptr, head ? head->W : nullptr, head ? head->b : nullptr,
                           L.fan_in[L.n_sine], head ? head->tmax : nullptr, head ? head->wtmax : nullptr,
-                          head ? head->inv_count : 0.f, head ? head->omega : 0.f, st, bias, om, net.act_bounds(),
-                          x_measured ? net.c->slots + 24 : nullptr);
+                          head ? head->inv_count : 0.f, head ? head->omega : 0.f, st, bias, om, c.slots.act_bound(0),
+                          x_measured ? c.slots.x_max() : nullptr);
 }
 
 static size_t head_backward_ws_floats(int64_t n, int hidden, int out_f) {
@@ -658,61 +486,86 @@ int inr_siren_param_offsets(const inr_siren_desc_t* desc, int64_t* offsets) {
     return 0;
 }
 
-size_t inr_siren_forward_workspace_bytes(const inr_siren_desc_t* desc, int64_t n) {
-    if (check_desc(desc)) return 0;
-    return 2 * round_up((size_t)(n > 0 ? n : 1) * desc->hidden_features * sizeof(float), 256) +
-           h3_ctx_bytes(make_layout(desc)) + round_up((size_t)(n > 0 ? n : 1) * desc->in_features * sizeof(float), 256);
+// ---- inference workspace: [feature buffer] | two activation buffers | split-GEMM context | HL32 image of the input --------------------
+// The ONE place that sizes and carves it: inr_siren_forward (no feature buffer: x is the caller's) and inr_siren_reconstruct (one
+// chunk of grid features).  workspace == nullptr: `total` only.
+struct InferView {
+    size_t total = 0;
+    float* feats = nullptr;             // reconstruct only: fp32 features of one chunk
+    float* buf[2] = {nullptr, nullptr}; // sine layers write them in turn
+    SplitCtx ctx;
+    char* xhl = nullptr;                // HL32 image of the input rows (pre-split path)
+    bool hp = false;                    // the pre-split kernels serve this network
+};
+static InferView infer_view(const inr_siren_desc_t* d, const Layout& L, int64_t rows, bool with_feats, void* workspace) {
+    InferView v;
+    const size_t feats_b = round_up((size_t)rows * d->in_features * sizeof(float), 256);
+    const size_t act_b = round_up((size_t)rows * d->hidden_features * sizeof(float), 256);
+    const size_t act_off = with_feats ? feats_b : 0;
+    const size_t ctx_off = act_off + 2 * act_b;
+    const size_t xhl_off = ctx_off + split_ctx_bytes(L);
+    v.total = xhl_off + feats_b;
+    if (!workspace) return v;
+    char* base = (char*)workspace;
+    if (with_feats) v.feats = (float*)base;
+    v.buf[0] = (float*)(base + act_off);
+    v.buf[1] = (float*)(base + act_off + act_b);
+    v.ctx = split_ctx(L, base + ctx_off);
+    v.xhl = base + xhl_off;
+    v.hp = v.ctx.on && hp_eligible(d, L);
+    return v;
 }
 
+size_t inr_siren_forward_workspace_bytes(const inr_siren_desc_t* desc, int64_t n) {
+    if (check_desc(desc)) return 0;
+    return infer_view(desc, make_layout(desc), n > 0 ? n : 1, false, nullptr).total;
+}
+
+// xhl_ready: the caller has already written the HL32 image of the input and its scale slot (hp_grid_fourier_hl); x unused
+// amax_ready: the caller has measured max|x| into its slot (inr_siren_forward: before the weight preparation, which needs it)
 static int siren_forward_impl(const inr_siren_desc_t* d, const Layout& L, const float* params, const float* x,
-                              int64_t n, float* y, int use_clamp, float clamp_min, float* buf0, float* buf1,
-                              hipStream_t st, const H3Ctx* h3 = nullptr, char* xhl = nullptr, bool xhl_ready = false,
-                              bool amax_ready = false) {
-    // xhl_ready: the caller has already written the HL32 image of the input and its scale slot (hp_grid_fourier_hl); x unused
-    // amax_ready: the caller has measured max|x| into slot 24 (inr_siren_forward: before the weight preparation, which needs it)
+                              int64_t n, float* y, int use_clamp, float clamp_min, const InferView& v, hipStream_t st,
+                              bool xhl_ready = false, bool amax_ready = false) {
+    const SplitCtx& c = v.ctx;
     const float* cur = x;
-    float* bufs[2] = {buf0, buf1};
-    if (h3 && h3->on && !xhl_ready && !amax_ready) {
-        if (int rc = h3_tensor_amax(h3->slots + 24, x, (long long)n * L.fan_in[0], st, 0x3f800000u)) return rc;
+    if (c.on && !xhl_ready && !amax_ready) {
+        if (int rc = h3_tensor_amax(c.slots.x_max(), x, (long long)n * L.fan_in[0], st, 0x3f800000u)) return rc;
     }
-    if (h3 && h3->on && xhl) {   // pre-split path: every activation lives in HBM as HL32 (gemm_hp.inc)
-        const HpNet net{h3, &L};
+    if (v.hp) {   // pre-split path: every activation lives in HBM as HL32 (gemm_hp.inc)
         if (!xhl_ready) {
-            if (int rc = hp_convert(xhl, x, n, L.fan_in[0], net.x_scale(), st)) return rc;
+            if (int rc = hp_convert(v.xhl, x, n, L.fan_in[0], c.x_scale(), st)) return rc;
         }
         if (hp_fused_forward_ok(L.fan_in[0], d->hidden_features, L.n_sine)) {
             // every sine layer and the head in ONE launch, the activations of a 64-row panel never leaving LDS (gemm_hp_fwd.inc)
-            const char* W[8];
-            const float* bias[8];
-            const unsigned* wmax[8];
+            const char* W[HpSlots::MAX_LAYERS];
+            const float* bias[HpSlots::MAX_LAYERS];
+            const unsigned* wmax[HpSlots::MAX_LAYERS];
             for (int l = 0; l < L.n_sine; ++l) {
-                W[l] = net.w_hl(l);
+                W[l] = c.w_hl(l);
                 bias[l] = params + L.b_off[l];
-                wmax[l] = h3->slots + l;
+                wmax[l] = c.slots.w_max(l);
             }
-            return hp_fused_forward(y, xhl, h3->slots + 24, n, L.fan_in[0], d->hidden_features, L.n_sine, W, bias, wmax,
+            return hp_fused_forward(y, v.xhl, c.slots.x_max(), n, L.fan_in[0], d->hidden_features, L.n_sine, W, bias, wmax,
                                     d->first_omega, d->hidden_omega, params + L.w_off[L.n_sine], params + L.b_off[L.n_sine],
                                     use_clamp, clamp_min, st);
         }
-        const char* in = xhl;
+        const char* in = v.xhl;
         for (int l = 0; l < L.n_sine; ++l) {
-            char* dst = reinterpret_cast<char*>(bufs[l & 1]);
-            const float omega = (l == 0) ? d->first_omega : d->hidden_omega;
-            if (int rc = hp_sine_forward(dst, nullptr, in, net.w_hl(l), params + L.b_off[l], n, L.fan_in[l], L.fan_out[l],
-                                         omega, net.act_scale(l), net.w_scale(l), 0, st, false, net.act_scale(l + 1)))
+            char* dst = reinterpret_cast<char*>(v.buf[l & 1]);
+            if (int rc = hp_sine_forward(dst, nullptr, in, c.w_hl(l), params + L.b_off[l], n, L.fan_in[l], L.fan_out[l],
+                                         layer_omega(d, l), c.act_scale(l), c.w_scale(l), 0, st, false, c.act_scale(l + 1)))
                 return rc;
             in = dst;
         }
         return hp_head_forward(y, in, params + L.w_off[L.n_sine], params + L.b_off[L.n_sine], n, d->hidden_features,
-                               use_clamp, clamp_min, st, false, 0.f, net.act_scale(L.n_sine));
+                               use_clamp, clamp_min, st, false, 0.f, c.act_scale(L.n_sine));
     }
     for (int l = 0; l < L.n_sine; ++l) {
-        float* dst = bufs[l & 1];
-        const float omega = (l == 0) ? d->first_omega : d->hidden_omega;
+        float* dst = v.buf[l & 1];
         H3Args ha;
-        if (h3 && h3->on) ha = h3_forward_args(*h3, L, l);
+        if (c.on) ha = h3_forward_args(c, l);
         if (int rc = gemm_sine_forward(dst, nullptr, cur, params + L.w_off[l], params + L.b_off[l], n, L.fan_in[l],
-                                       L.fan_out[l], omega, st, (h3 && h3->on) ? &ha : nullptr))
+                                       L.fan_out[l], layer_omega(d, l), st, c.on ? &ha : nullptr))
             return rc;
         cur = dst;
     }
@@ -726,37 +579,24 @@ int inr_siren_forward(const inr_siren_desc_t* desc, const float* params, const f
     INR_REQUIRE(params && x && y, INR_E_INVALID, "inr_siren_forward: null pointer");
     INR_REQUIRE(n >= 0 && n <= MAX_ROWS, INR_E_INVALID, "inr_siren_forward: bad row count %lld", (long long)n);
     if (n == 0) return 0;
-    INR_REQUIRE(workspace && workspace_bytes >= inr_siren_forward_workspace_bytes(desc, n), INR_E_WORKSPACE,
-                "inr_siren_forward: workspace too small");
-    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "inr_siren_forward: workspace must be 16-byte aligned");
     const Layout L = make_layout(desc);
-    const size_t half = round_up((size_t)n * desc->hidden_features * sizeof(float), 256);
-    float* b0 = (float*)workspace;
-    float* b1 = (float*)((char*)workspace + half);
-    bool amax_ready = false;
-    H3Ctx h3;
-    char* xhl = nullptr;
-    if (h3_eligible(L)) {
-        h3 = h3_make_ctx(L, (char*)workspace + 2 * half);
-        if (hp_eligible(desc, L)) {
-            xhl = (char*)workspace + 2 * half + h3_ctx_bytes(L);
-            // max|x| first: the a-priori bounds of the layers' outputs (the scales of their images) start from it
-            if (int rc = h3_tensor_amax(h3.slots + 24, x, (long long)n * L.fan_in[0], (hipStream_t)stream, 0x3f800000u)) return rc;
-            amax_ready = true;
-            if (int rc = hp_refresh_weights(HpNet{&h3, &L}, desc, params, (hipStream_t)stream, true)) return rc;
-        } else if (int rc = h3_refresh_weights(h3, L, params, (hipStream_t)stream)) {
-            return rc;
-        }
+    const InferView v = infer_view(desc, L, n, false, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "inr_siren_forward: workspace too small");
+    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "inr_siren_forward: workspace must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (v.hp) {
+        // max|x| first: the a-priori bounds of the layers' outputs (the scales of their images) start from it
+        if (int rc = h3_tensor_amax(v.ctx.slots.x_max(), x, (long long)n * L.fan_in[0], st, 0x3f800000u)) return rc;
+        if (int rc = hp_refresh_weights(v.ctx, desc, L, params, st, true)) return rc;
+    } else if (v.ctx.on) {
+        if (int rc = h3_refresh_weights(v.ctx, L, params, st)) return rc;
     }
-    return siren_forward_impl(desc, L, params, x, n, y, use_clamp, clamp_min, b0, b1, (hipStream_t)stream, &h3, xhl, false,
-                              amax_ready);
+    return siren_forward_impl(desc, L, params, x, n, y, use_clamp, clamp_min, v, st, false, v.hp);
 }
 
 size_t inr_siren_reconstruct_workspace_bytes(const inr_siren_desc_t* desc, int64_t chunk_rows) {
     if (check_desc(desc) || chunk_rows < 1) return 0;
-    const size_t feats = round_up((size_t)chunk_rows * desc->in_features * sizeof(float), 256);
-    const size_t act = round_up((size_t)chunk_rows * desc->hidden_features * sizeof(float), 256);
-    return 2 * feats + 2 * act + h3_ctx_bytes(make_layout(desc));   // second feature buffer: its HL32 image
+    return infer_view(desc, make_layout(desc), chunk_rows, true, nullptr).total;
 }
 
 int inr_siren_reconstruct(const inr_siren_desc_t* desc, const float* params, const int64_t* shape, int dim,
@@ -773,42 +613,30 @@ int inr_siren_reconstruct(const inr_siren_desc_t* desc, const float* params, con
         INR_REQUIRE(dim == desc->in_features, INR_E_INVALID,
                     "inr_siren_reconstruct: without B the grid dim (%d) must equal in_features (%d)", dim,
                     desc->in_features);
-    INR_REQUIRE(workspace && workspace_bytes >= inr_siren_reconstruct_workspace_bytes(desc, chunk_rows),
-                INR_E_WORKSPACE, "inr_siren_reconstruct: workspace too small");
+    const Layout L = make_layout(desc);
+    const InferView v = infer_view(desc, L, chunk_rows, true, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "inr_siren_reconstruct: workspace too small");
     INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "inr_siren_reconstruct: workspace must be 16-byte aligned");
     int64_t total = 1;
     for (int a = 0; a < dim; ++a) {
         INR_REQUIRE(shape[a] >= 1, INR_E_INVALID, "inr_siren_reconstruct: shape[%d] must be >= 1", a);
         total *= shape[a];
     }
-    const Layout L = make_layout(desc);
-    const size_t feats_b = round_up((size_t)chunk_rows * desc->in_features * sizeof(float), 256);
-    const size_t act_b = round_up((size_t)chunk_rows * desc->hidden_features * sizeof(float), 256);
-    float* feats = (float*)workspace;
-    float* b0 = (float*)((char*)workspace + feats_b);
-    float* b1 = (float*)((char*)workspace + feats_b + act_b);
     hipStream_t st = (hipStream_t)stream;
-    H3Ctx h3;
-    char* xhl = nullptr;
-    if (h3_eligible(L)) {
-        h3 = h3_make_ctx(L, (char*)workspace + feats_b + 2 * act_b);
-        if (hp_eligible(desc, L)) {
-            xhl = (char*)workspace + feats_b + 2 * act_b + h3_ctx_bytes(L);
-            if (int rc = hp_refresh_weights(HpNet{&h3, &L}, desc, params, st, false)) return rc;
-        } else if (int rc = h3_refresh_weights(h3, L, params, st)) {
-            return rc;
-        }
+    if (v.hp) {
+        if (int rc = hp_refresh_weights(v.ctx, desc, L, params, st, false)) return rc;
+    } else if (v.ctx.on) {
+        if (int rc = h3_refresh_weights(v.ctx, L, params, st)) return rc;
     }
     for (int64_t r0 = 0; r0 < total; r0 += chunk_rows) {
         const int64_t rows = (total - r0 < chunk_rows) ? (total - r0) : chunk_rows;
         // pre-split path with Fourier features: grid -> features -> HL32 image in ONE kernel (no fp32 feature matrix at all)
-        const bool direct = xhl && B && hp_grid_fourier_ok(m, dim);
-        int rc = direct ? hp_grid_fourier_hl(xhl, h3.slots + 24, shape, dim, r0, rows, B, m, st)
-                 : B    ? launch_fourier(feats, nullptr, shape, dim, r0, rows, B, m, st)
-                        : launch_mgrid(feats, shape, dim, r0, rows, st);
+        const bool direct = v.hp && B && hp_grid_fourier_ok(m, dim);
+        int rc = direct ? hp_grid_fourier_hl(v.xhl, v.ctx.slots.x_max(), shape, dim, r0, rows, B, m, st)
+                 : B    ? launch_fourier(v.feats, nullptr, shape, dim, r0, rows, B, m, st)
+                        : launch_mgrid(v.feats, shape, dim, r0, rows, st);
         if (rc) return rc;
-        rc = siren_forward_impl(desc, L, params, feats, rows, y + r0 * desc->out_features, use_clamp, clamp_min, b0,
-                                b1, st, &h3, xhl, direct);
+        rc = siren_forward_impl(desc, L, params, v.feats, rows, y + r0 * desc->out_features, use_clamp, clamp_min, v, st, direct);
         if (rc) return rc;
     }
     return 0;
@@ -859,60 +687,87 @@ static HpSlabPlan hp_slab_plan(const Layout& L, int64_t n) {
     return p;
 }
 
-// workspace carve for the fit: acts (n_sine x n x H), dacts (n_sine x n x H), y, gy, scratch
-struct FitCarve {
-    size_t act_b, out_b, scratch_b, total, h3_off, xhl_off;
+// ---- fit workspace: acts (n_sine x n x H) | dacts (n_sine x n x H) | y | gy | scratch | split-GEMM context | HL32 image of x ---------
+// The ONE place that sizes and carves it.  Every entry point that trains on a workspace (inr_siren_fit_cycle,
+// inr_siren_loss_grad_ex, inr_siren_forward_train / inr_siren_backward_train) builds this view once per call, so the two passes of
+// an autograd step see the same carve by construction.  workspace == nullptr: `total` only (the planner).  The fused
+// small-network step carves the same bytes its own way (siren_small.hip); `total` covers it.
+struct FitView {
+    size_t total = 0;
+    int64_t n = 0;
+    std::vector<float*> act, dact;      // act[0] = x, act[l + 1] = output of sine layer l; dact[l]: its omega cos(.), later dz_l
+    float *y = nullptr, *gy = nullptr;  // layer-wise path only
+    float* scratch = nullptr;           // reduction workspaces of the layer-wise path / the slab region of the pre-split step
+    SplitCtx ctx;
+    char* xhl = nullptr;                // HL32 image of x (pre-split path)
+    bool hp = false;                    // the pre-split kernels serve this network
+    const char* act_hl(int l) const { return l == 0 ? xhl : reinterpret_cast<const char*>(act[l]); }
 };
-static FitCarve fit_carve(const inr_siren_desc_t* d, const Layout& L, int64_t n) {
-    FitCarve c;
-    c.act_b = round_up((size_t)n * d->hidden_features * sizeof(float), 256);
-    c.out_b = round_up((size_t)n * d->out_features * sizeof(float), 256);
+static FitView fit_view(const inr_siren_desc_t* d, const Layout& L, int64_t n, const float* x, void* workspace) {
+    FitView v;
+    v.n = n;
+    const size_t act_b = round_up((size_t)n * d->hidden_features * sizeof(float), 256);
+    const size_t out_b = round_up((size_t)n * d->out_features * sizeof(float), 256);
     size_t scratch = head_backward_ws_floats(n, d->hidden_features, d->out_features);
     for (int l = 0; l < L.n_sine; ++l) {
         scratch = max2(scratch, param_grad_ws_floats(n, L.fan_in[l], L.fan_out[l]));
         if (l > 0) scratch = max2(scratch, input_grad_ws_floats(n, L.fan_in[l]));
     }
-    const size_t mse = (size_t)mse_blocks((int64_t)n * d->out_features) + 1;
-    if (mse > scratch) scratch = mse;
-    if (L.n_sine <= 8 && d->out_features == 1) scratch = max2(scratch, hp_slab_plan(L, n).total);   // deferred slabs of the HL32 step
-    c.scratch_b = round_up(scratch * sizeof(float), 256);
-    c.h3_off = 2 * (size_t)L.n_sine * c.act_b + 2 * c.out_b + c.scratch_b;
-    c.xhl_off = c.h3_off + h3_ctx_bytes(L);
-    c.total = c.xhl_off + round_up((size_t)n * d->in_features * sizeof(float), 256);   // HL32 image of the network input
-    if (small_path_ok(d, n)) {   // the fused small-network step carves the same workspace differently
-        const size_t small = round_up(small_workspace_floats(d, n, L.total) * sizeof(float), 256);
-        if (small > c.total) c.total = small;
-        if (small_multi_ok(d, n)) {
-            const size_t multi = round_up(small_multi_workspace_floats(d, n, L.total) * sizeof(float), 256);
-            if (multi > c.total) c.total = multi;
-        }
+    scratch = max2(scratch, (size_t)mse_blocks((int64_t)n * d->out_features) + 1);
+    if (L.n_sine <= HpSlots::MAX_LAYERS && d->out_features == 1)
+        scratch = max2(scratch, hp_slab_plan(L, n).total);   // deferred slabs of the HL32 step
+    const size_t y_off = 2 * (size_t)L.n_sine * act_b;
+    const size_t scratch_off = y_off + 2 * out_b;
+    const size_t ctx_off = scratch_off + round_up(scratch * sizeof(float), 256);
+    const size_t xhl_off = ctx_off + split_ctx_bytes(L);
+    v.total = xhl_off + round_up((size_t)n * d->in_features * sizeof(float), 256);
+    if (small_path_ok(d, n)) {
+        v.total = max2(v.total, round_up(small_workspace_floats(d, n, L.total) * sizeof(float), 256));
+        if (small_multi_ok(d, n)) v.total = max2(v.total, round_up(small_multi_workspace_floats(d, n, L.total) * sizeof(float), 256));
     }
-    return c;
+    if (!workspace) return v;
+    char* base = (char*)workspace;
+    v.act.resize(L.n_sine + 1);
+    v.dact.resize(L.n_sine);
+    v.act[0] = const_cast<float*>(x);
+    for (int l = 0; l < L.n_sine; ++l) {
+        v.act[l + 1] = (float*)(base + (size_t)l * act_b);
+        v.dact[l] = (float*)(base + (size_t)(L.n_sine + l) * act_b);
+    }
+    v.y = (float*)(base + y_off);
+    v.gy = (float*)(base + y_off + out_b);
+    v.scratch = (float*)(base + scratch_off);
+    v.ctx = split_ctx(L, base + ctx_off);
+    v.xhl = base + xhl_off;
+    v.hp = v.ctx.on && hp_eligible(d, L);
+    return v;
 }
 
 // one forward (with stash) + loss + backward of the layer-wise path; grads land in the flat gradient buffer.
 // count_total > 0: this is one row shard of a split fit (mean taken over count_total elements).
-static int fit_forward_backward(const inr_siren_desc_t* d, const Layout& L, const float* params, float* grads,
-                                std::vector<float*>& act, std::vector<float*>& dact, float* y, float* gy, float* scratch,
-                                const float* target, const float* weight, int64_t n, int64_t count_total,
-                                float* loss_dst, hipStream_t st, const H3Ctx* h3 = nullptr) {
+static int fit_forward_backward(const inr_siren_desc_t* d, const Layout& L, const float* params, float* grads, const FitView& v,
+                                const float* target, const float* weight, int64_t count_total, float* loss_dst, hipStream_t st) {
     const int H = d->hidden_features, O = d->out_features, head = L.n_sine;
-    const bool split = h3 && h3->on;
+    const int64_t n = v.n;
+    const std::vector<float*>&act = v.act, &dact = v.dact;
+    float* scratch = v.scratch;
+    const SplitCtx& c = v.ctx;
+    const bool split = c.on;
     if (split) {   // this step's weights as fp16 planes; dz scale slots back to zero
-        if (int rc = h3_refresh_weights(*h3, L, params, st)) return rc;
+        if (int rc = h3_refresh_weights(c, L, params, st)) return rc;
     }
     // forward with stash (SRDWI.py:58-59 per layer; dact = omega*cos(.) replaces autograd's saved z)
     for (int l = 0; l < L.n_sine; ++l) {
-        const float omega = (l == 0) ? d->first_omega : d->hidden_omega;
         H3Args ha;
-        if (split) ha = h3_forward_args(*h3, L, l);
+        if (split) ha = h3_forward_args(c, l);
         if (int rc = gemm_sine_forward(act[l + 1], dact[l], act[l], params + L.w_off[l], params + L.b_off[l], n,
-                                       L.fan_in[l], L.fan_out[l], omega, st, split ? &ha : nullptr))
+                                       L.fan_in[l], L.fan_out[l], layer_omega(d, l), st, split ? &ha : nullptr))
             return rc;
     }
     // head forward, loss + dL/dy (superresDWI.py:135), head backward; then the sine layers from last to first, dz
     // overwriting dact in place (bias gradients ride along: the head pass yields gb of the last sine layer, every
     // input-grad GEMM yields gb of the layer below from its epilogue)
+    unsigned* dz_amax = split ? c.slots.dz_max(head - 1) : nullptr;
     if (head_step_fused_ok(H, O, act[head], dact[head - 1], params + L.w_off[head], scratch)) {
         // one pass over act_L / dact_L does all three (kernels.hip: head_step_fused_kernel)
         const int64_t blocks = head_fused_blocks(n);
@@ -923,7 +778,7 @@ static int fit_forward_backward(const inr_siren_desc_t* d, const Layout& L, cons
         float* part_g = part_loss + blocks;
         if (int rc = launch_head_step_fused(dact[head - 1], slab_b, slab_w, part_loss, part_g, act[head], dact[head - 1],
                                             params + L.w_off[head], params + L.b_off[head], target, weight, n, H,
-                                            count_total, st, split ? h3->slots + 8 + head - 1 : nullptr))
+                                            count_total, st, dz_amax))
             return rc;
         if (int rc = launch_reduce_slabs(grads + L.b_off[head - 1], slab_b, (int)blocks, H, tmp, st)) return rc;
         if (int rc = launch_reduce_slabs(grads + L.w_off[head], slab_w, (int)blocks, H, tmp, st)) return rc;
@@ -931,20 +786,20 @@ static int fit_forward_backward(const inr_siren_desc_t* d, const Layout& L, cons
         if (int rc = launch_finish_sum(loss_dst, part_loss, (int)blocks, inv, st)) return rc;
         if (int rc = launch_finish_sum(grads + L.b_off[head], part_g, (int)blocks, 1.0f, st)) return rc;
     } else {
-        if (int rc = launch_head_forward(y, act[head], params + L.w_off[head], params + L.b_off[head], n, H, O, 0,
+        if (int rc = launch_head_forward(v.y, act[head], params + L.w_off[head], params + L.b_off[head], n, H, O, 0,
                                          0.f, st))
             return rc;
-        if (int rc = launch_mse(gy, loss_dst, y, target, weight, n * O, scratch + 1, st, count_total)) return rc;
+        if (int rc = launch_mse(v.gy, loss_dst, v.y, target, weight, n * O, scratch + 1, st, count_total)) return rc;
         if (int rc = head_backward(dact[head - 1], grads + L.w_off[head], grads + L.b_off[head],
-                                   grads + L.b_off[head - 1], gy, act[head], dact[head - 1], params + L.w_off[head], n,
-                                   H, O, scratch, st, split ? h3->slots + 8 + head - 1 : nullptr))
+                                   grads + L.b_off[head - 1], v.gy, act[head], dact[head - 1], params + L.w_off[head], n,
+                                   H, O, scratch, st, dz_amax))
             return rc;
     }
     for (int l = L.n_sine - 1; l >= 0; --l) {
         H3Args hp, hi;
         if (split) {
-            hp = h3_param_grad_args(*h3, l);
-            if (l > 0) hi = h3_input_grad_args(*h3, L, l);
+            hp = h3_param_grad_args(c, l);
+            if (l > 0) hi = h3_input_grad_args(c, l);
         }
         if (int rc = param_grad(grads + L.w_off[l], nullptr, dact[l], act[l], n, L.fan_in[l], L.fan_out[l],
                                 scratch, st, split ? &hp : nullptr))
@@ -968,25 +823,21 @@ static int fit_forward_backward(const inr_siren_desc_t* d, const Layout& L, cons
 // back.  Measured, ms per step, one launch per layer / merged (tools/side_stream_ab.py): 2,048 rows 0.182 / 0.146, 4,096: 0.216
 // / 0.181, 8,192: 0.325 / 0.277, 16,384: 0.454 / 0.381, 32,768: 0.674 / 0.630, 69,632: 1.318 / 1.279, 139,264: 2.431 / 2.408,
 // 262,144: 4.42 / 4.42.  (The last bits of the gradients differ between the two forms: other row ranges per partial sum.)
-tune_int g_hp_side_stream{1};   // (the name of the first form; key 20) identical bits either way
-tune_int g_hp_merge_blocks{256};  // key 22: block count the merged parameter-gradient launch aims at (row splits = this / tiles)
+static tune_int g_hp_side_stream{1};   // (the name of the first form; key 20) identical bits either way
+static tune_int g_hp_merge_blocks{256};  // key 22: block count the merged parameter-gradient launch aims at (row splits = this / tiles)
 
 // the same step on the pre-split path (gemm_hp.inc): act[l] (l >= 1) and dz are HL32, act[0] = the HL32 image of x,
-// dact fp32 until the backward pass overwrites it with dz (HL32, scaled from an a-priori bound).  Gradients are NOT reduced
-// here: every producer leaves its slab rows in `slabs` and `fin` describes them (the caller finishes with launch_finalize).
+// dact fp32 until the backward pass overwrites it with dz (HL32, scaled from an a-priori bound).
 // forward of the sine layers (stash kept for the backward pass); z_head: the last layer stashes z + b only (HPE_Z)
-static int hp_forward_pass(const inr_siren_desc_t* d, const Layout& L, const float* params, std::vector<float*>& act,
-                           std::vector<float*>& dact, const char* xhl, int64_t n, hipStream_t st, const H3Ctx& ctx, bool z_head,
-                           bool skip_last = false) {
-    // skip_last: the last sine layer runs inside hp_backward_pass with the head step in its epilogue (hp_sine_forward_head)
-    const HpNet net{&ctx, &L};
+// skip_last: the last sine layer runs inside hp_backward_pass with the head step in its epilogue (hp_sine_forward_head)
+static int hp_forward_pass(const inr_siren_desc_t* d, const Layout& L, const float* params, const FitView& v, hipStream_t st,
+                           bool z_head, bool skip_last = false) {
+    const SplitCtx& c = v.ctx;
     const int head = L.n_sine;
-    auto act_hl = [&](int l) -> const char* { return l == 0 ? xhl : reinterpret_cast<const char*>(act[l]); };
     for (int l = 0; l < L.n_sine - (skip_last ? 1 : 0); ++l) {
-        const float omega = (l == 0) ? d->first_omega : d->hidden_omega;
-        if (int rc = hp_sine_forward(reinterpret_cast<char*>(act[l + 1]), dact[l], act_hl(l), net.w_hl(l), params + L.b_off[l], n,
-                                     L.fan_in[l], L.fan_out[l], omega, net.act_scale(l), net.w_scale(l), 0, st,
-                                     z_head && l == head - 1, net.act_scale(l + 1)))
+        if (int rc = hp_sine_forward(reinterpret_cast<char*>(v.act[l + 1]), v.dact[l], v.act_hl(l), c.w_hl(l), params + L.b_off[l],
+                                     v.n, L.fan_in[l], L.fan_out[l], layer_omega(d, l), c.act_scale(l), c.w_scale(l), 0, st,
+                                     z_head && l == head - 1, c.act_scale(l + 1)))
             return rc;
     }
     return 0;
@@ -994,16 +845,17 @@ static int hp_forward_pass(const inr_siren_desc_t* d, const Layout& L, const flo
 
 // head step + backward of every layer.  The loss gradient is formed here from (target, weight) -- the fused fit -- or taken from
 // the caller (g_ext = dL/dy, the autograd path; target / weight unused, no loss).  Gradients are NOT reduced here: every producer
-// leaves its slab rows in `slabs` and `fin` describes them (the caller finishes with launch_finalize).
-static int hp_backward_pass(const inr_siren_desc_t* d, const Layout& L, const float* params, float* grads,
-                            std::vector<float*>& act, std::vector<float*>& dact, const char* xhl, float* slabs,
-                            const float* target, const float* weight, const float* g_ext, int64_t n, int64_t count_total,
-                            float* loss_dst, hipStream_t st, const H3Ctx& ctx, FinalizeJob& fin, bool z_head, bool fuse_head = false) {
+// leaves its slab rows in v.scratch and `fin` describes them (the caller finishes with launch_finalize).
+static int hp_backward_pass(const inr_siren_desc_t* d, const Layout& L, const float* params, float* grads, const FitView& v,
+                            const float* target, const float* weight, const float* g_ext, int64_t count_total, float* loss_dst,
+                            hipStream_t st, FinalizeJob& fin, bool z_head, bool fuse_head = false) {
     const int H = d->hidden_features, head = L.n_sine;
-    const HpNet net{&ctx, &L};
+    const int64_t n = v.n;
+    const SplitCtx& c = v.ctx;
+    float* slabs = v.scratch;
     const HpSlabPlan plan = hp_slab_plan(L, n);
     const float inv = (float)(1.0 / (double)(count_total > 0 ? count_total : n));
-    const float omega_last = (head - 1 == 0) ? d->first_omega : d->hidden_omega;
+    const float omega_last = layer_omega(d, head - 1);
     fin = FinalizeJob{};
     fin.nseg = 2 * (head + 1);
     for (int k = 0; k < fin.nseg; ++k) {
@@ -1017,47 +869,44 @@ static int hp_backward_pass(const inr_siren_desc_t* d, const Layout& L, const fl
     fin.grads = grads;
     fin.loss_out = loss_dst;
     fin.loss_scale = inv;
-    auto act_hl = [&](int l) -> const char* { return l == 0 ? xhl : reinterpret_cast<const char*>(act[l]); };
+    auto slab_of = [&](int k) { return slabs + plan.seg[k].slab; };
     // scale of dz_l: the head's bound for the last sine layer, else measured max|dz_{l+1}| * wnorm_{l+1} * omega_l
     auto dz_scale = [&](int l) {
         HpScale s;
         if (l == head - 1) {
-            s.wn = net.head_bound();
+            s.wn = c.slots.head_bound();
             s.mul = 1.f;
         } else {
-            s.meas = ctx.slots + 8 + l + 1;
-            s.wn = reinterpret_cast<const float*>(ctx.slots + 16 + l + 1);
-            s.mul = fabsf(l == 0 ? d->first_omega : d->hidden_omega) * 1.001f;
+            s.meas = c.slots.dz_max(l + 1);
+            s.wn = c.slots.wnorm(l + 1);
+            s.mul = fabsf(layer_omega(d, l)) * 1.001f;
         }
         return s;
     };
-    if (fuse_head) {   // the last sine layer with the head step in its epilogue: no z round trip, no head step kernel (gemm_hp_row.inc, HPE_HEAD)
-        const int rows = hp_row_head_rows(n);
-        const int kb = 2 * (head - 1) + 1, kw = 2 * head, kg = 2 * head + 1;   // b_{S-1}, W_head, b_head
+    {   // the head step: dz of the last sine layer + the slab rows of b_{S-1}, W_head, b_head and of the loss
+        const int kb = 2 * (head - 1) + 1, kw = 2 * head, kg = 2 * head + 1;
         float* part_loss = slabs + plan.part_loss;
-        if (int rc = hp_sine_forward_head(reinterpret_cast<char*>(dact[head - 1]), act_hl(head - 1), net.w_hl(head - 1),
-                                          params + L.b_off[head - 1], n, L.fan_in[head - 1], H, omega_last, net.act_scale(head - 1),
-                                          net.w_scale(head - 1), dz_scale(head - 1), params + L.w_off[head], params + L.b_off[head],
-                                          target, weight, count_total, const_cast<float*>(fin.seg[kb].slab),
-                                          const_cast<float*>(fin.seg[kw].slab), part_loss, const_cast<float*>(fin.seg[kg].slab),
-                                          ctx.slots + 8 + head - 1, st))
-            return rc;
+        char* dz_hl = reinterpret_cast<char*>(v.dact[head - 1]);
+        int rows;
+        if (fuse_head) {   // in the last sine layer's epilogue: no z round trip, no head step kernel (gemm_hp_row.inc, HPE_HEAD)
+            rows = hp_row_head_rows(n);
+            if (int rc = hp_sine_forward_head(dz_hl, v.act_hl(head - 1), c.w_hl(head - 1), params + L.b_off[head - 1], n,
+                                              L.fan_in[head - 1], H, omega_last, c.act_scale(head - 1), c.w_scale(head - 1),
+                                              dz_scale(head - 1), params + L.w_off[head], params + L.b_off[head], target, weight,
+                                              count_total, slab_of(kb), slab_of(kw), part_loss, slab_of(kg),
+                                              c.slots.dz_max(head - 1), st))
+                return rc;
+        } else {
+            rows = (int)hp_head_blocks(n);
+            if (int rc = hp_head_step(dz_hl, slab_of(kb), slab_of(kw), part_loss, slab_of(kg), v.act_hl(head), v.dact[head - 1],
+                                      params + L.w_off[head], params + L.b_off[head], target, weight, n, H, count_total,
+                                      c.slots.dz_max(head - 1), dz_scale(head - 1), st, z_head, omega_last, g_ext,
+                                      c.act_scale(head)))
+                return rc;
+        }
         fin.seg[kb].nslabs = fin.seg[kw].nslabs = fin.seg[kg].nslabs = rows;
         fin.part_loss = part_loss;
         fin.nparts = rows;
-    } else {
-        const int blocks = (int)hp_head_blocks(n);
-        const int kb = 2 * (head - 1) + 1, kw = 2 * head, kg = 2 * head + 1;   // b_{S-1}, W_head, b_head
-        float* part_loss = slabs + plan.part_loss;
-        if (int rc = hp_head_step(reinterpret_cast<char*>(dact[head - 1]), const_cast<float*>(fin.seg[kb].slab),
-                                  const_cast<float*>(fin.seg[kw].slab), part_loss, const_cast<float*>(fin.seg[kg].slab),
-                                  act_hl(head), dact[head - 1], params + L.w_off[head], params + L.b_off[head], target, weight,
-                                  n, H, count_total, ctx.slots + 8 + head - 1, dz_scale(head - 1), st, z_head, omega_last, g_ext,
-                                  net.act_scale(head)))
-            return rc;
-        fin.seg[kb].nslabs = fin.seg[kw].nslabs = fin.seg[kg].nslabs = blocks;
-        fin.part_loss = part_loss;
-        fin.nparts = blocks;
     }
     // (only where it pays: see above)
     const bool merge = g_hp_side_stream && L.n_sine > 1 && n < 200000 && L.n_sine <= hp_param_grad_multi_max();
@@ -1075,22 +924,22 @@ static int hp_backward_pass(const inr_siren_desc_t* d, const Layout& L, const fl
         if (merged_splits < min_by_len) merged_splits = min_by_len;
     }
     for (int l = L.n_sine - 1; l >= 0; --l) {
-        const char* dz = reinterpret_cast<const char*>(dact[l]);
+        const char* dz = reinterpret_cast<const char*>(v.dact[l]);
         int splits = hp_param_grad_splits(n, L.fan_in[l], L.fan_out[l]);     // (what the slab plan reserves: an upper bound)
         if (splits > merged_splits) splits = merged_splits;
         if (merge) {
-            jobs[njobs++] = HpParamGradJob{const_cast<float*>(fin.seg[2 * l].slab), splits, dz, act_hl(l), L.fan_in[l], L.fan_out[l],
-                                           dz_scale(l), net.act_scale(l)};
-        } else if (int rc = hp_param_grad_slabs(const_cast<float*>(fin.seg[2 * l].slab), splits, dz, act_hl(l), n, L.fan_in[l],
-                                                L.fan_out[l], dz_scale(l), net.act_scale(l), st)) {
+            jobs[njobs++] = HpParamGradJob{slab_of(2 * l), splits, dz, v.act_hl(l), L.fan_in[l], L.fan_out[l], dz_scale(l),
+                                           c.act_scale(l)};
+        } else if (int rc = hp_param_grad_slabs(slab_of(2 * l), splits, dz, v.act_hl(l), n, L.fan_in[l], L.fan_out[l], dz_scale(l),
+                                                c.act_scale(l), st)) {
             return rc;
         }
         fin.seg[2 * l].nslabs = splits;
         if (l > 0) {
             int rows = 0;
-            if (int rc = hp_input_grad(reinterpret_cast<char*>(dact[l - 1]), dz, net.wT_hl(l), dact[l - 1], n, L.fan_in[l],
-                                       L.fan_out[l], const_cast<float*>(fin.seg[2 * (l - 1) + 1].slab), &rows,
-                                       ctx.slots + 8 + l - 1, dz_scale(l), net.w_scale(l), dz_scale(l - 1), st))
+            if (int rc = hp_input_grad(reinterpret_cast<char*>(v.dact[l - 1]), dz, c.wT_hl(l), v.dact[l - 1], n, L.fan_in[l],
+                                       L.fan_out[l], slab_of(2 * (l - 1) + 1), &rows, c.slots.dz_max(l - 1), dz_scale(l),
+                                       c.w_scale(l), dz_scale(l - 1), st))
                 return rc;
             fin.seg[2 * (l - 1) + 1].nslabs = rows;
         }
@@ -1101,43 +950,41 @@ static int hp_backward_pass(const inr_siren_desc_t* d, const Layout& L, const fl
     return 0;
 }
 
-static int fit_forward_backward_hp(const inr_siren_desc_t* d, const Layout& L, const float* params, float* grads,
-                                   std::vector<float*>& act, std::vector<float*>& dact, const char* xhl, float* slabs,
-                                   const float* target, const float* weight, int64_t n, int64_t count_total, float* loss_dst,
-                                   hipStream_t st, const H3Ctx& ctx, FinalizeJob& fin) {
+static int fit_forward_backward_hp(const inr_siren_desc_t* d, const Layout& L, const float* params, float* grads, const FitView& v,
+                                   const float* target, const float* weight, int64_t count_total, float* loss_dst, hipStream_t st,
+                                   FinalizeJob& fin) {
     const int head = L.n_sine;
-    const HpNet net{&ctx, &L};
-    const float inv = (float)(1.0 / (double)(count_total > 0 ? count_total : n));
-    const float omega_last = (head - 1 == 0) ? d->first_omega : d->hidden_omega;
-    const HpHeadBoundArgs hb{params + L.w_off[head], params + L.b_off[head], ctx.slots + 25, weight ? ctx.slots + 26 : nullptr,
-                             inv, omega_last};
-    if (int rc = hp_refresh_weights(net, d, params, st, true, &hb)) return rc;
+    const HpSlots& s = v.ctx.slots;
+    const float inv = (float)(1.0 / (double)(count_total > 0 ? count_total : v.n));
+    const HpHeadBoundArgs hb{params + L.w_off[head], params + L.b_off[head], s.target_max(), weight ? s.weight_max() : nullptr,
+                             inv, layer_omega(d, head - 1)};
+    if (int rc = hp_refresh_weights(v.ctx, d, L, params, st, true, &hb)) return rc;
     // the output of the LAST sine layer feeds nothing but the head: that layer stashes z + b only (one fp32 matrix instead
     // of act + omega cos) and the head step forms sin / cos itself -- 2.1 GB less HBM traffic per step at N = 524,288
     const bool z_head = hp_z_stash_ok(L.fan_in[head - 1]);
     // ... and from 768 row panels (98,304 rows) on the head step rides in that layer's epilogue (a block of gemm_hp_row_kernel owns whole rows)
-    const bool fuse_head = z_head && hp_row_head_ok(n, d->hidden_features, L.fan_in[head - 1]);
-    if (int rc = hp_forward_pass(d, L, params, act, dact, xhl, n, st, ctx, z_head, fuse_head)) return rc;
-    return hp_backward_pass(d, L, params, grads, act, dact, xhl, slabs, target, weight, nullptr, n, count_total, loss_dst, st, ctx,
-                            fin, z_head, fuse_head);
+    const bool fuse_head = z_head && hp_row_head_ok(v.n, d->hidden_features, L.fan_in[head - 1]);
+    if (int rc = hp_forward_pass(d, L, params, v, st, z_head, fuse_head)) return rc;
+    return hp_backward_pass(d, L, params, grads, v, target, weight, nullptr, count_total, loss_dst, st, fin, z_head, fuse_head);
 }
 
-// per call: scales of the network input and of the targets, HL32 image of x
-static int hp_prepare_call(const H3Ctx& ctx, const Layout& L, char* xhl, const float* x, const float* target,
-                           const float* weight, int64_t n, int out_f, hipStream_t st, int64_t n_acq = 1, bool keep_x = false,
-                           bool keep_stats = false) {
-    // (several acquisitions behind one pointer: the bounds cover all of them)
+// max|x| of this call's rows into its slot (floor 1: see h3_tensor_amax)
+static int measure_x(const FitView& v, const Layout& L, hipStream_t st) {
+    return h3_tensor_amax(v.ctx.slots.x_max(), v.act[0], (long long)v.n * L.fan_in[0], st, 0x3f800000u);
+}
+// per call: scales of the targets (several acquisitions behind one pointer: the bounds cover all of them), HL32 image of x.
+// keep_stats / keep_x: they are the previous call's (the caller vouches for it: see ReuseStamp)
+static int hp_prepare_call(const FitView& v, const Layout& L, const float* target, const float* weight, int out_f, hipStream_t st,
+                           int64_t n_acq = 1, bool keep_x = false, bool keep_stats = false) {
+    const HpSlots& s = v.ctx.slots;
     if (!keep_stats) {
-        if (int rc = h3_tensor_amax(ctx.slots + 25, target, (long long)n * n_acq * out_f, st, 0u)) return rc;
+        if (int rc = h3_tensor_amax(s.target_max(), target, (long long)v.n * n_acq * out_f, st, 0u)) return rc;
         if (weight) {
-            if (int rc = h3_tensor_amax(ctx.slots + 26, weight, (long long)n * n_acq * out_f, st, 0u)) return rc;
+            if (int rc = h3_tensor_amax(s.weight_max(), weight, (long long)v.n * n_acq * out_f, st, 0u)) return rc;
         }
     }
-    if (keep_x) return 0;     // the HL32 image of x and its scale slot are the previous call's (the caller vouches for it)
-    HpScale sx;
-    sx.meas = ctx.slots + 24;
-    sx.mul = 1.f;
-    return hp_convert(xhl, x, n, L.fan_in[0], sx, st);
+    if (keep_x) return 0;
+    return hp_convert(v.xhl, v.act[0], v.n, L.fan_in[0], v.ctx.x_scale(), st);
 }
 
 // What the last inr_siren_loss_grad_ex call left in a workspace, remembered on the HOST (the call must not sync to look into the
@@ -1153,6 +1000,8 @@ struct ReuseStamp {
     bool image = false, stats = false;
     bool fwd_train = false;      // an inr_siren_forward_train stash is pending (inr_siren_backward_train consumes it)
     unsigned long long used = 0; // last use (least recently used entry is replaced)
+    bool holds_image(int64_t n_, int fan_in_, const void* x_) const { return image && n == n_ && fan_in == fan_in_ && x == x_; }
+    bool holds_stats(int64_t n_, const void* t, const void* w) const { return stats && n == n_ && target == t && weight == w; }
 };
 std::mutex g_reuse_mu;
 ReuseStamp g_reuse[64];
@@ -1172,12 +1021,16 @@ ReuseStamp* reuse_find(const void* ws, bool create) {      // (caller holds g_re
     lru->used = ++g_reuse_next;
     return lru;
 }
+// a call is about to rebuild the operand image and the statistics slots of this workspace: a later REUSE flag must not trust them
+void reuse_invalidate(const void* ws) {
+    std::lock_guard<std::mutex> lk(g_reuse_mu);
+    if (ReuseStamp* s = reuse_find(ws, false)) s->image = s->stats = s->fwd_train = false;
+}
 }   // namespace
 
 size_t inr_siren_fit_workspace_bytes(const inr_siren_desc_t* desc, int64_t n) {
     if (check_desc(desc) || n < 1) return 0;
-    const Layout L = make_layout(desc);
-    return fit_carve(desc, L, n).total;
+    return fit_view(desc, make_layout(desc), n, nullptr, nullptr).total;
 }
 
 int inr_siren_fit(const inr_siren_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x,
@@ -1193,86 +1046,64 @@ int inr_siren_fit_cycle(const inr_siren_desc_t* desc, float* params, float* grad
                         int64_t first_step, int n_steps, double lr, double beta1, double beta2, double eps, float* losses,
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = check_desc(desc)) return rc;
-    const float* target = targets;
-    const float* weight = weights;
-    INR_REQUIRE(params && grads && m && v && x && target, INR_E_INVALID, "inr_siren_fit: null pointer");
+    INR_REQUIRE(params && grads && m && v && x && targets, INR_E_INVALID, "inr_siren_fit: null pointer");
     INR_REQUIRE(n >= 1 && n <= MAX_ROWS, INR_E_INVALID, "inr_siren_fit: bad row count %lld", (long long)n);
     INR_REQUIRE(first_step >= 1 && n_steps >= 0, INR_E_INVALID, "inr_siren_fit: first_step >= 1, n_steps >= 0");
     INR_REQUIRE(n_acq >= 1 && first_acq >= 0 && first_acq < n_acq, INR_E_INVALID,
                 "inr_siren_fit_cycle: need n_acq >= 1 and 0 <= first_acq < n_acq");
     const int64_t acq_stride = n * desc->out_features;      // floats between consecutive acquisitions
     const Layout L = make_layout(desc);
-    const FitCarve c = fit_carve(desc, L, n);
-    INR_REQUIRE(workspace && workspace_bytes >= c.total, INR_E_WORKSPACE,
-                "inr_siren_fit: workspace too small (%zu < %zu)", workspace_bytes, c.total);
+    const FitView fv = fit_view(desc, L, n, x, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= fv.total, INR_E_WORKSPACE,
+                "inr_siren_fit: workspace too small (%zu < %zu)", workspace_bytes, fv.total);
     INR_REQUIRE(aligned16(workspace) && aligned16(params) && aligned16(grads) && aligned16(x), INR_E_ALIGN,
                 "inr_siren_fit: params/grads/x/workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)workspace;
-    {   // this call rebuilds the operand image and the statistics slots of the workspace: a later REUSE flag must not trust them
-        std::lock_guard<std::mutex> lk(g_reuse_mu);
-        if (ReuseStamp* s = reuse_find(workspace, false)) s->image = s->stats = s->fwd_train = false;
-    }
-    std::vector<float*> act(L.n_sine + 1), dact(L.n_sine);
-    act[0] = const_cast<float*>(x);
-    for (int l = 0; l < L.n_sine; ++l) {
-        act[l + 1] = (float*)(base + (size_t)l * c.act_b);
-        dact[l] = (float*)(base + (size_t)(L.n_sine + l) * c.act_b);
-    }
-    float* y = (float*)(base + 2 * (size_t)L.n_sine * c.act_b);
-    float* gy = (float*)((char*)y + c.out_b);
-    float* scratch = (float*)((char*)gy + c.out_b);
-    float* loss_sink = scratch;  // overwritten later in the step; only used when losses == nullptr
+    reuse_invalidate(workspace);
     if (small_path_ok(desc, n) && !g_force_generic) {
         // master.py regime (small network, few thousand rows): one fused forward+backward launch + one reduce/Adam
         // launch per step instead of ~45 layer-wise launches (csrc/siren_small.hip)
-        long long w_off[32], b_off[32];
-        for (int l = 0; l <= L.n_sine; ++l) { w_off[l] = L.w_off[l]; b_off[l] = L.b_off[l]; }
         if (g_small_multi && small_multi_ok(desc, n)) {   // all steps inside one persistent launch per 64 steps
-            const int rc = small_fit_multi(desc, w_off, b_off, L.total, params, grads, m, v, x, targets, weights, n_acq,
-                                           first_acq, n, first_step, n_steps, lr, beta1, beta2, eps, losses,
+            const int rc = small_fit_multi(desc, L.w_off.data(), L.b_off.data(), L.total, params, grads, m, v, x, targets, weights,
+                                           n_acq, first_acq, n, first_step, n_steps, lr, beta1, beta2, eps, losses,
                                            (float*)workspace, st);
             if (rc != INR_E_FALLBACK) return rc;   // (a device that cannot hold the grid co-resident: two launches per step)
         }
         for (int it = 0; it < n_steps; ++it) {
             const int64_t a = (first_acq + it) % n_acq;
-            if (int rc = small_fit_step(desc, w_off, b_off, L.total, params, grads, m, v, x, targets + a * acq_stride,
-                                        weights ? weights + a * acq_stride : nullptr, n, first_step + it, lr, beta1,
-                                        beta2, eps, losses ? losses + it : nullptr, (float*)workspace, st))
+            if (int rc = small_fit_step(desc, L.w_off.data(), L.b_off.data(), L.total, params, grads, m, v, x,
+                                        targets + a * acq_stride, weights ? weights + a * acq_stride : nullptr, n,
+                                        first_step + it, lr, beta1, beta2, eps, losses ? losses + it : nullptr,
+                                        (float*)workspace, st))
                 return rc;
         }
         return 0;
     }
 
-    H3Ctx h3;
-    if (h3_eligible(L)) {
-        h3 = h3_make_ctx(L, base + c.h3_off);
-        if (int rc = h3_tensor_amax(h3.slots + 24, x, (long long)n * L.fan_in[0], st, 0x3f800000u)) return rc;
+    if (fv.ctx.on) {
+        if (int rc = measure_x(fv, L, st)) return rc;
     }
-    const bool hp = hp_eligible(desc, L);
-    if (hp) loss_sink = scratch + hp_slab_plan(L, n).loss_sink;   // (scratch[0] is a slab row the finalize launch still reads)
-    char* xhl = base + c.xhl_off;
-    if (hp && n_steps > 0) {
-        if (int rc = hp_prepare_call(h3, L, xhl, x, targets, weights, n, desc->out_features, st, n_acq)) return rc;
+    // where the loss goes when the caller does not want it: a word the step overwrites later (layer-wise path), or the plan's own
+    // (pre-split path: scratch[0] is a slab row the finalize launch still reads)
+    float* loss_sink = fv.hp ? fv.scratch + hp_slab_plan(L, n).loss_sink : fv.scratch;
+    if (fv.hp && n_steps > 0) {
+        if (int rc = hp_prepare_call(fv, L, targets, weights, desc->out_features, st, n_acq)) return rc;
     }
     for (int it = 0; it < n_steps; ++it) {
         const int64_t a = (first_acq + it) % n_acq;
-        target = targets + a * acq_stride;
-        weight = weights ? weights + a * acq_stride : nullptr;
-        if (hp) {   // gradient sums, loss and the Adam step in one launch behind the backward pass
+        const float* target = targets + a * acq_stride;
+        const float* weight = weights ? weights + a * acq_stride : nullptr;
+        float* loss_dst = losses ? (losses + it) : loss_sink;
+        if (fv.hp) {   // gradient sums, loss and the Adam step in one launch behind the backward pass
             FinalizeJob fin;
-            if (int rc = fit_forward_backward_hp(desc, L, params, grads, act, dact, xhl, scratch, target, weight, n, 0,
-                                                 losses ? (losses + it) : loss_sink, st, h3, fin))
-                return rc;
+            if (int rc = fit_forward_backward_hp(desc, L, params, grads, fv, target, weight, 0, loss_dst, st, fin)) return rc;
             fin.params = params;
             fin.m = m;
             fin.v = v;
             if (int rc = launch_finalize(fin, first_step + it, lr, beta1, beta2, eps, st)) return rc;
             continue;
         }
-        if (int rc = fit_forward_backward(desc, L, params, grads, act, dact, y, gy, scratch, target, weight, n, 0,
-                                          losses ? (losses + it) : loss_sink, st, &h3))
-            return rc;
+        if (int rc = fit_forward_backward(desc, L, params, grads, fv, target, weight, 0, loss_dst, st)) return rc;
         if (int rc = launch_adam(params, grads, m, v, L.total, first_step + it, lr, beta1, beta2, eps, st)) return rc;
     }
     return 0;
@@ -1311,20 +1142,14 @@ int inr_siren_fit_cycle_batch(const inr_siren_desc_t* desc, int n_fits, float* c
         }
     }
     const Layout L = make_layout(desc);
-    const FitCarve c = fit_carve(desc, L, n);
-    INR_REQUIRE(workspace_bytes >= c.total, INR_E_WORKSPACE, "inr_siren_fit_cycle_batch: workspace too small (%zu < %zu)",
-                workspace_bytes, c.total);
+    const size_t need = fit_view(desc, L, n, nullptr, nullptr).total;
+    INR_REQUIRE(workspace_bytes >= need, INR_E_WORKSPACE, "inr_siren_fit_cycle_batch: workspace too small (%zu < %zu)",
+                workspace_bytes, need);
     if (small_path_ok(desc, n) && !g_force_generic && g_small_multi && small_batch_per_launch(desc, n) >= 2) {
-        {   // as in inr_siren_fit_cycle: these workspaces' operand images and statistics slots are no longer trustworthy
-            std::lock_guard<std::mutex> lk(g_reuse_mu);
-            for (int i = 0; i < n_fits; ++i)
-                if (ReuseStamp* s = reuse_find(workspaces[i], false)) s->image = s->stats = s->fwd_train = false;
-        }
-        long long w_off[32], b_off[32];
-        for (int l = 0; l <= L.n_sine; ++l) { w_off[l] = L.w_off[l]; b_off[l] = L.b_off[l]; }
-        const int rc = small_fit_batch(desc, w_off, b_off, L.total, n_fits, params, grads, m, v, x, targets, weights, n_acq,
-                                       first_acq, n, first_step, n_steps, lr, beta1, beta2, eps, losses, workspaces,
-                                       (hipStream_t)stream);
+        for (int i = 0; i < n_fits; ++i) reuse_invalidate(workspaces[i]);      // (as in inr_siren_fit_cycle)
+        const int rc = small_fit_batch(desc, L.w_off.data(), L.b_off.data(), L.total, n_fits, params, grads, m, v, x, targets,
+                                       weights, n_acq, first_acq, n, first_step, n_steps, lr, beta1, beta2, eps, losses,
+                                       workspaces, (hipStream_t)stream);
         if (rc != INR_E_FALLBACK) return rc;   // (the device refused the first grid: the solo calls below)
     }
     for (int i = 0; i < n_fits; ++i) {
@@ -1356,62 +1181,42 @@ int inr_siren_loss_grad_ex(const inr_siren_desc_t* desc, const float* params, fl
     INR_REQUIRE(count_total == 0 || count_total >= n * desc->out_features, INR_E_INVALID,
                 "inr_siren_loss_grad: count_total must be 0 or >= n*out_features");
     const Layout L = make_layout(desc);
-    const FitCarve c = fit_carve(desc, L, n);
-    INR_REQUIRE(workspace && workspace_bytes >= c.total, INR_E_WORKSPACE,
-                "inr_siren_loss_grad: workspace too small (%zu < %zu)", workspace_bytes, c.total);
+    const FitView fv = fit_view(desc, L, n, x, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= fv.total, INR_E_WORKSPACE,
+                "inr_siren_loss_grad: workspace too small (%zu < %zu)", workspace_bytes, fv.total);
     INR_REQUIRE(aligned16(workspace) && aligned16(params) && aligned16(grads) && aligned16(x), INR_E_ALIGN,
                 "inr_siren_loss_grad: params/grads/x/workspace must be 16-byte aligned");
-    char* base = (char*)workspace;
-    std::vector<float*> act(L.n_sine + 1), dact(L.n_sine);
-    act[0] = const_cast<float*>(x);
-    for (int l = 0; l < L.n_sine; ++l) {
-        act[l + 1] = (float*)(base + (size_t)l * c.act_b);
-        dact[l] = (float*)(base + (size_t)(L.n_sine + l) * c.act_b);
-    }
-    float* y = (float*)(base + 2 * (size_t)L.n_sine * c.act_b);
-    float* gy = (float*)((char*)y + c.out_b);
-    float* scratch = (float*)((char*)gy + c.out_b);
-    H3Ctx h3;
+    hipStream_t st = (hipStream_t)stream;
     // A network the pre-split kernels do not serve keeps no operand image and no target statistics in its workspace: there is
     // nothing a REUSE flag could refer to, so the flags are accepted and mean nothing (round 5: they were REFUSED, which made every
     // multi-step ShardedSirenFitter.step on e.g. Siren(32, 64, 1, 1) fail at its second step -- found by tests/test_gpu_nccl.py).
-    if (!hp_eligible(desc, L)) flags = 0;
-    const bool keep_x = (flags & INR_REUSE_INPUT_IMAGE) != 0;
+    if (!fv.hp) flags = 0;
+    const bool keep_x = (flags & INR_REUSE_INPUT_IMAGE) != 0, keep_stats = (flags & INR_REUSE_TARGET_STATS) != 0;
     {
         std::lock_guard<std::mutex> lk(g_reuse_mu);
         ReuseStamp* s = reuse_find(workspace, flags == 0);
-        if (flags & INR_REUSE_INPUT_IMAGE)
-            INR_REQUIRE(s && s->image && s->n == n && s->fan_in == L.fan_in[0] && s->x == x, INR_E_INVALID,
+        if (keep_x)
+            INR_REQUIRE(s && s->holds_image(n, L.fan_in[0], x), INR_E_INVALID,
                         "inr_siren_loss_grad_ex: INR_REUSE_INPUT_IMAGE, but this workspace does not hold the image of these %lld rows of x",
                         (long long)n);
-        if (flags & INR_REUSE_TARGET_STATS)
-            INR_REQUIRE(s && s->stats && s->n == n && s->target == target && s->weight == weight, INR_E_INVALID,
+        if (keep_stats)
+            INR_REQUIRE(s && s->holds_stats(n, target, weight), INR_E_INVALID,
                         "inr_siren_loss_grad_ex: INR_REUSE_TARGET_STATS, but this workspace does not hold the statistics of this target");
         if (!s) s = reuse_find(workspace, true);
-        const bool hp_path = hp_eligible(desc, L);
-        if (!(flags & INR_REUSE_INPUT_IMAGE)) { s->image = hp_path; s->x = x; s->fan_in = L.fan_in[0]; }
-        if (!(flags & INR_REUSE_TARGET_STATS)) { s->stats = hp_path; s->target = target; s->weight = weight; }
+        if (!keep_x) { s->image = fv.hp; s->x = x; s->fan_in = L.fan_in[0]; }
+        if (!keep_stats) { s->stats = fv.hp; s->target = target; s->weight = weight; }
         s->n = n;
     }
-    if (h3_eligible(L)) {
-        h3 = h3_make_ctx(L, base + c.h3_off);
-        if (!keep_x) {
-            if (int rc = h3_tensor_amax(h3.slots + 24, x, (long long)n * L.fan_in[0], (hipStream_t)stream, 0x3f800000u)) return rc;
-        }
+    if (fv.ctx.on && !keep_x) {
+        if (int rc = measure_x(fv, L, st)) return rc;
     }
-    if (hp_eligible(desc, L)) {
-        char* xhl = base + c.xhl_off;
-        if (int rc = hp_prepare_call(h3, L, xhl, x, target, weight, n, desc->out_features, (hipStream_t)stream, 1, keep_x,
-                                     (flags & INR_REUSE_TARGET_STATS) != 0))
-            return rc;
+    if (fv.hp) {
+        if (int rc = hp_prepare_call(fv, L, target, weight, desc->out_features, st, 1, keep_x, keep_stats)) return rc;
         FinalizeJob fin;
-        if (int rc = fit_forward_backward_hp(desc, L, params, grads, act, dact, xhl, scratch, target, weight, n, count_total, loss,
-                                             (hipStream_t)stream, h3, fin))
-            return rc;
-        return launch_finalize(fin, 0, 0.0, 0.0, 0.0, 0.0, (hipStream_t)stream);
+        if (int rc = fit_forward_backward_hp(desc, L, params, grads, fv, target, weight, count_total, loss, st, fin)) return rc;
+        return launch_finalize(fin, 0, 0.0, 0.0, 0.0, 0.0, st);
     }
-    return fit_forward_backward(desc, L, params, grads, act, dact, y, gy, scratch, target, weight, n, count_total, loss,
-                                (hipStream_t)stream, &h3);
+    return fit_forward_backward(desc, L, params, grads, fv, target, weight, count_total, loss, st);
 }
 
 // ---- the autograd path on the fused fit's kernels (include/inrhip.h (f)) ------------------------------------------------------
@@ -1420,36 +1225,6 @@ int inr_siren_hp_eligible(const inr_siren_desc_t* desc) {
     const Layout L = make_layout(desc);
     return hp_eligible(desc, L) ? 1 : 0;
 }
-
-namespace {
-struct TrainCarve {
-    std::vector<float*> act, dact;
-    float* scratch;
-    char* xhl;
-    H3Ctx h3;
-};
-// (the carve of inr_siren_fit: both passes of a step must see the same one)
-int train_carve(TrainCarve& t, const inr_siren_desc_t* desc, const Layout& L, const float* x, int64_t n, void* workspace,
-                size_t workspace_bytes, const char* who) {
-    const FitCarve c = fit_carve(desc, L, n);
-    INR_REQUIRE(workspace && workspace_bytes >= c.total, INR_E_WORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
-                c.total);
-    char* base = (char*)workspace;
-    t.act.assign(L.n_sine + 1, nullptr);
-    t.dact.assign(L.n_sine, nullptr);
-    t.act[0] = const_cast<float*>(x);
-    for (int l = 0; l < L.n_sine; ++l) {
-        t.act[l + 1] = (float*)(base + (size_t)l * c.act_b);
-        t.dact[l] = (float*)(base + (size_t)(L.n_sine + l) * c.act_b);
-    }
-    float* y = (float*)(base + 2 * (size_t)L.n_sine * c.act_b);
-    float* gy = (float*)((char*)y + c.out_b);
-    t.scratch = (float*)((char*)gy + c.out_b);
-    t.xhl = base + c.xhl_off;
-    t.h3 = h3_make_ctx(L, base + c.h3_off);
-    return 0;
-}
-}   // namespace
 
 int inr_siren_forward_train(const inr_siren_desc_t* desc, const float* params, const float* x, float* y, int64_t n,
                             void* workspace, size_t workspace_bytes, int flags, void* stream) {
@@ -1462,15 +1237,16 @@ int inr_siren_forward_train(const inr_siren_desc_t* desc, const float* params, c
                 "(ask inr_siren_hp_eligible)");
     INR_REQUIRE(aligned16(workspace) && aligned16(params) && aligned16(x), INR_E_ALIGN,
                 "inr_siren_forward_train: params/x/workspace must be 16-byte aligned");
-    TrainCarve t;
-    if (int rc = train_carve(t, desc, L, x, n, workspace, workspace_bytes, "inr_siren_forward_train")) return rc;
+    const FitView fv = fit_view(desc, L, n, x, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= fv.total, INR_E_WORKSPACE,
+                "inr_siren_forward_train: workspace too small (%zu < %zu)", workspace_bytes, fv.total);
     hipStream_t st = (hipStream_t)stream;
     const bool keep_x = (flags & INR_REUSE_INPUT_IMAGE) != 0;
     {
         std::lock_guard<std::mutex> lk(g_reuse_mu);
         ReuseStamp* s = reuse_find(workspace, !keep_x);
         if (keep_x)
-            INR_REQUIRE(s && s->image && s->n == n && s->fan_in == L.fan_in[0] && s->x == x, INR_E_INVALID,
+            INR_REQUIRE(s && s->holds_image(n, L.fan_in[0], x), INR_E_INVALID,
                         "inr_siren_forward_train: INR_REUSE_INPUT_IMAGE, but this workspace does not hold the image of these %lld rows of x",
                         (long long)n);
         s->image = true;
@@ -1481,21 +1257,16 @@ int inr_siren_forward_train(const inr_siren_desc_t* desc, const float* params, c
         s->fwd_train = true;
     }
     if (!keep_x) {
-        if (int rc = h3_tensor_amax(t.h3.slots + 24, x, (long long)n * L.fan_in[0], st, 0x3f800000u)) return rc;
-        HpScale sx;
-        sx.meas = t.h3.slots + 24;
-        sx.mul = 1.f;
-        if (int rc = hp_convert(t.xhl, x, n, L.fan_in[0], sx, st)) return rc;
+        if (int rc = measure_x(fv, L, st)) return rc;
+        if (int rc = hp_convert(fv.xhl, x, n, L.fan_in[0], fv.ctx.x_scale(), st)) return rc;
     }
-    const HpNet net{&t.h3, &L};
-    if (int rc = hp_refresh_weights(net, desc, params, st, true, nullptr)) return rc;      // (also zeroes this step's dz maxima)
+    if (int rc = hp_refresh_weights(fv.ctx, desc, L, params, st, true, nullptr)) return rc;      // (also zeroes this step's dz maxima)
     const int head = L.n_sine;
     const bool z_head = hp_z_stash_ok(L.fan_in[head - 1]);
-    if (int rc = hp_forward_pass(desc, L, params, t.act, t.dact, t.xhl, n, st, t.h3, z_head)) return rc;
-    const float omega_last = (head - 1 == 0) ? desc->first_omega : desc->hidden_omega;
-    return hp_head_forward(y, z_head ? reinterpret_cast<const char*>(t.dact[head - 1]) : reinterpret_cast<const char*>(t.act[head]),
-                           params + L.w_off[head], params + L.b_off[head], n, desc->hidden_features, 0, 0.f, st, z_head, omega_last,
-                           net.act_scale(head));
+    if (int rc = hp_forward_pass(desc, L, params, fv, st, z_head)) return rc;
+    return hp_head_forward(y, z_head ? reinterpret_cast<const char*>(fv.dact[head - 1]) : fv.act_hl(head),
+                           params + L.w_off[head], params + L.b_off[head], n, desc->hidden_features, 0, 0.f, st, z_head,
+                           layer_omega(desc, head - 1), fv.ctx.act_scale(head));
 }
 
 int inr_siren_backward_train(const inr_siren_desc_t* desc, const float* params, float* grads, const float* gy, int64_t n,
@@ -1516,22 +1287,21 @@ int inr_siren_backward_train(const inr_siren_desc_t* desc, const float* params, 
         s->fwd_train = false;       // (the backward overwrites the stash with dz: one backward per forward)
         x = s->x;
     }
-    TrainCarve t;
-    if (int rc = train_carve(t, desc, L, (const float*)x, n, workspace, workspace_bytes, "inr_siren_backward_train")) return rc;
+    const FitView fv = fit_view(desc, L, n, (const float*)x, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= fv.total, INR_E_WORKSPACE,
+                "inr_siren_backward_train: workspace too small (%zu < %zu)", workspace_bytes, fv.total);
     hipStream_t st = (hipStream_t)stream;
     const int head = L.n_sine;
     const bool z_head = hp_z_stash_ok(L.fan_in[head - 1]);
-    const HpNet net{&t.h3, &L};
-    const float omega_last = (head - 1 == 0) ? desc->first_omega : desc->hidden_omega;
     // the scale of the head's dz: max|gy| x max|w_head| x omega (measured: gy is the caller's)
-    if (int rc = h3_tensor_amax(t.h3.slots + 25, gy, (long long)n * desc->out_features, st, 0u)) return rc;
-    if (int rc = hp_head_bound_ext(net.head_bound(), t.h3.slots + 25, params + L.w_off[head], desc->hidden_features, omega_last, st))
+    const HpSlots& s = fv.ctx.slots;
+    if (int rc = h3_tensor_amax(s.gy_max(), gy, (long long)n * desc->out_features, st, 0u)) return rc;
+    if (int rc = hp_head_bound_ext(s.head_bound(), s.gy_max(), params + L.w_off[head], desc->hidden_features,
+                                   layer_omega(desc, head - 1), st))
         return rc;
     FinalizeJob fin;
-    float* loss_sink = t.scratch + hp_slab_plan(L, n).loss_sink;
-    if (int rc = hp_backward_pass(desc, L, params, grads, t.act, t.dact, t.xhl, t.scratch, nullptr, nullptr, gy, n, 1, loss_sink, st,
-                                  t.h3, fin, z_head))
-        return rc;
+    float* loss_sink = fv.scratch + hp_slab_plan(L, n).loss_sink;
+    if (int rc = hp_backward_pass(desc, L, params, grads, fv, nullptr, nullptr, gy, 1, loss_sink, st, fin, z_head)) return rc;
     return launch_finalize(fin, 0, 0.0, 0.0, 0.0, 0.0, st);
 }
 

@@ -71,6 +71,28 @@ struct HpScale {
                                       // stop at 40 so that the folded bias b 2^(ka + kb) stays finite)
 };
 
+// The scale slots at the head of a network's split-GEMM region (api.hip: SplitCtx): one 32-bit word each, float bits where the
+// getter says `unsigned*` (atomic-max targets and their readers), a float where it says `float*`.  Kernels receive these
+// pointers, never an index: this map is the only place that knows the numbers.
+struct HpSlots {
+    static constexpr int MAX_LAYERS = 8;      // sine layers a region serves
+    static constexpr size_t BYTES = 256;      // the slots' share of the region
+    unsigned* base = nullptr;
+    // rebuilt by every weight preparation (one per optimizer step / forward call)
+    unsigned* w_max(int l) const { return base + l; }                                        // max|W_l|
+    unsigned* dz_max(int l) const { return base + 8 + l; }                                   // measured max|dz_l|, zeroed there
+    float* wnorm(int l) const { return reinterpret_cast<float*>(base + 16 + l); }            // max_j sum_k |W_l[k][j]|
+    float* head_bound() const { return reinterpret_cast<float*>(base + 27); }                // a-priori bound of the head's dz
+    float* act_bound(int l) const { return reinterpret_cast<float*>(base + 32 + l); }        // a-priori bound of layer l's output
+    // measured once per call
+    unsigned* x_max() const { return base + 24; }        // max|x| (floor 1)
+    unsigned* target_max() const { return base + 25; }   // a fit: max|target| ...
+    unsigned* gy_max() const { return base + 25; }       // ... inr_siren_backward_train: max|gy| (the same slot: a workspace serves one of the two)
+    unsigned* weight_max() const { return base + 26; }   // max|weight|
+};
+static_assert(3 * HpSlots::MAX_LAYERS <= 24 && (32 + HpSlots::MAX_LAYERS) * sizeof(unsigned) <= HpSlots::BYTES,
+              "the slot map must fit its region");
+
 // one parameter-gradient GEMM of a step (hp_param_grad_multi: all of them in one launch)
 struct HpParamGradJob {
     float* slabs;

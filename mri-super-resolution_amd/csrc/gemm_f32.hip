@@ -29,7 +29,7 @@
 //     kernel 16x16x4 gives fwd 136 / input-grad 141 / param-grad 147 (32x32x2: 130 / 131 / 141);
 //   * tried without effect: start-time staggering of co-resident blocks or of the whole first wave, s_setprio in
 //     either direction; tried and slower: a persistent grid with cross-tile operand prefetch (-4 %).
-#include "common.h"
+#include "internal.h"
 #include <type_traits>
 
 namespace inr {
@@ -1129,20 +1129,20 @@ static unsigned hp_persistent_grid(long long tiles) {
 }
 bool hp_head_ok(int hidden) { return hidden == 128 || hidden == 256 || hidden == 512 || hidden == 1024; }
 
-// per-step weight preparation (gemm_hp.inc): slots[l] = max|W_l|, slots[8 + l] = 0 (dz maxima), slots[16 + l] = wnorm_l; `part`
+// per-step weight preparation (gemm_hp.inc): slots.w_max(l) = max|W_l|, slots.dz_max(l) = 0, slots.wnorm(l) = wnorm_l; `part`
 // = 8 x HP_PREP_MAXB x 2 words of scratch; head_bound nullable (forward-only callers)
 size_t hp_prep_part_bytes() { return (size_t)8 * HP_PREP_MAXB * 2 * sizeof(unsigned); }
-int hp_weight_prep(const float* const* W, const int* out_f, const int* in_f, int layers, char* planes, unsigned* slots,
+int hp_weight_prep(const float* const* W, const int* out_f, const int* in_f, int layers, char* planes, HpSlots slots,
                    unsigned* part, float* head_bound, const float* head_W, const float* head_b, int hidden, const unsigned* tmax,
                    const unsigned* wtmax, float inv_count, float omega, hipStream_t stream, const float* const* bias,
                    const float* layer_omega, float* act_bound, const unsigned* x_amax) {
-    INR_REQUIRE(layers >= 1 && layers <= 8, INR_E_INVALID, "hp_weight_prep: %d layers", layers);
+    INR_REQUIRE(layers >= 1 && layers <= HpSlots::MAX_LAYERS, INR_E_INVALID, "hp_weight_prep: %d layers", layers);
     HpWeightJobs jobs{};
     char* cur = planes;
     int max_tiles = 1, max_sb = 1;
     for (int l = 0; l < layers; ++l) {
         const long long n = (long long)out_f[l] * in_f[l];
-        jobs.job[l] = HpWeightJob{W[l], cur, cur + 4 * n, slots + l, slots + 16 + l, out_f[l], in_f[l], bias ? bias[l] : nullptr,
+        jobs.job[l] = HpWeightJob{W[l], cur, cur + 4 * n, slots.w_max(l), reinterpret_cast<unsigned*>(slots.wnorm(l)), out_f[l], in_f[l], bias ? bias[l] : nullptr,
                                   layer_omega ? layer_omega[l] : 0.f};
         cur += 8 * n;
         const int t = ((out_f[l] + 63) / 64) * ((in_f[l] + 63) / 64);
@@ -1152,7 +1152,7 @@ int hp_weight_prep(const float* const* W, const int* out_f, const int* in_f, int
     }
     jobs.layers = layers;
     jobs.part = part;
-    jobs.dz_slots = slots + 8;
+    jobs.dz_slots = slots.dz_max(0);
     jobs.head_bound = head_bound;
     jobs.head_W = head_W; jobs.head_b = head_b; jobs.hidden = hidden;
     jobs.tmax = tmax; jobs.wtmax = wtmax; jobs.inv_count = inv_count; jobs.omega = omega;

@@ -10,7 +10,7 @@
 // Measured (MI355X, 120x120 slice, 2 % noise): one lane per voxel 4.5 s (per-lane working set in scratch, the slowest
 // voxel of the slice -- 5000 evaluations -- sets the time), eight lanes per voxel 0.28 s; 230,400 voxels 0.85 s
 // (271 k fits/s; scipy on one host core: 104 fits/s).
-#include "common.h"
+#include "internal.h"
 
 namespace inr {
 

@@ -1,7 +1,7 @@
 // Bandwidth-bound kernels of the INR fit path: coordinate grid, Fourier features, linear head
 // (wavefront-shuffle row reduction), MSE residual/gradient, head backward, fixed-order column sums
 // and slab reductions (bias / weight gradients, loss), fused Adam.  All fp32, no float atomics.
-#include "common.h"
+#include "internal.h"
 
 namespace inr {
 
@@ -620,7 +620,7 @@ int launch_fourier(float* out, const float* x, const int64_t* shape, int dim, in
 
 // mode (use_clamp): 0 plain, 1 clamp(min=clamp_min), 2 y = clamp_min*tanh(.) with optional derivative dy
 int launch_head_forward(float* y, const float* a, const float* W, const float* b, int64_t n, int hidden,
-                        int out_f, int use_clamp, float clamp_min, hipStream_t st, float* dy = nullptr) {
+                        int out_f, int use_clamp, float clamp_min, hipStream_t st, float* dy) {
     if (n == 0) return 0;
     const bool vec = aligned16(a) && aligned16(W) && (hidden % 4 == 0);
     ProfScope ps(KC_OTHER, st);
@@ -640,7 +640,7 @@ int mse_blocks(int64_t count) { return (int)blocks_for(count, 256 * 4, 2048); }
 // count_total (0 = count): the divisor of the mean -- larger than `count` when this call sees one row shard of a
 // fit that is split over several GPUs (gradients and losses of the shards then simply add up)
 int launch_mse(float* gy, float* loss, const float* y, const float* t, const float* w, int64_t count,
-               float* partial, hipStream_t st, int64_t count_total = 0) {
+               float* partial, hipStream_t st, int64_t count_total) {
     const int nb = mse_blocks(count);
     const float inv = (float)(1.0 / (double)(count_total > 0 ? count_total : count));
     ProfScope ps(KC_OTHER, st);
@@ -661,7 +661,6 @@ int launch_head_dz(float* dz, const float* gy, const float* W, const float* dact
     return 0;
 }
 
-int64_t reduce_tmp_floats(int64_t nslabs, int64_t len);
 // chunking used by the column-sum path: ~2048 blocks, at least 32 rows per chunk
 int64_t colsum_rows_per_chunk(int64_t n, int C) {
     const int64_t col_groups = (C + 255) / 256;
@@ -679,9 +678,6 @@ int64_t colsum_ws_floats(int64_t n, int C, int G) {
     const int64_t chunks = colsum_chunks(n, C);
     return chunks * G * C + reduce_tmp_floats(chunks, (int64_t)G * C);
 }
-
-int launch_reduce_slabs(float* out, const float* slab, int nslabs, int64_t len, float* tmp, hipStream_t st);
-int64_t reduce_tmp_floats(int64_t nslabs, int64_t len);
 
 // out[G][C] = sum_rows g[row][gi]*X[row][c]; slab must hold colsum_ws_floats(n, C, G) floats
 int launch_colsum(float* out, const float* X, const float* g, int64_t n, int C, int G, float* slab,

@@ -2,7 +2,7 @@
 // The reference computes them on the host after copying the reconstruction back
 // (superresDWI.py:179-186 skimage structural_similarity; SRDWI.py:118-130 per-pixel np.polyfit in a Python
 // double loop).  Here the volume stays in HBM; everything accumulates in fp64 with fixed-order reductions.
-#include "common.h"
+#include "internal.h"
 
 namespace inr {
 

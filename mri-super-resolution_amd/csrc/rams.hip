@@ -14,7 +14,7 @@
 // is < 1 % of the work and uses simple direct kernels.
 // Weight normalisation (tfa WeightNormalization, g*v/||v||) is folded into the kernels when the parameters are
 // packed (host side, once per model) -- the packed layouts are documented in include/inrhip.h.
-#include "common.h"
+#include "internal.h"
 
 namespace inr {
 
@@ -901,7 +901,6 @@ static int rams_lds_blocks_per_b(int B, int npatch) {
                 (int)(rows_per_b), B, slab_cap)
 
 static inline bool rams_lds_aux_ok() { return g_rams_lds_waves == 42 && g_rams_epi_fuse != 0; }
-extern unsigned long long* g_stamps;   // diagnostic builds (-DR3_STAMPS): inr_debug_set_ptr(0, device buffer of 16 x u64)
 static int conv3d_h3_lds(const float* x, float* y, const _Float16* planes, const float* bias, float* chan_slab,
                          const unsigned* x_amax, const unsigned* w_amax, unsigned* y_amax, int B, int D1, int D2, int D3,
                          int pad, int cout, int y_cstride, int relu, int* nslab, hipStream_t st, long long slab_cap = -1,
@@ -1094,11 +1093,6 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_wgrad_kernel(const Conv3dWg
 
 constexpr int WGRAD_BLOCKS = 512;        // target number of blocks (two per CU)
 constexpr int WGRAD_BLOCKS_MAX = 1024;   // slabs the workspace is sized for (blocks_per_b * B never exceeds max(512, B))
-int64_t reduce_tmp_floats(int64_t nslabs, int64_t len);
-int launch_reduce_slabs(float* out, const float* slab, int nslabs, int64_t len, float* tmp, hipStream_t st);
-int launch_reduce_slabs_pitched(float* out, const float* slab, int nslabs, int64_t len, int64_t pitch, float* tmp, hipStream_t st);
-int64_t colsum_ws_floats(int64_t n, int C, int G);
-int launch_colsum(float* out, const float* X, const float* g, int64_t n, int C, int G, float* slab, hipStream_t st);
 
 size_t rams_conv3d_wgrad_ws_floats(long long nvox) {
     const size_t a = (size_t)WGRAD_BLOCKS_MAX * (CONV_W_FLOATS + RC) + (size_t)reduce_tmp_floats(WGRAD_BLOCKS_MAX, CONV_W_FLOATS + RC);

@@ -20,8 +20,6 @@ struct TLayer {
 };
 
 __host__ __device__ static inline long long pad4(long long n) { return (n + 3) / 4 * 4; }
-int launch_shift_loss_grad(double* loss, float* grad, const float* y_true, const float* y_pred, const float* mask,
-                           const float* upstream, int nimg, int size, int border, double* ws, hipStream_t st);
 
 static void rams_train_layers(const inr_rams_desc_t* d, std::vector<TLayer>& L, long long* raw_total, long long* fold_total) {
     long long ro = 0, fo = 0;

@@ -10,7 +10,7 @@
 // Same arithmetic as the big kernels (fp32 MFMA 32x32x2, k = 4h..4h+3 per 8-block, hardware sin/cos on FMA-reduced
 // revolutions), so results agree with the layer-by-layer path to rounding.
 // Eligibility (host): hidden in {32, 64}, in_features <= 32, out_features == 1.
-#include "common.h"
+#include "internal.h"
 #include <atomic>
 #include <vector>
 
@@ -449,7 +449,6 @@ struct SmallMulti {
 #else
 #define SM_STAMP(slot)
 #endif
-extern unsigned long long* g_stamps;
 
 // Data that crosses CUs (gradient slabs, updated parameters, loss partials) is stored write-through at agent scope, so a
 // block only has to wait for its own stores (vmcnt) before it announces itself -- no L2 write-back of the (much larger)

@@ -49,6 +49,13 @@ def test_host_only_entry_points_without_gpu():
     assert list(offs)[:4] == [0, 131072, 131584, 131584 + 262144]
     assert all(o % 4 == 0 for o in offs)
     assert lib.inr_siren_fit_workspace_bytes(ctypes.byref(desc), 4096) > 8 * 4096 * 512 * 4
+    # exact planner values (fit, forward, reconstruct), recorded before the workspace views replaced the hand-written carves:
+    # a view that sizes a workspace differently from what callers have allocated so far is a bug
+    small = _lib.SirenDesc(2, 64, 6, 1, 30.0, 30.0)
+    planners = (lib.inr_siren_fit_workspace_bytes, lib.inr_siren_forward_workspace_bytes,
+                lib.inr_siren_reconstruct_workspace_bytes)
+    assert [f(ctypes.byref(desc), 4096) for f in planners] == [139270656, 28315904, 32510208]
+    assert [f(ctypes.byref(small), 3600) for f in planners] == [25527040, 2074112, 2103040]
     bad = _lib.SirenDesc(0, 512, 3, 1, 30.0, 30.0)
     assert lib.inr_siren_param_count(ctypes.byref(bad)) == -1
     assert b"bad siren descriptor" in lib.inr_last_error()
