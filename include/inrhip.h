@@ -416,6 +416,72 @@ int inr_rams_shift_loss_grad(double* loss, float* grad_pred, const float* y_true
 int inr_hybrid_fit(double* params, int* status, int* nfev, double* cost, const double* signals, int64_t n_voxels,
                    void* stream);
 
+/* ---- PIA: the physics-informed autoencoder (PIA.py:16-155 `PIA`; PIA.py:286-327 `detect_PIDS_slice`) --------------------------
+ * Encoder n_signals -> hidden[0] -> ... -> hidden[n_hidden-1] (Linear + LeakyReLU each), three predictors (D, T2, v) of
+ * predictor_depth x (Linear + LeakyReLU) and a Linear to 3, then D = D_mean + D_delta tanh(.), T2 = T2_mean + T2_delta tanh(.),
+ * v = softmax(.), and the analytic decoder signal[a] = 1000 float(sum_c v_c exp(-b_a / 1000 D_c) exp(-TE_a / T2_c)), acquisition
+ * a = b index * n_te + TE index (PIA.py:123-129).  Dtypes are the reference's: D float64 (D_mean is a float64 tensor), T2 and v
+ * float32, the decoder's sum in float64, rounded once into the float32 signal.
+ * Flat parameter buffer: the 2 n_hidden + 3 (2 predictor_depth + 2) tensors of `named_parameters()` back to back WITHOUT padding
+ * (968,169 floats for the default shape), so that it is the reference's parameter vector; tensors start at any 4-byte boundary
+ * and the kernels load them accordingly.
+ * inr_pia_param_count / _offsets are defined for every valid descriptor.  The kernels serve n_signals == 16, widths that are
+ * multiples of 16, a last width of 256 or 512 and predictor_depth == 1 (INR_E_INVALID otherwise, before any device work).
+ * GEMMs run on the f32-input MFMA (v_mfma_f32_16x16x4_f32); gradient slabs are summed in a fixed order: no float atomics. */
+#define INR_PIA_MAX_HIDDEN 8
+#define INR_PIA_MAX_TABLE  8
+typedef struct inr_pia_desc {
+    int    n_signals;                       /* 16 */
+    int    n_hidden;                        /* encoder layers (5) */
+    int    hidden[INR_PIA_MAX_HIDDEN];      /* 32, 64, 128, 256, 512 */
+    int    predictor_depth;                 /* 1 */
+    int    n_b, n_te;                       /* n_b * n_te == n_signals */
+    float  leaky_slope;                     /* 0.01 (nn.LeakyReLU default) */
+    double b_values[INR_PIA_MAX_TABLE];     /* 0, 150, 1000, 1500 */
+    double te_values[INR_PIA_MAX_TABLE];    /* 0, 13, 93, 143 */
+    double D_mean[3], D_delta[3], T2_mean[3], T2_delta[3];
+} inr_pia_desc_t;
+int64_t inr_pia_param_count(const inr_pia_desc_t* desc);                 /* -1 for a bad descriptor */
+/* offsets[k] of tensor k in named_parameters() order; max_tensors >= 2 n_hidden + 3 (2 predictor_depth + 2) */
+int     inr_pia_param_offsets(const inr_pia_desc_t* desc, int64_t* offsets, int max_tensors);
+/* training != 0: what forward_train / backward_train / fit_step need for n rows (every activation, gradient buffers, slabs);
+ * training == 0: what inr_pia_forward needs for chunks of n rows.  0 for a descriptor the kernels do not serve. */
+size_t  inr_pia_workspace_bytes(const inr_pia_desc_t* desc, int64_t n, int training);
+/* model(x) without a stash, `chunk_rows` rows at a time (a whole volume's voxels in one call; results do not depend on the
+ * chunk size, bit for bit).  x [n][16]; signal [n][16] (nullable); D [n][3] float64, T2 [n][3], v [n][3] (nullable together). */
+int inr_pia_forward(const inr_pia_desc_t* desc, const float* params, const float* x, int64_t n, float* signal, double* D, float* T2,
+                    float* v, int64_t chunk_rows, void* workspace, size_t workspace_bytes, void* stream);
+/* the reference's own loop (model(x) -> any torch loss -> backward() -> torch.optim.Adam) on these kernels: the forward keeps
+ * every layer's ACTIVATION in `workspace` (the LeakyReLU derivative is its sign; the 3-wide outputs are re-computed), the
+ * backward takes d loss / d signal, D, T2, v (each nullable = zero) and writes every element of `grads` (flat, parameter
+ * order).  `params` and `x` must still hold what the forward ran on; one backward per forward on a workspace -- the library
+ * keeps no record of it: the caller pairs them. */
+int inr_pia_forward_train(const inr_pia_desc_t* desc, const float* params, const float* x, int64_t n, float* signal, double* D,
+                          float* T2, float* v, void* workspace, size_t workspace_bytes, void* stream);
+int inr_pia_backward_train(const inr_pia_desc_t* desc, const float* params, float* grads, const float* x, const float* g_signal,
+                           const double* g_D, const float* g_T2, const float* g_v, int64_t n, void* workspace,
+                           size_t workspace_bytes, void* stream);
+/* one step on the loss the class trains with, mean(PIDS * (signal - x)^2) (PIA.py:153; pids [n][16], nullable = 1): forward,
+ * loss, backward, fixed-order reduction and Adam (torch's single-tensor arithmetic, as inr_adam_step), all enqueued on
+ * `stream`; *loss (device) receives the loss BEFORE the update.  `step` is the 1-based Adam step. */
+int inr_pia_fit_step(const inr_pia_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x, const float* pids,
+                     int64_t n, int64_t step, double lr, double beta1, double beta2, double eps, float* loss, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* Launch families of the PIA kernels, counted like INR_LF_* but in a table of their own (the INR_LF_* table and its count are
+ * pinned by callers); inr_launch_counts_reset() clears both. */
+#define INR_PIA_LF_FWD   0   /* pia_gemm_kernel<FWD>: layer forward, f32-input MFMA 16x16x4, LeakyReLU epilogue */
+#define INR_PIA_LF_DX    1   /* pia_gemm_kernel<DX>: input gradient (the three heads' products in one K-loop) */
+#define INR_PIA_LF_DW    2   /* pia_gemm_kernel<DW>: parameter gradient, row-split slabs */
+#define INR_PIA_LF_HEAD  3   /* pia_head_kernel: 3-wide outputs, tanh / softmax, decoder, loss and their backward, a wave per row */
+#define INR_PIA_LF_COUNT 4
+int inr_pia_launch_count(int family, int64_t* count);
+/* detect_PIDS_slice (PIA.py:286-327): S [n_pixels][4 (b)][4 (TE)] float64, bvals [4] float64 ->
+ * adc_high [n_pixels] (ADC > 3), adc_negative [n_pixels] (ADC < 0), b_decay [n_pixels][4 (TE)][3], te_decay [n_pixels][4 (b)][3],
+ * all 0 / 1 as fp32.  A decay entry is (s[k + 1] - trunc(s[k]) >= 0): the reference truncates the left neighbour toward zero
+ * (it stores it into an integer array, PIA.py:312-313), and so does this. */
+int inr_pids_slice(float* adc_high, float* adc_negative, float* b_decay, float* te_decay, const double* S, const double* bvals,
+                   int64_t n_pixels, void* stream);
+
 /* AutoERD acceptance weights -- the per-pixel outlier rejection master.py runs before a 2-D fit (master.py:77-93).
  * values: [n_pixels][n_acquisitions] fp64 (every acquisition of the slice at that pixel); accept: same shape, fp32, 1 = keep,
  * 0 = reject.  Each pixel's sample is split in two exactly as sklearn.cluster.AgglomerativeClustering(n_clusters=2,

@@ -18,6 +18,7 @@ c_ptr_array = C.POINTER(C.c_void_p)   # host array of device pointers (nullable 
 
 INR_E_INVALID, INR_E_WORKSPACE, INR_E_ALIGN, INR_E_TIMEOUT = -1, -2, -3, -4     # include/inrhip.h
 INR_LF_COUNT = 14
+INR_PIA_LF_COUNT = 4
 
 
 class InrHipError(RuntimeError):
@@ -36,6 +37,13 @@ class SirenDesc(C.Structure):
 class RamsDesc(C.Structure):
     _fields_ = [("scale", C.c_int), ("filters", C.c_int), ("kernel_size", C.c_int), ("channels", C.c_int),
                 ("r", C.c_int), ("n_rfab", C.c_int), ("mean", C.c_float), ("std", C.c_float)]
+
+
+class PiaDesc(C.Structure):
+    _fields_ = [("n_signals", C.c_int), ("n_hidden", C.c_int), ("hidden", C.c_int * 8), ("predictor_depth", C.c_int),
+                ("n_b", C.c_int), ("n_te", C.c_int), ("leaky_slope", C.c_float), ("b_values", C.c_double * 8),
+                ("te_values", C.c_double * 8), ("D_mean", C.c_double * 3), ("D_delta", C.c_double * 3),
+                ("T2_mean", C.c_double * 3), ("T2_delta", C.c_double * 3)]
 
 
 class DeviceCaps(C.Structure):
@@ -141,6 +149,19 @@ SIGNATURES = {
     "inr_rams_shift_loss_grad": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_size_t, c_stream]),
     "inr_hybrid_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
+    "inr_pia_param_count": (C.c_int64, [C.POINTER(PiaDesc)]),
+    "inr_pia_param_offsets": (C.c_int, [C.POINTER(PiaDesc), c_i64p, C.c_int]),
+    "inr_pia_workspace_bytes": (C.c_size_t, [C.POINTER(PiaDesc), C.c_int64, C.c_int]),
+    "inr_pia_forward": (C.c_int, [C.POINTER(PiaDesc), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_int64,
+                                  C.c_void_p, C.c_size_t, c_stream]),
+    "inr_pia_forward_train": (C.c_int, [C.POINTER(PiaDesc), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, c_f32p, c_f32p,
+                                        C.c_void_p, C.c_size_t, c_stream]),
+    "inr_pia_backward_train": (C.c_int, [C.POINTER(PiaDesc), c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, c_f32p, c_f32p, C.c_int64,
+                                         C.c_void_p, C.c_size_t, c_stream]),
+    "inr_pia_fit_step": (C.c_int, [C.POINTER(PiaDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64,
+                                   C.c_double, C.c_double, C.c_double, C.c_double, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_pia_launch_count": (C.c_int, [C.c_int, c_i64p]),
+    "inr_pids_slice": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
     "inr_auto_erd": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
     "inr_prof_enable": (C.c_int, [C.c_int]),
     "inr_prof_reset": (C.c_int, []),

@@ -1677,6 +1677,7 @@ int inr_launch_count(int family, int64_t* count) {
 
 int inr_launch_counts_reset(void) {
     for (int f = 0; f < LF_COUNT; ++f) g_launches[f].store(0, std::memory_order_relaxed);
+    pia_launch_counts_reset();
     return 0;
 }
 

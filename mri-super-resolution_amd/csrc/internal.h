@@ -141,6 +141,9 @@ int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, cons
                       hipStream_t st);
 void set_hybrid_variant(int v);   // key 2
 
+// ---- pia.hip: the PIA autoencoder; its launch families are counted in a table of their own (inr_pia_launch_count) ---------------------
+void pia_launch_counts_reset();
+
 // ---- rams.hip (+ rams_train.inc) ---------------------------------------------------------------------------------------------------------
 long long rams_param_floats(const inr_rams_desc_t* d);
 size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W);

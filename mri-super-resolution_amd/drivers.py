@@ -378,7 +378,8 @@ def _sum_over_ranks(t: torch.Tensor) -> None:
 
 def fit_hybrid(hybrid_raw: np.ndarray, roi: Optional[Sequence[int]] = None, slice_index: Optional[int] = None,
                steps: int = 2500, seed: Optional[int] = 0, distributed: bool = False, gather_recon: bool = False,
-               target_dtype=None, **fit_kwargs) -> Dict[str, object]:
+               target_dtype=None, estimator: str = "curve_fit", pia_steps: int = 2000, pia_batch: int = 512,
+               pia_noise: float = 0.02, pia_lr: float = 1e-4, **fit_kwargs) -> Dict[str, object]:
     """superresHybrid.py:57-140.  ``hybrid_raw``: [X, Y, Z, 4 (b), 4 (TE)].  Per echo time one 4-D INR fit of the
     ROI (LR = every second in-plane voxel, coordinates (x, y, z, b)), re-sampled at twice the ROI size; the 16
     re-scaled images are normalised by the (b=0, TE=0) one (x1000) and one z-slice goes through the three-compartment
@@ -390,8 +391,17 @@ def fit_hybrid(hybrid_raw: np.ndarray, roi: Optional[Sequence[int]] = None, slic
     the z-slice that feeds the three-compartment fit ([2sx, 2sy, 4, 4]; every rank contributes the echo times it owns,
     zeros elsewhere), after which every rank runs the same hybrid fit.  ``recon_hybrid`` holds the owned echo times only
     unless ``gather_recon`` asks for a second all-reduce of the whole tensor.
-    ``target_dtype=np.float16``: the normalised volume is held in half precision (BASELINE config 5) and widened per fit."""
+    ``target_dtype=np.float16``: the normalised volume is held in half precision (BASELINE config 5) and widened per fit.
+
+    ``estimator="pia"`` replaces the per-voxel least-squares fit of one slice by the amortised estimator of the same maps: a
+    ``PIA`` autoencoder is trained for ``pia_steps`` fused steps on ``get_batch(pia_batch, pia_noise)`` batches (``seed`` also
+    seeds its initial weights and NumPy's global generator, which ``get_batch`` draws from) and then encodes EVERY voxel of
+    the super-resolved volume: ``D``, ``T2``, ``v`` are [2sx, 2sy, Z, 3].  ``pids`` holds the four ``detect_PIDS_slice`` maps
+    of slice ``slice_index``; ``pia_loss_before`` / ``pia_loss_after`` the unsupervised loss on one held-out batch before and
+    after training, ``model`` the trained ``PIA`` module itself (live, on the device); there is no ``status``.  The two estimators are different methods: their maps are not expected to agree."""
     from . import pia
+    if estimator not in ("curve_fit", "pia"):
+        raise ValueError(f"estimator must be 'curve_fit' or 'pia', got {estimator!r}")
     raw = np.asarray(hybrid_raw, dtype=np.float32)
     if raw.ndim != 5 or raw.shape[3] != 4 or raw.shape[4] != 4:
         raise ValueError(f"hybrid_raw must be [X, Y, Z, 4, 4], got {raw.shape}")
@@ -406,6 +416,8 @@ def fit_hybrid(hybrid_raw: np.ndarray, roi: Optional[Sequence[int]] = None, slic
     if target_dtype is not None:
         norm = norm.astype(target_dtype)
     spread = distributed and torch.distributed.is_initialized() and inr_dist.is_shared(torch.distributed.get_world_size())
+    if estimator == "pia" and spread and not gather_recon:                                 # before any fit runs
+        raise ValueError("estimator='pia' encodes the whole volume: pass gather_recon=True when the echo times are spread")
     rank = torch.distributed.get_rank() if spread else 0
     te_ranks = hybrid_te_groups(torch.distributed.get_world_size()) if spread else [[0]] * 4
     # (group creation is collective over the default group: every rank asks for every group, in the same order; cached)
@@ -440,6 +452,11 @@ def fit_hybrid(hybrid_raw: np.ndarray, roi: Optional[Sequence[int]] = None, slic
     else:
         sl = recon_hybrid[:, :, k].double()                                                # [2sx, 2sy, 4, 4]
     signals = (1000.0 * sl / (sl[..., 0:1, 0:1] + 1e-7)).reshape(-1, 16)                   # superresHybrid.py:131-138
+    if estimator == "pia":
+        out = _pia_maps(recon_hybrid, signals, (2 * sx, 2 * sy), seed, pia_steps, pia_batch, pia_noise, pia_lr)
+        out.update({"recon_hybrid": recon_hybrid, "signals": signals, "t_fit": t_fit, "t_recon": t_recon, "final_losses": losses,
+                    "slice_index": k, "owned_te": owned, "estimator": "pia"})
+        return out
     fit = pia.hybrid_fit_device(signals)
     x = fit["params"].cpu().numpy()
     t_hybrid = time.perf_counter() - t0
@@ -448,6 +465,41 @@ def fit_hybrid(hybrid_raw: np.ndarray, roi: Optional[Sequence[int]] = None, slic
     return {"recon_hybrid": recon_hybrid, "signals": signals, "D": x[:, 0:3].reshape(shape), "T2": x[:, 3:6].reshape(shape),
             "v": v.reshape(shape), "status": fit["status"].cpu().numpy().reshape(shape[:2]), "t_fit": t_fit,
             "t_recon": t_recon, "t_hybrid_fit": t_hybrid, "final_losses": losses, "slice_index": k, "owned_te": owned}
+
+
+def _pia_maps(recon_hybrid, slice_signals, plane, seed, steps, batch, noise, lr):
+    """The ``estimator="pia"`` half of ``fit_hybrid``: train a PIA on synthetic batches, encode the whole volume."""
+    from . import pia, pia_net
+    if seed is not None:
+        torch.manual_seed(seed)
+        np.random.seed(seed)
+    model = pia_net.PIA().cuda()
+    fitter = pia_net.PiaFitter(model, lr=lr)
+    held_out = pia_net.get_batch(batch, noise)[0].cuda()
+
+    def held_out_loss():
+        with torch.no_grad():
+            return float(model.loss_function(model(held_out)[0], held_out, 1.0))
+
+    before = held_out_loss()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    step_losses = [fitter.step(pia_net.get_batch(batch, noise)[0].cuda()) for _ in range(int(steps))]
+    torch.cuda.synchronize()
+    t_train = time.perf_counter() - t0
+    after = held_out_loss()
+    vol = recon_hybrid.reshape(recon_hybrid.shape[:3] + (16,))
+    vol_signals = (1000.0 * vol / (vol[..., 0:1] + 1e-7)).contiguous()                     # superresHybrid.py:131-138, every voxel
+    t0 = time.perf_counter()
+    D, T2, v = fitter.encode_volume(vol_signals)
+    torch.cuda.synchronize()
+    t_encode = time.perf_counter() - t0
+    maps = pia_net.detect_PIDS_slice(np.asarray(pia.BVALS), slice_signals.reshape(plane + (4, 4)).cpu().numpy())
+    return {"D": D.cpu().numpy(), "T2": T2.cpu().numpy(), "v": v.cpu().numpy(),
+            "pids": dict(zip(("PIDS_ADC1", "PIDS_ADC2", "PIDS_b_decay", "PIDS_TE_decay"), maps)),
+            "pia_loss_before": before, "pia_loss_after": after,
+            "pia_step_losses": torch.cat(step_losses).cpu().numpy() if step_losses else np.zeros(0, np.float32),
+            "t_pia_train": t_train, "t_pia_encode": t_encode, "t_hybrid_fit": t_train + t_encode, "model": model}
 
 
 def plan_volumes(volumes: Sequence[np.ndarray], steps: int, world: int, allow_sharding: bool = True, **fit_kwargs):

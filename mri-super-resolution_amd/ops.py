@@ -570,6 +570,7 @@ def siren_backward_train(desc: SirenDesc, params, grads, gy, workspace):
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
                    "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order
+PIA_LAUNCH_FAMILIES = ("pia_fwd", "pia_dx", "pia_dw", "pia_head")                        # INR_PIA_LF_*, a table of its own
 
 
 def launch_counts() -> dict:
@@ -578,6 +579,16 @@ def launch_counts() -> dict:
     for i, name in enumerate(LAUNCH_FAMILIES):
         n = C.c_int64(0)
         check(lib().inr_launch_count(i, C.byref(n)), "inr_launch_count")
+        out[name] = int(n.value)
+    return out
+
+
+def pia_launch_counts() -> dict:
+    """Launches each PIA kernel family has received since the last ``launch_counts_reset()``."""
+    out = {}
+    for i, name in enumerate(PIA_LAUNCH_FAMILIES):
+        n = C.c_int64(0)
+        check(lib().inr_pia_launch_count(i, C.byref(n)), "inr_pia_launch_count")
         out[name] = int(n.value)
     return out
 

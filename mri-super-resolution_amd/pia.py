@@ -78,3 +78,6 @@ def hybrid_fit(signals):
     v[:, 0:2] = x[:, 6:8]
     v[:, 2] = 1 - x[:, 6] - x[:, 7]
     return D, T2, v
+
+
+from .pia_net import PIA, ADC_slice, PiaFitter, detect_PIDS_slice, get_batch  # noqa: E402,F401  (the autoencoder half of PIA.py)

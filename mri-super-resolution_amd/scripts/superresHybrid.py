@@ -49,6 +49,12 @@ def build_parser():
     p.add_argument("--slice", type=int, default=9, dest="_slice", help="z-slice of the three-compartment fit (:127)")
     p.add_argument("--seed", type=int, default=None)
     p.add_argument("--fp16_targets", action="store_true", help="hold the normalised volume in half precision (BASELINE config 5)")
+    p.add_argument("--estimator", choices=("curve_fit", "pia"), default="curve_fit",
+                   help="compartment maps from the per-voxel least-squares fit of one slice (the reference's driver) or from a PIA "
+                        "autoencoder trained on synthetic batches and run over every voxel of the volume")
+    p.add_argument("--pia_steps", type=int, default=2000, help="training steps of the PIA estimator")
+    p.add_argument("--pia_batch", type=int, default=512, help="rows per synthetic training batch")
+    p.add_argument("--pia_noise", type=float, default=0.02, help="noise level of the synthetic training batches")
     return p
 
 
@@ -100,7 +106,9 @@ def run(args):
     res = drivers.fit_hybrid(raw, roi=roi, slice_index=args._slice, steps=args.number_of_epochs, seed=args.seed,
                              distributed=spread, gather_recon=spread, hidden_features=args.hidden_dim,
                              hidden_layers=args.num_layers, mapping_size=args.mapping_size, ff_scale=args.scale,
-                             target_dtype=np.float16 if args.fp16_targets else None)
+                             target_dtype=np.float16 if args.fp16_targets else None,
+                             **({"estimator": "pia", "pia_steps": args.pia_steps, "pia_batch": args.pia_batch,
+                                 "pia_noise": args.pia_noise} if args.estimator == "pia" else {}))
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     if rank != 0:
@@ -111,6 +119,8 @@ def run(args):
         fh.write(SSIM_HEADER_HYBRID)
     recon = res["recon_hybrid"].cpu().numpy()
     bins = res["v"].shape[:2]
+    if args.estimator == "pia":
+        return _write_pia(args, res, recon, out_dir, pt_id, roi, bvalues, te_values, dt)
     v_ep, v_lu = res["v"][..., 0], res["v"][..., 2]
     cancer = remove_small_objects((v_ep > 0.4) & (v_lu <= 0.2), 12)                       # :163-178
     adc_map = inr.calculate_ADC(bvalues, np.squeeze(recon[:, :, args._slice, :, 0]))      # :173
@@ -124,6 +134,29 @@ def run(args):
                "seconds": dt, "t_fit_s": res["t_fit"], "t_recon_s": res["t_recon"], "t_hybrid_fit_s": res["t_hybrid_fit"],
                "final_losses": res["final_losses"], "cancer_pixels": int(cancer.sum()),
                "voxel_fits_converged": float((res["status"] > 0).mean())}
+    with open(os.path.join(out_dir, "metrics.json"), "w") as fh:
+        json.dump(summary, fh, indent=1)
+    print(json.dumps(summary))
+    return summary
+
+
+def _write_pia(args, res, recon, out_dir, pt_id, roi, bvalues, te_values, dt):
+    """Outputs of ``--estimator pia``: volume-shaped maps, the PIDS maps of the slice, the cancer map of that slice."""
+    v_slice = res["v"][:, :, args._slice]
+    cancer = remove_small_objects((v_slice[..., 0] > 0.4) & (v_slice[..., 2] <= 0.2), 12)
+    adc_map = inr.calculate_ADC(bvalues, np.squeeze(recon[:, :, args._slice, :, 0]))
+    matio.savemat(os.path.join(out_dir, "hybrid.mat"), {
+        "recon_hybrid": recon, "D": res["D"], "T2": res["T2"], "v": res["v"], "adc_map": adc_map,
+        "cancer_map": cancer.astype(np.uint8), "b": bvalues, "TE": te_values, "slice": np.array([args._slice], np.int32),
+        **{k: np.asarray(m) for k, m in res["pids"].items()}})
+    np.save(os.path.join(out_dir, "recon_hybrid.npy"), recon)
+    summary = {"pt_id": str(pt_id), "input": os.path.abspath(args.data), "roi": list(roi), "slice": int(args._slice),
+               "recon_shape": list(recon.shape), "map_shape": list(res["v"].shape[:3]), "steps": int(args.number_of_epochs),
+               "seconds": dt, "t_fit_s": res["t_fit"], "t_recon_s": res["t_recon"], "estimator": "pia",
+               "pia_steps": int(args.pia_steps), "pia_batch": int(args.pia_batch), "pia_noise": float(args.pia_noise),
+               "t_pia_train_s": res["t_pia_train"], "t_pia_encode_s": res["t_pia_encode"],
+               "pia_loss_before": res["pia_loss_before"], "pia_loss_after": res["pia_loss_after"],
+               "final_losses": res["final_losses"], "cancer_pixels": int(cancer.sum())}
     with open(os.path.join(out_dir, "metrics.json"), "w") as fh:
         json.dump(summary, fh, indent=1)
     print(json.dumps(summary))
