@@ -404,6 +404,36 @@ int inr_rams_shift_loss_grad(double* loss, float* grad_pred, const float* y_true
                              const float* upstream, int n_images, int size, int border, void* workspace,
                              size_t workspace_bytes, void* stream);
 
+/* ---- a-15 (loss side): the shift-tolerant SSIM, cSSIM (multi-image-super-resolution/utils/loss.py:131-177 `ssim`).
+ * y_true, y_pred, mask: [n_images][size][size] fp32; c = size - 2*border, P = y_pred cropped by `border`.  For every label
+ * shift (i, j) in [0, 2*border]^2, with L and M the c x c windows of y_true and mask at offset (i, j):
+ *   tot = sum M;  b = sum(L M - P M) / tot;  x = (P M + b) M;  y = L M;  s_ij = SSIM_tf(x, y, max_val = 65535);
+ *   clear_only != 0: s_ij = (s_ij - 1) * tot / c^2 + 1;            out[b] (double) = max over (i, j) of s_ij
+ * (the reference then averages over b).  SSIM_tf is tf.image.ssim with its defaults: window = outer product of
+ * g[k] ~ exp(-k^2 / (2 * 1.5^2)), k = -5..5, normalised to sum 1, applied as a 'VALID' correlation (maps of (c-10)^2);
+ * mu_x = G*x, mu_y = G*y, l = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1), cs = (2 G*(xy) - 2 mu_x mu_y + C2) /
+ * (G*(x^2 + y^2) - mu_x^2 - mu_y^2 + C2), C1 = (0.01 * 65535)^2, C2 = (0.03 * 65535)^2, no sample-covariance correction;
+ * SSIM = mean of l * cs over the map.  The mask need not be binary (no power of M is folded).  All arithmetic is fp64 on the
+ * fp32 inputs, every reduction has a fixed order: repeated calls are bit-equal.  On return the first
+ * n_images * (2*border+1)^2 doubles of the workspace hold the table s_ij ([b][i][j]).
+ * A window without a clear pixel (tot = 0) is undefined in the reference (0/0): its s_ij is NaN here, the maximum passes NaN
+ * entries over, and out[b] is NaN only when every shift of image b is.
+ * Checked before any device work: null pointers, 1 <= n_images <= 65535, 0 <= border <= 16, size <= 8192 and
+ * size - 2*border >= 11 (INR_E_INVALID); workspace null or too small (INR_E_WORKSPACE), not 8-byte aligned (INR_E_ALIGN).
+ * The definition is restated from TensorFlow's documentation and the reference's source: it is pinned to a float64
+ * restatement and to analytic cases, not to TensorFlow's own output. */
+size_t inr_rams_shift_ssim_workspace_bytes(int n_images, int size, int border);
+int inr_rams_shift_ssim(double* out, const float* y_true, const float* y_pred, const float* mask, int n_images, int size,
+                        int border, int clear_only, void* workspace, size_t workspace_bytes, void* stream);
+/* loss[b] = 1 - cSSIM_b as above and grad_pred[b] = upstream[b] * d loss[b] / d y_pred[b] ([n_images][size][size] fp32, zero
+ * on the `border` frame), taken through image b's best shift as TensorFlow's reduce_max does (the first best shift on an exact
+ * tie), including the path through the brightness bias b, which depends on every masked pixel of P.  upstream nullable (= 1).
+ * The table s_ij is left in the workspace as by inr_rams_shift_ssim; the same argument checks apply. */
+size_t inr_rams_shift_ssim_grad_workspace_bytes(int n_images, int size, int border);
+int inr_rams_shift_ssim_grad(double* loss, float* grad_pred, const float* y_true, const float* y_pred, const float* mask,
+                             const float* upstream, int n_images, int size, int border, int clear_only, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
 /* ---- (f)-1: three-compartment hybrid fit (PIA.py:240-283 `three_compartment_fit` / `hybrid_fit`, called at
  * superresHybrid.py:140).  signals: [n_voxels][16] fp64, b-major over b = {0,150,1000,1500} x TE = {0,13,93,143}
  * (the order of PIA.py:263-265).  Runs scipy's bounded trust-region-reflective least squares (what

@@ -148,6 +148,12 @@ SIGNATURES = {
     "inr_rams_shift_loss_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "inr_rams_shift_loss_grad": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int,
                                            C.c_void_p, C.c_size_t, c_stream]),
+    "inr_rams_shift_ssim_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "inr_rams_shift_ssim": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_void_p, C.c_size_t, c_stream]),
+    "inr_rams_shift_ssim_grad_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "inr_rams_shift_ssim_grad": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p, C.c_size_t, c_stream]),
     "inr_hybrid_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
     "inr_pia_param_count": (C.c_int64, [C.POINTER(PiaDesc)]),
     "inr_pia_param_offsets": (C.c_int, [C.POINTER(PiaDesc), c_i64p, C.c_int]),

@@ -136,6 +136,14 @@ int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_
 int launch_adc(float* out, const float* data, const float* bvals, int64_t npix, int nb, hipStream_t st);
 int launch_auto_erd(float* accept, const double* values, const float* erd_map, int64_t npix, int n, int rule, hipStream_t st);
 
+// ---- cssim.hip: the shift-tolerant SSIM of the RAMS tree (utils/loss.py:131-177) and its gradient ---------------------------------------
+int cssim_min_crop();   // the cropped window must hold one 11 x 11 filter window
+size_t cssim_workspace_doubles(int nimg, int size, int border, bool grad);
+int launch_cssim(double* out, const float* y_true, const float* y_pred, const float* mask, int nimg, int size, int border,
+                 int clear_only, double* ws, hipStream_t st);
+int launch_cssim_grad(double* loss, float* grad, const float* y_true, const float* y_pred, const float* mask,
+                      const float* upstream, int nimg, int size, int border, int clear_only, double* ws, hipStream_t st);
+
 // ---- hybrid_fit.hip -----------------------------------------------------------------------------------------------------------------------
 int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, const double* signals, int64_t n,
                       hipStream_t st);

@@ -303,6 +303,58 @@ def l1_loss_and_grad(y_true, y_pred, y_mask, HR_SIZE=384, upstream=None):
     return loss, grad
 
 
+def _ssim_inputs(y_true, y_pred, y_mask, size):
+    dev = ops.require_gpu()
+
+    def prep(t):
+        t = torch.as_tensor(np.asarray(t, np.float32) if not torch.is_tensor(t) else t).to(dev, torch.float32)
+        if t.dim() == 4 and t.shape[-1] == 1:
+            t = t[..., 0]
+        if t.dim() != 3 or t.shape[1] != size or t.shape[2] != size:
+            raise ValueError(f"expected [B, {size}, {size}(, 1)], got {tuple(t.shape)}")
+        return t.contiguous()
+
+    yt, yp, mk = prep(y_true), prep(y_pred), prep(y_mask)
+    if not (yt.shape == yp.shape == mk.shape):
+        raise ValueError("y_true / y_pred / y_mask shape mismatch")
+    return dev, yt, yp, mk
+
+
+def ssim_per_image(y_true, y_pred, y_mask, size_image=384, clear_only=False, return_table=False):
+    """utils/loss.py:131-177 before its batch mean: per image, the maximum over the 7x7 label shifts of ``tf.image.ssim`` (11 x 11
+    Gaussian window, sigma 1.5, max_val 65535) between the brightness-corrected masked prediction and the masked label;
+    ``clear_only`` rescales by the share of clear pixels.  [B] float64; with ``return_table`` also the per-shift values
+    [B, 7, 7].  The definition is restated from TensorFlow's documentation and the reference's source (TensorFlow cannot be
+    run here): it is pinned to a float64 restatement and to analytic cases, not to the reference's own output."""
+    dev, yt, yp, mk = _ssim_inputs(y_true, y_pred, y_mask, int(size_image))
+    B = yt.shape[0]
+    out = torch.empty(B, dtype=torch.float64, device=dev)
+    ws = torch.empty((lib().inr_rams_shift_ssim_workspace_bytes(B, int(size_image), 3) + 7) // 8, dtype=torch.float64, device=dev)
+    check(lib().inr_rams_shift_ssim(out.data_ptr(), yt.data_ptr(), yp.data_ptr(), mk.data_ptr(), B, int(size_image), 3,
+                                    1 if clear_only else 0, ws.data_ptr(), ws.numel() * 8, ops._stream()), "inr_rams_shift_ssim")
+    return (out, ws[:B * 49].reshape(B, 7, 7).clone()) if return_table else out
+
+
+def ssim(y_true, y_pred, y_mask, size_image=384, clear_only=False):
+    """utils/loss.py:131-177: mean over the batch of the maximum cSSIM over the 7x7 shifts (see ``ssim_per_image``)."""
+    return ssim_per_image(y_true, y_pred, y_mask, size_image, clear_only).mean()
+
+
+def ssim_loss_and_grad(y_true, y_pred, y_mask, HR_SIZE=384, upstream=None, clear_only=False):
+    """``loss[b] = 1 - cSSIM_b`` (utils/loss.py:131-177) and the gradient of ``sum_b upstream[b] * loss[b]`` with respect to
+    ``y_pred`` ([B, S, S] fp32), through each image's best shift and through the brightness bias; zero on the border frame."""
+    dev, yt, yp, mk = _ssim_inputs(y_true, y_pred, y_mask, int(HR_SIZE))
+    B = yt.shape[0]
+    up = None if upstream is None else torch.as_tensor(upstream, dtype=torch.float32, device=dev).contiguous()
+    loss = torch.empty(B, dtype=torch.float64, device=dev)
+    grad = torch.empty_like(yp)
+    ws = torch.empty((lib().inr_rams_shift_ssim_grad_workspace_bytes(B, int(HR_SIZE), 3) + 7) // 8, dtype=torch.float64, device=dev)
+    check(lib().inr_rams_shift_ssim_grad(loss.data_ptr(), grad.data_ptr(), yt.data_ptr(), yp.data_ptr(), mk.data_ptr(),
+                                         0 if up is None else up.data_ptr(), B, int(HR_SIZE), 3, 1 if clear_only else 0,
+                                         ws.data_ptr(), ws.numel() * 8, ops._stream()), "inr_rams_shift_ssim_grad")
+    return loss, grad
+
+
 # ---- building blocks of the training step: the 3x3x3 convolution 32 -> 32 with its two gradients -----------------------
 def _conv_tensors(x, w, name):
     dev = ops.require_gpu()
@@ -450,11 +502,13 @@ class RamsTrainer:
         return self.model
 
     # ---- the outer loop (utils/training.py:108-191, 211-220) ---------------------------------------------------------------------
-    def test_step(self, lr_batch, hr, mask):
-        """training.py:211-220: forward (no update), per-image cL1 and the batch's cPSNR."""
+    def test_step(self, lr_batch, hr, mask, with_ssim=False):
+        """training.py:211-220: forward (no update), per-image cL1 and the batch's cPSNR; ``with_ssim`` adds the batch's cSSIM
+        (utils/loss.py:131-177) as a third value."""
         size = int(np.asarray(hr).shape[1]) if not torch.is_tensor(hr) else int(hr.shape[1])
         sr = self.sync_model().forward(lr_batch)
-        return l1_loss(hr, sr, mask, HR_SIZE=size), psnr(hr, sr, mask, size_image=size)
+        pair = l1_loss(hr, sr, mask, HR_SIZE=size), psnr(hr, sr, mask, size_image=size)
+        return pair + (ssim(hr, sr, mask, size_image=size),) if with_ssim else pair
 
     def save_checkpoint(self, directory, psnr_value, max_to_keep=3):
         """``tf.train.CheckpointManager(max_to_keep=3).save()`` (training.py:88-91, 187): step, best PSNR, variables, Adam state."""

@@ -7,6 +7,9 @@ super-resolved x3 by ``RAMS(3, 32, 3, 9, 8, 12)`` through ``predict_tensor`` and
 Flags: the reference's three (master.py:13-15: ``--out_folder``, ``--out_img_folder``, ``--exp_name``) with the same names and
 defaults, plus what the reference hard-codes or leaves undefined: ``--data_dir`` / ``--cases`` (the patient table ``cases`` that
 master.py:1 imports was never published: a JSON list of ``case`` constructor arguments, as for ``scripts/master.py``),
+``--ssim`` (adds ``cssim_vs_rescaled`` to every case record: the shift-tolerant SSIM of ``utils/loss.py:131-177`` between the
+super-resolved mean and the x3 linear rescale of the acquisition mean of the same slice -- there is no high-resolution label at
+inference, so this is a structure-agreement figure; without the flag nothing is computed or written differently),
 ``--weights`` (an ``.npz`` of the network's variables, ``RAMS.save_weights``: the checkpoint under ``ckpt/RED_RAMS`` that
 master.py:27-33 restores is shipped WITHOUT its ``*.data-00001-of-00002`` shard and there is no TensorFlow here to read one --
 without ``--weights`` the network keeps its random initialisation and the script says so), ``--sample_size`` (25) and ``--seed``
@@ -27,7 +30,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 from mri_super_resolution_amd import baselines, contrast, matio  # noqa: E402
-from mri_super_resolution_amd.rams import RAMS, predict_tensor  # noqa: E402
+from mri_super_resolution_amd.rams import RAMS, predict_tensor, ssim_per_image  # noqa: E402
 
 SCALE = 3           # master.py:20-26
 FILTERS = 32
@@ -49,6 +52,8 @@ def build_parser():
     parser.add_argument('--weights', default=None, help='.npz of the RAMS variables (<layer>/v|g|b); random initialisation otherwise')
     parser.add_argument('--sample_size', type=int, default=25, help='random 9-acquisition subsets per case (master.py:44)')
     parser.add_argument('--seed', type=int, default=None, help='seed of the subset draws (the reference draws unseeded)')
+    parser.add_argument('--ssim', action='store_true', help='add cssim_vs_rescaled (cSSIM, utils/loss.py:131-177, of the mean '
+                                                            'prediction against the rescaled acquisition mean) to every case record')
     return parser
 
 
@@ -71,6 +76,17 @@ def super_resolve_case(model, case, sample_size=25, rng=random):
     adc_large = -np.log((mean_pred / (b0_scaled + eps)) + eps) / case.b
     adc_large *= 1000000
     return mean_pred, adc_large, subsets
+
+
+def cssim_vs_rescaled(mean_pred, case, scale):
+    """cSSIM (7 x 7 shifts, all pixels clear) of the super-resolved mean against the linear x``scale`` rescale of the acquisition
+    mean of the same x256 uint16 slice, on the central square of a non-square slice."""
+    lor = case.dwi[:, :, case.cancer_slice, :].astype('uint16') * 256                        # master.py:40-42
+    ref = baselines.rescale(lor.astype(np.float64).mean(axis=-1), scale, anti_aliasing=False)
+    s = min(mean_pred.shape)
+    r0, c0 = (mean_pred.shape[0] - s) // 2, (mean_pred.shape[1] - s) // 2
+    crop = lambda a: np.ascontiguousarray(a[r0:r0 + s, c0:c0 + s], np.float32)[None]
+    return float(ssim_per_image(crop(ref), crop(mean_pred), np.ones((1, s, s), np.float32), size_image=s)[0])
 
 
 def run(args, cases):
@@ -96,6 +112,8 @@ def run(args, cases):
         matio.savemat(os.path.join(out_dir, 'images.mat'), {'DWI_mean': mean_pred, 'ADC_mean': adc_large})
         summary.append({"patient": pt_no, "shape": list(mean_pred.shape), "sample_size": args.sample_size, "seconds": dt,
                         "subsets": subsets, "out_dir": out_dir})
+        if getattr(args, "ssim", False):
+            summary[-1]["cssim_vs_rescaled"] = cssim_vs_rescaled(mean_pred, case, rams_network.cfg["scale"])
     with open(os.path.join(args.out_folder, args.exp_name + '.json'), 'w') as fh:
         json.dump({"weights": args.weights, "cases": summary}, fh)
     return {"cases": summary, "weights": args.weights}
