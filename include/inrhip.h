@@ -522,6 +522,67 @@ int inr_pids_slice(float* adc_high, float* adc_negative, float* b_decay, float* 
 int inr_auto_erd(float* accept, const double* values, const float* erd_map, int64_t n_pixels, int n_acquisitions, int rule,
                  void* stream);
 
+/* ---- the soft-ERD INR family (INR_ERD.py:28-67 `Siren`, prepare_qual_images.py:66-102) --------------------------------------------
+ * Trunk: SineLayer(in -> H, first), hidden_layers x SineLayer(H -> H), Linear(H -> H) + ReLU; head Linear(H -> 1) + ReLU; the
+ * in-module perturbation p = eps tanh(W2 tanh(W1 [x, sample] + b1) + b2) ([n][1]) is ADDED TO EVERY coordinate component
+ * before the trunk (INR_ERD.py:56-63; `sample` enters as the plain acquisition index).  The descriptor is inr_siren_desc_t
+ * with out_features == 1, in_features <= 8, hidden_features in {64, 128}, hidden_layers <= 8 (INR_E_INVALID otherwise: there
+ * is no other path).  Flat parameter buffer, every tensor padded to 16 bytes: trunk layer 0 .. hidden_layers + 1 (weight,
+ * bias), head, perturb_linear, perturb_linear2.  Group A = trunk + head = [0, group_b), group B = the perturb branch.
+ * Kernels: f32-input MFMA 32x32x2, hardware sin/cos, per-wave gradient slabs summed in a fixed order (bitwise reproducible). */
+#define INR_ERD_RUNNING   0
+#define INR_ERD_CONVERGED 1   /* the step whose forward loss was the first <= threshold has been applied; it was the last */
+#define INR_ERD_COLLAPSED 2   /* every output of the last applied step's forward was 0 (tested first: it wins) */
+int64_t inr_erd_param_count(const inr_siren_desc_t* desc);                  /* -1 for a descriptor the kernels do not serve */
+/* offsets[2 t], offsets[2 t + 1] = weight / bias of tensor t (hidden_layers + 5 tensors), then group_b; max_entries counts them */
+int     inr_erd_param_offsets(const inr_siren_desc_t* desc, int64_t* offsets, int max_entries);
+size_t  inr_erd_workspace_bytes(const inr_siren_desc_t* desc, int64_t n);   /* 0 for a shape the kernels do not serve */
+/* INR_ERD.py:54-67 forward at inference, `chunk_rows` rows per launch; the result does not depend on the chunk size, bit for bit */
+int inr_erd_forward(const inr_siren_desc_t* desc, const float* params, const float* x, int64_t n, float* y, int sample, float eps,
+                    int perturb, int64_t chunk_rows, void* stream);
+/* One acquisition of INR_ERD.py:259-267: loss = mean(w (f(x; sample, eps) - target)^2) (weight nullable = 1) and its gradient
+ * for every parameter.  accumulate != 0 adds loss and gradient to those of the previous calls on this workspace (same n), so
+ * `grads` / `*loss` then hold the sums; the slabs are summed in a fixed order. */
+int inr_erd_loss_grad(const inr_siren_desc_t* desc, const float* params, float* grads, const float* x, const float* target,
+                      const float* weight, int64_t n, int sample, float eps, int perturb, int accumulate, float* loss,
+                      void* workspace, size_t workspace_bytes, void* stream);
+/* Adam with two parameter groups (INR_ERD.py:252-255, 272-273): lr_net for group A, lr_perturb for group B; the arithmetic of
+ * inr_adam_step on each group's range.  `step` is the 1-based Adam step of both groups. */
+int inr_erd_adam_step(const inr_siren_desc_t* desc, float* params, const float* grads, float* m, float* v, int64_t step,
+                      double lr_net, double lr_perturb, double beta1, double beta2, double eps, void* stream);
+/* The pre-training loop INR_ERD.py:201-217 without a host read per step: enqueues max_steps x (step kernel, reduce + Adam +
+ * status kernel) and returns.  status (device, 16 bytes) = {int state, int steps_done, float last_loss, float y_max}; the
+ * caller initialises it to {INR_ERD_RUNNING, 0, 0, 0} and reads it when it likes.  Every kernel returns at entry unless the
+ * state is RUNNING, so a call on a finished status changes nothing.  Unweighted, perturbation off, one learning rate.
+ * first_step = the 1-based Adam step of the first enqueued step (steps_done + 1 of a status that is still RUNNING).
+ * Where the reference would, on a step that both converges and collapses, leave its loop with a freshly initialised network,
+ * this reports COLLAPSED and the caller re-initialises and goes on. */
+int inr_erd_pretrain(const inr_siren_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x,
+                     const float* target, int64_t n, int64_t first_step, int max_steps, double lr, double beta1, double beta2,
+                     double eps, float threshold, int* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The fine-tuning step INR_ERD.py:252-273, n_steps times: loss = sum_s mean(w_s (f(x; s, eps) - g_s)^2) over the n_acq
+ * acquisitions (targets, weights: [n_acq][n]; weights nullable) = n_acq accumulating step launches + one reduce / dual-Adam
+ * launch.  losses [n_steps] (nullable) receives each step's loss before its update. */
+int inr_erd_finetune(const inr_siren_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x,
+                     const float* targets, const float* weights, int n_acq, int64_t n, float perturb_eps, int64_t first_step,
+                     int n_steps, double lr_perturb, double lr_net, double beta1, double beta2, double eps, float* losses,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* Soft-ERD acquisition weights and the weighted mean image (INR_ERD.py:143-158, 225-235), one launch for all pixels, float64:
+ * values [n_pixels][K], b0 [n_pixels]; temp = max(mul exp(-slope mean(x) / b0), min_temp); where mean(x) > 2 noise_level:
+ * weights = exp(x / temp) (UNNORMALISED, as the reference hands it to the loss) and mean_image = the softmax-weighted mean
+ * (computed with the maximum subtracted); elsewhere weights = 1 / K and mean_image = mean(x).  b0 == 0 follows IEEE.
+ * *nonfinite_count (device int) receives the number of non-finite weights. */
+int inr_soft_erd(double* weights, double* mean_image, const double* values, const double* b0, int64_t n_pixels, int n_acquisitions,
+                 double noise_level, double mul, double slope, double min_temp, int* nonfinite_count, void* stream);
+/* Launch families of these kernels.  inr_launch_count serves them under ids of their own, above the INR_LF_* table (whose count
+ * callers pin); inr_launch_counts_reset() clears them too. */
+#define INR_LF_ERD_BASE    32
+#define INR_LF_ERD_STEP    32   /* erd_step_kernel<H, train>: forward + loss + backward of 32 rows per wave */
+#define INR_LF_ERD_REDUCE  33   /* erd_reduce_kernel: fixed-order slab sum (+ dual Adam, + status) */
+#define INR_LF_ERD_FORWARD 34   /* erd_step_kernel<H, inference> */
+#define INR_LF_ERD_SOFT    35   /* soft_erd_kernel */
+#define INR_LF_ERD_END     36
+
 /* ---- measurement hooks (bench.py roofline): per-kernel-class HIP-event timing on the launch stream.
  * class ids: 0 = GEMM forward (sine layer), 1 = GEMM input-grad, 2 = GEMM param-grad, 3 = other */
 int  inr_prof_enable(int enable);

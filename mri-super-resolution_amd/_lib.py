@@ -19,6 +19,8 @@ c_ptr_array = C.POINTER(C.c_void_p)   # host array of device pointers (nullable 
 INR_E_INVALID, INR_E_WORKSPACE, INR_E_ALIGN, INR_E_TIMEOUT = -1, -2, -3, -4     # include/inrhip.h
 INR_LF_COUNT = 14
 INR_PIA_LF_COUNT = 4
+INR_LF_ERD_STEP, INR_LF_ERD_REDUCE, INR_LF_ERD_FORWARD, INR_LF_ERD_SOFT = 32, 33, 34, 35
+INR_ERD_RUNNING, INR_ERD_CONVERGED, INR_ERD_COLLAPSED = 0, 1, 2
 
 
 class InrHipError(RuntimeError):
@@ -169,6 +171,23 @@ SIGNATURES = {
     "inr_pia_launch_count": (C.c_int, [C.c_int, c_i64p]),
     "inr_pids_slice": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
     "inr_auto_erd": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
+    "inr_erd_param_count": (C.c_int64, [C.POINTER(SirenDesc)]),
+    "inr_erd_param_offsets": (C.c_int, [C.POINTER(SirenDesc), c_i64p, C.c_int]),
+    "inr_erd_workspace_bytes": (C.c_size_t, [C.POINTER(SirenDesc), C.c_int64]),
+    "inr_erd_forward": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_int, C.c_float, C.c_int,
+                                  C.c_int64, c_stream]),
+    "inr_erd_loss_grad": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_float,
+                                    C.c_int, C.c_int, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_erd_adam_step": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_double, C.c_double,
+                                    C.c_double, C.c_double, C.c_double, c_stream]),
+    "inr_erd_pretrain": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64,
+                                   C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_size_t, c_stream]),
+    "inr_erd_finetune": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int,
+                                   C.c_int64, C.c_float, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                   C.c_double, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_soft_erd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double,
+                               C.c_double, C.c_double, C.c_void_p, c_stream]),
     "inr_prof_enable": (C.c_int, [C.c_int]),
     "inr_prof_reset": (C.c_int, []),
     "inr_prof_read": (C.c_int, [C.c_int, c_i64p, C.POINTER(C.c_double)]),

@@ -1714,6 +1714,7 @@ int inr_debug_reset(void) {
 }
 
 int inr_launch_count(int family, int64_t* count) {
+    if (family >= INR_LF_ERD_BASE && family < INR_LF_ERD_END && count) return erd_launch_count(family, count);
     INR_REQUIRE(family >= 0 && family < LF_COUNT && count, INR_E_INVALID, "inr_launch_count: bad arguments");
     *count = (int64_t)g_launches[family].load(std::memory_order_relaxed);
     return 0;
@@ -1722,6 +1723,7 @@ int inr_launch_count(int family, int64_t* count) {
 int inr_launch_counts_reset(void) {
     for (int f = 0; f < LF_COUNT; ++f) g_launches[f].store(0, std::memory_order_relaxed);
     pia_launch_counts_reset();
+    erd_launch_counts_reset();
     return 0;
 }
 

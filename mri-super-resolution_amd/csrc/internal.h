@@ -152,6 +152,10 @@ void set_hybrid_variant(int v);   // key 2
 // ---- pia.hip: the PIA autoencoder; its launch families are counted in a table of their own (inr_pia_launch_count) ---------------------
 void pia_launch_counts_reset();
 
+// ---- erd_siren.hip: the soft-ERD INR family; its launch families (INR_LF_ERD_*) are counted in a table of their own ------------------
+void erd_launch_counts_reset();
+int erd_launch_count(int family, int64_t* count);   // family in [INR_LF_ERD_BASE, INR_LF_ERD_END)
+
 // ---- rams.hip (+ rams_train.inc) ---------------------------------------------------------------------------------------------------------
 long long rams_param_floats(const inr_rams_desc_t* d);
 size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W);

@@ -666,3 +666,58 @@ def run_volumes(volumes: Sequence[np.ndarray], steps: int = 2500, allow_sharding
         raise FitError(f"run_volumes: fits of volumes {still} raised and no rank could take them over "
                        f"(errors='record' returns the NaN records instead)", records)
     return records
+
+
+# ---------------------------------------------------------------------------------------------------
+# INR_ERD.py:170-303 -- the soft-ERD INR of one (seed, case): pre-train on the soft-ERD mean image, one dual-learning-rate
+# fine-tuning step on the weighted acquisitions, mean reconstruction, four rows of SNR / CNR figures
+# ---------------------------------------------------------------------------------------------------
+def erd_inr_case(case, seed, scale=1, hidden_features=128, hidden_layers=3, pretrain_lr=3e-4, threshold=2e-5, max_steps=None,
+                 finetune_steps=1, lr_perturb=3e-4, lr_net=1e-7, perturb_eps=1.0 / 128.0, mul=1000, slope=20):
+    """``case`` carries ``pt_id, b, cancer_loc, contralateral_loc, noise, cancer_slice`` and the arrays ``b0`` [X, Y, Z] and
+    ``b3`` [X, Y, Z, K].  Returns ``(rows, info)``: the four CSV rows of INR_ERD.py:293-296 and what the fit did.  Targets are
+    normalised as the reference's dataset does (nn_mri.py:174-180: pixel -> 2 pixel - 1).  ``scale`` > 1 evaluates the mean
+    reconstruction on a ``scale`` times finer grid (the landmarks scale with it); 1 is the reference's grid.
+    One difference from INR_ERD.py as written, beside the collapse-wins rule of the pre-training loop: the model is built with
+    ``perturb=True``, so the fine-tuning step and the mean reconstruction run with the coordinate perturbation
+    (prepare_qual_images.py's behaviour).  INR_ERD.py builds its ``Siren`` with ``perturb=False`` and never switches it on: there
+    both run unperturbed and the ``perturb_linear*`` tensors never move."""
+    from . import erd_inr
+
+    dev = ops.require_gpu()
+    sl = case.cancer_slice
+    b = case.b[3]
+    b0 = np.asarray(case.b0[:, :, sl], dtype=np.float64)
+    dwi = np.asarray(case.b3[:, :, sl, :], dtype=np.float64)
+    K = dwi.shape[-1]
+    level = erd_inr.noise_level(case.b3, case.noise, sl)
+    weights, mean_image = erd_inr.soft_erd(dwi, b0, level, mul=mul, slope=slope)
+
+    model = erd_inr.ErdSiren(in_features=2, out_features=1, hidden_features=hidden_features, hidden_layers=hidden_layers,
+                             perturb=True).to(dev)
+    fitter = erd_inr.ErdFitter(model)
+    coords = ops.mgrid(b0.shape)
+    norm = lambda a: torch.from_numpy(2.0 * np.asarray(a, dtype=np.float32) - 1.0).reshape(-1).to(dev)      # noqa: E731
+    pre = fitter.pretrain(coords, norm(mean_image), lr=pretrain_lr, threshold=threshold, max_steps=max_steps)
+    targets = torch.stack([norm(dwi[:, :, a]) for a in range(K)])
+    wts = torch.stack([torch.from_numpy(weights[:, :, a].astype(np.float32)).reshape(-1) for a in range(K)]).to(dev)
+    losses = fitter.finetune(coords, targets, wts, steps=finetune_steps, lr_perturb=lr_perturb, lr_net=lr_net, eps=perturb_eps)
+
+    img = dwi.mean(-1)
+    out_shape = tuple(int(s) * int(scale) for s in b0.shape)
+    mean_recon = fitter.mean_reconstruction(out_shape, K, eps=perturb_eps)
+    adc_in = erd_inr.calc_adc(img, b0, b)
+    b0_out = b0 if scale == 1 else np.kron(b0, np.ones((scale, scale)))
+    adc_out = erd_inr.calc_adc(mean_recon, b0_out, b)
+
+    from types import SimpleNamespace
+    scaled = SimpleNamespace(cancer_loc=tuple(int(v) * int(scale) for v in case.cancer_loc),
+                             contralateral_loc=tuple(int(v) * int(scale) for v in case.contralateral_loc),
+                             noise=tuple(int(v) * int(scale) for v in case.noise))
+    rows = []
+    for image, at, kind, tag, digits in ((img, case, "DWI", "orig", 3), (mean_recon, scaled, "DWI", "recon", 3),
+                                         (adc_in, case, "ADC", "orig", 3), (adc_out, scaled, "ADC", "recon", 4)):
+        rows.append([str(seed)] + [round(float(v), digits) for v in erd_inr.calculate_CNR_SNR(at, image)] + [case.pt_id, kind, tag])
+    info = {"pretrain": pre, "finetune_loss": float(losses[-1]) if finetune_steps else float("nan"), "noise_level": float(level),
+            "mean_recon": mean_recon, "model": model}
+    return rows, info
