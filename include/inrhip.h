@@ -583,6 +583,48 @@ int inr_soft_erd(double* weights, double* mean_image, const double* values, cons
 #define INR_LF_ERD_SOFT    35   /* soft_erd_kernel */
 #define INR_LF_ERD_END     36
 
+/* ---- spatial derivatives of a fitted SIREN (nn_mri.py:205-221 `gradient`, `divergence`, `laplace`) -------------------------------
+ * The reference differentiates the network with two torch.autograd.grad passes with create_graph=True (a graph of the first
+ * backward pass, then its backward).  These entry points evaluate the same quantities in FORWARD mode, without a stash and
+ * without autograd: per row and layer they carry the value, one tangent per coordinate axis and a Laplacian accumulator
+ * (DESIGN.md 4d), on the f32-input MFMA (v_mfma_f32_32x32x2_f32) with the hardware sin / cos of the sine-layer epilogues.
+ *   y[n]               = network(features(x))                          (no clamp)
+ *   grad[n][d_tangent] = d y / d x_i, i < d_tangent                    (nullable)
+ *   lap[n]             = sum_{i < d_tangent} d^2 y / d x_i^2           (nullable; without it the accumulator is neither computed
+ *                                                                       nor carried)
+ * x[n][d] are the network's coordinates -- the [-1, 1] coordinates of inr_mgrid; multiply a first derivative along axis a by
+ * 2 / (shape[a] - 1) (a second one by its square) for per-voxel units.  B == NULL: the coordinates feed the network
+ * (in_features == d); otherwise features = [sin(2 pi x B^T) | cos(2 pi x B^T)], B[m][d], in_features == 2 m, as inr_fourier_map.
+ * d_tangent names the LEADING axes to differentiate along (1 <= d_tangent <= d): a DWI volume's grid (x, y, z, b) takes 3.
+ * `params` is the flat buffer of inr_siren_param_offsets.  Rows are processed `chunk_rows` at a time in `workspace`
+ * (inr_siren_jet_workspace_bytes(desc, d, m, min(chunk_rows, n), want_laplacian) bytes, m = 0 without B; sized for d tangents, so
+ * it serves every d_tangent); a row's bits depend neither on the chunk size nor on which of grad / lap were asked for, and
+ * repeated calls are bit-equal (fixed summation order, no float atomics).  Both calls only enqueue.
+ * Served: out_features == 1, 1 <= d <= 4, hidden width a multiple of 32 up to 1024, at least one hidden layer; anything else,
+ * and a null desc / params / x / shape / y, is INR_E_INVALID with a message before any device work; a null or short workspace is
+ * INR_E_WORKSPACE, a params or workspace pointer off a 16-byte boundary INR_E_ALIGN, likewise before any device work.
+ * The split-fp16 operand path of the fit is not used here. */
+size_t inr_siren_jet_workspace_bytes(const inr_siren_desc_t* desc, int d, int m, int64_t chunk_rows, int want_laplacian);
+/* nn_mri.py:205-221 on explicit coordinate rows: replaces gradient(y, x) / laplace(y, x) = two autograd.grad passes with
+ * create_graph=True over model(x). */
+int inr_siren_jet(const inr_siren_desc_t* desc, const float* params, const float* x, int64_t n, int d, int d_tangent, const float* B,
+                  int m, float* y, float* grad, float* lap, int64_t chunk_rows, void* workspace, size_t workspace_bytes,
+                  void* stream);
+/* the same on the dense grid get_mgrid(shape) (dim == d axes), coordinates generated in the kernels as by inr_siren_reconstruct:
+ * replaces laplace(model(input_mapping(get_mgrid(shape), B)), coords) of nn_mri.py:205-221, i.e. two autograd.grad passes with
+ * create_graph=True over the whole re-sampling grid.  Bit-equal with inr_siren_jet on the rows of inr_mgrid(shape). */
+int inr_siren_jet_grid(const inr_siren_desc_t* desc, const float* params, const int64_t* shape, int dim, int d_tangent,
+                       const float* B, int m, float* y, float* grad, float* lap, int64_t chunk_rows, void* workspace,
+                       size_t workspace_bytes, void* stream);
+/* Launch families of these kernels (nn_mri.py:205-221 has no counterpart: each stands for a slice of the two autograd.grad
+ * passes), counted like INR_LF_* but in a table of their own; inr_launch_counts_reset() clears it too.  Per chunk of rows:
+ * one INPUT launch, one LAYER launch per sine layer (one fewer without B: the first layer is the INPUT launch), one HEAD. */
+#define INR_JET_LF_INPUT 0   /* jet_fourier_kernel / jet_first_kernel: jets of the Fourier features, or the first sine layer on the VALU */
+#define INR_JET_LF_LAYER 1   /* jet_layer_kernel<J>: one sine layer on J planes, f32-input MFMA 32x32x2 */
+#define INR_JET_LF_HEAD  2   /* jet_head_kernel: J row dots, a wave per row */
+#define INR_JET_LF_COUNT 3
+int inr_jet_launch_count(int family, int64_t* count);
+
 /* ---- measurement hooks (bench.py roofline): per-kernel-class HIP-event timing on the launch stream.
  * class ids: 0 = GEMM forward (sine layer), 1 = GEMM input-grad, 2 = GEMM param-grad, 3 = other */
 int  inr_prof_enable(int enable);

@@ -12,10 +12,10 @@ rescale) . drivers.py (the reference's driver loops) . dist.py (fit partitioning
 """
 from ._lib import InrHipError, InrHipUnavailable  # noqa: F401
 from .ops import InrDeviceError  # noqa: F401
-from .inr import (ImageFitting_set, PN, ShardedSirenFitter, SineLayer, Siren, SirenFitter, calculate_ADC,  # noqa: F401
-                  calculate_combinations, fit_cycle_batch, fit_siren, flat_parameters, get_mgrid, input_mapping, reconstruct,
-                  resize_array)
+from .inr import (Derivatives, ImageFitting_set, PN, ShardedSirenFitter, SineLayer, Siren, SirenFitter, calculate_ADC,  # noqa: F401
+                  calculate_combinations, derivatives, divergence, fit_cycle_batch, fit_siren, flat_parameters, get_mgrid,
+                  gradient, input_mapping, laplace, reconstruct, resize_array)
 
-__all__ = ["ImageFitting_set", "PN", "ShardedSirenFitter", "SineLayer", "Siren", "SirenFitter", "calculate_ADC",
+__all__ = ["Derivatives", "derivatives", "divergence", "gradient", "laplace", "ImageFitting_set", "PN", "ShardedSirenFitter", "SineLayer", "Siren", "SirenFitter", "calculate_ADC",
            "calculate_combinations", "fit_cycle_batch", "fit_siren", "flat_parameters", "get_mgrid", "input_mapping",
            "reconstruct", "resize_array", "InrHipError", "InrHipUnavailable", "InrDeviceError"]

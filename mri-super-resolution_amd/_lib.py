@@ -19,6 +19,7 @@ c_ptr_array = C.POINTER(C.c_void_p)   # host array of device pointers (nullable 
 INR_E_INVALID, INR_E_WORKSPACE, INR_E_ALIGN, INR_E_TIMEOUT = -1, -2, -3, -4     # include/inrhip.h
 INR_LF_COUNT = 14
 INR_PIA_LF_COUNT = 4
+INR_JET_LF_INPUT, INR_JET_LF_LAYER, INR_JET_LF_HEAD, INR_JET_LF_COUNT = 0, 1, 2, 3
 INR_LF_ERD_STEP, INR_LF_ERD_REDUCE, INR_LF_ERD_FORWARD, INR_LF_ERD_SOFT = 32, 33, 34, 35
 INR_ERD_RUNNING, INR_ERD_CONVERGED, INR_ERD_COLLAPSED = 0, 1, 2
 
@@ -188,6 +189,12 @@ SIGNATURES = {
                                    C.c_double, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "inr_soft_erd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_double,
                                C.c_double, C.c_double, C.c_void_p, c_stream]),
+    "inr_siren_jet_workspace_bytes": (C.c_size_t, [C.POINTER(SirenDesc), C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "inr_siren_jet": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p,
+                                c_f32p, C.c_int64, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_siren_jet_grid": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_i64p, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p,
+                                     C.c_int64, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_jet_launch_count": (C.c_int, [C.c_int, c_i64p]),
     "inr_prof_enable": (C.c_int, [C.c_int]),
     "inr_prof_reset": (C.c_int, []),
     "inr_prof_read": (C.c_int, [C.c_int, c_i64p, C.POINTER(C.c_double)]),

@@ -1724,6 +1724,7 @@ int inr_launch_counts_reset(void) {
     for (int f = 0; f < LF_COUNT; ++f) g_launches[f].store(0, std::memory_order_relaxed);
     pia_launch_counts_reset();
     erd_launch_counts_reset();
+    jet_launch_counts_reset();
     return 0;
 }
 

@@ -156,6 +156,9 @@ void pia_launch_counts_reset();
 void erd_launch_counts_reset();
 int erd_launch_count(int family, int64_t* count);   // family in [INR_LF_ERD_BASE, INR_LF_ERD_END)
 
+// ---- jet.hip: forward-mode derivatives of a SIREN; its launch families (INR_JET_LF_*) are counted in a table of their own ------------
+void jet_launch_counts_reset();
+
 // ---- rams.hip (+ rams_train.inc) ---------------------------------------------------------------------------------------------------------
 long long rams_param_floats(const inr_rams_desc_t* d);
 size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W);

@@ -18,8 +18,10 @@ Citations are relative to /root/reference/implicit-neural-representations.
 """
 from __future__ import annotations
 
+import collections
 import itertools
 import math
+import weakref
 
 import numpy as np
 import torch
@@ -364,6 +366,7 @@ class Siren(nn.Module):
                              self.first_omega_0, self.hidden_omega_0)
 
     def forward(self, coords):
+        given = coords
         if self.flavor == "SRDWI":
             coords = coords.detach()  # SRDWI.py:88 (the reference also clones; the kernels never write x)
         lead = coords.shape[:-1]
@@ -378,6 +381,9 @@ class Siren(nn.Module):
         else:
             y = _SirenFn.apply(flat_x, self.first_omega_0, self.hidden_omega_0, *params)
         y = y.reshape(*lead, self.out_features)
+        if given.requires_grad and given.shape[-1] <= 4:
+            # where this output came from, for `laplace`: the custom backward passes carry no graph to differentiate twice
+            y._siren_origin = (weakref.ref(self), given)
         return (y, coords) if self.return_coords else y
 
     def _hp_train_ok(self, x, params) -> bool:
@@ -672,6 +678,73 @@ def reconstruct(model: Siren, shape, B=None, clamp_min=0.0, chunk_rows=1 << 20):
     y = ops.siren_reconstruct(desc, flat, shape, Bd, clamp_min, chunk_rows)
     shape = tuple(int(s) for s in shape)
     return y.view(*shape) if model.out_features == 1 else y.view(*shape, model.out_features)
+
+
+# ---------------------------------------------------------------------------------------------------
+# spatial derivatives of a fitted network (nn_mri.py:205-221)
+# ---------------------------------------------------------------------------------------------------
+Derivatives = collections.namedtuple("Derivatives", ["value", "gradient", "laplacian"])
+
+
+def derivatives(model: Siren, coords=None, *, shape=None, B=None, laplacian=True, d_tangent=None, chunk_rows=1 << 15):
+    """Value, coordinate gradient and Laplacian of ``model(input_mapping(coords, B))``, evaluated in forward mode by the
+    ``inr_siren_jet`` kernels: what nn_mri.py:205-221 ``gradient`` / ``laplace`` obtain from two ``autograd.grad`` passes with
+    ``create_graph=True``, without a stash of activations, so it runs on a re-sampling grid of millions of rows.
+
+    Exactly one of ``coords`` ([..., d] rows, d <= 4) and ``shape`` (the dense grid ``get_mgrid(shape)``, generated on the device)
+    is given.  Returns the named tuple ``(value, gradient, laplacian)`` of device tensors: for ``coords`` of shape ``lead + (d,)``
+    they have shapes ``lead``, ``lead + (d_tangent,)``, ``lead``; on a grid ``shape``, ``shape + (d_tangent,)``, ``shape``.
+    ``laplacian=False`` skips the second-order accumulator (the field is ``None``).  ``d_tangent`` (default d) differentiates along
+    the leading axes only: a DWI grid (x, y, z, b) takes 3, and the Laplacian then sums over those axes.
+
+    Derivatives are with respect to the NORMALISED ``[-1, 1]`` coordinates of ``get_mgrid``, as in the reference's helpers: multiply
+    ``gradient[..., a]`` by ``2 / (n_a - 1)`` for units per voxel along an axis of ``n_a`` samples, a second derivative by its
+    square.  The value is the raw network output (no clamp).  Both ``Siren`` flavours give the same bits: whether ``forward``
+    detaches its input plays no part here.  The call runs under ``torch.no_grad()`` semantics -- the results carry no graph."""
+    if (coords is None) == (shape is None):
+        raise ValueError("derivatives takes exactly one of coords and shape")
+    desc, flat = flat_parameters(model)
+    Bd = None if B is None else B.detach().to(flat.device, torch.float32).contiguous()
+    with torch.no_grad():
+        if coords is not None:
+            lead, d = tuple(coords.shape[:-1]), int(coords.shape[-1])
+            x = coords.detach().to(flat.device, torch.float32).reshape(-1, d).contiguous()
+            y, g, lap = ops.siren_jet(desc, flat, x=x, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian), chunk_rows=chunk_rows)
+        else:
+            lead = tuple(int(s) for s in shape)
+            y, g, lap = ops.siren_jet(desc, flat, shape=lead, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian),
+                                      chunk_rows=chunk_rows)
+    return Derivatives(y.view(*lead), g.view(*lead, g.shape[-1]), None if lap is None else lap.view(*lead))
+
+
+def gradient(y, x, grad_outputs=None):
+    """nn_mri.py:217-221: ``d y / d x`` through autograd (``x`` must not have been detached: the ``INRmodel`` flavour)."""
+    if grad_outputs is None:
+        grad_outputs = torch.ones_like(y)
+    return torch.autograd.grad(y, [x], grad_outputs=grad_outputs, create_graph=True)[0]
+
+
+def divergence(y, x):
+    """nn_mri.py:210-214: ``sum_i d y[..., i] / d x[..., i]`` through autograd."""
+    div = 0.
+    for i in range(y.shape[-1]):
+        div = div + torch.autograd.grad(y[..., i], x, torch.ones_like(y[..., i]), create_graph=True)[0][..., i:i + 1]
+    return div
+
+
+def laplace(y, x):
+    """nn_mri.py:205-207 ``divergence(gradient(y, x), x)`` for a ``y`` that came straight out of this package's ``Siren`` on the
+    input ``x`` (which requires grad, ``x.shape[-1] <= 4``): ``Siren.forward`` records the model and the input on such an output,
+    and the Laplacian is evaluated by ``derivatives`` on that record -- the backward passes of the HIP autograd functions are
+    plain kernel calls and leave no graph to differentiate a second time.  Returns ``x.shape[:-1] + (1,)``, without a graph,
+    in the units of ``x``.  Any other ``y`` raises ``TypeError``."""
+    origin = getattr(y, "_siren_origin", None)
+    model = origin[0]() if origin is not None else None
+    if model is None or origin[1] is not x:
+        raise TypeError("laplace: second derivatives exist only for direct Siren outputs -- y = Siren(...)(x) with this x, which "
+                        "requires grad and has at most 4 coordinates; for anything else (Fourier-feature inputs, grids, a "
+                        "transformed y) call mri_super_resolution_amd.inr.derivatives(model, coords or shape=..., B=...)")
+    return derivatives(model, x).laplacian.unsqueeze(-1)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -355,6 +355,51 @@ def siren_reconstruct(desc: SirenDesc, params, shape, B=None, clamp_min=0.0, chu
     return y
 
 
+def siren_jet(desc: SirenDesc, params, x=None, shape=None, B=None, d_tangent=None, want_grad=True, want_lap=True,
+              chunk_rows: int = 1 << 15):
+    """Value, coordinate gradient and Laplacian of a SIREN in forward mode (``inr_siren_jet`` on the rows ``x`` [n, d], or
+    ``inr_siren_jet_grid`` on ``get_mgrid(shape)``; exactly one of the two).  Returns ``(y [n], grad [n, d_tangent] or None,
+    lap [n] or None)``; derivatives are taken along the ``d_tangent`` leading axes (default: all ``d``)."""
+    _chk(params, "params")
+    if (x is None) == (shape is None):
+        raise ValueError("siren_jet takes exactly one of x and shape")
+    total, _ = siren_param_layout(desc)
+    if params.numel() != total:
+        raise ValueError(f"flat params has {params.numel()} floats, layout needs {total}")
+    if x is not None:
+        _chk(x, "x")
+        if x.dim() != 2:
+            raise ValueError(f"x {tuple(x.shape)} must be [n, d]")
+        n, d = int(x.shape[0]), int(x.shape[1])
+    else:
+        shape = tuple(int(s) for s in shape)
+        d, n = len(shape), 1
+        for s in shape:
+            n *= s
+    m = 0
+    if B is not None:
+        _chk(B, "B")
+        if B.dim() != 2 or B.shape[1] != d:
+            raise ValueError(f"B {tuple(B.shape)} must be [m, {d}]")
+        m = int(B.shape[0])
+    dt = d if d_tangent is None else int(d_tangent)
+    chunk_rows = max(1, min(int(chunk_rows), max(n, 1)))
+    dev = params.device
+    y = torch.empty(n, dtype=torch.float32, device=dev)
+    grad = torch.empty((n, dt), dtype=torch.float32, device=dev) if want_grad else None
+    lap = torch.empty(n, dtype=torch.float32, device=dev) if want_lap else None
+    nbytes = lib().inr_siren_jet_workspace_bytes(C.byref(desc), d, m, chunk_rows, 1 if want_lap else 0)
+    ws = _ws(nbytes, dev)        # (0 for a shape the kernels refuse: the call below says which)
+    if x is not None:
+        check(lib().inr_siren_jet(C.byref(desc), params.data_ptr(), x.data_ptr(), n, d, dt, _ptr(B), m, y.data_ptr(), _ptr(grad),
+                                  _ptr(lap), chunk_rows, ws.data_ptr(), ws.numel(), _stream()), "inr_siren_jet")
+    else:
+        check(lib().inr_siren_jet_grid(C.byref(desc), params.data_ptr(), shape_array(shape), d, dt, _ptr(B), m, y.data_ptr(),
+                                       _ptr(grad), _ptr(lap), chunk_rows, ws.data_ptr(), ws.numel(), _stream()),
+              "inr_siren_jet_grid")
+    return y, grad, lap
+
+
 def siren_fit_workspace_bytes(desc: SirenDesc, n: int) -> int:
     return int(lib().inr_siren_fit_workspace_bytes(C.byref(desc), int(n)))
 
@@ -589,6 +634,19 @@ def pia_launch_counts() -> dict:
     for i, name in enumerate(PIA_LAUNCH_FAMILIES):
         n = C.c_int64(0)
         check(lib().inr_pia_launch_count(i, C.byref(n)), "inr_pia_launch_count")
+        out[name] = int(n.value)
+    return out
+
+
+JET_LAUNCH_FAMILIES = ("jet_input", "jet_layer", "jet_head")                             # INR_JET_LF_*, a table of its own
+
+
+def jet_launch_counts() -> dict:
+    """Launches each derivative-kernel family has received since the last ``launch_counts_reset()``."""
+    out = {}
+    for i, name in enumerate(JET_LAUNCH_FAMILIES):
+        n = C.c_int64(0)
+        check(lib().inr_jet_launch_count(i, C.byref(n)), "inr_jet_launch_count")
         out[name] = int(n.value)
     return out
 

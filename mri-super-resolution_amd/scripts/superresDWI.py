@@ -22,6 +22,11 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     calculate_ADC of the x2 SR volume, of the x4 spline of the LR ROI and of the x2 spline of the HR ROI, each b-image
     multiplied back by ``maxes[b, 1]`` (TE index 1; for a plain volume the per-b maxima it was divided by).  Needs >= 2
     distinct b-values.
+  * ``--derivative_maps``: ``derivatives.mat`` with ``grad_mag`` and ``laplacian``, both of ``recon``'s shape [2R, 2R, Z, B] (one
+    map per b-image): the fitted network differentiated exactly on the grid of ``recon`` (nn_mri.py:205-221 ``gradient`` /
+    ``laplace``, evaluated in forward mode by ``inr.derivatives``) along the in-plane and through-plane axes -- not along the
+    b-value axis.  ``grad_mag = sqrt(sum_i (dy/dx_i)^2)``, ``laplacian = sum_i d^2y/dx_i^2``, of the un-clamped network, in the
+    normalised [-1, 1] coordinates of ``get_mgrid`` (times ``2 / (n_i - 1)`` per axis and order for per-voxel units).
 R = roi_end - roi_start.  Plots (superresDWI.py:164-233) are outside the build's scope.
 """
 from __future__ import annotations
@@ -64,6 +69,9 @@ def build_parser():
                         "217-241, where T = 100 is hard-coded); default 0 = off")
     p.add_argument("--adc", action="store_true",
                    help="also write adc.mat: ADC maps of SR, spline and HR (superresDWI.py:189-206); needs >= 2 b-values")
+    p.add_argument("--derivative_maps", action="store_true",
+                   help="also write derivatives.mat: gradient magnitude and Laplacian of the fitted network on recon's grid, "
+                        "along the spatial axes (nn_mri.py:205-221)")
     return p
 
 
@@ -175,6 +183,8 @@ def run_patient(path, pt_id, args):
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
         matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale))
+    if args.derivative_maps:
+        matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape))
     rec_h, sr_h = recon.cpu().numpy(), SR_recon.cpu().numpy()
     out_vars = {"recon": rec_h, "SR_recon": sr_h, "b": np.asarray(bvalues, np.float64)}
     if maxes is not None:
@@ -231,6 +241,14 @@ def _adc_maps(recon, hs, bvalues, signal_scale):
     out = {k: metrics.calculate_ADC_device(bvalues, (v * scale).contiguous()).cpu().numpy() for k, v in stacks.items()}
     out["b"] = np.asarray(bvalues, np.float64)
     return out
+
+
+def _derivative_maps(INR, B, test_shape):
+    """nn_mri.py:205-221 on the grid of ``recon``: tangents along the three spatial axes only (the b-value axis is the last of the
+    grid and is not differentiated along)."""
+    d = inr.derivatives(INR, shape=test_shape, B=B, d_tangent=min(3, len(test_shape)))
+    grad_mag = torch.sqrt((d.gradient * d.gradient).sum(dim=-1))
+    return {"grad_mag": grad_mag.cpu().numpy(), "laplacian": d.laplacian.cpu().numpy()}
 
 
 SUMMARY_KEYS = ("job", "n_coords", "steps", "t_fit_s", "t_recon_s", "train_voxels_per_s", "final_loss", "psnr_db",
