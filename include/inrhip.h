@@ -497,8 +497,8 @@ int inr_pia_backward_train(const inr_pia_desc_t* desc, const float* params, floa
 int inr_pia_fit_step(const inr_pia_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x, const float* pids,
                      int64_t n, int64_t step, double lr, double beta1, double beta2, double eps, float* loss, void* workspace,
                      size_t workspace_bytes, void* stream);
-/* Launch families of the PIA kernels, counted like INR_LF_* but in a table of their own (the INR_LF_* table and its count are
- * pinned by callers); inr_launch_counts_reset() clears both. */
+/* Launch families of the PIA kernels, counted like INR_LF_* but numbered from 0 and read through an entry point of their own
+ * (the INR_LF_* ids and their count are pinned by callers); inr_launch_counts_reset() clears them too. */
 #define INR_PIA_LF_FWD   0   /* pia_gemm_kernel<FWD>: layer forward, f32-input MFMA 16x16x4, LeakyReLU epilogue */
 #define INR_PIA_LF_DX    1   /* pia_gemm_kernel<DX>: input gradient (the three heads' products in one K-loop) */
 #define INR_PIA_LF_DW    2   /* pia_gemm_kernel<DW>: parameter gradient, row-split slabs */
@@ -617,8 +617,9 @@ int inr_siren_jet_grid(const inr_siren_desc_t* desc, const float* params, const 
                        const float* B, int m, float* y, float* grad, float* lap, int64_t chunk_rows, void* workspace,
                        size_t workspace_bytes, void* stream);
 /* Launch families of these kernels (nn_mri.py:205-221 has no counterpart: each stands for a slice of the two autograd.grad
- * passes), counted like INR_LF_* but in a table of their own; inr_launch_counts_reset() clears it too.  Per chunk of rows:
- * one INPUT launch, one LAYER launch per sine layer (one fewer without B: the first layer is the INPUT launch), one HEAD. */
+ * passes), counted like INR_LF_* but numbered from 0 and read through inr_jet_launch_count; inr_launch_counts_reset() clears
+ * them too.  Per chunk of rows: one INPUT launch, one LAYER launch per sine layer (one fewer without B: the first layer is the
+ * INPUT launch), one HEAD. */
 #define INR_JET_LF_INPUT 0   /* jet_fourier_kernel / jet_first_kernel: jets of the Fourier features, or the first sine layer on the VALU */
 #define INR_JET_LF_LAYER 1   /* jet_layer_kernel<J>: one sine layer on J planes, f32-input MFMA 32x32x2 */
 #define INR_JET_LF_HEAD  2   /* jet_head_kernel: J row dots, a wave per row */

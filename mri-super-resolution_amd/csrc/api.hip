@@ -43,9 +43,10 @@ static ProfState g_prof;
 bool prof_enabled() { return g_prof.enabled; }
 
 // ---- launch-family counters (inr_launch_count) ------------------------------------------------------------------------
-static std::atomic<long long> g_launches[LF_COUNT];
+// one table for every family (common.h: LaunchFamily and the bases beside it)
+static std::atomic<long long> g_launches[LF_TABLE];
 void count_launch(int family) {
-    if (family >= 0 && family < LF_COUNT) g_launches[family].fetch_add(1, std::memory_order_relaxed);
+    if (family >= 0 && family < LF_TABLE) g_launches[family].fetch_add(1, std::memory_order_relaxed);
 }
 // scopes of one class may nest (a launcher calling another launcher): only the outermost pair is recorded
 void prof_begin(int kc, hipStream_t s) {
@@ -1714,17 +1715,26 @@ int inr_debug_reset(void) {
 }
 
 int inr_launch_count(int family, int64_t* count) {
-    if (family >= INR_LF_ERD_BASE && family < INR_LF_ERD_END && count) return erd_launch_count(family, count);
-    INR_REQUIRE(family >= 0 && family < LF_COUNT && count, INR_E_INVALID, "inr_launch_count: bad arguments");
+    const bool known = (family >= 0 && family < LF_COUNT) || (family >= INR_LF_ERD_BASE && family < INR_LF_ERD_END);
+    INR_REQUIRE(known && count, INR_E_INVALID, "inr_launch_count: bad arguments");
     *count = (int64_t)g_launches[family].load(std::memory_order_relaxed);
     return 0;
 }
 
+int inr_pia_launch_count(int family, int64_t* count) {
+    INR_REQUIRE(family >= 0 && family < INR_PIA_LF_COUNT && count, INR_E_INVALID, "inr_pia_launch_count: bad arguments");
+    *count = (int64_t)g_launches[LF_PIA_BASE + family].load(std::memory_order_relaxed);
+    return 0;
+}
+
+int inr_jet_launch_count(int family, int64_t* count) {
+    INR_REQUIRE(family >= 0 && family < INR_JET_LF_COUNT && count, INR_E_INVALID, "inr_jet_launch_count: bad arguments");
+    *count = (int64_t)g_launches[LF_JET_BASE + family].load(std::memory_order_relaxed);
+    return 0;
+}
+
 int inr_launch_counts_reset(void) {
-    for (int f = 0; f < LF_COUNT; ++f) g_launches[f].store(0, std::memory_order_relaxed);
-    pia_launch_counts_reset();
-    erd_launch_counts_reset();
-    jet_launch_counts_reset();
+    for (auto& c : g_launches) c.store(0, std::memory_order_relaxed);
     return 0;
 }
 

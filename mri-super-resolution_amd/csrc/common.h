@@ -126,8 +126,27 @@ enum LaunchFamily {
     LF_SMALL_BATCH = 13,    // siren_small_batch_kernel: several small-network fits in one persistent cooperative launch
     LF_COUNT = 14
 };
-void count_launch(int family);
+// The one table behind inr_launch_count, inr_pia_launch_count and inr_jet_launch_count (api.hip).  The SIREN and ERD families sit
+// at their public ids; the PIA and jet families, whose public ids start at 0, at internal bases above them that no entry point
+// hands out.
+enum {
+    LF_PIA_BASE = INR_LF_ERD_END,                     // + INR_PIA_LF_*
+    LF_JET_BASE = LF_PIA_BASE + INR_PIA_LF_COUNT,     // + INR_JET_LF_*
+    LF_TABLE = LF_JET_BASE + INR_JET_LF_COUNT
+};
+static_assert(LF_COUNT <= INR_LF_ERD_BASE, "the SIREN families must end below the ERD ids");
+void count_launch(int family);   // family: an index of that table
 #define INR_E_FALLBACK (-100)   // internal: the chosen kernel cannot run on this device, the caller takes its next-best path
+
+// The constants of Adam step number `step` (1-based) as the kernels take them (adam_update below): host-side double bias
+// corrections, as torch's _single_tensor_adam does for python-float lr, rounded to fp32 once.
+struct AdamConsts {
+    float one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps;
+};
+static inline AdamConsts adam_consts(long long step, double lr, double b1, double b2, double eps) {
+    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    return AdamConsts{(float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(lr / bc1), (float)sqrt(bc2), (float)eps};
+}
 
 // ---- deferred gradient reduction of the fused fit (kernels.hip: finalize_kernel) -------------------------------------------
 // Every gradient tensor of a step is a fixed-order sum of slab rows its producer left behind (row-split parameter-gradient
@@ -156,7 +175,7 @@ struct FinalizeJob {
     float* loss_out;
     float* grads;
     float *params, *m, *v;              // params == nullptr: reduce only (inr_siren_loss_grad)
-    float one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps;
+    AdamConsts adam;                    // set by launch_finalize
 };
 int launch_finalize(FinalizeJob& job, long long adam_step, double lr, double b1, double b2, double eps, hipStream_t st);
 
@@ -189,21 +208,47 @@ struct ProfScope {
 #define INR_INV_2PI_LO 6.42063824329852650e-09f
 #define INR_SINCOS_FAST_LIMIT 1048576.0f
 
-__device__ __forceinline__ void sincos_f32(float x, float& s, float& c) {
-    if (__builtin_expect(!(fabsf(x) < INR_SINCOS_FAST_LIMIT), 0)) {
-        sincosf(x, &s, &c);
-        return;
-    }
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ f32x2_t sincos_f32_libm(float x) {   // {sin, cos}: the path of arguments beyond the fast limit
+    float s, c;
+    sincosf(x, &s, &c);
+    return f32x2_t{s, c};
+}
+__device__ __forceinline__ void sincos_f32_fast(float x, float& s, float& c) {   // |x| < INR_SINCOS_FAST_LIMIT
     const float k = rintf(x * INR_INV_2PI_HI);
     float f = fmaf(x, INR_INV_2PI_HI, -k);
     f = fmaf(x, INR_INV_2PI_LO, f);
     s = __builtin_amdgcn_sinf(f);
     c = __builtin_amdgcn_cosf(f);
 }
+__device__ __forceinline__ void sincos_f32(float x, float& s, float& c) {
+    if (__builtin_expect(!(fabsf(x) < INR_SINCOS_FAST_LIMIT), 0)) {
+        const f32x2_t r = sincos_f32_libm(x);
+        s = r[0];
+        c = r[1];
+        return;
+    }
+    sincos_f32_fast(x, s, c);
+}
+// The same with the libm branch out of line, for kernels with an unrolled MFMA epilogue: inlined there (64 times in the 128-wide
+// ERD kernel) it competes with the accumulators for registers and pushed them into scratch memory.
+static __device__ __noinline__ f32x2_t sincos_f32_libm_ool(float x) { return sincos_f32_libm(x); }
+__device__ __forceinline__ void sincos_f32_ool(float x, float& s, float& c) {
+    if (__builtin_expect(!(fabsf(x) < INR_SINCOS_FAST_LIMIT), 0)) {
+        const f32x2_t r = sincos_f32_libm_ool(x);
+        s = r[0];
+        c = r[1];
+        return;
+    }
+    sincos_f32_fast(x, s, c);
+}
 
 // Branch-free core of sincos_f32 on float2 (valid for |x| < INR_SINCOS_FAST_LIMIT; callers check that once per
 // tile and redo the tile through sincos_f32 otherwise, so the unrolled epilogue carries no libm code).
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void sincos_f32x2_fast(f32x2_t x, f32x2_t& s, f32x2_t& c) {
     const f32x2_t t = x * INR_INV_2PI_HI;
     const f32x2_t k = f32x2_t{rintf(t[0]), rintf(t[1])};
@@ -219,6 +264,45 @@ __device__ __forceinline__ float linspace_pm1(int64_t i, int64_t n) {
     const float step = 2.0f / static_cast<float>(n - 1);
     return (i < n / 2) ? fmaf(step, static_cast<float>(i), -1.0f)
                        : fmaf(-step, static_cast<float>(n - 1 - i), 1.0f);
+}
+
+// row of accumulator register r (0..15) of a 32 x 32 MFMA tile held by lane half hh = lane >> 5; the column is lane & 31
+__device__ __forceinline__ int mfma32_acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
+
+// sum / maximum over the 64 lanes of a wave, every lane receives it: xor butterfly, offsets 32 -> 1 (a fixed order -- callers'
+// bits depend on it)
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T wave_max(T v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = __builtin_elementwise_max(v, (T)__shfl_xor(v, off, 64));
+    return v;
+}
+
+// sum over a block of 256 threads, every thread receives it: per wave, then the four waves in a fixed order (red: 4 doubles of LDS)
+__device__ __forceinline__ double block_sum_f64(double v, double* red /*[4]*/) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    const double s = (red[0] + red[1]) + (red[2] + red[3]);
+    __syncthreads();
+    return s;
+}
+
+// One Adam step of one element in torch's single-tensor formulation: m.lerp_(g, 1 - b1), v = v b2 + (1 - b2) g g,
+// p -= step_size * m / (sqrt(v) / bc2_sqrt + eps).  p, m, v: old values in, new out.
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, float gi, const AdamConsts& c) {
+    const float mi = fmaf(gi - m, c.one_minus_b1, m);
+    const float vi = fmaf(c.one_minus_b2 * gi, gi, v * c.b2);
+    const float denom = __fsqrt_rn(vi) / c.bc2_sqrt + c.eps;
+    m = mi;
+    v = vi;
+    p = p - c.step_size * (mi / denom);
 }
 
 }  // namespace inr

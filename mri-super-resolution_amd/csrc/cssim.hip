@@ -39,16 +39,6 @@ struct GaussWin {
     double g[KW];
 };
 
-__device__ __forceinline__ double tile_sum_f64(double v, double* red /*[4]*/) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return s;
-}
-
 // The separable window on one tile for NM maps at once.  prod(row, col, v[NM]) gives the NM map values at position (row, col)
 // of the staged 26 x 42 input tile (it may form them from fewer staged sources).  Row pass: thread t < 208 filters 4 adjacent
 // outputs of input row t / 8 into h[NM][IH][HP]; column pass: thread t filters outputs (2 (t / 32) + {0, 1}, t % 32) -> out.
@@ -149,8 +139,8 @@ __global__ void __launch_bounds__(256) cssim_bias_kernel(double* __restrict__ bi
         sm += m;
         sd += m * (double)yt[(long long)(si + r) * size + sj + q] - m * (double)yp[(long long)(border + r) * size + border + q];
     }
-    sm = tile_sum_f64(sm, red);
-    sd = tile_sum_f64(sd, red);
+    sm = block_sum_f64(sm, red);
+    sd = block_sum_f64(sd, red);
     if (threadIdx.x == 0) {
         tot[(long long)b * ns * ns + blockIdx.x] = sm;
         bias[(long long)b * ns * ns + blockIdx.x] = sd / sm;
@@ -221,7 +211,7 @@ __global__ void __launch_bounds__(256) cssim_shift_kernel(double* __restrict__ d
         }
     }
     if (!GRAD) {
-        acc = tile_sum_f64(acc, red);
+        acc = block_sum_f64(acc, red);
         if (threadIdx.x == 0) dst[((long long)b * ns * ns + shift) * gridDim.x + blockIdx.x] = acc;
     }
 }
@@ -303,7 +293,7 @@ __global__ void __launch_bounds__(256) cssim_grad_filter_kernel(double* __restri
             acc += g * m;
         }
     }
-    acc = tile_sum_f64(acc, red);
+    acc = block_sum_f64(acc, red);
     if (threadIdx.x == 0) gpart[(long long)b * gridDim.x + blockIdx.x] = acc;
 }
 

@@ -14,26 +14,11 @@
 // wave on each of two SIMDs); weights go global -> LDS directly (a register prefetch of a 128 x 128 matrix would be 128 VGPRs).
 #include "internal.h"
 
-#include <atomic>
 #include <math.h>
 
 namespace inr {
 
-static std::atomic<long long> g_erd_launches[INR_LF_ERD_END - INR_LF_ERD_BASE];
-void erd_launch_counts_reset() {
-    for (auto& c : g_erd_launches) c.store(0, std::memory_order_relaxed);
-}
-int erd_launch_count(int family, int64_t* count) {
-    *count = (int64_t)g_erd_launches[family - INR_LF_ERD_BASE].load(std::memory_order_relaxed);
-    return 0;
-}
-
 namespace {
-
-inline void erd_count(int family) { g_erd_launches[family - INR_LF_ERD_BASE].fetch_add(1, std::memory_order_relaxed); }
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ERD_MAX_F = 8;
 constexpr int ERD_MAX_HIDDEN_LAYERS = 8;
@@ -66,29 +51,6 @@ struct ErdStep {
     float first_omega, hidden_omega, inv_count, sample, eps;
     int perturb, accumulate;
 };
-
-__device__ __forceinline__ int acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-
-// sincos_f32 with the libm branch (arguments beyond INR_SINCOS_FAST_LIMIT) kept out of line: inlined 64 times into the unrolled
-// epilogue of the 128-wide kernel it pushed the accumulators into scratch memory
-__device__ __noinline__ f32x2_t erd_sincos_libm(float x) {
-    float s, c;
-    sincosf(x, &s, &c);
-    return f32x2_t{s, c};
-}
-__device__ __forceinline__ void erd_sincos(float x, float& s, float& c) {
-    if (__builtin_expect(!(fabsf(x) < INR_SINCOS_FAST_LIMIT), 0)) {
-        const f32x2_t r = erd_sincos_libm(x);
-        s = r[0];
-        c = r[1];
-        return;
-    }
-    const float k = rintf(x * INR_INV_2PI_HI);
-    float f = fmaf(x, INR_INV_2PI_HI, -k);
-    f = fmaf(x, INR_INV_2PI_LO, f);
-    s = __builtin_amdgcn_sinf(f);
-    c = __builtin_amdgcn_cosf(f);
-}
 
 // u_j = tanh(b1[j] + W1[j] . [x, sample]) -- the same instruction sequence in the forward prologue and in the backward pass
 __device__ __forceinline__ float erd_perturb_unit(const float* W1, const float* b1, const float* in, int F, int j) {
@@ -217,12 +179,12 @@ __global__ void __launch_bounds__(ERD_THREADS) erd_step_kernel(const ErdStep p) 
             const float bj = bias[j];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = acc_row(r, hh);
+                const int i = mfma32_acc_row(r, hh);
                 const float z = acc[ct][r] + bj;
                 float av, dv;
                 if (sine) {
                     float sv, cv;
-                    erd_sincos(omega * z, sv, cv);
+                    sincos_f32_ool(omega * z, sv, cv);
                     av = sv;
                     dv = omega * cv;
                 } else {
@@ -289,7 +251,7 @@ __global__ void __launch_bounds__(ERD_THREADS) erd_step_kernel(const ErdStep p) 
         float gw = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int i = acc_row(r, hh);
+            const int i = mfma32_acc_row(r, hh);
             const float gi = gbuf[wave][i];
             gw = fmaf(gi, stageA[i * LDS_STRIDE + j], gw);
             dz[ct][r] = gi * wj * dlast[ct][r];
@@ -316,7 +278,7 @@ __global__ void __launch_bounds__(ERD_THREADS) erd_step_kernel(const ErdStep p) 
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int i = acc_row(r, hh);
+                    const int i = mfma32_acc_row(r, hh);
                     d_pref[ct][r] = (r0 + i < p.N) ? d_in[(long long)(r0 + i) * H + ct * 32 + l32] : 0.f;
                 }
         }
@@ -328,7 +290,7 @@ __global__ void __launch_bounds__(ERD_THREADS) erd_step_kernel(const ErdStep p) 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 gb += dz[ct][r];
-                stageD[acc_row(r, hh) * LDS_STRIDE + j] = dz[ct][r];
+                stageD[mfma32_acc_row(r, hh) * LDS_STRIDE + j] = dz[ct][r];
             }
             gb += __shfl_xor(gb, 32, 64);
             if (hh == 0) put(p.L.b_off[l] + j, gb);
@@ -383,7 +345,7 @@ __global__ void __launch_bounds__(ERD_THREADS) erd_step_kernel(const ErdStep p) 
                 }
                 if (kc < K) {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) put(p.L.w_off[l] + (long long)(ht * 32 + acc_row(r, hh)) * K + kc, wacc[r]);
+                    for (int r = 0; r < 16; ++r) put(p.L.w_off[l] + (long long)(ht * 32 + mfma32_acc_row(r, hh)) * K + kc, wacc[r]);
                 }
             }
         }
@@ -493,13 +455,7 @@ __global__ void __launch_bounds__(256) erd_reduce_kernel(const ErdReduce p) {
             float* __restrict__ v = p.v;
             float* __restrict__ w = p.params;
             const float step_size = i < p.group_b ? p.step_size_a : p.step_size_b;
-            const float one_minus_b1 = p.one_minus_b1, one_minus_b2 = p.one_minus_b2, b2 = p.b2, bc2_sqrt = p.bc2_sqrt, eps = p.eps;
-            const float mi = fmaf(gi - m[i], one_minus_b1, m[i]);           // the arithmetic of adam_kernel
-            const float vi = fmaf(one_minus_b2 * gi, gi, v[i] * b2);
-            const float denom = __fsqrt_rn(vi) / bc2_sqrt + eps;
-            m[i] = mi;
-            v[i] = vi;
-            w[i] = w[i] - step_size * (mi / denom);
+            adam_update(w[i], m[i], v[i], gi, AdamConsts{p.one_minus_b1, p.b2, p.one_minus_b2, step_size, p.bc2_sqrt, p.eps});
         }
     }
     if (blockIdx.x == 0 && (p.loss_out || p.status || p.gate_out)) {
@@ -653,28 +609,27 @@ int erd_launch_step(const inr_siren_desc_t* d, const ErdLayout& L, const ErdWs& 
     else
         hipLaunchKernelGGL((erd_step_kernel<64, TRAIN>), dim3(erd_blocks(n)), dim3(ERD_THREADS), 0, st, p);
     INR_LAUNCH_CHECK();
-    erd_count(TRAIN ? INR_LF_ERD_STEP : INR_LF_ERD_FORWARD);
+    count_launch(TRAIN ? INR_LF_ERD_STEP : INR_LF_ERD_FORWARD);
     return 0;
 }
 
 void erd_adam_consts(ErdReduce& r, int64_t step, double lr_a, double lr_b, double b1, double b2, double eps) {
-    // host-side double bias corrections, as launch_adam
-    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    const AdamConsts a = adam_consts(step, lr_a, b1, b2, eps);   // the two groups differ in the learning rate only
     r.do_adam = 1;
-    r.one_minus_b1 = (float)(1.0 - b1);
-    r.b2 = (float)b2;
-    r.one_minus_b2 = (float)(1.0 - b2);
-    r.step_size_a = (float)(lr_a / bc1);
-    r.step_size_b = (float)(lr_b / bc1);
-    r.bc2_sqrt = (float)sqrt(bc2);
-    r.eps = (float)eps;
+    r.one_minus_b1 = a.one_minus_b1;
+    r.b2 = a.b2;
+    r.one_minus_b2 = a.one_minus_b2;
+    r.step_size_a = a.step_size;
+    r.step_size_b = adam_consts(step, lr_b, b1, b2, eps).step_size;
+    r.bc2_sqrt = a.bc2_sqrt;
+    r.eps = a.eps;
 }
 
 int erd_launch_reduce(const ErdReduce& r, hipStream_t st) {
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL(erd_reduce_kernel, dim3((unsigned)((r.P + 63) / 64)), dim3(256), 0, st, r);
     INR_LAUNCH_CHECK();
-    erd_count(INR_LF_ERD_REDUCE);
+    count_launch(INR_LF_ERD_REDUCE);
     return 0;
 }
 
@@ -846,7 +801,7 @@ int inr_soft_erd(double* weights, double* mean_image, const double* values, cons
     hipLaunchKernelGGL(soft_erd_kernel, dim3((unsigned)((n_pixels + 255) / 256)), dim3(256), 0, st, weights, mean_image, values, b0,
                        (long long)n_pixels, n_acquisitions, noise_level, mul, slope, min_temp, nonfinite_count);
     INR_LAUNCH_CHECK();
-    erd_count(INR_LF_ERD_SOFT);
+    count_launch(INR_LF_ERD_SOFT);
     return 0;
 }
 

@@ -34,10 +34,6 @@
 
 namespace inr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BM = 128, BN = 128, BK = 32, NTHREADS = 256;
 constexpr int LDK = BK + 4;  // k-contiguous LDS row stride (floats)
 constexpr int LDM = BM;      // m-contiguous LDS row stride (floats)
@@ -178,7 +174,7 @@ __device__ __forceinline__ void epilogue(const GemmParams& p, const f32x16 (&acc
             const long long base = (long long)row_base * p.ldc + col;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int dr = (r & 3) + 8 * (r >> 2);
+                const int dr = mfma32_acc_row(r, 0);
                 if (CHECK && row_base + dr >= p.M) continue;
                 const long long off = base + (long long)dr * p.ldc;
                 const float v = acc[i][j][r];
@@ -398,6 +394,7 @@ __device__ __forceinline__ void epilogue_staged(const GemmParams& p, const f32x1
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
+                // mfma32_acc_row(r, h), open-coded: through the helper the pipe kernels' LDS address arithmetic changes
                 sub[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 64 + j * 32 + l32] = acc[i][j][r];
     epilogue_rows<EPI, 64>(p, sub, a, mulreg, n0, wn, lane, slab_row);
 }
@@ -466,8 +463,7 @@ __device__ __forceinline__ void epilogue_rows(const GemmParams& p, float* __rest
         }
     }
     if (EPI == EPI_MUL && p.amax_out) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) omax = fmaxf(omax, __shfl_xor(omax, off, 64));
+        omax = wave_max(omax);
         if (lane == 0) atomicMax(p.amax_out, __float_as_uint(omax));   // max is order independent: runs stay reproducible
     }
     if (EPI == EPI_MUL && p.colsum) {

@@ -464,8 +464,7 @@ __global__ void __launch_bounds__(256) INR_PACKED_F32 weight_amax_kernel(const W
     const int n = j.out_f * j.in_f;
     unsigned m = 0;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) m = max(m, __float_as_uint(j.W[i]) & 0x7fffffffu);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax(j.amax, m);
 }
 
@@ -514,7 +513,6 @@ __global__ void __launch_bounds__(256) INR_PACKED_F32 tensor_amax_kernel(unsigne
         m = max(max(m, v[0] & 0x7fffffffu), max(max(v[1] & 0x7fffffffu, v[2] & 0x7fffffffu), v[3] & 0x7fffffffu));
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) m = max(m, __float_as_uint(x[n4 * 4 + threadIdx.x]) & 0x7fffffffu);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }

@@ -571,8 +571,7 @@ __device__ __forceinline__ void gemm_hp_body(const HpParams& p, const int block_
     }
     HP_STAMP(4);
     if (p.amax_out) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) omax = fmaxf(omax, __shfl_xor(omax, off, 64));
+        omax = wave_max(omax);
         if (lane == 0) hp_atomic_max_bits(p.amax_out, omax);
     }
     if (p.colsum) {   // 8 rows per lane so far; the 8 lanes sharing a column group are lane ^ 8, ^ 16, ^ 32 (fixed order)
@@ -728,8 +727,7 @@ __global__ void __launch_bounds__(256) INR_PACKED_F32 hp_weight_stats_kernel(con
         }
         __syncthreads();
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) amax = max(amax, (unsigned)__shfl_xor((int)amax, off, 64));
+    amax = wave_max(amax);
     if ((threadIdx.x & 63) == 0) red_a[threadIdx.x >> 6] = amax;
     if (threadIdx.x < 64) {   // (lanes 16 .. 63 hold 0)
 #pragma unroll
@@ -867,18 +865,12 @@ __global__ void __launch_bounds__(256) INR_PACKED_F32 hp_head_bound_ext_kernel(f
     __shared__ float s2[4];
     float m = 0.f;
     for (int i = threadIdx.x; i < hidden; i += 256) m = fmaxf(m, fabsf(head_W[i]));
-#pragma unroll
+#pragma unroll   // wave_max(), open-coded: through the helper this translation unit's instruction schedule changes
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     if ((threadIdx.x & 63) == 0) s2[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0)
         head_bound[0] = __uint_as_float(*gmax) * fmaxf(fmaxf(s2[0], s2[1]), fmaxf(s2[2], s2[3])) * fabsf(omega) * 1.001f;
-}
-
-__device__ __forceinline__ float hp_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 // ---- head on HL32 activations -------------------------------------------------------------------------------------------
@@ -927,7 +919,7 @@ __global__ void __launch_bounds__(256) INR_PACKED_F32 hp_head_forward_kernel(flo
         hp_load_row<CPL>(a, r, H, c0, v, inv_sa);
 #pragma unroll
         for (int e = 0; e < CPL; ++e) acc = fmaf(v[e], w[e], acc);
-        float s = hp_wave_sum(acc) + b0;
+        float s = wave_sum(acc) + b0;
         if (use_clamp) s = fmaxf(s, clamp_min);
         if (lane == 0) y[r] = s;
     }
@@ -1015,7 +1007,7 @@ __global__ void __launch_bounds__(256) INR_PACKED_F32 hp_head_step_kernel(char* 
         if (GEXT) {
             g = g_ext[r];
         } else {
-            const float y = hp_wave_sum(acc) + b0;
+            const float y = wave_sum(acc) + b0;
             const float res = y - t[r];
             const float wr = wgt ? wgt[r] * res : res;
             g = 2.0f * wr * inv_count;
@@ -1066,8 +1058,7 @@ __global__ void __launch_bounds__(256) INR_PACKED_F32 hp_head_step_kernel(char* 
         part_g[blockIdx.x] = (red_s[1][0] + red_s[1][1]) + (red_s[1][2] + red_s[1][3]);
     }
     if (amax_out) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) omax = fmaxf(omax, __shfl_xor(omax, off, 64));
+        omax = wave_max(omax);
         if (lane == 0 && omax > 0.f) hp_atomic_max_bits(amax_out, omax);
     }
 }
@@ -1389,8 +1380,7 @@ __global__ void __launch_bounds__(HP_NTH, 2) gemm_hp_pkc_kernel(const HpParams p
         if (has_next) nxt = decode(vp + G);
     }
     if (EPI == HPE_MUL && p.amax_out) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) omax_run = fmaxf(omax_run, __shfl_xor(omax_run, off, 64));
+        omax_run = wave_max(omax_run);
         if (lane == 0) hp_atomic_max_bits(p.amax_out, omax_run);
     }
 }
@@ -1764,8 +1754,7 @@ __global__ void __launch_bounds__(HP_NTH, 2) gemm_hp_pkd_kernel(const HpParams p
     else if (accP[0][0][0] == 12345.678f) p.C_hl[0] = (char)accP[1][1][1];   // (diagnostic builds: keep the accumulators live)
     HP_STAMP(4);
     if (EPI == HPE_MUL && p.amax_out) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) omax_run = fmaxf(omax_run, __shfl_xor(omax_run, off, 64));
+        omax_run = wave_max(omax_run);
         if (lane == 0) hp_atomic_max_bits(p.amax_out, omax_run);
     }
 }

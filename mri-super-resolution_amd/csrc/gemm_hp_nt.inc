@@ -352,7 +352,7 @@ __global__ void __launch_bounds__(NT_NTH, 1) INR_PACKED_F32 gemm_hp_nt_kernel(co
         __builtin_amdgcn_raw_buffer_store_b128(lo, srdHL, voffhl + ro + 64, 0, 0);
     }
     if (p.amax_out) {   // one (conditional) atomic per block
-#pragma unroll
+#pragma unroll   // wave_max(), open-coded: through the helper this translation unit's instruction schedule changes
         for (int off = 32; off > 0; off >>= 1) omax = fmaxf(omax, __shfl_xor(omax, off, 64));
         float* red = reinterpret_cast<float*>(smem + 4 * 32 * SUB16 * 4);   // behind the four staging areas
         if (lane == 0) red[wave] = omax;

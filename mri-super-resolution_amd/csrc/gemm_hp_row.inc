@@ -386,8 +386,7 @@ __global__ void __launch_bounds__(HP_NTH, 2) gemm_hp_row_kernel(const HpParams p
         }
     }
     if ((EPI == HPE_MUL || EPI == HPE_HEAD) && p.amax_out) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) omax_run = fmaxf(omax_run, __shfl_xor(omax_run, off, 64));
+        omax_run = wave_max(omax_run);
         if (lane == 0 && (EPI == HPE_MUL || omax_run > 0.f)) hp_atomic_max_bits(p.amax_out, omax_run);
     }
 }

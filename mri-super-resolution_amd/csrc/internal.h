@@ -149,15 +149,8 @@ int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, cons
                       hipStream_t st);
 void set_hybrid_variant(int v);   // key 2
 
-// ---- pia.hip: the PIA autoencoder; its launch families are counted in a table of their own (inr_pia_launch_count) ---------------------
-void pia_launch_counts_reset();
-
-// ---- erd_siren.hip: the soft-ERD INR family; its launch families (INR_LF_ERD_*) are counted in a table of their own ------------------
-void erd_launch_counts_reset();
-int erd_launch_count(int family, int64_t* count);   // family in [INR_LF_ERD_BASE, INR_LF_ERD_END)
-
-// ---- jet.hip: forward-mode derivatives of a SIREN; its launch families (INR_JET_LF_*) are counted in a table of their own ------------
-void jet_launch_counts_reset();
+// (pia.hip, erd_siren.hip and jet.hip define public entry points only; their launch families are counted through count_launch in
+// api.hip's table like every other -- common.h: LF_PIA_BASE, LF_JET_BASE, and the ERD families at their public ids.)
 
 // ---- rams.hip (+ rams_train.inc) ---------------------------------------------------------------------------------------------------------
 long long rams_param_floats(const inr_rams_desc_t* d);

@@ -14,22 +14,11 @@
 // on its place in a chunk, or on which of the other outputs were asked for.
 #include "internal.h"
 
-#include <atomic>
 #include <vector>
 
 namespace inr {
 
-static std::atomic<long long> g_jet_launches[INR_JET_LF_COUNT];
-void jet_launch_counts_reset() {
-    for (int f = 0; f < INR_JET_LF_COUNT; ++f) g_jet_launches[f].store(0, std::memory_order_relaxed);
-}
-
 namespace {
-
-inline void jet_count(int family) { g_jet_launches[family].fetch_add(1, std::memory_order_relaxed); }
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int JET_MAX_D = 4;
 constexpr int JET_MAX_J = JET_MAX_D + 2;
@@ -42,27 +31,6 @@ constexpr float JET_TWO_PI = 6.283185307179586f;
 struct JetGrid {
     long long n[JET_MAX_D];
 };
-
-// sincos_f32 with the libm branch (arguments beyond INR_SINCOS_FAST_LIMIT) out of line, as in erd_siren.hip: inlined into the
-// unrolled epilogue it would compete with the J accumulator sets for registers
-__device__ __noinline__ f32x2_t jet_sincos_libm(float x) {
-    float s, c;
-    sincosf(x, &s, &c);
-    return f32x2_t{s, c};
-}
-__device__ __forceinline__ void jet_sincos(float x, float& s, float& c) {
-    if (__builtin_expect(!(fabsf(x) < INR_SINCOS_FAST_LIMIT), 0)) {
-        const f32x2_t r = jet_sincos_libm(x);
-        s = r[0];
-        c = r[1];
-        return;
-    }
-    const float k = rintf(x * INR_INV_2PI_HI);
-    float f = fmaf(x, INR_INV_2PI_HI, -k);
-    f = fmaf(x, INR_INV_2PI_LO, f);
-    s = __builtin_amdgcn_sinf(f);
-    c = __builtin_amdgcn_cosf(f);
-}
 
 // the d coordinates of one row: the inr_mgrid rule (last axis fastest, bit-exact linspace) or the caller's matrix
 template <bool FROM_GRID>
@@ -113,7 +81,7 @@ __global__ void __launch_bounds__(256) jet_fourier_kernel(float* __restrict__ ou
     for (int a = 0; a < JET_MAX_D; ++a)
         if (a < d) proj = fmaf(JET_TWO_PI * c[a], B[j * d + a], proj);
     float sn, cs;
-    jet_sincos(proj, sn, cs);
+    sincos_f32_ool(proj, sn, cs);
     o[j] = sn;
     o[m + j] = cs;
     float nb = 0.f;
@@ -148,7 +116,7 @@ __global__ void __launch_bounds__(256) jet_first_kernel(float* __restrict__ out,
     for (int a = 0; a < JET_MAX_D; ++a)
         if (a < d) z = fmaf(W0[h * d + a], c[a], z);
     float sn, cs;
-    jet_sincos(omega * z, sn, cs);
+    sincos_f32_ool(omega * z, sn, cs);
     const float oc = omega * cs;
     float* o = out + row * H + h;
     o[0] = sn;
@@ -162,8 +130,6 @@ __global__ void __launch_bounds__(256) jet_first_kernel(float* __restrict__ out,
         }
     if (lap) o[(1 + dt) * plane] = -((omega * omega * sn) * su);
 }
-
-__device__ __forceinline__ int jet_acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 // ---- one sine layer on J planes.  in: [J][.][lda] (lda a multiple of JET_KB, columns K .. lda - 1 zero), W [H][K], out [J][.][H].
 template <int J, bool LAP>
@@ -237,10 +203,10 @@ __global__ void __launch_bounds__(JET_THREADS) jet_layer_kernel(float* __restric
     const float o2 = omega * omega;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const long long row = row0 + wr * 32 + jet_acc_row(r, hh);
+        const long long row = row0 + wr * 32 + mfma32_acc_row(r, hh);
         if (row >= n_rows) continue;
         float sn, cs;
-        jet_sincos(omega * (acc[0][r] + bj), sn, cs);
+        sincos_f32_ool(omega * (acc[0][r] + bj), sn, cs);
         const float oc = omega * cs;
         float* o = out + row * H + col;
         o[0] = sn;
@@ -275,8 +241,7 @@ __global__ void __launch_bounds__(256) jet_head_kernel(float* __restrict__ y, fl
     }
 #pragma unroll
     for (int p = 0; p < JET_MAX_J; ++p)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) part[p] += __shfl_xor(part[p], off, 64);
+        part[p] = wave_sum(part[p]);
     if (lane != 0) return;
     y[row] = part[0] + b[0];
 #pragma unroll
@@ -364,7 +329,7 @@ int jet_launch_layer(int dt, int lap, hipStream_t st, float* out, long long out_
     }
 #undef JET_CASE
     INR_LAUNCH_CHECK();
-    jet_count(INR_JET_LF_LAYER);
+    count_launch(LF_JET_BASE + INR_JET_LF_LAYER);
     return 0;
 }
 
@@ -421,7 +386,7 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
             first_gemm = 1;
         }
         INR_LAUNCH_CHECK();
-        jet_count(INR_JET_LF_INPUT);
+        count_launch(LF_JET_BASE + INR_JET_LF_INPUT);
         for (int l = first_gemm; l < p.S; ++l) {
             const int K = l == 0 ? desc->in_features : H;
             const int lda = l == 0 ? p.pitch0 : H;
@@ -435,7 +400,7 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
                            lap ? lap + r0 : nullptr, buf[cur], (long long)chunk * H, params + p.w_off[p.S], params + p.b_off[p.S], H,
                            dt, has_q, rows);
         INR_LAUNCH_CHECK();
-        jet_count(INR_JET_LF_HEAD);
+        count_launch(LF_JET_BASE + INR_JET_LF_HEAD);
     }
     return 0;
 }
@@ -476,12 +441,6 @@ int inr_siren_jet_grid(const inr_siren_desc_t* desc, const float* params, const 
     }
     return jet_run("inr_siren_jet_grid", desc, params, nullptr, shape, total, dim, d_tangent, B, m, y, grad, lap, chunk_rows, workspace,
                    workspace_bytes, stream);
-}
-
-int inr_jet_launch_count(int family, int64_t* count) {
-    INR_REQUIRE(family >= 0 && family < INR_JET_LF_COUNT && count, INR_E_INVALID, "inr_jet_launch_count: bad arguments");
-    *count = (int64_t)g_jet_launches[family].load(std::memory_order_relaxed);
-    return 0;
 }
 
 }  // extern "C"

@@ -5,8 +5,6 @@
 
 namespace inr {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 struct GridShape {
     int64_t n[8];
     int dim;
@@ -67,12 +65,6 @@ __global__ void fourier_kernel(float* __restrict__ out, const float* __restrict_
 }
 
 // ---- a-5: head y = a W^T + b; one wave per row, shuffle reduction ---------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 template <bool VEC>
 __global__ void __launch_bounds__(256) head_forward_kernel(float* __restrict__ y, float* __restrict__ dy,
                                                            const float* __restrict__ a,
@@ -198,8 +190,7 @@ __global__ void __launch_bounds__(256) head_bwd_fused_kernel(float* dz, float* _
         sw += g * a4;
     }
     if (amax_out) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) omax = fmaxf(omax, __shfl_xor(omax, off, 64));
+        omax = wave_max(omax);
         if ((threadIdx.x & 63) == 0 && omax > 0.f) atomicMax(amax_out, __float_as_uint(omax));
     }
     red[0][threadIdx.x] = sb;
@@ -295,8 +286,7 @@ __global__ void __launch_bounds__(256) head_step_fused_kernel(float* dz, float* 
         part_g[blockIdx.x] = (red_s[1][0] + red_s[1][1]) + (red_s[1][2] + red_s[1][3]);
     }
     if (amax_out) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) omax = fmaxf(omax, __shfl_xor(omax, off, 64));
+        omax = wave_max(omax);
         if (lane == 0 && omax > 0.f) atomicMax(amax_out, __float_as_uint(omax));
     }
 }
@@ -443,13 +433,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(const FinalizeJob job) {
     const int64_t at = sg.dst + i;
     job.grads[at] = gi;
     if (job.params) {
-        const float m0 = job.m[at], v0 = job.v[at];
-        const float mi = fmaf(gi - m0, job.one_minus_b1, m0);
-        const float vi = fmaf(job.one_minus_b2 * gi, gi, v0 * job.b2);
-        const float denom = __fsqrt_rn(vi) / job.bc2_sqrt + job.eps;
-        job.m[at] = mi;
-        job.v[at] = vi;
-        job.params[at] = job.params[at] - job.step_size * (mi / denom);
+        adam_update(job.params[at], job.m[at], job.v[at], gi, job.adam);
     }
 }
 
@@ -497,17 +481,15 @@ __global__ void __launch_bounds__(256) finalize_v4_kernel(const FinalizeJob job)
         const f32x4 g4 = (a0 + a1) + (a2 + a3);
         *reinterpret_cast<f32x4*>(job.grads + at) = g4;
         if (job.params) {
-            const f32x4 m0 = *reinterpret_cast<const f32x4*>(job.m + at), v0 = *reinterpret_cast<const f32x4*>(job.v + at);
-            f32x4 p4 = *reinterpret_cast<const f32x4*>(job.params + at), m4, v4;
+            f32x4 m4 = *reinterpret_cast<const f32x4*>(job.m + at), v4 = *reinterpret_cast<const f32x4*>(job.v + at);
+            f32x4 p4 = *reinterpret_cast<const f32x4*>(job.params + at);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float gi = g4[q];
-                const float mi = fmaf(gi - m0[q], job.one_minus_b1, m0[q]);
-                const float vi = fmaf(job.one_minus_b2 * gi, gi, v0[q] * job.b2);
-                const float denom = __fsqrt_rn(vi) / job.bc2_sqrt + job.eps;
-                m4[q] = mi;
-                v4[q] = vi;
-                p4[q] = p4[q] - job.step_size * (mi / denom);
+                float pq = p4[q], mq = m4[q], vq = v4[q];
+                adam_update(pq, mq, vq, g4[q], job.adam);
+                p4[q] = pq;
+                m4[q] = mq;
+                v4[q] = vq;
             }
             *reinterpret_cast<f32x4*>(job.m + at) = m4;
             *reinterpret_cast<f32x4*>(job.v + at) = v4;
@@ -529,13 +511,7 @@ __global__ void __launch_bounds__(256) finalize_v4_kernel(const FinalizeJob job)
         const int64_t aj = sg.dst + j;
         job.grads[aj] = gi;
         if (job.params) {
-            const float m0 = job.m[aj], v0 = job.v[aj];
-            const float mi = fmaf(gi - m0, job.one_minus_b1, m0);
-            const float vi = fmaf(job.one_minus_b2 * gi, gi, v0 * job.b2);
-            const float denom = __fsqrt_rn(vi) / job.bc2_sqrt + job.eps;
-            job.m[aj] = mi;
-            job.v[aj] = vi;
-            job.params[aj] = job.params[aj] - job.step_size * (mi / denom);
+            adam_update(job.params[aj], job.m[aj], job.v[aj], gi, job.adam);
         }
     }
 }
@@ -548,12 +524,7 @@ __global__ void __launch_bounds__(256) adam_kernel(float* __restrict__ p, const 
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
         const float gi = g[i];
-        const float mi = fmaf(gi - m[i], one_minus_b1, m[i]);           // m.lerp_(g, 1-b1)
-        const float vi = fmaf(one_minus_b2 * gi, gi, v[i] * b2);        // v*b2 + (1-b2)*g*g
-        const float denom = __fsqrt_rn(vi) / bc2_sqrt + eps;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = p[i] - step_size * (mi / denom);
+        adam_update(p[i], m[i], v[i], gi, AdamConsts{one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps});
     }
 }
 
@@ -786,15 +757,7 @@ int launch_finalize(FinalizeJob& job, long long adam_step, double lr, double b1,
         job.s1_first[k + 1] = job.s1_first[k] + blocks;
     }
     const long long s1_blocks = job.s1_first[job.nseg];
-    if (job.params) {
-        const double bc1 = 1.0 - pow(b1, (double)adam_step), bc2 = 1.0 - pow(b2, (double)adam_step);
-        job.one_minus_b1 = (float)(1.0 - b1);
-        job.b2 = (float)b2;
-        job.one_minus_b2 = (float)(1.0 - b2);
-        job.step_size = (float)(lr / bc1);
-        job.bc2_sqrt = (float)sqrt(bc2);
-        job.eps = (float)eps;
-    }
+    if (job.params) job.adam = adam_consts(adam_step, lr, b1, b2, eps);
     ProfScope ps(KC_OTHER, st);
     if (s1_blocks > 0) {
         INR_REQUIRE(s1_blocks < (1ll << 31), INR_E_INVALID, "finalize: too many first-stage blocks (%lld)", s1_blocks);
@@ -825,15 +788,10 @@ int launch_finalize(FinalizeJob& job, long long adam_step, double lr, double b1,
 int launch_adam(float* p, const float* g, float* m, float* v, int64_t count, int64_t step, double lr, double b1,
                 double b2, double eps, hipStream_t st) {
     if (count == 0) return 0;
-    // host-side double bias corrections, as torch's _single_tensor_adam does for python-float lr
-    const double bc1 = 1.0 - pow(b1, (double)step);
-    const double bc2 = 1.0 - pow(b2, (double)step);
-    const double step_size = lr / bc1;
-    const double bc2_sqrt = sqrt(bc2);
+    const AdamConsts a = adam_consts(step, lr, b1, b2, eps);
     ProfScope ps(KC_OTHER, st);
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(count, 256, 4096)), dim3(256), 0, st, p, g, m, v, count,
-                       (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)step_size, (float)bc2_sqrt,
-                       (float)eps);
+    hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(count, 256, 4096)), dim3(256), 0, st, p, g, m, v, count, a.one_minus_b1,
+                       a.b2, a.one_minus_b2, a.step_size, a.bc2_sqrt, a.eps);
     INR_LAUNCH_CHECK();
     return 0;
 }

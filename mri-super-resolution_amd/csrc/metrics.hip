@@ -6,21 +6,6 @@
 
 namespace inr {
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double block_sum_f64(double v, double* red /*[4]*/) {
-    v = wave_sum_f64(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double s = (red[0] + red[1]) + (red[2] + red[3]);
-    __syncthreads();
-    return s;
-}
-
 // partial[b][blk] = sum over a slice of image b of (x - y)^2
 __global__ void __launch_bounds__(256) sqdiff_kernel(double* __restrict__ partial, const float* __restrict__ x,
                                                      const float* __restrict__ y, int64_t per_image, int blocks_per_image) {

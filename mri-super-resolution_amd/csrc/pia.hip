@@ -19,21 +19,10 @@
 // Gradient reduction, loss and Adam are the fused step's launch_finalize (kernels.hip): no float atomics anywhere.
 #include "internal.h"
 
-#include <atomic>
-
 namespace inr {
-
-// launch families of this file (INR_PIA_LF_* of include/inrhip.h), counted like the SIREN families but in their own table
-static std::atomic<long long> g_pia_launches[INR_PIA_LF_COUNT];
-void pia_launch_counts_reset() {
-    for (int f = 0; f < INR_PIA_LF_COUNT; ++f) g_pia_launches[f].store(0, std::memory_order_relaxed);
-}
 
 namespace {
 
-inline void pia_count(int family) { g_pia_launches[family].fetch_add(1, std::memory_order_relaxed); }
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(4))) f4u {   // four floats at 4-byte alignment: tensors of the flat parameter buffer start anywhere
     float x, y, z, w;
 };
@@ -201,7 +190,7 @@ int pia_launch_gemm(const PiaGemm& p, int nbatch, bool big, hipStream_t st) {
         hipLaunchKernelGGL((pia_gemm_kernel<2, 2, A_KC, B_KC, EPI>), grid, dim3(256), 0, st, p);
     }
     INR_LAUNCH_CHECK();
-    pia_count(EPI == PIA_FWD ? INR_PIA_LF_FWD : EPI == PIA_DX ? INR_PIA_LF_DX : INR_PIA_LF_DW);
+    count_launch(LF_PIA_BASE + (EPI == PIA_FWD ? INR_PIA_LF_FWD : EPI == PIA_DX ? INR_PIA_LF_DX : INR_PIA_LF_DW));
     return 0;
 }
 
@@ -251,12 +240,6 @@ struct PiaHead {
     int fused;              // 1: the loss is formed here from x and pids
 };
 
-template <typename T>
-__device__ __forceinline__ T wave_sum64(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 template <typename T>
 __device__ __forceinline__ T group_sum16(T v) {
 #pragma unroll
@@ -309,7 +292,7 @@ __global__ void __launch_bounds__(256) pia_head_kernel(const PiaHead p) {
                 float s = 0.f;
 #pragma unroll
                 for (int e = 0; e < E; ++e) s = fmaf(hv[j][e], w[j][c][e], s);
-                o[j][c] = wave_sum64(s) + bo[j][c];
+                o[j][c] = wave_sum(s) + bo[j][c];
             }
         }
         // encode (PIA.py:106-110)
@@ -603,7 +586,7 @@ int pia_launch_head(const PiaHead& a, int H, long long waves, hipStream_t st) {
     else
         hipLaunchKernelGGL((pia_head_kernel<1, BWD>), grid, dim3(256), 0, st, a);
     INR_LAUNCH_CHECK();
-    pia_count(INR_PIA_LF_HEAD);
+    count_launch(LF_PIA_BASE + INR_PIA_LF_HEAD);
     return 0;
 }
 
@@ -910,12 +893,6 @@ int inr_pia_fit_step(const inr_pia_desc_t* desc, float* params, float* grads, fl
         if (int rc = pia_launch_head<true>(a, s.H, w.waves, st)) return rc;
     }
     return pia_backward_layers(s, desc, params, params, grads, m, v, x, n, w, true, loss, step, lr, beta1, beta2, eps, st);
-}
-
-int inr_pia_launch_count(int family, int64_t* count) {
-    INR_REQUIRE(family >= 0 && family < INR_PIA_LF_COUNT && count, INR_E_INVALID, "inr_pia_launch_count: bad arguments");
-    *count = (int64_t)g_pia_launches[family].load(std::memory_order_relaxed);
-    return 0;
 }
 
 int inr_pids_slice(float* adc_high, float* adc_negative, float* b_decay, float* te_decay, const double* S, const double* bvals,

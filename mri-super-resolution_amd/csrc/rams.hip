@@ -18,10 +18,6 @@
 
 namespace inr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int RC = 32;                      // feature channels of the 3-D trunk (network.py: filters = 32)
 constexpr int CONV_THREADS = 512;           // 8 waves share one LDS copy of the kernel
 constexpr int CONV_W_FLOATS = 27 * RC * RC;
@@ -154,7 +150,7 @@ __global__ void __launch_bounds__(CONV_THREADS, 2) conv3d_c32_mfma_kernel(const 
             float* yb = p.y + ((long long)b * ovox + (long long)tile * 32) * p.y_cstride + l32;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = mfma32_acc_row(r, h);
                 float o = acc[m][r] + bias;
                 if (p.relu) o = fmaxf(o, 0.f);
                 if (tile * 32 + row < ovox) {
@@ -1078,7 +1074,7 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_wgrad_kernel(const Conv3dWg
             for (int s = 0; s < 4; ++s) acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(xv[3][s], dyv[s], acc[3], 0, 0, 0);
         }
     }
-    // C/D map: col = lane & 31 (co), row = (r & 3) + 8 (r >> 2) + 4 h (ci)
+    // C/D map: col = lane & 31 (co), row = mfma32_acc_row(r, h) (ci)
     const long long blk = (long long)b * gridDim.x + blockIdx.x;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -1086,7 +1082,7 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_wgrad_kernel(const Conv3dWg
         if (tap < 27) {
             float* dst = p.slab + (blk * 27 + tap) * RC * RC + l32;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) dst[((r & 3) + 8 * (r >> 2) + 4 * h) * RC] = acc[t][r];
+            for (int r = 0; r < 16; ++r) dst[mfma32_acc_row(r, h) * RC] = acc[t][r];
         }
     }
 }

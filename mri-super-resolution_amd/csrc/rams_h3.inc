@@ -57,8 +57,7 @@ constexpr int R3_SLOT = 1024;
 __device__ __forceinline__ void r3_block_amax(float v, unsigned* slot) {      // every thread of the block, exactly once
     __shared__ float r3_red[16];
     float m = fabsf(v);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+    m = wave_max(m);
     const int nw = (blockDim.x + 63) >> 6;
     if ((threadIdx.x & 63) == 0) r3_red[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -101,7 +100,7 @@ __device__ __forceinline__ void rams_weight_split_body(const R3SplitJob j) {
     __shared__ float amax_s;
     float m = 0.f;
     for (int i = threadIdx.x; i < CONV_W_FLOATS; i += 512) m = fmaxf(m, fabsf(j.w[i]));
-#pragma unroll
+#pragma unroll   // wave_max(), open-coded: through the helper this translation unit's instruction schedule changes
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
@@ -278,7 +277,7 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_h3_kernel(const Conv3
             float* yb = p.y + ((long long)b * ovox + (long long)tile * 32) * p.y_cstride + l32;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int row = mfma32_acc_row(r, h);
                 float o = (acc[m][r] * ua) * ub + bias;
                 if (p.relu) o = fmaxf(o, 0.f);
                 if (tile * 32 + row < ovox) {
@@ -947,7 +946,7 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_lds2_kernel(const Con
                 float tsum = 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int row = (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int row = mfma32_acc_row(r, h);
                     const long long vo = __shfl(gofs[m], row, 64);
                     float o = (acc[m][r] * ua) * ub + bias;
                     if (p.relu) o = fmaxf(o, 0.f);

@@ -16,9 +16,6 @@
 
 namespace inr {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int SMALL_MAX_LAYERS = 16;   // sine layers (1 + hidden_layers)
 
 struct SmallParams {
@@ -35,8 +32,6 @@ struct SmallParams {
     int N, F, S;                // rows, in_features, sine layers
     float first_omega, hidden_omega, inv_count;
 };
-
-__device__ __forceinline__ int acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 template <int H>
 __global__ void __launch_bounds__(256) siren_small_step_kernel(const SmallParams p) {
@@ -124,7 +119,7 @@ __global__ void __launch_bounds__(256) siren_small_step_kernel(const SmallParams
             const float bj = bias[j];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = acc_row(r, hh);
+                const int i = mfma32_acc_row(r, hh);
                 float sv, cv;
                 sincos_f32(omega * (acc[ct][r] + bj), sv, cv);
                 const float dv = omega * cv;
@@ -181,7 +176,7 @@ __global__ void __launch_bounds__(256) siren_small_step_kernel(const SmallParams
         float gw = 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int i = acc_row(r, hh);
+            const int i = mfma32_acc_row(r, hh);
             const float gi = gbuf[wave][i];
             gw = fmaf(gi, stageA[i * LDS_STRIDE + j], gw);
             dz[ct][r] = gi * wj * dlast[ct][r];
@@ -211,7 +206,7 @@ __global__ void __launch_bounds__(256) siren_small_step_kernel(const SmallParams
             for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int i = acc_row(r, hh);
+                    const int i = mfma32_acc_row(r, hh);
                     d_pref[ct][r] = (r0 + i < p.N) ? d_in[(long long)(r0 + i) * H + ct * 32 + l32] : 0.f;
                 }
         }
@@ -224,7 +219,7 @@ __global__ void __launch_bounds__(256) siren_small_step_kernel(const SmallParams
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 gb += dz[ct][r];
-                stageD[acc_row(r, hh) * LDS_STRIDE + j] = dz[ct][r];
+                stageD[mfma32_acc_row(r, hh) * LDS_STRIDE + j] = dz[ct][r];
             }
             gb += __shfl_xor(gb, 32, 64);
             if (hh == 0) slab[p.b_off[l] + j] = gb;
@@ -281,7 +276,7 @@ __global__ void __launch_bounds__(256) siren_small_step_kernel(const SmallParams
                 if (kc < K) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        slab[p.w_off[l] + (long long)(ht * 32 + acc_row(r, hh)) * K + kc] = wacc[r];
+                        slab[p.w_off[l] + (long long)(ht * 32 + mfma32_acc_row(r, hh)) * K + kc] = wacc[r];
                 }
             }
         }
@@ -317,12 +312,7 @@ __global__ void __launch_bounds__(256) small_reduce_adam_kernel(float* __restric
     if (q == 0 && i < P) {
         const float gi = (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
         grads[i] = gi;
-        const float mi = fmaf(gi - m[i], one_minus_b1, m[i]);
-        const float vi = fmaf(one_minus_b2 * gi, gi, v[i] * b2);
-        const float denom = __fsqrt_rn(vi) / bc2_sqrt + eps;
-        m[i] = mi;
-        v[i] = vi;
-        params[i] = params[i] - step_size * (mi / denom);
+        adam_update(params[i], m[i], v[i], gi, AdamConsts{one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps});
     }
     if (blockIdx.x == 0 && loss_out) {
         float acc = 0.f;
@@ -375,10 +365,10 @@ int small_fit_step(const inr_siren_desc_t* d, const long long* w_off, const long
         hipLaunchKernelGGL(siren_small_step_kernel<32>, dim3(blocks), dim3(256), 0, st, p);
     INR_LAUNCH_CHECK();
     count_launch(LF_SMALL_STEP);
-    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
+    const AdamConsts a = adam_consts(step, lr, b1, b2, eps);
     hipLaunchKernelGGL(small_reduce_adam_kernel, dim3((unsigned)((P + 63) / 64)), dim3(256), 0, st, params, grads, m, v,
-                       p.slabs, nwaves, P, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(lr / bc1),
-                       (float)sqrt(bc2), (float)eps, loss_out, p.loss_partial, p.inv_count);
+                       p.slabs, nwaves, P, a.one_minus_b1, a.b2, a.one_minus_b2, a.step_size, a.bc2_sqrt, a.eps, loss_out,
+                       p.loss_partial, p.inv_count);
     INR_LAUNCH_CHECK();
     return 0;
 }
@@ -925,19 +915,16 @@ __device__ __forceinline__ void small_multi_body(const SmallMulti& p, const Smal
                 for (int off = 1; off < tpp; off <<= 1) gi += __shfl_xor(gi, off, 64);
                 if (live && ql == 0) {
                     q.grads[i] = gi;
-                    const float mi = fmaf(gi - m0, p.one_minus_b1, m0);
-                    const float vi = fmaf(p.one_minus_b2 * gi, gi, v0 * p.b2);
-                    const float denom = __fsqrt_rn(vi) / bc2_sqrt + p.eps;
-                    q.m[i] = mi;
-                    q.v[i] = vi;
-                    store_shared(q.params + i, w0 - step_size * (mi / denom));
+                    adam_update(w0, m0, v0, gi, AdamConsts{p.one_minus_b1, p.b2, p.one_minus_b2, step_size, bc2_sqrt, p.eps});
+                    q.m[i] = m0;
+                    q.v[i] = v0;
+                    store_shared(q.params + i, w0);
                 }
             }
             if (blk == 0 && wave == 0 && q.losses) {
                 float ls = 0.f;
                 for (int b = lane; b < nblk; b += 64) ls += load_shared(q.loss_partial + b);
-#pragma unroll
-                for (int off = 32; off > 0; off >>= 1) ls += __shfl_xor(ls, off, 64);
+                ls = wave_sum(ls);
                 if (lane == 0) q.losses[step] = ls * p.inv_count;
             }
         }
@@ -1059,9 +1046,9 @@ static SmallProb small_prob(const inr_siren_desc_t* d, int64_t n, long long P, f
     return q;
 }
 
-// What the problems of a launch share: shape, coordinates, block split, reduction lanes, Adam constants.
+// What the problems of a launch share: shape, coordinates, block split, reduction lanes.
 static void small_shared(SmallMulti& p, const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P,
-                         const float* x, int64_t n, double b1, double b2, double eps) {
+                         const float* x, int64_t n) {
     const int S = d->hidden_layers + 1;
     const int nb = multi_blocks(d, n);
     p.x = x;
@@ -1071,19 +1058,20 @@ static void small_shared(SmallMulti& p, const inr_siren_desc_t* d, const long lo
     while (p.tpp < 8 && (long long)nb * SM_THREADS / (2 * p.tpp) >= P) p.tpp *= 2;   // lanes per parameter in the reduction
     p.first_omega = d->first_omega; p.hidden_omega = d->hidden_omega;
     p.inv_count = (float)(1.0 / (double)n);
-    p.one_minus_b1 = (float)(1.0 - b1); p.b2 = (float)b2; p.one_minus_b2 = (float)(1.0 - b2); p.eps = (float)eps;
     p.stamps = g_stamps;
     const int lim = g_small_spin_limit;
     p.spin_limit = lim > 0 ? (unsigned)lim : SM_SPIN_LIMIT;
 }
 
-// The Adam step sizes of steps [first_step + done, first_step + done + k) of one launch.
-static void small_schedule(SmallMulti& p, int64_t first_step, int done, int k, double lr, double b1, double b2) {
+// The Adam constants of steps [first_step + done, first_step + done + k) of one launch.
+static void small_schedule(SmallMulti& p, int64_t first_step, int done, int k, double lr, double b1, double b2, double eps) {
     p.n_steps = k;
+    const AdamConsts a0 = adam_consts(first_step + done, lr, b1, b2, eps);   // these four are the same at every step
+    p.one_minus_b1 = a0.one_minus_b1; p.b2 = a0.b2; p.one_minus_b2 = a0.one_minus_b2; p.eps = a0.eps;
     for (int i = 0; i < k; ++i) {
-        const double t = (double)(first_step + done + i);
-        p.step_size[i] = (float)(lr / (1.0 - pow(b1, t)));
-        p.bc2_sqrt[i] = (float)sqrt(1.0 - pow(b2, t));
+        const AdamConsts a = adam_consts(first_step + done + i, lr, b1, b2, eps);
+        p.step_size[i] = a.step_size;
+        p.bc2_sqrt[i] = a.bc2_sqrt;
     }
 }
 
@@ -1097,12 +1085,12 @@ int small_fit_multi(const inr_siren_desc_t* d, const long long* w_off, const lon
     const int nb = multi_blocks(d, n);
     SmallMulti p{};
     p.q = small_prob(d, n, P, params, grads, m, v, targets, weights, n_acq, ws);
-    small_shared(p, d, w_off, b_off, P, x, n, b1, b2, eps);
+    small_shared(p, d, w_off, b_off, P, x, n);
     for (int done = 0; done < n_steps; done += SM_MAX_STEPS) {
         const int k = n_steps - done < SM_MAX_STEPS ? n_steps - done : SM_MAX_STEPS;
         p.q.first_acq = (int)(((long long)first_acq + done) % n_acq);
         p.q.losses = losses ? losses + done : nullptr;
-        small_schedule(p, first_step, done, k, lr, b1, b2);
+        small_schedule(p, first_step, done, k, lr, b1, b2, eps);
         ProfScope ps(KC_OTHER, st);
         INR_HIP(hipMemsetAsync(p.q.sync, 0, (done == 0 ? 2 : 1) * sizeof(unsigned), st));   // the error word is sticky within a call
         void* args[] = {(void*)&p};
@@ -1157,7 +1145,7 @@ int small_fit_batch(const inr_siren_desc_t* d, const long long* w_off, const lon
     for (int g0 = 0; g0 < n_fits; g0 += per) {
         const int cnt = n_fits - g0 < per ? n_fits - g0 : per;
         SmallBatch b{};
-        small_shared(b.p, d, w_off, b_off, P, x, n, b1, b2, eps);
+        small_shared(b.p, d, w_off, b_off, P, x, n);
         b.p.stamps = nullptr;   // (a stamp buffer is sized for one problem's grid: batched launches do not stamp)
         SyncTable t{};
         for (int j = 0; j < cnt; ++j) {
@@ -1173,7 +1161,7 @@ int small_fit_batch(const inr_siren_desc_t* d, const long long* w_off, const lon
                 b.probs[j].first_acq = (int)(((long long)first_acq[i] + done) % n_acq[i]);
                 b.probs[j].losses = (losses && losses[i]) ? losses[i] + done : nullptr;
             }
-            small_schedule(b.p, first_step, done, k, lr, b1, b2);
+            small_schedule(b.p, first_step, done, k, lr, b1, b2, eps);
             ProfScope ps(KC_OTHER, st);
             // arrivals back to zero; the error words too on a problem's first launch (sticky within the call)
             hipLaunchKernelGGL(small_batch_sync_reset, dim3(1), dim3(64), 0, st, t, cnt, done == 0 ? 2 : 1);

@@ -615,40 +615,32 @@ def siren_backward_train(desc: SirenDesc, params, grads, gy, workspace):
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
                    "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order
-PIA_LAUNCH_FAMILIES = ("pia_fwd", "pia_dx", "pia_dw", "pia_head")                        # INR_PIA_LF_*, a table of its own
+PIA_LAUNCH_FAMILIES = ("pia_fwd", "pia_dx", "pia_dw", "pia_head")                        # INR_PIA_LF_*, numbered from 0
+JET_LAUNCH_FAMILIES = ("jet_input", "jet_layer", "jet_head")                             # INR_JET_LF_*, numbered from 0
+
+
+def _family_counts(entry: str, names) -> dict:
+    out = {}
+    for i, name in enumerate(names):
+        n = C.c_int64(0)
+        check(getattr(lib(), entry)(i, C.byref(n)), entry)
+        out[name] = int(n.value)
+    return out
 
 
 def launch_counts() -> dict:
     """Launches each kernel family has received since the last ``launch_counts_reset()`` (process-global)."""
-    out = {}
-    for i, name in enumerate(LAUNCH_FAMILIES):
-        n = C.c_int64(0)
-        check(lib().inr_launch_count(i, C.byref(n)), "inr_launch_count")
-        out[name] = int(n.value)
-    return out
+    return _family_counts("inr_launch_count", LAUNCH_FAMILIES)
 
 
 def pia_launch_counts() -> dict:
     """Launches each PIA kernel family has received since the last ``launch_counts_reset()``."""
-    out = {}
-    for i, name in enumerate(PIA_LAUNCH_FAMILIES):
-        n = C.c_int64(0)
-        check(lib().inr_pia_launch_count(i, C.byref(n)), "inr_pia_launch_count")
-        out[name] = int(n.value)
-    return out
-
-
-JET_LAUNCH_FAMILIES = ("jet_input", "jet_layer", "jet_head")                             # INR_JET_LF_*, a table of its own
+    return _family_counts("inr_pia_launch_count", PIA_LAUNCH_FAMILIES)
 
 
 def jet_launch_counts() -> dict:
     """Launches each derivative-kernel family has received since the last ``launch_counts_reset()``."""
-    out = {}
-    for i, name in enumerate(JET_LAUNCH_FAMILIES):
-        n = C.c_int64(0)
-        check(lib().inr_jet_launch_count(i, C.byref(n)), "inr_jet_launch_count")
-        out[name] = int(n.value)
-    return out
+    return _family_counts("inr_jet_launch_count", JET_LAUNCH_FAMILIES)
 
 
 def launch_counts_reset():

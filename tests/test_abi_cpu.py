@@ -205,3 +205,24 @@ def test_debug_switches_are_validated_readable_and_resettable():
     for fam in range(_lib.INR_LF_COUNT):
         assert lib.inr_launch_count(fam, ctypes.byref(n)) == 0 and n.value == 0
     assert lib.inr_launch_count(_lib.INR_LF_COUNT, ctypes.byref(n)) == _lib.INR_E_INVALID
+
+
+def test_launch_counters_share_one_reset_and_keep_their_id_ranges():
+    """Every launch family reads 0 through its own entry point after one reset; the accepted ids are exactly 0..13 and 32..35
+    (inr_launch_count), 0..3 (inr_pia_launch_count) and 0..2 (inr_jet_launch_count) -- the table's internal PIA / jet bases,
+    which start where the ERD ids end, are not reachable -- and a null `count` is refused everywhere."""
+    lib = _lib.lib()
+    n = ctypes.c_int64(-1)
+    assert lib.inr_launch_counts_reset() == 0
+    for entry, ids in ((lib.inr_launch_count, list(range(14)) + [32, 33, 34, 35]), (lib.inr_pia_launch_count, range(4)),
+                       (lib.inr_jet_launch_count, range(3))):
+        for fam in ids:
+            n.value = -1
+            assert entry(fam, ctypes.byref(n)) == 0 and n.value == 0, fam
+            assert entry(fam, None) == _lib.INR_E_INVALID, fam
+    pia_base, jet_base = 36, 36 + _lib.INR_PIA_LF_COUNT
+    for bad in [-1, 14, 31, 36] + list(range(pia_base, jet_base + _lib.INR_JET_LF_COUNT + 1)):
+        assert lib.inr_launch_count(bad, ctypes.byref(n)) == _lib.INR_E_INVALID, bad
+    assert lib.inr_pia_launch_count(4, ctypes.byref(n)) == _lib.INR_E_INVALID
+    assert lib.inr_pia_launch_count(-1, ctypes.byref(n)) == _lib.INR_E_INVALID
+    assert lib.inr_jet_launch_count(3, ctypes.byref(n)) == _lib.INR_E_INVALID

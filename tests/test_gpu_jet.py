@@ -32,18 +32,6 @@ def host_case(name):
     return _CACHE[name]
 
 
-def on_device(case):
-    """(desc, flat parameter buffer, x, B) on the GPU, laid out by inr_siren_param_offsets."""
-    desc = ops.make_desc(case["in_features"], case["hidden"], case["hidden_layers"], 1, jc.OMEGA, jc.OMEGA)
-    total, offsets = ops.siren_param_layout(desc)
-    flat = torch.zeros(total, dtype=torch.float32)
-    for (w_off, b_off), (W, b) in zip(offsets, case["weights"]):
-        flat[w_off:w_off + W.numel()] = W.reshape(-1)
-        flat[b_off:b_off + b.numel()] = b
-    B = None if case["B"] is None else case["B"].cuda()
-    return desc, flat.cuda(), case["x"].cuda(), B
-
-
 def check_accuracy(tag, got, ref, dev32):
     y, g, lap = got
     errs = (jc.rel_l2(y, ref[0]), jc.rel_l2(g, ref[1]), jc.rel_l2(lap, ref[2]))
@@ -57,7 +45,7 @@ def check_accuracy(tag, got, ref, dev32):
 @pytest.mark.parametrize("name", sorted(jc.CASES))
 def test_accuracy_launch_counts_and_forward_parity(name):
     case, ref, dev32 = host_case(name)
-    desc, flat, x, B = on_device(case)
+    desc, flat, x, B = jc.on_device(case)
     ops.launch_counts_reset()
     got = ops.siren_jet(desc, flat, x=x, B=B, chunk_rows=jc.CHUNK)
     counts = ops.jet_launch_counts()
@@ -76,7 +64,7 @@ def test_accuracy_launch_counts_and_forward_parity(name):
 @pytest.mark.parametrize("name", sorted(jc.CASES))
 def test_bits_do_not_depend_on_chunking_repetition_or_requested_outputs(name):
     case, _, _ = host_case(name)
-    desc, flat, x, B = on_device(case)
+    desc, flat, x, B = jc.on_device(case)
     y, g, lap = ops.siren_jet(desc, flat, x=x, B=B, chunk_rows=jc.CHUNK)
     for other in (ops.siren_jet(desc, flat, x=x, B=B, chunk_rows=jc.ROWS),      # one chunk
                   ops.siren_jet(desc, flat, x=x, B=B, chunk_rows=jc.CHUNK),     # a second run
@@ -94,7 +82,7 @@ def test_bits_do_not_depend_on_chunking_repetition_or_requested_outputs(name):
 def test_grid_entry_point_is_bit_equal_with_explicit_rows():
     """Case e: case b as the grid 11 x 31 x 3."""
     case, ref, dev32 = host_case("b")
-    desc, flat, x, B = on_device(case)
+    desc, flat, x, B = jc.on_device(case)
     assert torch.equal(inr.get_mgrid(case["grid"]), x)
     rows = ops.siren_jet(desc, flat, x=x, B=B, chunk_rows=jc.CHUNK)
     ops.launch_counts_reset()
@@ -105,7 +93,7 @@ def test_grid_entry_point_is_bit_equal_with_explicit_rows():
     check_accuracy("e (grid)", grid, ref, dev32)
     # raw coordinates through the grid form too (case a is the grid 31 x 33)
     case_a, ref_a, dev_a = host_case("a")
-    desc_a, flat_a, x_a, _ = on_device(case_a)
+    desc_a, flat_a, x_a, _ = jc.on_device(case_a)
     grid_a = ops.siren_jet(desc_a, flat_a, shape=case_a["grid"], chunk_rows=jc.CHUNK)
     for a, b in zip(grid_a, ops.siren_jet(desc_a, flat_a, x=x_a, chunk_rows=jc.CHUNK)):
         assert torch.equal(a, b)
@@ -115,7 +103,7 @@ def test_d_tangent_names_the_leading_axes():
     """4-D input, tangents along the three leading axes: the gradient equals those columns of the full call bit for bit, and the
     Laplacian the float64 restatement summed over those axes only."""
     case, ref, _ = host_case("c")
-    desc, flat, x, B = on_device(case)
+    desc, flat, x, B = jc.on_device(case)
     full = ops.siren_jet(desc, flat, x=x, B=B, chunk_rows=jc.CHUNK)
     y, g, lap = ops.siren_jet(desc, flat, x=x, B=B, d_tangent=3, chunk_rows=jc.CHUNK)
     assert tuple(g.shape) == (jc.ROWS, 3)
