@@ -6,7 +6,7 @@ The directory name carries a hyphen (it is the project name), so import it throu
 ``sys.path`` to get drop-in ``SRDWI`` / ``INRmodel`` / ``nn_mri`` modules for the reference's drivers.
 
 Layout:  csrc/ (HIP kernels + C ABI, built into libinrhip.so) . _lib.py (ctypes binding) . ops.py
-(tensor wrappers) . inr.py (reference module surface + fused fit / reconstruct) . metrics.py . baselines.py (spline
+(tensor wrappers) . flat.py (flat parameter buffer, workspaces and Adam state of every fitter) . inr.py (reference module surface + fused fit / reconstruct) . metrics.py . baselines.py (spline
 rescale) . drivers.py (the reference's driver loops) . dist.py (fit partitioning over GPUs, metric gather) . matio.py
 (.mat level 5) . reports.py (CSV schemas) . contrast.py (case / calculate_contrast) . scripts/ (superresDWI, master).
 """

@@ -11,6 +11,7 @@ fine-tuning step) on the fused kernels of ``csrc/erd_siren.hip``; ``soft_erd`` i
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 
 import numpy as np
 import torch
@@ -19,6 +20,7 @@ from torch import nn
 from . import ops
 from ._lib import INR_ERD_COLLAPSED, INR_ERD_CONVERGED, INR_ERD_RUNNING, check, lib
 from .contrast import eps, mag      # INR_ERD.py:25-26, the same two constants as master.py:42-43
+from .flat import AdamOwner, AdamState, FlatParams, Workspace
 from .inr import SineLayer
 
 STATE_NAMES = {INR_ERD_RUNNING: "running", INR_ERD_CONVERGED: "converged", INR_ERD_COLLAPSED: "collapsed"}
@@ -33,13 +35,8 @@ def _check_shape(in_features, hidden_features, hidden_layers, out_features):
 
 def erd_param_layout(desc):
     """(total, [(w_off, b_off)] per tensor in kernel order: trunk layers, head, perturb_linear, perturb_linear2, group_b)."""
-    total = lib().inr_erd_param_count(C.byref(desc))
-    if total < 0:
-        check(-1, "inr_erd_param_count")
-    tensors = desc.hidden_layers + 5
-    offs = (C.c_int64 * (2 * tensors + 1))()
-    check(lib().inr_erd_param_offsets(C.byref(desc), offs, 2 * tensors + 1), "inr_erd_param_offsets")
-    return int(total), [(int(offs[2 * t]), int(offs[2 * t + 1])) for t in range(tensors)], int(offs[2 * tensors])
+    total, offs = ops.param_layout(lib().inr_erd_param_count, lib().inr_erd_param_offsets, desc, 2 * (desc.hidden_layers + 5) + 1)
+    return total, list(zip(offs[0:-1:2], offs[1:-1:2])), offs[-1]
 
 
 class ErdSiren(nn.Module):
@@ -101,14 +98,8 @@ class ErdSiren(nn.Module):
         fitter = getattr(self, "_fitter", None)
         if fitter is not None and fitter.owns(self):
             return fitter.flat
-        desc = self.desc()
-        total, offsets, _ = erd_param_layout(desc)
-        params = self.kernel_parameters()
-        flat = torch.zeros(total, dtype=torch.float32, device=params[0].device)
-        for t, (w_off, b_off) in enumerate(offsets):
-            flat[w_off:w_off + params[2 * t].numel()] = params[2 * t].detach().reshape(-1)
-            flat[b_off:b_off + params[2 * t + 1].numel()] = params[2 * t + 1].detach().reshape(-1)
-        return flat
+        total, offsets, _ = erd_param_layout(self.desc())
+        return FlatParams(total, itertools.chain.from_iterable(offsets)).pack(self.kernel_parameters())
 
     def forward(self, coords, sample=0, eps=0, chunk_rows=1 << 16):
         ops.require_gpu()
@@ -176,7 +167,7 @@ def calculate_CNR_SNR(case, image):
     return np.log10(SNRc), np.log10(abs(SNRc - SNRb)), Sc, Sb, Sc / Sb
 
 
-class ErdFitter:
+class ErdFitter(AdamOwner):
     """The two training phases of INR_ERD.py on the fused kernels.  The model's parameters become views of one flat buffer
     (kernel order, every tensor padded to 16 bytes); Adam state lives here.  The reference creates a fresh optimizer for each
     phase (INR_ERD.py:196, 252-255): ``pretrain`` always starts from a zeroed one -- its Adam runs over the perturb branch too,
@@ -199,47 +190,37 @@ class ErdFitter:
         self.make_model = make_model
         self.desc = model.desc()
         self.total, self.offsets, self.group_b = erd_param_layout(self.desc)
-        self.flat = None
-        self._workspace = None
+        self.params = FlatParams(self.total, itertools.chain.from_iterable(self.offsets))
+        self._workspace = Workspace()
         self._adopt()
-        self.reset_optimizer()
+        self.adam = AdamState(self.flat)
+
+    @property
+    def flat(self):
+        return self.params.flat
 
     def _adopt(self):
         params = self.model.kernel_parameters()
         if not params[0].is_cuda:
             raise ops.InrDeviceError("move the model to the HIP device first (model.cuda())")
-        flat = torch.zeros(self.total, dtype=torch.float32, device=params[0].device)
-        views = []
-        for t, (w_off, b_off) in enumerate(self.offsets):
-            for p, off in ((params[2 * t], w_off), (params[2 * t + 1], b_off)):
-                view = flat[off:off + p.numel()].view_as(p)
-                view.copy_(p.detach())
-                p.data = view
-                views.append(view)
-        self.flat, self._views = flat, views
+        self.params.adopt(params)
         self.model._fitter = self
 
     def owns(self, model):
-        return model is self.model and all(p.data_ptr() == v.data_ptr() for p, v in zip(model.kernel_parameters(), self._views))
+        return model is self.model and self.params.owns(model.kernel_parameters())
 
     def reset_optimizer(self):
-        self.grads = torch.zeros_like(self.flat)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.step_count = 0
+        self.adam.reset()
 
     def _ws(self, n):
         need = lib().inr_erd_workspace_bytes(C.byref(self.desc), int(n))
         if need == 0:
             check(-1, "inr_erd_workspace_bytes")
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.flat.device)
-        return self._workspace
+        return self._workspace.grow(need, self.flat.device)
 
     def _rows(self, coords):
         if not self.owns(self.model):
-            self._adopt()
+            self._adopt()                             # moved / reloaded: re-flatten (the optimizer state is kept)
         return ops._chk(coords.detach().reshape(-1, coords.shape[-1]).contiguous(), "coords")
 
     def pretrain_steps(self, x, t, max_steps, lr, threshold, status):
@@ -348,11 +329,7 @@ class ErdFitter:
 
     def split(self, flat):
         """Views of a flat vector per tensor, in ``kernel_parameters()`` order."""
-        out = []
-        for (w_off, b_off), i in zip(self.offsets, range(0, 2 * len(self.offsets), 2)):
-            out += [flat[w_off:w_off + self._views[i].numel()].view_as(self._views[i]),
-                    flat[b_off:b_off + self._views[i + 1].numel()].view_as(self._views[i + 1])]
-        return out
+        return self.params.split(flat)
 
     def mean_reconstruction(self, shape, n_acquisitions, eps=1.0 / 128.0):
         """INR_ERD.py:276-282: the mean over acquisitions of ``f(x; s, eps)`` on the grid ``shape`` (any size: the network

@@ -28,6 +28,7 @@ import torch
 from torch import nn
 
 from . import ops
+from .flat import AdamOwner, AdamState, FlatParams, Workspace, WorkspacePool
 from .ops import InrDeviceError  # noqa: F401  (re-exported)
 
 
@@ -229,49 +230,26 @@ class _TrainState:
         self.model = model
         self.desc = model.desc()
         self.total, self.offsets = ops.siren_param_layout(self.desc)
-        self.flat = None
-        self._views = []
-        self._free_ws = None          # a workspace no pending forward owns
+        self.params = FlatParams(self.total, itertools.chain.from_iterable(self.offsets))
+        self.pool = WorkspacePool()
         self._last = None             # ((workspace data_ptr, x data_ptr, x._version, n, strides), x) of the last forward: x kept alive
 
+    @property
+    def flat(self):
+        return self.params.flat
+
     def ensure(self):
-        params = self.model.layer_parameters()
-        if self.flat is not None and self.flat.device == params[0].device and \
-                all(p.data_ptr() == v.data_ptr() for p, v in zip(params, self._views)):
-            return
-        flat = torch.zeros(self.total, dtype=torch.float32, device=params[0].device)
-        views = []
-        for l, (w_off, b_off) in enumerate(self.offsets):
-            w, b = params[2 * l], params[2 * l + 1]
-            vw = flat[w_off:w_off + w.numel()].view_as(w)
-            vb = flat[b_off:b_off + b.numel()].view_as(b)
-            vw.copy_(w.detach())
-            vb.copy_(b.detach())
-            w.data, b.data = vw, vb
-            views += [vw, vb]
-        self.flat, self._views, self._last = flat, views, None
+        if self.params.ensure(self.model.layer_parameters()):      # moved (also to another device) or reloaded
+            self._last = None         # the C side's operand image was prepared from the buffer this one replaces
 
     def take_workspace(self, n, device):
-        need = ops.siren_fit_workspace_bytes(self.desc, n)
-        ws, self._free_ws = self._free_ws, None
-        if ws is None or ws.numel() < need or ws.device != device:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
+        ws, fresh = self.pool.take(ops.siren_fit_workspace_bytes(self.desc, n), device)
+        if fresh:
             # A NEW allocation may have been handed the address of a workspace a dropped graph freed (a forward without backward
             # never gives its workspace back): the address alone would then match `_last` -- and the C side's stamp for it -- while
             # other tensors have owned the memory in between.  The operand image is only trusted on a workspace this state kept.
             self._last = None
         return ws
-
-    def give_back(self, ws):
-        if self._free_ws is None or ws.numel() >= self._free_ws.numel():
-            self._free_ws = ws
-
-    def split_grads(self, flat_grads):
-        out = []
-        for l, (w_off, b_off) in enumerate(self.offsets):
-            w, b = self._views[2 * l], self._views[2 * l + 1]
-            out += [flat_grads[w_off:w_off + w.numel()].view_as(w), flat_grads[b_off:b_off + b.numel()].view_as(b)]
-        return out
 
 
 class _SirenHpFn(torch.autograd.Function):
@@ -306,9 +284,9 @@ class _SirenHpFn(torch.autograd.Function):
                                "mri_super_resolution_amd.inr.HP_AUTOGRAD = False (layer-by-layer exact-fp32 path)")
         grads = torch.empty(st.total, dtype=torch.float32, device=gy.device)      # fresh: .grad may alias what is returned here
         ops.siren_backward_train(st.desc, st.flat, grads, gy.contiguous(), ctx.ws)
-        st.give_back(ctx.ws)
+        st.pool.give_back(ctx.ws)
         ctx.ws = None
-        return (None, None, *st.split_grads(grads))
+        return (None, None, *st.params.split(grads))
 
 
 class Siren(nn.Module):
@@ -400,7 +378,7 @@ class Siren(nn.Module):
 # ---------------------------------------------------------------------------------------------------
 # a-8 fused fit loop, a-9 dense re-sampling
 # ---------------------------------------------------------------------------------------------------
-class SirenFitter:
+class SirenFitter(AdamOwner):
     """Fused replacement of the reference's per-step Python loop (superresDWI.py:132-138,
     superresHybrid.py:109-114; weighted form master.py:143-148): forward, MSE, backward and Adam of
     ``n_steps`` full-batch steps are enqueued by ONE call into ``inr_siren_fit``.
@@ -417,38 +395,27 @@ class SirenFitter:
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
         self.desc = model.desc()
         self.total, self.offsets = ops.siren_param_layout(self.desc)
-        self.step_count = 0
-        self.flat = None
-        self._workspace = None
+        self.params = FlatParams(self.total, itertools.chain.from_iterable(self.offsets))
+        self._workspace = Workspace()
         self._adopt()
+        self.adam = AdamState(self.flat)
+
+    @property
+    def flat(self):
+        return self.params.flat
 
     def _adopt(self):
         params = self.model.layer_parameters()
-        dev = params[0].device
         if not params[0].is_cuda:
             raise InrDeviceError("move the model to the HIP device first (model.cuda())")
-        flat = torch.zeros(self.total, dtype=torch.float32, device=dev)
-        views = []
-        for l, (w_off, b_off) in enumerate(self.offsets):
-            w, b = params[2 * l], params[2 * l + 1]
-            vw = flat[w_off:w_off + w.numel()].view_as(w)
-            vb = flat[b_off:b_off + b.numel()].view_as(b)
-            vw.copy_(w.detach())
-            vb.copy_(b.detach())
-            w.data, b.data = vw, vb
-            views += [vw, vb]
-        old = self.flat
-        self.flat = flat
-        self._views = views
-        if old is None:
-            self.grads = torch.zeros_like(flat)
-            self.m = torch.zeros_like(flat)
-            self.v = torch.zeros_like(flat)
+        self.params.adopt(params)
 
     def _check_views(self):
-        params = self.model.layer_parameters()
-        if any(p.data_ptr() != v.data_ptr() for p, v in zip(params, self._views)):
-            self._adopt()  # model was moved / reloaded: re-flatten (Adam state is kept)
+        if not self.params.owns(self.model.layer_parameters()):
+            self._adopt()  # model was moved / reloaded: re-flatten (Adam state and step count are kept)
+
+    def _ws(self, x):
+        return self._workspace.grow(ops.siren_fit_workspace_bytes(self.desc, x.shape[0]), x.device)
 
     def step(self, model_input, target, n_steps=1, weight=None):
         """Run ``n_steps`` fit steps; returns the per-step losses as a device tensor (no sync)."""
@@ -457,12 +424,8 @@ class SirenFitter:
         t = target.detach().reshape(-1).contiguous()
         w = None if weight is None else weight.detach().reshape(-1).contiguous()
         losses = torch.empty(max(int(n_steps), 1), dtype=torch.float32, device=x.device)
-        need = ops.siren_fit_workspace_bytes(self.desc, x.shape[0])
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
         ops.siren_fit(self.desc, self.flat, self.grads, self.m, self.v, x, t, w, self.step_count + 1, int(n_steps),
-                      self.lr, self.betas[0], self.betas[1], self.eps, losses, self._workspace)
+                      self.lr, self.betas[0], self.betas[1], self.eps, losses, self._ws(x))
         self.step_count += int(n_steps)
         return losses[:n_steps]
 
@@ -475,17 +438,13 @@ class SirenFitter:
         t = targets.detach().reshape(targets.shape[0], -1).contiguous()
         w = None if weights is None else weights.detach().reshape(weights.shape[0], -1).contiguous()
         losses = torch.empty(max(int(n_steps), 1), dtype=torch.float32, device=x.device)
-        need = ops.siren_fit_workspace_bytes(self.desc, x.shape[0])
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = None
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
         ops.siren_fit_cycle(self.desc, self.flat, self.grads, self.m, self.v, x, t, w, int(first_acq), self.step_count + 1,
-                            int(n_steps), self.lr, self.betas[0], self.betas[1], self.eps, losses, self._workspace)
+                            int(n_steps), self.lr, self.betas[0], self.betas[1], self.eps, losses, self._ws(x))
         self.step_count += int(n_steps)
         return losses[:n_steps]
 
     def release_workspace(self):
-        self._workspace = None
+        self._workspace.release()
 
 
 def fit_cycle_batch(fitters, model_input, targets, n_steps, weights=None, first_acqs=None):
@@ -524,15 +483,10 @@ def fit_cycle_batch(fitters, model_input, targets, n_steps, weights=None, first_
     w = None if weights is None else [None if wt is None else wt.detach().reshape(wt.shape[0], -1).contiguous()
                                       for wt in weights]
     losses = torch.empty(K, max(int(n_steps), 1), dtype=torch.float32, device=x.device)
-    need = ops.siren_fit_workspace_bytes(f0.desc, x.shape[0])
-    for f in fitters:
-        if f._workspace is None or f._workspace.numel() < need:
-            f._workspace = None
-            f._workspace = torch.empty(need, dtype=torch.uint8, device=x.device)
     ops.siren_fit_cycle_batch(f0.desc, [f.flat for f in fitters], [f.grads for f in fitters], [f.m for f in fitters],
                               [f.v for f in fitters], x, t, w, [0] * K if first_acqs is None else [int(a) for a in first_acqs],
                               f0.step_count + 1, int(n_steps), f0.lr, f0.betas[0], f0.betas[1], f0.eps,
-                              [losses[k] for k in range(K)], [f._workspace for f in fitters])
+                              [losses[k] for k in range(K)], [f._ws(x) for f in fitters])
     for f in fitters:
         f.step_count += int(n_steps)
     return losses[:, :n_steps]
@@ -602,11 +556,11 @@ class ShardedSirenFitter(SirenFitter):
         w = None if weight is None else weight.detach().reshape(-1).contiguous()
         losses = torch.empty(max(int(n_steps), 1), dtype=torch.float32, device=x.device)
         count_total = self.global_rows * self.desc.out_features
+        ws = self._ws(x)
         for it in range(int(n_steps)):
             # from the second step of this call on, x / target / weight are unchanged: keep their operand image and maxima
-            flags = (ops.REUSE_INPUT_IMAGE | ops.REUSE_TARGET_STATS) if (it > 0 and self._workspace is not None) else 0
-            self._workspace = ops.siren_loss_grad(self.desc, self.flat, self.grads, x, t, w, count_total, self._loss,
-                                                  self._workspace, flags)
+            flags = (ops.REUSE_INPUT_IMAGE | ops.REUSE_TARGET_STATS) if it > 0 else 0
+            ops.siren_loss_grad(self.desc, self.flat, self.grads, x, t, w, count_total, self._loss, ws, flags)
             self._all_reduce(self._gbuf)          # gradient + loss in one message
             self.step_count += 1
             ops.adam_step(self.flat, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
@@ -630,11 +584,12 @@ class ShardedSirenFitter(SirenFitter):
             raise ValueError("first_acq out of range")
         losses = torch.empty(max(int(n_steps), 1), dtype=torch.float32, device=x.device)
         count_total = self.global_rows * self.desc.out_features
+        ws = self._ws(x)
         for it in range(int(n_steps)):
             a = (int(first_acq) + it) % n_acq
-            flags = ops.REUSE_INPUT_IMAGE if (it > 0 and self._workspace is not None) else 0      # (the targets do change)
-            self._workspace = ops.siren_loss_grad(self.desc, self.flat, self.grads, x, t[a], None if w is None else w[a],
-                                                  count_total, self._loss, self._workspace, flags)
+            flags = ops.REUSE_INPUT_IMAGE if it > 0 else 0      # (the targets do change)
+            ops.siren_loss_grad(self.desc, self.flat, self.grads, x, t[a], None if w is None else w[a], count_total, self._loss,
+                                ws, flags)
             self._all_reduce(self._gbuf)
             self.step_count += 1
             ops.adam_step(self.flat, self.grads, self.m, self.v, self.step_count, self.lr, self.betas[0], self.betas[1],
@@ -650,11 +605,7 @@ def flat_parameters(model: Siren):
     params = model.layer_parameters()
     if not params[0].is_cuda:
         raise InrDeviceError("move the model to the HIP device first (model.cuda())")
-    flat = torch.zeros(total, dtype=torch.float32, device=params[0].device)
-    for l, (w_off, b_off) in enumerate(offsets):
-        flat[w_off:w_off + params[2 * l].numel()] = params[2 * l].detach().reshape(-1)
-        flat[b_off:b_off + params[2 * l + 1].numel()] = params[2 * l + 1].detach().reshape(-1)
-    return desc, flat
+    return desc, FlatParams(total, itertools.chain.from_iterable(offsets)).pack(params)
 
 
 def fit_siren(model: Siren, model_input, target, steps, lr=1e-4, weight=None, chunk=250, fitter=None):

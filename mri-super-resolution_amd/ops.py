@@ -54,6 +54,73 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def _nbytes(t) -> int:
+    return t.numel() * t.element_size()
+
+
+def _workspace(workspace, need, device, name="workspace", flags=None):
+    """The caller's workspace, or a new one where none came.  One that is too small is an error -- except with ``flags``
+    (an int: the REUSE_* entry points), where it is replaced like a missing one, which a REUSE flag forbids: the flag speaks
+    of what the previous call left in its workspace."""
+    if workspace is not None and _nbytes(workspace) >= need:
+        return workspace
+    if workspace is not None and flags is None:
+        raise ValueError(f"{name} too small")
+    if flags:
+        raise ValueError("REUSE_* flags need the workspace of the previous call")
+    return _ws(need, device)
+
+
+def _rows(x, in_features, name="x") -> int:
+    """``x`` is a device tensor [n, in_features]; returns n."""
+    _chk(x, name)
+    if x.dim() != 2 or x.shape[1] != in_features:
+        raise ValueError(f"{name} {tuple(x.shape)} must be [n,{in_features}]")
+    return x.shape[0]
+
+
+def _chk_losses(losses, n_steps, name="losses"):
+    if losses is not None:
+        _chk(losses, name)
+        if losses.numel() < n_steps:
+            raise ValueError(f"{name} buffer shorter than n_steps")
+
+
+def _layer_dims(x, W, b, xname="x"):
+    """(n, fin, fout) of ``x`` [n, fin], ``W`` [fout, fin] and the optional bias [fout]."""
+    _chk(x, xname)
+    _chk(W, "weight")
+    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1]:
+        raise ValueError(f"{xname} {tuple(x.shape)} / weight {tuple(W.shape)} mismatch")
+    if b is not None:
+        _chk(b, "bias", (W.shape[0],))
+    return x.shape[0], x.shape[1], W.shape[0]
+
+
+def _grid_rows(shape, row_begin: int = 0, n_rows=None):
+    """(shape as ints, its row count, the length of the row window from ``row_begin`` -- by default to the end)."""
+    shape = tuple(int(s) for s in shape)
+    total = 1
+    for s in shape:
+        total *= s
+    n_rows = total - row_begin if n_rows is None else int(n_rows)
+    if row_begin < 0 or n_rows < 0 or row_begin + n_rows > total:
+        raise ValueError("row range outside the grid")
+    return shape, total, n_rows
+
+
+def param_layout(count_fn, offsets_fn, desc, n_entries: int):
+    """Ask the library for a flat parameter layout: ``count_fn(desc)`` gives the total in floats (negative: refused),
+    ``offsets_fn(desc, offsets, n_entries)`` fills the ``n_entries`` float offsets and returns a status.  Returns
+    ``(total, [offsets])``; a refusal raises ``InrHipError``."""
+    total = count_fn(C.byref(desc))
+    if total < 0:
+        check(int(total), getattr(count_fn, "__name__", "param count"))
+    offs = (C.c_int64 * n_entries)()
+    check(offsets_fn(C.byref(desc), offs, n_entries), getattr(offsets_fn, "__name__", "param offsets"))
+    return int(total), [int(o) for o in offs]
+
+
 def make_desc(in_features, hidden_features, hidden_layers, out_features, first_omega=30.0, hidden_omega=30.0):
     return SirenDesc(int(in_features), int(hidden_features), int(hidden_layers), int(out_features),
                      float(first_omega), float(hidden_omega))
@@ -68,13 +135,7 @@ def device_caps(device: int = 0) -> dict:
 # ---- a-1 / a-3 ------------------------------------------------------------------------------------
 def mgrid(shape, row_begin: int = 0, n_rows: int | None = None) -> torch.Tensor:
     dev = require_gpu()
-    shape = tuple(int(s) for s in shape)
-    total = 1
-    for s in shape:
-        total *= s
-    n_rows = total - row_begin if n_rows is None else int(n_rows)
-    if row_begin < 0 or n_rows < 0 or row_begin + n_rows > total:
-        raise ValueError("row range outside the grid")
+    shape, _, n_rows = _grid_rows(shape, row_begin, n_rows)
     out = torch.empty((n_rows, len(shape)), dtype=torch.float32, device=dev)
     if n_rows == 0:
         return out
@@ -101,12 +162,7 @@ def grid_fourier_map(shape, B: torch.Tensor, row_begin: int = 0, n_rows: int | N
     shape = tuple(int(s) for s in shape)
     if B.dim() != 2 or B.shape[1] != len(shape):
         raise ValueError(f"B {tuple(B.shape)} must be [m,{len(shape)}]")
-    total = 1
-    for s in shape:
-        total *= s
-    n_rows = total - row_begin if n_rows is None else int(n_rows)
-    if row_begin < 0 or n_rows < 0 or row_begin + n_rows > total:
-        raise ValueError("row range outside the grid")
+    _, _, n_rows = _grid_rows(shape, row_begin, n_rows)
     m = B.shape[0]
     out = torch.empty((n_rows, 2 * m), dtype=torch.float32, device=B.device)
     if n_rows == 0:
@@ -118,14 +174,7 @@ def grid_fourier_map(shape, B: torch.Tensor, row_begin: int = 0, n_rows: int | N
 
 # ---- per-layer pieces (autograd path) -------------------------------------------------------------------
 def sine_layer_forward(x, W, b, omega: float, stash: bool):
-    _chk(x, "x")
-    _chk(W, "weight")
-    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1]:
-        raise ValueError(f"x {tuple(x.shape)} / weight {tuple(W.shape)} mismatch")
-    n, fin = x.shape
-    fout = W.shape[0]
-    if b is not None:
-        _chk(b, "bias", (fout,))
+    n, fin, fout = _layer_dims(x, W, b)
     act = torch.empty((n, fout), dtype=torch.float32, device=x.device)
     dact = torch.empty_like(act) if stash else None
     check(lib().inr_sine_layer_forward(act.data_ptr(), _ptr(dact), x.data_ptr(), W.data_ptr(), _ptr(b), n, fin, fout,
@@ -135,14 +184,7 @@ def sine_layer_forward(x, W, b, omega: float, stash: bool):
 
 def tanh_layer_forward(x, W, b, scale: float, stash: bool):
     """act = scale*tanh(x W^T + b) and (if ``stash``) its derivative factor scale*(1-tanh^2)."""
-    _chk(x, "x")
-    _chk(W, "weight")
-    if x.dim() != 2 or W.dim() != 2 or x.shape[1] != W.shape[1]:
-        raise ValueError(f"x {tuple(x.shape)} / weight {tuple(W.shape)} mismatch")
-    n, fin = x.shape
-    fout = W.shape[0]
-    if b is not None:
-        _chk(b, "bias", (fout,))
+    n, fin, fout = _layer_dims(x, W, b)
     act = torch.empty((n, fout), dtype=torch.float32, device=x.device)
     dact = torch.empty_like(act) if stash else None
     check(lib().inr_tanh_layer_forward(act.data_ptr(), _ptr(dact), x.data_ptr(), W.data_ptr(), _ptr(b), n, fin, fout,
@@ -152,14 +194,7 @@ def tanh_layer_forward(x, W, b, scale: float, stash: bool):
 
 def linear_tanh_head_forward(a, W, b, scale: float, stash: bool):
     """y = scale*tanh(a W^T + b) for a few output columns, and (if ``stash``) scale*(1-tanh^2)."""
-    _chk(a, "a")
-    _chk(W, "weight")
-    if a.dim() != 2 or W.dim() != 2 or a.shape[1] != W.shape[1]:
-        raise ValueError(f"a {tuple(a.shape)} / weight {tuple(W.shape)} mismatch")
-    n, hidden = a.shape
-    out_f = W.shape[0]
-    if b is not None:
-        _chk(b, "bias", (out_f,))
+    n, hidden, out_f = _layer_dims(a, W, b, "a")
     y = torch.empty((n, out_f), dtype=torch.float32, device=a.device)
     dy = torch.empty_like(y) if stash else None
     check(lib().inr_linear_tanh_head_forward(y.data_ptr(), _ptr(dy), a.data_ptr(), W.data_ptr(), _ptr(b), n, hidden,
@@ -191,14 +226,7 @@ def acquisition_products(raw_b0, raw_b1, raw_b2, raw_b3):
 
 
 def linear_head_forward(a, W, b, clamp_min=None):
-    _chk(a, "a")
-    _chk(W, "weight")
-    if a.dim() != 2 or W.dim() != 2 or a.shape[1] != W.shape[1]:
-        raise ValueError(f"a {tuple(a.shape)} / weight {tuple(W.shape)} mismatch")
-    n, hidden = a.shape
-    out_f = W.shape[0]
-    if b is not None:
-        _chk(b, "bias", (out_f,))
+    n, hidden, out_f = _layer_dims(a, W, b, "a")
     y = torch.empty((n, out_f), dtype=torch.float32, device=a.device)
     check(lib().inr_linear_head_forward(y.data_ptr(), a.data_ptr(), W.data_ptr(), _ptr(b), n, hidden, out_f,
                                         0 if clamp_min is None else 1, float(clamp_min or 0.0), _stream()),
@@ -301,24 +329,23 @@ def adam_step(p, g, m, v, step: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8
 # ---- fused SIREN -----------------------------------------------------------------------------------------
 def siren_param_layout(desc: SirenDesc):
     """(total_floats, [(w_off, b_off)] per layer in network order, head last)."""
-    total = lib().inr_siren_param_count(C.byref(desc))
-    if total < 0:
-        check(int(total), "inr_siren_param_count")
-    n_layers = desc.hidden_layers + 2
-    offs = (C.c_int64 * (2 * n_layers))()
-    check(lib().inr_siren_param_offsets(C.byref(desc), offs), "inr_siren_param_offsets")
-    return int(total), [(int(offs[2 * l]), int(offs[2 * l + 1])) for l in range(n_layers)]
+    total, offs = param_layout(lib().inr_siren_param_count, lambda d, o, n: lib().inr_siren_param_offsets(d, o), desc,
+                               2 * (desc.hidden_layers + 2))
+    return total, list(zip(offs[0::2], offs[1::2]))
+
+
+def _chk_flat(desc: SirenDesc, **tensors):
+    """Every named tensor is a device fp32 vector of the layout's total."""
+    total, _ = siren_param_layout(desc)
+    for name, t in tensors.items():
+        _chk(t, name)
+        if t.numel() != total:
+            raise ValueError(f"{name} has {t.numel()} floats, layout needs {total}")
 
 
 def siren_forward(desc: SirenDesc, params, x, clamp_min=None):
-    _chk(params, "params")
-    _chk(x, "x")
-    if x.dim() != 2 or x.shape[1] != desc.in_features:
-        raise ValueError(f"x {tuple(x.shape)} must be [n,{desc.in_features}]")
-    total, _ = siren_param_layout(desc)
-    if params.numel() != total:
-        raise ValueError(f"flat params has {params.numel()} floats, layout needs {total}")
-    n = x.shape[0]
+    _chk_flat(desc, params=params)
+    n = _rows(x, desc.in_features)
     y = torch.empty((n, desc.out_features), dtype=torch.float32, device=x.device)
     nbytes = lib().inr_siren_forward_workspace_bytes(C.byref(desc), n)
     ws = _ws(nbytes, x.device)
@@ -329,14 +356,8 @@ def siren_forward(desc: SirenDesc, params, x, clamp_min=None):
 
 
 def siren_reconstruct(desc: SirenDesc, params, shape, B=None, clamp_min=0.0, chunk_rows: int = 1 << 20):
-    _chk(params, "params")
-    shape = tuple(int(s) for s in shape)
-    total_rows = 1
-    for s in shape:
-        total_rows *= s
-    total, _ = siren_param_layout(desc)
-    if params.numel() != total:
-        raise ValueError(f"flat params has {params.numel()} floats, layout needs {total}")
+    _chk_flat(desc, params=params)
+    shape, total_rows, _ = _grid_rows(shape)
     m = 0
     if B is not None:
         _chk(B, "B")
@@ -360,22 +381,17 @@ def siren_jet(desc: SirenDesc, params, x=None, shape=None, B=None, d_tangent=Non
     """Value, coordinate gradient and Laplacian of a SIREN in forward mode (``inr_siren_jet`` on the rows ``x`` [n, d], or
     ``inr_siren_jet_grid`` on ``get_mgrid(shape)``; exactly one of the two).  Returns ``(y [n], grad [n, d_tangent] or None,
     lap [n] or None)``; derivatives are taken along the ``d_tangent`` leading axes (default: all ``d``)."""
-    _chk(params, "params")
     if (x is None) == (shape is None):
         raise ValueError("siren_jet takes exactly one of x and shape")
-    total, _ = siren_param_layout(desc)
-    if params.numel() != total:
-        raise ValueError(f"flat params has {params.numel()} floats, layout needs {total}")
+    _chk_flat(desc, params=params)
     if x is not None:
         _chk(x, "x")
         if x.dim() != 2:
             raise ValueError(f"x {tuple(x.shape)} must be [n, d]")
         n, d = int(x.shape[0]), int(x.shape[1])
     else:
-        shape = tuple(int(s) for s in shape)
-        d, n = len(shape), 1
-        for s in shape:
-            n *= s
+        shape, n, _ = _grid_rows(shape)
+        d = len(shape)
     m = 0
     if B is not None:
         _chk(B, "B")
@@ -406,15 +422,8 @@ def siren_fit_workspace_bytes(desc: SirenDesc, n: int) -> int:
 
 def siren_fit(desc: SirenDesc, params, grads, m, v, x, target, weight, first_step: int, n_steps: int, lr: float,
               beta1=0.9, beta2=0.999, eps=1e-8, losses=None, workspace=None):
-    total, _ = siren_param_layout(desc)
-    for name, t in (("params", params), ("grads", grads), ("m", m), ("v", v)):
-        _chk(t, name)
-        if t.numel() != total:
-            raise ValueError(f"{name} has {t.numel()} floats, layout needs {total}")
-    _chk(x, "x")
-    if x.dim() != 2 or x.shape[1] != desc.in_features:
-        raise ValueError(f"x {tuple(x.shape)} must be [n,{desc.in_features}]")
-    n = x.shape[0]
+    _chk_flat(desc, params=params, grads=grads, m=m, v=v)
+    n = _rows(x, desc.in_features)
     _chk(target, "target")
     if target.numel() != n * desc.out_features:
         raise ValueError("target must have n*out_features elements")
@@ -422,19 +431,12 @@ def siren_fit(desc: SirenDesc, params, grads, m, v, x, target, weight, first_ste
         _chk(weight, "weight")
         if weight.numel() != n * desc.out_features:
             raise ValueError("weight must have n*out_features elements")
-    if losses is not None:
-        _chk(losses, "losses")
-        if losses.numel() < n_steps:
-            raise ValueError("losses buffer shorter than n_steps")
-    need = siren_fit_workspace_bytes(desc, n)
-    if workspace is None:
-        workspace = _ws(need, x.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError("workspace too small")
+    _chk_losses(losses, n_steps)
+    workspace = _workspace(workspace, siren_fit_workspace_bytes(desc, n), x.device)
     check(lib().inr_siren_fit(C.byref(desc), params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(),
                               x.data_ptr(), target.data_ptr(), _ptr(weight), n, int(first_step), int(n_steps),
                               float(lr), float(beta1), float(beta2), float(eps), _ptr(losses), workspace.data_ptr(),
-                              workspace.numel() * workspace.element_size(), _stream()), "inr_siren_fit")
+                              _nbytes(workspace), _stream()), "inr_siren_fit")
     return workspace
 
 
@@ -442,15 +444,8 @@ def siren_fit_cycle(desc: SirenDesc, params, grads, m, v, x, targets, weights, f
                     n_steps: int, lr: float, beta1=0.9, beta2=0.999, eps=1e-8, losses=None, workspace=None):
     """``inr_siren_fit_cycle``: ``targets`` (and ``weights``) are [n_acq, n * out_features]; step ``it`` fits acquisition
     ``(first_acq + it) % n_acq`` (master.py:137-148)."""
-    total, _ = siren_param_layout(desc)
-    for name, t in (("params", params), ("grads", grads), ("m", m), ("v", v)):
-        _chk(t, name)
-        if t.numel() != total:
-            raise ValueError(f"{name} has {t.numel()} floats, layout needs {total}")
-    _chk(x, "x")
-    if x.dim() != 2 or x.shape[1] != desc.in_features:
-        raise ValueError(f"x {tuple(x.shape)} must be [n,{desc.in_features}]")
-    n = x.shape[0]
+    _chk_flat(desc, params=params, grads=grads, m=m, v=v)
+    n = _rows(x, desc.in_features)
     _chk(targets, "targets")
     if targets.dim() != 2 or targets.shape[1] != n * desc.out_features:
         raise ValueError("targets must be [n_acq, n*out_features]")
@@ -461,19 +456,12 @@ def siren_fit_cycle(desc: SirenDesc, params, grads, m, v, x, targets, weights, f
             raise ValueError("weights must have the shape of targets")
     if not 0 <= int(first_acq) < n_acq:
         raise ValueError("first_acq out of range")
-    if losses is not None:
-        _chk(losses, "losses")
-        if losses.numel() < n_steps:
-            raise ValueError("losses buffer shorter than n_steps")
-    need = siren_fit_workspace_bytes(desc, n)
-    if workspace is None:
-        workspace = _ws(need, x.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError("workspace too small")
+    _chk_losses(losses, n_steps)
+    workspace = _workspace(workspace, siren_fit_workspace_bytes(desc, n), x.device)
     check(lib().inr_siren_fit_cycle(C.byref(desc), params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(),
                                     x.data_ptr(), targets.data_ptr(), _ptr(weights), int(n_acq), int(first_acq), n,
                                     int(first_step), int(n_steps), float(lr), float(beta1), float(beta2), float(eps),
-                                    _ptr(losses), workspace.data_ptr(), workspace.numel() * workspace.element_size(),
+                                    _ptr(losses), workspace.data_ptr(), _nbytes(workspace),
                                     _stream()), "inr_siren_fit_cycle")
     return workspace
 
@@ -493,18 +481,11 @@ def siren_fit_cycle_batch(desc: SirenDesc, params, grads, m, v, x, targets, weig
     for name, lst in (("weights", weights), ("losses", losses), ("workspaces", workspaces)):
         if lst is not None and len(lst) != K:
             raise ValueError(f"{name} has {len(lst)} entries, params {K}")
-    total, _ = siren_param_layout(desc)
     for k in range(K):
-        for name, t in (("params", params[k]), ("grads", grads[k]), ("m", m[k]), ("v", v[k])):
-            _chk(t, f"{name}[{k}]")
-            if t.numel() != total:
-                raise ValueError(f"{name}[{k}] has {t.numel()} floats, layout needs {total}")
+        _chk_flat(desc, **{f"params[{k}]": params[k], f"grads[{k}]": grads[k], f"m[{k}]": m[k], f"v[{k}]": v[k]})
     if len({t.data_ptr() for t in params}) != K:
         raise ValueError("two fits share one params buffer")
-    _chk(x, "x")
-    if x.dim() != 2 or x.shape[1] != desc.in_features:
-        raise ValueError(f"x {tuple(x.shape)} must be [n,{desc.in_features}]")
-    n = x.shape[0]
+    n = _rows(x, desc.in_features)
     n_acq = []
     for k in range(K):
         _chk(targets[k], f"targets[{k}]")
@@ -517,20 +498,14 @@ def siren_fit_cycle_batch(desc: SirenDesc, params, grads, m, v, x, targets, weig
                 raise ValueError(f"weights[{k}] must have the shape of targets[{k}]")
         if not 0 <= int(first_acqs[k]) < n_acq[k]:
             raise ValueError(f"first_acqs[{k}] out of range")
-        if losses is not None and losses[k] is not None:
-            _chk(losses[k], f"losses[{k}]")
-            if losses[k].numel() < n_steps:
-                raise ValueError(f"losses[{k}] shorter than n_steps")
+        if losses is not None:
+            _chk_losses(losses[k], n_steps, f"losses[{k}]")
     need = siren_fit_workspace_bytes(desc, n)
-    workspaces = list(workspaces) if workspaces is not None else [None] * K
-    for k in range(K):
-        if workspaces[k] is None:
-            workspaces[k] = _ws(need, x.device)
-        elif workspaces[k].numel() * workspaces[k].element_size() < need:
-            raise ValueError(f"workspaces[{k}] too small")
+    workspaces = [_workspace(w, need, x.device, f"workspaces[{k}]")
+                  for k, w in enumerate(workspaces if workspaces is not None else [None] * K)]
     if len({w.data_ptr() for w in workspaces}) != K:
         raise ValueError("two fits share one workspace")
-    ws_bytes = min(w.numel() * w.element_size() for w in workspaces)
+    ws_bytes = min(_nbytes(w) for w in workspaces)
 
     def ptrs(lst):
         return (C.c_void_p * K)(*[None if t is None else t.data_ptr() for t in lst])
@@ -549,27 +524,18 @@ REUSE_INPUT_IMAGE, REUSE_TARGET_STATS = 1, 2        # INR_REUSE_* of include/inr
 def siren_loss_grad(desc: SirenDesc, params, grads, x, target, weight, count_total: int, loss, workspace=None, flags: int = 0):
     """Forward + loss + backward of one row shard (no optimizer); see ``inr_siren_loss_grad`` / ``_ex`` (``flags``: the
     caller vouches that x / the targets are those of the previous call on this workspace)."""
-    total, _ = siren_param_layout(desc)
-    for name, t in (("params", params), ("grads", grads)):
-        _chk(t, name)
-        if t.numel() != total:
-            raise ValueError(f"{name} has {t.numel()} floats, layout needs {total}")
-    _chk(x, "x")
+    _chk_flat(desc, params=params, grads=grads)
+    n = _rows(x, desc.in_features)
     _chk(target, "target")
     _chk(loss, "loss")
-    n = x.shape[0]
-    if x.dim() != 2 or x.shape[1] != desc.in_features or target.numel() != n * desc.out_features:
-        raise ValueError("x / target shape mismatch")
+    if target.numel() != n * desc.out_features:
+        raise ValueError("target must have n*out_features elements")
     if weight is not None:
         _chk(weight, "weight")
-    need = siren_fit_workspace_bytes(desc, n)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        if flags:
-            raise ValueError("REUSE_* flags need the workspace of the previous call")
-        workspace = _ws(need, x.device)
+    workspace = _workspace(workspace, siren_fit_workspace_bytes(desc, n), x.device, flags=int(flags))
     check(lib().inr_siren_loss_grad_ex(C.byref(desc), params.data_ptr(), grads.data_ptr(), x.data_ptr(), target.data_ptr(),
                                        _ptr(weight), n, int(count_total), loss.data_ptr(), workspace.data_ptr(),
-                                       workspace.numel() * workspace.element_size(), int(flags), _stream()),
+                                       _nbytes(workspace), int(flags), _stream()),
           "inr_siren_loss_grad_ex")
     return workspace
 
@@ -582,20 +548,12 @@ def siren_hp_eligible(desc: SirenDesc) -> bool:
 def siren_forward_train(desc: SirenDesc, params, x, workspace=None, flags: int = 0):
     """``inr_siren_forward_train``: y = network(x), every layer's stash left in ``workspace`` for ``siren_backward_train``.
     Returns (y [n, 1], workspace)."""
-    total, _ = siren_param_layout(desc)
-    _chk(params, "params")
-    _chk(x, "x")
-    if params.numel() != total or x.dim() != 2 or x.shape[1] != desc.in_features:
-        raise ValueError("params / x shape mismatch")
-    n = x.shape[0]
-    need = siren_fit_workspace_bytes(desc, n)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        if flags:
-            raise ValueError("REUSE_* flags need the workspace of the previous call")
-        workspace = _ws(need, x.device)
+    _chk_flat(desc, params=params)
+    n = _rows(x, desc.in_features)
+    workspace = _workspace(workspace, siren_fit_workspace_bytes(desc, n), x.device, flags=int(flags))
     y = torch.empty(n, desc.out_features, dtype=torch.float32, device=x.device)
     check(lib().inr_siren_forward_train(C.byref(desc), params.data_ptr(), x.data_ptr(), y.data_ptr(), n, workspace.data_ptr(),
-                                        workspace.numel() * workspace.element_size(), int(flags), _stream()),
+                                        _nbytes(workspace), int(flags), _stream()),
           "inr_siren_forward_train")
     return y, workspace
 
@@ -607,7 +565,7 @@ def siren_backward_train(desc: SirenDesc, params, grads, gy, workspace):
     _chk(gy, "gy")
     n = gy.numel() // desc.out_features
     check(lib().inr_siren_backward_train(C.byref(desc), params.data_ptr(), grads.data_ptr(), gy.data_ptr(), n,
-                                         workspace.data_ptr(), workspace.numel() * workspace.element_size(), _stream()),
+                                         workspace.data_ptr(), _nbytes(workspace), _stream()),
           "inr_siren_backward_train")
     return grads
 

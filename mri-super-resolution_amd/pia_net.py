@@ -23,6 +23,7 @@ from torch.nn import functional as F
 
 from . import ops
 from ._lib import PiaDesc, check, lib
+from .flat import AdamOwner, AdamState, FlatParams, Workspace, WorkspacePool
 
 
 def _as_desc(model) -> PiaDesc:
@@ -57,13 +58,8 @@ def _as_desc(model) -> PiaDesc:
 
 def pia_param_layout(desc: PiaDesc):
     """(total, offsets) of the flat parameter buffer: the tensors of ``named_parameters()`` back to back, unpadded."""
-    total = lib().inr_pia_param_count(C.byref(desc))
-    if total < 0:
-        check(-1, "inr_pia_param_count")
-    n = 2 * desc.n_hidden + 3 * (2 * desc.predictor_depth + 2)
-    offs = (C.c_int64 * n)()
-    check(lib().inr_pia_param_offsets(C.byref(desc), offs, n), "inr_pia_param_offsets")
-    return int(total), [int(o) for o in offs]
+    return ops.param_layout(lib().inr_pia_param_count, lib().inr_pia_param_offsets, desc,
+                            2 * desc.n_hidden + 3 * (2 * desc.predictor_depth + 2))
 
 
 class _PiaState:
@@ -72,42 +68,34 @@ class _PiaState:
     def __init__(self, model):
         self.model = model
         self.desc = None
-        self.flat = None
-        self._views = []
-        self._free_ws = None
+        self.params = FlatParams(0, [])               # owns nothing: the first ensure() replaces it
+        self.pool = WorkspacePool()
+
+    @property
+    def flat(self):
+        return self.params.flat
 
     def ensure(self):
         params = list(self.model.parameters())
-        if self.flat is not None and self.flat.device == params[0].device and \
-                all(p.data_ptr() == v.data_ptr() for p, v in zip(params, self._views)):
+        if self.params.owns(params):
             return
-        self.desc = _as_desc(self.model)
-        total, offsets = pia_param_layout(self.desc)
-        assert len(offsets) == len(params) and total == sum(p.numel() for p in params)
-        flat = torch.empty(total, dtype=torch.float32, device=params[0].device)
-        views = []
-        for p, off in zip(params, offsets):
-            view = flat[off:off + p.numel()].view_as(p)
-            view.copy_(p.detach())
-            p.data = view
-            views.append(view)
-        self.flat, self._views, self.offsets = flat, views, offsets
+        self.desc = _as_desc(self.model)              # re-adoption reads the model's tables again
+        total, self.offsets = pia_param_layout(self.desc)
+        assert len(self.offsets) == len(params) and total == sum(p.numel() for p in params)
+        self.params = FlatParams(total, self.offsets)
+        self.params.adopt(params, zero=False)         # (the layout has no padding)
 
     def split(self, flat):
-        return [flat[off:off + v.numel()].view_as(v) for off, v in zip(self.offsets, self._views)]
+        return self.params.split(flat)
 
     def workspace(self, n, training, device):
         need = lib().inr_pia_workspace_bytes(C.byref(self.desc), int(n), int(training))
         if need == 0:
             check(-1, "inr_pia_workspace_bytes")
-        ws, self._free_ws = self._free_ws, None
-        if ws is None or ws.numel() < need or ws.device != device:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return ws
+        return self.pool.take(need, device)[0]
 
     def give_back(self, ws):
-        if self._free_ws is None or ws.numel() >= self._free_ws.numel():
-            self._free_ws = ws
+        self.pool.give_back(ws)
 
 
 def _outputs(n, dev):
@@ -266,7 +254,7 @@ def pia_forward(state: _PiaState, x: torch.Tensor, chunk_rows: int = 32768, devi
     return (signal if want_signal else None), D, T2, v
 
 
-class PiaFitter:
+class PiaFitter(AdamOwner):
     """The fused training step of a ``PIA`` (``inr_pia_fit_step``): forward, ``mean(pids * (signal - x) ** 2)``, backward,
     fixed-order gradient reduction and Adam in one enqueue, the loss left on the device."""
 
@@ -278,10 +266,10 @@ class PiaFitter:
         self.state = model._state
         self.state.ensure()
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
-        flat = self.state.flat
-        self.grads, self.m, self.v = torch.zeros_like(flat), torch.zeros_like(flat), torch.zeros_like(flat)
-        self.steps_done = 0
-        self._ws = None
+        self.adam = AdamState(self.state.flat)
+        self._ws = Workspace()
+
+    steps_done = AdamOwner.step_count
 
     def step(self, x: torch.Tensor, pids: torch.Tensor = None) -> torch.Tensor:
         """One step on the batch ``x`` [n, 16] (weights ``pids`` [n, 16], default 1).  Returns the loss before the update as a
@@ -297,14 +285,13 @@ class PiaFitter:
         need = lib().inr_pia_workspace_bytes(C.byref(st.desc), n, 1)
         if need == 0:
             check(-1, "inr_pia_workspace_bytes")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        ws = self._ws.grow(need, x.device)
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         self.steps_done += 1
         check(lib().inr_pia_fit_step(C.byref(st.desc), st.flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
                                      self.v.data_ptr(), x.data_ptr(), ops._ptr(pids), n, self.steps_done, self.lr, self.betas[0],
-                                     self.betas[1], self.eps, loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
-                                     ops._stream()), "inr_pia_fit_step")
+                                     self.betas[1], self.eps, loss.data_ptr(), ws.data_ptr(), ws.numel(), ops._stream()),
+              "inr_pia_fit_step")
         return loss
 
     def encode_volume(self, signals, chunk_rows: int = 32768):

@@ -20,6 +20,7 @@ import torch
 
 from . import ops
 from ._lib import RamsDesc, check, lib
+from .flat import AdamOwner, AdamState, Workspace
 
 MEAN = 7433.6436   # network.py:18
 STD = 2353.0723    # network.py:19
@@ -402,7 +403,7 @@ def conv3d_wgrad(x, dy, pad=1):
 
 
 # ---- the training step (utils/training.py:193-209) --------------------------------------------------------------------------
-class RamsTrainer:
+class RamsTrainer(AdamOwner):
     """``Trainer.train_step`` of the reference (utils/training.py:193-209) on the device: forward with every intermediate
     kept -> per-image cL1 (utils/loss.py:26-75) -> gradients of ``sum_b loss_b`` (what ``tape.gradient`` of the loss vector
     is) with respect to every ``v``, ``g`` and bias -> Adam in Keras' form.  One C call per step (``inr_rams_train_step``).
@@ -415,26 +416,25 @@ class RamsTrainer:
         dev = ops.require_gpu()
         self.model = model
         self.lr, self.b1, self.b2, self.eps = float(learning_rate), float(beta_1), float(beta_2), float(epsilon)
-        total = lib().inr_rams_train_param_count(C.byref(model.desc))
-        if total < 0:
-            check(int(total), "inr_rams_train_param_count")
-        offs = (C.c_int64 * (3 * 128))()
-        n = lib().inr_rams_train_param_offsets(C.byref(model.desc), offs, 128)
-        if n != len(model.specs):
-            raise RuntimeError(f"library reports {n} layers, the model has {len(model.specs)}")
-        self.offsets = [(int(offs[3 * i]), int(offs[3 * i + 1]), int(offs[3 * i + 2])) for i in range(n)]
-        flat = np.zeros(int(total), np.float32)
+        n = len(model.specs)
+
+        def offsets_fn(desc, offs, n_entries):        # (this one returns the layer count, or a negative status)
+            got = lib().inr_rams_train_param_offsets(desc, offs, n_entries // 3)
+            if got >= 0 and got != n:
+                raise RuntimeError(f"library reports {got} layers, the model has {n}")
+            return min(got, 0)
+
+        total, offs = ops.param_layout(lib().inr_rams_train_param_count, offsets_fn, model.desc, 3 * n)
+        self.offsets = list(zip(offs[0::3], offs[1::3], offs[2::3]))
+        flat = np.zeros(total, np.float32)
         for (name, ks, cin, cout), (ov, og, ob) in zip(model.specs, self.offsets):
             v = np.asarray(model.params[f"{name}/v"], np.float32).reshape(-1)
             flat[ov:ov + v.size] = v
             flat[og:og + cout] = model.params[f"{name}/g"]
             flat[ob:ob + cout] = model.params[f"{name}/b"]
         self.flat = torch.from_numpy(flat).to(dev)
-        self.grads = torch.zeros_like(self.flat)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self.step_count = 0
-        self._ws = None
+        self.adam = AdamState(self.flat)
+        self._workspace = Workspace()
 
     def _prep(self, lr_batch, hr, mask):
         dev = self.flat.device
@@ -454,31 +454,28 @@ class RamsTrainer:
         need = lib().inr_rams_train_workspace_bytes(C.byref(self.model.desc), B, H, W)
         if need == 0:
             check(-1, "inr_rams_train_workspace_bytes")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return x, yt, mk, B, H, W
+        return x, yt, mk, B, H, W, self._workspace.grow(need, dev)
 
     def loss_and_grads(self, lr_batch, hr, mask, want_prediction=False):
         """Per-image loss [B] (float64) and ``d sum(loss) / d parameters`` (left in ``self.grads``); no update."""
-        x, yt, mk, B, H, W = self._prep(lr_batch, hr, mask)
+        x, yt, mk, B, H, W, ws = self._prep(lr_batch, hr, mask)
         s = self.model.cfg["scale"]
         loss = torch.empty(B, dtype=torch.float64, device=x.device)
         pred = torch.empty((B, H * s, W * s), dtype=torch.float32, device=x.device) if want_prediction else None
         check(lib().inr_rams_train_grads(C.byref(self.model.desc), self.flat.data_ptr(), self.grads.data_ptr(), x.data_ptr(),
                                          yt.data_ptr(), mk.data_ptr(), loss.data_ptr(), 0 if pred is None else pred.data_ptr(),
-                                         B, H, W, self._ws.data_ptr(), self._ws.numel(), ops._stream()), "inr_rams_train_grads")
+                                         B, H, W, ws.data_ptr(), ws.numel(), ops._stream()), "inr_rams_train_grads")
         return (loss, pred) if want_prediction else loss
 
     def train_step(self, lr_batch, hr, mask):
         """One optimizer step; returns the per-image loss vector the reference feeds to ``train_loss`` (training.py:207)."""
-        x, yt, mk, B, H, W = self._prep(lr_batch, hr, mask)
+        x, yt, mk, B, H, W, ws = self._prep(lr_batch, hr, mask)
         loss = torch.empty(B, dtype=torch.float64, device=x.device)
         self.step_count += 1
         check(lib().inr_rams_train_step(C.byref(self.model.desc), self.flat.data_ptr(), self.grads.data_ptr(), self.m.data_ptr(),
                                         self.v.data_ptr(), x.data_ptr(), yt.data_ptr(), mk.data_ptr(), loss.data_ptr(), B, H, W,
-                                        self.step_count, self.lr, self.b1, self.b2, self.eps, self._ws.data_ptr(),
-                                        self._ws.numel(), ops._stream()), "inr_rams_train_step")
+                                        self.step_count, self.lr, self.b1, self.b2, self.eps, ws.data_ptr(), ws.numel(),
+                                        ops._stream()), "inr_rams_train_step")
         self.model.invalidate()
         return loss
 
