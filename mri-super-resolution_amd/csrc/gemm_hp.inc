@@ -1,6 +1,6 @@
 // Pre-split fp16 MFMA GEMM ("hp"): the split-fp16 arithmetic of gemm_h3.inc with every operand ALREADY split in HBM, staged
 // global -> LDS by buffer_load ... lds (no staging registers, no split VALU, no ds_write in the K-loop).  Included by
-// gemm_f32.hip.
+// gemm_hp.hip; the format's helpers are in split_fp16.h.
 //
 // HL32 storage of a matrix X[R][C] (C % 32 == 0): row r, 32-column block kb occupies the 128 bytes at
 // (r * C/32 + kb) * 128: halves hi(X[r][32kb .. 32kb+31]) then lo(...), hi = fp16(x * s) rounded to nearest,
@@ -84,10 +84,7 @@ __device__ __forceinline__ int hp_scale_exp(const HpScale& s) {
     if (!s.wn) return h3_scale_exp(__float_as_uint(b));   // inputs, weights: |k| <= 100 (their 2^k multiplies the bias fold)
     // gradients (bound = measured maximum x weight norm): the whole normal range -- a dz of 1e-32 three layers below a head
     // with 1e-23 weights kept 10 bits under the +-100 clamp (tests/test_gpu_hp_variants.py: weight magnitudes)
-    const int e = (int)((__float_as_uint(b) >> 23) & 0xff);
-    if (e == 0 || e == 255) return 0;
-    const int k = 14 - (e - 127);
-    return k > s.kmax ? s.kmax : (k < -126 ? -126 : k);
+    return h3_scale_exp(__float_as_uint(b), s.kmax, -126);
 }
 
 // atomic max on the float bits of a non-negative value, skipped when the slot already holds at least as much.  The slot only

@@ -1,5 +1,5 @@
 // Cross-layer fused forward of a whole SIREN on pre-split (HL32) operands -- the inference / dense re-sampling path
-// (inr_siren_forward, inr_siren_reconstruct: superresDWI.py:125-126,161-162).  Included by gemm_f32.hip behind gemm_hp.inc.
+// (inr_siren_forward, inr_siren_reconstruct: superresDWI.py:125-126,161-162).  Included by gemm_hp.hip behind gemm_hp.inc.
 //
 // The layer-wise forward writes every activation matrix to HBM and reads it back for the next layer: at hidden = 512 that is
 // 4 KB per row and layer in, 4 KB out -- ~19 KB per voxel over Siren(256,512,3,1), 2.7 TB/s at the 142 M voxels/s it reached,

@@ -1,17 +1,14 @@
 // Narrow-tile form of the pre-split (HL32) K-contiguous GEMM: 64 x 128 output tiles, four waves (2 x 2, each 32 x 64), one
-// block per tile and per CU, a SIX-stage operand ring.  Included by gemm_f32.hip behind gemm_hp.inc (same operand format, same LDS images, same
+// block per tile and per CU, a SIX-stage operand ring.  Included by gemm_hp.hip behind gemm_hp.inc (same operand format, same LDS images, same
 // three-product arithmetic, same epilogues).
 //
 // Why it exists.  The 128 x 256 tiles of gemm_hp_pkd / pkc are what the big fits want (one 8-wave block per CU, 48 MFMAs per
-// wave and K-tile), but a launch needs 256 of them to touch every CU once:
-//   * a fit of a few thousand rows (BASELINE config 1: 4,096 rows x 512 columns = 64 wide tiles) ran on a quarter of the chip:
-//     20-28 us per GEMM where the work is worth 2.5 us of the machine (profiles/r03_small_n.txt);
-//   * a launch whose tile count is a little above a multiple of 256 pays a whole extra round for the remainder (a 69,632-row
-//     shard: 4.25 rounds of tiles, 5 rounds of time).
-// Here a tile is a quarter of the wide one: 4,096 x 512 gives 256 tiles, and the remainder rows of a big launch are cut into
-// four times as many pieces (hp_sine_forward / hp_input_grad hand the rows behind the last full round of wide tiles to this
-// kernel).  Per FLOP it is the less efficient shape -- 12 fragment reads per 24 MFMAs instead of 16 per 48, one wave per SIMD
-// and block -- which is why it only takes what the wide kernels cannot fill.
+// wave and K-tile), but a launch needs 256 of them to touch every CU once: a fit of a few thousand rows (BASELINE config 1:
+// 4,096 rows x 512 columns = 64 wide tiles) ran on a quarter of the chip, 20-28 us per GEMM where the work is worth 2.5 us of
+// the machine (profiles/r03_small_n.txt).  Here a tile is a quarter of the wide one: 4,096 x 512 gives 256 tiles.  Per FLOP it
+// is the less efficient shape -- 12 fragment reads per 24 MFMAs instead of 16 per 48, one wave per SIMD and block -- which is
+// why it takes a launch only as a WHOLE, and only one whose wide tiles would leave a quarter of the CUs idle (hp_kc_choice in
+// gemm_hp.hip; handing it the remainder rows of a large launch was measured and dropped, see there).
 //
 // LDS: stage = A image 64 rows x 128 B (8 KB) + B image 128 rows x 128 B (16 KB); six stages = 144 KB, reused as the
 // epilogue staging area (4 waves x 32 rows x 68 floats).  DMA: 24 one-KB transfers per stage, six per wave (two A, four B).

@@ -8,7 +8,7 @@
 namespace inr {
 
 // ---- gemm_f32.hip: fp32 MFMA and split-fp16 (gemm_h3.inc) GEMMs -------------------------------------------------------------------
-int gemm_build_flags();
+int gemm_build_flags();   // inr_build_flags: this unit's diagnostic macros | hp_build_flags()
 int gemm_sine_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n,
                       int in_f, int out_f, float omega, hipStream_t stream, const H3Args* h3 = nullptr);
 int gemm_tanh_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n, int in_f,
@@ -28,10 +28,10 @@ extern tune_int g_mfma16;          // key 1
 extern tune_int g_h3;              // key 3
 extern tune_int g_h3_wide;         // key 6
 extern char* g_h3_scratch;         // inr_debug_set_ptr(1, .)
-extern unsigned long long* g_stamps;          // inr_debug_set_ptr(0, .): diagnostic builds only
-extern tune_int g_stamp_class, g_stamp_nth;   // keys 8, 9
+extern unsigned long long* g_stamps;          // inr_debug_set_ptr(0, .): diagnostic builds only (every unit with stamped kernels reads it)
 
-// ---- gemm_f32.hip: pre-split (HL32) path, gemm_hp*.inc ------------------------------------------------------------------------------
+// ---- gemm_hp.hip: the pre-split (HL32) GEMM family, gemm_hp*.inc ---------------------------------------------------------------------
+int hp_build_flags();
 bool hp_head_ok(int hidden);
 size_t hp_prep_part_bytes();
 int hp_weight_prep(const float* const* W, const int* out_f, const int* in_f, int layers, char* planes, HpSlots slots,
@@ -75,6 +75,7 @@ int hp_head_step(char* dz_hl, float* slab_b, float* slab_w, float* part_loss, fl
                  const float* dact, const float* W, const float* bias, const float* t, const float* wgt, int64_t n, int hidden,
                  int64_t count_total, unsigned* amax_out, HpScale so, hipStream_t stream, bool from_z = false,
                  float omega = 0.f, const float* g_ext = nullptr, HpScale sa = HpScale{});
+extern tune_int g_stamp_class, g_stamp_nth;       // keys 8, 9: which hp launch receives g_stamps
 extern tune_int g_hp_persistent, g_hp_stagger;   // keys 10, 11
 extern tune_int g_hp_zhead;                       // key 16
 extern tune_int g_hp_narrow;                      // key 18

@@ -15,6 +15,7 @@
 // Weight normalisation (tfa WeightNormalization, g*v/||v||) is folded into the kernels when the parameters are
 // packed (host side, once per model) -- the packed layouts are documented in include/inrhip.h.
 #include "internal.h"
+#include "split_fp16.h"
 
 namespace inr {
 

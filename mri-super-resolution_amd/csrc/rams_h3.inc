@@ -15,38 +15,20 @@
 #ifndef R3_ABLATE
 #define R3_ABLATE 0      // diagnostic builds: 1 = no operand split, 2 = no MFMAs, 4 = no global operand loads (wrong results)
 #endif
-typedef _Float16 r3_half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 r3_half2 __attribute__((ext_vector_type(2)));
-
 constexpr int R3_PLANE_HALVES = 27 * RC * RC;            // one plane (hi or lo) of a folded kernel
 constexpr int R3_LAYER_HALVES = 2 * R3_PLANE_HALVES;
 
-// power-of-two exponent that brings max|.| (float bits) to [2^14, 2^15); 0 for empty / zero / non-finite tensors
-__device__ __forceinline__ int r3_scale_exp(unsigned amax_bits) {
-    const int e = (int)((amax_bits >> 23) & 0xff);
-    if (e == 0 || e == 255) return 0;
-    const int k = 14 - (e - 127);
-    return k > 100 ? 100 : (k < -100 ? -100 : k);
-}
-__device__ __forceinline__ float r3_pow2(int k) { return __uint_as_float((unsigned)(127 + k) << 23); }
-
-// both halves rounded to nearest (v_cvt_pk_f16_f32): hi + lo = x s to 2^-24 (see h3_split2 in gemm_h3.inc)
-typedef float r3_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void r3_split2(float v0, float v1, float s, r3_half2& hi, r3_half2& lo) {
-    hi = __builtin_convertvector(r3_f32x2{v0 * s, v1 * s}, r3_half2);
-    const float r0 = __builtin_fmaf(v0, s, -(float)hi[0]), r1 = __builtin_fmaf(v1, s, -(float)hi[1]);
-    lo = __builtin_convertvector(r3_f32x2{r0, r1}, r3_half2);
-}
+// (the format -- h3_scale_exp, h3_pow2, h3_split2 -- is split_fp16.h's, shared with the GEMMs)
 
 // eight consecutive channels (two 16-byte loads) -> one hi and one lo MFMA operand
-__device__ __forceinline__ void r3_split8(const f32x4& x0, const f32x4& x1, float s, r3_half8& hi, r3_half8& lo) {
-    r3_half2 h[4], l[4];
-    r3_split2(x0[0], x0[1], s, h[0], l[0]);
-    r3_split2(x0[2], x0[3], s, h[1], l[1]);
-    r3_split2(x1[0], x1[1], s, h[2], l[2]);
-    r3_split2(x1[2], x1[3], s, h[3], l[3]);
-    hi = r3_half8{h[0][0], h[0][1], h[1][0], h[1][1], h[2][0], h[2][1], h[3][0], h[3][1]};
-    lo = r3_half8{l[0][0], l[0][1], l[1][0], l[1][1], l[2][0], l[2][1], l[3][0], l[3][1]};
+__device__ __forceinline__ void r3_split8(const f32x4& x0, const f32x4& x1, float s, half8& hi, half8& lo) {
+    half2v h[4], l[4];
+    h3_split2(x0[0], x0[1], s, h[0], l[0]);
+    h3_split2(x0[2], x0[3], s, h[1], l[1]);
+    h3_split2(x1[0], x1[1], s, h[2], l[2]);
+    h3_split2(x1[2], x1[3], s, h[3], l[3]);
+    hi = half8{h[0][0], h[0][1], h[1][0], h[1][1], h[2][0], h[2][1], h[3][0], h[3][1]};
+    lo = half8{l[0][0], l[0][1], l[1][0], l[1][1], l[2][0], l[2][1], l[3][0], l[3][1]};
 }
 
 // max|.| of a tensor without a hot atomic: a "slot" is R3_SLOT words (zeroed once per forward); every producer BLOCK folds
@@ -111,17 +93,17 @@ __device__ __forceinline__ void rams_weight_split_body(const R3SplitJob j) {
         *j.amax = __float_as_uint(t);
     }
     __syncthreads();
-    const float s = r3_pow2(r3_scale_exp(__float_as_uint(amax_s)));
+    const float s = h3_pow2(h3_scale_exp(__float_as_uint(amax_s)));
     // a thread takes one (tap, cin pair, cout): cin pairs keep cvt_pkrtz busy with two values
     for (int i = threadIdx.x; i < CONV_W_FLOATS / 2; i += 512) {
         const int n = i % RC, kp = (i / RC) % (RC / 2), tap = i / (RC * RC / 2);
         const int k = 2 * kp;
-        r3_half2 h, l;
-        if (j.flip) r3_split2(j.w[((26 - tap) * RC + n) * RC + k], j.w[((26 - tap) * RC + n) * RC + k + 1], s, h, l);
-        else r3_split2(j.w[(tap * RC + k) * RC + n], j.w[(tap * RC + k + 1) * RC + n], s, h, l);
+        half2v h, l;
+        if (j.flip) h3_split2(j.w[((26 - tap) * RC + n) * RC + k], j.w[((26 - tap) * RC + n) * RC + k + 1], s, h, l);
+        else h3_split2(j.w[(tap * RC + k) * RC + n], j.w[(tap * RC + k + 1) * RC + n], s, h, l);
         const int at = ((tap * 2 + k / 16) * 2 + (k % 16) / 8) * 256 + n * 8 + k % 8;
-        *reinterpret_cast<r3_half2*>(j.planes + at) = h;
-        *reinterpret_cast<r3_half2*>(j.planes + R3_PLANE_HALVES + at) = l;
+        *reinterpret_cast<half2v*>(j.planes + at) = h;
+        *reinterpret_cast<half2v*>(j.planes + R3_PLANE_HALVES + at) = l;
     }
 }
 
@@ -150,8 +132,8 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_h3_kernel(const Conv3
     const int b = blockIdx.y;
     for (int i = tid; i < R3_LAYER_HALVES / 8; i += CONV_THREADS)
         reinterpret_cast<u32x4*>(sw)[i] = reinterpret_cast<const u32x4*>(p.planes)[i];
-    const int ka = r3_scale_exp(r3_slot_max(p.x_amax)), kb = r3_scale_exp(*p.w_amax);
-    const float sa = r3_pow2(ka), ua = r3_pow2(-ka), ub = r3_pow2(-kb);
+    const int ka = h3_scale_exp(r3_slot_max(p.x_amax)), kb = h3_scale_exp(*p.w_amax);
+    const float sa = h3_pow2(ka), ua = h3_pow2(-ka), ub = h3_pow2(-kb);
     __syncthreads();
 
     const long long xbytes = p.x_elems_per_b * 4;
@@ -217,25 +199,25 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_h3_kernel(const Conv3
                     }
             }
         };
-        auto convert = [&](const f32x4(&a)[MT][4], r3_half8(&hi)[MT][2], r3_half8(&lo)[MT][2]) {
+        auto convert = [&](const f32x4(&a)[MT][4], half8(&hi)[MT][2], half8(&lo)[MT][2]) {
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     if (R3_ABLATE & 1) {
-                        hi[m][i] = __builtin_bit_cast(r3_half8, a[m][2 * i]);
-                        lo[m][i] = __builtin_bit_cast(r3_half8, a[m][2 * i + 1]);
+                        hi[m][i] = __builtin_bit_cast(half8, a[m][2 * i]);
+                        lo[m][i] = __builtin_bit_cast(half8, a[m][2 * i + 1]);
                     } else {
                         r3_split8(a[m][2 * i], a[m][2 * i + 1], sa, hi[m][i], lo[m][i]);
                     }
                 }
         };
-        auto mma_tap = [&](int tap, const r3_half8(&hi)[MT][2], const r3_half8(&lo)[MT][2]) {
+        auto mma_tap = [&](int tap, const half8(&hi)[MT][2], const half8(&lo)[MT][2]) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 const int at = ((tap * 2 + i) * 2 + h) * 256 + l32 * 8;
-                const r3_half8 bh = *reinterpret_cast<const r3_half8*>(sw + at);
-                const r3_half8 bl = *reinterpret_cast<const r3_half8*>(swl + at);
+                const half8 bh = *reinterpret_cast<const half8*>(sw + at);
+                const half8 bl = *reinterpret_cast<const half8*>(swl + at);
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     if (R3_ABLATE & 2) {
@@ -251,7 +233,7 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_h3_kernel(const Conv3
         // raw operands two taps ahead of their MFMAs (three rotating sets), the split one tap ahead (two sets):
         // the pattern repeats every 6 taps; 27 = 4 x 6 + 3
         f32x4 r0[MT][4], r1[MT][4], r2[MT][4];
-        r3_half8 h0[MT][2], l0[MT][2], h1[MT][2], l1[MT][2];
+        half8 h0[MT][2], l0[MT][2], h1[MT][2], l1[MT][2];
         load_tap(0, r0);
         load_tap(1, r1);
         convert(r0, h0, l0);
@@ -412,8 +394,8 @@ __global__ void __launch_bounds__(WAVES * 64, SINGLE ? 2 : 1) conv3d_c32_lds_ker
     const int ptiles = (pvox + 31) / 32;
     const int npatch = p.np1 * p.np2;
     if (tid < 64) reinterpret_cast<float*>(lds)[tid] = 0.f;
-    const int ka = r3_scale_exp(r3_slot_max(p.x_amax)), kb = r3_scale_exp(*p.w_amax);
-    const float sa = r3_pow2(ka), ua = r3_pow2(-ka), ub = r3_pow2(-kb);
+    const int ka = h3_scale_exp(r3_slot_max(p.x_amax)), kb = h3_scale_exp(*p.w_amax);
+    const float sa = h3_pow2(ka), ua = h3_pow2(-ka), ub = h3_pow2(-kb);
     const float bias = p.bias[l32];
     constexpr unsigned R3L_OOB = 0x40000000u;              // buffer offsets from here on are past every image: loads give 0, stores drop
     const __amdgpu_buffer_rsrc_t wsrd =
@@ -483,9 +465,9 @@ __global__ void __launch_bounds__(WAVES * 64, SINGLE ? 2 : 1) conv3d_c32_lds_ker
 #pragma unroll
         for (int i = 0; i < R3L_STAGE_Q; ++i) {
             if ((tid >> 3) + i * (NT / 8) < hvox) {
-                r3_half2 h0, l0, h1, l1;
-                r3_split2(sreg[i][0], sreg[i][1], sa, h0, l0);
-                r3_split2(sreg[i][2], sreg[i][3], sa, h1, l1);
+                half2v h0, l0, h1, l1;
+                h3_split2(sreg[i][0], sreg[i][1], sa, h0, l0);
+                h3_split2(sreg[i][2], sreg[i][3], sa, h1, l1);
                 char* at = at0 + i * (NT / 8) * R3L_VOX_BYTES;
                 *reinterpret_cast<uint2*>(at) = uint2{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
                 *reinterpret_cast<uint2*>(at + 64) = uint2{__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
@@ -592,7 +574,7 @@ __global__ void __launch_bounds__(WAVES * 64, SINGLE ? 2 : 1) conv3d_c32_lds_ker
                     w[2 * i + 1] = __builtin_amdgcn_raw_buffer_load_b128(wsrd, wlane, at + R3_PLANE_HALVES * 2, 0);
                 }
             };
-            r3_half8 a0[MT][4], a1[MT][4];                 // operands of two taps: (i = 0 hi, i = 0 lo, i = 1 hi, i = 1 lo)
+            half8 a0[MT][4], a1[MT][4];                 // operands of two taps: (i = 0 hi, i = 0 lo, i = 1 hi, i = 1 lo)
             // A lane's operand address for a tap: aB + dvb * aK with (aB, aK) = (image + lane base, 1) where the tap's temporal
             // offset d3 stays inside [0, D3) and (0, 0) -- the zero block -- where it does not; the pair is formed once per tile
             // for d3 = 0, 1, 2 (d3 is a compile-time constant of the unrolled loop: the groups of six start at multiples of three),
@@ -606,7 +588,7 @@ __global__ void __launch_bounds__(WAVES * 64, SINGLE ? 2 : 1) conv3d_c32_lds_ker
                     aB[m][d] = ok ? (unsigned)(im + abase[m]) : (unsigned)(h * 16);
                     aK[m][d] = ok ? 1u : 0u;
                 }
-            auto load_a = [&](auto d3c, int tap, r3_half8(&a)[MT][4]) {
+            auto load_a = [&](auto d3c, int tap, half8(&a)[MT][4]) {
                 constexpr int d3 = decltype(d3c)::value;            // == tap % 3
                 const int dvb = (((tap / 9) * HP2 + (tap / 3) % 3) * p.D3 + d3) * R3L_VOX_BYTES;     // wave-uniform
 #pragma unroll
@@ -615,21 +597,21 @@ __global__ void __launch_bounds__(WAVES * 64, SINGLE ? 2 : 1) conv3d_c32_lds_ker
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
                         if (R3_ABLATE & 16) {
-                            a[m][2 * i] = r3_half8{(_Float16)i, 1, 2, 3, 4, 5, 6, 7};
-                            a[m][2 * i + 1] = r3_half8{(_Float16)dvb, 1, 2, 3, 4, 5, 6, 7};
+                            a[m][2 * i] = half8{(_Float16)i, 1, 2, 3, 4, 5, 6, 7};
+                            a[m][2 * i + 1] = half8{(_Float16)dvb, 1, 2, 3, 4, 5, 6, 7};
                             continue;
                         }
-                        a[m][2 * i] = *reinterpret_cast<const r3_half8*>(row + i * 32);            // hi chunk 2 i + h
-                        a[m][2 * i + 1] = *reinterpret_cast<const r3_half8*>(row + i * 32 + 64);   // its lo chunk
+                        a[m][2 * i] = *reinterpret_cast<const half8*>(row + i * 32);            // hi chunk 2 i + h
+                        a[m][2 * i + 1] = *reinterpret_cast<const half8*>(row + i * 32 + 64);   // its lo chunk
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);      // the reads stay AHEAD of the previous tap's MFMAs (the scheduler had sunk
                                                         // them behind five of the six: one MFMA of cover for four ds_read_b128)
             };
-            auto mma = [&](const r3_half8(&a)[MT][4], const u32x4(&w)[4]) {
+            auto mma = [&](const half8(&a)[MT][4], const u32x4(&w)[4]) {
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
-                    const r3_half8 bh = __builtin_bit_cast(r3_half8, w[2 * i]), bl = __builtin_bit_cast(r3_half8, w[2 * i + 1]);
+                    const half8 bh = __builtin_bit_cast(half8, w[2 * i]), bl = __builtin_bit_cast(half8, w[2 * i + 1]);
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
                         if (R3_ABLATE & 2) {
@@ -669,7 +651,7 @@ __global__ void __launch_bounds__(WAVES * 64, SINGLE ? 2 : 1) conv3d_c32_lds_ker
                 // is then nine MFMAs (288 matrix-core cycles) ahead of its use, a weight quad eighteen -- which takes one set of
                 // operand registers and two of weight registers instead of two and three.
                 u32x4 wr[2][4];                            // weights of two taps (set = tap & 1)
-                r3_half8 ar[MT][4];                        // operands of one tap
+                half8 ar[MT][4];                        // operands of one tap
                 // operand address of tile m at the current tap: zero block + (run[m] * aK): run[m] walks the 27 taps by THREE
                 // wave-uniform steps (next temporal tap, next column, next row), so nothing per tap lives in scalar registers
                 unsigned rowoff[MT], run[MT];
@@ -688,12 +670,12 @@ __global__ void __launch_bounds__(WAVES * 64, SINGLE ? 2 : 1) conv3d_c32_lds_ker
                 };
                 auto ld_a = [&](int m, int i) __attribute__((always_inline)) {
                     const char* row = lds + rowoff[m];
-                    ar[m][2 * i] = *reinterpret_cast<const r3_half8*>(row + i * 32);
-                    ar[m][2 * i + 1] = *reinterpret_cast<const r3_half8*>(row + i * 32 + 64);
+                    ar[m][2 * i] = *reinterpret_cast<const half8*>(row + i * 32);
+                    ar[m][2 * i + 1] = *reinterpret_cast<const half8*>(row + i * 32 + 64);
                 };
                 auto mma3 = [&](int m, int i, int tap) __attribute__((always_inline)) {
-                    const r3_half8 bh = __builtin_bit_cast(r3_half8, wr[tap & 1][2 * i]);
-                    const r3_half8 bl = __builtin_bit_cast(r3_half8, wr[tap & 1][2 * i + 1]);
+                    const half8 bh = __builtin_bit_cast(half8, wr[tap & 1][2 * i]);
+                    const half8 bl = __builtin_bit_cast(half8, wr[tap & 1][2 * i + 1]);
                     acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[m][2 * i + 1], bh, acc[m], 0, 0, 0);
                     acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[m][2 * i], bl, acc[m], 0, 0, 0);
                     acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ar[m][2 * i], bh, acc[m], 0, 0, 0);
@@ -806,8 +788,8 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_lds2_kernel(const Con
     const int ptiles = (pvox + 31) / 32;
     const int npatch = p.np1 * p.np2;
     if (tid < 16) reinterpret_cast<float*>(zeros)[tid] = 0.f;
-    const int ka = r3_scale_exp(r3_slot_max(p.x_amax)), kb = r3_scale_exp(*p.w_amax);
-    const float sa = r3_pow2(ka), ua = r3_pow2(-ka), ub = r3_pow2(-kb);
+    const int ka = h3_scale_exp(r3_slot_max(p.x_amax)), kb = h3_scale_exp(*p.w_amax);
+    const float sa = h3_pow2(ka), ua = h3_pow2(-ka), ub = h3_pow2(-kb);
     const float bias = p.bias[l32];
     const float* xb = p.x + (long long)b * p.D1 * p.D2 * p.D3 * RC;
     const __amdgpu_buffer_rsrc_t wsrd =
@@ -838,9 +820,9 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_lds2_kernel(const Con
             const int u = tid + CONV_THREADS * i;
             const int hv = u >> 2, cc = u & 3;
             if (hv < hvox) {
-                r3_half2 h0, l0, h1, l1;
-                r3_split2(sreg[i][0], sreg[i][1], sa, h0, l0);
-                r3_split2(sreg[i][2], sreg[i][3], sa, h1, l1);
+                half2v h0, l0, h1, l1;
+                h3_split2(sreg[i][0], sreg[i][1], sa, h0, l0);
+                h3_split2(sreg[i][2], sreg[i][3], sa, h1, l1);
                 const int slot = (cc >> 1) ^ ((hv >> 2) & 3);
                 char* at = dst + hv * 64 + (cc & 1) * 8;
                 *reinterpret_cast<uint2*>(at + slot * 16) = uint2{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
@@ -896,8 +878,8 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_lds2_kernel(const Con
                     w[0] = __builtin_amdgcn_raw_buffer_load_b128(wsrd, at, 0, 0);
                     w[1] = __builtin_amdgcn_raw_buffer_load_b128(wsrd, at + R3_PLANE_HALVES * 2, 0, 0);
                 };
-                r3_half8 a0[MT][2], a1[MT][2];             // operands of two taps: (hi, lo) per tile
-                auto load_a = [&](int tap, r3_half8(&a)[MT][2]) {
+                half8 a0[MT][2], a1[MT][2];             // operands of two taps: (hi, lo) per tile
+                auto load_a = [&](int tap, half8(&a)[MT][2]) {
                     const int d3 = tap % 3;
                     const int dv = ((tap / 9) * HP2 + (tap / 3) % 3) * p.D3 + d3;
 #pragma unroll
@@ -906,12 +888,12 @@ __global__ void __launch_bounds__(CONV_THREADS) conv3d_c32_lds2_kernel(const Con
                         const bool ok = (tmask[m] >> d3) & 1u;
                         const char* row = ok ? im + hv * 64 : zeros;
                         const int slot = ok ? (h ^ ((hv >> 2) & 3)) : 0;
-                        a[m][0] = *reinterpret_cast<const r3_half8*>(row + slot * 16);
-                        a[m][1] = *reinterpret_cast<const r3_half8*>(row + (ok ? (slot ^ 2) : 0) * 16);
+                        a[m][0] = *reinterpret_cast<const half8*>(row + slot * 16);
+                        a[m][1] = *reinterpret_cast<const half8*>(row + (ok ? (slot ^ 2) : 0) * 16);
                     }
                 };
-                auto mma = [&](const r3_half8(&a)[MT][2], const u32x4(&w)[2]) {
-                    const r3_half8 bh = __builtin_bit_cast(r3_half8, w[0]), bl = __builtin_bit_cast(r3_half8, w[1]);
+                auto mma = [&](const half8(&a)[MT][2], const u32x4(&w)[2]) {
+                    const half8 bh = __builtin_bit_cast(half8, w[0]), bl = __builtin_bit_cast(half8, w[1]);
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
                         acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[m][1], bh, acc[m], 0, 0, 0);

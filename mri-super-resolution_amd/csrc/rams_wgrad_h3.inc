@@ -45,7 +45,7 @@ __device__ __forceinline__ void w3_wait8(w3_u32x2 (&f)[8]) {
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]));
 }
-__device__ __forceinline__ r3_half8 w3_frag(w3_u32x2 a, w3_u32x2 b) { return __builtin_bit_cast(r3_half8, u32x4{a[0], a[1], b[0], b[1]}); }
+__device__ __forceinline__ half8 w3_frag(w3_u32x2 a, w3_u32x2 b) { return __builtin_bit_cast(half8, u32x4{a[0], a[1], b[0], b[1]}); }
 
 __global__ void __launch_bounds__(512) conv3d_c32_wgrad_h3_kernel(const Conv3dWgradH3Params p) {
     constexpr int NT = 512;
@@ -61,8 +61,8 @@ __global__ void __launch_bounds__(512) conv3d_c32_wgrad_h3_kernel(const Conv3dWg
     const int pvox = p.PO1 * p.PO2 * p.O3;
     const int npatch = p.np1 * p.np2;
     if (tid < 64) reinterpret_cast<float*>(lds)[tid] = 0.f;
-    const int ka = r3_scale_exp(r3_slot_max(p.x_amax)), kd = r3_scale_exp(r3_slot_max(p.dy_amax));
-    const float sa = r3_pow2(ka), sd = r3_pow2(kd), ua = r3_pow2(-ka), ud = r3_pow2(-kd);
+    const int ka = h3_scale_exp(r3_slot_max(p.x_amax)), kd = h3_scale_exp(r3_slot_max(p.dy_amax));
+    const float sa = h3_pow2(ka), sd = h3_pow2(kd), ua = h3_pow2(-ka), ud = h3_pow2(-kd);
     const __amdgpu_buffer_rsrc_t xsrd = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(p.x) + (long long)b * p.D1 * p.D2 * p.D3 * RC, 0, p.D1 * p.D2 * p.D3 * RC * 4, 0x00020000);
     const __amdgpu_buffer_rsrc_t ysrd = __builtin_amdgcn_make_buffer_rsrc(
@@ -86,9 +86,9 @@ __global__ void __launch_bounds__(512) conv3d_c32_wgrad_h3_kernel(const Conv3dWg
     }
     const int dst0 = (tid >> 3) * R3L_VOX_BYTES + ((tid & 7) >> 1) * 16 + (tid & 1) * 8;
     auto split_store = [&](const f32x4 v, float s, char* at) __attribute__((always_inline)) {
-        r3_half2 h0, l0, h1, l1;
-        r3_split2(v[0], v[1], s, h0, l0);
-        r3_split2(v[2], v[3], s, h1, l1);
+        half2v h0, l0, h1, l1;
+        h3_split2(v[0], v[1], s, h0, l0);
+        h3_split2(v[2], v[3], s, h1, l1);
         *reinterpret_cast<uint2*>(at) = uint2{__builtin_bit_cast(unsigned, h0), __builtin_bit_cast(unsigned, h1)};
         *reinterpret_cast<uint2*>(at + 64) = uint2{__builtin_bit_cast(unsigned, l0), __builtin_bit_cast(unsigned, l1)};
     };
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(512) conv3d_c32_wgrad_h3_kernel(const Conv3dWg
 #pragma unroll
                     for (int e = 0; e < 2; ++e) fb[(j * 2 + lo) * 2 + e] = w3_tr_read(ya[e] + 32 * j + 64 * lo);
             w3_wait8(fb);
-            r3_half8 bh[2], bl[2];
+            half8 bh[2], bl[2];
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 bh[j] = w3_frag(fb[(j * 2) * 2], fb[(j * 2) * 2 + 1]);
@@ -194,8 +194,8 @@ __global__ void __launch_bounds__(512) conv3d_c32_wgrad_h3_kernel(const Conv3dWg
                     w3_wait8(fa);
 #pragma unroll
                     for (int i = 0; i < 2; ++i) {
-                        const r3_half8 ah = w3_frag(fa[(i * 2) * 2], fa[(i * 2) * 2 + 1]);
-                        const r3_half8 al = w3_frag(fa[(i * 2 + 1) * 2], fa[(i * 2 + 1) * 2 + 1]);
+                        const half8 ah = w3_frag(fa[(i * 2) * 2], fa[(i * 2) * 2 + 1]);
+                        const half8 al = w3_frag(fa[(i * 2 + 1) * 2], fa[(i * 2 + 1) * 2 + 1]);
 #pragma unroll
                         for (int j = 0; j < 2; ++j) {
                             acc[t][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh[j], acc[t][i][j], 0, 0, 0);
@@ -206,7 +206,7 @@ __global__ void __launch_bounds__(512) conv3d_c32_wgrad_h3_kernel(const Conv3dWg
                 }
             }
             if (bias_wave) {                               // x == 1: hi = 1, lo = 0 -> dy_lo + dy_hi, exact in fp32 accumulation
-                const r3_half8 one = {(_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1};
+                const half8 one = {(_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1, (_Float16)1};
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     acc[3][0][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(one, bl[j], acc[3][0][j], 0, 0, 0);

@@ -156,14 +156,15 @@ def test_compat_modules_import():
 
 
 def test_per_source_compiler_flags_name_real_sources_and_reach_the_source_hash():
-    """`_build.SOURCE_FLAGS` (the GEMM translation unit is compiled without packed fp32 VALU instructions) must name sources that
+    """`_build.SOURCE_FLAGS` (both GEMM translation units are compiled without packed fp32 VALU instructions) must name sources that
     exist -- a typo would silently build the default feature set -- and the compiler flags are part of what bench.py's kernel-source
     hash covers (a tracked PMC summary measured with other flags must read as stale)."""
     import hashlib
     import bench
     from mri_super_resolution_amd import _build
-    assert set(_build.SOURCE_FLAGS) <= set(_build.SOURCES) and "gemm_f32.hip" in _build.SOURCE_FLAGS
-    assert "-packed-fp32-ops" in _build.SOURCE_FLAGS["gemm_f32.hip"]
+    assert set(_build.SOURCE_FLAGS) <= set(_build.SOURCES)
+    for unit in ("gemm_f32.hip", "gemm_hp.hip"):
+        assert unit in _build.SOURCE_FLAGS and "-packed-fp32-ops" in _build.SOURCE_FLAGS[unit], unit
     h = hashlib.sha256()
     csrc = os.path.join(os.path.dirname(_build.__file__), "csrc")
     for f in sorted(os.listdir(csrc)):

@@ -87,7 +87,7 @@ CUS = 256     # MI355X (ops.device_caps: checked in the fixture below)
 
 
 def row_plan(n, width, persistent=2, narrow=1):
-    """hp_row_plan of csrc/gemm_f32.hip: (rows for the wide persistent kernels, rows for the 64 x 128 tiles of gemm_hp_nt_kernel),
+    """hp_row_plan of csrc/gemm_hp.hip: (rows for the wide persistent kernels, rows for the 64 x 128 tiles of gemm_hp_nt_kernel),
     spelled out a second time on purpose: a change of the dispatch has to be made in both places."""
     if not narrow or not persistent:
         return n, 0
@@ -100,7 +100,7 @@ def kc_families(K, deferred_ok, n, width, persistent=2, narrow=1, row=0, row_min
     wide, nar = row_plan(n, width, persistent, narrow)
     out = []
     if wide:
-        # hp_row_ok of csrc/gemm_f32.hip: the row-owning kernel takes 512-column launches with enough 128-row panels
+        # hp_kc_choice of csrc/gemm_hp.hip: the row-owning kernel takes 512-column launches with enough 128-row panels
         if row and persistent == 2 and width == 512 and deferred_ok and (wide + 127) // 128 >= row_min_tiles:
             out.append("hp_row")
         else:
@@ -646,6 +646,50 @@ def test_persistent_grid_cap_keeps_every_bit(name, keys, families):
             worst = max(worst, O.rel_l2(a, b))
     print(f"\n[cap {name}] bit-identical at caps 1, 3, 7; from float64: forward {O.rel_l2(got_y, want_y):.2e}"
           + ("" if families is None else f", worst gradient {worst:.2e}"))
+
+
+# ------------------------------------------------------------------ the narrow tiles against the wide kernel of every K class ---------
+# (in_features, hidden, hidden_layers): K = 64 one block per tile, K = 256 deferred (KT = 8) forward / in line input gradient;
+# K = 160 in line, K = 512 deferred (KT = 16) both ways; K = 256 deferred first layer
+NARROW_CLASSES = [(64, 256, 2), (160, 512, 2), (256, 512, 1)]
+
+
+@pytest.mark.parametrize("zhead", [1, 0])
+@pytest.mark.parametrize("n", [300, 777])
+@pytest.mark.parametrize("fin,hidden,layers", NARROW_CLASSES)
+def test_narrow_tiles_give_the_wide_kernels_bits_in_every_k_class(fin, hidden, layers, n, zhead):
+    """A few hundred ragged rows go to gemm_hp_nt_kernel by default (key 18 = 1) and to the wide kernel of their K with key 18 = 0.  The
+    narrow kernel takes the MFMA block order and the bias fold of that wide kernel (hp_kc_choice), so the forward output must agree BIT
+    FOR BIT -- with the z-only last layer and with the plain one (key 16).  The loss, every weight gradient, the last sine layer's bias
+    gradient and the head's gradients depend only on dz and the stash and are bit-equal too; the bias gradients of the layers below are
+    column sums the input-gradient epilogue partitions by its tile height (32-row against 64-row partial sums), pinned at 2e-6."""
+    net, _ = make_pair(fin, hidden, layers, seed=fin + n)
+    net.cuda()
+    g = torch.Generator().manual_seed(n + fin)
+    x = (torch.rand(n, fin, generator=g) * 2 - 1).cuda()
+    t = torch.rand(n, generator=g).cuda()
+    w = ((torch.rand(n, generator=g) > 0.25).float() * (0.5 + torch.rand(n, generator=g))).cuda()
+    runs = {}
+    for narrow in (1, 0):
+        with ops.debug_switch(18, narrow), ops.debug_switch(16, zhead):
+            ops.launch_counts_reset()
+            runs[narrow] = fused_loss_grads(net, x, t, w)
+            counts = ops.launch_counts()
+        check_families(counts, expected_families(fin, hidden, layers, n, True, narrow=narrow),
+                       expected_families(fin, hidden, layers, n, False, narrow=narrow))
+        wide = sum(counts[f] for f in ("hp_pkd", "hp_pkc", "hp_tile", "hp_row"))
+        kc = 3 * layers + 2      # K-contiguous launches: S forward + S - 1 input-gradient + S forward, S = layers + 1
+        assert (counts["hp_narrow"], wide) == ((kc, 0) if narrow else (0, kc)), counts
+    (l1, g1, y1), (l0, g0, y0) = runs[1], runs[0]
+    same = [np.array_equal(bits(a), bits(b)) for a, b in zip(g1, g0)]
+    dist = [O.rel_l2(a, b) for a, b in zip(g1, g0)]
+    print(f"\n[narrow {fin}-{hidden}x{layers} n={n} zhead={zhead}] forward bit-equal {np.array_equal(bits(y1), bits(y0))}, loss {l1 == l0}, "
+          f"gradients (W_0, b_0, ...) " + " ".join("bit" if s else f"{d:.1e}" for s, d in zip(same, dist)))
+    assert np.array_equal(bits(y1), bits(y0))
+    assert l1 == l0
+    for k, (s, d) in enumerate(zip(same, dist)):
+        colsum_bias = k % 2 == 1 and k // 2 < layers       # b_l of a sine layer with an input-gradient GEMM above it
+        assert d < 2e-6 if colsum_bias else s, (k, d)
 
 
 # ------------------------------------------------------------------ the default fit step at the row counts real fits run ---------
