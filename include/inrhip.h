@@ -626,6 +626,58 @@ int inr_siren_jet_grid(const inr_siren_desc_t* desc, const float* params, const 
 #define INR_JET_LF_COUNT 3
 int inr_jet_launch_count(int family, int64_t* count);
 
+/* ---- the WIRE complex-Gabor INR (INRmodel.py:66-120 `ComplexGaborLayer2D`; wiretest.ipynb cell 2 stacks it) -----------------------
+ * Layer 0 holds two REAL Linear(in -> H) (`linear`, `scale_orth`), layers 1 .. hidden_layers two COMPLEX Linear(H -> H) each, the
+ * head is a complex Linear(H -> 1) whose real part is the output.  With lin = linear(h), orth = scale_orth(h), w = omega_0,
+ * s = scale_0 a layer gives  exp(i w lin) exp(-s^2 (|lin|^2 + |orth|^2)), evaluated in real arithmetic as
+ *     A = exp(-w lin_i - s^2 (lin_r^2 + lin_i^2 + orth_r^2 + orth_i^2)),  out = A cos(w lin_r) + i A sin(w lin_r)
+ * (ONE exponential of the summed exponent).  No complex type crosses this ABI: a complex tensor is its interleaved (re, im)
+ * float pairs, torch's own layout (view_as_real).  s^2 is the fp32 product first_scale * first_scale (hidden_scale likewise).
+ * Flat parameter buffer (fp32, every tensor padded to 16 bytes; omega_0 / scale_0 are NOT in it): per layer linear.weight,
+ * linear.bias, scale_orth.weight, scale_orth.bias, layers front to back, then the head's weight and bias.
+ * Served: out_features == 1, hidden_features in {32, 64, 128, 256}, 0 <= hidden_layers <= 8, 1 <= in_features <= 1024;
+ * anything else, and a null desc / params / x / y, is INR_E_INVALID before any device work; a null or short workspace is
+ * INR_E_WORKSPACE, a pointer off a 16-byte boundary INR_E_ALIGN.  Arithmetic: f32-input MFMA 32x32x2 only;
+ * plain launches, fixed-order reductions, no float atomics: repeated calls are bit-equal.  Every call only enqueues. */
+typedef struct {
+    int   in_features, hidden_features, hidden_layers, out_features;
+    float first_omega, hidden_omega, first_scale, hidden_scale;
+} inr_wire_desc_t;
+int64_t inr_wire_param_count(const inr_wire_desc_t* desc);                   /* -1 for a descriptor the kernels do not serve */
+/* offsets[4 l + {0, 1, 2, 3}] = linear.weight, linear.bias, scale_orth.weight, scale_orth.bias of layer l <= hidden_layers, then
+ * the head's weight and bias: 4 (hidden_layers + 1) + 2 float offsets; max_entries counts them */
+int     inr_wire_param_offsets(const inr_wire_desc_t* desc, int64_t* offsets, int max_entries);
+size_t  inr_wire_workspace_bytes(const inr_wire_desc_t* desc, int64_t n, int training);   /* 0 for what is not served */
+/* INRmodel.py:109-120, one ComplexGaborLayer2D.forward.  is_first: x [n][in_features] real, real weights [H][in]; otherwise
+ * x [n][2H] = planes [re | im], in_features == out_features == H and interleaved complex weights [H][H][2] / biases [H][2].
+ * out [n][2H] = planes [re | im].  Workspace: inr_wire_layer_workspace_bytes(n, x's columns, out_features). */
+size_t inr_wire_layer_workspace_bytes(int64_t n, int in_columns, int out_features);
+int inr_wire_layer_forward(float* out, const float* x, const float* lin_w, const float* lin_b, const float* orth_w,
+                           const float* orth_b, int64_t n, int in_features, int out_features, int is_first, float omega, float scale,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* wiretest.ipynb cell 2 `forward`: y[n] = Re head(layers(x[n][in_features])); workspace: inr_wire_workspace_bytes(desc, n, 0) */
+int inr_wire_forward(const inr_wire_desc_t* desc, const float* params, const float* x, int64_t n, float* y, void* workspace,
+                     size_t workspace_bytes, void* stream);
+/* wiretest.ipynb cell 10: clamp(INR(input_mapping(get_mgrid(shape), B)), min) -> y[prod(shape)], grid + Fourier features made
+ * chunk by chunk in the workspace with the kernel of inr_grid_fourier_map; B == NULL feeds the raw coordinates
+ * (in_features == dim).  Arguments as inr_siren_reconstruct; bit-equal with inr_wire_forward on the same rows. */
+size_t inr_wire_reconstruct_workspace_bytes(const inr_wire_desc_t* desc, int64_t chunk_rows);
+int inr_wire_reconstruct(const inr_wire_desc_t* desc, const float* params, const int64_t* shape, int dim, const float* B, int m,
+                         float* y, int use_clamp, float clamp_min, int64_t chunk_rows, void* workspace, size_t workspace_bytes,
+                         void* stream);
+/* wiretest.ipynb cell 10, `loss = ((model_output - LR_ground_truth)**2).mean(); loss.backward()`: *loss = mean(w (y - t)^2)
+ * (weight nullable) and grads = its gradient in the flat layout, torch's convention for complex parameters
+ * (grad = dL/dRe + i dL/dIm; the head bias's imaginary part gets exactly 0).  Workspace: inr_wire_workspace_bytes(desc, n, 1). */
+int inr_wire_loss_grad(const inr_wire_desc_t* desc, const float* params, float* grads, const float* x, const float* target,
+                       const float* weight, int64_t n, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+/* wiretest.ipynb cell 10's plain branch, n_steps times: forward, MSE, backward, Adam over the flat buffer (a complex parameter
+ * is its two reals, as torch.optim.Adam views it; the arithmetic of inr_adam_step), with no host read.  first_step = the
+ * 1-based Adam step of the first iteration; losses[n_steps] (device, nullable) receives each step's loss before its update.
+ * One step is bit-equal with inr_wire_loss_grad + inr_adam_step.  Workspace: inr_wire_workspace_bytes(desc, n, 1). */
+int inr_wire_fit(const inr_wire_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x,
+                 const float* target, const float* weight, int64_t n, int64_t first_step, int n_steps, double lr, double beta1,
+                 double beta2, double eps, float* losses, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- measurement hooks (bench.py roofline): per-kernel-class HIP-event timing on the launch stream.
  * class ids: 0 = GEMM forward (sine layer), 1 = GEMM input-grad, 2 = GEMM param-grad, 3 = other */
 int  inr_prof_enable(int enable);

@@ -49,6 +49,12 @@ class PiaDesc(C.Structure):
                 ("T2_mean", C.c_double * 3), ("T2_delta", C.c_double * 3)]
 
 
+class WireDesc(C.Structure):
+    _fields_ = [("in_features", C.c_int), ("hidden_features", C.c_int), ("hidden_layers", C.c_int),
+                ("out_features", C.c_int), ("first_omega", C.c_float), ("hidden_omega", C.c_float),
+                ("first_scale", C.c_float), ("hidden_scale", C.c_float)]
+
+
 class DeviceCaps(C.Structure):
     _fields_ = [("abi_version", C.c_int), ("device", C.c_int), ("compute_units", C.c_int),
                 ("wavefront_size", C.c_int), ("lds_bytes_per_cu", C.c_int), ("clock_khz", C.c_int),
@@ -195,6 +201,20 @@ SIGNATURES = {
     "inr_siren_jet_grid": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_i64p, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p,
                                      C.c_int64, C.c_void_p, C.c_size_t, c_stream]),
     "inr_jet_launch_count": (C.c_int, [C.c_int, c_i64p]),
+    "inr_wire_param_count": (C.c_int64, [C.POINTER(WireDesc)]),
+    "inr_wire_param_offsets": (C.c_int, [C.POINTER(WireDesc), c_i64p, C.c_int]),
+    "inr_wire_workspace_bytes": (C.c_size_t, [C.POINTER(WireDesc), C.c_int64, C.c_int]),
+    "inr_wire_layer_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int, C.c_int]),
+    "inr_wire_layer_forward": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                         C.c_float, C.c_float, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_wire_forward": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_wire_reconstruct_workspace_bytes": (C.c_size_t, [C.POINTER(WireDesc), C.c_int64]),
+    "inr_wire_reconstruct": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_i64p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_float,
+                                       C.c_int64, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_wire_loss_grad": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p,
+                                     C.c_size_t, c_stream]),
+    "inr_wire_fit": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64,
+                               C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "inr_prof_enable": (C.c_int, [C.c_int]),
     "inr_prof_reset": (C.c_int, []),
     "inr_prof_read": (C.c_int, [C.c_int, c_i64p, C.POINTER(C.c_double)]),

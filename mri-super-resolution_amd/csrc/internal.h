@@ -153,6 +153,16 @@ void set_hybrid_variant(int v);   // key 2
 // (pia.hip, erd_siren.hip and jet.hip define public entry points only; their launch families are counted through count_launch in
 // api.hip's table like every other -- common.h: LF_PIA_BASE, LF_JET_BASE, and the ERD families at their public ids.)
 
+// ---- wire.hip: the complex-Gabor (WIRE) layers in real arithmetic, f32-input MFMA 32x32x2 -------------------------------------------
+// in [n][K] (K a multiple of 32) times the block image img [Q][H][K] (Q = 2 for the real first layer, else 4), Gabor epilogue:
+// out [n][2H] = [out_r | out_i]; stash (nullable) [n][Q H] receives lin_r (, lin_i), orth_r (, orth_i)
+int wire_gabor_forward(float* out, float* stash, const float* in, const float* img, const float* pb, int K, int H, int first,
+                       int64_t n, float omega, float s2, hipStream_t st);
+// G [n][2H] = dZ [n][4H] times the image, read through its transpose imgT [2H][4H]
+int wire_input_grad(float* G, const float* dZ, const float* imgT, int H, int64_t n, hipStream_t st);
+// slabs [splits][R][C] = per-split dZ^T X and bslab [splits][R] = per-split column sums of dZ (dZ [n][R], X [n][C])
+int wire_param_grad_slabs(float* slabs, float* bslab, const float* dZ, int R, const float* X, int C, int64_t n, hipStream_t st);
+
 // ---- rams.hip (+ rams_train.inc) ---------------------------------------------------------------------------------------------------------
 long long rams_param_floats(const inr_rams_desc_t* d);
 size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W);

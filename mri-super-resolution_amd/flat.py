@@ -11,6 +11,14 @@ def _bytes(need, device):
     return torch.empty(need, dtype=torch.uint8, device=device)
 
 
+def _view(vector, off, like):
+    """The slice of the float ``vector`` at ``off`` in the shape of ``like``.  A complex tensor is its interleaved (re, im)
+    float pairs -- torch's own layout -- seen through ``view_as_complex`` (``off`` must then be even)."""
+    if like.is_complex():
+        return torch.view_as_complex(vector[off:off + 2 * like.numel()].view(*like.shape, 2))
+    return vector[off:off + like.numel()].view_as(like)
+
+
 class FlatParams:
     """One flat fp32 buffer of ``total`` floats holding tensor k at ``offsets[k]``, in the order in which the caller hands
     its parameters over.  ``adopt`` re-points the parameters at views of the buffer, so the module, an external optimizer
@@ -24,7 +32,7 @@ class FlatParams:
     def _carve(self, vector, like):
         if len(like) != len(self.offsets):
             raise ValueError(f"{len(like)} tensors for a layout of {len(self.offsets)}")
-        return [vector[off:off + t.numel()].view_as(t) for off, t in zip(self.offsets, like)]
+        return [_view(vector, off, t) for off, t in zip(self.offsets, like)]
 
     def adopt(self, params, zero=True):
         """Build the buffer on ``params[0].device``, copy every parameter in and re-point its ``.data`` at its view.

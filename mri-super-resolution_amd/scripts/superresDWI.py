@@ -27,6 +27,11 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     ``laplace``, evaluated in forward mode by ``inr.derivatives``) along the in-plane and through-plane axes -- not along the
     b-value axis.  ``grad_mag = sqrt(sum_i (dy/dx_i)^2)``, ``laplacian = sum_i d^2y/dx_i^2``, of the un-clamped network, in the
     normalised [-1, 1] coordinates of ``get_mgrid`` (times ``2 / (n_i - 1)`` per axis and order for per-voxel units).
+``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
+hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
+plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
+``--transverse_length`` and ``--adc`` go through ``wire.reconstruct``.  The PerturbNet phase and ``--derivative_maps`` have no
+WIRE kernels and are refused before the fit.  The default ``--model siren`` is the path described above, unchanged.
 R = roi_end - roi_start.  Plots (superresDWI.py:164-233) are outside the build's scope.
 """
 from __future__ import annotations
@@ -44,7 +49,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 import mri_super_resolution_amd as inr  # noqa: E402
-from mri_super_resolution_amd import baselines, drivers, matio, metrics, reports  # noqa: E402
+from mri_super_resolution_amd import baselines, drivers, matio, metrics, reports, wire  # noqa: E402
 
 
 def build_parser():
@@ -72,6 +77,11 @@ def build_parser():
     p.add_argument("--derivative_maps", action="store_true",
                    help="also write derivatives.mat: gradient magnitude and Laplacian of the fitted network on recon's grid, "
                         "along the spatial axes (nn_mri.py:205-221)")
+    p.add_argument("--model", choices=("siren", "wire"), default="siren",
+                   help="network family: the SIREN of superresDWI.py, or the complex-Gabor WIRE network of wiretest.ipynb "
+                        "(hidden_features = hidden_dim // 2; no PerturbNet phase, no derivative maps)")
+    p.add_argument("--wire_omega", type=float, default=1.2, help="--model wire: omega_0 of every layer (wiretest.ipynb cell 7)")
+    p.add_argument("--wire_scale", type=float, default=1.2, help="--model wire: scale_0 of every layer (wiretest.ipynb cell 7)")
     return p
 
 
@@ -85,10 +95,11 @@ def load_input(path, key=None):
     return load_input_and_scale(path, key)[:4]
 
 
-def load_input_and_scale(path, key=None):
+def load_input_and_scale(path, key=None, refuse_acquisitions=None):
     """``load_input`` plus the per-b factors [B] that turn ``mean_img`` back into signal for the ADC maps: ``maxes[:, 1]``
     (TE index 1, superresDWI.py:193-195; None when ``hybrid_raw`` has a single TE) or, for a plain volume, the per-b maxima it
-    was divided by."""
+    was divided by.  ``refuse_acquisitions``: the reason for which an input with single acquisitions (``hybrid_raw``) is
+    refused (``_check_model``) -- raised before their products are formed on the device."""
     data = matio.loadmat(path)
     if key is None and "hybrid_raw" in data:
         key = "hybrid_raw"
@@ -99,6 +110,8 @@ def load_input_and_scale(path, key=None):
         key = keys[0]
     arr = data[key]
     if arr.dtype == object:                                           # hybrid_raw: superresDWI.py:44-83
+        if refuse_acquisitions:
+            raise ValueError(f"{path}: {refuse_acquisitions}")
         raw = [[np.asarray(arr[b][te], np.float64) for te in range(arr.shape[1])] for b in range(arr.shape[0])]
         maxes = np.array([[raw[b][te].max() for te in range(len(raw[b]))] for b in range(len(raw))])
         norm = [[raw[b][te] / maxes[b, te] for te in range(len(raw[b]))] for b in range(len(raw))]
@@ -117,7 +130,7 @@ def load_input_and_scale(path, key=None):
 def run_patient(path, pt_id, args):
     out_dir = os.path.join(args.output_address, f"pat{pt_id}")
     os.makedirs(out_dir, exist_ok=True)
-    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key)
+    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, _check_model(args))
     r0, r1 = args.roi_start, args.roi_end
     if r1 > min(mean_img.shape[:2]) or r0 < 0 or r1 - r0 < 14:
         raise ValueError(f"ROI {r0}:{r1} does not fit the {mean_img.shape[:2]} slices (SSIM needs >= 7 x 7 LR pixels)")
@@ -130,13 +143,22 @@ def run_patient(path, pt_id, args):
     mean_dataset = inr.ImageFitting_set([lr_img])
     dimension = len(mean_dataset.shape)
     B = torch.from_numpy(np.random.normal(size=(args.mapping_size, dimension)) * args.scale).float().cuda()   # :105-106
-    INR = inr.Siren(in_features=2 * args.mapping_size, out_features=1, hidden_features=args.hidden_dim,
-                    hidden_layers=args.num_layers).cuda()
+    if args.model == "wire":                                                              # wiretest.ipynb cell 7
+        INR = wire.Wire(in_features=2 * args.mapping_size, out_features=1, hidden_features=args.hidden_dim // 2,
+                        hidden_layers=args.num_layers, first_omega_0=args.wire_omega, hidden_omega_0=args.wire_omega,
+                        scale=args.wire_scale).cuda()
+        reconstruct = wire.reconstruct
+    else:
+        INR = inr.Siren(in_features=2 * args.mapping_size, out_features=1, hidden_features=args.hidden_dim,
+                        hidden_layers=args.num_layers).cuda()
+        reconstruct = inr.reconstruct
     model_input = inr.input_mapping(mean_dataset.coords[0], B)
     target = mean_dataset.pixels[0]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    if acq is None:
+    if args.model == "wire":                                  # the plain fit on the mean image (wiretest.ipynb cell 10)
+        fitter, losses = wire.fit_wire(INR, model_input, target, args.number_of_epochs, lr=args.learning_rate)
+    elif acq is None:
         fitter, losses = inr.fit_siren(INR, model_input, target, args.number_of_epochs, lr=args.learning_rate)
     else:
         acq_lr = [acq[r0:r1:2, r0:r1:2, :, :, k] for k in range(acq.shape[-1])]
@@ -147,8 +169,8 @@ def run_patient(path, pt_id, args):
     hr_shape = tuple(hr_img.shape)
     test_shape = (hr_shape[0] * 2, hr_shape[1] * 2) + hr_shape[2:]                         # :125
     t0 = time.perf_counter()
-    recon = inr.reconstruct(INR, test_shape, B)                                           # :161
-    SR_recon = inr.reconstruct(INR, hr_shape, B)                                          # :162
+    recon = reconstruct(INR, test_shape, B)                                               # :161
+    SR_recon = reconstruct(INR, hr_shape, B)                                              # :162
     torch.cuda.synchronize()
     t_rec = time.perf_counter() - t0
 
@@ -178,7 +200,7 @@ def run_patient(path, pt_id, args):
         "ssim_sr_mean": float(ssim_sr[okn].mean()), "ssim_spline_mean": float(ssim_spline[okn].mean()),
     }
     if args.transverse_length:
-        coronal, summary["t_coronal_s"] = _coronal(INR, B, mean_img, test_shape, args)
+        coronal, summary["t_coronal_s"] = _coronal(INR, B, mean_img, test_shape, args, reconstruct)
         matio.savemat(os.path.join(out_dir, "coronal.mat"), coronal)
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
@@ -195,6 +217,26 @@ def run_patient(path, pt_id, args):
         json.dump(summary, fh, indent=1)
     print(json.dumps(summary))
     return summary
+
+
+def _check_model(args):
+    """``--model wire``: refuses what has no WIRE kernels, before the input is loaded and anything touches the device.
+    Returns the reason for which an input with single acquisitions is to be refused (None: it is served)."""
+    if args.model != "wire":
+        return None
+    if args.derivative_maps:
+        raise ValueError("--derivative_maps needs the forward-mode derivative kernels, which exist for the SIREN only: "
+                         "there are no derivative maps of a WIRE network (--model wire)")
+    if args.hidden_dim // 2 not in wire.HIDDEN_SIZES or not 0 <= args.num_layers <= wire.MAX_HIDDEN_LAYERS or \
+            not 1 <= 2 * args.mapping_size <= wire.MAX_IN_FEATURES:
+        raise ValueError(f"--model wire serves hidden_dim // 2 in {wire.HIDDEN_SIZES}, num_layers <= {wire.MAX_HIDDEN_LAYERS} "
+                         f"and 2 * mapping_size <= {wire.MAX_IN_FEATURES} (got hidden_dim {args.hidden_dim}, num_layers "
+                         f"{args.num_layers}, mapping_size {args.mapping_size})")
+    if args.pertubation_epochs > 0:
+        return ("holds single acquisitions, and --pertubation_epochs > 0 asks for the PerturbNet phase: it needs the "
+                "network's input gradient through the Fourier map, which the WIRE kernels do not compute (--model wire); "
+                "pass --pertubation_epochs 0 to fit the mean image only")
+    return None
 
 
 def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
@@ -214,7 +256,7 @@ def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
             raise ValueError(f"--adc rescales by maxes[b, 1] (TE index 1, superresDWI.py:193); {path} has a single TE")
 
 
-def _coronal(INR, B, mean_img, test_shape, args):
+def _coronal(INR, B, mean_img, test_shape, args, reconstruct=inr.reconstruct):
     """superresDWI.py:217-241: the INR on a (2R, 2R, T, 1) grid -- the size-1 last axis puts b at -1, b index 0 -- without the
     clamp (:221), and the cubic spline of the HR ROI's b = 0 image along z (:231; the spline runs per line, so cropping the ROI
     first changes nothing).  -> (variables of coronal.mat, seconds)."""
@@ -222,7 +264,7 @@ def _coronal(INR, B, mean_img, test_shape, args):
     r0, r1 = args.roi_start, args.roi_end
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    sr = inr.reconstruct(INR, (test_shape[0], test_shape[1], T, 1), B, clamp_min=None)[..., 0]
+    sr = reconstruct(INR, (test_shape[0], test_shape[1], T, 1), B, clamp_min=None)[..., 0]
     hr0 = torch.from_numpy(np.ascontiguousarray(mean_img[r0:r1, r0:r1, :, 0], dtype=np.float64)).cuda()
     spline = baselines.resize_z(hr0, T)
     torch.cuda.synchronize()
