@@ -647,6 +647,7 @@ int64_t inr_wire_param_count(const inr_wire_desc_t* desc);                   /* 
 /* offsets[4 l + {0, 1, 2, 3}] = linear.weight, linear.bias, scale_orth.weight, scale_orth.bias of layer l <= hidden_layers, then
  * the head's weight and bias: 4 (hidden_layers + 1) + 2 float offsets; max_entries counts them */
 int     inr_wire_param_offsets(const inr_wire_desc_t* desc, int64_t* offsets, int max_entries);
+/* training: 0 = inr_wire_forward, 1 = inr_wire_loss_grad / inr_wire_fit, 2 = inr_wire_forward_stash + inr_wire_input_grad */
 size_t  inr_wire_workspace_bytes(const inr_wire_desc_t* desc, int64_t n, int training);   /* 0 for what is not served */
 /* INRmodel.py:109-120, one ComplexGaborLayer2D.forward.  is_first: x [n][in_features] real, real weights [H][in]; otherwise
  * x [n][2H] = planes [re | im], in_features == out_features == H and interleaved complex weights [H][H][2] / biases [H][2].
@@ -677,6 +678,20 @@ int inr_wire_loss_grad(const inr_wire_desc_t* desc, const float* params, float* 
 int inr_wire_fit(const inr_wire_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x,
                  const float* target, const float* weight, int64_t n, int64_t first_step, int n_steps, double lr, double beta1,
                  double beta2, double eps, float* losses, void* workspace, size_t workspace_bytes, void* stream);
+/* wiretest.ipynb cell 10's PerturbNet branch, `model_output = INR.forward(perturbed_input); loss.backward()` as far as the
+ * network's INPUT (cell 2 leaves its `coords.clone().detach()` commented out, so the gradient flows on through input_mapping into
+ * the PerturbNet): inr_wire_forward_stash gives y[n], bit-equal with inr_wire_forward, and leaves the four stashed quantities per
+ * (row, unit) in the workspace; inr_wire_input_grad turns a caller-given gy[n] = dL/dy into dx [n][in_features] (unpadded) =
+ * dL/dx, through G = gy (w_r, -w_i), the layers' backward epilogues, the input-gradient GEMMs against the transposed images and,
+ * for layer 0, one more against the transposed real image [in][2H].  It runs no forward and forms NO parameter gradient (the
+ * notebook's next inr_optim.zero_grad() discards them), and it CONSUMES the stash: one inr_wire_input_grad per
+ * inr_wire_forward_stash, same desc, params (unchanged in between), n and workspace.  Each row of y and dx depends on its own
+ * row of x and gy only, bit for bit, whatever n.  Refusals as above (n < 1 or n > 65535 * 2048 is INR_E_INVALID).
+ * Workspace: inr_wire_workspace_bytes(desc, n, 2). */
+int inr_wire_forward_stash(const inr_wire_desc_t* desc, const float* params, const float* x, int64_t n, float* y,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int inr_wire_input_grad(const inr_wire_desc_t* desc, const float* params, const float* gy, int64_t n, float* dx,
+                        void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- measurement hooks (bench.py roofline): per-kernel-class HIP-event timing on the launch stream.
  * class ids: 0 = GEMM forward (sine layer), 1 = GEMM input-grad, 2 = GEMM param-grad, 3 = other */

@@ -215,6 +215,8 @@ SIGNATURES = {
                                      C.c_size_t, c_stream]),
     "inr_wire_fit": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int64,
                                C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_wire_forward_stash": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_wire_input_grad": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "inr_prof_enable": (C.c_int, [C.c_int]),
     "inr_prof_reset": (C.c_int, []),
     "inr_prof_read": (C.c_int, [C.c_int, c_i64p, C.POINTER(C.c_double)]),

@@ -160,6 +160,8 @@ int wire_gabor_forward(float* out, float* stash, const float* in, const float* i
                        int64_t n, float omega, float s2, hipStream_t st);
 // G [n][2H] = dZ [n][4H] times the image, read through its transpose imgT [2H][4H]
 int wire_input_grad(float* G, const float* dZ, const float* imgT, int H, int64_t n, hipStream_t st);
+// dx [n][in_f] (unpadded, any in_f) = dZ0 [n][2H] times the real layer-0 image, read through its transpose imgT0 [in_f][2H]
+int wire_first_input_grad(float* dx, const float* dZ0, const float* imgT0, int in_f, int H, int64_t n, hipStream_t st);
 // slabs [splits][R][C] = per-split dZ^T X and bslab [splits][R] = per-split column sums of dZ (dZ [n][R], X [n][C])
 int wire_param_grad_slabs(float* slabs, float* bslab, const float* dZ, int R, const float* X, int C, int64_t n, hipStream_t st);
 

@@ -8,7 +8,9 @@
 //   wire_gemm_kernel<Q, GABOR> -- forward layer: a block owns 64 rows x 64 units of ALL Q quantities, a wave 32 x 32 of them, so
 //       lin_r, lin_i, orth_r, orth_i of one (row, unit) sit in registers together:  A = exp(-w lin_i - s^2 (lin_r^2 + lin_i^2 +
 //       orth_r^2 + orth_i^2)) as ONE exponential, out = A (cos, sin)(w lin_r).  Training also stashes the four quantities.
-//   wire_gemm_kernel<1, STORE> -- input gradient [d hr | d hi] = dZ [n][4H] times the image (read through its transpose)
+//   wire_gemm_kernel<1, STORE> -- input gradient [d hr | d hi] = dZ [n][4H] times the image (read through its transpose); with
+//       the transposed layer-0 image (wire_pack_first_t_kernel) also dx [n][in] = dZ0 [n][2H] times it: the gradient with
+//       respect to the network's real input (wiretest.ipynb cell 10's PerturbNet branch), any in_features, unpadded
 //   wire_bwd_kernel            -- G, stash, out -> dZ (in place over the stash)
 //   wire_pgrad_kernel          -- image gradient dZ^T [hr | hi], rows split into slabs of WIRE_SLAB_ROWS, one slab per split
 //   wire_colsum_kernel         -- per-slab column sums (bias gradients; with a row weight the head's weight gradient)
@@ -31,6 +33,10 @@ constexpr int WIRE_THREADS = 256;
 constexpr int WIRE_MAX_LAYERS = 9;          // 1 + hidden_layers
 constexpr int64_t WIRE_MAX_ROWS = (1ll << 31) - 256;
 constexpr int WIRE_SLAB_ROWS = 2048;       // rows per parameter-gradient slab: more rows than this split the sum
+// (a slab per WIRE_SLAB_ROWS rows rides on a grid's y / z axis, which ends at 65,535; the input-gradient mode keeps the limit)
+constexpr int64_t WIRE_MAX_STASH_ROWS = 65535ll * WIRE_SLAB_ROWS;
+
+enum { WIRE_WS_INFER = 0, WIRE_WS_TRAIN = 1, WIRE_WS_INPUT_GRAD = 2 };     // inr_wire_workspace_bytes' third argument
 
 enum { WIRE_EPI_GABOR = 0, WIRE_EPI_STORE = 1 };
 
@@ -58,6 +64,15 @@ __global__ void __launch_bounds__(256) wire_pack_first_kernel(float* __restrict_
         pb[j] = lb[j];
         pb[H + j] = ob[j];
     }
+}
+
+// layer 0 transposed, for the gradient with respect to the network's input: imgT [in][2H], row k = [lw[:, k] | ow[:, k]]
+__global__ void __launch_bounds__(256) wire_pack_first_t_kernel(float* __restrict__ imgT, const float* __restrict__ lw,
+                                                                const float* __restrict__ ow, int H, int in_f) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= in_f * 2 * H) return;
+    const int k = t / (2 * H), c = t - k * (2 * H);
+    imgT[t] = c < H ? lw[c * in_f + k] : ow[(c - H) * in_f + k];
 }
 
 // complex layer: img [4][H][2H], imgT (nullable: training only) [2H][4H] = its transpose as a [4H][2H] matrix, pb [4][H]
@@ -89,7 +104,8 @@ __global__ void __launch_bounds__(256) wire_pack_complex_kernel(float* __restric
 
 // ---- C[n][.] = A [n][K] (K a multiple of WIRE_KB, 16-byte aligned rows) times Q planes B_q [ncols][K], both K-contiguous.
 // GABOR: the layer epilogue on the Q quantities of a (row, unit); out [n][2 ncols], stash (nullable) [n][Q ncols].
-// STORE (Q = 1): out [n][ncols] = the product.
+// STORE (Q = 1): out [n][ncols] = the product, unpadded; ncols is arbitrary here (the tile load and the store guard the column
+// per lane), which is what lets the layer-0 input gradient write dx [n][in_features] for any in_features.
 template <int Q, int EPI>
 __global__ void __launch_bounds__(WIRE_THREADS) wire_gemm_kernel(float* __restrict__ out, float* __restrict__ stash,
                                                                  const float* __restrict__ A, const float* __restrict__ B,
@@ -143,7 +159,7 @@ __global__ void __launch_bounds__(WIRE_THREADS) wire_gemm_kernel(float* __restri
     }
 
     const int col = col0 + wc * 32 + l32;
-    if (col >= ncols) return;     // uniform over the wave: ncols is a multiple of 32
+    if (col >= ncols) return;     // per lane (no barrier follows); GABOR callers pass a multiple of 32: uniform over the wave there
     if (EPI == WIRE_EPI_STORE) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -425,15 +441,16 @@ int wire_splits(int64_t n) { return (int)((n + WIRE_SLAB_ROWS - 1) / WIRE_SLAB_R
 // what a workspace holds: bump allocation in floats, every region on a 256-byte boundary.  base == null: sizes only.
 struct WireView {
     float* x0 = nullptr;
-    float *img[WIRE_MAX_LAYERS], *imgT[WIRE_MAX_LAYERS], *pb[WIRE_MAX_LAYERS];
+    float *img[WIRE_MAX_LAYERS], *imgT[WIRE_MAX_LAYERS], *pb[WIRE_MAX_LAYERS];     // imgT[0]: WIRE_WS_INPUT_GRAD only
     float *act[WIRE_MAX_LAYERS], *Z[WIRE_MAX_LAYERS];     // inference: act[0], act[1] ping-pong, no Z
     float *G = nullptr, *y = nullptr, *gy = nullptr, *mse_part = nullptr, *loss_sink = nullptr;
     float *slabs = nullptr, *bslab = nullptr, *hslab = nullptr, *gslab = nullptr;
     size_t total = 0;
 };
 
-WireView wire_view(const WirePlan& p, int64_t n, bool training, void* base) {
+WireView wire_view(const WirePlan& p, int64_t n, int mode, void* base) {
     WireView v;
+    const bool training = mode != WIRE_WS_INFER;
     size_t at = 0;
     auto take = [&](size_t floats) {
         float* ptr = base ? (float*)base + at : nullptr;
@@ -444,7 +461,10 @@ WireView wire_view(const WirePlan& p, int64_t n, bool training, void* base) {
     v.x0 = take(N * p.K0);
     for (int l = 0; l <= p.L; ++l) {
         v.img[l] = take(l == 0 ? 2 * H * p.K0 : 8 * H * H);
-        v.imgT[l] = (l > 0 && training) ? take(8 * H * H) : nullptr;
+        if (l == 0)
+            v.imgT[l] = mode == WIRE_WS_INPUT_GRAD ? take((size_t)p.in_f * 2 * H) : nullptr;
+        else
+            v.imgT[l] = training ? take(8 * H * H) : nullptr;
         v.pb[l] = take(4 * H);
     }
     if (!training) {
@@ -455,9 +475,13 @@ WireView wire_view(const WirePlan& p, int64_t n, bool training, void* base) {
             v.act[l] = take(N * 2 * H);
             v.Z[l] = take(N * (l == 0 ? 2 : 4) * H);
         }
+        v.G = take(N * 2 * H);
+        if (mode == WIRE_WS_INPUT_GRAD) {       // no loss, no parameter gradients: y and gy are the caller's
+            v.total = at * sizeof(float);
+            return v;
+        }
         const size_t S = (size_t)wire_splits(n);
         const size_t img_max = p.L > 0 && 8 * H * H > 2 * H * p.K0 ? 8 * H * H : 2 * H * p.K0;
-        v.G = take(N * 2 * H);
         v.y = take(N);
         v.gy = take(N);
         v.mse_part = take((size_t)mse_blocks(n > 0 ? n : 1));
@@ -473,6 +497,11 @@ WireView wire_view(const WirePlan& p, int64_t n, bool training, void* base) {
 
 int wire_pack(const WirePlan& p, const WireView& v, const float* params, bool training, hipStream_t st) {
     const int H = p.H;
+    if (v.imgT[0]) {
+        hipLaunchKernelGGL(wire_pack_first_t_kernel, dim3(wire_blocks((long long)p.in_f * 2 * H)), dim3(256), 0, st, v.imgT[0],
+                           params + p.off[0], params + p.off[2], H, p.in_f);
+        INR_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(wire_pack_first_kernel, dim3(wire_blocks((long long)H * p.K0)), dim3(256), 0, st, v.img[0], v.pb[0],
                        params + p.off[0], params + p.off[1], params + p.off[2], params + p.off[3], H, p.in_f, p.K0);
     INR_LAUNCH_CHECK();
@@ -505,6 +534,14 @@ int wire_input_grad(float* G, const float* dZ, const float* imgT, int H, int64_t
     const dim3 grid((unsigned)((n + WIRE_BM - 1) / WIRE_BM), (unsigned)(2 * H / WIRE_BN));
     hipLaunchKernelGGL((wire_gemm_kernel<1, WIRE_EPI_STORE>), grid, dim3(WIRE_THREADS), 0, st, G, (float*)nullptr, dZ, imgT,
                        (const float*)nullptr, 4 * H, 2 * H, (long long)n, 0.f, 0.f);
+    INR_LAUNCH_CHECK();
+    return 0;
+}
+
+int wire_first_input_grad(float* dx, const float* dZ0, const float* imgT0, int in_f, int H, int64_t n, hipStream_t st) {
+    const dim3 grid((unsigned)((n + WIRE_BM - 1) / WIRE_BM), (unsigned)((in_f + WIRE_BN - 1) / WIRE_BN));
+    hipLaunchKernelGGL((wire_gemm_kernel<1, WIRE_EPI_STORE>), grid, dim3(WIRE_THREADS), 0, st, dx, (float*)nullptr, dZ0, imgT0,
+                       (const float*)nullptr, 2 * H, in_f, (long long)n, 0.f, 0.f);
     INR_LAUNCH_CHECK();
     return 0;
 }
@@ -600,13 +637,25 @@ int wire_check_train(const char* who, const inr_wire_desc_t* desc, const void* p
                      const void* target, int64_t n, const void* workspace, size_t workspace_bytes) {
     if (int rc = wire_check_desc(who, desc)) return rc;
     INR_REQUIRE(params && grads && x && target, INR_E_INVALID, "%s: null pointer", who);
-    // (a slab per WIRE_SLAB_ROWS rows rides on a grid's y / z axis, which ends at 65,535)
-    INR_REQUIRE(n >= 1 && n <= 65535ll * WIRE_SLAB_ROWS, INR_E_INVALID, "%s: bad row count %lld", who, (long long)n);
-    const size_t need = wire_view(wire_plan(desc), n, true, nullptr).total;
+    INR_REQUIRE(n >= 1 && n <= WIRE_MAX_STASH_ROWS, INR_E_INVALID, "%s: bad row count %lld", who, (long long)n);
+    const size_t need = wire_view(wire_plan(desc), n, WIRE_WS_TRAIN, nullptr).total;
     INR_REQUIRE(workspace && workspace_bytes >= need, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
                 workspace ? workspace_bytes : (size_t)0, need);
     INR_REQUIRE(aligned16(params) && aligned16(grads) && aligned16(workspace), INR_E_ALIGN,
                 "%s: params, grads and workspace must be 16-byte aligned", who);
+    return 0;
+}
+
+// the two halves of the input gradient share their refusals: `a`, `b` are the call's two row arrays
+int wire_check_stash(const char* who, const inr_wire_desc_t* desc, const void* params, const void* a, const void* b, int64_t n,
+                     const void* workspace, size_t workspace_bytes) {
+    if (int rc = wire_check_desc(who, desc)) return rc;
+    INR_REQUIRE(params && a && b, INR_E_INVALID, "%s: null pointer", who);
+    INR_REQUIRE(n >= 1 && n <= WIRE_MAX_STASH_ROWS, INR_E_INVALID, "%s: bad row count %lld", who, (long long)n);
+    const size_t need = wire_view(wire_plan(desc), n, WIRE_WS_INPUT_GRAD, nullptr).total;
+    INR_REQUIRE(workspace && workspace_bytes >= need, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
+                workspace ? workspace_bytes : (size_t)0, need);
+    INR_REQUIRE(aligned16(params) && aligned16(workspace), INR_E_ALIGN, "%s: params and workspace must be 16-byte aligned", who);
     return 0;
 }
 
@@ -685,11 +734,13 @@ int inr_wire_layer_forward(float* out, const float* x, const float* lin_w, const
 
 size_t inr_wire_workspace_bytes(const inr_wire_desc_t* desc, int64_t n, int training) {
     if (wire_check_desc("inr_wire_workspace_bytes", desc)) return 0;
-    if (n < 1 || n > (training ? 65535ll * WIRE_SLAB_ROWS : WIRE_MAX_ROWS)) {
+    // (any non-zero mode other than the input-gradient one is the training workspace, as before)
+    const int mode = training == WIRE_WS_INPUT_GRAD ? WIRE_WS_INPUT_GRAD : training != 0 ? WIRE_WS_TRAIN : WIRE_WS_INFER;
+    if (n < 1 || n > (mode ? WIRE_MAX_STASH_ROWS : WIRE_MAX_ROWS)) {
         set_error("inr_wire_workspace_bytes: bad row count %lld", (long long)n);
         return 0;
     }
-    return wire_view(wire_plan(desc), n, training != 0, nullptr).total;
+    return wire_view(wire_plan(desc), n, mode, nullptr).total;
 }
 
 // wiretest.ipynb cell 2 `Siren.forward` = nn.Sequential of ComplexGaborLayer2D.forward (INRmodel.py:109-120) + final_linear, .real
@@ -700,7 +751,7 @@ int inr_wire_forward(const inr_wire_desc_t* desc, const float* params, const flo
     INR_REQUIRE(n >= 0 && n <= WIRE_MAX_ROWS, INR_E_INVALID, "inr_wire_forward: bad row count %lld", (long long)n);
     if (n == 0) return 0;
     const WirePlan p = wire_plan(desc);
-    const WireView v = wire_view(p, n, false, workspace);
+    const WireView v = wire_view(p, n, WIRE_WS_INFER, workspace);
     INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "inr_wire_forward: workspace too small (%zu bytes, %zu needed)",
                 workspace ? workspace_bytes : (size_t)0, v.total);
     INR_REQUIRE(aligned16(params) && aligned16(workspace), INR_E_ALIGN, "inr_wire_forward: params and workspace must be 16-byte aligned");
@@ -717,7 +768,7 @@ size_t inr_wire_reconstruct_workspace_bytes(const inr_wire_desc_t* desc, int64_t
         return 0;
     }
     const WirePlan p = wire_plan(desc);
-    return round_up((size_t)chunk_rows * p.in_f * sizeof(float), 256) + wire_view(p, chunk_rows, false, nullptr).total;
+    return round_up((size_t)chunk_rows * p.in_f * sizeof(float), 256) + wire_view(p, chunk_rows, WIRE_WS_INFER, nullptr).total;
 }
 
 // wiretest.ipynb cell 9-10: get_mgrid -> input_mapping -> INR.forward -> torch.clamp(min=0), on chunks of the grid
@@ -742,13 +793,13 @@ int inr_wire_reconstruct(const inr_wire_desc_t* desc, const float* params, const
     }
     const WirePlan p = wire_plan(desc);
     const size_t feat_b = round_up((size_t)chunk_rows * p.in_f * sizeof(float), 256);
-    const size_t need = feat_b + wire_view(p, chunk_rows, false, nullptr).total;
+    const size_t need = feat_b + wire_view(p, chunk_rows, WIRE_WS_INFER, nullptr).total;
     INR_REQUIRE(workspace && workspace_bytes >= need, INR_E_WORKSPACE, "inr_wire_reconstruct: workspace too small (%zu bytes, %zu needed)",
                 workspace ? workspace_bytes : (size_t)0, need);
     INR_REQUIRE(aligned16(params) && aligned16(workspace), INR_E_ALIGN,
                 "inr_wire_reconstruct: params and workspace must be 16-byte aligned");
     float* feats = (float*)workspace;
-    const WireView v = wire_view(p, chunk_rows, false, (char*)workspace + feat_b);
+    const WireView v = wire_view(p, chunk_rows, WIRE_WS_INFER, (char*)workspace + feat_b);
     hipStream_t st = (hipStream_t)stream;
     if (int rc = wire_pack(p, v, params, false, st)) return rc;
     for (int64_t r0 = 0; r0 < total; r0 += chunk_rows) {
@@ -766,11 +817,50 @@ int inr_wire_loss_grad(const inr_wire_desc_t* desc, const float* params, float* 
                        const float* weight, int64_t n, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = wire_check_train("inr_wire_loss_grad", desc, params, grads, x, target, n, workspace, workspace_bytes)) return rc;
     const WirePlan p = wire_plan(desc);
-    const WireView v = wire_view(p, n, true, workspace);
+    const WireView v = wire_view(p, n, WIRE_WS_TRAIN, workspace);
     hipStream_t st = (hipStream_t)stream;
     INR_HIP(hipMemsetAsync(grads, 0, (size_t)p.total * sizeof(float), st));      // the padding between tensors
     if (int rc = wire_pad_rows(p, v, x, n, st)) return rc;
     return wire_loss_grad_impl(desc, p, v, params, grads, target, weight, n, loss, st);
+}
+
+// wiretest.ipynb cell 10's PerturbNet branch, first half: `model_output = INR.forward(perturbed_input)` with everything the
+// backward needs left in the workspace.  The kernels of inr_wire_loss_grad's forward: y is bit-equal with inr_wire_forward's.
+int inr_wire_forward_stash(const inr_wire_desc_t* desc, const float* params, const float* x, int64_t n, float* y, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    if (int rc = wire_check_stash("inr_wire_forward_stash", desc, params, x, y, n, workspace, workspace_bytes)) return rc;
+    const WirePlan p = wire_plan(desc);
+    const WireView v = wire_view(p, n, WIRE_WS_INPUT_GRAD, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = wire_pack(p, v, params, true, st)) return rc;
+    if (int rc = wire_pad_rows(p, v, x, n, st)) return rc;
+    return wire_forward_layers(desc, p, v, params, n, true, y, 0, 0.f, st);
+}
+
+// ... second half: `loss.backward()` as far as the network's input, dx [n][in_features] = gy[row] dy[row]/dx[row].  Consumes the
+// stash (dZ overwrites it layer by layer): one call per inr_wire_forward_stash.  No forward runs here and no parameter gradient
+// is formed -- the notebook's next inr_optim.zero_grad() would discard it.
+int inr_wire_input_grad(const inr_wire_desc_t* desc, const float* params, const float* gy, int64_t n, float* dx, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    if (int rc = wire_check_stash("inr_wire_input_grad", desc, params, gy, dx, n, workspace, workspace_bytes)) return rc;
+    const WirePlan p = wire_plan(desc);
+    const WireView v = wire_view(p, n, WIRE_WS_INPUT_GRAD, workspace);
+    hipStream_t st = (hipStream_t)stream;
+    const int H = p.H;
+    const long long work = (long long)n * H;
+    hipLaunchKernelGGL(wire_head_backward_kernel, dim3(wire_blocks(work)), dim3(256), 0, st, v.G, gy, params + p.off[4 * (p.L + 1)],
+                       H, (long long)n);
+    INR_LAUNCH_CHECK();
+    for (int l = p.L; l > 0; --l) {
+        hipLaunchKernelGGL(wire_bwd_kernel<4>, dim3(wire_blocks(work)), dim3(256), 0, st, v.Z[l], v.G, v.act[l], H, (long long)n,
+                           desc->hidden_omega, desc->hidden_scale * desc->hidden_scale);
+        INR_LAUNCH_CHECK();
+        if (int rc = wire_input_grad(v.G, v.Z[l], v.imgT[l], H, n, st)) return rc;
+    }
+    hipLaunchKernelGGL(wire_bwd_kernel<2>, dim3(wire_blocks(work)), dim3(256), 0, st, v.Z[0], v.G, v.act[0], H, (long long)n,
+                       desc->first_omega, desc->first_scale * desc->first_scale);
+    INR_LAUNCH_CHECK();
+    return wire_first_input_grad(dx, v.Z[0], v.imgT[0], p.in_f, H, n, st);
 }
 
 // wiretest.ipynb cell 10: the `ctr < number_of_epochs - pertubation_epochs` branch (forward, MSE, zero_grad, backward,
@@ -785,7 +875,7 @@ int inr_wire_fit(const inr_wire_desc_t* desc, float* params, float* grads, float
     INR_REQUIRE(aligned16(m) && aligned16(v_), INR_E_ALIGN, "inr_wire_fit: m and v must be 16-byte aligned");
     if (n_steps == 0) return 0;
     const WirePlan p = wire_plan(desc);
-    const WireView v = wire_view(p, n, true, workspace);
+    const WireView v = wire_view(p, n, WIRE_WS_TRAIN, workspace);
     hipStream_t st = (hipStream_t)stream;
     INR_HIP(hipMemsetAsync(grads, 0, (size_t)p.total * sizeof(float), st));
     if (int rc = wire_pad_rows(p, v, x, n, st)) return rc;

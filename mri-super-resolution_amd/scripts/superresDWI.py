@@ -30,8 +30,10 @@ Two optional products of the same fit (default off, so a plain run writes exactl
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
-``--transverse_length`` and ``--adc`` go through ``wire.reconstruct``.  The PerturbNet phase and ``--derivative_maps`` have no
-WIRE kernels and are refused before the fit.  The default ``--model siren`` is the path described above, unchanged.
+``--transverse_length`` and ``--adc`` go through ``wire.reconstruct``.  ``--derivative_maps`` has no WIRE kernels and is refused
+before the fit, and so is the PerturbNet phase HERE: the notebook's whole loop, PerturbNet tail included, is
+``scripts/wiretest.py`` (same flags, the notebook's defaults, built from this module's functions).  The default
+``--model siren`` is the path described above, unchanged.
 R = roi_end - roi_start.  Plots (superresDWI.py:164-233) are outside the build's scope.
 """
 from __future__ import annotations
@@ -127,10 +129,13 @@ def load_input_and_scale(path, key=None, refuse_acquisitions=None):
     return vol, None, bvals, None, per_b_max
 
 
-def run_patient(path, pt_id, args):
+def run_patient(path, pt_id, args, check_model=None, fit=None):
+    """One patient.  ``check_model`` / ``fit``: another driver's refusals and fit on this driver's loading, re-sampling and
+    outputs (``scripts/wiretest.py``); ``fit(args, INR, B, mean_dataset, model_input, target, acq_lr)`` returns the losses and
+    what it adds to ``metrics.json`` (``acq_lr``: the K low-resolution acquisition products, None for a plain volume)."""
     out_dir = os.path.join(args.output_address, f"pat{pt_id}")
     os.makedirs(out_dir, exist_ok=True)
-    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, _check_model(args))
+    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, (check_model or _check_model)(args))
     r0, r1 = args.roi_start, args.roi_end
     if r1 > min(mean_img.shape[:2]) or r0 < 0 or r1 - r0 < 14:
         raise ValueError(f"ROI {r0}:{r1} does not fit the {mean_img.shape[:2]} slices (SSIM needs >= 7 x 7 LR pixels)")
@@ -156,7 +161,11 @@ def run_patient(path, pt_id, args):
     target = mean_dataset.pixels[0]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    if args.model == "wire":                                  # the plain fit on the mean image (wiretest.ipynb cell 10)
+    fit_summary = {}
+    if fit is not None:
+        acq_lr = None if acq is None else [acq[r0:r1:2, r0:r1:2, :, :, k] for k in range(acq.shape[-1])]
+        losses, fit_summary = fit(args, INR, B, mean_dataset, model_input, target, acq_lr)
+    elif args.model == "wire":                                # the plain fit on the mean image (wiretest.ipynb cell 10)
         fitter, losses = wire.fit_wire(INR, model_input, target, args.number_of_epochs, lr=args.learning_rate)
     elif acq is None:
         fitter, losses = inr.fit_siren(INR, model_input, target, args.number_of_epochs, lr=args.learning_rate)
@@ -199,6 +208,7 @@ def run_patient(path, pt_id, args):
         "psnr_spline_db": float(metrics.psnr(hs, sp, 1.0)),
         "ssim_sr_mean": float(ssim_sr[okn].mean()), "ssim_spline_mean": float(ssim_spline[okn].mean()),
     }
+    summary.update(fit_summary)
     if args.transverse_length:
         coronal, summary["t_coronal_s"] = _coronal(INR, B, mean_img, test_shape, args, reconstruct)
         matio.savemat(os.path.join(out_dir, "coronal.mat"), coronal)
@@ -224,6 +234,17 @@ def _check_model(args):
     Returns the reason for which an input with single acquisitions is to be refused (None: it is served)."""
     if args.model != "wire":
         return None
+    _check_wire(args)
+    if args.pertubation_epochs > 0:
+        return ("holds single acquisitions, and --pertubation_epochs > 0 asks for the PerturbNet phase: it needs the "
+                "network's input gradient through the Fourier map, which this driver does not run for --model wire "
+                "(scripts/wiretest.py, the notebook's own loop, does); "
+                "pass --pertubation_epochs 0 to fit the mean image only")
+    return None
+
+
+def _check_wire(args):
+    """The outputs and shapes no WIRE kernel serves (also ``scripts/wiretest.py``'s refusals)."""
     if args.derivative_maps:
         raise ValueError("--derivative_maps needs the forward-mode derivative kernels, which exist for the SIREN only: "
                          "there are no derivative maps of a WIRE network (--model wire)")
@@ -232,11 +253,6 @@ def _check_model(args):
         raise ValueError(f"--model wire serves hidden_dim // 2 in {wire.HIDDEN_SIZES}, num_layers <= {wire.MAX_HIDDEN_LAYERS} "
                          f"and 2 * mapping_size <= {wire.MAX_IN_FEATURES} (got hidden_dim {args.hidden_dim}, num_layers "
                          f"{args.num_layers}, mapping_size {args.mapping_size})")
-    if args.pertubation_epochs > 0:
-        return ("holds single acquisitions, and --pertubation_epochs > 0 asks for the PerturbNet phase: it needs the "
-                "network's input gradient through the Fourier map, which the WIRE kernels do not compute (--model wire); "
-                "pass --pertubation_epochs 0 to fit the mean image only")
-    return None
 
 
 def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
@@ -297,12 +313,14 @@ SUMMARY_KEYS = ("job", "n_coords", "steps", "t_fit_s", "t_recon_s", "train_voxel
                 "psnr_spline_db", "ssim_sr_mean", "ssim_spline_mean")
 
 
-def main(argv=None):
-    """The patient loop (superresDWI.py:29).  Under ``torchrun`` (one process per GPU, WORLD_SIZE > 1) the patients are dealt
+def main(argv=None, parser=None, run=None):
+    """``parser`` / ``run``: another driver's flags and per-patient function on this loop (``scripts/wiretest.py``).
+    The patient loop (superresDWI.py:29).  Under ``torchrun`` (one process per GPU, WORLD_SIZE > 1) the patients are dealt
     over the ranks -- longest first by file size, the same deterministic ``dist.partition_fits`` schedule on every rank, no
     data-path collective --, every rank writes the outputs of its own patients, and ONE all_gather (RCCL) hands every rank
     the numeric summaries of all of them (rank 0 prints the list)."""
-    args = build_parser().parse_args(argv)
+    args = (parser or build_parser()).parse_args(argv)
+    run_patient = run or globals()["run_patient"]
     ids = args.pt_id if args.pt_id else [_patient_id(p) for p in args.data]
     if len(ids) != len(args.data):
         raise SystemExit("--pt_id needs one id per --data file")

@@ -7,11 +7,13 @@ gives ``exp(1j * omega_0 * lin) * exp(-scale_0**2 * (|lin|**2 + |orth|**2))``; t
 in real arithmetic.  Constructor signatures, RNG draw order, parameter names and ``state_dict()`` keys are the
 reference's; initialisation is ``nn.Linear``'s default (the reference defines an ``init_weights`` it never calls).
 
-``forward`` runs the inference kernels and carries no autograd graph: training goes through ``WireFitter``, which makes the
+``forward`` runs the inference kernels and carries no parameter gradients: training goes through ``WireFitter``, which makes the
 parameters live views of one flat fp32 buffer (a complex tensor is its interleaved ``(re, im)`` pairs) and runs forward, MSE,
-backward and Adam of many steps in one C call.  There is no CPU path and no layer-by-layer fallback: ``out_features == 1``,
-``hidden_features in {32, 64, 128, 256}``, ``hidden_layers <= 8``, ``in_features <= 1024``, ``trainable=False``; anything else
-raises.
+backward and Adam of many steps in one C call.  An input that requires grad gets the gradient with respect to ITSELF
+(``inr_wire_forward_stash`` / ``inr_wire_input_grad``): the notebook's network does not detach its input (cell 2), and cell
+10's PerturbNet phase -- ``drivers.fit_wire_with_perturbnet`` -- trains the PerturbNet through it.  There is no CPU path and
+no layer-by-layer fallback: ``out_features == 1``, ``hidden_features in {32, 64, 128, 256}``, ``hidden_layers <= 8``,
+``in_features <= 1024``, ``trainable=False``; anything else raises.
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ from torch import nn
 
 from . import ops
 from ._lib import WireDesc, check, lib, shape_array
-from .flat import AdamOwner, AdamState, FlatParams, Workspace
+from .flat import AdamOwner, AdamState, FlatParams, Workspace, WorkspacePool
 
 HIDDEN_SIZES = (32, 64, 128, 256)
 MAX_HIDDEN_LAYERS = 8
@@ -102,11 +104,52 @@ def wire_param_layout(desc):
     return ops.param_layout(lib().inr_wire_param_count, lib().inr_wire_param_offsets, desc, 4 * (desc.hidden_layers + 1) + 2)
 
 
+WS_INFER, WS_TRAIN, WS_INPUT_GRAD = 0, 1, 2      # inr_wire_workspace_bytes' third argument (include/inrhip.h)
+
+
+class _WireInputFn(torch.autograd.Function):
+    """``y = Wire(x)`` differentiated with respect to ``x`` ONLY: the forward is ``inr_wire_forward_stash`` (the kernels and bits
+    of ``inr_wire_forward``, with the stash kept), the backward ``inr_wire_input_grad``.  The parameters are not inputs of this
+    function, so their ``.grad`` stay untouched.  The stash workspace is held from the forward to its ONE backward, which
+    consumes it and hands the buffer back to ``pool``."""
+
+    @staticmethod
+    def forward(ctx, x, desc, flat, pool):
+        n = x.shape[0]
+        need = lib().inr_wire_workspace_bytes(C.byref(desc), n, WS_INPUT_GRAD)
+        if need == 0:
+            check(-1, "inr_wire_workspace_bytes")
+        ws, _ = pool.take(need, x.device)
+        y = torch.empty(n, dtype=torch.float32, device=x.device)
+        check(lib().inr_wire_forward_stash(C.byref(desc), flat.data_ptr(), x.data_ptr(), n, y.data_ptr(), ws.data_ptr(), ws.numel(),
+                                           ops._stream()), "inr_wire_forward_stash")
+        ctx.desc, ctx.flat, ctx.pool, ctx.ws, ctx.shape = desc, flat, pool, ws, tuple(x.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        if ctx.ws is None:
+            raise RuntimeError("Wire's input gradient runs ONE backward per forward (its stash workspace went back to the pool after "
+                               "the first): call the model again for a second backward")
+        n, fin = ctx.shape
+        gy = ops._chk(gy.contiguous(), "grad_output")
+        dx = torch.empty((n, fin), dtype=torch.float32, device=gy.device)
+        check(lib().inr_wire_input_grad(C.byref(ctx.desc), ctx.flat.data_ptr(), gy.data_ptr(), n, dx.data_ptr(), ctx.ws.data_ptr(),
+                                        ctx.ws.numel(), ops._stream()), "inr_wire_input_grad")
+        ctx.pool.give_back(ctx.ws)
+        ctx.ws = None
+        return dx, None, None, None
+
+
 class Wire(nn.Module):
     """The network of wiretest.ipynb cell 2 (there named ``Siren``): ``ComplexGaborLayer2D(in, H, is_first=True)``,
     ``hidden_layers`` complex layers, a complex ``final_linear``; ``forward`` returns the real part, ``[..., 1]``.  ``scale`` is
     every layer's ``sigma0``.  ``final_linear`` is registered before ``net`` and is also ``net``'s last module, as in the
-    notebook, so ``state_dict()`` lists the head under both names."""
+    notebook, so ``state_dict()`` lists the head under both names.
+
+    ``forward`` on an input that requires grad is differentiable with respect to that INPUT only (cell 2 does not detach it; the
+    gradient flows on into ``input_mapping`` and the PerturbNet): same kernels, same output bits, ONE backward per forward -- a
+    second raises.  The parameters never receive a ``.grad`` from it; they are trained by ``WireFitter``."""
 
     def __init__(self, in_features, hidden_features, hidden_layers, out_features, first_omega_0=10, hidden_omega_0=30.,
                  scale=10.0):
@@ -114,6 +157,7 @@ class Wire(nn.Module):
         _check_shape(in_features, hidden_features, hidden_layers, out_features)
         self.in_features, self.hidden_features, self.hidden_layers = in_features, hidden_features, hidden_layers
         self.out_features = out_features
+        self._input_grad_pool = WorkspacePool()      # the stash workspace of a forward whose input requires grad, until its backward
         net = [ComplexGaborLayer2D(in_features, hidden_features, omega0=first_omega_0, sigma0=scale, is_first=True,
                                    trainable=False)]
         for _ in range(hidden_layers):
@@ -153,7 +197,9 @@ class Wire(nn.Module):
 
     def forward(self, coords):
         ops.require_gpu()
-        x = ops._chk(coords.detach().reshape(-1, coords.shape[-1]).contiguous(), "coords")
+        wants_grad = coords.requires_grad and torch.is_grad_enabled()
+        x = coords if wants_grad else coords.detach()
+        x = ops._chk(x.reshape(-1, coords.shape[-1]).contiguous(), "coords")
         if x.shape[1] != self.in_features:
             raise ValueError(f"coords must be [..., {self.in_features}], got {tuple(coords.shape)}")
         desc = self.desc()
@@ -161,9 +207,11 @@ class Wire(nn.Module):
         if flat.device != x.device:
             raise ops.InrDeviceError("Wire: move the model to the input's HIP device first (model.cuda())")
         n = x.shape[0]
+        if wants_grad and n:
+            return _WireInputFn.apply(x, desc, flat, self._input_grad_pool).reshape(*coords.shape[:-1], 1)
         y = torch.empty(n, dtype=torch.float32, device=x.device)
         if n:
-            need = lib().inr_wire_workspace_bytes(C.byref(desc), n, 0)
+            need = lib().inr_wire_workspace_bytes(C.byref(desc), n, WS_INFER)
             if need == 0:
                 check(-1, "inr_wire_workspace_bytes")
             ws = ops._ws(need, x.device)
