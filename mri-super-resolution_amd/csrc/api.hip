@@ -81,15 +81,7 @@ static int check_desc(const inr_siren_desc_t* d) {
     return 0;
 }
 
-struct Layout {
-    int n_sine;                      // 1 + hidden_layers
-    std::vector<long long> w_off, b_off;  // per layer, head last (long long: what siren_small.hip and FinalizeSeg take)
-    std::vector<int> fan_in, fan_out;
-    long long total;
-};
-static float layer_omega(const inr_siren_desc_t* d, int l) { return l == 0 ? d->first_omega : d->hidden_omega; }
-
-static Layout make_layout(const inr_siren_desc_t* d) {
+Layout make_layout(const inr_siren_desc_t* d) {
     Layout L;
     L.n_sine = 1 + d->hidden_layers;
     long long off = 0;
@@ -500,19 +492,14 @@ struct InferView {
 };
 static InferView infer_view(const inr_siren_desc_t* d, const Layout& L, int64_t rows, bool with_feats, void* workspace) {
     InferView v;
-    const size_t feats_b = round_up((size_t)rows * d->in_features * sizeof(float), 256);
-    const size_t act_b = round_up((size_t)rows * d->hidden_features * sizeof(float), 256);
-    const size_t act_off = with_feats ? feats_b : 0;
-    const size_t ctx_off = act_off + 2 * act_b;
-    const size_t xhl_off = ctx_off + split_ctx_bytes(L);
-    v.total = xhl_off + feats_b;
+    WsCarver c(workspace, 256);
+    if (with_feats) v.feats = c.take<float>((size_t)rows * d->in_features);
+    for (int k = 0; k < 2; ++k) v.buf[k] = c.take<float>((size_t)rows * d->hidden_features);
+    char* ctx = c.take<char>(split_ctx_bytes(L));
+    v.xhl = c.take<char>((size_t)rows * d->in_features * sizeof(float));
+    v.total = c.bytes();
     if (!workspace) return v;
-    char* base = (char*)workspace;
-    if (with_feats) v.feats = (float*)base;
-    v.buf[0] = (float*)(base + act_off);
-    v.buf[1] = (float*)(base + act_off + act_b);
-    v.ctx = split_ctx(L, base + ctx_off);
-    v.xhl = base + xhl_off;
+    v.ctx = split_ctx(L, ctx);
     v.hp = v.ctx.on && hp_eligible(d, L);
     return v;
 }
@@ -663,15 +650,16 @@ static HpSlabPlan hp_slab_plan(const Layout& L, int64_t n) {
     // layer's epilogue (hp_sine_forward_head) -- the plan reserves for whichever is more
     int64_t hb = hp_head_blocks(n);
     if (hp_row_head_rows(n) > hb) hb = hp_row_head_rows(n);
-    size_t off = 0;
+    WsCarver c(nullptr, 4 * sizeof(float));      // offsets only: the plan is in floats from the slab region
+    auto here = [&] { return c.bytes() / sizeof(float); };
     auto add = [&](long long len, int rows) {
         HpSlabPlan::Seg sg;
         sg.len = len;
         sg.max_rows = rows;
-        sg.slab = off;
-        off += round_up((size_t)rows * (size_t)len, 4);
-        sg.stage1 = off;
-        if (rows > FIN_TALL) off += round_up((size_t)((rows + FIN_GROUP - 1) / FIN_GROUP) * (size_t)len, 4);
+        sg.slab = here();
+        c.take<float>((size_t)rows * (size_t)len);
+        sg.stage1 = here();
+        if (rows > FIN_TALL) c.take<float>((size_t)((rows + FIN_GROUP - 1) / FIN_GROUP) * (size_t)len);
         p.seg.push_back(sg);
     };
     for (int l = 0; l < S; ++l) {
@@ -680,11 +668,11 @@ static HpSlabPlan hp_slab_plan(const Layout& L, int64_t n) {
     }
     add(H, (int)hb);     // W_head: the head step's slab_w
     add(1, (int)hb);     // b_head: its per-block sums of g
-    p.part_loss = off;
-    off += round_up((size_t)hb, 4);
-    p.loss_sink = off;
-    off += 4;
-    p.total = off;
+    p.part_loss = here();
+    c.take<float>((size_t)hb);
+    p.loss_sink = here();
+    c.take<float>(4);
+    p.total = here();
     return p;
 }
 
@@ -707,8 +695,6 @@ struct FitView {
 static FitView fit_view(const inr_siren_desc_t* d, const Layout& L, int64_t n, const float* x, void* workspace) {
     FitView v;
     v.n = n;
-    const size_t act_b = round_up((size_t)n * d->hidden_features * sizeof(float), 256);
-    const size_t out_b = round_up((size_t)n * d->out_features * sizeof(float), 256);
     size_t scratch = head_backward_ws_floats(n, d->hidden_features, d->out_features);
     for (int l = 0; l < L.n_sine; ++l) {
         scratch = max2(scratch, param_grad_ws_floats(n, L.fan_in[l], L.fan_out[l]));
@@ -717,29 +703,28 @@ static FitView fit_view(const inr_siren_desc_t* d, const Layout& L, int64_t n, c
     scratch = max2(scratch, (size_t)mse_blocks((int64_t)n * d->out_features) + 1);
     if (L.n_sine <= HpSlots::MAX_LAYERS && d->out_features == 1)
         scratch = max2(scratch, hp_slab_plan(L, n).total);   // deferred slabs of the HL32 step
-    const size_t y_off = 2 * (size_t)L.n_sine * act_b;
-    const size_t scratch_off = y_off + 2 * out_b;
-    const size_t ctx_off = scratch_off + round_up(scratch * sizeof(float), 256);
-    const size_t xhl_off = ctx_off + split_ctx_bytes(L);
-    v.total = xhl_off + round_up((size_t)n * d->in_features * sizeof(float), 256);
+    WsCarver c(workspace, 256);
+    if (workspace) {
+        v.act.resize(L.n_sine + 1);
+        v.dact.resize(L.n_sine);
+        v.act[0] = const_cast<float*>(x);
+    }
+    for (int k = 0; k < 2 * L.n_sine; ++k) {      // every layer's output, then every layer's dact
+        float* a = c.take<float>((size_t)n * d->hidden_features);
+        if (workspace) (k < L.n_sine ? v.act[k + 1] : v.dact[k - L.n_sine]) = a;
+    }
+    v.y = c.take<float>((size_t)n * d->out_features);
+    v.gy = c.take<float>((size_t)n * d->out_features);
+    v.scratch = c.take<float>(scratch);
+    char* ctx = c.take<char>(split_ctx_bytes(L));
+    v.xhl = c.take<char>((size_t)n * d->in_features * sizeof(float));
+    v.total = c.bytes();
     if (small_path_ok(d, n)) {
         v.total = max2(v.total, round_up(small_workspace_floats(d, n, L.total) * sizeof(float), 256));
         if (small_multi_ok(d, n)) v.total = max2(v.total, round_up(small_multi_workspace_floats(d, n, L.total) * sizeof(float), 256));
     }
     if (!workspace) return v;
-    char* base = (char*)workspace;
-    v.act.resize(L.n_sine + 1);
-    v.dact.resize(L.n_sine);
-    v.act[0] = const_cast<float*>(x);
-    for (int l = 0; l < L.n_sine; ++l) {
-        v.act[l + 1] = (float*)(base + (size_t)l * act_b);
-        v.dact[l] = (float*)(base + (size_t)(L.n_sine + l) * act_b);
-    }
-    v.y = (float*)(base + y_off);
-    v.gy = (float*)(base + y_off + out_b);
-    v.scratch = (float*)(base + scratch_off);
-    v.ctx = split_ctx(L, base + ctx_off);
-    v.xhl = base + xhl_off;
+    v.ctx = split_ctx(L, ctx);
     v.hp = v.ctx.on && hp_eligible(d, L);
     return v;
 }
@@ -1538,10 +1523,7 @@ int inr_rams_forward(const inr_rams_desc_t* desc, const float* params, const flo
                 "inr_rams_forward: bad sizes (B=%d H=%d W=%d)", batch, height, width);
     INR_REQUIRE((long long)(height + 4) * (width + 4) * desc->channels * 32 * 4 < (1ll << 31), INR_E_INVALID,
                 "inr_rams_forward: one image's activations must stay below 2 GiB");
-    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_workspace_bytes(desc, batch, height, width), INR_E_WORKSPACE,
-                "inr_rams_forward: workspace too small");
-    INR_REQUIRE(aligned16(workspace) && aligned16(params), INR_E_ALIGN, "inr_rams_forward: params/workspace alignment");
-    return rams_forward_impl(desc, params, x, out, batch, height, width, clip_round, (float*)workspace,
+    return rams_forward_impl(desc, params, x, out, batch, height, width, clip_round, workspace, workspace_bytes,
                              (hipStream_t)stream);
 }
 
@@ -1610,11 +1592,7 @@ int inr_rams_train_grads(const inr_rams_desc_t* desc, const float* params, float
                          size_t workspace_bytes, void* stream) {
     if (int rc = check_rams_train(desc, batch, height, width)) return rc;
     INR_REQUIRE(params && grads && x && y_true && mask && loss, INR_E_INVALID, "inr_rams_train_grads: null pointer");
-    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_train_workspace_bytes(desc, batch, height, width), INR_E_WORKSPACE,
-                "inr_rams_train_grads: workspace too small");
-    INR_REQUIRE(aligned16(workspace) && aligned16(params) && aligned16(grads), INR_E_ALIGN,
-                "inr_rams_train_grads: params / grads / workspace must be 16-byte aligned");
-    return rams_train_grads(desc, params, grads, x, y_true, mask, loss, pred, batch, height, width, (float*)workspace,
+    return rams_train_grads(desc, params, grads, x, y_true, mask, loss, pred, batch, height, width, workspace, workspace_bytes,
                             (hipStream_t)stream);
 }
 

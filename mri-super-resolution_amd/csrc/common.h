@@ -46,6 +46,22 @@ void set_error(const char* fmt, ...);
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// How every unit hands out its caller-allocated workspace: ONE function `X_view(shape..., base)` per workspace takes the regions
+// in order and returns typed pointers plus the total.  The planner is that function with a null base (`take` returns null and
+// still advances); the entry point calls it once with the real base and checks `workspace_bytes >= total` before its first launch.
+// A region occupies its size rounded up to `align` bytes, the view's granularity.
+struct WsCarver {
+    char* base;
+    size_t align, at = 0;
+    WsCarver(void* base_, size_t align_bytes) : base(static_cast<char*>(base_)), align(align_bytes) {}
+    template <class T> T* take(size_t count) {
+        T* r = base ? reinterpret_cast<T*>(base + at) : nullptr;
+        at += round_up(count * sizeof(T), align);
+        return r;
+    }
+    size_t bytes() const { return at; }
+};
+
 // ---- per-kernel-class event profiler (bench.py roofline) ---------------------------------------
 // gemm_f32.hip and gemm_hp.hip are compiled without packed fp32 VALU instructions (_build.py: SOURCE_FLAGS -- they slow the MFMA kernels' epilogues);
 // kernels with no MFMA beside their VALU work switch them back on.  A no-op in translation units built with the default feature set.

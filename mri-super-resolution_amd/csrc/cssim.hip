@@ -344,50 +344,47 @@ GaussWin gauss_window() {   // tf.image.ssim: filter_size 11, filter_sigma 1.5, 
 
 int tiles_of(int rows, int cols) { return ((rows + TH - 1) / TH) * ((cols + TW - 1) / TW); }
 
-// the workspace in doubles; the per-shift table comes first (callers may read it back)
+// the workspace, carved in doubles with no padding; the per-shift table comes first (callers may read it back).  ws == null: `total` only
 struct CssimPlan {
-    size_t table, bias, tot, partial, inv, aed, gx, gpart, arg, total;
+    double *table, *bias, *tot, *partial, *inv, *aed, *gx, *gpart;
+    int* arg;
+    size_t total;   // doubles
 };
 
-CssimPlan cssim_plan(int nimg, int size, int border, bool grad) {
+CssimPlan cssim_plan(int nimg, int size, int border, bool grad, double* ws) {
     const size_t B = (size_t)(nimg > 0 ? nimg : 1);
     const size_t ns2 = (size_t)(2 * border + 1) * (2 * border + 1);
     const int c = size - 2 * border, n = c - (KW - 1), nf = size - (KW - 1);
     CssimPlan p{};
-    size_t at = 0;
-    auto take = [&](size_t count) {
-        const size_t here = at;
-        at += count;
-        return here;
-    };
-    p.table = take(B * ns2);
-    p.bias = take(B * ns2);
-    p.tot = take(B * ns2);
-    p.partial = take(B * ns2 * (size_t)tiles_of(n, n));
-    p.inv = take(B * 5 * (size_t)nf * nf);
+    WsCarver cv(ws, sizeof(double));
+    p.table = cv.take<double>(B * ns2);
+    p.bias = cv.take<double>(B * ns2);
+    p.tot = cv.take<double>(B * ns2);
+    p.partial = cv.take<double>(B * ns2 * (size_t)tiles_of(n, n));
+    p.inv = cv.take<double>(B * 5 * (size_t)nf * nf);
     if (grad) {
-        p.aed = take(B * 3 * (size_t)n * n);
-        p.gx = take(B * (size_t)c * c);
-        p.gpart = take(B * (size_t)tiles_of(c, c));
-        p.arg = take((B * sizeof(int) + 7) / 8);
+        p.aed = cv.take<double>(B * 3 * (size_t)n * n);
+        p.gx = cv.take<double>(B * (size_t)c * c);
+        p.gpart = cv.take<double>(B * (size_t)tiles_of(c, c));
+        p.arg = cv.take<int>(B);
     }
-    p.total = at;
+    p.total = cv.bytes() / sizeof(double);
     return p;
 }
 
 int cssim_forward(double* out, int* arg, const float* y_true, const float* y_pred, const float* mask, int nimg, int size,
-                  int border, int clear_only, int as_loss, double* ws, const CssimPlan& p, const GaussWin& G, hipStream_t st) {
+                  int border, int clear_only, int as_loss, const CssimPlan& p, const GaussWin& G, hipStream_t st) {
     const int ns = 2 * border + 1, c = size - 2 * border, n = c - (KW - 1), nf = size - (KW - 1);
     const double c1 = (0.01 * 65535.0) * (0.01 * 65535.0), c2 = (0.03 * 65535.0) * (0.03 * 65535.0);
-    hipLaunchKernelGGL(cssim_invariant_kernel, dim3(tiles_of(nf, nf), 1, nimg), dim3(256), 0, st, ws + p.inv, y_true, mask, size, G);
+    hipLaunchKernelGGL(cssim_invariant_kernel, dim3(tiles_of(nf, nf), 1, nimg), dim3(256), 0, st, p.inv, y_true, mask, size, G);
     INR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cssim_bias_kernel, dim3(ns * ns, nimg), dim3(256), 0, st, ws + p.bias, ws + p.tot, y_true, y_pred, mask, size,
+    hipLaunchKernelGGL(cssim_bias_kernel, dim3(ns * ns, nimg), dim3(256), 0, st, p.bias, p.tot, y_true, y_pred, mask, size,
                        border);
     INR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cssim_shift_kernel<false>, dim3(tiles_of(n, n), ns * ns, nimg), dim3(256), 0, st, ws + p.partial, y_true,
-                       y_pred, mask, ws + p.inv, ws + p.bias, (const int*)nullptr, size, border, G, c1, c2);
+    hipLaunchKernelGGL(cssim_shift_kernel<false>, dim3(tiles_of(n, n), ns * ns, nimg), dim3(256), 0, st, p.partial, y_true,
+                       y_pred, mask, p.inv, p.bias, (const int*)nullptr, size, border, G, c1, c2);
     INR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cssim_finish_kernel, dim3(nimg), dim3(64), 0, st, out, arg, ws + p.table, ws + p.partial, ws + p.tot, ns * ns,
+    hipLaunchKernelGGL(cssim_finish_kernel, dim3(nimg), dim3(64), 0, st, out, arg, p.table, p.partial, p.tot, ns * ns,
                        tiles_of(n, n), (double)n * (double)n, (double)c * (double)c, clear_only, as_loss);
     INR_LAUNCH_CHECK();
     return 0;
@@ -397,33 +394,33 @@ int cssim_forward(double* out, int* arg, const float* y_true, const float* y_pre
 
 int cssim_min_crop() { return KW; }
 
-size_t cssim_workspace_doubles(int nimg, int size, int border, bool grad) { return cssim_plan(nimg, size, border, grad).total; }
+size_t cssim_workspace_doubles(int nimg, int size, int border, bool grad) { return cssim_plan(nimg, size, border, grad, nullptr).total; }
 
 int launch_cssim(double* out, const float* y_true, const float* y_pred, const float* mask, int nimg, int size, int border,
                  int clear_only, double* ws, hipStream_t st) {
-    const CssimPlan p = cssim_plan(nimg, size, border, false);
+    const CssimPlan p = cssim_plan(nimg, size, border, false, ws);
     const GaussWin G = gauss_window();
     ProfScope ps(KC_OTHER, st);
-    return cssim_forward(out, nullptr, y_true, y_pred, mask, nimg, size, border, clear_only, 0, ws, p, G, st);
+    return cssim_forward(out, nullptr, y_true, y_pred, mask, nimg, size, border, clear_only, 0, p, G, st);
 }
 
 int launch_cssim_grad(double* loss, float* grad, const float* y_true, const float* y_pred, const float* mask,
                       const float* upstream, int nimg, int size, int border, int clear_only, double* ws, hipStream_t st) {
-    const CssimPlan p = cssim_plan(nimg, size, border, true);
+    const CssimPlan p = cssim_plan(nimg, size, border, true, ws);
     const GaussWin G = gauss_window();
     const int c = size - 2 * border, n = c - (KW - 1);
     const double c1 = (0.01 * 65535.0) * (0.01 * 65535.0), c2 = (0.03 * 65535.0) * (0.03 * 65535.0);
-    int* arg = reinterpret_cast<int*>(ws + p.arg);
+    int* arg = p.arg;
     ProfScope ps(KC_OTHER, st);
-    if (int rc = cssim_forward(loss, arg, y_true, y_pred, mask, nimg, size, border, clear_only, 1, ws, p, G, st)) return rc;
-    hipLaunchKernelGGL(cssim_shift_kernel<true>, dim3(tiles_of(n, n), 1, nimg), dim3(256), 0, st, ws + p.aed, y_true, y_pred, mask,
-                       ws + p.inv, ws + p.bias, arg, size, border, G, c1, c2);
+    if (int rc = cssim_forward(loss, arg, y_true, y_pred, mask, nimg, size, border, clear_only, 1, p, G, st)) return rc;
+    hipLaunchKernelGGL(cssim_shift_kernel<true>, dim3(tiles_of(n, n), 1, nimg), dim3(256), 0, st, p.aed, y_true, y_pred, mask,
+                       p.inv, p.bias, arg, size, border, G, c1, c2);
     INR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cssim_grad_filter_kernel, dim3(tiles_of(c, c), 1, nimg), dim3(256), 0, st, ws + p.gx, ws + p.gpart,
-                       ws + p.aed, y_true, y_pred, mask, ws + p.bias, arg, size, border, G);
+    hipLaunchKernelGGL(cssim_grad_filter_kernel, dim3(tiles_of(c, c), 1, nimg), dim3(256), 0, st, p.gx, p.gpart,
+                       p.aed, y_true, y_pred, mask, p.bias, arg, size, border, G);
     INR_LAUNCH_CHECK();
     const int blocks = (size * size + 255) / 256 < 1024 ? (size * size + 255) / 256 : 1024;
-    hipLaunchKernelGGL(cssim_grad_finish_kernel, dim3(blocks, nimg), dim3(256), 0, st, grad, ws + p.gx, ws + p.gpart, ws + p.tot,
+    hipLaunchKernelGGL(cssim_grad_finish_kernel, dim3(blocks, nimg), dim3(256), 0, st, grad, p.gx, p.gpart, p.tot,
                        mask, arg, upstream, size, border, tiles_of(c, c), (double)n * (double)n, clear_only);
     INR_LAUNCH_CHECK();
     return 0;

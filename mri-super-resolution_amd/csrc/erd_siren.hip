@@ -563,26 +563,20 @@ struct ErdWs {
     float *acts, *dacts, *slabs, *loss_partial, *ymax_partial;
     int* gate;
     int nwaves;
-    size_t floats;
+    size_t bytes;
 };
 
 void erd_carve(const inr_siren_desc_t* d, const ErdLayout& L, int64_t n, void* ws, ErdWs& w) {
     const size_t nh = (size_t)n * d->hidden_features;
     w.nwaves = erd_blocks(n) * ERD_WAVES;
-    float* f = static_cast<float*>(ws);
-    size_t at = 0;
-    auto take = [&](size_t cnt) {
-        float* r = f ? f + at : nullptr;
-        at += (cnt + 3) / 4 * 4;
-        return r;
-    };
-    w.acts = take((size_t)(L.T - 1) * nh);
-    w.dacts = take((size_t)(L.T - 1) * nh);
-    w.slabs = take((size_t)w.nwaves * (size_t)L.P);
-    w.loss_partial = take(w.nwaves);
-    w.ymax_partial = take(w.nwaves);
-    w.gate = reinterpret_cast<int*>(take(4));
-    w.floats = at;
+    WsCarver c(ws, 4 * sizeof(float));
+    w.acts = c.take<float>((size_t)(L.T - 1) * nh);
+    w.dacts = c.take<float>((size_t)(L.T - 1) * nh);
+    w.slabs = c.take<float>((size_t)w.nwaves * (size_t)L.P);
+    w.loss_partial = c.take<float>(w.nwaves);
+    w.ymax_partial = c.take<float>(w.nwaves);
+    w.gate = c.take<int>(4);
+    w.bytes = c.bytes();
 }
 
 struct ErdCall {
@@ -635,13 +629,16 @@ int erd_launch_reduce(const ErdReduce& r, hipStream_t st) {
 
 constexpr int64_t ERD_MAX_ROWS = 1 << 18;
 
-int erd_common_checks(const inr_siren_desc_t* desc, int64_t n, const void* ws, size_t ws_bytes, const char* who) {
+// the refusals the training entry points share; on success L and w hold the call's layout and its workspace view
+int erd_common_checks(const inr_siren_desc_t* desc, int64_t n, void* ws, size_t ws_bytes, const char* who, ErdLayout& L, ErdWs& w) {
     INR_REQUIRE(erd_desc_ok(desc), INR_E_INVALID,
                 "%s: the soft-ERD kernels serve out_features == 1, in_features <= 8, hidden_features in {64, 128}, "
                 "hidden_layers <= 8", who);
     INR_REQUIRE(n >= 1 && n <= ERD_MAX_ROWS, INR_E_INVALID, "%s: n = %lld outside 1 .. %lld", who, (long long)n,
                 (long long)ERD_MAX_ROWS);
-    INR_REQUIRE(ws && aligned16(ws) && ws_bytes >= inr_erd_workspace_bytes(desc, n), INR_E_WORKSPACE, "%s: workspace too small", who);
+    erd_layout(desc, L);
+    erd_carve(desc, L, n, ws, w);
+    INR_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.bytes, INR_E_WORKSPACE, "%s: workspace too small", who);
     return 0;
 }
 
@@ -680,7 +677,7 @@ size_t inr_erd_workspace_bytes(const inr_siren_desc_t* desc, int64_t n) {
     erd_layout(desc, L);
     ErdWs w;
     erd_carve(desc, L, n, nullptr, w);
-    return w.floats * sizeof(float);
+    return w.bytes;
 }
 
 int inr_erd_forward(const inr_siren_desc_t* desc, const float* params, const float* x, int64_t n, float* y, int sample, float eps,
@@ -703,13 +700,11 @@ int inr_erd_forward(const inr_siren_desc_t* desc, const float* params, const flo
 int inr_erd_loss_grad(const inr_siren_desc_t* desc, const float* params, float* grads, const float* x, const float* target,
                       const float* weight, int64_t n, int sample, float eps, int perturb, int accumulate, float* loss,
                       void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = erd_common_checks(desc, n, workspace, workspace_bytes, "inr_erd_loss_grad")) return rc;
+    ErdLayout L;
+    ErdWs w;
+    if (int rc = erd_common_checks(desc, n, workspace, workspace_bytes, "inr_erd_loss_grad", L, w)) return rc;
     INR_REQUIRE(params && grads && x && target && loss, INR_E_INVALID, "inr_erd_loss_grad: null pointer");
     INR_REQUIRE(aligned16(params), INR_E_ALIGN, "inr_erd_loss_grad: params must be 16-byte aligned");
-    ErdLayout L;
-    erd_layout(desc, L);
-    ErdWs w;
-    erd_carve(desc, L, n, workspace, w);
     hipStream_t st = (hipStream_t)stream;
     ErdCall c{target, weight, nullptr, nullptr, (float)sample, eps, perturb != 0, accumulate != 0};
     if (int rc = erd_launch_step<true>(desc, L, w, params, x, n, c, st)) return rc;
@@ -735,14 +730,12 @@ int inr_erd_adam_step(const inr_siren_desc_t* desc, float* params, const float* 
 int inr_erd_pretrain(const inr_siren_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x,
                      const float* target, int64_t n, int64_t first_step, int max_steps, double lr, double beta1, double beta2,
                      double eps, float threshold, int* status, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = erd_common_checks(desc, n, workspace, workspace_bytes, "inr_erd_pretrain")) return rc;
+    ErdLayout L;
+    ErdWs w;
+    if (int rc = erd_common_checks(desc, n, workspace, workspace_bytes, "inr_erd_pretrain", L, w)) return rc;
     INR_REQUIRE(params && grads && m && v && x && target && status && first_step >= 1 && max_steps >= 0, INR_E_INVALID,
                 "inr_erd_pretrain: null pointer or bad step numbers");
     INR_REQUIRE(aligned16(params), INR_E_ALIGN, "inr_erd_pretrain: params must be 16-byte aligned");
-    ErdLayout L;
-    erd_layout(desc, L);
-    ErdWs w;
-    erd_carve(desc, L, n, workspace, w);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(erd_gate_init_kernel, dim3(1), dim3(1), 0, st, w.gate, status);
     INR_LAUNCH_CHECK();
@@ -765,14 +758,12 @@ int inr_erd_finetune(const inr_siren_desc_t* desc, float* params, float* grads, 
                      const float* targets, const float* weights, int n_acq, int64_t n, float perturb_eps, int64_t first_step,
                      int n_steps, double lr_perturb, double lr_net, double beta1, double beta2, double eps, float* losses,
                      void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = erd_common_checks(desc, n, workspace, workspace_bytes, "inr_erd_finetune")) return rc;
+    ErdLayout L;
+    ErdWs w;
+    if (int rc = erd_common_checks(desc, n, workspace, workspace_bytes, "inr_erd_finetune", L, w)) return rc;
     INR_REQUIRE(params && grads && m && v && x && targets && n_acq >= 1 && first_step >= 1 && n_steps >= 0, INR_E_INVALID,
                 "inr_erd_finetune: null pointer or bad counts");
     INR_REQUIRE(aligned16(params), INR_E_ALIGN, "inr_erd_finetune: params must be 16-byte aligned");
-    ErdLayout L;
-    erd_layout(desc, L);
-    ErdWs w;
-    erd_carve(desc, L, n, workspace, w);
     hipStream_t st = (hipStream_t)stream;
     for (int it = 0; it < n_steps; ++it) {
         for (int s = 0; s < n_acq; ++s) {

@@ -3,9 +3,21 @@
 // a declaration that has drifted from its definition fails to compile in the file that is wrong.  Default arguments live here
 // and nowhere else.  (set_error, count_launch, launch_finalize and the profiler hooks are in common.h, beside their types.)
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 namespace inr {
+
+// ---- api.hip: the flat SIREN parameter layout (inr_siren_param_offsets) --------------------------------------------------------------
+struct Layout {
+    int n_sine;                      // 1 + hidden_layers
+    std::vector<long long> w_off, b_off;  // per layer, head last (long long: what siren_small.hip and FinalizeSeg take)
+    std::vector<int> fan_in, fan_out;
+    long long total;
+};
+Layout make_layout(const inr_siren_desc_t* d);
+inline float layer_omega(const inr_siren_desc_t* d, int l) { return l == 0 ? d->first_omega : d->hidden_omega; }
 
 // ---- gemm_f32.hip: fp32 MFMA and split-fp16 (gemm_h3.inc) GEMMs -------------------------------------------------------------------
 int gemm_build_flags();   // inr_build_flags: this unit's diagnostic macros | hp_build_flags()
@@ -169,7 +181,7 @@ int wire_param_grad_slabs(float* slabs, float* bslab, const float* dZ, int R, co
 long long rams_param_floats(const inr_rams_desc_t* d);
 size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W);
 int rams_forward_impl(const inr_rams_desc_t* d, const float* params, const float* x, float* out, int B, int H, int W,
-                      int clip_round, float* ws, hipStream_t st);
+                      int clip_round, void* workspace, size_t workspace_bytes, hipStream_t st);   // checks the workspace itself
 size_t rams_conv3d_wgrad_ws_floats(long long nvox);
 int rams_conv3d_forward(float* y, const float* x, const float* w, const float* bias, int B, int D1, int D2, int D3, int pad,
                         int relu, hipStream_t st);
@@ -182,7 +194,8 @@ long long rams_train_param_floats(const inr_rams_desc_t* d);
 int rams_train_param_offsets(const inr_rams_desc_t* d, int64_t* offsets, int max_layers);
 size_t rams_train_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W);
 int rams_train_grads(const inr_rams_desc_t* d, const float* raw, float* raw_grad, const float* x, const float* y_true,
-                     const float* mask, double* loss, float* pred, int B, int H, int W, float* ws, hipStream_t st);
+                     const float* mask, double* loss, float* pred, int B, int H, int W, void* workspace, size_t workspace_bytes,
+                     hipStream_t st);   // checks the workspace itself, before the first launch
 extern tune_int g_rams_h3, g_rams_force_lds;   // key 14 (bits 0-1, bit 2)
 extern tune_int g_rams_lds_waves;              // key 15
 extern tune_int g_rams_epi_fuse;               // key 24

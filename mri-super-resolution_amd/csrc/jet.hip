@@ -257,7 +257,7 @@ struct JetPlan {
     int d = 0, H = 0, S = 0;              // coordinate axes, hidden width, sine layers
     int pitch0 = 0;                       // Fourier features: 2m rounded up to JET_KB; raw coordinates: 0
     int max_pitch = 0;
-    std::vector<long long> w_off, b_off;  // the flat layout of inr_siren_param_offsets, head last
+    Layout L;                             // the flat layout of inr_siren_param_offsets, head last
 };
 
 int jet_check_desc(const char* who, const inr_siren_desc_t* d, int dims, int m, bool fourier) {
@@ -283,20 +283,18 @@ JetPlan jet_plan(const inr_siren_desc_t* d, int dims, bool fourier) {
     p.S = 1 + d->hidden_layers;
     p.pitch0 = fourier ? (int)round_up((size_t)d->in_features, JET_KB) : 0;
     p.max_pitch = p.pitch0 > p.H ? p.pitch0 : p.H;
-    long long off = 0;
-    for (int l = 0; l <= p.S; ++l) {
-        const int fin = l == 0 ? d->in_features : p.H;
-        const int fout = l == p.S ? d->out_features : p.H;
-        p.w_off.push_back(off);
-        off += (long long)round_up((size_t)fin * fout, 4);
-        p.b_off.push_back(off);
-        off += (long long)round_up((size_t)fout, 4);
-    }
+    p.L = make_layout(d);
     return p;
 }
 
-size_t jet_buffer_bytes(const JetPlan& p, int J, int64_t chunk) {
-    return round_up((size_t)J * (size_t)chunk * (size_t)p.max_pitch * sizeof(float), 256);
+// the workspace: two buffers of J planes [chunk][max_pitch] that the layers write in turn.  base == null: `total` only
+struct JetView { float* buf[2]; size_t total; };
+JetView jet_view(const JetPlan& p, int J, int64_t chunk, void* base) {
+    JetView v;
+    WsCarver c(base, 256);
+    for (int k = 0; k < 2; ++k) v.buf[k] = c.take<float>((size_t)J * (size_t)chunk * (size_t)p.max_pitch);
+    v.total = c.bytes();
+    return v;
 }
 
 template <int J, bool LAP>
@@ -350,13 +348,13 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
     const int has_q = lap ? 1 : 0;
     const int J = 1 + dt + has_q;
     const int64_t chunk = chunk_rows < n ? chunk_rows : n;
-    const size_t buf_b = jet_buffer_bytes(p, J, chunk);
-    INR_REQUIRE(workspace && workspace_bytes >= 2 * buf_b, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
-                workspace ? workspace_bytes : (size_t)0, 2 * buf_b);
+    const JetView v = jet_view(p, J, chunk, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
+                workspace ? workspace_bytes : (size_t)0, v.total);
     INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
 
     hipStream_t st = (hipStream_t)stream;
-    float* buf[2] = {(float*)workspace, (float*)((char*)workspace + buf_b)};
+    float* const* buf = v.buf;
     JetGrid g;
     for (int a = 0; a < JET_MAX_D; ++a) g.n[a] = (shape && a < d) ? shape[a] : 1;
     const int H = p.H;
@@ -379,10 +377,10 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
             const long long work = rows * H;
             if (x)
                 hipLaunchKernelGGL(jet_first_kernel<false>, dim3(jet_blocks(work)), dim3(256), 0, st, buf[0], plane, xc, g, d, dt,
-                                   has_q, (long long)r0, rows, params + p.w_off[0], params + p.b_off[0], H, desc->first_omega);
+                                   has_q, (long long)r0, rows, params + p.L.w_off[0], params + p.L.b_off[0], H, desc->first_omega);
             else
                 hipLaunchKernelGGL(jet_first_kernel<true>, dim3(jet_blocks(work)), dim3(256), 0, st, buf[0], plane, xc, g, d, dt,
-                                   has_q, (long long)r0, rows, params + p.w_off[0], params + p.b_off[0], H, desc->first_omega);
+                                   has_q, (long long)r0, rows, params + p.L.w_off[0], params + p.L.b_off[0], H, desc->first_omega);
             first_gemm = 1;
         }
         INR_LAUNCH_CHECK();
@@ -391,13 +389,12 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
             const int K = l == 0 ? desc->in_features : H;
             const int lda = l == 0 ? p.pitch0 : H;
             if (int rc = jet_launch_layer(dt, has_q, st, buf[cur ^ 1], (long long)chunk * H, buf[cur], (long long)chunk * lda, lda,
-                                          params + p.w_off[l], params + p.b_off[l], K, H, rows, l == 0 ? desc->first_omega
-                                                                                                      : desc->hidden_omega))
+                                          params + p.L.w_off[l], params + p.L.b_off[l], K, H, rows, layer_omega(desc, l)))
                 return rc;
             cur ^= 1;
         }
         hipLaunchKernelGGL(jet_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, y + r0, grad ? grad + r0 * dt : nullptr,
-                           lap ? lap + r0 : nullptr, buf[cur], (long long)chunk * H, params + p.w_off[p.S], params + p.b_off[p.S], H,
+                           lap ? lap + r0 : nullptr, buf[cur], (long long)chunk * H, params + p.L.w_off[p.S], params + p.L.b_off[p.S], H,
                            dt, has_q, rows);
         INR_LAUNCH_CHECK();
         count_launch(LF_JET_BASE + INR_JET_LF_HEAD);
@@ -415,7 +412,7 @@ extern "C" {
 size_t inr_siren_jet_workspace_bytes(const inr_siren_desc_t* desc, int d, int m, int64_t chunk_rows, int want_laplacian) {
     if (chunk_rows < 1 || chunk_rows > JET_MAX_ROWS) return 0;
     if (jet_check_desc("inr_siren_jet_workspace_bytes", desc, d, m, m > 0)) return 0;
-    return 2 * jet_buffer_bytes(jet_plan(desc, d, m > 0), 1 + d + (want_laplacian ? 1 : 0), chunk_rows);
+    return jet_view(jet_plan(desc, d, m > 0), 1 + d + (want_laplacian ? 1 : 0), chunk_rows, nullptr).total;
 }
 
 int inr_siren_jet(const inr_siren_desc_t* desc, const float* params, const float* x, int64_t n, int d, int d_tangent, const float* B,

@@ -513,17 +513,6 @@ inline long long pia_head_waves_fwd(long long n) {
     return (w + 3) / 4 * 4;
 }
 
-struct Carver {
-    char* base;
-    size_t at = 0;
-    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-    float* take(long long floats) {
-        float* r = base ? reinterpret_cast<float*>(base + at) : nullptr;
-        at += round_up((size_t)floats * sizeof(float), 256);
-        return r;
-    }
-};
-
 // the training workspace: every activation, the gradient buffers and every slab of a step
 struct PiaTrainWs {
     float* act[8];
@@ -542,26 +531,39 @@ struct PiaTrainWs {
 };
 
 void pia_train_ws(const PiaShape& s, long long n, void* base, PiaTrainWs& w) {
-    Carver c(base);
+    WsCarver c(base, 256);
     int maxw = s.in[0];
     for (int l = 0; l < s.L; ++l) {
-        w.act[l] = c.take(n * s.out[l]);
+        w.act[l] = c.take<float>(n * s.out[l]);
         if (s.out[l] > maxw) maxw = s.out[l];
     }
-    for (int j = 0; j < 3; ++j) w.h[j] = c.take(n * s.H);
-    for (int j = 0; j < 3; ++j) w.dzh[j] = c.take(n * s.H);
-    for (int k = 0; k < 2; ++k) w.dz[k] = c.take(n * maxw);
+    for (int j = 0; j < 3; ++j) w.h[j] = c.take<float>(n * s.H);
+    for (int j = 0; j < 3; ++j) w.dzh[j] = c.take<float>(n * s.H);
+    for (int k = 0; k < 2; ++k) w.dz[k] = c.take<float>(n * maxw);
     for (int l = 0; l < s.L; ++l) {
         w.enc_splits[l] = pia_dw_splits(n, s.out[l], s.in[l], 1);
-        w.enc_slab[l] = c.take((long long)w.enc_splits[l] * ((long long)s.out[l] * s.in[l] + s.out[l]));
+        w.enc_slab[l] = c.take<float>((long long)w.enc_splits[l] * ((long long)s.out[l] * s.in[l] + s.out[l]));
     }
     w.head_splits = pia_dw_splits(n, s.H, s.H, 3);
-    w.head_slab = c.take(3ll * w.head_splits * ((long long)s.H * s.H + s.H));
+    w.head_slab = c.take<float>(3ll * w.head_splits * ((long long)s.H * s.H + s.H));
     w.waves = pia_head_waves(n);
-    w.out_slab = c.take(3 * w.waves * (3ll * s.H + 3));
-    w.out_stage1 = c.take(3 * ((w.waves + FIN_GROUP - 1) / FIN_GROUP) * (3ll * s.H + 3));
-    w.part_loss = c.take(w.waves);
-    w.bytes = c.at;
+    w.out_slab = c.take<float>(3 * w.waves * (3ll * s.H + 3));
+    w.out_stage1 = c.take<float>(3 * ((w.waves + FIN_GROUP - 1) / FIN_GROUP) * (3ll * s.H + 3));
+    w.part_loss = c.take<float>(w.waves);
+    w.bytes = c.bytes();
+}
+
+// the forward-only workspace of one chunk: two ping-pong encoder buffers and the three head hidden activations
+struct PiaFwdWs { float *pp[2], *h[3]; size_t bytes; };
+PiaFwdWs pia_fwd_ws(const PiaShape& s, long long rows, void* base) {
+    PiaFwdWs w;
+    int maxw = 0;
+    for (int l = 0; l < s.L; ++l) maxw = s.out[l] > maxw ? s.out[l] : maxw;
+    WsCarver c(base, 256);
+    for (int k = 0; k < 2; ++k) w.pp[k] = c.take<float>(rows * maxw);
+    for (int j = 0; j < 3; ++j) w.h[j] = c.take<float>(rows * s.H);
+    w.bytes = c.bytes();
+    return w;
 }
 
 void pia_head_tables(const inr_pia_desc_t* d, PiaHead& a) {
@@ -780,13 +782,7 @@ size_t inr_pia_workspace_bytes(const inr_pia_desc_t* desc, int64_t n, int traini
         pia_train_ws(s, n, nullptr, w);
         return w.bytes;
     }
-    int maxw = 0;
-    for (int l = 0; l < s.L; ++l) maxw = s.out[l] > maxw ? s.out[l] : maxw;
-    Carver c(nullptr);
-    c.take(n * maxw);
-    c.take(n * maxw);
-    for (int j = 0; j < 3; ++j) c.take(n * s.H);
-    return c.at;
+    return pia_fwd_ws(s, n, nullptr).bytes;
 }
 
 int inr_pia_forward(const inr_pia_desc_t* desc, const float* params, const float* x, int64_t n, float* signal, double* D, float* T2,
@@ -797,17 +793,13 @@ int inr_pia_forward(const inr_pia_desc_t* desc, const float* params, const float
     INR_REQUIRE((signal || D) && (!D || (T2 && v)), INR_E_INVALID, "inr_pia_forward: no output (D, T2 and v come together)");
     INR_REQUIRE(aligned16(x), INR_E_ALIGN, "inr_pia_forward: x must be 16-byte aligned");
     if (chunk_rows > n) chunk_rows = n;
-    INR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= inr_pia_workspace_bytes(desc, chunk_rows, 0), INR_E_WORKSPACE,
+    const PiaFwdWs w = pia_fwd_ws(s, chunk_rows, workspace);
+    INR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.bytes, INR_E_WORKSPACE,
                 "inr_pia_forward: workspace too small for chunks of %lld rows", (long long)chunk_rows);
     hipStream_t st = (hipStream_t)stream;
-    int maxw = 0;
-    for (int l = 0; l < s.L; ++l) maxw = s.out[l] > maxw ? s.out[l] : maxw;
-    Carver c(workspace);
-    float* pp[2] = {c.take(chunk_rows * maxw), c.take(chunk_rows * maxw)};
-    float* h[3];
-    for (int j = 0; j < 3; ++j) h[j] = c.take(chunk_rows * s.H);
+    float* const* h = w.h;
     float* act[8];
-    for (int l = 0; l < s.L; ++l) act[l] = pp[l & 1];
+    for (int l = 0; l < s.L; ++l) act[l] = w.pp[l & 1];
     PiaHead a{};
     pia_head_tables(desc, a);
     for (int j = 0; j < 3; ++j) {
@@ -835,11 +827,11 @@ int inr_pia_forward_train(const inr_pia_desc_t* desc, const float* params, const
     if (int rc = pia_kernel_shape(desc, s, "inr_pia_forward_train")) return rc;
     INR_REQUIRE(params && x && signal && D && T2 && v && n >= 1, INR_E_INVALID, "inr_pia_forward_train: null pointer or non-positive size");
     INR_REQUIRE(aligned16(x), INR_E_ALIGN, "inr_pia_forward_train: x must be 16-byte aligned");
-    INR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= inr_pia_workspace_bytes(desc, n, 1), INR_E_WORKSPACE,
-                "inr_pia_forward_train: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     PiaTrainWs w;
     pia_train_ws(s, n, workspace, w);
+    INR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.bytes, INR_E_WORKSPACE,
+                "inr_pia_forward_train: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
     if (int rc = pia_forward_layers(s, desc, params, x, n, w.act, w.h, st)) return rc;
     PiaHead a{};
     pia_train_head_args(a, s, desc, params, w, n);
@@ -855,11 +847,11 @@ int inr_pia_backward_train(const inr_pia_desc_t* desc, const float* params, floa
     if (int rc = pia_kernel_shape(desc, s, "inr_pia_backward_train")) return rc;
     INR_REQUIRE(params && grads && x && n >= 1, INR_E_INVALID, "inr_pia_backward_train: null pointer or non-positive size");
     INR_REQUIRE(aligned16(x), INR_E_ALIGN, "inr_pia_backward_train: x must be 16-byte aligned");
-    INR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= inr_pia_workspace_bytes(desc, n, 1), INR_E_WORKSPACE,
-                "inr_pia_backward_train: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     PiaTrainWs w;
     pia_train_ws(s, n, workspace, w);
+    INR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.bytes, INR_E_WORKSPACE,
+                "inr_pia_backward_train: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
     PiaHead a{};
     pia_train_head_args(a, s, desc, params, w, n);
     a.g_signal = g_signal; a.g_D = g_D; a.g_T2 = g_T2; a.g_v = g_v;
@@ -879,11 +871,11 @@ int inr_pia_fit_step(const inr_pia_desc_t* desc, float* params, float* grads, fl
     INR_REQUIRE(params && grads && m && v && x && loss && n >= 1 && step >= 1, INR_E_INVALID,
                 "inr_pia_fit_step: null pointer or non-positive size / step");
     INR_REQUIRE(aligned16(x), INR_E_ALIGN, "inr_pia_fit_step: x must be 16-byte aligned");
-    INR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= inr_pia_workspace_bytes(desc, n, 1), INR_E_WORKSPACE,
-                "inr_pia_fit_step: workspace too small");
-    hipStream_t st = (hipStream_t)stream;
     PiaTrainWs w;
     pia_train_ws(s, n, workspace, w);
+    INR_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= w.bytes, INR_E_WORKSPACE,
+                "inr_pia_fit_step: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
     if (int rc = pia_forward_layers(s, desc, params, x, n, w.act, w.h, st)) return rc;
     PiaHead a{};
     pia_train_head_args(a, s, desc, params, w, n);

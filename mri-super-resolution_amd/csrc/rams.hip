@@ -1221,49 +1221,61 @@ long long rams_slab_floats(int B, int ovox_max) {
     return (long long)B * rows * RC + 2048 + (gates > 2048 ? gates : 2048);
 }
 
-size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W) {
-    const long long T = d->channels;
+// The forward pass's carve of its workspace, in the order the regions have always had.  base == null: `total` only.
+struct RamsFwdView {
+    float *bufA, *bufB, *bufC, *bufR, *bufP;   // [B][H+4][W+4][T][32] each: trunk, conv1 output, conv2 output (to be gated), stem output, padded copies
+    float *slab, *gate;                        // channel-sum slabs (slab_cap floats for the producers, then 2,048 of padding); gates [B][32]
+    long long slab_cap;
+    float *xn, *xpad, *g1, *g2, *upo, *glo;    // normalised input [B][H][W][T]; three of [B][H+2][W+2][T]; two of [B][H][W][S2]
+    unsigned *slots, *tslots;                  // split-fp16 state behind everything else: max|w| per convolution (1,024 words), n_slots
+    _Float16* planes;                          // tensor slots of R3_SLOT words, the weight planes
+    int n_conv, n_slots;
+    size_t total;                              // bytes
+};
+static RamsFwdView rams_fwd_view(const inr_rams_desc_t* d, int B, int H, int W, void* base) {
+    const long long T = d->channels, S2 = d->scale * d->scale;
     const long long big = (long long)B * (H + 4) * (W + 4) * T * RC;      // largest 5-D activation (padded reduction stage)
-    const long long slab = rams_slab_floats(B, (H + 4) * (W + 4) * (int)T);
-    const long long small = (long long)B * (H + 2) * (W + 2) * T * 4 + (long long)B * H * W * d->scale * d->scale * 2;
-    // split-fp16 inference: hi/lo planes of every 32 -> 32 kernel + scale slots
-    const long long h3 = (long long)rams_conv3d_count(d) * (R3_LAYER_HALVES / 2) + 1024 +
-                         (3ll * rams_conv3d_count(d) + 8) * R3_SLOT;
-    return (size_t)(5 * big + slab + small + 8192 + h3);
+    const long long slab_floats = rams_slab_floats(B, (H + 4) * (W + 4) * (int)T);
+    const long long gate_floats = (long long)B * RC > 2048 ? (long long)B * RC : 2048;
+    const long long n_in = (long long)B * H * W * T, n_pad = (long long)B * (H + 2) * (W + 2) * T;
+    RamsFwdView v;
+    WsCarver c(base, sizeof(float));
+    v.bufA = c.take<float>(big); v.bufB = c.take<float>(big); v.bufC = c.take<float>(big); v.bufR = c.take<float>(big);
+    v.bufP = c.take<float>(big);
+    v.slab = c.take<float>(slab_floats - gate_floats);
+    v.slab_cap = slab_floats - gate_floats - 2048;   // what the channel-sum producers may use
+    v.gate = c.take<float>(gate_floats);
+    v.xn = c.take<float>(n_in); v.xpad = c.take<float>(n_pad); v.g1 = c.take<float>(n_pad); v.g2 = c.take<float>(n_pad);
+    v.upo = c.take<float>(B * H * W * S2); v.glo = c.take<float>(B * H * W * S2);
+    c.take<float>(64);
+    // ... on a 256-byte ADDRESS, not offset (the caller owes 16-byte alignment only): `total` reserves the worst-case padding
+    v.n_conv = rams_conv3d_count(d);
+    v.n_slots = 3 * v.n_conv + 8;       // (at most three new tensors per convolution + stem, skip, ...)
+    WsCarver h(base ? reinterpret_cast<char*>(round_up(reinterpret_cast<uintptr_t>(c.base + c.bytes()), 256)) : nullptr, sizeof(float));
+    v.slots = h.take<unsigned>(1024); v.tslots = h.take<unsigned>((size_t)v.n_slots * R3_SLOT);
+    v.planes = h.take<_Float16>((size_t)v.n_conv * R3_LAYER_HALVES);
+    v.total = c.bytes() + 252 + h.bytes();
+    return v;
 }
 
+size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W) { return rams_fwd_view(d, B, H, W, nullptr).total / sizeof(float); }
+
 int rams_forward_impl(const inr_rams_desc_t* d, const float* params, const float* x, float* out, int B, int H, int W,
-                      int clip_round, float* ws, hipStream_t st) {
+                      int clip_round, void* workspace, size_t workspace_bytes, hipStream_t st) {
     const int T = d->channels, Cr = d->filters / d->r, S2 = d->scale * d->scale;
     const int Tr = T / d->r > 0 ? T / d->r : 1;
-    const long long big = (long long)B * (H + 4) * (W + 4) * T * RC;
-    float* bufA = ws;               // current trunk activation
-    float* bufB = bufA + big;       // conv1 output
-    float* bufC = bufB + big;       // conv2 output (to be gated)
-    float* bufR = bufC + big;       // trunk residual (stem output)
-    float* bufP = bufR + big;       // padded copies
-    float* slab = bufP + big;
-    const long long slab_floats = rams_slab_floats(B, (H + 4) * (W + 4) * T);
-    const long long gate_floats = (long long)B * RC > 2048 ? (long long)B * RC : 2048;
-    const long long slab_cap = slab_floats - gate_floats - 2048;   // what the channel-sum producers may use
-    float* gate = slab + slab_floats - gate_floats;  // [B][32]
-    float* xn = slab + slab_floats;                  // normalised input [B][H][W][T]
-    float* xpad = xn + (long long)B * H * W * T;     // reflect-padded [B][H+2][W+2][T]
-    float* g1 = xpad + (long long)B * (H + 2) * (W + 2) * T;
-    float* g2 = g1 + (long long)B * (H + 2) * (W + 2) * T;
-    float* upo = g2 + (long long)B * (H + 2) * (W + 2) * T;   // [B][H][W][S2]
-    float* glo = upo + (long long)B * H * W * S2;
-    // split-fp16 state behind everything else: [slots: 1024 x u32][planes of conv 0][planes of conv 1]...
+    const RamsFwdView v = rams_fwd_view(d, B, H, W, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "inr_rams_forward: workspace too small");
+    INR_REQUIRE(aligned16(workspace) && aligned16(params), INR_E_ALIGN, "inr_rams_forward: params/workspace alignment");
+    float *bufA = v.bufA, *bufB = v.bufB, *bufC = v.bufC, *bufR = v.bufR, *bufP = v.bufP;   // (the pass swaps them as it goes)
+    float *const slab = v.slab, *const gate = v.gate, *const xn = v.xn, *const xpad = v.xpad, *const g1 = v.g1, *const g2 = v.g2,
+          *const upo = v.upo, *const glo = v.glo;
+    unsigned *const slots = v.slots, *const tslots = v.tslots;
+    _Float16* const planes = v.planes;
+    const long long slab_cap = v.slab_cap;
+    const int n_conv = v.n_conv, n_slots = v.n_slots;
     const bool h3 = g_rams_h3 != 0;
-    const int n_conv = rams_conv3d_count(d);
     INR_REQUIRE(n_conv <= R3_MAX_CONVS, INR_E_INVALID, "rams: too many 3-D convolutions (%d)", n_conv);
-    unsigned* slots = reinterpret_cast<unsigned*>(ws + 5 * big + slab_floats + (long long)B * H * W * T +
-                                                  3 * (long long)B * (H + 2) * (W + 2) * T + 2 * (long long)B * H * W * S2 + 64);
-    slots = reinterpret_cast<unsigned*>((reinterpret_cast<uintptr_t>(slots) + 255) & ~(uintptr_t)255);
-    // words [0, 1024): max|w| per convolution; then R3_MAX_SLOTS tensor slots of R3_SLOT words each; then the weight planes
-    unsigned* tslots = slots + 1024;
-    const int n_slots = 3 * n_conv + 8;       // (at most three new tensors per convolution + stem, skip, ...)
-    _Float16* planes = reinterpret_cast<_Float16*>(tslots + (long long)n_slots * R3_SLOT);
     int conv_no = 0, next_slot = 0;
     auto new_slot = [&]() {     // (a graph with more tensors than slots would share the last one: a larger maximum, still a valid scale)
         const int k = next_slot < n_slots - 1 ? next_slot++ : n_slots - 1;

@@ -532,59 +532,97 @@ static TrainDims train_dims(const inr_rams_desc_t* d, int B, int H, int W) {
 // per-channel partial sums: the convolution epilogue writes [B][waves_per_b][32], the gate backward [B][64][32]
 static long long train_slab_floats(int B, int H, int W, int T) { return rams_slab_floats(B, (H + 4) * (W + 4) * T); }
 
-static size_t rams_train_ws_floats(const inr_rams_desc_t* d, int B, int H, int W) {
-    const TrainDims t = train_dims(d, B, H, W);
+// Every region of a step's workspace, in the order the step first touches them (forward, loss, backward), each on a 256-byte
+// boundary.  Sizes depend on (d, B, H, W) alone, so the whole carve is known -- and checked against the caller's byte count --
+// before the first launch.  base == null: `total` only.
+struct RamsTrainView {
+    std::vector<TLayer> L;                 // the layer table the regions are sized from
     long long raw_total, fold_total;
-    std::vector<TLayer> L;
-    rams_train_layers(d, L, &raw_total, &fold_total);
-    const int nred = t.T / 3;
-    long long n = 0;
-    n += 2 * fold_total;                                   // folded parameters, folded gradients
-    n += (long long)(1 + 3 * t.N + 1) * t.V;               // a0, per RFAB (r1, c2, out), trunk output
-    n += (long long)nred * 5 * t.Vp;                       // per reduction stage: padded in, r1, c2, out, next
-    n += 4 * t.Vp;                                         // gradient ping-pong + two temporaries
-    n += (long long)(t.N + nred + 1) * B * (3 * RC + 8);   // gates, means, squeezes
-    n += (long long)B * (H + 2) * (W + 2) * t.T * 8;       // 2-D branch tensors and their gradients
-    n += (long long)B * H * W * (t.S2 * 4 + RC * 2);       // head outputs / gradients
-    n += (long long)B * H * W * t.S2 * 2;                  // prediction and its gradient
-    n += (long long)L.size() * (sizeof(FoldLayer) / 4 + 1);
-    n += (long long)rams_conv3d_wgrad_ws_floats((long long)B * (H + 4) * (W + 4) * t.T);
-    n += train_slab_floats(B, H, W, t.T) + (long long)B * 1024 + 512 * 28 * 32 + 65536;   // pool / gate partials, stem slabs, misc
-    n += 512ll * (9 * t.T * t.T + t.T + 8);                // 2-D weight-gradient slabs
-    // split-fp16 convolutions: hi/lo planes of every 32 -> 32 kernel and of its data-gradient kernel, max|w| words, one max|x| slot
-    // per convolution call
-    n += 2ll * rams_conv3d_count(d) * (R3_LAYER_HALVES / 2 + R3_SLOT) + 1024 + 256;
-    n += (4ll * (t.N + nred) + 16) * R3_SLOT;              // slots of tensors whose producer records max|.| itself
-    return (size_t)n + 16384;
+    struct Block { float *pin, *r1, *c2, *out, *gate, *mean, *sq; };   // one attention block; pin: the reduction stages' padded input
+    float *fold, *gfold;                   // folded parameters and their gradients
+    float *xn, *xpad, *a0;
+    float *wgrad_ws, *slab, *gpart, *dpool;
+    unsigned *wslots, *tslots;             // max|w| (forward k, data gradient n_conv3 + k); n_tslots slots of R3_SLOT words
+    int n_conv3, n_tslots;
+    _Float16* planes;
+    float* zero_bias;
+    std::vector<Block> blk;                // N trunk blocks, then T / 3 reduction stages
+    float* tr;
+    std::vector<float*> red_out;
+    float *upo, *g1, *g2, *g3, *ggate, *gmean, *gsq, *glo, *pred, *dpred;
+    double* lws;
+    float *dA, *dB, *tmp, *tmp2, *dps, *keep, *dg1, *chain;
+    size_t total;                          // bytes
+};
+static RamsTrainView rams_train_view(const inr_rams_desc_t* d, int B, int H, int W, void* base) {
+    const TrainDims t = train_dims(d, B, H, W);
+    const int T = t.T, nred = T / 3, D1 = H + 2, D2 = W + 2;
+    const long long n_pad = (long long)B * D1 * D2 * T, n_hw = (long long)B * H * W;
+    RamsTrainView v;
+    rams_train_layers(d, v.L, &v.raw_total, &v.fold_total);
+    WsCarver c(base, 256);
+    auto f = [&](long long n) { return c.take<float>((size_t)n); };
+    v.fold = f(v.fold_total); v.gfold = f(v.fold_total);
+    f((long long)v.L.size() * (sizeof(FoldLayer) / 4 + 1));   // (round 3's device copy of the layer table: the workspace layout is kept)
+    v.xn = f((long long)B * H * W * T); v.xpad = f(n_pad); v.a0 = f(t.V);
+    v.wgrad_ws = f((long long)rams_conv3d_wgrad_ws_floats((long long)B * (H + 4) * (W + 4) * T));
+    v.slab = f(train_slab_floats(B, H, W, T)); v.gpart = f((long long)B * 1024); v.dpool = f((long long)B * RC);
+    // split-fp16 state of the 32 -> 32 convolutions; the max|w| words start on a 256-byte ADDRESS inside a region 64 words longer
+    v.n_conv3 = rams_conv3d_count(d);
+    v.n_tslots = 2 * v.n_conv3 + 4 * (t.N + nred) + 16;
+    v.wslots = c.take<unsigned>(1024 + 64);
+    v.wslots = reinterpret_cast<unsigned*>(round_up(reinterpret_cast<uintptr_t>(v.wslots), 256));
+    v.tslots = c.take<unsigned>((size_t)v.n_tslots * R3_SLOT);
+    v.planes = c.take<_Float16>(2 * (size_t)v.n_conv3 * R3_LAYER_HALVES);
+    v.zero_bias = f(RC);
+    v.blk.resize(t.N + nred);
+    for (int i = 0; i < t.N; ++i) v.blk[i] = {nullptr, f(t.V), f(t.V), f(t.V), f(B * RC), f(B * RC), f(B * 8)};
+    v.tr = f(t.V);
+    v.red_out.resize(nred);
+    for (int j = 0, D3 = T; j < nred; ++j, D3 -= 2) {
+        const long long vp = (long long)B * (D1 + 2) * (D2 + 2) * D3 * RC;
+        v.blk[t.N + j] = {f(vp), f(vp), f(vp), f(vp), f(B * RC), f(B * RC), f(B * 8)};
+        v.red_out[j] = f((long long)B * D1 * D2 * (D3 - 2) * RC);
+    }
+    v.upo = f(n_hw * t.S2);
+    v.g1 = f(n_pad); v.g2 = f(n_pad); v.g3 = f(n_pad);
+    v.ggate = f(B * RC); v.gmean = f(B * RC); v.gsq = f(B * 8);
+    v.glo = f(n_hw * t.S2); v.pred = f(n_hw * t.S2); v.dpred = f(n_hw * t.S2);
+    v.lws = c.take<double>((size_t)B * 49 + B + 8);
+    v.dA = f(t.Vp); v.dB = f(t.Vp); v.tmp = f(t.Vp); v.tmp2 = f(t.Vp);
+    v.dps = f(n_hw * t.S2);      // gradient of both pixel-shuffled heads
+    v.keep = f(n_pad); v.dg1 = f(n_pad);
+    v.chain = f(t.V);
+    v.total = c.bytes();
+    return v;
+}
+
+size_t rams_train_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W) {
+    return rams_train_view(d, B, H, W, nullptr).total / sizeof(float);
 }
 
 // ---- the step ---------------------------------------------------------------------------------------------------------------------
-struct Bump {
-    float* p;
-    float* take(long long n) {
-        float* r = p;
-        p += (n + 63) / 64 * 64;
-        return r;
-    }
-};
-
 // One forward + loss + backward.  raw: parameters (raw layout); raw_grad: receives d(sum_b loss_b)/d raw.  loss: [B] doubles.
 // pred (nullable): receives the un-clipped prediction [B][sH][sW].
-static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, float* raw_grad, const float* x, const float* y_true,
-                                 const float* mask, double* loss, float* pred_out, int B, int H, int W, float* ws,
-                                 hipStream_t st) {
+int rams_train_grads(const inr_rams_desc_t* d, const float* raw, float* raw_grad, const float* x, const float* y_true,
+                     const float* mask, double* loss, float* pred_out, int B, int H, int W, void* workspace, size_t workspace_bytes,
+                     hipStream_t st) {
     const TrainDims t = train_dims(d, B, H, W);
-    const size_t ws_floats = rams_train_ws_floats(d, B, H, W);
     const int T = t.T, Cr = t.Cr, Tr = t.Tr, S2 = t.S2, s = d->scale, nred = T / 3;
     INR_REQUIRE(d->filters == RC && d->kernel_size == 3 && T == 9 && s * s <= RC, INR_E_INVALID,
                 "rams train: filters must be 32, kernel 3, channels 9");
-    std::vector<TLayer> L;
-    long long raw_total, fold_total;
-    rams_train_layers(d, L, &raw_total, &fold_total);
-    Bump bp{ws};
-    float* fold = bp.take(fold_total);
-    float* gfold = bp.take(fold_total);
-    bp.take((long long)L.size() * (sizeof(FoldLayer) / 4 + 1));   // (round 3's device copy of the layer table: the workspace layout is kept)
+    const RamsTrainView v = rams_train_view(d, B, H, W, workspace);
+    const std::vector<TLayer>& L = v.L;
+    const long long raw_total = v.raw_total, fold_total = v.fold_total;
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "inr_rams_train_grads: workspace too small");
+    INR_REQUIRE(aligned16(workspace) && aligned16(raw) && aligned16(raw_grad), INR_E_ALIGN,
+                "inr_rams_train_grads: params / grads / workspace must be 16-byte aligned");
+    // the regions, under the names the step has always used
+    float *const fold = v.fold, *const gfold = v.gfold, *const xn = v.xn, *const xpad = v.xpad, *const a0 = v.a0, *const wgrad_ws = v.wgrad_ws,
+          *const slab = v.slab, *const gpart = v.gpart, *const dpool = v.dpool, *const zero_bias = v.zero_bias, *const tr = v.tr,
+          *const upo = v.upo, *const g1 = v.g1, *const g2 = v.g2, *const g3 = v.g3, *const ggate = v.ggate, *const gmean = v.gmean,
+          *const gsq = v.gsq, *const glo = v.glo, *const pred = v.pred, *const dpred = v.dpred, *const dA = v.dA, *const dB = v.dB,
+          *const tmp = v.tmp, *const tmp2 = v.tmp2, *const dps = v.dps, *const keep = v.keep, *const dg1 = v.dg1, *const chain = v.chain;
     FoldTable dl{};
     INR_REQUIRE(L.size() <= (size_t)FOLD_MAX_LAYERS && raw_total < (1ll << 31) && fold_total < (1ll << 31), INR_E_INVALID,
                 "rams train: %zu layers / %lld parameters exceed the by-value layer table", L.size(), raw_total);
@@ -601,35 +639,26 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
 
     const int D1 = H + 2, D2 = W + 2;
     const long long n_in = (long long)B * H * W * T, n_pad = (long long)B * D1 * D2 * T;
-    float* xn = bp.take(n_in);
-    float* xpad = bp.take(n_pad);
-    float* a0 = bp.take(t.V);
     struct Rfab { float *in, *r1, *c2, *out, *gate, *mean, *sq; int D1, D2, D3; int l0; unsigned* out_slot = nullptr; };
     std::vector<Rfab> R(t.N + nred);
-    float* wgrad_ws = bp.take((long long)rams_conv3d_wgrad_ws_floats((long long)B * (H + 4) * (W + 4) * T));
-    float* slab = bp.take(train_slab_floats(B, H, W, T));
-    float* gpart = bp.take((long long)B * 1024);
-    float* dpool = bp.take((long long)B * RC);
 
     // ---- split-fp16 state of the 32 -> 32 convolutions (forward and data gradient; debug key 14 = 0 keeps the f32-input kernels) ----
     const bool h3 = g_rams_h3 != 0;
-    const int n_conv3 = rams_conv3d_count(d);
+    const int n_conv3 = v.n_conv3;
     INR_REQUIRE(2 * n_conv3 <= R3_MAX_CONVS, INR_E_INVALID, "rams train: too many 3-D convolutions (%d)", n_conv3);
-    unsigned* wslots = reinterpret_cast<unsigned*>(bp.take(1024 + 64));              // max|w|: forward k, data gradient n_conv3 + k
-    wslots = reinterpret_cast<unsigned*>((reinterpret_cast<uintptr_t>(wslots) + 255) & ~(uintptr_t)255);
+    unsigned* const wslots = v.wslots;              // max|w|: forward k, data gradient n_conv3 + k
     // max|x| of each call's input: slots k / n_conv3 + k belong to forward / gradient call k (filled by a pass over the tensor when
     // nothing better is known), the rest to tensors whose PRODUCER records the maximum (convolution epilogues, the gated residual,
     // the ReLU and gate backward kernels): 63 of the 74 passes of a step are not needed
-    const int n_tslots = 2 * n_conv3 + 4 * (t.N + nred) + 16;
-    unsigned* tslots = reinterpret_cast<unsigned*>(bp.take((long long)n_tslots * R3_SLOT));
+    const int n_tslots = v.n_tslots;
+    unsigned* const tslots = v.tslots;
     int next_slot = 2 * n_conv3;
     auto new_slot = [&]() -> unsigned* {
         if (!h3 || next_slot >= n_tslots) return nullptr;      // (nullptr: the consumer measures the tensor itself)
         return tslots + (long long)(next_slot++) * R3_SLOT;
     };
     std::vector<const unsigned*> xslot_of((size_t)n_conv3, nullptr);     // the slot a forward call used: its weight gradient reads it
-    _Float16* planes = reinterpret_cast<_Float16*>(bp.take(2ll * n_conv3 * (R3_LAYER_HALVES / 2)));
-    float* zero_bias = bp.take(RC);
+    _Float16* const planes = v.planes;
     std::vector<int> conv3_of(L.size(), -1);       // layer -> index among the 32 -> 32 convolutions
     int last_nslab = 0;                             // per-batch-element channel-sum slabs the last forward convolution wrote
     if (h3) {
@@ -718,14 +747,14 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
     float* cur = a0;
     for (int i = 0; i < t.N; ++i) {
         Rfab& r = R[i];
-        r = Rfab{cur, bp.take(t.V), bp.take(t.V), bp.take(t.V), bp.take(B * RC), bp.take(B * RC), bp.take(B * 8), D1, D2, T, l};
+        const RamsTrainView::Block& k = v.blk[i];
+        r = Rfab{cur, k.r1, k.c2, k.out, k.gate, k.mean, k.sq, D1, D2, T, l};
         if (int rc = rfab_fwd(r, cur_slot)) return rc;
         cur = r.out;
         cur_slot = r.out_slot;
         l += 4;
     }
     const int l_trunk = l++;
-    float* tr = bp.take(t.V);
     if (int rc = conv(cur, tr, l_trunk, D1, D2, T, 1, 0, nullptr, RC, RC, cur_slot)) return rc;
     hipLaunchKernelGGL(accumulate_kernel, dim3(nblk(t.V)), dim3(256), 0, st, tr, a0, t.V);   // + long skip (network.py:129)
     INR_LAUNCH_CHECK();
@@ -733,19 +762,18 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
     cur = tr;
     cur_slot = nullptr;                                    // (conv + skip: measured by its consumer)
     int D3 = T;
-    std::vector<float*> red_out(nred);
+    const std::vector<float*>& red_out = v.red_out;
     std::vector<int> red_conv(nred);
     for (int j = 0; j < nred; ++j) {
         Rfab& r = R[t.N + j];
-        const long long vp = (long long)B * (D1 + 2) * (D2 + 2) * D3 * RC;
-        float* pin = bp.take(vp);
+        const RamsTrainView::Block& k = v.blk[t.N + j];
+        float* const pin = k.pin;
         hipLaunchKernelGGL(reflect_pad_v4_kernel, dim3((D1 + 2) * (D2 + 2), B), dim3(256), 0, st, pin, cur, D1, D2, D3 * RC / 4);
         INR_LAUNCH_CHECK();
-        r = Rfab{pin, bp.take(vp), bp.take(vp), bp.take(vp), bp.take(B * RC), bp.take(B * RC), bp.take(B * 8), D1 + 2, D2 + 2, D3, l};
+        r = Rfab{pin, k.r1, k.c2, k.out, k.gate, k.mean, k.sq, D1 + 2, D2 + 2, D3, l};
         if (int rc = rfab_fwd(r, cur_slot)) return rc;     // (reflect padding repeats samples: the maximum is that of `cur`)
         l += 4;
         red_conv[j] = l++;
-        red_out[j] = bp.take((long long)B * D1 * D2 * (D3 - 2) * RC);
         unsigned* ro_slot = new_slot();
         if (int rc = conv(r.out, red_out[j], red_conv[j], D1 + 2, D2 + 2, D3, 0, 1, nullptr, RC, RC, r.out_slot, ro_slot)) return rc;
         cur = red_out[j];
@@ -755,18 +783,10 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
     INR_REQUIRE(D3 == 3, INR_E_INVALID, "rams train: temporal depth before the head must be 3 (got %d)", D3);
     const int l_up = l++;
     const long long n_hw = (long long)B * H * W;
-    float* upo = bp.take(n_hw * S2);
     if (int rc = conv(cur, upo, l_up, D1, D2, 3, 0, 0, nullptr, S2, S2, cur_slot)) return rc;
     const float* up_in = cur;
     // global path (network.py:144-148)
     const int l_g = l;   // rtab conv1, conv2, squeeze, excite, global
-    float* g1 = bp.take(n_pad);
-    float* g2 = bp.take(n_pad);
-    float* g3 = bp.take(n_pad);
-    float* ggate = bp.take(B * RC);
-    float* gmean = bp.take(B * RC);
-    float* gsq = bp.take(B * 8);
-    float* glo = bp.take(n_hw * S2);
     const int nb2 = 64;
     launch_conv2d(g1, xpad, fold + L[l_g].fw, fold + L[l_g].fb, B, D1, D2, T, T, 1, 1, st);
     INR_LAUNCH_CHECK();
@@ -782,24 +802,14 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
     launch_conv2d(glo, g3, fold + L[l_g + 4].fw, fold + L[l_g + 4].fb, B, D1, D2, T, S2, 0, 0, st);
     INR_LAUNCH_CHECK();
     const long long n_out = n_hw * S2;
-    float* pred = bp.take(n_out);
-    float* dpred = bp.take(n_out);
     hipLaunchKernelGGL(shuffle_sum_kernel, dim3(nblk(n_out)), dim3(256), 0, st, pred, upo, glo, B, H, W, s, d->mean, d->std, 0);
     INR_LAUNCH_CHECK();
     if (pred_out) INR_HIP(hipMemcpyAsync(pred_out, pred, (size_t)n_out * 4, hipMemcpyDeviceToDevice, st));
 
     // ---- loss and its gradient (utils/loss.py:26-75; tape.gradient of the per-image vector = gradient of its sum) --------------
-    {
-        double* lws = reinterpret_cast<double*>(bp.take(2 * ((long long)B * 49 + B + 8)));
-        if (int rc = launch_shift_loss_grad(loss, dpred, y_true, pred, mask, nullptr, B, H * s, 3, lws, st)) return rc;
-    }
+    if (int rc = launch_shift_loss_grad(loss, dpred, y_true, pred, mask, nullptr, B, H * s, 3, v.lws, st)) return rc;
 
     // ---- backward ---------------------------------------------------------------------------------------------------------------
-    float* dA = bp.take(t.Vp);
-    float* dB = bp.take(t.Vp);
-    float* tmp = bp.take(t.Vp);
-    float* tmp2 = bp.take(t.Vp);
-    float* dps = bp.take(n_hw * S2);     // gradient of both pixel-shuffled heads
     hipLaunchKernelGGL(shuffle_backward_kernel, dim3(nblk(n_out)), dim3(256), 0, st, dps, dpred, B, H, W, s, d->std);
     INR_LAUNCH_CHECK();
     // weight gradient of a 32 -> 32 convolution: split-fp16 (default) needs max|x| -- the slot its forward call filled -- and max|dy|
@@ -932,15 +942,12 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
             return 0;
         };
         float* dg3 = dA;
-        float* dg2 = dB;
         if (int rc = wgrad2(l_g + 4, g3, dps, T, S2, 0)) return rc;
         hipLaunchKernelGGL(conv2d_dgrad_kernel, dim3(nblk(n_pad)), dim3(256), 0, st, dg3, dps, fold + L[l_g + 4].fw, B, D1, D2, T, S2, 0);
         INR_LAUNCH_CHECK();
-        float* keep = bp.take(n_pad);   // d g2 must survive wgrad2's use of tmp / tmp2
+        // (`keep`: d g2 must survive wgrad2's use of tmp / tmp2)
         if (int rc = gate_bwd(keep, dg3, g2, ggate, gmean, gsq, l_g + 2, (long long)D1 * D2, T, Tr)) return rc;
-        (void)dg2;
         if (int rc = wgrad2(l_g + 1, g1, keep, T, T, 1)) return rc;
-        float* dg1 = bp.take(n_pad);
         hipLaunchKernelGGL(conv2d_dgrad_kernel, dim3(nblk(n_pad)), dim3(256), 0, st, dg1, keep, fold + L[l_g + 1].fw, B, D1, D2, T, T, 1);
         INR_LAUNCH_CHECK();
         hipLaunchKernelGGL(relu_backward_kernel, dim3(nblk_capped(n_pad / 4 + 1)), dim3(256), 0, st, dg1, g1, n_pad);
@@ -972,8 +979,6 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
         INR_LAUNCH_CHECK();
         if (int rc = dgrad3(dB, tmp2, red_conv[j], D1 + 2, D2 + 2, din3)) return rc;    // dB = d (block output), padded dims
         if (int rc = rfab_bwd(r, dB)) return rc;                                       // dB = d (padded input)
-        const long long nin_v = (long long)B * D1 * D2 * din3 * RC;
-        (void)nin_v;
         hipLaunchKernelGGL(reflect_pad_backward_v4_kernel, dim3(D1 * D2, B), dim3(256), 0, st, dA, dB, D1, D2, din3 * RC / 4);
         INR_LAUNCH_CHECK();
         d3 = din3;
@@ -982,7 +987,6 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
     // d a_t stays where it is and IS the long skip's gradient of a0; the chain through the blocks runs in a buffer of its own
     // (three device-to-device copies of the tensor stood here: d a_t aside, the convolution's result back over it, the copy again)
     float* const skip = dA;
-    float* const chain = bp.take(t.V);
     if (int rc = wgrad3(l_trunk, trunk_in, dA, D1, D2, T, 1)) return rc;
     if (int rc = dgrad3(chain, dA, l_trunk, D1, D2, T)) return rc;                       // chain = d a_N
     for (int i = t.N - 1; i >= 0; --i)
@@ -1005,8 +1009,6 @@ static int rams_train_grads_impl(const inr_rams_desc_t* d, const float* raw, flo
         INR_HIP(hipMemcpyAsync(gfold + L[0].fw, tmp2, 27 * 32 * 4, hipMemcpyDeviceToDevice, st));
         INR_HIP(hipMemcpyAsync(gfold + L[0].fb, tmp2 + 27 * 32, 32 * 4, hipMemcpyDeviceToDevice, st));
     }
-    INR_REQUIRE((size_t)(bp.p - ws) <= ws_floats, INR_E_WORKSPACE, "rams train: workspace carve exceeded its estimate (%zu > %zu floats)",
-                (size_t)(bp.p - ws), ws_floats);
     // un-fold: (dK, db) -> (dv, dg, db)
     const FoldJobs JB{raw, raw_grad, gfold, (int)L.size()};
     hipLaunchKernelGGL(fold_backward_kernel, dim3((unsigned)L.size()), dim3(256), 0, st, JB, dl);
@@ -1033,11 +1035,4 @@ int rams_train_param_offsets(const inr_rams_desc_t* d, int64_t* offsets, int max
         offsets[3 * i + 2] = L[i].b;
     }
     return (int)L.size();
-}
-
-size_t rams_train_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W) { return rams_train_ws_floats(d, B, H, W); }
-
-int rams_train_grads(const inr_rams_desc_t* d, const float* raw, float* raw_grad, const float* x, const float* y_true,
-                     const float* mask, double* loss, float* pred, int B, int H, int W, float* ws, hipStream_t st) {
-    return rams_train_grads_impl(d, raw, raw_grad, x, y_true, mask, loss, pred, B, H, W, ws, st);
 }

@@ -335,24 +335,37 @@ bool small_path_ok(const inr_siren_desc_t* d, int64_t n) {
 
 static inline int small_blocks(int64_t n) { return (int)((n + 127) / 128); }
 
-size_t small_workspace_floats(const inr_siren_desc_t* d, int64_t n, long long P) {
-    const int S = d->hidden_layers + 1;
-    const size_t nh = (size_t)n * d->hidden_features;
-    return (size_t)(S + 1) * nh + (size_t)S * nh + (size_t)small_blocks(n) * 4 * (size_t)P + (size_t)small_blocks(n) * 4 + 64;
+// A small-network kernel's carve of the fit workspace (api.hip: fit_view covers `floats`).  multi: the persistent and batched
+// kernels (rows padded to whole blocks of either size, one slab per block, sync words), else the two-launch step.  ws == null: `floats` only.
+struct SmallView {
+    float *acts, *dacts, *slabs, *loss_partial;
+    unsigned* sync;   // multi only: [0] arrivals, [1] error word, on a 256-byte line of their own
+    size_t floats;
+};
+static SmallView small_view(const inr_siren_desc_t* d, int64_t n, long long P, float* ws, bool multi) {
+    const size_t S = d->hidden_layers + 1, nh = (size_t)(multi ? (n + 63) / 64 * 64 : n) * d->hidden_features;
+    const size_t nslab = multi ? (size_t)((n + 31) / 32) : (size_t)small_blocks(n) * 4;      // multi: the larger block count
+    SmallView v;
+    WsCarver c(ws, sizeof(float));
+    v.acts = c.take<float>((multi ? S : S + 1) * nh); v.dacts = c.take<float>(S * nh);
+    v.slabs = c.take<float>(nslab * (size_t)P); v.loss_partial = c.take<float>(multi ? round_up(nslab, 64) : nslab);
+    // the tails keep the 64 / nslab + 128 words behind the slabs that the planners have always reported: callers' allocations stay as they are
+    v.sync = c.take<unsigned>(multi ? nslab + 128 - round_up(nslab, 64) : 64);
+    v.floats = c.bytes() / sizeof(float);
+    return v;
 }
+
+size_t small_workspace_floats(const inr_siren_desc_t* d, int64_t n, long long P) { return small_view(d, n, P, nullptr, false).floats; }
 
 int small_fit_step(const inr_siren_desc_t* d, const long long* w_off, const long long* b_off, long long P, float* params,
                    float* grads, float* m, float* v, const float* x, const float* target, const float* weight, int64_t n,
                    int64_t step, double lr, double b1, double b2, double eps, float* loss_out, float* ws, hipStream_t st) {
     const int S = d->hidden_layers + 1, H = d->hidden_features;
     const int blocks = small_blocks(n), nwaves = blocks * 4;
-    const size_t nh = (size_t)n * H;
+    const SmallView w = small_view(d, n, P, ws, false);
     SmallParams p{};
     p.params = params;
-    p.acts = ws;
-    p.dacts = ws + (size_t)(S + 1) * nh;
-    p.slabs = p.dacts + (size_t)S * nh;
-    p.loss_partial = p.slabs + (size_t)nwaves * P;
+    p.acts = w.acts; p.dacts = w.dacts; p.slabs = w.slabs; p.loss_partial = w.loss_partial;
     p.x = x; p.target = target; p.weight = weight;
     for (int l = 0; l <= S; ++l) { p.w_off[l] = w_off[l]; p.b_off[l] = b_off[l]; }
     p.P = P; p.N = (int)n; p.F = d->in_features; p.S = S;
@@ -1022,25 +1035,15 @@ static inline int multi_blocks(const inr_siren_desc_t* d, int64_t n) {
     return (int)((n + rows - 1) / rows);
 }
 
-size_t small_multi_workspace_floats(const inr_siren_desc_t* d, int64_t n, long long P) {
-    const int S = d->hidden_layers + 1;
-    const size_t tile = (size_t)((n + 63) / 64) * 64 * d->hidden_features;      // rows padded to whole blocks (either block size)
-    const size_t nb = (size_t)((n + 31) / 32);                                  // the larger block count
-    return 2 * (size_t)S * tile + nb * (size_t)P + nb + 64 + 64;                // acts, dacts, slabs, loss partials, sync words
-}
+size_t small_multi_workspace_floats(const inr_siren_desc_t* d, int64_t n, long long P) { return small_view(d, n, P, nullptr, true).floats; }
 
 // One fit's slice of the workspace (inr_siren_fit_workspace_bytes): stash, slabs, loss partials, sync words.
 static SmallProb small_prob(const inr_siren_desc_t* d, int64_t n, long long P, float* params, float* grads, float* m, float* v,
                             const float* targets, const float* weights, int n_acq, float* ws) {
-    const int S = d->hidden_layers + 1, H = d->hidden_features;
-    const size_t tile = (size_t)((n + 63) / 64) * 64 * H;
+    const SmallView w = small_view(d, n, P, ws, true);
     SmallProb q{};
     q.params = params; q.grads = grads; q.m = m; q.v = v;
-    q.acts = ws;
-    q.dacts = ws + (size_t)S * tile;
-    q.slabs = q.dacts + (size_t)S * tile;
-    q.loss_partial = q.slabs + (size_t)((n + 31) / 32) * P;
-    q.sync = reinterpret_cast<unsigned*>(q.loss_partial + (((size_t)((n + 31) / 32) + 63) / 64) * 64);
+    q.acts = w.acts; q.dacts = w.dacts; q.slabs = w.slabs; q.loss_partial = w.loss_partial; q.sync = w.sync;
     q.targets = targets; q.weights = weights;
     q.n_acq = n_acq;
     return q;

@@ -438,8 +438,9 @@ WirePlan wire_plan(const inr_wire_desc_t* d) {
 
 int wire_splits(int64_t n) { return (int)((n + WIRE_SLAB_ROWS - 1) / WIRE_SLAB_ROWS); }
 
-// what a workspace holds: bump allocation in floats, every region on a 256-byte boundary.  base == null: sizes only.
+// what a workspace holds: every region on a 256-byte boundary and at least one element long.  base == null: sizes only.
 struct WireView {
+    float* feats = nullptr;     // the dense re-sampling only: fp32 features of one chunk, ahead of everything else
     float* x0 = nullptr;
     float *img[WIRE_MAX_LAYERS], *imgT[WIRE_MAX_LAYERS], *pb[WIRE_MAX_LAYERS];     // imgT[0]: WIRE_WS_INPUT_GRAD only
     float *act[WIRE_MAX_LAYERS], *Z[WIRE_MAX_LAYERS];     // inference: act[0], act[1] ping-pong, no Z
@@ -448,16 +449,13 @@ struct WireView {
     size_t total = 0;
 };
 
-WireView wire_view(const WirePlan& p, int64_t n, int mode, void* base) {
+WireView wire_view(const WirePlan& p, int64_t n, int mode, void* base, bool with_feats = false) {
     WireView v;
     const bool training = mode != WIRE_WS_INFER;
-    size_t at = 0;
-    auto take = [&](size_t floats) {
-        float* ptr = base ? (float*)base + at : nullptr;
-        at += round_up(floats ? floats : 1, 64);
-        return ptr;
-    };
+    WsCarver c(base, 64 * sizeof(float));
+    auto take = [&](size_t floats) { return c.take<float>(floats ? floats : 1); };
     const size_t H = (size_t)p.H, N = (size_t)n;
+    if (with_feats) v.feats = take(N * p.in_f);
     v.x0 = take(N * p.K0);
     for (int l = 0; l <= p.L; ++l) {
         v.img[l] = take(l == 0 ? 2 * H * p.K0 : 8 * H * H);
@@ -477,7 +475,7 @@ WireView wire_view(const WirePlan& p, int64_t n, int mode, void* base) {
         }
         v.G = take(N * 2 * H);
         if (mode == WIRE_WS_INPUT_GRAD) {       // no loss, no parameter gradients: y and gy are the caller's
-            v.total = at * sizeof(float);
+            v.total = c.bytes();
             return v;
         }
         const size_t S = (size_t)wire_splits(n);
@@ -491,7 +489,16 @@ WireView wire_view(const WirePlan& p, int64_t n, int mode, void* base) {
         v.hslab = take(S * 2 * H);
         v.gslab = take(S);
     }
-    v.total = at * sizeof(float);
+    v.total = c.bytes();
+    return v;
+}
+
+// the workspace of one stand-alone layer (inr_wire_layer_forward): padded input x0, block image img[0], packed biases pb[0]
+WireView wire_layer_view(int64_t n, int K, int H, void* base) {
+    WireView v;
+    WsCarver c(base, 64 * sizeof(float));
+    v.x0 = c.take<float>((size_t)n * K); v.img[0] = c.take<float>(4 * (size_t)H * K); v.pb[0] = c.take<float>(4 * (size_t)H);
+    v.total = c.bytes();
     return v;
 }
 
@@ -634,27 +641,29 @@ int wire_loss_grad_impl(const inr_wire_desc_t* d, const WirePlan& p, const WireV
 }
 
 int wire_check_train(const char* who, const inr_wire_desc_t* desc, const void* params, const void* grads, const void* x,
-                     const void* target, int64_t n, const void* workspace, size_t workspace_bytes) {
+                     const void* target, int64_t n, void* workspace, size_t workspace_bytes, WirePlan& p, WireView& v) {
     if (int rc = wire_check_desc(who, desc)) return rc;
     INR_REQUIRE(params && grads && x && target, INR_E_INVALID, "%s: null pointer", who);
     INR_REQUIRE(n >= 1 && n <= WIRE_MAX_STASH_ROWS, INR_E_INVALID, "%s: bad row count %lld", who, (long long)n);
-    const size_t need = wire_view(wire_plan(desc), n, WIRE_WS_TRAIN, nullptr).total;
-    INR_REQUIRE(workspace && workspace_bytes >= need, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
-                workspace ? workspace_bytes : (size_t)0, need);
+    p = wire_plan(desc);
+    v = wire_view(p, n, WIRE_WS_TRAIN, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
+                workspace ? workspace_bytes : (size_t)0, v.total);
     INR_REQUIRE(aligned16(params) && aligned16(grads) && aligned16(workspace), INR_E_ALIGN,
                 "%s: params, grads and workspace must be 16-byte aligned", who);
     return 0;
 }
 
-// the two halves of the input gradient share their refusals: `a`, `b` are the call's two row arrays
+// the two halves of the input gradient share their refusals (and so their view): `a`, `b` are the call's two row arrays
 int wire_check_stash(const char* who, const inr_wire_desc_t* desc, const void* params, const void* a, const void* b, int64_t n,
-                     const void* workspace, size_t workspace_bytes) {
+                     void* workspace, size_t workspace_bytes, WirePlan& p, WireView& v) {
     if (int rc = wire_check_desc(who, desc)) return rc;
     INR_REQUIRE(params && a && b, INR_E_INVALID, "%s: null pointer", who);
     INR_REQUIRE(n >= 1 && n <= WIRE_MAX_STASH_ROWS, INR_E_INVALID, "%s: bad row count %lld", who, (long long)n);
-    const size_t need = wire_view(wire_plan(desc), n, WIRE_WS_INPUT_GRAD, nullptr).total;
-    INR_REQUIRE(workspace && workspace_bytes >= need, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
-                workspace ? workspace_bytes : (size_t)0, need);
+    p = wire_plan(desc);
+    v = wire_view(p, n, WIRE_WS_INPUT_GRAD, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
+                workspace ? workspace_bytes : (size_t)0, v.total);
     INR_REQUIRE(aligned16(params) && aligned16(workspace), INR_E_ALIGN, "%s: params and workspace must be 16-byte aligned", who);
     return 0;
 }
@@ -684,9 +693,7 @@ int inr_wire_param_offsets(const inr_wire_desc_t* desc, int64_t* offsets, int ma
 
 size_t inr_wire_layer_workspace_bytes(int64_t n, int in_features, int out_features) {
     if (n < 1 || n > WIRE_MAX_ROWS || in_features < 1 || in_features > 1024 || out_features < 32 || out_features > 256) return 0;
-    const size_t K = round_up((size_t)in_features, WIRE_KB);
-    return (round_up((size_t)n * K, 64) + round_up(4 * (size_t)out_features * K, 64) + round_up(4 * (size_t)out_features, 64)) *
-           sizeof(float);
+    return wire_layer_view(n, (int)round_up((size_t)in_features, WIRE_KB), out_features, nullptr).total;
 }
 
 // INRmodel.py:109-120 `ComplexGaborLayer2D.forward` of one layer.  is_first: x [n][in] real, real weights; else x [n][2H] planes
@@ -705,17 +712,14 @@ int inr_wire_layer_forward(float* out, const float* x, const float* lin_w, const
     INR_REQUIRE(n >= 0 && n <= WIRE_MAX_ROWS, INR_E_INVALID, "inr_wire_layer_forward: bad row count %lld", (long long)n);
     INR_REQUIRE(std::isfinite(omega) && std::isfinite(scale), INR_E_INVALID, "inr_wire_layer_forward: omega / scale must be finite");
     if (n == 0) return 0;
-    const int fin = is_first ? in_features : 2 * H;
-    const size_t need = inr_wire_layer_workspace_bytes(n, fin, H);
-    INR_REQUIRE(workspace && workspace_bytes >= need, INR_E_WORKSPACE, "inr_wire_layer_forward: workspace too small (%zu bytes, %zu needed)",
-                workspace ? workspace_bytes : (size_t)0, need);
+    const int K = (int)round_up((size_t)(is_first ? in_features : 2 * H), WIRE_KB);
+    const WireView v = wire_layer_view(n, K, H, workspace);
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "inr_wire_layer_forward: workspace too small (%zu bytes, %zu needed)",
+                workspace ? workspace_bytes : (size_t)0, v.total);
     INR_REQUIRE(aligned16(workspace) && aligned16(out) && aligned16(x), INR_E_ALIGN,
                 "inr_wire_layer_forward: out, x and workspace must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    const int K = (int)round_up((size_t)fin, WIRE_KB);
-    float* x0 = (float*)workspace;
-    float* img = x0 + round_up((size_t)n * K, 64);
-    float* pb = img + round_up(4 * (size_t)H * K, 64);
+    float *const x0 = v.x0, *const img = v.img[0], *const pb = v.pb[0];
     const float* in = x;
     if (is_first) {
         hipLaunchKernelGGL(wire_pack_first_kernel, dim3(wire_blocks((long long)H * K)), dim3(256), 0, st, img, pb, lin_w, lin_b, orth_w,
@@ -767,8 +771,7 @@ size_t inr_wire_reconstruct_workspace_bytes(const inr_wire_desc_t* desc, int64_t
         set_error("inr_wire_reconstruct_workspace_bytes: bad chunk_rows %lld", (long long)chunk_rows);
         return 0;
     }
-    const WirePlan p = wire_plan(desc);
-    return round_up((size_t)chunk_rows * p.in_f * sizeof(float), 256) + wire_view(p, chunk_rows, WIRE_WS_INFER, nullptr).total;
+    return wire_view(wire_plan(desc), chunk_rows, WIRE_WS_INFER, nullptr, true).total;
 }
 
 // wiretest.ipynb cell 9-10: get_mgrid -> input_mapping -> INR.forward -> torch.clamp(min=0), on chunks of the grid
@@ -792,14 +795,12 @@ int inr_wire_reconstruct(const inr_wire_desc_t* desc, const float* params, const
         INR_REQUIRE(total <= WIRE_MAX_ROWS, INR_E_INVALID, "inr_wire_reconstruct: the grid has too many rows");
     }
     const WirePlan p = wire_plan(desc);
-    const size_t feat_b = round_up((size_t)chunk_rows * p.in_f * sizeof(float), 256);
-    const size_t need = feat_b + wire_view(p, chunk_rows, WIRE_WS_INFER, nullptr).total;
-    INR_REQUIRE(workspace && workspace_bytes >= need, INR_E_WORKSPACE, "inr_wire_reconstruct: workspace too small (%zu bytes, %zu needed)",
-                workspace ? workspace_bytes : (size_t)0, need);
+    const WireView v = wire_view(p, chunk_rows, WIRE_WS_INFER, workspace, true);
+    INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "inr_wire_reconstruct: workspace too small (%zu bytes, %zu needed)",
+                workspace ? workspace_bytes : (size_t)0, v.total);
     INR_REQUIRE(aligned16(params) && aligned16(workspace), INR_E_ALIGN,
                 "inr_wire_reconstruct: params and workspace must be 16-byte aligned");
-    float* feats = (float*)workspace;
-    const WireView v = wire_view(p, chunk_rows, WIRE_WS_INFER, (char*)workspace + feat_b);
+    float* const feats = v.feats;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = wire_pack(p, v, params, false, st)) return rc;
     for (int64_t r0 = 0; r0 < total; r0 += chunk_rows) {
@@ -815,9 +816,9 @@ int inr_wire_reconstruct(const inr_wire_desc_t* desc, const float* params, const
 // wiretest.ipynb cell 10: loss = ((INR.forward(model_input) - LR_ground_truth)**2).mean(); loss.backward()
 int inr_wire_loss_grad(const inr_wire_desc_t* desc, const float* params, float* grads, const float* x, const float* target,
                        const float* weight, int64_t n, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = wire_check_train("inr_wire_loss_grad", desc, params, grads, x, target, n, workspace, workspace_bytes)) return rc;
-    const WirePlan p = wire_plan(desc);
-    const WireView v = wire_view(p, n, WIRE_WS_TRAIN, workspace);
+    WirePlan p;
+    WireView v;
+    if (int rc = wire_check_train("inr_wire_loss_grad", desc, params, grads, x, target, n, workspace, workspace_bytes, p, v)) return rc;
     hipStream_t st = (hipStream_t)stream;
     INR_HIP(hipMemsetAsync(grads, 0, (size_t)p.total * sizeof(float), st));      // the padding between tensors
     if (int rc = wire_pad_rows(p, v, x, n, st)) return rc;
@@ -828,9 +829,9 @@ int inr_wire_loss_grad(const inr_wire_desc_t* desc, const float* params, float* 
 // backward needs left in the workspace.  The kernels of inr_wire_loss_grad's forward: y is bit-equal with inr_wire_forward's.
 int inr_wire_forward_stash(const inr_wire_desc_t* desc, const float* params, const float* x, int64_t n, float* y, void* workspace,
                            size_t workspace_bytes, void* stream) {
-    if (int rc = wire_check_stash("inr_wire_forward_stash", desc, params, x, y, n, workspace, workspace_bytes)) return rc;
-    const WirePlan p = wire_plan(desc);
-    const WireView v = wire_view(p, n, WIRE_WS_INPUT_GRAD, workspace);
+    WirePlan p;
+    WireView v;
+    if (int rc = wire_check_stash("inr_wire_forward_stash", desc, params, x, y, n, workspace, workspace_bytes, p, v)) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = wire_pack(p, v, params, true, st)) return rc;
     if (int rc = wire_pad_rows(p, v, x, n, st)) return rc;
@@ -842,9 +843,9 @@ int inr_wire_forward_stash(const inr_wire_desc_t* desc, const float* params, con
 // is formed -- the notebook's next inr_optim.zero_grad() would discard it.
 int inr_wire_input_grad(const inr_wire_desc_t* desc, const float* params, const float* gy, int64_t n, float* dx, void* workspace,
                         size_t workspace_bytes, void* stream) {
-    if (int rc = wire_check_stash("inr_wire_input_grad", desc, params, gy, dx, n, workspace, workspace_bytes)) return rc;
-    const WirePlan p = wire_plan(desc);
-    const WireView v = wire_view(p, n, WIRE_WS_INPUT_GRAD, workspace);
+    WirePlan p;
+    WireView v;
+    if (int rc = wire_check_stash("inr_wire_input_grad", desc, params, gy, dx, n, workspace, workspace_bytes, p, v)) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int H = p.H;
     const long long work = (long long)n * H;
@@ -868,14 +869,14 @@ int inr_wire_input_grad(const inr_wire_desc_t* desc, const float* params, const 
 int inr_wire_fit(const inr_wire_desc_t* desc, float* params, float* grads, float* m, float* v_, const float* x, const float* target,
                  const float* weight, int64_t n, int64_t first_step, int n_steps, double lr, double beta1, double beta2, double eps,
                  float* losses, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = wire_check_train("inr_wire_fit", desc, params, grads, x, target, n, workspace, workspace_bytes)) return rc;
+    WirePlan p;
+    WireView v;
+    if (int rc = wire_check_train("inr_wire_fit", desc, params, grads, x, target, n, workspace, workspace_bytes, p, v)) return rc;
     INR_REQUIRE(m && v_, INR_E_INVALID, "inr_wire_fit: null Adam state");
     INR_REQUIRE(first_step >= 1 && n_steps >= 0, INR_E_INVALID, "inr_wire_fit: first_step >= 1 and n_steps >= 0 (got %lld, %d)",
                 (long long)first_step, n_steps);
     INR_REQUIRE(aligned16(m) && aligned16(v_), INR_E_ALIGN, "inr_wire_fit: m and v must be 16-byte aligned");
     if (n_steps == 0) return 0;
-    const WirePlan p = wire_plan(desc);
-    const WireView v = wire_view(p, n, WIRE_WS_TRAIN, workspace);
     hipStream_t st = (hipStream_t)stream;
     INR_HIP(hipMemsetAsync(grads, 0, (size_t)p.total * sizeof(float), st));
     if (int rc = wire_pad_rows(p, v, x, n, st)) return rc;
