@@ -341,6 +341,28 @@ int inr_acquisition_products(float* out, const float* raw_b0, const float* raw_b
 int inr_rescale2d_linear(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
                          void* stream);
 
+/* ---- (f)-3: skimage 0.20 resize for 2-D images: down-scaling with the anti-aliasing Gaussian, orders 1 and 3 --------------------
+ * Replaces rescale(x, .5, anti_aliasing=True) of prepare_qual_images.py:152,198,207,267 (order 1, mode 'reflect') and
+ * rescale(X, scale=3, order=3, mode='edge', anti_aliasing=False, multichannel=True, preserve_range=True) of
+ * multi-image-super-resolution/utils/preprocessing.py:271-294 (bicubic), through the scipy calls skimage makes:
+ * ndi.gaussian_filter(img, max(0, (f - 1)/2), mode=M) when anti_aliasing != 0, f = in/out per axis (radius int(4 sigma + .5), at most
+ * INR_RESCALE_MAX_RADIUS: INR_E_INVALID beyond), then ndi.zoom(., 1/f, order, mode=M, grid_mode=True) -- order 3 with scipy's
+ * mirror-start B-spline prefilter, behind a 12-sample edge pad for M = 'nearest' -- then skimage's clip to the input's range.
+ * mode: INR_RESCALE_REFLECT (skimage 'reflect' = scipy 'mirror') or INR_RESCALE_EDGE ('edge' = 'nearest'); order: 1 or 3.
+ * in [n_images][H][W] fp32 -> out [n_images][OH][OW] fp32, fp64 arithmetic; every size 1..INR_RESCALE_MAX_LINE.
+ * clip_group: 0 = no clip; else n_images is a multiple of it and every run of clip_group consecutive images is clamped to the
+ * minimum and maximum of its own inputs (the images of one skimage call: 1 for a 2-D call, T for an (H, W, T) item of bicubic).
+ * workspace: inr_rescale2d_workspace_doubles(...) doubles (the filtered plane, the padded coefficient plane, the min/max slots),
+ * 16-byte aligned; 0 for arguments inr_rescale2d would refuse.  Plain launches, fixed-order reductions: calls are bit-equal.
+ * inr_rescale2d_linear below is unchanged and stays the path of up-scaling calls. */
+#define INR_RESCALE_REFLECT 0
+#define INR_RESCALE_EDGE 1
+#define INR_RESCALE_MAX_RADIUS 64
+#define INR_RESCALE_MAX_LINE 4096
+int64_t inr_rescale2d_workspace_doubles(int n_images, int height, int width, int order, int mode);
+int inr_rescale2d(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width, int order,
+                  int mode, int anti_aliasing, int clip_group, double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- (f)-3: the through-plane spline baseline (SRDWI.py:132-141 resize_array, used at superresDWI.py:231) -------------------
  * scipy.interpolate.interp1d(linspace(0, 1, n_in), y, kind='cubic') evaluated at linspace(0, 1, n_out): make_interp_spline(k=3),
  * not-a-knot end conditions, fp64 throughout.  in [n_lines][n_in] -> out [n_lines][n_out] (the last axis is contiguous:

@@ -22,6 +22,7 @@ INR_PIA_LF_COUNT = 4
 INR_JET_LF_INPUT, INR_JET_LF_LAYER, INR_JET_LF_HEAD, INR_JET_LF_COUNT = 0, 1, 2, 3
 INR_LF_ERD_STEP, INR_LF_ERD_REDUCE, INR_LF_ERD_FORWARD, INR_LF_ERD_SOFT = 32, 33, 34, 35
 INR_ERD_RUNNING, INR_ERD_CONVERGED, INR_ERD_COLLAPSED = 0, 1, 2
+INR_RESCALE_REFLECT, INR_RESCALE_EDGE, INR_RESCALE_MAX_RADIUS, INR_RESCALE_MAX_LINE = 0, 1, 64, 4096
 
 
 class InrHipError(RuntimeError):
@@ -127,6 +128,9 @@ SIGNATURES = {
     "inr_acquisition_products": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, C.c_int,
                                            c_stream]),
     "inr_rescale2d_linear": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_stream]),
+    "inr_rescale2d_workspace_doubles": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "inr_rescale2d": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                C.c_void_p, C.c_int64, c_stream]),
     "inr_adc_map": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_resize_z_cubic_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "inr_resize_z_cubic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, c_stream]),

@@ -4,8 +4,16 @@
 master.py:175 for up-scaling 2-D images: default order 1, mode 'reflect' -- which skimage 0.20 evaluates as
 ``scipy.ndimage.zoom(image, scale, order=1, mode='mirror', grid_mode=True)``; the anti-aliasing Gaussian has sigma
 ``max(0, (1/scale - 1)/2) = 0`` when ``scale >= 1``.  scikit-image itself is not installed in the build image: parity with
-skimage is therefore UNPINNED; the kernel is pinned against the scipy call skimage makes (tests).  Down-scaling (a real
-anti-aliasing filter) is not needed by the drivers and is rejected.
+skimage is therefore UNPINNED; the kernel is pinned against the scipy call skimage makes (tests).  ``rescale`` serves
+``scale >= 1`` only and refuses the rest, as it always has.
+
+``resize`` and ``rescale2d`` are skimage 0.20's ``resize`` / ``rescale`` for 2-D images in full (``inr_rescale2d``): the
+anti-aliasing Gaussian of a down-scale (``scipy.ndimage.gaussian_filter(img, max(0, (f - 1)/2))``, ``f = in/out`` from the rounded
+shapes), orders 1 and 3 (``scipy.ndimage.zoom(., 1/f, order, grid_mode=True)``, the cubic with scipy's B-spline prefilter), modes
+'reflect' (scipy 'mirror') and 'edge' (scipy 'nearest'), and the clip to the input's range.  They serve
+``rescale(x, .5, anti_aliasing=True)`` of prepare_qual_images.py:152,198,207,267 and ``bicubic`` of
+multi-image-super-resolution/utils/preprocessing.py:271-294.  Pinned to that scipy composition, like ``rescale``; skimage itself
+is not.
 
 ``resize_z`` is ``resize_array(arr, new_size, kind='cubic')`` (SRDWI.py:132-141), the through-plane baseline of
 superresDWI.py:231: scipy's ``interp1d(kind='cubic')`` -- a not-a-knot cubic spline -- along the last axis, in fp64
@@ -38,6 +46,60 @@ def rescale(image, scale, anti_aliasing: bool = True):
           "inr_rescale2d_linear")
     out = out.reshape(*x.shape[:-2], oh, ow)
     return out.cpu().numpy().astype(np.float64) if as_numpy else out
+
+
+_MODES = {"reflect": 0, "edge": 1}       # INR_RESCALE_REFLECT, INR_RESCALE_EDGE (include/inrhip.h)
+
+
+def _resize(who, image, out_hw, order, mode, anti_aliasing, clip, group_axes=None):
+    """The trailing two axes of ``image`` re-sampled to ``out_hw``; the images are clipped in groups of the product of the last
+    ``group_axes`` leading axes (None: all of them, one group)."""
+    if order not in (1, 3):
+        raise ValueError(f"{who}: order must be 1 or 3 (got {order!r})")
+    if mode not in _MODES:
+        raise ValueError(f"{who}: mode must be 'reflect' or 'edge' (got {mode!r})")
+    as_numpy = isinstance(image, np.ndarray)
+    x = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(ops.require_gpu()) if as_numpy else image
+    if not as_numpy and isinstance(x, torch.Tensor) and x.is_cuda:
+        x = x.contiguous()
+    ops._chk(x, "image")
+    if x.dim() < 2:
+        raise ValueError(f"{who} needs at least 2-D input")
+    h, w = int(x.shape[-2]), int(x.shape[-1])
+    oh, ow = (int(v) for v in out_hw)
+    if min(h, w, oh, ow) < 1:
+        raise ValueError(f"{who}: empty image or output shape ({h} x {w} -> {oh} x {ow})")
+    if anti_aliasing is None:
+        anti_aliasing = oh < h or ow < w                        # skimage: on exactly when an axis shrinks
+    flat = x.reshape(-1, h, w)
+    n = flat.shape[0]
+    out = torch.empty((n, oh, ow), dtype=torch.float32, device=x.device)
+    if n > 0:
+        lead = x.shape[:-2]
+        group = int(np.prod(lead if group_axes is None else lead[len(lead) - group_axes:], dtype=np.int64)) if clip else 0
+        need = lib().inr_rescale2d_workspace_doubles(n, h, w, order, _MODES[mode])
+        ws = torch.empty(max(int(need), 2), dtype=torch.float64, device=x.device)
+        check(lib().inr_rescale2d(out.data_ptr(), flat.data_ptr(), n, h, w, oh, ow, order, _MODES[mode], int(bool(anti_aliasing)),
+                                  group, ws.data_ptr(), ws.numel(), ops._stream()), "inr_rescale2d")
+    out = out.reshape(*x.shape[:-2], oh, ow)
+    return out.cpu().numpy().astype(np.float64) if as_numpy else out
+
+
+def resize(image, output_shape, order: int = 1, mode: str = 'reflect', anti_aliasing=None, clip: bool = True):
+    """``skimage.transform.resize`` (0.20) on the trailing two axes of ``image`` (ndarray in -> float64 ndarray out; device tensor
+    in -> fp32 device tensor): orders 1 and 3, modes 'reflect' and 'edge'; ``anti_aliasing=None`` switches the Gaussian on exactly
+    when an axis shrinks.  Leading axes are a batch that is clipped as ONE group (the minimum and maximum of all its images).
+    There is no CPU fallback."""
+    if len(output_shape) != 2:
+        raise ValueError("resize: output_shape is (rows, columns) of the trailing two axes")
+    return _resize("resize", image, output_shape, order, mode, anti_aliasing, clip)
+
+
+def rescale2d(image, scale, order: int = 1, mode: str = 'reflect', anti_aliasing: bool = False, clip: bool = True):
+    """``skimage.transform.rescale`` (0.20) for 2-D images -- what ``from skimage.transform import rescale`` of
+    prepare_qual_images.py resolves to.  The output shape is ``np.round(scale * shape)`` (half to even); the rest is ``resize``."""
+    out_hw = np.round(scale * np.asarray(image.shape[-2:], dtype=np.float64)).astype(np.int64)
+    return _resize("rescale2d", image, out_hw, order, mode, anti_aliasing, clip)
 
 
 def resize_z(arr, new_size: int = 128, kind: str = 'cubic'):

@@ -1469,6 +1469,25 @@ int inr_rescale2d_linear(float* out, const float* in, int n_images, int height, 
     return launch_rescale_linear(out, in, n_images, height, width, out_height, out_width, (hipStream_t)stream);
 }
 
+int64_t inr_rescale2d_workspace_doubles(int n_images, int height, int width, int order, int mode) {
+    if (rescale_check("inr_rescale2d_workspace_doubles", n_images, height, width, 1, 1, order, mode, 0, 0)) return 0;
+    return (int64_t)(rescale_view(n_images, height, width, order, mode, nullptr).total / sizeof(double));
+}
+
+int inr_rescale2d(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width, int order,
+                  int mode, int anti_aliasing, int clip_group, double* workspace, int64_t workspace_doubles, void* stream) {
+    INR_REQUIRE(out && in, INR_E_INVALID, "inr_rescale2d: null pointer");
+    if (int rc = rescale_check("inr_rescale2d", n_images, height, width, out_height, out_width, order, mode, anti_aliasing, clip_group))
+        return rc;
+    const RescaleView v = rescale_view(n_images, height, width, order, mode, workspace);
+    INR_REQUIRE(workspace && workspace_doubles >= 0 && (size_t)workspace_doubles * sizeof(double) >= v.total, INR_E_WORKSPACE,
+                "inr_rescale2d: workspace too small (%lld doubles, %zu needed)", workspace ? (long long)workspace_doubles : 0ll,
+                v.total / sizeof(double));
+    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "inr_rescale2d: workspace must be 16-byte aligned");
+    return launch_rescale2d(out, in, n_images, height, width, out_height, out_width, order, mode, anti_aliasing, clip_group, v,
+                            (hipStream_t)stream);
+}
+
 size_t inr_resize_z_cubic_workspace_bytes(int64_t n_lines, int n_in) {
     return resize_z_workspace_doubles(n_lines > 0 ? n_lines : 1, n_in > 0 ? n_in : 1) * sizeof(double);
 }

@@ -282,6 +282,15 @@ __device__ __forceinline__ float linspace_pm1(int64_t i, int64_t n) {
                        : fmaf(-step, static_cast<float>(n - 1 - i), 1.0f);
 }
 
+// scipy's 'mirror' boundary (skimage 'reflect'): reflection about the edge samples, period 2n - 2, any number of periods away
+__device__ __forceinline__ int mirror_index(int i, int n) {
+    if (n <= 1) return 0;
+    const int period = 2 * n - 2;
+    i %= period;
+    if (i < 0) i += period;
+    return i < n ? i : period - i;
+}
+
 // row of accumulator register r (0..15) of a 32 x 32 MFMA tile held by lane half hh = lane >> 5; the column is lane & 31
 __device__ __forceinline__ int mfma32_acc_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 

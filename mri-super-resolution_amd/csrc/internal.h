@@ -149,6 +149,15 @@ int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_
 int launch_adc(float* out, const float* data, const float* bvals, int64_t npix, int nb, hipStream_t st);
 int launch_auto_erd(float* accept, const double* values, const float* erd_map, int64_t npix, int n, int rule, hipStream_t st);
 
+// ---- rescale.hip: skimage resize for 2-D images (anti-aliasing Gaussian, orders 1 and 3, modes 'reflect' and 'edge') -------------------
+constexpr int RESCALE_MAX_RADIUS = INR_RESCALE_MAX_RADIUS;   // Gaussian taps per side that the kernel arguments carry
+constexpr int RESCALE_MAX_LINE = INR_RESCALE_MAX_LINE;       // one padded line, staged in LDS as doubles, fits 64 KiB
+struct RescaleView { double *filtered, *coef, *minmax; size_t total; };
+RescaleView rescale_view(int nimg, int H, int W, int order, int mode, void* base);
+int rescale_check(const char* who, int nimg, int H, int W, int OH, int OW, int order, int mode, int anti_aliasing, int clip_group);
+int launch_rescale2d(float* out, const float* in, int nimg, int H, int W, int OH, int OW, int order, int mode, int anti_aliasing,
+                     int clip_group, const RescaleView& v, hipStream_t st);
+
 // ---- cssim.hip: the shift-tolerant SSIM of the RAMS tree (utils/loss.py:131-177) and its gradient ---------------------------------------
 int cssim_min_crop();   // the cropped window must hold one 11 x 11 filter window
 size_t cssim_workspace_doubles(int nimg, int size, int border, bool grad);

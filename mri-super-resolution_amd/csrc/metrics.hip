@@ -274,14 +274,6 @@ int launch_shift_loss_grad(double* loss, float* grad, const float* y_true, const
 // skimage 0.20 resize -> scipy.ndimage.zoom(img, out/in, order=1, mode='mirror', grid_mode=True) (the anti-aliasing sigma
 // max(0, (1/s - 1)/2) is 0 when up-scaling): out[o] = (1 - f) in[m(i)] + f in[m(i + 1)], x = (o + 0.5) in/out - 0.5,
 // i = floor(x), f = x - i, m = reflection about the edge samples (period 2n - 2).  Coordinates and weights in double.
-__device__ __forceinline__ int mirror_index(int i, int n) {
-    if (n <= 1) return 0;
-    const int period = 2 * n - 2;
-    i %= period;
-    if (i < 0) i += period;
-    return i < n ? i : period - i;
-}
-
 __global__ void __launch_bounds__(256) rescale_linear_kernel(float* __restrict__ out, const float* __restrict__ in, int nimg, int H,
                                                              int W, int OH, int OW) {
     const long long total = (long long)nimg * OH * OW;

@@ -774,3 +774,74 @@ def erd_inr_case(case, seed, scale=1, hidden_features=128, hidden_layers=3, pret
     info = {"pretrain": pre, "finetune_loss": float(losses[-1]) if finetune_steps else float("nan"), "noise_level": float(level),
             "mean_recon": mean_recon, "model": model}
     return rows, info
+
+
+# ---------------------------------------------------------------------------------------------------
+# prepare_qual_images.py:147-300 -- the low-resolution (reader) study of one slice: fit the soft-ERD INR to the half-resolution
+# acquisitions, re-sample it on the full grid, and set it beside the low-resolution image, its interpolation and the full image
+# ---------------------------------------------------------------------------------------------------
+QUAL_PANELS = ("low", "interpolated", "SR", "base")
+
+
+def low_res_study(case, slice_index, seed, hidden_features=128, hidden_layers=3, pretrain_lr=3e-4, threshold=2e-5,
+                  max_steps=None, finetune_steps=502, lr_perturb=1e-5, lr_net=1e-7, perturb_eps=1.0 / 128.0, mul=1000, slope=20):
+    """``case`` as for ``erd_inr_case``; ``slice_index`` the slice of ``b0`` [X, Y, Z] / ``b3`` [X, Y, Z, K] to study.  Returns
+    ``(maps, label, info)``:
+
+    ``maps``: float64 images ``low`` (the acquisition mean down-scaled by 0.5 with the anti-aliasing Gaussian,
+    ``baselines.rescale2d``), ``interpolated`` (``low`` re-sampled linearly to the full grid), ``SR`` (the mean over acquisitions of the
+    fitted network on the full grid) and ``base`` (the acquisition mean itself), and the ADC maps ``adc_low, adc_interpolated,
+    adc_superres, adc_gold`` of prepare_qual_images.py:266-273 -- the two full-grid ones of the low-resolution data against the
+    down- and up-scaled ``b0``, the gold one against ``b0``.
+    ``label``: ``{"pt", "image", "1" .. "4"}``, the row of ``labels.csv`` without its file name: the four panel names in an order
+    drawn from ``random.Random`` seeded with (``seed``, patient, slice).
+    ``info``: what the fit did.
+
+    The model is pre-trained on ``low`` (threshold 2e-5), the soft-ERD weights come from the low-resolution stack with the noise
+    level of the FULL-resolution ``b3`` at the cancer slice (as the script takes it), and ``finetune_steps`` = 502 steps run at
+    1e-5 / 1e-7 with ``eps = 1/128``.  As in ``erd_inr_case``: targets are normalised pixel -> 2 pixel - 1 (nn_mri.py:174-180) and
+    the network's output is used as it is; a pre-training step that both converges and collapses counts as a collapse.
+    Where this differs from the script: the full grid is the slice's own shape, not the constant 128 (the two coincide on the
+    script's 128 x 128 data), so ``interpolated`` and the up-scaled ``b0`` are ``resize`` to that shape -- ``rescale(., 2)`` whenever
+    the sides are even; the script's unseeded ``random.sample`` is seeded; and the PNG figure is not drawn."""
+    import random
+
+    from . import baselines, erd_inr
+
+    dev = ops.require_gpu()
+    sl = int(slice_index)
+    b = case.b[3]
+    b0 = np.asarray(case.b0[:, :, sl], dtype=np.float64)
+    dwi = np.asarray(case.b3[:, :, sl, :], dtype=np.float64)
+    K = dwi.shape[-1]
+    base = dwi.mean(-1)
+    # every image is a skimage call of its own (its own clip range): the mean, the K acquisitions, b0 -- one launch chain
+    stack = np.concatenate([base[None], np.moveaxis(dwi, -1, 0), b0[None]])
+    out_hw = np.round(0.5 * np.asarray(base.shape, dtype=np.float64)).astype(np.int64)
+    lows = baselines._resize("low_res_study", stack, out_hw, 1, "reflect", True, True, group_axes=0)
+    low, low_all, b0_low = lows[0], np.moveaxis(lows[1:K + 1], 0, -1), lows[K + 1]
+    level = erd_inr.noise_level(case.b3, case.noise, case.cancer_slice)
+    weights, _ = erd_inr.soft_erd(low_all, b0_low, level, mul=mul, slope=slope)
+
+    model = erd_inr.ErdSiren(in_features=2, out_features=1, hidden_features=hidden_features, hidden_layers=hidden_layers,
+                             perturb=True).to(dev)
+    fitter = erd_inr.ErdFitter(model)
+    coords = ops.mgrid(low.shape)
+    norm = lambda a: torch.from_numpy(2.0 * np.asarray(a, dtype=np.float32) - 1.0).reshape(-1).to(dev)      # noqa: E731
+    pre = fitter.pretrain(coords, norm(low), lr=pretrain_lr, threshold=threshold, max_steps=max_steps)
+    targets = torch.stack([norm(low_all[:, :, a]) for a in range(K)])
+    wts = torch.stack([torch.from_numpy(weights[:, :, a].astype(np.float32)).reshape(-1) for a in range(K)]).to(dev)
+    losses = fitter.finetune(coords, targets, wts, steps=finetune_steps, lr_perturb=lr_perturb, lr_net=lr_net, eps=perturb_eps)
+    sr = fitter.mean_reconstruction(base.shape, K, eps=perturb_eps)
+
+    ups = baselines._resize("low_res_study", np.stack([low, b0_low]), base.shape, 1, "reflect", True, True, group_axes=0)
+    interpolated, b0_up = ups[0], ups[1]
+    maps = {"low": low, "interpolated": interpolated, "SR": sr, "base": base,
+            "adc_low": erd_inr.calc_adc(low, b0_low, b), "adc_interpolated": erd_inr.calc_adc(interpolated, b0_up, b),
+            "adc_superres": erd_inr.calc_adc(sr, b0_up, b), "adc_gold": erd_inr.calc_adc(base, b0, b)}
+    order = random.Random(f"{seed}:{case.pt_id}:{sl}").sample(range(4), 4)          # prepare_qual_images.py:276
+    label = {"pt": case.pt_id, "image": str(sl)}
+    label.update({str(order[k] + 1): QUAL_PANELS[k] for k in range(4)})
+    info = {"pretrain": pre, "finetune_loss": float(losses[-1]) if finetune_steps else float("nan"), "noise_level": float(level),
+            "b0_low": b0_low, "b0_up": b0_up, "model": model}
+    return maps, label, info
