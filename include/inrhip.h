@@ -659,8 +659,9 @@ int inr_jet_launch_count(int family, int64_t* count);
  * linear.bias, scale_orth.weight, scale_orth.bias, layers front to back, then the head's weight and bias.
  * Served: out_features == 1, hidden_features in {32, 64, 128, 256}, 0 <= hidden_layers <= 8, 1 <= in_features <= 1024;
  * anything else, and a null desc / params / x / y, is INR_E_INVALID before any device work; a null or short workspace is
- * INR_E_WORKSPACE, a pointer off a 16-byte boundary INR_E_ALIGN.  Arithmetic: f32-input MFMA 32x32x2 only;
- * plain launches, fixed-order reductions, no float atomics: repeated calls are bit-equal.  Every call only enqueues. */
+ * INR_E_WORKSPACE, a pointer off a 16-byte boundary INR_E_ALIGN.  Arithmetic: f32-input MFMA only, 32x32x2 and, in the
+ * derivative kernels (inr_wire_derivatives), 16x16x4; plain launches, fixed-order reductions, no float atomics:
+ * repeated calls are bit-equal.  Every call only enqueues. */
 typedef struct {
     int   in_features, hidden_features, hidden_layers, out_features;
     float first_omega, hidden_omega, first_scale, hidden_scale;
@@ -714,6 +715,39 @@ int inr_wire_forward_stash(const inr_wire_desc_t* desc, const float* params, con
                            void* workspace, size_t workspace_bytes, void* stream);
 int inr_wire_input_grad(const inr_wire_desc_t* desc, const float* params, const float* gy, int64_t n, float* dx,
                         void* workspace, size_t workspace_bytes, void* stream);
+/* Spatial derivatives of a fitted WIRE network (nn_mri.py:205-221 `gradient`, `divergence`, `laplace` applied to the stack of
+ * wiretest.ipynb cell 2, which leaves its `detach()` commented out): the reference takes two torch.autograd.grad passes with
+ * create_graph=True; these entry points evaluate the same quantities in FORWARD mode, without a stash and without autograd.  Per
+ * row and layer they carry the value, one tangent per coordinate axis and a Laplacian accumulator as planes [hr | hi], every plane
+ * multiplied by the layer's block image on the f32-input MFMA (v_mfma_f32_16x16x4_f32) and combined in registers.
+ *   y[n]               = Re head(layers(features(x)))                  (the raw network value, no clamp)
+ *   grad[n][d_tangent] = d y / d x_i, i < d_tangent                    (nullable)
+ *   lap[n]             = sum_{i < d_tangent} d^2 y / d x_i^2           (nullable; without it the accumulator is neither computed
+ *                                                                       nor carried)
+ * Semantics of inr_siren_jet / inr_siren_jet_grid: x[n][d] are the [-1, 1] coordinates of inr_mgrid (multiply a first derivative
+ * along axis a by 2 / (shape[a] - 1), a second one by its square, for per-voxel units); B == NULL feeds the coordinates to the
+ * network (in_features == d), otherwise features = [sin(2 pi x B^T) | cos(2 pi x B^T)], B[m][d], in_features == 2 m;
+ * d_tangent names the LEADING axes to differentiate along (1 <= d_tangent <= d <= 4).  `params` is the flat buffer of
+ * inr_wire_param_offsets.  Rows are processed `chunk_rows` at a time in `workspace`, which is counted in FLOATS
+ * (inr_wire_derivatives_workspace_floats(desc, d, m, min(chunk_rows, n), want_laplacian), m = 0 without B; sized for d tangents,
+ * so it serves every d_tangent): the layers' block images, the input jets and two buffers of planes the layers write in turn.
+ * A row's bits depend neither on the chunk size, nor on its place in a chunk, nor on which of grad / lap were asked for, and
+ * repeated calls are bit-equal (fixed summation order, no float atomics).  y agrees with inr_wire_forward to rounding, not bit for
+ * bit (another tile shape).  Both calls only enqueue.
+ * Served: what inr_wire_forward serves, with 1 <= d <= 4; anything else, and a null desc / params / x / shape / y, is
+ * INR_E_INVALID with a message before any device work; a null or short workspace is INR_E_WORKSPACE, a params or workspace
+ * pointer off a 16-byte boundary INR_E_ALIGN, likewise before any device work. */
+int64_t inr_wire_derivatives_workspace_floats(const inr_wire_desc_t* desc, int d, int m, int64_t chunk_rows,
+                                              int want_laplacian);   /* 0 for what is not served */
+/* on explicit coordinate rows: replaces gradient(y, x) / laplace(y, x) over y = INR(input_mapping(x, B)) */
+int inr_wire_derivatives(const inr_wire_desc_t* desc, const float* params, const float* x, int64_t n, int d, int d_tangent,
+                         const float* B, int m, float* y, float* grad, float* lap, int64_t chunk_rows, void* workspace,
+                         int64_t workspace_floats, void* stream);
+/* the same on the dense grid get_mgrid(shape) (dim == d axes), coordinates generated in the kernels as by inr_wire_reconstruct.
+ * Bit-equal with inr_wire_derivatives on the rows of inr_mgrid(shape). */
+int inr_wire_derivatives_grid(const inr_wire_desc_t* desc, const float* params, const int64_t* shape, int dim, int d_tangent,
+                              const float* B, int m, float* y, float* grad, float* lap, int64_t chunk_rows, void* workspace,
+                              int64_t workspace_floats, void* stream);
 
 /* ---- measurement hooks (bench.py roofline): per-kernel-class HIP-event timing on the launch stream.
  * class ids: 0 = GEMM forward (sine layer), 1 = GEMM input-grad, 2 = GEMM param-grad, 3 = other */

@@ -221,6 +221,11 @@ SIGNATURES = {
                                C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "inr_wire_forward_stash": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
     "inr_wire_input_grad": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, C.c_int64, c_f32p, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_wire_derivatives_workspace_floats": (C.c_int64, [C.POINTER(WireDesc), C.c_int, C.c_int, C.c_int64, C.c_int]),
+    "inr_wire_derivatives": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p,
+                                       c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "inr_wire_derivatives_grid": (C.c_int, [C.POINTER(WireDesc), c_f32p, c_i64p, C.c_int, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p,
+                                            c_f32p, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
     "inr_prof_enable": (C.c_int, [C.c_int]),
     "inr_prof_reset": (C.c_int, []),
     "inr_prof_read": (C.c_int, [C.c_int, c_i64p, C.POINTER(C.c_double)]),

@@ -8,7 +8,7 @@ import _bootstrap  # noqa: F401
 from mri_super_resolution_amd import inr as _inr  # noqa: E402
 from mri_super_resolution_amd.contrast import calculate_contrast, case, cases, save_dicom  # noqa: F401,E402
 from mri_super_resolution_amd.inr import ImageFitting_set, SineLayer, get_mgrid, input_mapping  # noqa: F401,E402
-# nn_mri.py:205-221: `gradient` / `divergence` are the autograd forms; `laplace` serves direct Siren outputs (see its docstring)
+# nn_mri.py:205-221: `gradient` / `divergence` are the autograd forms; `laplace` serves direct Siren and Wire outputs (see its docstring)
 from mri_super_resolution_amd.inr import divergence, gradient, laplace  # noqa: F401,E402
 
 

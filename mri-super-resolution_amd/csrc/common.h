@@ -282,6 +282,31 @@ __device__ __forceinline__ float linspace_pm1(int64_t i, int64_t n) {
                        : fmaf(-step, static_cast<float>(n - 1 - i), 1.0f);
 }
 
+// the coordinates of one row of the derivative kernels (jet.hip, wire_deriv.hip; d <= JET_MAX_D axes): the inr_mgrid rule (last axis
+// fastest, bit-exact linspace) or the caller's matrix x [.][d]
+constexpr int JET_MAX_D = 4;
+struct JetGrid {
+    long long n[JET_MAX_D];
+};
+template <bool FROM_GRID>
+__device__ __forceinline__ void jet_coords(float* c, const float* __restrict__ x, const JetGrid& g, int d, long long row) {
+    if (FROM_GRID) {
+        long long rem = row;
+#pragma unroll
+        for (int a = JET_MAX_D - 1; a >= 0; --a) {
+            c[a] = 0.f;
+            if (a < d) {
+                const long long idx = rem % g.n[a];
+                rem /= g.n[a];
+                c[a] = linspace_pm1(idx, g.n[a]);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int a = 0; a < JET_MAX_D; ++a) c[a] = (a < d) ? x[row * d + a] : 0.f;
+    }
+}
+
 // scipy's 'mirror' boundary (skimage 'reflect'): reflection about the edge samples, period 2n - 2, any number of periods away
 __device__ __forceinline__ int mirror_index(int i, int n) {
     if (n <= 1) return 0;

@@ -171,10 +171,26 @@ int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, cons
                       hipStream_t st);
 void set_hybrid_variant(int v);   // key 2
 
-// (pia.hip, erd_siren.hip and jet.hip define public entry points only; their launch families are counted through count_launch in
-// api.hip's table like every other -- common.h: LF_PIA_BASE, LF_JET_BASE, and the ERD families at their public ids.)
+// (pia.hip and erd_siren.hip define public entry points only, and jet.hip little else; their launch families are counted through
+// count_launch in api.hip's table like every other -- common.h: LF_PIA_BASE, LF_JET_BASE, and the ERD families at their public ids.)
+
+// ---- jet.hip ------------------------------------------------------------------------------------------------------------------------------
+// the jets of the Fourier features [sin p | cos p], p = 2 pi x B^T: out [1 + dt + lap][.][pitch] planes `plane` floats apart (pitch
+// = 2m rounded up to 32, pad columns zero).  x != null: the rows x [n_rows][d]; else rows row_begin .. of the grid `shape` [d]
+int jet_launch_fourier(float* out, long long plane, int pitch, const float* x, const int64_t* shape, int d, int dt, int lap,
+                       int64_t row_begin, int64_t n_rows, const float* B, int m, hipStream_t st);
 
 // ---- wire.hip: the complex-Gabor (WIRE) layers in real arithmetic, f32-input MFMA 32x32x2 -------------------------------------------
+constexpr int WIRE_MAX_LAYERS = 9;          // 1 + hidden_layers
+struct WirePlan {
+    int in_f = 0, H = 0, L = 0, K0 = 0;       // L = hidden (complex) layers; K0 = in_f rounded up to the K block (32)
+    long long off[4 * WIRE_MAX_LAYERS + 2];   // inr_wire_param_offsets
+    long long total = 0;
+};
+int wire_check_desc(const char* who, const inr_wire_desc_t* d);      // what inr_wire_forward serves
+WirePlan wire_plan(const inr_wire_desc_t* d);
+// parameters -> the layers' block images img[l] ([2][H][K0] for l = 0, else [4][H][2H]) and packed biases pb[l] ([4][H]), l <= L
+int wire_pack_images(const WirePlan& p, float* const* img, float* const* pb, const float* params, hipStream_t st);
 // in [n][K] (K a multiple of 32) times the block image img [Q][H][K] (Q = 2 for the real first layer, else 4), Gabor epilogue:
 // out [n][2H] = [out_r | out_i]; stash (nullable) [n][Q H] receives lin_r (, lin_i), orth_r (, orth_i)
 int wire_gabor_forward(float* out, float* stash, const float* in, const float* img, const float* pb, int K, int H, int first,

@@ -20,7 +20,6 @@ namespace inr {
 
 namespace {
 
-constexpr int JET_MAX_D = 4;
 constexpr int JET_MAX_J = JET_MAX_D + 2;
 constexpr int JET_BM = 64, JET_BN = 64, JET_KB = 32;
 constexpr int JET_LDS = JET_KB + 4;     // LDS row pitch in floats: 144 B keeps the 16-byte fragment reads aligned and off one bank
@@ -28,30 +27,7 @@ constexpr int JET_THREADS = 256;
 constexpr int64_t JET_MAX_ROWS = (1ll << 31) - 256;
 constexpr float JET_TWO_PI = 6.283185307179586f;
 
-struct JetGrid {
-    long long n[JET_MAX_D];
-};
-
-// the d coordinates of one row: the inr_mgrid rule (last axis fastest, bit-exact linspace) or the caller's matrix
-template <bool FROM_GRID>
-__device__ __forceinline__ void jet_coords(float* c, const float* __restrict__ x, const JetGrid& g, int d, long long row) {
-    if (FROM_GRID) {
-        long long rem = row;
-#pragma unroll
-        for (int a = JET_MAX_D - 1; a >= 0; --a) {
-            c[a] = 0.f;
-            if (a < d) {
-                const long long idx = rem % g.n[a];
-                rem /= g.n[a];
-                c[a] = linspace_pm1(idx, g.n[a]);
-            }
-        }
-    } else {
-#pragma unroll
-        for (int a = 0; a < JET_MAX_D; ++a) c[a] = (a < d) ? x[row * d + a] : 0.f;
-    }
-}
-
+// (the d coordinates of one row: jet_coords, common.h)
 // ---- input: jets of the Fourier features.  One thread per (row, frequency); planes of `pitch` = 2m rounded up to the GEMM's K block,
 // the pad columns zero.  a = [sin p | cos p] with p accumulated exactly as fourier_kernel does.
 template <bool FROM_GRID>
@@ -363,14 +339,8 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
         const float* xc = x ? x + r0 * d : nullptr;
         int cur = 0, first_gemm;
         if (fourier) {
-            const long long plane = (long long)chunk * p.pitch0;
-            const long long work = rows * (p.pitch0 / 2);
-            if (x)
-                hipLaunchKernelGGL(jet_fourier_kernel<false>, dim3(jet_blocks(work)), dim3(256), 0, st, buf[0], plane, p.pitch0, xc, g,
-                                   d, dt, has_q, (long long)r0, rows, B, m);
-            else
-                hipLaunchKernelGGL(jet_fourier_kernel<true>, dim3(jet_blocks(work)), dim3(256), 0, st, buf[0], plane, p.pitch0, xc, g,
-                                   d, dt, has_q, (long long)r0, rows, B, m);
+            if (int rc = jet_launch_fourier(buf[0], (long long)chunk * p.pitch0, p.pitch0, xc, shape, d, dt, has_q, r0, rows, B, m, st))
+                return rc;
             first_gemm = 0;
         } else {
             const long long plane = (long long)chunk * H;
@@ -403,6 +373,23 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
 }
 
 }  // namespace
+
+// ---- launcher other units may call (internal.h) ----------------------------------------------------------------------------
+int jet_launch_fourier(float* out, long long plane, int pitch, const float* x, const int64_t* shape, int d, int dt, int lap,
+                       int64_t row_begin, int64_t n_rows, const float* B, int m, hipStream_t st) {
+    JetGrid g;
+    for (int a = 0; a < JET_MAX_D; ++a) g.n[a] = (shape && a < d) ? shape[a] : 1;
+    const dim3 grid(jet_blocks((long long)n_rows * (pitch / 2)));
+    if (x)
+        hipLaunchKernelGGL(jet_fourier_kernel<false>, grid, dim3(256), 0, st, out, plane, pitch, x, g, d, dt, lap,
+                           (long long)row_begin, (long long)n_rows, B, m);
+    else
+        hipLaunchKernelGGL(jet_fourier_kernel<true>, grid, dim3(256), 0, st, out, plane, pitch, x, g, d, dt, lap,
+                           (long long)row_begin, (long long)n_rows, B, m);
+    INR_LAUNCH_CHECK();
+    return 0;
+}
+
 }  // namespace inr
 
 using namespace inr;

@@ -30,7 +30,6 @@ constexpr int WIRE_BM = 64, WIRE_BN = 64, WIRE_KB = 32;
 constexpr int WIRE_LDS = WIRE_KB + 4;       // LDS row pitch in floats (144 B: 16-byte fragment reads, off one bank)
 constexpr int WIRE_PG_LDS = 64 + 4;         // parameter-gradient tiles are [k][64]
 constexpr int WIRE_THREADS = 256;
-constexpr int WIRE_MAX_LAYERS = 9;          // 1 + hidden_layers
 constexpr int64_t WIRE_MAX_ROWS = (1ll << 31) - 256;
 constexpr int WIRE_SLAB_ROWS = 2048;       // rows per parameter-gradient slab: more rows than this split the sum
 // (a slab per WIRE_SLAB_ROWS rows rides on a grid's y / z axis, which ends at 65,535; the input-gradient mode keeps the limit)
@@ -389,11 +388,7 @@ __global__ void __launch_bounds__(256) wire_fold_head_kernel(float* __restrict__
 // ------------------------------------------------------ host ------------------------------------------------------
 inline unsigned wire_blocks(long long work) { return (unsigned)((work + 255) / 256); }
 
-struct WirePlan {
-    int in_f = 0, H = 0, L = 0, K0 = 0;       // L = hidden (complex) layers
-    long long off[4 * WIRE_MAX_LAYERS + 2];
-    long long total = 0;
-};
+}  // namespace
 
 int wire_check_desc(const char* who, const inr_wire_desc_t* d) {
     INR_REQUIRE(d != nullptr, INR_E_INVALID, "%s: wire descriptor is null", who);
@@ -436,7 +431,25 @@ WirePlan wire_plan(const inr_wire_desc_t* d) {
     return p;
 }
 
+namespace {
+
 int wire_splits(int64_t n) { return (int)((n + WIRE_SLAB_ROWS - 1) / WIRE_SLAB_ROWS); }
+
+// the images of every layer (imgT nullable: training only, the complex layers' transposes)
+int wire_pack_layers(const WirePlan& p, float* const* img, float* const* imgT, float* const* pb, const float* params,
+                     hipStream_t st) {
+    const int H = p.H;
+    hipLaunchKernelGGL(wire_pack_first_kernel, dim3(wire_blocks((long long)H * p.K0)), dim3(256), 0, st, img[0], pb[0],
+                       params + p.off[0], params + p.off[1], params + p.off[2], params + p.off[3], H, p.in_f, p.K0);
+    INR_LAUNCH_CHECK();
+    for (int l = 1; l <= p.L; ++l) {
+        hipLaunchKernelGGL(wire_pack_complex_kernel, dim3(wire_blocks((long long)H * H)), dim3(256), 0, st, img[l],
+                           imgT ? imgT[l] : (float*)nullptr, pb[l], params + p.off[4 * l], params + p.off[4 * l + 1],
+                           params + p.off[4 * l + 2], params + p.off[4 * l + 3], H);
+        INR_LAUNCH_CHECK();
+    }
+    return 0;
+}
 
 // what a workspace holds: every region on a 256-byte boundary and at least one element long.  base == null: sizes only.
 struct WireView {
@@ -509,21 +522,16 @@ int wire_pack(const WirePlan& p, const WireView& v, const float* params, bool tr
                            params + p.off[0], params + p.off[2], H, p.in_f);
         INR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(wire_pack_first_kernel, dim3(wire_blocks((long long)H * p.K0)), dim3(256), 0, st, v.img[0], v.pb[0],
-                       params + p.off[0], params + p.off[1], params + p.off[2], params + p.off[3], H, p.in_f, p.K0);
-    INR_LAUNCH_CHECK();
-    for (int l = 1; l <= p.L; ++l) {
-        hipLaunchKernelGGL(wire_pack_complex_kernel, dim3(wire_blocks((long long)H * H)), dim3(256), 0, st, v.img[l],
-                           training ? v.imgT[l] : (float*)nullptr, v.pb[l], params + p.off[4 * l], params + p.off[4 * l + 1],
-                           params + p.off[4 * l + 2], params + p.off[4 * l + 3], H);
-        INR_LAUNCH_CHECK();
-    }
-    return 0;
+    return wire_pack_layers(p, v.img, training ? v.imgT : nullptr, v.pb, params, st);
 }
 
 }  // namespace
 
 // ---- launchers other units may call (internal.h) ---------------------------------------------------------------------------
+int wire_pack_images(const WirePlan& p, float* const* img, float* const* pb, const float* params, hipStream_t st) {
+    return wire_pack_layers(p, img, nullptr, pb, params, st);
+}
+
 int wire_gabor_forward(float* out, float* stash, const float* in, const float* img, const float* pb, int K, int H, int first,
                        int64_t n, float omega, float s2, hipStream_t st) {
     const dim3 grid((unsigned)((n + WIRE_BM - 1) / WIRE_BM), (unsigned)((H + WIRE_BN - 1) / WIRE_BN));

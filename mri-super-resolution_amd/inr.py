@@ -684,11 +684,15 @@ def divergence(y, x):
 
 
 def laplace(y, x):
-    """nn_mri.py:205-207 ``divergence(gradient(y, x), x)`` for a ``y`` that came straight out of this package's ``Siren`` on the
-    input ``x`` (which requires grad, ``x.shape[-1] <= 4``): ``Siren.forward`` records the model and the input on such an output,
-    and the Laplacian is evaluated by ``derivatives`` on that record -- the backward passes of the HIP autograd functions are
-    plain kernel calls and leave no graph to differentiate a second time.  Returns ``x.shape[:-1] + (1,)``, without a graph,
+    """nn_mri.py:205-207 ``divergence(gradient(y, x), x)`` for a ``y`` that came straight out of this package's ``Siren`` or
+    ``wire.Wire`` on the input ``x`` (which requires grad, ``x.shape[-1] <= 4``): their ``forward`` records the model and the input
+    on such an output, and the Laplacian is evaluated by ``derivatives`` (``wire.derivatives``) on that record -- the backward
+    passes of the HIP autograd functions are plain kernel calls and leave no graph to differentiate a second time.  Returns ``x.shape[:-1] + (1,)``, without a graph,
     in the units of ``x``.  Any other ``y`` raises ``TypeError``."""
+    origin = getattr(y, "_wire_origin", None)
+    if origin is not None and origin[0]() is not None and origin[1] is x:
+        from . import wire          # (wire imports this module)
+        return wire.derivatives(origin[0](), x).laplacian.unsqueeze(-1)
     origin = getattr(y, "_siren_origin", None)
     model = origin[0]() if origin is not None else None
     if model is None or origin[1] is not x:

@@ -416,6 +416,53 @@ def siren_jet(desc: SirenDesc, params, x=None, shape=None, B=None, d_tangent=Non
     return y, grad, lap
 
 
+def wire_derivatives(desc: _lib.WireDesc, params, x=None, shape=None, B=None, d_tangent=None, want_grad=True, want_lap=True,
+                     chunk_rows: int = 1 << 15):
+    """Value, coordinate gradient and Laplacian of a WIRE network in forward mode (``inr_wire_derivatives`` on the rows ``x``
+    [n, d], or ``inr_wire_derivatives_grid`` on ``get_mgrid(shape)``; exactly one of the two).  ``params`` is the flat buffer of
+    ``inr_wire_param_offsets``.  Returns ``(y [n], grad [n, d_tangent] or None, lap [n] or None)``; derivatives are taken along
+    the ``d_tangent`` leading axes (default: all ``d``)."""
+    if (x is None) == (shape is None):
+        raise ValueError("wire_derivatives takes exactly one of x and shape")
+    _chk(params, "params")
+    total = lib().inr_wire_param_count(C.byref(desc))
+    if total < 0:
+        check(int(total), "inr_wire_param_count")
+    if params.numel() != total:
+        raise ValueError(f"params has {params.numel()} floats, layout needs {total}")
+    if x is not None:
+        _chk(x, "x")
+        if x.dim() != 2:
+            raise ValueError(f"x {tuple(x.shape)} must be [n, d]")
+        n, d = int(x.shape[0]), int(x.shape[1])
+    else:
+        shape, n, _ = _grid_rows(shape)
+        d = len(shape)
+    m = 0
+    if B is not None:
+        _chk(B, "B")
+        if B.dim() != 2 or B.shape[1] != d:
+            raise ValueError(f"B {tuple(B.shape)} must be [m, {d}]")
+        m = int(B.shape[0])
+    dt = d if d_tangent is None else int(d_tangent)
+    chunk_rows = max(1, min(int(chunk_rows), max(n, 1)))
+    dev = params.device
+    y = torch.empty(n, dtype=torch.float32, device=dev)
+    grad = torch.empty((n, dt), dtype=torch.float32, device=dev) if want_grad else None
+    lap = torch.empty(n, dtype=torch.float32, device=dev) if want_lap else None
+    floats = int(lib().inr_wire_derivatives_workspace_floats(C.byref(desc), d, m, chunk_rows, 1 if want_lap else 0))
+    ws = torch.empty(max(floats, 4), dtype=torch.float32, device=dev)      # (0 for a shape the kernels refuse: the call says which)
+    if x is not None:
+        check(lib().inr_wire_derivatives(C.byref(desc), params.data_ptr(), x.data_ptr(), n, d, dt, _ptr(B), m, y.data_ptr(),
+                                         _ptr(grad), _ptr(lap), chunk_rows, ws.data_ptr(), floats, _stream()),
+              "inr_wire_derivatives")
+    else:
+        check(lib().inr_wire_derivatives_grid(C.byref(desc), params.data_ptr(), shape_array(shape), d, dt, _ptr(B), m, y.data_ptr(),
+                                              _ptr(grad), _ptr(lap), chunk_rows, ws.data_ptr(), floats, _stream()),
+              "inr_wire_derivatives_grid")
+    return y, grad, lap
+
+
 def siren_fit_workspace_bytes(desc: SirenDesc, n: int) -> int:
     return int(lib().inr_siren_fit_workspace_bytes(C.byref(desc), int(n)))
 

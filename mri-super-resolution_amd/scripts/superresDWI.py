@@ -30,8 +30,10 @@ Two optional products of the same fit (default off, so a plain run writes exactl
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
-``--transverse_length`` and ``--adc`` go through ``wire.reconstruct``.  ``--derivative_maps`` has no WIRE kernels and is refused
-before the fit, and so is the PerturbNet phase HERE: the notebook's whole loop, PerturbNet tail included, is
+``--transverse_length`` and ``--adc`` go through ``wire.reconstruct``.  ``--wire_derivative_maps`` writes the ``derivatives.mat``
+described above from the WIRE network (``wire.derivatives``, the forward-mode kernels of the Gabor layer; same keys, shapes,
+axes and units); without ``--model wire`` it is refused before any device work, and ``--derivative_maps``, the SIREN's flag,
+stays refused under ``--model wire``.  So is the PerturbNet phase HERE: the notebook's whole loop, PerturbNet tail included, is
 ``scripts/wiretest.py`` (same flags, the notebook's defaults, built from this module's functions).  The default
 ``--model siren`` is the path described above, unchanged.
 R = roi_end - roi_start.  Plots (superresDWI.py:164-233) are outside the build's scope.
@@ -81,7 +83,11 @@ def build_parser():
                         "along the spatial axes (nn_mri.py:205-221)")
     p.add_argument("--model", choices=("siren", "wire"), default="siren",
                    help="network family: the SIREN of superresDWI.py, or the complex-Gabor WIRE network of wiretest.ipynb "
-                        "(hidden_features = hidden_dim // 2; no PerturbNet phase, no derivative maps)")
+                        "(hidden_features = hidden_dim // 2; no PerturbNet phase; derivative maps through "
+                        "--wire_derivative_maps)")
+    p.add_argument("--wire_derivative_maps", action="store_true",
+                   help="--model wire: also write derivatives.mat (grad_mag, laplacian on recon's grid, along the spatial axes) "
+                        "from the WIRE network's forward-mode derivative kernels")
     p.add_argument("--wire_omega", type=float, default=1.2, help="--model wire: omega_0 of every layer (wiretest.ipynb cell 7)")
     p.add_argument("--wire_scale", type=float, default=1.2, help="--model wire: scale_0 of every layer (wiretest.ipynb cell 7)")
     return p
@@ -217,6 +223,8 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale))
     if args.derivative_maps:
         matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape))
+    if args.wire_derivative_maps:
+        matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape, wire.derivatives))
     rec_h, sr_h = recon.cpu().numpy(), SR_recon.cpu().numpy()
     out_vars = {"recon": rec_h, "SR_recon": sr_h, "b": np.asarray(bvalues, np.float64)}
     if maxes is not None:
@@ -233,6 +241,9 @@ def _check_model(args):
     """``--model wire``: refuses what has no WIRE kernels, before the input is loaded and anything touches the device.
     Returns the reason for which an input with single acquisitions is to be refused (None: it is served)."""
     if args.model != "wire":
+        if getattr(args, "wire_derivative_maps", False):
+            raise ValueError("--wire_derivative_maps differentiates the WIRE network and needs --model wire; the SIREN's maps are "
+                             "--derivative_maps")
         return None
     _check_wire(args)
     if args.pertubation_epochs > 0:
@@ -244,7 +255,8 @@ def _check_model(args):
 
 
 def _check_wire(args):
-    """The outputs and shapes no WIRE kernel serves (also ``scripts/wiretest.py``'s refusals)."""
+    """The outputs and shapes no WIRE kernel serves (also ``scripts/wiretest.py``'s refusals).  ``--derivative_maps`` is the SIREN's
+    flag and keeps its refusal; the WIRE network's maps are ``--wire_derivative_maps``."""
     if args.derivative_maps:
         raise ValueError("--derivative_maps needs the forward-mode derivative kernels, which exist for the SIREN only: "
                          "there are no derivative maps of a WIRE network (--model wire)")
@@ -301,10 +313,10 @@ def _adc_maps(recon, hs, bvalues, signal_scale):
     return out
 
 
-def _derivative_maps(INR, B, test_shape):
+def _derivative_maps(INR, B, test_shape, derivatives=inr.derivatives):
     """nn_mri.py:205-221 on the grid of ``recon``: tangents along the three spatial axes only (the b-value axis is the last of the
-    grid and is not differentiated along)."""
-    d = inr.derivatives(INR, shape=test_shape, B=B, d_tangent=min(3, len(test_shape)))
+    grid and is not differentiated along).  ``derivatives``: ``inr.derivatives`` or ``wire.derivatives``, by the network."""
+    d = derivatives(INR, shape=test_shape, B=B, d_tangent=min(3, len(test_shape)))
     grad_mag = torch.sqrt((d.gradient * d.gradient).sum(dim=-1))
     return {"grad_mag": grad_mag.cpu().numpy(), "laplacian": d.laplacian.cpu().numpy()}
 

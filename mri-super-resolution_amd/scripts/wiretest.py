@@ -12,8 +12,9 @@ The flags are ``superresDWI``'s, the defaults the notebook's (cells 6-8): ``--ma
   * a plain volume [X, Y, Z] or [X, Y, Z, b]: the plain fit only (there are no single acquisitions to perturb towards).
 Outputs: the files of ``superresDWI --model wire`` (``recon.mat`` / ``recon.npy``, ``ssim_scores.csv``, ``metrics.json``, the
 optional ``--transverse_length`` / ``--adc`` products); ``metrics.json`` gains ``pn_steps`` (PerturbNet updates taken) and
-``pn_final_loss`` (the loss of the last one; null when none was taken).  ``--derivative_maps`` stays refused: there are no
-derivative maps of a WIRE network.  Loading, re-sampling, evaluation and writing are ``superresDWI``'s own functions.
+``pn_final_loss`` (the loss of the last one; null when none was taken).  ``--wire_derivative_maps`` adds ``derivatives.mat`` as
+in ``superresDWI --model wire``; ``--derivative_maps``, the SIREN's flag, stays refused.  Loading, re-sampling, evaluation and
+writing are ``superresDWI``'s own functions.
 """
 from __future__ import annotations
 

@@ -12,18 +12,22 @@ parameters live views of one flat fp32 buffer (a complex tensor is its interleav
 backward and Adam of many steps in one C call.  An input that requires grad gets the gradient with respect to ITSELF
 (``inr_wire_forward_stash`` / ``inr_wire_input_grad``): the notebook's network does not detach its input (cell 2), and cell
 10's PerturbNet phase -- ``drivers.fit_wire_with_perturbnet`` -- trains the PerturbNet through it.  There is no CPU path and
-no layer-by-layer fallback: ``out_features == 1``, ``hidden_features in {32, 64, 128, 256}``, ``hidden_layers <= 8``,
+no layer-by-layer fallback.  ``derivatives`` gives value, coordinate gradient and Laplacian of a fitted network in forward mode
+(``csrc/wire_deriv.hip``; nn_mri.py:205-221 over this stack), and ``inr.laplace`` serves a direct ``Wire`` output through it.
+Served: ``out_features == 1``, ``hidden_features in {32, 64, 128, 256}``, ``hidden_layers <= 8``,
 ``in_features <= 1024``, ``trainable=False``; anything else raises.
 """
 from __future__ import annotations
 
 import ctypes as C
+import weakref
 
 import torch
 from torch import nn
 
 from . import ops
 from ._lib import WireDesc, check, lib, shape_array
+from .inr import Derivatives
 from .flat import AdamOwner, AdamState, FlatParams, Workspace, WorkspacePool
 
 HIDDEN_SIZES = (32, 64, 128, 256)
@@ -208,16 +212,22 @@ class Wire(nn.Module):
             raise ops.InrDeviceError("Wire: move the model to the input's HIP device first (model.cuda())")
         n = x.shape[0]
         if wants_grad and n:
-            return _WireInputFn.apply(x, desc, flat, self._input_grad_pool).reshape(*coords.shape[:-1], 1)
-        y = torch.empty(n, dtype=torch.float32, device=x.device)
-        if n:
-            need = lib().inr_wire_workspace_bytes(C.byref(desc), n, WS_INFER)
-            if need == 0:
-                check(-1, "inr_wire_workspace_bytes")
-            ws = ops._ws(need, x.device)
-            check(lib().inr_wire_forward(C.byref(desc), flat.data_ptr(), x.data_ptr(), n, y.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         ops._stream()), "inr_wire_forward")
-        return y.reshape(*coords.shape[:-1], 1)
+            y = _WireInputFn.apply(x, desc, flat, self._input_grad_pool)
+        else:
+            y = torch.empty(n, dtype=torch.float32, device=x.device)
+            if n:
+                need = lib().inr_wire_workspace_bytes(C.byref(desc), n, WS_INFER)
+                if need == 0:
+                    check(-1, "inr_wire_workspace_bytes")
+                ws = ops._ws(need, x.device)
+                check(lib().inr_wire_forward(C.byref(desc), flat.data_ptr(), x.data_ptr(), n, y.data_ptr(), ws.data_ptr(),
+                                             ws.numel(), ops._stream()), "inr_wire_forward")
+        y = y.reshape(*coords.shape[:-1], 1)
+        if coords.requires_grad and coords.shape[-1] <= 4:
+            # where this output came from, for `inr.laplace`: the backward of _WireInputFn is a plain kernel call and leaves no
+            # graph to differentiate a second time (as Siren.forward does)
+            y._wire_origin = (weakref.ref(self), coords)
+        return y
 
 
 class WireFitter(AdamOwner):
@@ -336,3 +346,39 @@ def reconstruct(model: Wire, shape, B=None, clamp_min=0.0, chunk_rows=1 << 16):
                                      0 if Bd is None else Bd.shape[0], y.data_ptr(), int(clamp_min is not None),
                                      float(clamp_min or 0.0), chunk, ws.data_ptr(), ws.numel(), ops._stream()), "inr_wire_reconstruct")
     return y.view(*shape)
+
+
+def derivatives(model: Wire, coords=None, *, shape=None, B=None, laplacian=True, d_tangent=None, chunk_rows=1 << 15):
+    """Value, coordinate gradient and Laplacian of ``model(input_mapping(coords, B))``, evaluated in forward mode by the
+    ``inr_wire_derivatives`` kernels: what nn_mri.py:205-221 ``gradient`` / ``laplace`` obtain from two ``autograd.grad`` passes
+    with ``create_graph=True`` over the notebook's network (cell 2 does not detach its input), without a stash of activations,
+    so it runs on a re-sampling grid of millions of rows.  The WIRE counterpart of ``inr.derivatives``, with its shapes and units:
+
+    exactly one of ``coords`` ([..., d] rows, d <= 4) and ``shape`` (the dense grid ``get_mgrid(shape)``, generated on the
+    device) is given.  Returns ``inr.Derivatives(value, gradient, laplacian)`` of device tensors: for ``coords`` of shape
+    ``lead + (d,)`` they have shapes ``lead``, ``lead + (d_tangent,)``, ``lead``; on a grid ``shape``, ``shape + (d_tangent,)``,
+    ``shape``.  ``laplacian=False`` skips the second-order accumulator (the field is ``None``).  ``d_tangent`` (default d)
+    differentiates along the leading axes only: a DWI grid (x, y, z, b) takes 3, and the Laplacian then sums over those axes.
+    ``B=None`` feeds the raw coordinates (``in_features == d``); otherwise ``in_features == 2 * len(B)``.
+
+    Derivatives are with respect to the NORMALISED ``[-1, 1]`` coordinates of ``get_mgrid``: multiply ``gradient[..., a]`` by
+    ``2 / (n_a - 1)`` for units per voxel along an axis of ``n_a`` samples, a second derivative by its square.  The value is the
+    raw network output (no clamp); it agrees with ``model(...)`` to rounding, not bit for bit (another tile shape).  The results
+    carry no graph."""
+    if (coords is None) == (shape is None):
+        raise ValueError("derivatives takes exactly one of coords and shape")
+    ops.require_gpu()
+    desc = model.desc()
+    flat = model._flat(desc)
+    Bd = None if B is None else B.detach().to(flat.device, torch.float32).contiguous()
+    with torch.no_grad():
+        if coords is not None:
+            lead, d = tuple(coords.shape[:-1]), int(coords.shape[-1])
+            x = coords.detach().to(flat.device, torch.float32).reshape(-1, d).contiguous()
+            y, g, lap = ops.wire_derivatives(desc, flat, x=x, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian),
+                                             chunk_rows=chunk_rows)
+        else:
+            lead = tuple(int(s) for s in shape)
+            y, g, lap = ops.wire_derivatives(desc, flat, shape=lead, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian),
+                                             chunk_rows=chunk_rows)
+    return Derivatives(y.view(*lead), g.view(*lead, g.shape[-1]), None if lap is None else lap.view(*lead))

@@ -1,0 +1,199 @@
+"""Shared by test_wire_deriv_cpu.py / test_gpu_wire_deriv.py: the WIRE complex-Gabor stack of wiretest.ipynb cell 2 in plain complex
+torch, whose coordinate gradient and Laplacian come from double-backward autograd in float64 / complex128 -- an independent route
+to the numbers the forward-mode kernels of csrc/wire_deriv.hip produce; it uses none of their formulas --, the forward-mode formulas
+of DESIGN.md 4e restated in plain REAL torch (``forward_formulas``: their float32 evaluation on the host sets the Laplacian's
+tolerance), the fixture tests/golden/wire_deriv.npz (tools/make_wire_deriv_golden.py: the reference's own layer under float64
+double-backward) and the case table of the GPU test.
+
+A case is a dict: ``model`` (a ``wire.Wire`` on the host, default ``nn.Linear`` initialisation after ``manual_seed``), ``x`` [n, d]
+float32 coordinates, ``B`` [m, d] float32 or None, ``dt`` tangent axes, ``grid`` (the shape whose ``get_mgrid`` rows ``x`` is) or None."""
+import math
+import os
+
+import numpy as np
+import torch
+
+from mri_super_resolution_amd import wire
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wire_deriv.npz")
+CHUNK = 256
+OMEGA = SCALE = 1.2          # wiretest.ipynb cell 7
+
+
+def golden():
+    return np.load(GOLDEN)
+
+
+def mgrid_rows(shape):
+    """get_mgrid(shape) on the host in float32 (torch.linspace, 'ij' meshgrid, last axis fastest)."""
+    axes = [torch.linspace(-1, 1, steps=int(s)) for s in shape]
+    return torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, len(shape)).contiguous()
+
+
+# name -> what make_case takes.  The smallest shapes at which the kernels can still go wrong (32-row, 32-unit tiles; K blocks of 32):
+CASES = {
+    "fixture":  None,                                                                            # 333 rows; K0 pad 16 -> 32
+    "ragged":   dict(seed=21, d=3, dt=2, m=16, hidden=64, layers=2, grid=(11, 31, 3)),           # 1023: dt < d, ragged chunk and tile
+    "raw":      dict(seed=22, d=2, dt=2, m=0, hidden=32, layers=1, grid=(17, 21)),               # 357: raw-coordinate input jets
+    "j6":       dict(seed=23, d=4, dt=4, m=20, hidden=128, layers=1, n=130),                     # in = 40 (ragged pad), J = 6
+    "head":     dict(seed=24, d=3, dt=3, m=16, hidden=256, layers=0, n=70),                      # first layer straight to head
+    "notebook": dict(seed=25, d=4, dt=3, m=256, hidden=128, layers=3, n=200),                    # the notebook's network, driver's dt
+    "consts":   dict(seed=26, d=3, dt=3, m=8, hidden=32, layers=1, n=333, consts=(1.5, 0.9, 1.1, 0.7)),   # four distinct constants
+}
+
+
+def make_case(seed, d, dt, m, hidden, layers, n=None, grid=None, consts=None, b_scale=0.5):
+    """``consts`` = (first_omega, hidden_omega, first_scale, hidden_scale); default the notebook's 1.2 everywhere."""
+    torch.manual_seed(seed)
+    fo, ho, fs, hs = consts or (OMEGA, OMEGA, SCALE, SCALE)
+    model = wire.Wire(2 * m if m else d, hidden, layers, 1, first_omega_0=fo, hidden_omega_0=ho, scale=fs)
+    with torch.no_grad():
+        for k in range(1, layers + 1):
+            model.net[k].scale_0.fill_(hs)
+    g = torch.Generator().manual_seed(seed + 1000)
+    B = (torch.randn(m, d, generator=g) * b_scale).contiguous() if m else None
+    x = mgrid_rows(grid) if grid is not None else (torch.rand(n, d, generator=g) * 2 - 1).contiguous()
+    return {"model": model, "x": x, "B": B, "d": d, "dt": dt, "m": m, "grid": grid, "layers": layers, "hidden": hidden}
+
+
+def fixture_case():
+    """The fixture's network, coordinates and Fourier matrix as a case (weights exactly as the reference drew them)."""
+    g = golden()
+    m, d = g["B"].shape
+    hidden = g["w/net.0.linear.weight"].shape[0]
+    layers = sum(1 for k in g.files if k.endswith(".linear.weight")) - 1
+    model = wire.Wire(2 * m, hidden, layers, 1, first_omega_0=float(g["w/net.0.omega_0"][0]),
+                      hidden_omega_0=float(g[f"w/net.{min(1, layers)}.omega_0"][0]), scale=float(g["w/net.0.scale_0"][0]))
+    state = {}
+    for key, like in model.state_dict().items():
+        v = torch.from_numpy(g["w/" + key])
+        state[key] = torch.view_as_complex(v.contiguous()) if like.is_complex() else v
+    model.load_state_dict(state)
+    return {"model": model, "x": torch.from_numpy(g["x"]), "B": torch.from_numpy(g["B"]), "d": d, "dt": d, "m": m,
+            "grid": (3, 3, 37), "layers": layers, "hidden": hidden}
+
+
+def get_case(name):
+    return fixture_case() if CASES[name] is None else make_case(**CASES[name])
+
+
+def leaves(model, double=True):
+    """{state_dict name: tensor} on the host; double: float64 / complex128 copies of the float32 VALUES."""
+    out = {}
+    for k, v in model.state_dict().items():
+        v = v.detach().cpu()
+        out[k] = v.to(torch.complex128 if v.is_complex() else torch.float64) if double else v.clone()
+    return out
+
+
+def features(x, B):
+    """INRmodel.py:171-176 ``input_mapping``."""
+    if B is None:
+        return x
+    p = (2.0 * math.pi * x) @ B.T
+    return torch.cat([torch.sin(p), torch.cos(p)], dim=-1)
+
+
+def network(P, layers, feats):
+    """wiretest.ipynb cell 2 in complex torch: INRmodel.py:109-120 per layer, the head's real part."""
+    h = feats
+    for k in range(layers + 1):
+        w, s = P[f"net.{k}.omega_0"], P[f"net.{k}.scale_0"]
+        lin = h @ P[f"net.{k}.linear.weight"].T + P[f"net.{k}.linear.bias"]
+        orth = h @ P[f"net.{k}.scale_orth.weight"].T + P[f"net.{k}.scale_orth.bias"]
+        h = torch.exp(1j * w * lin) * torch.exp(-s * s * (lin.abs().square() + orth.abs().square()))
+    return (h @ P["final_linear.weight"].T + P["final_linear.bias"]).real[:, 0]
+
+
+def autograd_reference(case, d_tangent=None):
+    """(y [n], grad [n, dt], lap [n]) in float64: gradient by one backward pass with create_graph=True, Laplacian by a second
+    through each tangent component (rows are independent, so summing over rows before differentiating loses nothing)."""
+    dt = case["dt"] if d_tangent is None else d_tangent
+    P = leaves(case["model"])
+    B = None if case["B"] is None else case["B"].double()
+    x = case["x"].double().requires_grad_(True)
+    y = network(P, case["layers"], features(x, B))
+    g = torch.autograd.grad(y.sum(), x, create_graph=True)[0]
+    lap = torch.zeros_like(y)
+    for i in range(dt):
+        lap = lap + torch.autograd.grad(g[:, i].sum(), x, retain_graph=True)[0][:, i]
+    return y.detach(), g[:, :dt].detach(), lap.detach()
+
+
+def _image(P, k, hr, hi, bias, dtype):
+    """The four real quantities (lin_r, lin_i, orth_r, orth_i) of layer k applied to the planes (hr, hi); layer 0: hi is None and
+    lin_i = orth_i = 0."""
+    out = []
+    for name in ("linear", "scale_orth"):
+        W, b = P[f"net.{k}.{name}.weight"], P[f"net.{k}.{name}.bias"]
+        if k == 0:
+            r = hr @ W.to(dtype).T
+            out += [r + b.to(dtype) if bias else r, torch.zeros_like(r)]
+        else:
+            Wr, Wi, br, bi = W.real.to(dtype), W.imag.to(dtype), b.real.to(dtype), b.imag.to(dtype)
+            r, i = hr @ Wr.T - hi @ Wi.T, hr @ Wi.T + hi @ Wr.T
+            out += [r + br, i + bi] if bias else [r, i]
+    return out
+
+
+def forward_formulas(case, dtype, d_tangent=None):
+    """The forward-mode formulas in plain real torch on the host in ``dtype``: value a, tangents t_i, Laplacian
+    accumulator q carried layer by layer as planes (real, imaginary).  In float64 it equals ``autograd_reference`` to rounding; its
+    float32 deviation from float64 is the error plain float32 arithmetic makes on these formulas, which the Laplacian's tolerance
+    is a multiple of."""
+    dt = case["dt"] if d_tangent is None else d_tangent
+    P = leaves(case["model"], double=False)
+    x = case["x"].to(dtype)
+    if case["B"] is None:
+        a = x
+        t = [torch.zeros_like(x) for _ in range(dt)]
+        for i in range(dt):
+            t[i][:, i] = 1
+        q = torch.zeros_like(x)
+    else:
+        B = case["B"].to(dtype)
+        p = (2.0 * math.pi * x) @ B.T
+        s, c = torch.sin(p), torch.cos(p)
+        a = torch.cat([s, c], dim=-1)
+        t = [torch.cat([2.0 * math.pi * B[:, i] * c, -2.0 * math.pi * B[:, i] * s], dim=-1) for i in range(dt)]
+        nb = (2.0 * math.pi) ** 2 * (B[:, :dt] ** 2).sum(dim=1)
+        q = torch.cat([-nb * s, -nb * c], dim=-1)
+    a, t, q = (a, None), [(ti, None) for ti in t], (q, None)
+    for k in range(case["layers"] + 1):
+        w = float(P[f"net.{k}.omega_0"][0])
+        s2 = float(P[f"net.{k}.scale_0"][0]) ** 2
+        z = _image(P, k, *a, True, dtype)
+        u = [_image(P, k, *ti, False, dtype) for ti in t]
+        r = _image(P, k, *q, False, dtype)
+        amp = torch.exp(-w * z[1] - s2 * sum(zq * zq for zq in z))
+        o_r, o_i = amp * torch.cos(w * z[0]), amp * torch.sin(w * z[0])
+        pg = [(-w * ui[1] - 2 * s2 * sum(zq * uq for zq, uq in zip(z, ui)), w * ui[0]) for ui in u]
+        t = [(o_r * p - o_i * g, o_r * g + o_i * p) for p, g in pg]
+        S_r = sum(p * p - g * g for p, g in pg) if pg else 0.0
+        S_i = sum(2 * p * g for p, g in pg) if pg else 0.0
+        uu = sum(uq * uq for ui in u for uq in ui) if u else 0.0
+        LE = -w * r[1] - 2 * s2 * (sum(zq * rq for zq, rq in zip(z, r)) + uu)
+        c_r, c_i = S_r + LE, S_i + w * r[0]
+        a, q = (o_r, o_i), (o_r * c_r - o_i * c_i, o_r * c_i + o_i * c_r)
+    hw, hb = P["final_linear.weight"], P["final_linear.bias"]
+    w_r, w_i = hw.real.to(dtype)[0], hw.imag.to(dtype)[0]
+    dot = lambda pl: pl[0] @ w_r - pl[1] @ w_i      # noqa: E731
+    grad = torch.stack([dot(ti) for ti in t], dim=-1) if t else torch.zeros(x.shape[0], 0, dtype=dtype)
+    return dot(a) + hb.real.to(dtype)[0], grad, dot(q)
+
+
+def rel_l2(got, want):
+    got, want = torch.as_tensor(got).double().cpu().reshape(-1), torch.as_tensor(want).double().cpu().reshape(-1)
+    return float((got - want).norm() / want.norm())
+
+
+def max_rel(got, want):
+    got, want = torch.as_tensor(got).double().cpu().reshape(-1), torch.as_tensor(want).double().cpu().reshape(-1)
+    return float((got - want).abs().max() / want.abs().max())
+
+
+def on_device(case):
+    """(desc, flat parameter buffer, x, B) on the GPU, the flat buffer laid out by inr_wire_param_offsets."""
+    model = case["model"].cuda()
+    desc = model.desc()
+    return desc, model._flat(desc), case["x"].cuda(), None if case["B"] is None else case["B"].cuda()
