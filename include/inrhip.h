@@ -373,6 +373,48 @@ size_t inr_resize_z_cubic_workspace_bytes(int64_t n_lines, int n_in);
 int inr_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
+ * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
+ * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output
+ * has ever been compared against; tests/perceptual_common.py restates the definitions in float64 NumPy / SciPy.  FSIM.m and SR_SIM.m
+ * (perceptual_similarity.m:53-54) are third-party files under a research-only licence and have no counterpart here.
+ * Images are [n_images][H][W] fp32, all arithmetic is fp64, results are doubles; 1 <= n_images <= 65535, H, W >= 1.
+ * Window: r = ceil(3 sigma) <= INR_PERCEPTUAL_MAX_RADIUS, g[k] = exp(-k^2 / (2 sigma^2)) normalised, separable, indices clamped
+ * to the edge.  Refusals, all before any device work: INR_E_INVALID (null pointers, n_images < 1, sizes < 1, sigma <= 0 or a
+ * radius above 7, data_range <= 0, n_scales outside 1..INR_PERCEPTUAL_MAX_SCALES), INR_E_WORKSPACE (a null or short workspace),
+ * INR_E_ALIGN (a device pointer off a 16-byte boundary).
+ * workspace: typed, like inr_rescale2d's -- inr_perceptual_workspace_doubles(n_images, H, W, n_scales) DOUBLES serve every entry
+ * point below for that many images of that shape and that many scales (n_scales = 1 for inr_ssim2d_gauss); inr_image_mse and
+ * inr_hf_gain need inr_perceptual_workspace_doubles(n_images, 1, 1, 1), which every larger view of the same n_images covers.  0 for
+ * arguments that would be refused.  Plain launches and fixed-order reductions: repeated calls are bit-equal, and an image's results depend
+ * neither on the rest of the batch nor on where a pixel falls in a tile. */
+#define INR_PERCEPTUAL_MAX_RADIUS 7
+#define INR_PERCEPTUAL_MAX_SCALES 8
+int64_t inr_perceptual_workspace_doubles(int n_images, int height, int width, int n_scales);
+/* ssim(A, ref) of perceptual_similarity.m:50: mx = F x, vx = max(F(x^2) - mx^2, 0), vxy = F(xy) - mx my, C1 = (.01 L)^2,
+ * C2 = (.03 L)^2, l = (2 mx my + C1) / (mx^2 + my^2 + C1), cs = (2 vxy + C2) / (vx + vy + C2); ssim[b] = the mean of l cs over the
+ * FULL image (no border crop, biased variance: both unlike inr_ssim2d); mean_cs (nullable) [n_images] = the mean of cs; map
+ * (nullable) [n_images][H][W] fp32 = l cs. */
+int inr_ssim2d_gauss(double* ssim, double* mean_cs, float* map, const float* x, const float* y, int n_images, int height, int width,
+                     double sigma, double data_range, double* workspace, int64_t workspace_doubles, void* stream);
+/* multissim(A, ref) of perceptual_similarity.m:52: v_s = mean(cs) at scales 0 .. n_scales-2, v_last = mean(l cs), out[b] =
+ * prod v_s ^ weights[s] (pow: a negative v_s under a fractional weight gives NaN); between scales both images become their 2 x 2
+ * block means, indices clamped, ceil(H/2) x ceil(W/2), kept in fp64.  weights: n_scales HOST doubles.  per_scale (nullable)
+ * [n_images][n_scales] receives the v_s. */
+int inr_msssim2d(double* out, double* per_scale, const float* x, const float* y, int n_images, int height, int width,
+                 const double* weights, int n_scales, double sigma, double data_range, double* workspace, int64_t workspace_doubles,
+                 void* stream);
+/* imfilter(single(image), H) of HPF.m:8 for any 3 x 3 H: correlation, ZERO padding, same size; k9: 9 HOST doubles, row-major; the
+ * fp64 sum is rounded once to fp32. */
+int inr_filter3x3(float* out, const float* in, int n_images, int height, int width, const double* k9, void* stream);
+/* immse(A, ref) of perceptual_similarity.m:51: out[b] = mean (x - y)^2 over per_image samples. */
+int inr_image_mse(double* out, const float* x, const float* y, int n_images, int64_t per_image, double* workspace,
+                  int64_t workspace_doubles, void* stream);
+/* power_diff / pow_inter of perceptual_similarity.m:42-47 on the high-passed images: out[b] = sum max(h_sr - h_inter, 0)^2 /
+ * sum h_inter^2. */
+int inr_hf_gain(double* out, const float* h_sr, const float* h_inter, int n_images, int64_t per_image, double* workspace,
+                int64_t workspace_doubles, void* stream);
+
 /* ---- a-13/a-14: RAMS forward + predict_tensor (network.py:91-155, prediction.py:76-83) --------------------------
  * x [B][H][W][channels] fp32 (uint16-range values) -> out [B][scale*H][scale*W] fp32.  clip_round != 0 applies
  * predict_tensor's clip to [0, 2^16] and round-half-to-even.

@@ -134,6 +134,14 @@ SIGNATURES = {
     "inr_adc_map": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_resize_z_cubic_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "inr_resize_z_cubic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_perceptual_workspace_doubles": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "inr_ssim2d_gauss": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
+                                   C.c_void_p, C.c_int64, c_stream]),
+    "inr_msssim2d": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int,
+                               C.c_double, C.c_double, C.c_void_p, C.c_int64, c_stream]),
+    "inr_filter3x3": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), c_stream]),
+    "inr_image_mse": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
+    "inr_hf_gain": (C.c_int, [C.c_void_p, c_f32p, c_f32p, C.c_int, C.c_int64, C.c_void_p, C.c_int64, c_stream]),
     "inr_rams_param_count": (C.c_int64, [C.POINTER(RamsDesc)]),
     "inr_rams_workspace_bytes": (C.c_size_t, [C.POINTER(RamsDesc), C.c_int, C.c_int, C.c_int]),
     "inr_rams_forward": (C.c_int, [C.POINTER(RamsDesc), c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,

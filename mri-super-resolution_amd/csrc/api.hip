@@ -1504,6 +1504,72 @@ int inr_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in,
     return launch_resize_z_cubic(out, in, n_lines, n_in, n_out, (double*)workspace, (hipStream_t)stream);
 }
 
+// ---- the reader study's scores (perceptual.hip) ------------------------------------------------------------------------------------------
+int64_t inr_perceptual_workspace_doubles(int n_images, int height, int width, int n_scales) {
+    if (perceptual_check("inr_perceptual_workspace_doubles", n_images, height, width, 1.5, 1.0, n_scales)) return 0;
+    return (int64_t)(perceptual_view(n_images, height, width, n_scales, nullptr).total / sizeof(double));
+}
+
+// the workspace of one call: present, long enough for `need`, aligned
+static int perceptual_ws_check(const char* who, const double* workspace, int64_t workspace_doubles, size_t need) {
+    INR_REQUIRE(workspace && workspace_doubles >= 0 && (size_t)workspace_doubles * sizeof(double) >= need, INR_E_WORKSPACE,
+                "%s: workspace too small (%lld doubles, %zu needed)", who, workspace ? (long long)workspace_doubles : 0ll,
+                need / sizeof(double));
+    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
+    return 0;
+}
+
+int inr_ssim2d_gauss(double* ssim, double* mean_cs, float* map, const float* x, const float* y, int n_images, int height, int width,
+                     double sigma, double data_range, double* workspace, int64_t workspace_doubles, void* stream) {
+    INR_REQUIRE(ssim && x && y, INR_E_INVALID, "inr_ssim2d_gauss: null pointer");
+    if (int rc = perceptual_check("inr_ssim2d_gauss", n_images, height, width, sigma, data_range, 1)) return rc;
+    const PerceptualView v = perceptual_view(n_images, height, width, 1, workspace);
+    if (int rc = perceptual_ws_check("inr_ssim2d_gauss", workspace, workspace_doubles, v.total)) return rc;
+    INR_REQUIRE(aligned16(ssim) && aligned16(mean_cs) && aligned16(map) && aligned16(x) && aligned16(y), INR_E_ALIGN,
+                "inr_ssim2d_gauss: pointers must be 16-byte aligned");
+    return launch_ssim_gauss(ssim, mean_cs, map, x, y, n_images, height, width, sigma, data_range, v, (hipStream_t)stream);
+}
+
+int inr_msssim2d(double* out, double* per_scale, const float* x, const float* y, int n_images, int height, int width,
+                 const double* weights, int n_scales, double sigma, double data_range, double* workspace, int64_t workspace_doubles,
+                 void* stream) {
+    INR_REQUIRE(out && x && y && weights, INR_E_INVALID, "inr_msssim2d: null pointer");
+    if (int rc = perceptual_check("inr_msssim2d", n_images, height, width, sigma, data_range, n_scales)) return rc;
+    const PerceptualView v = perceptual_view(n_images, height, width, n_scales, workspace);
+    if (int rc = perceptual_ws_check("inr_msssim2d", workspace, workspace_doubles, v.total)) return rc;
+    INR_REQUIRE(aligned16(out) && aligned16(per_scale) && aligned16(x) && aligned16(y), INR_E_ALIGN,
+                "inr_msssim2d: pointers must be 16-byte aligned");
+    return launch_msssim(out, per_scale, x, y, n_images, height, width, weights, n_scales, sigma, data_range, v, (hipStream_t)stream);
+}
+
+int inr_filter3x3(float* out, const float* in, int n_images, int height, int width, const double* k9, void* stream) {
+    INR_REQUIRE(out && in && k9, INR_E_INVALID, "inr_filter3x3: null pointer");
+    if (int rc = perceptual_check("inr_filter3x3", n_images, height, width, 1.5, 1.0, 1)) return rc;
+    INR_REQUIRE(aligned16(out) && aligned16(in), INR_E_ALIGN, "inr_filter3x3: pointers must be 16-byte aligned");
+    return launch_filter3x3(out, in, n_images, height, width, k9, (hipStream_t)stream);
+}
+
+static int pair_score(const char* who, double* out, const float* x, const float* y, int n_images, int64_t per_image, int mode,
+                      double* workspace, int64_t workspace_doubles, void* stream) {
+    INR_REQUIRE(out && x && y, INR_E_INVALID, "%s: null pointer", who);
+    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && per_image >= 1, INR_E_INVALID, "%s: bad sizes (n_images=%d, per_image=%lld)", who,
+                n_images, (long long)per_image);
+    const PerceptualView v = perceptual_view(n_images, 1, 1, 1, workspace);
+    if (int rc = perceptual_ws_check(who, workspace, workspace_doubles, v.total)) return rc;
+    INR_REQUIRE(aligned16(out) && aligned16(x) && aligned16(y), INR_E_ALIGN, "%s: pointers must be 16-byte aligned", who);
+    return launch_pair_score(out, x, y, n_images, per_image, mode, v, (hipStream_t)stream);
+}
+
+int inr_image_mse(double* out, const float* x, const float* y, int n_images, int64_t per_image, double* workspace,
+                  int64_t workspace_doubles, void* stream) {
+    return pair_score("inr_image_mse", out, x, y, n_images, per_image, 0, workspace, workspace_doubles, stream);
+}
+
+int inr_hf_gain(double* out, const float* h_sr, const float* h_inter, int n_images, int64_t per_image, double* workspace,
+                int64_t workspace_doubles, void* stream) {
+    return pair_score("inr_hf_gain", out, h_sr, h_inter, n_images, per_image, 1, workspace, workspace_doubles, stream);
+}
+
 int inr_auto_erd(float* accept, const double* values, const float* erd_map, int64_t n_pixels, int n_acquisitions, int rule,
                  void* stream) {
     INR_REQUIRE(accept && values, INR_E_INVALID, "inr_auto_erd: null pointer");

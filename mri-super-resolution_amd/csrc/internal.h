@@ -158,6 +158,20 @@ int rescale_check(const char* who, int nimg, int H, int W, int OH, int OW, int o
 int launch_rescale2d(float* out, const float* in, int nimg, int H, int W, int OH, int OW, int order, int mode, int anti_aliasing,
                      int clip_group, const RescaleView& v, hipStream_t st);
 
+// ---- perceptual.hip: the reader study's scores (Gaussian SSIM, MS-SSIM, 3 x 3 high-pass, MSE, high-frequency gain) ------------------------
+constexpr int PERCEPTUAL_MAX_RADIUS = INR_PERCEPTUAL_MAX_RADIUS;   // window taps per side: what the tile's halo in LDS holds
+constexpr int PERCEPTUAL_MAX_SCALES = INR_PERCEPTUAL_MAX_SCALES;
+struct PerceptualView { double *reduce, *partial, *vals, *lx[2], *ly[2]; size_t total; };
+PerceptualView perceptual_view(int nimg, int H, int W, int n_scales, void* base);
+int perceptual_check(const char* who, int nimg, int H, int W, double sigma, double data_range, int n_scales);
+int launch_ssim_gauss(double* ssim, double* mean_cs, float* map, const float* x, const float* y, int nimg, int H, int W, double sigma,
+                      double data_range, const PerceptualView& v, hipStream_t st);
+int launch_msssim(double* out, double* per_scale, const float* x, const float* y, int nimg, int H, int W, const double* weights,
+                  int n_scales, double sigma, double data_range, const PerceptualView& v, hipStream_t st);
+int launch_filter3x3(float* out, const float* in, int nimg, int H, int W, const double* k9, hipStream_t st);
+int launch_pair_score(double* out, const float* x, const float* y, int nimg, int64_t per_image, int mode, const PerceptualView& v,
+                      hipStream_t st);
+
 // ---- cssim.hip: the shift-tolerant SSIM of the RAMS tree (utils/loss.py:131-177) and its gradient ---------------------------------------
 int cssim_min_crop();   // the cropped window must hold one 11 x 11 filter window
 size_t cssim_workspace_doubles(int nimg, int size, int border, bool grad);
