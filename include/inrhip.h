@@ -586,6 +586,26 @@ int inr_pids_slice(float* adc_high, float* adc_negative, float* b_decay, float* 
 int inr_auto_erd(float* accept, const double* values, const float* erd_map, int64_t n_pixels, int n_acquisitions, int rule,
                  void* stream);
 
+/* Whole-volume AutoERD with the ERD-weighted direction means and ADC maps of david.py:44-91, one launch for all pixels, float64.
+ * Every array is a stack of planes, pixels contiguous: values, accept, accept_in, adc [n_acquisitions][n_pixels]; the four maps
+ * [n_groups][n_pixels]; b0, erd_map [n_pixels].  group_sizes [n_groups] (HOST array, 1 <= n_groups <= INR_ERD_VOLUME_MAX_GROUPS, every
+ * size >= 1, summing to n_acquisitions) cuts the acquisitions into consecutive groups (the gradient directions).
+ * rule 1 / rule 2: the pixel's sample is split and acquisitions are rejected exactly as inr_auto_erd does it (the same partition,
+ * ties included; erd_map is float64 here and nullable = positive everywhere; only entries > 0 reject, so 0, negative, -inf and NaN
+ * keep everything); accept_in must be null.  rule 0: no clustering -- accept_in (nullable = all ones) is used as the acceptance
+ * weights as it is.  A pixel with a NON-FINITE value among its acquisitions (or whose extent overflows) is not clustered and keeps
+ * every acquisition; its sums follow IEEE.  2 <= n_acquisitions <= 32.
+ * Per group, three sequential sums over its acquisitions in index order, each from 0.0: sum_image += v, sum_accepted += v * a,
+ * sum_accepts += a; then direction_mean = sum_image / size, accepted_mean = sum_accepted / sum_accepts -- NaN (0 / 0) where a
+ * group is wholly rejected, and then accepted_adc is NaN too -- and adc(v) = -log(v / (b0 + 1e-7) + 1e-7) / b * 1000 of both
+ * means (ONE factor 1000: david.py:82-85); adc (nullable) receives adc(v) of every single acquisition (david.py:68-69).
+ * Every output is nullable on its own; b0 is needed only where an ADC output is asked for.  accept receives 1.0 = keep, 0.0 =
+ * reject (under rule 0 a copy of the weights used).  b != 0.  n_pixels == 0 is a no-op. */
+#define INR_ERD_VOLUME_MAX_GROUPS 8
+int inr_auto_erd_volume(double* accept, double* direction_mean, double* accepted_mean, double* direction_adc, double* accepted_adc,
+                   double* adc, const double* values, const double* b0, const double* erd_map, const double* accept_in,
+                   int64_t n_pixels, int n_acquisitions, const int* group_sizes, int n_groups, double b, int rule, void* stream);
+
 /* ---- the soft-ERD INR family (INR_ERD.py:28-67 `Siren`, prepare_qual_images.py:66-102) --------------------------------------------
  * Trunk: SineLayer(in -> H, first), hidden_layers x SineLayer(H -> H), Linear(H -> H) + ReLU; head Linear(H -> 1) + ReLU; the
  * in-module perturbation p = eps tanh(W2 tanh(W1 [x, sample] + b1) + b2) ([n][1]) is ADDED TO EVERY coordinate component

@@ -190,6 +190,8 @@ SIGNATURES = {
     "inr_pia_launch_count": (C.c_int, [C.c_int, c_i64p]),
     "inr_pids_slice": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_int64, c_stream]),
     "inr_auto_erd": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
+    "inr_auto_erd_volume": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_double, C.c_int, c_stream]),
     "inr_erd_param_count": (C.c_int64, [C.POINTER(SirenDesc)]),
     "inr_erd_param_offsets": (C.c_int, [C.POINTER(SirenDesc), c_i64p, C.c_int]),
     "inr_erd_workspace_bytes": (C.c_size_t, [C.POINTER(SirenDesc), C.c_int64]),

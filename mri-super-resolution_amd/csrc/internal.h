@@ -149,6 +149,12 @@ int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_
 int launch_adc(float* out, const float* data, const float* bvals, int64_t npix, int nb, hipStream_t st);
 int launch_auto_erd(float* accept, const double* values, const float* erd_map, int64_t npix, int n, int rule, hipStream_t st);
 
+// ---- erd_volume.hip: whole-volume AutoERD on cluster extents, the per-group means and their ADC maps (david.py:44-91) -----------------
+int erd_volume_check(int n, const int* group_sizes, int n_groups, double b, int rule);   // host only: no device is touched
+int launch_erd_volume(double* accept, double* direction_mean, double* accepted_mean, double* direction_adc, double* accepted_adc,
+                      double* adc, const double* values, const double* b0, const double* erd_map, const double* accept_in, int64_t npix,
+                      int n, const int* group_sizes, int n_groups, double b, int rule, hipStream_t st);
+
 // ---- rescale.hip: skimage resize for 2-D images (anti-aliasing Gaussian, orders 1 and 3, modes 'reflect' and 'edge') -------------------
 constexpr int RESCALE_MAX_RADIUS = INR_RESCALE_MAX_RADIUS;   // Gaussian taps per side that the kernel arguments carry
 constexpr int RESCALE_MAX_LINE = INR_RESCALE_MAX_LINE;       // one padded line, staged in LDS as doubles, fits 64 KiB

@@ -845,3 +845,66 @@ def low_res_study(case, slice_index, seed, hidden_features=128, hidden_layers=3,
     info = {"pretrain": pre, "finetune_loss": float(losses[-1]) if finetune_steps else float("nan"), "noise_level": float(level),
             "b0_low": b0_low, "b0_up": b0_up, "model": model}
     return maps, label, info
+
+
+# ---------------------------------------------------------------------------------------------------
+# david.py:31-91 -- AutoERD on whole slices, the plain and the ERD-accepted mean of every gradient direction, their ADC maps and
+# the lesion-contrast table
+# ---------------------------------------------------------------------------------------------------
+DAVID_METRICS = ("C", "CNR")
+DAVID_DIRECTIONS = ("x", "y", "z")
+
+
+def david_rows(case, res, k: int):
+    """The rows of david.py:70-91 -- ``(image, direction, acquisition, metric, value)`` in the reference's order -- from maps laid
+    out as ``erd.erd_volume`` returns them for ``case.dwi[:, :, slices, :]``; ``k`` is the cancer slice's position in ``slices``.
+    Host-side: ``contrast.calculate_contrast(case, 1, image, 0)`` per image."""
+    from . import contrast
+
+    sizes = [int(g) for g in np.asarray(case.acquisitions).reshape(-1)]
+    rows = []
+    first = 0
+    for g, size in enumerate(sizes):
+        name = DAVID_DIRECTIONS[g] if g < len(DAVID_DIRECTIONS) else str(g)
+        for acq in range(first, first + size):
+            images = (("DWI", np.asarray(case.dwi)[:, :, case.cancer_slice, acq]), ("ADC", res.adc[:, :, k, acq]))
+            values = [contrast.calculate_contrast(case, 1, im, 0) for _, im in images]
+            for inx, metric in enumerate(DAVID_METRICS):
+                rows.extend((image, name, acq, metric, v[inx]) for (image, _), v in zip(images, values))
+        first += size
+        images = (("DWI", res.direction_mean[g, :, :, k]), ("ADC", res.direction_adc[g, :, :, k]),
+                  ("DWI_ERD", res.accepted_mean[g, :, :, k]), ("ADC_ERD", res.accepted_adc[g, :, :, k]))
+        values = [contrast.calculate_contrast(case, 1, im, 0) for _, im in images]
+        for inx, metric in enumerate(DAVID_METRICS):
+            rows.extend((image, name, "mean", metric, v[inx]) for (image, _), v in zip(images, values))
+    return rows
+
+
+def david_study(case, rule: int = 1, slices="cancer"):
+    """``case`` is a ``contrast.case``.  One ``erd.erd_volume`` call over ``slices`` (``"cancer"``, ``"all"`` or slice indices,
+    which must include the cancer slice: the landmarks of the table belong to it) clusters every pixel (``rule`` 1 or 2; 0 uses
+    ``case.accept`` as it is), clears ``case.accept`` for the rejected acquisitions as david.py:55 does, and forms the means and
+    ADC maps.  The contrast numbers are computed host-side with ``contrast.calculate_contrast(case, 1, image, 0)`` on the cancer
+    slice, as the reference does.  Returns ``{"rows", "maps", "slices"}``: ``rows`` are ``(image, direction, acquisition, metric,
+    value)`` in the reference's order (david.py:70-91); ``maps`` holds float64 ``direction_mean, accepted_mean, direction_adc,
+    accepted_adc`` [G, X, Y, len(slices)], ``adc`` [X, Y, len(slices), n] and ``accept`` (as ``erd_volume`` returns it)."""
+    from . import erd
+
+    idx = erd.case_slices(case, slices)
+    if int(case.cancer_slice) not in idx:
+        raise ValueError(f"slices {idx} must include the cancer slice {case.cancer_slice}: the contrast landmarks belong to it")
+    emap = accept = None
+    if rule == 2:
+        if case.erd is None:
+            raise ValueError("--erd 2 needs the patient's ERD map (pat<NN>_ERD.mat: ADC_alldata_mm_ERD)")
+        emap = np.asarray(case.erd)[:, :, idx]
+    if rule == 0:
+        accept = np.asarray(case.accept)[:, :, idx, :]
+    res = erd.erd_volume(np.asarray(case.dwi)[:, :, idx, :], np.asarray(case.b0)[:, :, idx], case.acquisitions, case.b, rule=rule,
+                         erd_map=emap, accept=accept, per_acquisition_adc=True)
+    if rule != 0:
+        block = case.accept[:, :, idx, :]
+        block[res.accept == 0] = 0
+        case.accept[:, :, idx, :] = block
+    rows = david_rows(case, res, idx.index(int(case.cancer_slice)))
+    return {"rows": rows, "maps": res._asdict(), "slices": idx}

@@ -1,8 +1,9 @@
-"""The two CSV schemas the reference's drivers write, byte-compatible headers and row formats.
+"""The CSV schemas the reference's drivers write, byte-compatible headers and row formats.
 
 * ``SsimCsv``     -- superresDWI.py:27,36-37,186-187: ``Pt_id, b-value, slice, SSIM-spline, SSIM-SR`` (note the
                      comma-space separators), one row per (slice, b-value).
 * ``ContrastCsv`` -- master.py:59-62,190-195,254-259: ``seed,patient,direction,image,metric,performance``.
+* ``DavidCsv``    -- david.py:36-37,70-91: ``patient,image,direction,acquisition,metric,performance``.
 """
 from __future__ import annotations
 
@@ -11,6 +12,7 @@ import os
 SSIM_HEADER = 'Pt_id, b-value, slice, SSIM-spline, SSIM-SR\n'
 CONTRAST_HEADER = 'seed,patient,direction,image,metric,performance\n'
 CONTRAST_METRICS = ['C', 'CNR', 'CNR2']
+DAVID_HEADER = 'patient,image,direction,acquisition,metric,performance\n'
 
 
 class SsimCsv:
@@ -55,3 +57,19 @@ def read_csv(path, sep=','):
         lines = [l.rstrip('\n') for l in fh if l.strip()]
     keys = [k.strip() for k in lines[0].split(sep)]
     return [dict(zip(keys, [v.strip() for v in l.split(sep)])) for l in lines[1:]]
+
+
+class DavidCsv:
+    """david.py:36-37,70-91: one row per (image, direction, acquisition or ``mean``, metric)."""
+
+    def __init__(self, path):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        self.path = path
+        with open(path, 'w') as f:
+            f.write(DAVID_HEADER)
+
+    def rows(self, pt_no, rows):
+        """``rows``: ``(image, direction, acquisition, metric, value)`` in the order they are to be written."""
+        with open(self.path, 'a') as f:
+            for image, direction, acquisition, metric, value in rows:
+                f.write('{},{},{},{},{},{}\n'.format(pt_no, image, direction, acquisition, metric, value))
