@@ -582,7 +582,10 @@ int inr_pids_slice(float* adc_high, float* adc_negative, float* b_decay, float* 
  * affinity='euclidean', linkage='complete') splits it (scipy's nearest-neighbour chain + stable sort: ties fall as they do
  * there); rule 1 (--erd 1, majority voting): a cluster holding >= 2/3 of the acquisitions rejects the other; rule 2 (--erd 2,
  * intensity-cognisant): where erd_map (fp32 [n_pixels], nullable = everywhere) is positive, the cluster with the lower mean
- * is rejected.  2 <= n_acquisitions <= 32. */
+ * is rejected.  2 <= n_acquisitions <= 32.
+ * A pixel with a non-finite value (NaN, +-inf) among its n_acquisitions, or whose largest pairwise distance max - min overflows
+ * to +inf, is not clustered: all its accept entries are 1 (sklearn refuses such input; inr_auto_erd_volume keeps everything on
+ * exactly the same pixels).  The other pixels are unaffected. */
 int inr_auto_erd(float* accept, const double* values, const float* erd_map, int64_t n_pixels, int n_acquisitions, int rule,
                  void* stream);
 

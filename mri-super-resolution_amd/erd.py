@@ -22,7 +22,8 @@ from ._lib import check, lib
 def auto_erd(img, rule: int, erd_map=None) -> np.ndarray:
     """``img`` [H, W, n_acquisitions] (all acquisitions of one slice, any real dtype) -> accept [H, W, n] of 0 / 1 (int64, the
     dtype of ``case.accept``).  ``rule`` 1 = majority voting (--erd 1), 2 = intensity-cognisant (--erd 2; ``erd_map`` [H, W]:
-    pixels where it is not positive keep everything, master.py:89)."""
+    pixels where it is not positive keep everything, master.py:89).  A pixel holding a non-finite value, or finite values whose
+    largest difference overflows, is not clustered and keeps every acquisition, as in ``erd_volume``."""
     dev = ops.require_gpu()
     a = np.ascontiguousarray(np.asarray(img), dtype=np.float64)
     if a.ndim != 3:
