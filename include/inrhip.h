@@ -363,6 +363,46 @@ int64_t inr_rescale2d_workspace_doubles(int n_images, int height, int width, int
 int inr_rescale2d(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width, int order,
                   int mode, int anti_aliasing, int clip_group, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- register_imgset of the multi-image tree (multi-image-super-resolution/utils/preprocessing.py:138-161) --------------------------
+ * Per image of a set: the masked normalised cross-correlation against the set's clearest image (masked_register_translation, :155;
+ * Padfield 2012) and the cubic-spline scipy.ndimage.shift of the image (:156, 'reflect') and of its quality mask (:157, 'constant').
+ * Images and masks are [n_sets][T][H][W] fp32 (a mask pixel is set where it is != 0), arithmetic is fp64.  Plain launches, one thread
+ * per displacement in a fixed pixel order, fixed-order reductions, no floating-point atomics: repeated calls are bit-equal.
+ *
+ * inr_image_means (:149, and the clearances of select_T_images, :188): means [n_sets][T] = mean over H x W of each image (pass the
+ * masks); argmax (nullable) [n_sets] DEVICE ints = np.argmax of each set's means, the first maximum.
+ *
+ * inr_masked_xcorr (:155): image t of set s against image ref_index[s] (DEVICE ints, clamped to 0..T-1) of the same set, with the one
+ * mask m of image t on both sides, as skimage does when target_mask is None.  For every displacement d with |dy| <= max_dy,
+ * |dx| <= max_dx (H - 1, W - 1 is the reference's full search) pixel p of ref pairs with pixel p - d of x, and the pairs with m(p)
+ * and m(p - d) set give n, num = S_ab - S_a S_b / n, da = max(S_aa - S_a^2 / n, 0), db likewise, den = sqrt(da db) (all 0 for n = 0);
+ * tol = 1e3 2^-52 max den; C = clip(num / den, -1, 1) where den > tol, else 0; C = 0 where n < overlap_ratio max n.  The window only
+ * limits which displacements are evaluated: max den and max n are taken OVER THE WINDOW.  Per image: shifts [.][2] = the mean
+ * (dy, dx) of every d with C(d) == max C -- the translation to apply to x, scipy.ndimage.shift's argument --, peak = max C, n_max =
+ * the number of such d; map (nullable) [n_sets T][2 max_dy + 1][2 max_dx + 1] doubles = C, d = (-max_dy, -max_dx) first.
+ * 1 <= H, W <= INR_XCORR_MAX_SIDE, n_sets T <= 65535, 0 <= overlap_ratio <= 1.  workspace: inr_masked_xcorr_workspace_doubles(...)
+ * doubles (six sums per displacement and image), 16-byte aligned; 0 for arguments that would be refused, and every refusal comes
+ * before any device work.
+ *
+ * inr_shift2d (:156-157): scipy.ndimage.shift(in[b], shifts[b], order=3, mode, cval) as scipy 1.15 computes it: spline_filter with
+ * the half-sample-symmetric start for 'reflect' and the 'mirror' one for 'constant', the four B-spline weights per axis at o - s, taps
+ * beyond the line mapped by 'reflect' (d c b a | a b c d | d c b a), for 'constant' by 'mirror'; in 'constant' an output whose source
+ * coordinate leaves [0, n - 1] on either axis is cval exactly.  in / out [n_images][H][W] fp32 (the fp64 result rounded once), shifts
+ * [n_images][2] DEVICE doubles (dy, dx) -- inr_masked_xcorr's output, no host read in between; a shift of 1e9 or more, or NaN,
+ * gives NaN.  H, W <= INR_RESCALE_MAX_LINE.  workspace: inr_shift2d_workspace_doubles(...) doubles (the coefficient plane), 16-byte
+ * aligned; 0 for arguments that would be refused, before any device work. */
+#define INR_SHIFT_REFLECT 0
+#define INR_SHIFT_CONSTANT 1
+#define INR_XCORR_MAX_SIDE 4096
+int inr_image_means(double* means, int* argmax, const float* images, int n_sets, int T, int height, int width, void* stream);
+int64_t inr_masked_xcorr_workspace_doubles(int n_sets, int T, int height, int width, int max_dy, int max_dx);
+int inr_masked_xcorr(double* shifts, double* peak, int* n_max, double* map, const float* images, const float* masks,
+                     const int* ref_index, int n_sets, int T, int height, int width, int max_dy, int max_dx, double overlap_ratio,
+                     double* workspace, int64_t workspace_doubles, void* stream);
+int64_t inr_shift2d_workspace_doubles(int n_images, int height, int width, int mode);
+int inr_shift2d(float* out, const float* in, const double* shifts, int n_images, int height, int width, int mode, double cval,
+                double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- (f)-3: the through-plane spline baseline (SRDWI.py:132-141 resize_array, used at superresDWI.py:231) -------------------
  * scipy.interpolate.interp1d(linspace(0, 1, n_in), y, kind='cubic') evaluated at linspace(0, 1, n_out): make_interp_spline(k=3),
  * not-a-knot end conditions, fp64 throughout.  in [n_lines][n_in] -> out [n_lines][n_out] (the last axis is contiguous:

@@ -9,7 +9,7 @@ Layout:  csrc/ (HIP kernels + C ABI, built into libinrhip.so) . _lib.py (ctypes 
 (tensor wrappers) . flat.py (flat parameter buffer, workspaces and Adam state of every fitter) . inr.py (reference module surface + fused fit / reconstruct) . metrics.py . baselines.py (spline
 rescale) . drivers.py (the reference's driver loops) . dist.py (fit partitioning over GPUs, metric gather) . matio.py
 (.mat level 5) . reports.py (CSV schemas) . contrast.py (case / calculate_contrast) . wire.py (the complex-Gabor WIRE network and
-its fitter) . scripts/ (superresDWI, master).
+its fitter) . registration.py (masked registration and the multi-image data preparation) . scripts/ (superresDWI, master).
 """
 from ._lib import InrHipError, InrHipUnavailable  # noqa: F401
 from .ops import InrDeviceError  # noqa: F401

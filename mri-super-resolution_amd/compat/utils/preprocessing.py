@@ -1,5 +1,9 @@
-"""``utils/preprocessing.py`` of the reference, the part a model comparison needs: ``bicubic`` (preprocessing.py:271-294), the
-multi-image tree's own interpolation baseline.  The rest of that file prepares the PROBA-V data set and is not provided."""
+"""``utils/preprocessing.py`` of the reference on the device path: ``bicubic`` (preprocessing.py:271-294), the multi-image tree's own
+interpolation baseline, and the preparation of the PROBA-V data set -- ``register_dataset`` / ``register_imgset`` (:115-161, with
+``masked_register_translation`` and ``shift``, which they call), ``select_T_images`` (:165-216), ``sub_images`` / ``gen_sub``
+(:218-269) and ``augment_dataset`` / ``augment_imgset`` (:62-111), all from ``mri_super_resolution_amd.registration``.
+``register_imgset`` returns the REGISTERED images: the vendored copy returns its input (:161) and never imports
+``masked_register_translation`` (:15 is commented out), see that module.  ``load_dataset`` (:19-58) is a name that raises."""
 import os
 import sys
 
@@ -8,6 +12,15 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import _bootstrap  # noqa: F401,E402
 from mri_super_resolution_amd import baselines  # noqa: E402
+from mri_super_resolution_amd.registration import (augment_dataset, augment_imgset, gen_sub, masked_register_translation,  # noqa: E402,F401
+                                                   register_dataset, register_imgset, select_T_images, shift, sub_images)
+
+
+def load_dataset(base_dir, part, band):
+    """preprocessing.py:19-58 reads the PROBA-V PNG trees through ``cv2``: neither OpenCV nor the data set is part of this build.
+    The name exists so that ``from utils.preprocessing import load_dataset`` resolves; calling it says why nothing is read."""
+    raise NotImplementedError("load_dataset: reading the PROBA-V PNG trees (cv2.imread) is outside this build's scope; load "
+                              f"'{base_dir}/{part}/{band}' into [H, W, T] arrays yourself and pass them to register_dataset")
 
 
 def bicubic(X, scale=3):

@@ -164,6 +164,9 @@ int rescale_check(const char* who, int nimg, int H, int W, int OH, int OW, int o
 int launch_rescale2d(float* out, const float* in, int nimg, int H, int W, int OH, int OW, int order, int mode, int anti_aliasing,
                      int clip_group, const RescaleView& v, hipStream_t st);
 
+// (register.hip -- masked cross-correlation, image means, the spline shift -- defines public entry points only; the spline prefilter and
+// sampler it shares with rescale.hip are device code, in spline.h.)
+
 // ---- perceptual.hip: the reader study's scores (Gaussian SSIM, MS-SSIM, 3 x 3 high-pass, MSE, high-frequency gain) ------------------------
 constexpr int PERCEPTUAL_MAX_RADIUS = INR_PERCEPTUAL_MAX_RADIUS;   // window taps per side: what the tile's halo in LDS holds
 constexpr int PERCEPTUAL_MAX_SCALES = INR_PERCEPTUAL_MAX_SCALES;

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "internal.h"
+#include "spline.h"
 
 namespace inr {
 namespace {
@@ -85,48 +86,6 @@ __global__ void __launch_bounds__(256) rs_pad_kernel(double* __restrict__ out, c
     }
 }
 
-// the prefilter of one line of n >= 2 samples `stride` apart, in place (scipy ni_splines.c: gain, _init_causal_mirror, the causal
-// recursion, _init_anticausal_mirror, the anticausal recursion)
-__device__ __forceinline__ void rs_prefilter_line(double* c, long long stride, int n) {
-    const double z = -0.26794919243112270647;   // sqrt(3) - 2
-    const double gain = (1.0 - z) * (1.0 - 1.0 / z);
-    for (int i = 0; i < n; ++i) c[i * stride] *= gain;
-    const double zn = pow(z, (double)(n - 1));
-    double c0 = c[0] + zn * c[(n - 1) * stride], zi = z;
-    for (int i = 1; i < n - 1; ++i) {
-        c0 += zi * (c[i * stride] + zn * c[(n - 1 - i) * stride]);
-        zi *= z;
-    }
-    c[0] = c0 / (1.0 - zn * zn);
-    for (int i = 1; i < n; ++i) c[i * stride] += z * c[(i - 1) * stride];
-    c[(n - 1) * stride] = (z * c[(n - 2) * stride] + c[(n - 1) * stride]) * (z / (z * z - 1.0));
-    for (int i = n - 2; i >= 0; --i) c[i * stride] = z * (c[(i + 1) * stride] - c[i * stride]);
-}
-
-// axis 0: one thread per column, neighbouring lanes on neighbouring doubles of every row
-__global__ void __launch_bounds__(256) rs_prefilter_cols_kernel(double* __restrict__ c, long long columns, int PH, int PW) {
-    for (long long idx = (long long)blockIdx.x * 256 + threadIdx.x; idx < columns; idx += (long long)gridDim.x * 256)
-        rs_prefilter_line(c + (idx / PW) * ((long long)PH * PW) + idx % PW, PW, PH);
-}
-
-// axis 1: the lines are contiguous, so a block stages `rows` of them in LDS (coalesced both ways) at an odd pitch in doubles, and
-// one lane per staged row runs the recursion there: lanes a row apart sit an odd number of 8-byte words apart, on distinct banks
-constexpr int RS_ROW_THREADS = 64, RS_ROWS_MAX = 16, RS_LDS_BYTES = 65536;
-__global__ void __launch_bounds__(RS_ROW_THREADS) rs_prefilter_rows_kernel(double* __restrict__ c, long long lines, int PW, int rows,
-                                                                           int pitch) {
-    extern __shared__ double stage[];   // [rows][pitch]
-    for (long long first = (long long)blockIdx.x * rows; first < lines; first += (long long)gridDim.x * rows) {
-        const int have = (int)(lines - first < rows ? lines - first : rows);
-        double* g = c + first * PW;
-        for (int i = threadIdx.x; i < have * PW; i += RS_ROW_THREADS) stage[(i / PW) * pitch + i % PW] = g[i];
-        __syncthreads();
-        if ((int)threadIdx.x < have) rs_prefilter_line(stage + threadIdx.x * pitch, 1, PW);
-        __syncthreads();
-        for (int i = threadIdx.x; i < have * PW; i += RS_ROW_THREADS) g[i] = stage[(i / PW) * pitch + i % PW];
-        __syncthreads();
-    }
-}
-
 // samples the [nimg][PH][PW] plane c (PH = H + 2 pad) at the grid of the [OH][OW] output, separable with axis 0 first, clips, rounds
 // once to fp32.  mm == null: no clip; else image b belongs to group b / clip_group
 template <int ORDER>
@@ -147,15 +106,8 @@ __global__ void __launch_bounds__(256) rs_sample_kernel(float* __restrict__ out,
         if (ORDER == 1) {
             wy[0] = 1.0 - ty, wy[1] = ty, wx[0] = 1.0 - tx, wx[1] = tx;
         } else {
-            auto weights = [](double t, double* w) {
-                const double u = 1.0 - t;
-                w[0] = u * u * u / 6.0;
-                w[1] = (4.0 - 6.0 * t * t + 3.0 * t * t * t) / 6.0;
-                w[2] = (1.0 + 3.0 * t + 3.0 * t * t - 3.0 * t * t * t) / 6.0;
-                w[3] = t * t * t / 6.0;
-            };
-            weights(ty, wy);
-            weights(tx, wx);
+            bspline3_weights(ty, wy);
+            bspline3_weights(tx, wx);
         }
         const int first = ORDER == 1 ? 0 : -1;
 #pragma unroll
@@ -163,25 +115,13 @@ __global__ void __launch_bounds__(256) rs_sample_kernel(float* __restrict__ out,
             iy[k] = rs_index((int)fy0 + first + k, PH, mode);
             ix[k] = rs_index((int)fx0 + first + k, PW, mode);
         }
-        double v = 0.0;
-#pragma unroll
-        for (int kx = 0; kx < TAPS; ++kx) {
-            double col = 0.0;
-#pragma unroll
-            for (int ky = 0; ky < TAPS; ++ky) col += wy[ky] * img[(long long)iy[ky] * PW + ix[kx]];
-            v += wx[kx] * col;
-        }
+        double v = spline_tap_sum<TAPS>(img, PW, iy, ix, wy, wx);
         if (mm) {
             const double lo = mm[2 * (b / clip_group)], hi = mm[2 * (b / clip_group) + 1];
             v = v < lo ? lo : (v > hi ? hi : v);
         }
         out[idx] = (float)v;
     }
-}
-
-inline unsigned rs_blocks(long long work) {
-    const long long b = (work + 255) / 256;
-    return (unsigned)(b > 65536 ? 65536 : b);
 }
 
 // sigma and taps of one axis; false when the radius is beyond what RsTaps carries
@@ -266,22 +206,8 @@ int launch_rescale2d(float* out, const float* in, int nimg, int H, int W, int OH
     const long long padded = (long long)nimg * PH * PW;
     hipLaunchKernelGGL(rs_pad_kernel, dim3(rs_blocks(padded)), dim3(256), 0, st, v.coef, (const double*)v.filtered, padded, H, W, pad);
     INR_LAUNCH_CHECK();
-    if (PH > 1) {   // scipy leaves lines of one sample alone
-        hipLaunchKernelGGL(rs_prefilter_cols_kernel, dim3(rs_blocks((long long)nimg * PW)), dim3(256), 0, st, v.coef, (long long)nimg * PW,
-                           PH, PW);
-        INR_LAUNCH_CHECK();
-    }
-    if (PW > 1) {
-        const int pitch = PW | 1;
-        int rows = RS_LDS_BYTES / (pitch * (int)sizeof(double));
-        rows = rows > RS_ROWS_MAX ? RS_ROWS_MAX : rows;
-        static_assert(((RESCALE_MAX_LINE + 2 * RS_PAD) | 1) * sizeof(double) <= RS_LDS_BYTES, "one staged row must fit the LDS");
-        const long long lines = (long long)nimg * PH;
-        const long long blocks = (lines + rows - 1) / rows;
-        hipLaunchKernelGGL(rs_prefilter_rows_kernel, dim3((unsigned)(blocks > 65536 ? 65536 : blocks)), dim3(RS_ROW_THREADS),
-                           (size_t)rows * pitch * sizeof(double), st, v.coef, lines, PW, rows, pitch);
-        INR_LAUNCH_CHECK();
-    }
+    static_assert(((RESCALE_MAX_LINE + 2 * RS_PAD) | 1) * sizeof(double) <= RS_LDS_BYTES, "one staged row must fit the LDS");
+    if (int rc = launch_spline_prefilter<SPLINE_MIRROR>(v.coef, nimg, PH, PW, st)) return rc;
     hipLaunchKernelGGL(rs_sample_kernel<3>, dim3(rs_blocks(total)), dim3(256), 0, st, out, (const double*)v.coef, mm, total, H, W, OH, OW,
                        pad, mode, clip_group);
     INR_LAUNCH_CHECK();

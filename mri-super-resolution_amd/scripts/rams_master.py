@@ -10,6 +10,10 @@ master.py:1 imports was never published: a JSON list of ``case`` constructor arg
 ``--ssim`` (adds ``cssim_vs_rescaled`` to every case record: the shift-tolerant SSIM of ``utils/loss.py:131-177`` between the
 super-resolved mean and the x3 linear rescale of the acquisition mean of the same slice -- there is no high-resolution label at
 inference, so this is a structure-agreement figure; without the flag nothing is computed or written differently),
+``--register`` / ``--register_max_shift N`` (the slice's acquisitions are laid on acquisition 0 by masked cross-correlation within
+``N`` pixels, default 8, and a cubic-spline shift -- ``register_imgset`` of ``utils/preprocessing.py:138-161`` with all-clear masks,
+whose first-maximum rule picks acquisition 0 -- before the uint16 cast, and every case record gains ``shifts`` [T, 2]; master.py
+averages its subsets without ever aligning them, and without the flag nothing is computed or written differently),
 ``--weights`` (an ``.npz`` of the network's variables, ``RAMS.save_weights``: the checkpoint under ``ckpt/RED_RAMS`` that
 master.py:27-33 restores is shipped WITHOUT its ``*.data-00001-of-00002`` shard and there is no TensorFlow here to read one --
 without ``--weights`` the network keeps its random initialisation and the script says so), ``--sample_size`` (25) and ``--seed``
@@ -29,7 +33,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
-from mri_super_resolution_amd import baselines, contrast, matio  # noqa: E402
+from mri_super_resolution_amd import baselines, contrast, matio, registration  # noqa: E402
 from mri_super_resolution_amd.rams import RAMS, predict_tensor, ssim_per_image  # noqa: E402
 
 SCALE = 3           # master.py:20-26
@@ -54,14 +58,27 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=None, help='seed of the subset draws (the reference draws unseeded)')
     parser.add_argument('--ssim', action='store_true', help='add cssim_vs_rescaled (cSSIM, utils/loss.py:131-177, of the mean '
                                                             'prediction against the rescaled acquisition mean) to every case record')
+    parser.add_argument('--register', action='store_true', help='register the acquisitions of the slice to acquisition 0 before the '
+                                                                'uint16 cast and add shifts [T, 2] to every case record')
+    parser.add_argument('--register_max_shift', type=int, default=8, help='search window of --register in pixels per axis')
     return parser
 
 
-def super_resolve_case(model, case, sample_size=25, rng=random):
-    """master.py:38-57 for one patient; returns ``(mean_pred [3X, 3Y] float64, adc_large, subsets)``."""
+def register_slice(case, max_shift=8):
+    """The acquisitions [X, Y, T] of the cancer slice laid on acquisition 0 (all masks clear: the first of the equal clearances is
+    the reference); returns ``(registered float64 [X, Y, T], shifts [T, 2])``."""
+    seq = np.asarray(case.dwi[:, :, case.cancer_slice, :], np.float64)
+    reg, _, shifts = registration.register_imgset(seq, np.ones(seq.shape), max_shift=max_shift, return_shifts=True)
+    return np.clip(reg, 0.0, None), shifts                                                  # the cubic overshoots: the cast is unsigned
+
+
+def super_resolve_case(model, case, sample_size=25, rng=random, low_res_seq=None):
+    """master.py:38-57 for one patient; returns ``(mean_pred [3X, 3Y] float64, adc_large, subsets)``.  ``low_res_seq`` replaces the
+    slice's acquisitions [X, Y, T] (``register_slice``)."""
     _low_res_seq = case.dwi
     num_acq = _low_res_seq.shape[3]
-    low_res_seq = _low_res_seq[:, :, case.cancer_slice, :]
+    if low_res_seq is None:
+        low_res_seq = _low_res_seq[:, :, case.cancer_slice, :]
     lor = np.expand_dims(low_res_seq, 0).astype('uint16')
     lor = lor * 256
     channels = model.cfg["channels"]
@@ -102,7 +119,12 @@ def run(args, cases):
     summary = []
     for case in cases:
         t0 = time.perf_counter()
-        mean_pred, adc_large, subsets = super_resolve_case(rams_network, case, args.sample_size, rng)
+        shifts = None
+        if getattr(args, "register", False):
+            registered, shifts = register_slice(case, args.register_max_shift)
+            mean_pred, adc_large, subsets = super_resolve_case(rams_network, case, args.sample_size, rng, low_res_seq=registered)
+        else:
+            mean_pred, adc_large, subsets = super_resolve_case(rams_network, case, args.sample_size, rng)
         dt = time.perf_counter() - t0
         pt_no = case.pt_id.split('-')[-1]
         out_dir = os.path.join(args.out_img_folder, args.exp_name, pt_no)
@@ -114,6 +136,8 @@ def run(args, cases):
                         "subsets": subsets, "out_dir": out_dir})
         if getattr(args, "ssim", False):
             summary[-1]["cssim_vs_rescaled"] = cssim_vs_rescaled(mean_pred, case, rams_network.cfg["scale"])
+        if shifts is not None:
+            summary[-1]["shifts"] = np.asarray(shifts).tolist()
     with open(os.path.join(args.out_folder, args.exp_name + '.json'), 'w') as fh:
         json.dump({"weights": args.weights, "cases": summary}, fh)
     return {"cases": summary, "weights": args.weights}
