@@ -413,6 +413,43 @@ size_t inr_resize_z_cubic_workspace_bytes(int64_t n_lines, int n_in);
 int inr_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, void* workspace, size_t workspace_bytes,
                        void* stream);
 
+/* ---- Fourier re-sampling: k-space zero-fill (up) and truncation (down), the interpolation an MR scanner applies ---------
+ * No counterpart in the reference, whose only interpolation baseline is skimage's spline; the definition is scipy.signal.resample's.
+ * A line x[0..n) becomes y = A x, A [m][n]:
+ *   A[i][j] = (1/n) sum_{k = 0..K} c_k w(k) cos(2 pi k (p_i - j) / n),  L = min(n, m), K = floor(L/2),  p_i = i n/m + delta
+ *   c_0 = 1, c_k = 2 for 0 < k < L/2; at k = L/2 of an even L: 1 if L == n (the input's Nyquist bin), 2 if L == m < n (both bins folded).
+ * align:    INR_FOURIER_SAMPLE  delta = 0: sample 0 stays on sample 0, the grid of a decimation (scipy.signal.resample);
+ *           INR_FOURIER_CENTER  delta = (n/m - 1)/2: pixel centres, the grid of skimage's rescale.
+ * apodize:  alpha in [0, 1], a Tukey window over the kept band: r = k / (L/2), w = 1 for r <= 1 - alpha, else
+ *           (1 + cos(pi (r - 1 + alpha) / alpha)) / 2.  0 = no window, 1 = Hann.
+ * boundary: INR_FOURIER_PERIODIC  the above;
+ *           INR_FOURIER_MIRROR    the periodic operator E of the mirrored line, folded back onto the n samples, its first m rows.  SAMPLE:
+ *           the line [x, x[n-2:0:-1]] of period P = 2n - 2, E: P -> P m/n, A[:, j] = E[:, j] + E[:, P - j] for 0 < j < n - 1 -- needs
+ *           n >= 2 and (2n - 2) m divisible by n (INR_E_INVALID otherwise).  CENTER: [x, x[::-1]] of period 2n, E: 2n -> 2m,
+ *           A[:, j] = E[:, j] + E[:, 2n - 1 - j], any n and m.
+ * Rows of A sum to 1.  Every line length is 1..INR_FOURIER_MAX_LINE.  Two dimensions are the two axes in turn, Y = A_rows X A_cols^T.
+ *
+ * inr_fourier_operator: op [m][n] DEVICE doubles = A; one thread per entry, every phase reduced exactly in int64 before cospi, the terms
+ * added in ascending k.
+ * inr_fourier_resample2d: in [n_images][H][W] -> out [n_images][OH][OW] (out must not overlap in), fp64; the _f32 form reads and writes
+ * fp32 with fp64 inside and rounds once.  Each axis is one launch of a batched fp64 GEMM on v_mfma_f64_16x16x4_f64 (fixed K order, no
+ * atomics: calls are bit-equal); an axis with m == n, INR_FOURIER_SAMPLE and apodize == 0 is skipped and its data pass through bit for
+ * bit; so is an axis of one sample that stays one (its operator is [1] in every mode, and the mirror rule does not apply to it: the 1-D
+ * form is a batch of 1 x n images).  n_images == 0 succeeds and launches nothing; n_images max(H, OH) < 2^36.
+ * workspace: inr_fourier_resample_workspace_doubles(...) doubles (the two operators and the plane between the two passes), 16-byte
+ * aligned; 0 for sizes that would be refused.  Every refusal comes before any device work. */
+#define INR_FOURIER_SAMPLE 0
+#define INR_FOURIER_CENTER 1
+#define INR_FOURIER_PERIODIC 0
+#define INR_FOURIER_MIRROR 1
+#define INR_FOURIER_MAX_LINE 1024
+int inr_fourier_operator(double* op, int n, int m, int align, int boundary, double apodize, void* stream);
+int64_t inr_fourier_resample_workspace_doubles(int n_images, int height, int width, int out_height, int out_width);
+int inr_fourier_resample2d(double* out, const double* in, int n_images, int height, int width, int out_height, int out_width, int align,
+                           int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream);
+int inr_fourier_resample2d_f32(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
+                               int align, int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
  * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
  * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output

@@ -23,6 +23,7 @@ INR_JET_LF_INPUT, INR_JET_LF_LAYER, INR_JET_LF_HEAD, INR_JET_LF_COUNT = 0, 1, 2,
 INR_LF_ERD_STEP, INR_LF_ERD_REDUCE, INR_LF_ERD_FORWARD, INR_LF_ERD_SOFT = 32, 33, 34, 35
 INR_ERD_RUNNING, INR_ERD_CONVERGED, INR_ERD_COLLAPSED = 0, 1, 2
 INR_RESCALE_REFLECT, INR_RESCALE_EDGE, INR_RESCALE_MAX_RADIUS, INR_RESCALE_MAX_LINE = 0, 1, 64, 4096
+INR_FOURIER_SAMPLE, INR_FOURIER_CENTER, INR_FOURIER_PERIODIC, INR_FOURIER_MIRROR, INR_FOURIER_MAX_LINE = 0, 1, 0, 1, 1024
 
 
 class InrHipError(RuntimeError):
@@ -141,6 +142,12 @@ SIGNATURES = {
     "inr_adc_map": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_resize_z_cubic_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int]),
     "inr_resize_z_cubic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_size_t, c_stream]),
+    "inr_fourier_operator": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, c_stream]),
+    "inr_fourier_resample_workspace_doubles": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "inr_fourier_resample2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_double, C.c_void_p, C.c_int64, c_stream]),
+    "inr_fourier_resample2d_f32": (C.c_int, [c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_double, C.c_void_p, C.c_int64, c_stream]),
     "inr_perceptual_workspace_doubles": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "inr_ssim2d_gauss": (C.c_int, [C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double,
                                    C.c_void_p, C.c_int64, c_stream]),

@@ -1504,6 +1504,49 @@ int inr_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in,
     return launch_resize_z_cubic(out, in, n_lines, n_in, n_out, (double*)workspace, (hipStream_t)stream);
 }
 
+// ---- Fourier re-sampling (fourier.hip) ---------------------------------------------------------------------------------------------------
+int inr_fourier_operator(double* op, int n, int m, int align, int boundary, double apodize, void* stream) {
+    INR_REQUIRE(op, INR_E_INVALID, "inr_fourier_operator: null pointer");
+    if (int rc = fourier_operator_check("inr_fourier_operator", n, m, align, boundary, apodize)) return rc;
+    return launch_fourier_operator(op, n, m, align, boundary, apodize, (hipStream_t)stream);
+}
+
+int64_t inr_fourier_resample_workspace_doubles(int n_images, int height, int width, int out_height, int out_width) {
+    if (fourier_sizes_check("inr_fourier_resample_workspace_doubles", n_images, height, width, out_height, out_width)) return 0;
+    return (int64_t)(fourier_view(n_images, height, width, out_height, out_width, nullptr).total / sizeof(double));
+}
+
+// the arguments and the workspace of one re-sampling call, before any device work
+static int fourier_call_check(const char* who, const void* out, const void* in, int n_images, int height, int width, int out_height,
+                              int out_width, int align, int boundary, double apodize, const double* workspace, int64_t workspace_doubles) {
+    INR_REQUIRE(out && in, INR_E_INVALID, "%s: null pointer", who);
+    if (int rc = fourier_check(who, n_images, height, width, out_height, out_width, align, boundary, apodize)) return rc;
+    const size_t need = fourier_view(n_images, height, width, out_height, out_width, nullptr).total;
+    INR_REQUIRE(workspace && workspace_doubles >= 0 && (size_t)workspace_doubles * sizeof(double) >= need, INR_E_WORKSPACE,
+                "%s: workspace too small (%lld doubles, %zu needed)", who, workspace ? (long long)workspace_doubles : 0ll,
+                need / sizeof(double));
+    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
+    return 0;
+}
+
+int inr_fourier_resample2d(double* out, const double* in, int n_images, int height, int width, int out_height, int out_width, int align,
+                           int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream) {
+    if (int rc = fourier_call_check("inr_fourier_resample2d", out, in, n_images, height, width, out_height, out_width, align, boundary,
+                                    apodize, workspace, workspace_doubles))
+        return rc;
+    return launch_fourier_resample2d(out, in, n_images, height, width, out_height, out_width, align, boundary, apodize,
+                                     fourier_view(n_images, height, width, out_height, out_width, workspace), (hipStream_t)stream);
+}
+
+int inr_fourier_resample2d_f32(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
+                               int align, int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream) {
+    if (int rc = fourier_call_check("inr_fourier_resample2d_f32", out, in, n_images, height, width, out_height, out_width, align, boundary,
+                                    apodize, workspace, workspace_doubles))
+        return rc;
+    return launch_fourier_resample2d(out, in, n_images, height, width, out_height, out_width, align, boundary, apodize,
+                                     fourier_view(n_images, height, width, out_height, out_width, workspace), (hipStream_t)stream);
+}
+
 // ---- the reader study's scores (perceptual.hip) ------------------------------------------------------------------------------------------
 int64_t inr_perceptual_workspace_doubles(int n_images, int height, int width, int n_scales) {
     if (perceptual_check("inr_perceptual_workspace_doubles", n_images, height, width, 1.5, 1.0, n_scales)) return 0;

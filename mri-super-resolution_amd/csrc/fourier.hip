@@ -1,0 +1,267 @@
+// Fourier re-sampling of real lines and images: zero-filling k-space (up) and truncating it (down) -- the interpolation an MR scanner
+// itself applies, and the baseline a DWI super-resolution result is judged against first.  DESIGN.md 4j; tests/fourier_common.py restates
+// the operator in numpy and checks it against scipy.signal.resample.
+//
+//   y = A x,  A [m][n],  A[i][j] = (1/n) sum_{k = 0..K} c_k w(k) cos(2 pi k (p_i - j) / n),  L = min(n, m), K = floor(L/2),
+//   p_i = i n/m + delta;  delta = 0 (INR_FOURIER_SAMPLE: sample 0 stays on sample 0, scipy.signal.resample) or (n/m - 1)/2
+//   (INR_FOURIER_CENTER: pixel centres);  c_0 = 1, c_k = 2, and at k = L/2 of an even L: 1 when L == n (the input's Nyquist bin, split
+//   between +n/2 and -n/2), 2 when L == m < n (both bins folded onto the output's Nyquist);  w = Tukey window over the kept band.
+//   INR_FOURIER_MIRROR: the periodic operator E of the mirrored line, folded back onto the n samples, its first m rows:
+//     SAMPLE: [x, x[n-2:0:-1]], period P = 2n - 2, E: P -> P m/n, A[:, j] = E[:, j] + E[:, P - j] for 0 < j < n - 1
+//     CENTER: [x, x[::-1]],     period 2n,         E: 2n -> 2m,   A[:, j] = E[:, j] + E[:, 2n - 1 - j]
+//
+// The operator kernel forms one entry per thread: with q = 2 i En - 2 j Em (+ En - Em for CENTER) every phase is
+// pi (k q mod 2 En Em) / (En Em), reduced exactly in int64 before cospi; the terms are added in ascending k, a mirror entry is the sum
+// of its two cosine sums.  The apply kernel is a batched, strided fp64 GEMM on v_mfma_f64_16x16x4_f64 with a fixed K order and no
+// atomics: calls are bit-equal.  All arithmetic is fp64; the fp32 entry point converts on load and rounds once on the last store.
+#include <math.h>
+
+#include "internal.h"
+
+namespace inr {
+namespace {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int FR_TILE = 64;    // the block's output tile: 4 waves, 32 x 32 each (2 x 2 MFMA tiles)
+constexpr int FR_KS = 16;      // K per LDS stage: 4 MFMA steps
+constexpr int FR_PITCH = 81;   // doubles per staged k: the 16 k of a k-fastest store fall on 16 bank pairs, the two k of a read's lane
+                               // group on disjoint halves of the 64 banks (but for one pair)
+
+// one axis: A [m][n] from the periodic operator E: En -> Em
+struct FrAxis {
+    int n, m;
+    int En, Em;
+    int center;    // q gains En - Em
+    int fold;      // 0: none; 1: column En - j for 0 < j < n - 1 (whole-sample mirror); 2: column En - 1 - j (half-sample mirror)
+    double apodize;
+};
+
+FrAxis fr_axis(int n, int m, int align, int boundary, double apodize) {
+    FrAxis a{n, m, n, m, align == INR_FOURIER_CENTER, 0, apodize};
+    if (boundary == INR_FOURIER_MIRROR) {
+        if (a.center) {
+            a.En = 2 * n, a.Em = 2 * m, a.fold = 2;
+        } else {
+            a.En = 2 * n - 2, a.Em = (int)((long long)(2 * n - 2) * m / n), a.fold = 1;
+        }
+    }
+    return a;
+}
+
+// an axis whose data pass through bit for bit; the operator of a 1 -> 1 axis is [1] in every mode
+bool fr_identity(int n, int m, int align, double apodize) {
+    return n == m && (n == 1 || (align == INR_FOURIER_SAMPLE && apodize == 0.0));
+}
+
+// sum_{k = 0..K} c_k w(k) cos(pi (k q mod D) / (D/2)), D = 2 En Em, ascending k
+__device__ double fr_cos_sum(long long q, long long D, int L, double nyquist, double alpha) {
+    q %= D;
+    if (q < 0) q += D;
+    const double half = (double)(D / 2);
+    double s = 0.0;
+    for (int k = 0; k <= L / 2; ++k) {
+        const double c = k == 0 ? 1.0 : (2 * k == L ? nyquist : 2.0);
+        double w = 1.0;
+        if (alpha > 0.0) {
+            const double r = 2.0 * k / L;
+            if (r > 1.0 - alpha) w = 0.5 * (1.0 + cospi((r - 1.0 + alpha) / alpha));
+        }
+        s += c * w * cospi((double)((k * q) % D) / half);
+    }
+    return s;
+}
+
+__global__ void __launch_bounds__(256) fr_operator_kernel(double* __restrict__ op, FrAxis a) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)a.m * a.n) return;
+    const long long i = idx / a.n, j = idx % a.n;
+    const long long En = a.En, Em = a.Em, D = 2 * En * Em, off = a.center ? En - Em : 0;
+    const int L = a.En < a.Em ? a.En : a.Em;
+    const double nyquist = L == a.En ? 1.0 : 2.0;
+    double s = fr_cos_sum(2 * En * i - 2 * Em * j + off, D, L, nyquist, a.apodize);
+    if (a.fold == 1 && j > 0 && j < a.n - 1) s += fr_cos_sum(2 * En * i - 2 * Em * (En - j) + off, D, L, nyquist, a.apodize);
+    if (a.fold == 2) s += fr_cos_sum(2 * En * i - 2 * Em * (En - 1 - j) + off, D, L, nyquist, a.apodize);
+    op[idx] = s / (double)En;
+}
+
+// C [M][N] = A [M][K] B [K][N] per batch entry; A has k contiguous, C its columns; a batch stride of 0 shares the operand
+struct FrGemm {
+    long long M;
+    int N, K, batch;
+    long long a_batch, a_row;
+    long long b_batch, b_k, b_col;
+    long long c_batch, c_row;
+};
+
+template <typename TA, typename TB, typename TC>
+__global__ void __launch_bounds__(256) fr_gemm_kernel(TC* __restrict__ C, const TA* __restrict__ A, const TB* __restrict__ B, FrGemm g) {
+    __shared__ double As[FR_KS][FR_PITCH];   // [k][row]
+    __shared__ double Bs[FR_KS][FR_PITCH];   // [k][column]
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const long long row0 = (long long)blockIdx.x * FR_TILE;
+    const int col0 = blockIdx.y * FR_TILE;
+    for (int b = blockIdx.z; b < g.batch; b += gridDim.z) {
+        const TA* Ab = A + b * g.a_batch;
+        const TB* Bb = B + b * g.b_batch;
+        TC* Cb = C + b * g.c_batch;
+        f64x4 acc[2][2] = {};
+        for (int k0 = 0; k0 < g.K; k0 += FR_KS) {
+            for (int e = t; e < FR_TILE * FR_KS; e += 256) {
+                const int kk = e & (FR_KS - 1), r = e / FR_KS;
+                const long long row = row0 + r;
+                const int k = k0 + kk;
+                As[kk][r] = row < g.M && k < g.K ? (double)Ab[row * g.a_row + k] : 0.0;
+            }
+            for (int e = t; e < FR_TILE * FR_KS; e += 256) {
+                // the contiguous direction of B goes over neighbouring threads
+                const int kk = g.b_k == 1 ? e & (FR_KS - 1) : e / FR_TILE, c = g.b_k == 1 ? e / FR_KS : e & (FR_TILE - 1);
+                const int col = col0 + c, k = k0 + kk;
+                Bs[kk][c] = col < g.N && k < g.K ? (double)Bb[k * g.b_k + col * g.b_col] : 0.0;
+            }
+            __syncthreads();
+#pragma unroll
+            for (int ks = 0; ks < FR_KS; ks += 4) {
+                // A: lane holds A[row lane & 15][k lane >> 4]; B: B[k lane >> 4][column lane & 15]
+                const double a0 = As[ks + l4][wr + l15], a1 = As[ks + l4][wr + 16 + l15];
+                const double b0 = Bs[ks + l4][wc + l15], b1 = Bs[ks + l4][wc + 16 + l15];
+                acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
+            }
+            __syncthreads();
+        }
+        // the f64 result layout: column lane & 15, row (lane >> 4) + 4 reg -- not the f32 one
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                for (int reg = 0; reg < 4; ++reg) {
+                    const long long row = row0 + wr + 16 * mi + l4 + 4 * reg;
+                    const int col = col0 + wc + 16 * ni + l15;
+                    if (row < g.M && col < g.N) Cb[row * g.c_row + col] = (TC)acc[mi][ni][reg];
+                }
+    }
+}
+
+template <typename TA, typename TB, typename TC>
+int fr_gemm(TC* C, const TA* A, const TB* B, const FrGemm& g, hipStream_t st) {
+    const dim3 grid((unsigned)((g.M + FR_TILE - 1) / FR_TILE), (unsigned)((g.N + FR_TILE - 1) / FR_TILE),
+                    (unsigned)(g.batch < 65535 ? g.batch : 65535));
+    hipLaunchKernelGGL((fr_gemm_kernel<TA, TB, TC>), grid, dim3(256), 0, st, C, A, B, g);
+    INR_LAUNCH_CHECK();
+    return 0;
+}
+
+// the last axis of [rows][n] -> [rows][m]: every line times op^T
+template <typename TI, typename TO>
+int fr_apply_last(TO* out, const TI* in, const double* op, long long rows, int n, int m, hipStream_t st) {
+    return fr_gemm(out, in, op, FrGemm{rows, m, n, 1, 0, n, 0, 1, n, 0, m}, st);
+}
+
+// the second-last axis of [nimg][n][width] -> [nimg][m][width]: op times every image
+template <typename TI, typename TO>
+int fr_apply_rows(TO* out, const TI* in, const double* op, int nimg, int n, int m, int width, hipStream_t st) {
+    return fr_gemm(out, op, in, FrGemm{m, width, n, nimg, 0, n, (long long)n * width, width, 1, (long long)m * width, width}, st);
+}
+
+// passes: a 1 -> 1 axis is passed through (fr_identity) and needs no mirrored line
+int fr_axis_check(const char* who, int n, int m, int align, int boundary, bool passes) {
+    INR_REQUIRE(n >= 1 && m >= 1, INR_E_INVALID, "%s: bad sizes (a line of %d samples to %d)", who, n, m);
+    INR_REQUIRE(n <= FOURIER_MAX_LINE && m <= FOURIER_MAX_LINE, INR_E_INVALID, "%s: lines of at most %d samples (got %d -> %d)", who,
+                FOURIER_MAX_LINE, n, m);
+    if (boundary == INR_FOURIER_MIRROR && align == INR_FOURIER_SAMPLE && !(passes && n == 1 && m == 1))
+        INR_REQUIRE(n >= 2 && ((long long)(2 * n - 2) * m) % n == 0, INR_E_INVALID,
+                    "%s: the mirror boundary with align 'sample' needs n >= 2 and (2n - 2) m divisible by n (got %d -> %d)", who, n, m);
+    return 0;
+}
+
+int fr_mode_check(const char* who, int align, int boundary, double apodize) {
+    INR_REQUIRE(align == INR_FOURIER_SAMPLE || align == INR_FOURIER_CENTER, INR_E_INVALID,
+                "%s: align must be INR_FOURIER_SAMPLE or INR_FOURIER_CENTER (got %d)", who, align);
+    INR_REQUIRE(boundary == INR_FOURIER_PERIODIC || boundary == INR_FOURIER_MIRROR, INR_E_INVALID,
+                "%s: boundary must be INR_FOURIER_PERIODIC or INR_FOURIER_MIRROR (got %d)", who, boundary);
+    INR_REQUIRE(apodize >= 0.0 && apodize <= 1.0, INR_E_INVALID, "%s: apodize must be in [0, 1] (got %g)", who, apodize);
+    return 0;
+}
+
+template <typename T>
+int fr_resample2d(T* out, const T* in, int nimg, int H, int W, int OH, int OW, int align, int boundary, double apodize,
+                  const FourierView& v, hipStream_t st) {
+    if (nimg == 0) return 0;
+    ProfScope ps(KC_OTHER, st);
+    const bool cols = !fr_identity(W, OW, align, apodize), rows = !fr_identity(H, OH, align, apodize);
+    if (cols)
+        if (int rc = launch_fourier_operator(v.op_cols, W, OW, align, boundary, apodize, st)) return rc;
+    if (rows)
+        if (int rc = launch_fourier_operator(v.op_rows, H, OH, align, boundary, apodize, st)) return rc;
+    const long long lines = (long long)nimg * H;
+    if (cols && rows) {
+        if (int rc = fr_apply_last(v.mid, in, v.op_cols, lines, W, OW, st)) return rc;
+        return fr_apply_rows(out, (const double*)v.mid, v.op_rows, nimg, H, OH, OW, st);
+    }
+    if (cols) return fr_apply_last(out, in, v.op_cols, lines, W, OW, st);
+    if (rows) return fr_apply_rows(out, in, v.op_rows, nimg, H, OH, OW, st);
+    INR_HIP(hipMemcpyAsync(out, in, (size_t)lines * W * sizeof(T), hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+}  // namespace
+
+// the workspace: the two operators and the plane between the two passes.  base == null: `total` only
+FourierView fourier_view(int nimg, int H, int W, int OH, int OW, void* base) {
+    FourierView v;
+    WsCarver c(base, 256);
+    v.op_rows = c.take<double>((size_t)OH * (size_t)H);
+    v.op_cols = c.take<double>((size_t)OW * (size_t)W);
+    v.mid = c.take<double>((size_t)(nimg > 0 ? nimg : 1) * (size_t)H * (size_t)OW);
+    v.total = c.bytes();
+    return v;
+}
+
+int fourier_sizes_check(const char* who, int nimg, int H, int W, int OH, int OW) {
+    INR_REQUIRE(nimg >= 0, INR_E_INVALID, "%s: bad sizes (n_images = %d)", who, nimg);
+    if (int rc = fr_axis_check(who, H, OH, INR_FOURIER_CENTER, INR_FOURIER_PERIODIC, true)) return rc;
+    if (int rc = fr_axis_check(who, W, OW, INR_FOURIER_CENTER, INR_FOURIER_PERIODIC, true)) return rc;
+    // the row tiles of one launch are a grid's x extent
+    INR_REQUIRE((long long)nimg * (H > OH ? H : OH) < (1ll << 36), INR_E_INVALID, "%s: batch too large (%d images of %d rows)", who, nimg,
+                H > OH ? H : OH);
+    return 0;
+}
+
+int fourier_operator_check(const char* who, int n, int m, int align, int boundary, double apodize) {
+    if (int rc = fr_mode_check(who, align, boundary, apodize)) return rc;
+    return fr_axis_check(who, n, m, align, boundary, false);
+}
+
+int fourier_check(const char* who, int nimg, int H, int W, int OH, int OW, int align, int boundary, double apodize) {
+    if (int rc = fr_mode_check(who, align, boundary, apodize)) return rc;
+    if (int rc = fourier_sizes_check(who, nimg, H, W, OH, OW)) return rc;
+    if (int rc = fr_axis_check(who, H, OH, align, boundary, true)) return rc;
+    return fr_axis_check(who, W, OW, align, boundary, true);
+}
+
+// validated by fourier_operator_check
+int launch_fourier_operator(double* op, int n, int m, int align, int boundary, double apodize, hipStream_t st) {
+    const long long total = (long long)m * n;
+    hipLaunchKernelGGL(fr_operator_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, op, fr_axis(n, m, align, boundary, apodize));
+    INR_LAUNCH_CHECK();
+    return 0;
+}
+
+// everything validated (fourier_check) and the workspace checked by the caller
+int launch_fourier_resample2d(double* out, const double* in, int nimg, int H, int W, int OH, int OW, int align, int boundary,
+                              double apodize, const FourierView& v, hipStream_t st) {
+    return fr_resample2d(out, in, nimg, H, W, OH, OW, align, boundary, apodize, v, st);
+}
+
+int launch_fourier_resample2d(float* out, const float* in, int nimg, int H, int W, int OH, int OW, int align, int boundary,
+                              double apodize, const FourierView& v, hipStream_t st) {
+    return fr_resample2d(out, in, nimg, H, W, OH, OW, align, boundary, apodize, v, st);
+}
+
+}  // namespace inr

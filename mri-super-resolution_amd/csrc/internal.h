@@ -164,6 +164,19 @@ int rescale_check(const char* who, int nimg, int H, int W, int OH, int OW, int o
 int launch_rescale2d(float* out, const float* in, int nimg, int H, int W, int OH, int OW, int order, int mode, int anti_aliasing,
                      int clip_group, const RescaleView& v, hipStream_t st);
 
+// ---- fourier.hip: Fourier (k-space zero-fill / truncation) re-sampling, one dense operator per axis applied as an fp64 MFMA GEMM -----------
+constexpr int FOURIER_MAX_LINE = INR_FOURIER_MAX_LINE;
+struct FourierView { double *op_rows, *op_cols, *mid; size_t total; };
+FourierView fourier_view(int nimg, int H, int W, int OH, int OW, void* base);
+int fourier_sizes_check(const char* who, int nimg, int H, int W, int OH, int OW);   // what the planner can judge
+int fourier_operator_check(const char* who, int n, int m, int align, int boundary, double apodize);
+int fourier_check(const char* who, int nimg, int H, int W, int OH, int OW, int align, int boundary, double apodize);
+int launch_fourier_operator(double* op, int n, int m, int align, int boundary, double apodize, hipStream_t st);
+int launch_fourier_resample2d(double* out, const double* in, int nimg, int H, int W, int OH, int OW, int align, int boundary,
+                              double apodize, const FourierView& v, hipStream_t st);
+int launch_fourier_resample2d(float* out, const float* in, int nimg, int H, int W, int OH, int OW, int align, int boundary,
+                              double apodize, const FourierView& v, hipStream_t st);
+
 // (register.hip -- masked cross-correlation, image means, the spline shift -- defines public entry points only; the spline prefilter and
 // sampler it shares with rescale.hip are device code, in spline.h.)
 

@@ -10,17 +10,18 @@ from __future__ import annotations
 import os
 
 SSIM_HEADER = 'Pt_id, b-value, slice, SSIM-spline, SSIM-SR\n'
+SSIM_ZEROFILL_HEADER = 'Pt_id, b-value, slice, SSIM-zerofill, SSIM-SR\n'     # superresDWI --zerofill: the same rows, the Fourier baseline
 CONTRAST_HEADER = 'seed,patient,direction,image,metric,performance\n'
 CONTRAST_METRICS = ['C', 'CNR', 'CNR2']
 DAVID_HEADER = 'patient,image,direction,acquisition,metric,performance\n'
 
 
 class SsimCsv:
-    def __init__(self, path):
+    def __init__(self, path, header=SSIM_HEADER):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         self.path = path
         self._fh = open(path, mode='w')
-        self._fh.write(SSIM_HEADER)
+        self._fh.write(header)
 
     def row(self, pt_id, bvalue, _slice, ssim_spline, ssim_sr):
         self._fh.write(f'{pt_id}, {bvalue}, {_slice}, {ssim_spline}, {ssim_sr}\n')

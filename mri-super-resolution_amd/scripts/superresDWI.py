@@ -27,6 +27,12 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     ``laplace``, evaluated in forward mode by ``inr.derivatives``) along the in-plane and through-plane axes -- not along the
     b-value axis.  ``grad_mag = sqrt(sum_i (dy/dx_i)^2)``, ``laplacian = sum_i d^2y/dx_i^2``, of the un-clamped network, in the
     normalised [-1, 1] coordinates of ``get_mgrid`` (times ``2 / (n_i - 1)`` per axis and order for per-voxel units).
+  * ``--zerofill [--zerofill_apodize A]``: the interpolation an MR scanner applies, next to the spline:
+    ``baselines.fourier_resize(HR[::2, ::2], HR.shape, 'sample', 'mirror', A)`` clamped at 0 -- k-space zero-filling on the grid of the
+    decimation (LR sample j sits on HR sample 2j; ``rescale`` places pixel centres, half an LR pixel off), with the mirrored boundary
+    a cropped ROI needs.  ``ssim_scores_zerofill.csv`` holds the rows of ``ssim_scores.csv`` under the same protocol with the header
+    ``Pt_id, b-value, slice, SSIM-zerofill, SSIM-SR``; ``metrics.json`` gains ``psnr_zerofill_db`` and ``ssim_zerofill_mean``; with
+    ``--adc``, ``adc.mat`` gains ``adc_zerofill`` on the grid of ``adc_spline`` (x4 of the LR ROI).  Needs an even ROI side.
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
@@ -78,6 +84,11 @@ def build_parser():
                         "217-241, where T = 100 is hard-coded); default 0 = off")
     p.add_argument("--adc", action="store_true",
                    help="also write adc.mat: ADC maps of SR, spline and HR (superresDWI.py:189-206); needs >= 2 b-values")
+    p.add_argument("--zerofill", action="store_true",
+                   help="also score the k-space zero-fill baseline (Fourier re-sampling of every second HR pixel, mirrored boundary): "
+                        "ssim_scores_zerofill.csv, psnr_zerofill_db / ssim_zerofill_mean in metrics.json, adc_zerofill with --adc")
+    p.add_argument("--zerofill_apodize", type=float, default=0.0,
+                   help="--zerofill: Tukey window over the kept band, 0 (none, the default) .. 1 (Hann)")
     p.add_argument("--derivative_maps", action="store_true",
                    help="also write derivatives.mat: gradient magnitude and Laplacian of the fitted network on recon's grid, "
                         "along the spatial axes (nn_mri.py:205-221)")
@@ -199,6 +210,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     safe = lambda t: torch.where(ok[..., None, None], t, torch.ones_like(t)).clamp_min(1e-30)   # empty slices: finite, ignored
     ssim_spline = metrics.ssim_reference_protocol(safe(hs), safe(sp)).cpu().numpy()
     ssim_sr = metrics.ssim_reference_protocol(safe(hs), safe(ss)).cpu().numpy()
+    zf = _zerofill(hs, 2, args.zerofill_apodize) if getattr(args, "zerofill", False) else None
     with reports.SsimCsv(os.path.join(out_dir, "ssim_scores.csv")) as csv:
         for _slice in range(nz):
             for b in range(nb):
@@ -214,13 +226,22 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         "psnr_spline_db": float(metrics.psnr(hs, sp, 1.0)),
         "ssim_sr_mean": float(ssim_sr[okn].mean()), "ssim_spline_mean": float(ssim_spline[okn].mean()),
     }
+    if zf is not None:
+        ssim_zf = metrics.ssim_reference_protocol(safe(hs), safe(zf)).cpu().numpy()
+        with reports.SsimCsv(os.path.join(out_dir, "ssim_scores_zerofill.csv"), reports.SSIM_ZEROFILL_HEADER) as csv:
+            for _slice in range(nz):
+                for b in range(nb):
+                    csv.row(pt_id, bvalues[b] if b < len(bvalues) else b, _slice, float(ssim_zf[_slice, b]), float(ssim_sr[_slice, b]))
+        summary["psnr_zerofill_db"] = float(metrics.psnr(hs, zf, 1.0))
+        summary["ssim_zerofill_mean"] = float(ssim_zf[okn].mean())
     summary.update(fit_summary)
     if args.transverse_length:
         coronal, summary["t_coronal_s"] = _coronal(INR, B, mean_img, test_shape, args, reconstruct)
         matio.savemat(os.path.join(out_dir, "coronal.mat"), coronal)
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
-        matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale))
+        matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale,
+                                                                     args.zerofill_apodize if zf is not None else None))
     if args.derivative_maps:
         matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape))
     if args.wire_derivative_maps:
@@ -275,6 +296,12 @@ def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
     if args.transverse_length and nz < 4:
         raise ValueError(f"--transverse_length: the through-plane cubic spline needs at least 4 slices (scipy interp1d "
                          f"kind='cubic'); {path} has {nz}")
+    if getattr(args, "zerofill", False):
+        if not 0.0 <= args.zerofill_apodize <= 1.0:
+            raise ValueError(f"--zerofill_apodize must be in [0, 1] (got {args.zerofill_apodize})")
+        if (args.roi_end - args.roi_start) % 2:
+            raise ValueError(f"--zerofill re-samples every second pixel of the ROI back onto its grid with a mirrored boundary, which "
+                             f"needs an even ROI side (got {args.roi_end - args.roi_start})")
     if args.adc:
         if nb < 2:
             raise ValueError(f"--adc needs at least 2 b-values; {path} has {nb}")
@@ -300,14 +327,24 @@ def _coronal(INR, B, mean_img, test_shape, args, reconstruct=inr.reconstruct):
     return {"coronal_sr": sr.cpu().numpy(), "coronal_spline": spline.cpu().numpy(), "transverse_length": T}, t
 
 
-def _adc_maps(recon, hs, bvalues, signal_scale):
+def _zerofill(hs, factor, apodize):
+    """Every second pixel of the [.., R, R] stack ``hs`` re-sampled to ``factor`` times its grid by k-space zero-filling, sample 0 on
+    sample 0, mirrored boundary, clamped at 0 (a magnitude image)."""
+    lr = hs[..., ::2, ::2].contiguous()
+    return baselines.fourier_resize(lr, (factor * lr.shape[-2], factor * lr.shape[-1]), 'sample', 'mirror', apodize).clamp_min(0)
+
+
+def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None):
     """superresDWI.py:189-206 for all slices in one batch: every b-image times maxes[b, 1], then calculate_ADC per pixel, of
-    the x2 SR volume, the x4 spline of the LR ROI and the x2 spline of the HR ROI.  ``hs`` is the HR ROI as [Z, B, R, R]."""
+    the x2 SR volume, the x4 spline of the LR ROI and the x2 spline of the HR ROI.  ``hs`` is the HR ROI as [Z, B, R, R].
+    ``zerofill_apodize`` (not None): also ``adc_zerofill``, the x4 zero-fill of the LR ROI, on the grid of ``adc_spline``."""
     scale = torch.as_tensor(np.asarray(signal_scale, np.float32), device=recon.device)
     to_xyzb = lambda t: t.permute(2, 3, 0, 1).contiguous()                       # [Z, B, 2R, 2R] -> [2R, 2R, Z, B]
     stacks = {"adc_sr": recon,
               "adc_spline": to_xyzb(baselines.rescale(hs[:, :, ::2, ::2].contiguous(), 4)),
               "adc_hr": to_xyzb(baselines.rescale(hs, 2))}
+    if zerofill_apodize is not None:
+        stacks["adc_zerofill"] = to_xyzb(_zerofill(hs, 4, zerofill_apodize))
     out = {k: metrics.calculate_ADC_device(bvalues, (v * scale).contiguous()).cpu().numpy() for k, v in stacks.items()}
     out["b"] = np.asarray(bvalues, np.float64)
     return out
