@@ -1,6 +1,7 @@
-// extern "C" surface of libinrhip.so (see include/inrhip.h) + the fused SIREN fit / forward /
-// reconstruct orchestration.  Nothing here allocates device memory or synchronises (except
-// inr_prof_read and inr_device_caps, which are not on the hot path).
+// The library's own state (error string, profiler, launch counters, and the table of diagnostic switches, which has to see every
+// unit's) and the SIREN network path: the fused fit / forward / reconstruct orchestration and the layer-wise backward entry points
+// that share its helpers.  Every other family's entry points are at the end of the unit that owns its kernels.  Nothing here
+// allocates device memory or synchronises (except inr_prof_read and inr_device_caps, which are not on the hot path).
 #include <math.h>
 #include <stdarg.h>
 
@@ -71,8 +72,6 @@ static tune_int g_h3_serpentine{1};   // key 5
 static tune_int g_hp{1};  // key 7: pre-split (HL32) GEMM path inside the fused entry points; inr_debug_set(7, 0) falls back to gemm_h3
 
 // ---- shared helpers ---------------------------------------------------------------------------------
-static const int64_t MAX_ROWS = (1ll << 31) - 256;
-
 static int check_desc(const inr_siren_desc_t* d) {
     INR_REQUIRE(d != nullptr, INR_E_INVALID, "siren descriptor is null");
     INR_REQUIRE(d->in_features >= 1 && d->hidden_features >= 1 && d->hidden_layers >= 0 && d->out_features >= 1,
@@ -331,82 +330,7 @@ int inr_device_caps(int device, inr_device_caps_t* out) {
     return 0;
 }
 
-int inr_mgrid(float* out, const int64_t* shape, int dim, int64_t row_begin, int64_t n_rows, void* stream) {
-    INR_REQUIRE(out && shape, INR_E_INVALID, "inr_mgrid: null pointer");
-    INR_REQUIRE(row_begin >= 0 && n_rows >= 0, INR_E_INVALID, "inr_mgrid: negative row range");
-    return launch_mgrid(out, shape, dim, row_begin, n_rows, (hipStream_t)stream);
-}
-
-int inr_fourier_map(float* out, const float* x, const float* B, int64_t n, int d, int m, void* stream) {
-    INR_REQUIRE(out && x && B, INR_E_INVALID, "inr_fourier_map: null pointer");
-    INR_REQUIRE(n >= 0 && d >= 1 && m >= 1, INR_E_INVALID, "inr_fourier_map: bad sizes n=%lld d=%d m=%d",
-                (long long)n, d, m);
-    return launch_fourier(out, x, nullptr, d, 0, n, B, m, (hipStream_t)stream);
-}
-
-int inr_grid_fourier_map(float* out, const int64_t* shape, int dim, int64_t row_begin, int64_t n_rows,
-                         const float* B, int m, void* stream) {
-    INR_REQUIRE(out && shape && B, INR_E_INVALID, "inr_grid_fourier_map: null pointer");
-    INR_REQUIRE(row_begin >= 0 && n_rows >= 0 && m >= 1, INR_E_INVALID, "inr_grid_fourier_map: bad sizes");
-    return launch_fourier(out, nullptr, shape, dim, row_begin, n_rows, B, m, (hipStream_t)stream);
-}
-
-int inr_sine_layer_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n,
-                           int in_features, int out_features, float omega, void* stream) {
-    INR_REQUIRE(act && x && W, INR_E_INVALID, "inr_sine_layer_forward: null pointer");
-    INR_REQUIRE(n >= 0 && n <= MAX_ROWS && in_features >= 1 && out_features >= 1, INR_E_INVALID,
-                "inr_sine_layer_forward: bad sizes n=%lld in=%d out=%d", (long long)n, in_features, out_features);
-    if (n == 0) return 0;
-    return gemm_sine_forward(act, dact, x, W, b, n, in_features, out_features, omega, (hipStream_t)stream);
-}
-
-int inr_tanh_layer_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n,
-                           int in_features, int out_features, float scale, void* stream) {
-    INR_REQUIRE(act && x && W, INR_E_INVALID, "inr_tanh_layer_forward: null pointer");
-    INR_REQUIRE(n >= 0 && n <= MAX_ROWS && in_features >= 1 && out_features >= 1, INR_E_INVALID,
-                "inr_tanh_layer_forward: bad sizes");
-    if (n == 0) return 0;
-    return gemm_tanh_forward(act, dact, x, W, b, n, in_features, out_features, scale, (hipStream_t)stream);
-}
-
-int inr_linear_tanh_head_forward(float* y, float* dy, const float* a, const float* W, const float* b, int64_t n,
-                                 int in_features, int out_features, float scale, void* stream) {
-    INR_REQUIRE(y && a && W, INR_E_INVALID, "inr_linear_tanh_head_forward: null pointer");
-    INR_REQUIRE(n >= 0 && in_features >= 1 && out_features >= 1, INR_E_INVALID, "inr_linear_tanh_head_forward: bad sizes");
-    return launch_head_forward(y, a, W, b, n, in_features, out_features, 2, scale, (hipStream_t)stream, dy);
-}
-
-int inr_acquisition_products(float* out, const float* raw_b0, const float* raw_b1, const float* raw_b2, const float* raw_b3,
-                             int64_t n_voxels, int n1, int n2, int n3, void* stream) {
-    INR_REQUIRE(out && raw_b0 && raw_b1 && raw_b2 && raw_b3, INR_E_INVALID, "inr_acquisition_products: null pointer");
-    INR_REQUIRE(n_voxels >= 0 && n1 >= 1 && n2 >= 1 && n3 >= 1 && (long long)n1 * n2 * n3 < (1 << 24), INR_E_INVALID,
-                "inr_acquisition_products: bad sizes");
-    return launch_acquisition_products(out, raw_b0, raw_b1, raw_b2, raw_b3, n_voxels, n1, n2, n3, (hipStream_t)stream);
-}
-
-int inr_mul(float* out, const float* a, const float* b, int64_t count, void* stream) {
-    INR_REQUIRE(out && a && b && count >= 0, INR_E_INVALID, "inr_mul: bad arguments");
-    return launch_mul(out, a, b, count, (hipStream_t)stream);
-}
-
-int inr_linear_head_forward(float* y, const float* a, const float* W, const float* b, int64_t n, int in_features,
-                            int out_features, int use_clamp, float clamp_min, void* stream) {
-    INR_REQUIRE(y && a && W, INR_E_INVALID, "inr_linear_head_forward: null pointer");
-    INR_REQUIRE(n >= 0 && in_features >= 1 && out_features >= 1, INR_E_INVALID, "inr_linear_head_forward: bad sizes");
-    return launch_head_forward(y, a, W, b, n, in_features, out_features, use_clamp, clamp_min, (hipStream_t)stream);
-}
-
-size_t inr_mse_workspace_bytes(int64_t count) { return (size_t)mse_blocks(count > 0 ? count : 1) * sizeof(float); }
-
-int inr_mse_loss_grad(float* gy, float* loss, const float* y, const float* t, const float* w, int64_t count,
-                      void* workspace, size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(gy && loss && y && t, INR_E_INVALID, "inr_mse_loss_grad: null pointer");
-    INR_REQUIRE(count >= 1, INR_E_INVALID, "inr_mse_loss_grad: count must be >= 1");
-    INR_REQUIRE(workspace && workspace_bytes >= inr_mse_workspace_bytes(count), INR_E_WORKSPACE,
-                "inr_mse_loss_grad: workspace too small");
-    return launch_mse(gy, loss, y, t, w, count, (float*)workspace, (hipStream_t)stream);
-}
-
+// ---- layer-wise backward: head_backward, input_grad and param_grad above, which the fused fit shares ---------------------
 size_t inr_head_backward_workspace_bytes(int64_t n, int hidden, int out_features) {
     return head_backward_ws_floats(n > 0 ? n : 1, hidden, out_features) * sizeof(float);
 }
@@ -453,13 +377,6 @@ int inr_linear_param_grad(float* gW, float* gb, const float* dz, const float* x,
     INR_REQUIRE(workspace && workspace_bytes >= inr_linear_param_grad_workspace_bytes(n, in_features, out_features),
                 INR_E_WORKSPACE, "inr_linear_param_grad: workspace too small");
     return param_grad(gW, gb, dz, x, n, in_features, out_features, (float*)workspace, (hipStream_t)stream);
-}
-
-int inr_adam_step(float* p, const float* g, float* m, float* v, int64_t count, int64_t step, double lr,
-                  double beta1, double beta2, double eps, void* stream) {
-    INR_REQUIRE(p && g && m && v, INR_E_INVALID, "inr_adam_step: null pointer");
-    INR_REQUIRE(count >= 0 && step >= 1, INR_E_INVALID, "inr_adam_step: count >= 0 and step >= 1 required");
-    return launch_adam(p, g, m, v, count, step, lr, beta1, beta2, eps, (hipStream_t)stream);
 }
 
 // ---- fused SIREN -------------------------------------------------------------------------------------
@@ -1291,384 +1208,6 @@ int inr_siren_backward_train(const inr_siren_desc_t* desc, const float* params, 
     return launch_finalize(fin, 0, 0.0, 0.0, 0.0, 0.0, st);
 }
 
-// ---- metrics ---------------------------------------------------------------------------------------------
-size_t inr_metric_workspace_bytes(int n_images) {
-    return (size_t)metric_workspace_doubles(n_images > 0 ? n_images : 1) * sizeof(double);
-}
-
-int inr_psnr(double* out, const float* x, const float* y, int n_images, int64_t per_image, double data_range,
-             void* workspace, size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(out && x && y, INR_E_INVALID, "inr_psnr: null pointer");
-    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && per_image >= 1 && data_range > 0, INR_E_INVALID,
-                "inr_psnr: bad sizes");
-    INR_REQUIRE(workspace && workspace_bytes >= inr_metric_workspace_bytes(n_images), INR_E_WORKSPACE,
-                "inr_psnr: workspace too small");
-    return launch_psnr(out, x, y, n_images, per_image, data_range, (double*)workspace, (hipStream_t)stream);
-}
-
-int inr_ssim2d(double* out, const float* x, const float* y, int n_images, int height, int width, int win,
-               double data_range, int use_mask, float mask_thr, void* workspace, size_t workspace_bytes,
-               void* stream) {
-    INR_REQUIRE(out && x && y, INR_E_INVALID, "inr_ssim2d: null pointer");
-    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && win >= 3 && (win & 1) && height >= win && width >= win &&
-                    data_range > 0,
-                INR_E_INVALID, "inr_ssim2d: need odd win >= 3 and images at least win x win (got %dx%d, win %d)",
-                height, width, win);
-    INR_REQUIRE(workspace && workspace_bytes >= inr_metric_workspace_bytes(n_images), INR_E_WORKSPACE,
-                "inr_ssim2d: workspace too small");
-    return launch_ssim(out, x, y, n_images, height, width, win, data_range, use_mask, mask_thr, (double*)workspace,
-                       (hipStream_t)stream);
-}
-
-int inr_hybrid_fit(double* params, int* status, int* nfev, double* cost, const double* signals, int64_t n_voxels,
-                   void* stream) {
-    if (n_voxels == 0) return 0;
-    INR_REQUIRE(params && status && nfev && cost && signals, INR_E_INVALID, "inr_hybrid_fit: null pointer");
-    // (one 8-lane group per voxel, grid dimension is 32-bit: 2^31 - 1 blocks of 8 voxels)
-    INR_REQUIRE(n_voxels > 0 && n_voxels <= ((int64_t)1 << 33), INR_E_INVALID, "inr_hybrid_fit: bad voxel count %lld",
-                (long long)n_voxels);
-    return launch_hybrid_fit(params, status, nfev, cost, signals, n_voxels, (hipStream_t)stream);
-}
-
-size_t inr_rams_shift_loss_workspace_bytes(int n_images, int border) {
-    const int ns = 2 * (border > 0 ? border : 0) + 1;
-    return (size_t)(n_images > 0 ? n_images : 1) * ns * ns * sizeof(double);
-}
-
-int inr_rams_shift_loss(double* out, const float* y_true, const float* y_pred, const float* mask, int n_images, int size,
-                        int border, int mode, void* workspace, size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(out && y_true && y_pred && mask, INR_E_INVALID, "inr_rams_shift_loss: null pointer");
-    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && border >= 0 && border <= 16 && size > 2 * border &&
-                    (mode == 0 || mode == 1),
-                INR_E_INVALID, "inr_rams_shift_loss: bad arguments (size=%d border=%d mode=%d)", size, border, mode);
-    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_shift_loss_workspace_bytes(n_images, border), INR_E_WORKSPACE,
-                "inr_rams_shift_loss: workspace too small");
-    return launch_shift_loss(out, y_true, y_pred, mask, n_images, size, border, mode, (double*)workspace,
-                             (hipStream_t)stream);
-}
-
-static int conv3d_dims_ok(int B, int D1, int D2, int D3, int pad) {
-    INR_REQUIRE(B >= 1 && B <= 65535 && D1 >= 1 && D2 >= 1 && D3 >= 1 && (pad == 0 || pad == 1), INR_E_INVALID,
-                "conv3d: bad shape (B=%d D=%dx%dx%d pad=%d)", B, D1, D2, D3, pad);
-    INR_REQUIRE(D1 + 2 * pad > 2 && D2 + 2 * pad > 2 && D3 + 2 * pad > 2, INR_E_INVALID, "conv3d: volume smaller than the kernel");
-    INR_REQUIRE((long long)B * D1 * D2 * D3 * 32 * 4 < (1ll << 40), INR_E_INVALID, "conv3d: volume too large");
-    // the kernels address one image through a 32-bit buffer window
-    INR_REQUIRE((long long)D1 * D2 * D3 * 32 * 4 < (1ll << 31), INR_E_INVALID, "conv3d: one image must stay below 2 GiB");
-    return 0;
-}
-
-int inr_rams_conv3d_forward(float* y, const float* x, const float* w, const float* bias, int B, int D1, int D2, int D3, int pad,
-                            int relu, void* stream) {
-    INR_REQUIRE(y && x && w && bias, INR_E_INVALID, "inr_rams_conv3d_forward: null pointer");
-    if (int rc = conv3d_dims_ok(B, D1, D2, D3, pad)) return rc;
-    INR_REQUIRE(aligned16(x) && aligned16(w), INR_E_ALIGN, "inr_rams_conv3d_forward: x / w must be 16-byte aligned");
-    return rams_conv3d_forward(y, x, w, bias, B, D1, D2, D3, pad, relu, (hipStream_t)stream);
-}
-
-size_t inr_rams_conv3d_dgrad_workspace_bytes(void) { return (27 * 32 * 32 + 64) * sizeof(float); }
-
-int inr_rams_conv3d_dgrad(float* dx, const float* dy, const float* w, int B, int D1, int D2, int D3, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(dx && dy && w, INR_E_INVALID, "inr_rams_conv3d_dgrad: null pointer");
-    if (int rc = conv3d_dims_ok(B, D1, D2, D3, 1)) return rc;
-    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_conv3d_dgrad_workspace_bytes(), INR_E_WORKSPACE,
-                "inr_rams_conv3d_dgrad: workspace too small");
-    INR_REQUIRE(aligned16(dy) && aligned16(workspace), INR_E_ALIGN, "inr_rams_conv3d_dgrad: dy / workspace must be 16-byte aligned");
-    return rams_conv3d_dgrad_same(dx, dy, w, B, D1, D2, D3, (float*)workspace, (hipStream_t)stream);
-}
-
-size_t inr_rams_conv3d_wgrad_workspace_bytes(int B, int D1, int D2, int D3, int pad) {
-    const long long nvox = (long long)B * (D1 + 2 * pad - 2) * (D2 + 2 * pad - 2) * (D3 + 2 * pad - 2);
-    return rams_conv3d_wgrad_ws_floats(nvox > 0 ? nvox : 1) * sizeof(float);
-}
-
-int inr_rams_conv3d_wgrad(float* gw, float* gb, const float* x, const float* dy, int B, int D1, int D2, int D3, int pad,
-                          void* workspace, size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(gw && x && dy, INR_E_INVALID, "inr_rams_conv3d_wgrad: null pointer");
-    if (int rc = conv3d_dims_ok(B, D1, D2, D3, pad)) return rc;
-    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_conv3d_wgrad_workspace_bytes(B, D1, D2, D3, pad), INR_E_WORKSPACE,
-                "inr_rams_conv3d_wgrad: workspace too small");
-    INR_REQUIRE(aligned16(x) && aligned16(dy), INR_E_ALIGN, "inr_rams_conv3d_wgrad: x / dy must be 16-byte aligned");
-    return rams_conv3d_wgrad_auto(gw, gb, x, dy, B, D1, D2, D3, pad, (float*)workspace, (hipStream_t)stream);
-}
-
-size_t inr_rams_shift_loss_grad_workspace_bytes(int n_images, int border) {
-    return inr_rams_shift_loss_workspace_bytes(n_images, border) + (size_t)(n_images > 0 ? n_images : 1) * sizeof(int) + 8;
-}
-
-int inr_rams_shift_loss_grad(double* loss, float* grad_pred, const float* y_true, const float* y_pred, const float* mask,
-                             const float* upstream, int n_images, int size, int border, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(loss && grad_pred && y_true && y_pred && mask, INR_E_INVALID, "inr_rams_shift_loss_grad: null pointer");
-    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && border >= 0 && border <= 16 && size > 2 * border, INR_E_INVALID,
-                "inr_rams_shift_loss_grad: bad arguments (size=%d border=%d)", size, border);
-    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_shift_loss_grad_workspace_bytes(n_images, border), INR_E_WORKSPACE,
-                "inr_rams_shift_loss_grad: workspace too small");
-    INR_REQUIRE(((uintptr_t)workspace & 7) == 0, INR_E_ALIGN, "inr_rams_shift_loss_grad: workspace must be 8-byte aligned");
-    return launch_shift_loss_grad(loss, grad_pred, y_true, y_pred, mask, upstream, n_images, size, border, (double*)workspace,
-                                  (hipStream_t)stream);
-}
-
-static int shift_ssim_args_ok(const char* who, int n_images, int size, int border) {
-    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && border >= 0 && border <= 16 && size <= 8192 &&
-                    size - 2 * border >= cssim_min_crop(),
-                INR_E_INVALID, "%s: bad arguments (n_images=%d size=%d border=%d; size - 2*border >= %d)", who, n_images, size,
-                border, cssim_min_crop());
-    return 0;
-}
-
-static size_t shift_ssim_bytes(int n_images, int size, int border, bool grad) {
-    if (border < 0 || border > 16 || size > 8192 || size - 2 * border < cssim_min_crop()) return 0;
-    return cssim_workspace_doubles(n_images, size, border, grad) * sizeof(double);
-}
-
-size_t inr_rams_shift_ssim_workspace_bytes(int n_images, int size, int border) {
-    return shift_ssim_bytes(n_images, size, border, false);
-}
-
-int inr_rams_shift_ssim(double* out, const float* y_true, const float* y_pred, const float* mask, int n_images, int size,
-                        int border, int clear_only, void* workspace, size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(out && y_true && y_pred && mask, INR_E_INVALID, "inr_rams_shift_ssim: null pointer");
-    if (int rc = shift_ssim_args_ok("inr_rams_shift_ssim", n_images, size, border)) return rc;
-    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_shift_ssim_workspace_bytes(n_images, size, border), INR_E_WORKSPACE,
-                "inr_rams_shift_ssim: workspace too small");
-    INR_REQUIRE(((uintptr_t)workspace & 7) == 0, INR_E_ALIGN, "inr_rams_shift_ssim: workspace must be 8-byte aligned");
-    return launch_cssim(out, y_true, y_pred, mask, n_images, size, border, clear_only != 0, (double*)workspace,
-                        (hipStream_t)stream);
-}
-
-size_t inr_rams_shift_ssim_grad_workspace_bytes(int n_images, int size, int border) {
-    return shift_ssim_bytes(n_images, size, border, true);
-}
-
-int inr_rams_shift_ssim_grad(double* loss, float* grad_pred, const float* y_true, const float* y_pred, const float* mask,
-                             const float* upstream, int n_images, int size, int border, int clear_only, void* workspace,
-                             size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(loss && grad_pred && y_true && y_pred && mask, INR_E_INVALID, "inr_rams_shift_ssim_grad: null pointer");
-    if (int rc = shift_ssim_args_ok("inr_rams_shift_ssim_grad", n_images, size, border)) return rc;
-    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_shift_ssim_grad_workspace_bytes(n_images, size, border), INR_E_WORKSPACE,
-                "inr_rams_shift_ssim_grad: workspace too small");
-    INR_REQUIRE(((uintptr_t)workspace & 7) == 0, INR_E_ALIGN, "inr_rams_shift_ssim_grad: workspace must be 8-byte aligned");
-    return launch_cssim_grad(loss, grad_pred, y_true, y_pred, mask, upstream, n_images, size, border, clear_only != 0,
-                             (double*)workspace, (hipStream_t)stream);
-}
-
-int inr_adc_map(float* out, const float* data, const float* bvals, int64_t n_pixels, int n_b, void* stream) {
-    INR_REQUIRE(out && data && bvals, INR_E_INVALID, "inr_adc_map: null pointer");
-    INR_REQUIRE(n_pixels >= 0 && n_b >= 2 && n_b <= 32, INR_E_INVALID, "inr_adc_map: need 2 <= n_b <= 32");
-    return launch_adc(out, data, bvals, n_pixels, n_b, (hipStream_t)stream);
-}
-
-int inr_rescale2d_linear(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
-                         void* stream) {
-    INR_REQUIRE(out && in, INR_E_INVALID, "inr_rescale2d_linear: null pointer");
-    INR_REQUIRE(n_images >= 0 && height >= 1 && width >= 1 && out_height >= 1 && out_width >= 1, INR_E_INVALID,
-                "inr_rescale2d_linear: bad sizes");
-    INR_REQUIRE((long long)height * width < (1ll << 31) && (long long)out_height * out_width < (1ll << 31), INR_E_INVALID,
-                "inr_rescale2d_linear: image too large");
-    return launch_rescale_linear(out, in, n_images, height, width, out_height, out_width, (hipStream_t)stream);
-}
-
-int64_t inr_rescale2d_workspace_doubles(int n_images, int height, int width, int order, int mode) {
-    if (rescale_check("inr_rescale2d_workspace_doubles", n_images, height, width, 1, 1, order, mode, 0, 0)) return 0;
-    return (int64_t)(rescale_view(n_images, height, width, order, mode, nullptr).total / sizeof(double));
-}
-
-int inr_rescale2d(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width, int order,
-                  int mode, int anti_aliasing, int clip_group, double* workspace, int64_t workspace_doubles, void* stream) {
-    INR_REQUIRE(out && in, INR_E_INVALID, "inr_rescale2d: null pointer");
-    if (int rc = rescale_check("inr_rescale2d", n_images, height, width, out_height, out_width, order, mode, anti_aliasing, clip_group))
-        return rc;
-    const RescaleView v = rescale_view(n_images, height, width, order, mode, workspace);
-    INR_REQUIRE(workspace && workspace_doubles >= 0 && (size_t)workspace_doubles * sizeof(double) >= v.total, INR_E_WORKSPACE,
-                "inr_rescale2d: workspace too small (%lld doubles, %zu needed)", workspace ? (long long)workspace_doubles : 0ll,
-                v.total / sizeof(double));
-    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "inr_rescale2d: workspace must be 16-byte aligned");
-    return launch_rescale2d(out, in, n_images, height, width, out_height, out_width, order, mode, anti_aliasing, clip_group, v,
-                            (hipStream_t)stream);
-}
-
-size_t inr_resize_z_cubic_workspace_bytes(int64_t n_lines, int n_in) {
-    return resize_z_workspace_doubles(n_lines > 0 ? n_lines : 1, n_in > 0 ? n_in : 1) * sizeof(double);
-}
-
-int inr_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, void* workspace, size_t workspace_bytes,
-                       void* stream) {
-    INR_REQUIRE(out && in, INR_E_INVALID, "inr_resize_z_cubic: null pointer");
-    INR_REQUIRE(n_lines >= 1 && n_lines < (1ll << 31) && n_in >= 1 && n_out >= 1, INR_E_INVALID,
-                "inr_resize_z_cubic: bad sizes (n_lines=%lld, n_in=%d, n_out=%d)", (long long)n_lines, n_in, n_out);
-    INR_REQUIRE(n_in >= 4, INR_E_INVALID,
-                "inr_resize_z_cubic: a not-a-knot cubic spline needs at least 4 samples per line (got %d)", n_in);
-    INR_REQUIRE(workspace && workspace_bytes >= inr_resize_z_cubic_workspace_bytes(n_lines, n_in), INR_E_WORKSPACE,
-                "inr_resize_z_cubic: workspace too small");
-    return launch_resize_z_cubic(out, in, n_lines, n_in, n_out, (double*)workspace, (hipStream_t)stream);
-}
-
-// ---- Fourier re-sampling (fourier.hip) ---------------------------------------------------------------------------------------------------
-int inr_fourier_operator(double* op, int n, int m, int align, int boundary, double apodize, void* stream) {
-    INR_REQUIRE(op, INR_E_INVALID, "inr_fourier_operator: null pointer");
-    if (int rc = fourier_operator_check("inr_fourier_operator", n, m, align, boundary, apodize)) return rc;
-    return launch_fourier_operator(op, n, m, align, boundary, apodize, (hipStream_t)stream);
-}
-
-int64_t inr_fourier_resample_workspace_doubles(int n_images, int height, int width, int out_height, int out_width) {
-    if (fourier_sizes_check("inr_fourier_resample_workspace_doubles", n_images, height, width, out_height, out_width)) return 0;
-    return (int64_t)(fourier_view(n_images, height, width, out_height, out_width, nullptr).total / sizeof(double));
-}
-
-// the arguments and the workspace of one re-sampling call, before any device work
-static int fourier_call_check(const char* who, const void* out, const void* in, int n_images, int height, int width, int out_height,
-                              int out_width, int align, int boundary, double apodize, const double* workspace, int64_t workspace_doubles) {
-    INR_REQUIRE(out && in, INR_E_INVALID, "%s: null pointer", who);
-    if (int rc = fourier_check(who, n_images, height, width, out_height, out_width, align, boundary, apodize)) return rc;
-    const size_t need = fourier_view(n_images, height, width, out_height, out_width, nullptr).total;
-    INR_REQUIRE(workspace && workspace_doubles >= 0 && (size_t)workspace_doubles * sizeof(double) >= need, INR_E_WORKSPACE,
-                "%s: workspace too small (%lld doubles, %zu needed)", who, workspace ? (long long)workspace_doubles : 0ll,
-                need / sizeof(double));
-    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
-    return 0;
-}
-
-int inr_fourier_resample2d(double* out, const double* in, int n_images, int height, int width, int out_height, int out_width, int align,
-                           int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream) {
-    if (int rc = fourier_call_check("inr_fourier_resample2d", out, in, n_images, height, width, out_height, out_width, align, boundary,
-                                    apodize, workspace, workspace_doubles))
-        return rc;
-    return launch_fourier_resample2d(out, in, n_images, height, width, out_height, out_width, align, boundary, apodize,
-                                     fourier_view(n_images, height, width, out_height, out_width, workspace), (hipStream_t)stream);
-}
-
-int inr_fourier_resample2d_f32(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
-                               int align, int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream) {
-    if (int rc = fourier_call_check("inr_fourier_resample2d_f32", out, in, n_images, height, width, out_height, out_width, align, boundary,
-                                    apodize, workspace, workspace_doubles))
-        return rc;
-    return launch_fourier_resample2d(out, in, n_images, height, width, out_height, out_width, align, boundary, apodize,
-                                     fourier_view(n_images, height, width, out_height, out_width, workspace), (hipStream_t)stream);
-}
-
-// ---- the reader study's scores (perceptual.hip) ------------------------------------------------------------------------------------------
-int64_t inr_perceptual_workspace_doubles(int n_images, int height, int width, int n_scales) {
-    if (perceptual_check("inr_perceptual_workspace_doubles", n_images, height, width, 1.5, 1.0, n_scales)) return 0;
-    return (int64_t)(perceptual_view(n_images, height, width, n_scales, nullptr).total / sizeof(double));
-}
-
-// the workspace of one call: present, long enough for `need`, aligned
-static int perceptual_ws_check(const char* who, const double* workspace, int64_t workspace_doubles, size_t need) {
-    INR_REQUIRE(workspace && workspace_doubles >= 0 && (size_t)workspace_doubles * sizeof(double) >= need, INR_E_WORKSPACE,
-                "%s: workspace too small (%lld doubles, %zu needed)", who, workspace ? (long long)workspace_doubles : 0ll,
-                need / sizeof(double));
-    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
-    return 0;
-}
-
-int inr_ssim2d_gauss(double* ssim, double* mean_cs, float* map, const float* x, const float* y, int n_images, int height, int width,
-                     double sigma, double data_range, double* workspace, int64_t workspace_doubles, void* stream) {
-    INR_REQUIRE(ssim && x && y, INR_E_INVALID, "inr_ssim2d_gauss: null pointer");
-    if (int rc = perceptual_check("inr_ssim2d_gauss", n_images, height, width, sigma, data_range, 1)) return rc;
-    const PerceptualView v = perceptual_view(n_images, height, width, 1, workspace);
-    if (int rc = perceptual_ws_check("inr_ssim2d_gauss", workspace, workspace_doubles, v.total)) return rc;
-    INR_REQUIRE(aligned16(ssim) && aligned16(mean_cs) && aligned16(map) && aligned16(x) && aligned16(y), INR_E_ALIGN,
-                "inr_ssim2d_gauss: pointers must be 16-byte aligned");
-    return launch_ssim_gauss(ssim, mean_cs, map, x, y, n_images, height, width, sigma, data_range, v, (hipStream_t)stream);
-}
-
-int inr_msssim2d(double* out, double* per_scale, const float* x, const float* y, int n_images, int height, int width,
-                 const double* weights, int n_scales, double sigma, double data_range, double* workspace, int64_t workspace_doubles,
-                 void* stream) {
-    INR_REQUIRE(out && x && y && weights, INR_E_INVALID, "inr_msssim2d: null pointer");
-    if (int rc = perceptual_check("inr_msssim2d", n_images, height, width, sigma, data_range, n_scales)) return rc;
-    const PerceptualView v = perceptual_view(n_images, height, width, n_scales, workspace);
-    if (int rc = perceptual_ws_check("inr_msssim2d", workspace, workspace_doubles, v.total)) return rc;
-    INR_REQUIRE(aligned16(out) && aligned16(per_scale) && aligned16(x) && aligned16(y), INR_E_ALIGN,
-                "inr_msssim2d: pointers must be 16-byte aligned");
-    return launch_msssim(out, per_scale, x, y, n_images, height, width, weights, n_scales, sigma, data_range, v, (hipStream_t)stream);
-}
-
-int inr_filter3x3(float* out, const float* in, int n_images, int height, int width, const double* k9, void* stream) {
-    INR_REQUIRE(out && in && k9, INR_E_INVALID, "inr_filter3x3: null pointer");
-    if (int rc = perceptual_check("inr_filter3x3", n_images, height, width, 1.5, 1.0, 1)) return rc;
-    INR_REQUIRE(aligned16(out) && aligned16(in), INR_E_ALIGN, "inr_filter3x3: pointers must be 16-byte aligned");
-    return launch_filter3x3(out, in, n_images, height, width, k9, (hipStream_t)stream);
-}
-
-static int pair_score(const char* who, double* out, const float* x, const float* y, int n_images, int64_t per_image, int mode,
-                      double* workspace, int64_t workspace_doubles, void* stream) {
-    INR_REQUIRE(out && x && y, INR_E_INVALID, "%s: null pointer", who);
-    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && per_image >= 1, INR_E_INVALID, "%s: bad sizes (n_images=%d, per_image=%lld)", who,
-                n_images, (long long)per_image);
-    const PerceptualView v = perceptual_view(n_images, 1, 1, 1, workspace);
-    if (int rc = perceptual_ws_check(who, workspace, workspace_doubles, v.total)) return rc;
-    INR_REQUIRE(aligned16(out) && aligned16(x) && aligned16(y), INR_E_ALIGN, "%s: pointers must be 16-byte aligned", who);
-    return launch_pair_score(out, x, y, n_images, per_image, mode, v, (hipStream_t)stream);
-}
-
-int inr_image_mse(double* out, const float* x, const float* y, int n_images, int64_t per_image, double* workspace,
-                  int64_t workspace_doubles, void* stream) {
-    return pair_score("inr_image_mse", out, x, y, n_images, per_image, 0, workspace, workspace_doubles, stream);
-}
-
-int inr_hf_gain(double* out, const float* h_sr, const float* h_inter, int n_images, int64_t per_image, double* workspace,
-                int64_t workspace_doubles, void* stream) {
-    return pair_score("inr_hf_gain", out, h_sr, h_inter, n_images, per_image, 1, workspace, workspace_doubles, stream);
-}
-
-int inr_auto_erd(float* accept, const double* values, const float* erd_map, int64_t n_pixels, int n_acquisitions, int rule,
-                 void* stream) {
-    INR_REQUIRE(accept && values, INR_E_INVALID, "inr_auto_erd: null pointer");
-    INR_REQUIRE(n_pixels >= 0 && n_pixels < (1ll << 37), INR_E_INVALID, "inr_auto_erd: bad pixel count");
-    return launch_auto_erd(accept, values, erd_map, n_pixels, n_acquisitions, rule, (hipStream_t)stream);
-}
-
-int inr_auto_erd_volume(double* accept, double* direction_mean, double* accepted_mean, double* direction_adc, double* accepted_adc,
-                   double* adc, const double* values, const double* b0, const double* erd_map, const double* accept_in,
-                   int64_t n_pixels, int n_acquisitions, const int* group_sizes, int n_groups, double b, int rule, void* stream) {
-    INR_REQUIRE(values != nullptr, INR_E_INVALID, "inr_auto_erd_volume: null pointer (values)");
-    INR_REQUIRE(b0 != nullptr || !(direction_adc || accepted_adc || adc), INR_E_INVALID,
-                "inr_auto_erd_volume: null pointer (b0, which the ADC outputs need)");
-    INR_REQUIRE(n_pixels >= 0 && n_pixels < (1ll << 37), INR_E_INVALID, "inr_auto_erd_volume: bad pixel count");
-    if (int rc = erd_volume_check(n_acquisitions, group_sizes, n_groups, b, rule)) return rc;
-    INR_REQUIRE(rule == 0 || accept_in == nullptr, INR_E_INVALID,
-                "inr_auto_erd_volume: accept_in supplies the weights of rule 0; rules 1 and 2 compute them");
-    return launch_erd_volume(accept, direction_mean, accepted_mean, direction_adc, accepted_adc, adc, values, b0, erd_map, accept_in,
-                             n_pixels, n_acquisitions, group_sizes, n_groups, b, rule, (hipStream_t)stream);
-}
-
-// ---- RAMS ------------------------------------------------------------------------------------------------
-static int check_rams(const inr_rams_desc_t* d) {
-    INR_REQUIRE(d != nullptr, INR_E_INVALID, "rams descriptor is null");
-    INR_REQUIRE(d->filters == 32 && d->kernel_size == 3, INR_E_INVALID,
-                "rams kernels need filters == 32 and kernel_size == 3 (got %d, %d)", d->filters, d->kernel_size);
-    INR_REQUIRE(d->scale >= 1 && d->scale * d->scale <= 32 && d->r >= 1 && d->filters / d->r >= 1 &&
-                    d->filters / d->r <= 8 && d->n_rfab >= 0,
-                INR_E_INVALID, "bad rams descriptor (scale=%d r=%d N=%d)", d->scale, d->r, d->n_rfab);
-    INR_REQUIRE(d->channels >= 3 && d->channels <= 32 && d->channels - 2 * (d->channels / 3) == 3, INR_E_INVALID,
-                "rams: channels must leave a temporal depth of 3 before the head (channels=%d)", d->channels);
-    return 0;
-}
-
-int64_t inr_rams_param_count(const inr_rams_desc_t* desc) {
-    if (check_rams(desc)) return INR_E_INVALID;
-    return rams_param_floats(desc);
-}
-
-size_t inr_rams_workspace_bytes(const inr_rams_desc_t* desc, int batch, int height, int width) {
-    if (check_rams(desc) || batch < 1 || height < 3 || width < 3) return 0;
-    return rams_workspace_floats(desc, batch, height, width) * sizeof(float);
-}
-
-int inr_rams_forward(const inr_rams_desc_t* desc, const float* params, const float* x, float* out, int batch, int height,
-                     int width, int clip_round, void* workspace, size_t workspace_bytes, void* stream) {
-    if (int rc = check_rams(desc)) return rc;
-    INR_REQUIRE(params && x && out, INR_E_INVALID, "inr_rams_forward: null pointer");
-    INR_REQUIRE(batch >= 1 && batch <= 65535 && height >= 3 && width >= 3, INR_E_INVALID,
-                "inr_rams_forward: bad sizes (B=%d H=%d W=%d)", batch, height, width);
-    INR_REQUIRE((long long)(height + 4) * (width + 4) * desc->channels * 32 * 4 < (1ll << 31), INR_E_INVALID,
-                "inr_rams_forward: one image's activations must stay below 2 GiB");
-    return rams_forward_impl(desc, params, x, out, batch, height, width, clip_round, workspace, workspace_bytes,
-                             (hipStream_t)stream);
-}
-
 // ---- profiler --------------------------------------------------------------------------------------------
 int inr_prof_enable(int enable) {
     g_prof.enabled = enable != 0;
@@ -1701,54 +1240,6 @@ int inr_prof_read(int kernel_class, int64_t* launches, double* total_ms) {
     *launches = (int64_t)g_prof.spans[kernel_class].size();
     *total_ms = ms;
     return 0;
-}
-
-// ---- a-15 / (f)-4: RAMS training step ------------------------------------------------------------------------------------------
-static int check_rams_train(const inr_rams_desc_t* desc, int B, int H, int W) {
-    INR_REQUIRE(desc != nullptr, INR_E_INVALID, "rams descriptor is null");
-    INR_REQUIRE(desc->filters == 32 && desc->kernel_size == 3 && desc->channels == 9 && desc->scale >= 1 && desc->scale <= 5 &&
-                    desc->r >= 1 && desc->n_rfab >= 0,
-                INR_E_INVALID, "rams train: supported configuration is filters 32, kernel 3, channels 9");
-    INR_REQUIRE(B >= 1 && H >= 3 && W >= 3 && H == W, INR_E_INVALID,
-                "rams train: batch >= 1 and square low-resolution patches (the loss of utils/loss.py works on squares)");
-    return 0;
-}
-
-int64_t inr_rams_train_param_count(const inr_rams_desc_t* desc) {
-    if (!desc) return INR_E_INVALID;
-    return rams_train_param_floats(desc);
-}
-
-int inr_rams_train_param_offsets(const inr_rams_desc_t* desc, int64_t* offsets, int max_layers) {
-    INR_REQUIRE(desc && offsets, INR_E_INVALID, "inr_rams_train_param_offsets: null pointer");
-    return rams_train_param_offsets(desc, offsets, max_layers);
-}
-
-size_t inr_rams_train_workspace_bytes(const inr_rams_desc_t* desc, int batch, int height, int width) {
-    if (!desc || batch < 1 || height < 3 || width < 3) return 0;
-    return rams_train_workspace_floats(desc, batch, height, width) * sizeof(float);
-}
-
-int inr_rams_train_grads(const inr_rams_desc_t* desc, const float* params, float* grads, const float* x, const float* y_true,
-                         const float* mask, double* loss, float* pred, int batch, int height, int width, void* workspace,
-                         size_t workspace_bytes, void* stream) {
-    if (int rc = check_rams_train(desc, batch, height, width)) return rc;
-    INR_REQUIRE(params && grads && x && y_true && mask && loss, INR_E_INVALID, "inr_rams_train_grads: null pointer");
-    return rams_train_grads(desc, params, grads, x, y_true, mask, loss, pred, batch, height, width, workspace, workspace_bytes,
-                            (hipStream_t)stream);
-}
-
-int inr_rams_train_step(const inr_rams_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x,
-                        const float* y_true, const float* mask, double* loss, int batch, int height, int width, int64_t step,
-                        double lr, double beta1, double beta2, double eps, void* workspace, size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(m && v && step >= 1, INR_E_INVALID, "inr_rams_train_step: Adam state missing or step < 1");
-    if (int rc = inr_rams_train_grads(desc, params, grads, x, y_true, mask, loss, nullptr, batch, height, width, workspace,
-                                      workspace_bytes, stream))
-        return rc;
-    // Keras Adam: p -= lr sqrt(1 - b2^t) / (1 - b1^t) * m / (sqrt(v) + eps)  ==  the kernel's form with eps / sqrt(1 - b2^t)
-    const double bc2 = 1.0 - pow(beta2, (double)step);
-    return launch_adam(params, grads, m, v, rams_train_param_floats(desc), step, lr, beta1, beta2, eps / sqrt(bc2),
-                       (hipStream_t)stream);
 }
 
 int inr_debug_set_ptr(int key, void* ptr) {
@@ -1856,11 +1347,6 @@ int inr_jet_launch_count(int family, int64_t* count) {
 int inr_launch_counts_reset(void) {
     for (auto& c : g_launches) c.store(0, std::memory_order_relaxed);
     return 0;
-}
-
-int inr_sincos_probe(float* s, float* c, const float* x, int64_t n, void* stream) {
-    INR_REQUIRE(s && c && x && n >= 0, INR_E_INVALID, "inr_sincos_probe: bad arguments");
-    return launch_sincos_probe(s, c, x, n, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -46,6 +46,16 @@ void set_error(const char* fmt, ...);
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 static inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// the workspace of an fp64 image family (rescale, fourier, perceptual, register), which callers count in doubles: present, at
+// least `need_bytes` long, 16-byte aligned
+static inline int check_ws_doubles(const char* who, const double* workspace, int64_t workspace_doubles, size_t need_bytes) {
+    INR_REQUIRE(workspace && workspace_doubles >= 0 && (size_t)workspace_doubles * sizeof(double) >= need_bytes, INR_E_WORKSPACE,
+                "%s: workspace too small (%lld doubles, %zu needed)", who, workspace ? (long long)workspace_doubles : 0ll,
+                need_bytes / sizeof(double));
+    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
+    return 0;
+}
+
 // How every unit hands out its caller-allocated workspace: ONE function `X_view(shape..., base)` per workspace takes the regions
 // in order and returns typed pointers plus the total.  The planner is that function with a null base (`take` returns null and
 // still advances); the entry point calls it once with the real base and checks `workspace_bytes >= total` before its first launch.

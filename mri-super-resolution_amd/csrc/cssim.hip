@@ -390,9 +390,7 @@ int cssim_forward(double* out, int* arg, const float* y_true, const float* y_pre
     return 0;
 }
 
-}  // namespace
-
-int cssim_min_crop() { return KW; }
+int cssim_min_crop() { return KW; }   // the cropped window must hold one 11 x 11 filter window
 
 size_t cssim_workspace_doubles(int nimg, int size, int border, bool grad) { return cssim_plan(nimg, size, border, grad, nullptr).total; }
 
@@ -426,4 +424,55 @@ int launch_cssim_grad(double* loss, float* grad, const float* y_true, const floa
     return 0;
 }
 
+int shift_ssim_args_ok(const char* who, int n_images, int size, int border) {
+    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && border >= 0 && border <= 16 && size <= 8192 &&
+                    size - 2 * border >= cssim_min_crop(),
+                INR_E_INVALID, "%s: bad arguments (n_images=%d size=%d border=%d; size - 2*border >= %d)", who, n_images, size,
+                border, cssim_min_crop());
+    return 0;
+}
+
+size_t shift_ssim_bytes(int n_images, int size, int border, bool grad) {
+    if (border < 0 || border > 16 || size > 8192 || size - 2 * border < cssim_min_crop()) return 0;
+    return cssim_workspace_doubles(n_images, size, border, grad) * sizeof(double);
+}
+
+}  // namespace
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+size_t inr_rams_shift_ssim_workspace_bytes(int n_images, int size, int border) {
+    return shift_ssim_bytes(n_images, size, border, false);
+}
+
+int inr_rams_shift_ssim(double* out, const float* y_true, const float* y_pred, const float* mask, int n_images, int size,
+                        int border, int clear_only, void* workspace, size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(out && y_true && y_pred && mask, INR_E_INVALID, "inr_rams_shift_ssim: null pointer");
+    if (int rc = shift_ssim_args_ok("inr_rams_shift_ssim", n_images, size, border)) return rc;
+    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_shift_ssim_workspace_bytes(n_images, size, border), INR_E_WORKSPACE,
+                "inr_rams_shift_ssim: workspace too small");
+    INR_REQUIRE(((uintptr_t)workspace & 7) == 0, INR_E_ALIGN, "inr_rams_shift_ssim: workspace must be 8-byte aligned");
+    return launch_cssim(out, y_true, y_pred, mask, n_images, size, border, clear_only != 0, (double*)workspace,
+                        (hipStream_t)stream);
+}
+
+size_t inr_rams_shift_ssim_grad_workspace_bytes(int n_images, int size, int border) {
+    return shift_ssim_bytes(n_images, size, border, true);
+}
+
+int inr_rams_shift_ssim_grad(double* loss, float* grad_pred, const float* y_true, const float* y_pred, const float* mask,
+                             const float* upstream, int n_images, int size, int border, int clear_only, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(loss && grad_pred && y_true && y_pred && mask, INR_E_INVALID, "inr_rams_shift_ssim_grad: null pointer");
+    if (int rc = shift_ssim_args_ok("inr_rams_shift_ssim_grad", n_images, size, border)) return rc;
+    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_shift_ssim_grad_workspace_bytes(n_images, size, border), INR_E_WORKSPACE,
+                "inr_rams_shift_ssim_grad: workspace too small");
+    INR_REQUIRE(((uintptr_t)workspace & 7) == 0, INR_E_ALIGN, "inr_rams_shift_ssim_grad: workspace must be 8-byte aligned");
+    return launch_cssim_grad(loss, grad_pred, y_true, y_pred, mask, upstream, n_images, size, border, clear_only != 0,
+                             (double*)workspace, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -218,8 +218,7 @@ erd_volume_kernel(double* __restrict__ accept, double* __restrict__ direction_me
         }
 }
 
-}  // namespace
-
+// host only: no device is touched
 int erd_volume_check(int n, const int* group_sizes, int n_groups, double b, int rule) {
     INR_REQUIRE(n >= 2 && n <= EV_MAXN, INR_E_INVALID, "inr_auto_erd_volume: 2 <= acquisitions <= %d (got %d)", EV_MAXN, n);
     INR_REQUIRE(rule >= 0 && rule <= 2, INR_E_INVALID,
@@ -253,4 +252,25 @@ int launch_erd_volume(double* accept, double* direction_mean, double* accepted_m
     return 0;
 }
 
+}  // namespace
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+int inr_auto_erd_volume(double* accept, double* direction_mean, double* accepted_mean, double* direction_adc, double* accepted_adc,
+                   double* adc, const double* values, const double* b0, const double* erd_map, const double* accept_in,
+                   int64_t n_pixels, int n_acquisitions, const int* group_sizes, int n_groups, double b, int rule, void* stream) {
+    INR_REQUIRE(values != nullptr, INR_E_INVALID, "inr_auto_erd_volume: null pointer (values)");
+    INR_REQUIRE(b0 != nullptr || !(direction_adc || accepted_adc || adc), INR_E_INVALID,
+                "inr_auto_erd_volume: null pointer (b0, which the ADC outputs need)");
+    INR_REQUIRE(n_pixels >= 0 && n_pixels < (1ll << 37), INR_E_INVALID, "inr_auto_erd_volume: bad pixel count");
+    if (int rc = erd_volume_check(n_acquisitions, group_sizes, n_groups, b, rule)) return rc;
+    INR_REQUIRE(rule == 0 || accept_in == nullptr, INR_E_INVALID,
+                "inr_auto_erd_volume: accept_in supplies the weights of rule 0; rules 1 and 2 compute them");
+    return launch_erd_volume(accept, direction_mean, accepted_mean, direction_adc, accepted_adc, adc, values, b0, erd_map, accept_in,
+                             n_pixels, n_acquisitions, group_sizes, n_groups, b, rule, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -23,6 +23,9 @@ namespace {
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
+constexpr int FOURIER_MAX_LINE = INR_FOURIER_MAX_LINE;
+struct FourierView { double *op_rows, *op_cols, *mid; size_t total; };
+
 constexpr int FR_TILE = 64;    // the block's output tile: 4 waves, 32 x 32 each (2 x 2 MFMA tiles)
 constexpr int FR_KS = 16;      // K per LDS stage: 4 MFMA steps
 constexpr int FR_PITCH = 81;   // doubles per staged k: the 16 k of a k-fastest store fall on 16 bank pairs, the two k of a read's lane
@@ -189,6 +192,14 @@ int fr_mode_check(const char* who, int align, int boundary, double apodize) {
     return 0;
 }
 
+// validated by fourier_operator_check
+int launch_fourier_operator(double* op, int n, int m, int align, int boundary, double apodize, hipStream_t st) {
+    const long long total = (long long)m * n;
+    hipLaunchKernelGGL(fr_operator_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, op, fr_axis(n, m, align, boundary, apodize));
+    INR_LAUNCH_CHECK();
+    return 0;
+}
+
 template <typename T>
 int fr_resample2d(T* out, const T* in, int nimg, int H, int W, int OH, int OW, int align, int boundary, double apodize,
                   const FourierView& v, hipStream_t st) {
@@ -209,8 +220,6 @@ int fr_resample2d(T* out, const T* in, int nimg, int H, int W, int OH, int OW, i
     INR_HIP(hipMemcpyAsync(out, in, (size_t)lines * W * sizeof(T), hipMemcpyDeviceToDevice, st));
     return 0;
 }
-
-}  // namespace
 
 // the workspace: the two operators and the plane between the two passes.  base == null: `total` only
 FourierView fourier_view(int nimg, int H, int W, int OH, int OW, void* base) {
@@ -245,14 +254,6 @@ int fourier_check(const char* who, int nimg, int H, int W, int OH, int OW, int a
     return fr_axis_check(who, W, OW, align, boundary, true);
 }
 
-// validated by fourier_operator_check
-int launch_fourier_operator(double* op, int n, int m, int align, int boundary, double apodize, hipStream_t st) {
-    const long long total = (long long)m * n;
-    hipLaunchKernelGGL(fr_operator_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, op, fr_axis(n, m, align, boundary, apodize));
-    INR_LAUNCH_CHECK();
-    return 0;
-}
-
 // everything validated (fourier_check) and the workspace checked by the caller
 int launch_fourier_resample2d(double* out, const double* in, int nimg, int H, int W, int OH, int OW, int align, int boundary,
                               double apodize, const FourierView& v, hipStream_t st) {
@@ -264,4 +265,48 @@ int launch_fourier_resample2d(float* out, const float* in, int nimg, int H, int 
     return fr_resample2d(out, in, nimg, H, W, OH, OW, align, boundary, apodize, v, st);
 }
 
+// the arguments and the workspace of one re-sampling call, before any device work
+int fourier_call_check(const char* who, const void* out, const void* in, int n_images, int height, int width, int out_height,
+                       int out_width, int align, int boundary, double apodize, const double* workspace, int64_t workspace_doubles) {
+    INR_REQUIRE(out && in, INR_E_INVALID, "%s: null pointer", who);
+    if (int rc = fourier_check(who, n_images, height, width, out_height, out_width, align, boundary, apodize)) return rc;
+    return check_ws_doubles(who, workspace, workspace_doubles, fourier_view(n_images, height, width, out_height, out_width, nullptr).total);
+}
+
+}  // namespace
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+int inr_fourier_operator(double* op, int n, int m, int align, int boundary, double apodize, void* stream) {
+    INR_REQUIRE(op, INR_E_INVALID, "inr_fourier_operator: null pointer");
+    if (int rc = fourier_operator_check("inr_fourier_operator", n, m, align, boundary, apodize)) return rc;
+    return launch_fourier_operator(op, n, m, align, boundary, apodize, (hipStream_t)stream);
+}
+
+int64_t inr_fourier_resample_workspace_doubles(int n_images, int height, int width, int out_height, int out_width) {
+    if (fourier_sizes_check("inr_fourier_resample_workspace_doubles", n_images, height, width, out_height, out_width)) return 0;
+    return (int64_t)(fourier_view(n_images, height, width, out_height, out_width, nullptr).total / sizeof(double));
+}
+
+int inr_fourier_resample2d(double* out, const double* in, int n_images, int height, int width, int out_height, int out_width, int align,
+                           int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream) {
+    if (int rc = fourier_call_check("inr_fourier_resample2d", out, in, n_images, height, width, out_height, out_width, align, boundary,
+                                    apodize, workspace, workspace_doubles))
+        return rc;
+    return launch_fourier_resample2d(out, in, n_images, height, width, out_height, out_width, align, boundary, apodize,
+                                     fourier_view(n_images, height, width, out_height, out_width, workspace), (hipStream_t)stream);
+}
+
+int inr_fourier_resample2d_f32(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
+                               int align, int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream) {
+    if (int rc = fourier_call_check("inr_fourier_resample2d_f32", out, in, n_images, height, width, out_height, out_width, align, boundary,
+                                    apodize, workspace, workspace_doubles))
+        return rc;
+    return launch_fourier_resample2d(out, in, n_images, height, width, out_height, out_width, align, boundary, apodize,
+                                     fourier_view(n_images, height, width, out_height, out_width, workspace), (hipStream_t)stream);
+}
+
+}  // extern "C"

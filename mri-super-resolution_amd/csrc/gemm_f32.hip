@@ -961,8 +961,8 @@ int gemm_sine_forward(float* act, float* dact, const float* x, const float* W, c
 }
 
 // act[n][out] = scale*tanh(x W^T + b), optional dact = scale*(1 - tanh^2)   (PerturbNet hidden layer)
-int gemm_tanh_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n, int in_f,
-                      int out_f, float scale, hipStream_t stream) {
+static int gemm_tanh_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n, int in_f,
+                             int out_f, float scale, hipStream_t stream) {
     GemmParams p{};
     p.A = x; p.B = W; p.C = act; p.C2 = dact; p.bias = b; p.mul = nullptr;
     p.M = (int)n; p.N = out_f; p.K = in_f;
@@ -1063,5 +1063,28 @@ int gemm_param_grad_slabs(float* slabs, int splits, const float* dz, const float
     return launch_gemm<false, false, EPI_PLAIN>(p, vec, stream);
 }
 
-
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+int inr_sine_layer_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n,
+                           int in_features, int out_features, float omega, void* stream) {
+    INR_REQUIRE(act && x && W, INR_E_INVALID, "inr_sine_layer_forward: null pointer");
+    INR_REQUIRE(n >= 0 && n <= MAX_ROWS && in_features >= 1 && out_features >= 1, INR_E_INVALID,
+                "inr_sine_layer_forward: bad sizes n=%lld in=%d out=%d", (long long)n, in_features, out_features);
+    if (n == 0) return 0;
+    return gemm_sine_forward(act, dact, x, W, b, n, in_features, out_features, omega, (hipStream_t)stream);
+}
+
+int inr_tanh_layer_forward(float* act, float* dact, const float* x, const float* W, const float* b, int64_t n,
+                           int in_features, int out_features, float scale, void* stream) {
+    INR_REQUIRE(act && x && W, INR_E_INVALID, "inr_tanh_layer_forward: null pointer");
+    INR_REQUIRE(n >= 0 && n <= MAX_ROWS && in_features >= 1 && out_features >= 1, INR_E_INVALID,
+                "inr_tanh_layer_forward: bad sizes");
+    if (n == 0) return 0;
+    return gemm_tanh_forward(act, dact, x, W, b, n, in_features, out_features, scale, (hipStream_t)stream);
+}
+
+}  // extern "C"

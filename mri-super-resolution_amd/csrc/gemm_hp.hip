@@ -102,15 +102,6 @@ int hp_convert(char* out, const float* x, long long rows, int cols, HpScale sc, 
     return 0;
 }
 
-int hp_unconvert(float* out, const char* x, long long rows, int cols, HpScale sc, hipStream_t stream) {
-    if (rows <= 0) return 0;
-    long long blocks = (rows * cols + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(hp_unconvert_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, out, x, rows, cols, sc);
-    INR_LAUNCH_CHECK();
-    return 0;
-}
-
 static int hp_check_grid(const HpParams& p) {
     const long long total = (long long)p.tiles_m * p.tiles_n * p.splits;
     INR_REQUIRE(total > 0 && total < (1ll << 31), INR_E_INVALID, "hp gemm grid out of range (%lld blocks)", total);

@@ -847,8 +847,8 @@ __global__ void __launch_bounds__(64) hybrid_fit_g8_kernel(double* __restrict__ 
 static tune_int g_hybrid_variant{1};   // 1 = eight lanes per voxel (default), 0 = one lane per voxel (cross-check)
 void set_hybrid_variant(int v) { g_hybrid_variant = v; }
 
-int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, const double* signals, int64_t n,
-                      hipStream_t st) {
+static int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, const double* signals, int64_t n,
+                             hipStream_t st) {
     ProfScope ps(KC_OTHER, st);
     if (g_hybrid_variant == 1)
         hipLaunchKernelGGL(hybrid_fit_g8_kernel, dim3((unsigned)((n + 7) / 8)), dim3(64), 0, st, params, status, nfev,
@@ -861,3 +861,19 @@ int launch_hybrid_fit(double* params, int* status, int* nfev, double* cost, cons
 }
 
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+int inr_hybrid_fit(double* params, int* status, int* nfev, double* cost, const double* signals, int64_t n_voxels,
+                   void* stream) {
+    if (n_voxels == 0) return 0;
+    INR_REQUIRE(params && status && nfev && cost && signals, INR_E_INVALID, "inr_hybrid_fit: null pointer");
+    // (one 8-lane group per voxel, grid dimension is 32-bit: 2^31 - 1 blocks of 8 voxels)
+    INR_REQUIRE(n_voxels > 0 && n_voxels <= ((int64_t)1 << 33), INR_E_INVALID, "inr_hybrid_fit: bad voxel count %lld",
+                (long long)n_voxels);
+    return launch_hybrid_fit(params, status, nfev, cost, signals, n_voxels, (hipStream_t)stream);
+}
+
+}  // extern "C"

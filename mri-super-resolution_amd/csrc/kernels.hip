@@ -819,8 +819,8 @@ __global__ void __launch_bounds__(256) acquisition_products_kernel(float* __rest
     }
 }
 
-int launch_acquisition_products(float* out, const float* r0, const float* r1, const float* r2, const float* r3, int64_t nvox,
-                                int n1, int n2, int n3, hipStream_t st) {
+static int launch_acquisition_products(float* out, const float* r0, const float* r1, const float* r2, const float* r3, int64_t nvox,
+                                       int n1, int n2, int n3, hipStream_t st) {
     const int64_t total = nvox * 4 * n1 * n2 * n3;
     if (total == 0) return 0;
     ProfScope ps(KC_OTHER, st);
@@ -830,7 +830,7 @@ int launch_acquisition_products(float* out, const float* r0, const float* r1, co
     return 0;
 }
 
-int launch_mul(float* out, const float* a, const float* b, int64_t count, hipStream_t st) {
+static int launch_mul(float* out, const float* a, const float* b, int64_t count, hipStream_t st) {
     if (count == 0) return 0;
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL(mul_kernel, dim3(blocks_for(count, 256, 256 * 32)), dim3(256), 0, st, out, a, b, count);
@@ -838,7 +838,7 @@ int launch_mul(float* out, const float* a, const float* b, int64_t count, hipStr
     return 0;
 }
 
-int launch_sincos_probe(float* s, float* c, const float* x, int64_t n, hipStream_t st) {
+static int launch_sincos_probe(float* s, float* c, const float* x, int64_t n, hipStream_t st) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(sincos_probe_kernel, dim3(blocks_for(n, 256, 1 << 30)), dim3(256), 0, st, s, c, x, n);
     INR_LAUNCH_CHECK();
@@ -846,3 +846,79 @@ int launch_sincos_probe(float* s, float* c, const float* x, int64_t n, hipStream
 }
 
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+int inr_mgrid(float* out, const int64_t* shape, int dim, int64_t row_begin, int64_t n_rows, void* stream) {
+    INR_REQUIRE(out && shape, INR_E_INVALID, "inr_mgrid: null pointer");
+    INR_REQUIRE(row_begin >= 0 && n_rows >= 0, INR_E_INVALID, "inr_mgrid: negative row range");
+    return launch_mgrid(out, shape, dim, row_begin, n_rows, (hipStream_t)stream);
+}
+
+int inr_fourier_map(float* out, const float* x, const float* B, int64_t n, int d, int m, void* stream) {
+    INR_REQUIRE(out && x && B, INR_E_INVALID, "inr_fourier_map: null pointer");
+    INR_REQUIRE(n >= 0 && d >= 1 && m >= 1, INR_E_INVALID, "inr_fourier_map: bad sizes n=%lld d=%d m=%d",
+                (long long)n, d, m);
+    return launch_fourier(out, x, nullptr, d, 0, n, B, m, (hipStream_t)stream);
+}
+
+int inr_grid_fourier_map(float* out, const int64_t* shape, int dim, int64_t row_begin, int64_t n_rows,
+                         const float* B, int m, void* stream) {
+    INR_REQUIRE(out && shape && B, INR_E_INVALID, "inr_grid_fourier_map: null pointer");
+    INR_REQUIRE(row_begin >= 0 && n_rows >= 0 && m >= 1, INR_E_INVALID, "inr_grid_fourier_map: bad sizes");
+    return launch_fourier(out, nullptr, shape, dim, row_begin, n_rows, B, m, (hipStream_t)stream);
+}
+
+int inr_linear_tanh_head_forward(float* y, float* dy, const float* a, const float* W, const float* b, int64_t n,
+                                 int in_features, int out_features, float scale, void* stream) {
+    INR_REQUIRE(y && a && W, INR_E_INVALID, "inr_linear_tanh_head_forward: null pointer");
+    INR_REQUIRE(n >= 0 && in_features >= 1 && out_features >= 1, INR_E_INVALID, "inr_linear_tanh_head_forward: bad sizes");
+    return launch_head_forward(y, a, W, b, n, in_features, out_features, 2, scale, (hipStream_t)stream, dy);
+}
+
+int inr_acquisition_products(float* out, const float* raw_b0, const float* raw_b1, const float* raw_b2, const float* raw_b3,
+                             int64_t n_voxels, int n1, int n2, int n3, void* stream) {
+    INR_REQUIRE(out && raw_b0 && raw_b1 && raw_b2 && raw_b3, INR_E_INVALID, "inr_acquisition_products: null pointer");
+    INR_REQUIRE(n_voxels >= 0 && n1 >= 1 && n2 >= 1 && n3 >= 1 && (long long)n1 * n2 * n3 < (1 << 24), INR_E_INVALID,
+                "inr_acquisition_products: bad sizes");
+    return launch_acquisition_products(out, raw_b0, raw_b1, raw_b2, raw_b3, n_voxels, n1, n2, n3, (hipStream_t)stream);
+}
+
+int inr_mul(float* out, const float* a, const float* b, int64_t count, void* stream) {
+    INR_REQUIRE(out && a && b && count >= 0, INR_E_INVALID, "inr_mul: bad arguments");
+    return launch_mul(out, a, b, count, (hipStream_t)stream);
+}
+
+int inr_linear_head_forward(float* y, const float* a, const float* W, const float* b, int64_t n, int in_features,
+                            int out_features, int use_clamp, float clamp_min, void* stream) {
+    INR_REQUIRE(y && a && W, INR_E_INVALID, "inr_linear_head_forward: null pointer");
+    INR_REQUIRE(n >= 0 && in_features >= 1 && out_features >= 1, INR_E_INVALID, "inr_linear_head_forward: bad sizes");
+    return launch_head_forward(y, a, W, b, n, in_features, out_features, use_clamp, clamp_min, (hipStream_t)stream);
+}
+
+size_t inr_mse_workspace_bytes(int64_t count) { return (size_t)mse_blocks(count > 0 ? count : 1) * sizeof(float); }
+
+int inr_mse_loss_grad(float* gy, float* loss, const float* y, const float* t, const float* w, int64_t count,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(gy && loss && y && t, INR_E_INVALID, "inr_mse_loss_grad: null pointer");
+    INR_REQUIRE(count >= 1, INR_E_INVALID, "inr_mse_loss_grad: count must be >= 1");
+    INR_REQUIRE(workspace && workspace_bytes >= inr_mse_workspace_bytes(count), INR_E_WORKSPACE,
+                "inr_mse_loss_grad: workspace too small");
+    return launch_mse(gy, loss, y, t, w, count, (float*)workspace, (hipStream_t)stream);
+}
+
+int inr_adam_step(float* p, const float* g, float* m, float* v, int64_t count, int64_t step, double lr,
+                  double beta1, double beta2, double eps, void* stream) {
+    INR_REQUIRE(p && g && m && v, INR_E_INVALID, "inr_adam_step: null pointer");
+    INR_REQUIRE(count >= 0 && step >= 1, INR_E_INVALID, "inr_adam_step: count >= 0 and step >= 1 required");
+    return launch_adam(p, g, m, v, count, step, lr, beta1, beta2, eps, (hipStream_t)stream);
+}
+
+int inr_sincos_probe(float* s, float* c, const float* x, int64_t n, void* stream) {
+    INR_REQUIRE(s && c && x && n >= 0, INR_E_INVALID, "inr_sincos_probe: bad arguments");
+    return launch_sincos_probe(s, c, x, n, (hipStream_t)stream);
+}
+
+}  // extern "C"

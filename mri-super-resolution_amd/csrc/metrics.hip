@@ -216,10 +216,10 @@ __global__ void __launch_bounds__(256) shift_loss_grad_kernel(float* __restrict_
 
 constexpr int METRIC_BLOCKS = 64;
 
-int metric_workspace_doubles(int nimg) { return nimg * METRIC_BLOCKS; }
+static int metric_workspace_doubles(int nimg) { return nimg * METRIC_BLOCKS; }
 
-int launch_psnr(double* out, const float* x, const float* y, int nimg, int64_t per_image, double data_range,
-                double* ws, hipStream_t st) {
+static int launch_psnr(double* out, const float* x, const float* y, int nimg, int64_t per_image, double data_range,
+                       double* ws, hipStream_t st) {
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL(sqdiff_kernel, dim3(METRIC_BLOCKS, nimg), dim3(256), 0, st, ws, x, y, per_image, METRIC_BLOCKS);
     INR_LAUNCH_CHECK();
@@ -229,8 +229,8 @@ int launch_psnr(double* out, const float* x, const float* y, int nimg, int64_t p
     return 0;
 }
 
-int launch_ssim(double* out, const float* x, const float* y, int nimg, int H, int W, int win, double data_range,
-                int use_mask, float mask_thr, double* ws, hipStream_t st) {
+static int launch_ssim(double* out, const float* x, const float* y, int nimg, int H, int W, int win, double data_range,
+                       int use_mask, float mask_thr, double* ws, hipStream_t st) {
     const int pad = (win - 1) / 2;
     const double c1 = (0.01 * data_range) * (0.01 * data_range), c2 = (0.03 * data_range) * (0.03 * data_range);
     ProfScope ps(KC_OTHER, st);
@@ -243,8 +243,8 @@ int launch_ssim(double* out, const float* x, const float* y, int nimg, int H, in
     return 0;
 }
 
-int launch_shift_loss(double* out, const float* y_true, const float* y_pred, const float* mask, int nimg, int size,
-                      int border, int mode, double* ws, hipStream_t st) {
+static int launch_shift_loss(double* out, const float* y_true, const float* y_pred, const float* mask, int nimg, int size,
+                             int border, int mode, double* ws, hipStream_t st) {
     const int ns = 2 * border + 1;
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL(shift_loss_kernel, dim3(ns * ns, nimg), dim3(256), 0, st, ws, y_true, y_pred, mask, size, border, mode);
@@ -295,7 +295,7 @@ __global__ void __launch_bounds__(256) rescale_linear_kernel(float* __restrict__
     }
 }
 
-int launch_rescale_linear(float* out, const float* in, int nimg, int H, int W, int OH, int OW, hipStream_t st) {
+static int launch_rescale_linear(float* out, const float* in, int nimg, int H, int W, int OH, int OW, hipStream_t st) {
     const long long total = (long long)nimg * OH * OW;
     if (total == 0) return 0;
     long long blocks = (total + 255) / 256;
@@ -350,9 +350,9 @@ __global__ void __launch_bounds__(256) resize_z_cubic_kernel(double* __restrict_
 
 constexpr int RESIZE_Z_MAX_IN = 8192;   // the Thomas factor, n_in doubles, fits the 64 KiB of dynamic LDS
 
-size_t resize_z_workspace_doubles(int64_t n_lines, int n_in) { return (size_t)n_lines * (size_t)n_in; }
+static size_t resize_z_workspace_doubles(int64_t n_lines, int n_in) { return (size_t)n_lines * (size_t)n_in; }
 
-int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, double* ws, hipStream_t st) {
+static int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, double* ws, hipStream_t st) {
     INR_REQUIRE(n_in >= 4 && n_in <= RESIZE_Z_MAX_IN, INR_E_INVALID, "inr_resize_z_cubic: 4 to %d samples per line (got %d)",
                 RESIZE_Z_MAX_IN, n_in);
     ProfScope ps(KC_OTHER, st);
@@ -362,7 +362,7 @@ int launch_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_
     return 0;
 }
 
-int launch_adc(float* out, const float* data, const float* bvals, int64_t npix, int nb, hipStream_t st) {
+static int launch_adc(float* out, const float* data, const float* bvals, int64_t npix, int nb, hipStream_t st) {
     if (npix == 0) return 0;
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL(adc_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, st, out, data, bvals, npix, nb);
@@ -382,7 +382,7 @@ __global__ void __launch_bounds__(64) auto_erd_kernel(float* __restrict__ accept
     auto_erd_pixel(accept + pix * n, values + pix * n, n, rule, majority, !erd_map || erd_map[pix] > 0.f);
 }
 
-int launch_auto_erd(float* accept, const double* values, const float* erd_map, int64_t npix, int n, int rule, hipStream_t st) {
+static int launch_auto_erd(float* accept, const double* values, const float* erd_map, int64_t npix, int n, int rule, hipStream_t st) {
     INR_REQUIRE(n >= 2 && n <= ERD_MAXN, INR_E_INVALID, "inr_auto_erd: 2 <= acquisitions <= %d (got %d)", ERD_MAXN, n);
     INR_REQUIRE(rule == 1 || rule == 2, INR_E_INVALID, "inr_auto_erd: rule must be 1 (majority voting) or 2 (intensity-cognisant)");
     if (npix == 0) return 0;
@@ -395,3 +395,110 @@ int launch_auto_erd(float* accept, const double* values, const float* erd_map, i
 }
 
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+size_t inr_metric_workspace_bytes(int n_images) {
+    return (size_t)metric_workspace_doubles(n_images > 0 ? n_images : 1) * sizeof(double);
+}
+
+int inr_psnr(double* out, const float* x, const float* y, int n_images, int64_t per_image, double data_range,
+             void* workspace, size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(out && x && y, INR_E_INVALID, "inr_psnr: null pointer");
+    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && per_image >= 1 && data_range > 0, INR_E_INVALID,
+                "inr_psnr: bad sizes");
+    INR_REQUIRE(workspace && workspace_bytes >= inr_metric_workspace_bytes(n_images), INR_E_WORKSPACE,
+                "inr_psnr: workspace too small");
+    return launch_psnr(out, x, y, n_images, per_image, data_range, (double*)workspace, (hipStream_t)stream);
+}
+
+int inr_ssim2d(double* out, const float* x, const float* y, int n_images, int height, int width, int win,
+               double data_range, int use_mask, float mask_thr, void* workspace, size_t workspace_bytes,
+               void* stream) {
+    INR_REQUIRE(out && x && y, INR_E_INVALID, "inr_ssim2d: null pointer");
+    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && win >= 3 && (win & 1) && height >= win && width >= win &&
+                    data_range > 0,
+                INR_E_INVALID, "inr_ssim2d: need odd win >= 3 and images at least win x win (got %dx%d, win %d)",
+                height, width, win);
+    INR_REQUIRE(workspace && workspace_bytes >= inr_metric_workspace_bytes(n_images), INR_E_WORKSPACE,
+                "inr_ssim2d: workspace too small");
+    return launch_ssim(out, x, y, n_images, height, width, win, data_range, use_mask, mask_thr, (double*)workspace,
+                       (hipStream_t)stream);
+}
+
+size_t inr_rams_shift_loss_workspace_bytes(int n_images, int border) {
+    const int ns = 2 * (border > 0 ? border : 0) + 1;
+    return (size_t)(n_images > 0 ? n_images : 1) * ns * ns * sizeof(double);
+}
+
+int inr_rams_shift_loss(double* out, const float* y_true, const float* y_pred, const float* mask, int n_images, int size,
+                        int border, int mode, void* workspace, size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(out && y_true && y_pred && mask, INR_E_INVALID, "inr_rams_shift_loss: null pointer");
+    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && border >= 0 && border <= 16 && size > 2 * border &&
+                    (mode == 0 || mode == 1),
+                INR_E_INVALID, "inr_rams_shift_loss: bad arguments (size=%d border=%d mode=%d)", size, border, mode);
+    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_shift_loss_workspace_bytes(n_images, border), INR_E_WORKSPACE,
+                "inr_rams_shift_loss: workspace too small");
+    return launch_shift_loss(out, y_true, y_pred, mask, n_images, size, border, mode, (double*)workspace,
+                             (hipStream_t)stream);
+}
+
+size_t inr_rams_shift_loss_grad_workspace_bytes(int n_images, int border) {
+    return inr_rams_shift_loss_workspace_bytes(n_images, border) + (size_t)(n_images > 0 ? n_images : 1) * sizeof(int) + 8;
+}
+
+int inr_rams_shift_loss_grad(double* loss, float* grad_pred, const float* y_true, const float* y_pred, const float* mask,
+                             const float* upstream, int n_images, int size, int border, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(loss && grad_pred && y_true && y_pred && mask, INR_E_INVALID, "inr_rams_shift_loss_grad: null pointer");
+    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && border >= 0 && border <= 16 && size > 2 * border, INR_E_INVALID,
+                "inr_rams_shift_loss_grad: bad arguments (size=%d border=%d)", size, border);
+    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_shift_loss_grad_workspace_bytes(n_images, border), INR_E_WORKSPACE,
+                "inr_rams_shift_loss_grad: workspace too small");
+    INR_REQUIRE(((uintptr_t)workspace & 7) == 0, INR_E_ALIGN, "inr_rams_shift_loss_grad: workspace must be 8-byte aligned");
+    return launch_shift_loss_grad(loss, grad_pred, y_true, y_pred, mask, upstream, n_images, size, border, (double*)workspace,
+                                  (hipStream_t)stream);
+}
+
+int inr_adc_map(float* out, const float* data, const float* bvals, int64_t n_pixels, int n_b, void* stream) {
+    INR_REQUIRE(out && data && bvals, INR_E_INVALID, "inr_adc_map: null pointer");
+    INR_REQUIRE(n_pixels >= 0 && n_b >= 2 && n_b <= 32, INR_E_INVALID, "inr_adc_map: need 2 <= n_b <= 32");
+    return launch_adc(out, data, bvals, n_pixels, n_b, (hipStream_t)stream);
+}
+
+int inr_rescale2d_linear(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
+                         void* stream) {
+    INR_REQUIRE(out && in, INR_E_INVALID, "inr_rescale2d_linear: null pointer");
+    INR_REQUIRE(n_images >= 0 && height >= 1 && width >= 1 && out_height >= 1 && out_width >= 1, INR_E_INVALID,
+                "inr_rescale2d_linear: bad sizes");
+    INR_REQUIRE((long long)height * width < (1ll << 31) && (long long)out_height * out_width < (1ll << 31), INR_E_INVALID,
+                "inr_rescale2d_linear: image too large");
+    return launch_rescale_linear(out, in, n_images, height, width, out_height, out_width, (hipStream_t)stream);
+}
+
+size_t inr_resize_z_cubic_workspace_bytes(int64_t n_lines, int n_in) {
+    return resize_z_workspace_doubles(n_lines > 0 ? n_lines : 1, n_in > 0 ? n_in : 1) * sizeof(double);
+}
+
+int inr_resize_z_cubic(double* out, const double* in, int64_t n_lines, int n_in, int n_out, void* workspace, size_t workspace_bytes,
+                       void* stream) {
+    INR_REQUIRE(out && in, INR_E_INVALID, "inr_resize_z_cubic: null pointer");
+    INR_REQUIRE(n_lines >= 1 && n_lines < (1ll << 31) && n_in >= 1 && n_out >= 1, INR_E_INVALID,
+                "inr_resize_z_cubic: bad sizes (n_lines=%lld, n_in=%d, n_out=%d)", (long long)n_lines, n_in, n_out);
+    INR_REQUIRE(n_in >= 4, INR_E_INVALID,
+                "inr_resize_z_cubic: a not-a-knot cubic spline needs at least 4 samples per line (got %d)", n_in);
+    INR_REQUIRE(workspace && workspace_bytes >= inr_resize_z_cubic_workspace_bytes(n_lines, n_in), INR_E_WORKSPACE,
+                "inr_resize_z_cubic: workspace too small");
+    return launch_resize_z_cubic(out, in, n_lines, n_in, n_out, (double*)workspace, (hipStream_t)stream);
+}
+
+int inr_auto_erd(float* accept, const double* values, const float* erd_map, int64_t n_pixels, int n_acquisitions, int rule,
+                 void* stream) {
+    INR_REQUIRE(accept && values, INR_E_INVALID, "inr_auto_erd: null pointer");
+    INR_REQUIRE(n_pixels >= 0 && n_pixels < (1ll << 37), INR_E_INVALID, "inr_auto_erd: bad pixel count");
+    return launch_auto_erd(accept, values, erd_map, n_pixels, n_acquisitions, rule, (hipStream_t)stream);
+}
+
+}  // extern "C"

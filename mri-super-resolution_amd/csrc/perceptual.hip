@@ -19,6 +19,10 @@
 namespace inr {
 namespace {
 
+constexpr int PERCEPTUAL_MAX_RADIUS = INR_PERCEPTUAL_MAX_RADIUS;   // window taps per side: what the tile's halo in LDS holds
+constexpr int PERCEPTUAL_MAX_SCALES = INR_PERCEPTUAL_MAX_SCALES;
+struct PerceptualView { double *reduce, *partial, *vals, *lx[2], *ly[2]; size_t total; };
+
 constexpr int PC_TW = 32, PC_TH = 16;                                  // the output tile of one block of 256 threads: 2 pixels per thread
 constexpr int PC_RMAX = PERCEPTUAL_MAX_RADIUS;
 constexpr int PC_SW = PC_TW + 2 * PC_RMAX, PC_SH = PC_TH + 2 * PC_RMAX;   // the staged tile with its halo: 46 x 30
@@ -242,8 +246,6 @@ int pc_ssim_level(double* lcs, double* cs, float* map, const T* x, const T* y, i
     return 0;
 }
 
-}  // namespace
-
 // the workspace of every entry point of this unit: the two flat reductions' partials first (so that a view sized for any image
 // shape serves inr_image_mse and inr_hf_gain), the tile partials, the per-scale means, and two pairs of fp64 levels (level s lives
 // in pair s & 1).  base == null: `total` only
@@ -359,4 +361,67 @@ int launch_pair_score(double* out, const float* x, const float* y, int nimg, int
     return 0;
 }
 
+int pair_score(const char* who, double* out, const float* x, const float* y, int n_images, int64_t per_image, int mode,
+               double* workspace, int64_t workspace_doubles, void* stream) {
+    INR_REQUIRE(out && x && y, INR_E_INVALID, "%s: null pointer", who);
+    INR_REQUIRE(n_images >= 1 && n_images <= 65535 && per_image >= 1, INR_E_INVALID, "%s: bad sizes (n_images=%d, per_image=%lld)", who,
+                n_images, (long long)per_image);
+    const PerceptualView v = perceptual_view(n_images, 1, 1, 1, workspace);
+    if (int rc = check_ws_doubles(who, workspace, workspace_doubles, v.total)) return rc;
+    INR_REQUIRE(aligned16(out) && aligned16(x) && aligned16(y), INR_E_ALIGN, "%s: pointers must be 16-byte aligned", who);
+    return launch_pair_score(out, x, y, n_images, per_image, mode, v, (hipStream_t)stream);
+}
+
+}  // namespace
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+int64_t inr_perceptual_workspace_doubles(int n_images, int height, int width, int n_scales) {
+    if (perceptual_check("inr_perceptual_workspace_doubles", n_images, height, width, 1.5, 1.0, n_scales)) return 0;
+    return (int64_t)(perceptual_view(n_images, height, width, n_scales, nullptr).total / sizeof(double));
+}
+
+int inr_ssim2d_gauss(double* ssim, double* mean_cs, float* map, const float* x, const float* y, int n_images, int height, int width,
+                     double sigma, double data_range, double* workspace, int64_t workspace_doubles, void* stream) {
+    INR_REQUIRE(ssim && x && y, INR_E_INVALID, "inr_ssim2d_gauss: null pointer");
+    if (int rc = perceptual_check("inr_ssim2d_gauss", n_images, height, width, sigma, data_range, 1)) return rc;
+    const PerceptualView v = perceptual_view(n_images, height, width, 1, workspace);
+    if (int rc = check_ws_doubles("inr_ssim2d_gauss", workspace, workspace_doubles, v.total)) return rc;
+    INR_REQUIRE(aligned16(ssim) && aligned16(mean_cs) && aligned16(map) && aligned16(x) && aligned16(y), INR_E_ALIGN,
+                "inr_ssim2d_gauss: pointers must be 16-byte aligned");
+    return launch_ssim_gauss(ssim, mean_cs, map, x, y, n_images, height, width, sigma, data_range, v, (hipStream_t)stream);
+}
+
+int inr_msssim2d(double* out, double* per_scale, const float* x, const float* y, int n_images, int height, int width,
+                 const double* weights, int n_scales, double sigma, double data_range, double* workspace, int64_t workspace_doubles,
+                 void* stream) {
+    INR_REQUIRE(out && x && y && weights, INR_E_INVALID, "inr_msssim2d: null pointer");
+    if (int rc = perceptual_check("inr_msssim2d", n_images, height, width, sigma, data_range, n_scales)) return rc;
+    const PerceptualView v = perceptual_view(n_images, height, width, n_scales, workspace);
+    if (int rc = check_ws_doubles("inr_msssim2d", workspace, workspace_doubles, v.total)) return rc;
+    INR_REQUIRE(aligned16(out) && aligned16(per_scale) && aligned16(x) && aligned16(y), INR_E_ALIGN,
+                "inr_msssim2d: pointers must be 16-byte aligned");
+    return launch_msssim(out, per_scale, x, y, n_images, height, width, weights, n_scales, sigma, data_range, v, (hipStream_t)stream);
+}
+
+int inr_filter3x3(float* out, const float* in, int n_images, int height, int width, const double* k9, void* stream) {
+    INR_REQUIRE(out && in && k9, INR_E_INVALID, "inr_filter3x3: null pointer");
+    if (int rc = perceptual_check("inr_filter3x3", n_images, height, width, 1.5, 1.0, 1)) return rc;
+    INR_REQUIRE(aligned16(out) && aligned16(in), INR_E_ALIGN, "inr_filter3x3: pointers must be 16-byte aligned");
+    return launch_filter3x3(out, in, n_images, height, width, k9, (hipStream_t)stream);
+}
+
+int inr_image_mse(double* out, const float* x, const float* y, int n_images, int64_t per_image, double* workspace,
+                  int64_t workspace_doubles, void* stream) {
+    return pair_score("inr_image_mse", out, x, y, n_images, per_image, 0, workspace, workspace_doubles, stream);
+}
+
+int inr_hf_gain(double* out, const float* h_sr, const float* h_inter, int n_images, int64_t per_image, double* workspace,
+                int64_t workspace_doubles, void* stream) {
+    return pair_score("inr_hf_gain", out, h_sr, h_inter, n_images, per_image, 1, workspace, workspace_doubles, stream);
+}
+
+}  // extern "C"

@@ -799,7 +799,7 @@ struct Cursor {
     }
 };
 
-long long rams_param_floats(const inr_rams_desc_t* d) {
+static long long rams_param_floats(const inr_rams_desc_t* d) {
     Cursor c{nullptr};
     auto conv = [&]() { c.take(CONV_W_FLOATS); c.take(RC); };
     auto gate = [&](int C, int Cr) { c.take((long long)C * Cr); c.take(Cr); c.take((long long)Cr * C); c.take(C); };
@@ -1091,21 +1091,21 @@ __global__ void __launch_bounds__(512, 2) conv3d_c32_wgrad_kernel(const Conv3dWg
 constexpr int WGRAD_BLOCKS = 512;        // target number of blocks (two per CU)
 constexpr int WGRAD_BLOCKS_MAX = 1024;   // slabs the workspace is sized for (blocks_per_b * B never exceeds max(512, B))
 
-size_t rams_conv3d_wgrad_ws_floats(long long nvox) {
+static size_t rams_conv3d_wgrad_ws_floats(long long nvox) {
     const size_t a = (size_t)WGRAD_BLOCKS_MAX * (CONV_W_FLOATS + RC) + (size_t)reduce_tmp_floats(WGRAD_BLOCKS_MAX, CONV_W_FLOATS + RC);
     const size_t b = (size_t)colsum_ws_floats(nvox, RC, 1);
     return (a > b ? a : b) + 64 + 2 * R3_SLOT + 64;      // (+ two max|.| slots for the stand-alone split-fp16 call)
 }
 
-int rams_conv3d_forward(float* y, const float* x, const float* w, const float* bias, int B, int D1, int D2, int D3, int pad,
-                        int relu, hipStream_t st) {
+static int rams_conv3d_forward(float* y, const float* x, const float* w, const float* bias, int B, int D1, int D2, int D3, int pad,
+                               int relu, hipStream_t st) {
     const int ovox = (D1 + 2 * pad - 2) * (D2 + 2 * pad - 2) * (D3 + 2 * pad - 2);
     return conv3d_mfma(x, y, w, bias, nullptr, B, D1, D2, D3, pad, RC, RC, relu, rams_waves_per_b(B, ovox), st);
 }
 
 // dx = conv_same(dy, flip-transpose(w)); ws: 27*32*32 + 32 floats
-int rams_conv3d_dgrad_same(float* dx, const float* dy, const float* w, int B, int D1, int D2, int D3, float* ws,
-                           hipStream_t st) {
+static int rams_conv3d_dgrad_same(float* dx, const float* dy, const float* w, int B, int D1, int D2, int D3, float* ws,
+                                  hipStream_t st) {
     float* wd = ws;
     float* zero_bias = ws + CONV_W_FLOATS;
     INR_HIP(hipMemsetAsync(zero_bias, 0, RC * sizeof(float), st));
@@ -1117,8 +1117,8 @@ int rams_conv3d_dgrad_same(float* dx, const float* dy, const float* w, int B, in
     return conv3d_mfma(dy, dx, wd, zero_bias, nullptr, B, D1, D2, D3, 1, RC, RC, 0, rams_waves_per_b(B, D1 * D2 * D3), st);
 }
 
-int rams_conv3d_wgrad(float* gw, float* gb, const float* x, const float* dy, int B, int D1, int D2, int D3, int pad, float* ws,
-                      hipStream_t st) {
+static int rams_conv3d_wgrad(float* gw, float* gb, const float* x, const float* dy, int B, int D1, int D2, int D3, int pad, float* ws,
+                             hipStream_t st) {
     Conv3dWgradParams p{};
     p.x = x; p.dy = dy; p.slab = ws;
     p.B = B; p.D1 = D1; p.D2 = D2; p.D3 = D3; p.pad = pad;
@@ -1178,8 +1178,8 @@ int rams_conv3d_wgrad_h3(float* gw, float* gb, const float* x, const float* dy, 
 }
 
 // stand-alone weight gradient (the C-ABI building block): the arithmetic debug key 14 selects, like the training step
-int rams_conv3d_wgrad_auto(float* gw, float* gb, const float* x, const float* dy, int B, int D1, int D2, int D3, int pad, float* ws,
-                           hipStream_t st) {
+static int rams_conv3d_wgrad_auto(float* gw, float* gb, const float* x, const float* dy, int B, int D1, int D2, int D3, int pad, float* ws,
+                                  hipStream_t st) {
     if (g_rams_h3 != 2 || !r3l_fits(D1, D2, D3) || B > WGRAD_BLOCKS_MAX) return rams_conv3d_wgrad(gw, gb, x, dy, B, D1, D2, D3, pad, ws, st);
     const long long nvox = (long long)B * (D1 + 2 * pad - 2) * (D2 + 2 * pad - 2) * (D3 + 2 * pad - 2);
     float* tail = ws + (rams_conv3d_wgrad_ws_floats(nvox > 0 ? nvox : 1) - (2 * R3_SLOT + 64));
@@ -1258,10 +1258,10 @@ static RamsFwdView rams_fwd_view(const inr_rams_desc_t* d, int B, int H, int W, 
     return v;
 }
 
-size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W) { return rams_fwd_view(d, B, H, W, nullptr).total / sizeof(float); }
+static size_t rams_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W) { return rams_fwd_view(d, B, H, W, nullptr).total / sizeof(float); }
 
-int rams_forward_impl(const inr_rams_desc_t* d, const float* params, const float* x, float* out, int B, int H, int W,
-                      int clip_round, void* workspace, size_t workspace_bytes, hipStream_t st) {
+static int rams_forward_impl(const inr_rams_desc_t* d, const float* params, const float* x, float* out, int B, int H, int W,
+                             int clip_round, void* workspace, size_t workspace_bytes, hipStream_t st) {
     const int T = d->channels, Cr = d->filters / d->r, S2 = d->scale * d->scale;
     const int Tr = T / d->r > 0 ? T / d->r : 1;
     const RamsFwdView v = rams_fwd_view(d, B, H, W, workspace);
@@ -1476,4 +1476,138 @@ int rams_forward_impl(const inr_rams_desc_t* d, const float* params, const float
 
 #include "rams_train.inc"
 
+// ---- what the entry points below check before they call in --------------------------------------------------------------------------------
+static int conv3d_dims_ok(int B, int D1, int D2, int D3, int pad) {
+    INR_REQUIRE(B >= 1 && B <= 65535 && D1 >= 1 && D2 >= 1 && D3 >= 1 && (pad == 0 || pad == 1), INR_E_INVALID,
+                "conv3d: bad shape (B=%d D=%dx%dx%d pad=%d)", B, D1, D2, D3, pad);
+    INR_REQUIRE(D1 + 2 * pad > 2 && D2 + 2 * pad > 2 && D3 + 2 * pad > 2, INR_E_INVALID, "conv3d: volume smaller than the kernel");
+    INR_REQUIRE((long long)B * D1 * D2 * D3 * 32 * 4 < (1ll << 40), INR_E_INVALID, "conv3d: volume too large");
+    // the kernels address one image through a 32-bit buffer window
+    INR_REQUIRE((long long)D1 * D2 * D3 * 32 * 4 < (1ll << 31), INR_E_INVALID, "conv3d: one image must stay below 2 GiB");
+    return 0;
+}
+
+static int check_rams(const inr_rams_desc_t* d) {
+    INR_REQUIRE(d != nullptr, INR_E_INVALID, "rams descriptor is null");
+    INR_REQUIRE(d->filters == 32 && d->kernel_size == 3, INR_E_INVALID,
+                "rams kernels need filters == 32 and kernel_size == 3 (got %d, %d)", d->filters, d->kernel_size);
+    INR_REQUIRE(d->scale >= 1 && d->scale * d->scale <= 32 && d->r >= 1 && d->filters / d->r >= 1 &&
+                    d->filters / d->r <= 8 && d->n_rfab >= 0,
+                INR_E_INVALID, "bad rams descriptor (scale=%d r=%d N=%d)", d->scale, d->r, d->n_rfab);
+    INR_REQUIRE(d->channels >= 3 && d->channels <= 32 && d->channels - 2 * (d->channels / 3) == 3, INR_E_INVALID,
+                "rams: channels must leave a temporal depth of 3 before the head (channels=%d)", d->channels);
+    return 0;
+}
+
+static int check_rams_train(const inr_rams_desc_t* desc, int B, int H, int W) {
+    INR_REQUIRE(desc != nullptr, INR_E_INVALID, "rams descriptor is null");
+    INR_REQUIRE(desc->filters == 32 && desc->kernel_size == 3 && desc->channels == 9 && desc->scale >= 1 && desc->scale <= 5 &&
+                    desc->r >= 1 && desc->n_rfab >= 0,
+                INR_E_INVALID, "rams train: supported configuration is filters 32, kernel 3, channels 9");
+    INR_REQUIRE(B >= 1 && H >= 3 && W >= 3 && H == W, INR_E_INVALID,
+                "rams train: batch >= 1 and square low-resolution patches (the loss of utils/loss.py works on squares)");
+    return 0;
+}
+
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+int64_t inr_rams_param_count(const inr_rams_desc_t* desc) {
+    if (check_rams(desc)) return INR_E_INVALID;
+    return rams_param_floats(desc);
+}
+
+size_t inr_rams_workspace_bytes(const inr_rams_desc_t* desc, int batch, int height, int width) {
+    if (check_rams(desc) || batch < 1 || height < 3 || width < 3) return 0;
+    return rams_workspace_floats(desc, batch, height, width) * sizeof(float);
+}
+
+int inr_rams_forward(const inr_rams_desc_t* desc, const float* params, const float* x, float* out, int batch, int height,
+                     int width, int clip_round, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = check_rams(desc)) return rc;
+    INR_REQUIRE(params && x && out, INR_E_INVALID, "inr_rams_forward: null pointer");
+    INR_REQUIRE(batch >= 1 && batch <= 65535 && height >= 3 && width >= 3, INR_E_INVALID,
+                "inr_rams_forward: bad sizes (B=%d H=%d W=%d)", batch, height, width);
+    INR_REQUIRE((long long)(height + 4) * (width + 4) * desc->channels * 32 * 4 < (1ll << 31), INR_E_INVALID,
+                "inr_rams_forward: one image's activations must stay below 2 GiB");
+    return rams_forward_impl(desc, params, x, out, batch, height, width, clip_round, workspace, workspace_bytes,
+                             (hipStream_t)stream);
+}
+
+int inr_rams_conv3d_forward(float* y, const float* x, const float* w, const float* bias, int B, int D1, int D2, int D3, int pad,
+                            int relu, void* stream) {
+    INR_REQUIRE(y && x && w && bias, INR_E_INVALID, "inr_rams_conv3d_forward: null pointer");
+    if (int rc = conv3d_dims_ok(B, D1, D2, D3, pad)) return rc;
+    INR_REQUIRE(aligned16(x) && aligned16(w), INR_E_ALIGN, "inr_rams_conv3d_forward: x / w must be 16-byte aligned");
+    return rams_conv3d_forward(y, x, w, bias, B, D1, D2, D3, pad, relu, (hipStream_t)stream);
+}
+
+size_t inr_rams_conv3d_dgrad_workspace_bytes(void) { return (27 * 32 * 32 + 64) * sizeof(float); }
+
+int inr_rams_conv3d_dgrad(float* dx, const float* dy, const float* w, int B, int D1, int D2, int D3, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(dx && dy && w, INR_E_INVALID, "inr_rams_conv3d_dgrad: null pointer");
+    if (int rc = conv3d_dims_ok(B, D1, D2, D3, 1)) return rc;
+    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_conv3d_dgrad_workspace_bytes(), INR_E_WORKSPACE,
+                "inr_rams_conv3d_dgrad: workspace too small");
+    INR_REQUIRE(aligned16(dy) && aligned16(workspace), INR_E_ALIGN, "inr_rams_conv3d_dgrad: dy / workspace must be 16-byte aligned");
+    return rams_conv3d_dgrad_same(dx, dy, w, B, D1, D2, D3, (float*)workspace, (hipStream_t)stream);
+}
+
+size_t inr_rams_conv3d_wgrad_workspace_bytes(int B, int D1, int D2, int D3, int pad) {
+    const long long nvox = (long long)B * (D1 + 2 * pad - 2) * (D2 + 2 * pad - 2) * (D3 + 2 * pad - 2);
+    return rams_conv3d_wgrad_ws_floats(nvox > 0 ? nvox : 1) * sizeof(float);
+}
+
+int inr_rams_conv3d_wgrad(float* gw, float* gb, const float* x, const float* dy, int B, int D1, int D2, int D3, int pad,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(gw && x && dy, INR_E_INVALID, "inr_rams_conv3d_wgrad: null pointer");
+    if (int rc = conv3d_dims_ok(B, D1, D2, D3, pad)) return rc;
+    INR_REQUIRE(workspace && workspace_bytes >= inr_rams_conv3d_wgrad_workspace_bytes(B, D1, D2, D3, pad), INR_E_WORKSPACE,
+                "inr_rams_conv3d_wgrad: workspace too small");
+    INR_REQUIRE(aligned16(x) && aligned16(dy), INR_E_ALIGN, "inr_rams_conv3d_wgrad: x / dy must be 16-byte aligned");
+    return rams_conv3d_wgrad_auto(gw, gb, x, dy, B, D1, D2, D3, pad, (float*)workspace, (hipStream_t)stream);
+}
+
+// ---- a-15 / (f)-4: RAMS training step ------------------------------------------------------------------------------------------
+int64_t inr_rams_train_param_count(const inr_rams_desc_t* desc) {
+    if (!desc) return INR_E_INVALID;
+    return rams_train_param_floats(desc);
+}
+
+int inr_rams_train_param_offsets(const inr_rams_desc_t* desc, int64_t* offsets, int max_layers) {
+    INR_REQUIRE(desc && offsets, INR_E_INVALID, "inr_rams_train_param_offsets: null pointer");
+    return rams_train_param_offsets(desc, offsets, max_layers);
+}
+
+size_t inr_rams_train_workspace_bytes(const inr_rams_desc_t* desc, int batch, int height, int width) {
+    if (!desc || batch < 1 || height < 3 || width < 3) return 0;
+    return rams_train_workspace_floats(desc, batch, height, width) * sizeof(float);
+}
+
+int inr_rams_train_grads(const inr_rams_desc_t* desc, const float* params, float* grads, const float* x, const float* y_true,
+                         const float* mask, double* loss, float* pred, int batch, int height, int width, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+    if (int rc = check_rams_train(desc, batch, height, width)) return rc;
+    INR_REQUIRE(params && grads && x && y_true && mask && loss, INR_E_INVALID, "inr_rams_train_grads: null pointer");
+    return rams_train_grads(desc, params, grads, x, y_true, mask, loss, pred, batch, height, width, workspace, workspace_bytes,
+                            (hipStream_t)stream);
+}
+
+int inr_rams_train_step(const inr_rams_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x,
+                        const float* y_true, const float* mask, double* loss, int batch, int height, int width, int64_t step,
+                        double lr, double beta1, double beta2, double eps, void* workspace, size_t workspace_bytes, void* stream) {
+    INR_REQUIRE(m && v && step >= 1, INR_E_INVALID, "inr_rams_train_step: Adam state missing or step < 1");
+    if (int rc = inr_rams_train_grads(desc, params, grads, x, y_true, mask, loss, nullptr, batch, height, width, workspace,
+                                      workspace_bytes, stream))
+        return rc;
+    // Keras Adam: p -= lr sqrt(1 - b2^t) / (1 - b1^t) * m / (sqrt(v) + eps)  ==  the kernel's form with eps / sqrt(1 - b2^t)
+    const double bc2 = 1.0 - pow(beta2, (double)step);
+    return launch_adam(params, grads, m, v, rams_train_param_floats(desc), step, lr, beta1, beta2, eps / sqrt(bc2),
+                       (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -597,16 +597,16 @@ static RamsTrainView rams_train_view(const inr_rams_desc_t* d, int B, int H, int
     return v;
 }
 
-size_t rams_train_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W) {
+static size_t rams_train_workspace_floats(const inr_rams_desc_t* d, int B, int H, int W) {
     return rams_train_view(d, B, H, W, nullptr).total / sizeof(float);
 }
 
 // ---- the step ---------------------------------------------------------------------------------------------------------------------
 // One forward + loss + backward.  raw: parameters (raw layout); raw_grad: receives d(sum_b loss_b)/d raw.  loss: [B] doubles.
 // pred (nullable): receives the un-clipped prediction [B][sH][sW].
-int rams_train_grads(const inr_rams_desc_t* d, const float* raw, float* raw_grad, const float* x, const float* y_true,
-                     const float* mask, double* loss, float* pred_out, int B, int H, int W, void* workspace, size_t workspace_bytes,
-                     hipStream_t st) {
+static int rams_train_grads(const inr_rams_desc_t* d, const float* raw, float* raw_grad, const float* x, const float* y_true,
+                            const float* mask, double* loss, float* pred_out, int B, int H, int W, void* workspace, size_t workspace_bytes,
+                            hipStream_t st) {
     const TrainDims t = train_dims(d, B, H, W);
     const int T = t.T, Cr = t.Cr, Tr = t.Tr, S2 = t.S2, s = d->scale, nred = T / 3;
     INR_REQUIRE(d->filters == RC && d->kernel_size == 3 && T == 9 && s * s <= RC, INR_E_INVALID,
@@ -1016,7 +1016,7 @@ int rams_train_grads(const inr_rams_desc_t* d, const float* raw, float* raw_grad
     return 0;
 }
 
-long long rams_train_param_floats(const inr_rams_desc_t* d) {
+static long long rams_train_param_floats(const inr_rams_desc_t* d) {
     std::vector<TLayer> L;
     long long raw_total, fold_total;
     rams_train_layers(d, L, &raw_total, &fold_total);
@@ -1024,7 +1024,7 @@ long long rams_train_param_floats(const inr_rams_desc_t* d) {
 }
 
 // offsets[3 l .. 3 l + 2] = (v, g, b) of layer l; returns the number of layers (negative: buffer too small)
-int rams_train_param_offsets(const inr_rams_desc_t* d, int64_t* offsets, int max_layers) {
+static int rams_train_param_offsets(const inr_rams_desc_t* d, int64_t* offsets, int max_layers) {
     std::vector<TLayer> L;
     long long raw_total, fold_total;
     rams_train_layers(d, L, &raw_total, &fold_total);

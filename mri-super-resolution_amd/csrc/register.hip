@@ -307,10 +307,8 @@ int inr_masked_xcorr(double* shifts, double* peak, int* n_max, double* map, cons
     if (int rc = xcorr_check("inr_masked_xcorr", n_sets, T, height, width, max_dy, max_dx)) return rc;
     INR_REQUIRE(overlap_ratio >= 0.0 && overlap_ratio <= 1.0, INR_E_INVALID, "inr_masked_xcorr: overlap_ratio must lie in [0, 1] (got %g)",
                 overlap_ratio);
-    const size_t need = xcorr_doubles(n_sets, T, max_dy, max_dx);
-    INR_REQUIRE(workspace && workspace_doubles >= 0 && (size_t)workspace_doubles >= need, INR_E_WORKSPACE,
-                "inr_masked_xcorr: workspace too small (%lld doubles, %zu needed)", workspace ? (long long)workspace_doubles : 0ll, need);
-    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "inr_masked_xcorr: workspace must be 16-byte aligned");
+    const size_t need = xcorr_doubles(n_sets, T, max_dy, max_dx) * sizeof(double);
+    if (int rc = check_ws_doubles("inr_masked_xcorr", workspace, workspace_doubles, need)) return rc;
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(KC_OTHER, st);
     const int nimg = n_sets * T;
@@ -333,10 +331,8 @@ int inr_shift2d(float* out, const float* in, const double* shifts, int n_images,
                 double* workspace, int64_t workspace_doubles, void* stream) {
     INR_REQUIRE(out && in && shifts, INR_E_INVALID, "inr_shift2d: null pointer");
     if (int rc = shift_check("inr_shift2d", n_images, height, width, mode, cval)) return rc;
-    const int64_t need = inr_shift2d_workspace_doubles(n_images, height, width, mode);
-    INR_REQUIRE(workspace && workspace_doubles >= need, INR_E_WORKSPACE, "inr_shift2d: workspace too small (%lld doubles, %lld needed)",
-                workspace ? (long long)workspace_doubles : 0ll, (long long)need);
-    INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "inr_shift2d: workspace must be 16-byte aligned");
+    const size_t need = (size_t)inr_shift2d_workspace_doubles(n_images, height, width, mode) * sizeof(double);
+    if (int rc = check_ws_doubles("inr_shift2d", workspace, workspace_doubles, need)) return rc;
     if (n_images == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(KC_OTHER, st);

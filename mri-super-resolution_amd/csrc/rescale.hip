@@ -22,7 +22,10 @@
 namespace inr {
 namespace {
 
+constexpr int RESCALE_MAX_RADIUS = INR_RESCALE_MAX_RADIUS;   // Gaussian taps per side that the kernel arguments carry
+constexpr int RESCALE_MAX_LINE = INR_RESCALE_MAX_LINE;       // one padded line, staged in LDS as doubles, fits 64 KiB
 constexpr int RS_PAD = 12;   // scipy: _prepad_for_spline_filter
+struct RescaleView { double *filtered, *coef, *minmax; size_t total; };
 
 __device__ __forceinline__ int rs_index(int i, int n, int mode) {
     if (mode == INR_RESCALE_EDGE) return i < 0 ? 0 : (i > n - 1 ? n - 1 : i);
@@ -143,8 +146,6 @@ bool rs_taps(RsTaps& t, int n_in, int n_out, int anti_aliasing) {
 
 int rs_pad_of(int order, int mode) { return order == 3 && mode == INR_RESCALE_EDGE ? RS_PAD : 0; }
 
-}  // namespace
-
 // the workspace: the filtered plane, the (padded) coefficient plane -- which first serves as the buffer between the two Gaussian
 // passes -- and one (min, max) pair per image (an upper bound on the number of clip groups).  base == null: `total` only
 RescaleView rescale_view(int nimg, int H, int W, int order, int mode, void* base) {
@@ -214,4 +215,27 @@ int launch_rescale2d(float* out, const float* in, int nimg, int H, int W, int OH
     return 0;
 }
 
+}  // namespace
 }  // namespace inr
+
+using namespace inr;
+
+extern "C" {
+
+int64_t inr_rescale2d_workspace_doubles(int n_images, int height, int width, int order, int mode) {
+    if (rescale_check("inr_rescale2d_workspace_doubles", n_images, height, width, 1, 1, order, mode, 0, 0)) return 0;
+    return (int64_t)(rescale_view(n_images, height, width, order, mode, nullptr).total / sizeof(double));
+}
+
+int inr_rescale2d(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width, int order,
+                  int mode, int anti_aliasing, int clip_group, double* workspace, int64_t workspace_doubles, void* stream) {
+    INR_REQUIRE(out && in, INR_E_INVALID, "inr_rescale2d: null pointer");
+    if (int rc = rescale_check("inr_rescale2d", n_images, height, width, out_height, out_width, order, mode, anti_aliasing, clip_group))
+        return rc;
+    const RescaleView v = rescale_view(n_images, height, width, order, mode, workspace);
+    if (int rc = check_ws_doubles("inr_rescale2d", workspace, workspace_doubles, v.total)) return rc;
+    return launch_rescale2d(out, in, n_images, height, width, out_height, out_width, order, mode, anti_aliasing, clip_group, v,
+                            (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -527,11 +527,15 @@ int wire_pack(const WirePlan& p, const WireView& v, const float* params, bool tr
 
 }  // namespace
 
-// ---- launchers other units may call (internal.h) ---------------------------------------------------------------------------
+// ---- the launcher wire_deriv.hip calls (internal.h) ---------------------------------------------------------------------------
 int wire_pack_images(const WirePlan& p, float* const* img, float* const* pb, const float* params, hipStream_t st) {
     return wire_pack_layers(p, img, nullptr, pb, params, st);
 }
 
+namespace {
+
+// in [n][K] (K a multiple of 32) times the block image img [Q][H][K] (Q = 2 for the real first layer, else 4), Gabor epilogue:
+// out [n][2H] = [out_r | out_i]; stash (nullable) [n][Q H] receives lin_r (, lin_i), orth_r (, orth_i)
 int wire_gabor_forward(float* out, float* stash, const float* in, const float* img, const float* pb, int K, int H, int first,
                        int64_t n, float omega, float s2, hipStream_t st) {
     const dim3 grid((unsigned)((n + WIRE_BM - 1) / WIRE_BM), (unsigned)((H + WIRE_BN - 1) / WIRE_BN));
@@ -545,6 +549,7 @@ int wire_gabor_forward(float* out, float* stash, const float* in, const float* i
     return 0;
 }
 
+// G [n][2H] = dZ [n][4H] times the image, read through its transpose imgT [2H][4H]
 int wire_input_grad(float* G, const float* dZ, const float* imgT, int H, int64_t n, hipStream_t st) {
     const dim3 grid((unsigned)((n + WIRE_BM - 1) / WIRE_BM), (unsigned)(2 * H / WIRE_BN));
     hipLaunchKernelGGL((wire_gemm_kernel<1, WIRE_EPI_STORE>), grid, dim3(WIRE_THREADS), 0, st, G, (float*)nullptr, dZ, imgT,
@@ -553,6 +558,7 @@ int wire_input_grad(float* G, const float* dZ, const float* imgT, int H, int64_t
     return 0;
 }
 
+// dx [n][in_f] (unpadded, any in_f) = dZ0 [n][2H] times the real layer-0 image, read through its transpose imgT0 [in_f][2H]
 int wire_first_input_grad(float* dx, const float* dZ0, const float* imgT0, int in_f, int H, int64_t n, hipStream_t st) {
     const dim3 grid((unsigned)((n + WIRE_BM - 1) / WIRE_BM), (unsigned)((in_f + WIRE_BN - 1) / WIRE_BN));
     hipLaunchKernelGGL((wire_gemm_kernel<1, WIRE_EPI_STORE>), grid, dim3(WIRE_THREADS), 0, st, dx, (float*)nullptr, dZ0, imgT0,
@@ -561,6 +567,7 @@ int wire_first_input_grad(float* dx, const float* dZ0, const float* imgT0, int i
     return 0;
 }
 
+// slabs [splits][R][C] = per-split dZ^T X and bslab [splits][R] = per-split column sums of dZ (dZ [n][R], X [n][C])
 int wire_param_grad_slabs(float* slabs, float* bslab, const float* dZ, int R, const float* X, int C, int64_t n, hipStream_t st) {
     const int S = wire_splits(n);
     hipLaunchKernelGGL(wire_pgrad_kernel, dim3((unsigned)(R / 64), (unsigned)((C + 63) / 64), (unsigned)S), dim3(WIRE_THREADS), 0,
@@ -571,8 +578,6 @@ int wire_param_grad_slabs(float* slabs, float* bslab, const float* dZ, int R, co
     INR_LAUNCH_CHECK();
     return 0;
 }
-
-namespace {
 
 // rows already in v.x0.  training: stash everything, result in v.y; else ping-pong and write y_out (with the clamp)
 int wire_forward_layers(const inr_wire_desc_t* d, const WirePlan& p, const WireView& v, const float* params, int64_t n,
