@@ -292,6 +292,38 @@ int inr_siren_forward_train(const inr_siren_desc_t* desc, const float* params, c
 int inr_siren_backward_train(const inr_siren_desc_t* desc, const float* params, float* grads, const float* gy, int64_t n,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* (g) the voxel-footprint forward model (csrc/footprint.hip): a datum is not a point sample of the network but a
+ * weighted average over K sub-sample positions x_i + delta_k,
+ *     p_i = sum_k fw[k] y[i K + k],   loss = inv_count sum_i wt_i (p_i - t_i)^2,   inv_count = 1 / (count_total ? count_total : n).
+ * Sub-sample k of datum i is row i K + k (sub-sample minor) everywhere.  Limits: 1 <= K <= INR_FOOTPRINT_MAX_SAMPLES, 1 <= d <= 4,
+ * n >= 1, n K below 2^31 - 256 (the rows of one GEMM call).  Everything is validated before any device work: null pointer or bad
+ * n / K / d INR_E_INVALID, short workspace INR_E_WORKSPACE, misaligned workspace / params / grads / x_sub INR_E_ALIGN.  Workspaces
+ * are counted in floats.  All entries only enqueue; none uses float atomics, so repeated calls are bit-equal.
+ *   expand     out[(i K + k) d + a] = x[i d + a] + offsets[k d + a]: one fp32 addition (features then come from the Fourier map of a-3)
+ *   reduce     pred[i] = p_i, ONE fma chain over ascending k starting from 0
+ *   loss_grad  p_i by that same chain (the same bits; stored to `pred` when it is not null), r = p_i - t_i,
+ *              gy[i K + k] = fw[k] (2 wt_i r inv_count) (wt null: 1), *loss = inv_count sum_i wt_i r^2 from per-block partials in a fixed
+ *              grid.  count_total (0 = n, else >= n): the divisor when the call sees one row shard of a larger fit, as in (e).
+ *              Workspace: the planner's floats, 16-byte aligned.
+ *   fit        n_steps full-batch Adam steps enqueued by one call, no host read.  x_sub [n K][in_features] are the features of the
+ *              sub-samples, target / weight (nullable) [n], fw [K].  Per step: the training forward of (f) on the n K rows (the first
+ *              step of EVERY call re-images x_sub, later steps of the call keep the image), loss_grad, the backward of (f),
+ *              the Adam step of inr_adam_step with step number first_step + it (first_step >= 1).  losses (nullable) [n_steps].
+ *              Served: exactly what inr_siren_hp_eligible(desc) serves, asked per call (it depends on the diagnostic switches);
+ *              anything else is INR_E_INVALID, and the planner returns 0 for it (as for a bad n / K).
+ *              Workspace, every region 16-byte aligned: the fit workspace of n K rows | y [n K] | gy [n K] | the loss partials. */
+#define INR_FOOTPRINT_MAX_SAMPLES 64
+int inr_footprint_expand(float* out, const float* x, const float* offsets, int64_t n, int d, int K, void* stream);
+int inr_footprint_reduce(float* pred, const float* y, const float* fw, int64_t n, int K, void* stream);
+int64_t inr_footprint_loss_workspace_floats(int64_t n);
+int inr_footprint_loss_grad(float* gy, float* loss, float* pred, const float* y, const float* t, const float* wt, const float* fw,
+                            int64_t n, int K, int64_t count_total, void* workspace, int64_t workspace_floats, void* stream);
+int64_t inr_siren_fit_footprint_workspace_floats(const inr_siren_desc_t* desc, int64_t n, int K);
+int inr_siren_fit_footprint(const inr_siren_desc_t* desc, float* params, float* grads, float* m, float* v, const float* x_sub,
+                            const float* target, const float* weight, const float* fw, int64_t n, int K, int64_t first_step,
+                            int n_steps, double lr, double beta1, double beta2, double eps, float* losses, void* workspace,
+                            int64_t workspace_floats, void* stream);
+
 /* ---- a-12: end-of-fit metrics on the device (fp64 accumulation, fixed-order reductions) -----------------
  * workspace for all three image metrics: inr_metric_workspace_bytes(n_images).
  * inr_psnr:   out[b] (double) = 10*log10(data_range^2 / mean((x_b - y_b)^2)); x, y are [n_images][per_image] fp32.

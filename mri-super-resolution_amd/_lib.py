@@ -169,6 +169,15 @@ SIGNATURES = {
                                           c_stream]),
     "inr_siren_backward_train": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_size_t,
                                            c_stream]),
+    "inr_footprint_expand": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
+    "inr_footprint_reduce": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
+    "inr_footprint_loss_workspace_floats": (C.c_int64, [C.c_int64]),
+    "inr_footprint_loss_grad": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int64,
+                                          C.c_void_p, C.c_int64, c_stream]),
+    "inr_siren_fit_footprint_workspace_floats": (C.c_int64, [C.POINTER(SirenDesc), C.c_int64, C.c_int]),
+    "inr_siren_fit_footprint": (C.c_int, [C.POINTER(SirenDesc), c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                          C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                          c_f32p, C.c_void_p, C.c_int64, c_stream]),
     "inr_rams_shift_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "inr_rams_shift_loss": (C.c_int, [C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_void_p, C.c_size_t, c_stream]),

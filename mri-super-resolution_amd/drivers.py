@@ -26,6 +26,8 @@ import torch
 
 from . import dist as inr_dist
 from . import matio, metrics, ops
+from .footprint import (Footprint, FootprintSirenFitter, block_centres, block_footprint, block_means, footprint_forward,
+                        footprint_inputs)
 from .inr import PN, ImageFitting_set, ShardedSirenFitter, Siren, SirenFitter, fit_cycle_batch, input_mapping, reconstruct
 
 
@@ -95,7 +97,8 @@ def fit_volume(volume: np.ndarray, steps: int = 2500, *, seed: Optional[int] = 0
 def _fit_volume_once(volume: np.ndarray, steps: int = 2500, hidden_features: int = 512, hidden_layers: int = 3,
                      mapping_size: int = 128, ff_scale: float = 0.5, lr: float = 1e-4, seed: Optional[int] = 0,
                      downsample: bool = True, upscale_axes: int = 2, evaluate: bool = True, chunk_steps: int = 250,
-                     return_recon: bool = True, normalize: bool = True, group=None, _poison: bool = False) -> Dict[str, object]:
+                     return_recon: bool = True, normalize: bool = True, group=None, _poison: bool = False,
+                     lr_model: str = "decimate", footprint=None) -> Dict[str, object]:
     """One INR super-resolution fit of an N-D volume (first ``upscale_axes`` axes are in-plane).
 
     ``downsample=True``: the volume is the HR ground truth, training uses ``vol[::2, ::2, ...]`` and the result is
@@ -104,13 +107,37 @@ def _fit_volume_once(volume: np.ndarray, steps: int = 2500, hidden_features: int
     ``group``: a process group whose ranks fit this ONE volume together, each on its contiguous share of the rows
     (``ShardedSirenFitter``); every member ends with identical weights, only the group's first rank re-samples and
     evaluates (the others return timings and the final loss).
+    ``lr_model``: how the training data come from the HR volume.  "decimate" (default): every second sample.  "average" (needs
+    ``downsample=True`` and even up-scaled axes): the mean of every 2 x ... block over the up-scaled axes, placed at the block
+    centres in the HR grid's ``get_mgrid`` frame, so that the evaluation on ``hr_shape`` is aligned with the data.
+    ``footprint``: the forward model of a datum (``footprint.py``).  None (default): a point sample.  "box" (with "average"): the
+    block itself, ``Footprint.box`` 2 HR steps wide with 2 samples on every up-scaled axis.  A ``Footprint``: the caller's own rule
+    in the coordinates of the training grid (e.g. a Gaussian slice profile along z with ``downsample=False``).  With either
+    argument the result gains ``lr_model``, ``footprint_samples`` (K) and ``lr_consistency_psnr_db`` (the forward model's
+    prediction against the training data, data range 1).  A footprint cannot be combined with ``group``.
     """
+    if lr_model not in ("decimate", "average"):
+        raise ValueError(f"lr_model must be 'decimate' or 'average' (got {lr_model!r})")
+    if footprint is not None and not isinstance(footprint, Footprint) and footprint != "box":
+        raise ValueError(f"footprint must be None, 'box' or a Footprint (got {footprint!r})")
+    if footprint is not None and group is not None:
+        raise ValueError("a footprint fit cannot be shared by a rank group (group=): the sharded fitter is point-sampled")
+    if isinstance(footprint, str) and lr_model != "average":
+        raise ValueError("footprint='box' is the 2 x ... block of lr_model='average'")
     vol = np.ascontiguousarray(volume, dtype=np.float32)
     vmax = float(vol.max()) if normalize else 1.0       # superresHybrid normalises per (b, TE) before stacking (:57-63)
     vol = np.ascontiguousarray(vol / vmax)                                                     # superresDWI.py:50-55
     sl = tuple(slice(None, None, 2) if a < upscale_axes else slice(None) for a in range(vol.ndim))
     lr_vol = np.ascontiguousarray(vol[sl]) if downsample else vol
     hr_shape = vol.shape
+    if lr_model == "average":
+        if not downsample or any(s % 2 for s in hr_shape[:upscale_axes]):
+            raise ValueError("lr_model='average' needs downsample=True and even up-scaled axes")
+        lr_vol = block_means(vol, upscale_axes)
+    if isinstance(footprint, str):
+        footprint = block_footprint(hr_shape, upscale_axes)
+    if footprint is not None and footprint.dim != vol.ndim:
+        raise ValueError(f"the footprint has {footprint.dim} axes, the volume {vol.ndim}")
     test_shape = tuple(2 * s if a < upscale_axes else s for a, s in enumerate(hr_shape))
     # (seeding torch's global generator and drawing the weights from it is one critical section: `run_volumes(concurrent=k)` runs
     #  several fits of this process at once, and each must get the weights its seed gives a fit that runs alone)
@@ -134,11 +161,17 @@ def _fit_volume_once(volume: np.ndarray, steps: int = 2500, hidden_features: int
             torch.distributed.broadcast(Bh, src=src, group=group)
             B.copy_(Bh)
         model = Siren(2 * mapping_size, hidden_features, hidden_layers, 1).cuda()      # (the draw order of a shared fit: B, broadcast, weights)
-    data = ImageFitting_set([lr_vol])
-    model_input = input_mapping(data.coords[0], B)                        # built once per fit (superresDWI.py:122)
-    pixels = data.pixels[0]
+    if lr_model == "average":
+        coords = block_centres(hr_shape, upscale_axes)      # (in the HR grid's frame, not get_mgrid(lr_shape))
+        pixels = torch.from_numpy(lr_vol).cuda().reshape(-1, 1)
+    else:
+        data = ImageFitting_set([lr_vol])
+        coords, pixels = data.coords[0], data.pixels[0]
+    # built once per fit (superresDWI.py:122)
+    model_input = input_mapping(coords, B) if footprint is None else footprint_inputs(coords, B, footprint)
     if _poison:
         pixels = pixels * float("nan")
+    data_pixels = pixels        # (all of them: a shared fit trains on its slice)
     g_size = torch.distributed.get_world_size(group) if group is not None else 1
     g_rank = torch.distributed.get_rank(group) if group is not None else 0
     torch.cuda.current_stream().synchronize()      # (this fit's stream: fits may run side by side)
@@ -148,6 +181,8 @@ def _fit_volume_once(volume: np.ndarray, steps: int = 2500, hidden_features: int
         lo, hi = n_rows * g_rank // g_size, n_rows * (g_rank + 1) // g_size
         model_input, pixels = model_input[lo:hi].contiguous(), pixels[lo:hi].contiguous()
         fitter = ShardedSirenFitter(model, global_rows=n_rows, lr=lr, group=group)
+    elif footprint is not None:
+        fitter = FootprintSirenFitter(model, footprint, lr=lr)
     else:
         fitter = SirenFitter(model, lr=lr)
     losses = []
@@ -175,6 +210,11 @@ def _fit_volume_once(volume: np.ndarray, steps: int = 2500, hidden_features: int
         "e2e_voxels_per_s": recon.numel() / (t_fit + t_rec), "final_loss": float(torch.cat(losses)[-1]) if steps else None,
         "first_loss": float(losses[0][0]) if steps else None, "test_shape": test_shape, "scale_back": vmax,
     }
+    if lr_model != "decimate" or footprint is not None:
+        fp = footprint if footprint is not None else Footprint.point(vol.ndim)
+        out["lr_model"], out["footprint_samples"] = lr_model, fp.count
+        pred = footprint_forward(model, coords, B, fp)
+        out["lr_consistency_psnr_db"] = float(metrics.psnr(data_pixels.reshape(1, -1), pred.reshape(1, -1), 1.0))
     if evaluate and downsample:
         hr = torch.from_numpy(vol).cuda()
         sr = reconstruct(model, hr_shape, B)                             # SR_recon on the HR grid (superresDWI.py:162)

@@ -388,6 +388,7 @@ class SirenFitter(AdamOwner):
     Adam state (``m``, ``v``, step count) lives here, which is what lets a fit be continued or
     interleaved with other phases (superresDWI.py:139-156).
     """
+    batch_ok = True      # ``fit_cycle_batch`` may step this fitter's buffers itself (a subclass with a loss of its own says False)
 
     def __init__(self, model: Siren, lr=1e-4, betas=(0.9, 0.999), eps=1e-8):
         ops.require_gpu()
@@ -463,6 +464,9 @@ def fit_cycle_batch(fitters, model_input, targets, n_steps, weights=None, first_
     for f in fitters:
         if isinstance(f, ShardedSirenFitter):
             raise TypeError("fit_cycle_batch takes SirenFitter objects (a sharded fit steps through its own collectives)")
+        if not f.batch_ok:
+            raise TypeError(f"fit_cycle_batch steps point-sampled SirenFitter objects; a {type(f).__name__} steps through its own "
+                            "entry point")
         f._check_views()
     f0 = fitters[0]
 

@@ -617,6 +617,105 @@ def siren_backward_train(desc: SirenDesc, params, grads, gy, workspace):
     return grads
 
 
+# ---- the voxel-footprint forward model (include/inrhip.h (g)) ------------------------------------------------------------------
+FOOTPRINT_MAX_SAMPLES = 64      # INR_FOOTPRINT_MAX_SAMPLES
+
+
+def _chk_footprint_weights(fw) -> int:
+    _chk(fw, "footprint weights")
+    if fw.dim() != 1 or not 1 <= fw.numel() <= FOOTPRINT_MAX_SAMPLES:
+        raise ValueError(f"footprint weights {tuple(fw.shape)} must be [K], 1 <= K <= {FOOTPRINT_MAX_SAMPLES}")
+    return fw.numel()
+
+
+def _chk_footprint_data(n, target, weight):
+    _chk(target, "target")
+    if target.numel() != n:
+        raise ValueError(f"target has {target.numel()} elements, expected one per datum ({n})")
+    if weight is not None:
+        _chk(weight, "weight")
+        if weight.numel() != n:
+            raise ValueError(f"weight has {weight.numel()} elements, expected one per datum ({n})")
+
+
+def footprint_expand(x: torch.Tensor, offsets: torch.Tensor) -> torch.Tensor:
+    """``inr_footprint_expand``: ``x`` [n, d] and ``offsets`` [K, d] -> [n*K, d], row ``i*K + k`` = ``x[i] + offsets[k]``."""
+    _chk(x, "x")
+    _chk(offsets, "offsets")
+    if x.dim() != 2 or offsets.dim() != 2 or x.shape[1] != offsets.shape[1] or not 1 <= x.shape[1] <= 4:
+        raise ValueError(f"x {tuple(x.shape)} and offsets {tuple(offsets.shape)} must be [n,d] and [K,d], 1 <= d <= 4")
+    n, d = x.shape
+    K = offsets.shape[0]
+    if not 1 <= K <= FOOTPRINT_MAX_SAMPLES:
+        raise ValueError(f"a footprint has 1 .. {FOOTPRINT_MAX_SAMPLES} sub-samples (got {K})")
+    out = torch.empty((n * K, d), dtype=torch.float32, device=x.device)
+    if n == 0:
+        return out
+    check(lib().inr_footprint_expand(out.data_ptr(), x.data_ptr(), offsets.data_ptr(), n, d, K, _stream()), "inr_footprint_expand")
+    return out
+
+
+def footprint_reduce(y: torch.Tensor, fw: torch.Tensor) -> torch.Tensor:
+    """``inr_footprint_reduce``: ``y`` (n*K elements, sub-sample minor) and the weights ``fw`` [K] -> ``pred`` [n]."""
+    _chk(y, "y")
+    K = _chk_footprint_weights(fw)
+    if y.numel() % K:
+        raise ValueError(f"y has {y.numel()} elements, no multiple of K = {K}")
+    n = y.numel() // K
+    pred = torch.empty(n, dtype=torch.float32, device=y.device)
+    if n == 0:
+        return pred
+    check(lib().inr_footprint_reduce(pred.data_ptr(), y.data_ptr(), fw.data_ptr(), n, K, _stream()), "inr_footprint_reduce")
+    return pred
+
+
+def footprint_loss_grad(y, target, weight, fw, count_total: int = 0, want_pred: bool = False):
+    """``inr_footprint_loss_grad``: returns (gy [n*K], loss [1], pred [n] or None) of the footprint-averaged, weighted MSE."""
+    _chk(y, "y")
+    K = _chk_footprint_weights(fw)
+    if y.numel() == 0 or y.numel() % K:
+        raise ValueError(f"y has {y.numel()} elements, no positive multiple of K = {K}")
+    n = y.numel() // K
+    _chk_footprint_data(n, target, weight)
+    gy = torch.empty(n * K, dtype=torch.float32, device=y.device)
+    loss = torch.empty(1, dtype=torch.float32, device=y.device)
+    pred = torch.empty(n, dtype=torch.float32, device=y.device) if want_pred else None
+    floats = int(lib().inr_footprint_loss_workspace_floats(n))
+    ws = _ws(4 * floats, y.device)
+    check(lib().inr_footprint_loss_grad(gy.data_ptr(), loss.data_ptr(), _ptr(pred), y.data_ptr(), target.data_ptr(), _ptr(weight),
+                                        fw.data_ptr(), n, K, int(count_total), ws.data_ptr(), _nbytes(ws) // 4, _stream()),
+          "inr_footprint_loss_grad")
+    return gy, loss, pred
+
+
+def siren_fit_footprint_workspace_floats(desc: SirenDesc, n: int, K: int) -> int:
+    """``inr_siren_fit_footprint_workspace_floats``; 0 for what ``inr_siren_fit_footprint`` does not serve."""
+    return int(lib().inr_siren_fit_footprint_workspace_floats(C.byref(desc), int(n), int(K)))
+
+
+def siren_fit_footprint(desc: SirenDesc, params, grads, m, v, x_sub, target, weight, fw, first_step: int, n_steps: int, lr: float,
+                        beta1=0.9, beta2=0.999, eps=1e-8, losses=None, workspace=None):
+    """``inr_siren_fit_footprint``: ``x_sub`` [n*K, in_features] (sub-sample minor), ``target`` / ``weight`` one per datum,
+    ``fw`` [K].  Returns the workspace."""
+    _chk_flat(desc, params=params, grads=grads, m=m, v=v)
+    rows = _rows(x_sub, desc.in_features, "x_sub")
+    K = _chk_footprint_weights(fw)
+    if rows == 0 or rows % K:
+        raise ValueError(f"x_sub has {rows} rows, no positive multiple of K = {K}")
+    n = rows // K
+    _chk_footprint_data(n, target, weight)
+    _chk_losses(losses, n_steps)
+    if not siren_hp_eligible(desc):
+        raise ValueError("inr_siren_fit_footprint does not serve this network (ask inr_siren_hp_eligible: every sine layer a "
+                         "multiple of 32 wide, hidden 128 / 256 / 512 / 1024, one output)")
+    workspace = _workspace(workspace, 4 * siren_fit_footprint_workspace_floats(desc, n, K), x_sub.device)
+    check(lib().inr_siren_fit_footprint(C.byref(desc), params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(),
+                                        x_sub.data_ptr(), target.data_ptr(), _ptr(weight), fw.data_ptr(), n, K, int(first_step),
+                                        int(n_steps), float(lr), float(beta1), float(beta2), float(eps), _ptr(losses),
+                                        workspace.data_ptr(), _nbytes(workspace) // 4, _stream()), "inr_siren_fit_footprint")
+    return workspace
+
+
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
                    "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order

@@ -33,6 +33,16 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     a cropped ROI needs.  ``ssim_scores_zerofill.csv`` holds the rows of ``ssim_scores.csv`` under the same protocol with the header
     ``Pt_id, b-value, slice, SSIM-zerofill, SSIM-SR``; ``metrics.json`` gains ``psnr_zerofill_db`` and ``ssim_zerofill_mean``; with
     ``--adc``, ``adc.mat`` gains ``adc_zerofill`` on the grid of ``adc_spline`` (x4 of the LR ROI).  Needs an even ROI side.
+  * ``--lr_model average [--footprint box [--footprint_samples S]]``: the low-resolution image is the mean of every 2 x 2 block of the
+    HR ROI (what a scanner with twice the in-plane voxel size acquires) instead of every second pixel, placed at the block centres
+    in the HR grid's frame; the spline baseline is then ``baselines.rescale(LR, 2)`` of THAT image (pixel-centre placement is right
+    for block means).  ``--footprint box`` also fits under the matching forward model -- a datum is the average of the network over
+    S x S midpoint nodes of its 2 x 2 HR pixels (``footprint.py``, ``inr_siren_fit_footprint``) -- so that the fitted function is the
+    de-blurred image; ``--footprint point`` (default) fits point samples at the block centres.  ``metrics.json`` gains ``lr_model``,
+    ``footprint``, ``footprint_samples`` (K) and ``lr_consistency_psnr_db`` (the forward model against the LR data, data range 1).
+    Refused: ``--footprint box`` without ``--lr_model average``; either with ``--model wire``; ``--lr_model average`` with
+    ``--zerofill`` (defined on the decimation grid), an odd ROI side, or ``hybrid_raw`` and ``--pertubation_epochs > 0`` (the
+    PerturbNet phase is point-sampled).
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
@@ -60,6 +70,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 import mri_super_resolution_amd as inr  # noqa: E402
 from mri_super_resolution_amd import baselines, drivers, matio, metrics, reports, wire  # noqa: E402
+from mri_super_resolution_amd import footprint as footprint_mod  # noqa: E402
 
 
 def build_parser():
@@ -99,6 +110,14 @@ def build_parser():
     p.add_argument("--wire_derivative_maps", action="store_true",
                    help="--model wire: also write derivatives.mat (grad_mag, laplacian on recon's grid, along the spatial axes) "
                         "from the WIRE network's forward-mode derivative kernels")
+    p.add_argument("--lr_model", choices=("decimate", "average"), default="decimate",
+                   help="how the low-resolution image comes from the HR ROI: every second pixel (superresDWI.py:94), or the mean of "
+                        "every 2 x 2 block at the block centres")
+    p.add_argument("--footprint", choices=("point", "box"), default="point",
+                   help="--lr_model average: the forward model of a low-resolution pixel in the fit: a point sample, or the average "
+                        "of the network over its 2 x 2 HR pixels")
+    p.add_argument("--footprint_samples", type=int, default=2,
+                   help="--footprint box: midpoint nodes per in-plane axis (2 = the discrete block mean on the HR grid; at most 8)")
     p.add_argument("--wire_omega", type=float, default=1.2, help="--model wire: omega_0 of every layer (wiretest.ipynb cell 7)")
     p.add_argument("--wire_scale", type=float, default=1.2, help="--model wire: scale_0 of every layer (wiretest.ipynb cell 7)")
     return p
@@ -152,7 +171,10 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     what it adds to ``metrics.json`` (``acq_lr``: the K low-resolution acquisition products, None for a plain volume)."""
     out_dir = os.path.join(args.output_address, f"pat{pt_id}")
     os.makedirs(out_dir, exist_ok=True)
-    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, (check_model or _check_model)(args))
+    # (the footprint flags are refused for every caller of this function: another driver's ``check_model`` replaces ``_check_model``)
+    refuse_acquisitions = _check_footprint(args, external_fit=fit is not None)
+    refuse_acquisitions = (check_model or _check_model)(args) or refuse_acquisitions
+    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, refuse_acquisitions)
     r0, r1 = args.roi_start, args.roi_end
     if r1 > min(mean_img.shape[:2]) or r0 < 0 or r1 - r0 < 14:
         raise ValueError(f"ROI {r0}:{r1} does not fit the {mean_img.shape[:2]} slices (SSIM needs >= 7 x 7 LR pixels)")
@@ -160,8 +182,12 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     if args.seed is not None:
         np.random.seed(args.seed)
         torch.manual_seed(args.seed)
-    lr_img = mean_img[r0:r1:2, r0:r1:2]                                                   # superresDWI.py:94,97
     hr_img = mean_img[r0:r1, r0:r1]                                                       # :100,128
+    average = getattr(args, "lr_model", "decimate") == "average"
+    if average:
+        lr_img = footprint_mod.block_means(hr_img)
+    else:
+        lr_img = mean_img[r0:r1:2, r0:r1:2]                                               # superresDWI.py:94,97
     mean_dataset = inr.ImageFitting_set([lr_img])
     dimension = len(mean_dataset.shape)
     B = torch.from_numpy(np.random.normal(size=(args.mapping_size, dimension)) * args.scale).float().cuda()   # :105-106
@@ -174,7 +200,12 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         INR = inr.Siren(in_features=2 * args.mapping_size, out_features=1, hidden_features=args.hidden_dim,
                         hidden_layers=args.num_layers).cuda()
         reconstruct = inr.reconstruct
-    model_input = inr.input_mapping(mean_dataset.coords[0], B)
+    footprint = None
+    if average:
+        coords, footprint = _average_model(args, hr_img.shape)
+        model_input = inr.footprint_inputs(coords, B, footprint)
+    else:
+        model_input = inr.input_mapping(mean_dataset.coords[0], B)
     target = mean_dataset.pixels[0]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -184,6 +215,9 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         losses, fit_summary = fit(args, INR, B, mean_dataset, model_input, target, acq_lr)
     elif args.model == "wire":                                # the plain fit on the mean image (wiretest.ipynb cell 10)
         fitter, losses = wire.fit_wire(INR, model_input, target, args.number_of_epochs, lr=args.learning_rate)
+    elif average:                                             # (K = 1, the point footprint, is the plain fit at the block centres)
+        fitter = inr.FootprintSirenFitter(INR, footprint, lr=args.learning_rate) if footprint.count > 1 else None
+        fitter, losses = inr.fit_siren(INR, model_input, target, args.number_of_epochs, lr=args.learning_rate, fitter=fitter)
     elif acq is None:
         fitter, losses = inr.fit_siren(INR, model_input, target, args.number_of_epochs, lr=args.learning_rate)
     else:
@@ -205,7 +239,11 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     # [Z, B, X, Y] stacks of 2-D slices; spline baseline from every second HR pixel, x2 (superresDWI.py:181)
     hs = hr_d.permute(2, 3, 0, 1).contiguous()
     ss = SR_recon.permute(2, 3, 0, 1).contiguous()
-    sp = baselines.rescale(hs[:, :, ::2, ::2].contiguous(), 2)
+    if average:     # the baseline sees what the fit saw: the block means, whose pixel centres are where `rescale` places them
+        ls = torch.from_numpy(np.ascontiguousarray(lr_img, dtype=np.float32)).cuda().permute(2, 3, 0, 1).contiguous()
+    else:
+        ls = hs[:, :, ::2, ::2].contiguous()
+    sp = baselines.rescale(ls, 2)
     ok = hs.amax(dim=(-2, -1)) > 0
     safe = lambda t: torch.where(ok[..., None, None], t, torch.ones_like(t)).clamp_min(1e-30)   # empty slices: finite, ignored
     ssim_spline = metrics.ssim_reference_protocol(safe(hs), safe(sp)).cpu().numpy()
@@ -234,6 +272,10 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
                     csv.row(pt_id, bvalues[b] if b < len(bvalues) else b, _slice, float(ssim_zf[_slice, b]), float(ssim_sr[_slice, b]))
         summary["psnr_zerofill_db"] = float(metrics.psnr(hs, zf, 1.0))
         summary["ssim_zerofill_mean"] = float(ssim_zf[okn].mean())
+    if average:
+        pred = inr.footprint_forward(INR, coords, B, footprint)
+        summary.update({"lr_model": "average", "footprint": args.footprint, "footprint_samples": footprint.count,
+                        "lr_consistency_psnr_db": float(metrics.psnr(target.reshape(1, -1), pred.reshape(1, -1), 1.0))})
     summary.update(fit_summary)
     if args.transverse_length:
         coronal, summary["t_coronal_s"] = _coronal(INR, B, mean_img, test_shape, args, reconstruct)
@@ -241,7 +283,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
         matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale,
-                                                                     args.zerofill_apodize if zf is not None else None))
+                                                                     args.zerofill_apodize if zf is not None else None, ls))
     if args.derivative_maps:
         matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape))
     if args.wire_derivative_maps:
@@ -256,6 +298,44 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         json.dump(summary, fh, indent=1)
     print(json.dumps(summary))
     return summary
+
+
+def _average_model(args, hr_shape):
+    """``--lr_model average``: the coordinates of the LR data -- the centres of the 2 x 2 in-plane blocks in the HR grid's frame -- and
+    the footprint of ``--footprint``."""
+    if args.footprint == "box":
+        footprint = footprint_mod.block_footprint(hr_shape, 2, int(args.footprint_samples))
+    else:
+        footprint = inr.Footprint.point(len(hr_shape))
+    return footprint_mod.block_centres(hr_shape), footprint
+
+
+def _check_footprint(args, external_fit=False):
+    """``--lr_model`` / ``--footprint``: the combinations nothing serves, before the input is loaded and anything touches the device
+    (``run_patient`` calls it whichever driver's ``check_model`` it was given).  ``external_fit``: the fit is another driver's hook,
+    which knows neither the block-centre coordinates nor the ``n*K`` rows of a footprint.
+    Returns the reason for which an input with single acquisitions is to be refused (None: it is served)."""
+    lr_model, footprint = getattr(args, "lr_model", "decimate"), getattr(args, "footprint", "point")
+    if footprint == "box" and lr_model != "average":
+        raise ValueError("--footprint box is the 2 x 2 block of --lr_model average: pass --lr_model average with it")
+    if lr_model != "average":
+        return None
+    if args.model == "wire":
+        raise ValueError("--lr_model average / --footprint box run on the SIREN's fit kernels: not with --model wire")
+    if external_fit:
+        raise ValueError("--lr_model average / --footprint box are superresDWI's own fit: another driver's fit is point-sampled on "
+                         "the decimation grid")
+    if getattr(args, "zerofill", False):
+        raise ValueError("--lr_model average cannot be combined with --zerofill: zero-filling is defined on the decimation grid "
+                         "(LR sample j on HR sample 2j)")
+    if (args.roi_end - args.roi_start) % 2:
+        raise ValueError(f"--lr_model average takes 2 x 2 block means and needs an even ROI side (got {args.roi_end - args.roi_start})")
+    if footprint == "box" and not 1 <= args.footprint_samples <= 8:
+        raise ValueError(f"--footprint_samples must be 1 .. 8 per axis (S x S <= 64 sub-samples; got {args.footprint_samples})")
+    if args.pertubation_epochs > 0:
+        return ("holds single acquisitions, and --pertubation_epochs > 0 asks for the PerturbNet phase, which is point-sampled: "
+                "with --lr_model average pass --pertubation_epochs 0 to fit the mean image only")
+    return None
 
 
 def _check_model(args):
@@ -334,14 +414,15 @@ def _zerofill(hs, factor, apodize):
     return baselines.fourier_resize(lr, (factor * lr.shape[-2], factor * lr.shape[-1]), 'sample', 'mirror', apodize).clamp_min(0)
 
 
-def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None):
+def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None):
     """superresDWI.py:189-206 for all slices in one batch: every b-image times maxes[b, 1], then calculate_ADC per pixel, of
     the x2 SR volume, the x4 spline of the LR ROI and the x2 spline of the HR ROI.  ``hs`` is the HR ROI as [Z, B, R, R].
-    ``zerofill_apodize`` (not None): also ``adc_zerofill``, the x4 zero-fill of the LR ROI, on the grid of ``adc_spline``."""
+    ``zerofill_apodize`` (not None): also ``adc_zerofill``, the x4 zero-fill of the LR ROI, on the grid of ``adc_spline``.
+    ``ls``: the LR ROI as [Z, B, R/2, R/2] (default: every second pixel of ``hs``; ``--lr_model average``: the block means)."""
     scale = torch.as_tensor(np.asarray(signal_scale, np.float32), device=recon.device)
     to_xyzb = lambda t: t.permute(2, 3, 0, 1).contiguous()                       # [Z, B, 2R, 2R] -> [2R, 2R, Z, B]
     stacks = {"adc_sr": recon,
-              "adc_spline": to_xyzb(baselines.rescale(hs[:, :, ::2, ::2].contiguous(), 4)),
+              "adc_spline": to_xyzb(baselines.rescale(hs[:, :, ::2, ::2].contiguous() if ls is None else ls, 4)),
               "adc_hr": to_xyzb(baselines.rescale(hs, 2))}
     if zerofill_apodize is not None:
         stacks["adc_zerofill"] = to_xyzb(_zerofill(hs, 4, zerofill_apodize))

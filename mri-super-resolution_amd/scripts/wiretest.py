@@ -13,7 +13,9 @@ The flags are ``superresDWI``'s, the defaults the notebook's (cells 6-8): ``--ma
 Outputs: the files of ``superresDWI --model wire`` (``recon.mat`` / ``recon.npy``, ``ssim_scores.csv``, ``metrics.json``, the
 optional ``--transverse_length`` / ``--adc`` products); ``metrics.json`` gains ``pn_steps`` (PerturbNet updates taken) and
 ``pn_final_loss`` (the loss of the last one; null when none was taken).  ``--wire_derivative_maps`` adds ``derivatives.mat`` as
-in ``superresDWI --model wire``; ``--derivative_maps``, the SIREN's flag, stays refused.  Loading, re-sampling, evaluation and
+in ``superresDWI --model wire``; ``--derivative_maps``, the SIREN's flag, stays refused, and so are ``--lr_model average`` and
+``--footprint box``, which the parser inherits: the WIRE fit and the PerturbNet phase are point-sampled on the decimation grid
+(``superresDWI._check_footprint``, reached through ``run_patient`` before the input is loaded).  Loading, re-sampling, evaluation and
 writing are ``superresDWI``'s own functions.
 """
 from __future__ import annotations
