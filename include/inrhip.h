@@ -482,6 +482,42 @@ int inr_fourier_resample2d(double* out, const double* in, int n_images, int heig
 int inr_fourier_resample2d_f32(float* out, const float* in, int n_images, int height, int width, int out_height, int out_width,
                                int align, int boundary, double apodize, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- model-based super-resolution with a TV / Huber prior: the variational comparator of the fitted networks ------------
+ * No counterpart in the reference.  Images are [n_images][H][W] (HR) and [n_images][h][w] (LR), H = f0 h, W = f1 w, 1 <= f0, f1 <=
+ * INR_TVSR_MAX_FACTOR (1 x 1: denoising), H, W <= INR_TVSR_MAX_SIDE.  `kernel` is a HOST array k [f0][f1] of finite doubles that sum to
+ * 1 (to 1e-9): 1 / (f0 f1) is the block mean, the delta at (0, 0) the decimation (LR sample j on HR sample f j).
+ *   (A x)[i][j] = sum_{a, b} k[a][b] x[f0 i + a][f1 j + b] (the terms added in ascending (a, b)),  A^T r spreads k[a][b] r[i][j],
+ *   A A^T = |k|^2 I;  grad: forward differences, zero last row / column;  div = -grad^T.
+ * inr_block_apply2d: out [n][h][w] = A in.  inr_block_adjoint2d: out [n][H][W] = A^T in.  fp64, out must not overlap in.
+ * inr_tvsr_solve2d: out [n][H][W] = n_iter iterations of Chambolle-Pock (tau = sigma = 1/sqrt(8)) on
+ *   min_x 1/2 sum_i w_i ((A x)_i - y_i)^2 + lambda sum_j H_alpha(|(grad x)_j|),  H_0(t) = t,  H_alpha(t) = t^2 / (2 alpha) for t <= alpha,
+ *   t - alpha / 2 above, from x = xbar = x0, p = 0:
+ *     p <- (p + sigma grad(xbar)) / (1 + sigma alpha / lambda);  p <- p / max(1, |p| / lambda)   (lambda == 0: p = 0)
+ *     v <- x + tau div(p);  x' <- v - A^T(c (A v - y)), c_i = tau w_i / (1 + tau w_i |k|^2);  xbar <- 2 x' - x;  x <- x'
+ *   y [n][h][w]; weight [n][h][w] or null (= 1; must be >= 0 and finite -- device data, not checked; 0 is a missing datum, whose y is
+ *   never used); x0 [n][H][W] or null (block replication of y).  energy / change [n] DEVICE doubles or null: the objective at the
+ *   returned image (reduced in a fixed order: no float atomics, calls are bit-equal) and max |x' - x| of the last iteration (0 for
+ *   n_iter == 0, which returns x0).  ONE launch, no host read: one workgroup per image runs all iterations with workgroup barriers
+ *   only; a batch larger than the CU count is queued.  fp64 throughout; the _f32 form reads y / weight / x0 and writes out as fp32,
+ *   with fp64 inside, and rounds once (energy is that of the fp64 image).  n_images == 0 succeeds and launches nothing.
+ * workspace: inr_tvsr_workspace_doubles(n_images, H, W) doubles (the state x | xbar | p0 | p1 of every image), 16-byte aligned; 0 for
+ * sizes that would be refused.  Refusals, all before any device work: INR_E_INVALID (null out / y / kernel, n_images < 0, factors or
+ * sizes out of range, H or W no multiple of its factor, n_iter < 0, a negative or non-finite lambda / alpha, a kernel that is not
+ * finite or does not sum to 1), INR_E_WORKSPACE (null or short workspace), INR_E_ALIGN (workspace off a 16-byte boundary). */
+#define INR_TVSR_MAX_FACTOR 8
+#define INR_TVSR_MAX_SIDE 1024
+int inr_block_apply2d(double* out, const double* in, int n_images, int height, int width, int f0, int f1, const double* kernel,
+                      void* stream);
+int inr_block_adjoint2d(double* out, const double* in, int n_images, int height, int width, int f0, int f1, const double* kernel,
+                        void* stream);
+int64_t inr_tvsr_workspace_doubles(int n_images, int height, int width);
+int inr_tvsr_solve2d(double* out, double* energy, double* change, const double* y, const double* weight, const double* x0, int n_images,
+                     int height, int width, int f0, int f1, const double* kernel, double lambda, double alpha, int n_iter,
+                     double* workspace, int64_t workspace_doubles, void* stream);
+int inr_tvsr_solve2d_f32(float* out, double* energy, double* change, const float* y, const float* weight, const float* x0, int n_images,
+                         int height, int width, int f0, int f1, const double* kernel, double lambda, double alpha, int n_iter,
+                         double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
  * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
  * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output

@@ -23,6 +23,10 @@ superresDWI.py:231: scipy's ``interp1d(kind='cubic')`` -- a not-a-knot cubic spl
 k-space (zero-fill up, truncation down), the interpolation an MR scanner applies and the definition of
 ``scipy.signal.resample``, with a mirrored boundary so that a cropped region does not wrap around (``inr_fourier_resample2d``,
 DESIGN.md 4j).
+
+``tv_superres``, ``block_apply`` and ``block_adjoint`` are not the reference's either: the classical model-based reconstruction --
+the block operator ``A`` of the acquisition (block mean or decimation), no network, a TV / Huber prior, Chambolle-Pock on the
+device (``inr_tvsr_solve2d``) -- the comparator that says how much of a forward-model fit's gain is the model's.
 """
 from __future__ import annotations
 
@@ -213,6 +217,122 @@ def fourier_operator(n, m, align: str = 'sample', boundary: str = 'mirror', apod
     op = torch.empty((m, n), dtype=torch.float64, device=ops.require_gpu())
     check(lib().inr_fourier_operator(op.data_ptr(), n, m, *modes, ops._stream()), "inr_fourier_operator")
     return op.cpu().numpy()
+
+
+TV_DEFAULT_LAMBDA, TV_DEFAULT_HUBER, TV_DEFAULT_ITERS = 3e-3, 0.3, 300       # the sweep of DESIGN.md 4l
+
+
+def _block_kernel(who, kernel, factors):
+    """'mean', 'decimate' or an array [f0][f1] -> (f0, f1, nested float lists), refusing by name."""
+    try:
+        f0, f1 = (int(f) for f in factors)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: factors are (f0, f1), one per trailing axis (got {factors!r})") from None
+    if not (1 <= f0 <= ops.TVSR_MAX_FACTOR and 1 <= f1 <= ops.TVSR_MAX_FACTOR):
+        raise ValueError(f"{who}: factors are 1 .. {ops.TVSR_MAX_FACTOR} per axis (got {f0} x {f1})")
+    if isinstance(kernel, str):
+        if kernel == "mean":
+            k = np.full((f0, f1), 1.0 / (f0 * f1))
+        elif kernel == "decimate":
+            k = np.zeros((f0, f1))
+            k[0, 0] = 1.0
+        else:
+            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or an array [f0][f1] (got {kernel!r})")
+    else:
+        k = np.asarray(kernel, dtype=np.float64)
+        if k.shape != (f0, f1):
+            raise ValueError(f"{who}: the kernel array must be [{f0}][{f1}] (got {k.shape})")
+        if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
+            raise ValueError(f"{who}: the kernel array must be finite and sum to 1 (got sum {k.sum()!r})")
+    return f0, f1, k.tolist()
+
+
+def _block_input(who, image, name="input"):
+    """Refuses by name what is no image batch; -> (True for an ndarray, rows, columns, leading shape).  Touches no device."""
+    as_numpy = _fourier_input(who, image)
+    if image.ndim < 2:
+        raise ValueError(f"{who} needs at least 2-D {name}")
+    return as_numpy, int(image.shape[-2]), int(image.shape[-1]), tuple(image.shape[:-2])
+
+
+def _block_batch(image, as_numpy):
+    """-> the device tensor [n, rows, columns] (an ndarray as float64)."""
+    x = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float64)).to(ops.require_gpu()) if as_numpy else image
+    return x.reshape(-1, x.shape[-2], x.shape[-1]).contiguous()
+
+
+def _hr_sides(who, rows, cols, f0, f1):
+    if rows < 1 or cols < 1 or rows > ops.TVSR_MAX_SIDE or cols > ops.TVSR_MAX_SIDE:
+        raise ValueError(f"{who}: HR images of 1 .. {ops.TVSR_MAX_SIDE} samples per axis (got {rows} x {cols})")
+    if rows % f0 or cols % f1:
+        raise ValueError(f"{who}: the HR image {rows} x {cols} is no whole number of {f0} x {f1} blocks")
+
+
+def block_apply(x, factors, kernel="mean"):
+    """``A x``: every ``f0 x f1`` block of the trailing two axes of ``x`` summed with the weights ``kernel`` -- 'mean' (the block mean),
+    'decimate' (its first sample: LR sample j on HR sample f j) or an array [f0][f1] that sums to 1 (``inr_block_apply2d``, fp64).
+    Leading axes are a batch; ndarray in -> float64 ndarray out, device fp32 / fp64 tensor in -> the same out."""
+    f0, f1, k = _block_kernel("block_apply", kernel, factors)
+    as_numpy, H, W, lead = _block_input("block_apply", x)
+    _hr_sides("block_apply", H, W, f0, f1)
+    flat = _block_batch(x, as_numpy)
+    out = ops.block_apply(flat.double(), (f0, f1), k).to(flat.dtype).reshape(*lead, H // f0, W // f1)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def block_adjoint(r, factors, kernel="mean"):
+    """``A^T r``: ``kernel[a][b] r[i][j]`` spread over block (i, j) (``inr_block_adjoint2d``); types as ``block_apply``."""
+    f0, f1, k = _block_kernel("block_adjoint", kernel, factors)
+    as_numpy, h, w, lead = _block_input("block_adjoint", r)
+    _hr_sides("block_adjoint", h * f0, w * f1, f0, f1)
+    flat = _block_batch(r, as_numpy)
+    out = ops.block_adjoint(flat.double(), (f0, f1), k).to(flat.dtype).reshape(*lead, h * f0, w * f1)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, huber: float = TV_DEFAULT_HUBER,
+                n_iter: int = TV_DEFAULT_ITERS, weight=None, x0=None, return_info: bool = False):
+    """Model-based super-resolution of the trailing two axes of ``lr`` by ``factors`` = (f0, f1), 1 .. 8 each ((1, 1) denoises):
+    ``n_iter`` Chambolle-Pock iterations on ``1/2 sum w (A x - lr)^2 + lam sum H_huber(|grad x|)`` with the block operator ``A`` of
+    ``block_apply`` -- ``kernel`` 'mean', 'decimate' or an array [f0][f1] --, forward-difference gradient, ``huber`` = 0 the isotropic
+    TV and > 0 the Huber function (quadratic up to ``huber``); ``lam`` = 0 keeps the data term only.  ``weight`` (shape of ``lr``,
+    >= 0; 0 marks a missing datum) defaults to 1, ``x0`` (HR shape) to the block replication of ``lr``.  One launch for the whole
+    batch, one workgroup per image (``inr_tvsr_solve2d``).  ndarray in -> float64 ndarray out; device fp32 / fp64
+    tensor in -> the same out (fp64 inside, rounded once); ``weight`` / ``x0`` are given like ``lr``.  There is no CPU fallback.
+    ``return_info``: also a dict with ``energy`` (the objective at the result) and ``change`` (max |x' - x| of the last iteration),
+    both of the leading shape."""
+    who = "tv_superres"
+    f0, f1, k = _block_kernel(who, kernel, factors)
+    lam, huber = float(lam), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or n_iter < 0:
+        raise ValueError(f"{who}: n_iter must be an integer >= 0 (got {n_iter!r})")
+    as_numpy, h, w, lead = _block_input(who, lr)
+    _hr_sides(who, h * f0, w * f1, f0, f1)
+    extra = {}
+    for name, value, shape in (("weight", weight, (h, w)), ("x0", x0, (h * f0, w * f1))):
+        if value is None:
+            extra[name] = None
+            continue
+        if isinstance(value, np.ndarray) != as_numpy:
+            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
+        _fourier_input(who, value)
+        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
+            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
+        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
+            raise ValueError(f"{who}: weight must be finite and >= 0")
+        extra[name] = value
+    y = _block_batch(lr, as_numpy)
+    extra = {name: None if value is None else _block_batch(value, as_numpy) for name, value in extra.items()}
+    out, energy, change = ops.tvsr_solve(y, (f0, f1), k, lam, huber, int(n_iter), extra["weight"], extra["x0"])
+    out = out.reshape(*lead, h * f0, w * f1)
+    energy, change = energy.reshape(lead), change.reshape(lead)
+    if as_numpy:
+        out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
+    return (out, {"energy": energy, "change": change}) if return_info else out
 
 
 def resize_z(arr, new_size: int = 128, kind: str = 'cubic'):

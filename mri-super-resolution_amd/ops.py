@@ -716,6 +716,101 @@ def siren_fit_footprint(desc: SirenDesc, params, grads, m, v, x_sub, target, wei
     return workspace
 
 
+# ---- model-based TV / Huber super-resolution (include/inrhip.h) --------------------------------------------------------
+TVSR_MAX_FACTOR, TVSR_MAX_SIDE = _lib.INR_TVSR_MAX_FACTOR, _lib.INR_TVSR_MAX_SIDE
+
+
+def _chk_images(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
+    """A contiguous device batch [n, rows, columns] of one of ``dtypes``."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
+    if t.dim() != 3 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [n, rows, columns] batch (got {tuple(t.shape)})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def _block_kernel(kernel, factors):
+    """The HOST block kernel [f0][f1] as the C array the entry points take; refuses what they would refuse."""
+    f0, f1 = (int(f) for f in factors)
+    if not (1 <= f0 <= TVSR_MAX_FACTOR and 1 <= f1 <= TVSR_MAX_FACTOR):
+        raise ValueError(f"block factors are 1 .. {TVSR_MAX_FACTOR} per axis (got {f0} x {f1})")
+    flat = [float(v) for row in kernel for v in row]
+    if len(kernel) != f0 or len(flat) != f0 * f1:
+        raise ValueError(f"the block kernel must be [{f0}][{f1}]")
+    if not all(v == v and abs(v) != float("inf") for v in flat) or abs(sum(flat) - 1.0) > 1e-9:
+        raise ValueError(f"the block kernel must be finite and sum to 1 (sum {sum(flat)!r})")
+    return f0, f1, (C.c_double * (f0 * f1))(*flat)
+
+
+def _hr_shape(name, rows, cols, f0, f1):
+    if not (1 <= rows <= TVSR_MAX_SIDE and 1 <= cols <= TVSR_MAX_SIDE) or rows % f0 or cols % f1:
+        raise ValueError(f"{name}: HR images are 1 .. {TVSR_MAX_SIDE} samples per axis and whole {f0} x {f1} blocks (got {rows} x {cols})")
+
+
+def block_apply(x: torch.Tensor, factors, kernel) -> torch.Tensor:
+    """``inr_block_apply2d``: ``x`` [n, H, W] float64 -> ``A x`` [n, H/f0, W/f1]; ``kernel`` [f0][f1] host values that sum to 1."""
+    _chk_images(x, "x")
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, H, W = x.shape
+    _hr_shape("block_apply", H, W, f0, f1)
+    out = torch.empty((n, H // f0, W // f1), dtype=torch.float64, device=x.device)
+    check(lib().inr_block_apply2d(out.data_ptr(), x.data_ptr(), n, H, W, f0, f1, k, _stream()), "inr_block_apply2d")
+    return out
+
+
+def block_adjoint(r: torch.Tensor, factors, kernel) -> torch.Tensor:
+    """``inr_block_adjoint2d``: ``r`` [n, h, w] float64 -> ``A^T r`` [n, f0 h, f1 w]."""
+    _chk_images(r, "r")
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, h, w = r.shape
+    _hr_shape("block_adjoint", h * f0, w * f1, f0, f1)
+    out = torch.empty((n, h * f0, w * f1), dtype=torch.float64, device=r.device)
+    check(lib().inr_block_adjoint2d(out.data_ptr(), r.data_ptr(), n, h * f0, w * f1, f0, f1, k, _stream()), "inr_block_adjoint2d")
+    return out
+
+
+def tvsr_workspace_doubles(n: int, H: int, W: int) -> int:
+    """``inr_tvsr_workspace_doubles``; 0 for sizes ``inr_tvsr_solve2d`` refuses."""
+    return int(lib().inr_tvsr_workspace_doubles(int(n), int(H), int(W)))
+
+
+def tvsr_solve(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_iter: int, weight=None, x0=None, workspace=None):
+    """``inr_tvsr_solve2d`` / ``_f32`` by the dtype of ``y`` [n, h, w]: returns (x [n, f0 h, f1 w] of that dtype, energy [n] float64,
+    change [n] float64).  ``weight`` [n, h, w] and ``x0`` [n, f0 h, f1 w] share the dtype; ``workspace``: a float64 tensor."""
+    _chk_images(y, "y", (torch.float32, torch.float64))
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, h, w = y.shape
+    H, W = h * f0, w * f1
+    _hr_shape("tvsr_solve", H, W, f0, f1)
+    if weight is not None:
+        _chk_images(weight, "weight", (y.dtype,), y.shape)
+    if x0 is not None:
+        _chk_images(x0, "x0", (y.dtype,), (n, H, W))
+    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or n_iter < 0:
+        raise ValueError(f"tvsr_solve: lam and alpha must be finite and >= 0, n_iter >= 0 (got {lam!r}, {alpha!r}, {n_iter})")
+    out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
+    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
+    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    if n == 0:
+        return out, energy, change
+    need = tvsr_workspace_doubles(n, H, W)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
+    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
+        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
+    entry = "inr_tvsr_solve2d" if y.dtype == torch.float64 else "inr_tvsr_solve2d_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, H, W, f0,
+                                f1, k, lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()), entry)
+    return out, energy, change
+
+
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
                    "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order

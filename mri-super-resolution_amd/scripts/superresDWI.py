@@ -43,6 +43,14 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     Refused: ``--footprint box`` without ``--lr_model average``; either with ``--model wire``; ``--lr_model average`` with
     ``--zerofill`` (defined on the decimation grid), an odd ROI side, or ``hybrid_raw`` and ``--pertubation_epochs > 0`` (the
     PerturbNet phase is point-sampled).
+  * ``--tv_baseline [--tv_lambda L --tv_huber A --tv_iters N]``: the classical model-based reconstruction next to the spline -- no
+    network, the SAME forward operator as the low-resolution data (``--lr_model decimate``: the decimation, LR sample j on HR sample
+    2j; ``--lr_model average``: the 2 x 2 block mean) and a TV (A = 0) / Huber prior: ``baselines.tv_superres(LR, (2, 2), kernel, L, A,
+    N)`` on the LR ROI, every slice and b-image in one launch (``inr_tvsr_solve2d_f32``).  ``ssim_scores_tv.csv`` holds
+    the rows of ``ssim_scores.csv`` under the same protocol with the header ``Pt_id, b-value, slice, SSIM-tv, SSIM-SR``;
+    ``metrics.json`` gains ``psnr_tv_db``, ``ssim_tv_mean`` and ``tv_consistency_psnr_db`` (``A x`` against the LR data, data range 1);
+    with ``--adc``, ``adc.mat`` gains ``adc_tv`` on the grid of the HR ROI ([R, R, Z]).  It does not touch the fit, so it goes with
+    ``--zerofill`` and ``--model wire``.  Refused before the input is loaded: an odd ROI side, L < 0, A < 0, N outside 1 .. 100,000.
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
@@ -100,6 +108,14 @@ def build_parser():
                         "ssim_scores_zerofill.csv, psnr_zerofill_db / ssim_zerofill_mean in metrics.json, adc_zerofill with --adc")
     p.add_argument("--zerofill_apodize", type=float, default=0.0,
                    help="--zerofill: Tukey window over the kept band, 0 (none, the default) .. 1 (Hann)")
+    p.add_argument("--tv_baseline", action="store_true",
+                   help="also score the model-based TV / Huber reconstruction of the LR ROI under the forward model of --lr_model: "
+                        "ssim_scores_tv.csv, psnr_tv_db / ssim_tv_mean / tv_consistency_psnr_db in metrics.json, adc_tv with --adc")
+    p.add_argument("--tv_lambda", type=float, default=baselines.TV_DEFAULT_LAMBDA,
+                   help="--tv_baseline: weight of the prior (data in [0, 1]; default from the sweep of DESIGN.md 4l)")
+    p.add_argument("--tv_huber", type=float, default=baselines.TV_DEFAULT_HUBER,
+                   help="--tv_baseline: Huber threshold on the gradient magnitude; 0 = plain isotropic TV")
+    p.add_argument("--tv_iters", type=int, default=baselines.TV_DEFAULT_ITERS, help="--tv_baseline: Chambolle-Pock iterations, 1 .. 100,000")
     p.add_argument("--derivative_maps", action="store_true",
                    help="also write derivatives.mat: gradient magnitude and Laplacian of the fitted network on recon's grid, "
                         "along the spatial axes (nn_mri.py:205-221)")
@@ -168,11 +184,14 @@ def load_input_and_scale(path, key=None, refuse_acquisitions=None):
 def run_patient(path, pt_id, args, check_model=None, fit=None):
     """One patient.  ``check_model`` / ``fit``: another driver's refusals and fit on this driver's loading, re-sampling and
     outputs (``scripts/wiretest.py``); ``fit(args, INR, B, mean_dataset, model_input, target, acq_lr)`` returns the losses and
-    what it adds to ``metrics.json`` (``acq_lr``: the K low-resolution acquisition products, None for a plain volume)."""
+    what it adds to ``metrics.json`` (``acq_lr``: the K low-resolution acquisition products, None for a plain volume).  A hook that
+    fits other LR data than this function forms says so with an attribute ``changes_lr_data = True``: ``--tv_baseline``, which solves on
+    this function's LR ROI, is then refused; any other hook leaves it alone."""
     out_dir = os.path.join(args.output_address, f"pat{pt_id}")
     os.makedirs(out_dir, exist_ok=True)
     # (the footprint flags are refused for every caller of this function: another driver's ``check_model`` replaces ``_check_model``)
     refuse_acquisitions = _check_footprint(args, external_fit=fit is not None)
+    _check_tv(args, fit)
     refuse_acquisitions = (check_model or _check_model)(args) or refuse_acquisitions
     mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, refuse_acquisitions)
     r0, r1 = args.roi_start, args.roi_end
@@ -249,6 +268,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     ssim_spline = metrics.ssim_reference_protocol(safe(hs), safe(sp)).cpu().numpy()
     ssim_sr = metrics.ssim_reference_protocol(safe(hs), safe(ss)).cpu().numpy()
     zf = _zerofill(hs, 2, args.zerofill_apodize) if getattr(args, "zerofill", False) else None
+    tv = _tv_baseline(ls, args, average) if getattr(args, "tv_baseline", False) else None
     with reports.SsimCsv(os.path.join(out_dir, "ssim_scores.csv")) as csv:
         for _slice in range(nz):
             for b in range(nb):
@@ -272,6 +292,15 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
                     csv.row(pt_id, bvalues[b] if b < len(bvalues) else b, _slice, float(ssim_zf[_slice, b]), float(ssim_sr[_slice, b]))
         summary["psnr_zerofill_db"] = float(metrics.psnr(hs, zf, 1.0))
         summary["ssim_zerofill_mean"] = float(ssim_zf[okn].mean())
+    if tv is not None:
+        ssim_tv = metrics.ssim_reference_protocol(safe(hs), safe(tv)).cpu().numpy()
+        with reports.SsimCsv(os.path.join(out_dir, "ssim_scores_tv.csv"), reports.SSIM_TV_HEADER) as csv:
+            for _slice in range(nz):
+                for b in range(nb):
+                    csv.row(pt_id, bvalues[b] if b < len(bvalues) else b, _slice, float(ssim_tv[_slice, b]), float(ssim_sr[_slice, b]))
+        summary["psnr_tv_db"] = float(metrics.psnr(hs, tv, 1.0))
+        summary["ssim_tv_mean"] = float(ssim_tv[okn].mean())
+        summary["tv_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(tv, (2, 2), _tv_kernel(average)), 1.0))
     if average:
         pred = inr.footprint_forward(INR, coords, B, footprint)
         summary.update({"lr_model": "average", "footprint": args.footprint, "footprint_samples": footprint.count,
@@ -283,7 +312,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
         matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale,
-                                                                     args.zerofill_apodize if zf is not None else None, ls))
+                                                                     args.zerofill_apodize if zf is not None else None, ls, tv))
     if args.derivative_maps:
         matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape))
     if args.wire_derivative_maps:
@@ -414,11 +443,40 @@ def _zerofill(hs, factor, apodize):
     return baselines.fourier_resize(lr, (factor * lr.shape[-2], factor * lr.shape[-1]), 'sample', 'mirror', apodize).clamp_min(0)
 
 
-def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None):
+def _tv_kernel(average):
+    """The block kernel of the LR model: the 2 x 2 mean of ``--lr_model average``, else the decimation (LR sample j on HR sample 2j)."""
+    return "mean" if average else "decimate"
+
+
+def _tv_baseline(ls, args, average):
+    """``--tv_baseline``: the [Z, B, R/2, R/2] LR stack ``ls`` -> the [Z, B, R, R] TV / Huber reconstruction under the LR model's operator."""
+    return baselines.tv_superres(ls, (2, 2), _tv_kernel(average), args.tv_lambda, args.tv_huber, args.tv_iters)
+
+
+def _check_tv(args, fit=None):
+    """``--tv_baseline``: what it cannot serve, before the input is loaded and anything touches the device."""
+    if not getattr(args, "tv_baseline", False):
+        return
+    if (args.roi_end - args.roi_start) % 2:
+        raise ValueError(f"--tv_baseline solves for 2 x 2 HR pixels per LR pixel and needs an even ROI side (got "
+                         f"{args.roi_end - args.roi_start})")
+    if not 0.0 <= args.tv_lambda < float("inf"):
+        raise ValueError(f"--tv_lambda must be finite and >= 0 (got {args.tv_lambda})")
+    if not 0.0 <= args.tv_huber < float("inf"):
+        raise ValueError(f"--tv_huber must be finite and >= 0 (got {args.tv_huber})")
+    if not 1 <= args.tv_iters <= 100000:
+        raise ValueError(f"--tv_iters must be 1 .. 100,000 (got {args.tv_iters})")
+    if fit is not None and getattr(fit, "changes_lr_data", False):
+        raise ValueError("--tv_baseline solves on the LR ROI this driver forms: not with a fit hook that changes the LR data "
+                         "(changes_lr_data)")
+
+
+def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, tv=None):
     """superresDWI.py:189-206 for all slices in one batch: every b-image times maxes[b, 1], then calculate_ADC per pixel, of
     the x2 SR volume, the x4 spline of the LR ROI and the x2 spline of the HR ROI.  ``hs`` is the HR ROI as [Z, B, R, R].
     ``zerofill_apodize`` (not None): also ``adc_zerofill``, the x4 zero-fill of the LR ROI, on the grid of ``adc_spline``.
-    ``ls``: the LR ROI as [Z, B, R/2, R/2] (default: every second pixel of ``hs``; ``--lr_model average``: the block means)."""
+    ``ls``: the LR ROI as [Z, B, R/2, R/2] (default: every second pixel of ``hs``; ``--lr_model average``: the block means).
+    ``tv`` (not None): also ``adc_tv`` of the [Z, B, R, R] TV reconstruction, on the grid of the HR ROI."""
     scale = torch.as_tensor(np.asarray(signal_scale, np.float32), device=recon.device)
     to_xyzb = lambda t: t.permute(2, 3, 0, 1).contiguous()                       # [Z, B, 2R, 2R] -> [2R, 2R, Z, B]
     stacks = {"adc_sr": recon,
@@ -426,6 +484,8 @@ def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None):
               "adc_hr": to_xyzb(baselines.rescale(hs, 2))}
     if zerofill_apodize is not None:
         stacks["adc_zerofill"] = to_xyzb(_zerofill(hs, 4, zerofill_apodize))
+    if tv is not None:
+        stacks["adc_tv"] = to_xyzb(tv)
     out = {k: metrics.calculate_ADC_device(bvalues, (v * scale).contiguous()).cpu().numpy() for k, v in stacks.items()}
     out["b"] = np.asarray(bvalues, np.float64)
     return out
