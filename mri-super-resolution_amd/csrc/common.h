@@ -56,6 +56,18 @@ static inline int check_ws_doubles(const char* who, const double* workspace, int
     return 0;
 }
 
+// the dense grid `shape` [dim] of an entry point that walks it in chunks (jet.hip, wire_deriv.hip, wire.hip): every axis and the
+// row count within 1 .. max_rows.  *total receives the row count
+static inline int check_grid_shape(const char* who, const int64_t* shape, int dim, int64_t max_rows, int64_t* total) {
+    *total = 1;
+    for (int a = 0; a < dim; ++a) {
+        INR_REQUIRE(shape[a] >= 1 && shape[a] <= max_rows, INR_E_INVALID, "%s: shape[%d] must be >= 1", who, a);
+        *total *= shape[a];
+        INR_REQUIRE(*total <= max_rows, INR_E_INVALID, "%s: the grid has too many rows", who);
+    }
+    return 0;
+}
+
 // How every unit hands out its caller-allocated workspace: ONE function `X_view(shape..., base)` per workspace takes the regions
 // in order and returns typed pointers plus the total.  The planner is that function with a null base (`take` returns null and
 // still advances); the entry point calls it once with the real base and checks `workspace_bytes >= total` before its first launch.

@@ -3,7 +3,8 @@
 // argument checks and, in an extern "C" block at its end, its public entry points; a name is declared here only if a unit other
 // than the one that defines it uses it, and everything else in a unit is file-local.  Every .hip file includes this header -- the
 // defining one too, so that a declaration that has drifted from its definition fails to compile in the file that is wrong.
-// Default arguments live here and nowhere else.  (set_error, count_launch, launch_finalize and the profiler hooks are in common.h,
+// Default arguments live here and nowhere else.  One exception to "file-local": jet_host.h, the host code the two derivative units
+// (jet.hip, wire_deriv.hip) share and no other unit includes; it includes this header for them.  (set_error, count_launch, launch_finalize and the profiler hooks are in common.h,
 // beside their types; the launch families of every unit are counted through count_launch in api.hip's one table.)
 #pragma once
 #include <vector>

@@ -12,7 +12,7 @@
 //   jet_head_kernel    -- a wave per row: y = w.a + b, dy/dx_i = w.t_i, lap = w.q (lane-strided partial sums, xor-shuffle tree).
 // Every row is computed from its own coordinates alone with a fixed summation order: its bits do not depend on the chunk size,
 // on its place in a chunk, or on which of the other outputs were asked for.
-#include "internal.h"
+#include "jet_host.h"
 
 #include <vector>
 
@@ -20,11 +20,9 @@ namespace inr {
 
 namespace {
 
-constexpr int JET_MAX_J = JET_MAX_D + 2;
 constexpr int JET_BM = 64, JET_BN = 64, JET_KB = 32;
 constexpr int JET_LDS = JET_KB + 4;     // LDS row pitch in floats: 144 B keeps the 16-byte fragment reads aligned and off one bank
 constexpr int JET_THREADS = 256;
-constexpr int64_t JET_MAX_ROWS = (1ll << 31) - 256;
 constexpr float JET_TWO_PI = 6.283185307179586f;
 
 // (the d coordinates of one row: jet_coords, common.h)
@@ -273,83 +271,51 @@ JetView jet_view(const JetPlan& p, int J, int64_t chunk, void* base) {
     return v;
 }
 
-template <int J, bool LAP>
-void jet_launch_layer_as(dim3 grid, hipStream_t st, float* out, long long out_plane, const float* in, long long in_plane, int lda,
-                         const float* W, const float* bias, int K, int H, long long rows, float omega) {
-    hipLaunchKernelGGL((jet_layer_kernel<J, LAP>), grid, dim3(JET_THREADS), 0, st, out, out_plane, in, in_plane, lda, W, bias, K, H,
-                       rows, omega);
-}
-
 int jet_launch_layer(int dt, int lap, hipStream_t st, float* out, long long out_plane, const float* in, long long in_plane, int lda,
                      const float* W, const float* bias, int K, int H, long long rows, float omega) {
     const dim3 grid((unsigned)((rows + JET_BM - 1) / JET_BM), (unsigned)((H + JET_BN - 1) / JET_BN));
-#define JET_CASE(DT_, LAP_)                                                                                              \
-    case 2 * (DT_) + (LAP_):                                                                                             \
-        jet_launch_layer_as<1 + (DT_) + (LAP_), (LAP_) != 0>(grid, st, out, out_plane, in, in_plane, lda, W, bias, K, H, \
-                                                             rows, omega);                                              \
-        break;
-    switch (2 * dt + lap) {
-        JET_CASE(0, 0)
-        JET_CASE(1, 0)
-        JET_CASE(1, 1)
-        JET_CASE(2, 0)
-        JET_CASE(2, 1)
-        JET_CASE(3, 0)
-        JET_CASE(3, 1)
-        JET_CASE(4, 0)
-        JET_CASE(4, 1)
-        default:
-            INR_REQUIRE(false, INR_E_INVALID, "jet layer: no kernel for %d tangents, laplacian %d", dt, lap);
-    }
-#undef JET_CASE
+    const bool served = jet_dispatch(dt, lap, [&](auto j, auto with_lap) {
+        hipLaunchKernelGGL((jet_layer_kernel<decltype(j)::value, decltype(with_lap)::value>), grid, dim3(JET_THREADS), 0, st, out,
+                           out_plane, in, in_plane, lda, W, bias, K, H, rows, omega);
+    });
+    INR_REQUIRE(served, INR_E_INVALID, "jet layer: no kernel for %d tangents, laplacian %d", dt, lap);
     INR_LAUNCH_CHECK();
     count_launch(LF_JET_BASE + INR_JET_LF_LAYER);
     return 0;
 }
 
-inline unsigned jet_blocks(long long work) { return (unsigned)((work + 255) / 256); }
-
-// x != null: explicit rows [n][d]; else the grid `shape` ([d]).  Everything has been validated except what is checked here.
-int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, const float* x, const int64_t* shape, int64_t n,
-            int d, int d_tangent, const float* B, int m, float* y, float* grad, float* lap, int64_t chunk_rows, void* workspace,
-            size_t workspace_bytes, void* stream) {
-    INR_REQUIRE(d_tangent >= 1 && d_tangent <= d, INR_E_INVALID, "%s: 1 <= d_tangent <= d (got %d, d = %d)", who, d_tangent, d);
-    INR_REQUIRE(chunk_rows >= 1 && chunk_rows <= JET_MAX_ROWS, INR_E_INVALID, "%s: bad chunk_rows %lld", who, (long long)chunk_rows);
-    INR_REQUIRE(aligned16(params), INR_E_ALIGN, "%s: params must be 16-byte aligned", who);
-    if (n == 0) return 0;
-    const bool fourier = B != nullptr;
-    const JetPlan p = jet_plan(desc, d, fourier);
-    // with neither derivative asked for only the value plane is carried; a Laplacian needs the tangents too
-    const int dt = (grad || lap) ? d_tangent : 0;
-    const int has_q = lap ? 1 : 0;
-    const int J = 1 + dt + has_q;
-    const int64_t chunk = chunk_rows < n ? chunk_rows : n;
-    const JetView v = jet_view(p, J, chunk, workspace);
+// the resolved call c on the workspace.  The descriptor has been checked.
+int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, const JetCall& c, void* workspace,
+            size_t workspace_bytes) {
+    if (c.n == 0) return 0;
+    const bool fourier = c.B != nullptr;
+    const JetPlan p = jet_plan(desc, c.d, fourier);
+    const JetView v = jet_view(p, c.J, c.chunk, workspace);
     INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "%s: workspace too small (%zu bytes, %zu needed)", who,
                 workspace ? workspace_bytes : (size_t)0, v.total);
     INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
 
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = c.st;
     float* const* buf = v.buf;
-    JetGrid g;
-    for (int a = 0; a < JET_MAX_D; ++a) g.n[a] = (shape && a < d) ? shape[a] : 1;
+    const int d = c.d, dt = c.dt, has_q = c.has_q;
     const int H = p.H;
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const long long rows = (n - r0 < chunk) ? (n - r0) : chunk;
-        const float* xc = x ? x + r0 * d : nullptr;
+    for (int64_t r0 = 0; r0 < c.n; r0 += c.chunk) {
+        const long long rows = (c.n - r0 < c.chunk) ? (c.n - r0) : c.chunk;
+        const float* xc = c.x ? c.x + r0 * d : nullptr;
         int cur = 0, first_gemm;
         if (fourier) {
-            if (int rc = jet_launch_fourier(buf[0], (long long)chunk * p.pitch0, p.pitch0, xc, shape, d, dt, has_q, r0, rows, B, m, st))
+            if (int rc = jet_launch_fourier(buf[0], (long long)c.chunk * p.pitch0, p.pitch0, xc, c.shape, d, dt, has_q, r0, rows, c.B,
+                                            c.m, st))
                 return rc;
             first_gemm = 0;
         } else {
-            const long long plane = (long long)chunk * H;
+            const long long plane = (long long)c.chunk * H;
             const long long work = rows * H;
-            if (x)
-                hipLaunchKernelGGL(jet_first_kernel<false>, dim3(jet_blocks(work)), dim3(256), 0, st, buf[0], plane, xc, g, d, dt,
+            if (c.x)
+                hipLaunchKernelGGL(jet_first_kernel<false>, dim3(jet_blocks(work)), dim3(256), 0, st, buf[0], plane, xc, c.grid, d, dt,
                                    has_q, (long long)r0, rows, params + p.L.w_off[0], params + p.L.b_off[0], H, desc->first_omega);
             else
-                hipLaunchKernelGGL(jet_first_kernel<true>, dim3(jet_blocks(work)), dim3(256), 0, st, buf[0], plane, xc, g, d, dt,
+                hipLaunchKernelGGL(jet_first_kernel<true>, dim3(jet_blocks(work)), dim3(256), 0, st, buf[0], plane, xc, c.grid, d, dt,
                                    has_q, (long long)r0, rows, params + p.L.w_off[0], params + p.L.b_off[0], H, desc->first_omega);
             first_gemm = 1;
         }
@@ -358,14 +324,14 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
         for (int l = first_gemm; l < p.S; ++l) {
             const int K = l == 0 ? desc->in_features : H;
             const int lda = l == 0 ? p.pitch0 : H;
-            if (int rc = jet_launch_layer(dt, has_q, st, buf[cur ^ 1], (long long)chunk * H, buf[cur], (long long)chunk * lda, lda,
+            if (int rc = jet_launch_layer(dt, has_q, st, buf[cur ^ 1], (long long)c.chunk * H, buf[cur], (long long)c.chunk * lda, lda,
                                           params + p.L.w_off[l], params + p.L.b_off[l], K, H, rows, layer_omega(desc, l)))
                 return rc;
             cur ^= 1;
         }
-        hipLaunchKernelGGL(jet_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, y + r0, grad ? grad + r0 * dt : nullptr,
-                           lap ? lap + r0 : nullptr, buf[cur], (long long)chunk * H, params + p.L.w_off[p.S], params + p.L.b_off[p.S], H,
-                           dt, has_q, rows);
+        hipLaunchKernelGGL(jet_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, c.y + r0,
+                           c.grad ? c.grad + r0 * dt : nullptr, c.lap ? c.lap + r0 : nullptr, buf[cur], (long long)c.chunk * H,
+                           params + p.L.w_off[p.S], params + p.L.b_off[p.S], H, dt, has_q, rows);
         INR_LAUNCH_CHECK();
         count_launch(LF_JET_BASE + INR_JET_LF_HEAD);
     }
@@ -377,8 +343,7 @@ int jet_run(const char* who, const inr_siren_desc_t* desc, const float* params, 
 // ---- launcher other units may call (internal.h) ----------------------------------------------------------------------------
 int jet_launch_fourier(float* out, long long plane, int pitch, const float* x, const int64_t* shape, int d, int dt, int lap,
                        int64_t row_begin, int64_t n_rows, const float* B, int m, hipStream_t st) {
-    JetGrid g;
-    for (int a = 0; a < JET_MAX_D; ++a) g.n[a] = (shape && a < d) ? shape[a] : 1;
+    const JetGrid g = jet_grid(shape, d);
     const dim3 grid(jet_blocks((long long)n_rows * (pitch / 2)));
     if (x)
         hipLaunchKernelGGL(jet_fourier_kernel<false>, grid, dim3(256), 0, st, out, plane, pitch, x, g, d, dt, lap,
@@ -408,8 +373,9 @@ int inr_siren_jet(const inr_siren_desc_t* desc, const float* params, const float
     if (int rc = jet_check_desc("inr_siren_jet", desc, d, m, B != nullptr)) return rc;
     INR_REQUIRE(params && x && y, INR_E_INVALID, "inr_siren_jet: null pointer");
     INR_REQUIRE(n >= 0 && n <= JET_MAX_ROWS, INR_E_INVALID, "inr_siren_jet: bad row count %lld", (long long)n);
-    return jet_run("inr_siren_jet", desc, params, x, nullptr, n, d, d_tangent, B, m, y, grad, lap, chunk_rows, workspace,
-                   workspace_bytes, stream);
+    JetCall c;
+    if (int rc = jet_resolve(c, "inr_siren_jet", params, x, nullptr, n, d, d_tangent, B, m, y, grad, lap, chunk_rows, stream)) return rc;
+    return jet_run("inr_siren_jet", desc, params, c, workspace, workspace_bytes);
 }
 
 int inr_siren_jet_grid(const inr_siren_desc_t* desc, const float* params, const int64_t* shape, int dim, int d_tangent,
@@ -417,14 +383,13 @@ int inr_siren_jet_grid(const inr_siren_desc_t* desc, const float* params, const 
                        size_t workspace_bytes, void* stream) {
     if (int rc = jet_check_desc("inr_siren_jet_grid", desc, dim, m, B != nullptr)) return rc;
     INR_REQUIRE(params && shape && y, INR_E_INVALID, "inr_siren_jet_grid: null pointer");
-    int64_t total = 1;
-    for (int a = 0; a < dim; ++a) {
-        INR_REQUIRE(shape[a] >= 1 && shape[a] <= JET_MAX_ROWS, INR_E_INVALID, "inr_siren_jet_grid: shape[%d] must be >= 1", a);
-        total *= shape[a];
-        INR_REQUIRE(total <= JET_MAX_ROWS, INR_E_INVALID, "inr_siren_jet_grid: the grid has too many rows");
-    }
-    return jet_run("inr_siren_jet_grid", desc, params, nullptr, shape, total, dim, d_tangent, B, m, y, grad, lap, chunk_rows, workspace,
-                   workspace_bytes, stream);
+    int64_t total;
+    if (int rc = check_grid_shape("inr_siren_jet_grid", shape, dim, JET_MAX_ROWS, &total)) return rc;
+    JetCall c;
+    if (int rc = jet_resolve(c, "inr_siren_jet_grid", params, nullptr, shape, total, dim, d_tangent, B, m, y, grad, lap, chunk_rows,
+                             stream))
+        return rc;
+    return jet_run("inr_siren_jet_grid", desc, params, c, workspace, workspace_bytes);
 }
 
 }  // extern "C"

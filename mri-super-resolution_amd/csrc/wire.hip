@@ -801,12 +801,8 @@ int inr_wire_reconstruct(const inr_wire_desc_t* desc, const float* params, const
     else
         INR_REQUIRE(dim == desc->in_features, INR_E_INVALID,
                     "inr_wire_reconstruct: without B the grid dim (%d) must equal in_features (%d)", dim, desc->in_features);
-    int64_t total = 1;
-    for (int a = 0; a < dim; ++a) {
-        INR_REQUIRE(shape[a] >= 1 && shape[a] <= WIRE_MAX_ROWS, INR_E_INVALID, "inr_wire_reconstruct: shape[%d] must be >= 1", a);
-        total *= shape[a];
-        INR_REQUIRE(total <= WIRE_MAX_ROWS, INR_E_INVALID, "inr_wire_reconstruct: the grid has too many rows");
-    }
+    int64_t total;
+    if (int rc = check_grid_shape("inr_wire_reconstruct", shape, dim, WIRE_MAX_ROWS, &total)) return rc;
     const WirePlan p = wire_plan(desc);
     const WireView v = wire_view(p, chunk_rows, WIRE_WS_INFER, workspace, true);
     INR_REQUIRE(workspace && workspace_bytes >= v.total, INR_E_WORKSPACE, "inr_wire_reconstruct: workspace too small (%zu bytes, %zu needed)",

@@ -18,7 +18,7 @@
 // Every row is computed from its own coordinates alone with a fixed summation order, and every multiply-add of the epilogues is
 // spelled out (no contraction is left to the compiler): its bits do not depend on the chunk size, on its place in a chunk, on
 // which of the other outputs were asked for, or on rows versus grid form.
-#include "internal.h"
+#include "jet_host.h"
 
 #pragma clang fp contract(off)
 
@@ -26,11 +26,9 @@ namespace inr {
 
 namespace {
 
-constexpr int WD_MAX_J = JET_MAX_D + 2;
 constexpr int WD_BM = 32, WD_BN = 32, WD_KB = 32;
 constexpr int WD_LDS = WD_KB + 4;       // LDS row pitch in floats (144 B: 16-byte fragment reads, off one bank), as wire.hip / jet.hip
 constexpr int WD_THREADS = 256;
-constexpr int64_t WD_MAX_ROWS = (1ll << 31) - 256;
 
 // ---- input: raw coordinates.  One thread per (row, column of the K0-wide plane)
 template <bool FROM_GRID>
@@ -187,34 +185,32 @@ __global__ void __launch_bounds__(256) wired_head_kernel(float* __restrict__ y, 
     const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n_rows) return;      // uniform over the wave
     const int J = 1 + dt + has_q;
-    float part[WD_MAX_J];
+    float part[JET_MAX_J];
 #pragma unroll
-    for (int p = 0; p < WD_MAX_J; ++p) part[p] = 0.f;
+    for (int p = 0; p < JET_MAX_J; ++p) part[p] = 0.f;
     const float* a = in + row * 2 * H;
     for (int k = lane; k < H; k += 64) {
         const float w_r = w[2 * k], w_i = w[2 * k + 1];
 #pragma unroll
-        for (int p = 0; p < WD_MAX_J; ++p)
+        for (int p = 0; p < JET_MAX_J; ++p)
             if (p < J) {
                 part[p] = fmaf(a[p * plane + k], w_r, part[p]);
                 part[p] = fmaf(-a[p * plane + H + k], w_i, part[p]);
             }
     }
 #pragma unroll
-    for (int p = 0; p < WD_MAX_J; ++p) part[p] = wave_sum(part[p]);
+    for (int p = 0; p < JET_MAX_J; ++p) part[p] = wave_sum(part[p]);
     if (lane != 0) return;
     y[row] = part[0] + b[0];
 #pragma unroll
     for (int i = 0; i < JET_MAX_D; ++i)
         if (grad && i < dt) grad[row * dt + i] = part[1 + i];
 #pragma unroll
-    for (int p = 1; p < WD_MAX_J; ++p)
+    for (int p = 1; p < JET_MAX_J; ++p)
         if (lapl && p == 1 + dt) lapl[row] = part[p];
 }
 
 // ------------------------------------------------------ host ------------------------------------------------------
-inline unsigned wd_blocks(long long work) { return (unsigned)((work + 255) / 256); }
-
 // the descriptor and the input, before anything else: d coordinate axes, Fourier features (m frequencies) or raw coordinates
 int wd_check_desc(const char* who, const inr_wire_desc_t* desc, int d, int m, bool fourier) {
     if (int rc = wire_check_desc(who, desc)) return rc;
@@ -249,81 +245,52 @@ WdView wd_view(const WirePlan& p, int J, int64_t chunk, void* base) {
     return v;
 }
 
-template <int Q, int J, bool LAP>
-void wd_launch_layer_as(dim3 grid, hipStream_t st, float* out, long long out_plane, const float* in, long long in_plane,
-                        const float* img, const float* pb, int K, int H, long long rows, float omega, float s2) {
-    hipLaunchKernelGGL((wired_layer_kernel<Q, J, LAP>), grid, dim3(WD_THREADS), 0, st, out, out_plane, in, in_plane, img, pb, K, H,
-                       rows, omega, s2);
-}
-
 int wd_launch_layer(bool first, int dt, int lap, hipStream_t st, float* out, long long out_plane, const float* in, long long in_plane,
                     const float* img, const float* pb, int K, int H, long long rows, float omega, float s2) {
     const dim3 grid((unsigned)((rows + WD_BM - 1) / WD_BM), (unsigned)(H / WD_BN));
-#define WD_CASE(DT_, LAP_)                                                                                                   \
-    case 2 * (DT_) + (LAP_):                                                                                                 \
-        if (first)                                                                                                           \
-            wd_launch_layer_as<2, 1 + (DT_) + (LAP_), (LAP_) != 0>(grid, st, out, out_plane, in, in_plane, img, pb, K, H,    \
-                                                                   rows, omega, s2);                                        \
-        else                                                                                                                 \
-            wd_launch_layer_as<4, 1 + (DT_) + (LAP_), (LAP_) != 0>(grid, st, out, out_plane, in, in_plane, img, pb, K, H,    \
-                                                                   rows, omega, s2);                                        \
-        break;
-    switch (2 * dt + lap) {
-        WD_CASE(0, 0)
-        WD_CASE(1, 0)
-        WD_CASE(1, 1)
-        WD_CASE(2, 0)
-        WD_CASE(2, 1)
-        WD_CASE(3, 0)
-        WD_CASE(3, 1)
-        WD_CASE(4, 0)
-        WD_CASE(4, 1)
-        default:
-            INR_REQUIRE(false, INR_E_INVALID, "wire derivatives: no layer kernel for %d tangents, laplacian %d", dt, lap);
-    }
-#undef WD_CASE
+    const bool served = jet_dispatch(dt, lap, [&](auto j, auto with_lap) {
+        constexpr int J = decltype(j)::value;
+        constexpr bool LAP = decltype(with_lap)::value;
+        if (first)
+            hipLaunchKernelGGL((wired_layer_kernel<2, J, LAP>), grid, dim3(WD_THREADS), 0, st, out, out_plane, in, in_plane, img, pb,
+                               K, H, rows, omega, s2);
+        else
+            hipLaunchKernelGGL((wired_layer_kernel<4, J, LAP>), grid, dim3(WD_THREADS), 0, st, out, out_plane, in, in_plane, img, pb,
+                               K, H, rows, omega, s2);
+    });
+    INR_REQUIRE(served, INR_E_INVALID, "wire derivatives: no layer kernel for %d tangents, laplacian %d", dt, lap);
     INR_LAUNCH_CHECK();
     return 0;
 }
 
-// x != null: explicit rows [n][d]; else the grid `shape` ([d]).  The descriptor has been checked.
-int wd_run(const char* who, const inr_wire_desc_t* desc, const float* params, const float* x, const int64_t* shape, int64_t n, int d,
-           int d_tangent, const float* B, int m, float* y, float* grad, float* lap, int64_t chunk_rows, void* workspace,
-           int64_t workspace_floats, void* stream) {
-    INR_REQUIRE(d_tangent >= 1 && d_tangent <= d, INR_E_INVALID, "%s: 1 <= d_tangent <= d (got %d, d = %d)", who, d_tangent, d);
-    INR_REQUIRE(chunk_rows >= 1 && chunk_rows <= WD_MAX_ROWS, INR_E_INVALID, "%s: bad chunk_rows %lld", who, (long long)chunk_rows);
-    INR_REQUIRE(aligned16(params), INR_E_ALIGN, "%s: params must be 16-byte aligned", who);
-    if (n == 0) return 0;
+// the resolved call c on the workspace.  The descriptor has been checked.
+int wd_run(const char* who, const inr_wire_desc_t* desc, const float* params, const JetCall& c, void* workspace,
+           int64_t workspace_floats) {
+    if (c.n == 0) return 0;
     const WirePlan p = wire_plan(desc);
-    // with neither derivative asked for only the value plane is carried; a Laplacian needs the tangents too
-    const int dt = (grad || lap) ? d_tangent : 0;
-    const int has_q = lap ? 1 : 0;
-    const int J = 1 + dt + has_q;
-    const int64_t chunk = chunk_rows < n ? chunk_rows : n;
-    const WdView v = wd_view(p, J, chunk, workspace);
+    const WdView v = wd_view(p, c.J, c.chunk, workspace);
     INR_REQUIRE(workspace && workspace_floats >= v.total, INR_E_WORKSPACE, "%s: workspace too small (%lld floats, %lld needed)", who,
                 workspace ? (long long)workspace_floats : 0ll, (long long)v.total);
     INR_REQUIRE(aligned16(workspace), INR_E_ALIGN, "%s: workspace must be 16-byte aligned", who);
 
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = c.st;
     if (int rc = wire_pack_images(p, v.img, v.pb, params, st)) return rc;
-    JetGrid g;
-    for (int a = 0; a < JET_MAX_D; ++a) g.n[a] = (shape && a < d) ? shape[a] : 1;
+    const int d = c.d, dt = c.dt, has_q = c.has_q;
     const int H = p.H, K0 = p.K0, head = 4 * (p.L + 1);
     const float s2_first = desc->first_scale * desc->first_scale, s2_hidden = desc->hidden_scale * desc->hidden_scale;
-    const long long plane = (long long)chunk * 2 * H, plane0 = (long long)chunk * K0;
-    for (int64_t r0 = 0; r0 < n; r0 += chunk) {
-        const long long rows = (n - r0 < chunk) ? (n - r0) : chunk;
-        const float* xc = x ? x + r0 * d : nullptr;
-        if (B) {
-            if (int rc = jet_launch_fourier(v.feats, plane0, K0, xc, shape, d, dt, has_q, r0, rows, B, m, st)) return rc;
+    const long long plane = (long long)c.chunk * 2 * H, plane0 = (long long)c.chunk * K0;
+    for (int64_t r0 = 0; r0 < c.n; r0 += c.chunk) {
+        const long long rows = (c.n - r0 < c.chunk) ? (c.n - r0) : c.chunk;
+        const float* xc = c.x ? c.x + r0 * d : nullptr;
+        if (c.B) {
+            if (int rc = jet_launch_fourier(v.feats, plane0, K0, xc, c.shape, d, dt, has_q, r0, rows, c.B, c.m, st)) return rc;
         } else {
-            if (x)
-                hipLaunchKernelGGL(wired_input_kernel<false>, dim3(wd_blocks(rows * K0)), dim3(256), 0, st, v.feats, plane0, K0, xc, g,
-                                   d, dt, has_q, (long long)r0, rows);
+            if (c.x)
+                hipLaunchKernelGGL(wired_input_kernel<false>, dim3(jet_blocks(rows * K0)), dim3(256), 0, st, v.feats, plane0, K0, xc,
+                                   c.grid, d, dt, has_q, (long long)r0, rows);
             else
-                hipLaunchKernelGGL(wired_input_kernel<true>, dim3(wd_blocks(rows * K0)), dim3(256), 0, st, v.feats, plane0, K0, xc, g,
-                                   d, dt, has_q, (long long)r0, rows);
+                hipLaunchKernelGGL(wired_input_kernel<true>, dim3(jet_blocks(rows * K0)), dim3(256), 0, st, v.feats, plane0, K0, xc,
+                                   c.grid, d, dt, has_q, (long long)r0, rows);
             INR_LAUNCH_CHECK();
         }
         const float* in = v.feats;
@@ -335,8 +302,8 @@ int wd_run(const char* who, const inr_wire_desc_t* desc, const float* params, co
                 return rc;
             in = out;
         }
-        hipLaunchKernelGGL(wired_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, y + r0,
-                           grad ? grad + r0 * dt : nullptr, lap ? lap + r0 : nullptr, in, plane, params + p.off[head],
+        hipLaunchKernelGGL(wired_head_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, c.y + r0,
+                           c.grad ? c.grad + r0 * dt : nullptr, c.lap ? c.lap + r0 : nullptr, in, plane, params + p.off[head],
                            params + p.off[head + 1], H, dt, has_q, rows);
         INR_LAUNCH_CHECK();
     }
@@ -351,7 +318,7 @@ using namespace inr;
 extern "C" {
 
 int64_t inr_wire_derivatives_workspace_floats(const inr_wire_desc_t* desc, int d, int m, int64_t chunk_rows, int want_laplacian) {
-    if (chunk_rows < 1 || chunk_rows > WD_MAX_ROWS) {
+    if (chunk_rows < 1 || chunk_rows > JET_MAX_ROWS) {
         set_error("inr_wire_derivatives_workspace_floats: bad chunk_rows %lld", (long long)chunk_rows);
         return 0;
     }
@@ -364,9 +331,11 @@ int inr_wire_derivatives(const inr_wire_desc_t* desc, const float* params, const
                          int64_t workspace_floats, void* stream) {
     if (int rc = wd_check_desc("inr_wire_derivatives", desc, d, m, B != nullptr)) return rc;
     INR_REQUIRE(params && x && y, INR_E_INVALID, "inr_wire_derivatives: null pointer");
-    INR_REQUIRE(n >= 0 && n <= WD_MAX_ROWS, INR_E_INVALID, "inr_wire_derivatives: bad row count %lld", (long long)n);
-    return wd_run("inr_wire_derivatives", desc, params, x, nullptr, n, d, d_tangent, B, m, y, grad, lap, chunk_rows, workspace,
-                  workspace_floats, stream);
+    INR_REQUIRE(n >= 0 && n <= JET_MAX_ROWS, INR_E_INVALID, "inr_wire_derivatives: bad row count %lld", (long long)n);
+    JetCall c;
+    if (int rc = jet_resolve(c, "inr_wire_derivatives", params, x, nullptr, n, d, d_tangent, B, m, y, grad, lap, chunk_rows, stream))
+        return rc;
+    return wd_run("inr_wire_derivatives", desc, params, c, workspace, workspace_floats);
 }
 
 int inr_wire_derivatives_grid(const inr_wire_desc_t* desc, const float* params, const int64_t* shape, int dim, int d_tangent,
@@ -374,14 +343,13 @@ int inr_wire_derivatives_grid(const inr_wire_desc_t* desc, const float* params, 
                               int64_t workspace_floats, void* stream) {
     if (int rc = wd_check_desc("inr_wire_derivatives_grid", desc, dim, m, B != nullptr)) return rc;
     INR_REQUIRE(params && shape && y, INR_E_INVALID, "inr_wire_derivatives_grid: null pointer");
-    int64_t total = 1;
-    for (int a = 0; a < dim; ++a) {
-        INR_REQUIRE(shape[a] >= 1 && shape[a] <= WD_MAX_ROWS, INR_E_INVALID, "inr_wire_derivatives_grid: shape[%d] must be >= 1", a);
-        total *= shape[a];
-        INR_REQUIRE(total <= WD_MAX_ROWS, INR_E_INVALID, "inr_wire_derivatives_grid: the grid has too many rows");
-    }
-    return wd_run("inr_wire_derivatives_grid", desc, params, nullptr, shape, total, dim, d_tangent, B, m, y, grad, lap, chunk_rows,
-                  workspace, workspace_floats, stream);
+    int64_t total;
+    if (int rc = check_grid_shape("inr_wire_derivatives_grid", shape, dim, JET_MAX_ROWS, &total)) return rc;
+    JetCall c;
+    if (int rc = jet_resolve(c, "inr_wire_derivatives_grid", params, nullptr, shape, total, dim, d_tangent, B, m, y, grad, lap,
+                             chunk_rows, stream))
+        return rc;
+    return wd_run("inr_wire_derivatives_grid", desc, params, c, workspace, workspace_floats);
 }
 
 }  // extern "C"

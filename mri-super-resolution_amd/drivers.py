@@ -259,65 +259,26 @@ def fit_with_perturbnet(INR: Siren, B: torch.Tensor, mean_dataset: ImageFitting_
     ``perturb_optim.step()`` changes nothing -- kept exactly so (the loss is still evaluated).  With
     ``Siren(flavor='INRmodel')`` (INRmodel.py:147, inrDWI.py) the gradient flows INR input -> Fourier features -> PN.
     Returns the per-step INR losses (host list) and leaves the trained PerturbNet in ``fit_with_perturbnet.last_pn``."""
+    f = fit_with_perturbnet
+    losses, f.last_pn, f.last_pn_losses, _, _ = _fit_perturbnet(
+        INR, SirenFitter(INR, lr=lr), B, mean_dataset, acquisitions, number_of_epochs, pertubation_epochs, PN_dim, perturb_lr,
+        eps, perturb_net, clear_inr_grads=True)
+    return losses
+
+
+def _fit_perturbnet(INR, fitter, B, mean_dataset, acquisitions, number_of_epochs, pertubation_epochs, PN_dim, perturb_lr, eps,
+                    perturb_net, clear_inr_grads):
+    """The schedule ``fit_with_perturbnet`` and ``fit_wire_with_perturbnet`` share: ``fitter`` steps ``INR`` on the mean image,
+    the PerturbNet is stepped through ``INR``'s autograd function with ``ops.adam_step`` -- only where every one of its tensors
+    received a gradient (a SIREN of the SRDWI flavour detaches its input; a WIRE network never does).  ``clear_inr_grads``
+    drops what that backward left on ``INR.parameters()``.  Returns ``(INR losses, PerturbNet, its losses, its Adam state --
+    the (m, v) pair of each tensor --, its update count)``."""
     model_input = input_mapping(mean_dataset.coords[0], B)
     target = mean_dataset.pixels[0]
     dataset = ImageFitting_set(list(acquisitions))                                        # K device-resident targets
     dimension = len(dataset.shape)
     pn = perturb_net if perturb_net is not None else PN(in_features=model_input.shape[1], hidden_features=PN_dim,
                                                          dimension=dimension).cuda()
-    fitter = SirenFitter(INR, lr=lr)
-    head = max(number_of_epochs - pertubation_epochs, 0)
-    losses = [fitter.step(model_input, target, head)] if head else []
-    pn_params = [p for p in pn.parameters()]
-    pn_state = [(torch.zeros_like(p), torch.zeros_like(p)) for p in pn_params]
-    pn_steps, pn_losses = 0, []
-    for ctr in range(head, number_of_epochs):
-        if ctr % 2:
-            losses.append(fitter.step(model_input, target, 1))
-            continue
-        for sample in range(len(dataset)):
-            ground_truth = dataset.pixels[sample]
-            perturbed_input = input_mapping(pn(model_input, sample, eps), B)
-            model_output = INR(perturbed_input)
-            loss = ((model_output - ground_truth) ** 2).mean()
-            for p in pn_params:
-                p.grad = None
-            loss.backward()
-            pn_losses.append(loss.detach())
-            if all(p.grad is not None for p in pn_params):                                 # INRmodel flavour only
-                pn_steps += 1
-                for p, (m, v) in zip(pn_params, pn_state):
-                    ops.adam_step(p.data, p.grad.contiguous(), m, v, pn_steps, perturb_lr)
-            for p in INR.parameters():                                                    # inr_optim.zero_grad() of the next
-                p.grad = None                                                             # INR step clears these (:136)
-    fit_with_perturbnet.last_pn = pn
-    fit_with_perturbnet.last_pn_losses = [float(l) for l in pn_losses]
-    return [float(v) for v in torch.cat(losses).cpu()] if losses else []
-
-
-def fit_wire_with_perturbnet(INR, B: torch.Tensor, mean_dataset: ImageFitting_set, acquisitions: Sequence[np.ndarray],
-                             number_of_epochs: int = 2500, pertubation_epochs: int = 3, PN_dim: int = 128, lr: float = 5e-5,
-                             perturb_lr: float = 1e-6, eps: float = 1 / 128., perturb_net: Optional[PN] = None, fitter=None):
-    """wiretest.ipynb cell 10 for the WIRE network (``wire.Wire``), literally: the first ``number_of_epochs -
-    pertubation_epochs`` epochs are plain Adam steps on the mean image (ONE ``WireFitter.step`` call); in the tail, odd epochs
-    take one more INR step and even epochs one PerturbNet step per acquisition product --
-    ``loss(INR(input_mapping(PN(model_input, sample, eps), B)), acquisition_sample)`` with Adam(``perturb_lr``) on the PerturbNet
-    only.  The notebook's network does not detach its input (cell 2), so the gradient really flows WIRE input
-    (``inr_wire_input_grad``) -> Fourier features (``_FourierFn``) -> PerturbNet (``_PNFn``); the loss is torch's MSE, the update
-    ``ops.adam_step`` on each PerturbNet tensor.  The INR's parameters get no gradient in that branch (the notebook's next
-    ``inr_optim.zero_grad()`` would discard it).  All K targets are uploaded once.
-
-    Returns the per-step INR losses (host list); leaves the PerturbNet in ``fit_wire_with_perturbnet.last_pn``, its per-step
-    losses in ``.last_pn_losses`` and its Adam state, the ``(m, v)`` pair of each tensor, in ``.last_pn_state`` (``.last_pn_steps``
-    counts the updates).  ``fitter``: a ``WireFitter`` of ``INR`` to continue."""
-    from . import wire
-    model_input = input_mapping(mean_dataset.coords[0], B)
-    target = mean_dataset.pixels[0]
-    dataset = ImageFitting_set(list(acquisitions))                                        # K device-resident targets
-    dimension = len(dataset.shape)
-    pn = perturb_net if perturb_net is not None else PN(in_features=model_input.shape[1], hidden_features=PN_dim,
-                                                         dimension=dimension).cuda()
-    fitter = fitter if fitter is not None else wire.WireFitter(INR, lr=lr)
     head = max(number_of_epochs - pertubation_epochs, 0)
     losses = [fitter.step(model_input, target, head)] if head else []
     pn_params = [p for p in pn.parameters()]
@@ -336,14 +297,37 @@ def fit_wire_with_perturbnet(INR, B: torch.Tensor, mean_dataset: ImageFitting_se
                 p.grad = None
             loss.backward()
             pn_losses.append(loss.detach())
-            pn_steps += 1
-            for p, (m, v) in zip(pn_params, pn_state):                                    # perturb_optim.step()
-                ops.adam_step(p.data, p.grad.contiguous(), m, v, pn_steps, perturb_lr)
-    fit_wire_with_perturbnet.last_pn = pn
-    fit_wire_with_perturbnet.last_pn_losses = [float(l) for l in pn_losses]
-    fit_wire_with_perturbnet.last_pn_state = pn_state
-    fit_wire_with_perturbnet.last_pn_steps = pn_steps
-    return [float(v) for v in torch.cat(losses).cpu()] if losses else []
+            if all(p.grad is not None for p in pn_params):
+                pn_steps += 1
+                for p, (m, v) in zip(pn_params, pn_state):                                # perturb_optim.step()
+                    ops.adam_step(p.data, p.grad.contiguous(), m, v, pn_steps, perturb_lr)
+            if clear_inr_grads:
+                for p in INR.parameters():                                                # inr_optim.zero_grad() of the next
+                    p.grad = None                                                         # INR step clears these (:136)
+    return ([float(v) for v in torch.cat(losses).cpu()] if losses else []), pn, [float(l) for l in pn_losses], pn_state, pn_steps
+
+
+def fit_wire_with_perturbnet(INR, B: torch.Tensor, mean_dataset: ImageFitting_set, acquisitions: Sequence[np.ndarray],
+                             number_of_epochs: int = 2500, pertubation_epochs: int = 3, PN_dim: int = 128, lr: float = 5e-5,
+                             perturb_lr: float = 1e-6, eps: float = 1 / 128., perturb_net: Optional[PN] = None, fitter=None):
+    """wiretest.ipynb cell 10 for the WIRE network (``wire.Wire``), literally: the first ``number_of_epochs -
+    pertubation_epochs`` epochs are plain Adam steps on the mean image (ONE ``WireFitter.step`` call); in the tail, odd epochs
+    take one more INR step and even epochs one PerturbNet step per acquisition product --
+    ``loss(INR(input_mapping(PN(model_input, sample, eps), B)), acquisition_sample)`` with Adam(``perturb_lr``) on the PerturbNet
+    only.  The notebook's network does not detach its input (cell 2), so the gradient really flows WIRE input
+    (``inr_wire_input_grad``) -> Fourier features (``_FourierFn``) -> PerturbNet (``_PNFn``); the loss is torch's MSE, the update
+    ``ops.adam_step`` on each PerturbNet tensor.  The INR's parameters get no gradient in that branch (the notebook's next
+    ``inr_optim.zero_grad()`` would discard it).  All K targets are uploaded once.
+
+    Returns the per-step INR losses (host list); leaves the PerturbNet in ``fit_wire_with_perturbnet.last_pn``, its per-step
+    losses in ``.last_pn_losses`` and its Adam state, the ``(m, v)`` pair of each tensor, in ``.last_pn_state`` (``.last_pn_steps``
+    counts the updates).  ``fitter``: a ``WireFitter`` of ``INR`` to continue."""
+    from . import wire
+    f = fit_wire_with_perturbnet
+    losses, f.last_pn, f.last_pn_losses, f.last_pn_state, f.last_pn_steps = _fit_perturbnet(
+        INR, fitter if fitter is not None else wire.WireFitter(INR, lr=lr), B, mean_dataset, acquisitions, number_of_epochs,
+        pertubation_epochs, PN_dim, perturb_lr, eps, perturb_net, clear_inr_grads=False)
+    return losses
 
 
 def _slice_inputs(acquisitions, weights):

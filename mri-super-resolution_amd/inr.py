@@ -656,19 +656,24 @@ def derivatives(model: Siren, coords=None, *, shape=None, B=None, laplacian=True
     ``gradient[..., a]`` by ``2 / (n_a - 1)`` for units per voxel along an axis of ``n_a`` samples, a second derivative by its
     square.  The value is the raw network output (no clamp).  Both ``Siren`` flavours give the same bits: whether ``forward``
     detaches its input plays no part here.  The call runs under ``torch.no_grad()`` semantics -- the results carry no graph."""
+    return _derivatives(ops.siren_jet, lambda: flat_parameters(model), coords, shape, B, laplacian, d_tangent, chunk_rows)
+
+
+def _derivatives(jet, desc_and_flat, coords, shape, B, laplacian, d_tangent, chunk_rows):
+    """``derivatives`` and ``wire.derivatives`` after their docstrings: ``jet`` is ``ops.siren_jet`` or ``ops.wire_derivatives``,
+    ``desc_and_flat()`` gives the network's descriptor and flat parameter buffer."""
     if (coords is None) == (shape is None):
         raise ValueError("derivatives takes exactly one of coords and shape")
-    desc, flat = flat_parameters(model)
+    desc, flat = desc_and_flat()
     Bd = None if B is None else B.detach().to(flat.device, torch.float32).contiguous()
     with torch.no_grad():
         if coords is not None:
             lead, d = tuple(coords.shape[:-1]), int(coords.shape[-1])
             x = coords.detach().to(flat.device, torch.float32).reshape(-1, d).contiguous()
-            y, g, lap = ops.siren_jet(desc, flat, x=x, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian), chunk_rows=chunk_rows)
+            y, g, lap = jet(desc, flat, x=x, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian), chunk_rows=chunk_rows)
         else:
             lead = tuple(int(s) for s in shape)
-            y, g, lap = ops.siren_jet(desc, flat, shape=lead, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian),
-                                      chunk_rows=chunk_rows)
+            y, g, lap = jet(desc, flat, shape=lead, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian), chunk_rows=chunk_rows)
     return Derivatives(y.view(*lead), g.view(*lead, g.shape[-1]), None if lap is None else lap.view(*lead))
 
 

@@ -376,14 +376,10 @@ def siren_reconstruct(desc: SirenDesc, params, shape, B=None, clamp_min=0.0, chu
     return y
 
 
-def siren_jet(desc: SirenDesc, params, x=None, shape=None, B=None, d_tangent=None, want_grad=True, want_lap=True,
-              chunk_rows: int = 1 << 15):
-    """Value, coordinate gradient and Laplacian of a SIREN in forward mode (``inr_siren_jet`` on the rows ``x`` [n, d], or
-    ``inr_siren_jet_grid`` on ``get_mgrid(shape)``; exactly one of the two).  Returns ``(y [n], grad [n, d_tangent] or None,
-    lap [n] or None)``; derivatives are taken along the ``d_tangent`` leading axes (default: all ``d``)."""
-    if (x is None) == (shape is None):
-        raise ValueError("siren_jet takes exactly one of x and shape")
-    _chk_flat(desc, params=params)
+def _derivative_maps(planner, rows_fn, grid_fn, ws_dtype, desc, params, x, shape, B, d_tangent, want_grad, want_lap,
+                     chunk_rows):
+    """What ``siren_jet`` and ``wire_derivatives`` share once ``params`` has been checked: ``x`` or ``shape``, ``B``, the outputs,
+    a workspace of ``planner``'s count of ``ws_dtype`` elements, and the rows (``rows_fn``) or grid (``grid_fn``) entry point."""
     if x is not None:
         _chk(x, "x")
         if x.dim() != 2:
@@ -404,16 +400,27 @@ def siren_jet(desc: SirenDesc, params, x=None, shape=None, B=None, d_tangent=Non
     y = torch.empty(n, dtype=torch.float32, device=dev)
     grad = torch.empty((n, dt), dtype=torch.float32, device=dev) if want_grad else None
     lap = torch.empty(n, dtype=torch.float32, device=dev) if want_lap else None
-    nbytes = lib().inr_siren_jet_workspace_bytes(C.byref(desc), d, m, chunk_rows, 1 if want_lap else 0)
-    ws = _ws(nbytes, dev)        # (0 for a shape the kernels refuse: the call below says which)
+    count = int(getattr(lib(), planner)(C.byref(desc), d, m, chunk_rows, 1 if want_lap else 0))
+    ws = torch.empty(max(count, 16), dtype=ws_dtype, device=dev)      # (0 for a shape the kernels refuse: the call below says which)
     if x is not None:
-        check(lib().inr_siren_jet(C.byref(desc), params.data_ptr(), x.data_ptr(), n, d, dt, _ptr(B), m, y.data_ptr(), _ptr(grad),
-                                  _ptr(lap), chunk_rows, ws.data_ptr(), ws.numel(), _stream()), "inr_siren_jet")
+        check(getattr(lib(), rows_fn)(C.byref(desc), params.data_ptr(), x.data_ptr(), n, d, dt, _ptr(B), m, y.data_ptr(), _ptr(grad),
+                                      _ptr(lap), chunk_rows, ws.data_ptr(), ws.numel(), _stream()), rows_fn)
     else:
-        check(lib().inr_siren_jet_grid(C.byref(desc), params.data_ptr(), shape_array(shape), d, dt, _ptr(B), m, y.data_ptr(),
-                                       _ptr(grad), _ptr(lap), chunk_rows, ws.data_ptr(), ws.numel(), _stream()),
-              "inr_siren_jet_grid")
+        check(getattr(lib(), grid_fn)(C.byref(desc), params.data_ptr(), shape_array(shape), d, dt, _ptr(B), m, y.data_ptr(),
+                                      _ptr(grad), _ptr(lap), chunk_rows, ws.data_ptr(), ws.numel(), _stream()), grid_fn)
     return y, grad, lap
+
+
+def siren_jet(desc: SirenDesc, params, x=None, shape=None, B=None, d_tangent=None, want_grad=True, want_lap=True,
+              chunk_rows: int = 1 << 15):
+    """Value, coordinate gradient and Laplacian of a SIREN in forward mode (``inr_siren_jet`` on the rows ``x`` [n, d], or
+    ``inr_siren_jet_grid`` on ``get_mgrid(shape)``; exactly one of the two).  Returns ``(y [n], grad [n, d_tangent] or None,
+    lap [n] or None)``; derivatives are taken along the ``d_tangent`` leading axes (default: all ``d``)."""
+    if (x is None) == (shape is None):
+        raise ValueError("siren_jet takes exactly one of x and shape")
+    _chk_flat(desc, params=params)
+    return _derivative_maps("inr_siren_jet_workspace_bytes", "inr_siren_jet", "inr_siren_jet_grid", torch.uint8, desc,
+                            params, x, shape, B, d_tangent, want_grad, want_lap, chunk_rows)
 
 
 def wire_derivatives(desc: _lib.WireDesc, params, x=None, shape=None, B=None, d_tangent=None, want_grad=True, want_lap=True,
@@ -430,37 +437,9 @@ def wire_derivatives(desc: _lib.WireDesc, params, x=None, shape=None, B=None, d_
         check(int(total), "inr_wire_param_count")
     if params.numel() != total:
         raise ValueError(f"params has {params.numel()} floats, layout needs {total}")
-    if x is not None:
-        _chk(x, "x")
-        if x.dim() != 2:
-            raise ValueError(f"x {tuple(x.shape)} must be [n, d]")
-        n, d = int(x.shape[0]), int(x.shape[1])
-    else:
-        shape, n, _ = _grid_rows(shape)
-        d = len(shape)
-    m = 0
-    if B is not None:
-        _chk(B, "B")
-        if B.dim() != 2 or B.shape[1] != d:
-            raise ValueError(f"B {tuple(B.shape)} must be [m, {d}]")
-        m = int(B.shape[0])
-    dt = d if d_tangent is None else int(d_tangent)
-    chunk_rows = max(1, min(int(chunk_rows), max(n, 1)))
-    dev = params.device
-    y = torch.empty(n, dtype=torch.float32, device=dev)
-    grad = torch.empty((n, dt), dtype=torch.float32, device=dev) if want_grad else None
-    lap = torch.empty(n, dtype=torch.float32, device=dev) if want_lap else None
-    floats = int(lib().inr_wire_derivatives_workspace_floats(C.byref(desc), d, m, chunk_rows, 1 if want_lap else 0))
-    ws = torch.empty(max(floats, 4), dtype=torch.float32, device=dev)      # (0 for a shape the kernels refuse: the call says which)
-    if x is not None:
-        check(lib().inr_wire_derivatives(C.byref(desc), params.data_ptr(), x.data_ptr(), n, d, dt, _ptr(B), m, y.data_ptr(),
-                                         _ptr(grad), _ptr(lap), chunk_rows, ws.data_ptr(), floats, _stream()),
-              "inr_wire_derivatives")
-    else:
-        check(lib().inr_wire_derivatives_grid(C.byref(desc), params.data_ptr(), shape_array(shape), d, dt, _ptr(B), m, y.data_ptr(),
-                                              _ptr(grad), _ptr(lap), chunk_rows, ws.data_ptr(), floats, _stream()),
-              "inr_wire_derivatives_grid")
-    return y, grad, lap
+    return _derivative_maps("inr_wire_derivatives_workspace_floats", "inr_wire_derivatives",
+                            "inr_wire_derivatives_grid", torch.float32, desc, params, x, shape, B, d_tangent, want_grad, want_lap,
+                            chunk_rows)
 
 
 def siren_fit_workspace_bytes(desc: SirenDesc, n: int) -> int:

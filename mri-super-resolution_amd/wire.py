@@ -27,7 +27,7 @@ from torch import nn
 
 from . import ops
 from ._lib import WireDesc, check, lib, shape_array
-from .inr import Derivatives
+from .inr import _derivatives
 from .flat import AdamOwner, AdamState, FlatParams, Workspace, WorkspacePool
 
 HIDDEN_SIZES = (32, 64, 128, 256)
@@ -365,20 +365,9 @@ def derivatives(model: Wire, coords=None, *, shape=None, B=None, laplacian=True,
     ``2 / (n_a - 1)`` for units per voxel along an axis of ``n_a`` samples, a second derivative by its square.  The value is the
     raw network output (no clamp); it agrees with ``model(...)`` to rounding, not bit for bit (another tile shape).  The results
     carry no graph."""
-    if (coords is None) == (shape is None):
-        raise ValueError("derivatives takes exactly one of coords and shape")
-    ops.require_gpu()
-    desc = model.desc()
-    flat = model._flat(desc)
-    Bd = None if B is None else B.detach().to(flat.device, torch.float32).contiguous()
-    with torch.no_grad():
-        if coords is not None:
-            lead, d = tuple(coords.shape[:-1]), int(coords.shape[-1])
-            x = coords.detach().to(flat.device, torch.float32).reshape(-1, d).contiguous()
-            y, g, lap = ops.wire_derivatives(desc, flat, x=x, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian),
-                                             chunk_rows=chunk_rows)
-        else:
-            lead = tuple(int(s) for s in shape)
-            y, g, lap = ops.wire_derivatives(desc, flat, shape=lead, B=Bd, d_tangent=d_tangent, want_lap=bool(laplacian),
-                                             chunk_rows=chunk_rows)
-    return Derivatives(y.view(*lead), g.view(*lead, g.shape[-1]), None if lap is None else lap.view(*lead))
+    def desc_and_flat():
+        ops.require_gpu()
+        desc = model.desc()
+        return desc, model._flat(desc)
+
+    return _derivatives(ops.wire_derivatives, desc_and_flat, coords, shape, B, laplacian, d_tangent, chunk_rows)

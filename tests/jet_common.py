@@ -42,10 +42,12 @@ CASES = {
     "b": dict(seed=12, d=3, hidden=64, hidden_layers=2, m=16, grid=(11, 31, 3)),  # J = 5
     "c": dict(seed=13, d=4, hidden=128, hidden_layers=3, m=128),                  # J = 6, several K steps
     "d": dict(seed=14, d=3, hidden=512, hidden_layers=3, m=16),                   # several column tiles, K = 512
+    "e": dict(seed=15, d=1, hidden=96, hidden_layers=1, m=0, grid=(1023,)),       # H no multiple of the 64-column tile; d = 1
 }
 
 
 def features(x, B):
+    """INRmodel.py:171-176 ``input_mapping``."""
     if B is None:
         return x
     p = 2.0 * math.pi * x @ B.T

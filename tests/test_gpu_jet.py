@@ -33,8 +33,8 @@ def host_case(name):
 
 
 def check_accuracy(tag, got, ref, dev32):
-    y, g, lap = got
-    errs = (jc.rel_l2(y, ref[0]), jc.rel_l2(g, ref[1]), jc.rel_l2(lap, ref[2]))
+    """``got`` = (y, grad, lap) of one call; an output the call was not asked for (None) has no error."""
+    errs = tuple(0.0 if out is None else jc.rel_l2(out, want) for out, want in zip(got, ref))
     lap_bound = max(T1, 4 * dev32)
     print(f"jet {tag}: rel-L2 y {errs[0]:.3e} grad {errs[1]:.3e} lap {errs[2]:.3e} (float32 host formulas {dev32:.3e}, "
           f"lap bound {lap_bound:.3e})")
@@ -80,7 +80,7 @@ def test_bits_do_not_depend_on_chunking_repetition_or_requested_outputs(name):
 
 
 def test_grid_entry_point_is_bit_equal_with_explicit_rows():
-    """Case e: case b as the grid 11 x 31 x 3."""
+    """Case b as the grid 11 x 31 x 3."""
     case, ref, dev32 = host_case("b")
     desc, flat, x, B = jc.on_device(case)
     assert torch.equal(inr.get_mgrid(case["grid"]), x)
@@ -90,7 +90,7 @@ def test_grid_entry_point_is_bit_equal_with_explicit_rows():
     assert ops.jet_launch_counts() == {"jet_input": 4, "jet_layer": 12, "jet_head": 4}
     for a, b in zip(grid, rows):
         assert torch.equal(a, b)
-    check_accuracy("e (grid)", grid, ref, dev32)
+    check_accuracy("b (grid)", grid, ref, dev32)
     # raw coordinates through the grid form too (case a is the grid 31 x 33)
     case_a, ref_a, dev_a = host_case("a")
     desc_a, flat_a, x_a, _ = jc.on_device(case_a)
@@ -99,19 +99,29 @@ def test_grid_entry_point_is_bit_equal_with_explicit_rows():
         assert torch.equal(a, b)
 
 
-def test_d_tangent_names_the_leading_axes():
-    """4-D input, tangents along the three leading axes: the gradient equals those columns of the full call bit for bit, and the
-    Laplacian the float64 restatement summed over those axes only."""
-    case, ref, _ = host_case("c")
+@pytest.mark.parametrize("name,dt", [("c", 1), ("c", 2), ("c", 3), ("c", 4), ("e", 1)])
+def test_d_tangent_names_the_leading_axes(name, dt):
+    """Tangents along the ``dt`` leading axes of the 4-D case c (and the one axis of case e): the gradient equals those columns of
+    the full call bit for bit, and the Laplacian the float64 restatement summed over those axes only.  Each ``dt`` runs with the
+    Laplacian, without it and without either derivative: together every (tangents, Laplacian) pair the layer kernel is built
+    for, each against float64."""
+    case, ref, _ = host_case(name)
     desc, flat, x, B = jc.on_device(case)
     full = ops.siren_jet(desc, flat, x=x, B=B, chunk_rows=jc.CHUNK)
-    y, g, lap = ops.siren_jet(desc, flat, x=x, B=B, d_tangent=3, chunk_rows=jc.CHUNK)
-    assert tuple(g.shape) == (jc.ROWS, 3)
-    assert torch.equal(y, full[0]) and torch.equal(g, full[1][:, :3].contiguous())
-    ref3 = jc.autograd_reference(case, 3)
-    dev32 = jc.rel_l2(jc.forward_jet(case, torch.float32, 3)[2], ref3[2])
-    check_accuracy("c (d_tangent = 3)", (y, g, lap), ref3, dev32)
-    assert jc.rel_l2(ref3[2], ref[2]) > 1e-2          # the fourth axis does contribute: the two Laplacians differ
+    y, g, lap = ops.siren_jet(desc, flat, x=x, B=B, d_tangent=dt, chunk_rows=jc.CHUNK)
+    assert tuple(g.shape) == (jc.ROWS, dt)
+    assert torch.equal(y, full[0]) and torch.equal(g, full[1][:, :dt].contiguous())
+    ref_dt = jc.autograd_reference(case, dt)
+    dev32 = jc.rel_l2(jc.forward_jet(case, torch.float32, dt)[2], ref_dt[2])
+    check_accuracy(f"{name} (d_tangent = {dt})", (y, g, lap), ref_dt, dev32)
+    if dt < case["d"]:
+        assert jc.rel_l2(ref_dt[2], ref[2]) > 1e-2    # the axes left out do contribute: the two Laplacians differ
+    no_lap = ops.siren_jet(desc, flat, x=x, B=B, d_tangent=dt, want_lap=False, chunk_rows=jc.CHUNK)
+    assert no_lap[2] is None
+    check_accuracy(f"{name} (d_tangent = {dt}, no Laplacian)", no_lap, ref_dt, dev32)
+    value = ops.siren_jet(desc, flat, x=x, B=B, d_tangent=dt, want_grad=False, want_lap=False, chunk_rows=jc.CHUNK)
+    assert value[1] is None and value[2] is None
+    check_accuracy(f"{name} (value only)", value, ref_dt, dev32)
 
 
 def _model_case(model, x, B=None):

@@ -46,8 +46,8 @@ def run(case, **kw):
 
 
 def check_accuracy(tag, got, ref, dev32):
-    y, g, lap = got
-    errs = (wc.rel_l2(y, ref[0]), wc.rel_l2(g, ref[1]), wc.rel_l2(lap, ref[2]))
+    """``got`` = (y, grad, lap) of one call; an output the call was not asked for (None) has no error."""
+    errs = tuple(0.0 if out is None else wc.rel_l2(out, want) for out, want in zip(got, ref))
     lap_bound = max(T1, 4 * dev32)
     print(f"wire derivatives {tag}: rel-L2 y {errs[0]:.3e} grad {errs[1]:.3e} lap {errs[2]:.3e} (float32 host formulas "
           f"{dev32:.3e}, lap bound {lap_bound:.3e})")
@@ -108,6 +108,31 @@ def test_grid_entry_point_is_bit_equal_with_explicit_rows():
         for a, b in zip(grid, rows):
             assert torch.equal(a, b)
         check_accuracy(f"{name} (grid)", grid, ref, dev32)
+
+
+@pytest.mark.parametrize("dt", [1, 2, 3, 4])
+def test_d_tangent_names_the_leading_axes(dt):
+    """Case j6 (four axes) with tangents along the ``dt`` leading ones: the gradient equals those columns of the full call bit for
+    bit, and the Laplacian the float64 restatement summed over those axes only.  Each ``dt`` runs with the Laplacian, without it
+    and without either derivative: together every (tangents, Laplacian) pair the layer kernel is built for, each against
+    float64."""
+    case, ref, _ = host_case("j6")
+    n = case["x"].shape[0]
+    full = run(case)
+    y, g, lap = run(case, d_tangent=dt)
+    assert tuple(g.shape) == (n, dt)
+    assert torch.equal(y, full[0]) and torch.equal(g, full[1][:, :dt].contiguous())
+    ref_dt = wc.autograd_reference(case, dt)
+    dev32 = wc.rel_l2(wc.forward_formulas(case, torch.float32, dt)[2], ref_dt[2])
+    check_accuracy(f"j6 (d_tangent = {dt})", (y, g, lap), ref_dt, dev32)
+    if dt < case["d"]:
+        assert wc.rel_l2(ref_dt[2], ref[2]) > 1e-2    # the axes left out do contribute: the two Laplacians differ
+    no_lap = run(case, d_tangent=dt, want_lap=False)
+    assert no_lap[2] is None
+    check_accuracy(f"j6 (d_tangent = {dt}, no Laplacian)", no_lap, ref_dt, dev32)
+    value = run(case, d_tangent=dt, want_grad=False, want_lap=False)
+    assert value[1] is None and value[2] is None
+    check_accuracy("j6 (value only)", value, ref_dt, dev32)
 
 
 def test_workspace_guard_tail_stays_intact():

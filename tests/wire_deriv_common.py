@@ -13,6 +13,7 @@ import os
 import numpy as np
 import torch
 
+from jet_common import features, max_rel, mgrid_rows, rel_l2      # noqa: F401 (the tests reach them through this module)
 from mri_super_resolution_amd import wire
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wire_deriv.npz")
@@ -22,12 +23,6 @@ OMEGA = SCALE = 1.2          # wiretest.ipynb cell 7
 
 def golden():
     return np.load(GOLDEN)
-
-
-def mgrid_rows(shape):
-    """get_mgrid(shape) on the host in float32 (torch.linspace, 'ij' meshgrid, last axis fastest)."""
-    axes = [torch.linspace(-1, 1, steps=int(s)) for s in shape]
-    return torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1).reshape(-1, len(shape)).contiguous()
 
 
 # name -> what make_case takes.  The smallest shapes at which the kernels can still go wrong (32-row, 32-unit tiles; K blocks of 32):
@@ -84,14 +79,6 @@ def leaves(model, double=True):
         v = v.detach().cpu()
         out[k] = v.to(torch.complex128 if v.is_complex() else torch.float64) if double else v.clone()
     return out
-
-
-def features(x, B):
-    """INRmodel.py:171-176 ``input_mapping``."""
-    if B is None:
-        return x
-    p = (2.0 * math.pi * x) @ B.T
-    return torch.cat([torch.sin(p), torch.cos(p)], dim=-1)
 
 
 def network(P, layers, feats):
@@ -180,16 +167,6 @@ def forward_formulas(case, dtype, d_tangent=None):
     dot = lambda pl: pl[0] @ w_r - pl[1] @ w_i      # noqa: E731
     grad = torch.stack([dot(ti) for ti in t], dim=-1) if t else torch.zeros(x.shape[0], 0, dtype=dtype)
     return dot(a) + hb.real.to(dtype)[0], grad, dot(q)
-
-
-def rel_l2(got, want):
-    got, want = torch.as_tensor(got).double().cpu().reshape(-1), torch.as_tensor(want).double().cpu().reshape(-1)
-    return float((got - want).norm() / want.norm())
-
-
-def max_rel(got, want):
-    got, want = torch.as_tensor(got).double().cpu().reshape(-1), torch.as_tensor(want).double().cpu().reshape(-1)
-    return float((got - want).abs().max() / want.abs().max())
 
 
 def on_device(case):
