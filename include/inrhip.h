@@ -518,6 +518,48 @@ int inr_tvsr_solve2d_f32(float* out, double* energy, double* change, const float
                          int height, int width, int f0, int f1, const double* kernel, double lambda, double alpha, int n_iter,
                          double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- the same on volumes: a slice profile in the operator, a 3-D prior, one volume over many workgroups ----------------
+ * Volumes are [n_volumes][D][H][W] (HR) and [n_volumes][d][h][w] (LR), D = f0 d, H = f1 h, W = f2 w, factors 1 .. INR_TVSR_MAX_FACTOR,
+ * D, H, W <= INR_TVSR_MAX_SIDE; indices are 64-bit.  k0 [f0] (the slice profile), k1 [f1], k2 [f2] are HOST arrays of finite doubles,
+ * each summing to 1 (to 1e-9); the block kernel is k[a][b][c] = (k1[b] * k2[c]) * k0[a], formed in fp64 in that order.
+ *   (A x)[l][i][j] = sum_{a, b, c} k[a][b][c] x[f0 l + a][f1 i + b][f2 j + c] (the terms added in ascending (a, b, c)),  A A^T = |k|^2 I
+ *   with |k|^2 summed over the formed table in memory order;  grad = (g0 d0, g1 d1, g2 d2): forward differences along slice / row /
+ *   column with a zero last plane / row / column, scaled by the HOST weights grad_weights = {g0, g1, g2}, finite and >= 0 (the voxel
+ *   spacing: g0 = in-plane spacing / slice spacing);  div = -grad^T.
+ * inr_tvsr3d_block_apply: out [n][d][h][w] = A in.  inr_tvsr3d_block_adjoint: out [n][D][H][W] = A^T in.  fp64, one launch, out must not
+ *   overlap in.
+ * inr_tvsr3d_solve: out = n_iter iterations of the Chambolle-Pock iteration of inr_tvsr_solve2d on
+ *   min_x 1/2 sum_i w_i ((A x)_i - y_i)^2 + lambda sum_j H_alpha(sqrt((g1 d1 x)_j^2 + (g2 d2 x)_j^2 + (g0 d0 x)_j^2))
+ *   with tau = sigma = 1 / sqrt(4 sum g_a^2), the sum in the order (1, 2, 0) over the axes whose HR extent exceeds 1 (a zero sum: the
+ *   prior vanishes -- lambda = 0, tau = 1 / sqrt(8)).  Wherever the 2-D iteration combines its two axes this one combines row, column,
+ *   then slice: div p = + g1 p1[e] - g1 p1[e - W] + g2 p2[e] - g2 p2[e - 1] + g0 p0[e] - g0 p0[e - HW], |q| = sqrt((q1^2 + q2^2) +
+ *   q0^2); so D == 1 or g0 == 0 (with g1 = g2 = 1) is inr_tvsr_solve2d of every slice with the kernel k1[b] * k2[c], bit for bit.
+ *   Op sequence: init (x = xbar = x0 or the block replication of y, p = 0); per iteration a dual launch (thread per voxel; skipped
+ *   for lambda == 0) and a primal launch (workgroup per tile of whole LR blocks); a final launch (the result, the objective's
+ *   partials) and a fixed-order finish (energy, change).  Plain launches on `stream`, no host read, no float atomics: calls are
+ *   bit-equal on any stream and at any place in a batch.  y, weight, x0, energy, change: as for inr_tvsr_solve2d.  The _f32 form
+ *   reads y / weight / x0 and writes out as fp32, with fp64 inside, and rounds once (energy is that of the fp64 volume).
+ *   n_volumes == 0 succeeds and launches nothing.
+ * workspace: inr_tvsr3d_workspace_doubles(n_volumes, D, H, W, f0, f1, f2) doubles (the state x | xbar | p0 | p1 | p2 of every volume
+ * and the partials of energy and change), 16-byte aligned; 0 for sizes that would be refused.  Refusals, all before any device work:
+ * INR_E_INVALID (null out / y / in / factors / grad_weights, n_volumes < 0, factors or sizes out of range, an extent no multiple of
+ * its factor, n_iter outside 0 .. INR_TVSR3D_MAX_ITER, a negative or non-finite lambda / alpha / gradient weight, a factor that is
+ * not finite or does not sum to 1), INR_E_WORKSPACE (null or short workspace), INR_E_ALIGN (workspace off a 16-byte boundary). */
+#define INR_TVSR3D_MAX_ITER 100000
+int inr_tvsr3d_block_apply(double* out, const double* in, int n_volumes, int depth, int height, int width, int f0, int f1, int f2,
+                      const double* k0, const double* k1, const double* k2, void* stream);
+int inr_tvsr3d_block_adjoint(double* out, const double* in, int n_volumes, int depth, int height, int width, int f0, int f1, int f2,
+                        const double* k0, const double* k1, const double* k2, void* stream);
+int64_t inr_tvsr3d_workspace_doubles(int n_volumes, int depth, int height, int width, int f0, int f1, int f2);
+int inr_tvsr3d_solve(double* out, double* energy, double* change, const double* y, const double* weight, const double* x0, int n_volumes,
+                     int depth, int height, int width, int f0, int f1, int f2, const double* k0, const double* k1, const double* k2,
+                     const double* grad_weights, double lambda, double alpha, int n_iter, double* workspace, int64_t workspace_doubles,
+                     void* stream);
+int inr_tvsr3d_solve_f32(float* out, double* energy, double* change, const float* y, const float* weight, const float* x0, int n_volumes,
+                         int depth, int height, int width, int f0, int f1, int f2, const double* k0, const double* k1, const double* k2,
+                         const double* grad_weights, double lambda, double alpha, int n_iter, double* workspace,
+                         int64_t workspace_doubles, void* stream);
+
 /* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
  * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
  * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output

@@ -24,7 +24,7 @@ INR_LF_ERD_STEP, INR_LF_ERD_REDUCE, INR_LF_ERD_FORWARD, INR_LF_ERD_SOFT = 32, 33
 INR_ERD_RUNNING, INR_ERD_CONVERGED, INR_ERD_COLLAPSED = 0, 1, 2
 INR_RESCALE_REFLECT, INR_RESCALE_EDGE, INR_RESCALE_MAX_RADIUS, INR_RESCALE_MAX_LINE = 0, 1, 64, 4096
 INR_FOURIER_SAMPLE, INR_FOURIER_CENTER, INR_FOURIER_PERIODIC, INR_FOURIER_MIRROR, INR_FOURIER_MAX_LINE = 0, 1, 0, 1, 1024
-INR_TVSR_MAX_FACTOR, INR_TVSR_MAX_SIDE = 8, 1024
+INR_TVSR_MAX_FACTOR, INR_TVSR_MAX_SIDE, INR_TVSR3D_MAX_ITER = 8, 1024, 100000
 
 
 class InrHipError(RuntimeError):
@@ -179,6 +179,13 @@ SIGNATURES = {
     "inr_tvsr_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                        C.c_int, C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64,
                                        c_stream]),
+    "inr_tvsr3d_block_apply": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_double)] * 3 + [c_stream]),
+    "inr_tvsr3d_block_adjoint": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_double)] * 3 + [c_stream]),
+    "inr_tvsr3d_workspace_doubles": (C.c_int64, [C.c_int] * 7),
+    "inr_tvsr3d_solve": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 7 + [C.POINTER(C.c_double)] * 4 + [C.c_double, C.c_double, C.c_int,
+                                                                                                 C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvsr3d_solve_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 7 +
+                             [C.POINTER(C.c_double)] * 4 + [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
     "inr_footprint_expand": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
     "inr_footprint_reduce": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_footprint_loss_workspace_floats": (C.c_int64, [C.c_int64]),

@@ -27,6 +27,10 @@ DESIGN.md 4j).
 ``tv_superres``, ``block_apply`` and ``block_adjoint`` are not the reference's either: the classical model-based reconstruction --
 the block operator ``A`` of the acquisition (block mean or decimation), no network, a TV / Huber prior, Chambolle-Pock on the
 device (``inr_tvsr_solve2d``) -- the comparator that says how much of a forward-model fit's gain is the model's.
+
+``tv_superres3d``, ``block_apply3d``, ``block_adjoint3d`` and ``slice_profile`` are the same reconstruction on volumes: a separable
+block operator whose first factor is the slice profile, a 3-D prior with per-axis gradient weights, one volume over many workgroups
+(``inr_tvsr3d_solve``) -- what the through-plane study (``scripts/through_plane``) scores beside the spline.
 """
 from __future__ import annotations
 
@@ -329,6 +333,166 @@ def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, hube
     extra = {name: None if value is None else _block_batch(value, as_numpy) for name, value in extra.items()}
     out, energy, change = ops.tvsr_solve(y, (f0, f1), k, lam, huber, int(n_iter), extra["weight"], extra["x0"])
     out = out.reshape(*lead, h * f0, w * f1)
+    energy, change = energy.reshape(lead), change.reshape(lead)
+    if as_numpy:
+        out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
+    return (out, {"energy": energy, "change": change}) if return_info else out
+
+
+TV3D_DEFAULT_LAMBDA, TV3D_DEFAULT_HUBER, TV3D_DEFAULT_ITERS = 3e-3, 0.1, 300   # the sweep of DESIGN.md 4m
+TV3D_DEFAULT_GRAD_WEIGHTS = (1.0, 1.0, 1.0)
+
+
+def slice_profile(f, kind: str = "mean", fwhm=None):
+    """The slice profile k0 [f] of a thick slice made of ``f`` thin ones, as a float64 ndarray that sums to 1: 'mean' (a box over the
+    thick slice), 'decimate' (its first thin slice) or 'gaussian' -- a Gaussian of full width at half maximum ``fwhm``, in THICK
+    slices, centred on the thick slice and sampled at the centres of its ``f`` thin slices (positions ``(a + 1/2) / f - 1/2``), the
+    samples normalised to sum 1.  ``fwhm`` belongs to 'gaussian' alone."""
+    who = "slice_profile"
+    if int(f) != f or not 1 <= int(f) <= ops.TVSR_MAX_FACTOR:
+        raise ValueError(f"{who}: f is an integer 1 .. {ops.TVSR_MAX_FACTOR} (got {f!r})")
+    f = int(f)
+    if kind != "gaussian" and fwhm is not None:
+        raise ValueError(f"{who}: fwhm belongs to kind='gaussian' (got kind={kind!r})")
+    if kind == "mean":
+        return np.full(f, 1.0 / f)
+    if kind == "decimate":
+        k = np.zeros(f)
+        k[0] = 1.0
+        return k
+    if kind == "gaussian":
+        if fwhm is None or not 0.0 < float(fwhm) < np.inf:
+            raise ValueError(f"{who}: kind='gaussian' needs a finite fwhm > 0, in thick slices (got {fwhm!r})")
+        sigma = float(fwhm) / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+        pos = (2.0 * np.arange(f) + 1.0 - f) / (2.0 * f)        # (a + 1/2) / f - 1/2, antisymmetric to the bit
+        k = np.exp(-0.5 * (pos / sigma) ** 2)
+        if not k.sum() > 0.0:
+            raise ValueError(f"{who}: fwhm {fwhm!r} is too narrow: every sample of the Gaussian underflows")
+        return k / k.sum()
+    raise ValueError(f"{who}: kind must be 'mean', 'decimate' or 'gaussian' (got {kind!r})")
+
+
+def _block_kernel3d(who, kernel, factors):
+    """'mean', 'decimate' or a triple of 1-D arrays (k0 [f0], k1 [f1], k2 [f2]) -> ((f0, f1, f2), three float lists), refusing by name."""
+    try:
+        f = tuple(int(v) for v in factors)
+        if len(f) != 3:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: factors are (f0, f1, f2), one per trailing axis (got {factors!r})") from None
+    if not all(1 <= v <= ops.TVSR_MAX_FACTOR for v in f):
+        raise ValueError(f"{who}: factors are 1 .. {ops.TVSR_MAX_FACTOR} per axis (got {f[0]} x {f[1]} x {f[2]})")
+    if isinstance(kernel, str):
+        if kernel not in ("mean", "decimate"):
+            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2) (got {kernel!r})")
+        ks = [slice_profile(v, kernel) for v in f]
+    else:
+        try:
+            ks = [np.asarray(k, dtype=np.float64) for k in kernel]
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2)") from None
+        if len(ks) != 3 or any(k.shape != (v,) for k, v in zip(ks, f)):
+            raise ValueError(f"{who}: the kernel factors must be 1-D arrays of {f[0]}, {f[1]} and {f[2]} entries "
+                             f"(got {[k.shape for k in ks]})")
+        for axis, k in enumerate(ks):
+            if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
+                raise ValueError(f"{who}: kernel factor k{axis} must be finite and sum to 1 (got sum {k.sum()!r})")
+    return f, [k.tolist() for k in ks]
+
+
+def _volume_input(who, volume, name="input"):
+    """Refuses by name what is no batch of volumes; -> (True for an ndarray, (slices, rows, columns), leading shape)."""
+    as_numpy = _fourier_input(who, volume)
+    if volume.ndim < 3:
+        raise ValueError(f"{who} needs at least 3-D {name}")
+    return as_numpy, tuple(int(v) for v in volume.shape[-3:]), tuple(volume.shape[:-3])
+
+
+def _volume_batch(volume, as_numpy):
+    """-> the device tensor [n, slices, rows, columns] (an ndarray as float64)."""
+    x = torch.from_numpy(np.ascontiguousarray(volume, dtype=np.float64)).to(ops.require_gpu()) if as_numpy else volume
+    return x.reshape(-1, *x.shape[-3:]).contiguous()
+
+
+def _hr_sides3d(who, hr, f):
+    if any(s < 1 or s > ops.TVSR_MAX_SIDE for s in hr):
+        raise ValueError(f"{who}: HR volumes of 1 .. {ops.TVSR_MAX_SIDE} samples per axis (got {hr[0]} x {hr[1]} x {hr[2]})")
+    if any(s % v for s, v in zip(hr, f)):
+        raise ValueError(f"{who}: the HR volume {hr[0]} x {hr[1]} x {hr[2]} is no whole number of {f[0]} x {f[1]} x {f[2]} blocks")
+
+
+def block_apply3d(x, factors, kernel="mean"):
+    """``A x`` on volumes: every ``f0 x f1 x f2`` block of the trailing three axes (slice, row, column) of ``x`` summed with the
+    separable weights ``k[a][b][c] = (k1[b] k2[c]) k0[a]`` -- ``kernel`` 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2),
+    each summing to 1; k0 is the slice profile (``slice_profile``) -- (``inr_tvsr3d_block_apply``, fp64).  Leading axes are
+    a batch; ndarray in -> float64 ndarray out, device fp32 / fp64 tensor in -> the same out."""
+    f, k = _block_kernel3d("block_apply3d", kernel, factors)
+    as_numpy, hr, lead = _volume_input("block_apply3d", x)
+    _hr_sides3d("block_apply3d", hr, f)
+    flat = _volume_batch(x, as_numpy)
+    out = ops.block_apply3d(flat.double(), f, k).to(flat.dtype).reshape(*lead, *(s // v for s, v in zip(hr, f)))
+    return out.cpu().numpy() if as_numpy else out
+
+
+def block_adjoint3d(r, factors, kernel="mean"):
+    """``A^T r`` on volumes: ``k[a][b][c] r[l][i][j]`` spread over block (l, i, j) (``inr_tvsr3d_block_adjoint``); types as
+    ``block_apply3d``."""
+    f, k = _block_kernel3d("block_adjoint3d", kernel, factors)
+    as_numpy, lr, lead = _volume_input("block_adjoint3d", r)
+    hr = tuple(s * v for s, v in zip(lr, f))
+    _hr_sides3d("block_adjoint3d", hr, f)
+    flat = _volume_batch(r, as_numpy)
+    out = ops.block_adjoint3d(flat.double(), f, k).to(flat.dtype).reshape(*lead, *hr)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def tv_superres3d(lr, factors, kernel="mean", lam: float = TV3D_DEFAULT_LAMBDA, huber: float = TV3D_DEFAULT_HUBER,
+                  n_iter: int = TV3D_DEFAULT_ITERS, grad_weights=TV3D_DEFAULT_GRAD_WEIGHTS, weight=None, x0=None,
+                  return_info: bool = False):
+    """Model-based super-resolution of the trailing three axes (slice, row, column) of ``lr`` by ``factors`` = (f0, f1, f2), 1 .. 8
+    each: ``n_iter`` Chambolle-Pock iterations on ``1/2 sum w (A x - lr)^2 + lam sum H_huber(|grad x|)`` with the block operator
+    ``A`` of ``block_apply3d`` -- ``kernel`` 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2), k0 the slice profile -- and
+    the forward-difference gradient scaled per axis by ``grad_weights`` = (g0, g1, g2) >= 0 (slice, row, column; the voxel spacing:
+    g0 = in-plane spacing / slice spacing; g0 = 0 uncouples the slices, which then are ``tv_superres`` of each, bit for bit).
+    ``huber``, ``lam``, ``weight`` (shape of ``lr``) and ``x0`` (HR shape) as for ``tv_superres``.  Leading axes are a batch; a
+    volume is spread over many workgroups, two plain launches per iteration (``inr_tvsr3d_solve``).  ndarray in ->
+    float64 ndarray out; device fp32 / fp64 tensor in -> the same out (fp64 inside, rounded once).  There is no CPU fallback.
+    ``return_info``: also a dict with ``energy`` and ``change``, both of the leading shape."""
+    who = "tv_superres3d"
+    f, k = _block_kernel3d(who, kernel, factors)
+    lam, huber = float(lam), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or not 0 <= n_iter <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: n_iter must be an integer 0 .. {ops.TVSR3D_MAX_ITER} (got {n_iter!r})")
+    try:
+        g = tuple(float(v) for v in grad_weights)
+    except (TypeError, ValueError):
+        g = ()
+    if len(g) != 3 or not all(0.0 <= v < np.inf for v in g):
+        raise ValueError(f"{who}: grad_weights are (g0, g1, g2), finite and >= 0 (got {grad_weights!r})")
+    as_numpy, lo, lead = _volume_input(who, lr)
+    hr = tuple(s * v for s, v in zip(lo, f))
+    _hr_sides3d(who, hr, f)
+    extra = {}
+    for name, value, shape in (("weight", weight, lo), ("x0", x0, hr)):
+        if value is None:
+            extra[name] = None
+            continue
+        if isinstance(value, np.ndarray) != as_numpy:
+            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
+        _fourier_input(who, value)
+        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
+            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
+        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
+            raise ValueError(f"{who}: weight must be finite and >= 0")
+        extra[name] = value
+    y = _volume_batch(lr, as_numpy)
+    extra = {name: None if value is None else _volume_batch(value, as_numpy) for name, value in extra.items()}
+    out, energy, change = ops.tvsr_solve3d(y, f, k, lam, huber, int(n_iter), g, extra["weight"], extra["x0"])
+    out = out.reshape(*lead, *hr)
     energy, change = energy.reshape(lead), change.reshape(lead)
     if as_numpy:
         out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()

@@ -99,7 +99,7 @@ extern tune_int g_hp_head_rows;                   // key 23
 extern tune_int g_hp_row, g_hp_row_min_tiles;     // keys 27, 28: the row-owning 128 x 512 kernel
 extern tune_int g_hp_narrow_max_tiles;            // key 29
 extern tune_int g_hp_row_head, g_hp_row_head_min_tiles;   // keys 30, 31: the head step fused into the last sine layer
-extern tune_int g_hp_grid_cap;                    // key 32: test-only cap on the persistent grids
+extern tune_int g_hp_grid_cap;                    // key 32: test-only cap on the persistent grids (and on tvsr3d.hip's stride-loop grids)
 
 // ---- kernels.hip ----------------------------------------------------------------------------------------------------------------------
 int launch_mgrid(float* out, const int64_t* shape, int dim, int64_t row_begin, int64_t n_rows, hipStream_t st);

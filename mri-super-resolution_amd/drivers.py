@@ -932,3 +932,96 @@ def david_study(case, rule: int = 1, slices="cancer"):
         case.accept[:, :, idx, :] = block
     rows = david_rows(case, res, idx.index(int(case.cancer_slice)))
     return {"rows": rows, "maps": res._asdict(), "slices": idx}
+
+
+# ---------------------------------------------------------------------------------------------------
+# The through-plane study: thick slices from thin ones by a slice profile, and back by four methods -- scored, since
+# here the thin slices are the ground truth that ``--transverse_length`` never had
+# ---------------------------------------------------------------------------------------------------
+THROUGH_PLANE_METHODS = ("replicate", "spline", "zerofill", "tv3d")
+
+
+def check_through_plane(factor=2, profile="mean", fwhm=None, tv_lambda=3e-3, tv_huber=0.1, tv_iters=300, tv_gz=1.0, with_inr=False,
+                        footprint="point", number_of_epochs=2500):
+    """What ``through_plane_study`` cannot serve, by name; touches neither the input nor the device."""
+    who = "through_plane_study"
+    if int(factor) != factor or not 2 <= factor <= ops.TVSR_MAX_FACTOR:
+        raise ValueError(f"{who}: factor is the number of thin slices per thick one, 2 .. {ops.TVSR_MAX_FACTOR} (got {factor!r})")
+    if profile not in ("mean", "gaussian"):
+        raise ValueError(f"{who}: profile must be 'mean' or 'gaussian' (got {profile!r})")
+    if profile == "gaussian" and (fwhm is None or not 0.0 < float(fwhm) < float("inf")):
+        raise ValueError(f"{who}: the gaussian profile needs a finite fwhm > 0, in thick slices (got {fwhm!r})")
+    for name, value in (("tv_lambda", tv_lambda), ("tv_huber", tv_huber), ("tv_gz", tv_gz)):
+        if not 0.0 <= float(value) < float("inf"):
+            raise ValueError(f"{who}: {name} must be finite and >= 0 (got {value!r})")
+    if int(tv_iters) != tv_iters or not 1 <= tv_iters <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: tv_iters must be 1 .. 100,000 (got {tv_iters!r})")
+    if footprint not in ("point", "box"):
+        raise ValueError(f"{who}: footprint must be 'point' or 'box' (got {footprint!r})")
+    if with_inr:
+        if factor != 2 or profile != "mean":
+            raise ValueError(f"{who}: with_inr fits fit_volume's lr_model='average', the mean of 2 slices: factor 2 and the mean "
+                             f"profile only (got factor {factor}, profile {profile!r})")
+        if int(number_of_epochs) != number_of_epochs or number_of_epochs < 1:
+            raise ValueError(f"{who}: number_of_epochs must be >= 1 (got {number_of_epochs!r})")
+
+
+def through_plane_study(volume, factor=2, profile="mean", fwhm=None, tv_lambda=None, tv_huber=None, tv_iters=None, tv_gz=1.0,
+                        with_inr=False, footprint="point", number_of_epochs=2500, seed=0):
+    """``volume`` [X, Y, Z, B] (or [X, Y, Z]) in [0, 1], thin slices along Z: the thick slices ``block_apply3d(HR, (factor, 1, 1),
+    profile)`` of Z trimmed to a multiple of ``factor``, and their reconstructions on the thin slices, all on the device:
+    ``replicate`` (every thick slice ``factor`` times), ``spline`` (``baselines.resize_z``, the cubic spline along z of
+    ``--transverse_length``), ``zerofill`` (``baselines.fourier_resample`` along z, ``align='center'``, ``boundary='mirror'``,
+    clamped at 0) and ``tv3d`` (``baselines.tv_superres3d`` with the profile in its operator and gradient weights ``(tv_gz, 1, 1)``;
+    the ``TV3D_DEFAULT_*`` where an argument is None).  ``with_inr``: also ``sr``, ``fit_volume`` as it is on the z-first volume
+    (``upscale_axes=1, lr_model='average'``, ``footprint`` 'point' -> None or 'box'), for factor 2 and the mean profile only.
+    Returns ``{"volumes", "psnr", "ssim", "consistency", "kernel"}``: fp32 device stacks [Z, B, X, Y] (``hr``, ``thick`` [Z /
+    factor, ...] and the methods), PSNR (data range 1) and SSIM by the reference protocol [Z, B] per method, and the PSNR of
+    ``A tv3d`` against the thick slices."""
+    from . import baselines
+
+    lam = baselines.TV3D_DEFAULT_LAMBDA if tv_lambda is None else tv_lambda
+    huber = baselines.TV3D_DEFAULT_HUBER if tv_huber is None else tv_huber
+    iters = baselines.TV3D_DEFAULT_ITERS if tv_iters is None else tv_iters
+    check_through_plane(factor, profile, fwhm, lam, huber, iters, tv_gz, with_inr, footprint, number_of_epochs)
+    vol = np.asarray(volume)
+    if vol.ndim == 3:
+        vol = vol[..., None]
+    if vol.ndim != 4:
+        raise ValueError(f"through_plane_study: the volume is [X, Y, Z, B] or [X, Y, Z] (got {vol.shape})")
+    Z = vol.shape[2] - vol.shape[2] % factor
+    if Z // factor < 4:
+        raise ValueError(f"through_plane_study: {vol.shape[2]} slices make {Z // factor} thick slices of {factor}; the cubic spline along z "
+                         f"needs at least 4")
+    vol = vol[:, :, :Z]
+    dev = ops.require_gpu()
+    hr = torch.from_numpy(np.ascontiguousarray(vol, dtype=np.float32)).to(dev).permute(3, 2, 0, 1).contiguous()     # [B, Z, X, Y]
+    kernel = (baselines.slice_profile(factor, profile, fwhm if profile == "gaussian" else None), np.ones(1), np.ones(1))
+    f = (factor, 1, 1)
+    thick = baselines.block_apply3d(hr, f, kernel)
+    recon = {"replicate": thick.repeat_interleave(factor, dim=1),
+             "spline": baselines.resize_z(thick.permute(0, 2, 3, 1).contiguous(), Z).permute(0, 3, 1, 2).float().contiguous(),
+             "zerofill": baselines.fourier_resample(thick, Z, axis=1, align="center", boundary="mirror").clamp_min(0),
+             "tv3d": baselines.tv_superres3d(thick, f, kernel, lam, huber, int(iters), (float(tv_gz), 1.0, 1.0))}
+    consistency = float(metrics.psnr(thick, baselines.block_apply3d(recon["tv3d"], f, kernel), 1.0))
+    info = {}
+    if with_inr:
+        zfirst = np.ascontiguousarray(np.moveaxis(vol, 2, 0))                                                      # [Z, X, Y, B]
+        res = fit_volume(zfirst, steps=int(number_of_epochs), seed=seed, upscale_axes=1, lr_model="average",
+                         footprint=None if footprint == "point" else "box", return_recon=False)
+        sr = reconstruct(res["model"], zfirst.shape, res["B"]) * float(res["scale_back"])                          # on the thin slices
+        recon["sr"] = sr.permute(3, 0, 1, 2).contiguous()
+        info = {"inr_status": res["status"], "inr_final_loss": res["final_loss"], "inr_footprint_samples": res["footprint_samples"],
+                "inr_lr_consistency_psnr_db": res["lr_consistency_psnr_db"]}
+    stack = lambda t: t.permute(1, 0, 2, 3).contiguous()                                                           # [Z, B, X, Y]
+    hs = stack(hr)
+    ok = hs.amax(dim=(-2, -1)) > 0
+    safe = lambda t: torch.where(ok[..., None, None], t, torch.ones_like(t)).clamp_min(1e-30)    # empty slices: finite, ignored
+    volumes = {"hr": hs, "thick": stack(thick)}
+    psnr, ssim = {}, {}
+    for name, v in recon.items():
+        volumes[name] = stack(v)
+        psnr[name] = float(metrics.psnr(hs, volumes[name], 1.0))
+        ssim[name] = metrics.ssim_reference_protocol(safe(hs), safe(volumes[name])).cpu().numpy()
+    return {"volumes": volumes, "psnr": psnr, "ssim": ssim, "consistency": consistency, "kernel": kernel, "valid": ok.cpu().numpy(),
+            "info": info}

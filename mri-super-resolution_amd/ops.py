@@ -790,6 +790,116 @@ def tvsr_solve(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_ite
     return out, energy, change
 
 
+# ---- the same on volumes: slice profile, 3-D prior, many workgroups per volume (include/inrhip.h) ----------------------
+TVSR3D_MAX_ITER = _lib.INR_TVSR3D_MAX_ITER
+
+
+def _chk_volumes(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
+    """A contiguous device batch [n, slices, rows, columns] of one of ``dtypes``."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
+    if t.dim() != 4 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [n, slices, rows, columns] batch (got {tuple(t.shape)})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def _block_factors3d(kernel, factors):
+    """The HOST factors (k0 [f0], k1 [f1], k2 [f2]) as the C arrays the entry points take; refuses what they would refuse."""
+    f = tuple(int(v) for v in factors)
+    if len(f) != 3 or not all(1 <= v <= TVSR_MAX_FACTOR for v in f):
+        raise ValueError(f"block factors are three of 1 .. {TVSR_MAX_FACTOR} (got {tuple(factors)})")
+    if len(kernel) != 3:
+        raise ValueError("the block kernel is a triple of 1-D factors (k0 [f0], k1 [f1], k2 [f2])")
+    arrays = []
+    for axis, (k, fa) in enumerate(zip(kernel, f)):
+        flat = [float(v) for v in k]
+        if len(flat) != fa:
+            raise ValueError(f"kernel factor k{axis} must have {fa} entries (got {len(flat)})")
+        if not all(v == v and abs(v) != float("inf") for v in flat) or abs(sum(flat) - 1.0) > 1e-9:
+            raise ValueError(f"kernel factor k{axis} must be finite and sum to 1 (sum {sum(flat)!r})")
+        arrays.append((C.c_double * fa)(*flat))
+    return f, arrays
+
+
+def _hr_shape3d(name, D, H, W, f):
+    if not all(1 <= s <= TVSR_MAX_SIDE for s in (D, H, W)) or D % f[0] or H % f[1] or W % f[2]:
+        raise ValueError(f"{name}: HR volumes are 1 .. {TVSR_MAX_SIDE} samples per axis and whole {f[0]} x {f[1]} x {f[2]} blocks "
+                         f"(got {D} x {H} x {W})")
+
+
+def block_apply3d(x: torch.Tensor, factors, kernel) -> torch.Tensor:
+    """``inr_tvsr3d_block_apply``: ``x`` [n, D, H, W] float64 -> ``A x`` [n, D/f0, H/f1, W/f2]; ``kernel``: (k0, k1, k2) host values."""
+    _chk_volumes(x, "x")
+    f, k = _block_factors3d(kernel, factors)
+    n, D, H, W = x.shape
+    _hr_shape3d("block_apply3d", D, H, W, f)
+    out = torch.empty((n, D // f[0], H // f[1], W // f[2]), dtype=torch.float64, device=x.device)
+    check(lib().inr_tvsr3d_block_apply(out.data_ptr(), x.data_ptr(), n, D, H, W, *f, *k, _stream()), "inr_tvsr3d_block_apply")
+    return out
+
+
+def block_adjoint3d(r: torch.Tensor, factors, kernel) -> torch.Tensor:
+    """``inr_tvsr3d_block_adjoint``: ``r`` [n, d, h, w] float64 -> ``A^T r`` [n, f0 d, f1 h, f2 w]."""
+    _chk_volumes(r, "r")
+    f, k = _block_factors3d(kernel, factors)
+    n, d, h, w = r.shape
+    D, H, W = d * f[0], h * f[1], w * f[2]
+    _hr_shape3d("block_adjoint3d", D, H, W, f)
+    out = torch.empty((n, D, H, W), dtype=torch.float64, device=r.device)
+    check(lib().inr_tvsr3d_block_adjoint(out.data_ptr(), r.data_ptr(), n, D, H, W, *f, *k, _stream()), "inr_tvsr3d_block_adjoint")
+    return out
+
+
+def tvsr3d_workspace_doubles(n: int, D: int, H: int, W: int, factors) -> int:
+    """``inr_tvsr3d_workspace_doubles``; 0 for sizes ``inr_tvsr3d_solve`` refuses."""
+    f0, f1, f2 = (int(v) for v in factors)
+    return int(lib().inr_tvsr3d_workspace_doubles(int(n), int(D), int(H), int(W), f0, f1, f2))
+
+
+def tvsr_solve3d(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_iter: int, grad_weights=(1.0, 1.0, 1.0), weight=None,
+                 x0=None, workspace=None):
+    """``inr_tvsr3d_solve`` / ``_f32`` by the dtype of ``y`` [n, d, h, w]: returns (x [n, f0 d, f1 h, f2 w] of that dtype, energy [n]
+    float64, change [n] float64).  ``kernel``: (k0, k1, k2); ``grad_weights``: (g0, g1, g2) >= 0 for slice, row, column; ``weight``
+    [n, d, h, w] and ``x0`` [n, f0 d, f1 h, f2 w] share the dtype; ``workspace``: a float64 tensor."""
+    _chk_volumes(y, "y", (torch.float32, torch.float64))
+    f, k = _block_factors3d(kernel, factors)
+    n, d, h, w = y.shape
+    D, H, W = d * f[0], h * f[1], w * f[2]
+    _hr_shape3d("tvsr_solve3d", D, H, W, f)
+    if weight is not None:
+        _chk_volumes(weight, "weight", (y.dtype,), y.shape)
+    if x0 is not None:
+        _chk_volumes(x0, "x0", (y.dtype,), (n, D, H, W))
+    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= TVSR3D_MAX_ITER:
+        raise ValueError(f"tvsr_solve3d: lam and alpha must be finite and >= 0, n_iter 0 .. {TVSR3D_MAX_ITER} (got {lam!r}, {alpha!r}, "
+                         f"{n_iter})")
+    g = [float(v) for v in grad_weights]
+    if len(g) != 3 or not all(0.0 <= v < float("inf") for v in g):
+        raise ValueError(f"tvsr_solve3d: grad_weights are three finite values >= 0 (got {tuple(grad_weights)!r})")
+    out = torch.empty((n, D, H, W), dtype=y.dtype, device=y.device)
+    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
+    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    if n == 0:
+        return out, energy, change
+    need = tvsr3d_workspace_doubles(n, D, H, W, f)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
+    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
+        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
+    entry = "inr_tvsr3d_solve" if y.dtype == torch.float64 else "inr_tvsr3d_solve_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, D, H, W,
+                                *f, *k, (C.c_double * 3)(*g), lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()),
+          entry)
+    return out, energy, change
+
+
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
                    "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order
