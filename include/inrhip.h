@@ -560,6 +560,56 @@ int inr_tvsr3d_solve_f32(float* out, double* energy, double* change, const float
                          const double* grad_weights, double lambda, double alpha, int n_iter, double* workspace,
                          int64_t workspace_doubles, void* stream);
 
+/* ---- multi-frame TV / Huber super-resolution: K sub-pixel-shifted acquisitions of one image ---------------------------
+ * No counterpart in the reference.  Images are [n_images][H][W] (HR), frames [n_images][K][h][w] (LR), H = f0 h, W = f1 w, factors and
+ * sides as for inr_tvsr_solve2d, K = n_frames in 1 .. INR_TVMF_MAX_FRAMES; `kernel` is the HOST block kernel k [f0][f1] of
+ * inr_block_apply2d.  shifts [n_images][K][2] are DEVICE doubles, (rows, columns) in HR pixels.  Per frame and axis n = floor(s),
+ * t = s - n, and A_k = B S_k with the bilinear translation (S x)[i][j] = sum_{da, db in {0, 1}} wa wb x[i + n0 + da][j + n1 + db],
+ * wa = (1 - t0, t0)[da], wb likewise, is one sum over the effective kernel ke [f0 + 1][f1 + 1], formed on the device:
+ *   ke[a][b] = sum_{da, db} (wa wb) k[a - da][b - db] (ascending (da, db); a tap whose t is exactly 0 is not visited),
+ *   (A_k x)[i][j] = sum_{a, b} ke[a][b] x[n0 + f0 i + a][n1 + f1 j + b] (ascending (a, b); f0 (+ 1 if t0 > 0) rows, columns alike):
+ *   zero shifts give inr_block_apply2d bit for bit.
+ * A datum (k, i, j) is VALID when its footprint -- rows n0 + f0 i .. n0 + f0 i + f0 - 1 (+ 1 if t0 > 0), columns alike -- lies inside
+ * the image.  An invalid datum has weight 0 whatever `weight` holds; its y and weight are never read (they may be NaN).  A frame whose
+ * shift is not finite or exceeds 2^20 in magnitude is invalid as a whole; the range test precedes every conversion, so no shift value
+ * leads to an index outside the image.
+ * inr_frame_apply2d: out [n][K][h][w] = (A_k in)_k with 0 at invalid data; valid [n][K][h][w] bytes (1 / 0) or null.
+ * inr_frame_adjoint2d: out [n][H][W] = sum_k A_k^T in_k, a gather over the at most 2 x 2 valid LR pixels of every frame that reach an HR
+ *   pixel -- frames ascending, then LR rows, then columns; no atomics.  fp64, one launch each, out must not overlap in.
+ * inr_tvmf_solve2d: out [n][H][W] = n_iter iterations of Chambolle-Pock with both terms dual on
+ *   min_x 1/2 sum_k sum_i w_ki ((A_k x)_i - y_ki)^2 + lambda sum_j H_alpha(|(grad x)_j|)   (grad, div, H_alpha: inr_tvsr_solve2d),
+ *   from x = xbar = x0, p = 0, q = 0:
+ *     p <- (p + sigma grad(xbar)) / (1 + sigma alpha / lambda);  p <- p / max(1, |p| / lambda)   (lambda == 0: p = 0)
+ *     q_k <- (q_k + sigma (A_k xbar - y_k)) / (1 + sigma / w_k) at valid data with w_k > 0, else 0
+ *     x' <- x - tau (sum_k A_k^T q_k - div p);  xbar <- 2 x' - x;  x <- x'
+ *   tau = sigma = 1 / sqrt(8 + K' c), c = (sum |k|) (max |k|) >= |A_k|^2 for every shift, K' the number of the image's frames that hold a
+ *   valid datum (K unless a frame lies outside the image; such a frame is the zero operator).  The objective is NOT divided by K.
+ *   y [n][K][h][w]; weight [n][K][h][w] or null (= 1; finite and >= 0 -- device data, not checked; <= 0 or NaN is a missing datum); x0
+ *   [n][H][W] or null (the block replication of frame 0, all of which is then read).  energy / change / valid_fraction [n] DEVICE
+ *   doubles or null: the objective at the returned fp64 image, max |x' - x| of the last iteration (0 for n_iter == 0, which returns
+ *   x0), and the valid share of the K h w data.  Op sequence: init; per iteration a dual launch (thread per HR pixel and per LR datum)
+ *   and a primal launch (thread per HR pixel); a final launch and a fixed-order finish.  Plain launches on `stream`, no host read, no
+ *   float atomics: calls are bit-equal on any stream and at any place in a batch.  The _f32 form reads y / weight / x0 and writes out
+ *   as fp32, with fp64 inside, and rounds once.  n_images == 0 succeeds and launches nothing.
+ * workspace: inr_tvmf_workspace_doubles(n_images, K, H, W, f0, f1) doubles, 16-byte aligned; 0 for sizes that would be refused.
+ * Refusals, all before any device work: INR_E_INVALID (null out / y / in / shifts / kernel, n_images < 0, K, factors or sizes out of
+ * range, H or W no multiple of its factor, n_iter outside 0 .. INR_TVSR3D_MAX_ITER, a negative or non-finite lambda / alpha, a kernel
+ * that is not finite or does not sum to 1), INR_E_WORKSPACE (null or short workspace), INR_E_ALIGN (workspace off a 16-byte boundary). */
+#define INR_TVMF_MAX_FRAMES 64
+int inr_frame_apply2d(double* out, unsigned char* valid, const double* in, const double* shifts, int n_images, int n_frames, int height,
+                      int width, int f0, int f1, const double* kernel, void* stream);
+int inr_frame_adjoint2d(double* out, const double* in, const double* shifts, int n_images, int n_frames, int height, int width, int f0,
+                        int f1, const double* kernel, void* stream);
+int64_t inr_tvmf_workspace_doubles(int n_images, int n_frames, int height, int width, int f0, int f1);
+int inr_tvmf_solve2d(double* out, double* energy, double* change, double* valid_fraction, const double* y, const double* shifts,
+                     const double* weight, const double* x0, int n_images, int n_frames, int height, int width, int f0, int f1,
+                     const double* kernel, double lambda, double alpha, int n_iter, double* workspace, int64_t workspace_doubles,
+                     void* stream);
+int inr_tvmf_solve2d_f32(float* out, double* energy, double* change, double* valid_fraction, const float* y, const double* shifts,
+                         const float* weight, const float* x0, int n_images, int n_frames, int height, int width, int f0, int f1,
+                         const double* kernel, double lambda, double alpha, int n_iter, double* workspace, int64_t workspace_doubles,
+                         void* stream);
+
 /* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
  * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
  * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output

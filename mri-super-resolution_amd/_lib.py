@@ -24,7 +24,7 @@ INR_LF_ERD_STEP, INR_LF_ERD_REDUCE, INR_LF_ERD_FORWARD, INR_LF_ERD_SOFT = 32, 33
 INR_ERD_RUNNING, INR_ERD_CONVERGED, INR_ERD_COLLAPSED = 0, 1, 2
 INR_RESCALE_REFLECT, INR_RESCALE_EDGE, INR_RESCALE_MAX_RADIUS, INR_RESCALE_MAX_LINE = 0, 1, 64, 4096
 INR_FOURIER_SAMPLE, INR_FOURIER_CENTER, INR_FOURIER_PERIODIC, INR_FOURIER_MIRROR, INR_FOURIER_MAX_LINE = 0, 1, 0, 1, 1024
-INR_TVSR_MAX_FACTOR, INR_TVSR_MAX_SIDE, INR_TVSR3D_MAX_ITER = 8, 1024, 100000
+INR_TVSR_MAX_FACTOR, INR_TVSR_MAX_SIDE, INR_TVSR3D_MAX_ITER, INR_TVMF_MAX_FRAMES = 8, 1024, 100000, 64
 
 
 class InrHipError(RuntimeError):
@@ -186,6 +186,13 @@ SIGNATURES = {
                                                                                                  C.c_void_p, C.c_int64, c_stream]),
     "inr_tvsr3d_solve_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 7 +
                              [C.POINTER(C.c_double)] * 4 + [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "inr_frame_apply2d": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 6 + [C.POINTER(C.c_double), c_stream]),
+    "inr_frame_adjoint2d": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.POINTER(C.c_double), c_stream]),
+    "inr_tvmf_workspace_doubles": (C.c_int64, [C.c_int] * 6),
+    "inr_tvmf_solve2d": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 6 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_void_p,
+                                                                     C.c_int64, c_stream]),
+    "inr_tvmf_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, c_f32p, c_f32p] + [C.c_int] * 6 +
+                             [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
     "inr_footprint_expand": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
     "inr_footprint_reduce": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_footprint_loss_workspace_floats": (C.c_int64, [C.c_int64]),

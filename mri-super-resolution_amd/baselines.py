@@ -31,6 +31,11 @@ device (``inr_tvsr_solve2d``) -- the comparator that says how much
 ``tv_superres3d``, ``block_apply3d``, ``block_adjoint3d`` and ``slice_profile`` are the same reconstruction on volumes: a separable
 block operator whose first factor is the slice profile, a 3-D prior with per-axis gradient weights, one volume over many workgroups
 (``inr_tvsr3d_solve``) -- what the through-plane study (``scripts/through_plane``) scores beside the spline.
+
+``tv_superres_multi``, ``frame_apply``, ``frame_adjoint`` and ``estimate_shifts`` are the multi-frame form: K acquisitions of one
+image, each displaced by a fraction of a pixel, one operator ``A_k = B S_k`` per frame with a bilinear translation ``S_k``, data and
+prior both dual (``inr_tvmf_solve2d``) -- the classical comparator of the multi-image methods, which the
+register-and-average baseline is not (it aligns to whole pixels and discards what the fractions hold).
 """
 from __future__ import annotations
 
@@ -337,6 +342,175 @@ def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, hube
     if as_numpy:
         out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
     return (out, {"energy": energy, "change": change}) if return_info else out
+
+
+TVMF_DEFAULT_LAMBDA, TVMF_DEFAULT_HUBER, TVMF_DEFAULT_ITERS = 0.01, 0.03, 300  # the sweep of DESIGN.md 4n (8 frames, noise 0.02)
+
+
+def _frame_count(who, K):
+    if not 1 <= K <= ops.TVMF_MAX_FRAMES:
+        raise ValueError(f"{who}: frames per image are 1 .. {ops.TVMF_MAX_FRAMES} (got {K})")
+
+
+def _shift_input(who, shifts, lead, K=None):
+    """Refuses by name what is no shift array for images of leading shape ``lead``: [..., K, 2] or [K, 2] for all images, an array-like
+    or a float32 / float64 device tensor.  -> K.  Touches no device."""
+    if isinstance(shifts, torch.Tensor):
+        if not shifts.is_cuda:
+            raise ops.InrDeviceError(f"{who}: shifts is on {shifts.device}; pass an array or a device tensor (there is no CPU fallback)")
+        if shifts.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{who}: device shifts must be float32 or float64 (got {shifts.dtype})")
+        shape = tuple(shifts.shape)
+    else:
+        try:
+            shape = np.asarray(shifts, dtype=np.float64).shape
+        except (TypeError, ValueError):
+            raise TypeError(f"{who}: shifts must be an array [..., K, 2] or a device tensor (got {type(shifts).__name__})") from None
+    if len(shape) < 2 or shape[-1] != 2 or (len(shape) > 2 and shape[:-2] != tuple(lead)) or (K is not None and shape[-2] != K):
+        want = f"{tuple(lead) + ('K' if K is None else K, 2)} or {('K' if K is None else K, 2)}"
+        raise ValueError(f"{who}: shifts must have shape {want}, (rows, columns) in HR pixels per frame (got {shape})")
+    _frame_count(who, shape[-2])
+    return shape[-2]
+
+
+def _shift_batch(shifts, n, device):
+    """-> the device tensor [n, K, 2] float64; no host read for a device tensor."""
+    s = shifts.to(torch.float64) if isinstance(shifts, torch.Tensor) else torch.from_numpy(
+        np.ascontiguousarray(shifts, dtype=np.float64)).to(device)
+    K = s.shape[-2]
+    return (s.expand(n, K, 2) if s.dim() == 2 else s.reshape(n, K, 2)).contiguous()
+
+
+def frame_apply(x, factors, shifts, kernel="mean", return_valid: bool = False):
+    """The K frames ``A_k x = B S_k x`` of the trailing two axes of ``x``: ``S_k`` translates by ``shifts[..., k, :]`` = (rows, columns)
+    in HR pixels with bilinear weights -- ``(S x)[i] = x[i + s]`` --, ``B`` is ``block_apply`` (``inr_frame_apply2d``, fp64,
+    DESIGN.md 4n).  ``x`` [..., H, W] -> [..., K, H/f0, W/f1]; ``shifts`` [..., K, 2], or [K, 2] for all images, an array or a device
+    tensor.  A datum whose footprint leaves the image is invalid and comes back 0; ``return_valid`` adds the bool mask.  Types as
+    ``block_apply``."""
+    who = "frame_apply"
+    f0, f1, k = _block_kernel(who, kernel, factors)
+    as_numpy, H, W, lead = _block_input(who, x)
+    _hr_sides(who, H, W, f0, f1)
+    K = _shift_input(who, shifts, lead)
+    flat = _block_batch(x, as_numpy)
+    res = ops.frame_apply(flat.double(), _shift_batch(shifts, flat.shape[0], flat.device), (f0, f1), k, return_valid)
+    out, valid = res if return_valid else (res, None)
+    out = out.to(flat.dtype).reshape(*lead, K, H // f0, W // f1)
+    if return_valid:
+        valid = valid.reshape(out.shape)
+        return (out.cpu().numpy(), valid.cpu().numpy()) if as_numpy else (out, valid)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def frame_adjoint(r, factors, shifts, kernel="mean"):
+    """``sum_k A_k^T r_k``, the adjoint of ``frame_apply``: ``r`` [..., K, h, w] -> [..., f0 h, f1 w], a gather with no atomics in which
+    invalid data take no part (``inr_frame_adjoint2d``); types as ``block_apply``."""
+    who = "frame_adjoint"
+    f0, f1, k = _block_kernel(who, kernel, factors)
+    as_numpy, h, w, lead = _block_input(who, r)
+    if len(lead) < 1:
+        raise ValueError(f"{who} needs at least 3-D input [..., K, h, w]")
+    lead, K = lead[:-1], lead[-1]
+    _frame_count(who, K)
+    _hr_sides(who, h * f0, w * f1, f0, f1)
+    _shift_input(who, shifts, lead, K)
+    flat = _block_batch(r, as_numpy).reshape(-1, K, h, w)
+    out = ops.frame_adjoint(flat.double(), _shift_batch(shifts, flat.shape[0], flat.device), (f0, f1), k)
+    out = out.to(flat.dtype).reshape(*lead, h * f0, w * f1)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def tv_superres_multi(frames, factors, shifts, kernel="mean", lam: float = TVMF_DEFAULT_LAMBDA, huber: float = TVMF_DEFAULT_HUBER,
+                      n_iter: int = TVMF_DEFAULT_ITERS, weight=None, x0=None, return_info: bool = False):
+    """Multi-frame model-based super-resolution: ``frames`` [..., K, h, w] are K acquisitions of one image, frame k displaced by
+    ``shifts[..., k, :]`` = (rows, columns) HR pixels (``frame_apply``'s convention; [K, 2] serves all images; see
+    ``estimate_shifts``).  ``n_iter`` Chambolle-Pock iterations, data and prior both dual, on
+    ``1/2 sum_k sum w_k (A_k x - frames_k)^2 + lam sum H_huber(|grad x|)`` with the prior of ``tv_superres``.  The objective is NOT
+    divided by K: the data term grows with the number of frames, so ``lam`` is chosen for a frame count (the default for 8 frames at
+    noise 0.02 of a [0, 1] image; scale it with K).  A datum whose footprint leaves the image has weight 0 and is never read (it
+    may be NaN); a frame with a non-finite shift or one beyond 2^20 is ignored.  ``weight`` (shape of ``frames``, >= 0) defaults to 1,
+    ``x0`` [..., f0 h, f1 w] to the block replication of frame 0.  ``inr_tvmf_solve2d``.  ndarray in -> float64
+    ndarray out; device fp32 / fp64 tensor in -> the same out (fp64 inside, rounded once); ``weight`` / ``x0`` are given like
+    ``frames``.  There is no CPU fallback.  ``return_info``: also a dict with ``energy`` (the objective at the result), ``change``
+    (max |x' - x| of the last iteration) and ``valid_fraction`` (the valid share of the data), each of the leading shape."""
+    who = "tv_superres_multi"
+    f0, f1, k = _block_kernel(who, kernel, factors)
+    lam, huber = float(lam), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or not 0 <= n_iter <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: n_iter must be an integer in 0 .. {ops.TVSR3D_MAX_ITER} (got {n_iter!r})")
+    as_numpy, h, w, lead = _block_input(who, frames, "frames")
+    if len(lead) < 1:
+        raise ValueError(f"{who} needs at least 3-D frames [..., K, h, w]")
+    lead, K = lead[:-1], lead[-1]
+    _frame_count(who, K)
+    _hr_sides(who, h * f0, w * f1, f0, f1)
+    _shift_input(who, shifts, lead, K)
+    extra = {}
+    for name, value, shape in (("weight", weight, lead + (K, h, w)), ("x0", x0, lead + (h * f0, w * f1))):
+        if value is None:
+            extra[name] = None
+            continue
+        if isinstance(value, np.ndarray) != as_numpy:
+            raise TypeError(f"{who}: {name} must be given like frames ({'an ndarray' if as_numpy else 'a device tensor'})")
+        _fourier_input(who, value)
+        if tuple(value.shape) != shape or (not as_numpy and value.dtype != frames.dtype):
+            raise ValueError(f"{who}: {name} must have shape {shape} and the type of frames (got {tuple(value.shape)}, {value.dtype})")
+        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
+            raise ValueError(f"{who}: weight must be finite and >= 0")
+        extra[name] = value
+    y = _block_batch(frames, as_numpy).reshape(-1, K, h, w)
+    wt = None if extra["weight"] is None else _block_batch(extra["weight"], as_numpy).reshape(-1, K, h, w)
+    start = None if extra["x0"] is None else _block_batch(extra["x0"], as_numpy)
+    out, energy, change, valid = ops.tvmf_solve(y, _shift_batch(shifts, y.shape[0], y.device), (f0, f1), k, lam, huber, int(n_iter), wt,
+                                                start)
+    out = out.reshape(*lead, h * f0, w * f1)
+    info = {"energy": energy.reshape(lead), "change": change.reshape(lead), "valid_fraction": valid.reshape(lead)}
+    if as_numpy:
+        out, info = out.cpu().numpy(), {name: v.cpu().numpy() for name, v in info.items()}
+    return (out, info) if return_info else out
+
+
+def estimate_shifts(frames, factors, upsample: int = 4, max_shift=None, reference: int = 0):
+    """The shifts of ``frames`` [..., K, h, w] against frame ``reference``, for ``tv_superres_multi``: every frame is re-sampled to
+    (``upsample`` h, ``upsample`` w) by ``fourier_resize(align='center', boundary='mirror')`` and correlated with the re-sampled
+    reference by the masked normalised cross-correlation of ``registration`` with all-clear masks (two existing kernel families, no
+    new one).  The sign is ``masked_register_translation(ref, x, m)``'s -- ``x[i] ~ ref[i + s]`` --, which is ``frame_apply``'s.
+    ``max_shift`` (None: any overlap) limits the search, in LR pixels.  Returns [..., K, 2] float64 IN HR PIXELS, a multiple of the step
+    ``f / upsample`` per axis (means of equal maxima aside); the reference's row is 0.  ndarray in -> ndarray out; device tensor in ->
+    device tensor out with no host read on the way."""
+    from . import registration
+    who = "estimate_shifts"
+    try:
+        f0, f1 = (int(f) for f in factors)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: factors are (f0, f1), one per trailing axis (got {factors!r})") from None
+    if not (1 <= f0 <= ops.TVSR_MAX_FACTOR and 1 <= f1 <= ops.TVSR_MAX_FACTOR):
+        raise ValueError(f"{who}: factors are 1 .. {ops.TVSR_MAX_FACTOR} per axis (got {f0} x {f1})")
+    if isinstance(upsample, bool) or int(upsample) != upsample or not 1 <= upsample <= 16:
+        raise ValueError(f"{who}: upsample must be an integer in 1 .. 16 (got {upsample!r})")
+    u = int(upsample)
+    as_numpy, h, w, lead = _block_input(who, frames, "frames")
+    if len(lead) < 1:
+        raise ValueError(f"{who} needs at least 3-D frames [..., K, h, w]")
+    lead, K = lead[:-1], lead[-1]
+    _frame_count(who, K)
+    if isinstance(reference, bool) or int(reference) != reference or not 0 <= reference < K:
+        raise ValueError(f"{who}: reference must be a frame index in 0 .. {K - 1} (got {reference!r})")
+    if max_shift is not None and not 0.0 <= float(max_shift) < np.inf:
+        raise ValueError(f"{who}: max_shift must be None or a finite number of LR pixels >= 0 (got {max_shift!r})")
+    window = registration._window(who, (u * h, u * w), None if max_shift is None else int(np.ceil(float(max_shift) * u)))
+    _fourier_axis(who, h, u * h, "center", "mirror")
+    _fourier_axis(who, w, u * w, "center", "mirror")
+    up =fourier_resize(_block_batch(frames, as_numpy).double(), (u * h, u * w), align="center", boundary="mirror")
+    planes = up.reshape(-1, K, u * h, u * w).float().contiguous()
+    ref = torch.full((planes.shape[0],), int(reference), dtype=torch.int32, device=planes.device)
+    steps, _, _, _ = registration._xcorr(planes, torch.ones_like(planes), ref, window, 3 / 10)
+    out = (steps * torch.tensor([f0 / u, f1 / u], dtype=torch.float64, device=planes.device)).reshape(*lead, K, 2)
+    return out.cpu().numpy() if as_numpy else out
 
 
 TV3D_DEFAULT_LAMBDA, TV3D_DEFAULT_HUBER, TV3D_DEFAULT_ITERS = 3e-3, 0.1, 300   # the sweep of DESIGN.md 4m

@@ -1025,3 +1025,95 @@ def through_plane_study(volume, factor=2, profile="mean", fwhm=None, tv_lambda=N
         ssim[name] = metrics.ssim_reference_protocol(safe(hs), safe(volumes[name])).cpu().numpy()
     return {"volumes": volumes, "psnr": psnr, "ssim": ssim, "consistency": consistency, "kernel": kernel, "valid": ok.cpu().numpy(),
             "info": info}
+
+
+# ---------------------------------------------------------------------------------------------------
+MULTI_FRAME_METHODS = ("replicate", "tv", "ignored", "estimated", "true")
+MULTI_FRAME_MARGIN = 4
+
+
+def check_multi_frame(factor=2, frames=8, max_shift=1.5, noise=0.02, kernel="mean", tv_lambda=0.01, tv_huber=0.03, tv_iters=300,
+                      upsample=4):
+    """What ``multi_frame_study`` cannot serve, by name; touches neither the input nor the device."""
+    who = "multi_frame_study"
+    if int(factor) != factor or not 1 <= factor <= ops.TVSR_MAX_FACTOR:
+        raise ValueError(f"{who}: factor is the block side of a LR pixel, 1 .. {ops.TVSR_MAX_FACTOR} (got {factor!r})")
+    if int(frames) != frames or not 1 <= frames <= ops.TVMF_MAX_FRAMES:
+        raise ValueError(f"{who}: frames must be 1 .. {ops.TVMF_MAX_FRAMES} (got {frames!r})")
+    if not 0.0 <= float(max_shift) <= 64.0:
+        raise ValueError(f"{who}: max_shift must lie in 0 .. 64 HR pixels (got {max_shift!r})")
+    if not 0.0 <= float(noise) < float("inf"):
+        raise ValueError(f"{who}: noise must be finite and >= 0 (got {noise!r})")
+    if kernel not in ("mean", "decimate"):
+        raise ValueError(f"{who}: kernel must be 'mean' or 'decimate' (got {kernel!r})")
+    for name, value in (("tv_lambda", tv_lambda), ("tv_huber", tv_huber)):
+        if not 0.0 <= float(value) < float("inf"):
+            raise ValueError(f"{who}: {name} must be finite and >= 0 (got {value!r})")
+    if int(tv_iters) != tv_iters or not 1 <= tv_iters <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: tv_iters must be 1 .. 100,000 (got {tv_iters!r})")
+    if int(upsample) != upsample or not 1 <= upsample <= 16:
+        raise ValueError(f"{who}: upsample must be 1 .. 16 (got {upsample!r})")
+
+
+def simulate_frames(hr, factors, shifts, kernel="mean"):
+    """The noiseless frames [n, K, h, w] of the device images ``hr`` [n, H, W] displaced by ``shifts`` [n, K, 2] (HR pixels), with
+    ZEROS beyond the border so that every datum is defined: ``baselines.frame_apply`` of the image padded by whole blocks, cut back."""
+    from . import baselines
+    f0, f1 = factors
+    reach = float(np.abs(np.asarray(shifts)).max()) + 1.0 if np.size(shifts) else 1.0
+    p0, p1 = f0 * int(np.ceil(reach / f0)), f1 * int(np.ceil(reach / f1))
+    big = torch.nn.functional.pad(hr, (p1, p1, p0, p0))
+    out = baselines.frame_apply(big, factors, np.asarray(shifts, np.float64), kernel)
+    return out[..., p0 // f0:p0 // f0 + hr.shape[-2] // f0, p1 // f1:p1 // f1 + hr.shape[-1] // f1].contiguous()
+
+
+def multi_frame_study(slices, factor=2, frames=8, max_shift=1.5, noise=0.02, seed=0, kernel="mean", tv_lambda=None, tv_huber=None,
+                      tv_iters=None, upsample=4, true_shifts=False, slice_ids=None):
+    """``slices`` [Z, R, R] in [0, 1]: per slice ``frames`` acquisitions, each the ``factor`` x ``factor`` block operator of the slice
+    displaced by a shift drawn uniformly in +- ``max_shift`` HR pixels (frame 0 at rest) plus Gaussian noise of ``noise`` -- slice z
+    (``slice_ids[i]`` for row i where given, else i) draws its shifts, then its noise, from ``np.random.default_rng(seed * 1000 + z)``
+    --, and five reconstructions on the device:
+    ``replicate`` (block replication of frame 0), ``tv`` (``baselines.tv_superres`` of frame 0, its defaults), ``ignored`` (all frames,
+    shifts taken as zero), ``estimated`` (``baselines.estimate_shifts`` at ``upsample``, searched over ``max_shift`` + 1 HR pixels; the
+    true shifts with ``true_shifts``) and ``true``, the last three by ``baselines.tv_superres_multi`` (the ``TVMF_DEFAULT_*`` where an
+    argument is None).  Returns ``{"images", "frames", "shifts", "estimate", "psnr", "ssim", "shift_error", "info"}``: float64 device
+    stacks, PSNR inside a margin of 4 pixels and SSIM (data range 1) [Z] per method, and max |estimate - shifts| [Z]."""
+    from . import baselines
+
+    lam = baselines.TVMF_DEFAULT_LAMBDA if tv_lambda is None else tv_lambda
+    huber = baselines.TVMF_DEFAULT_HUBER if tv_huber is None else tv_huber
+    iters = baselines.TVMF_DEFAULT_ITERS if tv_iters is None else tv_iters
+    check_multi_frame(factor, frames, max_shift, noise, kernel, lam, huber, iters, upsample)
+    vol = np.asarray(slices, np.float64)
+    m = MULTI_FRAME_MARGIN
+    if vol.ndim != 3 or vol.shape[1] % factor or vol.shape[2] % factor or min(vol.shape[1:]) - 2 * m < 7:
+        raise ValueError(f"multi_frame_study: slices are [Z, rows, columns], whole blocks of {factor} and at least {7 + 2 * m} pixels "
+                         f"a side (got {vol.shape})")
+    Z, K, f = vol.shape[0], int(frames), (int(factor), int(factor))
+    h, w = vol.shape[1] // factor, vol.shape[2] // factor
+    shifts, eta = np.zeros((Z, K, 2)), np.zeros((Z, K, h, w))
+    ids = list(range(Z)) if slice_ids is None else [int(v) for v in slice_ids]
+    if len(ids) != Z or min(ids) < 0:
+        raise ValueError(f"multi_frame_study: slice_ids are one index >= 0 per slice (got {slice_ids!r} for {Z} slices)")
+    for z in range(Z):
+        rng = np.random.default_rng(int(seed) * 1000 + ids[z])
+        shifts[z] = rng.uniform(-max_shift, max_shift, (K, 2))
+        shifts[z, 0] = 0.0
+        eta[z] = noise * rng.standard_normal((K, h, w))
+    dev = ops.require_gpu()
+    hr = torch.from_numpy(vol).to(dev)
+    y = simulate_frames(hr, f, shifts, kernel) + torch.from_numpy(eta).to(dev)
+    true = torch.from_numpy(shifts).to(dev)
+    est = true if true_shifts else baselines.estimate_shifts(y, f, int(upsample), (float(max_shift) + 1.0) / factor)
+    solve = lambda s: baselines.tv_superres_multi(y, f, s, kernel, lam, huber, int(iters), return_info=True)
+    images = {"replicate": y[:, 0].repeat_interleave(factor, dim=1).repeat_interleave(factor, dim=2),
+              "tv": baselines.tv_superres(y[:, 0].contiguous(), f, kernel)}
+    info = {}
+    for name, s in (("ignored", torch.zeros_like(true)), ("estimated", est), ("true", true)):
+        images[name], res = solve(s)
+        info[name] = {k: v.cpu().numpy() for k, v in res.items()}
+    crop = lambda t: t[:, m:-m, m:-m].float().contiguous()
+    psnr = {name: metrics.psnr(crop(hr), crop(v), 1.0, per_image=True).cpu().numpy() for name, v in images.items()}
+    ssim = {name: metrics.ssim(crop(hr), crop(v), 1.0).cpu().numpy() for name, v in images.items()}
+    return {"images": images, "hr": hr, "frames": y, "shifts": true, "estimate": est, "psnr": psnr, "ssim": ssim,
+            "shift_error": (est - true).abs().amax(dim=(1, 2)).cpu().numpy(), "info": info}

@@ -900,6 +900,114 @@ def tvsr_solve3d(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_i
     return out, energy, change
 
 
+# ---- multi-frame TV / Huber super-resolution with sub-pixel shifts (include/inrhip.h) ----------------------------------
+TVMF_MAX_FRAMES = _lib.INR_TVMF_MAX_FRAMES
+
+
+def _chk_frames(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
+    """A contiguous device batch [n, frames, rows, columns] of one of ``dtypes``, 1 .. TVMF_MAX_FRAMES frames."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype not in dtypes:                                         # before the device: a host-only refusal
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
+    if not t.is_cuda:
+        raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
+    if t.dim() != 4 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [n, frames, rows, columns] batch (got {tuple(t.shape)})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if not 1 <= t.shape[1] <= TVMF_MAX_FRAMES:
+        raise ValueError(f"{name}: frames per image are 1 .. {TVMF_MAX_FRAMES} (got {t.shape[1]})")
+    return t
+
+
+def _chk_shifts(shifts, n, K) -> torch.Tensor:
+    """The DEVICE shifts [n, K, 2] float64, (rows, columns) in HR pixels; their values are the kernels' business."""
+    if not isinstance(shifts, torch.Tensor):
+        raise TypeError("shifts must be a torch.Tensor")
+    if shifts.dtype != torch.float64:
+        raise TypeError(f"shifts must be torch.float64 (got {shifts.dtype})")
+    if not shifts.is_cuda:
+        raise InrDeviceError(f"shifts is on {shifts.device}: the kernels only run on a HIP device (there is no CPU fallback)")
+    if tuple(shifts.shape) != (n, K, 2) or not shifts.is_contiguous():
+        raise ValueError(f"shifts must be a contiguous [{n}, {K}, 2] tensor (got {tuple(shifts.shape)})")
+    return shifts
+
+
+def frame_apply(x: torch.Tensor, shifts: torch.Tensor, factors, kernel, return_valid: bool = False):
+    """``inr_frame_apply2d``: ``x`` [n, H, W] float64 and ``shifts`` [n, K, 2] float64 -> the frames ``A_k x`` [n, K, H/f0, W/f1], 0 at
+    invalid data; ``return_valid``: also the validity mask, a bool tensor of that shape."""
+    _chk_images(x, "x")
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, H, W = x.shape
+    _hr_shape("frame_apply", H, W, f0, f1)
+    if not isinstance(shifts, torch.Tensor) or shifts.dim() != 3:
+        raise ValueError("frame_apply: shifts must be a [n, K, 2] tensor")
+    K = int(shifts.shape[1])
+    if not 1 <= K <= TVMF_MAX_FRAMES:
+        raise ValueError(f"frame_apply: frames per image are 1 .. {TVMF_MAX_FRAMES} (got {K})")
+    _chk_shifts(shifts, n, K)
+    out = torch.empty((n, K, H // f0, W // f1), dtype=torch.float64, device=x.device)
+    valid = torch.empty(out.shape, dtype=torch.uint8, device=x.device) if return_valid else None
+    check(lib().inr_frame_apply2d(out.data_ptr(), _ptr(valid), x.data_ptr(), shifts.data_ptr(), n, K, H, W, f0, f1, k, _stream()),
+          "inr_frame_apply2d")
+    return (out, valid.bool()) if return_valid else out
+
+
+def frame_adjoint(r: torch.Tensor, shifts: torch.Tensor, factors, kernel) -> torch.Tensor:
+    """``inr_frame_adjoint2d``: ``r`` [n, K, h, w] float64 -> ``sum_k A_k^T r_k`` [n, f0 h, f1 w]."""
+    _chk_frames(r, "r")
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, K, h, w = r.shape
+    _hr_shape("frame_adjoint", h * f0, w * f1, f0, f1)
+    _chk_shifts(shifts, n, K)
+    out = torch.empty((n, h * f0, w * f1), dtype=torch.float64, device=r.device)
+    check(lib().inr_frame_adjoint2d(out.data_ptr(), r.data_ptr(), shifts.data_ptr(), n, K, h * f0, w * f1, f0, f1, k, _stream()),
+          "inr_frame_adjoint2d")
+    return out
+
+
+def tvmf_workspace_doubles(n: int, K: int, H: int, W: int, factors) -> int:
+    """``inr_tvmf_workspace_doubles``; 0 for sizes ``inr_tvmf_solve2d`` refuses."""
+    f0, f1 = (int(v) for v in factors)
+    return int(lib().inr_tvmf_workspace_doubles(int(n), int(K), int(H), int(W), f0, f1))
+
+
+def tvmf_solve(y: torch.Tensor, shifts: torch.Tensor, factors, kernel, lam: float, alpha: float, n_iter: int, weight=None, x0=None,
+               workspace=None):
+    """``inr_tvmf_solve2d`` / ``_f32`` by the dtype of ``y`` [n, K, h, w]: returns (x [n, f0 h, f1 w] of that dtype, energy [n],
+    change [n], valid_fraction [n], all float64).  ``shifts`` [n, K, 2] float64 on the device; ``weight`` [n, K, h, w] and ``x0``
+    [n, f0 h, f1 w] share the dtype of ``y``; ``workspace``: a float64 tensor."""
+    _chk_frames(y, "y", (torch.float32, torch.float64))
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, K, h, w = y.shape
+    H, W = h * f0, w * f1
+    _hr_shape("tvmf_solve", H, W, f0, f1)
+    _chk_shifts(shifts, n, K)
+    if weight is not None:
+        _chk_frames(weight, "weight", (y.dtype,), y.shape)
+    if x0 is not None:
+        _chk_images(x0, "x0", (y.dtype,), (n, H, W))
+    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= TVSR3D_MAX_ITER:
+        raise ValueError(f"tvmf_solve: lam and alpha must be finite and >= 0, n_iter 0 .. {TVSR3D_MAX_ITER} (got {lam!r}, {alpha!r}, "
+                         f"{n_iter})")
+    out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
+    energy, change, valid = (torch.zeros(n, dtype=torch.float64, device=y.device) for _ in range(3))
+    if n == 0:
+        return out, energy, change, valid
+    need = tvmf_workspace_doubles(n, K, H, W, (f0, f1))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
+    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
+        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
+    entry = "inr_tvmf_solve2d" if y.dtype == torch.float64 else "inr_tvmf_solve2d_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), valid.data_ptr(), y.data_ptr(), shifts.data_ptr(),
+                                _ptr(weight), _ptr(x0), n, K, H, W, f0, f1, k, lam, alpha, n_iter, workspace.data_ptr(),
+                                workspace.numel(), _stream()), entry)
+    return out, energy, change, valid
+
+
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
                    "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order

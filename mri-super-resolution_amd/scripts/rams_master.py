@@ -17,7 +17,12 @@ averages its subsets without ever aligning them, and without the flag nothing is
 ``--weights`` (an ``.npz`` of the network's variables, ``RAMS.save_weights``: the checkpoint under ``ckpt/RED_RAMS`` that
 master.py:27-33 restores is shipped WITHOUT its ``*.data-00001-of-00002`` shard and there is no TensorFlow here to read one --
 without ``--weights`` the network keeps its random initialisation and the script says so), ``--sample_size`` (25) and ``--seed``
-(the reference draws the subsets from the unseeded ``random`` module).  ``save_dicom`` (master.py:58-62) is replaced by
+(the reference draws the subsets from the unseeded ``random`` module) and ``--tv_multiframe`` with ``--tv_lambda --tv_huber --tv_iters
+--tv_upsample`` (the classical multi-frame comparator, DESIGN.md 4n: ALL acquisitions of the slice divided by their maximum, their
+sub-pixel shifts against acquisition 0 by ``baselines.estimate_shifts``, ``baselines.tv_superres_multi`` at x3 with the mean kernel,
+scaled back -- ``DWI_tvmf.npy`` / ``ADC_tvmf.npy`` and the same two keys in ``images.mat``, ``tvmf_shifts``, ``tvmf_energy`` and
+``tvmf_valid_fraction`` in the case record, ``cssim_tvmf_vs_rescaled`` with ``--ssim``; the RAMS path is not touched, and without the
+flag nothing is computed or written differently).  ``save_dicom`` (master.py:58-62) is replaced by
 ``<out_img_folder>/<exp_name>/<pt_no>/images.mat`` + ``DWI_mean.npy`` / ``ADC_mean.npy`` (DICOM export is out of scope).
 """
 from __future__ import annotations
@@ -61,7 +66,51 @@ def build_parser():
     parser.add_argument('--register', action='store_true', help='register the acquisitions of the slice to acquisition 0 before the '
                                                                 'uint16 cast and add shifts [T, 2] to every case record')
     parser.add_argument('--register_max_shift', type=int, default=8, help='search window of --register in pixels per axis')
+    parser.add_argument('--tv_multiframe', action='store_true', help='also reconstruct the slice x3 from ALL its acquisitions by '
+                        'baselines.tv_superres_multi with estimated sub-pixel shifts: DWI_tvmf / ADC_tvmf beside the RAMS outputs')
+    parser.add_argument('--tv_lambda', type=float, default=baselines.TVMF_DEFAULT_LAMBDA,
+                        help='--tv_multiframe: weight of the prior (data scaled to [0, 1]; not divided by the number of acquisitions)')
+    parser.add_argument('--tv_huber', type=float, default=baselines.TVMF_DEFAULT_HUBER, help='--tv_multiframe: Huber threshold; 0 = TV')
+    parser.add_argument('--tv_iters', type=int, default=baselines.TVMF_DEFAULT_ITERS, help='--tv_multiframe: iterations, 1 .. 100,000')
+    parser.add_argument('--tv_upsample', type=int, default=4, help='--tv_multiframe: up-sampling of the shift estimate, 1 .. 16 '
+                        '(the step is 3 / this in HR pixels; the search window is --register_max_shift)')
     return parser
+
+
+def check_tv_multiframe(args):
+    """The refusals of the --tv_multiframe flags, before any case is loaded; without the flag its values are not looked at."""
+    if not getattr(args, "tv_multiframe", False):
+        return
+    for name in ("tv_lambda", "tv_huber"):
+        if not 0.0 <= getattr(args, name) < float("inf"):
+            raise ValueError(f"--{name} must be finite and >= 0 (got {getattr(args, name)!r})")
+    if not 1 <= args.tv_iters <= 100000:
+        raise ValueError(f"--tv_iters must be 1 .. 100,000 (got {args.tv_iters})")
+    if not 1 <= args.tv_upsample <= 16:
+        raise ValueError(f"--tv_upsample must be 1 .. 16 (got {args.tv_upsample})")
+    if args.register_max_shift < 0:
+        raise ValueError(f"--register_max_shift must be >= 0 (got {args.register_max_shift})")
+
+
+def tv_multiframe_case(case, scale=SCALE, lam=baselines.TVMF_DEFAULT_LAMBDA, huber=baselines.TVMF_DEFAULT_HUBER,
+                       n_iter=baselines.TVMF_DEFAULT_ITERS, upsample=4, max_shift=8):
+    """The classical multi-frame comparator of the RAMS mean: ALL acquisitions [X, Y, T] of the cancer slice, divided by their
+    maximum, their shifts against acquisition 0 by ``baselines.estimate_shifts`` (in HR pixels, searched within ``max_shift`` LR
+    pixels), ``baselines.tv_superres_multi`` at x``scale`` with the mean kernel, scaled back; the ADC by the formula of
+    ``super_resolve_case``.  Returns ``(dwi [3X, 3Y] float64, adc, shifts [T, 2], info)``."""
+    seq = np.asarray(case.dwi[:, :, case.cancer_slice, :], np.float64)
+    top = float(seq.max())
+    if not top > 0.0:
+        raise ValueError(f"{case.pt_id}: the acquisitions of slice {case.cancer_slice} are all zero")
+    frames = np.ascontiguousarray(seq.transpose(2, 0, 1)) / top
+    shifts = baselines.estimate_shifts(frames, (scale, scale), upsample, max_shift)
+    x, info = baselines.tv_superres_multi(frames, (scale, scale), shifts, "mean", lam, huber, n_iter, return_info=True)
+    dwi = x * top
+    b0 = np.asarray(case.b0[:, :, case.cancer_slice], np.float64)
+    b0_scaled = baselines.rescale(b0, scale, anti_aliasing=False)
+    adc = -np.log((dwi / (b0_scaled + eps)) + eps) / case.b
+    adc *= 1000000
+    return dwi, adc, shifts, info
 
 
 def register_slice(case, max_shift=8):
@@ -107,6 +156,7 @@ def cssim_vs_rescaled(mean_pred, case, scale):
 
 
 def run(args, cases):
+    check_tv_multiframe(args)
     rams_network = RAMS(scale=SCALE, filters=FILTERS, kernel_size=KERNEL_SIZE, channels=CHANNELS, r=R, N=N, seed=0)
     if args.weights:
         rams_network.load_weights(args.weights)
@@ -131,13 +181,26 @@ def run(args, cases):
         os.makedirs(out_dir, exist_ok=True)
         np.save(os.path.join(out_dir, 'DWI_mean.npy'), mean_pred)                            # instead of save_dicom (:58-62)
         np.save(os.path.join(out_dir, 'ADC_mean.npy'), adc_large)
-        matio.savemat(os.path.join(out_dir, 'images.mat'), {'DWI_mean': mean_pred, 'ADC_mean': adc_large})
+        images = {'DWI_mean': mean_pred, 'ADC_mean': adc_large}
+        tvmf = None
+        if getattr(args, "tv_multiframe", False):
+            tvmf = tv_multiframe_case(case, rams_network.cfg["scale"], args.tv_lambda, args.tv_huber, args.tv_iters, args.tv_upsample,
+                                      args.register_max_shift)
+            np.save(os.path.join(out_dir, 'DWI_tvmf.npy'), tvmf[0])
+            np.save(os.path.join(out_dir, 'ADC_tvmf.npy'), tvmf[1])
+            images.update(DWI_tvmf=tvmf[0], ADC_tvmf=tvmf[1])
+        matio.savemat(os.path.join(out_dir, 'images.mat'), images)
         summary.append({"patient": pt_no, "shape": list(mean_pred.shape), "sample_size": args.sample_size, "seconds": dt,
                         "subsets": subsets, "out_dir": out_dir})
         if getattr(args, "ssim", False):
             summary[-1]["cssim_vs_rescaled"] = cssim_vs_rescaled(mean_pred, case, rams_network.cfg["scale"])
         if shifts is not None:
             summary[-1]["shifts"] = np.asarray(shifts).tolist()
+        if tvmf is not None:
+            summary[-1].update(tvmf_shifts=np.asarray(tvmf[2]).tolist(), tvmf_energy=float(tvmf[3]["energy"]),
+                               tvmf_valid_fraction=float(tvmf[3]["valid_fraction"]))
+            if getattr(args, "ssim", False):                                                 # on the x256 scale of the RAMS mean
+                summary[-1]["cssim_tvmf_vs_rescaled"] = cssim_vs_rescaled(tvmf[0] * 256.0, case, rams_network.cfg["scale"])
     with open(os.path.join(args.out_folder, args.exp_name + '.json'), 'w') as fh:
         json.dump({"weights": args.weights, "cases": summary}, fh)
     return {"cases": summary, "weights": args.weights}
