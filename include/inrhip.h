@@ -610,6 +610,60 @@ int inr_tvmf_solve2d_f32(float* out, double* energy, double* change, double* val
                          const double* kernel, double lambda, double alpha, int n_iter, double* workspace, int64_t workspace_doubles,
                          void* stream);
 
+/* ---- multi-stack 3-D TV / Huber reconstruction with general slice profiles ---------------------------------------------
+ * No counterpart in the reference.  Volumes are [n_volumes][D][H][W] (HR: slice, row, column), D, H, W <= INR_TVSR_MAX_SIDE.  A call
+ * has n_stacks in 1 .. INR_TVMS_MAX_STACKS stacks, the same for every volume of the batch.  `geometry` is a HOST array int [S][12] =
+ * (f0, f1, f2, L0, L1, L2, o0, o1, o2, n0, n1, n2) per stack: per axis a spacing f in 1 .. INR_TVSR_MAX_FACTOR, a tap count L in
+ * 1 .. INR_TVMS_MAX_TAPS, an offset o in HR voxels with |o| <= 2^20 (it may be negative) and an LR extent n in 1 .. 2048.  `taps` are
+ * HOST doubles, per stack k0 [L0] | k1 [L1] | k2 [L2] concatenated, the stacks in order; each k_a is finite and sums to 1 (to 1e-9).
+ * Data (y, weight, the result of inr_tvms_apply) are [n_volumes][M], M = sum_s n0 n1 n2, the stacks in order, each [n0][n1][n2].
+ *   (A_s x)[l][i][j] = sum_{a, b, c} k[a][b][c] x[o0 + f0 l + a][o1 + f1 i + b][o2 + f2 j + c],  k[a][b][c] = (k1[b] * k2[c]) * k0[a],
+ *   the terms added in ascending (a, b, c): a stack with L = f, o = 0, n = N / f is inr_tvsr3d_block_apply bit for bit.  L > f: slices
+ *   overlap; L < f: gaps.  A datum is VALID when its footprint lies inside the volume on every axis (0 <= o + f i, o + f i + L <= N).
+ *   An invalid datum has weight 0 whatever `weight` holds; its y and weight are never read (they may be NaN) and its dual variable is
+ *   0.  Every range test precedes the address it guards, and the limits above keep o + f i + L within an int.
+ * inr_tvms_apply: out [n][M] = (A_s in)_s with 0 at invalid data; valid [n][M] bytes (1 / 0) or null.
+ * inr_tvms_adjoint: out [n][D][H][W] = sum_s A_s^T in_s, a gather: HR voxel m sums k[a][b][c] in[l][i][j] over the valid data whose
+ *   footprint holds m -- stacks ascending, then l, i, j ascending, per axis the indices floordiv(m - o - L + 1 + f - 1, f) ..
+ *   floordiv(m - o, f); no atomics.  For a block stack it is inr_tvsr3d_block_adjoint bit for bit.  fp64, one launch each, out must not
+ *   overlap in.
+ * inr_tvms_solve: out [n][D][H][W] = n_iter iterations of Chambolle-Pock with both terms dual on
+ *   min_x 1/2 sum_s sum_i w_si ((A_s x)_i - y_si)^2 + lambda sum_j H_alpha(sqrt((g1 d1 x)_j^2 + (g2 d2 x)_j^2 + (g0 d0 x)_j^2))
+ *   (differences, grad_weights, combining order, "axes longer than 1" rule, H_alpha: inr_tvsr3d_solve), from x = xbar = x0, p = 0, q = 0:
+ *     p   <- (p + sigma g d(xbar)) / (1 + sigma alpha / lambda);  p <- p / max(1, |p| / lambda)   (lambda == 0 or no axis longer than 1: p = 0)
+ *     q_s <- (q_s + sigma (A_s xbar - y_s)) / (1 + sigma / w_s)   at valid data with w_s > 0, else 0
+ *     x'  <- x - tau (sum_s A_s^T q_s - div p);  xbar <- 2 x' - x;  x <- x'
+ *   tau = sigma = 1 / sqrt(4 sum_a g_a^2 + sum_{s live} c_s): the first sum over the axes longer than 1 in the order (1, 2, 0), c_s =
+ *   prod_a (sum_t |k_a[t]|) (max_{r < f_a} sum_{t = r mod f_a} |k_a[t]|) in the order a = 0, 1, 2, the stacks ascending, a stack LIVE
+ *   when it holds a valid datum; formed on the host in fp64 (a zero bound: tau = 1 / sqrt(8)).  The objective is not divided by the
+ *   number of stacks.  x0 [n][D][H][W] or null: the normalised back-projection (sum_s A_s^T y_s) / (sum_s A_s^T 1) over the usable data
+ *   (valid, w > 0), 0 where no usable datum reaches.  weight [n][M] or null (1).  energy / change / valid_fraction [n] or null: the
+ *   objective at the result, max |x' - x| of the last iteration (0 for n_iter == 0), the valid share of the M data.
+ *   Launches: init; a back-projection launch without x0; per iteration a dual launch (thread per HR voxel where the prior is on, and
+ *   per datum) and a primal launch (thread per HR voxel); a final launch and a fixed-order finish.  Plain launches on `stream`, no
+ *   host read, no float atomics: calls are bit-equal on any stream and at any place in a batch.  The _f32 form reads y / weight / x0
+ *   and writes out as fp32, with fp64 inside, and rounds once.  n_volumes == 0 succeeds and launches nothing.
+ * workspace: inr_tvms_workspace_doubles(n_volumes, D, H, W, n_stacks, geometry) doubles (the state x | xbar | p0 | p1 | p2, q and the
+ * partials), 16-byte aligned; 0 for sizes that would be refused.  Refusals, all before any device work: INR_E_INVALID (null out / y /
+ * in / geometry / taps / grad_weights, n_volumes < 0, n_stacks, f, L, o, n or the HR sides out of range, n_iter outside 0 ..
+ * INR_TVSR3D_MAX_ITER, a negative or non-finite lambda / alpha / gradient weight, taps that are not finite or do not sum to 1),
+ * INR_E_WORKSPACE (null or short workspace), INR_E_ALIGN (workspace off a 16-byte boundary). */
+#define INR_TVMS_MAX_STACKS 8
+#define INR_TVMS_MAX_TAPS 16
+int inr_tvms_apply(double* out, unsigned char* valid, const double* in, int n_volumes, int depth, int height, int width, int n_stacks,
+                   const int* geometry, const double* taps, void* stream);
+int inr_tvms_adjoint(double* out, const double* in, int n_volumes, int depth, int height, int width, int n_stacks, const int* geometry,
+                     const double* taps, void* stream);
+int64_t inr_tvms_workspace_doubles(int n_volumes, int depth, int height, int width, int n_stacks, const int* geometry);
+int inr_tvms_solve(double* out, double* energy, double* change, double* valid_fraction, const double* y, const double* weight,
+                   const double* x0, int n_volumes, int depth, int height, int width, int n_stacks, const int* geometry,
+                   const double* taps, const double* grad_weights, double lambda, double alpha, int n_iter, double* workspace,
+                   int64_t workspace_doubles, void* stream);
+int inr_tvms_solve_f32(float* out, double* energy, double* change, double* valid_fraction, const float* y, const float* weight,
+                       const float* x0, int n_volumes, int depth, int height, int width, int n_stacks, const int* geometry,
+                       const double* taps, const double* grad_weights, double lambda, double alpha, int n_iter, double* workspace,
+                       int64_t workspace_doubles, void* stream);
+
 /* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
  * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
  * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output

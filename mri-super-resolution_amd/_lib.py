@@ -25,6 +25,7 @@ INR_ERD_RUNNING, INR_ERD_CONVERGED, INR_ERD_COLLAPSED = 0, 1, 2
 INR_RESCALE_REFLECT, INR_RESCALE_EDGE, INR_RESCALE_MAX_RADIUS, INR_RESCALE_MAX_LINE = 0, 1, 64, 4096
 INR_FOURIER_SAMPLE, INR_FOURIER_CENTER, INR_FOURIER_PERIODIC, INR_FOURIER_MIRROR, INR_FOURIER_MAX_LINE = 0, 1, 0, 1, 1024
 INR_TVSR_MAX_FACTOR, INR_TVSR_MAX_SIDE, INR_TVSR3D_MAX_ITER, INR_TVMF_MAX_FRAMES = 8, 1024, 100000, 64
+INR_TVMS_MAX_STACKS, INR_TVMS_MAX_TAPS = 8, 16
 
 
 class InrHipError(RuntimeError):
@@ -193,6 +194,14 @@ SIGNATURES = {
                                                                      C.c_int64, c_stream]),
     "inr_tvmf_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, C.c_void_p, c_f32p, c_f32p] + [C.c_int] * 6 +
                              [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvms_apply": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_double), c_stream]),
+    "inr_tvms_adjoint": (C.c_int, [C.c_void_p] * 2 + [C.c_int] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_double), c_stream]),
+    "inr_tvms_workspace_doubles": (C.c_int64, [C.c_int] * 5 + [C.POINTER(C.c_int)]),
+    "inr_tvms_solve": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 2 +
+                       [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvms_solve_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 5 +
+                           [C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 2 +
+                           [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
     "inr_footprint_expand": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
     "inr_footprint_reduce": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_footprint_loss_workspace_floats": (C.c_int64, [C.c_int64]),

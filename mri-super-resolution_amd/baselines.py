@@ -36,6 +36,11 @@ block operator whose first factor is the slice profile, a 3-D prior with per-axi
 image, each displaced by a fraction of a pixel, one operator ``A_k = B S_k`` per frame with a bilinear translation ``S_k``, data and
 prior both dual (``inr_tvmf_solve2d``) -- the classical comparator of the multi-image methods, which the
 register-and-average baseline is not (it aligns to whole pixels and discards what the fractions hold).
+
+``tv_superres_stacks``, ``stack_geometry``, ``profile_taps``, ``stack_apply`` and ``stack_adjoint`` are the multi-stack form on
+volumes: 1 .. 8 stacks of thick slices of one volume -- different orientations, whole-voxel offsets, slice profiles wider
+(overlapping) or narrower (gapped) than the slice spacing --, one operator ``A_s`` per stack with a validity rule for footprints that
+leave the volume, data and prior both dual (``inr_tvms_solve``) -- what ``scripts/multi_stack`` scores.
 """
 from __future__ import annotations
 
@@ -671,6 +676,248 @@ def tv_superres3d(lr, factors, kernel="mean", lam: float = TV3D_DEFAULT_LAMBDA, 
     if as_numpy:
         out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
     return (out, {"energy": energy, "change": change}) if return_info else out
+
+
+TVMS_DEFAULT_LAMBDA, TVMS_DEFAULT_HUBER, TVMS_DEFAULT_ITERS = 0.01, 0.01, 300  # the sweep of DESIGN.md 4o (3 stacks, noise 0.02)
+
+
+class StackGeometry(tuple):
+    """The immutable record ``(factors, kernels, offsets)`` of one stack (``stack_geometry``)."""
+    __slots__ = ()
+    factors = property(lambda self: self[0])
+    kernels = property(lambda self: self[1])
+    offsets = property(lambda self: self[2])
+
+    def __repr__(self):
+        return f"StackGeometry(factors={self[0]!r}, kernels={self[1]!r}, offsets={self[2]!r})"
+
+
+def stack_geometry(factors, kernel="mean", offsets=(0, 0, 0)):
+    """One stack of thick slices for ``stack_apply`` / ``tv_superres_stacks``: per trailing axis (slice, row, column) a spacing
+    ``factors`` = (f0, f1, f2), 1 .. 8, between neighbouring LR samples, a profile and an offset in HR voxels (|o| <= 2^20, it may be
+    negative): LR sample i of an axis is the profile-weighted sum of the HR samples o + f i .. o + f i + L - 1.  ``kernel``: 'mean' /
+    'decimate' (length f per axis, as in ``tv_superres3d``) or a triple of 1-D arrays of ANY length 1 .. 16, each summing to 1
+    (``profile_taps``): longer than f the slices overlap, shorter they leave gaps.  Returns an immutable record (factors, kernels,
+    offsets)."""
+    who = "stack_geometry"
+    try:
+        f = tuple(int(v) for v in factors)
+        if len(f) != 3 or any(int(v) != v for v in factors):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: factors are (f0, f1, f2), one per trailing axis (got {factors!r})") from None
+    if not all(1 <= v <= ops.TVSR_MAX_FACTOR for v in f):
+        raise ValueError(f"{who}: factors are 1 .. {ops.TVSR_MAX_FACTOR} per axis (got {f[0]} x {f[1]} x {f[2]})")
+    if isinstance(kernel, str):
+        if kernel not in ("mean", "decimate"):
+            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2) (got {kernel!r})")
+        ks = [slice_profile(v, kernel) for v in f]
+    else:
+        try:
+            ks = [np.asarray(k, dtype=np.float64) for k in kernel]
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2)") from None
+        if len(ks) != 3 or any(k.ndim != 1 or not 1 <= k.size <= ops.TVMS_MAX_TAPS for k in ks):
+            raise ValueError(f"{who}: the kernel is a triple of 1-D arrays of 1 .. {ops.TVMS_MAX_TAPS} taps (got {[k.shape for k in ks]})")
+        for axis, k in enumerate(ks):
+            if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
+                raise ValueError(f"{who}: kernel factor k{axis} must be finite and sum to 1 (got sum {k.sum()!r})")
+    try:
+        o = tuple(int(v) for v in offsets)
+        if len(o) != 3 or any(int(v) != v for v in offsets):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: offsets are three whole numbers of HR voxels (got {offsets!r})") from None
+    if not all(abs(v) <= ops.TVMS_MAX_OFFSET for v in o):
+        raise ValueError(f"{who}: offsets are within +-{ops.TVMS_MAX_OFFSET} HR voxels (got {o})")
+    return StackGeometry((f, tuple(tuple(float(v) for v in k) for k in ks), o))
+
+
+def profile_taps(length, spacing, kind: str = "gaussian", fwhm=None):
+    """``length`` taps (1 .. 16) of a slice profile on HR sub-slice centres, centred on the footprint and normalised to sum 1, as a
+    float64 ndarray: 'mean' (a box over the footprint) or 'gaussian' of full width at half maximum ``fwhm`` in units of ``spacing`` HR
+    voxels (the slice spacing), sampled at the positions ``(t + 1/2 - length/2) / spacing``.  ``length == spacing`` is
+    ``slice_profile``; a longer profile overlaps its neighbours.  ``fwhm`` belongs to 'gaussian' alone."""
+    who = "profile_taps"
+    if isinstance(length, bool) or int(length) != length or not 1 <= int(length) <= ops.TVMS_MAX_TAPS:
+        raise ValueError(f"{who}: length is an integer 1 .. {ops.TVMS_MAX_TAPS} (got {length!r})")
+    if isinstance(spacing, bool) or int(spacing) != spacing or not 1 <= int(spacing) <= ops.TVSR_MAX_FACTOR:
+        raise ValueError(f"{who}: spacing is an integer 1 .. {ops.TVSR_MAX_FACTOR} (got {spacing!r})")
+    L, f = int(length), int(spacing)
+    if kind != "gaussian" and fwhm is not None:
+        raise ValueError(f"{who}: fwhm belongs to kind='gaussian' (got kind={kind!r})")
+    if kind == "mean":
+        return np.full(L, 1.0 / L)
+    if kind == "gaussian":
+        if fwhm is None or not 0.0 < float(fwhm) < np.inf:
+            raise ValueError(f"{who}: kind='gaussian' needs a finite fwhm > 0, in units of the spacing (got {fwhm!r})")
+        sigma = float(fwhm) / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+        pos = (2.0 * np.arange(L) + 1.0 - L) / (2.0 * f)          # (t + 1/2 - L/2) / f, antisymmetric to the bit
+        k = np.exp(-0.5 * (pos / sigma) ** 2)
+        if not k.sum() > 0.0:
+            raise ValueError(f"{who}: fwhm {fwhm!r} is too narrow: every sample of the Gaussian underflows")
+        return k / k.sum()
+    raise ValueError(f"{who}: kind must be 'gaussian' or 'mean' (got {kind!r})")
+
+
+def _geometries(who, geometries):
+    """One record or a sequence of them -> a list of ``StackGeometry``, 1 .. 8 of them."""
+    geos = [geometries] if isinstance(geometries, StackGeometry) else list(geometries)
+    if not 1 <= len(geos) <= ops.TVMS_MAX_STACKS:
+        raise ValueError(f"{who}: stacks per volume are 1 .. {ops.TVMS_MAX_STACKS} (got {len(geos)})")
+    for g in geos:
+        if not isinstance(g, StackGeometry):
+            raise TypeError(f"{who}: every geometry is a record of stack_geometry() (got {type(g).__name__})")
+    return geos
+
+
+def default_lr_shape(geometry, hr_shape):
+    """Per axis ``max(1, floor((N - L - o) / f) + 1)``: the LR indices from 0 to the last whose footprint lies inside the volume."""
+    return tuple(max(1, (int(N) - len(k) - o) // f + 1) for N, f, k, o in zip(hr_shape, *geometry))
+
+
+def _lr_shape(who, shape):
+    try:
+        n = tuple(int(v) for v in shape)
+        if len(n) != 3:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: an LR shape is (n0, n1, n2) (got {shape!r})") from None
+    if not all(1 <= v <= ops.TVMS_MAX_EXTENT for v in n):
+        raise ValueError(f"{who}: LR extents are 1 .. {ops.TVMS_MAX_EXTENT} per axis (got {n})")
+    return n
+
+
+def _hr_shape(who, hr_shape):
+    try:
+        hr = tuple(int(v) for v in hr_shape)
+        if len(hr) != 3:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: hr_shape is (D, H, W) (got {hr_shape!r})") from None
+    if any(s < 1 or s > ops.TVSR_MAX_SIDE for s in hr):
+        raise ValueError(f"{who}: HR volumes of 1 .. {ops.TVSR_MAX_SIDE} samples per axis (got {hr[0]} x {hr[1]} x {hr[2]})")
+    return hr
+
+
+def stack_apply(x, geometry, lr_shape=None, return_valid: bool = False):
+    """``A_s x``, one stack of thick slices of the trailing three axes (slice, row, column) of ``x``:
+    ``(A x)[l][i][j] = sum k[a][b][c] x[o0 + f0 l + a][o1 + f1 i + b][o2 + f2 j + c]`` with ``geometry`` of ``stack_geometry`` and
+    ``k[a][b][c] = (k1[b] k2[c]) k0[a]`` (``inr_tvms_apply``, fp64); a block stack is ``block_apply3d`` bit for bit.
+    ``lr_shape`` (n0, n1, n2) defaults per axis to ``max(1, floor((N - L - o) / f) + 1)``, the indices whose footprints lie inside.
+    A datum whose footprint leaves the volume is invalid and comes back 0; ``return_valid`` adds the bool mask.  Leading axes are a
+    batch; ndarray in -> float64 ndarray out, device fp32 / fp64 tensor in -> the same out."""
+    who = "stack_apply"
+    if not isinstance(geometry, StackGeometry):
+        raise TypeError(f"{who}: geometry is a record of stack_geometry() (got {type(geometry).__name__})")
+    as_numpy, hr, lead = _volume_input(who, x)
+    _hr_shape(who, hr)
+    n = default_lr_shape(geometry, hr) if lr_shape is None else lr_shape
+    n = _lr_shape(who, n)
+    flat = _volume_batch(x, as_numpy)
+    res = ops.stack_apply(flat.double(), [(geometry.factors, geometry.kernels, geometry.offsets, n)], return_valid)
+    out, valid = res if return_valid else (res, None)
+    out = out.to(flat.dtype).reshape(*lead, *n)
+    if return_valid:
+        valid = valid.reshape(out.shape)
+        return (out.cpu().numpy(), valid.cpu().numpy()) if as_numpy else (out, valid)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def stack_adjoint(r, geometry, hr_shape):
+    """``A_s^T r``, the adjoint of ``stack_apply``: ``r`` [..., n0, n1, n2] -> [..., D, H, W], a gather with no atomics in which invalid
+    data take no part (``inr_tvms_adjoint``); for a block stack ``block_adjoint3d`` bit for bit.  Types as ``stack_apply``."""
+    who = "stack_adjoint"
+    if not isinstance(geometry, StackGeometry):
+        raise TypeError(f"{who}: geometry is a record of stack_geometry() (got {type(geometry).__name__})")
+    as_numpy, n, lead = _volume_input(who, r)
+    _lr_shape(who, n)
+    hr = _hr_shape(who, hr_shape)
+    flat = _volume_batch(r, as_numpy)
+    out = ops.stack_adjoint(flat.double().reshape(flat.shape[0], -1), [(geometry.factors, geometry.kernels, geometry.offsets, n)], hr)
+    out = out.to(flat.dtype).reshape(*lead, *hr)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def tv_superres_stacks(stacks, geometries, hr_shape, lam: float = TVMS_DEFAULT_LAMBDA, huber: float = TVMS_DEFAULT_HUBER,
+                       n_iter: int = TVMS_DEFAULT_ITERS, grad_weights=TV3D_DEFAULT_GRAD_WEIGHTS, weight=None, x0=None,
+                       return_info: bool = False):
+    """Multi-stack model-based reconstruction of one volume ``hr_shape`` = (D, H, W) from 1 .. 8 ``stacks`` of thick slices -- a list
+    of arrays [..., n0, n1, n2] with the same leading axes and type, stack s acquired with ``geometries[s]`` of ``stack_geometry``:
+    stacks of different orientation (the thick axis on different axes), stacks that differ only in their offset (slice-shifted), and
+    profiles wider (overlap) or narrower (gaps) than the slice spacing.  ``n_iter`` Chambolle-Pock iterations, data and prior both
+    dual, on ``1/2 sum_s sum w_s (A_s x - stacks_s)^2 + lam sum H_huber(|grad x|)`` with the prior, ``grad_weights`` and ``huber`` of
+    ``tv_superres3d``.  The objective is NOT divided by the number of stacks: the data term grows with it, so ``lam`` BELONGS TO A
+    STACK COUNT AND A NOISE LEVEL (the default: three orthogonal stacks at noise 0.02 of a [0, 1] volume; a noiseless design wants a
+    smaller one).  A datum whose footprint leaves the volume has weight 0 and is never read (it may be NaN).  ``weight``: a list of
+    the shapes of ``stacks`` (>= 0; 0 marks a missing datum) or None; ``x0`` [..., D, H, W] defaults to the normalised
+    back-projection ``(sum A_s^T y_s) / (sum A_s^T 1)``.  ``inr_tvms_solve`` (DESIGN.md 4o).  ndarrays in -> float64 ndarray out;
+    device fp32 / fp64 tensors in -> the same out (fp64 inside, rounded once).  There is no CPU fallback.  ``return_info``: also a
+    dict with ``energy`` (the objective at the result), ``change`` (max |x' - x| of the last iteration) and ``valid_fraction`` (the
+    valid share of the data), each of the leading shape."""
+    who = "tv_superres_stacks"
+    geos = _geometries(who, geometries)
+    if isinstance(stacks, (np.ndarray, torch.Tensor)) or not hasattr(stacks, "__len__"):
+        raise TypeError(f"{who}: stacks is a list of arrays, one per geometry (got {type(stacks).__name__})")
+    stacks = list(stacks)
+    if len(stacks) != len(geos):
+        raise ValueError(f"{who}: {len(stacks)} stacks for {len(geos)} geometries")
+    hr = _hr_shape(who, hr_shape)
+    lam, huber = float(lam), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or not 0 <= n_iter <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: n_iter must be an integer 0 .. {ops.TVSR3D_MAX_ITER} (got {n_iter!r})")
+    try:
+        g = tuple(float(v) for v in grad_weights)
+    except (TypeError, ValueError):
+        g = ()
+    if len(g) != 3 or not all(0.0 <= v < np.inf for v in g):
+        raise ValueError(f"{who}: grad_weights are (g0, g1, g2), finite and >= 0 (got {grad_weights!r})")
+    as_numpy, _, lead = _volume_input(who, stacks[0], "stacks")
+    table = []
+    for s, (y, geo) in enumerate(zip(stacks, geos)):
+        if _volume_input(who, y, "stacks")[0] != as_numpy:
+            raise TypeError(f"{who}: the stacks must all be ndarrays or all device tensors")
+        if tuple(y.shape[:-3]) != lead or y.dtype != stacks[0].dtype:
+            raise ValueError(f"{who}: stack {s} must have the leading axes {lead} and the type of stack 0 (got {tuple(y.shape)}, {y.dtype})")
+        table.append((geo.factors, geo.kernels, geo.offsets, _lr_shape(who, y.shape[-3:])))
+    if weight is not None:
+        if isinstance(weight, (np.ndarray, torch.Tensor)) or not hasattr(weight, "__len__") or len(weight) != len(stacks):
+            raise TypeError(f"{who}: weight is a list of arrays, one per stack, or None")
+        for s, (wv, y) in enumerate(zip(weight, stacks)):
+            if isinstance(wv, np.ndarray) != as_numpy:
+                raise TypeError(f"{who}: weight must be given like stacks ({'ndarrays' if as_numpy else 'device tensors'})")
+            _fourier_input(who, wv)
+            if tuple(wv.shape) != tuple(y.shape) or (not as_numpy and wv.dtype != y.dtype):
+                raise ValueError(f"{who}: weight {s} must have shape {tuple(y.shape)} and the type of its stack "
+                                 f"(got {tuple(wv.shape)}, {wv.dtype})")
+            if as_numpy:
+                with np.errstate(invalid="ignore"):
+                    if (wv < 0).any() or np.isinf(wv).any():
+                        raise ValueError(f"{who}: weight must be >= 0 and not infinite")
+    if x0 is not None:
+        if isinstance(x0, np.ndarray) != as_numpy:
+            raise TypeError(f"{who}: x0 must be given like stacks ({'an ndarray' if as_numpy else 'a device tensor'})")
+        _fourier_input(who, x0)
+        if tuple(x0.shape) != lead + hr or (not as_numpy and x0.dtype != stacks[0].dtype):
+            raise ValueError(f"{who}: x0 must have shape {lead + hr} and the type of stacks (got {tuple(x0.shape)}, {x0.dtype})")
+
+    def rows(arrays):
+        flat = [_volume_batch(a, as_numpy) for a in arrays]
+        return torch.cat([a.reshape(a.shape[0], -1) for a in flat], dim=1).contiguous()
+
+    y = rows(stacks)
+    wt = None if weight is None else rows(weight)
+    start = None if x0 is None else _volume_batch(x0, as_numpy)
+    out, energy, change, valid = ops.tvms_solve(y, table, hr, lam, huber, int(n_iter), g, wt, start)
+    out = out.reshape(*lead, *hr)
+    info = {"energy": energy.reshape(lead), "change": change.reshape(lead), "valid_fraction": valid.reshape(lead)}
+    if as_numpy:
+        out, info = out.cpu().numpy(), {name: v.cpu().numpy() for name, v in info.items()}
+    return (out, info) if return_info else out
 
 
 def resize_z(arr, new_size: int = 128, kind: str = 'cubic'):

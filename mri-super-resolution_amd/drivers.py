@@ -1028,7 +1028,106 @@ def through_plane_study(volume, factor=2, profile="mean", fwhm=None, tv_lambda=N
 
 
 # ---------------------------------------------------------------------------------------------------
-MULTI_FRAME_METHODS = ("replicate", "tv", "ignored", "estimated", "true")
+MULTI_STACK_DESIGNS = ("shifted", "orthogonal", "overlap")
+MULTI_STACK_TRIM = 2            # thin slices left out of the PSNR at either end of the volume
+
+
+def check_multi_stack(design="shifted", factor=2, noise=0.0, fwhm=None, tv_lambda=0.01, tv_huber=0.01, tv_iters=300, tv_gz=1.0):
+    """What ``multi_stack_study`` cannot serve, by name; touches neither the input nor the device."""
+    who = "multi_stack_study"
+    if design not in MULTI_STACK_DESIGNS:
+        raise ValueError(f"{who}: design must be one of {', '.join(MULTI_STACK_DESIGNS)} (got {design!r})")
+    if isinstance(factor, bool) or int(factor) != factor or not 2 <= factor <= ops.TVSR_MAX_FACTOR:
+        raise ValueError(f"{who}: factor is the slice thickness in thin slices, 2 .. {ops.TVSR_MAX_FACTOR} (got {factor!r})")
+    if not 0.0 <= float(noise) < float("inf"):
+        raise ValueError(f"{who}: noise must be finite and >= 0 (got {noise!r})")
+    if fwhm is not None:
+        if design != "overlap":
+            raise ValueError(f"{who}: fwhm belongs to design='overlap' (got design={design!r})")
+        if not 0.0 < float(fwhm) < float("inf"):
+            raise ValueError(f"{who}: fwhm must be finite and > 0, in thick slices (got {fwhm!r})")
+    for name, value in (("tv_lambda", tv_lambda), ("tv_huber", tv_huber), ("tv_gz", tv_gz)):
+        if not 0.0 <= float(value) < float("inf"):
+            raise ValueError(f"{who}: {name} must be finite and >= 0 (got {value!r})")
+    if int(tv_iters) != tv_iters or not 1 <= tv_iters <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: tv_iters must be 1 .. 100,000 (got {tv_iters!r})")
+
+
+def multi_stack_designs(design, factor=2, fwhm=None):
+    """The stacks of a design as ``baselines.stack_geometry`` records, thin slices along axis 0: ``shifted`` -- two axial stacks of
+    thickness ``factor``, the second displaced by ``factor // 2`` thin slices; ``orthogonal`` -- axial, coronal and sagittal, each
+    thick by ``factor`` on its own axis; ``overlap`` -- one axial stack with ``2 * factor`` Gaussian taps (``fwhm`` thick slices,
+    default 1) at spacing ``factor``.  -> (names, geometries)."""
+    from . import baselines
+    one, mean = np.ones(1), np.full(factor, 1.0 / factor)
+    if design == "shifted":
+        return ("axial", "axial_shifted"), [baselines.stack_geometry((factor, 1, 1), (mean, one, one)),
+                                            baselines.stack_geometry((factor, 1, 1), (mean, one, one), (factor // 2, 0, 0))]
+    if design == "orthogonal":
+        return ("axial", "coronal", "sagittal"), [baselines.stack_geometry((factor, 1, 1), (mean, one, one)),
+                                                  baselines.stack_geometry((1, factor, 1), (one, mean, one)),
+                                                  baselines.stack_geometry((1, 1, factor), (one, one, mean))]
+    taps = baselines.profile_taps(2 * factor, factor, "gaussian", 1.0 if fwhm is None else fwhm)
+    return ("axial_overlap",), [baselines.stack_geometry((factor, 1, 1), (taps, one, one))]
+
+
+def multi_stack_study(volume, design, factor=2, noise=0.0, seed=0, fwhm=None, tv_lambda=None, tv_huber=None, tv_iters=None, tv_gz=1.0):
+    """``volume`` [Z, X, Y] in [0, 1], thin slices along Z: the stacks of ``design`` (``multi_stack_designs``) formed from the thin
+    slices by ``baselines.stack_apply`` -- plus Gaussian noise of ``noise`` drawn from ``np.random.default_rng(seed)``, the stacks in
+    order --, and their reconstructions on the thin slices, all float64 on the device: every stack alone by
+    ``baselines.tv_superres_stacks`` (``<name>``) and, where it is a block stack that tiles the volume, also by
+    ``baselines.tv_superres3d`` (``<name>_tv3d``); ``mean``, the voxel-wise mean of the single-stack solves; ``joint``, all stacks in one
+    solve.  Gradient weights ``(tv_gz, 1, 1)``; the ``TVMS_DEFAULT_*`` where an argument is None (they belong to three stacks at noise
+    0.02).  Returns ``{"volumes", "stacks", "geometries", "names", "psnr", "ssim", "valid", "info"}``: float64 device volumes [Z, X, Y]
+    (``hr`` and the methods), the stacks' data, PSNR (data range 1) over the thin slices ``MULTI_STACK_TRIM:-MULTI_STACK_TRIM`` -- the end
+    slices, which a displaced stack does not cover, are left out -- and SSIM by the reference protocol [Z] per method."""
+    from . import baselines
+
+    lam = baselines.TVMS_DEFAULT_LAMBDA if tv_lambda is None else tv_lambda
+    huber = baselines.TVMS_DEFAULT_HUBER if tv_huber is None else tv_huber
+    iters = baselines.TVMS_DEFAULT_ITERS if tv_iters is None else tv_iters
+    check_multi_stack(design, factor, noise, fwhm, lam, huber, iters, tv_gz)
+    vol = np.asarray(volume, dtype=np.float64)
+    if vol.ndim != 3:
+        raise ValueError(f"multi_stack_study: the volume is [Z, X, Y] (got {vol.shape})")
+    if vol.shape[0] < 2 * MULTI_STACK_TRIM + 2 * factor:
+        raise ValueError(f"multi_stack_study: {vol.shape[0]} slices are too few for thick slices of {factor} and a margin of "
+                         f"{MULTI_STACK_TRIM}")
+    dev = ops.require_gpu()
+    hr = torch.from_numpy(np.ascontiguousarray(vol)).to(dev)
+    names, geos = multi_stack_designs(design, int(factor), fwhm)
+    rng = np.random.default_rng(seed)
+    stacks = []
+    for geo in geos:
+        y = baselines.stack_apply(hr, geo)
+        if noise > 0:
+            y = y + float(noise) * torch.from_numpy(rng.standard_normal(tuple(y.shape))).to(dev)
+        stacks.append(y.contiguous())
+    g = (float(tv_gz), 1.0, 1.0)
+    recon, info = {}, {}
+    for name, geo, y in zip(names, geos, stacks):
+        recon[name], meta = baselines.tv_superres_stacks([y], [geo], vol.shape, lam, huber, int(iters), g, return_info=True)
+        info[name] = {k: float(v) for k, v in meta.items()}
+        block = all(len(k) == f for k, f in zip(geo.kernels, geo.factors)) and geo.offsets == (0, 0, 0)
+        if block and all(n * f == N for n, f, N in zip(y.shape, geo.factors, vol.shape)):
+            recon[name + "_tv3d"] = baselines.tv_superres3d(y, geo.factors, geo.kernels, lam, huber, int(iters), g)
+    if len(names) > 1:
+        recon["mean"] = sum(recon[name] for name in names) / float(len(names))
+        recon["joint"], meta = baselines.tv_superres_stacks(stacks, geos, vol.shape, lam, huber, int(iters), g, return_info=True)
+        info["joint"] = {k: float(v) for k, v in meta.items()}
+    ok = hr.amax(dim=(-2, -1)) > 0
+    safe = lambda t: torch.where(ok[..., None, None], t, torch.ones_like(t)).clamp_min(1e-30).float()   # empty slices: finite, ignored
+    core = slice(MULTI_STACK_TRIM, vol.shape[0] - MULTI_STACK_TRIM)
+    psnr, ssim = {}, {}
+    for name, v in recon.items():
+        psnr[name] = float(-10.0 * torch.log10(((hr[core] - v[core]) ** 2).mean()))
+        ssim[name] = metrics.ssim_reference_protocol(safe(hr), safe(v)).cpu().numpy()
+    return {"volumes": {"hr": hr, **recon}, "stacks": stacks, "geometries": geos, "names": names, "psnr": psnr, "ssim": ssim,
+            "valid": ok.cpu().numpy(), "info": info}
+
+
+# ---------------------------------------------------------------------------------------------------
+MULTI_FRAME_METHODS =("replicate", "tv", "ignored", "estimated", "true")
 MULTI_FRAME_MARGIN = 4
 
 

@@ -1008,6 +1008,121 @@ def tvmf_solve(y: torch.Tensor, shifts: torch.Tensor, factors, kernel, lam: floa
     return out, energy, change, valid
 
 
+# ---- multi-stack 3-D TV / Huber reconstruction with general slice profiles (include/inrhip.h) --------------------------
+TVMS_MAX_STACKS, TVMS_MAX_TAPS = _lib.INR_TVMS_MAX_STACKS, _lib.INR_TVMS_MAX_TAPS
+TVMS_MAX_OFFSET, TVMS_MAX_EXTENT = 1 << 20, 2048
+
+
+def _stack_tables(name, stacks, D, H, W):
+    """``stacks``: a sequence of (f [3], taps (k0, k1, k2), o [3], n [3]) -> (S, M, the C arrays ``geometry`` int [S][12] and ``taps``, the
+    per-stack shapes); refuses what the entry points would refuse."""
+    if not all(1 <= s <= TVSR_MAX_SIDE for s in (D, H, W)):
+        raise ValueError(f"{name}: HR volumes are 1 .. {TVSR_MAX_SIDE} samples per axis (got {D} x {H} x {W})")
+    stacks = list(stacks)
+    if not 1 <= len(stacks) <= TVMS_MAX_STACKS:
+        raise ValueError(f"{name}: stacks per volume are 1 .. {TVMS_MAX_STACKS} (got {len(stacks)})")
+    geo, taps, shapes = [], [], []
+    for s, (f, ks, o, n) in enumerate(stacks):
+        f, o, n = (tuple(int(v) for v in t) for t in (f, o, n))
+        ks = [[float(v) for v in k] for k in ks]
+        if len(f) != 3 or len(o) != 3 or len(n) != 3 or len(ks) != 3:
+            raise ValueError(f"{name}: stack {s} needs three spacings, tap vectors, offsets and extents")
+        if not all(1 <= v <= TVSR_MAX_FACTOR for v in f):
+            raise ValueError(f"{name}: spacings are 1 .. {TVSR_MAX_FACTOR} per axis (stack {s}: {f})")
+        if not all(1 <= len(k) <= TVMS_MAX_TAPS for k in ks):
+            raise ValueError(f"{name}: tap counts are 1 .. {TVMS_MAX_TAPS} per axis (stack {s}: {[len(k) for k in ks]})")
+        if not all(abs(v) <= TVMS_MAX_OFFSET for v in o):
+            raise ValueError(f"{name}: offsets are within +-{TVMS_MAX_OFFSET} HR voxels (stack {s}: {o})")
+        if not all(1 <= v <= TVMS_MAX_EXTENT for v in n):
+            raise ValueError(f"{name}: LR extents are 1 .. {TVMS_MAX_EXTENT} per axis (stack {s}: {n})")
+        for axis, k in enumerate(ks):
+            if not all(v == v and abs(v) != float("inf") for v in k) or abs(sum(k) - 1.0) > 1e-9:
+                raise ValueError(f"{name}: taps k{axis} of stack {s} must be finite and sum to 1 (sum {sum(k)!r})")
+            taps.extend(k)
+        geo.extend(f + tuple(len(k) for k in ks) + o + n)
+        shapes.append(n)
+    M = sum(n[0] * n[1] * n[2] for n in shapes)
+    return len(stacks), M, (C.c_int * len(geo))(*geo), (C.c_double * len(taps))(*taps), shapes
+
+
+def stack_apply(x: torch.Tensor, stacks, return_valid: bool = False):
+    """``inr_tvms_apply``: ``x`` [n, D, H, W] float64 -> the data ``(A_s x)_s`` [n, M], 0 at invalid data; ``stacks`` as
+    ``_stack_tables`` takes them; ``return_valid``: also the validity mask, a bool tensor [n, M]."""
+    _chk_volumes(x, "x")
+    n, D, H, W = x.shape
+    S, M, geo, taps, _ = _stack_tables("stack_apply", stacks, D, H, W)
+    out = torch.empty((n, M), dtype=torch.float64, device=x.device)
+    valid = torch.empty(out.shape, dtype=torch.uint8, device=x.device) if return_valid else None
+    check(lib().inr_tvms_apply(out.data_ptr(), _ptr(valid), x.data_ptr(), n, D, H, W, S, geo, taps, _stream()), "inr_tvms_apply")
+    return (out, valid.bool()) if return_valid else out
+
+
+def _chk_rows(t, name, dtypes, n, M):
+    """A contiguous device batch [n, M] of one of ``dtypes`` (n None: any)."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
+    if not t.is_cuda:
+        raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
+    if t.dim() != 2 or not t.is_contiguous() or t.shape[1] != M or (n is not None and t.shape[0] != n):
+        raise ValueError(f"{name} must be a contiguous [{'n' if n is None else n}, {M}] batch (got {tuple(t.shape)})")
+    return t
+
+
+def stack_adjoint(r: torch.Tensor, stacks, hr_shape) -> torch.Tensor:
+    """``inr_tvms_adjoint``: ``r`` [n, M] float64 -> ``sum_s A_s^T r_s`` [n, D, H, W]."""
+    D, H, W = (int(v) for v in hr_shape)
+    S, M, geo, taps, _ = _stack_tables("stack_adjoint", stacks, D, H, W)
+    _chk_rows(r, "r", (torch.float64,), None, M)
+    n = r.shape[0]
+    out = torch.empty((n, D, H, W), dtype=torch.float64, device=r.device)
+    check(lib().inr_tvms_adjoint(out.data_ptr(), r.data_ptr(), n, D, H, W, S, geo, taps, _stream()), "inr_tvms_adjoint")
+    return out
+
+
+def tvms_workspace_doubles(n: int, D: int, H: int, W: int, stacks) -> int:
+    """``inr_tvms_workspace_doubles``; 0 for sizes ``inr_tvms_solve`` refuses."""
+    S, _, geo, _, _ = _stack_tables("tvms_workspace_doubles", stacks, int(D), int(H), int(W))
+    return int(lib().inr_tvms_workspace_doubles(int(n), int(D), int(H), int(W), S, geo))
+
+
+def tvms_solve(y: torch.Tensor, stacks, hr_shape, lam: float, alpha: float, n_iter: int, grad_weights=(1.0, 1.0, 1.0), weight=None,
+               x0=None, workspace=None):
+    """``inr_tvms_solve`` / ``_f32`` by the dtype of ``y`` [n, M]: returns (x [n, D, H, W] of that dtype, energy [n], change [n],
+    valid_fraction [n], all float64).  ``stacks`` as ``_stack_tables`` takes them; ``weight`` [n, M] and ``x0`` [n, D, H, W] share the
+    dtype of ``y``; ``workspace``: a float64 tensor."""
+    D, H, W = (int(v) for v in hr_shape)
+    S, M, geo, taps, _ = _stack_tables("tvms_solve", stacks, D, H, W)
+    _chk_rows(y, "y", (torch.float32, torch.float64), None, M)
+    n = y.shape[0]
+    if weight is not None:
+        _chk_rows(weight, "weight", (y.dtype,), n, M)
+    if x0 is not None:
+        _chk_volumes(x0, "x0", (y.dtype,), (n, D, H, W))
+    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= TVSR3D_MAX_ITER:
+        raise ValueError(f"tvms_solve: lam and alpha must be finite and >= 0, n_iter 0 .. {TVSR3D_MAX_ITER} (got {lam!r}, {alpha!r}, "
+                         f"{n_iter})")
+    g = [float(v) for v in grad_weights]
+    if len(g) != 3 or not all(0.0 <= v < float("inf") for v in g):
+        raise ValueError(f"tvms_solve: grad_weights are three finite values >= 0 (got {tuple(grad_weights)!r})")
+    out = torch.empty((n, D, H, W), dtype=y.dtype, device=y.device)
+    energy, change, valid = (torch.zeros(n, dtype=torch.float64, device=y.device) for _ in range(3))
+    if n == 0:
+        return out, energy, change, valid
+    need = int(lib().inr_tvms_workspace_doubles(n, D, H, W, S, geo))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
+    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
+        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
+    entry = "inr_tvms_solve" if y.dtype == torch.float64 else "inr_tvms_solve_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), valid.data_ptr(), y.data_ptr(), _ptr(weight),
+                                _ptr(x0), n, D, H, W, S, geo, taps, (C.c_double * 3)(*g), lam, alpha, n_iter, workspace.data_ptr(),
+                                workspace.numel(), _stream()), entry)
+    return out, energy, change, valid
+
+
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
                    "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order
