@@ -664,6 +664,54 @@ int inr_tvms_solve_f32(float* out, double* energy, double* change, double* valid
                        const double* taps, const double* grad_weights, double lambda, double alpha, int n_iter, double* workspace,
                        int64_t workspace_doubles, void* stream);
 
+/* ---- TV / Huber super-resolution under a dense separable acquisition model ---------------------------------------------
+ * No counterpart in the reference.  Images are [n_images][H][W] (HR) and [n_images][h][w] (LR); H = height, W = width, h = lr_height,
+ * w = lr_width, each 1 .. INR_TVSR_MAX_SIDE, h and w below, equal to or above H and W.  The acquisition model is ANY separable linear
+ * operator given by r0 [h][H] and r1 [w][W], dense DEVICE doubles shared by the whole batch (inr_fourier_operator forms k-space
+ * truncation in this layout):
+ *   A x = (R0 x) R1^T [h][w],   A^T r = R0^T (r R1) [H][W].
+ * Their values are not inspected: no operator, weight or datum value reaches an index, and a NaN gives NaNs and no fault.  Every
+ * contraction is a batched fp64 GEMM on v_mfma_f64_16x16x4_f64 with a fixed K order and no atomics (the tile loop of
+ * inr_fourier_resample2d); both directions pass through a plane [n][h][W] of the workspace.
+ * inr_tvop_apply: out [n][h][w] = A in.  inr_tvop_adjoint: out [n][H][W] = A^T in.  fp64, two launches each, out must not overlap in.
+ *   They are the launches of the solver with a plain store: A x has the same bits in both.
+ * inr_tvop_solve2d: out [n][H][W] = n_iter iterations of Chambolle-Pock with both terms dual (the iteration of inr_tvmf_solve2d) on
+ *   min_x 1/2 sum_i w_i ((A x)_i - y_i)^2 + lambda sum_j H_alpha(|(grad x)_j|)   (grad, div, H_alpha: inr_tvsr_solve2d),
+ *   from x = xbar = x0, p = 0, q = 0:
+ *     p <- (p + sigma grad(xbar)) / (1 + sigma alpha / lambda);  p <- p / max(1, |p| / lambda)   (lambda == 0: p = 0)
+ *     q <- (q + sigma (A xbar - y)) / (1 + sigma / w) where w > 0, else 0
+ *     x' <- x - tau (A^T q - div p);  xbar <- 2 x' - x;  x <- x'
+ *   tau = sigma = 1 / sqrt(8 + c0 c1), c_a = (max_i sum_j |R_a[i][j]|) (max_j sum_i |R_a[i][j]|) >= |R_a|_2^2, the sums in ascending
+ *   index, formed by a kernel and read from the workspace by the others: there is no host read in a solve.
+ *   y [n][h][w]; weight [n][h][w] or null (= 1; finite and >= 0 -- device data, not checked; <= 0 or NaN is a missing datum, whose y is
+ *   never used and may be NaN); x0 [n][H][W] or null: the normalised back-projection through the absolute operators,
+ *   (|R0|^T (u y) |R1|) / (|R0|^T u |R1|) with u = [w > 0], 0 where the denominator is not > 0.  energy / change [n] DEVICE doubles or
+ *   null: the objective at the returned fp64 image and max |x' - x| of the last iteration (0 for n_iter == 0, which returns the start).
+ *   Launches: step, init, without x0 the back-projection (the adjoint's two launches twice); per iteration a dual launch (thread per HR
+ *   pixel; skipped for lambda == 0) and four GEMM launches -- R0 xbar, (.) R1^T with the q update as its epilogue, q R1, R0^T (.) with
+ *   the primal update as its epilogue --; A x once more with the data term summed per tile, an HR-tile launch (the result, the prior)
+ *   and a fixed-order finish.  Plain launches on `stream`, no host read, no atomics: calls are bit-equal on any stream and at any place
+ *   in a batch.  The _f32 form reads y / weight / x0 and writes out as fp32, with fp64 operators and state, and rounds once.
+ *   n_images == 0 succeeds and launches nothing.
+ * workspace: inr_tvop_workspace_doubles(n_images, H, W, h, w) doubles for every entry above, 16-byte aligned; 0 for sizes that would be
+ * refused.  With e(v) = v rounded up to even, T(v) = ceil(v / 64), TL = T(h) T(w), TH = T(H) T(W) it is
+ *   2 + e(4 n H W) + e(n h w) + e(n h W) + e(n (TL + TH)) + e(n TH)
+ * (the step, the state x | xbar | p0 | p1, q, the plane, the partials of energy and of change; n = 1 for n_images == 0).
+ * Refusals, all before any device work: INR_E_INVALID (null out / y / in / r0 / r1, n_images < 0, a side out of range, n_iter outside
+ * 0 .. INR_TVSR3D_MAX_ITER, a negative or non-finite lambda / alpha), INR_E_WORKSPACE (null or short workspace), INR_E_ALIGN (workspace
+ * off a 16-byte boundary). */
+int64_t inr_tvop_workspace_doubles(int n_images, int height, int width, int lr_height, int lr_width);
+int inr_tvop_apply(double* out, const double* in, const double* r0, const double* r1, int n_images, int height, int width, int lr_height,
+                   int lr_width, double* workspace, int64_t workspace_doubles, void* stream);
+int inr_tvop_adjoint(double* out, const double* in, const double* r0, const double* r1, int n_images, int height, int width, int lr_height,
+                     int lr_width, double* workspace, int64_t workspace_doubles, void* stream);
+int inr_tvop_solve2d(double* out, double* energy, double* change, const double* y, const double* weight, const double* x0,
+                     const double* r0, const double* r1, int n_images, int height, int width, int lr_height, int lr_width, double lambda,
+                     double alpha, int n_iter, double* workspace, int64_t workspace_doubles, void* stream);
+int inr_tvop_solve2d_f32(float* out, double* energy, double* change, const float* y, const float* weight, const float* x0,
+                         const double* r0, const double* r1, int n_images, int height, int width, int lr_height, int lr_width,
+                         double lambda, double alpha, int n_iter, double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
  * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
  * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output

@@ -202,6 +202,12 @@ SIGNATURES = {
     "inr_tvms_solve_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 5 +
                            [C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 2 +
                            [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvop_workspace_doubles": (C.c_int64, [C.c_int] * 5),
+    "inr_tvop_apply": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvop_adjoint": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvop_solve2d": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvop_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
+                             [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
     "inr_footprint_expand": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
     "inr_footprint_reduce": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_footprint_loss_workspace_floats": (C.c_int64, [C.c_int64]),

@@ -41,6 +41,11 @@ register-and-average baseline is not (it aligns to whole pixels and discards wha
 volumes: 1 .. 8 stacks of thick slices of one volume -- different orientations, whole-voxel offsets, slice profiles wider
 (overlapping) or narrower (gapped) than the slice spacing --, one operator ``A_s`` per stack with a validity rule for footprints that
 leave the volume, data and prior both dual (``inr_tvms_solve``) -- what ``scripts/multi_stack`` scores.
+
+``tv_superres_operator``, ``operator_apply``, ``operator_adjoint``, ``psf_operator`` and ``block_operator`` are the same prior under
+ANY separable linear acquisition model ``A x = R0 x R1^T`` with dense operators: k-space truncation (``fourier_operator``), a
+point-spread function wider than the pixel, a ratio that is no whole number -- the models the block solvers cannot write.  Two fp64
+GEMMs per operator application inside the iteration (``inr_tvop_solve2d``).
 """
 from __future__ import annotations
 
@@ -918,6 +923,178 @@ def tv_superres_stacks(stacks, geometries, hr_shape, lam: float = TVMS_DEFAULT_L
     if as_numpy:
         out, info = out.cpu().numpy(), {name: v.cpu().numpy() for name, v in info.items()}
     return (out, info) if return_info else out
+
+
+# the sweep of DESIGN.md 4p (k-space truncation and a Gaussian PSF, x2, noise 0.02 of a [0, 1] image)
+TVOP_DEFAULT_LAMBDA, TVOP_DEFAULT_HUBER, TVOP_DEFAULT_ITERS = 3e-3, 0.03, 500
+
+
+def psf_operator(n, m, fwhm, kind: str = "gaussian"):
+    """The operator [m][n] of one axis for a point-spread function wider (or narrower) than the pixel, a float64 ndarray formed on the
+    host: row ``i`` is centred on HR sample ``(i + 1/2) n / m - 1/2`` -- pixel centres, any ratio ``n / m`` -- and has the full width at
+    half maximum ``fwhm`` in LR pixels.  'gaussian': the Gaussian sampled at the HR samples; 'box': the overlap of a box of that width
+    with every sample's unit cell (``fwhm = 1`` on a whole ratio is the block mean).  Every row is normalised to sum 1 over the samples
+    inside the line.  For ``tv_superres_operator``, ``operator_apply`` and ``operator_adjoint``."""
+    who = "psf_operator"
+    for name, v in (("n", n), ("m", m)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= int(v) <= ops.TVSR_MAX_SIDE:
+            raise ValueError(f"{who}: {name} is an integer 1 .. {ops.TVSR_MAX_SIDE} (got {v!r})")
+    if kind not in ("gaussian", "box"):
+        raise ValueError(f"{who}: kind must be 'gaussian' or 'box' (got {kind!r})")
+    try:
+        ok = 0.0 < float(fwhm) < np.inf
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"{who}: fwhm must be finite and > 0, in LR pixels (got {fwhm!r})")
+    n, m = int(n), int(m)
+    centre = (np.arange(m) + 0.5) * n / m - 0.5
+    j = np.arange(n, dtype=np.float64)
+    width = float(fwhm) * n / m                                     # in HR samples
+    if kind == "gaussian":
+        sigma = width / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+        op = np.exp(-0.5 * ((j[None, :] - centre[:, None]) / sigma) ** 2)
+    else:
+        lo, hi = centre[:, None] - width / 2.0, centre[:, None] + width / 2.0
+        op = np.clip(np.minimum(hi, j[None, :] + 0.5) - np.maximum(lo, j[None, :] - 0.5), 0.0, None)
+    total = op.sum(axis=1, keepdims=True)
+    if not (total > 0.0).all():
+        raise ValueError(f"{who}: fwhm {fwhm!r} is too narrow: a row of the operator holds no sample")
+    return op / total
+
+
+def block_operator(n, f, kernel="mean"):
+    """The dense form [n / f][n] of a 1-D block kernel, a float64 ndarray: ``op[i][f i + a] = kernel[a]`` -- 'mean' (1 / f), 'decimate'
+    (the block's first sample) or ``f`` finite values that sum to 1.  ``(block_operator(H, f0, k0), block_operator(W, f1, k1))`` is the
+    operator of ``block_apply`` with the kernel ``outer(k0, k1)``."""
+    who = "block_operator"
+    if isinstance(f, bool) or int(f) != f or not 1 <= int(f) <= ops.TVSR_MAX_FACTOR:
+        raise ValueError(f"{who}: f is an integer 1 .. {ops.TVSR_MAX_FACTOR} (got {f!r})")
+    if isinstance(n, bool) or int(n) != n or not 1 <= int(n) <= ops.TVSR_MAX_SIDE or int(n) % int(f):
+        raise ValueError(f"{who}: n is an integer 1 .. {ops.TVSR_MAX_SIDE} and a whole number of blocks of {f} (got {n!r})")
+    n, f = int(n), int(f)
+    if isinstance(kernel, str):
+        if kernel == "mean":
+            k = np.full(f, 1.0 / f)
+        elif kernel == "decimate":
+            k = np.zeros(f)
+            k[0] = 1.0
+        else:
+            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or {f} values (got {kernel!r})")
+    else:
+        k = np.asarray(kernel, dtype=np.float64)
+        if k.shape != (f,):
+            raise ValueError(f"{who}: the kernel array must have {f} entries (got shape {k.shape})")
+        if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
+            raise ValueError(f"{who}: the kernel array must be finite and sum to 1 (got sum {k.sum()!r})")
+    op = np.zeros((n // f, n))
+    for i in range(n // f):
+        op[i, f * i:f * i + f] = k
+    return op
+
+
+def _operator_pair(who, operators):
+    """``operators`` = (R0 [h, H], R1 [w, W]), float64 ndarrays (finite) or device float64 tensors -> (getter of the device pair, H, W,
+    h, w), refusing by name.  Touches no device until the getter is called."""
+    try:
+        r0, r1 = operators
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: operators are a pair (R0 [h, H], R1 [w, W])") from None
+    for name, r in (("operators[0]", r0), ("operators[1]", r1)):
+        if isinstance(r, np.ndarray):
+            if r.dtype != np.float64:
+                raise TypeError(f"{who}: {name} must be float64 (got {r.dtype})")
+            if r.ndim == 2 and not np.isfinite(r).all():
+                raise ValueError(f"{who}: {name} must be finite")
+        elif isinstance(r, torch.Tensor):
+            if r.dtype != torch.float64:
+                raise TypeError(f"{who}: {name} must be float64 (got {r.dtype})")
+            if not r.is_cuda:
+                raise ops.InrDeviceError(f"{who}: {name} is on {r.device}; pass an ndarray or a device tensor (there is no CPU fallback)")
+        else:
+            raise TypeError(f"{who}: {name} must be a float64 ndarray or a device float64 tensor (got {type(r).__name__})")
+        if r.ndim != 2 or not all(1 <= int(s) <= ops.TVSR_MAX_SIDE for s in r.shape):
+            raise ValueError(f"{who}: {name} must be 2-D with sides of 1 .. {ops.TVSR_MAX_SIDE} (got shape {tuple(r.shape)})")
+    (h, H), (w, W) = (int(s) for s in r0.shape), (int(s) for s in r1.shape)
+
+    def device_pair():
+        dev = ops.require_gpu()
+        return tuple((torch.from_numpy(np.ascontiguousarray(r)).to(dev) if isinstance(r, np.ndarray) else r.contiguous()) for r in (r0, r1))
+
+    return device_pair, H, W, h, w
+
+
+def _operator_through(who, image, operators, forward):
+    pair, H, W, h, w = _operator_pair(who, operators)
+    as_numpy, rows, cols, lead = _block_input(who, image)
+    src, dst = ((H, W), (h, w)) if forward else ((h, w), (H, W))
+    if (rows, cols) != src:
+        raise ValueError(f"{who}: the operators take images of {src[0]} x {src[1]} (got {rows} x {cols})")
+    flat = _block_batch(image, as_numpy)
+    out = (ops.tvop_apply if forward else ops.tvop_adjoint)(flat.double(), pair()).to(flat.dtype).reshape(*lead, *dst)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def operator_apply(x, operators):
+    """``A x = R0 x R1^T`` on the trailing two axes of ``x`` [..., H, W] -> [..., h, w]; ``operators`` = (R0 [h, H], R1 [w, W]) as
+    float64 ndarrays or device float64 tensors (``fourier_operator``, ``psf_operator``, ``block_operator`` or any other).  Two fp64
+    GEMM launches (``inr_tvop_apply``).  ndarray in -> float64 ndarray out, device fp32 / fp64 tensor in -> the same out (fp64
+    inside, rounded once)."""
+    return _operator_through("operator_apply", x, operators, True)
+
+
+def operator_adjoint(r, operators):
+    """``A^T r = R0^T r R1`` on the trailing two axes of ``r`` [..., h, w] -> [..., H, W] (``inr_tvop_adjoint``); types as
+    ``operator_apply``."""
+    return _operator_through("operator_adjoint", r, operators, False)
+
+
+def tv_superres_operator(lr, operators, lam: float = TVOP_DEFAULT_LAMBDA, huber: float = TVOP_DEFAULT_HUBER,
+                         n_iter: int = TVOP_DEFAULT_ITERS, weight=None, x0=None, return_info: bool = False):
+    """Model-based super-resolution under ANY separable linear acquisition model: ``lr`` [..., h, w] was made as ``A x = R0 x R1^T``
+    with ``operators`` = (R0 [h, H], R1 [w, W]), float64 ndarrays (finite) or device float64 tensors shared by the whole batch --
+    k-space truncation (``fourier_operator``), a point-spread function wider than the pixel (``psf_operator``), a ratio that is no
+    whole number, a block kernel (``block_operator``).  ``n_iter`` Chambolle-Pock iterations, data and prior both dual, on
+    ``1/2 sum w (A x - lr)^2 + lam sum H_huber(|grad x|)`` with the prior of ``tv_superres``; the step comes from a bound on the
+    operators' norms formed on the device.  The defaults are those of data in [0, 1] at noise 0.02; scale ``lam`` and
+    ``huber`` with the data's range.  ``weight`` (shape of ``lr``, >= 0; 0 marks a missing datum, which is never read) defaults to 1,
+    ``x0`` [..., H, W] to the normalised back-projection through the absolute operators.  ``inr_tvop_solve2d``.
+    ndarray in -> float64 ndarray out; device fp32 / fp64 tensor in -> the same out (fp64 inside, rounded once); ``weight`` / ``x0``
+    are given like ``lr``.  There is no CPU fallback.  ``return_info``: also a dict with ``energy`` (the objective at the result) and
+    ``change`` (max |x' - x| of the last iteration), both of the leading shape."""
+    who = "tv_superres_operator"
+    pair, H, W, h, w = _operator_pair(who, operators)
+    lam, huber = float(lam), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or not 0 <= n_iter <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: n_iter must be an integer in 0 .. {ops.TVSR3D_MAX_ITER} (got {n_iter!r})")
+    as_numpy, rows, cols, lead = _block_input(who, lr, "lr")
+    if (rows, cols) != (h, w):
+        raise ValueError(f"{who}: the operators make LR images of {h} x {w} (got lr of {rows} x {cols})")
+    extra = {}
+    for name, value, shape in (("weight", weight, (h, w)), ("x0", x0, (H, W))):
+        if value is None:
+            extra[name] = None
+            continue
+        if isinstance(value, np.ndarray) != as_numpy:
+            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
+        _fourier_input(who, value)
+        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
+            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
+        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
+            raise ValueError(f"{who}: weight must be finite and >= 0")
+        extra[name] = value
+    y = _block_batch(lr, as_numpy)
+    extra = {name: None if value is None else _block_batch(value, as_numpy) for name, value in extra.items()}
+    out, energy, change = ops.tvop_solve(y, pair(), lam, huber, int(n_iter), extra["weight"], extra["x0"])
+    out = out.reshape(*lead, H, W)
+    energy, change = energy.reshape(lead), change.reshape(lead)
+    if as_numpy:
+        out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
+    return (out, {"energy": energy, "change": change}) if return_info else out
 
 
 def resize_z(arr, new_size: int = 128, kind: str = 'cubic'):

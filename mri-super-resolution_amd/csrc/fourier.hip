@@ -16,20 +16,16 @@
 // atomics: calls are bit-equal.  All arithmetic is fp64; the fp32 entry point converts on load and rounds once on the last store.
 #include <math.h>
 
+#include "gemm_f64.h"
 #include "internal.h"
 
 namespace inr {
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 constexpr int FOURIER_MAX_LINE = INR_FOURIER_MAX_LINE;
 struct FourierView { double *op_rows, *op_cols, *mid; size_t total; };
 
-constexpr int FR_TILE = 64;    // the block's output tile: 4 waves, 32 x 32 each (2 x 2 MFMA tiles)
-constexpr int FR_KS = 16;      // K per LDS stage: 4 MFMA steps
-constexpr int FR_PITCH = 81;   // doubles per staged k: the 16 k of a k-fastest store fall on 16 bank pairs, the two k of a read's lane
-                               // group on disjoint halves of the 64 banks (but for one pair)
+constexpr int FR_TILE = GF_TILE;   // the block's output tile (gemm_f64.h)
 
 // one axis: A [m][n] from the periodic operator E: En -> Em
 struct FrAxis {
@@ -97,57 +93,25 @@ struct FrGemm {
     long long c_batch, c_row;
 };
 
+// the plain store of an element, rounded once to the result's type
+template <typename TC>
+struct FrStore {
+    TC* C;
+    long long c_row;
+    __device__ __forceinline__ void operator()(long long row, int col, int, double v) const { C[row * c_row + col] = (TC)v; }
+};
+
+// the tile loop is gf_tile (gemm_f64.h), shared with tvop.hip
 template <typename TA, typename TB, typename TC>
 __global__ void __launch_bounds__(256) fr_gemm_kernel(TC* __restrict__ C, const TA* __restrict__ A, const TB* __restrict__ B, FrGemm g) {
-    __shared__ double As[FR_KS][FR_PITCH];   // [k][row]
-    __shared__ double Bs[FR_KS][FR_PITCH];   // [k][column]
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int wr = (wave >> 1) * 32, wc = (wave & 1) * 32;
-    const int l15 = lane & 15, l4 = lane >> 4;
+    __shared__ double As[GF_KS][GF_PITCH];   // [k][row]
+    __shared__ double Bs[GF_KS][GF_PITCH];   // [k][column]
     const long long row0 = (long long)blockIdx.x * FR_TILE;
     const int col0 = blockIdx.y * FR_TILE;
     for (int b = blockIdx.z; b < g.batch; b += gridDim.z) {
-        const TA* Ab = A + b * g.a_batch;
-        const TB* Bb = B + b * g.b_batch;
-        TC* Cb = C + b * g.c_batch;
-        f64x4 acc[2][2] = {};
-        for (int k0 = 0; k0 < g.K; k0 += FR_KS) {
-            for (int e = t; e < FR_TILE * FR_KS; e += 256) {
-                const int kk = e & (FR_KS - 1), r = e / FR_KS;
-                const long long row = row0 + r;
-                const int k = k0 + kk;
-                As[kk][r] = row < g.M && k < g.K ? (double)Ab[row * g.a_row + k] : 0.0;
-            }
-            for (int e = t; e < FR_TILE * FR_KS; e += 256) {
-                // the contiguous direction of B goes over neighbouring threads
-                const int kk = g.b_k == 1 ? e & (FR_KS - 1) : e / FR_TILE, c = g.b_k == 1 ? e / FR_KS : e & (FR_TILE - 1);
-                const int col = col0 + c, k = k0 + kk;
-                Bs[kk][c] = col < g.N && k < g.K ? (double)Bb[k * g.b_k + col * g.b_col] : 0.0;
-            }
-            __syncthreads();
-#pragma unroll
-            for (int ks = 0; ks < FR_KS; ks += 4) {
-                // A: lane holds A[row lane & 15][k lane >> 4]; B: B[k lane >> 4][column lane & 15]
-                const double a0 = As[ks + l4][wr + l15], a1 = As[ks + l4][wr + 16 + l15];
-                const double b0 = Bs[ks + l4][wc + l15], b1 = Bs[ks + l4][wc + 16 + l15];
-                acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-                acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-                acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-                acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-            }
-            __syncthreads();
-        }
-        // the f64 result layout: column lane & 15, row (lane >> 4) + 4 reg -- not the f32 one
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int reg = 0; reg < 4; ++reg) {
-                    const long long row = row0 + wr + 16 * mi + l4 + 4 * reg;
-                    const int col = col0 + wc + 16 * ni + l15;
-                    if (row < g.M && col < g.N) Cb[row * g.c_row + col] = (TC)acc[mi][ni][reg];
-                }
+        FrStore<TC> store{C + b * g.c_batch, g.c_row};
+        gf_tile<GfIdentity, GfIdentity>(As, Bs, A + b * g.a_batch, g.a_row, 1, B + b * g.b_batch, g.b_k, g.b_col, row0, col0, g.M, g.N, g.K, b,
+                                        store);
     }
 }
 

@@ -1216,3 +1216,105 @@ def multi_frame_study(slices, factor=2, frames=8, max_shift=1.5, noise=0.02, see
     ssim = {name: metrics.ssim(crop(hr), crop(v), 1.0).cpu().numpy() for name, v in images.items()}
     return {"images": images, "hr": hr, "frames": y, "shifts": true, "estimate": est, "psnr": psnr, "ssim": ssim,
             "shift_error": (est - true).abs().amax(dim=(1, 2)).cpu().numpy(), "info": info}
+
+
+# ---------------------------------------------------------------------------------------------------
+ACQUISITION_MODELS = ("kspace", "gaussian", "block")
+ACQUISITION_METHODS = ("spline", "zerofill", "tv_block", "tv_operator")
+
+
+def check_acquisition_model(model="kspace", side=50, factor=None, lr_side=None, fwhm=None, noise=0.02, tv_lambda=3e-3, tv_huber=0.03,
+                            tv_iters=500):
+    """What ``acquisition_model_study`` cannot serve, by name; touches neither the input nor the device.  Returns the LR side: ``side
+    / factor`` (``factor`` defaults to 2) or ``lr_side``, which may be any whole number -- the ratio need not be one."""
+    who = "acquisition_model_study"
+    if model not in ACQUISITION_MODELS:
+        raise ValueError(f"{who}: model must be one of {', '.join(ACQUISITION_MODELS)} (got {model!r})")
+    if isinstance(side, bool) or int(side) != side or not 7 <= side <= ops.TVSR_MAX_SIDE:
+        raise ValueError(f"{who}: the HR side is 7 .. {ops.TVSR_MAX_SIDE} pixels (got {side!r})")
+    if factor is not None and lr_side is not None:
+        raise ValueError(f"{who}: give factor or lr_side, not both (got {factor!r} and {lr_side!r})")
+    if lr_side is None:
+        factor = 2 if factor is None else factor
+        if isinstance(factor, bool) or int(factor) != factor or not 1 <= factor <= ops.TVSR_MAX_FACTOR or side % int(factor):
+            raise ValueError(f"{who}: factor is 1 .. {ops.TVSR_MAX_FACTOR} and divides the HR side {side} (got {factor!r})")
+        m = int(side) // int(factor)
+    else:
+        if isinstance(lr_side, bool) or int(lr_side) != lr_side or not 2 <= lr_side <= ops.TVSR_MAX_SIDE:
+            raise ValueError(f"{who}: lr_side is 2 .. {ops.TVSR_MAX_SIDE} pixels (got {lr_side!r})")
+        m = int(lr_side)
+    if model == "block" and (side % m or side // m > ops.TVSR_MAX_FACTOR):
+        raise ValueError(f"{who}: model='block' needs a whole number of blocks of at most {ops.TVSR_MAX_FACTOR} pixels ({side} -> {m})")
+    if fwhm is not None:
+        if model != "gaussian":
+            raise ValueError(f"{who}: fwhm belongs to model='gaussian' (got model={model!r})")
+        if not 0.0 < float(fwhm) < float("inf"):
+            raise ValueError(f"{who}: fwhm must be finite and > 0, in LR pixels (got {fwhm!r})")
+    if not 0.0 <= float(noise) < float("inf"):
+        raise ValueError(f"{who}: noise must be finite and >= 0 (got {noise!r})")
+    for name, value in (("tv_lambda", tv_lambda), ("tv_huber", tv_huber)):
+        if not 0.0 <= float(value) < float("inf"):
+            raise ValueError(f"{who}: {name} must be finite and >= 0 (got {value!r})")
+    if int(tv_iters) != tv_iters or not 1 <= tv_iters <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: tv_iters must be 1 .. 100,000 (got {tv_iters!r})")
+    return m
+
+
+def acquisition_operators(model, side, lr_side, fwhm=None):
+    """The pair (R0, R1) [lr_side][side] of float64 ndarrays that makes the LR data of ``acquisition_model_study``: 'kspace' is
+    ``fourier_operator(align='center', boundary='mirror')``, 'gaussian' ``psf_operator`` of ``fwhm`` LR pixels (default 1.2), 'block'
+    the block mean."""
+    from . import baselines
+    if model == "kspace":
+        op = baselines.fourier_operator(side, lr_side, "center", "mirror")
+    elif model == "gaussian":
+        op = baselines.psf_operator(side, lr_side, 1.2 if fwhm is None else fwhm, "gaussian")
+    else:
+        op = baselines.block_operator(side, side // lr_side, "mean")
+    return op, op.copy()
+
+
+def acquisition_model_study(slices, model="kspace", factor=None, lr_side=None, fwhm=None, noise=0.02, seed=0, tv_lambda=None,
+                            tv_huber=None, tv_iters=None, slice_ids=None):
+    """``slices`` [Z, R, R] in [0, 1]: the LR slices [Z, m, m] are made with the operator of ``model`` (``acquisition_operators``) plus
+    Gaussian noise of ``noise`` -- slice z (``slice_ids[i]`` for row i where given, else i) draws it from
+    ``np.random.default_rng(seed * 1000 + z)`` --, and reconstructed on the device by
+    ``spline`` (``baselines.rescale`` for a whole ratio, else ``baselines.resize``), ``zerofill`` (``baselines.fourier_resize``, 'center' /
+    'mirror'), ``tv_block`` (``baselines.tv_superres`` with the mean kernel: the model every other study assumes; absent when the ratio is
+    no whole number of blocks) and ``tv_operator`` (``baselines.tv_superres_operator`` with the operator that made the data).  Both TV
+    rows share ``tv_lambda``, ``tv_huber`` and ``tv_iters`` (the ``TVOP_DEFAULT_*`` where None): they differ in the forward model alone.
+    Returns ``{"images", "hr", "lr", "operators", "methods", "psnr", "ssim", "consistency", "info"}``: float64 device stacks, PSNR and
+    SSIM (data range 1) [Z] per method, and the PSNR of ``A tv_operator`` against the LR data [Z]."""
+    from . import baselines
+
+    lam = baselines.TVOP_DEFAULT_LAMBDA if tv_lambda is None else tv_lambda
+    huber = baselines.TVOP_DEFAULT_HUBER if tv_huber is None else tv_huber
+    iters = baselines.TVOP_DEFAULT_ITERS if tv_iters is None else tv_iters
+    vol = np.asarray(slices, np.float64)
+    if vol.ndim != 3 or vol.shape[1] != vol.shape[2]:
+        raise ValueError(f"acquisition_model_study: slices are [Z, R, R] (got {vol.shape})")
+    Z, R = vol.shape[0], vol.shape[1]
+    m = check_acquisition_model(model, R, factor, lr_side, fwhm, noise, lam, huber, iters)
+    ids = list(range(Z)) if slice_ids is None else [int(v) for v in slice_ids]
+    if len(ids) != Z or (Z and min(ids) < 0):
+        raise ValueError(f"acquisition_model_study: slice_ids are one index >= 0 per slice (got {slice_ids!r} for {Z} slices)")
+    eta = np.stack([noise * np.random.default_rng(int(seed) * 1000 + z).standard_normal((m, m)) for z in ids])
+    dev = ops.require_gpu()
+    pair = tuple(torch.from_numpy(r).to(dev) for r in acquisition_operators(model, R, m, fwhm))
+    hr = torch.from_numpy(vol).to(dev)
+    y = baselines.operator_apply(hr, pair) + torch.from_numpy(eta).to(dev)
+    whole = R % m == 0 and R // m <= ops.TVSR_MAX_FACTOR
+    images = {"spline": (baselines.rescale(y.float().contiguous(), R // m) if R % m == 0 else baselines.resize(y.float().contiguous(), (R, R))).double(),
+              "zerofill": baselines.fourier_resize(y, (R, R), "center", "mirror")}
+    info = {}
+    if whole:
+        images["tv_block"], res = baselines.tv_superres(y, (R // m, R // m), "mean", lam, huber, int(iters), return_info=True)
+        info["tv_block"] = {k: v.cpu().numpy() for k, v in res.items()}
+    images["tv_operator"], res = baselines.tv_superres_operator(y, pair, lam, huber, int(iters), return_info=True)
+    info["tv_operator"] = {k: v.cpu().numpy() for k, v in res.items()}
+    f32 = lambda t: t.float().contiguous()
+    psnr = {name: metrics.psnr(f32(hr), f32(v), 1.0, per_image=True).cpu().numpy() for name, v in images.items()}
+    ssim = {name: metrics.ssim(f32(hr), f32(v), 1.0).cpu().numpy() for name, v in images.items()}
+    consistency = metrics.psnr(f32(y), f32(baselines.operator_apply(images["tv_operator"], pair)), 1.0, per_image=True).cpu().numpy()
+    return {"images": images, "hr": hr, "lr": y, "operators": pair, "methods": tuple(images), "psnr": psnr, "ssim": ssim,
+            "consistency": consistency, "info": info}

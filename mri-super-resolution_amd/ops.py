@@ -1123,6 +1123,116 @@ def tvms_solve(y: torch.Tensor, stacks, hr_shape, lam: float, alpha: float, n_it
     return out, energy, change, valid
 
 
+# ---- TV / Huber super-resolution under a dense separable operator (include/inrhip.h) -----------------------------------
+def _chk_operators(operators, H, W, h, w):
+    """The DEVICE operators (R0 [h, H], R1 [w, W]) float64, contiguous; their values are the kernels' business."""
+    try:
+        r0, r1 = operators
+    except (TypeError, ValueError):
+        raise ValueError("operators are a pair (R0 [h, H], R1 [w, W])") from None
+    for name, r, shape in (("operators[0]", r0, (h, H)), ("operators[1]", r1, (w, W))):
+        if not isinstance(r, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor")
+        if r.dtype != torch.float64:
+            raise TypeError(f"{name} must be torch.float64 (got {r.dtype})")
+        if not r.is_cuda:
+            raise InrDeviceError(f"{name} is on {r.device}: the kernels only run on a HIP device (there is no CPU fallback)")
+        if tuple(r.shape) != shape or not r.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {list(shape)} tensor (got {tuple(r.shape)})")
+    return r0, r1
+
+
+def _operator_sides(name, operators):
+    """(H, W, h, w) from the shapes of the pair, each side 1 .. TVSR_MAX_SIDE."""
+    try:
+        r0, r1 = operators
+        (h, H), (w, W) = (int(v) for v in r0.shape), (int(v) for v in r1.shape)
+    except (TypeError, ValueError, AttributeError):
+        raise ValueError(f"{name}: operators are a pair of 2-D tensors (R0 [h, H], R1 [w, W])") from None
+    if not all(1 <= s <= TVSR_MAX_SIDE for s in (H, W, h, w)):
+        raise ValueError(f"{name}: every side of the operators is 1 .. {TVSR_MAX_SIDE} (got R0 {h} x {H}, R1 {w} x {W})")
+    return H, W, h, w
+
+
+def tvop_workspace_doubles(n: int, H: int, W: int, h: int, w: int) -> int:
+    """``inr_tvop_workspace_doubles``; 0 for sizes ``inr_tvop_solve2d`` refuses."""
+    return int(lib().inr_tvop_workspace_doubles(int(n), int(H), int(W), int(h), int(w)))
+
+
+def _tvop_workspace(workspace, need, device):
+    if workspace is None:
+        return torch.empty(need, dtype=torch.float64, device=device)
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
+        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
+    return workspace
+
+
+def tvop_apply(x: torch.Tensor, operators, workspace=None) -> torch.Tensor:
+    """``inr_tvop_apply``: ``x`` [n, H, W] float64 -> ``A x = R0 x R1^T`` [n, h, w]; ``operators`` = (R0 [h, H], R1 [w, W]), device
+    float64; ``workspace``: a float64 tensor of ``tvop_workspace_doubles(n, H, W, h, w)``."""
+    _chk_images(x, "x")
+    H, W, h, w = _operator_sides("tvop_apply", operators)
+    n = x.shape[0]
+    if tuple(x.shape[1:]) != (H, W):
+        raise ValueError(f"x has shape {tuple(x.shape)}, expected {(n, H, W)}")
+    r0, r1 = _chk_operators(operators, H, W, h, w)
+    out = torch.empty((n, h, w), dtype=torch.float64, device=x.device)
+    if n == 0:
+        return out
+    workspace = _tvop_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), x.device)
+    check(lib().inr_tvop_apply(out.data_ptr(), x.data_ptr(), r0.data_ptr(), r1.data_ptr(), n, H, W, h, w, workspace.data_ptr(),
+                               workspace.numel(), _stream()), "inr_tvop_apply")
+    return out
+
+
+def tvop_adjoint(r: torch.Tensor, operators, workspace=None) -> torch.Tensor:
+    """``inr_tvop_adjoint``: ``r`` [n, h, w] float64 -> ``A^T r = R0^T r R1`` [n, H, W]; arguments as ``tvop_apply``."""
+    _chk_images(r, "r")
+    H, W, h, w = _operator_sides("tvop_adjoint", operators)
+    n = r.shape[0]
+    if tuple(r.shape[1:]) != (h, w):
+        raise ValueError(f"r has shape {tuple(r.shape)}, expected {(n, h, w)}")
+    r0, r1 = _chk_operators(operators, H, W, h, w)
+    out = torch.empty((n, H, W), dtype=torch.float64, device=r.device)
+    if n == 0:
+        return out
+    workspace = _tvop_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), r.device)
+    check(lib().inr_tvop_adjoint(out.data_ptr(), r.data_ptr(), r0.data_ptr(), r1.data_ptr(), n, H, W, h, w, workspace.data_ptr(),
+                                 workspace.numel(), _stream()), "inr_tvop_adjoint")
+    return out
+
+
+def tvop_solve(y: torch.Tensor, operators, lam: float, alpha: float, n_iter: int, weight=None, x0=None, workspace=None):
+    """``inr_tvop_solve2d`` / ``_f32`` by the dtype of ``y`` [n, h, w]: returns (x [n, H, W] of that dtype, energy [n] float64, change
+    [n] float64).  ``operators`` = (R0 [h, H], R1 [w, W]), device float64, shared by the batch; ``weight`` [n, h, w] and ``x0``
+    [n, H, W] share the dtype of ``y``; ``workspace``: a float64 tensor."""
+    _chk_images(y, "y", (torch.float32, torch.float64))
+    H, W, h, w = _operator_sides("tvop_solve", operators)
+    n = y.shape[0]
+    if tuple(y.shape[1:]) != (h, w):
+        raise ValueError(f"y has shape {tuple(y.shape)}, expected {(n, h, w)}")
+    r0, r1 = _chk_operators(operators, H, W, h, w)
+    if weight is not None:
+        _chk_images(weight, "weight", (y.dtype,), y.shape)
+    if x0 is not None:
+        _chk_images(x0, "x0", (y.dtype,), (n, H, W))
+    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= TVSR3D_MAX_ITER:
+        raise ValueError(f"tvop_solve: lam and alpha must be finite and >= 0, n_iter 0 .. {TVSR3D_MAX_ITER} (got {lam!r}, {alpha!r}, "
+                         f"{n_iter})")
+    out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
+    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
+    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    if n == 0:
+        return out, energy, change
+    workspace = _tvop_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), y.device)
+    entry = "inr_tvop_solve2d" if y.dtype == torch.float64 else "inr_tvop_solve2d_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), r0.data_ptr(),
+                                r1.data_ptr(), n, H, W, h, w, lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()),
+          entry)
+    return out, energy, change
+
+
 # ---- diagnostics ------------------------------------------------------------------------------------------
 LAUNCH_FAMILIES = ("hp_pkd", "hp_pkc", "hp_tile", "hp_rc", "h3", "f32_pipe16", "f32_pipe", "f32_generic", "small_multi",
                    "small_step", "hp_narrow", "hp_fused_fwd", "hp_row", "small_batch")   # INR_LF_* of include/inrhip.h, in order
