@@ -712,6 +712,43 @@ int inr_tvop_solve2d_f32(float* out, double* energy, double* change, const float
                          const double* r0, const double* r1, int n_images, int height, int width, int lr_height, int lr_width,
                          double lambda, double alpha, int n_iter, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- channel-coupled (vectorial) TV / Huber super-resolution: one prior over the channels of a group --------------------
+ * No counterpart in the reference.  A group is C = channels images of one anatomy (the b-values of a DWI slice), 1 <= C <=
+ * INR_TVJ_MAX_CHANNELS: x [n_groups][C][H][W] (HR), y [n_groups][C][h][w] (LR); sides, factors and the HOST `kernel` as for
+ * inr_tvsr_solve2d.  `channel_weights` is a HOST array mu [C] of finite doubles in [0, 1], or null (all 1): with max mu <= 1 the
+ * operator K x = (mu_c grad x_c)_c keeps |K|^2 <= 8 and the steps tau = sigma = 1/sqrt(8); larger weights are a rescaled lambda / alpha.
+ * inr_tvj_solve2d: out = n_iter iterations of Chambolle-Pock on
+ *   min_x 1/2 sum_c sum_i w_ci ((A x_c)_i - y_ci)^2 + lambda sum_j H_alpha( sqrt( sum_c mu_c^2 |(grad x_c)_j|^2 ) )   (coupling 1: joint)
+ *   min_x 1/2 sum_c sum_i w_ci ((A x_c)_i - y_ci)^2 + lambda sum_c sum_j H_alpha( mu_c |(grad x_c)_j| )               (coupling 0: none)
+ *   (A, grad, div, H_alpha: inr_tvsr_solve2d), from x = xbar = x0, p = 0:
+ *     q_c <- (p_c + sigma (mu_c grad(xbar_c))) / (1 + sigma alpha / lambda)
+ *     n <- sqrt(sum_c |q_c|^2) / lambda (ascending c; none: per channel);  p_c <- n > 1 ? q_c / n : q_c       (lambda == 0: p = 0)
+ *     v_c <- x_c + tau (mu_c div(p_c));  x'_c <- v_c - A^T(c_c (A v_c - y_c)), c_ci = tau w_ci / (1 + tau w_ci |k|^2)
+ *     xbar <- 2 x' - x;  x <- x'
+ *   It replaces, per iteration, C gradients, C scalings, the reduction of the squared norms over the channel axis, the projection, C
+ *   divergences and C data proximal maps.  The expression order is that of inr_tvsr_solve2d with the products by mu_c placed as written:
+ *   C == 1, and coupling 0 with mu = 1 per channel, give its bits.  y, weight, x0 [.][C][..] as for inr_tvsr_solve2d (weight 0: a
+ *   missing datum whose y is never read; x0 null: block replication).  energy / change [n_groups] DEVICE doubles or null: the objective
+ *   at the returned fp64 x (fixed order, no float atomics) and max |x' - x| of the last iteration over all channels.  ONE launch, no
+ *   host read: one workgroup of 1,024 threads per group runs all iterations with workgroup barriers only; groups beyond the CU count
+ *   are queued.  The _f32 form reads y / weight / x0 and writes out as fp32, fp64 inside, rounded once.  n_groups == 0 succeeds and
+ *   launches nothing.
+ * workspace: inr_tvj_workspace_doubles(n_groups, C, H, W) = 4 n C H W doubles (the state x | xbar | p0 | p1 of every group; n = 1 for
+ * n_groups == 0), 16-byte aligned; 0 for sizes that would be refused.  Refusals, all before any device work: INR_E_INVALID (null out / y /
+ * kernel, n_groups < 0, channels outside 1 .. INR_TVJ_MAX_CHANNELS, factors or sizes out of range, H or W no multiple of its factor,
+ * n_iter < 0, a negative or non-finite lambda / alpha, coupling not 0 / 1, a kernel that is not finite or does not sum to 1, a channel
+ * weight that is not finite or outside [0, 1]), INR_E_WORKSPACE (null or short workspace), INR_E_ALIGN (workspace off a 16-byte
+ * boundary). */
+#define INR_TVJ_MAX_CHANNELS 16
+int64_t inr_tvj_workspace_doubles(int n_groups, int channels, int height, int width);
+int inr_tvj_solve2d(double* out, double* energy, double* change, const double* y, const double* weight, const double* x0, int n_groups,
+                    int channels, int height, int width, int f0, int f1, const double* kernel, const double* channel_weights,
+                    double lambda, double alpha, int coupling, int n_iter, double* workspace, int64_t workspace_doubles, void* stream);
+int inr_tvj_solve2d_f32(float* out, double* energy, double* change, const float* y, const float* weight, const float* x0, int n_groups,
+                        int channels, int height, int width, int f0, int f1, const double* kernel, const double* channel_weights,
+                        double lambda, double alpha, int coupling, int n_iter, double* workspace, int64_t workspace_doubles,
+                        void* stream);
+
 /* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
  * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
  * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output

@@ -26,6 +26,7 @@ INR_RESCALE_REFLECT, INR_RESCALE_EDGE, INR_RESCALE_MAX_RADIUS, INR_RESCALE_MAX_L
 INR_FOURIER_SAMPLE, INR_FOURIER_CENTER, INR_FOURIER_PERIODIC, INR_FOURIER_MIRROR, INR_FOURIER_MAX_LINE = 0, 1, 0, 1, 1024
 INR_TVSR_MAX_FACTOR, INR_TVSR_MAX_SIDE, INR_TVSR3D_MAX_ITER, INR_TVMF_MAX_FRAMES = 8, 1024, 100000, 64
 INR_TVMS_MAX_STACKS, INR_TVMS_MAX_TAPS = 8, 16
+INR_TVJ_MAX_CHANNELS = 16
 
 
 class InrHipError(RuntimeError):
@@ -208,6 +209,11 @@ SIGNATURES = {
     "inr_tvop_solve2d": (C.c_int, [C.c_void_p] * 8 + [C.c_int] * 5 + [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
     "inr_tvop_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 +
                              [C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvj_workspace_doubles": (C.c_int64, [C.c_int] * 4),
+    "inr_tvj_solve2d": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.POINTER(C.c_double)] * 2 + [C.c_double, C.c_double, C.c_int, C.c_int,
+                                                                                                C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvj_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 6 +
+                            [C.POINTER(C.c_double)] * 2 + [C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int64, c_stream]),
     "inr_footprint_expand": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
     "inr_footprint_reduce": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_footprint_loss_workspace_floats": (C.c_int64, [C.c_int64]),

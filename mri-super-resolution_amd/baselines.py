@@ -46,6 +46,11 @@ leave the volume, data and prior both dual (``inr_tvms_solve``) --
 ANY separable linear acquisition model ``A x = R0 x R1^T`` with dense operators: k-space truncation (``fourier_operator``), a
 point-spread function wider than the pixel, a ratio that is no whole number -- the models the block solvers cannot write.  Two fp64
 GEMMs per operator application inside the iteration (``inr_tvop_solve2d``).
+
+``tv_superres_joint`` and ``channel_weights`` are the block solver with ONE prior over the channels of a group -- the b-values of a
+DWI slice --: one gradient norm per pixel over all channels (vectorial TV / Huber), so that the low-SNR channels take their edges
+from the others.  One workgroup per group (``inr_tvj_solve2d``); what ``superresDWI --tv_joint`` and
+``scripts/joint_bvalues`` score.
 """
 from __future__ import annotations
 
@@ -354,7 +359,97 @@ def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, hube
     return (out, {"energy": energy, "change": change}) if return_info else out
 
 
-TVMF_DEFAULT_LAMBDA, TVMF_DEFAULT_HUBER, TVMF_DEFAULT_ITERS = 0.01, 0.03, 300  # the sweep of DESIGN.md 4n (8 frames, noise 0.02)
+TVJ_DEFAULT_LAMBDA, TVJ_DEFAULT_HUBER, TVJ_DEFAULT_ITERS = 0.048, 0.01, 300    # the sweep of DESIGN.md 4q (ADC RMSE, noise 0.02)
+
+
+def channel_weights(lr, rule: str = "equal"):
+    """The channel weights ``mu`` [C] (float64 ndarray) of ``tv_superres_joint`` for ``lr`` [..., C, h, w].  'equal': all 1.
+    'sqrt_signal': ``mu_c = sqrt(min_c' m_c' / m_c)`` with ``m_c`` the mean of channel c over every other axis -- the strongest channel
+    gets the smallest weight, the weakest gets 1, so that no channel's edges drown the others' in the joint norm, and every weight
+    is within (0, 1] as the solver's step bound requires.  The means are ONE host read of C values, taken here, outside the solve
+    (which reads nothing back); a channel whose mean is not positive raises."""
+    who = "channel_weights"
+    as_numpy = _fourier_input(who, lr)
+    if lr.ndim < 3:
+        raise ValueError(f"{who} needs at least 3-D input [..., C, h, w]")
+    C = int(lr.shape[-3])
+    if rule == "equal":
+        return np.ones(C, np.float64)
+    if rule != "sqrt_signal":
+        raise ValueError(f"{who}: rule must be 'equal' or 'sqrt_signal' (got {rule!r})")
+    axes = tuple(a for a in range(lr.ndim) if a != lr.ndim - 3)
+    m = np.asarray(lr, np.float64).mean(axis=axes) if as_numpy else lr.double().mean(dim=axes).cpu().numpy()
+    if not (np.isfinite(m).all() and (m > 0).all()):
+        raise ValueError(f"{who}: 'sqrt_signal' needs a positive mean in every channel (got {m.tolist()})")
+    return np.sqrt(m.min() / m)
+
+
+def tv_superres_joint(lr, factors, kernel="mean", lam: float = TVJ_DEFAULT_LAMBDA, huber: float = TVJ_DEFAULT_HUBER,
+                      n_iter: int = TVJ_DEFAULT_ITERS, channel_weights=None, coupling: str = "joint", weight=None, x0=None,
+                      return_info: bool = False):
+    """``tv_superres`` with ONE prior over the channels of a group: ``lr`` [..., C, h, w], the third axis from the end the channel axis
+    (the b-values of a slice), 1 <= C <= 16, leading axes a batch of groups.  ``n_iter`` Chambolle-Pock iterations on
+    ``1/2 sum_c sum w (A x_c - lr_c)^2 + lam sum_j H_huber(sqrt(sum_c mu_c^2 |grad x_c|_j^2))``: one gradient norm per pixel over all
+    channels, so that edges are shared and noise is not.  ``coupling='none'`` takes the norm per channel
+    (``sum_c lam H_huber(mu_c |grad x_c|)``; with ``mu = 1`` that is ``tv_superres`` of every channel, bit for bit).
+    ``channel_weights``: C values in [0, 1] (``channel_weights(lr, rule)``; None: all 1) -- larger weights are a rescaled ``lam`` and
+    ``huber``.  At equal ``lam`` the coupled prior is weaker per channel than the per-channel one: it has defaults of its own.
+    ``weight`` / ``x0`` / types / ``return_info`` as ``tv_superres`` (``energy`` and ``change`` per group, of the leading shape).  One
+    launch for the whole batch, one workgroup per group (``inr_tvj_solve2d``).  There is no CPU fallback."""
+    who = "tv_superres_joint"
+    f0, f1, k = _block_kernel(who, kernel, factors)
+    lam, huber = float(lam), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or n_iter < 0:
+        raise ValueError(f"{who}: n_iter must be an integer >= 0 (got {n_iter!r})")
+    if coupling not in ("joint", "none"):
+        raise ValueError(f"{who}: coupling must be 'joint' or 'none' (got {coupling!r})")
+    as_numpy = _fourier_input(who, lr)
+    if lr.ndim < 3:
+        raise ValueError(f"{who} needs at least 3-D input [..., C, h, w]")
+    C, h, w, lead = int(lr.shape[-3]), int(lr.shape[-2]), int(lr.shape[-1]), tuple(lr.shape[:-3])
+    if not 1 <= C <= ops.TVJ_MAX_CHANNELS:
+        raise ValueError(f"{who}: channels are 1 .. {ops.TVJ_MAX_CHANNELS} per group (got {C})")
+    _hr_sides(who, h * f0, w * f1, f0, f1)
+    mu = None
+    if channel_weights is not None:
+        mu = np.asarray(channel_weights, np.float64).reshape(-1)
+        if mu.shape != (C,) or not (np.isfinite(mu).all() and (mu >= 0).all() and (mu <= 1).all()):
+            raise ValueError(f"{who}: channel_weights are {C} finite values within [0, 1] (got {mu.tolist()}); larger weights are a "
+                             f"rescaled lam and huber")
+        mu = mu.tolist()
+    extra = {}
+    for name, value, shape in (("weight", weight, (C, h, w)), ("x0", x0, (C, h * f0, w * f1))):
+        if value is None:
+            extra[name] = None
+            continue
+        if isinstance(value, np.ndarray) != as_numpy:
+            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
+        _fourier_input(who, value)
+        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
+            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
+        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
+            raise ValueError(f"{who}: weight must be finite and >= 0")
+        extra[name] = value
+
+    def groups(value):
+        t = torch.from_numpy(np.ascontiguousarray(value, dtype=np.float64)).to(ops.require_gpu()) if as_numpy else value
+        return t.reshape(-1, *t.shape[-3:]).contiguous()
+
+    y = groups(lr)
+    extra = {name: None if value is None else groups(value) for name, value in extra.items()}
+    out, energy, change = ops.tvj_solve(y, (f0, f1), k, mu, lam, huber, coupling, int(n_iter), extra["weight"], extra["x0"])
+    out = out.reshape(*lead, C, h * f0, w * f1)
+    energy, change = energy.reshape(lead), change.reshape(lead)
+    if as_numpy:
+        out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
+    return (out, {"energy": energy, "change": change}) if return_info else out
+
+
+TVMF_DEFAULT_LAMBDA,TVMF_DEFAULT_HUBER, TVMF_DEFAULT_ITERS = 0.01, 0.03, 300  # the sweep of DESIGN.md 4n (8 frames, noise 0.02)
 
 
 def _frame_count(who, K):

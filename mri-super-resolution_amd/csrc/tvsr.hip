@@ -32,43 +32,10 @@
 // energy: the objective at the returned x (the fp64 x, before the fp32 entry rounds it); every thread adds its LR blocks and then its
 // HR pixels in ascending order, wave_sum's butterfly adds the lanes, thread 0 adds the 16 waves in ascending order: no float atomics,
 // the same bits on every call and at every position in a batch.  change: max |x' - x| of the last iteration (0 for n_iter = 0).
-#include <cmath>
-
-#include "internal.h"
+#include "tv_block.h"   // the shape, the block kernel and their checks, shared with tvj.hip
 
 namespace inr {
 namespace {
-
-constexpr int TV_THREADS = 1024;
-constexpr int TV_WAVES = TV_THREADS / 64;
-constexpr int TV_MAX_FACTOR = INR_TVSR_MAX_FACTOR;
-constexpr int TV_MAX_SIDE = INR_TVSR_MAX_SIDE;
-constexpr int TV_MAX_GRID = 1 << 16;
-
-// the block kernel, by value in the kernel arguments
-struct TvBlock {
-    double k[TV_MAX_FACTOR * TV_MAX_FACTOR];   // [f0][f1]
-    double k2;                                  // sum k^2
-};
-
-struct TvShape {
-    int H, W, h, w, f0, f1;
-};
-
-__device__ __forceinline__ double tv_huber(double t, double alpha) {
-    if (alpha == 0.0) return t;
-    return t <= alpha ? t * t / (2.0 * alpha) : t - alpha / 2.0;
-}
-
-// (A x) of LR block (bi, bj) of one image: the terms in ascending (a, b)
-__device__ __forceinline__ double tv_block_sum(const double* x, const double* ks, const TvShape& s, int bi, int bj) {
-    double acc = 0.0;
-    for (int a = 0; a < s.f0; ++a) {
-        const double* row = x + (size_t)(bi * s.f0 + a) * s.W + bj * s.f1;
-        for (int b = 0; b < s.f1; ++b) acc += ks[a * s.f1 + b] * row[b];
-    }
-    return acc;
-}
 
 template <typename T>
 __global__ void __launch_bounds__(TV_THREADS) tv_solve_kernel(T* out, double* energy, double* change, const T* y, const T* weight,
@@ -220,36 +187,6 @@ __global__ void __launch_bounds__(256) tv_adjoint_kernel(double* __restrict__ ou
         const int bi = i / s.f0, bj = j / s.f1;
         out[t] = ks[(i - bi * s.f0) * s.f1 + (j - bj * s.f1)] * in[img * s.h * s.w + (long long)bi * s.w + bj];
     }
-}
-
-// the HR sizes and the block factors of one call
-int tv_shape_check(const char* who, int n_images, int H, int W, int f0, int f1, TvShape* s) {
-    INR_REQUIRE(n_images >= 0, INR_E_INVALID, "%s: bad sizes (n_images = %d)", who, n_images);
-    INR_REQUIRE(f0 >= 1 && f0 <= TV_MAX_FACTOR && f1 >= 1 && f1 <= TV_MAX_FACTOR, INR_E_INVALID,
-                "%s: block factors are 1 .. %d per axis (got %d x %d)", who, TV_MAX_FACTOR, f0, f1);
-    INR_REQUIRE(H >= 1 && W >= 1 && H <= TV_MAX_SIDE && W <= TV_MAX_SIDE, INR_E_INVALID,
-                "%s: bad sizes (HR images of 1 .. %d samples per axis, got %d x %d)", who, TV_MAX_SIDE, H, W);
-    INR_REQUIRE(H % f0 == 0 && W % f1 == 0, INR_E_INVALID, "%s: the HR image %d x %d is no whole number of %d x %d blocks", who, H, W,
-                f0, f1);
-    *s = TvShape{H, W, H / f0, W / f1, f0, f1};
-    return 0;
-}
-
-// the caller's HOST kernel [f0][f1]: finite entries that sum to 1
-int tv_block_check(const char* who, const double* kernel, int f0, int f1, TvBlock* kb) {
-    INR_REQUIRE(kernel, INR_E_INVALID, "%s: null pointer (kernel)", who);
-    double sum = 0.0, k2 = 0.0;
-    for (int t = 0; t < TV_MAX_FACTOR * TV_MAX_FACTOR; ++t) kb->k[t] = 0.0;
-    for (int t = 0; t < f0 * f1; ++t) {
-        INR_REQUIRE(std::isfinite(kernel[t]), INR_E_INVALID, "%s: the block kernel must be finite (entry %d is %g)", who, t, kernel[t]);
-        kb->k[t] = kernel[t];
-        sum += kernel[t];
-        k2 += kernel[t] * kernel[t];
-    }
-    INR_REQUIRE(std::isfinite(sum) && std::fabs(sum - 1.0) <= 1e-9, INR_E_INVALID, "%s: the block kernel must sum to 1 (got %.17g)", who,
-                sum);
-    kb->k2 = k2;
-    return 0;
 }
 
 unsigned tv_grid(long long work) {

@@ -1318,3 +1318,103 @@ def acquisition_model_study(slices, model="kspace", factor=None, lr_side=None, f
     consistency = metrics.psnr(f32(y), f32(baselines.operator_apply(images["tv_operator"], pair)), 1.0, per_image=True).cpu().numpy()
     return {"images": images, "hr": hr, "lr": y, "operators": pair, "methods": tuple(images), "psnr": psnr, "ssim": ssim,
             "consistency": consistency, "info": info}
+
+
+# ---- the joint b-value study: one prior over the b-values of a slice against one per image ----------------------------
+JOINT_METHODS = ("replicate", "tv", "tv_joint")
+SYNTHETIC_B = (0.0, 150.0, 1000.0, 1500.0)
+
+
+def check_joint_bvalues(side=50, n_b=4, factor=2, kernel="mean", noise=0.02, tv_lambda=3e-3, tv_joint_lambda=0.048, tv_huber=0.01,
+                        tv_iters=300, weights="equal"):
+    """What ``joint_bvalue_study`` cannot serve, by name; touches neither the input nor the device.  Returns the LR side."""
+    who = "joint_bvalue_study"
+    if isinstance(side, bool) or int(side) != side or not 7 <= side <= ops.TVSR_MAX_SIDE:
+        raise ValueError(f"{who}: the HR side is 7 .. {ops.TVSR_MAX_SIDE} pixels (got {side!r})")
+    if isinstance(n_b, bool) or int(n_b) != n_b or not 2 <= n_b <= ops.TVJ_MAX_CHANNELS:
+        raise ValueError(f"{who}: a group is 2 .. {ops.TVJ_MAX_CHANNELS} b-values (got {n_b!r})")
+    if isinstance(factor, bool) or int(factor) != factor or not 1 <= factor <= ops.TVSR_MAX_FACTOR or side % int(factor) or \
+            side // int(factor) < 7:
+        raise ValueError(f"{who}: factor is 1 .. {ops.TVSR_MAX_FACTOR}, divides the HR side {side} and leaves >= 7 LR pixels (got {factor!r})")
+    if kernel not in ("mean", "decimate"):
+        raise ValueError(f"{who}: kernel must be 'mean' or 'decimate' (got {kernel!r})")
+    if not 0.0 <= float(noise) < float("inf"):
+        raise ValueError(f"{who}: noise must be finite and >= 0 (got {noise!r})")
+    for name, value in (("tv_lambda", tv_lambda), ("tv_joint_lambda", tv_joint_lambda), ("tv_huber", tv_huber)):
+        if not 0.0 <= float(value) < float("inf"):
+            raise ValueError(f"{who}: {name} must be finite and >= 0 (got {value!r})")
+    if int(tv_iters) != tv_iters or not 1 <= tv_iters <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: tv_iters must be 1 .. 100,000 (got {tv_iters!r})")
+    if weights not in ("equal", "sqrt_signal"):
+        raise ValueError(f"{who}: weights must be 'equal' or 'sqrt_signal' (got {weights!r})")
+    return int(side) // int(factor)
+
+
+def synthetic_decay(slices, bvalues=SYNTHETIC_B):
+    """``slices`` [Z, R, R] in [0, 1] -> [Z, B, R, R]: a mono-exponential decay whose ADC is high where the in-plane smoothed image
+    (Gaussian, sigma 1) is dark, ``0.6e-3 + 1.8e-3 (1 - smooth / max)``: the study case of DESIGN.md 4q."""
+    from scipy.ndimage import gaussian_filter
+    roi = np.asarray(slices, np.float64)
+    adc = 0.6e-3 + 1.8e-3 * (1 - np.clip(gaussian_filter(roi, (0, 1, 1)) / roi.max(), 0, 1))
+    b = np.asarray(bvalues, np.float64)
+    return roi[:, None] * np.exp(-b[None, :, None, None] * adc[:, None])
+
+
+def loglinear_adc(x, bvalues):
+    """ADC [..., H, W] of the device stack ``x`` [..., B, H, W]: minus the least-squares slope of log(max(x, 1e-3)) over b, fp64."""
+    b = torch.as_tensor(np.asarray(bvalues, np.float64), device=x.device)
+    bc = (b - b.mean())[:, None, None]
+    return -(bc * torch.log(x.double().clamp_min(1e-3))).sum(dim=-3) / (bc * bc).sum()
+
+
+def joint_bvalue_study(hr, bvalues, factor=2, kernel="mean", noise=0.02, seed=0, tv_lambda=None, tv_joint_lambda=None, tv_huber=None,
+                       tv_iters=None, weights="equal", slice_ids=None):
+    """``hr`` [Z, B, R, R] in [0, 1], the B b-values of Z slices: the LR stack [Z, B, m, m] is ``baselines.block_apply`` under ``kernel``
+    plus Gaussian noise of ``noise`` -- slice z (``slice_ids[i]`` where given, else i) draws its [B, m, m] from
+    ``np.random.default_rng(seed * 1000 + z)`` --, reconstructed on the device by ``replicate`` (block replication), ``tv``
+    (``baselines.tv_superres``, every image on its own, ``tv_lambda``: ``TV_DEFAULT_LAMBDA`` where None) and ``tv_joint``
+    (``baselines.tv_superres_joint``, B the channel axis, ``tv_joint_lambda`` and ``channel_weights(lr, weights)``); both share
+    ``tv_huber`` and ``tv_iters`` (the ``TVJ_DEFAULT_*`` where None).  Returns ``{"images", "hr", "lr", "methods", "psnr", "ssim"``
+    [Z, B] per method (data range 1), ``"psnr_b"`` [B] and ``"psnr_all"`` per method, ``"adc"`` [Z, R, R] per method and of ``hr``
+    (``loglinear_adc``), ``"adc_rmse"`` per method inside ``b_min image > 0.25 max``, ``"mask"``, ``"channel_weights"``, ``"info"}``."""
+    from . import baselines
+
+    lam = baselines.TV_DEFAULT_LAMBDA if tv_lambda is None else tv_lambda
+    lam_j = baselines.TVJ_DEFAULT_LAMBDA if tv_joint_lambda is None else tv_joint_lambda
+    huber = baselines.TVJ_DEFAULT_HUBER if tv_huber is None else tv_huber
+    iters = baselines.TVJ_DEFAULT_ITERS if tv_iters is None else tv_iters
+    vol = np.asarray(hr, np.float64)
+    if vol.ndim != 4 or vol.shape[2] != vol.shape[3]:
+        raise ValueError(f"joint_bvalue_study: hr is [Z, B, R, R] (got {vol.shape})")
+    Z, B, R = vol.shape[0], vol.shape[1], vol.shape[2]
+    b = np.asarray(bvalues, np.float64).reshape(-1)
+    if b.size != B or np.ptp(b) == 0 or not np.isfinite(b).all():
+        raise ValueError(f"joint_bvalue_study: bvalues are {B} finite values that are not all equal (got {b.tolist()})")
+    m = check_joint_bvalues(R, B, factor, kernel, noise, lam, lam_j, huber, iters, weights)
+    ids = list(range(Z)) if slice_ids is None else [int(v) for v in slice_ids]
+    if len(ids) != Z or (Z and min(ids) < 0):
+        raise ValueError(f"joint_bvalue_study: slice_ids are one index >= 0 per slice (got {slice_ids!r} for {Z} slices)")
+    f = int(factor)
+    eta = np.stack([noise * np.random.default_rng(int(seed) * 1000 + z).standard_normal((B, m, m)) for z in ids])
+    dev = ops.require_gpu()
+    hr_d = torch.from_numpy(vol).to(dev)
+    y = baselines.block_apply(hr_d, (f, f), kernel) + torch.from_numpy(eta).to(dev)
+    mu = baselines.channel_weights(y, weights)
+    images, info = {"replicate": y.repeat_interleave(f, dim=-2).repeat_interleave(f, dim=-1).contiguous()}, {}
+    images["tv"], res = baselines.tv_superres(y, (f, f), kernel, lam, huber, int(iters), return_info=True)
+    info["tv"] = {k: v.cpu().numpy() for k, v in res.items()}
+    images["tv_joint"], res = baselines.tv_superres_joint(y, (f, f), kernel, lam_j, huber, int(iters), mu, return_info=True)
+    info["tv_joint"] = {k: v.cpu().numpy() for k, v in res.items()}
+    f32 = lambda t: t.float().contiguous()
+    per_b = lambda t: f32(t.transpose(0, 1)).reshape(B, Z * R, R)
+    psnr = {name: metrics.psnr(f32(hr_d), f32(v), 1.0, per_image=True).cpu().numpy().reshape(Z, B) for name, v in images.items()}
+    ssim = {name: metrics.ssim(f32(hr_d), f32(v), 1.0).cpu().numpy().reshape(Z, B) for name, v in images.items()}
+    psnr_b = {name: metrics.psnr(per_b(hr_d), per_b(v), 1.0, per_image=True).cpu().numpy() for name, v in images.items()}
+    psnr_all = {name: float(metrics.psnr(f32(hr_d), f32(v), 1.0)) for name, v in images.items()}
+    b0 = hr_d[:, int(np.argmin(b))]
+    mask = b0 > 0.25 * b0.max()
+    adc = {name: loglinear_adc(v, b) for name, v in images.items()}
+    adc["hr"] = loglinear_adc(hr_d, b)
+    adc_rmse = {name: float(((adc[name] - adc["hr"])[mask] ** 2).mean().sqrt()) for name in images}
+    return {"images": images, "hr": hr_d, "lr": y, "methods": tuple(images), "psnr": psnr, "ssim": ssim, "psnr_b": psnr_b,
+            "psnr_all": psnr_all, "adc": adc, "adc_rmse": adc_rmse, "mask": mask, "channel_weights": mu, "info": info}

@@ -790,6 +790,75 @@ def tvsr_solve(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_ite
     return out, energy, change
 
 
+# ---- the same with one prior over the channels of a group (include/inrhip.h) -------------------------------------------
+TVJ_MAX_CHANNELS = _lib.INR_TVJ_MAX_CHANNELS
+_TVJ_COUPLING = {"none": 0, "joint": 1}
+
+
+def _chk_groups(t, name, dtypes, shape=None) -> torch.Tensor:
+    """A contiguous device batch [n, channels, rows, columns] of one of ``dtypes``."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
+    if t.dtype not in dtypes:
+        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
+    if t.dim() != 4 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous [n, channels, rows, columns] batch (got {tuple(t.shape)})")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def tvj_workspace_doubles(n: int, channels: int, H: int, W: int) -> int:
+    """``inr_tvj_workspace_doubles``; 0 for sizes ``inr_tvj_solve2d`` refuses."""
+    return int(lib().inr_tvj_workspace_doubles(int(n), int(channels), int(H), int(W)))
+
+
+def tvj_solve(y: torch.Tensor, factors, kernel, channel_weights, lam: float, alpha: float, coupling, n_iter: int, weight=None, x0=None,
+              workspace=None):
+    """``inr_tvj_solve2d`` / ``_f32`` by the dtype of ``y`` [n, C, h, w]: returns (x [n, C, f0 h, f1 w] of that dtype, energy [n]
+    float64, change [n] float64).  ``channel_weights``: C host values in [0, 1] or None (all 1); ``coupling``: 'joint' or 'none';
+    ``weight`` [n, C, h, w] and ``x0`` [n, C, f0 h, f1 w] share the dtype; ``workspace``: a float64 tensor."""
+    _chk_groups(y, "y", (torch.float32, torch.float64))
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, ch, h, w = y.shape
+    H, W = h * f0, w * f1
+    if not 1 <= ch <= TVJ_MAX_CHANNELS:
+        raise ValueError(f"tvj_solve: channels are 1 .. {TVJ_MAX_CHANNELS} per group (got {ch})")
+    _hr_shape("tvj_solve", H, W, f0, f1)
+    if coupling not in _TVJ_COUPLING:
+        raise ValueError(f"tvj_solve: coupling must be 'joint' or 'none' (got {coupling!r})")
+    mu = None
+    if channel_weights is not None:
+        vals = [float(v) for v in channel_weights]
+        if len(vals) != ch or not all(0.0 <= v <= 1.0 for v in vals):
+            raise ValueError(f"tvj_solve: channel_weights are {ch} finite values within [0, 1] (got {vals!r})")
+        mu = (C.c_double * ch)(*vals)
+    if weight is not None:
+        _chk_groups(weight, "weight", (y.dtype,), y.shape)
+    if x0 is not None:
+        _chk_groups(x0, "x0", (y.dtype,), (n, ch, H, W))
+    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or n_iter < 0:
+        raise ValueError(f"tvj_solve: lam and alpha must be finite and >= 0, n_iter >= 0 (got {lam!r}, {alpha!r}, {n_iter})")
+    out = torch.empty((n, ch, H, W), dtype=y.dtype, device=y.device)
+    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
+    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    if n == 0:
+        return out, energy, change
+    need = tvj_workspace_doubles(n, ch, H, W)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
+    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
+        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
+    entry = "inr_tvj_solve2d" if y.dtype == torch.float64 else "inr_tvj_solve2d_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, ch, H, W,
+                                f0, f1, k, mu, lam, alpha, _TVJ_COUPLING[coupling], n_iter, workspace.data_ptr(), workspace.numel(),
+                                _stream()), entry)
+    return out, energy, change
+
+
 # ---- the same on volumes: slice profile, 3-D prior, many workgroups per volume (include/inrhip.h, DESIGN.md 4m) ----------------------
 TVSR3D_MAX_ITER = _lib.INR_TVSR3D_MAX_ITER
 

@@ -51,6 +51,13 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     ``metrics.json`` gains ``psnr_tv_db``, ``ssim_tv_mean`` and ``tv_consistency_psnr_db`` (``A x`` against the LR data, data range 1);
     with ``--adc``, ``adc.mat`` gains ``adc_tv`` on the grid of the HR ROI ([R, R, Z]).  It does not touch the fit, so it goes with
     ``--zerofill`` and ``--model wire``.  Refused before the input is loaded: an odd ROI side, L < 0, A < 0, N outside 1 .. 100,000.
+  * ``--tv_joint [--tv_joint_lambda LJ --tv_joint_weights equal|sqrt_signal]`` (with ``--tv_baseline``): the same reconstruction with
+    ONE prior over the b-values of a slice -- the [Z, B, R/2, R/2] LR stack with B as the channel axis,
+    ``baselines.tv_superres_joint(LR, (2, 2), kernel, LJ, A, N, channel_weights)``, one workgroup per slice (``inr_tvj_solve2d_f32``,
+    DESIGN.md 4q), with ``--tv_huber`` and ``--tv_iters``.  ``ssim_scores_tv_joint.csv`` (``Pt_id, b-value, slice, SSIM-tv-joint,
+    SSIM-SR``); ``metrics.json`` gains ``psnr_tv_joint_db``, ``ssim_tv_joint_mean`` and ``tv_joint_consistency_psnr_db``; with ``--adc``,
+    ``adc.mat`` gains ``adc_tv_joint``.  Refused: without ``--tv_baseline``, LJ < 0 (before the input is loaded), an input with fewer
+    than 2 b-values or more than 16 (before the fit).
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
@@ -116,6 +123,14 @@ def build_parser():
     p.add_argument("--tv_huber", type=float, default=baselines.TV_DEFAULT_HUBER,
                    help="--tv_baseline: Huber threshold on the gradient magnitude; 0 = plain isotropic TV")
     p.add_argument("--tv_iters", type=int, default=baselines.TV_DEFAULT_ITERS, help="--tv_baseline: Chambolle-Pock iterations, 1 .. 100,000")
+    p.add_argument("--tv_joint", action="store_true",
+                   help="--tv_baseline: also score the channel-coupled reconstruction, one prior over the b-values of a slice (needs >= 2 "
+                        "b-values): ssim_scores_tv_joint.csv, psnr_tv_joint_db / ssim_tv_joint_mean / tv_joint_consistency_psnr_db in "
+                        "metrics.json, adc_tv_joint with --adc; uses --tv_huber and --tv_iters")
+    p.add_argument("--tv_joint_lambda", type=float, default=baselines.TVJ_DEFAULT_LAMBDA,
+                   help="--tv_joint: weight of the coupled prior (default from the sweep of DESIGN.md 4q)")
+    p.add_argument("--tv_joint_weights", choices=("equal", "sqrt_signal"), default="equal",
+                   help="--tv_joint: the channel weights of the coupled norm (baselines.channel_weights)")
     p.add_argument("--derivative_maps", action="store_true",
                    help="also write derivatives.mat: gradient magnitude and Laplacian of the fitted network on recon's grid, "
                         "along the spatial axes (nn_mri.py:205-221)")
@@ -269,6 +284,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     ssim_sr = metrics.ssim_reference_protocol(safe(hs), safe(ss)).cpu().numpy()
     zf = _zerofill(hs, 2, args.zerofill_apodize) if getattr(args, "zerofill", False) else None
     tv = _tv_baseline(ls, args, average) if getattr(args, "tv_baseline", False) else None
+    tvj = _tv_joint(ls, args, average) if getattr(args, "tv_joint", False) else None
     with reports.SsimCsv(os.path.join(out_dir, "ssim_scores.csv")) as csv:
         for _slice in range(nz):
             for b in range(nb):
@@ -301,6 +317,15 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         summary["psnr_tv_db"] = float(metrics.psnr(hs, tv, 1.0))
         summary["ssim_tv_mean"] = float(ssim_tv[okn].mean())
         summary["tv_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(tv, (2, 2), _tv_kernel(average)), 1.0))
+    if tvj is not None:
+        ssim_tvj = metrics.ssim_reference_protocol(safe(hs), safe(tvj)).cpu().numpy()
+        with reports.SsimCsv(os.path.join(out_dir, "ssim_scores_tv_joint.csv"), reports.SSIM_TV_JOINT_HEADER) as csv:
+            for _slice in range(nz):
+                for b in range(nb):
+                    csv.row(pt_id, bvalues[b] if b < len(bvalues) else b, _slice, float(ssim_tvj[_slice, b]), float(ssim_sr[_slice, b]))
+        summary["psnr_tv_joint_db"] = float(metrics.psnr(hs, tvj, 1.0))
+        summary["ssim_tv_joint_mean"] = float(ssim_tvj[okn].mean())
+        summary["tv_joint_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(tvj, (2, 2), _tv_kernel(average)), 1.0))
     if average:
         pred = inr.footprint_forward(INR, coords, B, footprint)
         summary.update({"lr_model": "average", "footprint": args.footprint, "footprint_samples": footprint.count,
@@ -312,7 +337,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
         matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale,
-                                                                     args.zerofill_apodize if zf is not None else None, ls, tv))
+                                                                     args.zerofill_apodize if zf is not None else None, ls, tv, tvj))
     if args.derivative_maps:
         matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape))
     if args.wire_derivative_maps:
@@ -398,7 +423,7 @@ def _check_wire(args):
 
 
 def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
-    """Refuses --transverse_length / --adc on an input that cannot give them, before the fit starts."""
+    """Refuses --transverse_length / --adc / --tv_joint on an input that cannot give them, before the fit starts."""
     nz, nb = mean_img.shape[2], mean_img.shape[3]
     if args.transverse_length < 0:
         raise ValueError(f"--transverse_length must be >= 0 (got {args.transverse_length})")
@@ -411,6 +436,9 @@ def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
         if (args.roi_end - args.roi_start) % 2:
             raise ValueError(f"--zerofill re-samples every second pixel of the ROI back onto its grid with a mirrored boundary, which "
                              f"needs an even ROI side (got {args.roi_end - args.roi_start})")
+    if getattr(args, "tv_joint", False) and not 2 <= nb <= baselines.ops.TVJ_MAX_CHANNELS:
+        raise ValueError(f"--tv_joint couples the b-values of a slice and needs 2 .. {baselines.ops.TVJ_MAX_CHANNELS} of them; {path} "
+                         f"has {nb}")
     if args.adc:
         if nb < 2:
             raise ValueError(f"--adc needs at least 2 b-values; {path} has {nb}")
@@ -453,8 +481,22 @@ def _tv_baseline(ls, args, average):
     return baselines.tv_superres(ls, (2, 2), _tv_kernel(average), args.tv_lambda, args.tv_huber, args.tv_iters)
 
 
+def _tv_joint(ls, args, average):
+    """``--tv_joint``: the [Z, B, R/2, R/2] LR stack ``ls`` -> the [Z, B, R, R] reconstruction with one prior over the B channels of a
+    slice; the weights of ``sqrt_signal`` are one host read of B means, before the solve."""
+    mu = baselines.channel_weights(ls, args.tv_joint_weights)
+    return baselines.tv_superres_joint(ls, (2, 2), _tv_kernel(average), args.tv_joint_lambda, args.tv_huber, args.tv_iters, mu)
+
+
 def _check_tv(args, fit=None):
-    """``--tv_baseline``: what it cannot serve, before the input is loaded and anything touches the device."""
+    """``--tv_baseline`` / ``--tv_joint``: what they cannot serve, before the input is loaded and anything touches the device."""
+    if getattr(args, "tv_joint", False):
+        if not getattr(args, "tv_baseline", False):
+            raise ValueError("--tv_joint is scored beside the per-channel reconstruction: pass --tv_baseline with it")
+        if not 0.0 <= args.tv_joint_lambda < float("inf"):
+            raise ValueError(f"--tv_joint_lambda must be finite and >= 0 (got {args.tv_joint_lambda})")
+        if args.tv_joint_weights not in ("equal", "sqrt_signal"):
+            raise ValueError(f"--tv_joint_weights must be equal or sqrt_signal (got {args.tv_joint_weights})")
     if not getattr(args, "tv_baseline", False):
         return
     if (args.roi_end - args.roi_start) % 2:
@@ -471,12 +513,12 @@ def _check_tv(args, fit=None):
                          "(changes_lr_data)")
 
 
-def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, tv=None):
+def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, tv=None, tvj=None):
     """superresDWI.py:189-206 for all slices in one batch: every b-image times maxes[b, 1], then calculate_ADC per pixel, of
     the x2 SR volume, the x4 spline of the LR ROI and the x2 spline of the HR ROI.  ``hs`` is the HR ROI as [Z, B, R, R].
     ``zerofill_apodize`` (not None): also ``adc_zerofill``, the x4 zero-fill of the LR ROI, on the grid of ``adc_spline``.
     ``ls``: the LR ROI as [Z, B, R/2, R/2] (default: every second pixel of ``hs``; ``--lr_model average``: the block means).
-    ``tv`` (not None): also ``adc_tv`` of the [Z, B, R, R] TV reconstruction, on the grid of the HR ROI."""
+    ``tv`` / ``tvj`` (not None): also ``adc_tv`` / ``adc_tv_joint`` of the [Z, B, R, R] TV reconstructions, on the grid of the HR ROI."""
     scale = torch.as_tensor(np.asarray(signal_scale, np.float32), device=recon.device)
     to_xyzb = lambda t: t.permute(2, 3, 0, 1).contiguous()                       # [Z, B, 2R, 2R] -> [2R, 2R, Z, B]
     stacks = {"adc_sr": recon,
@@ -486,7 +528,9 @@ def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, 
         stacks["adc_zerofill"] = to_xyzb(_zerofill(hs, 4, zerofill_apodize))
     if tv is not None:
         stacks["adc_tv"] = to_xyzb(tv)
-    out = {k: metrics.calculate_ADC_device(bvalues, (v * scale).contiguous()).cpu().numpy() for k, v in stacks.items()}
+    if tvj is not None:
+        stacks["adc_tv_joint"] = to_xyzb(tvj)
+    out ={k: metrics.calculate_ADC_device(bvalues, (v * scale).contiguous()).cpu().numpy() for k, v in stacks.items()}
     out["b"] = np.asarray(bvalues, np.float64)
     return out
 

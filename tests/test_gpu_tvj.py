@@ -1,0 +1,389 @@
+"""GPU: the channel-coupled TV / Huber solver of csrc/tvj.hip against its float64 restatement (tests/tvj_common.py), bit for bit against
+the per-image solver where the two problems coincide, across a batch, against properties that do not depend on the restatement, on
+the study case, and through ``superresDWI --tv_joint`` and ``scripts/joint_bvalues``.
+
+Bounds are those of tests/test_gpu_tvsr.py, by the same derivation: the iteration is non-expansive, about ten roundings of 1.1e-16
+per pixel, channel and iteration give 1e-12 after 1,000 iterations on data in [0, 1], and 1e-10 absolute on the image leaves two
+orders of margin (the sum over at most 16 channels adds 15 roundings to one norm per pixel and iteration: the same order).  ``change``
+is the difference of two images within the bound: 2e-10.  ``energy`` is a sum of at most C (H W + h w) non-negative terms of a few
+roundings each: 1e-12 relative against the restated objective at the returned image.  Every test prints what it measured before it
+asserts."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import tvj_common as J
+from tests import tvsr_common as T
+from mri_super_resolution_amd import baselines, drivers, matio, metrics, ops, reports
+from mri_super_resolution_amd.scripts import joint_bvalues as jb_script
+from mri_super_resolution_amd.scripts import superresDWI as dwi_script
+
+pytestmark = pytest.mark.gpu
+
+SOLVER_BOUND = 1e-10
+ENERGY_BOUND = 1e-12
+
+
+def _dev(a, dtype=torch.float64):
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda", dtype)
+
+
+def _compare(name, y, f, kernel, lam, alpha, n_iter, mu=None, coupling="joint", w=None, x0=None):
+    got, info = baselines.tv_superres_joint(y, f, kernel, lam, alpha, n_iter, mu, coupling, weight=w, x0=x0, return_info=True)
+    want, _, change = J.solve_joint(y, f, kernel, lam, alpha, n_iter, mu, coupling, w=w, x0=x0, return_info=True)
+    at_image = J.energy_joint(got, np.where(w == 0, 0.0, y) if w is not None else y, T.block_kernel(kernel, f), lam, alpha, w, mu, coupling)
+    err = float(np.abs(got - want).max())
+    e_rel = float(np.abs(info["energy"] - at_image).max() / np.abs(at_image).max()) if np.abs(at_image).max() > 0 else \
+        float(np.abs(info["energy"]).max())
+    c_err = float(np.abs(info["change"] - change).max())
+    print(f"{name}, {coupling}, {n_iter} iterations: max|got - restated| = {err:.3e} (bound {SOLVER_BOUND:.0e}), energy against the "
+          f"restated objective at the returned image {e_rel:.2e} (bound {ENERGY_BOUND:.0e}), |change - restated| {c_err:.2e} (change "
+          f"{float(change.max()):.2e})")
+    assert got.dtype == np.float64 and got.shape == want.shape
+    assert err <= SOLVER_BOUND
+    assert c_err <= 2 * SOLVER_BOUND            # the difference of two images that are each within the bound
+    assert e_rel <= ENERGY_BOUND
+    return got, info
+
+
+# ---- against the restatement ------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("coupling", ("joint", "none"))
+@pytest.mark.parametrize("n_iter", (1, 2, 300))
+def test_solver_matches_the_restatement_on_the_weighted_three_channel_case(n_iter, coupling):
+    _, y, w = J.case_data()
+    _compare("3 x 6x10 (3, 2) mean, weighted Huber, mu (1, .5, .25)", y, J.CASE_FACTORS, "mean", J.CASE_LAM, J.CASE_ALPHA, n_iter, J.CASE_MU,
+             coupling, w=w)
+
+
+def test_solver_matches_the_restatement_on_sixteen_channels_and_on_a_zero_weight():
+    rng = np.random.default_rng(16)
+    hr = rng.random((2, 1, 6, 10)) * np.linspace(1.0, 0.1, 16)[None, :, None, None] + 0.05 * rng.random((2, 16, 6, 10))
+    y = T.apply_A(hr, T.block_kernel("mean", (3, 2)))
+    mu = np.linspace(0.2, 1.0, 16)
+    for coupling in ("joint", "none"):
+        _compare("16 x 6x10 (3, 2)", y, (3, 2), "mean", 0.05, 0.02, 60, mu, coupling)
+    _compare("16 x 6x10 (3, 2), plain TV, mu = 1", y, (3, 2), "mean", 0.05, 0.0, 60)
+    # a channel with mu = 0 leaves the prior: its p stays 0 and it solves its data term alone
+    _, y3, w3 = J.case_data()
+    for coupling in ("joint", "none"):
+        got, _ = _compare("3 x 6x10, mu (1, 0, .5)", y3, J.CASE_FACTORS, "mean", J.CASE_LAM, J.CASE_ALPHA, 40, (1.0, 0.0, 0.5), coupling, w=w3)
+        alone = baselines.tv_superres(y3[:, 1], J.CASE_FACTORS, "mean", 0.0, 0.0, 40, weight=w3[:, 1])
+        assert np.array_equal(got[:, 1], alone)
+
+
+@pytest.mark.parametrize("H,W,f", ((7, 1024, (7, 1)), (1024, 3, (1, 3))), ids=("7x1024by7x1", "1024x3by1x3"))
+def test_solver_matches_the_restatement_on_ragged_strides_and_a_one_block_axis(H, W, f):
+    """C = 2: H W is no multiple of the 1,024 threads, C h w neither, and one axis is a single block or a single pixel per block."""
+    rng = np.random.default_rng(H)
+    hr = rng.random((2, 2, H, W))
+    k = rng.random(f) + 0.1
+    for name, kernel in (("mean", "mean"), ("random", k / k.sum())):
+        y = T.apply_A(hr, T.block_kernel(kernel, f))
+        w = rng.random(y.shape) * (rng.random(y.shape) > 0.1)
+        _compare(f"2 x {H}x{W} {f} {name}", y, f, kernel, 0.02, 0.05, 40, (1.0, 0.7), "joint", w=w, x0=rng.random(hr.shape))
+    _compare(f"2 x {H}x{W} {f} decimate, plain TV", T.apply_A(hr, T.block_kernel("decimate", f)), f, "decimate", 0.02, 0.0, 40)
+
+
+def test_properties_at_the_edges_of_the_parameters():
+    rng = np.random.default_rng(5)
+    hr, y, w = J.case_data()
+    f = J.CASE_FACTORS
+    # lambda = 0: the replication start satisfies the data and stays, exactly
+    for n_iter in (1, 50):
+        x, info = baselines.tv_superres_joint(y, f, "mean", 0.0, 0.0, n_iter, return_info=True)
+        print(f"lambda = 0, {n_iter} iterations: x == x0 {np.array_equal(x, T.replicate(y, f))}, energy {float(info['energy'][0]):.2e}, "
+              f"change {float(info['change'][0]):.2e}")
+        assert np.array_equal(x, T.replicate(y, f))
+    # n_iter = 0 returns x0: the given one, or the block replication
+    x0 = rng.random(hr.shape)
+    x, info = baselines.tv_superres_joint(y, f, "mean", 0.05, 0.02, 0, x0=x0, return_info=True)
+    assert np.array_equal(x, x0) and float(info["change"][0]) == 0.0
+    assert np.array_equal(baselines.tv_superres_joint(y, f, "mean", 0.05, 0.02, 0), T.replicate(y, f))
+    # a missing datum (w = 0) is never read: whatever y holds there -- 1e3 or NaN --, the same bits come out
+    start = T.replicate(y, f)
+    a, ia = baselines.tv_superres_joint(y, f, "mean", J.CASE_LAM, J.CASE_ALPHA, 30, J.CASE_MU, weight=w, x0=start, return_info=True)
+    for value in (1e3, float("nan")):
+        other = y.copy()
+        other[w == 0] = value
+        b, ib = baselines.tv_superres_joint(other, f, "mean", J.CASE_LAM, J.CASE_ALPHA, 30, J.CASE_MU, weight=w, x0=start, return_info=True)
+        same = np.array_equal(a, b) and np.array_equal(ia["energy"], ib["energy"]) and np.array_equal(ia["change"], ib["change"])
+        print(f"the w = 0 datum holds {value}: same bits {same}")
+        assert (w == 0).sum() == 1 and np.isfinite(b).all() and same
+
+
+# ---- bit for bit: what a wrong channel stride or summation order breaks -------------------------------------------------------------
+def test_one_channel_is_the_per_image_solver_bit_for_bit():
+    rng = np.random.default_rng(7)
+    hr = rng.random((5, 14, 9))
+    y = T.apply_A(hr, T.block_kernel("mean", (2, 3)))
+    w = rng.random(y.shape) * (rng.random(y.shape) > 0.1)
+    for alpha in (0.0, 0.05):
+        want, winfo = baselines.tv_superres(y, (2, 3), "mean", 0.02, alpha, 50, weight=w, return_info=True)
+        for coupling in ("joint", "none"):
+            got, info = baselines.tv_superres_joint(y[:, None], (2, 3), "mean", 0.02, alpha, 50, None, coupling, weight=w[:, None],
+                                                    return_info=True)
+            same = (np.array_equal(got[:, 0], want), np.array_equal(info["energy"], winfo["energy"]), np.array_equal(info["change"], winfo["change"]))
+            print(f"C = 1, alpha {alpha}, {coupling}: image, energy, change equal tv_superres: {same}")
+            assert all(same)
+
+
+def test_uncoupled_unit_weights_are_the_per_image_solver_of_every_channel_bit_for_bit():
+    _, y, w = J.case_data()
+    rng = np.random.default_rng(8)
+    y = np.concatenate([y, rng.random(y.shape)])                     # two groups
+    w = np.concatenate([w, w])
+    got, info = baselines.tv_superres_joint(y, J.CASE_FACTORS, "mean", J.CASE_LAM, J.CASE_ALPHA, 80, None, "none", weight=w, return_info=True)
+    want, winfo = baselines.tv_superres(y, J.CASE_FACTORS, "mean", J.CASE_LAM, J.CASE_ALPHA, 80, weight=w, return_info=True)
+    e_rel = float(np.abs(info["energy"] - winfo["energy"].sum(axis=1)).max() / winfo["energy"].sum(axis=1).max())
+    print(f"coupling none, mu = 1: images equal {np.array_equal(got, want)}; change equals the channel maximum "
+          f"{np.array_equal(info['change'], winfo['change'].max(axis=1))}; energy against the channel sum {e_rel:.2e} (bound 1e-12)")
+    assert np.array_equal(got, want)
+    assert np.array_equal(info["change"], winfo["change"].max(axis=1))
+    assert e_rel <= 1e-12
+    # and the coupled result is another one
+    assert not np.array_equal(baselines.tv_superres_joint(y, J.CASE_FACTORS, "mean", J.CASE_LAM, J.CASE_ALPHA, 80, weight=w), want)
+
+
+def test_fp32_is_the_fp64_result_rounded_once_and_types_come_back_as_given():
+    rng = np.random.default_rng(9)
+    hr, y, w = J.case_data()
+    y32, w32, x32 = _dev(y, torch.float32), _dev(w, torch.float32), _dev(rng.random(hr.shape), torch.float32)
+    for coupling in ("joint", "none"):
+        args = (J.CASE_FACTORS, "mean", J.CASE_LAM, J.CASE_ALPHA, 100, J.CASE_MU, coupling)
+        got, info = baselines.tv_superres_joint(y32, *args, weight=w32, x0=x32, return_info=True)
+        want, winfo = baselines.tv_superres_joint(y32.double(), *args, weight=w32.double(), x0=x32.double(), return_info=True)
+        same = torch.equal(got, want.float())
+        print(f"{coupling}: fp32 out == fp64 out rounded once: {same}; max|fp32 - fp64| = {float((got.double() - want).abs().max()):.2e}")
+        assert got.dtype == torch.float32 and want.dtype == torch.float64 and got.is_cuda and info["energy"].dtype == torch.float64
+        assert same
+        assert torch.equal(info["energy"], winfo["energy"]) and torch.equal(info["change"], winfo["change"])
+    # leading axes are a batch of groups and keep their shape
+    stack = _dev(rng.random((2, 3, 4, 4, 6)), torch.float32)
+    out, info = baselines.tv_superres_joint(stack, (2, 1), n_iter=5, return_info=True)
+    assert out.shape == (2, 3, 4, 8, 6) and info["energy"].shape == info["change"].shape == (2, 3)
+    assert isinstance(baselines.tv_superres_joint(rng.random((3, 4, 6)), (2, 2), n_iter=3), np.ndarray)
+    # sqrt_signal reads the channel means of a device stack once, on the host
+    mu = baselines.channel_weights(stack, "sqrt_signal")
+    m = stack.double().mean(dim=(0, 1, 3, 4)).cpu().numpy()
+    assert mu.dtype == np.float64 and np.array_equal(mu, np.sqrt(m.min() / m)) and mu.max() == 1.0
+
+
+# ---- a batch ------------------------------------------------------------------------------------------------------------------------------
+def test_a_batch_beyond_the_cu_count_equals_its_solitary_solves_bit_for_bit():
+    """300 different groups of 2 x 12 x 12: more workgroups than the 256 CUs, so some are queued behind others."""
+    rng = np.random.default_rng(11)
+    n, f = 300, (2, 3)
+    y = _dev(rng.random((n, 2, 6, 4)))
+    w = _dev(rng.random((n, 2, 6, 4)) * (rng.random((n, 2, 6, 4)) > 0.1))
+    args = (f, "mean", 0.02, 0.05, 25, (1.0, 0.6))
+    out, info = baselines.tv_superres_joint(y, *args, weight=w, return_info=True)
+    torch.cuda.synchronize()
+    differ = 0
+    for i in range(n):
+        one, one_info = baselines.tv_superres_joint(y[i:i + 1], *args, weight=w[i:i + 1], return_info=True)
+        differ += int(not (torch.equal(one[0], out[i]) and torch.equal(one_info["energy"][0], info["energy"][i])
+                           and torch.equal(one_info["change"][0], info["change"][i])))
+    again, again_info = baselines.tv_superres_joint(y, *args, weight=w, return_info=True)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        on_side, side_info = baselines.tv_superres_joint(y, *args, weight=w, return_info=True)
+    side.synchronize()
+    # a group's result does not depend on its position in the batch
+    perm = torch.from_numpy(rng.permutation(n)).cuda()
+    moved, moved_info = baselines.tv_superres_joint(y[perm].contiguous(), *args, weight=w[perm].contiguous(), return_info=True)
+    distinct = len({out[i].cpu().numpy().tobytes() for i in range(n)})
+    print(f"{n} groups of 2x12x12: {differ} differ from their solitary solve; second run equal {torch.equal(again, out)}; side stream equal "
+          f"{torch.equal(on_side, out)}; permuted batch equal {torch.equal(moved, out[perm])}; {distinct} distinct results")
+    assert out.shape == (n, 2, 12, 12) and distinct == n
+    assert differ == 0
+    assert torch.equal(again, out) and torch.equal(again_info["energy"], info["energy"]) and torch.equal(again_info["change"], info["change"])
+    assert torch.equal(on_side, out) and torch.equal(side_info["energy"], info["energy"])
+    assert torch.equal(moved, out[perm]) and torch.equal(moved_info["energy"], info["energy"][perm])
+
+
+# ---- independent of the restatement ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("C", (2, 4))
+def test_identical_channels_are_the_per_image_solver_at_scaled_parameters(C):
+    _, y1 = T.case_data()
+    y = np.repeat(y1[:, None], C, axis=1)
+    w = np.repeat(T.CASE_W[:, None], C, axis=1)
+    got = baselines.tv_superres_joint(y, T.CASE_FACTORS, "mean", T.CASE_LAM, T.CASE_ALPHA, 300, weight=w)
+    want = baselines.tv_superres(y1, T.CASE_FACTORS, "mean", T.CASE_LAM / np.sqrt(C), T.CASE_ALPHA / np.sqrt(C), 300, weight=T.CASE_W)
+    err = max(float(np.abs(got[:, c] - want).max()) for c in range(C))
+    print(f"C = {C} identical channels: max|coupled - tv_superres at lam / sqrt(C), huber / sqrt(C)| = {err:.2e} (bound 1e-9)")
+    assert err <= 1e-9
+
+
+def test_energy_reaches_the_lbfgs_minimum_which_shares_nothing_with_the_iteration():
+    hr, y, w = J.case_data()
+    minimum = J.lbfgs_minimum_joint(y, T.block_kernel("mean", J.CASE_FACTORS), J.CASE_LAM, J.CASE_ALPHA, w, J.CASE_MU, hr.shape)
+    _, info = baselines.tv_superres_joint(y, J.CASE_FACTORS, "mean", J.CASE_LAM, J.CASE_ALPHA, 1000, J.CASE_MU, weight=w, return_info=True)
+    gap = (float(info["energy"][0]) - minimum) / minimum
+    print(f"L-BFGS-B minimum {minimum:.12f}, energy after 1,000 iterations {float(info['energy'][0]):.12f}, relative gap {gap:.2e}")
+    assert abs(gap) <= 1e-9
+
+
+# ---- the study case on the device -----------------------------------------------------------------------------------------------------------
+def test_the_study_case_on_the_device():
+    hr, y, b = J.study_case(0)
+    args = ((2, 2), "mean", J.STUDY_LAM, J.STUDY_HUBER, J.STUDY_ITERS)
+    scores = {}
+    for coupling in ("joint", "none"):
+        got = baselines.tv_superres_joint(y, *args, None, coupling)
+        want = J.solve_joint(y, *args, coupling=coupling)
+        err = float(np.abs(got - want).max())
+        scores[coupling] = J.study_scores(got, hr, b)
+        print(f"study case, {coupling}: max|got - restated| = {err:.3e} (bound {SOLVER_BOUND:.0e}); b = 1500 PSNR {scores[coupling][0]:.2f} dB, "
+              f"all channels {scores[coupling][1]:.2f} dB, ADC RMSE {scores[coupling][2]:.4e}")
+        assert err <= SOLVER_BOUND
+    assert scores["joint"][0] >= scores["none"][0] + 1.0
+    assert scores["joint"][2] < scores["none"][2]
+
+
+def test_ops_wrapper_checks_before_it_launches():
+    y = torch.rand(2, 3, 3, 5, device="cuda", dtype=torch.float64)
+    k = [[0.25, 0.25], [0.25, 0.25]]
+    out, energy, change = ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", 3)
+    assert out.shape == (2, 3, 6, 10) and energy.shape == change.shape == (2,)
+    with pytest.raises(ValueError, match="contiguous"):
+        ops.tvj_solve(y[:, :, :, ::2], (2, 2), k, None, 0.01, 0.0, "joint", 3)
+    with pytest.raises(ValueError, match="contiguous \\[n, channels, rows, columns\\]"):
+        ops.tvj_solve(y[0], (2, 2), k, None, 0.01, 0.0, "joint", 3)
+    with pytest.raises(TypeError, match="float32 or torch.float64"):
+        ops.tvj_solve(y.half(), (2, 2), k, None, 0.01, 0.0, "joint", 3)
+    with pytest.raises(ValueError, match="weight has shape"):
+        ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", 3, weight=y[:1].contiguous())
+    with pytest.raises(ValueError, match="x0 has shape"):
+        ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", 3, x0=y)
+    with pytest.raises(ValueError, match="sum to 1"):
+        ops.tvj_solve(y, (2, 2), [[1.0, 1.0], [1.0, 1.0]], None, 0.01, 0.0, "joint", 3)
+    with pytest.raises(ValueError, match="channel_weights are 3 finite values within \\[0, 1\\]"):
+        ops.tvj_solve(y, (2, 2), k, (1.0, 2.0, 0.5), 0.01, 0.0, "joint", 3)
+    with pytest.raises(ValueError, match="coupling must be 'joint' or 'none'"):
+        ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, 1, 3)
+    with pytest.raises(ValueError, match="channels are 1 .. 16"):
+        ops.tvj_solve(torch.rand(1, 17, 3, 5, device="cuda", dtype=torch.float64), (2, 2), k, None, 0.01, 0.0, "joint", 3)
+    with pytest.raises(ValueError, match="workspace must be a device float64 tensor of at least 1440"):
+        ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", 3, workspace=torch.empty(1439, device="cuda", dtype=torch.float64))
+    with pytest.raises(ValueError, match="n_iter >= 0"):
+        ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", -1)
+    ws = torch.empty(1440, device="cuda", dtype=torch.float64)
+    again = ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", 3, workspace=ws)[0]
+    assert torch.equal(again, out)
+
+
+# ---- the drivers ----------------------------------------------------------------------------------------------------------------------------
+TIMINGS = ("t_fit_s", "t_recon_s", "train_voxels_per_s")        # wall-clock: the only values two runs of one command do not share
+JOINT_KEYS = {"psnr_tv_joint_db", "ssim_tv_joint_mean", "tv_joint_consistency_psnr_db"}
+
+
+def _four_b_volume(path, n_b=4):
+    """The synthetic four-b volume of test_gpu_tvsr.py's --adc test."""
+    rng = np.random.default_rng(3)
+    bvals = np.array([0.0, 150.0, 1000.0, 1500.0])[:n_b]
+    gx, gy, gz = np.meshgrid(np.linspace(0, 1, 32), np.linspace(0, 1, 32), np.linspace(0, 1, 2), indexing="ij")
+    vol = np.stack([500 * (1.2 + np.sin(3 * gx + gz) * np.cos(2 * gy)) * np.exp(-0.7 * b) for b in range(4)], axis=-1)
+    vol *= 1 + 0.02 * rng.standard_normal(vol.shape)
+    matio.savemat(path, {"vol": vol[..., :n_b], "b": bvals})
+    return bvals
+
+
+def test_superresDWI_tv_joint(tmp_path):
+    path = str(tmp_path / "pat068_vol.mat")
+    bvals = _four_b_volume(path)
+    common = ["--data", path, "--number_of_epochs", "5", "--hidden_dim", "128", "--num_layers", "2", "--mapping_size", "32", "--roi_start",
+              "2", "--roi_end", "30", "--seed", "0", "--adc", "--tv_baseline", "--tv_lambda", "2e-3", "--tv_huber", "0.05", "--tv_iters", "80"]
+    joint = ["--tv_joint", "--tv_joint_lambda", "0.01", "--tv_joint_weights", "sqrt_signal"]
+    out_plain, out = str(tmp_path / "plain"), str(tmp_path / "joint")
+    res_plain = dwi_script.main(common + ["--output_address", out_plain])[0]
+    res = dwi_script.main(common + joint + ["--output_address", out])[0]
+    d_plain, d = os.path.join(out_plain, "pat068"), os.path.join(out, "pat068")
+    # a direct call on the LR stack the driver forms
+    mean_img, _, _, _, scale = dwi_script.load_input_and_scale(path)
+    hs = torch.from_numpy(np.ascontiguousarray(mean_img[2:30, 2:30], dtype=np.float32)).cuda().permute(2, 3, 0, 1).contiguous()
+    ls = hs[:, :, ::2, ::2].contiguous()
+    mu = baselines.channel_weights(ls, "sqrt_signal")
+    tvj = baselines.tv_superres_joint(ls, (2, 2), "decimate", 0.01, 0.05, 80, mu)
+    stack = (tvj.permute(2, 3, 0, 1).contiguous() * torch.as_tensor(scale.astype(np.float32), device="cuda")).contiguous()
+    want_adc = metrics.calculate_ADC_device(bvals, stack).cpu().numpy()
+    adc = matio.loadmat(os.path.join(d, "adc.mat"))
+    m = json.load(open(os.path.join(d, "metrics.json")))
+    rows = reports.read_csv(os.path.join(d, "ssim_scores.csv"))
+    jrows = reports.read_csv(os.path.join(d, "ssim_scores_tv_joint.csv"))
+    floor = lambda t: t.clamp_min(1e-30)
+    want_ssim = metrics.ssim_reference_protocol(floor(hs), floor(tvj)).cpu().numpy().reshape(-1)
+    col = np.array([float(r["SSIM-tv-joint"]) for r in jrows])
+    want_psnr = float(metrics.psnr(hs, tvj, 1.0))
+    print(f"--tv_joint: psnr_tv_joint_db {m['psnr_tv_joint_db']:.3f} (direct {want_psnr:.3f}), psnr_tv_db {m['psnr_tv_db']:.3f}, "
+          f"ssim_tv_joint_mean {m['ssim_tv_joint_mean']:.4f}, tv_joint_consistency_psnr_db {m['tv_joint_consistency_psnr_db']:.2f}, "
+          f"channel weights {mu.tolist()}, adc_tv_joint median {np.nanmedian(adc['adc_tv_joint']):.3e}")
+    assert open(os.path.join(d, "ssim_scores_tv_joint.csv")).readline() == reports.SSIM_TV_JOINT_HEADER
+    assert len(jrows) == len(rows) == 8 and set(jrows[0]) == {"Pt_id", "b-value", "slice", "SSIM-tv-joint", "SSIM-SR"}
+    for key in ("Pt_id", "b-value", "slice", "SSIM-SR"):
+        assert [r[key] for r in jrows] == [r[key] for r in rows], key
+    assert np.array_equal(col, want_ssim) and m["ssim_tv_joint_mean"] == pytest.approx(col.mean())
+    assert m["psnr_tv_joint_db"] == want_psnr == res["psnr_tv_joint_db"]
+    assert m["tv_joint_consistency_psnr_db"] == float(metrics.psnr(ls, baselines.block_apply(tvj, (2, 2), "decimate"), 1.0))
+    assert adc["adc_tv_joint"].shape == (28, 28, 2) and np.array_equal(adc["adc_tv_joint"], want_adc, equal_nan=True)
+    # without --tv_joint: every file and key is what it was, byte for byte, apart from the wall-clock values
+    plain = json.load(open(os.path.join(d_plain, "metrics.json")))
+    assert set(m) - set(plain) == JOINT_KEYS and not [k for k in list(plain) + list(res_plain) if "joint" in k]
+    strip = lambda s: json.dumps({k: v for k, v in s.items() if k not in TIMINGS and k not in JOINT_KEYS}, indent=1).encode()
+    assert strip(plain) == strip(m)
+    assert list(plain) == [k for k in m if k not in JOINT_KEYS]
+    assert sorted(os.listdir(d)) == sorted(os.listdir(d_plain) + ["ssim_scores_tv_joint.csv"])
+    for name in ("recon.npy", "ssim_scores.csv", "ssim_scores_tv.csv"):
+        assert open(os.path.join(d_plain, name), "rb").read() == open(os.path.join(d, name), "rb").read(), name
+    adc_plain = matio.loadmat(os.path.join(d_plain, "adc.mat"))
+    assert set(adc) - set(adc_plain) == {"adc_tv_joint"}
+    for key in adc_plain:
+        if not key.startswith("__"):
+            assert np.array_equal(adc_plain[key], adc[key], equal_nan=True), key
+    # a single-b input is refused before the fit
+    single = str(tmp_path / "pat069_vol.mat")
+    _four_b_volume(single, n_b=1)
+    with pytest.raises(ValueError, match="--tv_joint couples the b-values of a slice and needs 2 .. 16 of them.*has 1"):
+        dwi_script.main(["--data", single, "--number_of_epochs", "5", "--roi_start", "2", "--roi_end", "30", "--tv_baseline", "--tv_joint",
+                         "--output_address", str(tmp_path / "single")])
+
+
+def test_joint_bvalues_on_pat07(tmp_path, golden):
+    vol = golden("pat07_volume.npz")["vol"]
+    path = str(tmp_path / "pat07_mean_b0.mat")
+    matio.savemat(path, {"data_mean_b0": vol})
+    which = [10, 14, 18]
+    out = str(tmp_path / "jb")
+    res = jb_script.main(["--data", path, "--output_address", out, "--synthetic_adc", "--slices", "10", "14", "18", "--tv_iters", "100",
+                          "--tv_lambda", "0.012"])[0]
+    d = os.path.join(out, "pat07")
+    assert sorted(os.listdir(d)) == ["joint_bvalues.csv", "joint_bvalues.mat", "metrics.json"]
+    m = json.load(open(os.path.join(d, "metrics.json")))
+    rows = reports.read_csv(os.path.join(d, "joint_bvalues.csv"))
+    # direct calls on the data the driver forms
+    mean_img = dwi_script.load_input_and_scale(path)[0]
+    roi = np.ascontiguousarray(mean_img[40:90, 40:90].transpose(2, 3, 0, 1), dtype=np.float64)[which][:, 0]
+    hr = drivers.synthetic_decay(roi / roi.max())
+    eta = np.stack([0.02 * np.random.default_rng(z).standard_normal((4, 25, 25)) for z in which])
+    y = baselines.block_apply(_dev(hr), (2, 2), "mean") + _dev(eta)
+    tv = baselines.tv_superres(y, (2, 2), "mean", 0.012, baselines.TVJ_DEFAULT_HUBER, 100)
+    tvj = baselines.tv_superres_joint(y, (2, 2), "mean", baselines.TVJ_DEFAULT_LAMBDA, baselines.TVJ_DEFAULT_HUBER, 100)
+    f32 = lambda t: t.float().contiguous()
+    for name, image in (("tv", tv), ("tv_joint", tvj)):
+        want_ssim = metrics.ssim(f32(_dev(hr)), f32(image), 1.0).cpu().numpy().reshape(-1)
+        want_psnr = metrics.psnr(f32(_dev(hr)), f32(image), 1.0, per_image=True).cpu().numpy().reshape(-1)
+        assert np.array_equal(np.array([float(r[f"SSIM-{name}"]) for r in rows]), want_ssim), name
+        assert np.array_equal(np.array([float(r[f"PSNR-{name}"]) for r in rows]), want_psnr), name
+    print(f"joint_bvalues on pat07 (synthetic ADC, 100 iterations): " + ", ".join(
+        f"{name}: PSNR {m[f'psnr_{name}_db']:.2f} dB, b = 1500 {m[f'psnr_{name}_b1500_db']:.2f} dB, ADC RMSE {m[f'adc_rmse_{name}']:.3e}"
+        for name in drivers.JOINT_METHODS))
+    assert len(rows) == 12 and [r["slice"] for r in rows] == [str(z) for z in which for _ in range(4)]
+    assert [float(r["b-value"]) for r in rows[:4]] == list(drivers.SYNTHETIC_B)
+    assert m["methods"] == list(drivers.JOINT_METHODS) == res["methods"] and m["channel_weights"] == [1.0] * 4
+    mat = matio.loadmat(os.path.join(d, "joint_bvalues.mat"))
+    assert mat["tv_joint"].shape == mat["hr"].shape == (50, 50, 3, 4) and mat["lr"].shape == (25, 25, 3, 4) and mat["adc_tv_joint"].shape == (50, 50, 3)
+    assert np.array_equal(mat["tv_joint"], tvj.cpu().numpy().transpose(2, 3, 0, 1))
+    assert all(np.isfinite(m[f"adc_rmse_{name}"]) for name in drivers.JOINT_METHODS)
