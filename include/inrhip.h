@@ -749,6 +749,40 @@ int inr_tvj_solve2d_f32(float* out, double* energy, double* change, const float*
                         double lambda, double alpha, int coupling, int n_iter, double* workspace, int64_t workspace_doubles,
                         void* stream);
 
+/* ---- second-order TGV super-resolution under the block operator: a prior that does not terrace smooth intensity -------
+ * No counterpart in the reference.  Images, sides, factors and the HOST `kernel` as for inr_tvsr_solve2d.  An auxiliary field
+ * v = (v0, v1) [n_images][2][H][W] absorbs the smooth part of the gradient (Bredies, Kunisch, Pock 2010; Knoll et al. 2011):
+ * inr_tgv_solve2d: out = n_iter iterations of Chambolle-Pock (tau = sigma = 1/sqrt(12)) on
+ *   min_{x, v} 1/2 sum_i w_i ((A x)_i - y_i)^2 + lam1 sum_j H_alpha(|(grad x)_j - v_j|) + lam0 sum_j |(Ev)_j|_F,
+ *   lam1 = lambda, lam0 = ratio * lambda;  Ev = (e00, e11, e01) = (d0 v0, d1 v1, (d1 v0 + d0 v1) / 2) with d0 / d1 the forward
+ *   differences of grad (zero last row / column), |Ev|_F = sqrt(e00^2 + e11^2 + 2 e01^2), div0 / div1 the negative adjoints of d0 / d1
+ *   (A, grad, div, H_alpha: inr_tvsr_solve2d), from x = xbar = x0, v = vbar = 0, p = 0, r = 0:
+ *     q <- (p + sigma (grad(xbar) - vbar)) / (1 + sigma alpha / lam1);  p <- q / max(1, |q| / lam1)
+ *     s <- r + sigma E(vbar);                                           r <- s / max(1, |s|_F / lam0)
+ *     u <- x + tau div(p);  x' <- u - A^T(c (A u - y)), c_i = tau w_i / (1 + tau w_i |k|^2)
+ *     v0' <- v0 + tau (p0 + div0 r00 + div1 r01);  v1' <- v1 + tau (p1 + div1 r11 + div0 r01)
+ *     xbar <- 2 x' - x;  vbar <- 2 v' - v;  x <- x';  v <- v'
+ *   The steps hold because |(grad x - v, Ev)|^2 <= 12 (|x|^2 + |v|^2) (csrc/tgv.hip).  lambda == 0 skips the dual phases: p, r and v
+ *   stay 0 and the result is the data-only iteration (ratio is still checked).  y, weight, x0 as for inr_tvsr_solve2d (weight 0: a
+ *   missing datum whose y is never read; x0 null: block replication).  v_out [n][2][H][W] DEVICE or null: the field at the end.
+ *   energy / change [n] DEVICE doubles or null: the objective at the returned fp64 (x, v) (fixed order, no float atomics) and
+ *   max |x' - x| of the last iteration, on x only (0 for n_iter == 0, which returns x0 and v = 0).  ONE launch, no host read: one
+ *   workgroup of 1,024 threads per image runs all iterations with two workgroup barriers per iteration; images beyond the CU count are
+ *   queued.  The _f32 form reads y / weight / x0 and writes out and v_out as fp32, fp64 inside, rounded once.  n_images == 0
+ *   succeeds and launches nothing.
+ * workspace: inr_tgv_workspace_doubles(n_images, H, W) = 11 n H W doubles (the state x | xbar | v0 | v1 | vbar0 | vbar1 | p0 | p1 |
+ * r00 | r11 | r01 of every image; n = 1 for n_images == 0), 16-byte aligned; 0 for sizes that would be refused.  Refusals, all before
+ * any device work: INR_E_INVALID (null out / y / kernel, n_images < 0, factors or sizes out of range, H or W no multiple of its
+ * factor, n_iter < 0, a negative or non-finite lambda / alpha, a ratio that is not finite or <= 0, a kernel that is not finite or does
+ * not sum to 1), INR_E_WORKSPACE (null or short workspace), INR_E_ALIGN (workspace off a 16-byte boundary). */
+int64_t inr_tgv_workspace_doubles(int n_images, int height, int width);
+int inr_tgv_solve2d(double* out, double* v_out, double* energy, double* change, const double* y, const double* weight, const double* x0,
+                    int n_images, int height, int width, int f0, int f1, const double* kernel, double lambda, double ratio, double alpha,
+                    int n_iter, double* workspace, int64_t workspace_doubles, void* stream);
+int inr_tgv_solve2d_f32(float* out, float* v_out, double* energy, double* change, const float* y, const float* weight, const float* x0,
+                        int n_images, int height, int width, int f0, int f1, const double* kernel, double lambda, double ratio,
+                        double alpha, int n_iter, double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- the reader study's image scores (implicit-neural-representations/perceptual_similarity_tests/perceptual_similarity.m, HPF.m) -----
  * The scores that the reference computes in MATLAB on the panels of prepare_qual_images.py, by the DEFINITIONS of DESIGN.md 4g:
  * MATLAB's documented defaults for ssim, immse, imfilter and fspecial('unsharp'), and Wang et al. 2003 for MS-SSIM.  No MATLAB output

@@ -214,6 +214,11 @@ SIGNATURES = {
                                                                                                 C.c_void_p, C.c_int64, c_stream]),
     "inr_tvj_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 6 +
                             [C.POINTER(C.c_double)] * 2 + [C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "inr_tgv_workspace_doubles": (C.c_int64, [C.c_int] * 3),
+    "inr_tgv_solve2d": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int,
+                                                                    C.c_void_p, C.c_int64, c_stream]),
+    "inr_tgv_solve2d_f32": (C.c_int, [c_f32p, c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 5 +
+                            [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p, C.c_int64, c_stream]),
     "inr_footprint_expand": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, C.c_int, c_stream]),
     "inr_footprint_reduce": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_int64, C.c_int, c_stream]),
     "inr_footprint_loss_workspace_floats": (C.c_int64, [C.c_int64]),

@@ -314,6 +314,25 @@ def block_adjoint(r, factors, kernel="mean"):
     return out.cpu().numpy() if as_numpy else out
 
 
+def _weight_and_start(who, lr, as_numpy, lead, weight, lr_shape, x0, hr_shape):
+    """``weight`` (``lead + lr_shape``) and ``x0`` (``lead + hr_shape``) of a per-image solver, refused by name where they are not given
+    like ``lr``; -> {"weight", "x0"}: None, or the device tensor [n, rows, columns]."""
+    extra = {}
+    for name, value, shape in (("weight", weight, lr_shape), ("x0", x0, hr_shape)):
+        if value is None:
+            extra[name] = None
+            continue
+        if isinstance(value, np.ndarray) != as_numpy:
+            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
+        _fourier_input(who, value)
+        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
+            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
+        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
+            raise ValueError(f"{who}: weight must be finite and >= 0")
+        extra[name] = value
+    return {name: None if value is None else _block_batch(value, as_numpy) for name, value in extra.items()}   # the device last
+
+
 def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, huber: float = TV_DEFAULT_HUBER,
                 n_iter: int = TV_DEFAULT_ITERS, weight=None, x0=None, return_info: bool = False):
     """Model-based super-resolution of the trailing two axes of ``lr`` by ``factors`` = (f0, f1), 1 .. 8 each ((1, 1) denoises):
@@ -336,21 +355,8 @@ def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, hube
         raise ValueError(f"{who}: n_iter must be an integer >= 0 (got {n_iter!r})")
     as_numpy, h, w, lead = _block_input(who, lr)
     _hr_sides(who, h * f0, w * f1, f0, f1)
-    extra = {}
-    for name, value, shape in (("weight", weight, (h, w)), ("x0", x0, (h * f0, w * f1))):
-        if value is None:
-            extra[name] = None
-            continue
-        if isinstance(value, np.ndarray) != as_numpy:
-            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
-        _fourier_input(who, value)
-        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
-            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
-        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
-            raise ValueError(f"{who}: weight must be finite and >= 0")
-        extra[name] = value
+    extra = _weight_and_start(who, lr, as_numpy, lead, weight, (h, w), x0, (h * f0, w * f1))
     y = _block_batch(lr, as_numpy)
-    extra = {name: None if value is None else _block_batch(value, as_numpy) for name, value in extra.items()}
     out, energy, change = ops.tvsr_solve(y, (f0, f1), k, lam, huber, int(n_iter), extra["weight"], extra["x0"])
     out = out.reshape(*lead, h * f0, w * f1)
     energy, change = energy.reshape(lead), change.reshape(lead)
@@ -447,6 +453,45 @@ def tv_superres_joint(lr, factors, kernel="mean", lam: float = TVJ_DEFAULT_LAMBD
     if as_numpy:
         out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
     return (out, {"energy": energy, "change": change}) if return_info else out
+
+
+TGV_DEFAULT_LAMBDA, TGV_DEFAULT_RATIO, TGV_DEFAULT_HUBER, TGV_DEFAULT_ITERS = 0.005, 0.5, 0.0, 300   # the sweep of DESIGN.md 4r
+
+
+def tgv_superres(lr, factors, kernel="mean", lam: float = TGV_DEFAULT_LAMBDA, ratio: float = TGV_DEFAULT_RATIO,
+                 huber: float = TGV_DEFAULT_HUBER, n_iter: int = TGV_DEFAULT_ITERS, weight=None, x0=None, return_info: bool = False):
+    """``tv_superres`` under the second-order total generalized variation, which does not terrace smooth intensity: ``n_iter``
+    Chambolle-Pock iterations on ``1/2 sum w (A x - lr)^2 + lam sum H_huber(|grad x - v|) + ratio lam sum |E v|_F`` over the image ``x``
+    and an auxiliary vector field ``v`` that absorbs the smooth part of the gradient (``E v`` its symmetrised derivative): a ramp costs
+    nothing, an edge still costs its jump.  ``ratio`` > 0 weighs the second-order term against the first (large: towards
+    ``tv_superres``); ``lam`` = 0 keeps the data term only.  Input types, leading-axis batching, ``kernel``, ``weight``, ``x0`` and dtype
+    rules as ``tv_superres``.  One launch for the whole batch, one workgroup per image (``inr_tgv_solve2d``).  There is no
+    CPU fallback.  ``return_info``: also a dict with ``energy`` (the objective at the returned ``(x, v)``), ``change`` (max |x' - x| of
+    the last iteration), both of the leading shape, and ``v`` [..., 2, H, W]."""
+    who = "tgv_superres"
+    f0, f1, k = _block_kernel(who, kernel, factors)
+    lam, ratio, huber = float(lam), float(ratio), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 < ratio < np.inf:
+        raise ValueError(f"{who}: ratio must be finite and > 0 (got {ratio!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or n_iter < 0:
+        raise ValueError(f"{who}: n_iter must be an integer >= 0 (got {n_iter!r})")
+    as_numpy, h, w, lead = _block_input(who, lr)
+    _hr_sides(who, h * f0, w * f1, f0, f1)
+    extra = _weight_and_start(who, lr, as_numpy, lead, weight, (h, w), x0, (h * f0, w * f1))
+    y = _block_batch(lr, as_numpy)
+    out, v, energy, change = ops.tgv_solve(y, (f0, f1), k, lam, ratio, huber, int(n_iter), extra["weight"], extra["x0"],
+                                           want_v=return_info)
+    out = out.reshape(*lead, h * f0, w * f1)
+    if not return_info:
+        return out.cpu().numpy() if as_numpy else out
+    v, energy, change = v.reshape(*lead, 2, h * f0, w * f1), energy.reshape(lead), change.reshape(lead)
+    if as_numpy:
+        out, v, energy, change = out.cpu().numpy(), v.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
+    return out, {"energy": energy, "change": change, "v": v}
 
 
 TVMF_DEFAULT_LAMBDA,TVMF_DEFAULT_HUBER, TVMF_DEFAULT_ITERS = 0.01, 0.03, 300  # the sweep of DESIGN.md 4n (8 frames, noise 0.02)

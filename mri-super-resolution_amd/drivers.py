@@ -1418,3 +1418,94 @@ def joint_bvalue_study(hr, bvalues, factor=2, kernel="mean", noise=0.02, seed=0,
     adc_rmse = {name: float(((adc[name] - adc["hr"])[mask] ** 2).mean().sqrt()) for name in images}
     return {"images": images, "hr": hr_d, "lr": y, "methods": tuple(images), "psnr": psnr, "ssim": ssim, "psnr_b": psnr_b,
             "psnr_all": psnr_all, "adc": adc, "adc_rmse": adc_rmse, "mask": mask, "channel_weights": mu, "info": info}
+
+
+# ---- the second-order study: does TGV remove the terraces of TV on smoothly varying intensity? ------------------------
+SECOND_ORDER_METHODS = ("replicate", "tv", "tgv")
+FLAT_THRESHOLD = 1e-3
+
+
+def check_second_order(rows=48, cols=48, factor=2, kernel="mean", noise=0.02, tv_lambda=3e-3, tv_huber=0.3, tgv_lambda=0.005, tgv_ratio=0.5,
+                       tgv_huber=0.0, iters=300):
+    """What ``second_order_study`` cannot serve, by name; touches neither the input nor the device.  Returns the LR sides."""
+    who = "second_order_study"
+    for name, side in (("rows", rows), ("cols", cols)):
+        if isinstance(side, bool) or int(side) != side or not 2 <= side <= ops.TVSR_MAX_SIDE:
+            raise ValueError(f"{who}: the HR image has 2 .. {ops.TVSR_MAX_SIDE} {name} (got {side!r})")
+    if isinstance(factor, bool) or int(factor) != factor or not 1 <= factor <= ops.TVSR_MAX_FACTOR or rows % int(factor) or cols % int(factor):
+        raise ValueError(f"{who}: factor is 1 .. {ops.TVSR_MAX_FACTOR} and divides the HR sides {rows} x {cols} (got {factor!r})")
+    if kernel not in ("mean", "decimate"):
+        raise ValueError(f"{who}: kernel must be 'mean' or 'decimate' (got {kernel!r})")
+    if not 0.0 <= float(noise) < float("inf"):
+        raise ValueError(f"{who}: noise must be finite and >= 0 (got {noise!r})")
+    for name, value in (("tv_lambda", tv_lambda), ("tv_huber", tv_huber), ("tgv_lambda", tgv_lambda), ("tgv_huber", tgv_huber)):
+        if not 0.0 <= float(value) < float("inf"):
+            raise ValueError(f"{who}: {name} must be finite and >= 0 (got {value!r})")
+    if not 0.0 < float(tgv_ratio) < float("inf"):
+        raise ValueError(f"{who}: tgv_ratio must be finite and > 0 (got {tgv_ratio!r})")
+    if int(iters) != iters or not 1 <= iters <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: iters must be 1 .. 100,000 (got {iters!r})")
+    return int(rows) // int(factor), int(cols) // int(factor)
+
+
+def second_order_phantom(n=48):
+    """A ramp, a quadratic and a disc, [n, n] float64 in (0, 1]: ``0.2 + 0.5 i + 0.2 j^2 + 0.25 [(i - 0.4)^2 + (j - 0.55)^2 < 0.04]`` with
+    ``i, j = index / (n - 1)``, divided by its maximum -- smooth intensity that a first-order prior terraces."""
+    t = np.arange(n) / (n - 1.0)
+    i, j = t[:, None], t[None, :]
+    x = 0.2 + 0.5 * i + 0.2 * j ** 2 + 0.25 * ((i - 0.4) ** 2 + (j - 0.55) ** 2 < 0.04)
+    return x / x.max()
+
+
+def flat_area_index(x, threshold=FLAT_THRESHOLD):
+    """The share of the interior pixels of every image of the device stack ``x`` [..., H, W] whose forward-difference gradient
+    magnitude is below ``threshold``: a flat-area index of staircasing (fp64; the last row and column have no full gradient)."""
+    x = x.double()
+    g0 = x[..., 1:, :-1] - x[..., :-1, :-1]
+    g1 = x[..., :-1, 1:] - x[..., :-1, :-1]
+    return ((g0 * g0 + g1 * g1).sqrt() < threshold).double().mean(dim=(-2, -1))
+
+
+def second_order_study(hr, factor=2, kernel="mean", noise=0.02, seed=0, tv_lambda=None, tv_huber=None, tgv_lambda=None, tgv_ratio=None,
+                       tgv_huber=None, iters=None, slice_ids=None):
+    """``hr`` [Z, H, W] in [0, 1]: the LR stack [Z, h, w] is ``baselines.block_apply`` under ``kernel`` plus Gaussian noise of ``noise``
+    -- slice z (``slice_ids[i]`` where given, else i) draws its [h, w] from ``np.random.default_rng(seed * 1000 + z)`` --,
+    reconstructed on the device by ``replicate`` (block replication), ``tv`` (``baselines.tv_superres`` with ``tv_lambda``, ``tv_huber``:
+    the ``TV_DEFAULT_*`` where None) and ``tgv`` (``baselines.tgv_superres`` with ``tgv_lambda``, ``tgv_ratio``, ``tgv_huber``: the
+    ``TGV_DEFAULT_*`` where None), all with ``iters`` iterations (``TGV_DEFAULT_ITERS``).  Returns ``{"images", "hr", "lr", "methods",
+    "psnr", "ssim", "flat"`` [Z] per method (data range 1; ``flat`` also of ``hr``: ``flat_area_index``), ``"psnr_all"`` per method,
+    ``"info"}``."""
+    from . import baselines
+
+    lam = baselines.TV_DEFAULT_LAMBDA if tv_lambda is None else tv_lambda
+    huber = baselines.TV_DEFAULT_HUBER if tv_huber is None else tv_huber
+    lam_g = baselines.TGV_DEFAULT_LAMBDA if tgv_lambda is None else tgv_lambda
+    ratio = baselines.TGV_DEFAULT_RATIO if tgv_ratio is None else tgv_ratio
+    huber_g = baselines.TGV_DEFAULT_HUBER if tgv_huber is None else tgv_huber
+    iters = baselines.TGV_DEFAULT_ITERS if iters is None else iters
+    vol = np.asarray(hr, np.float64)
+    if vol.ndim != 3:
+        raise ValueError(f"second_order_study: hr is [Z, H, W] (got {vol.shape})")
+    Z, H, W = vol.shape
+    h, w = check_second_order(H, W, factor, kernel, noise, lam, huber, lam_g, ratio, huber_g, iters)
+    ids = list(range(Z)) if slice_ids is None else [int(v) for v in slice_ids]
+    if len(ids) != Z or (Z and min(ids) < 0):
+        raise ValueError(f"second_order_study: slice_ids are one index >= 0 per slice (got {slice_ids!r} for {Z} slices)")
+    f = int(factor)
+    eta = np.stack([noise * np.random.default_rng(int(seed) * 1000 + z).standard_normal((h, w)) for z in ids])
+    dev = ops.require_gpu()
+    hr_d = torch.from_numpy(vol).to(dev)
+    y = baselines.block_apply(hr_d, (f, f), kernel) + torch.from_numpy(eta).to(dev)
+    images, info = {"replicate": y.repeat_interleave(f, dim=-2).repeat_interleave(f, dim=-1).contiguous()}, {}
+    images["tv"], res = baselines.tv_superres(y, (f, f), kernel, lam, huber, int(iters), return_info=True)
+    info["tv"] = {k: v.cpu().numpy() for k, v in res.items()}
+    images["tgv"], res = baselines.tgv_superres(y, (f, f), kernel, lam_g, ratio, huber_g, int(iters), return_info=True)
+    info["tgv"] = {k: v.cpu().numpy() for k, v in res.items()}
+    f32 = lambda t: t.float().contiguous()
+    psnr = {name: metrics.psnr(f32(hr_d), f32(v), 1.0, per_image=True).cpu().numpy() for name, v in images.items()}
+    ssim = {name: metrics.ssim(f32(hr_d), f32(v), 1.0).cpu().numpy() for name, v in images.items()}
+    psnr_all = {name: float(metrics.psnr(f32(hr_d), f32(v), 1.0)) for name, v in images.items()}
+    flat = {name: flat_area_index(v).cpu().numpy() for name, v in images.items()}
+    flat["hr"] = flat_area_index(hr_d).cpu().numpy()
+    return {"images": images, "hr": hr_d, "lr": y, "methods": tuple(images), "psnr": psnr, "ssim": ssim, "flat": flat,
+            "psnr_all": psnr_all, "info": info}

@@ -859,6 +859,49 @@ def tvj_solve(y: torch.Tensor, factors, kernel, channel_weights, lam: float, alp
     return out, energy, change
 
 
+# ---- second-order TGV under the block operator (include/inrhip.h) --------------------------------------------------------
+def tgv_workspace_doubles(n: int, H: int, W: int) -> int:
+    """``inr_tgv_workspace_doubles``; 0 for sizes ``inr_tgv_solve2d`` refuses."""
+    return int(lib().inr_tgv_workspace_doubles(int(n), int(H), int(W)))
+
+
+def tgv_solve(y: torch.Tensor, factors, kernel, lam: float, ratio: float, alpha: float, n_iter: int, weight=None, x0=None,
+              workspace=None, want_v=True):
+    """``inr_tgv_solve2d`` / ``_f32`` by the dtype of ``y`` [n, h, w]: returns (x [n, f0 h, f1 w] of that dtype, v [n, 2, f0 h, f1 w] of
+    that dtype or None where ``want_v`` is false, energy [n] float64, change [n] float64).  ``lam`` weighs the first-order term,
+    ``ratio * lam`` the second-order one; ``weight`` [n, h, w] and ``x0`` [n, f0 h, f1 w] share the dtype; ``workspace``: a float64
+    tensor."""
+    _chk_images(y, "y", (torch.float32, torch.float64))
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, h, w = y.shape
+    H, W = h * f0, w * f1
+    _hr_shape("tgv_solve", H, W, f0, f1)
+    if weight is not None:
+        _chk_images(weight, "weight", (y.dtype,), y.shape)
+    if x0 is not None:
+        _chk_images(x0, "x0", (y.dtype,), (n, H, W))
+    lam, ratio, alpha, n_iter = float(lam), float(ratio), float(alpha), int(n_iter)
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or n_iter < 0:
+        raise ValueError(f"tgv_solve: lam and alpha must be finite and >= 0, n_iter >= 0 (got {lam!r}, {alpha!r}, {n_iter})")
+    if not (0.0 < ratio < float("inf")):
+        raise ValueError(f"tgv_solve: ratio must be finite and > 0 (got {ratio!r})")
+    out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
+    v = torch.empty((n, 2, H, W), dtype=y.dtype, device=y.device) if want_v else None
+    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
+    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    if n == 0:
+        return out, v, energy, change
+    need = tgv_workspace_doubles(n, H, W)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
+    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
+        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
+    entry = "inr_tgv_solve2d" if y.dtype == torch.float64 else "inr_tgv_solve2d_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), _ptr(v), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, H,
+                                W, f0, f1, k, lam, ratio, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()), entry)
+    return out, v, energy, change
+
+
 # ---- the same on volumes: slice profile, 3-D prior, many workgroups per volume (include/inrhip.h, DESIGN.md 4m) ----------------------
 TVSR3D_MAX_ITER = _lib.INR_TVSR3D_MAX_ITER
 

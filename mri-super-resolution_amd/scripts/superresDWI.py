@@ -58,6 +58,12 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     SSIM-SR``); ``metrics.json`` gains ``psnr_tv_joint_db``, ``ssim_tv_joint_mean`` and ``tv_joint_consistency_psnr_db``; with ``--adc``,
     ``adc.mat`` gains ``adc_tv_joint``.  Refused: without ``--tv_baseline``, LJ < 0 (before the input is loaded), an input with fewer
     than 2 b-values or more than 16 (before the fit).
+  * ``--tv_tgv [--tv_tgv_lambda LG --tv_tgv_ratio R]`` (with ``--tv_baseline``): the same [Z, B, R/2, R/2] stack, every image on its
+    own, under the second-order TGV prior, which does not terrace smooth intensity:
+    ``baselines.tgv_superres(LR, (2, 2), kernel, LG, R, A, N)`` (``inr_tgv_solve2d_f32``), with ``--tv_huber`` and
+    ``--tv_iters``.  ``ssim_scores_tv_tgv.csv`` (``Pt_id, b-value, slice, SSIM-tv-tgv, SSIM-SR``); ``metrics.json`` gains
+    ``psnr_tv_tgv_db``, ``ssim_tv_tgv_mean`` and ``tv_tgv_consistency_psnr_db``; with ``--adc``, ``adc.mat`` gains ``adc_tv_tgv``.
+    Refused before the input is loaded: without ``--tv_baseline``, LG < 0, R <= 0.
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
@@ -131,6 +137,14 @@ def build_parser():
                    help="--tv_joint: weight of the coupled prior (default from the sweep of DESIGN.md 4q)")
     p.add_argument("--tv_joint_weights", choices=("equal", "sqrt_signal"), default="equal",
                    help="--tv_joint: the channel weights of the coupled norm (baselines.channel_weights)")
+    p.add_argument("--tv_tgv", action="store_true",
+                   help="with --tv_baseline: also the second-order TGV reconstruction, which does not terrace smooth intensity: "
+                        "ssim_scores_tv_tgv.csv, psnr_tv_tgv_db / ssim_tv_tgv_mean / tv_tgv_consistency_psnr_db in metrics.json, "
+                        "adc_tv_tgv with --adc; uses --tv_huber and --tv_iters")
+    p.add_argument("--tv_tgv_lambda", type=float, default=baselines.TGV_DEFAULT_LAMBDA,
+                   help="--tv_tgv: weight of the first-order term (default from the sweep of DESIGN.md 4r)")
+    p.add_argument("--tv_tgv_ratio", type=float, default=baselines.TGV_DEFAULT_RATIO,
+                   help="--tv_tgv: second-order weight / first-order weight, > 0")
     p.add_argument("--derivative_maps", action="store_true",
                    help="also write derivatives.mat: gradient magnitude and Laplacian of the fitted network on recon's grid, "
                         "along the spatial axes (nn_mri.py:205-221)")
@@ -285,6 +299,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     zf = _zerofill(hs, 2, args.zerofill_apodize) if getattr(args, "zerofill", False) else None
     tv = _tv_baseline(ls, args, average) if getattr(args, "tv_baseline", False) else None
     tvj = _tv_joint(ls, args, average) if getattr(args, "tv_joint", False) else None
+    tgv = _tv_tgv(ls, args, average) if getattr(args, "tv_tgv", False) else None
     with reports.SsimCsv(os.path.join(out_dir, "ssim_scores.csv")) as csv:
         for _slice in range(nz):
             for b in range(nb):
@@ -326,6 +341,15 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         summary["psnr_tv_joint_db"] = float(metrics.psnr(hs, tvj, 1.0))
         summary["ssim_tv_joint_mean"] = float(ssim_tvj[okn].mean())
         summary["tv_joint_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(tvj, (2, 2), _tv_kernel(average)), 1.0))
+    if tgv is not None:
+        ssim_tgv = metrics.ssim_reference_protocol(safe(hs), safe(tgv)).cpu().numpy()
+        with reports.SsimCsv(os.path.join(out_dir, "ssim_scores_tv_tgv.csv"), reports.SSIM_TV_TGV_HEADER) as csv:
+            for _slice in range(nz):
+                for b in range(nb):
+                    csv.row(pt_id, bvalues[b] if b < len(bvalues) else b, _slice, float(ssim_tgv[_slice, b]), float(ssim_sr[_slice, b]))
+        summary["psnr_tv_tgv_db"] = float(metrics.psnr(hs, tgv, 1.0))
+        summary["ssim_tv_tgv_mean"] = float(ssim_tgv[okn].mean())
+        summary["tv_tgv_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(tgv, (2, 2), _tv_kernel(average)), 1.0))
     if average:
         pred = inr.footprint_forward(INR, coords, B, footprint)
         summary.update({"lr_model": "average", "footprint": args.footprint, "footprint_samples": footprint.count,
@@ -337,7 +361,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
         matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale,
-                                                                     args.zerofill_apodize if zf is not None else None, ls, tv, tvj))
+                                                                     args.zerofill_apodize if zf is not None else None, ls, tv, tvj, tgv))
     if args.derivative_maps:
         matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape))
     if args.wire_derivative_maps:
@@ -488,8 +512,22 @@ def _tv_joint(ls, args, average):
     return baselines.tv_superres_joint(ls, (2, 2), _tv_kernel(average), args.tv_joint_lambda, args.tv_huber, args.tv_iters, mu)
 
 
+def _tv_tgv(ls, args, average):
+    """``--tv_tgv``: the [Z, B, R/2, R/2] LR stack ``ls`` -> the [Z, B, R, R] second-order TGV reconstruction, every image on its own,
+    under the LR model's operator."""
+    return baselines.tgv_superres(ls, (2, 2), _tv_kernel(average), args.tv_tgv_lambda, args.tv_tgv_ratio, args.tv_huber, args.tv_iters)
+
+
 def _check_tv(args, fit=None):
-    """``--tv_baseline`` / ``--tv_joint``: what they cannot serve, before the input is loaded and anything touches the device."""
+    """``--tv_baseline`` / ``--tv_joint`` / ``--tv_tgv``: what they cannot serve, before the input is loaded and anything touches the
+    device."""
+    if getattr(args, "tv_tgv", False):
+        if not getattr(args, "tv_baseline", False):
+            raise ValueError("--tv_tgv is scored beside the first-order reconstruction: pass --tv_baseline with it")
+        if not 0.0 <= args.tv_tgv_lambda < float("inf"):
+            raise ValueError(f"--tv_tgv_lambda must be finite and >= 0 (got {args.tv_tgv_lambda})")
+        if not 0.0 < args.tv_tgv_ratio < float("inf"):
+            raise ValueError(f"--tv_tgv_ratio must be finite and > 0 (got {args.tv_tgv_ratio})")
     if getattr(args, "tv_joint", False):
         if not getattr(args, "tv_baseline", False):
             raise ValueError("--tv_joint is scored beside the per-channel reconstruction: pass --tv_baseline with it")
@@ -513,12 +551,13 @@ def _check_tv(args, fit=None):
                          "(changes_lr_data)")
 
 
-def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, tv=None, tvj=None):
+def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, tv=None, tvj=None, tgv=None):
     """superresDWI.py:189-206 for all slices in one batch: every b-image times maxes[b, 1], then calculate_ADC per pixel, of
     the x2 SR volume, the x4 spline of the LR ROI and the x2 spline of the HR ROI.  ``hs`` is the HR ROI as [Z, B, R, R].
     ``zerofill_apodize`` (not None): also ``adc_zerofill``, the x4 zero-fill of the LR ROI, on the grid of ``adc_spline``.
     ``ls``: the LR ROI as [Z, B, R/2, R/2] (default: every second pixel of ``hs``; ``--lr_model average``: the block means).
-    ``tv`` / ``tvj`` (not None): also ``adc_tv`` / ``adc_tv_joint`` of the [Z, B, R, R] TV reconstructions, on the grid of the HR ROI."""
+    ``tv`` / ``tvj`` / ``tgv`` (not None): also ``adc_tv`` / ``adc_tv_joint`` / ``adc_tv_tgv`` of the [Z, B, R, R] TV / TGV
+    reconstructions, on the grid of the HR ROI."""
     scale = torch.as_tensor(np.asarray(signal_scale, np.float32), device=recon.device)
     to_xyzb = lambda t: t.permute(2, 3, 0, 1).contiguous()                       # [Z, B, 2R, 2R] -> [2R, 2R, Z, B]
     stacks = {"adc_sr": recon,
@@ -530,6 +569,8 @@ def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, 
         stacks["adc_tv"] = to_xyzb(tv)
     if tvj is not None:
         stacks["adc_tv_joint"] = to_xyzb(tvj)
+    if tgv is not None:
+        stacks["adc_tv_tgv"] = to_xyzb(tgv)
     out ={k: metrics.calculate_ADC_device(bvalues, (v * scale).contiguous()).cpu().numpy() for k, v in stacks.items()}
     out["b"] = np.asarray(bvalues, np.float64)
     return out
