@@ -279,10 +279,15 @@ def _block_input(who, image, name="input"):
     return as_numpy, int(image.shape[-2]), int(image.shape[-1]), tuple(image.shape[:-2])
 
 
+def _device_batch(value, as_numpy, rank):
+    """-> the device tensor [n, <the trailing ``rank`` axes>] (an ndarray as float64)."""
+    x = torch.from_numpy(np.ascontiguousarray(value, dtype=np.float64)).to(ops.require_gpu()) if as_numpy else value
+    return x.reshape(-1, *x.shape[-rank:]).contiguous()
+
+
 def _block_batch(image, as_numpy):
     """-> the device tensor [n, rows, columns] (an ndarray as float64)."""
-    x = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float64)).to(ops.require_gpu()) if as_numpy else image
-    return x.reshape(-1, x.shape[-2], x.shape[-1]).contiguous()
+    return _device_batch(image, as_numpy, 2)
 
 
 def _hr_sides(who, rows, cols, f0, f1):
@@ -314,23 +319,58 @@ def block_adjoint(r, factors, kernel="mean"):
     return out.cpu().numpy() if as_numpy else out
 
 
-def _weight_and_start(who, lr, as_numpy, lead, weight, lr_shape, x0, hr_shape):
-    """``weight`` (``lead + lr_shape``) and ``x0`` (``lead + hr_shape``) of a per-image solver, refused by name where they are not given
-    like ``lr``; -> {"weight", "x0"}: None, or the device tensor [n, rows, columns]."""
+def _weight_and_start(who, lr, as_numpy, lead, weight, lr_shape, x0, hr_shape, like="lr"):
+    """``weight`` (``lead + lr_shape``) and ``x0`` (``lead + hr_shape``) of a solver, refused by name where they are not given like
+    ``lr`` (``like``: what the messages call it); -> {"weight", "x0"}: None, or the device tensor [n, *lr_shape] / [n, *hr_shape]."""
     extra = {}
     for name, value, shape in (("weight", weight, lr_shape), ("x0", x0, hr_shape)):
         if value is None:
             extra[name] = None
             continue
         if isinstance(value, np.ndarray) != as_numpy:
-            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
+            raise TypeError(f"{who}: {name} must be given like {like} ({'an ndarray' if as_numpy else 'a device tensor'})")
         _fourier_input(who, value)
         if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
-            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
+            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of {like} (got {tuple(value.shape)}, "
+                             f"{value.dtype})")
         if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
             raise ValueError(f"{who}: weight must be finite and >= 0")
-        extra[name] = value
-    return {name: None if value is None else _block_batch(value, as_numpy) for name, value in extra.items()}   # the device last
+        extra[name] = (value, len(shape))
+    return {name: None if item is None else _device_batch(item[0], as_numpy, item[1]) for name, item in extra.items()}   # the device last
+
+
+def _tv_scalars(who, lam, huber, n_iter, max_iter=None, span="0 .."):
+    """(lam, huber, n_iter) of a solver, refused by name; ``span``: how the function words the range of ``n_iter`` up to ``max_iter``."""
+    lam, huber = float(lam), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or n_iter < 0 or (max_iter is not None and n_iter > max_iter):
+        bound = ">= 0" if max_iter is None else f"{span} {max_iter}"
+        raise ValueError(f"{who}: n_iter must be an integer {bound} (got {n_iter!r})")
+    return lam, huber, int(n_iter)
+
+
+def _grad_weights(who, grad_weights):
+    """(g0, g1, g2) of a 3-D prior as floats, refused by name."""
+    try:
+        g = tuple(float(v) for v in grad_weights)
+    except (TypeError, ValueError):
+        g = ()
+    if len(g) != 3 or not all(0.0 <= v < np.inf for v in g):
+        raise ValueError(f"{who}: grad_weights are (g0, g1, g2), finite and >= 0 (got {grad_weights!r})")
+    return g
+
+
+def _tv_output(as_numpy, lead, out, trailing, info, return_info):
+    """The tail of a solver: ``out`` [n, *trailing] and the per-image ``info`` tensors [n] in the leading shape, ndarrays if ndarrays
+    came in."""
+    out = out.reshape(*lead, *trailing)
+    info = {name: v.reshape(lead) for name, v in info.items()}
+    if as_numpy:
+        out, info = out.cpu().numpy(), {name: v.cpu().numpy() for name, v in info.items()}
+    return (out, info) if return_info else out
 
 
 def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, huber: float = TV_DEFAULT_HUBER,
@@ -346,23 +386,13 @@ def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, hube
     both of the leading shape."""
     who = "tv_superres"
     f0, f1, k = _block_kernel(who, kernel, factors)
-    lam, huber = float(lam), float(huber)
-    if not 0.0 <= lam < np.inf:
-        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
-    if not 0.0 <= huber < np.inf:
-        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
-    if int(n_iter) != n_iter or n_iter < 0:
-        raise ValueError(f"{who}: n_iter must be an integer >= 0 (got {n_iter!r})")
+    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter)
     as_numpy, h, w, lead = _block_input(who, lr)
     _hr_sides(who, h * f0, w * f1, f0, f1)
     extra = _weight_and_start(who, lr, as_numpy, lead, weight, (h, w), x0, (h * f0, w * f1))
     y = _block_batch(lr, as_numpy)
-    out, energy, change = ops.tvsr_solve(y, (f0, f1), k, lam, huber, int(n_iter), extra["weight"], extra["x0"])
-    out = out.reshape(*lead, h * f0, w * f1)
-    energy, change = energy.reshape(lead), change.reshape(lead)
-    if as_numpy:
-        out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
-    return (out, {"energy": energy, "change": change}) if return_info else out
+    out, energy, change = ops.tvsr_solve(y, (f0, f1), k, lam, huber, n_iter, extra["weight"], extra["x0"])
+    return _tv_output(as_numpy, lead, out, (h * f0, w * f1), {"energy": energy, "change": change}, return_info)
 
 
 TVJ_DEFAULT_LAMBDA, TVJ_DEFAULT_HUBER, TVJ_DEFAULT_ITERS = 0.048, 0.01, 300    # the sweep of DESIGN.md 4q (ADC RMSE, noise 0.02)
@@ -404,13 +434,7 @@ def tv_superres_joint(lr, factors, kernel="mean", lam: float = TVJ_DEFAULT_LAMBD
     launch for the whole batch, one workgroup per group (``inr_tvj_solve2d``).  There is no CPU fallback."""
     who = "tv_superres_joint"
     f0, f1, k = _block_kernel(who, kernel, factors)
-    lam, huber = float(lam), float(huber)
-    if not 0.0 <= lam < np.inf:
-        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
-    if not 0.0 <= huber < np.inf:
-        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
-    if int(n_iter) != n_iter or n_iter < 0:
-        raise ValueError(f"{who}: n_iter must be an integer >= 0 (got {n_iter!r})")
+    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter)
     if coupling not in ("joint", "none"):
         raise ValueError(f"{who}: coupling must be 'joint' or 'none' (got {coupling!r})")
     as_numpy = _fourier_input(who, lr)
@@ -427,32 +451,10 @@ def tv_superres_joint(lr, factors, kernel="mean", lam: float = TVJ_DEFAULT_LAMBD
             raise ValueError(f"{who}: channel_weights are {C} finite values within [0, 1] (got {mu.tolist()}); larger weights are a "
                              f"rescaled lam and huber")
         mu = mu.tolist()
-    extra = {}
-    for name, value, shape in (("weight", weight, (C, h, w)), ("x0", x0, (C, h * f0, w * f1))):
-        if value is None:
-            extra[name] = None
-            continue
-        if isinstance(value, np.ndarray) != as_numpy:
-            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
-        _fourier_input(who, value)
-        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
-            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
-        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
-            raise ValueError(f"{who}: weight must be finite and >= 0")
-        extra[name] = value
-
-    def groups(value):
-        t = torch.from_numpy(np.ascontiguousarray(value, dtype=np.float64)).to(ops.require_gpu()) if as_numpy else value
-        return t.reshape(-1, *t.shape[-3:]).contiguous()
-
-    y = groups(lr)
-    extra = {name: None if value is None else groups(value) for name, value in extra.items()}
-    out, energy, change = ops.tvj_solve(y, (f0, f1), k, mu, lam, huber, coupling, int(n_iter), extra["weight"], extra["x0"])
-    out = out.reshape(*lead, C, h * f0, w * f1)
-    energy, change = energy.reshape(lead), change.reshape(lead)
-    if as_numpy:
-        out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
-    return (out, {"energy": energy, "change": change}) if return_info else out
+    extra = _weight_and_start(who, lr, as_numpy, lead, weight, (C, h, w), x0, (C, h * f0, w * f1))
+    y = _device_batch(lr, as_numpy, 3)
+    out, energy, change = ops.tvj_solve(y, (f0, f1), k, mu, lam, huber, coupling, n_iter, extra["weight"], extra["x0"])
+    return _tv_output(as_numpy, lead, out, (C, h * f0, w * f1), {"energy": energy, "change": change}, return_info)
 
 
 TGV_DEFAULT_LAMBDA, TGV_DEFAULT_RATIO, TGV_DEFAULT_HUBER, TGV_DEFAULT_ITERS = 0.005, 0.5, 0.0, 300   # the sweep of DESIGN.md 4r
@@ -470,28 +472,21 @@ def tgv_superres(lr, factors, kernel="mean", lam: float = TGV_DEFAULT_LAMBDA, ra
     the last iteration), both of the leading shape, and ``v`` [..., 2, H, W]."""
     who = "tgv_superres"
     f0, f1, k = _block_kernel(who, kernel, factors)
-    lam, ratio, huber = float(lam), float(ratio), float(huber)
-    if not 0.0 <= lam < np.inf:
-        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    ratio = float(ratio)
+    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter)
     if not 0.0 < ratio < np.inf:
         raise ValueError(f"{who}: ratio must be finite and > 0 (got {ratio!r})")
-    if not 0.0 <= huber < np.inf:
-        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
-    if int(n_iter) != n_iter or n_iter < 0:
-        raise ValueError(f"{who}: n_iter must be an integer >= 0 (got {n_iter!r})")
     as_numpy, h, w, lead = _block_input(who, lr)
     _hr_sides(who, h * f0, w * f1, f0, f1)
     extra = _weight_and_start(who, lr, as_numpy, lead, weight, (h, w), x0, (h * f0, w * f1))
     y = _block_batch(lr, as_numpy)
-    out, v, energy, change = ops.tgv_solve(y, (f0, f1), k, lam, ratio, huber, int(n_iter), extra["weight"], extra["x0"],
-                                           want_v=return_info)
-    out = out.reshape(*lead, h * f0, w * f1)
+    out, v, energy, change = ops.tgv_solve(y, (f0, f1), k, lam, ratio, huber, n_iter, extra["weight"], extra["x0"], want_v=return_info)
     if not return_info:
-        return out.cpu().numpy() if as_numpy else out
-    v, energy, change = v.reshape(*lead, 2, h * f0, w * f1), energy.reshape(lead), change.reshape(lead)
-    if as_numpy:
-        out, v, energy, change = out.cpu().numpy(), v.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
-    return out, {"energy": energy, "change": change, "v": v}
+        return _tv_output(as_numpy, lead, out, (h * f0, w * f1), {}, False)
+    out, info = _tv_output(as_numpy, lead, out, (h * f0, w * f1), {"energy": energy, "change": change}, True)
+    v = v.reshape(*lead, 2, h * f0, w * f1)
+    info["v"] = v.cpu().numpy() if as_numpy else v
+    return out, info
 
 
 TVMF_DEFAULT_LAMBDA,TVMF_DEFAULT_HUBER, TVMF_DEFAULT_ITERS = 0.01, 0.03, 300  # the sweep of DESIGN.md 4n (8 frames, noise 0.02)
@@ -585,13 +580,7 @@ def tv_superres_multi(frames, factors, shifts, kernel="mean", lam: float = TVMF_
     (max |x' - x| of the last iteration) and ``valid_fraction`` (the valid share of the data), each of the leading shape."""
     who = "tv_superres_multi"
     f0, f1, k = _block_kernel(who, kernel, factors)
-    lam, huber = float(lam), float(huber)
-    if not 0.0 <= lam < np.inf:
-        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
-    if not 0.0 <= huber < np.inf:
-        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
-    if int(n_iter) != n_iter or not 0 <= n_iter <= ops.TVSR3D_MAX_ITER:
-        raise ValueError(f"{who}: n_iter must be an integer in 0 .. {ops.TVSR3D_MAX_ITER} (got {n_iter!r})")
+    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER, "in 0 ..")
     as_numpy, h, w, lead = _block_input(who, frames, "frames")
     if len(lead) < 1:
         raise ValueError(f"{who} needs at least 3-D frames [..., K, h, w]")
@@ -599,29 +588,11 @@ def tv_superres_multi(frames, factors, shifts, kernel="mean", lam: float = TVMF_
     _frame_count(who, K)
     _hr_sides(who, h * f0, w * f1, f0, f1)
     _shift_input(who, shifts, lead, K)
-    extra = {}
-    for name, value, shape in (("weight", weight, lead + (K, h, w)), ("x0", x0, lead + (h * f0, w * f1))):
-        if value is None:
-            extra[name] = None
-            continue
-        if isinstance(value, np.ndarray) != as_numpy:
-            raise TypeError(f"{who}: {name} must be given like frames ({'an ndarray' if as_numpy else 'a device tensor'})")
-        _fourier_input(who, value)
-        if tuple(value.shape) != shape or (not as_numpy and value.dtype != frames.dtype):
-            raise ValueError(f"{who}: {name} must have shape {shape} and the type of frames (got {tuple(value.shape)}, {value.dtype})")
-        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
-            raise ValueError(f"{who}: weight must be finite and >= 0")
-        extra[name] = value
-    y = _block_batch(frames, as_numpy).reshape(-1, K, h, w)
-    wt = None if extra["weight"] is None else _block_batch(extra["weight"], as_numpy).reshape(-1, K, h, w)
-    start = None if extra["x0"] is None else _block_batch(extra["x0"], as_numpy)
-    out, energy, change, valid = ops.tvmf_solve(y, _shift_batch(shifts, y.shape[0], y.device), (f0, f1), k, lam, huber, int(n_iter), wt,
-                                                start)
-    out = out.reshape(*lead, h * f0, w * f1)
-    info = {"energy": energy.reshape(lead), "change": change.reshape(lead), "valid_fraction": valid.reshape(lead)}
-    if as_numpy:
-        out, info = out.cpu().numpy(), {name: v.cpu().numpy() for name, v in info.items()}
-    return (out, info) if return_info else out
+    extra = _weight_and_start(who, frames, as_numpy, lead, weight, (K, h, w), x0, (h * f0, w * f1), like="frames")
+    y = _device_batch(frames, as_numpy, 3)
+    out, energy, change, valid = ops.tvmf_solve(y, _shift_batch(shifts, y.shape[0], y.device), (f0, f1), k, lam, huber, n_iter,
+                                                extra["weight"], extra["x0"])
+    return _tv_output(as_numpy, lead, out, (h * f0, w * f1), {"energy": energy, "change": change, "valid_fraction": valid}, return_info)
 
 
 def estimate_shifts(frames, factors, upsample: int = 4, max_shift=None, reference: int = 0):
@@ -734,8 +705,7 @@ def _volume_input(who, volume, name="input"):
 
 def _volume_batch(volume, as_numpy):
     """-> the device tensor [n, slices, rows, columns] (an ndarray as float64)."""
-    x = torch.from_numpy(np.ascontiguousarray(volume, dtype=np.float64)).to(ops.require_gpu()) if as_numpy else volume
-    return x.reshape(-1, *x.shape[-3:]).contiguous()
+    return _device_batch(volume, as_numpy, 3)
 
 
 def _hr_sides3d(who, hr, f):
@@ -784,43 +754,15 @@ def tv_superres3d(lr, factors, kernel="mean", lam: float = TV3D_DEFAULT_LAMBDA, 
     ``return_info``: also a dict with ``energy`` and ``change``, both of the leading shape."""
     who = "tv_superres3d"
     f, k = _block_kernel3d(who, kernel, factors)
-    lam, huber = float(lam), float(huber)
-    if not 0.0 <= lam < np.inf:
-        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
-    if not 0.0 <= huber < np.inf:
-        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
-    if int(n_iter) != n_iter or not 0 <= n_iter <= ops.TVSR3D_MAX_ITER:
-        raise ValueError(f"{who}: n_iter must be an integer 0 .. {ops.TVSR3D_MAX_ITER} (got {n_iter!r})")
-    try:
-        g = tuple(float(v) for v in grad_weights)
-    except (TypeError, ValueError):
-        g = ()
-    if len(g) != 3 or not all(0.0 <= v < np.inf for v in g):
-        raise ValueError(f"{who}: grad_weights are (g0, g1, g2), finite and >= 0 (got {grad_weights!r})")
+    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER)
+    g = _grad_weights(who, grad_weights)
     as_numpy, lo, lead = _volume_input(who, lr)
     hr = tuple(s * v for s, v in zip(lo, f))
     _hr_sides3d(who, hr, f)
-    extra = {}
-    for name, value, shape in (("weight", weight, lo), ("x0", x0, hr)):
-        if value is None:
-            extra[name] = None
-            continue
-        if isinstance(value, np.ndarray) != as_numpy:
-            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
-        _fourier_input(who, value)
-        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
-            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
-        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
-            raise ValueError(f"{who}: weight must be finite and >= 0")
-        extra[name] = value
+    extra = _weight_and_start(who, lr, as_numpy, lead, weight, lo, x0, hr)
     y = _volume_batch(lr, as_numpy)
-    extra = {name: None if value is None else _volume_batch(value, as_numpy) for name, value in extra.items()}
-    out, energy, change = ops.tvsr_solve3d(y, f, k, lam, huber, int(n_iter), g, extra["weight"], extra["x0"])
-    out = out.reshape(*lead, *hr)
-    energy, change = energy.reshape(lead), change.reshape(lead)
-    if as_numpy:
-        out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
-    return (out, {"energy": energy, "change": change}) if return_info else out
+    out, energy, change = ops.tvsr_solve3d(y, f, k, lam, huber, n_iter, g, extra["weight"], extra["x0"])
+    return _tv_output(as_numpy, lead, out, hr, {"energy": energy, "change": change}, return_info)
 
 
 TVMS_DEFAULT_LAMBDA, TVMS_DEFAULT_HUBER, TVMS_DEFAULT_ITERS = 0.01, 0.01, 300  # the sweep of DESIGN.md 4o (3 stacks, noise 0.02)
@@ -1008,19 +950,8 @@ def tv_superres_stacks(stacks, geometries, hr_shape, lam: float = TVMS_DEFAULT_L
     if len(stacks) != len(geos):
         raise ValueError(f"{who}: {len(stacks)} stacks for {len(geos)} geometries")
     hr = _hr_shape(who, hr_shape)
-    lam, huber = float(lam), float(huber)
-    if not 0.0 <= lam < np.inf:
-        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
-    if not 0.0 <= huber < np.inf:
-        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
-    if int(n_iter) != n_iter or not 0 <= n_iter <= ops.TVSR3D_MAX_ITER:
-        raise ValueError(f"{who}: n_iter must be an integer 0 .. {ops.TVSR3D_MAX_ITER} (got {n_iter!r})")
-    try:
-        g = tuple(float(v) for v in grad_weights)
-    except (TypeError, ValueError):
-        g = ()
-    if len(g) != 3 or not all(0.0 <= v < np.inf for v in g):
-        raise ValueError(f"{who}: grad_weights are (g0, g1, g2), finite and >= 0 (got {grad_weights!r})")
+    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER)
+    g = _grad_weights(who, grad_weights)
     as_numpy, _, lead = _volume_input(who, stacks[0], "stacks")
     table = []
     for s, (y, geo) in enumerate(zip(stacks, geos)):
@@ -1057,12 +988,8 @@ def tv_superres_stacks(stacks, geometries, hr_shape, lam: float = TVMS_DEFAULT_L
     y = rows(stacks)
     wt = None if weight is None else rows(weight)
     start = None if x0 is None else _volume_batch(x0, as_numpy)
-    out, energy, change, valid = ops.tvms_solve(y, table, hr, lam, huber, int(n_iter), g, wt, start)
-    out = out.reshape(*lead, *hr)
-    info = {"energy": energy.reshape(lead), "change": change.reshape(lead), "valid_fraction": valid.reshape(lead)}
-    if as_numpy:
-        out, info = out.cpu().numpy(), {name: v.cpu().numpy() for name, v in info.items()}
-    return (out, info) if return_info else out
+    out, energy, change, valid = ops.tvms_solve(y, table, hr, lam, huber, n_iter, g, wt, start)
+    return _tv_output(as_numpy, lead, out, hr, {"energy": energy, "change": change, "valid_fraction": valid}, return_info)
 
 
 # the sweep of DESIGN.md 4p (k-space truncation and a Gaussian PSF, x2, noise 0.02 of a [0, 1] image)
@@ -1204,37 +1131,14 @@ def tv_superres_operator(lr, operators, lam: float = TVOP_DEFAULT_LAMBDA, huber:
     ``change`` (max |x' - x| of the last iteration), both of the leading shape."""
     who = "tv_superres_operator"
     pair, H, W, h, w = _operator_pair(who, operators)
-    lam, huber = float(lam), float(huber)
-    if not 0.0 <= lam < np.inf:
-        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
-    if not 0.0 <= huber < np.inf:
-        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
-    if int(n_iter) != n_iter or not 0 <= n_iter <= ops.TVSR3D_MAX_ITER:
-        raise ValueError(f"{who}: n_iter must be an integer in 0 .. {ops.TVSR3D_MAX_ITER} (got {n_iter!r})")
+    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER, "in 0 ..")
     as_numpy, rows, cols, lead = _block_input(who, lr, "lr")
     if (rows, cols) != (h, w):
         raise ValueError(f"{who}: the operators make LR images of {h} x {w} (got lr of {rows} x {cols})")
-    extra = {}
-    for name, value, shape in (("weight", weight, (h, w)), ("x0", x0, (H, W))):
-        if value is None:
-            extra[name] = None
-            continue
-        if isinstance(value, np.ndarray) != as_numpy:
-            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
-        _fourier_input(who, value)
-        if tuple(value.shape) != lead + shape or (not as_numpy and value.dtype != lr.dtype):
-            raise ValueError(f"{who}: {name} must have shape {lead + shape} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
-        if name == "weight" and as_numpy and not (np.isfinite(value).all() and (value >= 0).all()):
-            raise ValueError(f"{who}: weight must be finite and >= 0")
-        extra[name] = value
+    extra = _weight_and_start(who, lr, as_numpy, lead, weight, (h, w), x0, (H, W))
     y = _block_batch(lr, as_numpy)
-    extra = {name: None if value is None else _block_batch(value, as_numpy) for name, value in extra.items()}
-    out, energy, change = ops.tvop_solve(y, pair(), lam, huber, int(n_iter), extra["weight"], extra["x0"])
-    out = out.reshape(*lead, H, W)
-    energy, change = energy.reshape(lead), change.reshape(lead)
-    if as_numpy:
-        out, energy, change = out.cpu().numpy(), energy.cpu().numpy(), change.cpu().numpy()
-    return (out, {"energy": energy, "change": change}) if return_info else out
+    out, energy, change = ops.tvop_solve(y, pair(), lam, huber, n_iter, extra["weight"], extra["x0"])
+    return _tv_output(as_numpy, lead, out, (H, W), {"energy": energy, "change": change}, return_info)
 
 
 def resize_z(arr, new_size: int = 128, kind: str = 'cubic'):

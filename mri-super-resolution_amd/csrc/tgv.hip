@@ -42,6 +42,9 @@
 // energy: E at the returned fp64 (x, v); every thread adds its LR blocks and then its HR pixels in ascending order (the first-order
 // terms into one sum, the second-order terms into another, scaled by lam1 and lam0 and added in that order), wave_sum adds the lanes,
 // thread 0 the 16 waves in ascending order: tvsr.hip's order, no float atomics.  change: max |x' - x| of the last iteration, on x only.
+//
+// The start of x and xbar, the block items of the primal phase, the data term and the reduction of energy and change are tv_block.h's,
+// the ones tvsr.hip runs (which is why lambda = 0 gives its bits); those helpers hold no barrier, the two of an iteration stand below.
 #include "tv_block.h"
 
 namespace inr {
@@ -73,11 +76,9 @@ __global__ void __launch_bounds__(TV_THREADS) tgv_solve_kernel(T* out, T* v_out,
         double* r01 = r11 + HW;
         const T* yi = y + (size_t)img * hw;
         const T* wi = weight ? weight + (size_t)img * hw : nullptr;
+        const T* x0i = x0 ? x0 + (size_t)img * HW : nullptr;
         for (int e = tid; e < HW; e += TV_THREADS) {
-            const int i = e / W, j = e - i * W;
-            const double v = x0 ? (double)x0[(size_t)img * HW + e] : (double)yi[(i / s.f0) * s.w + j / s.f1];
-            x[e] = v;
-            xbar[e] = v;
+            tv_start_pixel(x, xbar, x0i, yi, s, e);
             v0[e] = 0.0;
             v1[e] = 0.0;
             vbar0[e] = 0.0;
@@ -129,34 +130,8 @@ __global__ void __launch_bounds__(TV_THREADS) tgv_solve_kernel(T* out, T* v_out,
             }
             __syncthreads();   // barrier 1: p and r are complete
             const bool last = it + 1 == n_iter;
-            for (int blk = tid; blk < hw; blk += TV_THREADS) {
-                const int bi = blk / s.w, bj = blk - bi * s.w;
-                double acc = 0.0;
-                for (int a = 0; a < s.f0; ++a)
-                    for (int b = 0; b < s.f1; ++b) {
-                        const int i = bi * s.f0 + a, j = bj * s.f1 + b, e = i * W + j;
-                        double d = 0.0;
-                        if (i + 1 < s.H) d += p0[e];
-                        if (i > 0) d -= p0[e - W];
-                        if (j + 1 < W) d += p1[e];
-                        if (j > 0) d -= p1[e - 1];
-                        const double u = x[e] + tau * d;
-                        xbar[e] = u;   // u waits here for the second pass: nobody else reads xbar in this phase
-                        acc += ks[a * s.f1 + b] * u;
-                    }
-                const double wv = wi ? (double)wi[blk] : 1.0;
-                // a missing datum (w = 0) takes no part, whatever y holds there
-                const double r = wv == 0.0 ? 0.0 : tau * wv / (1.0 + tau * wv * kb.k2) * (acc - (double)yi[blk]);
-                for (int a = 0; a < s.f0; ++a)
-                    for (int b = 0; b < s.f1; ++b) {
-                        const int e = (bi * s.f0 + a) * W + bj * s.f1 + b;
-                        const double xo = x[e];
-                        const double xn = xbar[e] - ks[a * s.f1 + b] * r;
-                        xbar[e] = 2.0 * xn - xo;
-                        x[e] = xn;
-                        if (last) ch = fmax(ch, fabs(xn - xo));
-                    }
-            }
+            for (int blk = tid; blk < hw; blk += TV_THREADS)   // the block items: tvsr.hip's step with u in place of v
+                tv_primal_block(x, xbar, p0, p1, ks, s, kb.k2, yi, wi, blk, 1.0, tau, last, ch);
             if (lam1 > 0.0)
                 for (int e = tid; e < HW; e += TV_THREADS) {
                     const int i = e / W, j = e - i * W;
@@ -182,14 +157,7 @@ __global__ void __launch_bounds__(TV_THREADS) tgv_solve_kernel(T* out, T* v_out,
         }
         // the objective at (x, v), the image and the field
         double en = 0.0;
-        for (int blk = tid; blk < hw; blk += TV_THREADS) {
-            const int bi = blk / s.w, bj = blk - bi * s.w;
-            const double wv = wi ? (double)wi[blk] : 1.0;
-            if (wv != 0.0) {
-                const double r = tv_block_sum(x, ks, s, bi, bj) - (double)yi[blk];
-                en += 0.5 * wv * r * r;
-            }
-        }
+        for (int blk = tid; blk < hw; blk += TV_THREADS) tv_add_data_term(en, x, ks, s, yi, wi, blk);
         double reg1 = 0.0, reg0 = 0.0;
         for (int e = tid; e < HW; e += TV_THREADS) {
             const int i = e / W, j = e - i * W;
@@ -216,39 +184,12 @@ __global__ void __launch_bounds__(TV_THREADS) tgv_solve_kernel(T* out, T* v_out,
             en += lam1 * reg1;
             en += lam0 * reg0;
         }
-        en = wave_sum(en);
-        if ((tid & 63) == 0) red[tid >> 6] = en;
-        __syncthreads();
-        if (tid == 0 && energy) {
-            double sum = 0.0;
-            for (int k = 0; k < TV_WAVES; ++k) sum += red[k];
-            energy[img] = sum;
-        }
-        __syncthreads();
-        ch = wave_max(ch);
-        if ((tid & 63) == 0) red[tid >> 6] = ch;
-        __syncthreads();
-        if (tid == 0 && change) {
-            double m = 0.0;
-            for (int k = 0; k < TV_WAVES; ++k) m = fmax(m, red[k]);
-            change[img] = m;
-        }
-        __syncthreads();   // red is free for the next image
+        tv_store_energy_change(en, ch, red, energy, change, (size_t)img);   // ends with a barrier: red is free for the next image
     }
 }
 
 // the workspace: the 11 fields of every image.  base == null: `total` only
-struct TgvView {
-    double* state;
-    size_t total;
-};
-TgvView tgv_view(int n_images, int H, int W, void* base) {
-    TgvView v;
-    WsCarver c(base, 16);
-    v.state = c.take<double>((size_t)(n_images > 0 ? n_images : 1) * TGV_FIELDS * (size_t)H * (size_t)W);
-    v.total = c.bytes();
-    return v;
-}
+TvStateView tgv_view(int n_images, int H, int W, void* base) { return tv_state_view(n_images, TGV_FIELDS, H, W, base); }
 
 template <typename T>
 int tgv_solve(const char* who, T* out, T* v_out, double* energy, double* change, const T* y, const T* weight, const T* x0, int n_images,
@@ -258,14 +199,12 @@ int tgv_solve(const char* who, T* out, T* v_out, double* energy, double* change,
     TvShape s;
     TvBlock kb;
     if (int rc = tv_shape_check(who, n_images, H, W, f0, f1, &s)) return rc;
-    INR_REQUIRE(n_iter >= 0, INR_E_INVALID, "%s: n_iter must be >= 0 (got %d)", who, n_iter);
-    INR_REQUIRE(std::isfinite(lam) && lam >= 0.0, INR_E_INVALID, "%s: lambda must be finite and >= 0 (got %g)", who, lam);
+    if (int rc = tv_params_check(who, lam, alpha, n_iter, -1)) return rc;
     INR_REQUIRE(std::isfinite(ratio) && ratio > 0.0, INR_E_INVALID, "%s: ratio must be finite and > 0 (got %g)", who, ratio);
-    INR_REQUIRE(std::isfinite(alpha) && alpha >= 0.0, INR_E_INVALID, "%s: alpha must be finite and >= 0 (got %g)", who, alpha);
     if (int rc = tv_block_check(who, kernel, f0, f1, &kb)) return rc;
     if (int rc = check_ws_doubles(who, workspace, workspace_doubles, tgv_view(n_images, H, W, nullptr).total)) return rc;
     if (n_images == 0) return 0;
-    const TgvView v = tgv_view(n_images, H, W, workspace);
+    const TvStateView v = tgv_view(n_images, H, W, workspace);
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL((tgv_solve_kernel<T>), dim3((unsigned)(n_images < TV_MAX_GRID ? n_images : TV_MAX_GRID)), dim3(TV_THREADS), 0, st,
                        out, v_out, energy, change, y, weight, x0, v.state, n_images, s, kb, lam, ratio * lam, alpha, n_iter);

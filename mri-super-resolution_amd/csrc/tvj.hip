@@ -35,6 +35,9 @@
 // energy: E at the returned fp64 x; every thread adds its data terms in ascending (channel, block), then its pixels in ascending order
 // (joint: one term per pixel, the sum over c in ascending c; none: the channels of a pixel in ascending c), wave_sum, thread 0 over the
 // 16 waves: for C = 1 tvsr.hip's order.  change: max |x' - x| of the last iteration over all channels.
+//
+// The start, the primal block step, the data term and the reduction of energy and change are tv_block.h's, the ones tvsr.hip runs:
+// each works on ONE channel's pointers with int indices (H W <= 2^20); the offsets between channels and groups stay size_t here.
 #include "tv_block.h"
 
 namespace inr {
@@ -69,10 +72,7 @@ __global__ void __launch_bounds__(TV_THREADS) tvj_solve_kernel(T* out, double* e
         const T* wg = weight ? weight + g * Chw : nullptr;
         for (size_t t = tid; t < CHW; t += TV_THREADS) {
             const size_t c = t / HW, e = t - c * HW;
-            const size_t i = e / W, j = e - i * W;
-            const double v = x0 ? (double)x0[g * CHW + t] : (double)yg[c * hw + (i / s.f0) * s.w + j / s.f1];
-            x[t] = v;
-            xbar[t] = v;
+            tv_start_pixel(x + c * HW, xbar + c * HW, x0 ? x0 + g * CHW + c * HW : nullptr, yg + c * hw, s, (int)e);
             p0[t] = 0.0;
             p1[t] = 0.0;
         }
@@ -119,37 +119,8 @@ __global__ void __launch_bounds__(TV_THREADS) tvj_solve_kernel(T* out, double* e
             const bool last = it + 1 == n_iter;
             for (size_t item = tid; item < Chw; item += TV_THREADS) {
                 const size_t c = item / hw, blk = item - c * hw;
-                const size_t bi = blk / s.w, bj = blk - bi * s.w;
-                double* xc = x + c * HW;
-                double* xbc = xbar + c * HW;
-                const double* p0c = p0 + c * HW;
-                const double* p1c = p1 + c * HW;
-                const double m = mu[c];
-                double acc = 0.0;
-                for (int a = 0; a < s.f0; ++a)
-                    for (int b = 0; b < s.f1; ++b) {
-                        const size_t i = bi * s.f0 + a, j = bj * s.f1 + b, e = i * W + j;
-                        double d = 0.0;
-                        if (i + 1 < (size_t)s.H) d += p0c[e];
-                        if (i > 0) d -= p0c[e - W];
-                        if (j + 1 < W) d += p1c[e];
-                        if (j > 0) d -= p1c[e - 1];
-                        const double v = xc[e] + tau * (m * d);
-                        xbc[e] = v;   // v waits here for the second pass: nobody else reads this block of xbar in this phase
-                        acc += ks[a * s.f1 + b] * v;
-                    }
-                const double wv = wg ? (double)wg[item] : 1.0;
-                // a missing datum (w = 0) takes no part, whatever y holds there
-                const double r = wv == 0.0 ? 0.0 : tau * wv / (1.0 + tau * wv * kb.k2) * (acc - (double)yg[item]);
-                for (int a = 0; a < s.f0; ++a)
-                    for (int b = 0; b < s.f1; ++b) {
-                        const size_t e = (bi * s.f0 + a) * W + bj * s.f1 + b;
-                        const double xo = xc[e];
-                        const double xn = xbc[e] - ks[a * s.f1 + b] * r;
-                        xbc[e] = 2.0 * xn - xo;
-                        xc[e] = xn;
-                        if (last) ch = fmax(ch, fabs(xn - xo));
-                    }
+                tv_primal_block(x + c * HW, xbar + c * HW, p0 + c * HW, p1 + c * HW, ks, s, kb.k2, yg + c * hw,
+                                wg ? wg + c * hw : nullptr, (int)blk, mu[c], tau, last, ch);
             }
             __syncthreads();   // barrier 2: x and xbar are complete
         }
@@ -157,12 +128,7 @@ __global__ void __launch_bounds__(TV_THREADS) tvj_solve_kernel(T* out, double* e
         double en = 0.0;
         for (size_t item = tid; item < Chw; item += TV_THREADS) {
             const size_t c = item / hw, blk = item - c * hw;
-            const size_t bi = blk / s.w, bj = blk - bi * s.w;
-            const double wv = wg ? (double)wg[item] : 1.0;
-            if (wv != 0.0) {
-                const double r = tv_block_sum(x + c * HW, ks, s, (int)bi, (int)bj) - (double)yg[item];
-                en += 0.5 * wv * r * r;
-            }
+            tv_add_data_term(en, x + c * HW, ks, s, yg + c * hw, wg ? wg + c * hw : nullptr, (int)blk);
         }
         double reg = 0.0;
         for (size_t e = tid; e < HW; e += TV_THREADS) {
@@ -185,24 +151,7 @@ __global__ void __launch_bounds__(TV_THREADS) tvj_solve_kernel(T* out, double* e
             if (lam > 0.0 && joint) reg += tv_huber(sqrt(ss), alpha);
         }
         if (lam > 0.0) en += lam * reg;
-        en = wave_sum(en);
-        if ((tid & 63) == 0) red[tid >> 6] = en;
-        __syncthreads();
-        if (tid == 0 && energy) {
-            double sum = 0.0;
-            for (int k = 0; k < TV_WAVES; ++k) sum += red[k];
-            energy[g] = sum;
-        }
-        __syncthreads();
-        ch = wave_max(ch);
-        if ((tid & 63) == 0) red[tid >> 6] = ch;
-        __syncthreads();
-        if (tid == 0 && change) {
-            double m = 0.0;
-            for (int k = 0; k < TV_WAVES; ++k) m = fmax(m, red[k]);
-            change[g] = m;
-        }
-        __syncthreads();   // red is free for the next group
+        tv_store_energy_change(en, ch, red, energy, change, g);   // ends with a barrier: red is free for the next group
     }
 }
 
@@ -215,17 +164,7 @@ int tvj_group_check(const char* who, int n_groups, int channels) {
 }
 
 // the workspace: the state x | xbar | p0 | p1, each [C][H][W], of every group.  base == null: `total` only
-struct TvjView {
-    double* state;
-    size_t total;
-};
-TvjView tvj_view(int n_groups, int C, int H, int W, void* base) {
-    TvjView v;
-    WsCarver c(base, 16);
-    v.state = c.take<double>((size_t)(n_groups > 0 ? n_groups : 1) * 4 * (size_t)C * (size_t)H * (size_t)W);
-    v.total = c.bytes();
-    return v;
-}
+TvStateView tvj_view(int n_groups, int C, int H, int W, void* base) { return tv_state_view(n_groups, 4 * C, H, W, base); }
 
 template <typename T>
 int tvj_solve(const char* who, T* out, double* energy, double* change, const T* y, const T* weight, const T* x0, int n_groups, int C,
@@ -237,9 +176,7 @@ int tvj_solve(const char* who, T* out, double* energy, double* change, const T* 
     TvjWeights cw;
     if (int rc = tvj_group_check(who, n_groups, C)) return rc;
     if (int rc = tv_shape_check(who, n_groups, H, W, f0, f1, &s)) return rc;
-    INR_REQUIRE(n_iter >= 0, INR_E_INVALID, "%s: n_iter must be >= 0 (got %d)", who, n_iter);
-    INR_REQUIRE(std::isfinite(lam) && lam >= 0.0, INR_E_INVALID, "%s: lambda must be finite and >= 0 (got %g)", who, lam);
-    INR_REQUIRE(std::isfinite(alpha) && alpha >= 0.0, INR_E_INVALID, "%s: alpha must be finite and >= 0 (got %g)", who, alpha);
+    if (int rc = tv_params_check(who, lam, alpha, n_iter, -1)) return rc;
     INR_REQUIRE(coupling == 0 || coupling == 1, INR_E_INVALID, "%s: coupling is 0 (none) or 1 (joint) (got %d)", who, coupling);
     if (int rc = tv_block_check(who, kernel, f0, f1, &kb)) return rc;
     for (int c = 0; c < TVJ_MAX_CHANNELS; ++c) {
@@ -251,7 +188,7 @@ int tvj_solve(const char* who, T* out, double* energy, double* change, const T* 
     }
     if (int rc = check_ws_doubles(who, workspace, workspace_doubles, tvj_view(n_groups, C, H, W, nullptr).total)) return rc;
     if (n_groups == 0) return 0;
-    const TvjView v = tvj_view(n_groups, C, H, W, workspace);
+    const TvStateView v = tvj_view(n_groups, C, H, W, workspace);
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL((tvj_solve_kernel<T>), dim3((unsigned)(n_groups < TV_MAX_GRID ? n_groups : TV_MAX_GRID)), dim3(TV_THREADS), 0, st,
                        out, energy, change, y, weight, x0, v.state, n_groups, C, s, kb, cw, lam, alpha, coupling, n_iter);

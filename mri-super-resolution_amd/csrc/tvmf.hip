@@ -40,30 +40,23 @@
 //
 // An image's HR pixels followed by its K h w data are cut into "parts" of MF_PART elements; the partials are per PART, and thread t
 // of the finish adds partials t, t + 256, ... in ascending order, so the bits of energy and change depend on the shape alone: not on
-// the grid (capped at MF_MAX_GRID, or by the test-only inr_debug_set(32, .)), the stream, or the place in a batch.  All arithmetic is
+// the grid (capped at TV_STRIDE_MAX_GRID, or by the test-only inr_debug_set(32, .)), the stream, or the place in a batch.  All arithmetic is
 // fp64; the fp32 entry converts at load and rounds once at the store.  The unit is compiled with -ffp-contract=off (_build.py), so
 // the two entries, whose kernels differ in their loads and stores only, agree bit for bit.
-#include <cmath>
-
-#include "internal.h"
+//
+// The block kernel with its check and the size refusals are tv_block.h's (TvBlock carries c beside |k|^2); the Huber function, the
+// floor division, the grids, the refusals of the scalar parameters and the finish kernel are tv_shared.h's, which tv_block.h includes.
+#include "tv_block.h"
 
 namespace inr {
 namespace {
 
 constexpr int MF_THREADS = 256;
 constexpr int MF_MAX_FACTOR = INR_TVSR_MAX_FACTOR;
-constexpr int MF_MAX_SIDE = INR_TVSR_MAX_SIDE;
 constexpr int MF_MAX_FRAMES = INR_TVMF_MAX_FRAMES;
-constexpr int MF_MAX_GRID = 2048;
 constexpr int MF_PART = 4 * MF_THREADS;                                  // elements of a part: four per thread
 constexpr int MF_KE_MAX = (MF_MAX_FACTOR + 1) * (MF_MAX_FACTOR + 1);
 constexpr double MF_MAX_SHIFT = 1048576.0;                               // 2^20 HR pixels
-
-// the block kernel, by value in the kernel arguments
-struct MfBlock {
-    double k[MF_MAX_FACTOR * MF_MAX_FACTOR];   // [f0][f1]
-    double c;                                   // (sum |k|) (max |k|)
-};
 
 struct MfShape {
     int H, W, h, w, f0, f1, K;
@@ -137,12 +130,6 @@ __device__ __forceinline__ double mf_apply(const double* x, const double* kek, c
     return acc;
 }
 
-// floor(u / f) for f > 0
-__device__ __forceinline__ int mf_floordiv(int u, int f) {
-    const int q = u / f;
-    return u - q * f < 0 ? q - 1 : q;
-}
-
 // sum_k (A_k^T r_k)[mi][mj]: r [K][h][w] of one image, geo [K][4], ke [K][(f0 + 1)(f1 + 1)]
 __device__ __forceinline__ double mf_gather(const double* r, const int* geo, const double* ke, const MfShape& s, int mi, int mj) {
     const int es = s.f1 + 1, ke_size = (s.f0 + 1) * es;
@@ -152,8 +139,8 @@ __device__ __forceinline__ double mf_gather(const double* r, const int* geo, con
         const int n0 = geo[4 * k], n1 = geo[4 * k + 1], flags = geo[4 * k + 2];
         if (!(flags & 1)) continue;
         const int ea = s.f0 + ((flags >> 1) & 1), eb = s.f1 + ((flags >> 2) & 1);
-        const int ih = mf_floordiv(mi - n0, s.f0), ah = mi - n0 - ih * s.f0;   // the last LR row that reaches mi, 0 <= ah < f0
-        const int jh = mf_floordiv(mj - n1, s.f1), bh = mj - n1 - jh * s.f1;
+        const int ih = tv_floordiv(mi - n0, s.f0), ah = mi - n0 - ih * s.f0;   // the last LR row that reaches mi, 0 <= ah < f0
+        const int jh = tv_floordiv(mj - n1, s.f1), bh = mj - n1 - jh * s.f1;
         const double* kek = ke + (size_t)k * ke_size;
         const double* rk = r + (size_t)k * hw;
         for (int di = ah + s.f0 < ea ? -1 : 0; di <= 0; ++di) {               // the row before reaches mi with its extra tap row only
@@ -167,11 +154,6 @@ __device__ __forceinline__ double mf_gather(const double* r, const int* geo, con
         }
     }
     return g;
-}
-
-__device__ __forceinline__ double mf_huber(double t, double alpha) {
-    if (alpha == 0.0) return t;
-    return t <= alpha ? t * t / (2.0 * alpha) : t - alpha / 2.0;
 }
 
 // the workspace: the state x | xbar | p0 | p1 of every image, q [n][K][h][w], the table ke [n][K][(f0 + 1)(f1 + 1)] and geo [n][K][4],
@@ -199,7 +181,7 @@ MfView mf_view(int n, const MfShape& s, void* base) {
 
 template <typename T>
 __global__ void __launch_bounds__(MF_THREADS) mf_init_kernel(MfView v, const T* y, const T* x0, const double* shifts, long long n, MfShape s,
-                                                             MfBlock kb) {
+                                                             TvBlock kb) {
     __shared__ double ks[MF_MAX_FACTOR * MF_MAX_FACTOR];
     if ((int)threadIdx.x < s.f0 * s.f1) ks[threadIdx.x] = kb.k[threadIdx.x];
     __syncthreads();
@@ -334,7 +316,7 @@ __global__ void __launch_bounds__(MF_THREADS) mf_final_kernel(T* out, MfView v, 
                 if (lam > 0.0) {
                     const double g0 = i + 1 < s.H ? x[e + s.W] - xe : 0.0;
                     const double g1 = j + 1 < s.W ? x[e + 1] - xe : 0.0;
-                    reg += mf_huber(sqrt(g0 * g0 + g1 * g1), alpha);
+                    reg += tv_huber(sqrt(g0 * g0 + g1 * g1), alpha);
                 }
                 if (n_iter > 0) ch = fmax(ch, fabs(diff[e]));
             } else if (u < HW + Khw) {
@@ -355,42 +337,12 @@ __global__ void __launch_bounds__(MF_THREADS) mf_final_kernel(T* out, MfView v, 
         if (lam > 0.0) en += lam * reg;
         en = block_sum_f64(en, red);
         cnt = block_sum_f64(cnt, red);
-        ch = wave_max(ch);
-        if ((tid & 63) == 0) red[tid >> 6] = ch;
-        __syncthreads();
+        ch = block_max_f64(ch, red);   // ends with a barrier: red is free for the next item
         if (tid == 0) {
             v.epart[item] = en;
             v.vpart[item] = cnt;
-            v.chpart[item] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+            v.chpart[item] = ch;
         }
-        __syncthreads();   // red is free for the next item
-    }
-}
-
-// energy / change / valid_fraction [n] from the partials [n][parts]: thread t adds (maximises) partials t, t + 256, ... in ascending
-// order, then the lanes by wave_sum's butterfly, then the four waves in order
-__global__ void __launch_bounds__(MF_THREADS) mf_finish_kernel(double* energy, double* change, double* valid_fraction, MfView v, long long n,
-                                                               MfShape s) {
-    __shared__ double red[MF_THREADS / 64];
-    const int tid = threadIdx.x;
-    for (long long img = blockIdx.x; img < n; img += gridDim.x) {
-        double en = 0.0, ch = 0.0, cnt = 0.0;
-        for (int p = tid; p < s.parts; p += MF_THREADS) {
-            en += v.epart[img * s.parts + p];
-            cnt += v.vpart[img * s.parts + p];
-            ch = fmax(ch, v.chpart[img * s.parts + p]);
-        }
-        en = block_sum_f64(en, red);
-        cnt = block_sum_f64(cnt, red);
-        ch = wave_max(ch);
-        if ((tid & 63) == 0) red[tid >> 6] = ch;
-        __syncthreads();
-        if (tid == 0) {
-            if (energy) energy[img] = en;
-            if (change) change[img] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-            if (valid_fraction) valid_fraction[img] = cnt / ((double)s.K * s.h * s.w);
-        }
-        __syncthreads();
     }
 }
 
@@ -398,7 +350,7 @@ __global__ void __launch_bounds__(MF_THREADS) mf_finish_kernel(double* energy, d
 // frame's ke in LDS
 __global__ void __launch_bounds__(MF_THREADS) mf_apply_kernel(double* __restrict__ out, unsigned char* __restrict__ valid,
                                                               const double* __restrict__ in, const double* __restrict__ shifts, long long n,
-                                                              MfShape s, MfBlock kb) {
+                                                              MfShape s, TvBlock kb) {
     __shared__ double ks[MF_MAX_FACTOR * MF_MAX_FACTOR];
     __shared__ double kes[MF_KE_MAX];
     const int tid = threadIdx.x;
@@ -423,7 +375,7 @@ __global__ void __launch_bounds__(MF_THREADS) mf_apply_kernel(double* __restrict
 
 // out [n][H][W] = sum_k A_k^T in [n][K][h][w]: one workgroup per 256 HR pixels of an image forms the image's table in LDS
 __global__ void __launch_bounds__(MF_THREADS) mf_adjoint_kernel(double* __restrict__ out, const double* __restrict__ in,
-                                                                const double* __restrict__ shifts, long long n, MfShape s, MfBlock kb,
+                                                                const double* __restrict__ shifts, long long n, MfShape s, TvBlock kb,
                                                                 int chunks) {
     __shared__ double ks[MF_MAX_FACTOR * MF_MAX_FACTOR];
     __shared__ double kes[MF_MAX_FRAMES * MF_KE_MAX];
@@ -455,46 +407,16 @@ __global__ void __launch_bounds__(MF_THREADS) mf_adjoint_kernel(double* __restri
 }
 
 int mf_shape_check(const char* who, int n, int K, int H, int W, int f0, int f1, MfShape* s) {
+    // n_images, then the frame count, then tv_block.h's refusals of the factors and the sizes: the order callers have always seen
     INR_REQUIRE(n >= 0, INR_E_INVALID, "%s: bad sizes (n_images = %d)", who, n);
     INR_REQUIRE(K >= 1 && K <= MF_MAX_FRAMES, INR_E_INVALID, "%s: frames per image are 1 .. %d (got %d)", who, MF_MAX_FRAMES, K);
-    INR_REQUIRE(f0 >= 1 && f0 <= MF_MAX_FACTOR && f1 >= 1 && f1 <= MF_MAX_FACTOR, INR_E_INVALID,
-                "%s: block factors are 1 .. %d per axis (got %d x %d)", who, MF_MAX_FACTOR, f0, f1);
-    INR_REQUIRE(H >= 1 && W >= 1 && H <= MF_MAX_SIDE && W <= MF_MAX_SIDE, INR_E_INVALID,
-                "%s: bad sizes (HR images of 1 .. %d samples per axis, got %d x %d)", who, MF_MAX_SIDE, H, W);
-    INR_REQUIRE(H % f0 == 0 && W % f1 == 0, INR_E_INVALID, "%s: the HR image %d x %d is no whole number of %d x %d blocks", who, H, W,
-                f0, f1);
-    MfShape v{H, W, H / f0, W / f1, f0, f1, K, 0};
+    TvShape b;
+    if (int rc = tv_shape_check(who, n, H, W, f0, f1, &b)) return rc;
+    MfShape v{H, W, b.h, b.w, f0, f1, K, 0};
     v.parts = (int)(((long long)H * W + (long long)K * v.h * v.w + MF_PART - 1) / MF_PART);   // <= 65 * 2^20 / 1,024
     *s = v;
     return 0;
 }
-
-// the caller's HOST kernel [f0][f1]: finite entries that sum to 1
-int mf_block_check(const char* who, const double* kernel, int f0, int f1, MfBlock* kb) {
-    INR_REQUIRE(kernel, INR_E_INVALID, "%s: null pointer (kernel)", who);
-    double sum = 0.0, l1 = 0.0, top = 0.0;
-    for (int t = 0; t < MF_MAX_FACTOR * MF_MAX_FACTOR; ++t) kb->k[t] = 0.0;
-    for (int t = 0; t < f0 * f1; ++t) {
-        INR_REQUIRE(std::isfinite(kernel[t]), INR_E_INVALID, "%s: the block kernel must be finite (entry %d is %g)", who, t, kernel[t]);
-        kb->k[t] = kernel[t];
-        sum += kernel[t];
-        l1 += std::fabs(kernel[t]);
-        top = std::fmax(top, std::fabs(kernel[t]));
-    }
-    INR_REQUIRE(std::isfinite(sum) && std::fabs(sum - 1.0) <= 1e-9, INR_E_INVALID, "%s: the block kernel must sum to 1 (got %.17g)", who,
-                sum);
-    kb->c = l1 * top;
-    return 0;
-}
-
-// grids: capped, with a stride loop in every kernel; inr_debug_set(32, .) caps them further (tests walk the stride on small images)
-unsigned mf_grid(long long workgroups) {
-    long long g = workgroups < 1 ? 1 : (workgroups > MF_MAX_GRID ? MF_MAX_GRID : workgroups);
-    const int cap = g_hp_grid_cap;
-    if (cap > 0 && g > cap) g = cap;
-    return (unsigned)g;
-}
-unsigned mf_thread_grid(long long threads) { return mf_grid((threads + MF_THREADS - 1) / MF_THREADS); }
 
 template <typename T>
 int mf_solve(const char* who, T* out, double* energy, double* change, double* valid_fraction, const T* y, const double* shifts,
@@ -503,39 +425,32 @@ int mf_solve(const char* who, T* out, double* energy, double* change, double* va
     INR_REQUIRE(out && y, INR_E_INVALID, "%s: null pointer", who);
     INR_REQUIRE(shifts, INR_E_INVALID, "%s: null pointer (shifts)", who);
     MfShape s;
-    MfBlock kb;
+    TvBlock kb;
     if (int rc = mf_shape_check(who, n, K, H, W, f0, f1, &s)) return rc;
-    INR_REQUIRE(n_iter >= 0 && n_iter <= INR_TVSR3D_MAX_ITER, INR_E_INVALID, "%s: n_iter must be 0 .. %d (got %d)", who,
-                INR_TVSR3D_MAX_ITER, n_iter);
-    INR_REQUIRE(std::isfinite(lam) && lam >= 0.0, INR_E_INVALID, "%s: lambda must be finite and >= 0 (got %g)", who, lam);
-    INR_REQUIRE(std::isfinite(alpha) && alpha >= 0.0, INR_E_INVALID, "%s: alpha must be finite and >= 0 (got %g)", who, alpha);
-    if (int rc = mf_block_check(who, kernel, f0, f1, &kb)) return rc;
+    if (int rc = tv_params_check(who, lam, alpha, n_iter, INR_TVSR3D_MAX_ITER)) return rc;
+    if (int rc = tv_block_check(who, kernel, f0, f1, &kb)) return rc;
     if (int rc = check_ws_doubles(who, workspace, workspace_doubles, mf_view(n, s, nullptr).total)) return rc;
     if (n == 0) return 0;
     const MfView v = mf_view(n, s, workspace);
     const long long pixels = (long long)n * H * W, data = (long long)n * K * s.h * s.w;
     const long long table = (long long)n * K * (f0 + 1) * (f1 + 1), items = (long long)n * s.parts;
     ProfScope ps(KC_OTHER, st);
-    hipLaunchKernelGGL((mf_init_kernel<T>), dim3(mf_thread_grid(pixels + data + table + n)), dim3(MF_THREADS), 0, st, v, y, x0, shifts,
+    hipLaunchKernelGGL((mf_init_kernel<T>), dim3(tv_thread_grid(pixels + data + table + n, MF_THREADS)), dim3(MF_THREADS), 0, st, v, y, x0, shifts,
                        (long long)n, s, kb);
     INR_LAUNCH_CHECK();
     const long long begin = lam > 0.0 ? 0 : pixels;
     for (int it = 0; it < n_iter; ++it) {
-        hipLaunchKernelGGL((mf_dual_kernel<T>), dim3(mf_thread_grid(pixels + data - begin)), dim3(MF_THREADS), 0, st, v, y, weight,
+        hipLaunchKernelGGL((mf_dual_kernel<T>), dim3(tv_thread_grid(pixels + data - begin, MF_THREADS)), dim3(MF_THREADS), 0, st, v, y, weight,
                            (long long)n, s, lam, alpha, begin);
         INR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(mf_primal_kernel, dim3(mf_thread_grid(pixels)), dim3(MF_THREADS), 0, st, v, (long long)n, s,
+        hipLaunchKernelGGL(mf_primal_kernel, dim3(tv_thread_grid(pixels, MF_THREADS)), dim3(MF_THREADS), 0, st, v, (long long)n, s,
                            (int)(it + 1 == n_iter));
         INR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((mf_final_kernel<T>), dim3(mf_grid(items)), dim3(MF_THREADS), 0, st, out, v, y, weight, (long long)n, s, lam, alpha,
+    hipLaunchKernelGGL((mf_final_kernel<T>), dim3(tv_grid(items)), dim3(MF_THREADS), 0, st, out, v, y, weight, (long long)n, s, lam, alpha,
                        n_iter);
     INR_LAUNCH_CHECK();
-    if (energy || change || valid_fraction) {
-        hipLaunchKernelGGL(mf_finish_kernel, dim3(mf_grid(n)), dim3(MF_THREADS), 0, st, energy, change, valid_fraction, v, (long long)n, s);
-        INR_LAUNCH_CHECK();
-    }
-    return 0;
+    return tv_finish<MF_THREADS>(energy, change, valid_fraction, v.epart, s.parts, v.chpart, s.parts, v.vpart, (double)s.K * s.h * s.w, n, st);
 }
 
 }  // namespace
@@ -572,13 +487,13 @@ int inr_frame_apply2d(double* out, unsigned char* valid, const double* in, const
     INR_REQUIRE(out && in, INR_E_INVALID, "inr_frame_apply2d: null pointer");
     INR_REQUIRE(shifts, INR_E_INVALID, "inr_frame_apply2d: null pointer (shifts)");
     MfShape s;
-    MfBlock kb;
+    TvBlock kb;
     if (int rc = mf_shape_check("inr_frame_apply2d", n_images, n_frames, height, width, f0, f1, &s)) return rc;
-    if (int rc = mf_block_check("inr_frame_apply2d", kernel, f0, f1, &kb)) return rc;
+    if (int rc = tv_block_check("inr_frame_apply2d", kernel, f0, f1, &kb)) return rc;
     if (n_images == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(KC_OTHER, st);
-    hipLaunchKernelGGL(mf_apply_kernel, dim3(mf_grid((long long)n_images * n_frames)), dim3(MF_THREADS), 0, st, out, valid, in, shifts,
+    hipLaunchKernelGGL(mf_apply_kernel, dim3(tv_grid((long long)n_images * n_frames)), dim3(MF_THREADS), 0, st, out, valid, in, shifts,
                        (long long)n_images, s, kb);
     INR_LAUNCH_CHECK();
     return 0;
@@ -589,14 +504,14 @@ int inr_frame_adjoint2d(double* out, const double* in, const double* shifts, int
     INR_REQUIRE(out && in, INR_E_INVALID, "inr_frame_adjoint2d: null pointer");
     INR_REQUIRE(shifts, INR_E_INVALID, "inr_frame_adjoint2d: null pointer (shifts)");
     MfShape s;
-    MfBlock kb;
+    TvBlock kb;
     if (int rc = mf_shape_check("inr_frame_adjoint2d", n_images, n_frames, height, width, f0, f1, &s)) return rc;
-    if (int rc = mf_block_check("inr_frame_adjoint2d", kernel, f0, f1, &kb)) return rc;
+    if (int rc = tv_block_check("inr_frame_adjoint2d", kernel, f0, f1, &kb)) return rc;
     if (n_images == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(KC_OTHER, st);
     const int chunks = (height * width + MF_THREADS - 1) / MF_THREADS;
-    hipLaunchKernelGGL(mf_adjoint_kernel, dim3(mf_grid((long long)n_images * chunks)), dim3(MF_THREADS), 0, st, out, in, shifts,
+    hipLaunchKernelGGL(mf_adjoint_kernel, dim3(tv_grid((long long)n_images * chunks)), dim3(MF_THREADS), 0, st, out, in, shifts,
                        (long long)n_images, s, kb, chunks);
     INR_LAUNCH_CHECK();
     return 0;

@@ -43,11 +43,12 @@
 // Consecutive datum threads take consecutive j, the fastest LR index, so the reads of xbar are contiguous whenever f_2 = 1.  A
 // volume's HR voxels followed by its M data are cut into "parts" of MS_PART elements; the partials are per PART, and thread t of the
 // finish adds partials t, t + 256, ... in ascending order, so the bits of energy and change depend on the shape alone: not on the
-// grid (capped at MS_MAX_GRID, or by the test-only inr_debug_set(32, .)), the stream, or the place in a batch.  All arithmetic is
+// grid (capped at TV_STRIDE_MAX_GRID, or by the test-only inr_debug_set(32, .)), the stream, or the place in a batch.  All arithmetic is
 // fp64; the fp32 entry converts at load and rounds once at the store.
-#include <cmath>
-
-#include "internal.h"
+//
+// The Huber function, the floor division, the grids, the refusals of the scalar parameters and the gradient weights, the step setup
+// of the prior and the finish kernel are tv_shared.h's.
+#include "tv_shared.h"
 
 namespace inr {
 namespace {
@@ -59,7 +60,6 @@ constexpr int MS_MAX_FACTOR = INR_TVSR_MAX_FACTOR;
 constexpr int MS_MAX_SIDE = INR_TVSR_MAX_SIDE;
 constexpr int MS_MAX_EXTENT = 2048;
 constexpr int MS_MAX_OFFSET = 1 << 20;
-constexpr int MS_MAX_GRID = 2048;
 constexpr int MS_PART = 4 * MS_THREADS;   // elements of a part: four per thread
 
 // one stack: the caller's geometry, the valid index range lo .. hi per axis (empty: hi < lo; lo is cut to n and hi to -1, which keeps
@@ -95,12 +95,6 @@ __device__ __forceinline__ void ms_stage(MsLds* lds, const MsTable& tab, int S) 
     for (int t = threadIdx.x; t < S * 3 * MS_MAX_TAPS; t += blockDim.x) (&lds->k[0][0][0])[t] = (&tab.k[0][0][0])[t];
     for (int t = threadIdx.x; t < S; t += blockDim.x) lds->g[t] = tab.g[t];
     __syncthreads();
-}
-
-// floor(u / f) for f > 0
-__device__ __host__ __forceinline__ int ms_floordiv(int u, int f) {
-    const int q = u / f;
-    return u - q * f < 0 ? q - 1 : q;
 }
 
 // datum u of a volume's row of M -> its stack and LR indices
@@ -142,8 +136,8 @@ __device__ __forceinline__ double ms_apply(const double* x, const MsLds* t, cons
 // the LR indices of axis a whose footprint holds HR coordinate m, cut to the valid ones
 __device__ __forceinline__ void ms_reach(const MsStack& g, int a, int m, int* first, int* last) {
     const int u = m - g.o[a], f = g.f[a], L = g.L[a];
-    *first = max(ms_floordiv(u - L + 1 + f - 1, f), (int)g.lo[a]);
-    *last = min(ms_floordiv(u, f), (int)g.hi[a]);
+    *first = max(tv_floordiv(u - L + 1 + f - 1, f), (int)g.lo[a]);
+    *last = min(tv_floordiv(u, f), (int)g.hi[a]);
 }
 
 // sum_s (A_s^T r_s) at HR voxel (z, i, j): val(u) is r at datum u of the volume's row
@@ -170,11 +164,6 @@ __device__ __forceinline__ double ms_gather(const MsLds* t, int S, int z, int i,
         }
     }
     return acc;
-}
-
-__device__ __forceinline__ double ms_huber(double t, double alpha) {
-    if (alpha == 0.0) return t;
-    return t <= alpha ? t * t / (2.0 * alpha) : t - alpha / 2.0;
 }
 
 // the workspace: the state x | xbar | p0 | p1 | p2 of every volume, q [n][M], and the partials [n][parts] of energy, change and the
@@ -363,7 +352,7 @@ __global__ void __launch_bounds__(MS_THREADS) ms_final_kernel(T* out, MsView v, 
                     const double d2 = j + 1 < s.W ? x[e + 1] - xe : 0.0;
                     const double d0 = z + 1 < s.D ? x[e + HW] - xe : 0.0;
                     const double t1 = c.g1 * d1, t2 = c.g2 * d2, t0 = c.g0 * d0;
-                    reg += ms_huber(sqrt((t1 * t1 + t2 * t2) + t0 * t0), c.alpha);
+                    reg += tv_huber(sqrt((t1 * t1 + t2 * t2) + t0 * t0), c.alpha);
                 }
                 if (n_iter > 0) ch = fmax(ch, fabs(diff[e]));
             } else if (u < DHW + s.M) {
@@ -382,42 +371,12 @@ __global__ void __launch_bounds__(MS_THREADS) ms_final_kernel(T* out, MsView v, 
         if (c.lam > 0.0) en += c.lam * reg;
         en = block_sum_f64(en, red);
         cnt = block_sum_f64(cnt, red);
-        ch = wave_max(ch);
-        if ((tid & 63) == 0) red[tid >> 6] = ch;
-        __syncthreads();
+        ch = block_max_f64(ch, red);   // ends with a barrier: red is free for the next item
         if (tid == 0) {
             v.epart[item] = en;
             v.vpart[item] = cnt;
-            v.chpart[item] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+            v.chpart[item] = ch;
         }
-        __syncthreads();   // red is free for the next item
-    }
-}
-
-// energy / change / valid_fraction [n] from the partials [n][parts]: thread t adds (maximises) partials t, t + 256, ... in ascending
-// order, then the lanes by wave_sum's butterfly, then the four waves in order
-__global__ void __launch_bounds__(MS_THREADS) ms_finish_kernel(double* energy, double* change, double* valid_fraction, MsView v, long long n,
-                                                               MsShape s) {
-    __shared__ double red[MS_THREADS / 64];
-    const int tid = threadIdx.x;
-    for (long long img = blockIdx.x; img < n; img += gridDim.x) {
-        double en = 0.0, ch = 0.0, cnt = 0.0;
-        for (long long p = tid; p < s.parts; p += MS_THREADS) {
-            en += v.epart[img * s.parts + p];
-            cnt += v.vpart[img * s.parts + p];
-            ch = fmax(ch, v.chpart[img * s.parts + p]);
-        }
-        en = block_sum_f64(en, red);
-        cnt = block_sum_f64(cnt, red);
-        ch = wave_max(ch);
-        if ((tid & 63) == 0) red[tid >> 6] = ch;
-        __syncthreads();
-        if (tid == 0) {
-            if (energy) energy[img] = en;
-            if (change) change[img] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-            if (valid_fraction) valid_fraction[img] = cnt / (double)s.M;
-        }
-        __syncthreads();
     }
 }
 
@@ -459,7 +418,7 @@ void ms_stack_ranges(MsStack* g, const int N[3]) {
     for (int a = 0; a < 3; ++a) {
         const int f = g->f[a], n = g->n[a];
         const int lo = g->o[a] >= 0 ? 0 : (-g->o[a] + f - 1) / f;
-        const int top = ms_floordiv(N[a] - (int)g->L[a] - g->o[a], f);
+        const int top = tv_floordiv(N[a] - (int)g->L[a] - g->o[a], f);
         const int hi = top < n - 1 ? top : n - 1;
         g->lo[a] = (short)(lo < n ? lo : n);
         g->hi[a] = (short)(hi > -1 ? hi : -1);
@@ -540,15 +499,6 @@ int ms_taps_check(const char* who, const double* taps, const MsShape& s, MsTable
     return 0;
 }
 
-// grids: capped, with a stride loop in every kernel; inr_debug_set(32, .) caps them further (tests walk the stride on small volumes)
-unsigned ms_grid(long long workgroups) {
-    long long g = workgroups < 1 ? 1 : (workgroups > MS_MAX_GRID ? MS_MAX_GRID : workgroups);
-    const int cap = g_hp_grid_cap;
-    if (cap > 0 && g > cap) g = cap;
-    return (unsigned)g;
-}
-unsigned ms_thread_grid(long long threads) { return ms_grid((threads + MS_THREADS - 1) / MS_THREADS); }
-
 template <typename T>
 int ms_solve(const char* who, T* out, double* energy, double* change, double* valid_fraction, const T* y, const T* weight, const T* x0,
              int n, int D, int H, int W, int S, const int* geometry, const double* taps, const double* grad_weights, double lam,
@@ -559,22 +509,14 @@ int ms_solve(const char* who, T* out, double* energy, double* change, double* va
     MsTable tab;
     double csum = 0.0;
     if (int rc = ms_shape_check(who, n, D, H, W, S, geometry, &s, &tab)) return rc;
-    INR_REQUIRE(n_iter >= 0 && n_iter <= INR_TVSR3D_MAX_ITER, INR_E_INVALID, "%s: n_iter must be 0 .. %d (got %d)", who,
-                INR_TVSR3D_MAX_ITER, n_iter);
-    INR_REQUIRE(std::isfinite(lam) && lam >= 0.0, INR_E_INVALID, "%s: lambda must be finite and >= 0 (got %g)", who, lam);
-    INR_REQUIRE(std::isfinite(alpha) && alpha >= 0.0, INR_E_INVALID, "%s: alpha must be finite and >= 0 (got %g)", who, alpha);
-    for (int a = 0; a < 3; ++a)
-        INR_REQUIRE(std::isfinite(grad_weights[a]) && grad_weights[a] >= 0.0, INR_E_INVALID,
-                    "%s: the gradient weights must be finite and >= 0 (g%d is %g)", who, a, grad_weights[a]);
+    if (int rc = tv_params_check(who, lam, alpha, n_iter, INR_TVSR3D_MAX_ITER)) return rc;
+    if (int rc = tv_grad_weights_check(who, grad_weights)) return rc;
     if (int rc = ms_taps_check(who, taps, s, &tab, &csum)) return rc;
     if (int rc = check_ws_doubles(who, workspace, workspace_doubles, ms_view(n, s, nullptr).total)) return rc;
     if (n == 0) return 0;
     MsStep c;
     c.g0 = grad_weights[0], c.g1 = grad_weights[1], c.g2 = grad_weights[2];
-    double gsum = 0.0;
-    if (H > 1) gsum += c.g1 * c.g1;
-    if (W > 1) gsum += c.g2 * c.g2;
-    if (D > 1) gsum += c.g0 * c.g0;
+    const double gsum = tv_grad_weight_sum(grad_weights, D, H, W);
     c.lam = gsum > 0.0 ? lam : 0.0;
     const double bound = 4.0 * gsum + csum;
     c.tau = bound > 0.0 ? 1.0 / std::sqrt(bound) : 1.0 / std::sqrt(8.0);
@@ -582,30 +524,26 @@ int ms_solve(const char* who, T* out, double* energy, double* change, double* va
     const MsView v = ms_view(n, s, workspace);
     const long long voxels = (long long)n * D * H * W, data = (long long)n * s.M, items = (long long)n * s.parts;
     ProfScope ps(KC_OTHER, st);
-    hipLaunchKernelGGL((ms_init_kernel<T>), dim3(ms_thread_grid(voxels + data)), dim3(MS_THREADS), 0, st, v, x0, (long long)n, s);
+    hipLaunchKernelGGL((ms_init_kernel<T>), dim3(tv_thread_grid(voxels + data, MS_THREADS)), dim3(MS_THREADS), 0, st, v, x0, (long long)n, s);
     INR_LAUNCH_CHECK();
     if (!x0) {
-        hipLaunchKernelGGL((ms_backproject_kernel<T>), dim3(ms_thread_grid(voxels)), dim3(MS_THREADS), 0, st, v, y, weight, (long long)n, s,
+        hipLaunchKernelGGL((ms_backproject_kernel<T>), dim3(tv_thread_grid(voxels, MS_THREADS)), dim3(MS_THREADS), 0, st, v, y, weight, (long long)n, s,
                            tab);
         INR_LAUNCH_CHECK();
     }
     const long long begin = c.lam > 0.0 ? 0 : voxels;
     for (int it = 0; it < n_iter; ++it) {
-        hipLaunchKernelGGL((ms_dual_kernel<T>), dim3(ms_thread_grid(voxels + data - begin)), dim3(MS_THREADS), 0, st, v, y, weight,
+        hipLaunchKernelGGL((ms_dual_kernel<T>), dim3(tv_thread_grid(voxels + data - begin, MS_THREADS)), dim3(MS_THREADS), 0, st, v, y, weight,
                            (long long)n, s, tab, c, begin);
         INR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(ms_primal_kernel, dim3(ms_thread_grid(voxels)), dim3(MS_THREADS), 0, st, v, (long long)n, s, tab, c,
+        hipLaunchKernelGGL(ms_primal_kernel, dim3(tv_thread_grid(voxels, MS_THREADS)), dim3(MS_THREADS), 0, st, v, (long long)n, s, tab, c,
                            (int)(it + 1 == n_iter));
         INR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((ms_final_kernel<T>), dim3(ms_grid(items)), dim3(MS_THREADS), 0, st, out, v, y, weight, (long long)n, s, tab, c,
+    hipLaunchKernelGGL((ms_final_kernel<T>), dim3(tv_grid(items)), dim3(MS_THREADS), 0, st, out, v, y, weight, (long long)n, s, tab, c,
                        n_iter);
     INR_LAUNCH_CHECK();
-    if (energy || change || valid_fraction) {
-        hipLaunchKernelGGL(ms_finish_kernel, dim3(ms_grid(n)), dim3(MS_THREADS), 0, st, energy, change, valid_fraction, v, (long long)n, s);
-        INR_LAUNCH_CHECK();
-    }
-    return 0;
+    return tv_finish<MS_THREADS>(energy, change, valid_fraction, v.epart, s.parts, v.chpart, s.parts, v.vpart, (double)s.M, n, st);
 }
 
 int ms_operator(const char* who, bool adjoint, double* out, unsigned char* valid, const double* in, int n, int D, int H, int W, int S,
@@ -619,10 +557,10 @@ int ms_operator(const char* who, bool adjoint, double* out, unsigned char* valid
     if (n == 0) return 0;
     ProfScope ps(KC_OTHER, st);
     if (adjoint)
-        hipLaunchKernelGGL(ms_adjoint_kernel, dim3(ms_thread_grid((long long)n * D * H * W)), dim3(MS_THREADS), 0, st, out, in, (long long)n,
+        hipLaunchKernelGGL(ms_adjoint_kernel, dim3(tv_thread_grid((long long)n * D * H * W, MS_THREADS)), dim3(MS_THREADS), 0, st, out, in, (long long)n,
                            s, tab);
     else
-        hipLaunchKernelGGL(ms_apply_kernel, dim3(ms_thread_grid((long long)n * s.M)), dim3(MS_THREADS), 0, st, out, valid, in, (long long)n,
+        hipLaunchKernelGGL(ms_apply_kernel, dim3(tv_thread_grid((long long)n * s.M, MS_THREADS)), dim3(MS_THREADS), 0, st, out, valid, in, (long long)n,
                            s, tab);
     INR_LAUNCH_CHECK();
     return 0;

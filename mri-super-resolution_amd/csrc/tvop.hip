@@ -38,21 +38,20 @@
 // STREAM ORDER IS THE BARRIER between launches.
 //
 // The partials are per TILE and the tile count depends on the shape alone, so the bits of energy and change depend neither on the
-// grid (capped at OP_MAX_GRID, or by the test-only inr_debug_set(32, .)), nor on the stream, nor on the place in a batch.  All
+// grid (capped at TV_STRIDE_MAX_GRID, or by the test-only inr_debug_set(32, .)), nor on the stream, nor on the place in a batch.  All
 // arithmetic is fp64; the fp32 entry converts y / weight / x0 at the load and rounds the result once.  The unit is compiled with
 // -ffp-contract=off (_build.py), so the two entries agree bit for bit in their fp64 state.  No operator, weight or datum VALUE reaches
 // an index: a NaN anywhere gives NaNs and no fault.
-#include <cmath>
-
+//
+// The Huber function, the block maximum, the grids, the refusals of the scalar parameters and the finish kernel are tv_shared.h's.
 #include "gemm_f64.h"
-#include "internal.h"
+#include "tv_shared.h"
 
 namespace inr {
 namespace {
 
 constexpr int OP_THREADS = 256;
 constexpr int OP_MAX_SIDE = INR_TVSR_MAX_SIDE;
-constexpr int OP_MAX_GRID = 2048;
 
 struct OpShape {
     int H, W, h, w;
@@ -79,21 +78,6 @@ OpView op_view(int n, const OpShape& s, void* base) {
     v.chpart = c.take<double>(nn * (size_t)s.TH);
     v.total = c.bytes();
     return v;
-}
-
-__device__ __forceinline__ double op_huber(double t, double alpha) {
-    if (alpha == 0.0) return t;
-    return t <= alpha ? t * t / (2.0 * alpha) : t - alpha / 2.0;
-}
-
-// maximum over the block of 256, every thread receives it (red: 4 doubles of LDS)
-__device__ __forceinline__ double op_block_max(double v, double* red) {
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double m = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-    __syncthreads();
-    return m;
 }
 
 // ---- the contraction: C [M][N] = A [M][K] B [K][N] per image, operands by strides (a batch stride of 0 shares an operator) --------------
@@ -182,7 +166,7 @@ struct OpPrimal {
     }
     __device__ __forceinline__ void end(long long item, double* red) {
         if (!last) return;                       // uniform over the launch
-        const double m = op_block_max(ch, red);
+        const double m = block_max_f64(ch, red);
         if (threadIdx.x == 0) chpart[item] = m;
     }
 };
@@ -250,8 +234,8 @@ __device__ double op_norm_bound(const double* __restrict__ R, int m, int n, doub
         for (int i = 0; i < m; ++i) s += fabs(R[(size_t)i * n + j]);
         cmax = fmax(cmax, s);
     }
-    rmax = op_block_max(rmax, red);
-    cmax = op_block_max(cmax, red);
+    rmax = block_max_f64(rmax, red);
+    cmax = block_max_f64(cmax, red);
     return rmax * cmax;
 }
 __global__ void __launch_bounds__(OP_THREADS) op_step_kernel(double* __restrict__ tau, const double* __restrict__ R0,
@@ -345,30 +329,11 @@ __global__ void __launch_bounds__(OP_THREADS) op_final_hr_kernel(T* __restrict__
             if (lam > 0.0) {
                 const double g0 = i + 1 < s.H ? x[e + s.W] - xe : 0.0;
                 const double g1 = j + 1 < s.W ? x[e + 1] - xe : 0.0;
-                reg += op_huber(sqrt(g0 * g0 + g1 * g1), alpha);
+                reg += tv_huber(sqrt(g0 * g0 + g1 * g1), alpha);
             }
         }
         reg = block_sum_f64(reg, red);
         if (tid == 0) v.epart[img * parts + s.TL + tile] = lam > 0.0 ? lam * reg : 0.0;
-    }
-}
-
-// energy / change [n]: thread t adds (maximises) partials t, t + 256, ... in ascending order, then the lanes by wave_sum's butterfly,
-// then the four waves in order
-__global__ void __launch_bounds__(OP_THREADS) op_finish_kernel(double* energy, double* change, OpView v, long long n, OpShape s, int n_iter) {
-    __shared__ double red[OP_THREADS / 64];
-    const int tid = threadIdx.x, parts = s.TL + s.TH;
-    for (long long img = blockIdx.x; img < n; img += gridDim.x) {
-        double en = 0.0, ch = 0.0;
-        for (int p = tid; p < parts; p += OP_THREADS) en += v.epart[img * parts + p];
-        if (n_iter > 0)
-            for (int p = tid; p < s.TH; p += OP_THREADS) ch = fmax(ch, v.chpart[img * s.TH + p]);
-        en = block_sum_f64(en, red);
-        ch = op_block_max(ch, red);
-        if (tid == 0) {
-            if (energy) energy[img] = en;
-            if (change) change[img] = ch;
-        }
     }
 }
 
@@ -386,19 +351,10 @@ int op_shape_check(const char* who, int n, int H, int W, int h, int w, OpShape* 
     return 0;
 }
 
-// grids: capped, with a stride loop in every kernel; inr_debug_set(32, .) caps them further (tests walk the stride on small images)
-unsigned op_grid(long long workgroups) {
-    long long g = workgroups < 1 ? 1 : (workgroups > OP_MAX_GRID ? OP_MAX_GRID : workgroups);
-    const int cap = g_hp_grid_cap;
-    if (cap > 0 && g > cap) g = cap;
-    return (unsigned)g;
-}
-unsigned op_thread_grid(long long threads) { return op_grid((threads + OP_THREADS - 1) / OP_THREADS); }
-
 template <class XA, class XB, class Epi>
 int op_gemm(const double* A, const double* B, OpGemm g, int n, const Epi& epi, hipStream_t st) {
     g.items = (long long)n * g.tiles_r * g.tiles_c;
-    hipLaunchKernelGGL((op_gemm_kernel<XA, XB, Epi>), dim3(op_grid(g.items)), dim3(OP_THREADS), 0, st, A, B, g, epi);
+    hipLaunchKernelGGL((op_gemm_kernel<XA, XB, Epi>), dim3(tv_grid(g.items)), dim3(OP_THREADS), 0, st, A, B, g, epi);
     INR_LAUNCH_CHECK();
     return 0;
 }
@@ -442,10 +398,7 @@ int op_solve(const char* who, T* out, double* energy, double* change, const T* y
     INR_REQUIRE(r0 && r1, INR_E_INVALID, "%s: null pointer (r0 / r1)", who);
     OpShape s;
     if (int rc = op_shape_check(who, n, H, W, h, w, &s)) return rc;
-    INR_REQUIRE(n_iter >= 0 && n_iter <= INR_TVSR3D_MAX_ITER, INR_E_INVALID, "%s: n_iter must be 0 .. %d (got %d)", who,
-                INR_TVSR3D_MAX_ITER, n_iter);
-    INR_REQUIRE(std::isfinite(lam) && lam >= 0.0, INR_E_INVALID, "%s: lambda must be finite and >= 0 (got %g)", who, lam);
-    INR_REQUIRE(std::isfinite(alpha) && alpha >= 0.0, INR_E_INVALID, "%s: alpha must be finite and >= 0 (got %g)", who, alpha);
+    if (int rc = tv_params_check(who, lam, alpha, n_iter, INR_TVSR3D_MAX_ITER)) return rc;
     if (int rc = check_ws_doubles(who, workspace, workspace_doubles, op_view(n, s, nullptr).total)) return rc;
     if (n == 0) return 0;
     const OpView v = op_view(n, s, workspace);
@@ -455,22 +408,22 @@ int op_solve(const char* who, T* out, double* energy, double* change, const T* y
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL(op_step_kernel, dim3(1), dim3(OP_THREADS), 0, st, v.tau, r0, r1, s);
     INR_LAUNCH_CHECK();
-    hipLaunchKernelGGL((op_init_kernel<T>), dim3(op_thread_grid(pixels + data)), dim3(OP_THREADS), 0, st, v, y, weight, x0, (long long)n, s);
+    hipLaunchKernelGGL((op_init_kernel<T>), dim3(tv_thread_grid(pixels + data, OP_THREADS)), dim3(OP_THREADS), 0, st, v, y, weight, x0, (long long)n, s);
     INR_LAUNCH_CHECK();
     if (!x0) {
         if (int rc = op_cols_t<GfAbs>(v.q, r1, n, s, op_store_mid(v, s), st)) return rc;
         if (int rc = op_rows_t<GfAbs>(r0, v.mid, n, s, OpSetX{v.state, H, W}, st)) return rc;
-        hipLaunchKernelGGL((op_fill_kernel<T>), dim3(op_thread_grid(data)), dim3(OP_THREADS), 0, st, v.q, weight, data, 1);
+        hipLaunchKernelGGL((op_fill_kernel<T>), dim3(tv_thread_grid(data, OP_THREADS)), dim3(OP_THREADS), 0, st, v.q, weight, data, 1);
         INR_LAUNCH_CHECK();
         if (int rc = op_cols_t<GfAbs>(v.q, r1, n, s, op_store_mid(v, s), st)) return rc;
         if (int rc = op_rows_t<GfAbs>(r0, v.mid, n, s, OpNormX{v.state, H, W}, st)) return rc;
-        hipLaunchKernelGGL((op_fill_kernel<T>), dim3(op_thread_grid(data)), dim3(OP_THREADS), 0, st, v.q, weight, data, 0);
+        hipLaunchKernelGGL((op_fill_kernel<T>), dim3(tv_thread_grid(data, OP_THREADS)), dim3(OP_THREADS), 0, st, v.q, weight, data, 0);
         INR_LAUNCH_CHECK();
     }
     OpGemm rows{s.h, s.W, s.H, 0, s.H, 1, img, s.W, 1, s.tl_r, s.th_c, 0};   // launch 2 on a field of the state: the image stride is 4 H W
     for (int it = 0; it < n_iter; ++it) {
         if (lam > 0.0) {
-            hipLaunchKernelGGL(op_dual_kernel, dim3(op_thread_grid(pixels)), dim3(OP_THREADS), 0, st, v, (long long)n, s, lam, alpha);
+            hipLaunchKernelGGL(op_dual_kernel, dim3(tv_thread_grid(pixels, OP_THREADS)), dim3(OP_THREADS), 0, st, v, (long long)n, s, lam, alpha);
             INR_LAUNCH_CHECK();
         }
         if (int rc = op_gemm<GfIdentity, GfIdentity>(r0, xbar, rows, n, op_store_mid(v, s), st)) return rc;
@@ -480,14 +433,11 @@ int op_solve(const char* who, T* out, double* energy, double* change, const T* y
     }
     if (int rc = op_gemm<GfIdentity, GfIdentity>(r0, v.state, rows, n, op_store_mid(v, s), st)) return rc;
     if (int rc = op_cols(v.mid, r1, n, s, OpEnergy<T>{y, weight, v.epart, (long long)h * w, w, s.TL, s.TL + s.TH, 0.0}, st)) return rc;
-    hipLaunchKernelGGL((op_final_hr_kernel<T>), dim3(op_grid((long long)n * s.TH)), dim3(OP_THREADS), 0, st, out, v, (long long)n, s, lam,
+    hipLaunchKernelGGL((op_final_hr_kernel<T>), dim3(tv_grid((long long)n * s.TH)), dim3(OP_THREADS), 0, st, out, v, (long long)n, s, lam,
                        alpha);
     INR_LAUNCH_CHECK();
-    if (energy || change) {
-        hipLaunchKernelGGL(op_finish_kernel, dim3(op_grid(n)), dim3(OP_THREADS), 0, st, energy, change, v, (long long)n, s, n_iter);
-        INR_LAUNCH_CHECK();
-    }
-    return 0;
+    // the energy partials: data per LR tile, then prior per HR tile; the change partials are written in the last iteration only
+    return tv_finish<OP_THREADS>(energy, change, nullptr, v.epart, s.TL + s.TH, v.chpart, n_iter > 0 ? s.TH : 0, nullptr, 1.0, n, st);
 }
 
 }  // namespace

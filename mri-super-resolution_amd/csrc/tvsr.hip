@@ -32,10 +32,15 @@
 // energy: the objective at the returned x (the fp64 x, before the fp32 entry rounds it); every thread adds its LR blocks and then its
 // HR pixels in ascending order, wave_sum's butterfly adds the lanes, thread 0 adds the 16 waves in ascending order: no float atomics,
 // the same bits on every call and at every position in a batch.  change: max |x' - x| of the last iteration (0 for n_iter = 0).
-#include "tv_block.h"   // the shape, the block kernel and their checks, shared with tvj.hip
+//
+// The start, the primal block step, the data term and the reduction of energy and change are tv_block.h's, shared with tvj.hip and
+// tgv.hip; the Huber function, the parameter refusals and the workspace view are tv_shared.h's, shared with the whole family.
+#include "tv_block.h"
 
 namespace inr {
 namespace {
+
+constexpr int TV_FIELDS = 4;   // x | xbar | p0 | p1 of every image: the workspace is tv_state_view(n, TV_FIELDS, H, W, .)
 
 template <typename T>
 __global__ void __launch_bounds__(TV_THREADS) tv_solve_kernel(T* out, double* energy, double* change, const T* y, const T* weight,
@@ -48,17 +53,15 @@ __global__ void __launch_bounds__(TV_THREADS) tv_solve_kernel(T* out, double* en
     const double tau = 1.0 / sqrt(8.0), sigma = tau;
     if (tid < s.f0 * s.f1) ks[tid] = kb.k[tid];
     for (int img = blockIdx.x; img < n_images; img += gridDim.x) {
-        double* x = state + (size_t)img * 4 * HW;
+        double* x = state + (size_t)img * TV_FIELDS * HW;
         double* xbar = x + HW;
         double* p0 = xbar + HW;
         double* p1 = p0 + HW;
         const T* yi = y + (size_t)img * hw;
         const T* wi = weight ? weight + (size_t)img * hw : nullptr;
+        const T* x0i = x0 ? x0 + (size_t)img * HW : nullptr;
         for (int e = tid; e < HW; e += TV_THREADS) {
-            const int i = e / W, j = e - i * W;
-            const double v = x0 ? (double)x0[(size_t)img * HW + e] : (double)yi[(i / s.f0) * s.w + j / s.f1];
-            x[e] = v;
-            xbar[e] = v;
+            tv_start_pixel(x, xbar, x0i, yi, s, e);
             p0[e] = 0.0;
             p1[e] = 0.0;
         }
@@ -85,46 +88,13 @@ __global__ void __launch_bounds__(TV_THREADS) tv_solve_kernel(T* out, double* en
             }
             __syncthreads();   // barrier 1: p is complete
             const bool last = it + 1 == n_iter;
-            for (int blk = tid; blk < hw; blk += TV_THREADS) {
-                const int bi = blk / s.w, bj = blk - bi * s.w;
-                double acc = 0.0;
-                for (int a = 0; a < s.f0; ++a)
-                    for (int b = 0; b < s.f1; ++b) {
-                        const int i = bi * s.f0 + a, j = bj * s.f1 + b, e = i * W + j;
-                        double d = 0.0;
-                        if (i + 1 < s.H) d += p0[e];
-                        if (i > 0) d -= p0[e - W];
-                        if (j + 1 < W) d += p1[e];
-                        if (j > 0) d -= p1[e - 1];
-                        const double v = x[e] + tau * d;
-                        xbar[e] = v;   // v waits here for the second pass: nobody else reads xbar in this phase
-                        acc += ks[a * s.f1 + b] * v;
-                    }
-                const double wv = wi ? (double)wi[blk] : 1.0;
-                // a missing datum (w = 0) takes no part, whatever y holds there
-                const double r = wv == 0.0 ? 0.0 : tau * wv / (1.0 + tau * wv * kb.k2) * (acc - (double)yi[blk]);
-                for (int a = 0; a < s.f0; ++a)
-                    for (int b = 0; b < s.f1; ++b) {
-                        const int e = (bi * s.f0 + a) * W + bj * s.f1 + b;
-                        const double xo = x[e];
-                        const double xn = xbar[e] - ks[a * s.f1 + b] * r;
-                        xbar[e] = 2.0 * xn - xo;
-                        x[e] = xn;
-                        if (last) ch = fmax(ch, fabs(xn - xo));
-                    }
-            }
+            for (int blk = tid; blk < hw; blk += TV_THREADS)
+                tv_primal_block(x, xbar, p0, p1, ks, s, kb.k2, yi, wi, blk, 1.0, tau, last, ch);
             __syncthreads();   // barrier 2: x and xbar are complete
         }
         // the objective at x, and the image
         double en = 0.0;
-        for (int blk = tid; blk < hw; blk += TV_THREADS) {
-            const int bi = blk / s.w, bj = blk - bi * s.w;
-            const double wv = wi ? (double)wi[blk] : 1.0;
-            if (wv != 0.0) {
-                const double r = tv_block_sum(x, ks, s, bi, bj) - (double)yi[blk];
-                en += 0.5 * wv * r * r;
-            }
-        }
+        for (int blk = tid; blk < hw; blk += TV_THREADS) tv_add_data_term(en, x, ks, s, yi, wi, blk);
         double reg = 0.0;
         for (int e = tid; e < HW; e += TV_THREADS) {
             const int i = e / W, j = e - i * W;
@@ -137,24 +107,7 @@ __global__ void __launch_bounds__(TV_THREADS) tv_solve_kernel(T* out, double* en
             }
         }
         if (lam > 0.0) en += lam * reg;
-        en = wave_sum(en);
-        if ((tid & 63) == 0) red[tid >> 6] = en;
-        __syncthreads();
-        if (tid == 0 && energy) {
-            double sum = 0.0;
-            for (int k = 0; k < TV_WAVES; ++k) sum += red[k];
-            energy[img] = sum;
-        }
-        __syncthreads();
-        ch = wave_max(ch);
-        if ((tid & 63) == 0) red[tid >> 6] = ch;
-        __syncthreads();
-        if (tid == 0 && change) {
-            double m = 0.0;
-            for (int k = 0; k < TV_WAVES; ++k) m = fmax(m, red[k]);
-            change[img] = m;
-        }
-        __syncthreads();   // red is free for the next image
+        tv_store_energy_change(en, ch, red, energy, change, (size_t)img);   // ends with a barrier: red is free for the next image
     }
 }
 
@@ -189,24 +142,6 @@ __global__ void __launch_bounds__(256) tv_adjoint_kernel(double* __restrict__ ou
     }
 }
 
-unsigned tv_grid(long long work) {
-    const long long b = (work + 255) / 256;
-    return (unsigned)(b < 1 ? 1 : (b > TV_MAX_GRID ? TV_MAX_GRID : b));
-}
-
-// the workspace: the state x | xbar | p0 | p1 of every image.  base == null: `total` only
-struct TvView {
-    double* state;
-    size_t total;
-};
-TvView tv_view(int n_images, int H, int W, void* base) {
-    TvView v;
-    WsCarver c(base, 16);
-    v.state = c.take<double>((size_t)(n_images > 0 ? n_images : 1) * 4 * (size_t)H * (size_t)W);
-    v.total = c.bytes();
-    return v;
-}
-
 template <typename T>
 int tv_solve(const char* who, T* out, double* energy, double* change, const T* y, const T* weight, const T* x0, int n_images, int H,
              int W, int f0, int f1, const double* kernel, double lam, double alpha, int n_iter, double* workspace,
@@ -215,13 +150,11 @@ int tv_solve(const char* who, T* out, double* energy, double* change, const T* y
     TvShape s;
     TvBlock kb;
     if (int rc = tv_shape_check(who, n_images, H, W, f0, f1, &s)) return rc;
-    INR_REQUIRE(n_iter >= 0, INR_E_INVALID, "%s: n_iter must be >= 0 (got %d)", who, n_iter);
-    INR_REQUIRE(std::isfinite(lam) && lam >= 0.0, INR_E_INVALID, "%s: lambda must be finite and >= 0 (got %g)", who, lam);
-    INR_REQUIRE(std::isfinite(alpha) && alpha >= 0.0, INR_E_INVALID, "%s: alpha must be finite and >= 0 (got %g)", who, alpha);
+    if (int rc = tv_params_check(who, lam, alpha, n_iter, -1)) return rc;
     if (int rc = tv_block_check(who, kernel, f0, f1, &kb)) return rc;
-    if (int rc = check_ws_doubles(who, workspace, workspace_doubles, tv_view(n_images, H, W, nullptr).total)) return rc;
+    if (int rc = check_ws_doubles(who, workspace, workspace_doubles, tv_state_view(n_images, TV_FIELDS, H, W, nullptr).total)) return rc;
     if (n_images == 0) return 0;
-    const TvView v = tv_view(n_images, H, W, workspace);
+    const TvStateView v = tv_state_view(n_images, TV_FIELDS, H, W, workspace);
     ProfScope ps(KC_OTHER, st);
     hipLaunchKernelGGL((tv_solve_kernel<T>), dim3((unsigned)(n_images < TV_MAX_GRID ? n_images : TV_MAX_GRID)), dim3(TV_THREADS), 0, st,
                        out, energy, change, y, weight, x0, v.state, n_images, s, kb, lam, alpha, n_iter);
@@ -239,7 +172,7 @@ extern "C" {
 int64_t inr_tvsr_workspace_doubles(int n_images, int height, int width) {
     TvShape s;
     if (tv_shape_check("inr_tvsr_workspace_doubles", n_images, height, width, 1, 1, &s)) return 0;
-    return (int64_t)(tv_view(n_images, height, width, nullptr).total / sizeof(double));
+    return (int64_t)(tv_state_view(n_images, TV_FIELDS, height, width, nullptr).total / sizeof(double));
 }
 
 int inr_tvsr_solve2d(double* out, double* energy, double* change, const double* y, const double* weight, const double* x0, int n_images,
@@ -266,7 +199,7 @@ int inr_block_apply2d(double* out, const double* in, int n_images, int height, i
     if (n_images == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(KC_OTHER, st);
-    hipLaunchKernelGGL(tv_apply_kernel, dim3(tv_grid((long long)n_images * s.h * s.w)), dim3(256), 0, st, out, in, (long long)n_images, s,
+    hipLaunchKernelGGL(tv_apply_kernel, dim3(tv_pixel_grid((long long)n_images * s.h * s.w)), dim3(256), 0, st, out, in, (long long)n_images, s,
                        kb);
     INR_LAUNCH_CHECK();
     return 0;
@@ -282,7 +215,7 @@ int inr_block_adjoint2d(double* out, const double* in, int n_images, int height,
     if (n_images == 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     ProfScope ps(KC_OTHER, st);
-    hipLaunchKernelGGL(tv_adjoint_kernel, dim3(tv_grid((long long)n_images * s.H * s.W)), dim3(256), 0, st, out, in, (long long)n_images,
+    hipLaunchKernelGGL(tv_adjoint_kernel, dim3(tv_pixel_grid((long long)n_images * s.H * s.W)), dim3(256), 0, st, out, in, (long long)n_images,
                        s, kb);
     INR_LAUNCH_CHECK();
     return 0;

@@ -30,11 +30,11 @@
 //
 // A volume's tiles are dealt to at most TV3_PARTS "parts" (part j owns tiles j, j + parts, ...), and a workgroup takes whole parts
 // in a grid-stride loop.  The partials of energy and change are per PART, not per workgroup, so their bits depend on the shape
-// alone: not on the grid (capped at TV3_MAX_GRID, or by the test-only inr_debug_set(32, .)), the stream, or the place in a batch.
+// alone: not on the grid (capped at TV_STRIDE_MAX_GRID, or by the test-only inr_debug_set(32, .)), the stream, or the place in a batch.
 // No float atomics.  All arithmetic is fp64; the fp32 entry converts at load and rounds once at the store.
-#include <cmath>
-
-#include "internal.h"
+//
+// The Huber function, the grids, the refusals of the scalar parameters, the step setup and the finish kernel are tv_shared.h's.
+#include "tv_shared.h"
 
 namespace inr {
 namespace {
@@ -42,7 +42,6 @@ namespace {
 constexpr int TV3_THREADS = 256;
 constexpr int TV3_MAX_FACTOR = INR_TVSR_MAX_FACTOR;
 constexpr int TV3_MAX_SIDE = INR_TVSR_MAX_SIDE;
-constexpr int TV3_MAX_GRID = 2048;
 constexpr int TV3_PARTS = 1024;                 // parts per volume, at most
 constexpr int TV3_TILE = 2048;                  // HR voxels of a tile, at most (16 KiB of LDS for v, 16 KiB for the blocks' residuals)
 constexpr int TV3_TILE_COLS = 64;               // HR columns of a tile, at most
@@ -65,11 +64,6 @@ struct Tv3Shape {
 struct Tv3Step {
     double g0, g1, g2, tau, lam, alpha;   // lam: 0 where the prior vanishes
 };
-
-__device__ __forceinline__ double tv3_huber(double t, double alpha) {
-    if (alpha == 0.0) return t;
-    return t <= alpha ? t * t / (2.0 * alpha) : t - alpha / 2.0;
-}
 
 // k[a][b][c] = (k1[b] * k2[c]) * k0[a] into ks [f0][f1][f2]; the caller synchronises
 __device__ __forceinline__ void tv3_form_table(double* ks, const Tv3Kernel& kb, const Tv3Shape& s) {
@@ -250,11 +244,8 @@ __global__ void __launch_bounds__(TV3_THREADS) tv3_primal_kernel(double* state, 
             __syncthreads();   // vt and rs are free for the next tile
         }
         if (last) {
-            ch = wave_max(ch);
-            if ((tid & 63) == 0) red[tid >> 6] = ch;
-            __syncthreads();
-            if (tid == 0) chpart[item] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-            __syncthreads();
+            ch = block_max_f64(ch, red);
+            if (tid == 0) chpart[item] = ch;
         }
     }
 }
@@ -289,7 +280,7 @@ __global__ void __launch_bounds__(TV3_THREADS) tv3_final_kernel(T* out, double* 
                     const double d2 = v.j + 1 < s.W ? x[v.e + 1] - xe : 0.0;
                     const double d0 = v.z + 1 < s.D ? x[v.e + HW] - xe : 0.0;
                     const double t1 = c.g1 * d1, t2 = c.g2 * d2, t0 = c.g0 * d0;
-                    reg += tv3_huber(sqrt((t1 * t1 + t2 * t2) + t0 * t0), c.alpha);
+                    reg += tv_huber(sqrt((t1 * t1 + t2 * t2) + t0 * t0), c.alpha);
                 }
             }
             __syncthreads();
@@ -306,30 +297,6 @@ __global__ void __launch_bounds__(TV3_THREADS) tv3_final_kernel(T* out, double* 
         if (c.lam > 0.0) en += c.lam * reg;
         en = block_sum_f64(en, red);
         if (tid == 0) epart[item] = en;
-    }
-}
-
-// energy / change [n] from the partials [n][parts]: thread t adds (maximises) partials t, t + 256, ... in ascending order, then the
-// lanes by wave_sum's butterfly, then the four waves in order
-__global__ void __launch_bounds__(TV3_THREADS) tv3_finish_kernel(double* energy, double* change, const double* epart, const double* chpart,
-                                                                 long long n, int parts, int n_iter) {
-    __shared__ double red[TV3_THREADS / 64];
-    const int tid = threadIdx.x;
-    for (long long img = blockIdx.x; img < n; img += gridDim.x) {
-        double en = 0.0, ch = 0.0;
-        for (int p = tid; p < parts; p += TV3_THREADS) {
-            en += epart[img * parts + p];
-            if (n_iter > 0) ch = fmax(ch, chpart[img * parts + p]);
-        }
-        en = block_sum_f64(en, red);
-        ch = wave_max(ch);
-        if ((tid & 63) == 0) red[tid >> 6] = ch;
-        __syncthreads();
-        if (tid == 0) {
-            if (energy) energy[img] = en;
-            if (change) change[img] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-        }
-        __syncthreads();
     }
 }
 
@@ -428,15 +395,6 @@ int tv3_kernel_check(const char* who, const double* k0, const double* k1, const 
     return 0;
 }
 
-// grids: capped, with a stride loop in every kernel; inr_debug_set(32, .) caps them further (tests walk the stride on a small volume)
-unsigned tv3_grid(long long workgroups) {
-    long long g = workgroups < 1 ? 1 : (workgroups > TV3_MAX_GRID ? TV3_MAX_GRID : workgroups);
-    const int cap = g_hp_grid_cap;
-    if (cap > 0 && g > cap) g = cap;
-    return (unsigned)g;
-}
-unsigned tv3_voxel_grid(long long voxels) { return tv3_grid((voxels + TV3_THREADS - 1) / TV3_THREADS); }
-
 // the workspace: the state x | xbar | p0 | p1 | p2 of every volume, then the partials of energy and change.  base == null: `total` only
 struct Tv3View {
     double *state, *epart, *chpart;
@@ -461,49 +419,37 @@ int tv3_solve(const char* who, T* out, double* energy, double* change, const T* 
     Tv3Shape s;
     Tv3Kernel kb;
     if (int rc = tv3_shape_check(who, n, D, H, W, f0, f1, f2, &s)) return rc;
-    INR_REQUIRE(n_iter >= 0 && n_iter <= INR_TVSR3D_MAX_ITER, INR_E_INVALID, "%s: n_iter must be 0 .. %d (got %d)", who,
-                INR_TVSR3D_MAX_ITER, n_iter);
-    INR_REQUIRE(std::isfinite(lam) && lam >= 0.0, INR_E_INVALID, "%s: lambda must be finite and >= 0 (got %g)", who, lam);
-    INR_REQUIRE(std::isfinite(alpha) && alpha >= 0.0, INR_E_INVALID, "%s: alpha must be finite and >= 0 (got %g)", who, alpha);
+    if (int rc = tv_params_check(who, lam, alpha, n_iter, INR_TVSR3D_MAX_ITER)) return rc;
     INR_REQUIRE(grad_weights, INR_E_INVALID, "%s: null pointer (grad_weights)", who);
-    for (int a = 0; a < 3; ++a)
-        INR_REQUIRE(std::isfinite(grad_weights[a]) && grad_weights[a] >= 0.0, INR_E_INVALID,
-                    "%s: the gradient weights must be finite and >= 0 (g%d is %g)", who, a, grad_weights[a]);
+    if (int rc = tv_grad_weights_check(who, grad_weights)) return rc;
     if (int rc = tv3_kernel_check(who, k0, k1, k2, s, &kb)) return rc;
     if (int rc = check_ws_doubles(who, workspace, workspace_doubles, tv3_view(n, s, nullptr).total)) return rc;
     if (n == 0) return 0;
     Tv3Step c;
     c.g0 = grad_weights[0], c.g1 = grad_weights[1], c.g2 = grad_weights[2];
-    double gsum = 0.0;
-    if (H > 1) gsum += c.g1 * c.g1;
-    if (W > 1) gsum += c.g2 * c.g2;
-    if (D > 1) gsum += c.g0 * c.g0;
+    const double gsum = tv_grad_weight_sum(grad_weights, D, H, W);
     c.lam = gsum > 0.0 ? lam : 0.0;
     c.tau = gsum > 0.0 ? 1.0 / std::sqrt(4.0 * gsum) : 1.0 / std::sqrt(8.0);
     c.alpha = alpha;
     const Tv3View v = tv3_view(n, s, workspace);
     const long long voxels = (long long)n * D * H * W, items = (long long)n * s.parts;
     ProfScope ps(KC_OTHER, st);
-    hipLaunchKernelGGL((tv3_init_kernel<T>), dim3(tv3_voxel_grid(voxels)), dim3(TV3_THREADS), 0, st, v.state, y, x0, (long long)n, s);
+    hipLaunchKernelGGL((tv3_init_kernel<T>), dim3(tv_thread_grid(voxels, TV3_THREADS)), dim3(TV3_THREADS), 0, st, v.state, y, x0, (long long)n, s);
     INR_LAUNCH_CHECK();
     for (int it = 0; it < n_iter; ++it) {
         if (c.lam > 0.0) {
-            hipLaunchKernelGGL(tv3_dual_kernel, dim3(tv3_voxel_grid(voxels)), dim3(TV3_THREADS), 0, st, v.state, (long long)n, s, c);
+            hipLaunchKernelGGL(tv3_dual_kernel, dim3(tv_thread_grid(voxels, TV3_THREADS)), dim3(TV3_THREADS), 0, st, v.state, (long long)n, s, c);
             INR_LAUNCH_CHECK();
         }
-        hipLaunchKernelGGL((tv3_primal_kernel<T>), dim3(tv3_grid(items)), dim3(TV3_THREADS), 0, st, v.state, v.chpart, y, weight,
+        hipLaunchKernelGGL((tv3_primal_kernel<T>), dim3(tv_grid(items)), dim3(TV3_THREADS), 0, st, v.state, v.chpart, y, weight,
                            (long long)n, s, kb, c, (int)(it + 1 == n_iter));
         INR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL((tv3_final_kernel<T>), dim3(tv3_grid(items)), dim3(TV3_THREADS), 0, st, out, v.epart, v.state, y, weight,
+    hipLaunchKernelGGL((tv3_final_kernel<T>), dim3(tv_grid(items)), dim3(TV3_THREADS), 0, st, out, v.epart, v.state, y, weight,
                        (long long)n, s, kb, c);
     INR_LAUNCH_CHECK();
-    if (energy || change) {
-        hipLaunchKernelGGL(tv3_finish_kernel, dim3(tv3_grid(n)), dim3(TV3_THREADS), 0, st, energy, change, v.epart, v.chpart, (long long)n,
-                           s.parts, n_iter);
-        INR_LAUNCH_CHECK();
-    }
-    return 0;
+    // chpart is written in the last iteration only: without one there is nothing to read
+    return tv_finish<TV3_THREADS>(energy, change, nullptr, v.epart, s.parts, v.chpart, n_iter > 0 ? s.parts : 0, nullptr, 1.0, n, st);
 }
 
 int tv3_operator(const char* who, bool adjoint, double* out, const double* in, int n, int D, int H, int W, int f0, int f1, int f2,
@@ -516,10 +462,10 @@ int tv3_operator(const char* who, bool adjoint, double* out, const double* in, i
     if (n == 0) return 0;
     ProfScope ps(KC_OTHER, st);
     if (adjoint)
-        hipLaunchKernelGGL(tv3_adjoint_kernel, dim3(tv3_voxel_grid((long long)n * D * H * W)), dim3(TV3_THREADS), 0, st, out, in,
+        hipLaunchKernelGGL(tv3_adjoint_kernel, dim3(tv_thread_grid((long long)n * D * H * W, TV3_THREADS)), dim3(TV3_THREADS), 0, st, out, in,
                            (long long)n, s, kb);
     else
-        hipLaunchKernelGGL(tv3_apply_kernel, dim3(tv3_voxel_grid((long long)n * s.d * s.h * s.w)), dim3(TV3_THREADS), 0, st, out, in,
+        hipLaunchKernelGGL(tv3_apply_kernel, dim3(tv_thread_grid((long long)n * s.d * s.h * s.w, TV3_THREADS)), dim3(TV3_THREADS), 0, st, out, in,
                            (long long)n, s, kb);
     INR_LAUNCH_CHECK();
     return 0;

@@ -699,19 +699,60 @@ def siren_fit_footprint(desc: SirenDesc, params, grads, m, v, x_sub, target, wei
 TVSR_MAX_FACTOR, TVSR_MAX_SIDE = _lib.INR_TVSR_MAX_FACTOR, _lib.INR_TVSR_MAX_SIDE
 
 
-def _chk_images(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
-    """A contiguous device batch [n, rows, columns] of one of ``dtypes``."""
+def _chk_batch(t, name, rank, what, dtypes, shape=None, dtype_first=False) -> torch.Tensor:
+    """A contiguous device batch of ``rank`` axes -- ``what`` names them -- of one of ``dtypes`` and, where given, of ``shape``.
+    ``dtype_first``: the dtype, a host-only refusal, comes before the device."""
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
+    wrong_dtype = TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})") if t.dtype not in dtypes else None
+    if dtype_first and wrong_dtype:
+        raise wrong_dtype
     if not t.is_cuda:
         raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
-    if t.dtype not in dtypes:
-        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
-    if t.dim() != 3 or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous [n, rows, columns] batch (got {tuple(t.shape)})")
+    if wrong_dtype:
+        raise wrong_dtype
+    if t.dim() != rank or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {what} batch (got {tuple(t.shape)})")
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
     return t
+
+
+def _chk_images(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
+    return _chk_batch(t, name, 3, "[n, rows, columns]", dtypes, shape)
+
+
+def _tv_scalars(who, lam, alpha, n_iter, max_iter=None):
+    """(lam, alpha, n_iter) of a solve as the entry points take them; refuses what they would refuse."""
+    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
+    top = float("inf") if max_iter is None else max_iter
+    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= top:
+        bound = "n_iter >= 0" if max_iter is None else f"n_iter 0 .. {max_iter}"
+        raise ValueError(f"{who}: lam and alpha must be finite and >= 0, {bound} (got {lam!r}, {alpha!r}, {n_iter})")
+    return lam, alpha, n_iter
+
+
+def _grad_weights(who, grad_weights):
+    """(g0, g1, g2) of a 3-D prior as host floats."""
+    g = [float(v) for v in grad_weights]
+    if len(g) != 3 or not all(0.0 <= v < float("inf") for v in g):
+        raise ValueError(f"{who}: grad_weights are three finite values >= 0 (got {tuple(grad_weights)!r})")
+    return g
+
+
+def _f64_workspace(workspace, need, device) -> torch.Tensor:
+    """The caller's workspace, or a fresh one of ``need`` doubles."""
+    if workspace is None:
+        return torch.empty(need, dtype=torch.float64, device=device)
+    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
+        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
+    return workspace
+
+
+def _tv_results(y, entry, count=2):
+    """``count`` per-image float64 results (energy, change, ...) beside ``y`` [n, ...], and ``entry`` or its ``_f32`` twin by the dtype."""
+    results = [torch.zeros(y.shape[0], dtype=torch.float64, device=y.device) for _ in range(count)]
+    return results, entry if y.dtype == torch.float64 else entry + "_f32"
 
 
 def _block_kernel(kernel, factors):
@@ -771,20 +812,12 @@ def tvsr_solve(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_ite
         _chk_images(weight, "weight", (y.dtype,), y.shape)
     if x0 is not None:
         _chk_images(x0, "x0", (y.dtype,), (n, H, W))
-    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
-    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or n_iter < 0:
-        raise ValueError(f"tvsr_solve: lam and alpha must be finite and >= 0, n_iter >= 0 (got {lam!r}, {alpha!r}, {n_iter})")
+    lam, alpha, n_iter = _tv_scalars("tvsr_solve", lam, alpha, n_iter)
     out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
-    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
-    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    (energy, change), entry = _tv_results(y, "inr_tvsr_solve2d")
     if n == 0:
         return out, energy, change
-    need = tvsr_workspace_doubles(n, H, W)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
-    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
-        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
-    entry = "inr_tvsr_solve2d" if y.dtype == torch.float64 else "inr_tvsr_solve2d_f32"
+    workspace = _f64_workspace(workspace, tvsr_workspace_doubles(n, H, W), y.device)
     check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, H, W, f0,
                                 f1, k, lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()), entry)
     return out, energy, change
@@ -796,18 +829,7 @@ _TVJ_COUPLING = {"none": 0, "joint": 1}
 
 
 def _chk_groups(t, name, dtypes, shape=None) -> torch.Tensor:
-    """A contiguous device batch [n, channels, rows, columns] of one of ``dtypes``."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
-    if t.dtype not in dtypes:
-        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
-    if t.dim() != 4 or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous [n, channels, rows, columns] batch (got {tuple(t.shape)})")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    return t
+    return _chk_batch(t, name, 4, "[n, channels, rows, columns]", dtypes, shape)
 
 
 def tvj_workspace_doubles(n: int, channels: int, H: int, W: int) -> int:
@@ -839,20 +861,12 @@ def tvj_solve(y: torch.Tensor, factors, kernel, channel_weights, lam: float, alp
         _chk_groups(weight, "weight", (y.dtype,), y.shape)
     if x0 is not None:
         _chk_groups(x0, "x0", (y.dtype,), (n, ch, H, W))
-    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
-    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or n_iter < 0:
-        raise ValueError(f"tvj_solve: lam and alpha must be finite and >= 0, n_iter >= 0 (got {lam!r}, {alpha!r}, {n_iter})")
+    lam, alpha, n_iter = _tv_scalars("tvj_solve", lam, alpha, n_iter)
     out = torch.empty((n, ch, H, W), dtype=y.dtype, device=y.device)
-    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
-    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    (energy, change), entry = _tv_results(y, "inr_tvj_solve2d")
     if n == 0:
         return out, energy, change
-    need = tvj_workspace_doubles(n, ch, H, W)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
-    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
-        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
-    entry = "inr_tvj_solve2d" if y.dtype == torch.float64 else "inr_tvj_solve2d_f32"
+    workspace = _f64_workspace(workspace, tvj_workspace_doubles(n, ch, H, W), y.device)
     check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, ch, H, W,
                                 f0, f1, k, mu, lam, alpha, _TVJ_COUPLING[coupling], n_iter, workspace.data_ptr(), workspace.numel(),
                                 _stream()), entry)
@@ -880,23 +894,16 @@ def tgv_solve(y: torch.Tensor, factors, kernel, lam: float, ratio: float, alpha:
         _chk_images(weight, "weight", (y.dtype,), y.shape)
     if x0 is not None:
         _chk_images(x0, "x0", (y.dtype,), (n, H, W))
-    lam, ratio, alpha, n_iter = float(lam), float(ratio), float(alpha), int(n_iter)
-    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or n_iter < 0:
-        raise ValueError(f"tgv_solve: lam and alpha must be finite and >= 0, n_iter >= 0 (got {lam!r}, {alpha!r}, {n_iter})")
+    ratio = float(ratio)
+    lam, alpha, n_iter = _tv_scalars("tgv_solve", lam, alpha, n_iter)
     if not (0.0 < ratio < float("inf")):
         raise ValueError(f"tgv_solve: ratio must be finite and > 0 (got {ratio!r})")
     out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
     v = torch.empty((n, 2, H, W), dtype=y.dtype, device=y.device) if want_v else None
-    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
-    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    (energy, change), entry = _tv_results(y, "inr_tgv_solve2d")
     if n == 0:
         return out, v, energy, change
-    need = tgv_workspace_doubles(n, H, W)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
-    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
-        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
-    entry = "inr_tgv_solve2d" if y.dtype == torch.float64 else "inr_tgv_solve2d_f32"
+    workspace = _f64_workspace(workspace, tgv_workspace_doubles(n, H, W), y.device)
     check(getattr(lib(), entry)(out.data_ptr(), _ptr(v), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, H,
                                 W, f0, f1, k, lam, ratio, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()), entry)
     return out, v, energy, change
@@ -907,18 +914,7 @@ TVSR3D_MAX_ITER = _lib.INR_TVSR3D_MAX_ITER
 
 
 def _chk_volumes(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
-    """A contiguous device batch [n, slices, rows, columns] of one of ``dtypes``."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
-    if t.dtype not in dtypes:
-        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
-    if t.dim() != 4 or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous [n, slices, rows, columns] batch (got {tuple(t.shape)})")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
-    return t
+    return _chk_batch(t, name, 4, "[n, slices, rows, columns]", dtypes, shape)
 
 
 def _block_factors3d(kernel, factors):
@@ -988,24 +984,13 @@ def tvsr_solve3d(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_i
         _chk_volumes(weight, "weight", (y.dtype,), y.shape)
     if x0 is not None:
         _chk_volumes(x0, "x0", (y.dtype,), (n, D, H, W))
-    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
-    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= TVSR3D_MAX_ITER:
-        raise ValueError(f"tvsr_solve3d: lam and alpha must be finite and >= 0, n_iter 0 .. {TVSR3D_MAX_ITER} (got {lam!r}, {alpha!r}, "
-                         f"{n_iter})")
-    g = [float(v) for v in grad_weights]
-    if len(g) != 3 or not all(0.0 <= v < float("inf") for v in g):
-        raise ValueError(f"tvsr_solve3d: grad_weights are three finite values >= 0 (got {tuple(grad_weights)!r})")
+    lam, alpha, n_iter = _tv_scalars("tvsr_solve3d", lam, alpha, n_iter, TVSR3D_MAX_ITER)
+    g = _grad_weights("tvsr_solve3d", grad_weights)
     out = torch.empty((n, D, H, W), dtype=y.dtype, device=y.device)
-    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
-    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    (energy, change), entry = _tv_results(y, "inr_tvsr3d_solve")
     if n == 0:
         return out, energy, change
-    need = tvsr3d_workspace_doubles(n, D, H, W, f)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
-    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
-        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
-    entry = "inr_tvsr3d_solve" if y.dtype == torch.float64 else "inr_tvsr3d_solve_f32"
+    workspace = _f64_workspace(workspace, tvsr3d_workspace_doubles(n, D, H, W, f), y.device)
     check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, D, H, W,
                                 *f, *k, (C.c_double * 3)(*g), lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()),
           entry)
@@ -1018,16 +1003,7 @@ TVMF_MAX_FRAMES = _lib.INR_TVMF_MAX_FRAMES
 
 def _chk_frames(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
     """A contiguous device batch [n, frames, rows, columns] of one of ``dtypes``, 1 .. TVMF_MAX_FRAMES frames."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if t.dtype not in dtypes:                                         # before the device: a host-only refusal
-        raise TypeError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
-    if not t.is_cuda:
-        raise InrDeviceError(f"{name} is on {t.device}: the kernels only run on a HIP device (there is no CPU fallback)")
-    if t.dim() != 4 or not t.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous [n, frames, rows, columns] batch (got {tuple(t.shape)})")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    _chk_batch(t, name, 4, "[n, frames, rows, columns]", dtypes, shape, dtype_first=True)
     if not 1 <= t.shape[1] <= TVMF_MAX_FRAMES:
         raise ValueError(f"{name}: frames per image are 1 .. {TVMF_MAX_FRAMES} (got {t.shape[1]})")
     return t
@@ -1100,20 +1076,12 @@ def tvmf_solve(y: torch.Tensor, shifts: torch.Tensor, factors, kernel, lam: floa
         _chk_frames(weight, "weight", (y.dtype,), y.shape)
     if x0 is not None:
         _chk_images(x0, "x0", (y.dtype,), (n, H, W))
-    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
-    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= TVSR3D_MAX_ITER:
-        raise ValueError(f"tvmf_solve: lam and alpha must be finite and >= 0, n_iter 0 .. {TVSR3D_MAX_ITER} (got {lam!r}, {alpha!r}, "
-                         f"{n_iter})")
+    lam, alpha, n_iter = _tv_scalars("tvmf_solve", lam, alpha, n_iter, TVSR3D_MAX_ITER)
     out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
-    energy, change, valid = (torch.zeros(n, dtype=torch.float64, device=y.device) for _ in range(3))
+    (energy, change, valid), entry = _tv_results(y, "inr_tvmf_solve2d", 3)
     if n == 0:
         return out, energy, change, valid
-    need = tvmf_workspace_doubles(n, K, H, W, (f0, f1))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
-    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
-        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
-    entry = "inr_tvmf_solve2d" if y.dtype == torch.float64 else "inr_tvmf_solve2d_f32"
+    workspace = _f64_workspace(workspace, tvmf_workspace_doubles(n, K, H, W, (f0, f1)), y.device)
     check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), valid.data_ptr(), y.data_ptr(), shifts.data_ptr(),
                                 _ptr(weight), _ptr(x0), n, K, H, W, f0, f1, k, lam, alpha, n_iter, workspace.data_ptr(),
                                 workspace.numel(), _stream()), entry)
@@ -1212,23 +1180,13 @@ def tvms_solve(y: torch.Tensor, stacks, hr_shape, lam: float, alpha: float, n_it
         _chk_rows(weight, "weight", (y.dtype,), n, M)
     if x0 is not None:
         _chk_volumes(x0, "x0", (y.dtype,), (n, D, H, W))
-    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
-    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= TVSR3D_MAX_ITER:
-        raise ValueError(f"tvms_solve: lam and alpha must be finite and >= 0, n_iter 0 .. {TVSR3D_MAX_ITER} (got {lam!r}, {alpha!r}, "
-                         f"{n_iter})")
-    g = [float(v) for v in grad_weights]
-    if len(g) != 3 or not all(0.0 <= v < float("inf") for v in g):
-        raise ValueError(f"tvms_solve: grad_weights are three finite values >= 0 (got {tuple(grad_weights)!r})")
+    lam, alpha, n_iter = _tv_scalars("tvms_solve", lam, alpha, n_iter, TVSR3D_MAX_ITER)
+    g = _grad_weights("tvms_solve", grad_weights)
     out = torch.empty((n, D, H, W), dtype=y.dtype, device=y.device)
-    energy, change, valid = (torch.zeros(n, dtype=torch.float64, device=y.device) for _ in range(3))
+    (energy, change, valid), entry = _tv_results(y, "inr_tvms_solve", 3)
     if n == 0:
         return out, energy, change, valid
-    need = int(lib().inr_tvms_workspace_doubles(n, D, H, W, S, geo))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.float64, device=y.device)
-    elif workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
-        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
-    entry = "inr_tvms_solve" if y.dtype == torch.float64 else "inr_tvms_solve_f32"
+    workspace = _f64_workspace(workspace, int(lib().inr_tvms_workspace_doubles(n, D, H, W, S, geo)), y.device)
     check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), valid.data_ptr(), y.data_ptr(), _ptr(weight),
                                 _ptr(x0), n, D, H, W, S, geo, taps, (C.c_double * 3)(*g), lam, alpha, n_iter, workspace.data_ptr(),
                                 workspace.numel(), _stream()), entry)
@@ -1271,14 +1229,6 @@ def tvop_workspace_doubles(n: int, H: int, W: int, h: int, w: int) -> int:
     return int(lib().inr_tvop_workspace_doubles(int(n), int(H), int(W), int(h), int(w)))
 
 
-def _tvop_workspace(workspace, need, device):
-    if workspace is None:
-        return torch.empty(need, dtype=torch.float64, device=device)
-    if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float64 or not workspace.is_cuda or workspace.numel() < need:
-        raise ValueError(f"workspace must be a device float64 tensor of at least {need} elements")
-    return workspace
-
-
 def tvop_apply(x: torch.Tensor, operators, workspace=None) -> torch.Tensor:
     """``inr_tvop_apply``: ``x`` [n, H, W] float64 -> ``A x = R0 x R1^T`` [n, h, w]; ``operators`` = (R0 [h, H], R1 [w, W]), device
     float64; ``workspace``: a float64 tensor of ``tvop_workspace_doubles(n, H, W, h, w)``."""
@@ -1291,7 +1241,7 @@ def tvop_apply(x: torch.Tensor, operators, workspace=None) -> torch.Tensor:
     out = torch.empty((n, h, w), dtype=torch.float64, device=x.device)
     if n == 0:
         return out
-    workspace = _tvop_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), x.device)
+    workspace = _f64_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), x.device)
     check(lib().inr_tvop_apply(out.data_ptr(), x.data_ptr(), r0.data_ptr(), r1.data_ptr(), n, H, W, h, w, workspace.data_ptr(),
                                workspace.numel(), _stream()), "inr_tvop_apply")
     return out
@@ -1308,7 +1258,7 @@ def tvop_adjoint(r: torch.Tensor, operators, workspace=None) -> torch.Tensor:
     out = torch.empty((n, H, W), dtype=torch.float64, device=r.device)
     if n == 0:
         return out
-    workspace = _tvop_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), r.device)
+    workspace = _f64_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), r.device)
     check(lib().inr_tvop_adjoint(out.data_ptr(), r.data_ptr(), r0.data_ptr(), r1.data_ptr(), n, H, W, h, w, workspace.data_ptr(),
                                  workspace.numel(), _stream()), "inr_tvop_adjoint")
     return out
@@ -1328,17 +1278,12 @@ def tvop_solve(y: torch.Tensor, operators, lam: float, alpha: float, n_iter: int
         _chk_images(weight, "weight", (y.dtype,), y.shape)
     if x0 is not None:
         _chk_images(x0, "x0", (y.dtype,), (n, H, W))
-    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
-    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= TVSR3D_MAX_ITER:
-        raise ValueError(f"tvop_solve: lam and alpha must be finite and >= 0, n_iter 0 .. {TVSR3D_MAX_ITER} (got {lam!r}, {alpha!r}, "
-                         f"{n_iter})")
+    lam, alpha, n_iter = _tv_scalars("tvop_solve", lam, alpha, n_iter, TVSR3D_MAX_ITER)
     out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
-    energy = torch.zeros(n, dtype=torch.float64, device=y.device)
-    change = torch.zeros(n, dtype=torch.float64, device=y.device)
+    (energy, change), entry = _tv_results(y, "inr_tvop_solve2d")
     if n == 0:
         return out, energy, change
-    workspace = _tvop_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), y.device)
-    entry = "inr_tvop_solve2d" if y.dtype == torch.float64 else "inr_tvop_solve2d_f32"
+    workspace = _f64_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), y.device)
     check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), r0.data_ptr(),
                                 r1.data_ptr(), n, H, W, h, w, lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()),
           entry)

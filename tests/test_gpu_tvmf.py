@@ -145,6 +145,13 @@ def test_solver_matches_the_restatement_on_ragged_shapes(shape, f):
         _compare(f"{shape} {f} {name}", frames, f, shifts, kernel, 0.02, 0.05, 40, w=w, x0=rng.random(hr.shape))
 
 
+def test_more_partials_than_the_finish_has_threads():
+    """512 x 512 with unit factors and one frame is 512 parts: every thread of the finish kernel adds (maximises) two partials of
+    energy, change and the count of valid data.  The bounds of _compare."""
+    rng = np.random.default_rng(512)
+    _compare("512x512 (1, 1), K = 1, 512 parts", rng.random((1, 1, 512, 512)), (1, 1), np.array([[(0.25, -0.5)]]), "mean", 0.05, 0.02, 3)
+
+
 def test_one_frame_and_unit_factors_match_the_restatement():
     rng = np.random.default_rng(21)
     hr = rng.random((1, 12, 10))

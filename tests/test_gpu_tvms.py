@@ -119,6 +119,14 @@ def test_solver_matches_the_restatement_with_and_without_x0_and_weights():
         _compare(f"7x9x10, stack {s} alone", [ys[s]], [st], M.CASE_SHAPE, M.CASE_LAM, M.CASE_ALPHA, 50, w=[ws[s]])
 
 
+def test_more_partials_than_the_finish_has_threads():
+    """33 x 64 x 64 under one unit stack is 135,168 voxels and as many data, 264 parts: eight threads of the finish kernel add
+    (maximise) two partials of energy, change and the count of valid data.  The bounds of _compare."""
+    hr = (33, 64, 64)
+    unit = M.stack((1, 1, 1), (M.ONE, M.ONE, M.ONE), (0, 0, 0), hr)
+    _compare("33x64x64, one unit stack, 264 parts", [np.random.default_rng(264).random(hr)], [unit], hr, 0.05, 0.02, 3)
+
+
 def test_one_slice_is_an_image_and_matches_the_multi_frame_solver():
     rng = np.random.default_rng(3)
     hr = rng.random((12, 10))

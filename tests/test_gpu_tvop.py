@@ -98,6 +98,22 @@ def test_ragged_shapes_against_the_restatement(shape, lr_shape):
             assert e_x <= C.X_BOUND and e_ch <= C.CHANGE_BOUND and e_en <= C.ENERGY_REL
 
 
+@pytest.mark.parametrize("n_iter", (0, 2))
+def test_more_partials_than_the_finish_has_threads(n_iter):
+    """(1024, 1024) -> (64, 64) is 1 LR tile and 256 HR tiles, 257 energy partials: thread 0 of the finish kernel adds two.  Without
+    an iteration the change partials are never written and the change is 0."""
+    pair = C.random_pair((1024, 1024), (64, 64), seed=2)
+    y = np.random.default_rng(257).random((1, 64, 64))
+    want, _, want_ch = C.solve(y, *pair, 0.05, 0.02, n_iter, return_info=True)
+    got, info = baselines.tv_superres_operator(y, pair, 0.05, 0.02, n_iter, return_info=True)
+    at = C.energy(got, y, *pair, 0.05, 0.02, None)
+    e_x, e_ch, e_en = np.abs(got - want).max(), np.abs(info["change"] - want_ch).max(), (np.abs(info["energy"] - at) / at).max()
+    print(f"(1024, 1024) -> (64, 64), {n_iter} iterations: max|x diff| {e_x:.2e}, change {info['change'].tolist()} (diff {e_ch:.2e}), "
+          f"energy rel diff {e_en:.2e}")
+    assert e_x <= C.X_BOUND and e_ch <= C.CHANGE_BOUND and e_en <= C.ENERGY_REL
+    assert n_iter > 0 or not info["change"].any()
+
+
 def test_the_minimum_is_reached():
     hr, y, w, pair = _case()
     low = _case_minimum()

@@ -109,6 +109,21 @@ def test_solver_matches_the_restatement_on_ragged_extents(shape, f):
     _compare(f"{shape} {f} mean, plain TV", T.apply_A(hr, T.block_table(T.block_factors("mean", f))), f, "mean", 0.02, 0.0, 20)
 
 
+@pytest.mark.parametrize("n_iter", (0, 3))
+def test_more_partials_than_the_finish_has_threads(n_iter):
+    """257 x 1 x 1 with unit factors is 257 tiles: thread 0 of the finish kernel adds (maximises) two partials.  The energy against
+    the restated objective at the returned volume, within the 1e-12 relative of the other energy checks of this file; without an
+    iteration the change partials are never written and the change is 0."""
+    y = np.random.default_rng(257).random((2, 257, 1, 1))
+    k = (np.ones(1), np.ones(1), np.ones(1))
+    got, info = _compare("257x1x1 (1, 1, 1), 257 tiles", y, (1, 1, 1), k, 0.05, 0.02, n_iter)
+    at = T.energy(got, y, T.block_table(k), 0.05, 0.02)
+    e_rel = float((np.abs(info["energy"] - at) / np.abs(at)).max())
+    print(f"energy {info['energy'].tolist()} against the restated objective at the returned volume: {e_rel:.2e} relative")
+    assert e_rel <= 1e-12
+    assert n_iter > 0 or not info["change"].any()
+
+
 @pytest.fixture(scope="module")
 def pat07():
     return T.pat07_roi()                    # [28, 50, 50] in [0, 1]

@@ -156,6 +156,46 @@ def test_header_library_and_ctypes_table_carry_the_symbols():
     assert np.array_equal(drivers.second_order_phantom(), G.phantom())
 
 
+def test_the_family_has_one_definition_of_what_it_shares():
+    """the Huber function, the floor division, the stride-loop grids, the parameter refusals and the finish kernel
+    live once in tv_shared.h, the phases of the three single-workgroup kernels once in tv_block.h, and no unit keeps a copy."""
+    csrc = os.path.join(ROOT, "mri-super-resolution_amd", "csrc")
+    read = lambda name: open(os.path.join(csrc, name)).read()
+    shared, block = read("tv_shared.h"), read("tv_block.h")
+    units = {name: read(name) for name in ("tvsr.hip", "tvsr3d.hip", "tvmf.hip", "tvms.hip", "tvop.hip", "tvj.hip", "tgv.hip")}
+    for name in ("tvsr3d.hip", "tvms.hip", "tvop.hip"):
+        assert '#include "tv_shared.h"' in units[name], name
+    for name in ("tvsr.hip", "tvj.hip", "tgv.hip", "tvmf.hip"):          # through tv_block.h, whose checks tvmf.hip calls
+        assert '#include "tv_block.h"' in units[name], name
+    assert '#include "tv_shared.h"' in block
+    for text in ("double tv_huber(", "int tv_floordiv(", "unsigned tv_grid(", "unsigned tv_thread_grid(", "double block_max_f64(",
+                 "int tv_params_check(", "int tv_grad_weights_check(", "double tv_grad_weight_sum(", "TvStateView tv_state_view(",
+                 " tv_finish_kernel("):
+        assert shared.count(text) == 1 and text not in block, text
+    for text in ("void tv_start_pixel(", "void tv_primal_block(", "void tv_add_data_term(", "void tv_store_energy_change(",
+                 "int tv_shape_check(", "int tv_block_check(", "unsigned tv_pixel_grid("):
+        assert block.count(text) == 1 and text not in shared, text
+    # the phase helpers hold no barrier: the only ones of tv_block.h are the four of the reduction after the iterations
+    phases = block.split("void tv_store_energy_change(")[0]
+    assert "__syncthreads" not in re.sub(r"//.*", "", phases) and block.count("__syncthreads();") == 4
+    for name, src in units.items():
+        code = re.sub(r"//.*", "", src)
+        assert not re.search(r"\bdouble\s+\w*huber\w*\s*\(", code), name                     # no Huber function of its own
+        assert not re.search(r"\bunsigned\s+\w*grid\w*\s*\(", code), name                    # no *_grid
+        assert not re.search(r"\bint\s+\w*floordiv\w*\s*\(", code), name                     # no *_floordiv
+        assert not re.search(r"\w*finish_kernel\s*\(\s*double", code), name                  # no *_finish_kernel
+        assert not re.search(r"\bdouble\s+\w*block_max\w*\s*\(", code) and "fmax(fmax(red[0]" not in code, name
+        assert "n_iter must be" not in src and "lambda must be finite" not in src and "alpha must be finite" not in src, name
+        assert not re.search(r"struct\s+\w*View\s*\{\s*double\s*\*\s*state;\s*size_t total;", code), name
+    for name in ("tvsr.hip", "tvj.hip", "tgv.hip"):
+        # the shared phases are called, the loops and the two barriers of an iteration stay in the unit
+        for call in ("tv_start_pixel(", "tv_primal_block(", "tv_add_data_term(", "tv_store_energy_change("):
+            assert units[name].count(call) == 1, (name, call)
+        assert units[name].count("__syncthreads();   // barrier") == 2, name
+    for name in ("tvsr3d.hip", "tvmf.hip", "tvms.hip", "tvop.hip"):
+        assert units[name].count("tv_finish<") == 1 and units[name].count("tv_params_check(") == 1, name
+
+
 def test_workspace_plan():
     plan = _lib.lib().inr_tgv_workspace_doubles
     # x | xbar | v0 | v1 | vbar0 | vbar1 | p0 | p1 | r00 | r11 | r01 of every image, nothing else
