@@ -749,6 +749,52 @@ int inr_tvj_solve2d_f32(float* out, double* energy, double* change, const float*
                         double lambda, double alpha, int coupling, int n_iter, double* workspace, int64_t workspace_doubles,
                         void* stream);
 
+/* ---- model-based S0 / ADC super-resolution: the mono-exponential model inside the solver, a TV prior on the maps ------
+ * No counterpart in the reference.  A group is the C = channels b-values of one slice, 2 <= C <= INR_TVJ_MAX_CHANNELS, y
+ * [n_groups][C][h][w] (LR); the unknowns are the two parameter maps, out [n_groups][2][H][W]: map 0 the b = 0 signal s, map 1 the ADC d.
+ * Sides, factors and the HOST `kernel` as for inr_tvsr_solve2d.  `b` is a HOST array [C] of finite b-values >= 0, not all equal;
+ * `map_weights` a HOST array (mu_s, mu_u) of finite doubles in [0, 1], or null (both 1).
+ * inr_tvadc_solve2d: out = n_iter iterations of the exact nonlinear primal-dual method (Valkonen 2014) on
+ *   min 1/2 sum_c sum_i w_ci ((A (s .* exp(-b_c d)))_i - y_ci)^2 + lambda R(s, d),   0 <= s <= s_max,  0 <= d <= adc_max
+ *   R = sum_j H_alpha( sqrt( mu_s^2 |(grad s)_j|^2 + mu_u^2 |(grad u)_j|^2 ) )   (coupling 1: joint)
+ *   R = sum_j H_alpha( mu_s |(grad s)_j| ) + sum_j H_alpha( mu_u |(grad u)_j| ) (coupling 0: none)
+ *   in the normalised ADC u = d b_max (beta_c = b_c / b_max, u_max = adc_max b_max), from s = sbar, u = ubar, p = 0, z = 0:
+ *     q_m <- (p_m + sigma (mu_m grad(mbar))) / (1 + sigma alpha / lambda), m in {s, u};  n <- sqrt(|q_s|^2 + |q_u|^2) / lambda (none:
+ *     per map);  p_m <- n > 1 ? q_m / n : q_m                                                              (lambda == 0: p = 0)
+ *     r <- (A (sbar .* exp(-beta_c ubar)))_i - y_ci;  z_ci <- (z_ci + sigma r) / (1 + sigma / w_ci)         (w_ci == 0: z_ci = 0)
+ *     g_s <- sum_c exp(-beta_c u) (A^T z_c) - mu_s div(p_s);  g_u <- sum_c (-beta_c s exp(-beta_c u)) (A^T z_c) - mu_u div(p_u)
+ *     s' <- fmin(fmax(s - tau g_s, 0), s_max);  u' <- fmin(fmax(u - tau g_u, 0), u_max);  sbar <- 2 s' - s;  ubar <- 2 u' - u
+ *   with tau = sigma = 1 / sqrt(8 + c_A sum_c (1 + beta_c^2 s_max^2)), c_A = (sum |k|)(max |k|): a bound on the Jacobian of the whole
+ *   operator that holds everywhere on the box.  Convergence of the nonlinear method is local; the objective is not convex.  The start:
+ *   x0 [n_groups][2][H][W] (s, d) clamped into the box, or (x0 null) the block replication of the first channel of smallest b, clamped,
+ *   and d = adc0.  weight [n_groups][C][h][w] or null (all 1): weight 0 is a missing datum whose y is never read by the iteration.
+ *   energy / change [n_groups] DEVICE doubles or null: the objective at the returned fp64 maps (fixed order, no float atomics) and
+ *   max(|s' - s|, |u' - u|) of the last iteration.  ONE launch, no host read: one workgroup of 1,024 threads per group runs all
+ *   iterations with workgroup barriers only; groups beyond the CU count are queued.  fp64 exp, 2 C calls per pixel and iteration.  The
+ *   _f32 form reads y / weight / x0 and writes out as fp32, fp64 inside, rounded once.  n_groups == 0 succeeds and launches nothing.
+ * workspace: inr_tvadc_workspace_doubles(n_groups, C, H, W, f0, f1) = n (8 H W + C h w) doubles (s | u | sbar | ubar | p_s0 | p_s1 | p_u0
+ * | p_u1 and z of every group; n = 1 for n_groups == 0), 16-byte aligned; 0 for sizes that would be refused.  Refusals, all before any
+ * device work: INR_E_INVALID (null out / y / b / kernel, n_groups < 0, channels outside 2 .. INR_TVJ_MAX_CHANNELS, factors or sizes out
+ * of range, H or W no multiple of its factor, n_iter < 0, a negative or non-finite lambda / alpha, coupling not 0 / 1, a kernel that is
+ * not finite or does not sum to 1, a b-value that is not finite or negative, b-values all equal, s_max or adc_max not finite and > 0,
+ * adc0 outside [0, adc_max], a map weight that is not finite or outside [0, 1]), INR_E_WORKSPACE (null or short workspace), INR_E_ALIGN
+ * (workspace off a 16-byte boundary).
+ * inr_adc_signal: out [n_maps][C][pixels] = s0 [n_maps][pixels] exp(-b_c adc [n_maps][pixels]), the model's images of two maps; `b` a HOST
+ * array [C] of finite doubles, 1 <= C <= INR_TVJ_MAX_CHANNELS; fp64 inside, the _f32 form rounds once. */
+int64_t inr_tvadc_workspace_doubles(int n_groups, int channels, int height, int width, int f0, int f1);
+int inr_tvadc_solve2d(double* out, double* energy, double* change, const double* y, const double* weight, const double* x0, int n_groups,
+                      int channels, int height, int width, int f0, int f1, const double* kernel, const double* b,
+                      const double* map_weights, double lambda, double alpha, int coupling, int n_iter, double s_max, double adc_max,
+                      double adc0, double* workspace, int64_t workspace_doubles, void* stream);
+int inr_tvadc_solve2d_f32(float* out, double* energy, double* change, const float* y, const float* weight, const float* x0, int n_groups,
+                          int channels, int height, int width, int f0, int f1, const double* kernel, const double* b,
+                          const double* map_weights, double lambda, double alpha, int coupling, int n_iter, double s_max,
+                          double adc_max, double adc0, double* workspace, int64_t workspace_doubles, void* stream);
+int inr_adc_signal(double* out, const double* s0, const double* adc, const double* b, int64_t n_maps, int channels, int64_t pixels,
+                   void* stream);
+int inr_adc_signal_f32(float* out, const float* s0, const float* adc, const double* b, int64_t n_maps, int channels, int64_t pixels,
+                       void* stream);
+
 /* ---- second-order TGV super-resolution under the block operator: a prior that does not terrace smooth intensity -------
  * No counterpart in the reference.  Images, sides, factors and the HOST `kernel` as for inr_tvsr_solve2d.  An auxiliary field
  * v = (v0, v1) [n_images][2][H][W] absorbs the smooth part of the gradient (Bredies, Kunisch, Pock 2010; Knoll et al. 2011):

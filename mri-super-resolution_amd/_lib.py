@@ -214,6 +214,14 @@ SIGNATURES = {
                                                                                                 C.c_void_p, C.c_int64, c_stream]),
     "inr_tvj_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 6 +
                             [C.POINTER(C.c_double)] * 2 + [C.c_double, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvadc_workspace_doubles": (C.c_int64, [C.c_int] * 6),
+    "inr_tvadc_solve2d": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 6 + [C.POINTER(C.c_double)] * 3 +
+                          [C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_int64, c_stream]),
+    "inr_tvadc_solve2d_f32": (C.c_int, [c_f32p, C.c_void_p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 6 +
+                              [C.POINTER(C.c_double)] * 3 + [C.c_double, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                             C.c_double, C.c_void_p, C.c_int64, c_stream]),
+    "inr_adc_signal": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int64, c_stream]),
+    "inr_adc_signal_f32": (C.c_int, [c_f32p] * 3 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int64, c_stream]),
     "inr_tgv_workspace_doubles": (C.c_int64, [C.c_int] * 3),
     "inr_tgv_solve2d": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int,
                                                                     C.c_void_p, C.c_int64, c_stream]),

@@ -51,6 +51,11 @@ GEMMs per operator application inside the iteration (``inr_tvop_solve2d``, DESIG
 DWI slice --: one gradient norm per pixel over all channels (vectorial TV / Huber), so that the low-SNR channels take their edges
 from the others.  One workgroup per group (``inr_tvj_solve2d``); what ``superresDWI --tv_joint`` and
 ``scripts/joint_bvalues`` score.
+
+``tv_superres_adc`` and ``adc_signal`` put the mono-exponential model inside the block solver: the unknowns of a group of b-values are
+the two parameter maps, the b = 0 signal and the ADC, in a box, under a Huber-TV prior on the maps; the exact nonlinear primal-dual
+method with the data term dualised, one workgroup per group (``inr_tvadc_solve2d``); what ``superresDWI --tv_adc`` and
+``scripts/joint_bvalues --with_adc_model`` score.
 """
 from __future__ import annotations
 
@@ -455,6 +460,113 @@ def tv_superres_joint(lr, factors, kernel="mean", lam: float = TVJ_DEFAULT_LAMBD
     y = _device_batch(lr, as_numpy, 3)
     out, energy, change = ops.tvj_solve(y, (f0, f1), k, mu, lam, huber, coupling, n_iter, extra["weight"], extra["x0"])
     return _tv_output(as_numpy, lead, out, (C, h * f0, w * f1), {"energy": energy, "change": change}, return_info)
+
+
+# the sweep of DESIGN.md 4t (ADC RMSE of the solver's map subject to the b = 0 PSNR of the per-channel solver, noise 0.02)
+ADC_DEFAULT_LAMBDA, ADC_DEFAULT_HUBER, ADC_DEFAULT_ITERS = 0.00125, 0.03, 3000
+ADC_DEFAULT_MAP_WEIGHTS, ADC_DEFAULT_COUPLING = (1.0, 0.05), "joint"
+ADC_DEFAULT_S_MAX, ADC_DEFAULT_ADC_MAX, ADC_DEFAULT_ADC0 = 1.5, 4e-3, 1e-3
+
+
+def _adc_model(who, b, channels, map_weights, coupling, s_max, adc_max, adc0):
+    """The model's host values of ``tv_superres_adc``, refused by name: -> (b, (mu_s, mu_d), s_max, adc_max, adc0) as floats."""
+    try:
+        vals = np.asarray(b, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: b must be a sequence of b-values (got {b!r})") from None
+    if not 2 <= channels <= ops.TVJ_MAX_CHANNELS:
+        raise ValueError(f"{who}: b-values are 2 .. {ops.TVJ_MAX_CHANNELS} per group (got {channels})")
+    if vals.shape != (channels,):
+        raise ValueError(f"{who}: b has {vals.size} b-values, expected one per channel ({channels})")
+    if not (np.isfinite(vals).all() and (vals >= 0).all()):
+        raise ValueError(f"{who}: b-values must be finite and >= 0 (got {vals.tolist()})")
+    if vals.max() == vals.min():
+        raise ValueError(f"{who}: the b-values are all equal ({vals[0]!r}): they determine no ADC")
+    if coupling not in ("joint", "none"):
+        raise ValueError(f"{who}: coupling must be 'joint' or 'none' (got {coupling!r})")
+    try:
+        mu = np.asarray(map_weights, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        mu = np.zeros(0)
+    if mu.shape != (2,) or not (np.isfinite(mu).all() and (mu >= 0).all() and (mu <= 1).all()):
+        raise ValueError(f"{who}: map_weights are (mu_s, mu_d), two finite values within [0, 1] (got {map_weights!r}); larger weights are "
+                         f"a rescaled lam and huber")
+    s_max, adc_max, adc0 = float(s_max), float(adc_max), float(adc0)
+    if not 0.0 < s_max < np.inf:
+        raise ValueError(f"{who}: s_max must be finite and > 0 (got {s_max!r})")
+    if not 0.0 < adc_max < np.inf or not adc_max * vals.max() < np.inf:
+        raise ValueError(f"{who}: adc_max must be finite and > 0 (got {adc_max!r})")
+    if not 0.0 <= adc0 <= adc_max:
+        raise ValueError(f"{who}: adc0 must be within [0, adc_max] (got {adc0!r}, adc_max {adc_max!r})")
+    return vals.tolist(), mu.tolist(), s_max, adc_max, adc0
+
+
+def tv_superres_adc(lr, b, factors, kernel="mean", lam: float = ADC_DEFAULT_LAMBDA, huber: float = ADC_DEFAULT_HUBER,
+                    n_iter: int = ADC_DEFAULT_ITERS, map_weights=ADC_DEFAULT_MAP_WEIGHTS, coupling: str = ADC_DEFAULT_COUPLING,
+                    s_max: float = ADC_DEFAULT_S_MAX, adc_max: float = ADC_DEFAULT_ADC_MAX, adc0: float = ADC_DEFAULT_ADC0, weight=None,
+                    x0=None, return_info: bool = False):
+    """Model-based super-resolution of the two PARAMETER MAPS of a multi-b-value group: ``lr`` [..., C, h, w], the third axis from the
+    end the b-values ``b`` [C] of a slice (2 <= C <= 16, finite, >= 0, not all equal), leading axes a batch of groups.  ``n_iter``
+    iterations of the exact nonlinear primal-dual method on
+    ``1/2 sum_c sum w (A (s0 exp(-b_c adc)) - lr_c)^2 + lam R(s0, adc)`` over ``0 <= s0 <= s_max``, ``0 <= adc <= adc_max``, with the
+    block operator ``A`` of ``tv_superres`` and the Huber-TV prior of ``tv_superres_joint`` on the two maps -- the ADC normalised by the
+    largest b-value --: ``coupling='joint'`` one gradient norm per pixel over both maps, ``'none'`` one per map; ``map_weights`` =
+    (mu_s, mu_d) in [0, 1].  Two unknowns per pixel instead of C: noise in the high-b channels can only enter through the ADC, both
+    maps are non-negative, and the ADC needs no clipped logarithm.  The objective is not convex and the method converges locally: from
+    the default start -- the block replication of the lowest b-value and ``adc0`` everywhere -- it needs about three times the
+    iterations of ``tv_superres_joint``.  -> ``(s0 [..., H, W], adc [..., H, W])``, and with ``return_info`` a dict with ``energy`` (the
+    objective at the result) and ``change`` (max |s' - s|, |u' - u| of the last iteration, u the normalised ADC) of the leading shape.
+    ``x0``: a pair ``(s0, adc)`` of HR maps, clamped into the box; ``weight`` (shape of ``lr``, >= 0; 0 a missing datum).  ndarray in ->
+    float64 ndarrays out; device fp32 / fp64 tensor in -> the same out (fp64 inside, rounded once).  One launch for the whole batch,
+    one workgroup per group (``inr_tvadc_solve2d``).  There is no CPU fallback."""
+    who = "tv_superres_adc"
+    f0, f1, k = _block_kernel(who, kernel, factors)
+    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter)
+    as_numpy = _fourier_input(who, lr)
+    if lr.ndim < 3:
+        raise ValueError(f"{who} needs at least 3-D input [..., C, h, w]")
+    C, h, w, lead = int(lr.shape[-3]), int(lr.shape[-2]), int(lr.shape[-1]), tuple(lr.shape[:-3])
+    vals, mu, s_max, adc_max, adc0 = _adc_model(who, b, C, map_weights, coupling, s_max, adc_max, adc0)
+    H, W = h * f0, w * f1
+    _hr_sides(who, H, W, f0, f1)
+    if x0 is not None:
+        if not isinstance(x0, (tuple, list)) or len(x0) != 2:
+            raise ValueError(f"{who}: x0 is a pair (s0, adc) of maps of shape {lead + (H, W)}")
+        for m in x0:
+            if isinstance(m, np.ndarray) != as_numpy:
+                raise TypeError(f"{who}: x0 must be given like lr ({'ndarrays' if as_numpy else 'device tensors'})")
+            _fourier_input(who, m)
+            if tuple(m.shape) != lead + (H, W) or (not as_numpy and m.dtype != lr.dtype):
+                raise ValueError(f"{who}: x0 is a pair (s0, adc) of maps of shape {lead + (H, W)} and the type of lr (got "
+                                 f"{tuple(m.shape)}, {m.dtype})")
+        x0 = np.stack(x0, axis=-3) if as_numpy else torch.stack(tuple(x0), dim=-3)
+    extra = _weight_and_start(who, lr, as_numpy, lead, weight, (C, h, w), x0, (2, H, W))
+    y = _device_batch(lr, as_numpy, 3)
+    s0, adc, energy, change = ops.tvadc_solve(y, vals, (f0, f1), k, mu, lam, huber, coupling, n_iter, s_max, adc_max, adc0,
+                                              extra["weight"], extra["x0"])
+    info = {name: v.reshape(lead) for name, v in (("energy", energy), ("change", change))}
+    s0, adc = s0.reshape(*lead, H, W), adc.reshape(*lead, H, W)
+    if as_numpy:
+        s0, adc, info = s0.cpu().numpy(), adc.cpu().numpy(), {name: v.cpu().numpy() for name, v in info.items()}
+    return (s0, adc, info) if return_info else (s0, adc)
+
+
+def adc_signal(s0, adc, b):
+    """The images of the mono-exponential model, ``s0 exp(-b_c adc)`` [..., C, H, W], of two maps [..., H, W] of one shape and type and
+    1 .. 16 finite b-values (``inr_adc_signal``; fp64 inside, rounded once).  ndarrays in -> float64 ndarray out, device fp32 / fp64
+    tensors in -> the same out."""
+    who = "adc_signal"
+    as_numpy, H, W, lead = _block_input(who, s0)
+    if isinstance(adc, np.ndarray) != as_numpy:
+        raise TypeError(f"{who}: adc must be given like s0 ({'an ndarray' if as_numpy else 'a device tensor'})")
+    _fourier_input(who, adc)
+    if tuple(adc.shape) != tuple(s0.shape) or (not as_numpy and adc.dtype != s0.dtype):
+        raise ValueError(f"{who}: adc must have the shape and type of s0 ({tuple(s0.shape)}; got {tuple(adc.shape)}, {adc.dtype})")
+    vals = np.asarray(b, np.float64).reshape(-1)
+    if not 1 <= vals.size <= ops.TVJ_MAX_CHANNELS or not np.isfinite(vals).all():
+        raise ValueError(f"{who}: b is 1 .. {ops.TVJ_MAX_CHANNELS} finite b-values (got {vals.tolist()})")
+    out = ops.adc_signal(_block_batch(s0, as_numpy), _block_batch(adc, as_numpy), vals.tolist()).reshape(*lead, vals.size, H, W)
+    return out.cpu().numpy() if as_numpy else out
 
 
 TGV_DEFAULT_LAMBDA, TGV_DEFAULT_RATIO, TGV_DEFAULT_HUBER, TGV_DEFAULT_ITERS = 0.005, 0.5, 0.0, 300   # the sweep of DESIGN.md 4r

@@ -1,4 +1,5 @@
-// What the block-operator TV / Huber units share (tvsr.hip, tvj.hip, tgv.hip; the shape and kernel checks also serve tvmf.hip): the shape
+// What the block-operator TV / Huber units share (tvsr.hip, tvj.hip, tgv.hip; the shape and kernel checks also serve tvmf.hip and
+// tvadc.hip, whose nonlinear phases are its own, and tvadc.hip reduces with tv_store_energy_change): the shape
 // and the block kernel of a call with their checks, the block sum (A x), and the phases that the three single-workgroup kernels have
 // in common -- the start, the primal block step, the data term of the objective and the reduction of energy and change.  One
 // definition: the units compute the same bits where their problems coincide.  What the whole family shares is in tv_shared.h.

@@ -1350,6 +1350,27 @@ def check_joint_bvalues(side=50, n_b=4, factor=2, kernel="mean", noise=0.02, tv_
     return int(side) // int(factor)
 
 
+def check_adc_model(bvalues=SYNTHETIC_B, lam=None, weight=None, iters=None):
+    """What the ``tv_adc`` row of ``joint_bvalue_study`` cannot serve, by name; touches no device.  -> (lam, weight, iters), the
+    ``ADC_DEFAULT_*`` where None."""
+    from . import baselines
+
+    who = "joint_bvalue_study"
+    lam = baselines.ADC_DEFAULT_LAMBDA if lam is None else lam
+    weight = baselines.ADC_DEFAULT_MAP_WEIGHTS[1] if weight is None else weight
+    iters = baselines.ADC_DEFAULT_ITERS if iters is None else iters
+    b = np.asarray(bvalues, np.float64).reshape(-1)
+    if not (np.isfinite(b).all() and (b >= 0).all()) or np.ptp(b) == 0:
+        raise ValueError(f"{who}: the S0 / ADC model needs finite b-values >= 0 that are not all equal (got {b.tolist()})")
+    if not 0.0 <= float(lam) < float("inf"):
+        raise ValueError(f"{who}: tv_adc_lambda must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= float(weight) <= 1.0:
+        raise ValueError(f"{who}: tv_adc_weight must be within [0, 1] (got {weight!r})")
+    if int(iters) != iters or not 1 <= iters <= ops.TVSR3D_MAX_ITER:
+        raise ValueError(f"{who}: tv_adc_iters must be 1 .. 100,000 (got {iters!r})")
+    return float(lam), float(weight), int(iters)
+
+
 def synthetic_decay(slices, bvalues=SYNTHETIC_B):
     """``slices`` [Z, R, R] in [0, 1] -> [Z, B, R, R]: a mono-exponential decay whose ADC is high where the in-plane smoothed image
     (Gaussian, sigma 1) is dark, ``0.6e-3 + 1.8e-3 (1 - smooth / max)``: the study case of DESIGN.md 4q."""
@@ -1368,7 +1389,7 @@ def loglinear_adc(x, bvalues):
 
 
 def joint_bvalue_study(hr, bvalues, factor=2, kernel="mean", noise=0.02, seed=0, tv_lambda=None, tv_joint_lambda=None, tv_huber=None,
-                       tv_iters=None, weights="equal", slice_ids=None):
+                       tv_iters=None, weights="equal", slice_ids=None, adc_model=None):
     """``hr`` [Z, B, R, R] in [0, 1], the B b-values of Z slices: the LR stack [Z, B, m, m] is ``baselines.block_apply`` under ``kernel``
     plus Gaussian noise of ``noise`` -- slice z (``slice_ids[i]`` where given, else i) draws its [B, m, m] from
     ``np.random.default_rng(seed * 1000 + z)`` --, reconstructed on the device by ``replicate`` (block replication), ``tv``
@@ -1376,7 +1397,11 @@ def joint_bvalue_study(hr, bvalues, factor=2, kernel="mean", noise=0.02, seed=0,
     (``baselines.tv_superres_joint``, B the channel axis, ``tv_joint_lambda`` and ``channel_weights(lr, weights)``); both share
     ``tv_huber`` and ``tv_iters`` (the ``TVJ_DEFAULT_*`` where None).  Returns ``{"images", "hr", "lr", "methods", "psnr", "ssim"``
     [Z, B] per method (data range 1), ``"psnr_b"`` [B] and ``"psnr_all"`` per method, ``"adc"`` [Z, R, R] per method and of ``hr``
-    (``loglinear_adc``), ``"adc_rmse"`` per method inside ``b_min image > 0.25 max``, ``"mask"``, ``"channel_weights"``, ``"info"}``."""
+    (``loglinear_adc``), ``"adc_rmse"`` per method inside ``b_min image > 0.25 max``, ``"mask"``, ``"channel_weights"``, ``"info"}``.
+    ``adc_model`` (a dict with any of ``lam``, ``weight``, ``iters``; the ``ADC_DEFAULT_*`` where missing): also the method ``tv_adc``,
+    ``baselines.tv_superres_adc`` on the same LR stack -- its images are the model's, ``baselines.adc_signal`` of the two
+    maps; ``adc["tv_adc"]`` and ``adc_rmse["tv_adc"]`` are the SOLVER'S map, and ``"adc_loglinear"`` / ``"adc_rmse_loglinear"`` hold the
+    log-linear fit of its images beside it; ``"s0"`` the b = 0 map.  Without it every entry is what it was."""
     from . import baselines
 
     lam = baselines.TV_DEFAULT_LAMBDA if tv_lambda is None else tv_lambda
@@ -1391,6 +1416,8 @@ def joint_bvalue_study(hr, bvalues, factor=2, kernel="mean", noise=0.02, seed=0,
     if b.size != B or np.ptp(b) == 0 or not np.isfinite(b).all():
         raise ValueError(f"joint_bvalue_study: bvalues are {B} finite values that are not all equal (got {b.tolist()})")
     m = check_joint_bvalues(R, B, factor, kernel, noise, lam, lam_j, huber, iters, weights)
+    if adc_model is not None:
+        model_args = check_adc_model(b, **adc_model)
     ids = list(range(Z)) if slice_ids is None else [int(v) for v in slice_ids]
     if len(ids) != Z or (Z and min(ids) < 0):
         raise ValueError(f"joint_bvalue_study: slice_ids are one index >= 0 per slice (got {slice_ids!r} for {Z} slices)")
@@ -1405,6 +1432,11 @@ def joint_bvalue_study(hr, bvalues, factor=2, kernel="mean", noise=0.02, seed=0,
     info["tv"] = {k: v.cpu().numpy() for k, v in res.items()}
     images["tv_joint"], res = baselines.tv_superres_joint(y, (f, f), kernel, lam_j, huber, int(iters), mu, return_info=True)
     info["tv_joint"] = {k: v.cpu().numpy() for k, v in res.items()}
+    if adc_model is not None:
+        s0, adc_map, res = baselines.tv_superres_adc(y, b.tolist(), (f, f), kernel, model_args[0], baselines.ADC_DEFAULT_HUBER, model_args[2],
+                                                     (1.0, model_args[1]), return_info=True)
+        images["tv_adc"] = baselines.adc_signal(s0.contiguous(), adc_map.contiguous(), b.tolist())
+        info["tv_adc"] = {k: v.cpu().numpy() for k, v in res.items()}
     f32 = lambda t: t.float().contiguous()
     per_b = lambda t: f32(t.transpose(0, 1)).reshape(B, Z * R, R)
     psnr = {name: metrics.psnr(f32(hr_d), f32(v), 1.0, per_image=True).cpu().numpy().reshape(Z, B) for name, v in images.items()}
@@ -1415,9 +1447,15 @@ def joint_bvalue_study(hr, bvalues, factor=2, kernel="mean", noise=0.02, seed=0,
     mask = b0 > 0.25 * b0.max()
     adc = {name: loglinear_adc(v, b) for name, v in images.items()}
     adc["hr"] = loglinear_adc(hr_d, b)
-    adc_rmse = {name: float(((adc[name] - adc["hr"])[mask] ** 2).mean().sqrt()) for name in images}
-    return {"images": images, "hr": hr_d, "lr": y, "methods": tuple(images), "psnr": psnr, "ssim": ssim, "psnr_b": psnr_b,
-            "psnr_all": psnr_all, "adc": adc, "adc_rmse": adc_rmse, "mask": mask, "channel_weights": mu, "info": info}
+    rmse = lambda a: float(((a - adc["hr"])[mask] ** 2).mean().sqrt())
+    out = {}
+    if adc_model is not None:                  # the solver's own map; the log-linear fit of its images stands beside it
+        out = {"adc_loglinear": {"tv_adc": adc["tv_adc"]}, "adc_rmse_loglinear": {"tv_adc": rmse(adc["tv_adc"])}, "s0": {"tv_adc": s0}}
+        adc["tv_adc"] = adc_map.double()
+    adc_rmse = {name: rmse(adc[name]) for name in images}
+    out.update({"images": images, "hr": hr_d, "lr": y, "methods": tuple(images), "psnr": psnr, "ssim": ssim, "psnr_b": psnr_b,
+                "psnr_all": psnr_all, "adc": adc, "adc_rmse": adc_rmse, "mask": mask, "channel_weights": mu, "info": info})
+    return out
 
 
 # ---- the second-order study: does TGV remove the terraces of TV on smoothly varying intensity? ------------------------

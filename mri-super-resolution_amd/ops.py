@@ -873,6 +873,96 @@ def tvj_solve(y: torch.Tensor, factors, kernel, channel_weights, lam: float, alp
     return out, energy, change
 
 
+# ---- the S0 / ADC maps of a group as the unknowns (include/inrhip.h) ------------------------------------------------------
+def _bvalues(who, b, count=None, least=2):
+    """The HOST b-values as floats, refused by name: ``count`` of them (None: ``least`` .. TVJ_MAX_CHANNELS), finite."""
+    try:
+        vals = [float(v) for v in b]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: b must be a sequence of b-values (got {b!r})") from None
+    if count is not None and len(vals) != count:
+        raise ValueError(f"{who}: b has {len(vals)} b-values, expected one per channel ({count})")
+    if not least <= len(vals) <= TVJ_MAX_CHANNELS:
+        raise ValueError(f"{who}: b-values are {least} .. {TVJ_MAX_CHANNELS} per group (got {len(vals)})")
+    if not all(abs(v) < float("inf") for v in vals):
+        raise ValueError(f"{who}: b-values must be finite (got {vals!r})")
+    return vals
+
+
+def _tvadc_model(who, b, channels, map_weights, coupling, s_max, adc_max, adc0):
+    """(b, map weights, s_max, adc_max, adc0) of a solve as host floats; refuses what ``inr_tvadc_solve2d`` would refuse."""
+    if not 2 <= channels <= TVJ_MAX_CHANNELS:
+        raise ValueError(f"{who}: b-values are 2 .. {TVJ_MAX_CHANNELS} per group (got {channels})")
+    vals = _bvalues(who, b, channels)
+    if not all(v >= 0.0 for v in vals):
+        raise ValueError(f"{who}: b-values must be finite and >= 0 (got {vals!r})")
+    if max(vals) == min(vals):
+        raise ValueError(f"{who}: the b-values are all equal ({vals[0]!r}): they determine no ADC")
+    if coupling not in _TVJ_COUPLING:
+        raise ValueError(f"{who}: coupling must be 'joint' or 'none' (got {coupling!r})")
+    mu = [float(v) for v in map_weights]
+    if len(mu) != 2 or not all(0.0 <= v <= 1.0 for v in mu):
+        raise ValueError(f"{who}: map_weights are (mu_s, mu_d), two finite values within [0, 1] (got {mu!r})")
+    s_max, adc_max, adc0 = float(s_max), float(adc_max), float(adc0)
+    if not 0.0 < s_max < float("inf"):
+        raise ValueError(f"{who}: s_max must be finite and > 0 (got {s_max!r})")
+    if not 0.0 < adc_max < float("inf") or not adc_max * max(vals) < float("inf"):
+        raise ValueError(f"{who}: adc_max must be finite and > 0 (got {adc_max!r})")
+    if not 0.0 <= adc0 <= adc_max:
+        raise ValueError(f"{who}: adc0 must be within [0, adc_max] (got {adc0!r}, adc_max {adc_max!r})")
+    return vals, mu, s_max, adc_max, adc0
+
+
+def tvadc_workspace_doubles(n: int, channels: int, H: int, W: int, factors) -> int:
+    """``inr_tvadc_workspace_doubles``; 0 for sizes ``inr_tvadc_solve2d`` refuses."""
+    return int(lib().inr_tvadc_workspace_doubles(int(n), int(channels), int(H), int(W), int(factors[0]), int(factors[1])))
+
+
+def tvadc_solve(y: torch.Tensor, b, factors, kernel, map_weights, lam: float, alpha: float, coupling, n_iter: int, s_max: float,
+                adc_max: float, adc0: float, weight=None, x0=None, workspace=None):
+    """``inr_tvadc_solve2d`` / ``_f32`` by the dtype of ``y`` [n, C, h, w]: returns (s0 [n, f0 h, f1 w] and adc [n, f0 h, f1 w] of that
+    dtype -- two views of one [n, 2, H, W] tensor --, energy [n] float64, change [n] float64).  ``b``: C host b-values; ``map_weights``:
+    (mu_s, mu_d) host values in [0, 1]; ``coupling``: 'joint' or 'none'; ``weight`` [n, C, h, w] and ``x0`` [n, 2, f0 h, f1 w] (the
+    maps s0, adc) share the dtype; ``workspace``: a float64 tensor."""
+    who = "tvadc_solve"
+    _chk_groups(y, "y", (torch.float32, torch.float64))
+    f0, f1, k = _block_kernel(kernel, factors)
+    n, ch, h, w = y.shape
+    H, W = h * f0, w * f1
+    vals, mu, s_max, adc_max, adc0 = _tvadc_model(who, b, ch, map_weights, coupling, s_max, adc_max, adc0)
+    _hr_shape(who, H, W, f0, f1)
+    if weight is not None:
+        _chk_groups(weight, "weight", (y.dtype,), y.shape)
+    if x0 is not None:
+        _chk_groups(x0, "x0", (y.dtype,), (n, 2, H, W))
+    lam, alpha, n_iter = _tv_scalars(who, lam, alpha, n_iter)
+    out = torch.empty((n, 2, H, W), dtype=y.dtype, device=y.device)
+    (energy, change), entry = _tv_results(y, "inr_tvadc_solve2d")
+    if n == 0:
+        return out[:, 0], out[:, 1], energy, change
+    workspace = _f64_workspace(workspace, tvadc_workspace_doubles(n, ch, H, W, (f0, f1)), y.device)
+    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, ch, H, W,
+                                f0, f1, k, (C.c_double * ch)(*vals), (C.c_double * 2)(*mu), lam, alpha, _TVJ_COUPLING[coupling], n_iter,
+                                s_max, adc_max, adc0, workspace.data_ptr(), workspace.numel(), _stream()), entry)
+    return out[:, 0], out[:, 1], energy, change
+
+
+def adc_signal(s0: torch.Tensor, adc: torch.Tensor, b) -> torch.Tensor:
+    """``inr_adc_signal`` / ``_f32`` by the dtype of ``s0`` [n, H, W]: the model's images ``s0 exp(-b_c adc)`` [n, C, H, W] of two maps
+    of one shape and dtype; ``b``: C host b-values, 1 .. 16."""
+    _chk_images(s0, "s0", (torch.float32, torch.float64))
+    _chk_images(adc, "adc", (s0.dtype,), s0.shape)
+    vals = _bvalues("adc_signal", b, least=1)
+    n, H, W = s0.shape
+    out = torch.empty((n, len(vals), H, W), dtype=s0.dtype, device=s0.device)
+    if out.numel() == 0:
+        return out
+    entry = "inr_adc_signal" if s0.dtype == torch.float64 else "inr_adc_signal_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), s0.data_ptr(), adc.data_ptr(), (C.c_double * len(vals))(*vals), n, len(vals), H * W,
+                                _stream()), entry)
+    return out
+
+
 # ---- second-order TGV under the block operator (include/inrhip.h, DESIGN.md 4r) --------------------------------------------------------
 def tgv_workspace_doubles(n: int, H: int, W: int) -> int:
     """``inr_tgv_workspace_doubles``; 0 for sizes ``inr_tgv_solve2d`` refuses."""

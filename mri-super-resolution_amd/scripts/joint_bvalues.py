@@ -13,7 +13,13 @@ gives it a mono-exponential decay over b = 0 / 150 / 1000 / 1500 whose ADC is hi
   tv_joint   ``baselines.tv_superres_joint`` with ``--tv_joint_lambda`` and the channel weights of ``--weights``: the b-values of a
              slice are the channels of one group.
 
-Both TV rows use ``--tv_huber --tv_iters``.  Per patient, under ``<output_address>/pat<id>/``: ``joint_bvalues.csv`` (one row per slice
+``--with_adc_model [--tv_adc_lambda LA --tv_adc_weight M --tv_adc_iters NA]`` adds
+
+  tv_adc     ``baselines.tv_superres_adc``: the S0 / ADC maps of a slice are the unknowns; its images are the model's,
+             ``s0 exp(-b adc)``, and its ``adc_rmse_tv_adc`` is the SOLVER'S map against the HR data's; ``adc_rmse_loglinear_tv_adc`` is the
+             log-linear fit of its images, for comparison.  ``joint_bvalues.mat`` gains ``s0_tv_adc`` and ``adc_loglinear_tv_adc``.
+
+Without the flag every output is byte for byte what it was.  Both TV rows use ``--tv_huber --tv_iters``.  Per patient, under ``<output_address>/pat<id>/``: ``joint_bvalues.csv`` (one row per slice
 and b-value: ``Pt_id, b-value, slice``, then ``SSIM-<method>`` and ``PSNR-<method>`` for the three methods), ``metrics.json``
 (``psnr_<method>_db`` over everything, ``psnr_<method>_b<value>_db`` per b-value, ``ssim_<method>_mean``, ``adc_rmse_<method>``: the RMSE
 of the log-linear ADC against the HR data's inside ``b_min image > 0.25 max``, the channel weights and the arguments) and
@@ -53,7 +59,17 @@ def build_parser():
     p.add_argument("--slices", type=int, nargs="*", default=None, help="slice indexes (default: every slice)")
     p.add_argument("--synthetic_adc", action="store_true",
                    help="give a 3-D volume a mono-exponential decay over b = 0 / 150 / 1000 / 1500 (the study case)")
+    p.add_argument("--with_adc_model", action="store_true",
+                   help="add the row tv_adc: the S0 / ADC maps as the unknowns of one solve per slice (DESIGN.md 4t)")
+    p.add_argument("--tv_adc_lambda", type=float, default=baselines.ADC_DEFAULT_LAMBDA, help="--with_adc_model: weight of the prior on the maps")
+    p.add_argument("--tv_adc_weight", type=float, default=baselines.ADC_DEFAULT_MAP_WEIGHTS[1],
+                   help="--with_adc_model: weight of the normalised ADC map in the prior, within [0, 1]")
+    p.add_argument("--tv_adc_iters", type=int, default=baselines.ADC_DEFAULT_ITERS, help="--with_adc_model: iterations, 1 .. 100,000")
     return p
+
+
+def _adc_model(args):
+    return dict(lam=args.tv_adc_lambda, weight=args.tv_adc_weight, iters=args.tv_adc_iters) if args.with_adc_model else None
 
 
 def check_args(args, n_b=None):
@@ -63,6 +79,8 @@ def check_args(args, n_b=None):
     n_b = (len(drivers.SYNTHETIC_B) if args.synthetic_adc else 2) if n_b is None else n_b
     m = drivers.check_joint_bvalues(args.roi_end - args.roi_start, n_b, args.factor, args.kernel, args.noise, args.tv_lambda,
                                     args.tv_joint_lambda, args.tv_huber, args.tv_iters, args.weights)
+    if args.with_adc_model:
+        drivers.check_adc_model(**_adc_model(args))
     if args.slices is not None and (not args.slices or min(args.slices) < 0):
         raise ValueError(f"--slices are indexes >= 0 (got {args.slices})")
     return m
@@ -92,7 +110,7 @@ def run_patient(path, pt_id, args):
     os.makedirs(out_dir, exist_ok=True)
     # slice z of the volume draws from seed * 1000 + z whatever --slices selects
     res = drivers.joint_bvalue_study(hr, b, args.factor, args.kernel, args.noise, args.seed, args.tv_lambda, args.tv_joint_lambda,
-                                     args.tv_huber, args.tv_iters, args.weights, slice_ids=which)
+                                     args.tv_huber, args.tv_iters, args.weights, slice_ids=which, adc_model=_adc_model(args))
     methods = res["methods"]
     with open(os.path.join(out_dir, "joint_bvalues.csv"), "w") as fh:
         fh.write(", ".join(["Pt_id", "b-value", "slice"] + [f"SSIM-{name}" for name in methods] + [f"PSNR-{name}" for name in methods]) + "\n")
@@ -105,6 +123,8 @@ def run_patient(path, pt_id, args):
                "seed": int(args.seed), "tv_lambda": args.tv_lambda, "tv_joint_lambda": args.tv_joint_lambda, "tv_huber": args.tv_huber,
                "tv_iters": int(args.tv_iters), "weights": args.weights, "channel_weights": [float(v) for v in res["channel_weights"]],
                "methods": list(methods)}
+    if args.with_adc_model:
+        summary.update(tv_adc_lambda=args.tv_adc_lambda, tv_adc_weight=args.tv_adc_weight, tv_adc_iters=int(args.tv_adc_iters))
     for name in methods:
         summary[f"psnr_{name}_db"] = res["psnr_all"][name]
         for j in range(len(b)):
@@ -112,9 +132,14 @@ def run_patient(path, pt_id, args):
         summary[f"ssim_{name}_mean"] = float(res["ssim"][name].mean())
         summary[f"adc_rmse_{name}"] = res["adc_rmse"][name]
     summary["tv_joint_energy_mean"] = float(res["info"]["tv_joint"]["energy"].mean())
+    if args.with_adc_model:
+        summary["adc_rmse_loglinear_tv_adc"] = res["adc_rmse_loglinear"]["tv_adc"]
+        summary["tv_adc_energy_mean"] = float(res["info"]["tv_adc"]["energy"].mean())
     host = lambda t: t.cpu().numpy()
     mat = {name: host(res["images"][name]).transpose(2, 3, 0, 1) for name in methods}                                 # [X, Y, Z, B]
     mat.update({f"adc_{name}": host(v).transpose(1, 2, 0) for name, v in res["adc"].items()})                          # [X, Y, Z]
+    if args.with_adc_model:
+        mat.update(s0_tv_adc=host(res["s0"]["tv_adc"]).transpose(1, 2, 0), adc_loglinear_tv_adc=host(res["adc_loglinear"]["tv_adc"]).transpose(1, 2, 0))
     mat.update(hr=host(res["hr"]).transpose(2, 3, 0, 1), lr=host(res["lr"]).transpose(2, 3, 0, 1), b=b,
                slices=np.asarray(which, np.float64))
     matio.savemat(os.path.join(out_dir, "joint_bvalues.mat"), mat)

@@ -58,6 +58,15 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     SSIM-SR``); ``metrics.json`` gains ``psnr_tv_joint_db``, ``ssim_tv_joint_mean`` and ``tv_joint_consistency_psnr_db``; with ``--adc``,
     ``adc.mat`` gains ``adc_tv_joint``.  Refused: without ``--tv_baseline``, LJ < 0 (before the input is loaded), an input with fewer
     than 2 b-values or more than 16 (before the fit).
+  * ``--tv_adc [--tv_adc_lambda LA --tv_adc_weight M --tv_adc_iters NA]`` (with ``--tv_baseline``): the S0 / ADC maps of every slice as
+    the unknowns of ONE solve over its b-values, ``baselines.tv_superres_adc(Y, b, (2, 2), kernel, LA, huber, NA, (1, M))``
+    (``inr_tvadc_solve2d_f32``) with the file's b-values; ``Y`` is the LR stack in the signal's own units, every b-image
+    times ``maxes[b, 1]`` over the largest of them (as is, where the file has a single TE).  The model's images ``s0 exp(-b adc)``, back
+    in the units of the stack, are scored like the other TV rows: ``ssim_scores_tv_adc.csv`` (``Pt_id, b-value, slice, SSIM-tv-adc,
+    SSIM-SR``); ``metrics.json`` gains ``psnr_tv_adc_db``, ``ssim_tv_adc_mean`` and ``tv_adc_consistency_psnr_db``; with ``--adc``,
+    ``adc.mat`` gains ``adc_tv_adc`` -- the solver's own map, no log-linear fit of its images -- and ``s0_tv_adc``.  Refused: without
+    ``--tv_baseline``, LA < 0, M outside [0, 1], NA outside 1 .. 100,000 (before the input is loaded), an input without 2 .. 16
+    distinct, non-negative b-values (once it is known).
   * ``--tv_tgv [--tv_tgv_lambda LG --tv_tgv_ratio R]`` (with ``--tv_baseline``): the same [Z, B, R/2, R/2] stack, every image on its
     own, under the second-order TGV prior, which does not terrace smooth intensity:
     ``baselines.tgv_superres(LR, (2, 2), kernel, LG, R, A, N)`` (``inr_tgv_solve2d_f32``), with ``--tv_huber`` and
@@ -137,6 +146,15 @@ def build_parser():
                    help="--tv_joint: weight of the coupled prior (default from the sweep of DESIGN.md 4q)")
     p.add_argument("--tv_joint_weights", choices=("equal", "sqrt_signal"), default="equal",
                    help="--tv_joint: the channel weights of the coupled norm (baselines.channel_weights)")
+    p.add_argument("--tv_adc", action="store_true",
+                   help="with --tv_baseline: also the model-based S0 / ADC reconstruction, whose unknowns are the two parameter maps of a "
+                        "slice: ssim_scores_tv_adc.csv, psnr_tv_adc_db / ssim_tv_adc_mean / tv_adc_consistency_psnr_db in metrics.json, "
+                        "adc_tv_adc and s0_tv_adc with --adc (needs 2 .. 16 distinct b-values)")
+    p.add_argument("--tv_adc_lambda", type=float, default=baselines.ADC_DEFAULT_LAMBDA,
+                   help="--tv_adc: weight of the prior on the maps (default from the sweep of DESIGN.md 4t)")
+    p.add_argument("--tv_adc_weight", type=float, default=baselines.ADC_DEFAULT_MAP_WEIGHTS[1],
+                   help="--tv_adc: weight of the normalised ADC map in the prior, within [0, 1]")
+    p.add_argument("--tv_adc_iters", type=int, default=baselines.ADC_DEFAULT_ITERS, help="--tv_adc: iterations, 1 .. 100,000")
     p.add_argument("--tv_tgv", action="store_true",
                    help="with --tv_baseline: also the second-order TGV reconstruction, which does not terrace smooth intensity: "
                         "ssim_scores_tv_tgv.csv, psnr_tv_tgv_db / ssim_tv_tgv_mean / tv_tgv_consistency_psnr_db in metrics.json, "
@@ -300,6 +318,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     tv = _tv_baseline(ls, args, average) if getattr(args, "tv_baseline", False) else None
     tvj = _tv_joint(ls, args, average) if getattr(args, "tv_joint", False) else None
     tgv = _tv_tgv(ls, args, average) if getattr(args, "tv_tgv", False) else None
+    tva = _tv_adc(ls, args, average, bvalues, signal_scale) if getattr(args, "tv_adc", False) else None
     with reports.SsimCsv(os.path.join(out_dir, "ssim_scores.csv")) as csv:
         for _slice in range(nz):
             for b in range(nb):
@@ -350,6 +369,15 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         summary["psnr_tv_tgv_db"] = float(metrics.psnr(hs, tgv, 1.0))
         summary["ssim_tv_tgv_mean"] = float(ssim_tgv[okn].mean())
         summary["tv_tgv_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(tgv, (2, 2), _tv_kernel(average)), 1.0))
+    if tva is not None:
+        ssim_tva = metrics.ssim_reference_protocol(safe(hs), safe(tva["images"])).cpu().numpy()
+        with reports.SsimCsv(os.path.join(out_dir, "ssim_scores_tv_adc.csv"), reports.SSIM_TV_ADC_HEADER) as csv:
+            for _slice in range(nz):
+                for b in range(nb):
+                    csv.row(pt_id, bvalues[b] if b < len(bvalues) else b, _slice, float(ssim_tva[_slice, b]), float(ssim_sr[_slice, b]))
+        summary["psnr_tv_adc_db"] = float(metrics.psnr(hs, tva["images"], 1.0))
+        summary["ssim_tv_adc_mean"] = float(ssim_tva[okn].mean())
+        summary["tv_adc_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(tva["images"], (2, 2), _tv_kernel(average)), 1.0))
     if average:
         pred = inr.footprint_forward(INR, coords, B, footprint)
         summary.update({"lr_model": "average", "footprint": args.footprint, "footprint_samples": footprint.count,
@@ -360,8 +388,11 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         matio.savemat(os.path.join(out_dir, "coronal.mat"), coronal)
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
-        matio.savemat(os.path.join(out_dir, "adc.mat"), _adc_maps(recon, hs, bvalues, signal_scale,
-                                                                     args.zerofill_apodize if zf is not None else None, ls, tv, tvj, tgv))
+        adc_vars = _adc_maps(recon, hs, bvalues, signal_scale, args.zerofill_apodize if zf is not None else None, ls, tv, tvj, tgv)
+        if tva is not None:                                                         # [Z, R, R] -> [R, R, Z], the layout of the other maps
+            adc_vars["adc_tv_adc"] = tva["adc"].permute(1, 2, 0).contiguous().cpu().numpy()
+            adc_vars["s0_tv_adc"] = (tva["s0"] * tva["unit"]).permute(1, 2, 0).contiguous().cpu().numpy()
+        matio.savemat(os.path.join(out_dir, "adc.mat"), adc_vars)
     if args.derivative_maps:
         matio.savemat(os.path.join(out_dir, "derivatives.mat"), _derivative_maps(INR, B, test_shape))
     if args.wire_derivative_maps:
@@ -447,7 +478,7 @@ def _check_wire(args):
 
 
 def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
-    """Refuses --transverse_length / --adc / --tv_joint on an input that cannot give them, before the fit starts."""
+    """Refuses --transverse_length / --adc / --tv_joint / --tv_adc on an input that cannot give them, before the fit starts."""
     nz, nb = mean_img.shape[2], mean_img.shape[3]
     if args.transverse_length < 0:
         raise ValueError(f"--transverse_length must be >= 0 (got {args.transverse_length})")
@@ -463,6 +494,13 @@ def _check_optional_outputs(args, path, mean_img, bvalues, signal_scale):
     if getattr(args, "tv_joint", False) and not 2 <= nb <= baselines.ops.TVJ_MAX_CHANNELS:
         raise ValueError(f"--tv_joint couples the b-values of a slice and needs 2 .. {baselines.ops.TVJ_MAX_CHANNELS} of them; {path} "
                          f"has {nb}")
+    if getattr(args, "tv_adc", False):
+        b = np.asarray(bvalues, np.float64).reshape(-1)
+        if not 2 <= nb <= baselines.ops.TVJ_MAX_CHANNELS:
+            raise ValueError(f"--tv_adc fits one decay over the b-values of a slice and needs 2 .. {baselines.ops.TVJ_MAX_CHANNELS} of them; "
+                             f"{path} has {nb}")
+        if len(b) != nb or not np.isfinite(b).all() or (b < 0).any() or np.ptp(b) == 0:
+            raise ValueError(f"--tv_adc needs {nb} distinct, finite b-values >= 0 (variable 'b'); {path} gives {list(bvalues)}")
     if args.adc:
         if nb < 2:
             raise ValueError(f"--adc needs at least 2 b-values; {path} has {nb}")
@@ -518,8 +556,22 @@ def _tv_tgv(ls, args, average):
     return baselines.tgv_superres(ls, (2, 2), _tv_kernel(average), args.tv_tgv_lambda, args.tv_tgv_ratio, args.tv_huber, args.tv_iters)
 
 
+def _tv_adc(ls, args, average, bvalues, signal_scale):
+    """``--tv_adc``: the [Z, B, R/2, R/2] LR stack ``ls`` -> {"s0", "adc" [Z, R, R], "images" [Z, B, R, R], "unit"}: the maps of the
+    mono-exponential model solved on the stack in the signal's own units -- every b-image times its ``signal_scale`` over the largest
+    (``unit``), so that the data stay within [0, 1] --, and the model's images back in the units of ``ls``."""
+    scale = torch.ones(ls.shape[1], dtype=ls.dtype, device=ls.device) if signal_scale is None else \
+        torch.as_tensor(np.asarray(signal_scale, np.float32), device=ls.device)
+    unit = float(scale.max())
+    rel = (scale / unit)[None, :, None, None]
+    s0, adc = baselines.tv_superres_adc((ls * rel).contiguous(), [float(v) for v in bvalues], (2, 2), _tv_kernel(average), args.tv_adc_lambda,
+                                        baselines.ADC_DEFAULT_HUBER, args.tv_adc_iters, (1.0, args.tv_adc_weight))
+    images = baselines.adc_signal(s0.contiguous(), adc.contiguous(), [float(v) for v in bvalues]) / rel
+    return {"s0": s0, "adc": adc, "images": images.contiguous(), "unit": unit}
+
+
 def _check_tv(args, fit=None):
-    """``--tv_baseline`` / ``--tv_joint`` / ``--tv_tgv``: what they cannot serve, before the input is loaded and anything touches the
+    """``--tv_baseline`` / ``--tv_joint`` / ``--tv_tgv`` / ``--tv_adc``: what they cannot serve, before the input is loaded and anything touches the
     device."""
     if getattr(args, "tv_tgv", False):
         if not getattr(args, "tv_baseline", False):
@@ -528,6 +580,15 @@ def _check_tv(args, fit=None):
             raise ValueError(f"--tv_tgv_lambda must be finite and >= 0 (got {args.tv_tgv_lambda})")
         if not 0.0 < args.tv_tgv_ratio < float("inf"):
             raise ValueError(f"--tv_tgv_ratio must be finite and > 0 (got {args.tv_tgv_ratio})")
+    if getattr(args, "tv_adc", False):
+        if not getattr(args, "tv_baseline", False):
+            raise ValueError("--tv_adc is scored beside the per-channel reconstruction: pass --tv_baseline with it")
+        if not 0.0 <= args.tv_adc_lambda < float("inf"):
+            raise ValueError(f"--tv_adc_lambda must be finite and >= 0 (got {args.tv_adc_lambda})")
+        if not 0.0 <= args.tv_adc_weight <= 1.0:
+            raise ValueError(f"--tv_adc_weight must be within [0, 1] (got {args.tv_adc_weight})")
+        if not 1 <= args.tv_adc_iters <= 100000:
+            raise ValueError(f"--tv_adc_iters must be 1 .. 100,000 (got {args.tv_adc_iters})")
     if getattr(args, "tv_joint", False):
         if not getattr(args, "tv_baseline", False):
             raise ValueError("--tv_joint is scored beside the per-channel reconstruction: pass --tv_baseline with it")
