@@ -1202,6 +1202,14 @@ int inr_siren_backward_train(const inr_siren_desc_t* desc, const float* params, 
     if (int rc = hp_head_bound_ext(s.head_bound(), s.gy_max(), params + L.w_off[head], desc->hidden_features,
                                    layer_omega(desc, head - 1), st))
         return rc;
+    // "every element written" (include/inrhip.h): the finalize launch sums the tensors only, so the padding behind a tensor whose
+    // length is no multiple of 4 floats -- the head's bias, at least -- is zeroed here
+    for (int l = 0; l <= L.n_sine; ++l) {
+        const long long w_end = L.w_off[l] + (long long)L.fan_in[l] * L.fan_out[l], b_end = L.b_off[l] + L.fan_out[l];
+        const long long next = l < L.n_sine ? L.w_off[l + 1] : L.total;
+        if (w_end < L.b_off[l]) INR_HIP(hipMemsetAsync(grads + w_end, 0, (size_t)(L.b_off[l] - w_end) * sizeof(float), st));
+        if (b_end < next) INR_HIP(hipMemsetAsync(grads + b_end, 0, (size_t)(next - b_end) * sizeof(float), st));
+    }
     FinalizeJob fin;
     float* loss_sink = fv.scratch + hp_slab_plan(L, n).loss_sink;
     if (int rc = hp_backward_pass(desc, L, params, grads, fv, nullptr, nullptr, gy, 1, loss_sink, st, fin, z_head)) return rc;

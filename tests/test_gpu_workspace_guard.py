@@ -1,7 +1,8 @@
 """Every workspace view stays inside the bytes its planner reports.
 
-Each case allocates ``planner bytes + 4096``, fills the tail with 0xA5, passes ``workspace_bytes = planner bytes`` to ONE call
-per entry point and asserts that the call succeeds, that the tail is untouched and that the outputs are finite.  The shapes are
+Each case puts a workspace of exactly the planner's bytes between the two 0xA5 guards of tests/guard_common.py, passes
+``workspace_bytes = planner bytes`` to ONE call per entry point and asserts that the call succeeds, that both guards are untouched and
+that the outputs are finite.  The shapes are
 the smallest at which a carve can still go wrong: a ragged last block, both block sizes of the small-network kernels, every
 mode of a view.  Only allocated memory is read and written.
 """
@@ -11,32 +12,27 @@ import numpy as np
 import pytest
 import torch
 
+from tests import guard_common
 from mri_super_resolution_amd import _lib, rams
 
 pytestmark = pytest.mark.gpu
-TAIL = 4096
 ADAM = (1e-4, 0.9, 0.999, 1e-8)
 DEV = "cuda:0"
 
 
-class Guarded:
-    """A workspace of `need` bytes followed by a guard tail."""
+class Guarded(guard_common.Guarded):
+    """A zeroed workspace of `need` bytes between a guard head and a guard tail."""
 
     def __init__(self, need):
         assert need > 0, _lib.lib().inr_last_error()
         self.need = int(need)
-        self.buf = torch.zeros(self.need + TAIL, dtype=torch.uint8, device=DEV)
-        self.buf[self.need:] = 0xA5
-        self.args = (self.buf.data_ptr(), self.need)
-
-    def intact(self):
-        torch.cuda.synchronize()
-        return bool((self.buf[self.need:] == 0xA5).all())
+        super().__init__(self.need, torch.uint8, 0x00, DEV)
+        self.args = (self.ptr, self.need)
 
 
 def run(ws, rc, *outputs):
     assert rc == 0, (rc, _lib.lib().inr_last_error())
-    assert ws.intact(), "the call wrote past the bytes its planner reports"
+    assert ws.intact(), "the call wrote outside the bytes its planner reports"
     for o in outputs:
         assert bool(torch.isfinite(o).all())
 
