@@ -795,6 +795,38 @@ int inr_adc_signal(double* out, const double* s0, const double* adc, const doubl
 int inr_adc_signal_f32(float* out, const float* s0, const float* adc, const double* b, int64_t n_maps, int channels, int64_t pixels,
                        void* stream);
 
+/* ---- Marchenko-Pastur PCA denoising of a multi-measurement stack, with a noise map -----------------------------------
+ * No counterpart in the reference tree, whose later driver reads a stack denoised elsewhere (`hybrid_raw_clean`).  Veraart et al.,
+ * NeuroImage 2016; the cutoff estimators of Cordero-Grande et al. 2019 (`dwidenoise`).  x [M][D][H][W] DEVICE, measurement-major, every
+ * volume contiguous; the window (w0, w1, w2) has odd sides w_a <= n_a, N = w0 w1 w2 voxels; mask [D][H][W] DEVICE bytes or null (all
+ * inside).  r = min(M, N) <= INR_MPPCA_MAX_RANK, q = max(M, N) <= INR_MPPCA_MAX_LONG.  For every voxel (z, y, x) inside the mask:
+ *   1. the window starts at clamp(i - w / 2, 0, n - w) along each axis: shifted inward at the edges, never mirrored or padded (mirroring
+ *      duplicates columns, the matrix loses rank and the smallest eigenvalues become rounding noise).  X is the M x N matrix of its
+ *      voxels in (dz, dy, dx) order, c the column of the voxel itself (N / 2 only in the interior).  The mask removes no column.
+ *   2. G = X X^T (M <= N) or X^T X (N < M), r x r, summed over the long index in ascending order.
+ *   3. s_0 <= ... <= s_{r-1} the eigenvalues of G, lam_p = max(s_p, 0) / q; an eigenvalue s_p <= q eps s_{r-1} is numerically zero (what
+ *      summing q products leaves of an exact zero): its lam_p is 0 and it is noise whatever step 4 decides.
+ *   4. clam = 0, cut = 0, sigma2 = 0;  for p = 0 .. r - 1:  clam += lam_p;  gam = (p + 1) / (q - (r - p - 1)) (estimator 2, "exp2") or
+ *      (p + 1) / q (estimator 1, "exp1");  a = clam / (p + 1);  b = (lam_p - lam_0) / (4 sqrt(gam));  if b < a: sigma2 = a, cut = p + 1.
+ *      Then cut = max(cut, the number of numerically zero eigenvalues): exact low-rank data comes back with its rank and sigma = 0.
+ *   5. sigma = sqrt(sigma2), rank = r - cut; with V_s the eigenvectors cut .. r - 1:  xhat = V_s (V_s^T X[:, c]) (M <= N) or
+ *      X (V_s V_s[c, :]^T) (N < M);  out[:, z, y, x] = xhat -- the voxel's own column only (sliding window, no overlap averaging).
+ * Outside the mask out = x, sigma = 0, rank = -1.  out [M][D][H][W], sigma [D][H][W] (null: not wanted), rank [D][H][W] (null: not
+ * wanted) DEVICE; out must not overlap x.  ONE launch, no workspace, no host read, no float atomics: one workgroup per voxel (a capped
+ * grid with a stride loop) forms G in LDS, diagonalises it by cyclic two-sided Jacobi in round-robin ordering, fp64 throughout, until
+ * the off-diagonal sum of squares is at most (r eps)^2 ||G||_F^2, ranks the eigenvalues and projects.  A voxel that has not converged
+ * after 30 sweeps (data that is not finite) gets rank = -2, sigma = 0, out = x.  Two runs give the same bits, whatever the grid.  The
+ * _f32 form reads x and writes out / sigma as fp32, fp64 inside, rounded once.  D H W == 0 succeeds and launches nothing.
+ * Refusals, all INR_E_INVALID and before any device work: null out or x, M < 2, a negative size, a window side that is even or < 1,
+ * N < 2, min(M, N) > INR_MPPCA_MAX_RANK (shrink the window or split the measurements), max(M, N) > INR_MPPCA_MAX_LONG, an estimator
+ * that is not 1 or 2, a window side larger than its axis. */
+#define INR_MPPCA_MAX_RANK 64
+#define INR_MPPCA_MAX_LONG 1024
+int inr_mppca_denoise(double* out, double* sigma, int32_t* rank, const double* x, const uint8_t* mask, int M, int D, int H, int W, int w0,
+                      int w1, int w2, int estimator, void* stream);
+int inr_mppca_denoise_f32(float* out, float* sigma, int32_t* rank, const float* x, const uint8_t* mask, int M, int D, int H, int W,
+                          int w0, int w1, int w2, int estimator, void* stream);
+
 /* ---- second-order TGV super-resolution under the block operator: a prior that does not terrace smooth intensity -------
  * No counterpart in the reference.  Images, sides, factors and the HOST `kernel` as for inr_tvsr_solve2d.  An auxiliary field
  * v = (v0, v1) [n_images][2][H][W] absorbs the smooth part of the gradient (Bredies, Kunisch, Pock 2010; Knoll et al. 2011):

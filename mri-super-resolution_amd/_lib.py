@@ -27,6 +27,7 @@ INR_FOURIER_SAMPLE, INR_FOURIER_CENTER, INR_FOURIER_PERIODIC, INR_FOURIER_MIRROR
 INR_TVSR_MAX_FACTOR, INR_TVSR_MAX_SIDE, INR_TVSR3D_MAX_ITER, INR_TVMF_MAX_FRAMES = 8, 1024, 100000, 64
 INR_TVMS_MAX_STACKS, INR_TVMS_MAX_TAPS = 8, 16
 INR_TVJ_MAX_CHANNELS = 16
+INR_MPPCA_MAX_RANK, INR_MPPCA_MAX_LONG = 64, 1024
 
 
 class InrHipError(RuntimeError):
@@ -222,6 +223,8 @@ SIGNATURES = {
                                                              C.c_double, C.c_void_p, C.c_int64, c_stream]),
     "inr_adc_signal": (C.c_int, [C.c_void_p] * 3 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int64, c_stream]),
     "inr_adc_signal_f32": (C.c_int, [c_f32p] * 3 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int64, c_stream]),
+    "inr_mppca_denoise": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [c_stream]),
+    "inr_mppca_denoise_f32": (C.c_int, [c_f32p] * 2 + [C.c_void_p, c_f32p, C.c_void_p] + [C.c_int] * 8 + [c_stream]),
     "inr_tgv_workspace_doubles": (C.c_int64, [C.c_int] * 3),
     "inr_tgv_solve2d": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int,
                                                                     C.c_void_p, C.c_int64, c_stream]),

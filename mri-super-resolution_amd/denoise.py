@@ -1,0 +1,132 @@
+"""Denoising of the multi-measurement acquisition stack before any fit: Marchenko-Pastur PCA (Veraart et al., NeuroImage 2016; the
+cutoff estimators of Cordero-Grande et al. 2019) on the HIP kernel of csrc/mppca.hip (``inr_mppca_denoise``).
+
+The reference's later driver (inrDWI.py:44) fits ``hybrid_raw_clean``, the multi-b / multi-TE stack after a denoising step made outside
+its tree; ``mppca`` is that step, ``stack_hybrid`` / ``unstack_hybrid`` turn the ``[b][TE]`` cell of a ``master.mat`` into the
+measurement-major stack it takes and back, and ``scripts/denoise.py`` writes the clean cell.  Every voxel of the 16 to ~40
+measurements spans only a few signal components: the spectrum of the M x N matrix of a voxel's window tells the noise level and how many
+components are noise, and the voxel is projected onto the others.  The noise map ``sigma`` comes with it.  There is no CPU fallback."""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import ops
+
+DEFAULT_WINDOW = (5, 5, 5)
+ESTIMATORS = tuple(ops.MPPCA_ESTIMATORS)
+
+
+def mppca(data, window=DEFAULT_WINDOW, mask=None, estimator="exp2", return_info=False, measurement_axis=0):
+    """MP-PCA denoising of ``data`` [M, D, H, W] (``measurement_axis=0``) or [X, Y, Z, M] (``measurement_axis=-1``, the layout of the
+    drivers); a 3-D input [M, H, W] (or [X, Y, M]) is one slice, and takes a window (1, a, b) or its two in-plane sides (a, b).
+    ``data``: an ndarray (any real dtype; float64 inside and out) or a device tensor (float32 or float64, returned as given).
+    ``window``: three odd sides over the volume axes in the order they have in ``data``, each at most its axis -- larger sides are
+    refused by name, not shrunk.  ``mask``: the volume's shape, non-zero inside; outside it the data pass through.  ``estimator``:
+    'exp2' (the default) or 'exp1'.  Returns the denoised data like ``data``; with ``return_info`` also a dict with ``sigma`` (the
+    noise map, the volume's shape) and ``rank`` (the number of signal components, int32; -1 outside the mask, -2 where the
+    eigensolver did not converge -- data that is not finite)."""
+    who = "mppca"
+    if measurement_axis not in (0, -1):
+        raise ValueError(f"{who}: measurement_axis must be 0 or -1 (got {measurement_axis!r})")
+    as_numpy = isinstance(data, np.ndarray)
+    if not as_numpy:
+        if not isinstance(data, torch.Tensor):
+            raise TypeError(f"{who} takes an ndarray or a device tensor (got {type(data).__name__})")
+        if not data.is_cuda:
+            raise ops.InrDeviceError(f"{who}: the tensor is on {data.device}; pass an ndarray or a device tensor (there is no CPU fallback)")
+        if data.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"{who}: device tensors must be float32 or float64 (got {data.dtype})")
+    if data.ndim not in (3, 4):
+        raise ValueError(f"{who}: data must be [M, D, H, W] or one slice [M, H, W] (got shape {tuple(data.shape)})")
+    if estimator not in ops.MPPCA_ESTIMATORS:
+        raise ValueError(f"{who}: estimator must be 'exp1' or 'exp2' (got {estimator!r})")
+    one_slice = data.ndim == 3
+    window = tuple(window)
+    if one_slice and len(window) == 2:
+        window = (1,) + window
+    last = measurement_axis == -1
+    volume = tuple(data.shape[:-1] if last else data.shape[1:])
+    M = int(data.shape[-1] if last else data.shape[0])
+    if one_slice:
+        volume = (1,) + volume
+    window = ops.mppca_window(who, window, volume, M)               # host-only refusals come before the device is asked for
+    if mask is not None and tuple(mask.shape) != (volume[1:] if one_slice else volume):
+        raise ValueError(f"{who}: mask has shape {tuple(mask.shape)}, expected {volume[1:] if one_slice else volume}")
+    device = ops.require_gpu() if as_numpy else data.device
+    x = torch.from_numpy(np.array(data, dtype=np.float64, order="C")).to(device) if as_numpy else data
+    if last:
+        x = x.movedim(-1, 0)
+    x = x.reshape((M,) + volume).contiguous()
+    m = None
+    if mask is not None:
+        m = torch.from_numpy(np.ascontiguousarray(np.asarray(mask) != 0)) if isinstance(mask, np.ndarray) else (mask != 0)
+        m = m.to(device).reshape(volume).contiguous().view(torch.uint8)
+    out, sigma, rank = ops.mppca_denoise(x, window, m, estimator, want_sigma=return_info, want_rank=return_info)
+    shape_v = volume[1:] if one_slice else volume
+    out = out.reshape((M,) + shape_v)
+    if last:
+        out = out.movedim(0, -1).contiguous()
+    if as_numpy:
+        out = out.cpu().numpy()
+    if not return_info:
+        return out
+    sigma, rank = sigma.reshape(shape_v), rank.reshape(shape_v)
+    if as_numpy:
+        sigma, rank = sigma.cpu().numpy(), rank.cpu().numpy()
+    return out, {"sigma": sigma, "rank": rank}
+
+
+def _cell_rows(cell):
+    """The ``[b][TE]`` cell (an object ndarray or nested sequences) as a list of lists of ndarrays."""
+    if isinstance(cell, np.ndarray) and cell.dtype == object:
+        if cell.ndim != 2:
+            raise ValueError(f"the cell must be [b][TE] (got an object array of shape {cell.shape})")
+        return [[np.asarray(cell[b, te]) for te in range(cell.shape[1])] for b in range(cell.shape[0])]
+    return [[np.asarray(v) for v in row] for row in cell]
+
+
+def stack_hybrid(cell):
+    """The ``[b][TE]`` cell of a ``master.mat`` (b = 0: [X, Y, Z] or [X, Y, Z, 1]; b > 0: [X, Y, Z, K]) as ONE stack [M, X, Y, Z], every
+    acquisition its own measurement, in the order (b, TE, acquisition).  The values are copied, never converted: the dtype is the
+    cell's (mixed dtypes are refused), so ``unstack_hybrid(stack_hybrid(cell), cell)`` is the cell bit for bit."""
+    rows = _cell_rows(cell)
+    volumes, shape, dtype = [], None, None
+    for b, row in enumerate(rows):
+        for te, a in enumerate(row):
+            if a.ndim not in (3, 4):
+                raise ValueError(f"cell [{b}][{te}] must be [X, Y, Z] or [X, Y, Z, K] (got shape {a.shape})")
+            shape = a.shape[:3] if shape is None else shape
+            dtype = a.dtype if dtype is None else dtype
+            if a.shape[:3] != shape or a.dtype != dtype:
+                raise ValueError(f"cell [{b}][{te}] is {a.dtype} {a.shape[:3]}, the cells before it {dtype} {shape}")
+            volumes.extend([a] if a.ndim == 3 else [a[..., k] for k in range(a.shape[3])])
+    if not volumes:
+        raise ValueError("the cell is empty")
+    return np.stack(volumes, axis=0)
+
+
+def unstack_hybrid(stack, like):
+    """``stack`` [M, X, Y, Z] back in the layout of the cell ``like`` (the one ``stack_hybrid`` read): an object ndarray where ``like`` is
+    one, else nested lists."""
+    rows = _cell_rows(like)
+    stack = np.asarray(stack)
+    need = sum(1 if a.ndim == 3 else a.shape[3] for row in rows for a in row)
+    if stack.ndim != 4 or stack.shape[0] != need:
+        raise ValueError(f"the stack must be [M, X, Y, Z] with the M = {need} measurements of the cell (got shape {stack.shape})")
+    out, at = [], 0
+    for row in rows:
+        new_row = []
+        for a in row:
+            k = 1 if a.ndim == 3 else a.shape[3]
+            part = stack[at] if a.ndim == 3 else np.stack([stack[at + j] for j in range(k)], axis=-1)
+            new_row.append(np.ascontiguousarray(part))
+            at += k
+        out.append(new_row)
+    if isinstance(like, np.ndarray) and like.dtype == object:
+        arr = np.empty(like.shape, dtype=object)
+        for b, row in enumerate(out):
+            for te, a in enumerate(row):
+                arr[b, te] = a
+        return arr
+    return out

@@ -963,6 +963,58 @@ def adc_signal(s0: torch.Tensor, adc: torch.Tensor, b) -> torch.Tensor:
     return out
 
 
+# ---- MP-PCA denoising of a multi-measurement stack (include/inrhip.h) -----------------------------------------------------
+MPPCA_ESTIMATORS = {"exp1": 1, "exp2": 2}
+
+
+def mppca_window(who, window, shape, M):
+    """The window (w0, w1, w2) of a stack of ``M`` measurements over a volume ``shape`` as ints; refuses, by name, what
+    ``inr_mppca_denoise`` would refuse."""
+    try:
+        win = tuple(int(w) for w in window)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: window must be three odd sides (got {window!r})") from None
+    if len(win) != 3 or any(w < 1 or w % 2 == 0 for w in win) or any(int(w) != w for w in window):
+        raise ValueError(f"{who}: window must be three odd sides >= 1 (got {tuple(window)!r})")
+    for name, w, n in zip(("first", "second", "third"), win, shape):
+        if n > 0 and w > n:
+            raise ValueError(f"{who}: the {name} window side ({w}) is larger than its axis ({n}): choose a smaller window "
+                             f"(volume {tuple(shape)}, window {win})")
+    N = win[0] * win[1] * win[2]
+    if M < 2 or N < 2:
+        raise ValueError(f"{who}: at least 2 measurements and a window of at least 2 voxels are needed (got M = {M}, N = {N})")
+    if min(M, N) > _lib.INR_MPPCA_MAX_RANK:
+        raise ValueError(f"{who}: min(M, N) = min({M}, {N}) exceeds the rank limit {_lib.INR_MPPCA_MAX_RANK}: shrink the window or "
+                         f"split the measurements")
+    if max(M, N) > _lib.INR_MPPCA_MAX_LONG:
+        raise ValueError(f"{who}: max(M, N) = max({M}, {N}) exceeds {_lib.INR_MPPCA_MAX_LONG}")
+    return win
+
+
+def mppca_denoise(x: torch.Tensor, window=(5, 5, 5), mask=None, estimator="exp2", want_sigma=True, want_rank=True):
+    """``inr_mppca_denoise`` / ``_f32`` by the dtype of ``x`` [M, D, H, W] on the current stream: returns (out [M, D, H, W] of that dtype,
+    sigma [D, H, W] of that dtype or None, rank [D, H, W] int32 or None).  ``mask``: a device uint8 or bool tensor [D, H, W] or None;
+    ``estimator``: 'exp1' or 'exp2'."""
+    who = "mppca_denoise"
+    _chk_batch(x, "x", 4, "[M, D, H, W]", (torch.float32, torch.float64))
+    if estimator not in MPPCA_ESTIMATORS:
+        raise ValueError(f"{who}: estimator must be 'exp1' or 'exp2' (got {estimator!r})")
+    M, D, H, W = x.shape
+    win = mppca_window(who, window, (D, H, W), M)
+    if mask is not None:
+        _chk_batch(mask, "mask", 3, "[D, H, W]", (torch.uint8, torch.bool), (D, H, W))
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    out = torch.empty_like(x)
+    sigma = torch.empty((D, H, W), dtype=x.dtype, device=x.device) if want_sigma else None
+    rank = torch.empty((D, H, W), dtype=torch.int32, device=x.device) if want_rank else None
+    if D * H * W == 0:
+        return out, sigma, rank
+    entry = "inr_mppca_denoise" if x.dtype == torch.float64 else "inr_mppca_denoise_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), _ptr(sigma), _ptr(rank), x.data_ptr(), _ptr(mask), M, D, H, W, *win,
+                                MPPCA_ESTIMATORS[estimator], _stream()), entry)
+    return out, sigma, rank
+
+
 # ---- second-order TGV under the block operator (include/inrhip.h, DESIGN.md 4r) --------------------------------------------------------
 def tgv_workspace_doubles(n: int, H: int, W: int) -> int:
     """``inr_tgv_workspace_doubles``; 0 for sizes ``inr_tgv_solve2d`` refuses."""

@@ -1,0 +1,73 @@
+#!/usr/bin/env python3
+"""MP-PCA denoising of the raw acquisition stack of a ``master.mat``: the step between the scanner's file and every fit.
+
+    python -m mri_super_resolution_amd.scripts.denoise --data master.mat --out clean.mat [--window 5 5 5] [--estimator exp2]
+                                                       [--key hybrid_raw]
+
+The reference's later driver (inrDWI.py:44) reads ``hybrid_raw_clean``, the ``hybrid_raw`` cell after a denoising step made outside its
+tree.  This script makes it: every acquisition of every [b][TE] cell of ``--key`` is one measurement of ONE stack
+(``denoise.stack_hybrid``), ``denoise.mppca`` (``inr_mppca_denoise``) denoises it over a window of ``--window`` voxels
+along (X, Y, Z), and the result goes back into the cell's layout.  ``--out`` holds ``<key>_clean`` in that layout, ``sigma`` (the noise
+map [X, Y, Z], in the file's units), ``rank`` (signal components per voxel, int32) and every other variable of the input file as it was;
+it is what ``superresDWI --key hybrid_raw_clean`` accepts.  A plain volume [X, Y, Z, B] under ``--key`` is denoised along its last axis.
+A window side larger than its axis is refused, not shrunk."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
+from mri_super_resolution_amd import denoise, matio  # noqa: E402
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="MP-PCA denoising of the acquisition stack of a master.mat")
+    p.add_argument("--data", required=True, help="the input .mat (MAT-5)")
+    p.add_argument("--out", required=True, help="the .mat to write")
+    p.add_argument("--key", default="hybrid_raw", help="the [b][TE] cell (or plain [X, Y, Z, B] volume) to denoise")
+    p.add_argument("--window", type=int, nargs=3, default=list(denoise.DEFAULT_WINDOW), metavar=("A", "B", "C"),
+                   help="odd window sides over (X, Y, Z), each at most its axis")
+    p.add_argument("--estimator", choices=denoise.ESTIMATORS, default="exp2", help="the cutoff estimator")
+    return p
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    data = matio.loadmat(args.data)
+    if args.key not in data:
+        raise KeyError(f"{args.data}: no variable '{args.key}' (it holds {[k for k in data if not k.startswith('__')]})")
+    raw = data[args.key]
+    if isinstance(raw, np.ndarray) and raw.dtype == object:
+        cell = np.empty(raw.shape, dtype=object)
+        for idx in np.ndindex(raw.shape):
+            cell[idx] = np.asarray(raw[idx], np.float64)
+        stack = denoise.stack_hybrid(cell)
+        clean, info = denoise.mppca(stack, args.window, estimator=args.estimator, return_info=True)
+        clean = denoise.unstack_hybrid(clean, cell)
+        M = stack.shape[0]
+    else:
+        vol = np.asarray(raw, np.float64)
+        if vol.ndim != 4:
+            raise ValueError(f"{args.data}: '{args.key}' must be a [b][TE] cell or a volume [X, Y, Z, B] (got shape {vol.shape})")
+        clean, info = denoise.mppca(vol, args.window, estimator=args.estimator, return_info=True, measurement_axis=-1)
+        M = vol.shape[-1]
+    out = {k: v for k, v in data.items() if not k.startswith("__")}
+    out[f"{args.key}_clean"] = clean
+    out["sigma"] = info["sigma"]
+    out["rank"] = info["rank"]
+    matio.savemat(args.out, out)
+    summary = {"input": os.path.abspath(args.data), "output": os.path.abspath(args.out), "key": args.key, "measurements": int(M),
+               "window": [int(w) for w in args.window], "estimator": args.estimator, "sigma_median": float(np.median(info["sigma"])),
+               "rank_histogram": np.bincount(info["rank"].reshape(-1).clip(min=0)).tolist(),
+               "unconverged": int((info["rank"] == -2).sum())}
+    print(json.dumps(summary))
+    return summary
+
+
+if __name__ == "__main__":
+    main()

@@ -73,6 +73,11 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     ``--tv_iters``.  ``ssim_scores_tv_tgv.csv`` (``Pt_id, b-value, slice, SSIM-tv-tgv, SSIM-SR``); ``metrics.json`` gains
     ``psnr_tv_tgv_db``, ``ssim_tv_tgv_mean`` and ``tv_tgv_consistency_psnr_db``; with ``--adc``, ``adc.mat`` gains ``adc_tv_tgv``.
     Refused before the input is loaded: without ``--tv_baseline``, LG < 0, R <= 0.
+  * ``--denoise mppca [--denoise_window a b c]``: MP-PCA denoising (``denoise.mppca``, ``inr_mppca_denoise``) of the raw
+    stack before the per-cell normalisation of ``load_input_and_scale`` -- for ``hybrid_raw`` every acquisition of every [b][TE] cell is
+    a measurement (``denoise.stack_hybrid``), for a plain volume the b axis is; the window's sides are over (X, Y, Z), default 5 5 5,
+    and a side larger than its axis is refused.  ``metrics.json`` gains ``denoise``, ``denoise_window`` and ``denoise_sigma_median``
+    (the median of the noise map, in the units of the file).  Without the flag every output is bit for bit what it was.
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
@@ -100,6 +105,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 import mri_super_resolution_amd as inr  # noqa: E402
 from mri_super_resolution_amd import baselines, drivers, matio, metrics, reports, wire  # noqa: E402
+from mri_super_resolution_amd import denoise as denoise_mod  # noqa: E402
 from mri_super_resolution_amd import footprint as footprint_mod  # noqa: E402
 
 
@@ -181,6 +187,11 @@ def build_parser():
                         "of the network over its 2 x 2 HR pixels")
     p.add_argument("--footprint_samples", type=int, default=2,
                    help="--footprint box: midpoint nodes per in-plane axis (2 = the discrete block mean on the HR grid; at most 8)")
+    p.add_argument("--denoise", choices=("none", "mppca"), default="none",
+                   help="denoise the raw stack before the per-cell normalisation: MP-PCA over the acquisitions of hybrid_raw (or the b "
+                        "axis of a plain volume); metrics.json gains denoise, denoise_window and denoise_sigma_median")
+    p.add_argument("--denoise_window", type=int, nargs=3, default=list(denoise_mod.DEFAULT_WINDOW), metavar=("A", "B", "C"),
+                   help="--denoise mppca: odd window sides over (X, Y, Z), each at most its axis")
     p.add_argument("--wire_omega", type=float, default=1.2, help="--model wire: omega_0 of every layer (wiretest.ipynb cell 7)")
     p.add_argument("--wire_scale", type=float, default=1.2, help="--model wire: scale_0 of every layer (wiretest.ipynb cell 7)")
     return p
@@ -196,11 +207,13 @@ def load_input(path, key=None):
     return load_input_and_scale(path, key)[:4]
 
 
-def load_input_and_scale(path, key=None, refuse_acquisitions=None):
+def load_input_and_scale(path, key=None, refuse_acquisitions=None, denoise=None):
     """``load_input`` plus the per-b factors [B] that turn ``mean_img`` back into signal for the ADC maps: ``maxes[:, 1]``
     (TE index 1, superresDWI.py:193-195; None when ``hybrid_raw`` has a single TE) or, for a plain volume, the per-b maxima it
     was divided by.  ``refuse_acquisitions``: the reason for which an input with single acquisitions (``hybrid_raw``) is
-    refused (``_check_model``) -- raised before their products are formed on the device."""
+    refused (``_check_model``) -- raised before their products are formed on the device.  ``denoise``: None, or a dict with ``window``
+    (and optionally ``estimator``): the raw stack is MP-PCA denoised before anything is divided by a maximum, and the dict receives
+    ``sigma_median``, the median of the noise map in the file's units."""
     data = matio.loadmat(path)
     if key is None and "hybrid_raw" in data:
         key = "hybrid_raw"
@@ -214,6 +227,11 @@ def load_input_and_scale(path, key=None, refuse_acquisitions=None):
         if refuse_acquisitions:
             raise ValueError(f"{path}: {refuse_acquisitions}")
         raw = [[np.asarray(arr[b][te], np.float64) for te in range(arr.shape[1])] for b in range(arr.shape[0])]
+        if denoise is not None:
+            clean, info = denoise_mod.mppca(denoise_mod.stack_hybrid(raw), denoise["window"], estimator=denoise.get("estimator", "exp2"),
+                                            return_info=True)
+            raw = denoise_mod.unstack_hybrid(clean, raw)
+            denoise["sigma_median"] = float(np.median(info["sigma"]))
         maxes = np.array([[raw[b][te].max() for te in range(len(raw[b]))] for b in range(len(raw))])
         norm = [[raw[b][te] / maxes[b, te] for te in range(len(raw[b]))] for b in range(len(raw))]
         acq = drivers.acquisition_products(norm)                       # [X, Y, Z, B, K]
@@ -222,6 +240,10 @@ def load_input_and_scale(path, key=None, refuse_acquisitions=None):
     vol = np.asarray(arr, np.float64)
     if vol.ndim == 3:
         vol = vol[..., None]
+    if denoise is not None:
+        vol, info = denoise_mod.mppca(vol, denoise["window"], estimator=denoise.get("estimator", "exp2"), return_info=True,
+                                      measurement_axis=-1)
+        denoise["sigma_median"] = float(np.median(info["sigma"]))
     per_b_max = vol.reshape(-1, vol.shape[-1]).max(axis=0)
     vol = vol / per_b_max                                                # per-b normalisation (superresDWI.py:50-55)
     bvals = np.asarray(data["b"], np.float64).reshape(-1) if "b" in data else np.zeros(vol.shape[-1])
@@ -240,7 +262,8 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     refuse_acquisitions = _check_footprint(args, external_fit=fit is not None)
     _check_tv(args, fit)
     refuse_acquisitions = (check_model or _check_model)(args) or refuse_acquisitions
-    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, refuse_acquisitions)
+    denoise = {"window": tuple(args.denoise_window)} if getattr(args, "denoise", "none") == "mppca" else None
+    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, refuse_acquisitions, denoise)
     r0, r1 = args.roi_start, args.roi_end
     if r1 > min(mean_img.shape[:2]) or r0 < 0 or r1 - r0 < 14:
         raise ValueError(f"ROI {r0}:{r1} does not fit the {mean_img.shape[:2]} slices (SSIM needs >= 7 x 7 LR pixels)")
@@ -382,6 +405,8 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         pred = inr.footprint_forward(INR, coords, B, footprint)
         summary.update({"lr_model": "average", "footprint": args.footprint, "footprint_samples": footprint.count,
                         "lr_consistency_psnr_db": float(metrics.psnr(target.reshape(1, -1), pred.reshape(1, -1), 1.0))})
+    if denoise is not None:
+        summary.update({"denoise": "mppca", "denoise_window": list(denoise["window"]), "denoise_sigma_median": denoise["sigma_median"]})
     summary.update(fit_summary)
     if args.transverse_length:
         coronal, summary["t_coronal_s"] = _coronal(INR, B, mean_img, test_shape, args, reconstruct)

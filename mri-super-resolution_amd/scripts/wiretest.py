@@ -16,7 +16,8 @@ optional ``--transverse_length`` / ``--adc`` products); ``metrics.json`` gains `
 in ``superresDWI --model wire``; ``--derivative_maps``, the SIREN's flag, stays refused, and so are ``--lr_model average`` and
 ``--footprint box``, which the parser inherits: the WIRE fit and the PerturbNet phase are point-sampled on the decimation grid
 (``superresDWI._check_footprint``, reached through ``run_patient`` before the input is loaded).  Loading, re-sampling, evaluation and
-writing are ``superresDWI``'s own functions.
+writing are ``superresDWI``'s own functions, so ``--denoise mppca [--denoise_window a b c]`` (MP-PCA denoising of the raw stack before
+the per-cell normalisation) is inherited with them.
 """
 from __future__ import annotations
 
