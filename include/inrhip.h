@@ -827,6 +827,50 @@ int inr_mppca_denoise(double* out, double* sigma, int32_t* rank, const double* x
 int inr_mppca_denoise_f32(float* out, float* sigma, int32_t* rank, const float* x, const uint8_t* mask, int M, int D, int H, int W,
                           int w0, int w1, int w2, int estimator, void* stream);
 
+/* ---- Gibbs-ringing removal by local sub-voxel shifts ---------------------------------------------------------------------
+ * No counterpart in the reference.  Kellner et al., MRM 2016 (`mrdegibbs`, DIPY's `gibbs_removal`); pinned to the definition below,
+ * which tests/degibbs_common.py restates in float64 numpy.  The data must lie on the acquired grid: scanner-interpolated or
+ * partial-Fourier data ring at another period and are not served.  All arithmetic is fp64.
+ * One line x[0..n), periodic, nshifts = N, window (w_min, w_max), all indices mod n:
+ *   shifts   s_0 = 0, s_j = j / (2N) and s_{N+j} = -j / (2N) for j = 1 .. N: 2N + 1 candidates in this order.
+ *   copies   x_s[i] = sum_j h_s((i - j) mod n) x[j] in ascending j, h_s(d) = (1/n) sum_{k = 0 .. floor(n/2)} c_k cos(2 pi k (d + s) / n)
+ *            in ascending k, c_0 = 1, c_k = 2, c_{n/2} = 1 for even n (the Nyquist bin split between +n/2 and -n/2); with s = j / (2N)
+ *            the phase is pi ((k (2N d + j)) mod (2N n)) / (N n), reduced exactly in integers.  x_s[i] is the band-limited interpolant
+ *            at i + s.  The copy for s_0 is the line itself, bit for bit.
+ *   measure  d_s[i] = |x_s[i] - x_s[i-1]|;  L_s[i] = sum_{t = w_min .. w_max} d_s[i - t],  R_s[i] = sum_t d_s[i + t + 1], ascending t;
+ *            tv_s[i] = min(L_s[i], R_s[i]).
+ *   choice   choice[i] = the first index in list order with the smallest tv (a strict < while walking the list).
+ *   output   with s the chosen shift: out[i] = x[i] (s = 0), (1 - s) x_s[i] + s x_s[i-1] (s > 0), (1 + s) x_s[i] - s x_s[i+1] (s < 0).
+ * One image I [H][W]:  c_a(k) = 1 + cos(2 pi k / n_a), exactly 0 at k = n_a / 2;  G1(k0, k1) = c_0(k0) / (c_0(k0) + c_1(k1)), and 1/2 at
+ * the one bin where both vanish (the published code zeroes that bin; with 1/2 the two parts sum to the image);  I1 = Re IDFT2(G1 DFT2(I)),
+ * I0 = I - I1;  out = U1(I1) + U0(I0) with U_a the line operation along axis a (0: down the rows, 1: along the columns).
+ * inr_degibbs_lines: in, out [n_lines][n] DEVICE, lines contiguous; choice [n_lines][n] DEVICE int32 or null (not wanted).
+ * inr_degibbs2d: in, out [n_images][H][W] DEVICE; choice [2][n_images][H][W] DEVICE int32, the axis-0 pass first, or null.
+ * out must not overlap in.  The workspace (DEVICE, 16-byte aligned, the planner's doubles) holds the table h [2 nshifts][n] of an axis
+ * -- never a dense operator per shift -- and, for images, the DFT matrices of the split and six planes of a chunk of images: a batch
+ * whose planes would exceed INR_DEGIBBS_CHUNK_DOUBLES doubles is walked in chunks of whole images inside the call, and its bits do not
+ * depend on that.  One kernel runs the whole shift loop of a pass on v_mfma_f64_16x16x4_f64; fixed-order sums, no atomics, no host
+ * read: two runs give the same bits, whatever the grid, the stream and an image's place in the batch.  The _f32 forms convert on load and
+ * round once on the last store.  n_lines == 0 / n_images == 0 succeed and launch nothing.  The planners return 0 for sizes every call
+ * refuses (they do not know the window: a line of 5 .. 2 w_max + 2 samples is planned and then refused).
+ * Refusals, before any device work: INR_E_INVALID for a null out or in, a negative count, nshifts outside 1 .. INR_DEGIBBS_MAX_SHIFTS,
+ * a window that does not satisfy 1 <= w_min <= w_max <= INR_DEGIBBS_MAX_WINDOW, a line (rows, columns) outside 2 w_max + 3 ..
+ * INR_DEGIBBS_MAX_LINE samples, out overlapping in; INR_E_WORKSPACE for a workspace smaller than planned (INR_E_ALIGN: misaligned). */
+#define INR_DEGIBBS_MAX_LINE 1024
+#define INR_DEGIBBS_MAX_SHIFTS 64
+#define INR_DEGIBBS_MAX_WINDOW 8
+#define INR_DEGIBBS_CHUNK_DOUBLES 2097152
+int64_t inr_degibbs_lines_workspace_doubles(long long n_lines, int n, int nshifts);
+int64_t inr_degibbs2d_workspace_doubles(int n_images, int height, int width, int nshifts);
+int inr_degibbs_lines(double* out, int32_t* choice, const double* in, long long n_lines, int n, int nshifts, int w_min, int w_max,
+                      double* workspace, int64_t workspace_doubles, void* stream);
+int inr_degibbs_lines_f32(float* out, int32_t* choice, const float* in, long long n_lines, int n, int nshifts, int w_min, int w_max,
+                          double* workspace, int64_t workspace_doubles, void* stream);
+int inr_degibbs2d(double* out, int32_t* choice, const double* in, int n_images, int height, int width, int nshifts, int w_min, int w_max,
+                  double* workspace, int64_t workspace_doubles, void* stream);
+int inr_degibbs2d_f32(float* out, int32_t* choice, const float* in, int n_images, int height, int width, int nshifts, int w_min,
+                      int w_max, double* workspace, int64_t workspace_doubles, void* stream);
+
 /* ---- second-order TGV super-resolution under the block operator: a prior that does not terrace smooth intensity -------
  * No counterpart in the reference.  Images, sides, factors and the HOST `kernel` as for inr_tvsr_solve2d.  An auxiliary field
  * v = (v0, v1) [n_images][2][H][W] absorbs the smooth part of the gradient (Bredies, Kunisch, Pock 2010; Knoll et al. 2011):

@@ -28,6 +28,7 @@ INR_TVSR_MAX_FACTOR, INR_TVSR_MAX_SIDE, INR_TVSR3D_MAX_ITER, INR_TVMF_MAX_FRAMES
 INR_TVMS_MAX_STACKS, INR_TVMS_MAX_TAPS = 8, 16
 INR_TVJ_MAX_CHANNELS = 16
 INR_MPPCA_MAX_RANK, INR_MPPCA_MAX_LONG = 64, 1024
+INR_DEGIBBS_MAX_LINE, INR_DEGIBBS_MAX_SHIFTS, INR_DEGIBBS_MAX_WINDOW, INR_DEGIBBS_CHUNK_DOUBLES = 1024, 64, 8, 1 << 21
 
 
 class InrHipError(RuntimeError):
@@ -225,6 +226,12 @@ SIGNATURES = {
     "inr_adc_signal_f32": (C.c_int, [c_f32p] * 3 + [C.POINTER(C.c_double), C.c_int64, C.c_int, C.c_int64, c_stream]),
     "inr_mppca_denoise": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 8 + [c_stream]),
     "inr_mppca_denoise_f32": (C.c_int, [c_f32p] * 2 + [C.c_void_p, c_f32p, C.c_void_p] + [C.c_int] * 8 + [c_stream]),
+    "inr_degibbs_lines_workspace_doubles": (C.c_int64, [C.c_longlong, C.c_int, C.c_int]),
+    "inr_degibbs2d_workspace_doubles": (C.c_int64, [C.c_int] * 4),
+    "inr_degibbs_lines": (C.c_int, [C.c_void_p] * 3 + [C.c_longlong] + [C.c_int] * 4 + [C.c_void_p, C.c_int64, c_stream]),
+    "inr_degibbs_lines_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_longlong] + [C.c_int] * 4 + [C.c_void_p, C.c_int64, c_stream]),
+    "inr_degibbs2d": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p, C.c_int64, c_stream]),
+    "inr_degibbs2d_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p] + [C.c_int] * 6 + [C.c_void_p, C.c_int64, c_stream]),
     "inr_tgv_workspace_doubles": (C.c_int64, [C.c_int] * 3),
     "inr_tgv_solve2d": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int,
                                                                     C.c_void_p, C.c_int64, c_stream]),

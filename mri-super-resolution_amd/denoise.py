@@ -5,7 +5,13 @@ The reference's later driver (inrDWI.py:44) fits ``hybrid_raw_clean``, the multi
 its tree; ``mppca`` is that step, ``stack_hybrid`` / ``unstack_hybrid`` turn the ``[b][TE]`` cell of a ``master.mat`` into the
 measurement-major stack it takes and back, and ``scripts/denoise.py`` writes the clean cell.  Every voxel of the 16 to ~40
 measurements spans only a few signal components: the spectrum of the M x N matrix of a voxel's window tells the noise level and how many
-components are noise, and the voxel is projected onto the others.  The noise map ``sigma`` comes with it.  There is no CPU fallback."""
+components are noise, and the voxel is projected onto the others.  The noise map ``sigma`` comes with it.
+
+``degibbs`` / ``degibbs_lines`` are the step that follows it in every pipeline (``mrdegibbs`` after ``dwidenoise``): Gibbs-ringing
+removal by local sub-voxel shifts (Kellner et al., MRM 2016) on the HIP kernels of csrc/degibbs.hip (``inr_degibbs2d``,
+``inr_degibbs_lines``).  An MR image is a truncated Fourier series, so every edge rings with a period of one acquired
+pixel; MP-PCA cannot remove that, it is signal.  The data must lie on the acquired grid -- scanner-interpolated or partial-Fourier data
+ring at another period and are not served -- and the 3-D variant is out of scope.  There is no CPU fallback."""
 from __future__ import annotations
 
 import numpy as np
@@ -15,6 +21,7 @@ from . import ops
 
 DEFAULT_WINDOW = (5, 5, 5)
 ESTIMATORS = tuple(ops.MPPCA_ESTIMATORS)
+DEGIBBS_DEFAULT_SHIFTS, DEGIBBS_DEFAULT_WINDOW = ops.DEGIBBS_DEFAULT_SHIFTS, ops.DEGIBBS_DEFAULT_WINDOW
 
 
 def mppca(data, window=DEFAULT_WINDOW, mask=None, estimator="exp2", return_info=False, measurement_axis=0):
@@ -75,6 +82,79 @@ def mppca(data, window=DEFAULT_WINDOW, mask=None, estimator="exp2", return_info=
     if as_numpy:
         sigma, rank = sigma.cpu().numpy(), rank.cpu().numpy()
     return out, {"sigma": sigma, "rank": rank}
+
+
+def _degibbs_input(who, data):
+    """True for an ndarray; refuses everything that is neither an ndarray nor a device float32 / float64 tensor."""
+    if isinstance(data, np.ndarray):
+        if data.dtype.kind not in "fiu" or data.dtype == np.float16:
+            raise TypeError(f"{who}: an ndarray must be real and at least float32 (got {data.dtype})")
+        return True
+    if not isinstance(data, torch.Tensor):
+        raise TypeError(f"{who} takes an ndarray or a device tensor (got {type(data).__name__})")
+    if data.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"{who}: device tensors must be float32 or float64 (got {data.dtype})")
+    if not data.is_cuda:
+        raise ops.InrDeviceError(f"{who}: the tensor is on {data.device}; pass an ndarray or a device tensor (there is no CPU fallback)")
+    return False
+
+
+def _axis(who, axis, ndim):
+    if isinstance(axis, bool) or int(axis) != axis or not -ndim <= axis < ndim:
+        raise ValueError(f"{who}: axis {axis!r} is out of range for {ndim} axes")
+    return int(axis) % ndim
+
+
+def degibbs(data, axes=(-2, -1), nshifts=DEGIBBS_DEFAULT_SHIFTS, window=DEGIBBS_DEFAULT_WINDOW, return_info=False):
+    """Gibbs-ringing removal of the images spanned by the two ``axes`` of ``data``; every other axis is batch (``axes=(0, 1)`` serves
+    the drivers' [X, Y, Z, M] layout; axes that are not the last two are moved and made contiguous here).  ``data``: an ndarray (any
+    real dtype; float64 inside and out) or a device tensor (float32 or float64, returned as given).  ``nshifts``: sub-pixel shifts per
+    side, 1 .. 64; ``window``: (w_min, w_max) of the oscillation measure, 1 <= w_min <= w_max <= 8; each image side needs
+    2 w_max + 3 .. 1024 samples.  Returns the unrung data like ``data``; with ``return_info`` also a dict with ``shift`` [2, ...], the
+    chosen shifts in pixels (float64) of the pass along ``axes[0]`` and of the pass along ``axes[1]``."""
+    who = "degibbs"
+    as_numpy = _degibbs_input(who, data)
+    if data.ndim < 2 or len(tuple(axes)) != 2:
+        raise ValueError(f"{who}: data needs at least 2 axes and axes names two of them (got shape {tuple(data.shape)}, axes {axes!r})")
+    a0, a1 = (_axis(who, a, data.ndim) for a in axes)
+    if a0 == a1:
+        raise ValueError(f"{who}: axes must be two different axes (got {axes!r})")
+    nshifts, w_min, w_max = ops.degibbs_params(who, (data.shape[a0], data.shape[a1]), nshifts, window)   # host-only refusals first
+    device = ops.require_gpu() if as_numpy else data.device
+    x = torch.from_numpy(np.array(data, dtype=np.float64, order="C")).to(device) if as_numpy else data
+    moved = x.movedim((a0, a1), (-2, -1))
+    batch = tuple(moved.shape[:-2])
+    H, W = moved.shape[-2:]
+    out, choice = ops.degibbs2d(moved.reshape((-1, H, W)).contiguous(), nshifts, (w_min, w_max), want_choice=return_info)
+    out = out.reshape(batch + (H, W)).movedim((-2, -1), (a0, a1)).contiguous()
+    if as_numpy:
+        out = out.cpu().numpy()
+    if not return_info:
+        return out
+    shift = ops.degibbs_shift(choice, nshifts).reshape((2,) + batch + (H, W)).movedim((-2, -1), (a0 + 1, a1 + 1)).contiguous()
+    return out, {"shift": shift.cpu().numpy() if as_numpy else shift}
+
+
+def degibbs_lines(x, axis=-1, nshifts=DEGIBBS_DEFAULT_SHIFTS, window=DEGIBBS_DEFAULT_WINDOW, return_info=False):
+    """The 1-D operation of ``degibbs`` on the lines of ``x`` along ``axis`` (periodic lines on the acquired grid); input, output and
+    ``return_info`` (``shift``, the shape of ``x``) as for ``degibbs``."""
+    who = "degibbs_lines"
+    as_numpy = _degibbs_input(who, x)
+    if x.ndim < 1:
+        raise ValueError(f"{who}: x needs at least 1 axis")
+    ax = _axis(who, axis, x.ndim)
+    nshifts, w_min, w_max = ops.degibbs_params(who, (x.shape[ax],), nshifts, window)
+    device = ops.require_gpu() if as_numpy else x.device
+    t = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(device) if as_numpy else x
+    moved = t.movedim(ax, -1)
+    out, choice = ops.degibbs_lines(moved.reshape((-1, moved.shape[-1])).contiguous(), nshifts, (w_min, w_max), want_choice=return_info)
+    out = out.reshape(moved.shape).movedim(-1, ax).contiguous()
+    if as_numpy:
+        out = out.cpu().numpy()
+    if not return_info:
+        return out
+    shift = ops.degibbs_shift(choice, nshifts).reshape(moved.shape).movedim(-1, ax).contiguous()
+    return out, {"shift": shift.cpu().numpy() if as_numpy else shift}
 
 
 def _cell_rows(cell):

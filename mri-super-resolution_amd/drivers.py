@@ -1275,7 +1275,7 @@ def acquisition_operators(model, side, lr_side, fwhm=None):
 
 
 def acquisition_model_study(slices, model="kspace", factor=None, lr_side=None, fwhm=None, noise=0.02, seed=0, tv_lambda=None,
-                            tv_huber=None, tv_iters=None, slice_ids=None):
+                            tv_huber=None, tv_iters=None, slice_ids=None, with_degibbs=False):
     """``slices`` [Z, R, R] in [0, 1]: the LR slices [Z, m, m] are made with the operator of ``model`` (``acquisition_operators``) plus
     Gaussian noise of ``noise`` -- slice z (``slice_ids[i]`` for row i where given, else i) draws it from
     ``np.random.default_rng(seed * 1000 + z)`` --, and reconstructed on the device by
@@ -1283,6 +1283,8 @@ def acquisition_model_study(slices, model="kspace", factor=None, lr_side=None, f
     'mirror'), ``tv_block`` (``baselines.tv_superres`` with the mean kernel: the model every other study assumes; absent when the ratio is
     no whole number of blocks) and ``tv_operator`` (``baselines.tv_superres_operator`` with the operator that made the data).  Both TV
     rows share ``tv_lambda``, ``tv_huber`` and ``tv_iters`` (the ``TVOP_DEFAULT_*`` where None): they differ in the forward model alone.
+    ``with_degibbs`` adds ``degibbs_zerofill`` and ``degibbs_spline``: the LR slices unrung on their own grid (``denoise.degibbs`` at its
+    defaults; the LR side must be at least 9), then re-sampled as ``zerofill`` and ``spline`` are.
     Returns ``{"images", "hr", "lr", "operators", "methods", "psnr", "ssim", "consistency", "info"}``: float64 device stacks, PSNR and
     SSIM (data range 1) [Z] per method, and the PSNR of ``A tv_operator`` against the LR data [Z]."""
     from . import baselines
@@ -1295,6 +1297,8 @@ def acquisition_model_study(slices, model="kspace", factor=None, lr_side=None, f
         raise ValueError(f"acquisition_model_study: slices are [Z, R, R] (got {vol.shape})")
     Z, R = vol.shape[0], vol.shape[1]
     m = check_acquisition_model(model, R, factor, lr_side, fwhm, noise, lam, huber, iters)
+    if with_degibbs:
+        ops.degibbs_params("acquisition_model_study: with_degibbs", (m, m), ops.DEGIBBS_DEFAULT_SHIFTS, ops.DEGIBBS_DEFAULT_WINDOW)
     ids = list(range(Z)) if slice_ids is None else [int(v) for v in slice_ids]
     if len(ids) != Z or (Z and min(ids) < 0):
         raise ValueError(f"acquisition_model_study: slice_ids are one index >= 0 per slice (got {slice_ids!r} for {Z} slices)")
@@ -1304,14 +1308,19 @@ def acquisition_model_study(slices, model="kspace", factor=None, lr_side=None, f
     hr = torch.from_numpy(vol).to(dev)
     y = baselines.operator_apply(hr, pair) + torch.from_numpy(eta).to(dev)
     whole = R % m == 0 and R // m <= ops.TVSR_MAX_FACTOR
-    images = {"spline": (baselines.rescale(y.float().contiguous(), R // m) if R % m == 0 else baselines.resize(y.float().contiguous(), (R, R))).double(),
-              "zerofill": baselines.fourier_resize(y, (R, R), "center", "mirror")}
+    spline = lambda t: (baselines.rescale(t.float().contiguous(), R // m) if R % m == 0 else baselines.resize(t.float().contiguous(), (R, R))).double()
+    images = {"spline": spline(y), "zerofill": baselines.fourier_resize(y, (R, R), "center", "mirror")}
     info = {}
     if whole:
         images["tv_block"], res = baselines.tv_superres(y, (R // m, R // m), "mean", lam, huber, int(iters), return_info=True)
         info["tv_block"] = {k: v.cpu().numpy() for k, v in res.items()}
     images["tv_operator"], res = baselines.tv_superres_operator(y, pair, lam, huber, int(iters), return_info=True)
     info["tv_operator"] = {k: v.cpu().numpy() for k, v in res.items()}
+    if with_degibbs:
+        from . import denoise
+        unrung = denoise.degibbs(y.contiguous())
+        images["degibbs_zerofill"] = baselines.fourier_resize(unrung, (R, R), "center", "mirror")
+        images["degibbs_spline"] = spline(unrung)
     f32 = lambda t: t.float().contiguous()
     psnr = {name: metrics.psnr(f32(hr), f32(v), 1.0, per_image=True).cpu().numpy() for name, v in images.items()}
     ssim = {name: metrics.ssim(f32(hr), f32(v), 1.0).cpu().numpy() for name, v in images.items()}

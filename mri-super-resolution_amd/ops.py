@@ -1015,6 +1015,78 @@ def mppca_denoise(x: torch.Tensor, window=(5, 5, 5), mask=None, estimator="exp2"
     return out, sigma, rank
 
 
+# ---- Gibbs-ringing removal by local sub-voxel shifts (include/inrhip.h) ---------------------------------------------------
+DEGIBBS_DEFAULT_SHIFTS, DEGIBBS_DEFAULT_WINDOW = 20, (1, 3)
+
+
+def degibbs_params(who, sides, nshifts, window):
+    """(nshifts, w_min, w_max) as ints for lines of the lengths ``sides``; refuses, by name, what ``inr_degibbs_lines`` /
+    ``inr_degibbs2d`` would refuse."""
+    try:
+        win = tuple(int(w) for w in window)
+        ok = len(win) == 2 and all(int(w) == w for w in window)
+    except (TypeError, ValueError):
+        win, ok = (), False
+    if not ok or not 1 <= win[0] <= win[1] <= _lib.INR_DEGIBBS_MAX_WINDOW:
+        raise ValueError(f"{who}: window must be (w_min, w_max) with 1 <= w_min <= w_max <= {_lib.INR_DEGIBBS_MAX_WINDOW} (got {window!r})")
+    if isinstance(nshifts, bool) or int(nshifts) != nshifts or not 1 <= int(nshifts) <= _lib.INR_DEGIBBS_MAX_SHIFTS:
+        raise ValueError(f"{who}: nshifts must be 1 .. {_lib.INR_DEGIBBS_MAX_SHIFTS} (got {nshifts!r})")
+    for n in sides:
+        if not 2 * win[1] + 3 <= n <= _lib.INR_DEGIBBS_MAX_LINE:
+            raise ValueError(f"{who}: lines of 2 w_max + 3 = {2 * win[1] + 3} .. {_lib.INR_DEGIBBS_MAX_LINE} samples (got {n})")
+    return int(nshifts), win[0], win[1]
+
+
+def degibbs_lines_workspace_doubles(n_lines: int, n: int, nshifts: int = DEGIBBS_DEFAULT_SHIFTS) -> int:
+    """``inr_degibbs_lines_workspace_doubles``; 0 for sizes every call refuses."""
+    return int(lib().inr_degibbs_lines_workspace_doubles(n_lines, n, nshifts))
+
+
+def degibbs2d_workspace_doubles(n: int, H: int, W: int, nshifts: int = DEGIBBS_DEFAULT_SHIFTS) -> int:
+    """``inr_degibbs2d_workspace_doubles``; 0 for sizes every call refuses."""
+    return int(lib().inr_degibbs2d_workspace_doubles(n, H, W, nshifts))
+
+
+def degibbs_lines(x: torch.Tensor, nshifts=DEGIBBS_DEFAULT_SHIFTS, window=DEGIBBS_DEFAULT_WINDOW, want_choice=False, workspace=None):
+    """``inr_degibbs_lines`` / ``_f32`` by the dtype of ``x`` [n_lines, n] on the current stream: returns (out like ``x``, choice
+    [n_lines, n] int32 -- the index of the chosen shift in list order -- or None)."""
+    _chk_batch(x, "x", 2, "[n_lines, n]", (torch.float32, torch.float64), dtype_first=True)
+    n_lines, n = x.shape
+    nshifts, w_min, w_max = degibbs_params("degibbs_lines", (n,), nshifts, window)
+    out = torch.empty_like(x)
+    choice = torch.empty((n_lines, n), dtype=torch.int32, device=x.device) if want_choice else None
+    if n_lines == 0:
+        return out, choice
+    ws = _f64_workspace(workspace, degibbs_lines_workspace_doubles(n_lines, n, nshifts), x.device)
+    entry = "inr_degibbs_lines" if x.dtype == torch.float64 else "inr_degibbs_lines_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), _ptr(choice), x.data_ptr(), n_lines, n, nshifts, w_min, w_max, ws.data_ptr(), ws.numel(),
+                                _stream()), entry)
+    return out, choice
+
+
+def degibbs2d(x: torch.Tensor, nshifts=DEGIBBS_DEFAULT_SHIFTS, window=DEGIBBS_DEFAULT_WINDOW, want_choice=False, workspace=None):
+    """``inr_degibbs2d`` / ``_f32`` by the dtype of ``x`` [n, H, W] on the current stream: returns (out like ``x``, choice [2, n, H, W]
+    int32, the axis-0 pass first, or None)."""
+    _chk_images(x, "x", (torch.float32, torch.float64))
+    n, H, W = x.shape
+    nshifts, w_min, w_max = degibbs_params("degibbs2d", (H, W), nshifts, window)
+    out = torch.empty_like(x)
+    choice = torch.empty((2, n, H, W), dtype=torch.int32, device=x.device) if want_choice else None
+    if n == 0:
+        return out, choice
+    ws = _f64_workspace(workspace, degibbs2d_workspace_doubles(n, H, W, nshifts), x.device)
+    entry = "inr_degibbs2d" if x.dtype == torch.float64 else "inr_degibbs2d_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), _ptr(choice), x.data_ptr(), n, H, W, nshifts, w_min, w_max, ws.data_ptr(), ws.numel(),
+                                _stream()), entry)
+    return out, choice
+
+
+def degibbs_shift(choice: torch.Tensor, nshifts: int) -> torch.Tensor:
+    """The chosen shifts in pixels (float64) from the indices ``choice`` of ``degibbs_lines`` / ``degibbs2d``."""
+    c = choice.to(torch.float64)
+    return torch.where(c <= nshifts, c, nshifts - c) / (2.0 * nshifts)
+
+
 # ---- second-order TGV under the block operator (include/inrhip.h, DESIGN.md 4r) --------------------------------------------------------
 def tgv_workspace_doubles(n: int, H: int, W: int) -> int:
     """``inr_tgv_workspace_doubles``; 0 for sizes ``inr_tgv_solve2d`` refuses."""

@@ -15,7 +15,10 @@ to ``side / --factor`` pixels a side (default 2) or to ``--lr_side`` pixels, whi
   zerofill     ``baselines.fourier_resize``, 'center' / 'mirror';
   tv_block     ``baselines.tv_superres`` with the mean kernel -- skipped, and absent from every output, when the ratio is no whole
                number of blocks;
-  tv_operator  ``baselines.tv_superres_operator`` with the operator that made the data.
+  tv_operator  ``baselines.tv_superres_operator`` with the operator that made the data;
+  degibbs_zerofill, degibbs_spline   only with ``--with_degibbs``: the LR slice unrung on its own grid (``denoise.degibbs``, Gibbs-ringing
+               removal by local sub-voxel shifts; the LR side must be at least 9), then re-sampled as ``zerofill`` /
+               ``spline`` are.  For ``--model kspace``, whose LR slices ring by construction, this is the study that step exists for.
 
 Both TV rows use ``--tv_lambda --tv_huber --tv_iters``.  Per patient, under ``<output_address>/pat<id>/``: ``acquisition_model.csv``
 (one row per slice: ``Pt_id, b-value, slice``, ``SSIM-<method>`` for the methods that ran), ``metrics.json`` (``psnr_<method>_db`` and
@@ -30,7 +33,7 @@ import os
 
 import numpy as np
 
-from mri_super_resolution_amd import baselines, drivers, matio
+from mri_super_resolution_amd import baselines, drivers, matio, ops
 from mri_super_resolution_amd.scripts.superresDWI import _patient_id, load_input_and_scale
 
 
@@ -55,6 +58,8 @@ def build_parser():
     p.add_argument("--roi_end", type=int, default=90)
     p.add_argument("--slices", type=int, nargs="*", default=None, help="slice indexes (default: every slice)")
     p.add_argument("--b_index", type=int, default=0, help="which b-value of the volume is studied")
+    p.add_argument("--with_degibbs", action="store_true",
+                   help="add the rows degibbs_zerofill and degibbs_spline: unring the LR slice (denoise.degibbs), then re-sample")
     return p
 
 
@@ -68,6 +73,8 @@ def check_args(args):
         raise ValueError(f"--slices are indexes >= 0 (got {args.slices})")
     if args.b_index < 0:
         raise ValueError(f"--b_index must be >= 0 (got {args.b_index})")
+    if getattr(args, "with_degibbs", False):
+        ops.degibbs_params("--with_degibbs", (m, m), ops.DEGIBBS_DEFAULT_SHIFTS, ops.DEGIBBS_DEFAULT_WINDOW)
     return m
 
 
@@ -87,7 +94,8 @@ def run_patient(path, pt_id, args):
     slices = np.ascontiguousarray(mean_img[r0:r1, r0:r1, :, args.b_index].transpose(2, 0, 1))[which]
     # slice z of the volume draws from seed * 1000 + z whatever --slices selects
     res = drivers.acquisition_model_study(slices, args.model, args.factor, args.lr_side, args.fwhm, args.noise, args.seed, args.tv_lambda,
-                                          args.tv_huber, args.tv_iters, slice_ids=which)
+                                          args.tv_huber, args.tv_iters, slice_ids=which,
+                                          with_degibbs=getattr(args, "with_degibbs", False))
     methods = res["methods"]
     b_value = float(bvalues[args.b_index]) if args.b_index < len(bvalues) else float(args.b_index)
     with open(os.path.join(out_dir, "acquisition_model.csv"), "w") as fh:

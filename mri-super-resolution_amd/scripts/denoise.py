@@ -2,7 +2,7 @@
 """MP-PCA denoising of the raw acquisition stack of a ``master.mat``: the step between the scanner's file and every fit.
 
     python -m mri_super_resolution_amd.scripts.denoise --data master.mat --out clean.mat [--window 5 5 5] [--estimator exp2]
-                                                       [--key hybrid_raw]
+                                                       [--key hybrid_raw] [--degibbs [--degibbs_shifts N]]
 
 The reference's later driver (inrDWI.py:44) reads ``hybrid_raw_clean``, the ``hybrid_raw`` cell after a denoising step made outside its
 tree.  This script makes it: every acquisition of every [b][TE] cell of ``--key`` is one measurement of ONE stack
@@ -10,7 +10,10 @@ tree.  This script makes it: every acquisition of every [b][TE] cell of ``--key`
 along (X, Y, Z), and the result goes back into the cell's layout.  ``--out`` holds ``<key>_clean`` in that layout, ``sigma`` (the noise
 map [X, Y, Z], in the file's units), ``rank`` (signal components per voxel, int32) and every other variable of the input file as it was;
 it is what ``superresDWI --key hybrid_raw_clean`` accepts.  A plain volume [X, Y, Z, B] under ``--key`` is denoised along its last axis.
-A window side larger than its axis is refused, not shrunk."""
+A window side larger than its axis is refused, not shrunk.  ``--degibbs`` unrings the (X, Y) planes of every measurement after MP-PCA
+(``denoise.degibbs``, Gibbs-ringing removal by local sub-voxel shifts with ``--degibbs_shifts`` shifts per side, DESIGN.md 4v -- the
+order of ``dwidenoise`` and ``mrdegibbs``; the data must lie on the acquired grid) and writes that as ``<key>_clean``; the summary gains
+``degibbs`` and ``degibbs_mean_abs_shift``.  Without the flag every output is what it was."""
 from __future__ import annotations
 
 import argparse
@@ -33,6 +36,8 @@ def build_parser():
     p.add_argument("--window", type=int, nargs=3, default=list(denoise.DEFAULT_WINDOW), metavar=("A", "B", "C"),
                    help="odd window sides over (X, Y, Z), each at most its axis")
     p.add_argument("--estimator", choices=denoise.ESTIMATORS, default="exp2", help="the cutoff estimator")
+    p.add_argument("--degibbs", action="store_true", help="unring the (X, Y) planes of every measurement after MP-PCA")
+    p.add_argument("--degibbs_shifts", type=int, default=denoise.DEGIBBS_DEFAULT_SHIFTS, help="--degibbs: sub-pixel shifts per side, 1 .. 64")
     return p
 
 
@@ -48,6 +53,8 @@ def main(argv=None):
             cell[idx] = np.asarray(raw[idx], np.float64)
         stack = denoise.stack_hybrid(cell)
         clean, info = denoise.mppca(stack, args.window, estimator=args.estimator, return_info=True)
+        if args.degibbs:                                                 # [M, X, Y, Z]: the (X, Y) planes
+            clean, gibbs = denoise.degibbs(clean, (1, 2), args.degibbs_shifts, return_info=True)
         clean = denoise.unstack_hybrid(clean, cell)
         M = stack.shape[0]
     else:
@@ -55,6 +62,8 @@ def main(argv=None):
         if vol.ndim != 4:
             raise ValueError(f"{args.data}: '{args.key}' must be a [b][TE] cell or a volume [X, Y, Z, B] (got shape {vol.shape})")
         clean, info = denoise.mppca(vol, args.window, estimator=args.estimator, return_info=True, measurement_axis=-1)
+        if args.degibbs:                                                 # [X, Y, Z, M]
+            clean, gibbs = denoise.degibbs(clean, (0, 1), args.degibbs_shifts, return_info=True)
         M = vol.shape[-1]
     out = {k: v for k, v in data.items() if not k.startswith("__")}
     out[f"{args.key}_clean"] = clean
@@ -65,6 +74,8 @@ def main(argv=None):
                "window": [int(w) for w in args.window], "estimator": args.estimator, "sigma_median": float(np.median(info["sigma"])),
                "rank_histogram": np.bincount(info["rank"].reshape(-1).clip(min=0)).tolist(),
                "unconverged": int((info["rank"] == -2).sum())}
+    if args.degibbs:
+        summary.update({"degibbs": True, "degibbs_mean_abs_shift": float(np.abs(gibbs["shift"]).mean())})
     print(json.dumps(summary))
     return summary
 

@@ -78,6 +78,10 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     a measurement (``denoise.stack_hybrid``), for a plain volume the b axis is; the window's sides are over (X, Y, Z), default 5 5 5,
     and a side larger than its axis is refused.  ``metrics.json`` gains ``denoise``, ``denoise_window`` and ``denoise_sigma_median``
     (the median of the noise map, in the units of the file).  Without the flag every output is bit for bit what it was.
+  * ``--degibbs``: Gibbs-ringing removal by local sub-voxel shifts (``denoise.degibbs``, ``inr_degibbs2d``) of the (X, Y)
+    planes of the raw stack, after ``--denoise`` and before the per-cell normalisation -- the order of ``dwidenoise`` and
+    ``mrdegibbs``.  The data must lie on the acquired grid (scanner-interpolated or partial-Fourier data ring at another period).
+    ``metrics.json`` gains ``degibbs`` and ``degibbs_mean_abs_shift`` (pixels).  Without the flag every output is what it was.
 ``--model wire`` fits the complex-Gabor network of wiretest.ipynb (cells 2, 7) instead of the SIREN: ``hidden_features =
 hidden_dim // 2`` (cell 7), ``omega_0 = --wire_omega`` and ``scale_0 = --wire_scale`` for every layer (1.2 both, cell 7), the
 plain fit on the mean image (cell 10's first branch) through ``wire.fit_wire``; re-sampling, the SSIM CSV,
@@ -192,6 +196,9 @@ def build_parser():
                         "axis of a plain volume); metrics.json gains denoise, denoise_window and denoise_sigma_median")
     p.add_argument("--denoise_window", type=int, nargs=3, default=list(denoise_mod.DEFAULT_WINDOW), metavar=("A", "B", "C"),
                    help="--denoise mppca: odd window sides over (X, Y, Z), each at most its axis")
+    p.add_argument("--degibbs", action="store_true",
+                   help="unring the (X, Y) planes of the raw stack (after --denoise, before the per-cell normalisation); metrics.json "
+                        "gains degibbs and degibbs_mean_abs_shift")
     p.add_argument("--wire_omega", type=float, default=1.2, help="--model wire: omega_0 of every layer (wiretest.ipynb cell 7)")
     p.add_argument("--wire_scale", type=float, default=1.2, help="--model wire: scale_0 of every layer (wiretest.ipynb cell 7)")
     return p
@@ -207,13 +214,15 @@ def load_input(path, key=None):
     return load_input_and_scale(path, key)[:4]
 
 
-def load_input_and_scale(path, key=None, refuse_acquisitions=None, denoise=None):
+def load_input_and_scale(path, key=None, refuse_acquisitions=None, denoise=None, degibbs=None):
     """``load_input`` plus the per-b factors [B] that turn ``mean_img`` back into signal for the ADC maps: ``maxes[:, 1]``
     (TE index 1, superresDWI.py:193-195; None when ``hybrid_raw`` has a single TE) or, for a plain volume, the per-b maxima it
     was divided by.  ``refuse_acquisitions``: the reason for which an input with single acquisitions (``hybrid_raw``) is
     refused (``_check_model``) -- raised before their products are formed on the device.  ``denoise``: None, or a dict with ``window``
     (and optionally ``estimator``): the raw stack is MP-PCA denoised before anything is divided by a maximum, and the dict receives
-    ``sigma_median``, the median of the noise map in the file's units."""
+    ``sigma_median``, the median of the noise map in the file's units.  ``degibbs``: None, or a dict (optionally with ``nshifts``): the (X,
+    Y) planes of the raw stack are unrung (``denoise.degibbs``) after the denoising and before anything is divided by a maximum, and
+    the dict receives ``mean_abs_shift`` (pixels)."""
     data = matio.loadmat(path)
     if key is None and "hybrid_raw" in data:
         key = "hybrid_raw"
@@ -232,6 +241,11 @@ def load_input_and_scale(path, key=None, refuse_acquisitions=None, denoise=None)
                                             return_info=True)
             raw = denoise_mod.unstack_hybrid(clean, raw)
             denoise["sigma_median"] = float(np.median(info["sigma"]))
+        if degibbs is not None:
+            clean, info = denoise_mod.degibbs(denoise_mod.stack_hybrid(raw), (1, 2), degibbs.get("nshifts", denoise_mod.DEGIBBS_DEFAULT_SHIFTS),
+                                              return_info=True)
+            raw = denoise_mod.unstack_hybrid(clean, raw)
+            degibbs["mean_abs_shift"] = float(np.abs(info["shift"]).mean())
         maxes = np.array([[raw[b][te].max() for te in range(len(raw[b]))] for b in range(len(raw))])
         norm = [[raw[b][te] / maxes[b, te] for te in range(len(raw[b]))] for b in range(len(raw))]
         acq = drivers.acquisition_products(norm)                       # [X, Y, Z, B, K]
@@ -244,6 +258,9 @@ def load_input_and_scale(path, key=None, refuse_acquisitions=None, denoise=None)
         vol, info = denoise_mod.mppca(vol, denoise["window"], estimator=denoise.get("estimator", "exp2"), return_info=True,
                                       measurement_axis=-1)
         denoise["sigma_median"] = float(np.median(info["sigma"]))
+    if degibbs is not None:
+        vol, info = denoise_mod.degibbs(vol, (0, 1), degibbs.get("nshifts", denoise_mod.DEGIBBS_DEFAULT_SHIFTS), return_info=True)
+        degibbs["mean_abs_shift"] = float(np.abs(info["shift"]).mean())
     per_b_max = vol.reshape(-1, vol.shape[-1]).max(axis=0)
     vol = vol / per_b_max                                                # per-b normalisation (superresDWI.py:50-55)
     bvals = np.asarray(data["b"], np.float64).reshape(-1) if "b" in data else np.zeros(vol.shape[-1])
@@ -263,7 +280,8 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     _check_tv(args, fit)
     refuse_acquisitions = (check_model or _check_model)(args) or refuse_acquisitions
     denoise = {"window": tuple(args.denoise_window)} if getattr(args, "denoise", "none") == "mppca" else None
-    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, refuse_acquisitions, denoise)
+    degibbs = {} if getattr(args, "degibbs", False) else None
+    mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, refuse_acquisitions, denoise, degibbs)
     r0, r1 = args.roi_start, args.roi_end
     if r1 > min(mean_img.shape[:2]) or r0 < 0 or r1 - r0 < 14:
         raise ValueError(f"ROI {r0}:{r1} does not fit the {mean_img.shape[:2]} slices (SSIM needs >= 7 x 7 LR pixels)")
@@ -407,6 +425,8 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
                         "lr_consistency_psnr_db": float(metrics.psnr(target.reshape(1, -1), pred.reshape(1, -1), 1.0))})
     if denoise is not None:
         summary.update({"denoise": "mppca", "denoise_window": list(denoise["window"]), "denoise_sigma_median": denoise["sigma_median"]})
+    if degibbs is not None:
+        summary.update({"degibbs": True, "degibbs_mean_abs_shift": degibbs["mean_abs_shift"]})
     summary.update(fit_summary)
     if args.transverse_length:
         coronal, summary["t_coronal_s"] = _coronal(INR, B, mean_img, test_shape, args, reconstruct)

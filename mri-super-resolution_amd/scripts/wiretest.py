@@ -17,7 +17,7 @@ in ``superresDWI --model wire``; ``--derivative_maps``, the SIREN's flag, stays 
 ``--footprint box``, which the parser inherits: the WIRE fit and the PerturbNet phase are point-sampled on the decimation grid
 (``superresDWI._check_footprint``, reached through ``run_patient`` before the input is loaded).  Loading, re-sampling, evaluation and
 writing are ``superresDWI``'s own functions, so ``--denoise mppca [--denoise_window a b c]`` (MP-PCA denoising of the raw stack before
-the per-cell normalisation) is inherited with them.
+the per-cell normalisation) and ``--degibbs`` (Gibbs-ringing removal after it) are inherited with them.
 """
 from __future__ import annotations
 
