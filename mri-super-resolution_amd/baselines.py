@@ -59,6 +59,8 @@ method with the data term dualised, one workgroup per group (``inr_tvadc_solve2d
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -251,29 +253,25 @@ def fourier_operator(n, m, align: str = 'sample', boundary: str = 'mirror', apod
 TV_DEFAULT_LAMBDA, TV_DEFAULT_HUBER, TV_DEFAULT_ITERS = 3e-3, 0.3, 300       # the sweep of DESIGN.md 4l
 
 
+def _named_kernel(kind, *f):
+    """The block kernel 'mean' or 'decimate' of the factors ``f`` (one: 1-D, two: [f0][f1]) as a float64 ndarray; None for another name."""
+    if kind == "mean":
+        return np.full(f, 1.0 / math.prod(f))
+    if kind == "decimate":
+        k = np.zeros(f)
+        k.flat[0] = 1.0
+        return k
+    return None
+
+
 def _block_kernel(who, kernel, factors):
     """'mean', 'decimate' or an array [f0][f1] -> (f0, f1, nested float lists), refusing by name."""
-    try:
-        f0, f1 = (int(f) for f in factors)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: factors are (f0, f1), one per trailing axis (got {factors!r})") from None
-    if not (1 <= f0 <= ops.TVSR_MAX_FACTOR and 1 <= f1 <= ops.TVSR_MAX_FACTOR):
-        raise ValueError(f"{who}: factors are 1 .. {ops.TVSR_MAX_FACTOR} per axis (got {f0} x {f1})")
+    f0, f1 = ops.tv_factors(who, factors)
     if isinstance(kernel, str):
-        if kernel == "mean":
-            k = np.full((f0, f1), 1.0 / (f0 * f1))
-        elif kernel == "decimate":
-            k = np.zeros((f0, f1))
-            k[0, 0] = 1.0
-        else:
-            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or an array [f0][f1] (got {kernel!r})")
-    else:
-        k = np.asarray(kernel, dtype=np.float64)
-        if k.shape != (f0, f1):
-            raise ValueError(f"{who}: the kernel array must be [{f0}][{f1}] (got {k.shape})")
-        if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
-            raise ValueError(f"{who}: the kernel array must be finite and sum to 1 (got sum {k.sum()!r})")
-    return f0, f1, k.tolist()
+        name, kernel = kernel, _named_kernel(kernel, f0, f1)
+        if kernel is None:
+            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or an array [f0][f1] (got {name!r})")
+    return f0, f1, ops.tv_block_kernel(who, kernel, (f0, f1))
 
 
 def _block_input(who, image, name="input"):
@@ -295,20 +293,13 @@ def _block_batch(image, as_numpy):
     return _device_batch(image, as_numpy, 2)
 
 
-def _hr_sides(who, rows, cols, f0, f1):
-    if rows < 1 or cols < 1 or rows > ops.TVSR_MAX_SIDE or cols > ops.TVSR_MAX_SIDE:
-        raise ValueError(f"{who}: HR images of 1 .. {ops.TVSR_MAX_SIDE} samples per axis (got {rows} x {cols})")
-    if rows % f0 or cols % f1:
-        raise ValueError(f"{who}: the HR image {rows} x {cols} is no whole number of {f0} x {f1} blocks")
-
-
 def block_apply(x, factors, kernel="mean"):
     """``A x``: every ``f0 x f1`` block of the trailing two axes of ``x`` summed with the weights ``kernel`` -- 'mean' (the block mean),
     'decimate' (its first sample: LR sample j on HR sample f j) or an array [f0][f1] that sums to 1 (``inr_block_apply2d``, fp64).
     Leading axes are a batch; ndarray in -> float64 ndarray out, device fp32 / fp64 tensor in -> the same out."""
     f0, f1, k = _block_kernel("block_apply", kernel, factors)
     as_numpy, H, W, lead = _block_input("block_apply", x)
-    _hr_sides("block_apply", H, W, f0, f1)
+    ops.tv_hr_sides("block_apply", (H, W), (f0, f1))
     flat = _block_batch(x, as_numpy)
     out = ops.block_apply(flat.double(), (f0, f1), k).to(flat.dtype).reshape(*lead, H // f0, W // f1)
     return out.cpu().numpy() if as_numpy else out
@@ -318,7 +309,7 @@ def block_adjoint(r, factors, kernel="mean"):
     """``A^T r``: ``kernel[a][b] r[i][j]`` spread over block (i, j) (``inr_block_adjoint2d``); types as ``block_apply``."""
     f0, f1, k = _block_kernel("block_adjoint", kernel, factors)
     as_numpy, h, w, lead = _block_input("block_adjoint", r)
-    _hr_sides("block_adjoint", h * f0, w * f1, f0, f1)
+    ops.tv_hr_sides("block_adjoint", (h * f0, w * f1), (f0, f1))
     flat = _block_batch(r, as_numpy)
     out = ops.block_adjoint(flat.double(), (f0, f1), k).to(flat.dtype).reshape(*lead, h * f0, w * f1)
     return out.cpu().numpy() if as_numpy else out
@@ -344,30 +335,6 @@ def _weight_and_start(who, lr, as_numpy, lead, weight, lr_shape, x0, hr_shape, l
     return {name: None if item is None else _device_batch(item[0], as_numpy, item[1]) for name, item in extra.items()}   # the device last
 
 
-def _tv_scalars(who, lam, huber, n_iter, max_iter=None, span="0 .."):
-    """(lam, huber, n_iter) of a solver, refused by name; ``span``: how the function words the range of ``n_iter`` up to ``max_iter``."""
-    lam, huber = float(lam), float(huber)
-    if not 0.0 <= lam < np.inf:
-        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
-    if not 0.0 <= huber < np.inf:
-        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
-    if int(n_iter) != n_iter or n_iter < 0 or (max_iter is not None and n_iter > max_iter):
-        bound = ">= 0" if max_iter is None else f"{span} {max_iter}"
-        raise ValueError(f"{who}: n_iter must be an integer {bound} (got {n_iter!r})")
-    return lam, huber, int(n_iter)
-
-
-def _grad_weights(who, grad_weights):
-    """(g0, g1, g2) of a 3-D prior as floats, refused by name."""
-    try:
-        g = tuple(float(v) for v in grad_weights)
-    except (TypeError, ValueError):
-        g = ()
-    if len(g) != 3 or not all(0.0 <= v < np.inf for v in g):
-        raise ValueError(f"{who}: grad_weights are (g0, g1, g2), finite and >= 0 (got {grad_weights!r})")
-    return g
-
-
 def _tv_output(as_numpy, lead, out, trailing, info, return_info):
     """The tail of a solver: ``out`` [n, *trailing] and the per-image ``info`` tensors [n] in the leading shape, ndarrays if ndarrays
     came in."""
@@ -391,9 +358,9 @@ def tv_superres(lr, factors, kernel="mean", lam: float = TV_DEFAULT_LAMBDA, hube
     both of the leading shape."""
     who = "tv_superres"
     f0, f1, k = _block_kernel(who, kernel, factors)
-    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter)
+    lam, huber, n_iter = ops.tv_scalars(who, lam, huber, n_iter)
     as_numpy, h, w, lead = _block_input(who, lr)
-    _hr_sides(who, h * f0, w * f1, f0, f1)
+    ops.tv_hr_sides(who, (h * f0, w * f1), (f0, f1))
     extra = _weight_and_start(who, lr, as_numpy, lead, weight, (h, w), x0, (h * f0, w * f1))
     y = _block_batch(lr, as_numpy)
     out, energy, change = ops.tvsr_solve(y, (f0, f1), k, lam, huber, n_iter, extra["weight"], extra["x0"])
@@ -439,23 +406,15 @@ def tv_superres_joint(lr, factors, kernel="mean", lam: float = TVJ_DEFAULT_LAMBD
     launch for the whole batch, one workgroup per group (``inr_tvj_solve2d``).  There is no CPU fallback."""
     who = "tv_superres_joint"
     f0, f1, k = _block_kernel(who, kernel, factors)
-    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter)
-    if coupling not in ("joint", "none"):
-        raise ValueError(f"{who}: coupling must be 'joint' or 'none' (got {coupling!r})")
+    lam, huber, n_iter = ops.tv_scalars(who, lam, huber, n_iter)
+    ops.tv_coupling(who, coupling)
     as_numpy = _fourier_input(who, lr)
     if lr.ndim < 3:
         raise ValueError(f"{who} needs at least 3-D input [..., C, h, w]")
     C, h, w, lead = int(lr.shape[-3]), int(lr.shape[-2]), int(lr.shape[-1]), tuple(lr.shape[:-3])
-    if not 1 <= C <= ops.TVJ_MAX_CHANNELS:
-        raise ValueError(f"{who}: channels are 1 .. {ops.TVJ_MAX_CHANNELS} per group (got {C})")
-    _hr_sides(who, h * f0, w * f1, f0, f1)
-    mu = None
-    if channel_weights is not None:
-        mu = np.asarray(channel_weights, np.float64).reshape(-1)
-        if mu.shape != (C,) or not (np.isfinite(mu).all() and (mu >= 0).all() and (mu <= 1).all()):
-            raise ValueError(f"{who}: channel_weights are {C} finite values within [0, 1] (got {mu.tolist()}); larger weights are a "
-                             f"rescaled lam and huber")
-        mu = mu.tolist()
+    ops.tvj_channels(who, C)
+    ops.tv_hr_sides(who, (h * f0, w * f1), (f0, f1))
+    mu = ops.tvj_channel_weights(who, channel_weights, C)
     extra = _weight_and_start(who, lr, as_numpy, lead, weight, (C, h, w), x0, (C, h * f0, w * f1))
     y = _device_batch(lr, as_numpy, 3)
     out, energy, change = ops.tvj_solve(y, (f0, f1), k, mu, lam, huber, coupling, n_iter, extra["weight"], extra["x0"])
@@ -466,39 +425,6 @@ def tv_superres_joint(lr, factors, kernel="mean", lam: float = TVJ_DEFAULT_LAMBD
 ADC_DEFAULT_LAMBDA, ADC_DEFAULT_HUBER, ADC_DEFAULT_ITERS = 0.00125, 0.03, 3000
 ADC_DEFAULT_MAP_WEIGHTS, ADC_DEFAULT_COUPLING = (1.0, 0.05), "joint"
 ADC_DEFAULT_S_MAX, ADC_DEFAULT_ADC_MAX, ADC_DEFAULT_ADC0 = 1.5, 4e-3, 1e-3
-
-
-def _adc_model(who, b, channels, map_weights, coupling, s_max, adc_max, adc0):
-    """The model's host values of ``tv_superres_adc``, refused by name: -> (b, (mu_s, mu_d), s_max, adc_max, adc0) as floats."""
-    try:
-        vals = np.asarray(b, np.float64).reshape(-1)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: b must be a sequence of b-values (got {b!r})") from None
-    if not 2 <= channels <= ops.TVJ_MAX_CHANNELS:
-        raise ValueError(f"{who}: b-values are 2 .. {ops.TVJ_MAX_CHANNELS} per group (got {channels})")
-    if vals.shape != (channels,):
-        raise ValueError(f"{who}: b has {vals.size} b-values, expected one per channel ({channels})")
-    if not (np.isfinite(vals).all() and (vals >= 0).all()):
-        raise ValueError(f"{who}: b-values must be finite and >= 0 (got {vals.tolist()})")
-    if vals.max() == vals.min():
-        raise ValueError(f"{who}: the b-values are all equal ({vals[0]!r}): they determine no ADC")
-    if coupling not in ("joint", "none"):
-        raise ValueError(f"{who}: coupling must be 'joint' or 'none' (got {coupling!r})")
-    try:
-        mu = np.asarray(map_weights, np.float64).reshape(-1)
-    except (TypeError, ValueError):
-        mu = np.zeros(0)
-    if mu.shape != (2,) or not (np.isfinite(mu).all() and (mu >= 0).all() and (mu <= 1).all()):
-        raise ValueError(f"{who}: map_weights are (mu_s, mu_d), two finite values within [0, 1] (got {map_weights!r}); larger weights are "
-                         f"a rescaled lam and huber")
-    s_max, adc_max, adc0 = float(s_max), float(adc_max), float(adc0)
-    if not 0.0 < s_max < np.inf:
-        raise ValueError(f"{who}: s_max must be finite and > 0 (got {s_max!r})")
-    if not 0.0 < adc_max < np.inf or not adc_max * vals.max() < np.inf:
-        raise ValueError(f"{who}: adc_max must be finite and > 0 (got {adc_max!r})")
-    if not 0.0 <= adc0 <= adc_max:
-        raise ValueError(f"{who}: adc0 must be within [0, adc_max] (got {adc0!r}, adc_max {adc_max!r})")
-    return vals.tolist(), mu.tolist(), s_max, adc_max, adc0
 
 
 def tv_superres_adc(lr, b, factors, kernel="mean", lam: float = ADC_DEFAULT_LAMBDA, huber: float = ADC_DEFAULT_HUBER,
@@ -521,14 +447,14 @@ def tv_superres_adc(lr, b, factors, kernel="mean", lam: float = ADC_DEFAULT_LAMB
     one workgroup per group (``inr_tvadc_solve2d``).  There is no CPU fallback."""
     who = "tv_superres_adc"
     f0, f1, k = _block_kernel(who, kernel, factors)
-    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter)
+    lam, huber, n_iter = ops.tv_scalars(who, lam, huber, n_iter)
     as_numpy = _fourier_input(who, lr)
     if lr.ndim < 3:
         raise ValueError(f"{who} needs at least 3-D input [..., C, h, w]")
     C, h, w, lead = int(lr.shape[-3]), int(lr.shape[-2]), int(lr.shape[-1]), tuple(lr.shape[:-3])
-    vals, mu, s_max, adc_max, adc0 = _adc_model(who, b, C, map_weights, coupling, s_max, adc_max, adc0)
+    vals, mu, s_max, adc_max, adc0 = ops.tvadc_model(who, b, C, map_weights, coupling, s_max, adc_max, adc0)
     H, W = h * f0, w * f1
-    _hr_sides(who, H, W, f0, f1)
+    ops.tv_hr_sides(who, (H, W), (f0, f1))
     if x0 is not None:
         if not isinstance(x0, (tuple, list)) or len(x0) != 2:
             raise ValueError(f"{who}: x0 is a pair (s0, adc) of maps of shape {lead + (H, W)}")
@@ -562,10 +488,8 @@ def adc_signal(s0, adc, b):
     _fourier_input(who, adc)
     if tuple(adc.shape) != tuple(s0.shape) or (not as_numpy and adc.dtype != s0.dtype):
         raise ValueError(f"{who}: adc must have the shape and type of s0 ({tuple(s0.shape)}; got {tuple(adc.shape)}, {adc.dtype})")
-    vals = np.asarray(b, np.float64).reshape(-1)
-    if not 1 <= vals.size <= ops.TVJ_MAX_CHANNELS or not np.isfinite(vals).all():
-        raise ValueError(f"{who}: b is 1 .. {ops.TVJ_MAX_CHANNELS} finite b-values (got {vals.tolist()})")
-    out = ops.adc_signal(_block_batch(s0, as_numpy), _block_batch(adc, as_numpy), vals.tolist()).reshape(*lead, vals.size, H, W)
+    vals = ops.adc_bvalues(who, b)
+    out = ops.adc_signal(_block_batch(s0, as_numpy), _block_batch(adc, as_numpy), vals).reshape(*lead, len(vals), H, W)
     return out.cpu().numpy() if as_numpy else out
 
 
@@ -585,11 +509,10 @@ def tgv_superres(lr, factors, kernel="mean", lam: float = TGV_DEFAULT_LAMBDA, ra
     who = "tgv_superres"
     f0, f1, k = _block_kernel(who, kernel, factors)
     ratio = float(ratio)
-    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter)
-    if not 0.0 < ratio < np.inf:
-        raise ValueError(f"{who}: ratio must be finite and > 0 (got {ratio!r})")
+    lam, huber, n_iter = ops.tv_scalars(who, lam, huber, n_iter)
+    ops.tgv_ratio(who, ratio)
     as_numpy, h, w, lead = _block_input(who, lr)
-    _hr_sides(who, h * f0, w * f1, f0, f1)
+    ops.tv_hr_sides(who, (h * f0, w * f1), (f0, f1))
     extra = _weight_and_start(who, lr, as_numpy, lead, weight, (h, w), x0, (h * f0, w * f1))
     y = _block_batch(lr, as_numpy)
     out, v, energy, change = ops.tgv_solve(y, (f0, f1), k, lam, ratio, huber, n_iter, extra["weight"], extra["x0"], want_v=return_info)
@@ -602,11 +525,6 @@ def tgv_superres(lr, factors, kernel="mean", lam: float = TGV_DEFAULT_LAMBDA, ra
 
 
 TVMF_DEFAULT_LAMBDA,TVMF_DEFAULT_HUBER, TVMF_DEFAULT_ITERS = 0.01, 0.03, 300  # the sweep of DESIGN.md 4n (8 frames, noise 0.02)
-
-
-def _frame_count(who, K):
-    if not 1 <= K <= ops.TVMF_MAX_FRAMES:
-        raise ValueError(f"{who}: frames per image are 1 .. {ops.TVMF_MAX_FRAMES} (got {K})")
 
 
 def _shift_input(who, shifts, lead, K=None):
@@ -626,7 +544,7 @@ def _shift_input(who, shifts, lead, K=None):
     if len(shape) < 2 or shape[-1] != 2 or (len(shape) > 2 and shape[:-2] != tuple(lead)) or (K is not None and shape[-2] != K):
         want = f"{tuple(lead) + ('K' if K is None else K, 2)} or {('K' if K is None else K, 2)}"
         raise ValueError(f"{who}: shifts must have shape {want}, (rows, columns) in HR pixels per frame (got {shape})")
-    _frame_count(who, shape[-2])
+    ops.tvmf_frame_count(who, shape[-2])
     return shape[-2]
 
 
@@ -647,7 +565,7 @@ def frame_apply(x, factors, shifts, kernel="mean", return_valid: bool = False):
     who = "frame_apply"
     f0, f1, k = _block_kernel(who, kernel, factors)
     as_numpy, H, W, lead = _block_input(who, x)
-    _hr_sides(who, H, W, f0, f1)
+    ops.tv_hr_sides(who, (H, W), (f0, f1))
     K = _shift_input(who, shifts, lead)
     flat = _block_batch(x, as_numpy)
     res = ops.frame_apply(flat.double(), _shift_batch(shifts, flat.shape[0], flat.device), (f0, f1), k, return_valid)
@@ -668,8 +586,8 @@ def frame_adjoint(r, factors, shifts, kernel="mean"):
     if len(lead) < 1:
         raise ValueError(f"{who} needs at least 3-D input [..., K, h, w]")
     lead, K = lead[:-1], lead[-1]
-    _frame_count(who, K)
-    _hr_sides(who, h * f0, w * f1, f0, f1)
+    ops.tvmf_frame_count(who, K)
+    ops.tv_hr_sides(who, (h * f0, w * f1), (f0, f1))
     _shift_input(who, shifts, lead, K)
     flat = _block_batch(r, as_numpy).reshape(-1, K, h, w)
     out = ops.frame_adjoint(flat.double(), _shift_batch(shifts, flat.shape[0], flat.device), (f0, f1), k)
@@ -692,13 +610,13 @@ def tv_superres_multi(frames, factors, shifts, kernel="mean", lam: float = TVMF_
     (max |x' - x| of the last iteration) and ``valid_fraction`` (the valid share of the data), each of the leading shape."""
     who = "tv_superres_multi"
     f0, f1, k = _block_kernel(who, kernel, factors)
-    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER, "in 0 ..")
+    lam, huber, n_iter = ops.tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER, "in 0 ..")
     as_numpy, h, w, lead = _block_input(who, frames, "frames")
     if len(lead) < 1:
         raise ValueError(f"{who} needs at least 3-D frames [..., K, h, w]")
     lead, K = lead[:-1], lead[-1]
-    _frame_count(who, K)
-    _hr_sides(who, h * f0, w * f1, f0, f1)
+    ops.tvmf_frame_count(who, K)
+    ops.tv_hr_sides(who, (h * f0, w * f1), (f0, f1))
     _shift_input(who, shifts, lead, K)
     extra = _weight_and_start(who, frames, as_numpy, lead, weight, (K, h, w), x0, (h * f0, w * f1), like="frames")
     y = _device_batch(frames, as_numpy, 3)
@@ -717,12 +635,7 @@ def estimate_shifts(frames, factors, upsample: int = 4, max_shift=None, referenc
     device tensor out with no host read on the way."""
     from . import registration
     who = "estimate_shifts"
-    try:
-        f0, f1 = (int(f) for f in factors)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: factors are (f0, f1), one per trailing axis (got {factors!r})") from None
-    if not (1 <= f0 <= ops.TVSR_MAX_FACTOR and 1 <= f1 <= ops.TVSR_MAX_FACTOR):
-        raise ValueError(f"{who}: factors are 1 .. {ops.TVSR_MAX_FACTOR} per axis (got {f0} x {f1})")
+    f0, f1 = ops.tv_factors(who, factors)
     if isinstance(upsample, bool) or int(upsample) != upsample or not 1 <= upsample <= 16:
         raise ValueError(f"{who}: upsample must be an integer in 1 .. 16 (got {upsample!r})")
     u = int(upsample)
@@ -730,7 +643,7 @@ def estimate_shifts(frames, factors, upsample: int = 4, max_shift=None, referenc
     if len(lead) < 1:
         raise ValueError(f"{who} needs at least 3-D frames [..., K, h, w]")
     lead, K = lead[:-1], lead[-1]
-    _frame_count(who, K)
+    ops.tvmf_frame_count(who, K)
     if isinstance(reference, bool) or int(reference) != reference or not 0 <= reference < K:
         raise ValueError(f"{who}: reference must be a frame index in 0 .. {K - 1} (got {reference!r})")
     if max_shift is not None and not 0.0 <= float(max_shift) < np.inf:
@@ -750,6 +663,17 @@ TV3D_DEFAULT_LAMBDA, TV3D_DEFAULT_HUBER, TV3D_DEFAULT_ITERS = 3e-3, 0.1, 300   #
 TV3D_DEFAULT_GRAD_WEIGHTS = (1.0, 1.0, 1.0)
 
 
+def _gaussian_taps(who, count, spacing, fwhm):
+    """``count`` samples of a Gaussian of full width at half maximum ``fwhm`` at the positions ``(t + 1/2 - count/2) / spacing``, centred
+    on the footprint and normalised to sum 1."""
+    sigma = float(fwhm) / (2.0 * np.sqrt(2.0 * np.log(2.0)))
+    pos = (2.0 * np.arange(count) + 1.0 - count) / (2.0 * spacing)       # antisymmetric to the bit
+    k = np.exp(-0.5 * (pos / sigma) ** 2)
+    if not k.sum() > 0.0:
+        raise ValueError(f"{who}: fwhm {fwhm!r} is too narrow: every sample of the Gaussian underflows")
+    return k / k.sum()
+
+
 def slice_profile(f, kind: str = "mean", fwhm=None):
     """The slice profile k0 [f] of a thick slice made of ``f`` thin ones, as a float64 ndarray that sums to 1: 'mean' (a box over the
     thick slice), 'decimate' (its first thin slice) or 'gaussian' -- a Gaussian of full width at half maximum ``fwhm``, in THICK
@@ -761,50 +685,30 @@ def slice_profile(f, kind: str = "mean", fwhm=None):
     f = int(f)
     if kind != "gaussian" and fwhm is not None:
         raise ValueError(f"{who}: fwhm belongs to kind='gaussian' (got kind={kind!r})")
-    if kind == "mean":
-        return np.full(f, 1.0 / f)
-    if kind == "decimate":
-        k = np.zeros(f)
-        k[0] = 1.0
-        return k
     if kind == "gaussian":
         if fwhm is None or not 0.0 < float(fwhm) < np.inf:
             raise ValueError(f"{who}: kind='gaussian' needs a finite fwhm > 0, in thick slices (got {fwhm!r})")
-        sigma = float(fwhm) / (2.0 * np.sqrt(2.0 * np.log(2.0)))
-        pos = (2.0 * np.arange(f) + 1.0 - f) / (2.0 * f)        # (a + 1/2) / f - 1/2, antisymmetric to the bit
-        k = np.exp(-0.5 * (pos / sigma) ** 2)
-        if not k.sum() > 0.0:
-            raise ValueError(f"{who}: fwhm {fwhm!r} is too narrow: every sample of the Gaussian underflows")
-        return k / k.sum()
-    raise ValueError(f"{who}: kind must be 'mean', 'decimate' or 'gaussian' (got {kind!r})")
+        return _gaussian_taps(who, f, f, fwhm)                   # at (a + 1/2) / f - 1/2
+    k = _named_kernel(kind, f)
+    if k is None:
+        raise ValueError(f"{who}: kind must be 'mean', 'decimate' or 'gaussian' (got {kind!r})")
+    return k
+
+
+def _kernel_factors(who, kernel, f, taps=False):
+    """'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2) -> three float lists: of ``f`` entries per axis, or (``taps``) the
+    arrays of any 1 .. 16 entries."""
+    if isinstance(kernel, str):
+        if kernel not in ("mean", "decimate"):
+            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2) (got {kernel!r})")
+        kernel = [_named_kernel(kernel, v) for v in f]
+    return ops.tv_kernel_factors(who, kernel, None if taps else f)
 
 
 def _block_kernel3d(who, kernel, factors):
     """'mean', 'decimate' or a triple of 1-D arrays (k0 [f0], k1 [f1], k2 [f2]) -> ((f0, f1, f2), three float lists), refusing by name."""
-    try:
-        f = tuple(int(v) for v in factors)
-        if len(f) != 3:
-            raise ValueError
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: factors are (f0, f1, f2), one per trailing axis (got {factors!r})") from None
-    if not all(1 <= v <= ops.TVSR_MAX_FACTOR for v in f):
-        raise ValueError(f"{who}: factors are 1 .. {ops.TVSR_MAX_FACTOR} per axis (got {f[0]} x {f[1]} x {f[2]})")
-    if isinstance(kernel, str):
-        if kernel not in ("mean", "decimate"):
-            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2) (got {kernel!r})")
-        ks = [slice_profile(v, kernel) for v in f]
-    else:
-        try:
-            ks = [np.asarray(k, dtype=np.float64) for k in kernel]
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2)") from None
-        if len(ks) != 3 or any(k.shape != (v,) for k, v in zip(ks, f)):
-            raise ValueError(f"{who}: the kernel factors must be 1-D arrays of {f[0]}, {f[1]} and {f[2]} entries "
-                             f"(got {[k.shape for k in ks]})")
-        for axis, k in enumerate(ks):
-            if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
-                raise ValueError(f"{who}: kernel factor k{axis} must be finite and sum to 1 (got sum {k.sum()!r})")
-    return f, [k.tolist() for k in ks]
+    f = ops.tv_factors(who, factors, 3)
+    return f, _kernel_factors(who, kernel, f)
 
 
 def _volume_input(who, volume, name="input"):
@@ -820,13 +724,6 @@ def _volume_batch(volume, as_numpy):
     return _device_batch(volume, as_numpy, 3)
 
 
-def _hr_sides3d(who, hr, f):
-    if any(s < 1 or s > ops.TVSR_MAX_SIDE for s in hr):
-        raise ValueError(f"{who}: HR volumes of 1 .. {ops.TVSR_MAX_SIDE} samples per axis (got {hr[0]} x {hr[1]} x {hr[2]})")
-    if any(s % v for s, v in zip(hr, f)):
-        raise ValueError(f"{who}: the HR volume {hr[0]} x {hr[1]} x {hr[2]} is no whole number of {f[0]} x {f[1]} x {f[2]} blocks")
-
-
 def block_apply3d(x, factors, kernel="mean"):
     """``A x`` on volumes: every ``f0 x f1 x f2`` block of the trailing three axes (slice, row, column) of ``x`` summed with the
     separable weights ``k[a][b][c] = (k1[b] k2[c]) k0[a]`` -- ``kernel`` 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2),
@@ -834,7 +731,7 @@ def block_apply3d(x, factors, kernel="mean"):
     a batch; ndarray in -> float64 ndarray out, device fp32 / fp64 tensor in -> the same out."""
     f, k = _block_kernel3d("block_apply3d", kernel, factors)
     as_numpy, hr, lead = _volume_input("block_apply3d", x)
-    _hr_sides3d("block_apply3d", hr, f)
+    ops.tv_hr_sides("block_apply3d", hr, f)
     flat = _volume_batch(x, as_numpy)
     out = ops.block_apply3d(flat.double(), f, k).to(flat.dtype).reshape(*lead, *(s // v for s, v in zip(hr, f)))
     return out.cpu().numpy() if as_numpy else out
@@ -846,7 +743,7 @@ def block_adjoint3d(r, factors, kernel="mean"):
     f, k = _block_kernel3d("block_adjoint3d", kernel, factors)
     as_numpy, lr, lead = _volume_input("block_adjoint3d", r)
     hr = tuple(s * v for s, v in zip(lr, f))
-    _hr_sides3d("block_adjoint3d", hr, f)
+    ops.tv_hr_sides("block_adjoint3d", hr, f)
     flat = _volume_batch(r, as_numpy)
     out = ops.block_adjoint3d(flat.double(), f, k).to(flat.dtype).reshape(*lead, *hr)
     return out.cpu().numpy() if as_numpy else out
@@ -866,11 +763,11 @@ def tv_superres3d(lr, factors, kernel="mean", lam: float = TV3D_DEFAULT_LAMBDA, 
     ``return_info``: also a dict with ``energy`` and ``change``, both of the leading shape."""
     who = "tv_superres3d"
     f, k = _block_kernel3d(who, kernel, factors)
-    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER)
-    g = _grad_weights(who, grad_weights)
+    lam, huber, n_iter = ops.tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER)
+    g = ops.tv_grad_weights(who, grad_weights)
     as_numpy, lo, lead = _volume_input(who, lr)
     hr = tuple(s * v for s, v in zip(lo, f))
-    _hr_sides3d(who, hr, f)
+    ops.tv_hr_sides(who, hr, f)
     extra = _weight_and_start(who, lr, as_numpy, lead, weight, lo, x0, hr)
     y = _volume_batch(lr, as_numpy)
     out, energy, change = ops.tvsr_solve3d(y, f, k, lam, huber, n_iter, g, extra["weight"], extra["x0"])
@@ -899,37 +796,10 @@ def stack_geometry(factors, kernel="mean", offsets=(0, 0, 0)):
     (``profile_taps``): longer than f the slices overlap, shorter they leave gaps.  Returns an immutable record (factors, kernels,
     offsets)."""
     who = "stack_geometry"
-    try:
-        f = tuple(int(v) for v in factors)
-        if len(f) != 3 or any(int(v) != v for v in factors):
-            raise ValueError
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: factors are (f0, f1, f2), one per trailing axis (got {factors!r})") from None
-    if not all(1 <= v <= ops.TVSR_MAX_FACTOR for v in f):
-        raise ValueError(f"{who}: factors are 1 .. {ops.TVSR_MAX_FACTOR} per axis (got {f[0]} x {f[1]} x {f[2]})")
-    if isinstance(kernel, str):
-        if kernel not in ("mean", "decimate"):
-            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2) (got {kernel!r})")
-        ks = [slice_profile(v, kernel) for v in f]
-    else:
-        try:
-            ks = [np.asarray(k, dtype=np.float64) for k in kernel]
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2)") from None
-        if len(ks) != 3 or any(k.ndim != 1 or not 1 <= k.size <= ops.TVMS_MAX_TAPS for k in ks):
-            raise ValueError(f"{who}: the kernel is a triple of 1-D arrays of 1 .. {ops.TVMS_MAX_TAPS} taps (got {[k.shape for k in ks]})")
-        for axis, k in enumerate(ks):
-            if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
-                raise ValueError(f"{who}: kernel factor k{axis} must be finite and sum to 1 (got sum {k.sum()!r})")
-    try:
-        o = tuple(int(v) for v in offsets)
-        if len(o) != 3 or any(int(v) != v for v in offsets):
-            raise ValueError
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: offsets are three whole numbers of HR voxels (got {offsets!r})") from None
-    if not all(abs(v) <= ops.TVMS_MAX_OFFSET for v in o):
-        raise ValueError(f"{who}: offsets are within +-{ops.TVMS_MAX_OFFSET} HR voxels (got {o})")
-    return StackGeometry((f, tuple(tuple(float(v) for v in k) for k in ks), o))
+    f = ops.tv_factors(who, factors, 3, whole=True)
+    ks = _kernel_factors(who, kernel, f, taps=True)
+    o = ops.tvms_offsets(who, offsets)
+    return StackGeometry((f, tuple(tuple(k) for k in ks), o))
 
 
 def profile_taps(length, spacing, kind: str = "gaussian", fwhm=None):
@@ -946,24 +816,18 @@ def profile_taps(length, spacing, kind: str = "gaussian", fwhm=None):
     if kind != "gaussian" and fwhm is not None:
         raise ValueError(f"{who}: fwhm belongs to kind='gaussian' (got kind={kind!r})")
     if kind == "mean":
-        return np.full(L, 1.0 / L)
+        return _named_kernel(kind, L)
     if kind == "gaussian":
         if fwhm is None or not 0.0 < float(fwhm) < np.inf:
             raise ValueError(f"{who}: kind='gaussian' needs a finite fwhm > 0, in units of the spacing (got {fwhm!r})")
-        sigma = float(fwhm) / (2.0 * np.sqrt(2.0 * np.log(2.0)))
-        pos = (2.0 * np.arange(L) + 1.0 - L) / (2.0 * f)          # (t + 1/2 - L/2) / f, antisymmetric to the bit
-        k = np.exp(-0.5 * (pos / sigma) ** 2)
-        if not k.sum() > 0.0:
-            raise ValueError(f"{who}: fwhm {fwhm!r} is too narrow: every sample of the Gaussian underflows")
-        return k / k.sum()
+        return _gaussian_taps(who, L, f, fwhm)
     raise ValueError(f"{who}: kind must be 'gaussian' or 'mean' (got {kind!r})")
 
 
 def _geometries(who, geometries):
     """One record or a sequence of them -> a list of ``StackGeometry``, 1 .. 8 of them."""
     geos = [geometries] if isinstance(geometries, StackGeometry) else list(geometries)
-    if not 1 <= len(geos) <= ops.TVMS_MAX_STACKS:
-        raise ValueError(f"{who}: stacks per volume are 1 .. {ops.TVMS_MAX_STACKS} (got {len(geos)})")
+    ops.tvms_stack_count(who, len(geos))
     for g in geos:
         if not isinstance(g, StackGeometry):
             raise TypeError(f"{who}: every geometry is a record of stack_geometry() (got {type(g).__name__})")
@@ -973,30 +837,6 @@ def _geometries(who, geometries):
 def default_lr_shape(geometry, hr_shape):
     """Per axis ``max(1, floor((N - L - o) / f) + 1)``: the LR indices from 0 to the last whose footprint lies inside the volume."""
     return tuple(max(1, (int(N) - len(k) - o) // f + 1) for N, f, k, o in zip(hr_shape, *geometry))
-
-
-def _lr_shape(who, shape):
-    try:
-        n = tuple(int(v) for v in shape)
-        if len(n) != 3:
-            raise ValueError
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: an LR shape is (n0, n1, n2) (got {shape!r})") from None
-    if not all(1 <= v <= ops.TVMS_MAX_EXTENT for v in n):
-        raise ValueError(f"{who}: LR extents are 1 .. {ops.TVMS_MAX_EXTENT} per axis (got {n})")
-    return n
-
-
-def _hr_shape(who, hr_shape):
-    try:
-        hr = tuple(int(v) for v in hr_shape)
-        if len(hr) != 3:
-            raise ValueError
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: hr_shape is (D, H, W) (got {hr_shape!r})") from None
-    if any(s < 1 or s > ops.TVSR_MAX_SIDE for s in hr):
-        raise ValueError(f"{who}: HR volumes of 1 .. {ops.TVSR_MAX_SIDE} samples per axis (got {hr[0]} x {hr[1]} x {hr[2]})")
-    return hr
 
 
 def stack_apply(x, geometry, lr_shape=None, return_valid: bool = False):
@@ -1010,9 +850,9 @@ def stack_apply(x, geometry, lr_shape=None, return_valid: bool = False):
     if not isinstance(geometry, StackGeometry):
         raise TypeError(f"{who}: geometry is a record of stack_geometry() (got {type(geometry).__name__})")
     as_numpy, hr, lead = _volume_input(who, x)
-    _hr_shape(who, hr)
+    ops.tv_hr_shape3d(who, hr)
     n = default_lr_shape(geometry, hr) if lr_shape is None else lr_shape
-    n = _lr_shape(who, n)
+    n = ops.tvms_lr_shape(who, n)
     flat = _volume_batch(x, as_numpy)
     res = ops.stack_apply(flat.double(), [(geometry.factors, geometry.kernels, geometry.offsets, n)], return_valid)
     out, valid = res if return_valid else (res, None)
@@ -1030,8 +870,8 @@ def stack_adjoint(r, geometry, hr_shape):
     if not isinstance(geometry, StackGeometry):
         raise TypeError(f"{who}: geometry is a record of stack_geometry() (got {type(geometry).__name__})")
     as_numpy, n, lead = _volume_input(who, r)
-    _lr_shape(who, n)
-    hr = _hr_shape(who, hr_shape)
+    ops.tvms_lr_shape(who, n)
+    hr = ops.tv_hr_shape3d(who, hr_shape)
     flat = _volume_batch(r, as_numpy)
     out = ops.stack_adjoint(flat.double().reshape(flat.shape[0], -1), [(geometry.factors, geometry.kernels, geometry.offsets, n)], hr)
     out = out.to(flat.dtype).reshape(*lead, *hr)
@@ -1061,9 +901,9 @@ def tv_superres_stacks(stacks, geometries, hr_shape, lam: float = TVMS_DEFAULT_L
     stacks = list(stacks)
     if len(stacks) != len(geos):
         raise ValueError(f"{who}: {len(stacks)} stacks for {len(geos)} geometries")
-    hr = _hr_shape(who, hr_shape)
-    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER)
-    g = _grad_weights(who, grad_weights)
+    hr = ops.tv_hr_shape3d(who, hr_shape)
+    lam, huber, n_iter = ops.tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER)
+    g = ops.tv_grad_weights(who, grad_weights)
     as_numpy, _, lead = _volume_input(who, stacks[0], "stacks")
     table = []
     for s, (y, geo) in enumerate(zip(stacks, geos)):
@@ -1071,7 +911,7 @@ def tv_superres_stacks(stacks, geometries, hr_shape, lam: float = TVMS_DEFAULT_L
             raise TypeError(f"{who}: the stacks must all be ndarrays or all device tensors")
         if tuple(y.shape[:-3]) != lead or y.dtype != stacks[0].dtype:
             raise ValueError(f"{who}: stack {s} must have the leading axes {lead} and the type of stack 0 (got {tuple(y.shape)}, {y.dtype})")
-        table.append((geo.factors, geo.kernels, geo.offsets, _lr_shape(who, y.shape[-3:])))
+        table.append((geo.factors, geo.kernels, geo.offsets, ops.tvms_lr_shape(who, y.shape[-3:])))
     if weight is not None:
         if isinstance(weight, (np.ndarray, torch.Tensor)) or not hasattr(weight, "__len__") or len(weight) != len(stacks):
             raise TypeError(f"{who}: weight is a list of arrays, one per stack, or None")
@@ -1153,12 +993,8 @@ def block_operator(n, f, kernel="mean"):
         raise ValueError(f"{who}: n is an integer 1 .. {ops.TVSR_MAX_SIDE} and a whole number of blocks of {f} (got {n!r})")
     n, f = int(n), int(f)
     if isinstance(kernel, str):
-        if kernel == "mean":
-            k = np.full(f, 1.0 / f)
-        elif kernel == "decimate":
-            k = np.zeros(f)
-            k[0] = 1.0
-        else:
+        k = _named_kernel(kernel, f)
+        if k is None:
             raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or {f} values (got {kernel!r})")
     else:
         k = np.asarray(kernel, dtype=np.float64)
@@ -1175,10 +1011,8 @@ def block_operator(n, f, kernel="mean"):
 def _operator_pair(who, operators):
     """``operators`` = (R0 [h, H], R1 [w, W]), float64 ndarrays (finite) or device float64 tensors -> (getter of the device pair, H, W,
     h, w), refusing by name.  Touches no device until the getter is called."""
-    try:
-        r0, r1 = operators
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: operators are a pair (R0 [h, H], R1 [w, W])") from None
+    r0, r1 = ops.tvop_operator_pair(who, operators)
+    sides = []
     for name, r in (("operators[0]", r0), ("operators[1]", r1)):
         if isinstance(r, np.ndarray):
             if r.dtype != np.float64:
@@ -1192,9 +1026,8 @@ def _operator_pair(who, operators):
                 raise ops.InrDeviceError(f"{who}: {name} is on {r.device}; pass an ndarray or a device tensor (there is no CPU fallback)")
         else:
             raise TypeError(f"{who}: {name} must be a float64 ndarray or a device float64 tensor (got {type(r).__name__})")
-        if r.ndim != 2 or not all(1 <= int(s) <= ops.TVSR_MAX_SIDE for s in r.shape):
-            raise ValueError(f"{who}: {name} must be 2-D with sides of 1 .. {ops.TVSR_MAX_SIDE} (got shape {tuple(r.shape)})")
-    (h, H), (w, W) = (int(s) for s in r0.shape), (int(s) for s in r1.shape)
+        sides.append(ops.tvop_operator_shape(who, name, r.shape))
+    (h, H), (w, W) = sides
 
     def device_pair():
         dev = ops.require_gpu()
@@ -1243,7 +1076,7 @@ def tv_superres_operator(lr, operators, lam: float = TVOP_DEFAULT_LAMBDA, huber:
     ``change`` (max |x' - x| of the last iteration), both of the leading shape."""
     who = "tv_superres_operator"
     pair, H, W, h, w = _operator_pair(who, operators)
-    lam, huber, n_iter = _tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER, "in 0 ..")
+    lam, huber, n_iter = ops.tv_scalars(who, lam, huber, n_iter, ops.TVSR3D_MAX_ITER, "in 0 ..")
     as_numpy, rows, cols, lead = _block_input(who, lr, "lr")
     if (rows, cols) != (h, w):
         raise ValueError(f"{who}: the operators make LR images of {h} x {w} (got lr of {rows} x {cols})")

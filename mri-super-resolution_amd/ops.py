@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -696,7 +697,15 @@ def siren_fit_footprint(desc: SirenDesc, params, grads, m, v, x_sub, target, wei
 
 
 # ---- model-based TV / Huber super-resolution (include/inrhip.h) --------------------------------------------------------
+#
+# Every rule about a HOST argument of this family is one validator below, named after its unit and taking ``who``, the caller's name: the
+# public wrappers (baselines.py, the drivers) call it before the device is asked for, the entry-point wrappers here call it again in
+# front of the kernel.  A validator reads no device tensor and returns plain Python values; the C arrays are the entry points' own step.
 TVSR_MAX_FACTOR, TVSR_MAX_SIDE = _lib.INR_TVSR_MAX_FACTOR, _lib.INR_TVSR_MAX_SIDE
+TVJ_MAX_CHANNELS, TVMF_MAX_FRAMES, TVSR3D_MAX_ITER = _lib.INR_TVJ_MAX_CHANNELS, _lib.INR_TVMF_MAX_FRAMES, _lib.INR_TVSR3D_MAX_ITER
+TVMS_MAX_STACKS, TVMS_MAX_TAPS = _lib.INR_TVMS_MAX_STACKS, _lib.INR_TVMS_MAX_TAPS
+TVMS_MAX_OFFSET, TVMS_MAX_EXTENT = 1 << 20, 2048
+_TVJ_COUPLING = {"none": 0, "joint": 1}
 
 
 def _chk_batch(t, name, rank, what, dtypes, shape=None, dtype_first=False) -> torch.Tensor:
@@ -722,22 +731,214 @@ def _chk_images(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
     return _chk_batch(t, name, 3, "[n, rows, columns]", dtypes, shape)
 
 
-def _tv_scalars(who, lam, alpha, n_iter, max_iter=None):
-    """(lam, alpha, n_iter) of a solve as the entry points take them; refuses what they would refuse."""
-    lam, alpha, n_iter = float(lam), float(alpha), int(n_iter)
-    top = float("inf") if max_iter is None else max_iter
-    if not (0.0 <= lam < float("inf")) or not (0.0 <= alpha < float("inf")) or not 0 <= n_iter <= top:
-        bound = "n_iter >= 0" if max_iter is None else f"n_iter 0 .. {max_iter}"
-        raise ValueError(f"{who}: lam and alpha must be finite and >= 0, {bound} (got {lam!r}, {alpha!r}, {n_iter})")
-    return lam, alpha, n_iter
+def tv_factors(who, factors, rank=2, whole=False):
+    """The ``rank`` block factors as ints, 1 .. TVSR_MAX_FACTOR each, refused by name; ``whole``: a fractional factor is refused, not
+    truncated."""
+    try:
+        f = tuple(int(v) for v in factors)
+        if len(f) != rank or (whole and any(int(v) != v for v in factors)):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: factors are {'(f0, f1)' if rank == 2 else '(f0, f1, f2)'}, one per trailing axis (got {factors!r})") from None
+    if not all(1 <= v <= TVSR_MAX_FACTOR for v in f):
+        raise ValueError(f"{who}: factors are 1 .. {TVSR_MAX_FACTOR} per axis (got {' x '.join(str(v) for v in f)})")
+    return f
 
 
-def _grad_weights(who, grad_weights):
-    """(g0, g1, g2) of a 3-D prior as host floats."""
-    g = [float(v) for v in grad_weights]
-    if len(g) != 3 or not all(0.0 <= v < float("inf") for v in g):
-        raise ValueError(f"{who}: grad_weights are three finite values >= 0 (got {tuple(grad_weights)!r})")
+def tv_block_kernel(who, kernel, factors):
+    """The HOST block kernel [f0][f1] as nested floats: finite, summing to 1 within 1e-9."""
+    f0, f1 = factors
+    k = np.asarray(kernel, dtype=np.float64)
+    if k.shape != (f0, f1):
+        raise ValueError(f"{who}: the kernel array must be [{f0}][{f1}] (got {k.shape})")
+    if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
+        raise ValueError(f"{who}: the kernel array must be finite and sum to 1 (got sum {k.sum()!r})")
+    return k.tolist()
+
+
+def tv_kernel_factors(who, kernel, factors=None):
+    """The HOST triple of 1-D kernel factors (k0, k1, k2) as float lists, each finite and summing to 1 within 1e-9: of ``factors``
+    entries per axis, or (None: the taps of a stack) of any 1 .. TVMS_MAX_TAPS."""
+    try:
+        ks = [np.asarray(k, dtype=np.float64) for k in kernel]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: kernel must be 'mean', 'decimate' or a triple of 1-D arrays (k0, k1, k2)") from None
+    if factors is None:
+        if len(ks) != 3 or any(k.ndim != 1 or not 1 <= k.size <= TVMS_MAX_TAPS for k in ks):
+            raise ValueError(f"{who}: the kernel is a triple of 1-D arrays of 1 .. {TVMS_MAX_TAPS} taps (got {[k.shape for k in ks]})")
+    elif len(ks) != 3 or any(k.shape != (v,) for k, v in zip(ks, factors)):
+        f = factors
+        raise ValueError(f"{who}: the kernel factors must be 1-D arrays of {f[0]}, {f[1]} and {f[2]} entries (got {[k.shape for k in ks]})")
+    for axis, k in enumerate(ks):
+        if not np.isfinite(k).all() or abs(k.sum() - 1.0) > 1e-9:
+            raise ValueError(f"{who}: kernel factor k{axis} must be finite and sum to 1 (got sum {k.sum()!r})")
+    return [k.tolist() for k in ks]
+
+
+def tv_hr_sides(who, hr, factors=None):
+    """The HR sides (two: an image, three: a volume), 1 .. TVSR_MAX_SIDE each and, where given, whole blocks of ``factors``."""
+    what, got = "image" if len(hr) == 2 else "volume", " x ".join(str(s) for s in hr)
+    if any(s < 1 or s > TVSR_MAX_SIDE for s in hr):
+        raise ValueError(f"{who}: HR {what}s of 1 .. {TVSR_MAX_SIDE} samples per axis (got {got})")
+    if factors is not None and any(s % f for s, f in zip(hr, factors)):
+        raise ValueError(f"{who}: the HR {what} {got} is no whole number of {' x '.join(str(f) for f in factors)} blocks")
+
+
+def tv_hr_shape3d(who, hr_shape):
+    """``hr_shape`` = (D, H, W) of a volume as ints, every side 1 .. TVSR_MAX_SIDE."""
+    try:
+        hr = tuple(int(v) for v in hr_shape)
+        if len(hr) != 3:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: hr_shape is (D, H, W) (got {hr_shape!r})") from None
+    tv_hr_sides(who, hr)
+    return hr
+
+
+def tv_scalars(who, lam, huber, n_iter, max_iter=None, span="0 .."):
+    """(lam, huber, n_iter) of a solver, refused by name; ``span``: how the caller words the range of ``n_iter`` up to ``max_iter``."""
+    lam, huber = float(lam), float(huber)
+    if not 0.0 <= lam < np.inf:
+        raise ValueError(f"{who}: lam must be finite and >= 0 (got {lam!r})")
+    if not 0.0 <= huber < np.inf:
+        raise ValueError(f"{who}: huber must be finite and >= 0 (got {huber!r})")
+    if int(n_iter) != n_iter or n_iter < 0 or (max_iter is not None and n_iter > max_iter):
+        bound = ">= 0" if max_iter is None else f"{span} {max_iter}"
+        raise ValueError(f"{who}: n_iter must be an integer {bound} (got {n_iter!r})")
+    return lam, huber, int(n_iter)
+
+
+def tv_grad_weights(who, grad_weights):
+    """(g0, g1, g2) of a 3-D prior as floats, refused by name."""
+    try:
+        g = tuple(float(v) for v in grad_weights)
+    except (TypeError, ValueError):
+        g = ()
+    if len(g) != 3 or not all(0.0 <= v < np.inf for v in g):
+        raise ValueError(f"{who}: grad_weights are (g0, g1, g2), finite and >= 0 (got {grad_weights!r})")
     return g
+
+
+def tv_coupling(who, coupling):
+    """'joint' or 'none', the prior's norm over the channels (or maps) of a group."""
+    if coupling not in tuple(_TVJ_COUPLING):
+        raise ValueError(f"{who}: coupling must be 'joint' or 'none' (got {coupling!r})")
+    return coupling
+
+
+def tvj_channels(who, channels):
+    if not 1 <= channels <= TVJ_MAX_CHANNELS:
+        raise ValueError(f"{who}: channels are 1 .. {TVJ_MAX_CHANNELS} per group (got {channels})")
+
+
+def tvj_channel_weights(who, channel_weights, channels):
+    """The HOST channel weights as ``channels`` floats within [0, 1], or None (all 1)."""
+    if channel_weights is None:
+        return None
+    mu = np.asarray(channel_weights, np.float64).reshape(-1)
+    if mu.shape != (channels,) or not (np.isfinite(mu).all() and (mu >= 0).all() and (mu <= 1).all()):
+        raise ValueError(f"{who}: channel_weights are {channels} finite values within [0, 1] (got {mu.tolist()}); larger weights are a "
+                         f"rescaled lam and huber")
+    return mu.tolist()
+
+
+def tvadc_model(who, b, channels, map_weights, coupling, s_max, adc_max, adc0):
+    """The S0 / ADC model's host values, refused by name: -> (b, (mu_s, mu_d), s_max, adc_max, adc0) as floats."""
+    try:
+        vals = np.asarray(b, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: b must be a sequence of b-values (got {b!r})") from None
+    if not 2 <= channels <= TVJ_MAX_CHANNELS:
+        raise ValueError(f"{who}: b-values are 2 .. {TVJ_MAX_CHANNELS} per group (got {channels})")
+    if vals.shape != (channels,):
+        raise ValueError(f"{who}: b has {vals.size} b-values, expected one per channel ({channels})")
+    if not (np.isfinite(vals).all() and (vals >= 0).all()):
+        raise ValueError(f"{who}: b-values must be finite and >= 0 (got {vals.tolist()})")
+    if vals.max() == vals.min():
+        raise ValueError(f"{who}: the b-values are all equal ({vals[0]!r}): they determine no ADC")
+    tv_coupling(who, coupling)
+    try:
+        mu = np.asarray(map_weights, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        mu = np.zeros(0)
+    if mu.shape != (2,) or not (np.isfinite(mu).all() and (mu >= 0).all() and (mu <= 1).all()):
+        raise ValueError(f"{who}: map_weights are (mu_s, mu_d), two finite values within [0, 1] (got {map_weights!r}); larger weights are "
+                         f"a rescaled lam and huber")
+    s_max, adc_max, adc0 = float(s_max), float(adc_max), float(adc0)
+    if not 0.0 < s_max < np.inf:
+        raise ValueError(f"{who}: s_max must be finite and > 0 (got {s_max!r})")
+    if not 0.0 < adc_max < np.inf or not adc_max * vals.max() < np.inf:
+        raise ValueError(f"{who}: adc_max must be finite and > 0 (got {adc_max!r})")
+    if not 0.0 <= adc0 <= adc_max:
+        raise ValueError(f"{who}: adc0 must be within [0, adc_max] (got {adc0!r}, adc_max {adc_max!r})")
+    return vals.tolist(), mu.tolist(), s_max, adc_max, adc0
+
+
+def adc_bvalues(who, b):
+    """The HOST b-values of ``adc_signal`` as floats: 1 .. TVJ_MAX_CHANNELS of them, finite."""
+    vals = np.asarray(b, np.float64).reshape(-1)
+    if not 1 <= vals.size <= TVJ_MAX_CHANNELS or not np.isfinite(vals).all():
+        raise ValueError(f"{who}: b is 1 .. {TVJ_MAX_CHANNELS} finite b-values (got {vals.tolist()})")
+    return vals.tolist()
+
+
+def tgv_ratio(who, ratio):
+    ratio = float(ratio)
+    if not 0.0 < ratio < np.inf:
+        raise ValueError(f"{who}: ratio must be finite and > 0 (got {ratio!r})")
+    return ratio
+
+
+def tvmf_frame_count(who, K):
+    if not 1 <= K <= TVMF_MAX_FRAMES:
+        raise ValueError(f"{who}: frames per image are 1 .. {TVMF_MAX_FRAMES} (got {K})")
+
+
+def tvms_stack_count(who, count):
+    if not 1 <= count <= TVMS_MAX_STACKS:
+        raise ValueError(f"{who}: stacks per volume are 1 .. {TVMS_MAX_STACKS} (got {count})")
+
+
+def tvms_offsets(who, offsets):
+    """The offsets of a stack, three whole numbers of HR voxels within +-TVMS_MAX_OFFSET, as ints."""
+    try:
+        o = tuple(int(v) for v in offsets)
+        if len(o) != 3 or any(int(v) != v for v in offsets):
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: offsets are three whole numbers of HR voxels (got {offsets!r})") from None
+    if not all(abs(v) <= TVMS_MAX_OFFSET for v in o):
+        raise ValueError(f"{who}: offsets are within +-{TVMS_MAX_OFFSET} HR voxels (got {o})")
+    return o
+
+
+def tvms_lr_shape(who, shape):
+    """The LR shape (n0, n1, n2) of a stack as ints, 1 .. TVMS_MAX_EXTENT each."""
+    try:
+        n = tuple(int(v) for v in shape)
+        if len(n) != 3:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: an LR shape is (n0, n1, n2) (got {shape!r})") from None
+    if not all(1 <= v <= TVMS_MAX_EXTENT for v in n):
+        raise ValueError(f"{who}: LR extents are 1 .. {TVMS_MAX_EXTENT} per axis (got {n})")
+    return n
+
+
+def tvop_operator_pair(who, operators):
+    try:
+        r0, r1 = operators
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: operators are a pair (R0 [h, H], R1 [w, W])") from None
+    return r0, r1
+
+
+def tvop_operator_shape(who, name, shape):
+    """The shape [rows, columns] of one operator of the pair as ints, every side 1 .. TVSR_MAX_SIDE."""
+    if len(shape) != 2 or not all(1 <= int(s) <= TVSR_MAX_SIDE for s in shape):
+        raise ValueError(f"{who}: {name} must be 2-D with sides of 1 .. {TVSR_MAX_SIDE} (got shape {tuple(shape)})")
+    return int(shape[0]), int(shape[1])
 
 
 def _f64_workspace(workspace, need, device) -> torch.Tensor:
@@ -749,36 +950,50 @@ def _f64_workspace(workspace, need, device) -> torch.Tensor:
     return workspace
 
 
-def _tv_results(y, entry, count=2):
-    """``count`` per-image float64 results (energy, change, ...) beside ``y`` [n, ...], and ``entry`` or its ``_f32`` twin by the dtype."""
-    results = [torch.zeros(y.shape[0], dtype=torch.float64, device=y.device) for _ in range(count)]
-    return results, entry if y.dtype == torch.float64 else entry + "_f32"
+def _tv_solve(entry, y, chk_y, chk_x0, hr, weight, x0, workspace, need, rest, results=2, after_out=(), after_y=()):
+    """The tail the solves share, behind their checks of ``y`` and of the host values: ``weight`` like ``y`` (``chk_y``) and ``x0`` like
+    the result [n, *hr] (``chk_x0``), both of the dtype of ``y``; the result and ``results`` per-image float64 values; ``entry`` or its
+    ``_f32`` twin by the dtype; nothing launched for n = 0; the float64 workspace of ``need()`` doubles, the caller's or a fresh one;
+    the call ``entry(out, *after_out, *results, y, *after_y, weight, x0, *rest, workspace, its doubles, stream)``.
+    -> (out, *results)."""
+    n = y.shape[0]
+    if weight is not None:
+        chk_y(weight, "weight", (y.dtype,), y.shape)
+    if x0 is not None:
+        chk_x0(x0, "x0", (y.dtype,), (n, *hr))
+    out = torch.empty((n, *hr), dtype=y.dtype, device=y.device)
+    values = [torch.zeros(n, dtype=torch.float64, device=y.device) for _ in range(results)]
+    if n:
+        entry = entry if y.dtype == torch.float64 else entry + "_f32"
+        workspace = _f64_workspace(workspace, need(), y.device)
+        check(getattr(lib(), entry)(out.data_ptr(), *after_out, *(v.data_ptr() for v in values), y.data_ptr(), *after_y, _ptr(weight),
+                                    _ptr(x0), *rest, workspace.data_ptr(), workspace.numel(), _stream()), entry)
+    return (out, *values)
 
 
-def _block_kernel(kernel, factors):
-    """The HOST block kernel [f0][f1] as the C array the entry points take; refuses what they would refuse."""
-    f0, f1 = (int(f) for f in factors)
-    if not (1 <= f0 <= TVSR_MAX_FACTOR and 1 <= f1 <= TVSR_MAX_FACTOR):
-        raise ValueError(f"block factors are 1 .. {TVSR_MAX_FACTOR} per axis (got {f0} x {f1})")
-    flat = [float(v) for row in kernel for v in row]
-    if len(kernel) != f0 or len(flat) != f0 * f1:
-        raise ValueError(f"the block kernel must be [{f0}][{f1}]")
-    if not all(v == v and abs(v) != float("inf") for v in flat) or abs(sum(flat) - 1.0) > 1e-9:
-        raise ValueError(f"the block kernel must be finite and sum to 1 (sum {sum(flat)!r})")
-    return f0, f1, (C.c_double * (f0 * f1))(*flat)
+def _solve_scalars(who, lam, alpha, n_iter, max_iter=None):
+    """``tv_scalars`` of what ``float`` and ``int`` make of an entry point's scalars: a fractional ``n_iter`` is truncated here, as ever."""
+    return tv_scalars(who, float(lam), float(alpha), int(n_iter), max_iter)
 
 
-def _hr_shape(name, rows, cols, f0, f1):
-    if not (1 <= rows <= TVSR_MAX_SIDE and 1 <= cols <= TVSR_MAX_SIDE) or rows % f0 or cols % f1:
-        raise ValueError(f"{name}: HR images are 1 .. {TVSR_MAX_SIDE} samples per axis and whole {f0} x {f1} blocks (got {rows} x {cols})")
+def _doubles(values):
+    """The C array of host floats an entry point takes."""
+    values = list(values)
+    return (C.c_double * len(values))(*values)
+
+
+def _block_kernel(who, kernel, factors):
+    """(f0, f1, the C array [f0][f1]) of a 2-D block operator."""
+    f0, f1 = tv_factors(who, factors)
+    return f0, f1, _doubles(v for row in tv_block_kernel(who, kernel, (f0, f1)) for v in row)
 
 
 def block_apply(x: torch.Tensor, factors, kernel) -> torch.Tensor:
     """``inr_block_apply2d``: ``x`` [n, H, W] float64 -> ``A x`` [n, H/f0, W/f1]; ``kernel`` [f0][f1] host values that sum to 1."""
     _chk_images(x, "x")
-    f0, f1, k = _block_kernel(kernel, factors)
+    f0, f1, k = _block_kernel("block_apply", kernel, factors)
     n, H, W = x.shape
-    _hr_shape("block_apply", H, W, f0, f1)
+    tv_hr_sides("block_apply", (H, W), (f0, f1))
     out = torch.empty((n, H // f0, W // f1), dtype=torch.float64, device=x.device)
     check(lib().inr_block_apply2d(out.data_ptr(), x.data_ptr(), n, H, W, f0, f1, k, _stream()), "inr_block_apply2d")
     return out
@@ -787,9 +1002,9 @@ def block_apply(x: torch.Tensor, factors, kernel) -> torch.Tensor:
 def block_adjoint(r: torch.Tensor, factors, kernel) -> torch.Tensor:
     """``inr_block_adjoint2d``: ``r`` [n, h, w] float64 -> ``A^T r`` [n, f0 h, f1 w]."""
     _chk_images(r, "r")
-    f0, f1, k = _block_kernel(kernel, factors)
+    f0, f1, k = _block_kernel("block_adjoint", kernel, factors)
     n, h, w = r.shape
-    _hr_shape("block_adjoint", h * f0, w * f1, f0, f1)
+    tv_hr_sides("block_adjoint", (h * f0, w * f1), (f0, f1))
     out = torch.empty((n, h * f0, w * f1), dtype=torch.float64, device=r.device)
     check(lib().inr_block_adjoint2d(out.data_ptr(), r.data_ptr(), n, h * f0, w * f1, f0, f1, k, _stream()), "inr_block_adjoint2d")
     return out
@@ -803,31 +1018,18 @@ def tvsr_workspace_doubles(n: int, H: int, W: int) -> int:
 def tvsr_solve(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_iter: int, weight=None, x0=None, workspace=None):
     """``inr_tvsr_solve2d`` / ``_f32`` by the dtype of ``y`` [n, h, w]: returns (x [n, f0 h, f1 w] of that dtype, energy [n] float64,
     change [n] float64).  ``weight`` [n, h, w] and ``x0`` [n, f0 h, f1 w] share the dtype; ``workspace``: a float64 tensor."""
+    who = "tvsr_solve"
     _chk_images(y, "y", (torch.float32, torch.float64))
-    f0, f1, k = _block_kernel(kernel, factors)
+    f0, f1, k = _block_kernel(who, kernel, factors)
     n, h, w = y.shape
     H, W = h * f0, w * f1
-    _hr_shape("tvsr_solve", H, W, f0, f1)
-    if weight is not None:
-        _chk_images(weight, "weight", (y.dtype,), y.shape)
-    if x0 is not None:
-        _chk_images(x0, "x0", (y.dtype,), (n, H, W))
-    lam, alpha, n_iter = _tv_scalars("tvsr_solve", lam, alpha, n_iter)
-    out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
-    (energy, change), entry = _tv_results(y, "inr_tvsr_solve2d")
-    if n == 0:
-        return out, energy, change
-    workspace = _f64_workspace(workspace, tvsr_workspace_doubles(n, H, W), y.device)
-    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, H, W, f0,
-                                f1, k, lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()), entry)
-    return out, energy, change
+    tv_hr_sides(who, (H, W), (f0, f1))
+    lam, alpha, n_iter = _solve_scalars(who, lam, alpha, n_iter)
+    return _tv_solve("inr_tvsr_solve2d", y, _chk_images, _chk_images, (H, W), weight, x0, workspace,
+                     lambda: tvsr_workspace_doubles(n, H, W), (n, H, W, f0, f1, k, lam, alpha, n_iter))
 
 
 # ---- the same with one prior over the channels of a group (include/inrhip.h, DESIGN.md 4q) -------------------------------------------
-TVJ_MAX_CHANNELS = _lib.INR_TVJ_MAX_CHANNELS
-_TVJ_COUPLING = {"none": 0, "joint": 1}
-
-
 def _chk_groups(t, name, dtypes, shape=None) -> torch.Tensor:
     return _chk_batch(t, name, 4, "[n, channels, rows, columns]", dtypes, shape)
 
@@ -842,77 +1044,22 @@ def tvj_solve(y: torch.Tensor, factors, kernel, channel_weights, lam: float, alp
     """``inr_tvj_solve2d`` / ``_f32`` by the dtype of ``y`` [n, C, h, w]: returns (x [n, C, f0 h, f1 w] of that dtype, energy [n]
     float64, change [n] float64).  ``channel_weights``: C host values in [0, 1] or None (all 1); ``coupling``: 'joint' or 'none';
     ``weight`` [n, C, h, w] and ``x0`` [n, C, f0 h, f1 w] share the dtype; ``workspace``: a float64 tensor."""
+    who = "tvj_solve"
     _chk_groups(y, "y", (torch.float32, torch.float64))
-    f0, f1, k = _block_kernel(kernel, factors)
+    f0, f1, k = _block_kernel(who, kernel, factors)
     n, ch, h, w = y.shape
     H, W = h * f0, w * f1
-    if not 1 <= ch <= TVJ_MAX_CHANNELS:
-        raise ValueError(f"tvj_solve: channels are 1 .. {TVJ_MAX_CHANNELS} per group (got {ch})")
-    _hr_shape("tvj_solve", H, W, f0, f1)
-    if coupling not in _TVJ_COUPLING:
-        raise ValueError(f"tvj_solve: coupling must be 'joint' or 'none' (got {coupling!r})")
-    mu = None
-    if channel_weights is not None:
-        vals = [float(v) for v in channel_weights]
-        if len(vals) != ch or not all(0.0 <= v <= 1.0 for v in vals):
-            raise ValueError(f"tvj_solve: channel_weights are {ch} finite values within [0, 1] (got {vals!r})")
-        mu = (C.c_double * ch)(*vals)
-    if weight is not None:
-        _chk_groups(weight, "weight", (y.dtype,), y.shape)
-    if x0 is not None:
-        _chk_groups(x0, "x0", (y.dtype,), (n, ch, H, W))
-    lam, alpha, n_iter = _tv_scalars("tvj_solve", lam, alpha, n_iter)
-    out = torch.empty((n, ch, H, W), dtype=y.dtype, device=y.device)
-    (energy, change), entry = _tv_results(y, "inr_tvj_solve2d")
-    if n == 0:
-        return out, energy, change
-    workspace = _f64_workspace(workspace, tvj_workspace_doubles(n, ch, H, W), y.device)
-    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, ch, H, W,
-                                f0, f1, k, mu, lam, alpha, _TVJ_COUPLING[coupling], n_iter, workspace.data_ptr(), workspace.numel(),
-                                _stream()), entry)
-    return out, energy, change
+    tvj_channels(who, ch)
+    tv_hr_sides(who, (H, W), (f0, f1))
+    tv_coupling(who, coupling)
+    mu = tvj_channel_weights(who, channel_weights, ch)
+    lam, alpha, n_iter = _solve_scalars(who, lam, alpha, n_iter)
+    return _tv_solve("inr_tvj_solve2d", y, _chk_groups, _chk_groups, (ch, H, W), weight, x0, workspace,
+                     lambda: tvj_workspace_doubles(n, ch, H, W),
+                     (n, ch, H, W, f0, f1, k, None if mu is None else _doubles(mu), lam, alpha, _TVJ_COUPLING[coupling], n_iter))
 
 
 # ---- the S0 / ADC maps of a group as the unknowns (include/inrhip.h, DESIGN.md 4t) ------------------------------------------------------
-def _bvalues(who, b, count=None, least=2):
-    """The HOST b-values as floats, refused by name: ``count`` of them (None: ``least`` .. TVJ_MAX_CHANNELS), finite."""
-    try:
-        vals = [float(v) for v in b]
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: b must be a sequence of b-values (got {b!r})") from None
-    if count is not None and len(vals) != count:
-        raise ValueError(f"{who}: b has {len(vals)} b-values, expected one per channel ({count})")
-    if not least <= len(vals) <= TVJ_MAX_CHANNELS:
-        raise ValueError(f"{who}: b-values are {least} .. {TVJ_MAX_CHANNELS} per group (got {len(vals)})")
-    if not all(abs(v) < float("inf") for v in vals):
-        raise ValueError(f"{who}: b-values must be finite (got {vals!r})")
-    return vals
-
-
-def _tvadc_model(who, b, channels, map_weights, coupling, s_max, adc_max, adc0):
-    """(b, map weights, s_max, adc_max, adc0) of a solve as host floats; refuses what ``inr_tvadc_solve2d`` would refuse."""
-    if not 2 <= channels <= TVJ_MAX_CHANNELS:
-        raise ValueError(f"{who}: b-values are 2 .. {TVJ_MAX_CHANNELS} per group (got {channels})")
-    vals = _bvalues(who, b, channels)
-    if not all(v >= 0.0 for v in vals):
-        raise ValueError(f"{who}: b-values must be finite and >= 0 (got {vals!r})")
-    if max(vals) == min(vals):
-        raise ValueError(f"{who}: the b-values are all equal ({vals[0]!r}): they determine no ADC")
-    if coupling not in _TVJ_COUPLING:
-        raise ValueError(f"{who}: coupling must be 'joint' or 'none' (got {coupling!r})")
-    mu = [float(v) for v in map_weights]
-    if len(mu) != 2 or not all(0.0 <= v <= 1.0 for v in mu):
-        raise ValueError(f"{who}: map_weights are (mu_s, mu_d), two finite values within [0, 1] (got {mu!r})")
-    s_max, adc_max, adc0 = float(s_max), float(adc_max), float(adc0)
-    if not 0.0 < s_max < float("inf"):
-        raise ValueError(f"{who}: s_max must be finite and > 0 (got {s_max!r})")
-    if not 0.0 < adc_max < float("inf") or not adc_max * max(vals) < float("inf"):
-        raise ValueError(f"{who}: adc_max must be finite and > 0 (got {adc_max!r})")
-    if not 0.0 <= adc0 <= adc_max:
-        raise ValueError(f"{who}: adc0 must be within [0, adc_max] (got {adc0!r}, adc_max {adc_max!r})")
-    return vals, mu, s_max, adc_max, adc0
-
-
 def tvadc_workspace_doubles(n: int, channels: int, H: int, W: int, factors) -> int:
     """``inr_tvadc_workspace_doubles``; 0 for sizes ``inr_tvadc_solve2d`` refuses."""
     return int(lib().inr_tvadc_workspace_doubles(int(n), int(channels), int(H), int(W), int(factors[0]), int(factors[1])))
@@ -926,24 +1073,16 @@ def tvadc_solve(y: torch.Tensor, b, factors, kernel, map_weights, lam: float, al
     maps s0, adc) share the dtype; ``workspace``: a float64 tensor."""
     who = "tvadc_solve"
     _chk_groups(y, "y", (torch.float32, torch.float64))
-    f0, f1, k = _block_kernel(kernel, factors)
+    f0, f1, k = _block_kernel(who, kernel, factors)
     n, ch, h, w = y.shape
     H, W = h * f0, w * f1
-    vals, mu, s_max, adc_max, adc0 = _tvadc_model(who, b, ch, map_weights, coupling, s_max, adc_max, adc0)
-    _hr_shape(who, H, W, f0, f1)
-    if weight is not None:
-        _chk_groups(weight, "weight", (y.dtype,), y.shape)
-    if x0 is not None:
-        _chk_groups(x0, "x0", (y.dtype,), (n, 2, H, W))
-    lam, alpha, n_iter = _tv_scalars(who, lam, alpha, n_iter)
-    out = torch.empty((n, 2, H, W), dtype=y.dtype, device=y.device)
-    (energy, change), entry = _tv_results(y, "inr_tvadc_solve2d")
-    if n == 0:
-        return out[:, 0], out[:, 1], energy, change
-    workspace = _f64_workspace(workspace, tvadc_workspace_doubles(n, ch, H, W, (f0, f1)), y.device)
-    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, ch, H, W,
-                                f0, f1, k, (C.c_double * ch)(*vals), (C.c_double * 2)(*mu), lam, alpha, _TVJ_COUPLING[coupling], n_iter,
-                                s_max, adc_max, adc0, workspace.data_ptr(), workspace.numel(), _stream()), entry)
+    vals, mu, s_max, adc_max, adc0 = tvadc_model(who, b, ch, map_weights, coupling, s_max, adc_max, adc0)
+    tv_hr_sides(who, (H, W), (f0, f1))
+    lam, alpha, n_iter = _solve_scalars(who, lam, alpha, n_iter)
+    out, energy, change = _tv_solve("inr_tvadc_solve2d", y, _chk_groups, _chk_groups, (2, H, W), weight, x0, workspace,
+                                    lambda: tvadc_workspace_doubles(n, ch, H, W, (f0, f1)),
+                                    (n, ch, H, W, f0, f1, k, _doubles(vals), _doubles(mu), lam, alpha, _TVJ_COUPLING[coupling], n_iter,
+                                     s_max, adc_max, adc0))
     return out[:, 0], out[:, 1], energy, change
 
 
@@ -952,14 +1091,13 @@ def adc_signal(s0: torch.Tensor, adc: torch.Tensor, b) -> torch.Tensor:
     of one shape and dtype; ``b``: C host b-values, 1 .. 16."""
     _chk_images(s0, "s0", (torch.float32, torch.float64))
     _chk_images(adc, "adc", (s0.dtype,), s0.shape)
-    vals = _bvalues("adc_signal", b, least=1)
+    vals = adc_bvalues("adc_signal", b)
     n, H, W = s0.shape
     out = torch.empty((n, len(vals), H, W), dtype=s0.dtype, device=s0.device)
     if out.numel() == 0:
         return out
     entry = "inr_adc_signal" if s0.dtype == torch.float64 else "inr_adc_signal_f32"
-    check(getattr(lib(), entry)(out.data_ptr(), s0.data_ptr(), adc.data_ptr(), (C.c_double * len(vals))(*vals), n, len(vals), H * W,
-                                _stream()), entry)
+    check(getattr(lib(), entry)(out.data_ptr(), s0.data_ptr(), adc.data_ptr(), _doubles(vals), n, len(vals), H * W, _stream()), entry)
     return out
 
 
@@ -1099,68 +1237,39 @@ def tgv_solve(y: torch.Tensor, factors, kernel, lam: float, ratio: float, alpha:
     that dtype or None where ``want_v`` is false, energy [n] float64, change [n] float64).  ``lam`` weighs the first-order term,
     ``ratio * lam`` the second-order one; ``weight`` [n, h, w] and ``x0`` [n, f0 h, f1 w] share the dtype; ``workspace``: a float64
     tensor."""
+    who = "tgv_solve"
     _chk_images(y, "y", (torch.float32, torch.float64))
-    f0, f1, k = _block_kernel(kernel, factors)
+    f0, f1, k = _block_kernel(who, kernel, factors)
     n, h, w = y.shape
     H, W = h * f0, w * f1
-    _hr_shape("tgv_solve", H, W, f0, f1)
-    if weight is not None:
-        _chk_images(weight, "weight", (y.dtype,), y.shape)
-    if x0 is not None:
-        _chk_images(x0, "x0", (y.dtype,), (n, H, W))
+    tv_hr_sides(who, (H, W), (f0, f1))
     ratio = float(ratio)
-    lam, alpha, n_iter = _tv_scalars("tgv_solve", lam, alpha, n_iter)
-    if not (0.0 < ratio < float("inf")):
-        raise ValueError(f"tgv_solve: ratio must be finite and > 0 (got {ratio!r})")
-    out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
+    lam, alpha, n_iter = _solve_scalars(who, lam, alpha, n_iter)
+    tgv_ratio(who, ratio)
     v = torch.empty((n, 2, H, W), dtype=y.dtype, device=y.device) if want_v else None
-    (energy, change), entry = _tv_results(y, "inr_tgv_solve2d")
-    if n == 0:
-        return out, v, energy, change
-    workspace = _f64_workspace(workspace, tgv_workspace_doubles(n, H, W), y.device)
-    check(getattr(lib(), entry)(out.data_ptr(), _ptr(v), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, H,
-                                W, f0, f1, k, lam, ratio, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()), entry)
+    out, energy, change = _tv_solve("inr_tgv_solve2d", y, _chk_images, _chk_images, (H, W), weight, x0, workspace,
+                                    lambda: tgv_workspace_doubles(n, H, W), (n, H, W, f0, f1, k, lam, ratio, alpha, n_iter),
+                                    after_out=(_ptr(v),))
     return out, v, energy, change
 
 
 # ---- the same on volumes: slice profile, 3-D prior, many workgroups per volume (include/inrhip.h, DESIGN.md 4m) ----------------------
-TVSR3D_MAX_ITER = _lib.INR_TVSR3D_MAX_ITER
-
-
 def _chk_volumes(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
     return _chk_batch(t, name, 4, "[n, slices, rows, columns]", dtypes, shape)
 
 
-def _block_factors3d(kernel, factors):
-    """The HOST factors (k0 [f0], k1 [f1], k2 [f2]) as the C arrays the entry points take; refuses what they would refuse."""
-    f = tuple(int(v) for v in factors)
-    if len(f) != 3 or not all(1 <= v <= TVSR_MAX_FACTOR for v in f):
-        raise ValueError(f"block factors are three of 1 .. {TVSR_MAX_FACTOR} (got {tuple(factors)})")
-    if len(kernel) != 3:
-        raise ValueError("the block kernel is a triple of 1-D factors (k0 [f0], k1 [f1], k2 [f2])")
-    arrays = []
-    for axis, (k, fa) in enumerate(zip(kernel, f)):
-        flat = [float(v) for v in k]
-        if len(flat) != fa:
-            raise ValueError(f"kernel factor k{axis} must have {fa} entries (got {len(flat)})")
-        if not all(v == v and abs(v) != float("inf") for v in flat) or abs(sum(flat) - 1.0) > 1e-9:
-            raise ValueError(f"kernel factor k{axis} must be finite and sum to 1 (sum {sum(flat)!r})")
-        arrays.append((C.c_double * fa)(*flat))
-    return f, arrays
-
-
-def _hr_shape3d(name, D, H, W, f):
-    if not all(1 <= s <= TVSR_MAX_SIDE for s in (D, H, W)) or D % f[0] or H % f[1] or W % f[2]:
-        raise ValueError(f"{name}: HR volumes are 1 .. {TVSR_MAX_SIDE} samples per axis and whole {f[0]} x {f[1]} x {f[2]} blocks "
-                         f"(got {D} x {H} x {W})")
+def _block_kernel3d(who, kernel, factors):
+    """((f0, f1, f2), the C arrays k0 [f0], k1 [f1], k2 [f2]) of a 3-D block operator."""
+    f = tv_factors(who, factors, 3)
+    return f, [_doubles(k) for k in tv_kernel_factors(who, kernel, f)]
 
 
 def block_apply3d(x: torch.Tensor, factors, kernel) -> torch.Tensor:
     """``inr_tvsr3d_block_apply``: ``x`` [n, D, H, W] float64 -> ``A x`` [n, D/f0, H/f1, W/f2]; ``kernel``: (k0, k1, k2) host values."""
     _chk_volumes(x, "x")
-    f, k = _block_factors3d(kernel, factors)
+    f, k = _block_kernel3d("block_apply3d", kernel, factors)
     n, D, H, W = x.shape
-    _hr_shape3d("block_apply3d", D, H, W, f)
+    tv_hr_sides("block_apply3d", (D, H, W), f)
     out = torch.empty((n, D // f[0], H // f[1], W // f[2]), dtype=torch.float64, device=x.device)
     check(lib().inr_tvsr3d_block_apply(out.data_ptr(), x.data_ptr(), n, D, H, W, *f, *k, _stream()), "inr_tvsr3d_block_apply")
     return out
@@ -1169,10 +1278,10 @@ def block_apply3d(x: torch.Tensor, factors, kernel) -> torch.Tensor:
 def block_adjoint3d(r: torch.Tensor, factors, kernel) -> torch.Tensor:
     """``inr_tvsr3d_block_adjoint``: ``r`` [n, d, h, w] float64 -> ``A^T r`` [n, f0 d, f1 h, f2 w]."""
     _chk_volumes(r, "r")
-    f, k = _block_factors3d(kernel, factors)
+    f, k = _block_kernel3d("block_adjoint3d", kernel, factors)
     n, d, h, w = r.shape
     D, H, W = d * f[0], h * f[1], w * f[2]
-    _hr_shape3d("block_adjoint3d", D, H, W, f)
+    tv_hr_sides("block_adjoint3d", (D, H, W), f)
     out = torch.empty((n, D, H, W), dtype=torch.float64, device=r.device)
     check(lib().inr_tvsr3d_block_adjoint(out.data_ptr(), r.data_ptr(), n, D, H, W, *f, *k, _stream()), "inr_tvsr3d_block_adjoint")
     return out
@@ -1189,38 +1298,21 @@ def tvsr_solve3d(y: torch.Tensor, factors, kernel, lam: float, alpha: float, n_i
     """``inr_tvsr3d_solve`` / ``_f32`` by the dtype of ``y`` [n, d, h, w]: returns (x [n, f0 d, f1 h, f2 w] of that dtype, energy [n]
     float64, change [n] float64).  ``kernel``: (k0, k1, k2); ``grad_weights``: (g0, g1, g2) >= 0 for slice, row, column; ``weight``
     [n, d, h, w] and ``x0`` [n, f0 d, f1 h, f2 w] share the dtype; ``workspace``: a float64 tensor."""
+    who = "tvsr_solve3d"
     _chk_volumes(y, "y", (torch.float32, torch.float64))
-    f, k = _block_factors3d(kernel, factors)
+    f, k = _block_kernel3d(who, kernel, factors)
     n, d, h, w = y.shape
     D, H, W = d * f[0], h * f[1], w * f[2]
-    _hr_shape3d("tvsr_solve3d", D, H, W, f)
-    if weight is not None:
-        _chk_volumes(weight, "weight", (y.dtype,), y.shape)
-    if x0 is not None:
-        _chk_volumes(x0, "x0", (y.dtype,), (n, D, H, W))
-    lam, alpha, n_iter = _tv_scalars("tvsr_solve3d", lam, alpha, n_iter, TVSR3D_MAX_ITER)
-    g = _grad_weights("tvsr_solve3d", grad_weights)
-    out = torch.empty((n, D, H, W), dtype=y.dtype, device=y.device)
-    (energy, change), entry = _tv_results(y, "inr_tvsr3d_solve")
-    if n == 0:
-        return out, energy, change
-    workspace = _f64_workspace(workspace, tvsr3d_workspace_doubles(n, D, H, W, f), y.device)
-    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), n, D, H, W,
-                                *f, *k, (C.c_double * 3)(*g), lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()),
-          entry)
-    return out, energy, change
+    tv_hr_sides(who, (D, H, W), f)
+    lam, alpha, n_iter = _solve_scalars(who, lam, alpha, n_iter, TVSR3D_MAX_ITER)
+    g = tv_grad_weights(who, grad_weights)
+    return _tv_solve("inr_tvsr3d_solve", y, _chk_volumes, _chk_volumes, (D, H, W), weight, x0, workspace,
+                     lambda: tvsr3d_workspace_doubles(n, D, H, W, f), (n, D, H, W, *f, *k, _doubles(g), lam, alpha, n_iter))
 
 
 # ---- multi-frame TV / Huber super-resolution with sub-pixel shifts (include/inrhip.h, DESIGN.md 4n) ----------------------------------
-TVMF_MAX_FRAMES = _lib.INR_TVMF_MAX_FRAMES
-
-
 def _chk_frames(t, name, dtypes=(torch.float64,), shape=None) -> torch.Tensor:
-    """A contiguous device batch [n, frames, rows, columns] of one of ``dtypes``, 1 .. TVMF_MAX_FRAMES frames."""
-    _chk_batch(t, name, 4, "[n, frames, rows, columns]", dtypes, shape, dtype_first=True)
-    if not 1 <= t.shape[1] <= TVMF_MAX_FRAMES:
-        raise ValueError(f"{name}: frames per image are 1 .. {TVMF_MAX_FRAMES} (got {t.shape[1]})")
-    return t
+    return _chk_batch(t, name, 4, "[n, frames, rows, columns]", dtypes, shape, dtype_first=True)
 
 
 def _chk_shifts(shifts, n, K) -> torch.Tensor:
@@ -1239,15 +1331,15 @@ def _chk_shifts(shifts, n, K) -> torch.Tensor:
 def frame_apply(x: torch.Tensor, shifts: torch.Tensor, factors, kernel, return_valid: bool = False):
     """``inr_frame_apply2d``: ``x`` [n, H, W] float64 and ``shifts`` [n, K, 2] float64 -> the frames ``A_k x`` [n, K, H/f0, W/f1], 0 at
     invalid data; ``return_valid``: also the validity mask, a bool tensor of that shape."""
+    who = "frame_apply"
     _chk_images(x, "x")
-    f0, f1, k = _block_kernel(kernel, factors)
+    f0, f1, k = _block_kernel(who, kernel, factors)
     n, H, W = x.shape
-    _hr_shape("frame_apply", H, W, f0, f1)
+    tv_hr_sides(who, (H, W), (f0, f1))
     if not isinstance(shifts, torch.Tensor) or shifts.dim() != 3:
         raise ValueError("frame_apply: shifts must be a [n, K, 2] tensor")
     K = int(shifts.shape[1])
-    if not 1 <= K <= TVMF_MAX_FRAMES:
-        raise ValueError(f"frame_apply: frames per image are 1 .. {TVMF_MAX_FRAMES} (got {K})")
+    tvmf_frame_count(who, K)
     _chk_shifts(shifts, n, K)
     out = torch.empty((n, K, H // f0, W // f1), dtype=torch.float64, device=x.device)
     valid = torch.empty(out.shape, dtype=torch.uint8, device=x.device) if return_valid else None
@@ -1258,10 +1350,12 @@ def frame_apply(x: torch.Tensor, shifts: torch.Tensor, factors, kernel, return_v
 
 def frame_adjoint(r: torch.Tensor, shifts: torch.Tensor, factors, kernel) -> torch.Tensor:
     """``inr_frame_adjoint2d``: ``r`` [n, K, h, w] float64 -> ``sum_k A_k^T r_k`` [n, f0 h, f1 w]."""
+    who = "frame_adjoint"
     _chk_frames(r, "r")
-    f0, f1, k = _block_kernel(kernel, factors)
     n, K, h, w = r.shape
-    _hr_shape("frame_adjoint", h * f0, w * f1, f0, f1)
+    tvmf_frame_count(who, K)
+    f0, f1, k = _block_kernel(who, kernel, factors)
+    tv_hr_sides(who, (h * f0, w * f1), (f0, f1))
     _chk_shifts(shifts, n, K)
     out = torch.empty((n, h * f0, w * f1), dtype=torch.float64, device=r.device)
     check(lib().inr_frame_adjoint2d(out.data_ptr(), r.data_ptr(), shifts.data_ptr(), n, K, h * f0, w * f1, f0, f1, k, _stream()),
@@ -1280,63 +1374,37 @@ def tvmf_solve(y: torch.Tensor, shifts: torch.Tensor, factors, kernel, lam: floa
     """``inr_tvmf_solve2d`` / ``_f32`` by the dtype of ``y`` [n, K, h, w]: returns (x [n, f0 h, f1 w] of that dtype, energy [n],
     change [n], valid_fraction [n], all float64).  ``shifts`` [n, K, 2] float64 on the device; ``weight`` [n, K, h, w] and ``x0``
     [n, f0 h, f1 w] share the dtype of ``y``; ``workspace``: a float64 tensor."""
+    who = "tvmf_solve"
     _chk_frames(y, "y", (torch.float32, torch.float64))
-    f0, f1, k = _block_kernel(kernel, factors)
     n, K, h, w = y.shape
+    tvmf_frame_count(who, K)
+    f0, f1, k = _block_kernel(who, kernel, factors)
     H, W = h * f0, w * f1
-    _hr_shape("tvmf_solve", H, W, f0, f1)
+    tv_hr_sides(who, (H, W), (f0, f1))
     _chk_shifts(shifts, n, K)
-    if weight is not None:
-        _chk_frames(weight, "weight", (y.dtype,), y.shape)
-    if x0 is not None:
-        _chk_images(x0, "x0", (y.dtype,), (n, H, W))
-    lam, alpha, n_iter = _tv_scalars("tvmf_solve", lam, alpha, n_iter, TVSR3D_MAX_ITER)
-    out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
-    (energy, change, valid), entry = _tv_results(y, "inr_tvmf_solve2d", 3)
-    if n == 0:
-        return out, energy, change, valid
-    workspace = _f64_workspace(workspace, tvmf_workspace_doubles(n, K, H, W, (f0, f1)), y.device)
-    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), valid.data_ptr(), y.data_ptr(), shifts.data_ptr(),
-                                _ptr(weight), _ptr(x0), n, K, H, W, f0, f1, k, lam, alpha, n_iter, workspace.data_ptr(),
-                                workspace.numel(), _stream()), entry)
-    return out, energy, change, valid
+    lam, alpha, n_iter = _solve_scalars(who, lam, alpha, n_iter, TVSR3D_MAX_ITER)
+    return _tv_solve("inr_tvmf_solve2d", y, _chk_frames, _chk_images, (H, W), weight, x0, workspace,
+                     lambda: tvmf_workspace_doubles(n, K, H, W, (f0, f1)), (n, K, H, W, f0, f1, k, lam, alpha, n_iter), results=3,
+                     after_y=(shifts.data_ptr(),))
 
 
 # ---- multi-stack 3-D TV / Huber reconstruction with general slice profiles (include/inrhip.h, DESIGN.md 4o) --------------------------
-TVMS_MAX_STACKS, TVMS_MAX_TAPS = _lib.INR_TVMS_MAX_STACKS, _lib.INR_TVMS_MAX_TAPS
-TVMS_MAX_OFFSET, TVMS_MAX_EXTENT = 1 << 20, 2048
-
-
-def _stack_tables(name, stacks, D, H, W):
+def _stack_tables(who, stacks, D, H, W):
     """``stacks``: a sequence of (f [3], taps (k0, k1, k2), o [3], n [3]) -> (S, M, the C arrays ``geometry`` int [S][12] and ``taps``, the
     per-stack shapes); refuses what the entry points would refuse."""
-    if not all(1 <= s <= TVSR_MAX_SIDE for s in (D, H, W)):
-        raise ValueError(f"{name}: HR volumes are 1 .. {TVSR_MAX_SIDE} samples per axis (got {D} x {H} x {W})")
+    tv_hr_sides(who, (D, H, W))
     stacks = list(stacks)
-    if not 1 <= len(stacks) <= TVMS_MAX_STACKS:
-        raise ValueError(f"{name}: stacks per volume are 1 .. {TVMS_MAX_STACKS} (got {len(stacks)})")
+    tvms_stack_count(who, len(stacks))
     geo, taps, shapes = [], [], []
     for s, (f, ks, o, n) in enumerate(stacks):
         f, o, n = (tuple(int(v) for v in t) for t in (f, o, n))
-        ks = [[float(v) for v in k] for k in ks]
-        if len(f) != 3 or len(o) != 3 or len(n) != 3 or len(ks) != 3:
-            raise ValueError(f"{name}: stack {s} needs three spacings, tap vectors, offsets and extents")
-        if not all(1 <= v <= TVSR_MAX_FACTOR for v in f):
-            raise ValueError(f"{name}: spacings are 1 .. {TVSR_MAX_FACTOR} per axis (stack {s}: {f})")
-        if not all(1 <= len(k) <= TVMS_MAX_TAPS for k in ks):
-            raise ValueError(f"{name}: tap counts are 1 .. {TVMS_MAX_TAPS} per axis (stack {s}: {[len(k) for k in ks]})")
-        if not all(abs(v) <= TVMS_MAX_OFFSET for v in o):
-            raise ValueError(f"{name}: offsets are within +-{TVMS_MAX_OFFSET} HR voxels (stack {s}: {o})")
-        if not all(1 <= v <= TVMS_MAX_EXTENT for v in n):
-            raise ValueError(f"{name}: LR extents are 1 .. {TVMS_MAX_EXTENT} per axis (stack {s}: {n})")
-        for axis, k in enumerate(ks):
-            if not all(v == v and abs(v) != float("inf") for v in k) or abs(sum(k) - 1.0) > 1e-9:
-                raise ValueError(f"{name}: taps k{axis} of stack {s} must be finite and sum to 1 (sum {sum(k)!r})")
-            taps.extend(k)
+        f, ks = tv_factors(f"{who}: stack {s}", f, 3), tv_kernel_factors(f"{who}: stack {s}", ks)
+        o, n = tvms_offsets(f"{who}: stack {s}", o), tvms_lr_shape(f"{who}: stack {s}", n)
+        taps.extend(v for k in ks for v in k)
         geo.extend(f + tuple(len(k) for k in ks) + o + n)
         shapes.append(n)
     M = sum(n[0] * n[1] * n[2] for n in shapes)
-    return len(stacks), M, (C.c_int * len(geo))(*geo), (C.c_double * len(taps))(*taps), shapes
+    return len(stacks), M, (C.c_int * len(geo))(*geo), _doubles(taps), shapes
 
 
 def stack_apply(x: torch.Tensor, stacks, return_valid: bool = False):
@@ -1351,8 +1419,9 @@ def stack_apply(x: torch.Tensor, stacks, return_valid: bool = False):
     return (out, valid.bool()) if return_valid else out
 
 
-def _chk_rows(t, name, dtypes, n, M):
-    """A contiguous device batch [n, M] of one of ``dtypes`` (n None: any)."""
+def _chk_rows(t, name, dtypes, shape):
+    """A contiguous device batch [n, M] = ``shape`` of one of ``dtypes`` (n None: any)."""
+    n, M = shape
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if t.dtype not in dtypes:
@@ -1366,9 +1435,9 @@ def _chk_rows(t, name, dtypes, n, M):
 
 def stack_adjoint(r: torch.Tensor, stacks, hr_shape) -> torch.Tensor:
     """``inr_tvms_adjoint``: ``r`` [n, M] float64 -> ``sum_s A_s^T r_s`` [n, D, H, W]."""
-    D, H, W = (int(v) for v in hr_shape)
+    D, H, W = tv_hr_shape3d("stack_adjoint", hr_shape)
     S, M, geo, taps, _ = _stack_tables("stack_adjoint", stacks, D, H, W)
-    _chk_rows(r, "r", (torch.float64,), None, M)
+    _chk_rows(r, "r", (torch.float64,), (None, M))
     n = r.shape[0]
     out = torch.empty((n, D, H, W), dtype=torch.float64, device=r.device)
     check(lib().inr_tvms_adjoint(out.data_ptr(), r.data_ptr(), n, D, H, W, S, geo, taps, _stream()), "inr_tvms_adjoint")
@@ -1386,35 +1455,22 @@ def tvms_solve(y: torch.Tensor, stacks, hr_shape, lam: float, alpha: float, n_it
     """``inr_tvms_solve`` / ``_f32`` by the dtype of ``y`` [n, M]: returns (x [n, D, H, W] of that dtype, energy [n], change [n],
     valid_fraction [n], all float64).  ``stacks`` as ``_stack_tables`` takes them; ``weight`` [n, M] and ``x0`` [n, D, H, W] share the
     dtype of ``y``; ``workspace``: a float64 tensor."""
-    D, H, W = (int(v) for v in hr_shape)
-    S, M, geo, taps, _ = _stack_tables("tvms_solve", stacks, D, H, W)
-    _chk_rows(y, "y", (torch.float32, torch.float64), None, M)
+    who = "tvms_solve"
+    D, H, W = tv_hr_shape3d(who, hr_shape)
+    S, M, geo, taps, _ = _stack_tables(who, stacks, D, H, W)
+    _chk_rows(y, "y", (torch.float32, torch.float64), (None, M))
     n = y.shape[0]
-    if weight is not None:
-        _chk_rows(weight, "weight", (y.dtype,), n, M)
-    if x0 is not None:
-        _chk_volumes(x0, "x0", (y.dtype,), (n, D, H, W))
-    lam, alpha, n_iter = _tv_scalars("tvms_solve", lam, alpha, n_iter, TVSR3D_MAX_ITER)
-    g = _grad_weights("tvms_solve", grad_weights)
-    out = torch.empty((n, D, H, W), dtype=y.dtype, device=y.device)
-    (energy, change, valid), entry = _tv_results(y, "inr_tvms_solve", 3)
-    if n == 0:
-        return out, energy, change, valid
-    workspace = _f64_workspace(workspace, int(lib().inr_tvms_workspace_doubles(n, D, H, W, S, geo)), y.device)
-    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), valid.data_ptr(), y.data_ptr(), _ptr(weight),
-                                _ptr(x0), n, D, H, W, S, geo, taps, (C.c_double * 3)(*g), lam, alpha, n_iter, workspace.data_ptr(),
-                                workspace.numel(), _stream()), entry)
-    return out, energy, change, valid
+    lam, alpha, n_iter = _solve_scalars(who, lam, alpha, n_iter, TVSR3D_MAX_ITER)
+    g = tv_grad_weights(who, grad_weights)
+    return _tv_solve("inr_tvms_solve", y, _chk_rows, _chk_volumes, (D, H, W), weight, x0, workspace,
+                     lambda: int(lib().inr_tvms_workspace_doubles(n, D, H, W, S, geo)),
+                     (n, D, H, W, S, geo, taps, _doubles(g), lam, alpha, n_iter), results=3)
 
 
 # ---- TV / Huber super-resolution under a dense separable operator (include/inrhip.h, DESIGN.md 4p) -----------------------------------
 def _chk_operators(operators, H, W, h, w):
     """The DEVICE operators (R0 [h, H], R1 [w, W]) float64, contiguous; their values are the kernels' business."""
-    try:
-        r0, r1 = operators
-    except (TypeError, ValueError):
-        raise ValueError("operators are a pair (R0 [h, H], R1 [w, W])") from None
-    for name, r, shape in (("operators[0]", r0, (h, H)), ("operators[1]", r1, (w, W))):
+    for name, r, shape in zip(("operators[0]", "operators[1]"), operators, ((h, H), (w, W))):
         if not isinstance(r, torch.Tensor):
             raise TypeError(f"{name} must be a torch.Tensor")
         if r.dtype != torch.float64:
@@ -1423,18 +1479,13 @@ def _chk_operators(operators, H, W, h, w):
             raise InrDeviceError(f"{name} is on {r.device}: the kernels only run on a HIP device (there is no CPU fallback)")
         if tuple(r.shape) != shape or not r.is_contiguous():
             raise ValueError(f"{name} must be a contiguous {list(shape)} tensor (got {tuple(r.shape)})")
-    return r0, r1
+    return tuple(operators)
 
 
-def _operator_sides(name, operators):
+def _operator_sides(who, operators):
     """(H, W, h, w) from the shapes of the pair, each side 1 .. TVSR_MAX_SIDE."""
-    try:
-        r0, r1 = operators
-        (h, H), (w, W) = (int(v) for v in r0.shape), (int(v) for v in r1.shape)
-    except (TypeError, ValueError, AttributeError):
-        raise ValueError(f"{name}: operators are a pair of 2-D tensors (R0 [h, H], R1 [w, W])") from None
-    if not all(1 <= s <= TVSR_MAX_SIDE for s in (H, W, h, w)):
-        raise ValueError(f"{name}: every side of the operators is 1 .. {TVSR_MAX_SIDE} (got R0 {h} x {H}, R1 {w} x {W})")
+    (h, H), (w, W) = (tvop_operator_shape(who, f"operators[{i}]", getattr(r, "shape", ()))
+                      for i, r in enumerate(tvop_operator_pair(who, operators)))
     return H, W, h, w
 
 
@@ -1482,26 +1533,16 @@ def tvop_solve(y: torch.Tensor, operators, lam: float, alpha: float, n_iter: int
     """``inr_tvop_solve2d`` / ``_f32`` by the dtype of ``y`` [n, h, w]: returns (x [n, H, W] of that dtype, energy [n] float64, change
     [n] float64).  ``operators`` = (R0 [h, H], R1 [w, W]), device float64, shared by the batch; ``weight`` [n, h, w] and ``x0``
     [n, H, W] share the dtype of ``y``; ``workspace``: a float64 tensor."""
+    who = "tvop_solve"
     _chk_images(y, "y", (torch.float32, torch.float64))
-    H, W, h, w = _operator_sides("tvop_solve", operators)
+    H, W, h, w = _operator_sides(who, operators)
     n = y.shape[0]
     if tuple(y.shape[1:]) != (h, w):
         raise ValueError(f"y has shape {tuple(y.shape)}, expected {(n, h, w)}")
     r0, r1 = _chk_operators(operators, H, W, h, w)
-    if weight is not None:
-        _chk_images(weight, "weight", (y.dtype,), y.shape)
-    if x0 is not None:
-        _chk_images(x0, "x0", (y.dtype,), (n, H, W))
-    lam, alpha, n_iter = _tv_scalars("tvop_solve", lam, alpha, n_iter, TVSR3D_MAX_ITER)
-    out = torch.empty((n, H, W), dtype=y.dtype, device=y.device)
-    (energy, change), entry = _tv_results(y, "inr_tvop_solve2d")
-    if n == 0:
-        return out, energy, change
-    workspace = _f64_workspace(workspace, tvop_workspace_doubles(n, H, W, h, w), y.device)
-    check(getattr(lib(), entry)(out.data_ptr(), energy.data_ptr(), change.data_ptr(), y.data_ptr(), _ptr(weight), _ptr(x0), r0.data_ptr(),
-                                r1.data_ptr(), n, H, W, h, w, lam, alpha, n_iter, workspace.data_ptr(), workspace.numel(), _stream()),
-          entry)
-    return out, energy, change
+    lam, alpha, n_iter = _solve_scalars(who, lam, alpha, n_iter, TVSR3D_MAX_ITER)
+    return _tv_solve("inr_tvop_solve2d", y, _chk_images, _chk_images, (H, W), weight, x0, workspace,
+                     lambda: tvop_workspace_doubles(n, H, W, h, w), (r0.data_ptr(), r1.data_ptr(), n, H, W, h, w, lam, alpha, n_iter))
 
 
 # ---- diagnostics ------------------------------------------------------------------------------------------

@@ -166,7 +166,7 @@ def test_ops_wrapper_checks_before_it_launches():
         ops.tgv_solve(y, (2, 2), k, 0.01, 0.0, 0.0, 3)
     with pytest.raises(ValueError, match="workspace must be a device float64 tensor of at least 1320"):
         ops.tgv_solve(y, (2, 2), k, 0.01, 2.0, 0.0, 3, workspace=torch.empty(1319, device="cuda", dtype=torch.float64))
-    with pytest.raises(ValueError, match="n_iter >= 0"):
+    with pytest.raises(ValueError, match="n_iter must be an integer >= 0"):
         ops.tgv_solve(y, (2, 2), k, 0.01, 2.0, 0.0, -1)
     ws = torch.empty(1320, device="cuda", dtype=torch.float64)
     again = ops.tgv_solve(y, (2, 2), k, 0.01, 2.0, 0.0, 3, workspace=ws)

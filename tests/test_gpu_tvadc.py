@@ -271,7 +271,7 @@ def test_ops_wrapper_checks_before_it_launches(monkeypatch):
                               ("b-values must be finite and >= 0", dict(b=(0.0, -1.0, 1000.0))), ("all equal", dict(b=(5.0, 5.0, 5.0))),
                               ("map_weights are", dict(mu=(1.0, 2.0))), ("coupling must be 'joint' or 'none'", dict(coupling=1)),
                               ("s_max must be finite and > 0", dict(s_max=0.0)), ("adc_max must be finite and > 0", dict(adc_max=float("inf"))),
-                              ("adc0 must be within", dict(adc0=5e-3)), ("n_iter >= 0", dict(n_iter=-1)),
+                              ("adc0 must be within", dict(adc0=5e-3)), ("n_iter must be an integer >= 0", dict(n_iter=-1)),
                               (f"workspace must be a device float64 tensor of at least {need}",
                                dict(workspace=torch.empty(need - 1, device="cuda", dtype=torch.float64)))):
         a = dict(y=y, b=b, mu=(1.0, 0.1), coupling="joint", n_iter=3, s_max=1.5, adc_max=4e-3, adc0=1e-3, weight=None, x0=None, workspace=None)

@@ -269,7 +269,7 @@ def test_ops_wrapper_checks_before_it_launches():
         ops.tvj_solve(torch.rand(1, 17, 3, 5, device="cuda", dtype=torch.float64), (2, 2), k, None, 0.01, 0.0, "joint", 3)
     with pytest.raises(ValueError, match="workspace must be a device float64 tensor of at least 1440"):
         ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", 3, workspace=torch.empty(1439, device="cuda", dtype=torch.float64))
-    with pytest.raises(ValueError, match="n_iter >= 0"):
+    with pytest.raises(ValueError, match="n_iter must be an integer >= 0"):
         ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", -1)
     ws = torch.empty(1440, device="cuda", dtype=torch.float64)
     again = ops.tvj_solve(y, (2, 2), k, None, 0.01, 0.0, "joint", 3, workspace=ws)[0]

@@ -311,7 +311,7 @@ def test_ops_wrappers_check_before_they_launch():
         ops.tvmf_solve(y, s, f, [[1.0], [1.0]], 0.01, 0.0, 3)
     with pytest.raises(ValueError, match=f"workspace must be a device float64 tensor of at least {need}"):
         ops.tvmf_solve(y, s, f, k, 0.01, 0.0, 3, workspace=torch.empty(need - 1, device="cuda", dtype=torch.float64))
-    with pytest.raises(ValueError, match="n_iter 0 .. 100000"):
+    with pytest.raises(ValueError, match="n_iter must be an integer 0 .. 100000"):
         ops.tvmf_solve(y, s, f, k, 0.01, 0.0, -1)
     with pytest.raises(ValueError, match="frames per image are 1 .. 64"):
         ops.tvmf_solve(torch.rand(1, 65, 2, 2, device="cuda", dtype=torch.float64), torch.zeros(1, 65, 2, device="cuda",

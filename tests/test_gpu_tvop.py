@@ -266,9 +266,9 @@ def test_types_shapes_and_refusals():
         ops.tvop_solve(y, dev_pair, 0.02, 0.05, 5, x0=y)
     with pytest.raises(ValueError, match="y has shape"):
         ops.tvop_solve(x, dev_pair, 0.02, 0.05, 5)
-    with pytest.raises(ValueError, match="lam and alpha"):
+    with pytest.raises(ValueError, match="lam must be finite and >= 0"):
         ops.tvop_solve(y, dev_pair, -1.0, 0.05, 5)
-    with pytest.raises(ValueError, match="lam and alpha"):
+    with pytest.raises(ValueError, match="n_iter must be an integer 0 .. 100000"):
         ops.tvop_solve(y, dev_pair, 0.02, 0.05, 100001)
     for call in (lambda s: ops.tvop_solve(y, dev_pair, 0.02, 0.05, 5, workspace=s), lambda s: ops.tvop_apply(x, dev_pair, workspace=s),
                  lambda s: ops.tvop_adjoint(y, dev_pair, workspace=s)):

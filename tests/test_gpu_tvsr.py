@@ -220,7 +220,7 @@ def test_ops_wrappers_check_before_they_launch():
         ops.tvsr_solve(y, (2, 2), [[1.0, 1.0], [1.0, 1.0]], 0.01, 0.0, 3)
     with pytest.raises(ValueError, match="workspace must be a device float64 tensor of at least 480"):
         ops.tvsr_solve(y, (2, 2), k, 0.01, 0.0, 3, workspace=torch.empty(479, device="cuda", dtype=torch.float64))
-    with pytest.raises(ValueError, match="n_iter >= 0"):
+    with pytest.raises(ValueError, match="n_iter must be an integer >= 0"):
         ops.tvsr_solve(y, (2, 2), k, 0.01, 0.0, -1)
 
 

@@ -310,7 +310,7 @@ def test_ops_wrappers_check_before_they_launch():
         ops.tvsr_solve3d(y, f, ([1.0, 1.0], [0.5, 0.5], [1.0]), 0.01, 0.0, 3)
     with pytest.raises(ValueError, match=f"workspace must be a device float64 tensor of at least {need}"):
         ops.tvsr_solve3d(y, f, k, 0.01, 0.0, 3, workspace=torch.empty(need - 1, device="cuda", dtype=torch.float64))
-    with pytest.raises(ValueError, match="n_iter 0 .. 100000"):
+    with pytest.raises(ValueError, match="n_iter must be an integer 0 .. 100000"):
         ops.tvsr_solve3d(y, f, k, 0.01, 0.0, -1)
     with pytest.raises(ValueError, match="grad_weights"):
         ops.tvsr_solve3d(y, f, k, 0.01, 0.0, 3, grad_weights=(1.0, -1.0, 1.0))

@@ -257,7 +257,7 @@ def test_python_entry_points_refuse_by_name():
     with pytest.raises(TypeError, match="y must be a torch.Tensor"):
         ops.tvadc_solve(np.ones((1, 2, 4, 4)), (0.0, 1000.0), (2, 2), k, (1.0, 0.1), 0.01, 0.0, "joint", 3, 1.5, 4e-3, 1e-3)
     ok = dict(b=(0.0, 400.0, 1000.0), channels=3, map_weights=(1.0, 0.1), coupling="joint", s_max=1.5, adc_max=4e-3, adc0=1e-3)
-    assert ops._tvadc_model("tvadc_solve", **ok) == ([0.0, 400.0, 1000.0], [1.0, 0.1], 1.5, 4e-3, 1e-3)
+    assert ops.tvadc_model("tvadc_solve", **ok) == ([0.0, 400.0, 1000.0], [1.0, 0.1], 1.5, 4e-3, 1e-3)
     for change, text in (({"channels": 1, "b": (0.0,)}, "b-values are 2 .. 16 per group \\(got 1\\)"), ({"channels": 17}, "b-values are 2 .. 16"),
                          ({"b": (0.0, 1000.0)}, "b has 2 b-values, expected one per channel \\(3\\)"),
                          ({"b": (0.0, -1.0, 5.0)}, "b-values must be finite and >= 0"), ({"b": (0.0, float("nan"), 5.0)}, "b-values must be finite"),
@@ -266,7 +266,7 @@ def test_python_entry_points_refuse_by_name():
                          ({"s_max": float("nan")}, "s_max must be finite and > 0"), ({"adc_max": 0.0}, "adc_max must be finite and > 0"),
                          ({"adc0": 1.0}, "adc0 must be within \\[0, adc_max\\]")):
         with pytest.raises(ValueError, match=f"tvadc_solve: {text}"):
-            ops._tvadc_model("tvadc_solve", **{**ok, **change})
+            ops.tvadc_model("tvadc_solve", **{**ok, **change})
     # the defaults are the ones the drivers' flags carry
     args = dwi_script.build_parser().parse_args(["--data", "x.mat"])
     assert args.tv_adc is False and (args.tv_adc_lambda, args.tv_adc_weight, args.tv_adc_iters) == (
