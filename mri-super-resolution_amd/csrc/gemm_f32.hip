@@ -18,7 +18,8 @@
 //       under the last K-tile, bias-gradient column sums.
 //   gemm_f32_pipe_kernel   -- the same structure on v_mfma_f32_32x32x2_f32 (2x2 accumulators, k = 4h..4h+3 per
 //       8-block).  Kept for A/B (inr_debug_set(1, 0)): 5-7 % slower (tools/gemm_ab.py).
-//   gemm_f32_kernel        -- generic fallback (any shape/alignment: scalar guarded loads), 32x32x2, plain loop.
+//   gemm_f32_kernel        -- generic fallback (any shape/alignment: scalar guarded loads), 32x32x2, plain loop; its
+//       epilogue is scalar and guarded, so it also takes every output the float4 epilogue cannot write (N % 4 != 0).
 // blockIdx is remapped so that consecutive logical tiles (which share an A row-panel) land on the same XCD.
 //
 // Measured facts that shaped it (s_memtime stamps: tools/stamp_timeline.py; tools/mfma_rate.hip, tools/gemm_ab.py):
@@ -816,7 +817,16 @@ static int launch_gemm(GemmParams p, bool vec, hipStream_t stream, bool* used_fa
     // operand, and every byte offset inside one block's SRD stays below 2^31
     const long long a_span = A_KC ? (long long)BM * p.lda : (long long)p.k_per_split * p.lda;
     const long long b_span = B_KC ? (long long)BN * p.ldb : (long long)p.k_per_split * p.ldb;
-    const bool fast = vec && !g_force_generic && (!A_KC || p.K % BK == 0) && (!B_KC || p.K % BK == 0) &&
+    // ... and the staged epilogue moves float4s only: a lane keeps or drops four columns together, so N must not cut a
+    // float4, a row of C must start on one (ldc, slab stride), and so must every array the epilogue reads or writes at
+    // C's offsets (dact, the factor), the bias and the column-sum slab.  Anything else runs the generic kernel, whose
+    // epilogue is scalar and guarded.
+    constexpr bool EPI_STASH = EPI == EPI_SINE_STASH || EPI == EPI_TANH_STASH;
+    constexpr bool EPI_BIAS = EPI == EPI_SINE || EPI == EPI_SINE_STASH || EPI == EPI_TANH || EPI == EPI_TANH_STASH;
+    const bool epi_vec = p.N % 4 == 0 && p.ldc % 4 == 0 && p.slab_stride % 4 == 0 && aligned16(p.C) &&
+                         (!EPI_STASH || aligned16(p.C2)) && (!EPI_BIAS || aligned16(p.bias)) &&
+                         (EPI != EPI_MUL || (aligned16(p.mul) && aligned16(p.colsum)));
+    const bool fast = vec && epi_vec && !g_force_generic && (!A_KC || p.K % BK == 0) && (!B_KC || p.K % BK == 0) &&
                       (a_span + (long long)BK * p.lda) * 4 < (1ll << 31) &&
                       (b_span + (long long)BK * p.ldb) * 4 < (1ll << 31);
     if (used_fast) *used_fast = fast;

@@ -178,6 +178,8 @@ def sine_layer_forward(x, W, b, omega: float, stash: bool):
     n, fin, fout = _layer_dims(x, W, b)
     act = torch.empty((n, fout), dtype=torch.float32, device=x.device)
     dact = torch.empty_like(act) if stash else None
+    if n == 0:      # nothing to launch (an empty tensor has no address to pass)
+        return act, dact
     check(lib().inr_sine_layer_forward(act.data_ptr(), _ptr(dact), x.data_ptr(), W.data_ptr(), _ptr(b), n, fin, fout,
                                        float(omega), _stream()), "inr_sine_layer_forward")
     return act, dact
@@ -188,6 +190,8 @@ def tanh_layer_forward(x, W, b, scale: float, stash: bool):
     n, fin, fout = _layer_dims(x, W, b)
     act = torch.empty((n, fout), dtype=torch.float32, device=x.device)
     dact = torch.empty_like(act) if stash else None
+    if n == 0:      # nothing to launch (an empty tensor has no address to pass)
+        return act, dact
     check(lib().inr_tanh_layer_forward(act.data_ptr(), _ptr(dact), x.data_ptr(), W.data_ptr(), _ptr(b), n, fin, fout,
                                        float(scale), _stream()), "inr_tanh_layer_forward")
     return act, dact
@@ -296,6 +300,8 @@ def sine_layer_backward_input(dz, W, dact_prev, out=None, need_bias=False):
         gb = torch.empty((fin,), dtype=torch.float32, device=dz.device)
         ws = _ws(lib().inr_sine_layer_backward_input_workspace_bytes(n, fin), dz.device)
         ws_ptr, ws_bytes = ws.data_ptr(), ws.numel()
+    if n == 0:      # nothing to launch: an empty result, and the sum over no rows
+        return (out, gb.zero_()) if need_bias else out
     check(lib().inr_sine_layer_backward_input(out.data_ptr(), _ptr(gb), dz.data_ptr(), W.data_ptr(), _ptr(dact_prev), n,
                                               fin, fout, ws_ptr, ws_bytes, _stream()),
           "inr_sine_layer_backward_input")
