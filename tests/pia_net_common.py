@@ -51,9 +51,10 @@ def leaky(z):
     return torch.where(z > 0, z, SLOPE * z)
 
 
-def forward64(params, x, dtype=torch.float64):
+def forward64(params, x, dtype=torch.float64, b_values=B_VALUES, te_values=TE_VALUES):
     """-> signal (float64 values of the float32-rounded decoder output), D, T2, v (float64).  `dtype=torch.float32` runs the
-    layers in float32 instead (a diagnostic: how far plain float32 arithmetic is from float64 on a given batch)."""
+    layers in float32 instead (a diagnostic: how far plain float32 arithmetic is from float64 on a given batch).
+    `b_values` / `te_values` are the acquisition tables (n_b * n_te == 16), b-major as PIA.py:123-124 walks them."""
     p = [t.to(dtype) for t in params]
     a = x.to(dtype)
     L = (len(p) - 12) // 2                        # encoder layers (5 for the default shape); predictor_depth 1
@@ -68,27 +69,34 @@ def forward64(params, x, dtype=torch.float64):
     D = dm + dd * torch.tanh(heads[0]).double()
     T2 = tm + td * torch.tanh(heads[1]).double()
     v = torch.softmax(heads[2], dim=1).double()
-    nb = torch.tensor([-b / 1000 for b in B_VALUES for _ in TE_VALUES], dtype=torch.float64)
-    te = torch.tensor([float(t) for _ in B_VALUES for t in TE_VALUES], dtype=torch.float64)
+    nb = torch.tensor([-b / 1000 for b in b_values for _ in te_values], dtype=torch.float64)
+    te = torch.tensor([float(t) for _ in b_values for t in te_values], dtype=torch.float64)
     S = sum(v[:, c:c + 1] * torch.exp(nb[None, :] * D[:, c:c + 1]) * torch.exp(-te[None, :] / T2[:, c:c + 1]) for c in range(3))
     signal = (1000 * S.float()).double()          # the float32 tensor `decode` writes into
     return signal, D.double(), T2.double(), v.double()
 
 
-def loss_and_grads64(params, x, pids, dtype=torch.float64):
-    """Unsupervised loss (float64) and its 22 gradients for float64 leaf copies of `params`."""
+def loss_and_grads64(params, x, pids, dtype=torch.float64, b_values=B_VALUES, te_values=TE_VALUES, functional=None):
+    """Unsupervised loss (float64) and its gradients, one per parameter tensor, for float64 leaf copies of `params`.
+    `functional(signal, D, T2, v) -> scalar` replaces the unsupervised loss when given (`pids` is then unused); a parameter
+    the functional does not reach gets a zero gradient, which is what the backward kernels write for it."""
     leaves = [t.detach().to(dtype).requires_grad_(True) for t in params]
-    signal, D, T2, v = forward64(leaves, x, dtype)
-    loss = torch.mean(torch.as_tensor(pids).double() * (signal - x.double()) ** 2)
-    grads = torch.autograd.grad(loss, leaves)
+    signal, D, T2, v = forward64(leaves, x, dtype, b_values, te_values)
+    if functional is None:
+        loss = torch.mean(torch.as_tensor(pids).double() * (signal - x.double()) ** 2)
+        grads = torch.autograd.grad(loss, leaves)
+    else:
+        loss = functional(signal, D, T2, v)
+        grads = [torch.zeros_like(t) if g is None else g for g, t in zip(torch.autograd.grad(loss, leaves, allow_unused=True), leaves)]
     return loss.detach(), [g.detach() for g in grads], (signal.detach(), D.detach(), T2.detach(), v.detach())
 
 
 KINK_EPS = 2.0 ** -18
 
 
-def kink_rows(params, x, eps=KINK_EPS):
-    """Rows of `x` on which the gradient is not defined at float32 resolution, judged by float64 alone.
+def kink_rows(params, x, eps=KINK_EPS, b_values=B_VALUES, te_values=TE_VALUES):
+    """(`b_values` / `te_values` are accepted for a uniform call signature and unused: every LeakyReLU lies below the decoder.)
+    Rows of `x` on which the gradient is not defined at float32 resolution, judged by float64 alone.
 
     LeakyReLU has a kink at zero.  A pre-activation z = sum_k a_k w_k + b evaluated in float32 carries an error of up to
     K u sum_k |a_k w_k| (u = 2^-24, K <= 512 terms; about sqrt(K) u = 23 u when the roundings behave like a random walk), plus

@@ -2,6 +2,7 @@
 """Generate tests/golden/pia_net.npz by running the REAL reference `PIA` class on the CPU.
 
     python tools/gen_golden_pia_net.py --reference <checkout>/implicit-neural-representations
+    python tools/gen_golden_pia_net.py --reference <checkout>/implicit-neural-representations --shapes    # pia_net_shapes.npz
 
 Imports `PIA` from the reference checkout at generation time and writes data only: SHA-256 of the seeded initial weights,
 a `get_batch` batch, forward / loss / gradients in float32 and from a float64 deep copy, the deviation of the former from
@@ -25,12 +26,89 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import pia_net_common as C  # noqa: E402
 
 
+REF_ERR_TIER = 1e-5      # the project's gradient tier: a training case whose reference run misses it is no yardstick
+
+
+def shapes(R):
+    """tests/golden/pia_net_shapes.npz: the yardstick of tests/pia_shapes_common.CASES.
+
+    Per case: SHA-256 of the seeded initial weights and of the input batch, the reference class's float32-versus-float64-deepcopy
+    deviation per output and per gradient tensor (`ref_err_out`, `ref_err_grad`), and float64 values to which
+    tests/test_pia_shapes_cpu.py pins the restatement at 1e-12: the outputs by the every-97th rule, the gradients as every 997th
+    element of the tensors laid end to end plus each tensor's L1 norm (the every-97th rule on every gradient tensor of every
+    case would come to 1.7 MB).  Inputs are not stored: they are `pia_net.get_batch` under the case's NumPy seed -- the
+    project's own generator, which tests/test_pia_net_cpu.py holds to the reference's draws, so that generator and tests build
+    the same bits -- filtered by `kink_rows`.  A training case whose reference run deviates more than REF_ERR_TIER on any
+    tensor stops the generator: choose another seed or a deeper shape of the same class in the table, never a wider bound.
+    Also `detect_PIDS_slice` on the seeded one-row slices of `pids_slice_input`."""
+    import pia_shapes_common as S
+    from mri_super_resolution_amd import pia_net
+
+    out = {"case_names": np.array([c.name for c in S.CASES])}
+    for case in S.CASES:
+        b_values, te_values = case.tables
+        torch.manual_seed(0)
+        m = R.PIA(hidden_dims=list(case.hidden), b_values=list(b_values), TE_values=list(te_values))
+        m64 = copy.deepcopy(m).double()
+        host = [p.detach().clone() for p in m.parameters()]
+        pre = case.name
+        out[f"{pre}/init_sha"] = np.array(S.params_sha([p.numpy() for p in host]))
+        x, pids, flagged = S.case_inputs(case, host, pia_net.get_batch)
+        out[f"{pre}/x_sha"] = np.array(C.sha(x.numpy()))
+        if flagged is not None:
+            out[f"{pre}/flagged"] = np.array(flagged)
+            assert flagged <= S.MAX_FLAGGED * S.pool_rows(case.rows), (pre, flagged)
+        o32, o64 = m(x), m64(x.double())
+        idx = (("signal", 0), ("D", 2), ("T2", 3), ("v", 4))
+        out[f"{pre}/ref_err_out"] = np.array([C.rel_dev(o32[i].detach().numpy(), o64[i].detach().numpy()) for _, i in idx])
+        for k, i in idx:
+            out[f"{pre}/f64/{k}"] = C.sample(o64[i].detach().numpy().astype(np.float64))
+        line = f"{pre}: flagged {flagged}, ref_err out {out[pre + '/ref_err_out'].max():.2e}"
+        if case.kind != "forward":
+            if case.kind == "train":
+                l32 = m.loss_function(o32[0], x, pids)
+                l64 = m64.loss_function(o64[0], x.double(), pids.double())
+            else:
+                w = S.functional_weights(case.rows, case.seed)
+                named32 = {k: o32[i] for k, i in idx}
+                named64 = {k: o64[i] for k, i in idx}
+                l32 = sum((w[k] * named32[k]).sum() for k in S.functional_terms(case.functional))
+                l64 = sum((w[k].double() * named64[k]).sum() for k in S.functional_terms(case.functional))
+            l32.backward()
+            l64.backward()
+            out[f"{pre}/f64/loss"] = np.array(l64.item())
+            g32 = [np.zeros(tuple(p.shape), np.float32) if p.grad is None else p.grad.numpy() for p in m.parameters()]
+            g64 = [np.zeros(tuple(p.shape), np.float64) if p.grad is None else p.grad.numpy() for p in m64.parameters()]
+            # a tensor the functional does not reach has a zero gradient on both sides: no deviation, and NaN marks it
+            err = np.array([C.rel_dev(a, b) if np.abs(b).max() > 0 else np.nan for a, b in zip(g32, g64)])
+            out[f"{pre}/ref_err_grad"] = err
+            out[f"{pre}/f64/grad_flat"], out[f"{pre}/f64/grad_l1"] = S.flat_grad_sample(g64)
+            line += f", ref_err grad {np.nanmin(err):.2e} .. {np.nanmax(err):.2e} (median {np.nanmedian(err):.2e})"
+            if case.kind == "train":
+                assert np.nanmax(err) <= REF_ERR_TIER and out[f"{pre}/ref_err_out"].max() <= REF_ERR_TIER, \
+                    f"{pre}: the reference's own float32 run is {np.nanmax(err):.2e} off its float64 copy -- not a yardstick"
+        print(line, flush=True)
+    bv = np.array(C.B_VALUES, dtype=np.float64)
+    for n in S.PIDS_PIXELS:
+        res = R.detect_PIDS_slice(bv, S.pids_slice_input(n))
+        for k, a in zip(("adc1", "adc2", "b_decay", "te_decay"), res):
+            out[f"pids_slice/{n}/{k}"] = a.astype(np.uint8)
+        print(f"pids_slice/{n}: sums", [float(a.sum()) for a in res])
+    path = os.path.join(ROOT, "tests", "golden", "pia_net_shapes.npz")
+    np.savez_compressed(path, **out)
+    print("pia_net_shapes.npz", os.path.getsize(path), "bytes")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", required=True, help="directory of the reference checkout that holds PIA.py")
+    ap.add_argument("--shapes", action="store_true", help="write tests/golden/pia_net_shapes.npz (the shape-class table) instead")
     args = ap.parse_args()
     sys.path.insert(0, args.reference)
     import PIA as R  # noqa: E402  (the reference module itself)
+    if args.shapes:
+        sys.path.insert(0, ROOT)
+        return shapes(R)
 
     out = {}
 
