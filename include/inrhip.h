@@ -871,6 +871,64 @@ int inr_degibbs2d(double* out, int32_t* choice, const double* in, int n_images, 
 int inr_degibbs2d_f32(float* out, int32_t* choice, const float* in, int n_images, int height, int width, int nshifts, int w_min,
                       int w_max, double* workspace, int64_t workspace_doubles, void* stream);
 
+/* ---- non-local means on volumes and non-local MRI upsampling --------------------------------------------------------------
+ * No counterpart in the reference.  Buades et al. 2005 in its MRI form (Rician bias correction: Wiest-Daessle et al. 2008, Manjon et al.
+ * 2008; a per-voxel strength) and the upsampling of Manjon et al., Medical Image Analysis 2010; pinned to the definition below, which
+ * tests/nlm_common.py restates in float64 numpy.  All arithmetic is fp64.
+ * A guide G [D][H][W], C value volumes X_c [D][H][W], search radii s = (s0, s1, s2), 0 .. INR_NLM_MAX_SEARCH each, patch radii
+ * r = (r0, r1, r2), 0 .. INR_NLM_MAX_PATCH each, a strength h2_p > 0 (one scalar, or one value per voxel):
+ *   offsets   for a voxel p and an offset t != 0 of the search box, q = p + t; an offset whose q lies outside the volume is skipped.
+ *   distance  d2(p, t) = (1 / n) sum_d (G[p + d] - G[q + d])^2 over the patch offsets d for which both p + d and q + d lie inside the
+ *             volume, n their number (d = 0 always counts).  Indices are never clamped or mirrored, so the squared-difference field of t
+ *             followed by a separable box sum is exact at the borders too, and n is a product of three per-axis counts.
+ *   weights   w(p, t) = exp(-d2 / h2_p), no cutoff;  wmax_p = max_t w;  the centre weight wc = wmax_p, or 1 where wmax_p is not > 0
+ *             (INR_NLM_CENTER_MAX), or wc = 1 (INR_NLM_CENTER_ONE).
+ *   output    V_c = X_c, or X_c^2 under Rician correction;  m_c(p) = (sum_t w V_c[q] + wc V_c[p]) / (sum_t w + wc), the offsets in
+ *             ascending (t0, t1, t2), the centre last;  out_c(p) = m_c(p), or sqrt(max(m_c(p) - 2 sigma2_p, 0)) under Rician correction.
+ *   copies    a voxel whose h2_p is not > 0 (zero, negative, NaN) or that lies outside the mask is copied, out = X; it still serves as a
+ *             neighbour of others.
+ * inr_nlm3d: out, x [n_groups][C][D][H][W] DEVICE; guide [n_groups][D][H][W] DEVICE or null (C must be 1: the guide is x); h2_map
+ * [n_groups][D][H][W] DEVICE or null (the scalar h2 holds everywhere; with a map the scalar is ignored); sigma2 [n_groups][D][H][W] DEVICE
+ * or null (no Rician correction); mask [n_groups][D][H][W] DEVICE bytes or null (all inside).  out must not overlap x or guide.  ONE
+ * launch over n_groups x tiles: a workgroup owns a tile of 256 output voxels (4 x 8 x 8, or 1 x 16 x 16 where s0 + r0 == 0), stages the
+ * guide with a halo of s + r in LDS, and per offset forms the field and its three box sums there (at most 85,056 bytes); the sums of a
+ * voxel stay in registers.  No index depends on a data value: no value, NaN included, leads to an address outside a buffer.
+ * inr_nlm_upsample: y [n][D/f0][H/f1][W/f2], out [n][D][H][W] DEVICE; x0 [n][D][H][W] DEVICE or null (the block replication of y);
+ * guide [n][D][H][W] DEVICE or null (every pass is guided by its own input); k0 [f0], k1 [f1], k2 [f2] HOST, the block operator A of
+ * inr_tvsr3d_block_apply; levels [n_levels] HOST.  From x = x0, for each level h_l and each of n_iter passes:
+ *   x' = NLM(x) with INR_NLM_CENTER_ONE and the scalar h2 = h_l^2;   x <- x' - relax * N(A x' - y),  N the replication over a block:
+ *   with relax = 1, A x = y afterwards up to rounding.  change [n_levels * n_iter][n] DEVICE or null: mean |x_new - x_old| of every pass,
+ * from per-block partials added in a fixed order.  The workspace (DEVICE, 16-byte aligned, the planner's doubles) holds two HR states and
+ * the partials.  No atomics and no host read anywhere: two runs give the same bits, whatever the grid, the stream and a volume's place
+ * in the batch.  The _f32 forms convert on load and round once on the last store.  n_groups == 0 / n_volumes == 0 succeed and launch
+ * nothing.  Refusals, before any device work: INR_E_INVALID for a null out, x or y, a size below 1 or a volume of 2^31 voxels or more,
+ * a radius out of range, C outside 1 .. INR_NLM_MAX_CHANNELS, a null guide with C > 1, a scalar h2 that is not finite and > 0, a center
+ * that is neither constant, out overlapping x or guide, factors outside 1 .. INR_TVSR_MAX_FACTOR, an extent that is no multiple of its
+ * factor, a kernel factor that is not finite or does not sum to 1, n_levels * n_iter outside 0 .. INR_NLM_MAX_PASSES, a level that is not
+ * finite and > 0, relax outside (0, 1]; INR_E_WORKSPACE for a null or short workspace (INR_E_ALIGN: misaligned).  The planner returns 0 for
+ * sizes every call refuses. */
+#define INR_NLM_MAX_SEARCH 5
+#define INR_NLM_MAX_PATCH 2
+#define INR_NLM_MAX_CHANNELS 16
+#define INR_NLM_MAX_PASSES 10000
+#define INR_NLM_CENTER_MAX 0
+#define INR_NLM_CENTER_ONE 1
+int inr_nlm3d(double* out, const double* x, const double* guide, double h2, const double* h2_map, const double* sigma2, const uint8_t* mask,
+              int n_groups, int channels, int depth, int height, int width, int s0, int s1, int s2, int r0, int r1, int r2, int center,
+              void* stream);
+int inr_nlm3d_f32(float* out, const float* x, const float* guide, double h2, const float* h2_map, const float* sigma2, const uint8_t* mask,
+                  int n_groups, int channels, int depth, int height, int width, int s0, int s1, int s2, int r0, int r1, int r2, int center,
+                  void* stream);
+int64_t inr_nlm_upsample_workspace_doubles(int n_volumes, int depth, int height, int width, int f0, int f1, int f2);
+int inr_nlm_upsample(double* out, double* change, const double* y, const double* x0, const double* guide, int n_volumes, int depth, int height,
+                     int width, int f0, int f1, int f2, const double* k0, const double* k1, const double* k2, const double* levels,
+                     int n_levels, int n_iter, double relax, int s0, int s1, int s2, int r0, int r1, int r2, double* workspace,
+                     int64_t workspace_doubles, void* stream);
+int inr_nlm_upsample_f32(float* out, double* change, const float* y, const float* x0, const float* guide, int n_volumes, int depth, int height,
+                         int width, int f0, int f1, int f2, const double* k0, const double* k1, const double* k2, const double* levels,
+                         int n_levels, int n_iter, double relax, int s0, int s1, int s2, int r0, int r1, int r2, double* workspace,
+                         int64_t workspace_doubles, void* stream);
+
 /* ---- second-order TGV super-resolution under the block operator: a prior that does not terrace smooth intensity -------
  * No counterpart in the reference.  Images, sides, factors and the HOST `kernel` as for inr_tvsr_solve2d.  An auxiliary field
  * v = (v0, v1) [n_images][2][H][W] absorbs the smooth part of the gradient (Bredies, Kunisch, Pock 2010; Knoll et al. 2011):

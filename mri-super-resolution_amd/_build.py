@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libinrhip.so")
 SOURCES = ("api.hip", "gemm_f32.hip", "gemm_hp.hip", "kernels.hip", "metrics.hip", "rams.hip", "siren_small.hip",
            "hybrid_fit.hip", "pia.hip", "cssim.hip", "erd_siren.hip", "jet.hip", "wire.hip", "rescale.hip", "wire_deriv.hip",
            "perceptual.hip", "erd_volume.hip", "register.hip", "fourier.hip", "footprint.hip", "tvsr.hip", "tvsr3d.hip", "tvmf.hip",
-           "tvms.hip", "tvop.hip", "tvj.hip", "tgv.hip", "tvadc.hip", "mppca.hip", "degibbs.hip")
+           "tvms.hip", "tvop.hip", "tvj.hip", "tgv.hip", "tvadc.hip", "mppca.hip", "degibbs.hip", "nlm.hip")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # Per-source code-generation flags.  The two GEMM translation units are compiled WITHOUT packed fp32 VALU instructions (v_pk_mul_f32 /
 # v_pk_fma_f32): beside MFMAs they cost the deferred-epilogue GEMM of gemm_hp.hip 3 % (profiles/r04_nt_ab.txt); VALU-bound kernels switch them

@@ -29,6 +29,7 @@ INR_TVMS_MAX_STACKS, INR_TVMS_MAX_TAPS = 8, 16
 INR_TVJ_MAX_CHANNELS = 16
 INR_MPPCA_MAX_RANK, INR_MPPCA_MAX_LONG = 64, 1024
 INR_DEGIBBS_MAX_LINE, INR_DEGIBBS_MAX_SHIFTS, INR_DEGIBBS_MAX_WINDOW, INR_DEGIBBS_CHUNK_DOUBLES = 1024, 64, 8, 1 << 21
+INR_NLM_MAX_SEARCH, INR_NLM_MAX_PATCH, INR_NLM_MAX_CHANNELS, INR_NLM_MAX_PASSES, INR_NLM_CENTER_MAX, INR_NLM_CENTER_ONE = 5, 2, 16, 10000, 0, 1
 
 
 class InrHipError(RuntimeError):
@@ -232,6 +233,13 @@ SIGNATURES = {
     "inr_degibbs_lines_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p, C.c_longlong] + [C.c_int] * 4 + [C.c_void_p, C.c_int64, c_stream]),
     "inr_degibbs2d": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_void_p, C.c_int64, c_stream]),
     "inr_degibbs2d_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p] + [C.c_int] * 6 + [C.c_void_p, C.c_int64, c_stream]),
+    "inr_nlm3d": (C.c_int, [C.c_void_p] * 3 + [C.c_double] + [C.c_void_p] * 3 + [C.c_int] * 12 + [c_stream]),
+    "inr_nlm3d_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, C.c_double, c_f32p, c_f32p, C.c_void_p] + [C.c_int] * 12 + [c_stream]),
+    "inr_nlm_upsample_workspace_doubles": (C.c_int64, [C.c_int] * 7),
+    "inr_nlm_upsample": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 7 + [C.POINTER(C.c_double)] * 4 + [C.c_int, C.c_int, C.c_double] +
+                         [C.c_int] * 6 + [C.c_void_p, C.c_int64, c_stream]),
+    "inr_nlm_upsample_f32": (C.c_int, [c_f32p, C.c_void_p, c_f32p, c_f32p, c_f32p] + [C.c_int] * 7 + [C.POINTER(C.c_double)] * 4 +
+                             [C.c_int, C.c_int, C.c_double] + [C.c_int] * 6 + [C.c_void_p, C.c_int64, c_stream]),
     "inr_tgv_workspace_doubles": (C.c_int64, [C.c_int] * 3),
     "inr_tgv_solve2d": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.POINTER(C.c_double), C.c_double, C.c_double, C.c_double, C.c_int,
                                                                     C.c_void_p, C.c_int64, c_stream]),

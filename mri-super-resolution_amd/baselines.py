@@ -774,6 +774,48 @@ def tv_superres3d(lr, factors, kernel="mean", lam: float = TV3D_DEFAULT_LAMBDA, 
     return _tv_output(as_numpy, lead, out, hr, {"energy": energy, "change": change}, return_info)
 
 
+NLM_DEFAULT_LEVELS = (0.125, 0.0625, 0.03125, 0.015625, 0.0078125)   # Manjon et al. 2010: h = 32 .. 2 on an 8-bit scale, data in [0, 1]
+NLM_DEFAULT_ITERS, NLM_DEFAULT_SEARCH, NLM_DEFAULT_PATCH = 2, 2, 1
+
+
+def nlm_upsample(lr, factors, kernel="mean", levels=NLM_DEFAULT_LEVELS, n_iter: int = NLM_DEFAULT_ITERS, search=NLM_DEFAULT_SEARCH,
+                 patch=NLM_DEFAULT_PATCH, relax: float = 1.0, guide=None, x0=None, return_info: bool = False):
+    """Non-local upsampling (Manjon et al., Medical Image Analysis 2010) of the trailing three axes (slice, row, column) of ``lr`` by
+    ``factors`` = (f0, f1, f2), 1 .. 8 each: from ``x0`` (None: the block replication of ``lr``), for every strength ``h`` of
+    ``levels`` and each of ``n_iter`` passes, a non-local-means filter (search radius ``search``, patch radius ``patch``, an int or a
+    triple; strength ``h^2``, centre weight 1) guided by the current estimate -- or by the fixed ``guide`` (HR shape), e.g. another
+    contrast --, followed by the mean correction ``x <- x' - relax N(A x' - lr)`` under the block operator ``A`` of ``block_apply3d``
+    (``kernel`` 'mean', 'decimate' or a triple of 1-D arrays), ``N`` the replication over a block: with ``relax`` = 1 every pass ends
+    with ``A x = lr``.  The levels suit data in [0, 1].  Leading axes are a batch (``inr_nlm_upsample``).  ndarray in ->
+    float64 ndarray out; device fp32 / fp64 tensor in -> the same out (fp64 inside, rounded once).  There is no CPU fallback.
+    ``return_info``: also a dict with ``change`` [passes, ...leading shape], the mean absolute change of every pass."""
+    who = "nlm_upsample"
+    f, k = _block_kernel3d(who, kernel, factors)
+    s, r = ops.nlm_radii(who, search, patch)
+    lv, n_iter, relax = ops.nlm_schedule(who, levels, n_iter, relax)
+    as_numpy, lo, lead = _volume_input(who, lr)
+    hr = tuple(v * g for v, g in zip(lo, f))
+    ops.nlm_volume(who, hr)
+    for name, value in (("x0", x0), ("guide", guide)):
+        if value is None:
+            continue
+        if isinstance(value, np.ndarray) != as_numpy:
+            raise TypeError(f"{who}: {name} must be given like lr ({'an ndarray' if as_numpy else 'a device tensor'})")
+        _fourier_input(who, value)
+        if tuple(value.shape) != lead + hr or (not as_numpy and value.dtype != lr.dtype):
+            raise ValueError(f"{who}: {name} must have shape {lead + hr} and the type of lr (got {tuple(value.shape)}, {value.dtype})")
+    y = _volume_batch(lr, as_numpy)                                      # the device last
+    start, gd = (None if v is None else _volume_batch(v, as_numpy) for v in (x0, guide))
+    out, change = ops.nlm_upsample(y, f, k, lv, n_iter, s, r, relax, gd, start, want_change=return_info)
+    out = out.reshape(*lead, *hr)
+    if as_numpy:
+        out = out.cpu().numpy()
+    if not return_info:
+        return out
+    change = change.reshape((len(lv) * n_iter,) + lead)
+    return out, {"change": change.cpu().numpy() if as_numpy else change}
+
+
 TVMS_DEFAULT_LAMBDA, TVMS_DEFAULT_HUBER, TVMS_DEFAULT_ITERS = 0.01, 0.01, 300  # the sweep of DESIGN.md 4o (3 stacks, noise 0.02)
 
 

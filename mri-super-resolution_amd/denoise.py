@@ -11,7 +11,10 @@ components are noise, and the voxel is projected onto the others.  The noise map
 removal by local sub-voxel shifts (Kellner et al., MRM 2016) on the HIP kernels of csrc/degibbs.hip (``inr_degibbs2d``,
 ``inr_degibbs_lines``).  An MR image is a truncated Fourier series, so every edge rings with a period of one acquired
 pixel; MP-PCA cannot remove that, it is signal.  The data must lie on the acquired grid -- scanner-interpolated or partial-Fourier data
-ring at another period and are not served -- and the 3-D variant is out of scope.  There is no CPU fallback."""
+ring at another period and are not served -- and the 3-D variant is out of scope.
+
+``nlm`` is the non-local-means filter in its MRI form (Rician bias correction, a noise level per voxel) on the HIP kernel of csrc/nlm.hip
+(``inr_nlm3d``): the consumer of the noise map that ``mppca`` returns.  There is no CPU fallback."""
 from __future__ import annotations
 
 import numpy as np
@@ -155,6 +158,118 @@ def degibbs_lines(x, axis=-1, nshifts=DEGIBBS_DEFAULT_SHIFTS, window=DEGIBBS_DEF
         return out
     shift = ops.degibbs_shift(choice, nshifts).reshape(moved.shape).movedim(-1, ax).contiguous()
     return out, {"shift": shift.cpu().numpy() if as_numpy else shift}
+
+
+def _nlm_like(who, name, value, shape):
+    """``value`` (an ndarray or a tensor) as a tensor, refused by name unless it has ``shape``."""
+    if isinstance(value, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(value, dtype=np.float64))
+    elif isinstance(value, torch.Tensor):
+        t = value
+    else:
+        raise TypeError(f"{who}: {name} must be an ndarray or a tensor (got {type(value).__name__})")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{who}: {name} has shape {tuple(t.shape)}, expected {tuple(shape)}")
+    return t
+
+
+def nlm(data, sigma, beta=1.0, search=3, patch=1, guide=None, rician=False, mask=None, center="max"):
+    """Non-local-means denoising (Buades et al. 2005; for MRI Wiest-Daessle et al. 2008, Manjon et al. 2008) on the HIP kernel of
+    csrc/nlm.hip (``inr_nlm3d``).  The trailing three axes of ``data`` are the volume (a 2-D input is one image, D = 1),
+    leading axes a batch.  ``data``: an ndarray (any real dtype; float64 inside and out) or a device tensor (float32 or float64,
+    returned as given).  ``sigma``: the noise level, a number or an array of the volume's shape -- ``mppca(..., return_info=True)``
+    returns one; the strength is ``h2 = 2 beta sigma^2`` per voxel, and a voxel whose strength is not > 0 passes through.  ``search``
+    / ``patch``: the radii of the search box (0 .. 5) and of the patch (0 .. 2), an int or a triple over the volume's axes.  ``guide``:
+    None (each volume guides itself), 'mean' (the mean over the leading axes guides all of them: one group of at most 16 channels that
+    share their weights -- the measurements of one acquisition) or an array of the volume's shape.  ``rician``: average the squares
+    and remove the bias ``2 sigma^2`` (magnitude data).  ``mask``: the volume's shape, non-zero inside; outside it the data pass
+    through.  ``center``: 'max' (the centre voxel weighs as much as its best neighbour) or 'one'.  There is no CPU fallback."""
+    who = "nlm"
+    as_numpy = _degibbs_input(who, data)
+    if data.ndim < 2:
+        raise ValueError(f"{who}: data needs at least 2 axes (got shape {tuple(data.shape)})")
+    image = data.ndim == 2
+    given = tuple(int(v) for v in (data.shape if image else data.shape[-3:]))      # the volume as the caller sees it
+    volume = (1,) + given if image else given
+    lead = () if image else tuple(int(v) for v in data.shape[:-3])
+    s, r = ops.nlm_radii(who, search, patch)                                         # host-only refusals come before the device
+    if image:
+        if (isinstance(search, (tuple, list)) and s[0]) or (isinstance(patch, (tuple, list)) and r[0]):
+            raise ValueError(f"{who}: an image has no first axis to search (got search {search!r}, patch {patch!r})")
+        s, r = (0,) + s[1:], (0,) + r[1:]
+    ops.nlm_center(who, center)
+    ops.nlm_volume(who, volume)
+    beta = float(beta)
+    if not (np.isfinite(beta) and beta > 0.0):
+        raise ValueError(f"{who}: beta must be finite and > 0 (got {beta!r})")
+    if sigma is None:
+        raise ValueError(f"{who}: sigma is required: a number or an array of the volume's shape {given}")
+    sigma_map = None
+    if isinstance(sigma, (np.ndarray, torch.Tensor)) and sigma.ndim > 0:
+        sigma_map = _nlm_like(who, "sigma", sigma, given)
+    else:
+        try:
+            sigma = float(sigma)
+        except (TypeError, ValueError):
+            raise TypeError(f"{who}: sigma must be a number, an ndarray or a tensor (got {type(sigma).__name__})") from None
+        if not (np.isfinite(sigma) and sigma > 0.0):
+            raise ValueError(f"{who}: a scalar sigma must be finite and > 0 (got {sigma!r})")
+    n = int(np.prod(lead, dtype=np.int64)) if lead else 1
+    shared = guide is not None
+    if isinstance(guide, str):
+        if guide != "mean":
+            raise ValueError(f"{who}: guide must be None, 'mean' or an array of the volume's shape (got {guide!r})")
+        if n > ops._lib.INR_NLM_MAX_CHANNELS:
+            raise ValueError(f"{who}: guide='mean' filters the leading axes as one group of at most {ops._lib.INR_NLM_MAX_CHANNELS} channels "
+                             f"(got {n}): split them")
+    elif guide is not None:
+        guide = _nlm_like(who, "guide", guide, given)
+    if mask is not None:
+        mask = _nlm_like(who, "mask", mask, given)
+    device = ops.require_gpu() if as_numpy else data.device
+    x = torch.from_numpy(np.array(data, dtype=np.float64, order="C")).to(device) if as_numpy else data
+    x = x.reshape((n,) + volume).contiguous()
+    dtype = x.dtype
+
+    def per_group(t, groups):
+        return None if t is None else t.to(device=device, dtype=dtype).reshape((1,) + volume).expand((groups,) + volume).contiguous()
+
+    if sigma_map is not None:
+        sg = sigma_map.to(device=device, dtype=torch.float64)
+        h2_one, s2_one = (2.0 * beta) * sg * sg, sg * sg
+    else:
+        h2_one = None
+        s2_one = torch.full(volume, sigma * sigma, dtype=torch.float64, device=device) if rician else None
+    if not rician:
+        s2_one = None
+    m_one = None if mask is None else (mask.to(device) != 0).reshape((1,) + volume)
+    if isinstance(guide, str):
+        g_one = x.mean(dim=0)
+    else:
+        g_one = guide
+
+    def run(xs, groups, chans, gd):
+        h2 = per_group(h2_one, groups) if h2_one is not None else 2.0 * beta * sigma * sigma
+        mk = None if m_one is None else m_one.expand((groups,) + volume).contiguous().view(torch.uint8)
+        return ops.nlm3d(xs.reshape((groups, chans) + volume), h2, s, r, gd, per_group(s2_one, groups), mk, center)
+
+    if not shared:
+        out = run(x, n, 1, None)
+    else:
+        gd = per_group(g_one, 1)
+        step = ops._lib.INR_NLM_MAX_CHANNELS
+        out = torch.cat([run(x[i:i + step], 1, min(step, n - i), gd).reshape((-1,) + volume) for i in range(0, n, step)]) if n else x.clone()
+    out = out.reshape(lead + given)
+    return out.cpu().numpy() if as_numpy else out
+
+
+def nlm_stack(stack, sigma, beta=1.0, search=3, patch=1, rician=False):
+    """``nlm`` of a measurement-major ndarray stack [M, X, Y, Z] under the noise map ``sigma`` (that of ``mppca``), in groups of at most
+    16 measurements in the stack's order, each group guided by its mean -- what ``scripts/denoise --method nlm`` and ``superresDWI
+    --denoise nlm`` run."""
+    step = ops._lib.INR_NLM_MAX_CHANNELS
+    return np.concatenate([nlm(stack[i:i + step], sigma, beta, search, patch, guide="mean", rician=rician)
+                           for i in range(0, stack.shape[0], step)], axis=0)
 
 
 def _cell_rows(cell):

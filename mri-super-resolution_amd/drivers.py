@@ -941,10 +941,20 @@ def david_study(case, rule: int = 1, slices="cancer"):
 THROUGH_PLANE_METHODS = ("replicate", "spline", "zerofill", "tv3d")
 
 
+NLM_STARTS = ("replicate", "spline")
+
+
 def check_through_plane(factor=2, profile="mean", fwhm=None, tv_lambda=3e-3, tv_huber=0.1, tv_iters=300, tv_gz=1.0, with_inr=False,
-                        footprint="point", number_of_epochs=2500):
+                        footprint="point", number_of_epochs=2500, with_nlm=False, nlm_start="replicate", nlm_iters=2, nlm_search=2,
+                        nlm_patch=1):
     """What ``through_plane_study`` cannot serve, by name; touches neither the input nor the device."""
     who = "through_plane_study"
+    if with_nlm:
+        from . import baselines
+        if nlm_start not in NLM_STARTS:
+            raise ValueError(f"{who}: nlm_start must be 'replicate' or 'spline' (got {nlm_start!r})")
+        ops.nlm_radii(who, nlm_search, nlm_patch)
+        ops.nlm_schedule(who, baselines.NLM_DEFAULT_LEVELS, nlm_iters, 1.0)
     if int(factor) != factor or not 2 <= factor <= ops.TVSR_MAX_FACTOR:
         raise ValueError(f"{who}: factor is the number of thin slices per thick one, 2 .. {ops.TVSR_MAX_FACTOR} (got {factor!r})")
     if profile not in ("mean", "gaussian"):
@@ -967,7 +977,8 @@ def check_through_plane(factor=2, profile="mean", fwhm=None, tv_lambda=3e-3, tv_
 
 
 def through_plane_study(volume, factor=2, profile="mean", fwhm=None, tv_lambda=None, tv_huber=None, tv_iters=None, tv_gz=1.0,
-                        with_inr=False, footprint="point", number_of_epochs=2500, seed=0):
+                        with_inr=False, footprint="point", number_of_epochs=2500, seed=0, with_nlm=False, nlm_start="replicate",
+                        nlm_iters=None, nlm_search=None, nlm_patch=None):
     """``volume`` [X, Y, Z, B] (or [X, Y, Z]) in [0, 1], thin slices along Z: the thick slices ``block_apply3d(HR, (factor, 1, 1),
     profile)`` of Z trimmed to a multiple of ``factor``, and their reconstructions on the thin slices, all on the device:
     ``replicate`` (every thick slice ``factor`` times), ``spline`` (``baselines.resize_z``, the cubic spline along z of
@@ -977,13 +988,20 @@ def through_plane_study(volume, factor=2, profile="mean", fwhm=None, tv_lambda=N
     (``upscale_axes=1, lr_model='average'``, ``footprint`` 'point' -> None or 'box'), for factor 2 and the mean profile only.
     Returns ``{"volumes", "psnr", "ssim", "consistency", "kernel"}``: fp32 device stacks [Z, B, X, Y] (``hr``, ``thick`` [Z /
     factor, ...] and the methods), PSNR (data range 1) and SSIM by the reference protocol [Z, B] per method, and the PSNR of
-    ``A tv3d`` against the thick slices."""
+    ``A tv3d`` against the thick slices.  ``with_nlm``: also ``nlm``, ``baselines.nlm_upsample`` with the profile in its mean
+    correction, ``NLM_DEFAULT_LEVELS`` and ``nlm_iters`` passes per level (the ``NLM_DEFAULT_*`` where an argument is None), from the
+    replication (``nlm_start='replicate'``) or from the spline above after one mean correction (``'spline'``); the result gains
+    ``nlm_consistency``, the PSNR of ``A nlm`` against the thick slices."""
     from . import baselines
 
     lam = baselines.TV3D_DEFAULT_LAMBDA if tv_lambda is None else tv_lambda
     huber = baselines.TV3D_DEFAULT_HUBER if tv_huber is None else tv_huber
     iters = baselines.TV3D_DEFAULT_ITERS if tv_iters is None else tv_iters
-    check_through_plane(factor, profile, fwhm, lam, huber, iters, tv_gz, with_inr, footprint, number_of_epochs)
+    n_iters = baselines.NLM_DEFAULT_ITERS if nlm_iters is None else nlm_iters
+    n_search = baselines.NLM_DEFAULT_SEARCH if nlm_search is None else nlm_search
+    n_patch = baselines.NLM_DEFAULT_PATCH if nlm_patch is None else nlm_patch
+    check_through_plane(factor, profile, fwhm, lam, huber, iters, tv_gz, with_inr, footprint, number_of_epochs, with_nlm, nlm_start,
+                        n_iters, n_search, n_patch)
     vol = np.asarray(volume)
     if vol.ndim == 3:
         vol = vol[..., None]
@@ -1004,6 +1022,14 @@ def through_plane_study(volume, factor=2, profile="mean", fwhm=None, tv_lambda=N
              "zerofill": baselines.fourier_resample(thick, Z, axis=1, align="center", boundary="mirror").clamp_min(0),
              "tv3d": baselines.tv_superres3d(thick, f, kernel, lam, huber, int(iters), (float(tv_gz), 1.0, 1.0))}
     consistency = float(metrics.psnr(thick, baselines.block_apply3d(recon["tv3d"], f, kernel), 1.0))
+    extra = {}
+    if with_nlm:
+        start = None
+        if nlm_start == "spline":                                     # one mean correction: A start = thick
+            residual = baselines.block_apply3d(recon["spline"], f, kernel) - thick
+            start = (recon["spline"] - residual.repeat_interleave(factor, dim=1)).contiguous()
+        recon["nlm"] = baselines.nlm_upsample(thick, f, kernel, baselines.NLM_DEFAULT_LEVELS, int(n_iters), n_search, n_patch, x0=start)
+        extra["nlm_consistency"] = float(metrics.psnr(thick, baselines.block_apply3d(recon["nlm"], f, kernel), 1.0))
     info = {}
     if with_inr:
         zfirst = np.ascontiguousarray(np.moveaxis(vol, 2, 0))                                                      # [Z, X, Y, B]
@@ -1024,7 +1050,7 @@ def through_plane_study(volume, factor=2, profile="mean", fwhm=None, tv_lambda=N
         psnr[name] = float(metrics.psnr(hs, volumes[name], 1.0))
         ssim[name] = metrics.ssim_reference_protocol(safe(hs), safe(volumes[name])).cpu().numpy()
     return {"volumes": volumes, "psnr": psnr, "ssim": ssim, "consistency": consistency, "kernel": kernel, "valid": ok.cpu().numpy(),
-            "info": info}
+            "info": info, **extra}
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -1231,6 +1231,137 @@ def degibbs_shift(choice: torch.Tensor, nshifts: int) -> torch.Tensor:
     return torch.where(c <= nshifts, c, nshifts - c) / (2.0 * nshifts)
 
 
+# ---- non-local means on volumes and non-local upsampling (include/inrhip.h) ----------------------------------------------
+NLM_CENTERS = {"max": _lib.INR_NLM_CENTER_MAX, "one": _lib.INR_NLM_CENTER_ONE}
+
+
+def _nlm_triple(who, name, value, most):
+    try:
+        raw = (value,) * 3 if isinstance(value, (int, np.integer)) and not isinstance(value, bool) else tuple(value)
+        t = tuple(int(v) for v in raw)
+        ok = len(t) == 3 and all(int(v) == v and not isinstance(v, bool) for v in raw)
+    except (TypeError, ValueError):
+        t, ok = (), False
+    if not ok or not all(0 <= v <= most for v in t):
+        raise ValueError(f"{who}: {name} must be an int or a triple of ints 0 .. {most} (got {value!r})")
+    return t
+
+
+def nlm_radii(who, search, patch):
+    """The search radii (s0, s1, s2), 0 .. 5 each, and the patch radii (r0, r1, r2), 0 .. 2 each, from an int or a triple; refuses, by
+    name, what ``inr_nlm3d`` would refuse."""
+    return _nlm_triple(who, "search", search, _lib.INR_NLM_MAX_SEARCH), _nlm_triple(who, "patch", patch, _lib.INR_NLM_MAX_PATCH)
+
+
+def nlm_center(who, center):
+    if center not in NLM_CENTERS:
+        raise ValueError(f"{who}: center must be 'max' or 'one' (got {center!r})")
+    return NLM_CENTERS[center]
+
+
+def nlm_strength(who, h2):
+    """A scalar strength ``h2`` as a float: finite and > 0."""
+    try:
+        v = float(h2)
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: h2 must be a number or a device map (got {h2!r})") from None
+    if not (np.isfinite(v) and v > 0.0):
+        raise ValueError(f"{who}: a scalar h2 must be finite and > 0 (got {h2!r})")
+    return v
+
+
+def nlm_channels(who, channels):
+    if not 1 <= channels <= _lib.INR_NLM_MAX_CHANNELS:
+        raise ValueError(f"{who}: channels must be 1 .. {_lib.INR_NLM_MAX_CHANNELS} (got {channels})")
+    return channels
+
+
+def nlm_volume(who, shape):
+    """A volume (D, H, W): every side at least 1, fewer than 2^31 voxels."""
+    if len(shape) != 3 or any(s < 1 for s in shape) or shape[0] * shape[1] * shape[2] >= 1 << 31:
+        raise ValueError(f"{who}: volumes of at least 1 sample per axis and fewer than 2^31 voxels (got {' x '.join(str(s) for s in shape)})")
+
+
+def nlm_schedule(who, levels, n_iter, relax):
+    """(the levels as floats, n_iter, relax): every level finite and > 0, ``len(levels) * n_iter`` in 0 .. 10,000, relax in (0, 1]."""
+    try:
+        lv = [float(v) for v in levels]
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: levels must be a sequence of numbers (got {levels!r})") from None
+    if not all(np.isfinite(v) and v > 0.0 and v * v > 0.0 for v in lv):
+        raise ValueError(f"{who}: every level must be finite and > 0 (got {levels!r})")
+    if isinstance(n_iter, bool) or int(n_iter) != n_iter or int(n_iter) < 0 or len(lv) * int(n_iter) > _lib.INR_NLM_MAX_PASSES:
+        raise ValueError(f"{who}: n_iter must be an integer >= 0 with len(levels) * n_iter <= {_lib.INR_NLM_MAX_PASSES} "
+                         f"(got {len(lv)} levels, n_iter = {n_iter!r})")
+    relax = float(relax)
+    if not 0.0 < relax <= 1.0:
+        raise ValueError(f"{who}: relax must lie in (0, 1] (got {relax!r})")
+    return lv, int(n_iter), relax
+
+
+def nlm3d(x: torch.Tensor, h2, search=3, patch=1, guide=None, sigma2=None, mask=None, center="max"):
+    """``inr_nlm3d`` / ``_f32`` by the dtype of ``x`` [G, C, D, H, W] on the current stream: returns out like ``x``.  ``h2``: a number
+    (finite, > 0) or a device map [G, D, H, W] of that dtype; ``guide`` [G, D, H, W] of that dtype or None (C must be 1: ``x`` guides
+    itself); ``sigma2`` [G, D, H, W] of that dtype or None (None: no Rician correction); ``mask`` [G, D, H, W] uint8 / bool or None;
+    ``search`` / ``patch``: an int or a triple; ``center``: 'max' or 'one'."""
+    who = "nlm3d"
+    s, r = nlm_radii(who, search, patch)
+    c = nlm_center(who, center)
+    h2_map = h2 if isinstance(h2, torch.Tensor) else None
+    h2 = 0.0 if h2_map is not None else nlm_strength(who, h2)
+    _chk_batch(x, "x", 5, "[G, C, D, H, W]", (torch.float32, torch.float64), dtype_first=True)
+    G, Cn, D, H, W = x.shape
+    nlm_channels(who, Cn)
+    nlm_volume(who, (D, H, W))
+    if guide is None and Cn != 1:
+        raise ValueError(f"{who}: without a guide x must have one channel (got {Cn}): the guide is x itself")
+    for name, t in (("guide", guide), ("h2", h2_map), ("sigma2", sigma2)):
+        if t is not None:
+            _chk_batch(t, name, 4, "[G, D, H, W]", (x.dtype,), (G, D, H, W))
+    if mask is not None:
+        _chk_batch(mask, "mask", 4, "[G, D, H, W]", (torch.uint8, torch.bool), (G, D, H, W))
+        mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask
+    out = torch.empty_like(x)
+    if G == 0:
+        return out
+    entry = "inr_nlm3d" if x.dtype == torch.float64 else "inr_nlm3d_f32"
+    check(getattr(lib(), entry)(out.data_ptr(), x.data_ptr(), _ptr(guide), h2, _ptr(h2_map), _ptr(sigma2), _ptr(mask), G, Cn, D, H, W, *s, *r,
+                                c, _stream()), entry)
+    return out
+
+
+def nlm_upsample_workspace_doubles(n: int, D: int, H: int, W: int, factors) -> int:
+    """``inr_nlm_upsample_workspace_doubles``; 0 for sizes ``inr_nlm_upsample`` refuses."""
+    f0, f1, f2 = (int(v) for v in factors)
+    return int(lib().inr_nlm_upsample_workspace_doubles(int(n), int(D), int(H), int(W), f0, f1, f2))
+
+
+def nlm_upsample(y: torch.Tensor, factors, kernel, levels, n_iter: int = 2, search=2, patch=1, relax: float = 1.0, guide=None, x0=None,
+                 workspace=None, want_change=True):
+    """``inr_nlm_upsample`` / ``_f32`` by the dtype of ``y`` [n, d, h, w]: returns (x [n, f0 d, f1 h, f2 w] of that dtype, change
+    [len(levels) * n_iter, n] float64 or None).  ``kernel``: (k0, k1, k2) host values; ``levels``: the strengths h_l, one NLM pass uses
+    h2 = h_l^2; ``guide`` and ``x0`` [n, f0 d, f1 h, f2 w] share the dtype; ``workspace``: a float64 tensor."""
+    who = "nlm_upsample"
+    f, k = _block_kernel3d(who, kernel, factors)
+    s, r = nlm_radii(who, search, patch)
+    lv, n_iter, relax = nlm_schedule(who, levels, n_iter, relax)
+    _chk_volumes(y, "y", (torch.float32, torch.float64))
+    n, d, h, w = y.shape
+    D, H, W = d * f[0], h * f[1], w * f[2]
+    nlm_volume(who, (D, H, W))
+    for name, t in (("guide", guide), ("x0", x0)):
+        if t is not None:
+            _chk_volumes(t, name, (y.dtype,), (n, D, H, W))
+    out = torch.empty((n, D, H, W), dtype=y.dtype, device=y.device)
+    change = torch.zeros((len(lv) * n_iter, n), dtype=torch.float64, device=y.device) if want_change else None
+    if n:
+        entry = "inr_nlm_upsample" if y.dtype == torch.float64 else "inr_nlm_upsample_f32"
+        ws = _f64_workspace(workspace, nlm_upsample_workspace_doubles(n, D, H, W, f), y.device)
+        check(getattr(lib(), entry)(out.data_ptr(), _ptr(change), y.data_ptr(), _ptr(x0), _ptr(guide), n, D, H, W, *f, *k, _doubles(lv),
+                                    len(lv), n_iter, relax, *s, *r, ws.data_ptr(), ws.numel(), _stream()), entry)
+    return out, change
+
+
 # ---- second-order TGV under the block operator (include/inrhip.h, DESIGN.md 4r) --------------------------------------------------------
 def tgv_workspace_doubles(n: int, H: int, W: int) -> int:
     """``inr_tgv_workspace_doubles``; 0 for sizes ``inr_tgv_solve2d`` refuses."""

@@ -14,6 +14,7 @@ SSIM_ZEROFILL_HEADER = 'Pt_id, b-value, slice, SSIM-zerofill, SSIM-SR\n'     # s
 SSIM_TV_HEADER = 'Pt_id, b-value, slice, SSIM-tv, SSIM-SR\n'                 # superresDWI --tv_baseline: the same rows, the TV / Huber baseline
 SSIM_TV_JOINT_HEADER = 'Pt_id, b-value, slice, SSIM-tv-joint, SSIM-SR\n'     # superresDWI --tv_joint: the same rows, the channel-coupled solver
 SSIM_TV_TGV_HEADER = 'Pt_id, b-value, slice, SSIM-tv-tgv, SSIM-SR\n'         # superresDWI --tv_tgv: the same rows, the second-order TGV solver
+SSIM_NLM_HEADER = 'Pt_id, b-value, slice, SSIM-nlm, SSIM-SR\n'               # superresDWI --nlm_baseline: the same rows, the non-local upsampling
 SSIM_TV_ADC_HEADER = 'Pt_id, b-value, slice, SSIM-tv-adc, SSIM-SR\n'         # superresDWI --tv_adc: the same rows, the images of the S0 / ADC model
 THROUGH_PLANE_COLUMNS =('SSIM-replicate', 'SSIM-spline', 'SSIM-zerofill', 'SSIM-tv3d')   # scripts/through_plane: then SSIM-SR with --with_inr
 CONTRAST_HEADER = 'seed,patient,direction,image,metric,performance\n'

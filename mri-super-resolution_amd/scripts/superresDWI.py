@@ -73,6 +73,11 @@ Two optional products of the same fit (default off, so a plain run writes exactl
     ``--tv_iters``.  ``ssim_scores_tv_tgv.csv`` (``Pt_id, b-value, slice, SSIM-tv-tgv, SSIM-SR``); ``metrics.json`` gains
     ``psnr_tv_tgv_db``, ``ssim_tv_tgv_mean`` and ``tv_tgv_consistency_psnr_db``; with ``--adc``, ``adc.mat`` gains ``adc_tv_tgv``.
     Refused before the input is loaded: without ``--tv_baseline``, LG < 0, R <= 0.
+  * ``--nlm_baseline [--nlm_iters N --nlm_search S --nlm_patch P]``: the non-local upsampling of Manjon et al. 2010
+    (``baselines.nlm_upsample``) of the same LR stack, every b-value's [Z, R/2, R/2] volume by the factors (1, 2, 2) under
+    the forward model of ``--lr_model``: ``ssim_scores_nlm.csv``, ``psnr_nlm_db`` / ``ssim_nlm_mean`` / ``nlm_consistency_psnr_db`` in
+    ``metrics.json``, ``adc_nlm`` in ``adc.mat`` with ``--adc``.  Refused before the input is loaded: an odd ROI side, radii out of range.
+    ``--denoise nlm`` filters the raw stack by ``denoise.nlm_stack`` under MP-PCA's noise map and records the keys of ``--denoise mppca``.
   * ``--denoise mppca [--denoise_window a b c]``: MP-PCA denoising (``denoise.mppca``, ``inr_mppca_denoise``) of the raw
     stack before the per-cell normalisation of ``load_input_and_scale`` -- for ``hybrid_raw`` every acquisition of every [b][TE] cell is
     a measurement (``denoise.stack_hybrid``), for a plain volume the b axis is; the window's sides are over (X, Y, Z), default 5 5 5,
@@ -108,7 +113,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(os.path.dirname(_HERE)))
 import mri_super_resolution_amd as inr  # noqa: E402
-from mri_super_resolution_amd import baselines, drivers, matio, metrics, reports, wire  # noqa: E402
+from mri_super_resolution_amd import baselines, drivers, matio, metrics, ops, reports, wire  # noqa: E402
 from mri_super_resolution_amd import denoise as denoise_mod  # noqa: E402
 from mri_super_resolution_amd import footprint as footprint_mod  # noqa: E402
 
@@ -173,6 +178,13 @@ def build_parser():
                    help="--tv_tgv: weight of the first-order term (default from the sweep of DESIGN.md 4r)")
     p.add_argument("--tv_tgv_ratio", type=float, default=baselines.TGV_DEFAULT_RATIO,
                    help="--tv_tgv: second-order weight / first-order weight, > 0")
+    p.add_argument("--nlm_baseline", action="store_true",
+                   help="also score the non-local upsampling of the LR ROI (baselines.nlm_upsample on the [B, Z, R/2, R/2] volumes, "
+                        "factors (1, 2, 2), the forward model of --lr_model): ssim_scores_nlm.csv, psnr_nlm_db / ssim_nlm_mean / "
+                        "nlm_consistency_psnr_db in metrics.json, adc_nlm with --adc")
+    p.add_argument("--nlm_iters", type=int, default=baselines.NLM_DEFAULT_ITERS, help="--nlm_baseline: passes per level")
+    p.add_argument("--nlm_search", type=int, default=baselines.NLM_DEFAULT_SEARCH, help="--nlm_baseline: search radius, 0 .. 5")
+    p.add_argument("--nlm_patch", type=int, default=baselines.NLM_DEFAULT_PATCH, help="--nlm_baseline: patch radius, 0 .. 2")
     p.add_argument("--derivative_maps", action="store_true",
                    help="also write derivatives.mat: gradient magnitude and Laplacian of the fitted network on recon's grid, "
                         "along the spatial axes (nn_mri.py:205-221)")
@@ -191,9 +203,10 @@ def build_parser():
                         "of the network over its 2 x 2 HR pixels")
     p.add_argument("--footprint_samples", type=int, default=2,
                    help="--footprint box: midpoint nodes per in-plane axis (2 = the discrete block mean on the HR grid; at most 8)")
-    p.add_argument("--denoise", choices=("none", "mppca"), default="none",
+    p.add_argument("--denoise", choices=("none", "mppca", "nlm"), default="none",
                    help="denoise the raw stack before the per-cell normalisation: MP-PCA over the acquisitions of hybrid_raw (or the b "
-                        "axis of a plain volume); metrics.json gains denoise, denoise_window and denoise_sigma_median")
+                        "axis of a plain volume), or (nlm) non-local means of the raw stack under MP-PCA's noise map; metrics.json "
+                        "gains denoise, denoise_window and denoise_sigma_median")
     p.add_argument("--denoise_window", type=int, nargs=3, default=list(denoise_mod.DEFAULT_WINDOW), metavar=("A", "B", "C"),
                    help="--denoise mppca: odd window sides over (X, Y, Z), each at most its axis")
     p.add_argument("--degibbs", action="store_true",
@@ -239,6 +252,8 @@ def load_input_and_scale(path, key=None, refuse_acquisitions=None, denoise=None,
         if denoise is not None:
             clean, info = denoise_mod.mppca(denoise_mod.stack_hybrid(raw), denoise["window"], estimator=denoise.get("estimator", "exp2"),
                                             return_info=True)
+            if denoise.get("method") == "nlm":                          # the projection is discarded, the noise map kept
+                clean = denoise_mod.nlm_stack(denoise_mod.stack_hybrid(raw), info["sigma"])
             raw = denoise_mod.unstack_hybrid(clean, raw)
             denoise["sigma_median"] = float(np.median(info["sigma"]))
         if degibbs is not None:
@@ -255,8 +270,11 @@ def load_input_and_scale(path, key=None, refuse_acquisitions=None, denoise=None,
     if vol.ndim == 3:
         vol = vol[..., None]
     if denoise is not None:
+        noisy = vol
         vol, info = denoise_mod.mppca(vol, denoise["window"], estimator=denoise.get("estimator", "exp2"), return_info=True,
                                       measurement_axis=-1)
+        if denoise.get("method") == "nlm":
+            vol = np.ascontiguousarray(np.moveaxis(denoise_mod.nlm_stack(np.ascontiguousarray(np.moveaxis(noisy, -1, 0)), info["sigma"]), 0, -1))
         denoise["sigma_median"] = float(np.median(info["sigma"]))
     if degibbs is not None:
         vol, info = denoise_mod.degibbs(vol, (0, 1), degibbs.get("nshifts", denoise_mod.DEGIBBS_DEFAULT_SHIFTS), return_info=True)
@@ -278,8 +296,10 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     # (the footprint flags are refused for every caller of this function: another driver's ``check_model`` replaces ``_check_model``)
     refuse_acquisitions = _check_footprint(args, external_fit=fit is not None)
     _check_tv(args, fit)
+    _check_nlm(args, fit)
     refuse_acquisitions = (check_model or _check_model)(args) or refuse_acquisitions
-    denoise = {"window": tuple(args.denoise_window)} if getattr(args, "denoise", "none") == "mppca" else None
+    denoise = ({"window": tuple(args.denoise_window), "method": args.denoise} if getattr(args, "denoise", "none") in ("mppca", "nlm")
+               else None)
     degibbs = {} if getattr(args, "degibbs", False) else None
     mean_img, acq, bvalues, maxes, signal_scale = load_input_and_scale(path, args.key, refuse_acquisitions, denoise, degibbs)
     r0, r1 = args.roi_start, args.roi_end
@@ -360,6 +380,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
     tvj = _tv_joint(ls, args, average) if getattr(args, "tv_joint", False) else None
     tgv = _tv_tgv(ls, args, average) if getattr(args, "tv_tgv", False) else None
     tva = _tv_adc(ls, args, average, bvalues, signal_scale) if getattr(args, "tv_adc", False) else None
+    nlm = _nlm_baseline(ls, args, average) if getattr(args, "nlm_baseline", False) else None
     with reports.SsimCsv(os.path.join(out_dir, "ssim_scores.csv")) as csv:
         for _slice in range(nz):
             for b in range(nb):
@@ -419,12 +440,21 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         summary["psnr_tv_adc_db"] = float(metrics.psnr(hs, tva["images"], 1.0))
         summary["ssim_tv_adc_mean"] = float(ssim_tva[okn].mean())
         summary["tv_adc_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(tva["images"], (2, 2), _tv_kernel(average)), 1.0))
+    if nlm is not None:
+        ssim_nlm = metrics.ssim_reference_protocol(safe(hs), safe(nlm)).cpu().numpy()
+        with reports.SsimCsv(os.path.join(out_dir, "ssim_scores_nlm.csv"), reports.SSIM_NLM_HEADER) as csv:
+            for _slice in range(nz):
+                for b in range(nb):
+                    csv.row(pt_id, bvalues[b] if b < len(bvalues) else b, _slice, float(ssim_nlm[_slice, b]), float(ssim_sr[_slice, b]))
+        summary["psnr_nlm_db"] = float(metrics.psnr(hs, nlm, 1.0))
+        summary["ssim_nlm_mean"] = float(ssim_nlm[okn].mean())
+        summary["nlm_consistency_psnr_db"] = float(metrics.psnr(ls, baselines.block_apply(nlm, (2, 2), _tv_kernel(average)), 1.0))
     if average:
         pred = inr.footprint_forward(INR, coords, B, footprint)
         summary.update({"lr_model": "average", "footprint": args.footprint, "footprint_samples": footprint.count,
                         "lr_consistency_psnr_db": float(metrics.psnr(target.reshape(1, -1), pred.reshape(1, -1), 1.0))})
     if denoise is not None:
-        summary.update({"denoise": "mppca", "denoise_window": list(denoise["window"]), "denoise_sigma_median": denoise["sigma_median"]})
+        summary.update({"denoise": denoise["method"], "denoise_window": list(denoise["window"]), "denoise_sigma_median": denoise["sigma_median"]})
     if degibbs is not None:
         summary.update({"degibbs": True, "degibbs_mean_abs_shift": degibbs["mean_abs_shift"]})
     summary.update(fit_summary)
@@ -433,7 +463,7 @@ def run_patient(path, pt_id, args, check_model=None, fit=None):
         matio.savemat(os.path.join(out_dir, "coronal.mat"), coronal)
         np.save(os.path.join(out_dir, "coronal.npy"), coronal["coronal_sr"])
     if args.adc:
-        adc_vars = _adc_maps(recon, hs, bvalues, signal_scale, args.zerofill_apodize if zf is not None else None, ls, tv, tvj, tgv)
+        adc_vars = _adc_maps(recon, hs, bvalues, signal_scale, args.zerofill_apodize if zf is not None else None, ls, tv, tvj, tgv, nlm)
         if tva is not None:                                                         # [Z, R, R] -> [R, R, Z], the layout of the other maps
             adc_vars["adc_tv_adc"] = tva["adc"].permute(1, 2, 0).contiguous().cpu().numpy()
             adc_vars["s0_tv_adc"] = (tva["s0"] * tva["unit"]).permute(1, 2, 0).contiguous().cpu().numpy()
@@ -615,6 +645,29 @@ def _tv_adc(ls, args, average, bvalues, signal_scale):
     return {"s0": s0, "adc": adc, "images": images.contiguous(), "unit": unit}
 
 
+def _nlm_baseline(ls, args, average):
+    """``--nlm_baseline``: the [Z, B, R/2, R/2] LR stack ``ls`` -> the [Z, B, R, R] non-local upsampling: every b-value's [Z, R/2, R/2]
+    volume by the factors (1, 2, 2) under the LR model's operator."""
+    k = [1.0, 0.0] if not average else [0.5, 0.5]
+    out = baselines.nlm_upsample(ls.permute(1, 0, 2, 3).contiguous(), (1, 2, 2), ([1.0], k, k), baselines.NLM_DEFAULT_LEVELS, args.nlm_iters,
+                                 args.nlm_search, args.nlm_patch)
+    return out.permute(1, 0, 2, 3).contiguous()
+
+
+def _check_nlm(args, fit=None):
+    """``--nlm_baseline``: what it cannot serve, before the input is loaded and anything touches the device."""
+    if not getattr(args, "nlm_baseline", False):
+        return
+    if (args.roi_end - args.roi_start) % 2:
+        raise ValueError(f"--nlm_baseline solves for 2 x 2 HR pixels per LR pixel and needs an even ROI side (got "
+                         f"{args.roi_end - args.roi_start})")
+    ops.nlm_radii("--nlm_baseline", args.nlm_search, args.nlm_patch)
+    ops.nlm_schedule("--nlm_baseline", baselines.NLM_DEFAULT_LEVELS, args.nlm_iters, 1.0)
+    if fit is not None and getattr(fit, "changes_lr_data", False):
+        raise ValueError("--nlm_baseline solves on the LR ROI this driver forms: not with a fit hook that changes the LR data "
+                         "(changes_lr_data)")
+
+
 def _check_tv(args, fit=None):
     """``--tv_baseline`` / ``--tv_joint`` / ``--tv_tgv`` / ``--tv_adc``: what they cannot serve, before the input is loaded and anything touches the
     device."""
@@ -657,13 +710,13 @@ def _check_tv(args, fit=None):
                          "(changes_lr_data)")
 
 
-def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, tv=None, tvj=None, tgv=None):
+def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, tv=None, tvj=None, tgv=None, nlm=None):
     """superresDWI.py:189-206 for all slices in one batch: every b-image times maxes[b, 1], then calculate_ADC per pixel, of
     the x2 SR volume, the x4 spline of the LR ROI and the x2 spline of the HR ROI.  ``hs`` is the HR ROI as [Z, B, R, R].
     ``zerofill_apodize`` (not None): also ``adc_zerofill``, the x4 zero-fill of the LR ROI, on the grid of ``adc_spline``.
     ``ls``: the LR ROI as [Z, B, R/2, R/2] (default: every second pixel of ``hs``; ``--lr_model average``: the block means).
     ``tv`` / ``tvj`` / ``tgv`` (not None): also ``adc_tv`` / ``adc_tv_joint`` / ``adc_tv_tgv`` of the [Z, B, R, R] TV / TGV
-    reconstructions, on the grid of the HR ROI."""
+    reconstructions, on the grid of the HR ROI; ``nlm`` (not None): also ``adc_nlm`` of the non-local upsampling, on that grid."""
     scale = torch.as_tensor(np.asarray(signal_scale, np.float32), device=recon.device)
     to_xyzb = lambda t: t.permute(2, 3, 0, 1).contiguous()                       # [Z, B, 2R, 2R] -> [2R, 2R, Z, B]
     stacks = {"adc_sr": recon,
@@ -677,6 +730,8 @@ def _adc_maps(recon, hs, bvalues, signal_scale, zerofill_apodize=None, ls=None, 
         stacks["adc_tv_joint"] = to_xyzb(tvj)
     if tgv is not None:
         stacks["adc_tv_tgv"] = to_xyzb(tgv)
+    if nlm is not None:
+        stacks["adc_nlm"] = to_xyzb(nlm)
     out ={k: metrics.calculate_ADC_device(bvalues, (v * scale).contiguous()).cpu().numpy() for k, v in stacks.items()}
     out["b"] = np.asarray(bvalues, np.float64)
     return out

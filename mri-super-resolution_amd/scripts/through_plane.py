@@ -13,11 +13,15 @@ the thin slices' centres) and reconstructs the thin slices on the device by
               ``--tv_gz`` the weight of the slice direction's differences: in-plane spacing / slice spacing);
   SR          with ``--with_inr``: ``drivers.fit_volume`` as it is on the z-first volume (``upscale_axes=1, lr_model='average'``,
               ``--footprint point|box``) -- for ``--factor 2 --profile mean`` only, the one forward model that fit has.
+  nlm         with ``--with_nlm``: ``baselines.nlm_upsample`` (non-local upsampling): non-local-means passes at falling
+              strengths, each followed by the mean correction under the profile; ``--nlm_start replicate|spline`` (the spline after
+              one mean correction), ``--nlm_iters`` passes per level, ``--nlm_search`` / ``--nlm_patch`` the radii.
 
 Per patient, under ``<output_address>/pat<id>/``: ``through_plane.csv`` (one row per slice and b-value: ``Pt_id, b-value, slice,
 SSIM-replicate, SSIM-spline, SSIM-zerofill, SSIM-tv3d[, SSIM-SR]``, SSIM by the reference protocol), ``metrics.json``
 (``psnr_<method>_db``, ``ssim_<method>_mean``, ``tv3d_consistency_psnr_db``: ``A tv3d`` against the thick slices) and
-``through_plane.mat`` (the volumes, [X, Y, Z, B]).  Every flag is checked before the input is loaded; a volume that makes fewer than 4
+``through_plane.mat`` (the volumes, [X, Y, Z, B]).  ``--with_nlm`` adds the column ``SSIM-nlm``, ``psnr_nlm_db``, ``ssim_nlm_mean``,
+``nlm_consistency_psnr_db``, the ``nlm_*`` settings and the volume ``nlm``; without it every output is what it was.  Every flag is checked before the input is loaded; a volume that makes fewer than 4
 thick slices is refused (the cubic spline needs 4 samples)."""
 from __future__ import annotations
 
@@ -55,13 +59,20 @@ def build_parser():
                         "network over its two thin slices")
     p.add_argument("--number_of_epochs", type=int, default=2500, help="--with_inr: steps of the fit")
     p.add_argument("--seed", type=int, default=0, help="--with_inr: seeds the Fourier matrix and the weights")
+    p.add_argument("--with_nlm", action="store_true", help="also the non-local upsampling of baselines.nlm_upsample (method nlm)")
+    p.add_argument("--nlm_start", choices=drivers.NLM_STARTS, default="replicate",
+                   help="--with_nlm: start from the replication, or from the spline after one mean correction")
+    p.add_argument("--nlm_iters", type=int, default=baselines.NLM_DEFAULT_ITERS, help="--with_nlm: passes per level")
+    p.add_argument("--nlm_search", type=int, default=baselines.NLM_DEFAULT_SEARCH, help="--with_nlm: search radius, 0 .. 5")
+    p.add_argument("--nlm_patch", type=int, default=baselines.NLM_DEFAULT_PATCH, help="--with_nlm: patch radius, 0 .. 2")
     return p
 
 
 def check_args(args):
     """Every refusal of the flags, before the input is loaded and anything touches the device."""
     drivers.check_through_plane(args.factor, args.profile, args.fwhm, args.tv_lambda, args.tv_huber, args.tv_iters, args.tv_gz,
-                                args.with_inr, args.footprint, args.number_of_epochs)
+                                args.with_inr, args.footprint, args.number_of_epochs, args.with_nlm, args.nlm_start, args.nlm_iters,
+                                args.nlm_search, args.nlm_patch)
     if args.roi_start < 0 or args.roi_end - args.roi_start < 7:
         raise ValueError(f"ROI {args.roi_start}:{args.roi_end}: SSIM needs >= 7 x 7 pixels")
 
@@ -75,9 +86,10 @@ def run_patient(path, pt_id, args):
     out_dir = os.path.join(args.output_address, f"pat{pt_id}")
     os.makedirs(out_dir, exist_ok=True)
     res = drivers.through_plane_study(mean_img[r0:r1, r0:r1], args.factor, args.profile, args.fwhm, args.tv_lambda, args.tv_huber,
-                                      args.tv_iters, args.tv_gz, args.with_inr, args.footprint, args.number_of_epochs, args.seed)
-    methods = list(drivers.THROUGH_PLANE_METHODS) + (["sr"] if args.with_inr else [])
-    columns = list(reports.THROUGH_PLANE_COLUMNS) + (["SSIM-SR"] if args.with_inr else [])
+                                      args.tv_iters, args.tv_gz, args.with_inr, args.footprint, args.number_of_epochs, args.seed,
+                                      args.with_nlm, args.nlm_start, args.nlm_iters, args.nlm_search, args.nlm_patch)
+    methods = list(drivers.THROUGH_PLANE_METHODS) + (["sr"] if args.with_inr else []) + (["nlm"] if args.with_nlm else [])
+    columns = list(reports.THROUGH_PLANE_COLUMNS) + (["SSIM-SR"] if args.with_inr else []) + (["SSIM-nlm"] if args.with_nlm else [])
     nz, nb = res["ssim"]["tv3d"].shape
     with open(os.path.join(out_dir, "through_plane.csv"), "w") as fh:
         fh.write(", ".join(["Pt_id", "b-value", "slice"] + columns) + "\n")
@@ -93,6 +105,10 @@ def run_patient(path, pt_id, args):
         summary[f"ssim_{m}_mean"] = float(res["ssim"][m][res["valid"]].mean())
         if m == "tv3d":
             summary["tv3d_consistency_psnr_db"] = res["consistency"]
+        if m == "nlm":
+            summary["nlm_consistency_psnr_db"] = res["nlm_consistency"]
+            summary.update({"nlm_start": args.nlm_start, "nlm_iters": int(args.nlm_iters), "nlm_search": int(args.nlm_search),
+                            "nlm_patch": int(args.nlm_patch)})
     summary.update(res["info"])
     to_xyzb = lambda t: t.permute(2, 3, 0, 1).contiguous().cpu().numpy()                       # [Z, B, X, Y] -> [X, Y, Z, B]
     mat = {name: to_xyzb(v) for name, v in res["volumes"].items()}
